@@ -17,11 +17,12 @@ apart on the street grid of one fixed world of walls and clutter, every feature 
 descriptor-BUILD path (rsx_sc_add_points) -- so consecutive keyframes overlap, streets are revisited in
 both directions and the descriptors are as dense and as similar to each other as a real sequence's.
 Queries: 8192 new scans, half of them revisits of a driven place (arbitrary heading), half places the
-drive never saw.  Nothing is planted at descriptor level; correctness of what was timed is checked
+drive never saw.  Nothing is planted at descriptor level; correctness of what was timed is checked (--full)
 against the CPU oracle on >= 256 queries of the timed batch (`oracle_checked_queries`).
 
-Besides `value` (that workload through the default path: fp16 MFMA lower-bound filter -> exact fp64
-re-scoring of the survivors) the line carries
+A plain run measures `value` alone (that workload through the default path: fp16 MFMA lower-bound filter -> exact fp64
+re-scoring of the survivors; `roofline` and the per-query counters come from the same timed steps).  With --full the
+line also carries what the secondary legs measure and check:
   data_dependence   the same batch shape on (a) the round-1 descriptor-level random DB with planted rotated
                     copies, (b) the drive with continuous landmark heights (non-binary descriptors, oracle-checked) and
                     (c) the exact-all path (filter off: every pair scored in fp64) = the data-independent floor, each with
@@ -36,8 +37,12 @@ re-scoring of the survivors) the line carries
   latency_q1_n1k_us BASELINE configs[1]; orora / cen2019 / icp / frontend: the other parts of the path
   odometry_e2e      BASELINE configs[0] and [2]: the file-based odometry entry end to end on a moving sensor with known poses
                     (scans/s resident / from host memory / from PNG files, PNG decode separately, checked against the oracle chain)
+(--full --no-cpu-baseline: without cpu_baseline and the oracle checks; --full --only-main: the headline and cpu_baseline.)
 With --gpus G the DB is sharded block-cyclically over G ranks (same DB, same batch => strong scaling); a
 query batch is two stages with one RCCL all-gather of per-rank top-k lists each (sharded.py).
+
+--dump-outputs DIR writes the records of the last timed step (dist.npy, index.npy, shift.npy: queries x top-k, float64);
+the inputs are generated from fixed seeds, so two builds can be compared output for output.
 
 RSX_BENCH_LOCAL_BACKEND=module:function (tests only) replaces the GPU shard by a CPU stand-in and RCCL by
 gloo so that the launcher / timing / reduction logic can be driven at world 2 without GPUs
@@ -1217,6 +1222,15 @@ class LegGuard:
             timer.cancel()
 
 
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the records the timed path handed back in its last step (queries x top-k), one float64 .npy per
+    field (index and shift are small integers: exact in float64); 8192 x 10 records = 2 MB in all"""
+    os.makedirs(out_dir, exist_ok=True)
+    res = np.asarray(res)
+    for name in res.dtype.names:
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(res[name], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1225,8 +1239,14 @@ def main():
     ap.add_argument("--db", type=int, default=10000, help="keyframes in the (global) DB")
     ap.add_argument("--queries", type=int, default=8192, help="queries per step")
     ap.add_argument("--topk", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--only-main", action="store_true", help="time only the headline workload (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every secondary leg (other layouts, data dependence, host entry, latency, "
+                         "orora / cen2019 / icp / frontend / odometry, all-pairs, SLAM stream) and the CPU baseline + oracle "
+                         "check; off (default): the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the records of the last timed step (dist / index / shift, float64) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline + oracle check")
+    ap.add_argument("--only-main", action="store_true", help="--full without the secondary legs (profiling runs)")
     ap.add_argument("--data", choices=["trajectory", "random"], default="trajectory",
                     help="headline DB: descriptors built from a synthetic drive (default) or the round-1 random descriptors")
     ap.add_argument("--filter-kind", choices=["auto", "direct", "spectral", "spectral2"], default="auto",
@@ -1300,6 +1320,10 @@ def main():
 
     dt, per_rank, (launches, kern_ms), (evals, cands) = main_wl.timed(args.steps, args.warmup, profile=True, settle_steps=96)
     res = main_wl.results()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+    secondary_legs = args.full and not args.only_main
+    cpu_baseline = args.full and not args.no_cpu_baseline
     failures = []
     if args.data != "trajectory" or ctx.stub:
         ok = r_src < n_elig
@@ -1350,7 +1374,7 @@ def main():
     guard = LegGuard(ctx, out, failures, json_fd)
 
     # ---- every layout of this world (query groups x DB shards), same DB, same batch ------------------
-    if world > 1 and not args.only_main:
+    if world > 1 and secondary_legs:
         fill = db_descs if db_descs is not None else descs
         lay = {}
         st_l = max(3, args.steps // 4)
@@ -1397,7 +1421,7 @@ def main():
                                   "exchange_ms_per_step_per_rank = device time inside the collectives (waiting for the slowest peer included)")
 
     # ---- data dependence: the random DB and the exact-all floor, same batch shape --------------
-    if not ctx.stub and not args.only_main:
+    if not ctx.stub and secondary_legs:
         dd = {}
 
         def leg_random_db():
@@ -1439,7 +1463,7 @@ def main():
             dd["trajectory_continuous_z"] = {"queries_per_sec": nq * st_c / dtc, "ms_per_step": dtc / st_c * 1e3,
                                              "exact_evals_per_query": evc / (nq * st_c), "previewed_candidates_per_query": cdc / (nq * st_c),
                                              "workload": f"scancontext_exhaustive_top{k}_q{nq}_db{n_db}_trajectory_z_uniform(-1,4)"}
-            if rank == 0 and not args.no_cpu_baseline:
+            if rank == 0 and cpu_baseline:
                 from oracle import pyoracle as po
                 om = po.Manager()
                 for i in range(n_db):
@@ -1510,7 +1534,7 @@ def main():
         guard.run("scale_100k", leg_100k)
 
     if rank == 0 and not ctx.stub:
-        if not args.only_main and world == 1:
+        if secondary_legs and world == 1:
             out["host_entry"] = host_entry_leg(main_wl.mgr, q_descs, n_elig, k, out["ms_per_step"])
             if not out["host_entry"]["pinned_identical_to_pageable"]:
                 failures.append("host-buffer entry: pinned and pageable buffers give different records")
@@ -1519,7 +1543,7 @@ def main():
             out["layout_emulation"] = layout_emulation_leg(ctx.local_rank, db_descs, q_descs, n_elig, k, res=res)
             if out["layout_emulation"]["filter_shard_records_identical"] is False:
                 failures.append("layout emulation: the filter-shard layout's records differ from the unsharded ones")
-        if not args.only_main:
+        if secondary_legs:
             # BASELINE configs[1]: 1 query vs 1k-keyframe DB (latency of the synchronous host call)
             small = scancontext.SCManager(device=ctx.local_rank)
             small.add_descriptors_f32(main_wl.mgr.export_descriptors_f32(0, min(1000, main_wl.mgr.local_size)))
@@ -1538,7 +1562,7 @@ def main():
             for nm in ("n200000", "n400000"):
                 if not out["latency_q1"][nm]["first_4_queries_identical_to_exact_all"]:
                     failures.append(f"latency_q1 {nm}: the single-query path and the exact-all path disagree")
-            out["orora"] = orora_leg(ctx.local_rank, args.no_cpu_baseline)
+            out["orora"] = orora_leg(ctx.local_rank, not cpu_baseline)
             sel = out["orora"]["with_max_clique_selection"]
             if sel.get("selection_identical_to_oracle") is False or sel.get("max_abs_pose_diff_vs_oracle", 0.0) > 1e-4:
                 failures.append("orora: the max-clique selection (or the solver behind it) differs from the oracle")
@@ -1546,7 +1570,7 @@ def main():
             out["icp"] = icp_leg(ctx.local_rank)
             out["loop_verify"] = loop_verify_leg(ctx.local_rank)
             out["frontend"] = frontend_leg(ctx.local_rank)
-            out["odometry_e2e"] = odometry_e2e_leg(ctx.local_rank, args.no_cpu_baseline)
+            out["odometry_e2e"] = odometry_e2e_leg(ctx.local_rank, not cpu_baseline)
             oe = out["odometry_e2e"]
             if not oe["identical_resident_vs_host"] or oe.get("counts_identical_to_oracle") is False or oe.get("max_abs_pose_diff_vs_oracle", 0.0) > 1e-4:
                 failures.append("odometry_e2e: pipeline differs from the oracle chain / between its two entries")
@@ -1555,14 +1579,14 @@ def main():
             out["allpairs_100k"] = allpairs_leg(ctx.local_rank)
             if not out["allpairs_100k"]["planted_revisits_recovered"]:
                 failures.append("all-pairs: planted revisits not recovered")
-            if db_pts is not None and not args.no_cpu_baseline:
+            if db_pts is not None and cpu_baseline:
                 out["slam_stream"] = slam_stream_leg(ctx.local_rank, db_pts, db_off)
                 ss = out["slam_stream"]
                 if ss["candidate_mode_identical_to_oracle"] != ss["queries"] or ss["exhaustive_mode_identical_to_oracle"] != ss["queries"]:
                     failures.append("streaming SLAM emulation differs from the oracle")
                 if ss.get("cpp_host") and ss["cpp_host"].get("detections_identical_to_python_harness") is False:
                     failures.append("streaming SLAM emulation: the C++ host's detections differ from the Python harness's")
-        if not args.no_cpu_baseline:
+        if cpu_baseline:
             if db_pts is None:
                 raise SystemExit("cpu_baseline needs --data trajectory (the oracle rebuilds the DB from the clouds)")
             base, chk = cpu_baseline_and_check(db_pts, db_off, q_descs, n_elig, k, res)

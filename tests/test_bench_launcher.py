@@ -8,12 +8,13 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(gpus, extra_env=None):
+def _run(gpus, extra_env=None, args=("--full",)):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -21,7 +22,7 @@ def _run(gpus, extra_env=None):
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     env.update(extra_env or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-           "--db", "150", "--queries", "4", "--topk", "3", "--no-cpu-baseline"]
+           "--db", "150", "--queries", "4", "--topk", "3", "--no-cpu-baseline", *args]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p, lines
@@ -58,7 +59,7 @@ def test_headline_is_the_db_shard_layout_for_a_large_batch_too():
     env["RSX_BENCH_LOCAL_BACKEND"] = "tests.bench_stub:make"
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--db", "80", "--queries", "1024",
-           "--topk", "2", "--no-cpu-baseline"]
+           "--topk", "2", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -119,3 +120,24 @@ def test_a_secondary_layout_that_wedges_is_cut_at_its_deadline():
     out = json.loads(lines[0])
     assert out["value"] > 0 and out["cut_short"] is True and out["n_gpus"] == 2
     assert any("layout 2x1" in m and "no result after 5 s" in m for m in out["secondary_failures"])
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_run_is_the_headline_alone_and_dumps_its_records(gpus, tmp_path):
+    """Without --full the run times the headline and nothing else; --dump-outputs writes the last timed step's records
+    (float64, one file per field) from inputs that are the same in every run."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p, lines = _run(gpus, args=("--dump-outputs", str(d)))
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len(lines) == 1, (p.stdout, p.stderr[-2000:])
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["n_gpus"] == gpus and out["failures"] == []
+        assert out["value"] == pytest.approx(4 / (out["ms_per_step"] * 1e-3), rel=1e-6)
+        assert "layouts" not in out and "cpu_baseline" not in out
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("dist", "index", "shift")})
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float64 and a.shape == (4, 3), (n, a.dtype, a.shape)
+        assert np.array_equal(a, dumps[1][n]), n
+    assert np.all(dumps[0]["index"] >= 0) and np.all(np.diff(dumps[0]["dist"], axis=1) >= 0)

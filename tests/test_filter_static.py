@@ -24,13 +24,15 @@ def test_no_instruction_touches_inflight_lds_destinations(kind):
 def _kernel_resources(src, extra=()):
     """(vgpr_count, vgpr_spill_count, scratch bytes) per kernel name fragment, from the ISA metadata hipcc emits for gfx950"""
     import re
+    import tempfile
     csrc = os.path.join(ROOT, "navtech-radar-slam_amd", "csrc")
-    out = os.path.join("/tmp", f"rsx_static_{os.path.basename(src)}.s")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-           "-fhip-fp32-correctly-rounded-divide-sqrt", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, *extra, "-x", "hip",
-           "--cuda-device-only", "-S", os.path.join(csrc, src), "-o", out]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=900)
-    text = open(out).read()
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, f"rsx_static_{os.path.basename(src)}.s")
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
+               "-fhip-fp32-correctly-rounded-divide-sqrt", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, *extra, "-x", "hip",
+               "--cuda-device-only", "-S", os.path.join(csrc, src), "-o", out]
+        subprocess.run(cmd, check=True, capture_output=True, timeout=900)
+        text = open(out).read()
     res = {}
     for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", text):
         res[m.group(1)] = (int(m.group(3)), int(m.group(4)), int(m.group(2)))

@@ -1,7 +1,9 @@
 """The ROS-facing packaging of the boundary (SURVEY 8b "ORORA package surface" / "build surface"): the `orora`
 package with run_orora.launch that the reference's top-level launch file includes, and the sc_pgo CMakeLists with
 the USE_RSX switch.  ROS is absent here, so: the launch/CMake files are checked against the reference's own launch
-graph, and the orora package is configured and built with plain CMake (its non-catkin path)."""
+graph (tests/golden/ros_reference.json: what the reference's top-level launch file and SC-A-LOAM CMakeLists.txt declare),
+and the orora package is configured and built with plain CMake (its non-catkin path)."""
+import json
 import os
 import re
 import shutil
@@ -12,7 +14,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROS = os.path.join(ROOT, "navtech-radar-slam_amd", "ros")
-REF_TOP = "/root/reference/launch/navtech_radar_slam_mulran.launch"
+with open(os.path.join(ROOT, "tests", "golden", "ros_reference.json")) as _f:
+    REF = json.load(_f)
 
 
 def test_run_orora_launch_matches_the_reference_include():
@@ -25,10 +28,10 @@ def test_run_orora_launch_matches_the_reference_include():
     assert pkg.find("name").text == "orora"
     cm = open(os.path.join(ROS, "orora", "CMakeLists.txt")).read()
     assert f"add_executable({node.get('type')} " in cm and "RSX_WITH_ROS" in cm
-    if os.path.exists(REF_TOP):  # the reference includes $(find orora)/launch/run_orora.launch with exactly these args
-        inc = ET.parse(REF_TOP).getroot().find("include")
-        assert inc.get("file") == "$(find orora)/launch/run_orora.launch"
-        assert {a.get("name") for a in inc.findall("arg")} <= args
+    # the reference includes $(find orora)/launch/run_orora.launch with exactly these args
+    inc = REF["top_launch_include"]
+    assert inc["file"] == "$(find orora)/launch/run_orora.launch"
+    assert set(inc["args"]) <= args
     src = open(os.path.join(ROOT, "navtech-radar-slam_amd", "host", "odometry.cpp")).read()
     assert '"/orora/odom"' in src and '"/orora/cloud_local"' in src    # sc_pgo.launch:6-7 remaps these two
 
@@ -39,12 +42,10 @@ def test_sc_pgo_cmake_keeps_the_reference_target_and_adds_use_rsx():
     assert "add_executable(alaserPGO src/laserPosegraphOptimization.cpp)" in cm                      # shim build
     assert "add_executable(alaserPGO src/laserPosegraphOptimization.cpp include/scancontext/Scancontext.cpp)" in cm
     assert re.search(r"include_directories\(BEFORE[^)]*navtech-radar-slam_amd/host", cm)
-    if os.path.exists("/root/reference/pgo/SC-A-LOAM/CMakeLists.txt"):
-        ref = open("/root/reference/pgo/SC-A-LOAM/CMakeLists.txt").read()
-        for comp in re.search(r"find_package\(catkin REQUIRED COMPONENTS(.*?)\)", ref, re.S).group(1).split():
-            assert comp in cm, comp                                                               # same catkin components
-        for pkg in ("PCL", "OpenCV", "OpenMP", "GTSAM"):
-            assert f"find_package({pkg} REQUIRED" in cm
+    for comp in REF["sc_pgo_catkin_components"]:
+        assert comp in cm, comp                                                                   # same catkin components
+    for pkg in ("PCL", "OpenCV", "OpenMP", "GTSAM"):
+        assert f"find_package({pkg} REQUIRED" in cm
 
 
 @pytest.mark.skipif(shutil.which("cmake") is None, reason="cmake not installed")

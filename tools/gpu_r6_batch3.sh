@@ -1,10 +1,11 @@
 set -u
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-(timeout 1200 python bench.py > gpurun_out/bench_full.json 2> gpurun_out/bench_full.err); echo "bench rc=$?"; tail -c 300 gpurun_out/bench_full.err
+R=$(realpath -m "${R:-results}"); export R; mkdir -p "$R"   # the --full bench line lands here (override: R=<dir>)
+(timeout 1200 python bench.py --full > $R/bench_full.json 2> $R/bench_full.err); echo "bench rc=$?"; tail -c 300 $R/bench_full.err
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/bench_full.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.environ["R"] + "/bench_full.json").read().strip().splitlines()[-1])
 print({k: d[k] for k in ("value", "ms_per_step", "failures") if k in d})
 print("roofline", {k: d["roofline"][k] for k in ("frac", "avg_launch_ms")})
 print("secondary", d["config"].get("secondary"))
