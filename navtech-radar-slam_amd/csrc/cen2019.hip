@@ -1338,8 +1338,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT <= 512 ? 
 //   pass 2a               marks (flag reads), mark bits to HBM
 //   pass 2b               closed runs: the three scans chunk by chunk, chunks without a mark skipped
 // Same records, same mark bits as cen_runs, which stays for single scans and rows wider than 4096 bins (tests/test_gpu_cen2019.py:
-// batches through this kernel, single scans and test_wide_rows through the block form) and for A / B runs (RSX_CEN_FORMS=block,
-// experiments build).
+// batches through this kernel, single scans and test_wide_rows through the block form).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int RW_WAVES = 4;             // wavefronts (= azimuths) per workgroup
 constexpr int RW_CH = 8;                // chunks of 512 bins: rows of <= 4096 bins
@@ -1721,18 +1720,16 @@ void launch_chain(rsx_cen2019 *h, const uint8_t *d_imgs, int64_t img_stride, int
     hipLaunchKernelGGL((cen_stats<C, NT, 1>), dim3((unsigned)rows, (unsigned)nb), dim3(NT), 0, s, d_imgs, img_stride, rows, cols, stride, off, sc, h->hist.as<unsigned>());
   hipLaunchKernelGGL(cen_scalars, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, s, sc, nb, (int64_t)rows * cols);
   const int hrpb = rpb > 1 ? HIST_ROWS : 1;
-  // (experiments build: RSX_CEN_FORMS=block runs the workgroup-per-azimuth forms of cen_hist AND cen_runs in a batch too -- the two go
-  // together: cen_runs_wave reads the per-thread records only cen_hist_wave writes, cen_runs the per-wavefront maxima of cen_hist)
-  static const bool hist_block_form = [] { const char *e = rsx::exp_env("RSX_CEN_FORMS"); return e && e[0] == 'b'; }();
-  bool hist_done = false;
+  // a batch: a wavefront per azimuth in cen_hist AND cen_runs (the two forms go together: cen_runs_wave reads the per-thread records
+  // only cen_hist_wave writes, cen_runs the per-wavefront maxima of cen_hist); single scans and rows over 4096 bins: the block forms
+  bool wave_forms = false;
+  if constexpr (C == 8 && NT == 64 * HW_CH && NT == 64 * RW_CH) wave_forms = rpb > 1;
   if constexpr (C == 8 && NT == 64 * HW_CH) {
-    if (!hist_block_form && rpb > 1) {  // a batch: a wavefront per azimuth
+    if (wave_forms)
       hipLaunchKernelGGL(cen_hist_wave, dim3((unsigned)((rows + HW_WAVES - 1) / HW_WAVES), (unsigned)nb), dim3(64 * HW_WAVES), 0, s, d_imgs, img_stride,
                          rows, cols, stride, off, sc, h->hist.as<unsigned>(), h->opener.as<OpRec<C>>(), h->negmax.as<unsigned short>());
-      hist_done = true;
-    }
   }
-  if (!hist_done)
+  if (!wave_forms)
     hipLaunchKernelGGL((cen_hist<C, NT>), dim3((unsigned)((rows + hrpb - 1) / hrpb), (unsigned)nb), dim3(NT), 0, s, d_imgs, img_stride, rows, cols,
                        stride, off, sc, h->hist.as<unsigned>(), h->opener.as<OpRec<C>>(), h->wavemax.as<unsigned>(), hrpb);
   hipLaunchKernelGGL(cen_pick, dim3((unsigned)nb), dim3(256), 0, s, sc, h->hist.as<unsigned>(), p.max_points);
@@ -1741,15 +1738,13 @@ void launch_chain(rsx_cen2019 *h, const uint8_t *d_imgs, int64_t img_stride, int
   hipLaunchKernelGGL(cen_resolve, dim3((unsigned)nb), dim3(1024), 0, s, sc, h->list.as<unsigned long long>(), (int64_t)rows * cols, rows, cols,
                      p.max_points);
   const int rrpb = rpb > 1 ? RUNS_ROWS : 1;
-  const bool block_form = !hist_done;  // (the form cen_hist took)
   if constexpr (C == 8 && NT == 64 * RW_CH) {
-    if (!block_form && rpb > 1) {  // a batch: a wavefront per azimuth (cen_runs_wave; a single scan's 400 wavefronts would walk their rows one chunk after the other: 17 us against 7)
+    if (wave_forms)  // (a single scan's 400 wavefronts would walk their rows one chunk after the other: 17 us against 7)
       hipLaunchKernelGGL(cen_runs_wave, dim3((unsigned)((rows + RW_WAVES - 1) / RW_WAVES), (unsigned)nb), dim3(64 * RW_WAVES), 0, s, d_imgs, img_stride,
                          rows, cols, stride, off, sc, p.min_range, row_cap, h->row_runs.as<uint2>(), h->row_nruns.as<unsigned>(),
                          h->markbits.as<MarkT<C>>(), h->negmax.as<unsigned short>());
-    }
   }
-  if (!(C == 8 && NT == 64 * RW_CH) || block_form || rpb <= 1)
+  if (!wave_forms)
     hipLaunchKernelGGL((cen_runs<C, NT>), dim3((unsigned)((rows + rrpb - 1) / rrpb), (unsigned)nb), dim3(NT), 0, s, d_imgs, img_stride, rows, cols,
                        stride, off, sc, p.min_range, row_cap, h->row_runs.as<uint2>(), h->row_nruns.as<unsigned>(),
                        h->markbits.as<MarkT<C>>(), h->wavemax.as<unsigned>(), rrpb);
@@ -1791,15 +1786,10 @@ int extract_device(rsx_cen2019 *h, const uint8_t *d_imgs, int64_t img_stride, in
     // <= 4096 bins: 512 threads x 8 bins (about 100 VGPRs: four waves per SIMD; 256 x 16 needs 176: two); wider rows: 1024 x 16
     // (a Navtech CIR row has 3360 bins = 420 threads.  448 threads -- no eighth wave that executes the row passes with all
     // lanes off -- measured SLOWER: 54.2 k against 57.4 k scans/s batched, seven waves do not spread evenly over four SIMDs;
-    // 256 threads x 16 bins: 43 k.  tools/ab_cen.py, experiments build.  The timing exits that took cen_hist apart for DESIGN.md
+    // 256 threads x 16 bins: 43 k ("Where round 4 points").  The timing exits that took cen_hist apart for DESIGN.md
     // -- `if (dbg & 1) return;` in front of its barriers -- made the 1024-thread instantiation sum garbage even with dbg = 0
     // (tests/test_gpu_cen2019.py::test_wide_rows caught it) and are gone again.)
-    static const int cfg = [] { const char *e = rsx::exp_env("RSX_CEN_CFG"); return e ? atoi(e) : 0; }();
-    if (cfg == 1 && cols <= 16 * 256)
-      launch_chain<16, 256>(h, im, img_stride, n, stride, off, p, azp, az_stride, resolution, max_targets, tg, pxy, cn, row_cap, s);
-    else if (cfg == 2 && cols <= 8 * 448)
-      launch_chain<8, 448>(h, im, img_stride, n, stride, off, p, azp, az_stride, resolution, max_targets, tg, pxy, cn, row_cap, s);
-    else if (cols <= 8 * 512)
+    if (cols <= 8 * 512)
       launch_chain<8, 512>(h, im, img_stride, n, stride, off, p, azp, az_stride, resolution, max_targets, tg, pxy, cn, row_cap, s);
     else
       launch_chain<16, 1024>(h, im, img_stride, n, stride, off, p, azp, az_stride, resolution, max_targets, tg, pxy, cn, row_cap, s);

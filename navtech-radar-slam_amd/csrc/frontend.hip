@@ -551,76 +551,15 @@ __global__ __launch_bounds__(256) void fe_compact_valid(const uint8_t *__restric
   if (threadIdx.x == 0) vcount[blockIdx.x] = run;
 }
 
-// knnMatch(2) + ratio between CONSECUTIVE scans of a batch: blockIdx.y = pair j (slots first + j and first + j + 1 of the
-// [slot][stride] arrays), blockIdx.z = direction: 0 queries = slot A against train = slot B -> fwd[j][i], 1 the reverse
-// -> bwd[j][i].  Queries and train descriptors are taken from the compacted lists of valid keypoints (ascending index, so
-// "the first minimum wins" is the scan order of fe_match / BFMatcher); invalid queries get -1.
-// FOUR LANES PER QUERY: a block of 256 threads takes 64 queries, lane part p scans entries p, p + 4, ... of every train
-// tile and the four partial (d1, i1, d2) are merged under the order of the sequential scan (smaller distance, then the
-// smaller train index) -- a lone thread per query scanning 800 descriptors left most of the chip idle.
-constexpr int FM_Q = 64;  // queries per block
-__global__ __launch_bounds__(256) void fe_match_consecutive(const uint32_t *__restrict__ descs, const uint8_t *__restrict__ valids,
-                                                            const int32_t *__restrict__ counts, int stride, int first,
-                                                            const int32_t *__restrict__ vidx, const int32_t *__restrict__ vcount, float ratio,
-                                                            int32_t *__restrict__ fwd, int32_t *__restrict__ bwd) {
-  __shared__ uint32_t st[256 * 8];
-  __shared__ int32_t si[256];
-  const int j = blockIdx.y, dir = blockIdx.z;
-  const int qs = j + dir, ts = j + 1 - dir;  // slots relative to `first`
-  const int nq = counts[first + qs] < stride ? counts[first + qs] : stride;
-  const uint32_t *q = descs + (int64_t)(first + qs) * stride * 8, *t = descs + (int64_t)(first + ts) * stride * 8;
-  const int32_t *qi = vidx + (int64_t)qs * stride, *ti = vidx + (int64_t)ts * stride;
-  int32_t *out_idx = (dir ? bwd : fwd) + (int64_t)j * stride;
-  // keypoints without a descriptor match nothing: block b clears the invalid ones among keypoints [256 b, 256 b + 256)
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < nq; i += gridDim.x * 256)
-    if (!valids[(int64_t)(first + qs) * stride + i]) out_idx[i] = -1;
-  const int nqv = vcount[qs], ntv = vcount[ts];
-  for (int q0 = blockIdx.x * FM_Q; q0 < nqv; q0 += gridDim.x * FM_Q) {  // (uniform per block)
-    const int jq = q0 + (threadIdx.x >> 2), part = threadIdx.x & 3;
-    const bool live = jq < nqv;
-    const int iq = live ? qi[jq] : 0;
-    uint32_t me[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) me[w] = live ? q[(int64_t)iq * 8 + w] : 0u;
-    // the two smallest (distance, train index) pairs as ONE number each, distance << 20 | index (distances <= 256, indices
-    // below `stride` <= 2^20): "smaller distance, then the smaller train index" is the numbers' order, the second smallest
-    // number carries the second smallest distance (a tie of two entries counts twice, as in the sequential scan), and an
-    // update is min / max / min instead of two compares and five selects
-    uint32_t k1 = 0xffffffffu, k2 = 0xffffffffu;
-    for (int j0 = 0; j0 < ntv; j0 += 256) {
-      __syncthreads();
-      const int jt = j0 + threadIdx.x;
-      const int it = jt < ntv ? ti[jt] : 0;
-#pragma unroll
-      for (int w = 0; w < 8; w++) st[threadIdx.x * 8 + w] = jt < ntv ? t[(int64_t)it * 8 + w] : 0u;
-      si[threadIdx.x] = it;
-      __syncthreads();
-      const int lim = ntv - j0 < 256 ? ntv - j0 : 256;
-      for (int jj = part; jj < lim; jj += 4) {
-        uint32_t d = 0;
-#pragma unroll
-        for (int w = 0; w < 8; w++) d += (uint32_t)__popc(me[w] ^ st[jj * 8 + w]);
-        const uint32_t key = (d << 20) | (uint32_t)si[jj];
-        k2 = min(k2, max(k1, key));
-        k1 = min(k1, key);
-      }
-    }
-#pragma unroll
-    for (int o = 1; o <= 2; o <<= 1) {  // merge the four shares
-      const uint32_t o1 = (uint32_t)__shfl_xor((int)k1, o), o2 = (uint32_t)__shfl_xor((int)k2, o);
-      k2 = min(max(k1, o1), min(k2, o2));
-      k1 = min(k1, o1);
-    }
-    const int d1 = (int)(k1 >> 20), d2 = (int)(k2 >> 20), i1 = (int)(k1 & 0xfffffu);
-    if (live && part == 0) out_idx[iq] = (k1 != 0xffffffffu && k2 != 0xffffffffu && (float)d1 < ratio * (float)d2) ? i1 : -1;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// fe_match_consecutive on the MATRIX cores (round 6).  A Hamming distance is a K = 256 contraction: with the bits as +-1,
+// knnMatch(2) + ratio between CONSECUTIVE scans of a batch: pair j = slots first + j and first + j + 1 of the [slot][stride]
+// arrays, direction 0: queries = slot A against train = slot B -> fwd[j][i], 1 the reverse -> bwd[j][i].  Queries and train
+// descriptors are taken from the compacted lists of valid keypoints (ascending index, so "the first minimum wins" is the scan
+// order of fe_match / BFMatcher); invalid queries get -1.
+// On the MATRIX cores (round 6).  A Hamming distance is a K = 256 contraction: with the bits as +-1,
 // a . b = 256 - 2 hamming(a, b).  v_mfma_f32_32x32x64_f8f6f4 takes 64 fp8 values per lane pair and instruction, so FOUR of them
 // give the 32 x 32 distances of a tile of 32 train descriptors against a wavefront's 32 queries -- exact small integers in fp32 --
-// where the vector form spends 8 x (LDS read + xor + popcount) per pair and lane (27 instructions: 75 M pairs per 64-scan window,
+// where the vector form of round 5 spent 8 x (LDS read + xor + popcount) per pair and lane (27 instructions: 75 M pairs per 64-scan window,
 // 113 us).  Rows = train descriptors (the A operand, a tile staged in LDS as fp8 bytes by the block's 256 threads -- one
 // descriptor dword = 32 bytes each: 4 bits -> 4 bytes by one multiply, (n x 0x00204081) & 0x01010101, shifted into the sign
 // bits of 0x38 = 1.0 -- rows 272 bytes apart: conflict-free ds_read_b128), columns = queries (the B operand, expanded once, in
@@ -1119,15 +1058,9 @@ int rsx_frontend_match_consecutive_device(rsx_frontend *h, const uint8_t *d_desc
   RSX_TRY(h->vcount.reserve((size_t)(n_pairs + 1) * 4, s, false));
   hipLaunchKernelGGL(fe_compact_valid, dim3((unsigned)(n_pairs + 1)), dim3(256), 0, s, d_valid, d_counts, max_targets, first_slot,
                      h->vidx.as<int32_t>(), h->vcount.as<int32_t>());
-  static const bool valu_form = [] { const char *e = rsx::exp_env("RSX_FE_MATCH"); return e && e[0] == 'v'; }();  // experiments build: RSX_FE_MATCH=valu
-  if (valu_form)
-    hipLaunchKernelGGL(fe_match_consecutive, dim3((unsigned)((max_targets + FM_Q - 1) / FM_Q < 32 ? (max_targets + FM_Q - 1) / FM_Q : 32), (unsigned)n_pairs, 2), dim3(256), 0, s,
-                       reinterpret_cast<const uint32_t *>(d_desc), d_valid, d_counts, max_targets, first_slot, h->vidx.as<int32_t>(),
-                       h->vcount.as<int32_t>(), ratio, d_fwd, d_bwd);
-  else
-    hipLaunchKernelGGL(fe_match_consecutive_mfma, dim3((unsigned)(2 * n_pairs), (unsigned)((max_targets + MM_QB - 1) / MM_QB < FE_MM_GX ? (max_targets + MM_QB - 1) / MM_QB : FE_MM_GX)), dim3(256), 0, s,
-                       reinterpret_cast<const uint32_t *>(d_desc), d_valid, d_counts, max_targets, first_slot, h->vidx.as<int32_t>(),
-                       h->vcount.as<int32_t>(), ratio, d_fwd, d_bwd);
+  hipLaunchKernelGGL(fe_match_consecutive_mfma, dim3((unsigned)(2 * n_pairs), (unsigned)((max_targets + MM_QB - 1) / MM_QB < FE_MM_GX ? (max_targets + MM_QB - 1) / MM_QB : FE_MM_GX)), dim3(256), 0, s,
+                     reinterpret_cast<const uint32_t *>(d_desc), d_valid, d_counts, max_targets, first_slot, h->vidx.as<int32_t>(),
+                     h->vcount.as<int32_t>(), ratio, d_fwd, d_bwd);
   RSX_HIP(hipGetLastError());
   return RSX_OK;
 } RSX_CATCH_ALL

@@ -27,7 +27,9 @@ inline int fail(int code, const char *fmt, ...) {
 }
 
 // Experiment / tuning knobs read from the environment exist only in -DRSX_EXPERIMENTS builds (make EXPERIMENTS=1, what
-// tools/prof*.sh and tools/spectral/* build): the product library has no hidden switches.
+// tools/prof*.sh and tools/spectral/* build): the product library has no hidden switches.  The experiments build carries
+// tuning numbers and profiling of the kernels the product runs, not alternative kernels: a variant that lost its A/B test
+// is deleted (its measurement stays in DESIGN.md, its code in git history).
 inline const char *exp_env(const char *name) {
 #ifdef RSX_EXPERIMENTS
   return std::getenv(name);

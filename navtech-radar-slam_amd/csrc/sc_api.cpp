@@ -68,7 +68,6 @@ struct rsx_sc {
   struct {
     bool valid = false, filtered = false;
     int32_t nq = 0, k = 0;
-    int32_t window_head = 0;  // > 0: stage 1 left window records for this many list positions only; stage 2 adds the rest on demand
     int64_t n_items = 0, n_eligible = 0;
     const int64_t *q_elig = nullptr;
     QueryView qv{};
@@ -334,19 +333,10 @@ int filter_reserve(rsx_sc *h, int64_t n_items, int64_t qb, hipStream_t s) {
   return RSX_OK;
 }
 
-// RSX_SC_WINDOW=0 (experiments build): re-scoring without the matrix-core window previews
-bool use_window() {
-  static const bool on = [] {
-    const char *e = rsx::exp_env("RSX_SC_WINDOW");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // images -> MFMA filter -> short list + round edges of one query batch
 // elig_monotone: the per-query limits elig[] do not decrease with the query index (self queries)
 int filter_and_select(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, const int64_t *elig,
-                      int32_t first_target, int32_t k, hipStream_t s, bool elig_monotone = false, int32_t window_head_only = 0) {
+                      int32_t first_target, int32_t k, hipStream_t s, bool elig_monotone = false) {
   const DbView db = db_view(h);
   const int64_t ld = (n_items + 31) / 32 * 32;
   lb_t *lb = h->w->f_lb.as<lb_t>();
@@ -359,9 +349,8 @@ int filter_and_select(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_
                         h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
   // alignment + window preview of the head of every short list on the matrix cores (what re-scoring would otherwise
   // do on the VALU, one entry per wavefront)
-  if (!use_window()) return RSX_OK;
   return launch_window(db, q, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                       h->w->f_win.as<WindowPreview>(), s, window_head_only);
+                       h->w->f_win.as<WindowPreview>(), s);
 }
 
 int rescore(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, const int64_t *elig, int32_t round_begin,
@@ -371,7 +360,7 @@ int rescore(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, 
   return launch_rescore(db_view(h), q, h->w->f_lb.as<lb_t>(), ld, n_items, n_eligible, elig, h->w->f_cand.as<RescoreEntry>(),
                         h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), filter_eps(), round_begin, round_end, tau_src,
                         seed, d_out, k, s, (h->prof.on && h->stats.p) ? h->stats.as<unsigned long long>() : nullptr,
-                        use_window() ? h->w->f_win.as<WindowPreview>() : nullptr);
+                        h->w->f_win.as<WindowPreview>());
 }
 
 int32_t first_round_target() {
@@ -397,27 +386,10 @@ int run_topk_filtered(rsx_sc *h, const QueryView &qv, int64_t n_items, int64_t n
     q.norm = qv.norm + b0 * NS;
     q.nq = bn;
     const int64_t *elig = d_q_elig ? d_q_elig + b0 : nullptr;
-    // size of the first re-scoring round; later rounds double.  With the two-phase scoring (every candidate of a round
-    // gets the cheap alignment + fp32 preview, only the few the previews cannot exclude are evaluated exactly) a round
-    // costs more in barriers than in arithmetic, so the first one is large: measured on MI355X (10k trajectory DB, 8192
-    // queries, ms per step / exact evaluations per query): 64 -> 4.24 / 11.2, 128 -> 4.18 / 10.4; the one-pass scoring of
-    // round 1 (RSX_SC_TWO_PHASE=0: first round scored exactly, 96 evaluations per query) 4.0 with 64
+    // size of the first re-scoring round; later rounds double (measured on MI355X with the earlier 4-wave rounds kernel, 10k
+    // trajectory DB, 8192 queries, ms per step / exact evaluations per query: 64 -> 4.24 / 11.2, 128 -> 4.18 / 10.4)
     RSX_TRY(filter_and_select(h, q, n_items, n_eligible, elig, first_round_target(), k, s, elig_monotone));
-    // exact re-scoring: the 8-wave workgroup in rounds (sc_rescore_kernel; also what the sharded stages use), or
-    // -- RSX_SC_RESCORE=walk, experimental -- one wave per query walking the bound-ordered short list with
-    // the fp32 pruning preview (sc_walk_kernel: identical results, 6.3 instead of 5.6 ms per step on the bench:
-    // the per-query chain of ~125 dependent candidates is latency-bound at 2 waves per SIMD)
-    static const bool use_walk = [] {
-      const char *e = rsx::exp_env("RSX_SC_RESCORE");
-      return e && e[0] == 'w';
-    }();
-    if (use_walk) {
-      const int64_t ld = (n_items + 31) / 32 * 32;
-      RSX_TRY(launch_walk(db_view(h), q, h->w->f_lb.as<lb_t>(), ld, n_items, n_eligible, elig, h->w->f_cand.as<RescoreEntry>(),
-                          h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), filter_eps(), d_out + b0 * k, k, s));
-    } else {
-      RSX_TRY(rescore(h, q, n_items, n_eligible, elig, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, d_out + b0 * k, s));
-    }
+    RSX_TRY(rescore(h, q, n_items, n_eligible, elig, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, d_out + b0 * k, s));
   }
   return RSX_OK;
 }
@@ -1369,14 +1341,9 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
     // Round 6: where the whole batch goes through ONE filter workspace (the usual case: 8192 queries against 10 000 entries), only
     // the FILTER runs piece by piece -- keys, query images and bound rows of piece c while piece c + 1 goes up -- and the stages
     // behind it (short lists, window previews, re-scoring) run ONCE over the whole batch: their fixed costs (~90 us of dependent
-    // small kernels per piece) are what the piecewise chains paid three times.  RSX_SC_HOST_TAIL=pieces (experiments build)
-    // keeps the chains.
-    static const bool one_tail_allowed = [] {
-      const char *e = rsx::exp_env("RSX_SC_HOST_TAIL");
-      return !(e && e[0] == 'p');
-    }();
+    // small kernels per piece) are what the piecewise chains paid three times.
     const int64_t items = local_count_below(h, n_eligible), elig_all = n_eligible < 0 ? h->n_global : n_eligible;
-    const bool one_tail = one_tail_allowed && !use_q1(h, nq, items) && use_filter(h, nq, items) && filter_batch(items, nq) >= nq;
+    const bool one_tail = !use_q1(h, nq, items) && use_filter(h, nq, items) && filter_batch(items, nq) >= nq;
     auto filter_pieces_one_tail = [&]() -> int {
       hipStream_t s = h->stream;
       h->w = &h->ws[0];
@@ -1412,9 +1379,8 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
       const DbView db = db_view(h);
       RSX_TRY(launch_select(db, lb, ld, items, nq, elig_all, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
                             h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
-      if (use_window())
-        RSX_TRY(launch_window(db, all, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                              h->w->f_win.as<WindowPreview>(), s, 0));
+      RSX_TRY(launch_window(db, all, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
+                            h->w->f_win.as<WindowPreview>(), s));
       return rescore(h, all, items, elig_all, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, h->topk.as<rsx_sc_hit>(), s);
     };
     auto all_pieces = [&]() -> int {
@@ -1507,9 +1473,8 @@ int rsx_sc_query_bounds_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t 
     RSX_TRY(launch_gather_bounds(reinterpret_cast<const lb_t *>(d_lb_blocks), block_ld, block_stride, b0, q.nq, h->w->f_lb.as<lb_t>(), ld, s));
     RSX_TRY(launch_select(db, h->w->f_lb.as<lb_t>(), ld, n_items, q.nq, n_elig, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
                           h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
-    if (use_window())
-      RSX_TRY(launch_window(db, q, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                            h->w->f_win.as<WindowPreview>(), s));
+    RSX_TRY(launch_window(db, q, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
+                          h->w->f_win.as<WindowPreview>(), s));
     RSX_TRY(rescore(h, q, n_items, n_elig, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, d_out + b0 * k, s));
   }
   return RSX_OK;
@@ -1535,7 +1500,6 @@ int rsx_sc_query_stage1_elig_device(rsx_sc *h, const float *d_q, int32_t nq, int
   const int64_t n_elig = n_eligible < 0 ? h->n_global : n_eligible;
   RSX_TRY(h->st_partial.reserve((size_t)nq * k * sizeof(rsx_sc_hit), s, false));
   const bool filtered = use_filter(h, nq, items) && filter_batch(items, nq) >= nq;
-  int32_t window_head = 0;
   if (filtered) {
     // round 0 only: this shard's share of the ~160 lowest bounds per query -- enough for the merged
     // k-th distance to be the final one for almost every query (a single GPU needs ~120 exact scores
@@ -1551,19 +1515,9 @@ int rsx_sc_query_stage1_elig_device(rsx_sc *h, const float *d_q, int32_t nq, int
     if (first < 8) first = 8;
     if (first > 128) first = 128;
     RSX_TRY(filter_reserve(h, items, nq, s));
-    // Round 5 experiment, OFF by default (RSX_SC_WINDOW_HEAD=1 in the experiments build): a DB shard's window kernel scores only
-    // the head of the list that round 0 re-scores -- S shards previewing 128 list positions each are S times one GPU's window
-    // kernel -- and stage 2 makes the records behind the head ON DEMAND, for the positions whose bound can still reach the k-th
-    // best distance of the merged lists (sc_window_tail_kernel).  Emulated per-rank compute, 1 x 8, 8192 queries against a
-    // 10 000-entry random DB (tools/bench_layouts.py): the whole head in stage 1 1.20 ms; head only and NO tail (stage 2 pays a
-    // VALU preview, one entry per wavefront, per candidate) 6.87 ms; head only + tail on demand 1.52 ms -- a second launch of a
-    // workgroup per query that stages the query's images again costs more than the previews it saves.
-    static const bool head_only = [] {
-      const char *e = rsx::exp_env("RSX_SC_WINDOW_HEAD");
-      return e && e[0] == '1';
-    }();
-    window_head = (head_only && h->p.shard_world > 1 && use_window()) ? first : 0;
-    RSX_TRY(filter_and_select(h, qv, items, n_elig, d_q_elig, first, k, s, elig_monotone != 0, window_head));
+    // (every shard makes the window records of its whole list head in stage 1: making the records behind a shorter head on
+    // demand in stage 2 was measured slower)
+    RSX_TRY(filter_and_select(h, qv, items, n_elig, d_q_elig, first, k, s, elig_monotone != 0));
     RSX_TRY(rescore(h, qv, items, n_elig, d_q_elig, 0, 1, nullptr, nullptr, k, h->st_partial.as<rsx_sc_hit>(), s));
   } else {
     RSX_TRY(run_topk(h, qv, items, n_elig, d_q_elig, k, h->st_partial.as<rsx_sc_hit>(), s, elig_monotone != 0));  // complete already
@@ -1571,7 +1525,6 @@ int rsx_sc_query_stage1_elig_device(rsx_sc *h, const float *d_q, int32_t nq, int
   RSX_HIP(hipMemcpyAsync(d_partial, h->st_partial.p, (size_t)nq * k * sizeof(rsx_sc_hit), hipMemcpyDeviceToDevice, s));
   h->st.valid = true;
   h->st.filtered = filtered;
-  h->st.window_head = window_head;
   h->st.nq = nq;
   h->st.k = k;
   h->st.n_items = items;
@@ -1591,13 +1544,9 @@ int rsx_sc_query_stage2_device(rsx_sc *h, int32_t nq, int32_t k, const rsx_sc_hi
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
   h->st.valid = false;
-  if (h->st.filtered) {
-    if (h->st.window_head > 0)
-      RSX_TRY(launch_window_tail(db_view(h), nq, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                                 h->w->f_win.as<WindowPreview>(), h->st.window_head, d_global, s));
+  if (h->st.filtered)
     return rescore(h, h->st.qv, h->st.n_items, h->st.n_eligible, h->st.q_elig, 1, RESCORE_ALL_ROUNDS, d_global,
                    h->st_partial.as<rsx_sc_hit>(), k, d_out, s);
-  }
   RSX_HIP(hipMemcpyAsync(d_out, h->st_partial.p, (size_t)nq * k * sizeof(rsx_sc_hit), hipMemcpyDeviceToDevice, s));
   return RSX_OK;
 } RSX_CATCH_ALL

@@ -65,8 +65,8 @@ __device__ __forceinline__ float wave_min_f32(float v) {
   return fminf(fminf(r0, r1), fminf(r2, r3));
 }
 
-// the per-lane registers of one entry (lane = column): loaded by pair_group itself, or ahead of time by a
-// caller that overlaps the global-memory latency with the previous entry's arithmetic (sc_walk_kernel)
+// the per-lane registers of one entry (lane = column), loaded ahead of time by a caller that overlaps the global-memory
+// latency with the previous entry's arithmetic (sc_pair2_kernel, sc_rescore_wave_kernel, sc_q1.hip)
 struct EntryRegs {
   float4 ecol[5];
   double v, n2;

@@ -492,7 +492,7 @@ __device__ __forceinline__ int64_t n_elig_items(const Elig &el, int q, int64_t n
 }
 
 // ------------------------------------------------------------------------------------------
-// short list + round edges of one query (feeds sc_rescore_kernel): histogram of the eligible bounds,
+// short list + round edges of one query (feeds sc_window_kernel and sc_rescore_wave_kernel): histogram of the eligible bounds,
 // prefix sum, then
 //   t_cap  = edge of the last bin b_cap whose cumulative count still fits RESCORE_SHORTLIST_CAP
 //   t_r    = edge of the first bin with at least target[r] bounds at or below it, clamped to t_cap
@@ -608,8 +608,8 @@ __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__
     reinterpret_cast<int32_t *>(thr)[(int64_t)q * RESCORE_THR_STRIDE + RESCORE_NUM_THR + threadIdx.x] = b >= 0 ? hist[b] : 0;
   }
   // compaction of bins <= b_cap, ORDERED BY BIN (counting sort: entry of bin b goes to [cum[b-1], cum[b]),
-  // any order inside a bin): sc_walk_kernel walks the list in ascending-bound order, sc_rescore_kernel
-  // does not care
+  // any order inside a bin): the window records cover the head of the list, and sc_rescore_wave_kernel walks the rest in
+  // ascending-bound order, stopping at the first bin whose lower edge tau excludes
   RescoreEntry *out = slist + (int64_t)q * RESCORE_SHORTLIST_CAP;
   __shared__ int fill[H_BINS];
   for (int i = threadIdx.x; i < H_BINS; i += 256) fill[i] = i ? hist[i - 1] : 0;  // exclusive prefix = first position

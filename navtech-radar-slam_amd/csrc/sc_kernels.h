@@ -121,22 +121,17 @@ struct RescoreEntry {
 int launch_select(const DbView &db, const lb_t *lb, int64_t ld_lb, int64_t n_items, int32_t nq, int64_t n_eligible,
                   const int64_t *q_elig, int32_t first_target, RescoreEntry *slist, int32_t *sl_cnt, float *thr,
                   hipStream_t s);
-// one workgroup per query: rounds [round_begin, round_end) of ascending bound with tau tightening
+// one wave per query: list positions of rounds [round_begin, round_end) of ascending bound with tau tightening
 // (round_end = RESCORE_ALL_ROUNDS: also the entries beyond the short list); writes the top-k it knows.
+// win: the window records of launch_window for the same short lists (the head of every list);
 // tau_src (optional): a top-k that covers more than this shard -- its k-th distance caps tau;
 // seed (optional): this shard's hits from an earlier stage, merged into the output.
 constexpr int RESCORE_ALL_ROUNDS = RESCORE_NUM_THR + 1;
 int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t ld_lb, int64_t n_items,
                    int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
                    const float *thr, double eps, int32_t round_begin, int32_t round_end, const rsx_sc_hit *tau_src,
-                   const rsx_sc_hit *seed, rsx_sc_hit *d_out, int32_t k, hipStream_t s,
-                   unsigned long long *d_stats = nullptr, const WindowPreview *win = nullptr);
-
-// the same job by one wave per query walking the short list in ascending-bound order (needs the short list
-// ordered by histogram bin, which launch_select produces); single-shard, single-stage
-int launch_walk(const DbView &db, const QueryView &q, const lb_t *lb, int64_t ld_lb, int64_t n_items,
-                int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
-                const float *thr, double eps, rsx_sc_hit *d_out, int32_t k, hipStream_t s);
+                   const rsx_sc_hit *seed, rsx_sc_hit *d_out, int32_t k, hipStream_t s, unsigned long long *d_stats,
+                   const WindowPreview *win);
 
 // ---- MFMA lower-bound filter (sc_filter.hip) ----
 constexpr int FILTER_QIMG_BYTES = 9984;  // LDS image of one query (two displaced fp16 copies)
@@ -205,14 +200,8 @@ size_t window_qimg_bytes(int32_t nq);  // direct-filter images + key images of a
 int launch_window_db_keys(const double *vkey, int64_t first, int64_t count, void *vk16, float *vk_n, hipStream_t s);
 // qimg: window_qimg_bytes(nq) of workspace (filled here); out: [nq][WINDOW_P]
 // k: the top-k the query batch asks for; eps: the filter's error budget (filter_eps())
-// head_only > 0: records for the first head_only list positions (rounded up to 32) only, "no record" behind them -- stage 1
-// of a DB shard scores only that many entries per query, and S shards previewing 128 each is S times the work of one GPU
 int launch_window(const DbView &db, const QueryView &q, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt,
-                  int32_t k, double eps, WindowPreview *out, hipStream_t s, int32_t head_only = 0);
-// stage 2 of a DB shard after a head-only stage 1: records for the list positions behind the head whose bound can still reach
-// the k-th best distance of d_global [nq][k] (the merged stage-1 lists); qimg still holds stage 1's query images
-int launch_window_tail(const DbView &db, int32_t nq, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt, int32_t k, double eps,
-                       WindowPreview *out, int32_t head, const rsx_sc_hit *d_global, hipStream_t s);
+                  int32_t k, double eps, WindowPreview *out, hipStream_t s);
 const char *window_kernel_name();
 
 // ---- one query in one launch (sc_q1.hip): the live detector's regime, nq <= Q1_MAX_NQ ----

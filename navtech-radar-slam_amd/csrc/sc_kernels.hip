@@ -6,8 +6,9 @@
 //   pair_group<B>     distanceBtnScanContext for one query x B entries   SC.cpp:69-148   (device function)
 //   sc_pair_kernel    pair_group over every entry / a gather list        SC.cpp:380-395  (small problems, the 3
 //                     kd-tree candidates, rsx_sc_pair_distances)
-//   sc_rescore_kernel pair_group over the entries the MFMA filter (sc_filter.hip) could not exclude,
-//                     in rounds of ascending bound with tau tightening (batched exhaustive queries)
+//   sc_pair2_kernel   the same in top-k form, in two phases (fp32 alignment + preview, then exact fp64)
+//   sc_rescore_wave_kernel  the exact distances of the entries the MFMA filter (sc_filter.hip / sc_spec.hip) and
+//                     the window previews (sc_window.hip) could not exclude (batched exhaustive queries)
 //   sc_merge_kernel   the strict-< "first wins" candidate loop           SC.cpp:380-395 (generalised to top-k)
 //   sc_knn_kernel     nanoflann 3-NN on ring keys                        SC.cpp:367-374, NF.hpp:383-408
 //
@@ -87,7 +88,7 @@ constexpr int OFF_QIMG = 0;
 constexpr int OFF_QN1 = 60 * Q_COL_STRIDE;       // 10560
 constexpr int OFF_QV1 = OFF_QN1 + 512;           // 11072
 constexpr int OFF_WAVES = OFF_QV1 + 512;         // 11584
-// pruning preview (sc_walk_kernel): the query's unit columns in fp32 (column stride 80 B = 5 LDS slots, odd:
+// pruning preview (phase_a, sc_pair2_kernel): the query's unit columns in fp32 (column stride 80 B = 5 LDS slots, odd:
 // conflict-free ds_read_b128 across the lanes of a group) + a flag "every non-empty column norm is in
 // [1e-15, 1e15]"; lives behind the per-wave region of the kernels that use it
 constexpr int QP_COL_STRIDE = NR * 4;            // 80
@@ -129,7 +130,7 @@ constexpr int pair_waves_per_simd() {
 // {1e7, 0} when no shift of the window has an effective column (SC.cpp:133-134 initial values).
 // ------------------------------------------------------------------------------------------
 
-// FAST alignment (sc_rescore_kernel): fastAlignUsingVkey asks for the FIRST strict minimum over the 60 shifts of a
+// Fast alignment (phase_a below): fastAlignUsingVkey asks for the FIRST strict minimum over the 60 shifts of a
 // 60-term fp64 sum.  The 60 sums are first evaluated in fp32 (15 x ds_read_b128 + 4 packed VALU per lane instead of
 // 30 x 2 reads + 180 fp64 operations).  With E = ||v1||^2 + ||v2||^2, every fp32 value D~[k] is within
 //   eps_D = 129.3 * 2^-24 * E  (conversion + subtraction rounding 8.02 u E, 60 fused accumulations 121.3 u E)
@@ -145,23 +146,19 @@ constexpr float kFastAlignEps = 1.6e-5f;  // > 2^-16.5 = 129.3 * 2^-24 * 1.04, o
 __host__ __device__ constexpr int fimg_base(int j) { return (j == 0 ? 0 : j == 1 ? 37 : j == 2 ? 73 : 109) * 16; }
 typedef float float2p __attribute__((ext_vector_type(2)));
 
-// PREVIEW (sc_walk_kernel): once the alignment k* is known, the 7 window distances are first evaluated
+// Preview (phase_a below): once the alignment k* is known, the 7 window distances are first evaluated
 // cheaply in fp32 -- dot products of the query's unit columns (fp32 image in LDS at smem + off_preview)
 // with the entry's raw fp32 column, scaled by 1/n2, summed by a wave reduction: no fp64 division, no
-// sequential sum -- and the exact stages 2-3 only run when that preview, minus a margin far above its
+// sequential sum -- and the exact evaluation only runs when that preview, minus a margin far above its
 // error (a few 1e-6: 20-term dot products and a 60-term sum of values <= 1 in fp32), can still reach
-// tau_prune = the k-th best exact distance so far.  Column norms outside [1e-15, 1e15] (fp32 products
-// could under- or overflow) and non-finite previews disable it.  A pruned group returns {+inf, ...}
-// ("not a hit"); with tau_prune = +inf nothing is pruned.
+// the k-th best exact distance so far.  Column norms outside [1e-15, 1e15] (fp32 products could under-
+// or overflow) and non-finite previews disable it.
 constexpr float kPreviewMargin = 1e-4f;
 
 
-template <int B, bool PREVIEW = false, bool FAST = false, int SO = dev::SO_SSE2>
+template <int B, int SO = dev::SO_SSE2>
 __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, char *wsm, int lane,
-                                           const int64_t (&eslot)[B], double &bd_out, int &bk_out,
-                                           double tau_prune = INFINITY, int off_preview = 0,
-                                           const EntryRegs *pre = nullptr, float e1 = 0.0f) {
-  static_assert(!FAST || B == 1, "the fast alignment takes its decisions per wave: one entry per group");
+                                           const int64_t (&eslot)[B], double &bd_out, int &bk_out) {
   const int cl = lane < NS ? lane : 0;       // entry column owned in stage 2
   const int kk = lane < NS ? lane : NS - 1;  // shift owned in stage 1
   const double *v1 = reinterpret_cast<const double *>(smem + OFF_QV1);
@@ -171,60 +168,14 @@ __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, c
     wave_lds_fence();
 #pragma unroll
     for (int b = 0; b < B; b++) {
-      if (pre) {
-        ev[b] = pre[b].v;
+      ev[b] = db.vkey[eslot[b] * NS + cl];
+      const float4 *src = reinterpret_cast<const float4 *>(db.desc + eslot[b] * DS + cl * NR);
 #pragma unroll
-        for (int i = 0; i < 5; i++) ecol[b][i] = pre[b].ecol[i];
-        en2[b] = pre[b].n2;
-      } else {
-        ev[b] = db.vkey[eslot[b] * NS + cl];
-        const float4 *src = reinterpret_cast<const float4 *>(db.desc + eslot[b] * DS + cl * NR);
-#pragma unroll
-        for (int i = 0; i < 5; i++) ecol[b][i] = src[i];
-        en2[b] = db.norm[eslot[b] * NS + cl];
-      }
+      for (int i = 0; i < 5; i++) ecol[b][i] = src[i];
+      en2[b] = db.norm[eslot[b] * NS + cl];
     }
 
     int kstar[B];
-    bool need_exact = true;  // wave-uniform
-    if constexpr (FAST) {
-      const float vf = (float)ev[0];
-      if (lane < NS) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          float *img = reinterpret_cast<float *>(wsm + fimg_base(j));
-          if (lane >= j) img[lane - j] = vf;
-          img[lane + NS - j] = vf;
-          if (lane < j) img[lane + 2 * NS - j] = vf;
-        }
-      }
-      const float e2 = wave_sum_f32(lane < NS ? vf * vf : 0.0f);
-      wave_lds_fence();
-      const int j = (-kk) & 3;
-      const float4 *yp = reinterpret_cast<const float4 *>(wsm + fimg_base(j) + (NS - kk - j) * 4);
-      const float4 *xp = reinterpret_cast<const float4 *>(smem + off_preview + QP_V1F);
-      float2p a0 = {0.0f, 0.0f}, a1 = {0.0f, 0.0f};
-#pragma unroll
-      for (int i = 0; i < NS / 4; i++) {
-        const float4 x = xp[i], y = yp[i];
-        const float2p d0 = float2p{x.x, x.y} - float2p{y.x, y.y}, d1 = float2p{x.z, x.w} - float2p{y.z, y.w};
-        a0 = __builtin_elementwise_fma(d0, d0, a0);
-        a1 = __builtin_elementwise_fma(d1, d1, a1);
-      }
-      const float D = (a0[0] + a0[1]) + (a1[0] + a1[1]);
-      const float dmin = wave_min_f32(lane < NS ? D : INFINITY);  // fminf drops NaNs: they are caught by the ballot below
-      const float thr = dmin + 2.0f * kFastAlignEps * (e1 + e2);
-      const unsigned long long nan_bal = __ballot(lane < NS && !(D == D));
-      const unsigned long long cand = __ballot(lane < NS && D <= thr);
-      // dmin < 1e12: the winning norm is < 1e6 < the reference's 1e7 init (SC.cpp:96); thr finite: E finite
-      if (!nan_bal && dmin < 1e12f && thr < 3.0e38f && __popcll(cand) == 1) {
-        kstar[0] = __ffsll((long long)cand) - 1;
-        need_exact = false;
-      }
-      wave_lds_fence();  // the fp64 key images / similarity terms overwrite the fp32 images
-    }
-
-    if (need_exact) {
 #pragma unroll
     for (int b = 0; b < B; b++) {
       const double v = ev[b];
@@ -289,56 +240,6 @@ __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, c
       for (int off = 32; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off));
       unsigned long long bal = __ballot(ok && nrm == m);
       kstar[b] = bal ? (__ffsll((long long)bal) - 1) : 0;  // first strict minimum = lowest shift
-    }
-    }  // need_exact
-
-    if constexpr (PREVIEW) {
-      if (tau_prune < INFINITY && *reinterpret_cast<const int *>(smem + off_preview + QP_FLAG)) {  // wave-uniform
-        bool any_alive = false;
-#pragma unroll
-        for (int b = 0; b < B; b++) {
-          const int ks = kstar[b];
-          const double n2 = en2[b];
-          const bool n2_ok = (n2 == 0.0) || (n2 >= 1e-15 && n2 <= 1e15);
-          if (__ballot(!n2_ok && lane < NS)) {  // unusual scale (or NaN): no preview for this entry
-            any_alive = true;
-            continue;
-          }
-          const float r2 = (n2 == 0.0) ? 0.0f : (float)(1.0 / n2);
-          float best = INFINITY;
-#pragma unroll 1
-          for (int t = 0; t < 7; t++) {
-            int k = ks + t - 3;
-            k += (k < 0) ? NS : 0;
-            k -= (k >= NS) ? NS : 0;
-            int c = cl + k;
-            c -= (c >= NS) ? NS : 0;
-            const float4 *qp = reinterpret_cast<const float4 *>(smem + off_preview + c * QP_COL_STRIDE);
-            float dot = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 5; i++) {
-              const float4 q4 = qp[i];
-              dot = fmaf(q4.x, ecol[b][i].x, dot);
-              dot = fmaf(q4.y, ecol[b][i].y, dot);
-              dot = fmaf(q4.z, ecol[b][i].z, dot);
-              dot = fmaf(q4.w, ecol[b][i].w, dot);
-            }
-            const bool valid = (lane < NS) && !((qn1[c] == 0.0) | (n2 == 0.0));  // SC.cpp:78
-            const float sum = wave_sum_f32(valid ? dot * r2 : 0.0f);
-            const int ne = __popcll(__ballot(valid));
-            const float d = 1.0f - sum / (float)ne;  // ne == 0: NaN, ignored like SC.cpp:87-88,134
-            if (!(d == d) && ne != 0) best = -INFINITY;  // non-finite data: never prune
-            best = fminf(best, d);                        // fminf drops the 0/0 NaN
-          }
-          // exact distance >= preview - error: it cannot enter a top-k whose k-th distance is tau_prune
-          if (!(best - kPreviewMargin > (float)tau_prune)) any_alive = true;
-        }
-        if (!any_alive) {
-          bd_out = INFINITY;
-          bk_out = 0x7fffffff;
-          return;
-        }
-      }
     }
 
     // ---- stage 2: column cosine terms for the 7 shifts k*-3..k*+3 (SC.cpp:123-144, 69-90) ----
@@ -437,7 +338,7 @@ __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, c
 
 
 // ------------------------------------------------------------------------------------------
-// The same pair function in two phases, one entry per wavefront (sc_rescore_kernel):
+// The same pair function in two phases, one entry per wavefront (sc_pair2_kernel):
 //   phase A  alignment k* (fast fp32 form with exact fallback, see above) + the fp32 preview of the 7 window
 //            distances: a value pv with |pv - exact distance| <= kPreviewMargin -- cheap (~40 % of a full
 //            evaluation), and good for BOTH directions: pv - margin prunes, and the k-th smallest pv + margin over
@@ -748,7 +649,7 @@ __global__ __launch_bounds__(256, W) void sc_pair_kernel(PairArgs a) {
     }
     double bd;
     int bk;
-    pair_group<B, false, false, SO>(a.db, smem, wsm, lane, eslot, bd, bk);
+    pair_group<B, SO>(a.db, smem, wsm, lane, eslot, bd, bk);
 
     // ---- outputs ----
 #pragma unroll
@@ -987,40 +888,13 @@ __global__ __launch_bounds__(1024) void sc_knn_kernel(const float *__restrict__ 
 }
 
 
-// ------------------------------------------------------------------------------------------
-// sc_rescore_kernel: exact re-scoring behind the MFMA filter (sc_filter.hip / sc_spec.hip), one RS_WAVES-wave workgroup
-// per query.  The query's candidates arrive as a short list of (bound, slot) records -- the entries
-// with the smallest filter bounds -- and are scored in rounds of ascending bound: after every round
-// the workgroup merges its per-wave top-k lists into tau (the k-th best exact distance so far) and
-// the next round only scores entries with bound - eps <= tau.  It stops as soon as the next bound
-// range cannot reach the top-k; entries beyond the short list (bound >= t_cap) are only scanned when
-// tau still admits them.  Output: the final top-k, sorted by (dist, global index), padded {1e7,0,0}.
-// ------------------------------------------------------------------------------------------
-constexpr int RS_CAND_CAP = 1024;  // candidates of one round (or chunk of a round) in LDS: slot | k* << 26, and their previews
-static_assert(RESCORE_SHORTLIST_CAP % RS_CAND_CAP == 0, "rounds are processed in chunks of RS_CAND_CAP list entries");
-constexpr int RS_SLOT_BITS = 26;   // local slots < 2^26 (64 M entries per shard) when the two-phase scoring is used
-#ifndef RSX_RESCORE_PREVIEW
-#define RSX_RESCORE_PREVIEW 1
-#endif
-constexpr bool kRescorePreview = RSX_RESCORE_PREVIEW != 0;
-
-template <int B, int RS_WAVES>
-struct RescoreLds {
-  static constexpr int OFF_CAND = OFF_WAVES + RS_WAVES * B * ENT_SIZE;
-  static constexpr int OFF_PV = OFF_CAND + RS_CAND_CAP * 4;                        // int32 candidate slots (| k* << 26 after phase A)
-  static constexpr int OFF_XCH = OFF_PV + RS_CAND_CAP * 4;                         // fp32 previews of the candidates
-  static constexpr int OFF_MISC = OFF_XCH + RS_WAVES * RSX_SC_MAX_TOPK * 16;       // per-wave top-k lists
-  static constexpr int OFF_QP32 = OFF_MISC + 64;                                    // fp32 preview image of the query
-  static constexpr int SIZE = OFF_QP32 + QP_SIZE;
-};
-
 struct RescoreArgs {
   DbView db;
   QueryView q;
   const lb_t *lb;  // filter bounds [nq][ld_lb] (only read past the short list)
   int64_t ld_lb, n_items, n_eligible;
   const int64_t *q_elig;
-  const RescoreEntry *slist;  // [nq][RS_CAND_CAP]
+  const RescoreEntry *slist;  // [nq][RESCORE_SHORTLIST_CAP]
   const int32_t *sl_cnt;      // [nq]
   const float *thr;           // [nq][RESCORE_THR_STRIDE]: round edges t_0 <= t_1 <= ... (the last one is t_cap), then the
                               // number of short-list entries below each edge as int32
@@ -1030,339 +904,10 @@ struct RescoreArgs {
   double eps;
   int32_t k;
   int32_t round_begin, round_end;  // rounds [begin, end) of the short list; end > RESCORE_NUM_THR: also the rest
-  unsigned long long *stats;       // optional (bench instrumentation): [0] += candidates scored (phase A or full), [1] += queries
-                                   // that scored any, [2] += exact window evaluations (phase B; two-phase scoring only)
-  int32_t two_phase;               // B == 1: alignment + fp32 preview of every candidate first, exact evaluation of the few left
-  const WindowPreview *win;        // [nq][WINDOW_P] records of sc_window.hip (sc_rescore_wave_kernel only); stats[3] += records used,
-                                   // stats[11] += exact alignments
+  unsigned long long *stats;       // optional (bench instrumentation): [0] += candidates looked at, [1] += queries that scored
+                                   // any, [2] += exact window evaluations (phase B)
+  const WindowPreview *win;        // [nq][WINDOW_P] records of sc_window.hip; stats[3] += records used, stats[11] += exact alignments
 };
-
-// k-th smallest valid record (by (dist, index)) of the nrec records in xch, by RANK COUNTING on one wave:
-// every lane takes a record and counts the valid records before it (nrec broadcast LDS reads, no
-// dependent cross-lane steps -- the first version selected the minimum k times with a 6-step shuffle
-// reduction each, ~20 k cycles per merge, which made every re-scoring round cost as much as 3 pair
-// evaluations).  Records are distinct under the order (every entry is scored once).  When out != nullptr
-// the k smallest are written to out[0..k) in order, padded with {1e7,0,0} (SC.cpp:362-364).  Returns the
-// k-th distance or +inf.
-__device__ __forceinline__ double wave_select_kth(const rsx_sc_hit *xch, int nrec, int k, int lane, rsx_sc_hit *out) {
-  double kth = INFINITY;
-  int nvalid = 0;
-  for (int base = 0; base < nrec; base += 64) {  // uniform trip count
-    const int t = base + lane;
-    rsx_sc_hit me;
-    me.dist = kBig; me.index = 0; me.shift = 0;
-    if (t < nrec) me = xch[t];
-    const bool valid = me.dist < kBig;  // padding is {>= 1e7, ...}
-    int rank = 0;
-    int j = 0;
-    for (; j + 8 <= nrec; j += 8) {  // 8 reads in flight per step (one LDS round trip per 8 records, not per record)
-      rsx_sc_hit o[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) o[u] = xch[j + u];  // same address in every lane: broadcast reads
-#pragma unroll
-      for (int u = 0; u < 8; u++) rank += ((o[u].dist < kBig) && hit_before(o[u].dist, o[u].index, me.dist, me.index)) ? 1 : 0;
-    }
-    for (; j < nrec; j++) {
-      const rsx_sc_hit o = xch[j];
-      rank += ((o.dist < kBig) && hit_before(o.dist, o.index, me.dist, me.index)) ? 1 : 0;
-    }
-    if (out && valid && rank < k) out[rank] = me;
-    const unsigned long long is_kth = __ballot(valid && rank == k - 1);
-    if (is_kth) kth = __shfl(me.dist, __ffsll((long long)is_kth) - 1);
-    nvalid += __popcll(__ballot(valid));
-  }
-  if (out) {
-    rsx_sc_hit pad;
-    pad.dist = kBig; pad.index = 0; pad.shift = 0;
-    for (int r = nvalid + lane; r < k; r += 64) out[r] = pad;
-  }
-  return kth;
-}
-
-// RS_WAVES waves per workgroup, W = waves per SIMD the register allocator leaves room for (several
-// workgroups share a CU so that one query's barriers / merges hide behind another's scoring)
-template <int B, int RS_WAVES, int W, bool TWO, int SO>
-__global__ __launch_bounds__(RS_WAVES * 64, W) void sc_rescore_kernel(RescoreArgs a) {
-  static_assert(!TWO || B == 1, "two-phase scoring handles one entry per wavefront");
-  if (a.stats) a.stats += (blockIdx.x % RESCORE_STAT_COPIES) * RESCORE_STAT_WORDS;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using L = RescoreLds<B, RS_WAVES>;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int qi = blockIdx.x;
-  char *wsm = smem + OFF_WAVES + wave * (B * ENT_SIZE);
-  int32_t *cand = reinterpret_cast<int32_t *>(smem + L::OFF_CAND);
-  rsx_sc_hit *xch = reinterpret_cast<rsx_sc_hit *>(smem + L::OFF_XCH);
-  int *s_ncand = reinterpret_cast<int *>(smem + L::OFF_MISC);
-  double *s_tau = reinterpret_cast<double *>(smem + L::OFF_MISC + 8);
-
-  // the query image is only brought into LDS when the first candidate shows up: in the later stages
-  // of a sharded search most queries have nothing left to score
-  bool query_loaded = false;
-  bool scored_any = false;
-  if (threadIdx.x == 0) {
-    *s_ncand = 0;
-    *s_tau = INFINITY;
-  }
-  __syncthreads();
-
-  int64_t n_elig = a.n_eligible;
-  if (a.q_elig) {
-    const int64_t e = a.q_elig[qi];
-    n_elig = e < n_elig ? e : n_elig;
-  }
-  // local slots [0, n_rows) are the eligible ones
-  int64_t n_rows = 0;
-  if (n_elig > a.db.idx_base) {
-    n_rows = (n_elig - a.db.idx_base + a.db.idx_stride - 1) / a.db.idx_stride;
-    n_rows = n_rows < a.n_items ? n_rows : a.n_items;
-  }
-
-  double ld = INFINITY;  // per-wave sorted top-k, one record per lane; lives across rounds
-  int li = 0x7fffffff, ls = 0;
-  // tau never exceeds the k-th distance of a top-k that covers more than this shard (multi-GPU
-  // stage 2): any upper bound of the global k-th best distance prunes correctly
-  double tau_init = INFINITY;
-  if (a.tau_src) {
-    const double d = a.tau_src[(int64_t)qi * a.k + (a.k - 1)].dist;
-    if (d < kBig) tau_init = d;
-  }
-  double tau = tau_init;
-  if (a.seed && wave == 0 && lane < a.k) {  // sorted, padded {1e7,0,0} at the end
-    const rsx_sc_hit h = a.seed[(int64_t)qi * a.k + lane];
-    if (h.dist < kBig) {
-      ld = h.dist; li = h.index; ls = h.shift;
-    }
-  }
-
-  // region timing for profiling runs (wave 0 of every workgroup, s_memtime): [4] query load, [5] phase A, [6] preview
-  // merge, [7] phase B, [8] exact merge, [9] gather / append, [10] whole workgroup
-  long long t_last = 0;
-  const bool timing = a.stats != nullptr && wave == 0;
-  auto tick = [&](int slot) {
-    if (!timing) return;
-    const long long t = clock64();
-    if (slot >= 0 && lane == 0) atomicAdd(a.stats + slot, (unsigned long long)(t - t_last));
-    t_last = t;
-  };
-  const long long t_begin = timing ? clock64() : 0;
-  tick(-1);
-  // score cand[0..ncand) (all waves), then refresh tau
-  auto score_and_merge = [&](int ncand) {
-    tick(9);
-    if (ncand == 0) return;  // (uniform) nothing selected: lists and tau are unchanged
-    if (a.stats && threadIdx.x == 0) {
-      atomicAdd(a.stats, (unsigned long long)ncand);
-      if (!scored_any) atomicAdd(a.stats + 1, 1ull);
-    }
-    if (!query_loaded) {
-      if (threadIdx.x == 0) *reinterpret_cast<int *>(smem + L::OFF_QP32 + QP_FLAG) = 1;
-      __syncthreads();
-      load_query_to_lds(a.q, qi, smem, threadIdx.x, RS_WAVES * 64, L::OFF_QP32);
-      __syncthreads();
-      query_loaded = true;
-      tick(4);
-    }
-    scored_any = true;
-    // ||v1||^2 in fp32 for the error bound of the fast alignment (every wave for itself)
-    const float v1f = lane < NS ? reinterpret_cast<const float *>(smem + L::OFF_QP32 + QP_V1F)[lane] : 0.0f;
-    const float e1 = wave_sum_f32(v1f * v1f);
-    const int ngroups = (ncand + B - 1) / B;
-    if constexpr (TWO) {
-      {
-        // ---- phase A: k* and the fp32 preview pv of every candidate; the k-th smallest (pv + margin) over this
-        // round's candidates and the exact hits known so far is an upper bound of the final k-th best distance ----
-        float *pvs = reinterpret_cast<float *>(smem + L::OFF_PV);
-        double ud = ld;  // this wave's exact hits so far + its candidates' preview upper bounds
-        int ui = li, us = ls;
-        // (requesting the next candidate's registers one candidate ahead was tried: 48 more live registers, one
-        // workgroup per CU fewer, 3 % slower -- four waves per SIMD already hide the entry loads)
-        EntryRegs cur;
-        Touch tch;
-        for (int g = wave; g < ncand; g += RS_WAVES) {
-          const int64_t slot = cand[g];
-          const int64_t gidx = a.db.idx_base + slot * a.db.idx_stride;
-          float pv = INFINITY;  // ineligible: never scored
-          int ks = 0;
-          if (gidx < n_elig) {
-            if (g + RS_WAVES < ncand) touch_entry(a.db, cand[g + RS_WAVES], lane, tch);
-            load_entry(a.db, slot, lane, cur);
-            ks = phase_a<SO>(smem, wsm, lane, cur, L::OFF_QP32, e1, pv);
-            touch_keep(tch);  // phase A has waited for cur's registers, which were requested after the touch
-            const bool usable = (pv == pv) && fabsf(pv) < 3.0e38f;  // NaN / -inf: no preview; +inf: never a hit
-            if (usable) topk_insert(ud, ui, us, lane, a.k, (double)pv + (double)kPreviewMargin, (int)gidx, 0);
-            if (!(pv == pv)) pv = -INFINITY;  // no preview: phase B must look at it
-          }
-          if (lane == 0) {
-            pvs[g] = pv;
-            cand[g] = (int32_t)slot | (ks << RS_SLOT_BITS);
-          }
-        }
-        tick(5);
-        if (lane < a.k) {
-          rsx_sc_hit h;
-          h.dist = ud; h.index = ui; h.shift = us;
-          xch[wave * a.k + lane] = h;
-        }
-        __syncthreads();
-        if (wave == 0) {
-          const double t = wave_select_kth(xch, RS_WAVES * a.k, a.k, lane, nullptr);
-          if (lane == 0) *s_tau = t < tau ? t : tau;  // tau: the exact bound carried in
-        }
-        __syncthreads();
-        const double tau_ub = *s_tau;
-        tick(6);
-        // (each wave using only its OWN k-th smallest upper bound saves the two barriers but quadruples the exact
-        // evaluations: 43 instead of 11 per query, 7.5 instead of 4.2 ms per step)
-        // ---- phase B: exact evaluation of the candidates the previews cannot exclude ----
-        for (int g = wave; g < ncand; g += RS_WAVES) {
-          const float pv = pvs[g];
-          // this wave's own k-th exact distance tightens the test as it goes
-          const double kth_local = __shfl(ld, a.k - 1);
-          const double t_eff = kth_local < tau_ub ? kth_local : tau_ub;
-          if ((double)pv - (double)kPreviewMargin > t_eff) continue;  // exact >= pv - margin > k-th best: not in the top-k
-          const int32_t packed = cand[g];
-          const int64_t slot = packed & ((1 << RS_SLOT_BITS) - 1);
-          load_entry(a.db, slot, lane, cur);
-          double bd;
-          int bk;
-          phase_b<SO>(smem, wsm, lane, cur, (packed >> RS_SLOT_BITS) & 63, bd, bk);
-          if (a.stats && lane == 0) atomicAdd(a.stats + 2, 1ull);
-          const int64_t gidx = a.db.idx_base + slot * a.db.idx_stride;
-          if (bd < kBig) topk_insert(ld, li, ls, lane, a.k, bd, (int)gidx, bk);
-        }
-        __syncthreads();  // phase B of every wave is done with pvs / cand / xch before they are re-used
-        tick(7);
-      }
-    }
-    if constexpr (!TWO) {
-    for (int g = wave; g < ngroups; g += RS_WAVES) {
-      int64_t eslot[B];
-      bool evalid[B];
-#pragma unroll
-      for (int b = 0; b < B; b++) {
-        const int item = g * B + b;
-        evalid[b] = item < ncand;
-        eslot[b] = cand[evalid[b] ? item : (ncand - 1)];
-      }
-      double bd;
-      int bk;
-      // tau is finite from the second round on: candidates then leave after the alignment + fp32 preview unless
-      // they can still reach the top-k
-      pair_group<B, kRescorePreview, B == 1, SO>(a.db, smem, wsm, lane, eslot, bd, bk, tau, L::OFF_QP32, nullptr, e1);
-#pragma unroll
-      for (int b = 0; b < B; b++) {
-        const double dist = __shfl(bd, b * 8);
-        const int shift = __shfl(bk, b * 8);
-        if (!evalid[b]) continue;
-        const int64_t gidx = a.db.idx_base + eslot[b] * a.db.idx_stride;
-        if (gidx < n_elig && dist < kBig) topk_insert(ld, li, ls, lane, a.k, dist, (int)gidx, shift);
-      }
-    }
-    }
-    if (lane < a.k) {
-      rsx_sc_hit h;
-      h.dist = ld; h.index = li; h.shift = ls;
-      xch[wave * a.k + lane] = h;
-    }
-    __syncthreads();
-    if (wave == 0) {
-      const double t = wave_select_kth(xch, RS_WAVES * a.k, a.k, lane, nullptr);
-      if (lane == 0) {
-        *s_tau = t < tau_init ? t : tau_init;
-        *s_ncand = 0;
-      }
-    }
-    __syncthreads();
-    tau = *s_tau;
-    tick(8);
-  };
-
-  // block-wide append of this thread's candidate (wave ballot + one LDS atomic per wave)
-  auto append = [&](bool pass, int32_t slot) {
-    const unsigned long long bal = __ballot(pass);
-    int wbase = 0;
-    if (lane == 0 && bal) wbase = atomicAdd(s_ncand, __popcll(bal));
-    wbase = __shfl(wbase, 0);
-    if (pass) cand[wbase + __popcll(bal & ((1ull << lane) - 1ull))] = slot;
-  };
-
-  // ---- rounds over the short list ----
-  const int sl_cnt = a.sl_cnt[qi];
-  const RescoreEntry *sl = a.slist + (int64_t)qi * RESCORE_SHORTLIST_CAP;
-  const float *thr = a.thr + (int64_t)qi * RESCORE_THR_STRIDE;
-  const int32_t *rcnt = reinterpret_cast<const int32_t *>(thr) + RESCORE_NUM_THR;
-  const float t_cap = thr[RESCORE_NUM_THR - 1];
-  float lo = a.round_begin > 0 ? thr[a.round_begin - 1] : -INFINITY;
-  bool done = false;
-  const int r_end = a.round_end < RESCORE_NUM_THR ? a.round_end : RESCORE_NUM_THR;
-  for (int r = a.round_begin; r < r_end; r++) {
-    const float hi = thr[r];
-    if (!(lo < hi)) continue;  // empty range (uniform)
-    if ((double)lo - a.eps > tau) {  // (stage 2: the global tau may already exclude everything left)
-      done = true;
-      break;
-    }
-    // the short list is ordered by bin and the round edges are bin edges: round r is one contiguous range
-    // (bin 0, first in the list, also holds the NaN / -inf "always re-score" bounds)
-    const int i0 = r > 0 ? rcnt[r - 1] : 0, i1 = rcnt[r] < sl_cnt ? rcnt[r] : sl_cnt;
-    for (int c0 = i0; c0 < i1; c0 += RS_CAND_CAP) {  // (one chunk, unless a round is longer than the LDS candidate list)
-      const int c1 = c0 + RS_CAND_CAP < i1 ? c0 + RS_CAND_CAP : i1;
-      for (int i = c0 + threadIdx.x; i < c1; i += RS_WAVES * 64) {
-        const RescoreEntry e = sl[i];
-        append(!((double)e.lb - a.eps > tau), e.slot);
-      }
-      __syncthreads();
-      const int ncand = *s_ncand;
-      score_and_merge(ncand);
-    }
-    lo = hi;
-    if ((double)lo - a.eps > tau) {  // every remaining bound is >= lo: nothing can reach the top-k
-      done = true;
-      break;
-    }
-  }
-
-  // ---- entries beyond the short list (bound >= t_cap), only while tau admits them ----
-  if (!done && a.round_end > RESCORE_NUM_THR && t_cap < INFINITY && !((double)t_cap - a.eps > tau)) {
-    const lb_t *row = a.lb + (int64_t)qi * a.ld_lb;
-    const bool take_all = (t_cap == -INFINITY);  // empty short list: NaN bounds are here too
-    int64_t pos = 0;
-    while (pos < n_rows) {
-      // gather up to RS_CAND_CAP candidates, 1024 rows at a time
-      int ncand = 0;
-      while (pos < n_rows && ncand <= RS_CAND_CAP - RS_WAVES * 64) {
-        const int64_t i = pos + threadIdx.x;
-        bool pass = false;
-        if (i < n_rows) {
-          const float d = (float)row[i];
-          const bool beyond = take_all ? true : (d >= t_cap);
-          pass = beyond && (d != INFINITY) && !((double)d - a.eps > tau);
-        }
-        append(pass, (int32_t)i);
-        pos += RS_WAVES * 64;
-        __syncthreads();
-        ncand = *s_ncand;
-        __syncthreads();
-      }
-      score_and_merge(ncand);
-    }
-  }
-
-  // ---- output: top-k of everything this workgroup knows ----
-  if (!scored_any && a.seed) {  // nothing scored in this stage: the earlier hits are the answer
-    if (threadIdx.x < a.k) a.out[(int64_t)qi * a.k + threadIdx.x] = a.seed[(int64_t)qi * a.k + threadIdx.x];
-    return;
-  }
-  if (lane < a.k) {
-    rsx_sc_hit h;
-    h.dist = ld; h.index = li; h.shift = ls;
-    xch[wave * a.k + lane] = h;
-  }
-  __syncthreads();
-  if (wave == 0) wave_select_kth(xch, RS_WAVES * a.k, a.k, lane, a.out + (int64_t)qi * a.k);
-  if (timing && lane == 0) atomicAdd(a.stats + 10, (unsigned long long)(clock64() - t_begin));
-}
 
 template <int B, int W, int SO>
 int launch_pairs_t(const PairArgs &a, int gx, hipStream_t s) {
@@ -1380,25 +925,12 @@ int launch_pairs_t(const PairArgs &a, int gx, hipStream_t s) {
   return RSX_OK;
 }
 
-// kernel variant = entries per wave iteration (B) x register-occupancy target (W waves/SIMD);
-// RSX_SC_PAIR_VARIANT="B,W" overrides the tuned default (measured on MI355X)
-struct Variant { int b, w; };
-Variant pair_variant() {
-  static Variant v = [] {
-    Variant d{2, 4};
-    const char *e = rsx::exp_env("RSX_SC_PAIR_VARIANT");
-    int b = 0, w = 0;
-    if (e && sscanf(e, "%d,%d", &b, &w) == 2) {
-      if ((b == 1 && w == 4) || (b == 2 && (w == 3 || w == 4)) || (b == 4 && w == 2)) d = Variant{b, w};
-    }
-    return d;
-  }();
-  return v;
-}
-int pair_B() { return pair_variant().b; }
+// sc_pair_kernel's shape: entries per wave iteration (B) x register-occupancy target (W waves/SIMD), measured on MI355X
+// 
+constexpr int kPairB = 2, kPairW = 4;
 
 int choose_gx(int64_t n_items, int32_t nq) {
-  const int kB = pair_B();
+  const int kB = kPairB;
   const int64_t ngroups = (n_items + kB - 1) / kB;
   int64_t max_gx = (ngroups + 3) / 4;
   if (max_gx < 1) max_gx = 1;
@@ -1489,21 +1021,15 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
   a.nslots = gx * 4;
   PairProfiler *pp = (g_prof && g_prof->on && g_prof->ev && g_prof->used < PairProfiler::kMax) ? g_prof : nullptr;
   if (pp) RSX_HIP(hipEventRecord(pp->ev[2 * pp->used], s));
-  const Variant var = pair_variant();
-  static const bool one_phase = rsx::exp_env("RSX_SC_PAIR_ONE_PHASE") != nullptr;  // experiments: the round-1/2 kernel for top-k too
-  if (a.partial && !out_dist && !one_phase) {
+  if (a.partial && !out_dist) {  // top-k only: the two-phase kernel
     static_assert(PAIR2_LDS <= 48 * 1024, "within the default dynamic LDS limit: no per-device opt-in needed");
     RSX_SO_DISPATCH(db.sum_order, hipLaunchKernelGGL((sc_pair2_kernel<4, SO>), dim3(gx, q.nq), dim3(256), PAIR2_LDS, s, a));
     RSX_HIP(hipGetLastError());
-  } else if (db.sum_order != dev::SO_SSE2) {  // (the other shapes are tuning experiments of the default order)
+  } else {  // every pair's distance (out_dist), with or without the top-k
     int st = RSX_OK;
-    if (var.b != 2) return fail(RSX_ERR_BAD_ARG, "RSX_SC_PAIR_VARIANT applies to the default summation order only");
-    RSX_SO_DISPATCH(db.sum_order, st = (launch_pairs_t<2, 4, SO>(a, gx, s)));
+    RSX_SO_DISPATCH(db.sum_order, st = (launch_pairs_t<kPairB, kPairW, SO>(a, gx, s)));
     RSX_TRY(st);
-  } else if (var.b == 1) RSX_TRY((launch_pairs_t<1, 4, dev::SO_SSE2>(a, gx, s)));
-  else if (var.b == 2 && var.w == 3) RSX_TRY((launch_pairs_t<2, 3, dev::SO_SSE2>(a, gx, s)));
-  else if (var.b == 2) RSX_TRY((launch_pairs_t<2, 4, dev::SO_SSE2>(a, gx, s)));
-  else RSX_TRY((launch_pairs_t<4, 2, dev::SO_SSE2>(a, gx, s)));
+  }
   if (pp) {
     RSX_HIP(hipEventRecord(pp->ev[2 * pp->used + 1], s));
     pp->used++;
@@ -1517,170 +1043,10 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
   return RSX_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// sc_walk_kernel: exact re-scoring behind the filter, ONE WAVE per query (single-GPU path).  The short
-// list arrives ordered by bound (by histogram bin, sc_select_kernel), so the wave walks it in ascending
-// order: every candidate sees the tau (k-th best exact distance) of everything before it -- no rounds,
-// no barriers, no cross-wave merges -- and from the k-th hit on most candidates leave pair_group after
-// the alignment + fp32 preview.  It stops at the first bin whose lower edge minus eps exceeds tau.
-// Entries beyond the short list (bound >= t_cap) are scanned from the bounds row only while tau still
-// admits them.  Output: the final top-k, sorted by (dist, global index), padded {1e7,0,0}.
-// LDS per wave: query images (fp64 + fp32 preview) + one pair_group region = 19.9 KB -> 8 waves per CU,
-// 2 per SIMD, 256 registers each (the preview does not spill).
-// ------------------------------------------------------------------------------------------
-struct WalkLds {
-  static constexpr int OFF_QP32 = OFF_WAVES + ENT_SIZE;
-  static constexpr int SIZE = OFF_QP32 + QP_SIZE;
-};
-
 __device__ __forceinline__ float bound_bin_lo(float lb) {  // lower edge of the 2048-bin histogram bin of lb
   if (!(lb > 0.0f)) return -INFINITY;
   const float x = lb * 2048.0f;
   return x >= 2047.0f ? 2047.0f / 2048.0f : floorf(x) / 2048.0f;
-}
-
-template <int SO>
-__global__ __launch_bounds__(64, 2) void sc_walk_kernel(RescoreArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x;
-  const int qi = blockIdx.x;
-  char *wsm = smem + OFF_WAVES;
-
-  int64_t n_elig = a.n_eligible;
-  if (a.q_elig) {
-    const int64_t e = a.q_elig[qi];
-    n_elig = e < n_elig ? e : n_elig;
-  }
-  int64_t n_rows = 0;  // local slots [0, n_rows) are the eligible ones
-  if (n_elig > a.db.idx_base) {
-    n_rows = (n_elig - a.db.idx_base + a.db.idx_stride - 1) / a.db.idx_stride;
-    n_rows = n_rows < a.n_items ? n_rows : a.n_items;
-  }
-
-  double ld = INFINITY;  // sorted top-k, one record per lane
-  int li = 0x7fffffff, ls = 0;
-  double tau = INFINITY;
-  bool query_loaded = false;
-
-  auto ensure_query = [&]() {
-    if (!query_loaded) {
-      if (lane == 0) *reinterpret_cast<int *>(smem + WalkLds::OFF_QP32 + QP_FLAG) = 1;
-      load_query_to_lds(a.q, qi, smem, lane, 64, WalkLds::OFF_QP32);
-      query_loaded = true;
-    }
-  };
-  // score one entry whose registers are already loaded (or being loaded)
-  auto score_regs = [&](int32_t slot, const EntryRegs &er) {
-    ensure_query();
-    const int64_t eslot[1] = {slot};
-    double bd;
-    int bk;
-    pair_group<1, true, false, SO>(a.db, smem, wsm, lane, eslot, bd, bk, a.round_begin ? INFINITY : tau, WalkLds::OFF_QP32, &er);
-    const double dist = __shfl(bd, 0);
-    const int shift = __shfl(bk, 0);
-    const int64_t gidx = a.db.idx_base + (int64_t)slot * a.db.idx_stride;
-    if (gidx < n_elig && dist < kBig) {
-      topk_insert(ld, li, ls, lane, a.k, dist, (int)gidx, shift);
-      tau = __shfl(ld, a.k - 1);  // +inf until k hits exist
-    }
-  };
-  auto score = [&](int32_t slot) {
-    EntryRegs er;
-    load_entry(a.db, slot, lane, er);
-    score_regs(slot, er);
-  };
-
-  // ---- the short list, ascending bin order; the registers of entry i+1 are requested before entry i is
-  // scored, so their global-memory latency hides behind its arithmetic ----
-  const int sl_cnt = a.sl_cnt[qi];
-  const RescoreEntry *sl = a.slist + (int64_t)qi * RESCORE_SHORTLIST_CAP;
-  const float t_cap = a.thr[(int64_t)qi * RESCORE_THR_STRIDE + (RESCORE_NUM_THR - 1)];
-  bool done = false;
-  for (int base = 0; base < sl_cnt && !done; base += 64) {
-    const int n_here = (sl_cnt - base < 64) ? (sl_cnt - base) : 64;
-    RescoreEntry mine;  // one coalesced read per 64 candidates
-    mine.lb = INFINITY;
-    mine.slot = 0;
-    if (lane < n_here) mine = sl[base + lane];
-    EntryRegs cur, nxt;
-    load_entry(a.db, __shfl(mine.slot, 0), lane, cur);
-    for (int i = 0; i < n_here; i++) {
-      const float lb = __shfl(mine.lb, i);
-      const int32_t slot = __shfl(mine.slot, i);
-      if (i + 1 < n_here) load_entry(a.db, __shfl(mine.slot, i + 1), lane, nxt);
-      // every later entry sits in this bin or a higher one
-      if ((double)bound_bin_lo(lb) - a.eps > tau) {
-        done = true;
-        break;
-      }
-      if (!((double)lb - a.eps > tau)) score_regs(slot, cur);  // NaN / -inf bounds: always scored
-      cur = nxt;
-    }
-  }
-
-  // ---- entries beyond the short list (bound >= t_cap), only while tau admits them ----
-  if (!done && t_cap < INFINITY && !((double)t_cap - a.eps > tau)) {
-    const lb_t *row = a.lb + (int64_t)qi * a.ld_lb;
-    const bool take_all = (t_cap == -INFINITY);  // empty short list: NaN bounds are here too
-    for (int64_t pos = 0; pos < n_rows; pos += 64) {
-      const int64_t i = pos + lane;
-      const float d = (i < n_rows) ? (float)row[i] : INFINITY;
-      const bool beyond = take_all ? true : (d >= t_cap);
-      unsigned long long bal = __ballot((i < n_rows) && beyond && (d != INFINITY));
-      while (bal) {
-        const int l = __ffsll((long long)bal) - 1;
-        bal &= bal - 1;
-        const float dl = __shfl(d, l);
-        if ((double)dl - a.eps > tau) continue;
-        score((int32_t)(pos + l));
-      }
-    }
-  }
-
-  if (lane < a.k) {
-    rsx_sc_hit h;
-    if (ld == INFINITY) {
-      h.dist = kBig; h.index = 0; h.shift = 0;
-    } else {
-      h.dist = ld; h.index = li; h.shift = ls;
-    }
-    a.out[(int64_t)qi * a.k + lane] = h;
-  }
-}
-
-int launch_walk(const DbView &db, const QueryView &q, const lb_t *lb, int64_t ld_lb, int64_t n_items,
-                int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
-                const float *thr, double eps, rsx_sc_hit *d_out, int32_t k, hipStream_t s) {
-  if (q.nq <= 0) return RSX_OK;
-  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k=%d out of range [1,%d]", k, RSX_SC_MAX_TOPK);
-  if (db.sum_order != dev::SO_SSE2) return fail(RSX_ERR_BAD_ARG, "the walk kernel (an experiment) exists for the default summation order only");
-  static bool attr_set = false;
-  if (!attr_set) {
-    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sc_walk_kernel<dev::SO_SSE2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                WalkLds::SIZE));
-    attr_set = true;
-  }
-  RescoreArgs a;
-  a.db = db;
-  a.q = q;
-  a.lb = lb;
-  a.ld_lb = ld_lb;
-  a.n_items = n_items;
-  a.n_eligible = n_eligible < 0 ? INT64_MAX : n_eligible;
-  a.q_elig = q_elig;
-  a.slist = slist;
-  a.sl_cnt = sl_cnt;
-  a.thr = thr;
-  a.out = d_out;
-  a.tau_src = nullptr;
-  a.seed = nullptr;
-  a.eps = eps;
-  a.k = k;
-  a.round_begin = rsx::exp_env("RSX_WALK_NOPREVIEW") ? 1 : 0;  // experiment: disable the pruning preview
-  a.round_end = RESCORE_ALL_ROUNDS;
-  hipLaunchKernelGGL(sc_walk_kernel<dev::SO_SSE2>, dim3(q.nq), dim3(64), WalkLds::SIZE, s, a);
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1689,12 +1055,14 @@ int launch_walk(const DbView &db, const QueryView &q, const lb_t *lb, int64_t ld
 // left per query is: pick the k-th smallest preview upper bound (an upper bound of the final k-th best distance), and
 // evaluate exactly -- phase B, ~13 entries per query -- the few entries whose preview lower bound does not exceed it, in
 // ascending order of that lower bound so that the exact k-th best takes over as early as possible.  No barriers, no
-// merges between waves, no imbalance between them (the 4-wave workgroup of sc_rescore_kernel spent 64 % of its wave
+// merges between waves, no imbalance between them (the 4-wave workgroup this kernel replaced spent 64 % of its wave
 // cycles waiting once its phase A was gone), and 9.0 KiB of LDS per query (the query image stays in fp32 and is
 // converted on the fly) instead of 40 KiB: 12 queries per CU in flight instead of 4.
 // Entries without k* (alignment not unique within the window kernel's error bound, or beyond its WINDOW_P positions)
 // get the exact fp64 alignment first; their preview is still a valid LOWER bound (minimum over the union of the candidate
-// windows), so most of them are never touched.  Same stage interface as sc_rescore_kernel (rounds, tau_src, seed).
+// windows), so most of them are never touched.  A launch can cover some rounds of the list only (round_begin /
+// round_end), start from a tau bound over more shards (tau_src) and merge hits of an earlier stage (seed): the two stages
+// of a DB shard.
 // ------------------------------------------------------------------------------------------
 constexpr int RW_CH = (WINDOW_P + 63) / 64;  // window records per lane
 
@@ -2052,19 +1420,6 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
   }
 }
 
-template <int B, int NW, int W, bool TWO = false, int SO = dev::SO_SSE2>
-static int launch_rescore_t(const RescoreArgs &a, hipStream_t s) {
-  static bool attr_set = false;
-  constexpr int lds = RescoreLds<B, NW>::SIZE;
-  if (!attr_set) {
-    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sc_rescore_kernel<B, NW, W, TWO, SO>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((sc_rescore_kernel<B, NW, W, TWO, SO>), dim3(a.q.nq), dim3(NW * 64), lds, s, a);
-  return RSX_OK;
-}
-
 int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t ld_lb, int64_t n_items,
                    int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
                    const float *thr, double eps, int32_t round_begin, int32_t round_end, const rsx_sc_hit *tau_src,
@@ -2072,15 +1427,6 @@ int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t
                    const WindowPreview *win) {
   if (q.nq <= 0) return RSX_OK;
   if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k=%d out of range [1,%d]", k, RSX_SC_MAX_TOPK);
-  // workgroup shape (entries per wave iteration, waves, waves/SIMD); RSX_SC_RESCORE_VARIANT picks one:
-  // 0: (1, 4, 4) four workgroups per CU (default)   1: (1, 16, 4)   2: (2, 12, 3)   3: (2, 6, 3)   4: (1, 8, 4) two per CU
-  // 5: (1, 6, 4).  Measured on the bench (10k DB, 8192 queries, ms per step): 4.86 / 6.9 / 6.8 / 7.7 / 5.34 / 5.75 --
-  // four 4-wave workgroups per CU keep more queries in flight, so one query's barriers and merge hide behind
-  // the others' scoring
-  static const int variant = [] {
-    const char *e = rsx::exp_env("RSX_SC_RESCORE_VARIANT");
-    return (e && *e) ? atoi(e) : 0;
-  }();
   RescoreArgs a;
   a.db = db;
   a.q = q;
@@ -2101,40 +1447,7 @@ int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t
   a.round_end = round_end;
   a.stats = d_stats;
   a.win = win;
-  static const bool no_two_phase = [] {
-    const char *e = rsx::exp_env("RSX_SC_TWO_PHASE");  // experiments: 0 = the one-pass scoring of round 1
-    return e && e[0] == '0';
-  }();
-  a.two_phase = (!no_two_phase && variant == 0 && n_items < (1ll << RS_SLOT_BITS)) ? 1 : 0;
-  // with the window records of sc_window.hip: one wave per query (RSX_SC_RESCORE=rounds, experiments: the 4-wave workgroup)
-  static const bool force_rounds = [] {
-    const char *e = rsx::exp_env("RSX_SC_RESCORE");
-    return e && e[0] == 'r';
-  }();
-  if (win && !force_rounds) {
-    RSX_SO_DISPATCH(db.sum_order, hipLaunchKernelGGL(sc_rescore_wave_kernel<SO>, dim3(q.nq), dim3(64), WaveLds::SIZE, s, a));
-    RSX_HIP(hipGetLastError());
-    return RSX_OK;
-  }
-  if (db.sum_order != dev::SO_SSE2) {  // (the other workgroup shapes are tuning experiments of the default order)
-    int st = RSX_OK;
-    if (a.two_phase) RSX_SO_DISPATCH(db.sum_order, st = (launch_rescore_t<1, 4, 4, true, SO>(a, s)));
-    else RSX_SO_DISPATCH(db.sum_order, st = (launch_rescore_t<1, 4, 4, false, SO>(a, s)));
-    RSX_TRY(st);
-    RSX_HIP(hipGetLastError());
-    return RSX_OK;
-  }
-  switch (variant) {
-    case 1: RSX_TRY((launch_rescore_t<1, 16, 4>(a, s))); break;
-    case 2: RSX_TRY((launch_rescore_t<2, 12, 3>(a, s))); break;
-    case 3: RSX_TRY((launch_rescore_t<2, 6, 3>(a, s))); break;
-    case 4: RSX_TRY((launch_rescore_t<1, 8, 4>(a, s))); break;
-    case 5: RSX_TRY((launch_rescore_t<1, 6, 4>(a, s))); break;
-    default:
-      if (a.two_phase) RSX_TRY((launch_rescore_t<1, 4, 4, true>(a, s)));
-      else RSX_TRY((launch_rescore_t<1, 4, 4>(a, s)));
-      break;
-  }
+  RSX_SO_DISPATCH(db.sum_order, hipLaunchKernelGGL(sc_rescore_wave_kernel<SO>, dim3(q.nq), dim3(64), WaveLds::SIZE, s, a));
   RSX_HIP(hipGetLastError());
   return RSX_OK;
 }

@@ -2,7 +2,7 @@
 //
 // Where it sits.  The lower-bound filter (sc_spec.hip / sc_filter.hip) gives every (query, entry) pair the minimum of
 // the column-cosine distance over ALL 60 shifts; sc_select_kernel turns a query's row of bounds into a short list in
-// ascending-bound order; sc_rescore_kernel then needs, for every short-list entry it looks at,
+// ascending-bound order; the re-scoring needs, for every short-list entry it looks at,
 //     k*  = the sector-key alignment of the pair (fastAlignUsingVkey, SC.cpp:93-113) and
 //     pv ~= dist(query, entry) = min over the 7 shifts k* - 3 .. k* + 3 of d_k (SC.cpp:116-148)
 // to decide which few entries deserve the exact fp64 evaluation.  Rounds 1-2 computed both on the VALU, one entry per
@@ -108,15 +108,9 @@ struct WindowArgs {
   WindowPreview *out;
   double eps;  // the filter's error budget, as the re-scoring kernel applies it to a bound
   int32_t k;
-  int32_t head;   // |head| = list positions pass 1 always processes (a multiple of 32, <= WINDOW_HEAD); negative: the
-                  // positions behind them get "no record" (stage 1 of a DB shard: it scores the head only)
 };
 
-
-// TAIL (stage 2 of a DB shard whose stage 1 scored the head only): no pass 1; the positions behind the head whose bound can
-// still reach `tau` -- the k-th best distance of the merged stage-1 lists, known only after the exchange -- get their records now
-template <bool TAIL>
-__device__ __forceinline__ void window_body(const WindowArgs &a, const rsx_sc_hit *__restrict__ global) {
+__global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float s_ub[WINDOW_HEAD];
   __shared__ int s_pos[WINDOW_P];
@@ -220,30 +214,15 @@ __device__ __forceinline__ void window_body(const WindowArgs &a, const rsx_sc_hi
     return (have && kstar >= 0 && pv < 3.0e38f) ? pv + WINDOW_MARGIN : INFINITY;  // NaN fails the compare
   };
 
-  const int head = a.head < 0 ? -a.head : a.head;
+  // ---- pass 1: the head of the list ----
   float tau_ub;
-  if constexpr (TAIL) {
-    if (sl_cnt <= head) return;  // uniform
-    const double t = global[(int64_t)qi * a.k + (a.k - 1)].dist;  // (1e7 while fewer than k entries are known: everything passes)
-    tau_ub = __double2float_ru(t);
-  } else {
-    // ---- pass 1: the head of the list ----
-    const int cnt1 = sl_cnt < head ? sl_cnt : head;
+  {
+    const int cnt1 = sl_cnt < WINDOW_HEAD ? sl_cnt : WINDOW_HEAD;
     float ub = INFINITY;
     if (wave * 32 < cnt1) ub = do_group(wave * 32 + n, wave * 32 + n < cnt1, wave * 32);
     if (hh == 0) s_ub[wave * 32 + n] = ub;
     __syncthreads();
-    if (sl_cnt <= head) return;  // uniform
-    if (a.head < 0) {  // (uniform) the rest of the list: no record
-      const int lim = sl_cnt < WINDOW_P ? sl_cnt : WINDOW_P;
-      for (int pos = head + (int)threadIdx.x; pos < lim; pos += 256) {
-        WindowPreview o;
-        o.pv = __builtin_nanf("");
-        o.ks = -2;
-        a.out[(int64_t)qi * WINDOW_P + pos] = o;
-      }
-      return;
-    }
+    if (sl_cnt <= WINDOW_HEAD) return;  // uniform
 
     // ---- the k-th smallest upper bound of the head: an upper bound of the final k-th best distance.  Only entries whose
     // filter bound does not exceed it can matter to the re-scoring kernel (whose own bound is at least as tight) ----
@@ -267,13 +246,12 @@ __device__ __forceinline__ void window_body(const WindowArgs &a, const rsx_sc_hi
       const float c0 = __shfl(v0, b0 ? __ffsll((long long)b0) - 1 : 0), c1 = __shfl(v1, b1 ? __ffsll((long long)b1) - 1 : 0);
       tau_ub = b0 ? c0 : c1;  // ranks are a permutation of 0..127: exactly one of the two ballots has a bit
     }
-
   }
   // ---- pass 2: list positions WINDOW_HEAD .. WINDOW_P - 1 whose bound can still matter; the others get "no record" ----
   if (wave == 0) {
     int n2 = 0;
     const int lim = sl_cnt < WINDOW_P ? sl_cnt : WINDOW_P;
-    for (int p0 = head; p0 < lim; p0 += 64) {
+    for (int p0 = WINDOW_HEAD; p0 < lim; p0 += 64) {
       const int pos = p0 + lane;
       bool pass = false;
       if (pos < lim) {
@@ -300,9 +278,6 @@ __device__ __forceinline__ void window_body(const WindowArgs &a, const rsx_sc_hi
   }
 }
 
-__global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) { window_body<false>(a, nullptr); }
-__global__ __launch_bounds__(256, WIN_OCC) void sc_window_tail_kernel(WindowArgs a, const rsx_sc_hit *__restrict__ global) { window_body<true>(a, global); }
-
 }  // namespace
 
 size_t window_qimg_bytes(int32_t nq) { return (size_t)nq * (FILTER_QIMG_BYTES + WINDOW_QK_BYTES) + 1024; }
@@ -316,7 +291,7 @@ int launch_window_db_keys(const double *vkey, int64_t first, int64_t count, void
 }
 
 int launch_window(const DbView &db, const QueryView &q, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt,
-                  int32_t k, double eps, WindowPreview *out, hipStream_t s, int32_t head_only) {
+                  int32_t k, double eps, WindowPreview *out, hipStream_t s) {
   if (q.nq <= 0) return RSX_OK;
   char *img = static_cast<char *>(qimg);
   char *kimg = img + (size_t)q.nq * FILTER_QIMG_BYTES;
@@ -335,38 +310,7 @@ int launch_window(const DbView &db, const QueryView &q, void *qimg, const Rescor
   a.out = out;
   a.eps = eps;
   a.k = k < 1 ? 1 : (k > WINDOW_HEAD ? WINDOW_HEAD : k);
-  a.head = WINDOW_HEAD;
-  if (head_only > 0) {  // a DB shard's stage 1 scores only its first `head_only` list positions
-    int32_t hd = (head_only + 31) / 32 * 32;
-    if (hd > WINDOW_HEAD) hd = WINDOW_HEAD;
-    a.head = -hd;
-  }
   hipLaunchKernelGGL(sc_window_kernel, dim3((unsigned)q.nq), dim3(256), W_LDS, s, a);
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
-}
-
-// stage 2 of a DB shard: the records behind the head that stage 1 left out, for the list positions whose bound can still reach
-// the k-th best distance of the merged stage-1 lists (d_global [nq][k]).  The query images of stage 1 are still in qimg.
-int launch_window_tail(const DbView &db, int32_t nq, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt, int32_t k, double eps,
-                       WindowPreview *out, int32_t head, const rsx_sc_hit *d_global, hipStream_t s) {
-  if (nq <= 0) return RSX_OK;
-  char *img = static_cast<char *>(qimg);
-  WindowArgs a;
-  a.hnR = static_cast<const char *>(db.hnR);
-  a.vk16 = static_cast<const char *>(db.vk16);
-  a.vk_n = db.vk_n;
-  a.cmask = reinterpret_cast<const u64 *>(db.cmask);
-  a.qimg = img;
-  a.qkimg = img + (size_t)nq * FILTER_QIMG_BYTES;
-  a.slist = slist;
-  a.sl_cnt = sl_cnt;
-  a.out = out;
-  a.eps = eps;
-  a.k = k < 1 ? 1 : (k > WINDOW_HEAD ? WINDOW_HEAD : k);
-  int32_t hd = (head + 31) / 32 * 32;
-  a.head = hd > WINDOW_HEAD ? WINDOW_HEAD : hd;
-  hipLaunchKernelGGL(sc_window_tail_kernel, dim3((unsigned)nq), dim3(256), W_LDS, s, a, d_global);
   RSX_HIP(hipGetLastError());
   return RSX_OK;
 }

@@ -316,7 +316,7 @@ def test_full_size_100k_properties(sc, oracle):
 
 def test_rescore_beyond_the_short_list(sc, oracle):
     """Duplicate-heavy databases: more equal bounds than the 2048-entry short list holds, so the
-    re-scoring has to fall back to scanning the bound row (sc_rescore_kernel's rest path)."""
+    re-scoring has to fall back to scanning the bound row (sc_rescore_wave_kernel's pass beyond the short list)."""
     rng = np.random.default_rng(17)
     base = synth.random_descriptors(40, 8, binary=False)
     rand = make_db(41, 900, binary=False)

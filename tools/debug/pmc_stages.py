@@ -1,4 +1,4 @@
-"""staged bring-up of csrc/pmc.hip: one stage per process (tools/gpu_pmc_debug.sh runs each under a short timeout)"""
+"""staged bring-up of csrc/pmc.hip: one stage per process (a job script runs each under a short timeout)"""
 import os
 import sys
 import time
