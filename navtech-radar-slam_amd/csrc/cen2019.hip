@@ -1694,11 +1694,10 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void cen_pack(Scal *scal, int rows
 struct rsx_cen2019 {
   int device = 0, rows = 0, cols = 0;
   std::mutex mu;
-  hipStream_t stream = nullptr;
+  rsx::Stream stream;
   rsx::DevBuf img, scal, hist, list, row_out, row_n, targets, xy, az, counts, opener, row_runs, row_nruns, markbits, wavemax, negmax;
   rsx::DevBuf one;          // single-scan entry: [count | targets | xy] in one piece, read back with one copy
-  void *one_host = nullptr;  // its pinned mirror
-  size_t one_host_bytes = 0;
+  rsx::PinnedBuf one_host;  // its pinned mirror
 };
 
 using rsx::fail;
@@ -1813,21 +1812,16 @@ int rsx_cen2019_create(int device, int32_t rows, int32_t cols, rsx_cen2019 **out
   if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
   *out = nullptr;
   if (rows < 1 || rows > 1024 || cols < 2 || cols > 16384) return fail(RSX_ERR_BAD_ARG, "image shape %d x %d unsupported", rows, cols);
-  int ndev = rsx_device_count();
-  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
-  rsx_cen2019 *h = new (std::nothrow) rsx_cen2019();
+  RSX_TRY(rsx::check_device(device));
+  std::unique_ptr<rsx_cen2019> h(new (std::nothrow) rsx_cen2019());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->device = device;
   h->rows = rows;
   h->cols = cols;
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  if (e == hipSuccess) e = h->stream.create();
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -1835,10 +1829,6 @@ int rsx_cen2019_destroy(rsx_cen2019 *h) try {
   if (!h) return RSX_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->one_host) (void)hipHostFree(h->one_host);
-  h->one.release();
-  for (rsx::DevBuf *b : {&h->img, &h->scal, &h->hist, &h->list, &h->row_out, &h->row_n, &h->targets, &h->xy, &h->az, &h->counts, &h->opener, &h->row_runs, &h->row_nruns, &h->markbits, &h->wavemax, &h->negmax}) b->release();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -1885,13 +1875,7 @@ int rsx_cen2019_extract_batch(rsx_cen2019 *h, const uint8_t *imgs, int32_t n_ima
     const size_t kp = (size_t)mt * 8, total = 256 + 2 * kp;
     RSX_TRY(h->img.reserve(ibytes, s, false));
     RSX_TRY(h->one.reserve(total, s, false));
-    if (total > h->one_host_bytes) {
-      if (h->one_host) (void)hipHostFree(h->one_host);
-      h->one_host = nullptr;
-      h->one_host_bytes = 0;
-      RSX_HIP(hipHostMalloc(&h->one_host, total, hipHostMallocDefault));
-      h->one_host_bytes = total;
-    }
+    RSX_TRY(h->one_host.reserve(total));
     RSX_HIP(hipMemcpyAsync(h->img.p, imgs, ibytes, hipMemcpyHostToDevice, s));
     const float *d_az = nullptr;
     if (azimuths) {
@@ -1905,15 +1889,15 @@ int rsx_cen2019_extract_batch(rsx_cen2019 *h, const uint8_t *imgs, int32_t n_ima
                            reinterpret_cast<int *>(d_one), s));
     // the count and the first 16 384 keypoint slots (a scan yields ~3 000) in one copy; a longer list takes a second one
     const size_t first = mt < 16384 ? (size_t)mt : 16384, fb = first * 8;
-    RSX_HIP(hipMemcpyAsync(h->one_host, d_one, 256 + fb, hipMemcpyDeviceToHost, s));
-    if (out_xy) RSX_HIP(hipMemcpyAsync(static_cast<char *>(h->one_host) + 256 + kp, d_one + 256 + kp, fb, hipMemcpyDeviceToHost, s));
+    RSX_HIP(hipMemcpyAsync(h->one_host.p, d_one, 256 + fb, hipMemcpyDeviceToHost, s));
+    if (out_xy) RSX_HIP(hipMemcpyAsync(static_cast<char *>(h->one_host.p) + 256 + kp, d_one + 256 + kp, fb, hipMemcpyDeviceToHost, s));
     RSX_HIP(hipStreamSynchronize(s));
-    const char *hp = static_cast<const char *>(h->one_host);
+    const char *hp = static_cast<const char *>(h->one_host.p);
     const unsigned cnt = *reinterpret_cast<const unsigned *>(hp);
     out_counts[0] = (int32_t)cnt;
     const unsigned w = cnt < (unsigned)max_targets ? cnt : (unsigned)max_targets;
     if (w > first) {
-      RSX_HIP(hipMemcpyAsync(h->one_host, d_one, out_xy ? total : 256 + kp, hipMemcpyDeviceToHost, s));
+      RSX_HIP(hipMemcpyAsync(h->one_host.p, d_one, out_xy ? total : 256 + kp, hipMemcpyDeviceToHost, s));
       RSX_HIP(hipStreamSynchronize(s));
     }
     if (w) {

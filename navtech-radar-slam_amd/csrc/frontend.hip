@@ -719,7 +719,7 @@ struct rsx_frontend {
   int device = 0, rows = 0, cols = 0, W = 0;
   double cart_res = 0.0;
   std::mutex mu;
-  hipStream_t stream = nullptr;
+  rsx::Stream stream;
   rsx::DevBuf img, map_rb, map_th, az1, cart, tmp, blur, tables, uv, desc, valid, q, qv, t, tv, m_idx, m_d1, m_d2, vidx, vcount;
   // the map depends on the radar's range resolution and azimuth grid: rebuilt only when they change
   double map_radar_res = -1.0;
@@ -811,10 +811,8 @@ int rsx_frontend_create(int device, int32_t rows, int32_t cols, const rsx_fronte
   if (params) dp = *params;
   if (rows < 2 || cols < 2 || dp.cart_pixel_width < 2 * BORDER + 1 || dp.cart_pixel_width > 8192 || !(dp.cart_resolution > 0.0f))
     return fail(RSX_ERR_BAD_ARG, "bad image shape / Cartesian parameters");
-  const int ndev = rsx_device_count();
-  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
-  rsx_frontend *h = new (std::nothrow) rsx_frontend();
+  RSX_TRY(rsx::check_device(device));
+  std::unique_ptr<rsx_frontend> h(new (std::nothrow) rsx_frontend());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->device = device;
   h->rows = rows;
@@ -825,29 +823,17 @@ int rsx_frontend_create(int device, int32_t rows, int32_t cols, const rsx_fronte
   h->tiles = (dp.flags & RSX_FRONTEND_TILES) != 0;
   h->exact_az = (dp.flags & RSX_FRONTEND_EXACT_AZIMUTH) != 0;
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  }
+  if (e == hipSuccess) e = h->stream.create();
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
   const size_t npx = (size_t)h->W * h->W;
-  int st = RSX_OK;
-  for (rsx::DevBuf *b : {&h->map_rb, &h->map_th, &h->cart, &h->tmp, &h->blur})
-    if (st == RSX_OK) st = b->reserve(npx * sizeof(float), h->stream, false);
-  if (st == RSX_OK) st = h->tables.reserve(TAB_BYTES, h->stream, false);
-  if (st == RSX_OK) {
-    std::vector<uint8_t> tab(TAB_BYTES, 0);
-    build_tables(reinterpret_cast<float *>(&tab[TAB_GAUSS]), reinterpret_cast<float *>(&tab[TAB_DIR]),
-                 reinterpret_cast<int8_t *>(&tab[TAB_PAIRS]));
-    build_disc(reinterpret_cast<int8_t *>(&tab[TAB_DISC]));
-    e = hipMemcpy(h->tables.p, tab.data(), TAB_BYTES, hipMemcpyHostToDevice);
-    if (e != hipSuccess) st = fail(RSX_ERR_HIP, "tables: %s", hipGetErrorString(e));
-  }
-  if (st != RSX_OK) {
-    rsx_frontend_destroy(h);
-    return st;
-  }
-  *out = h;
+  for (rsx::DevBuf *b : {&h->map_rb, &h->map_th, &h->cart, &h->tmp, &h->blur}) RSX_TRY(b->reserve(npx * sizeof(float), h->stream, false));
+  RSX_TRY(h->tables.reserve(TAB_BYTES, h->stream, false));
+  std::vector<uint8_t> tab(TAB_BYTES, 0);
+  build_tables(reinterpret_cast<float *>(&tab[TAB_GAUSS]), reinterpret_cast<float *>(&tab[TAB_DIR]), reinterpret_cast<int8_t *>(&tab[TAB_PAIRS]));
+  build_disc(reinterpret_cast<int8_t *>(&tab[TAB_DISC]));
+  e = hipMemcpy(h->tables.p, tab.data(), TAB_BYTES, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "tables: %s", hipGetErrorString(e));
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -855,10 +841,6 @@ int rsx_frontend_destroy(rsx_frontend *h) try {
   if (!h) return RSX_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (rsx::DevBuf *b : {&h->img, &h->map_rb, &h->map_th, &h->az1, &h->cart, &h->tmp, &h->blur, &h->tables, &h->uv, &h->desc, &h->valid, &h->q,
-                         &h->qv, &h->t, &h->tv, &h->m_idx, &h->m_d1, &h->m_d2, &h->vidx, &h->vcount})
-    b->release();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL

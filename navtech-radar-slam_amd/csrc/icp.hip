@@ -650,9 +650,9 @@ __global__ __launch_bounds__(PI_NT) void icp_persistent_kernel(IcpArgs A) {
 struct rsx_icp {
   int device = 0;
   std::mutex mu;
-  hipStream_t stream = nullptr;
+  rsx::Stream stream;
   rsx::DevBuf src, tgt, cur, best, guess, bar;
-  void *state_host = nullptr;  // pinned, device-visible: the kernel writes the result there (no read-back to enqueue)
+  rsx::PinnedBuf state_host;  // pinned, device-visible: the kernel writes the result there (no read-back to enqueue)
   int n_wg = 0;  // workgroups of the persistent kernel: one per CU, at most PI_MAX_G
 };
 
@@ -673,19 +673,14 @@ int rsx_icp_default_params(rsx_icp_params *p) try {
 int rsx_icp_create(int device, rsx_icp **out) try {
   if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
   *out = nullptr;
-  int ndev = rsx_device_count();
-  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
-  rsx_icp *h = new (std::nothrow) rsx_icp();
+  RSX_TRY(rsx::check_device(device));
+  std::unique_ptr<rsx_icp> h(new (std::nothrow) rsx_icp());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->device = device;
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  if (e == hipSuccess) e = h->stream.create();
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -693,9 +688,6 @@ int rsx_icp_destroy(rsx_icp *h) try {
   if (!h) return RSX_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (rsx::DevBuf *b : {&h->src, &h->tgt, &h->cur, &h->best, &h->guess, &h->bar}) b->release();
-  if (h->state_host) (void)hipHostFree(h->state_host);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -751,7 +743,7 @@ int align_device_counts_locked(rsx_icp *h, const void *d_src, int64_t n_s, const
   const size_t cap = (size_t)(n_s > 0 ? n_s : 1);
   RSX_TRY(h->cur.reserve(2 * cap * 16, s, false));
   RSX_TRY(h->best.reserve(3 * cap * 8, s, false));
-  if (!h->state_host) RSX_HIP(hipHostMalloc(&h->state_host, sizeof(IcpState), hipHostMallocDefault));
+  RSX_TRY(h->state_host.reserve(sizeof(IcpState)));
   RSX_TRY(h->guess.reserve(64, s, false));
   if (!h->bar.p) {
     RSX_TRY(h->bar.reserve(rsx::grid::BYTES, s, false));
@@ -771,7 +763,7 @@ int align_device_counts_locked(rsx_icp *h, const void *d_src, int64_t n_s, const
   A.guess = guess ? h->guess.as<float>() : nullptr;
   A.cur = h->cur.as<float4>();
   A.best = h->best.as<unsigned long long>();
-  A.S = static_cast<IcpState *>(h->state_host);
+  A.S = static_cast<IcpState *>(h->state_host.p);
   A.bar = h->bar.as<unsigned>();
   A.max_d2 = (float)(p.max_corr_dist * p.max_corr_dist);
   A.max_iterations = p.max_iterations;
@@ -788,7 +780,7 @@ int align_device_counts_locked(rsx_icp *h, const void *d_src, int64_t n_s, const
     RSX_HIP(hipGetLastError());
   }
   RSX_HIP(hipStreamSynchronize(s));
-  const IcpState hstate = *static_cast<const IcpState *>(h->state_host);
+  const IcpState hstate = *static_cast<const IcpState *>(h->state_host.p);
   if (hstate.state == ST_GAVE_UP)
     return fail(RSX_ERR_HIP, "a grid barrier of the persistent kernel gave up after 5 s: its workgroups were not all resident (CUs masked, or another process holds a part of the device)");
   std::memcpy(out->transform, hstate.final_t, sizeof(out->transform));

@@ -100,13 +100,13 @@ __global__ __launch_bounds__(256) void lv_fill_kf(int32_t *__restrict__ kf_of, i
 struct rsx_kfstore {
   int device = 0;
   std::mutex mu;
-  hipStream_t stream = nullptr;
+  rsx::Stream stream;
   rsx::DevBuf clouds;        // float4 per point, keyframes back to back
   rsx::DevBuf kf_of;         // int32 per point: its keyframe
   std::vector<int64_t> off;  // keyframe i = points [off[i], off[i + 1])
   rsx::DevBuf stage, work_s, work_t, tf;
-  rsx_voxelgrid *vg_s = nullptr, *vg_t = nullptr;
-  rsx_icp *icp = nullptr;
+  rsx::Owned<rsx_voxelgrid, rsx_voxelgrid_destroy> vg_s, vg_t;
+  rsx::Owned<rsx_icp, rsx_icp_destroy> icp;
 };
 
 using rsx::fail;
@@ -195,30 +195,23 @@ extern "C" {
 int rsx_kfstore_create(int device, rsx_kfstore **out) try {
   if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
   *out = nullptr;
-  int ndev = rsx_device_count();
-  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
-  rsx_kfstore *h = new (std::nothrow) rsx_kfstore();
+  RSX_TRY(rsx::check_device(device));
+  std::unique_ptr<rsx_kfstore> h(new (std::nothrow) rsx_kfstore());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->device = device;
-  int st = RSX_OK;
-  try {
-    h->off.push_back(0);
-  } catch (...) {
-    delete h;
-    return fail(RSX_ERR_OOM, "host alloc");
-  }
+  h->off.push_back(0);
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) st = fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  if (st == RSX_OK) st = rsx_voxelgrid_create(device, &h->vg_s);
-  if (st == RSX_OK) st = rsx_voxelgrid_create(device, &h->vg_t);
-  if (st == RSX_OK) st = rsx_icp_create(device, &h->icp);
-  if (st != RSX_OK) {
-    rsx_kfstore_destroy(h);
-    return st;
-  }
-  *out = h;
+  if (e == hipSuccess) e = h->stream.create();
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
+  rsx_voxelgrid *vg_s = nullptr, *vg_t = nullptr;
+  rsx_icp *icp = nullptr;
+  RSX_TRY(rsx_voxelgrid_create(device, &vg_s));
+  h->vg_s.reset(vg_s);
+  RSX_TRY(rsx_voxelgrid_create(device, &vg_t));
+  h->vg_t.reset(vg_t);
+  RSX_TRY(rsx_icp_create(device, &icp));
+  h->icp.reset(icp);
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -226,11 +219,6 @@ int rsx_kfstore_destroy(rsx_kfstore *h) try {
   if (!h) return RSX_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->icp) rsx_icp_destroy(h->icp);
-  if (h->vg_s) rsx_voxelgrid_destroy(h->vg_s);
-  if (h->vg_t) rsx_voxelgrid_destroy(h->vg_t);
-  for (rsx::DevBuf *b : {&h->clouds, &h->kf_of, &h->stage, &h->work_s, &h->work_t, &h->tf}) b->release();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -315,7 +303,7 @@ int rsx_loop_submap(rsx_kfstore *h, int32_t key, int32_t submap_size, const doub
   RSX_HIP(hipSetDevice(h->device));
   const float *d = nullptr;
   int64_t n = 0;
-  RSX_TRY(submap_device(h, h->vg_t, key, submap_size, pose_matrix(root_pose6), leaf, &d, &n));
+  RSX_TRY(submap_device(h, h->vg_t.get(), key, submap_size, pose_matrix(root_pose6), leaf, &d, &n));
   *out_count = n;
   const int64_t w = n < max_out ? n : max_out;
   if (w > 0) {
@@ -344,14 +332,14 @@ int rsx_loop_verify(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const do
   int64_t first[2], np[2];
   submap_slice(h, curr_idx, 0, &first[0], &np[0]);
   submap_slice(h, loop_idx, p.history_keyframe_search_num, &first[1], &np[1]);
-  rsx_voxelgrid *vgs[2] = {h->vg_s, h->vg_t};
+  rsx_voxelgrid *vgs[2] = {h->vg_s.get(), h->vg_t.get()};
   rsx_icp_result ir;
   int64_t ns = 0, nt = 0;
   {
-    std::lock_guard<std::mutex> lks(rsx::vg::mutex_of(h->vg_s));
-    std::lock_guard<std::mutex> lkt(rsx::vg::mutex_of(h->vg_t));
-    std::lock_guard<std::mutex> lki(rsx::icp::mutex_of(h->icp));
-    hipStream_t s = rsx::icp::stream_of(h->icp);
+    std::lock_guard<std::mutex> lks(rsx::vg::mutex_of(h->vg_s.get()));
+    std::lock_guard<std::mutex> lkt(rsx::vg::mutex_of(h->vg_t.get()));
+    std::lock_guard<std::mutex> lki(rsx::icp::mutex_of(h->icp.get()));
+    hipStream_t s = rsx::icp::stream_of(h->icp.get());
     rsx::vg::JobIn jobs[2];
     rsx::vg::DeviceCloud dc[2];
     int which[2], nj = 0;
@@ -367,7 +355,7 @@ int rsx_loop_verify(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const do
       d_cloud[which[j]] = dc[j].d_out;
       d_cnt[which[j]] = dc[j].d_count;
     }
-    RSX_TRY(rsx::icp::align_device_counts_locked(h->icp, d_cloud[0], np[0], d_cnt[0], 16, d_cloud[1], np[1], d_cnt[1], 16, &p.icp, nullptr, &ir,
+    RSX_TRY(rsx::icp::align_device_counts_locked(h->icp.get(), d_cloud[0], np[0], d_cnt[0], 16, d_cloud[1], np[1], d_cnt[1], 16, &p.icp, nullptr, &ir,
                                                  &ns, &nt));
   }
   out->n_source = ns;
@@ -438,8 +426,8 @@ int rsx_kfstore_build_map(rsx_kfstore *h, const double *poses6, int64_t n_poses,
   const float *d = nullptr;
   int64_t m = 0;
   {
-    std::lock_guard<std::mutex> lkv(rsx::vg::mutex_of(h->vg_t));
-    RSX_TRY(rsx::vg::filter_device(h->vg_t, h->work_t.p, total, 16, 12, leaf, total, &d, &m, s));  // (syncs s: km is free to go)
+    std::lock_guard<std::mutex> lkv(rsx::vg::mutex_of(h->vg_t.get()));
+    RSX_TRY(rsx::vg::filter_device(h->vg_t.get(), h->work_t.p, total, 16, 12, leaf, total, &d, &m, s));  // (syncs s: km is free to go)
     *out_count = m;
     const int64_t w = m < max_out ? m : max_out;
     if (w > 0) {

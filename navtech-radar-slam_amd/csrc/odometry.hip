@@ -111,18 +111,18 @@ __global__ __launch_bounds__(256) void odo_gather(const float2 *__restrict__ sta
 constexpr int N_SETS = 3, N_LANES = 2;
 struct OdoSet {
   rsx::DevBuf az, targets, xy, counts, desc, valid;  // slot 0 = the previous scan, slots 1 .. MAX_WINDOW = the window
-  void *pin = nullptr;  // pinned: counts[MAX_WINDOW + 1], pair_cnt[MAX_WINDOW], results[MAX_WINDOW], then the staged azimuth grids
+  rsx::PinnedBuf pin;  // pinned: counts[MAX_WINDOW + 1], pair_cnt[MAX_WINDOW], results[MAX_WINDOW], then the staged azimuth grids
 };
 
 struct rsx_odometry {
   int device = 0, rows = 0, cols = 0;
   rsx_odometry_params prm{};
   std::mutex mu;
-  hipStream_t lane_stream[N_LANES] = {}, match_stream = nullptr, copy_stream = nullptr;
-  hipEvent_t ev_up = nullptr, ev_e[N_SETS] = {}, ev_m[N_SETS] = {};
-  rsx_cen2019 *cen[N_LANES] = {};
-  rsx_frontend *fe[N_LANES] = {};
-  rsx_orora *reg = nullptr;
+  rsx::Stream lane_stream[N_LANES], match_stream, copy_stream;
+  rsx::Event ev_up, ev_e[N_SETS], ev_m[N_SETS];
+  rsx::Owned<rsx_cen2019, rsx_cen2019_destroy> cen[N_LANES];
+  rsx::Owned<rsx_frontend, rsx_frontend_destroy> fe[N_LANES];
+  rsx::Owned<rsx_orora, rsx_orora_destroy> reg;
   OdoSet set[N_SETS];
   rsx::DevBuf imgs[N_SETS], fwd, bwd, stage_src, stage_dst, pair_cnt, src, dst, offsets, results;
   uint64_t windows = 0;  // windows enqueued since creation: window g works in set[g % N_SETS] on lane g & 1
@@ -173,18 +173,18 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   // the azimuth grids go to the device once: cen2019's polar -> Cartesian and the Cartesian image both read them there.
   // Staged in pinned memory so that the copy does not wait for the stream (the area was last read by E(g - 3): long done)
   const size_t na = (size_t)h->rows * (azimuths_per_image ? n : 1);
-  float *paz = reinterpret_cast<float *>(static_cast<char *>(q.pin) + PIN_AZ);
+  float *paz = reinterpret_cast<float *>(static_cast<char *>(q.pin.p) + PIN_AZ);
   std::memcpy(paz, azimuths, na * 4);
   RSX_HIP(hipMemcpyAsync(q.az.p, paz, na * 4, hipMemcpyHostToDevice, s));
   int32_t *d_counts = q.counts.as<int32_t>();
-  RSX_TRY(rsx_cen2019_extract_batch_device(h->cen[lane], d_imgs, n, img_stride, row_stride, h->prm.col_offset, &h->prm.cen, q.az.as<float>(),
+  RSX_TRY(rsx_cen2019_extract_batch_device(h->cen[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, &h->prm.cen, q.az.as<float>(),
                                            azimuths_per_image, h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy,
                                            q.xy.as<float>() + slot_xy, K, d_counts + 1, s));
   // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
   // how the sequence is cut into windows, and nothing about the grids is looked at on the host
-  RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane], d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
+  RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
                                                  azimuths_per_image ? (int64_t)h->rows : 0, h->prm.radar_resolution, s));
-  RSX_TRY(rsx_frontend_describe_batch_device(h->fe[lane], q.xy.as<float>() + slot_xy, d_counts + 1, n, K, q.desc.as<uint8_t>() + (size_t)K * 32,
+  RSX_TRY(rsx_frontend_describe_batch_device(h->fe[lane].get(), q.xy.as<float>() + slot_xy, d_counts + 1, n, K, q.desc.as<uint8_t>() + (size_t)K * 32,
                                              q.valid.as<uint8_t>() + (size_t)K, s));
   // the last scan of the window becomes the previous scan of the next one (slot 0 of the next set, which M(g - 2) read; the
   // next window's own extraction, on the other lane, writes slots 1 .. n of that set only)
@@ -209,17 +209,17 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out) {
   const int first = h->have_prev ? 0 : 1, n_pairs = n - first;
   *first_out = first;
   if (n_pairs > 0) {
-    RSX_TRY(rsx_frontend_match_consecutive_device(h->fe[g & 1], q.desc.as<uint8_t>(), q.valid.as<uint8_t>(), d_counts, K, first, n_pairs,
+    RSX_TRY(rsx_frontend_match_consecutive_device(h->fe[g & 1].get(), q.desc.as<uint8_t>(), q.valid.as<uint8_t>(), d_counts, K, first, n_pairs,
                                                   h->prm.frontend.ratio, h->fwd.as<int32_t>(), h->bwd.as<int32_t>(), s));
     hipLaunchKernelGGL(odo_cross, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
                        h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>());
     hipLaunchKernelGGL(odo_gather, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_src.as<float2>(), h->stage_dst.as<float2>(),
                        h->pair_cnt.as<int32_t>(), n_pairs, K, h->src.as<float2>(), h->dst.as<float2>(), h->offsets.as<int64_t>());
     RSX_HIP(hipGetLastError());
-    RSX_TRY(rsx_orora_register_batch_device(h->reg, h->src.as<float>(), h->dst.as<float>(), h->offsets.as<int64_t>(), n_pairs, &h->prm.orora,
+    RSX_TRY(rsx_orora_register_batch_device(h->reg.get(), h->src.as<float>(), h->dst.as<float>(), h->offsets.as<int64_t>(), n_pairs, &h->prm.orora,
                                             h->results.as<rsx_orora_result>(), s));
   }
-  char *pin = static_cast<char *>(q.pin);
+  char *pin = static_cast<char *>(q.pin.p);
   RSX_HIP(hipMemcpyAsync(pin + PIN_COUNTS, d_counts, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, s));
   if (n_pairs > 0) {
     RSX_HIP(hipMemcpyAsync(pin + PIN_PAIRS, h->pair_cnt.p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, s));
@@ -235,7 +235,7 @@ int finish_window(rsx_odometry *h, uint64_t g, int n, int first, rsx_odometry_sc
   OdoSet &q = h->set[g % N_SETS];
   const int K = h->prm.max_keypoints;
   const size_t slot_xy = (size_t)K * 2;
-  char *pin = static_cast<char *>(q.pin);
+  char *pin = static_cast<char *>(q.pin.p);
   RSX_HIP(hipEventSynchronize(h->ev_m[g % N_SETS]));
   const int32_t *hc = reinterpret_cast<const int32_t *>(pin + PIN_COUNTS), *hp = reinterpret_cast<const int32_t *>(pin + PIN_PAIRS);
   const rsx_orora_result *hr = reinterpret_cast<const rsx_orora_result *>(pin + PIN_RES);
@@ -315,38 +315,37 @@ int rsx_odometry_create(const rsx_odometry_params *params, int32_t rows, int32_t
   if (p.max_keypoints < 16 || p.max_keypoints > rsx_orora_max_correspondences())
     return fail(RSX_ERR_BAD_ARG, "max_keypoints %d outside [16, %d]", p.max_keypoints, rsx_orora_max_correspondences());
   if (p.col_offset < 0 || !(p.radar_resolution > 0.0f)) return fail(RSX_ERR_BAD_ARG, "bad col_offset / radar_resolution");
-  rsx_odometry *h = new (std::nothrow) rsx_odometry();
+  std::unique_ptr<rsx_odometry> h(new (std::nothrow) rsx_odometry());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->device = p.device;
   h->rows = rows;
   h->cols = cols;
   h->prm = p;
-  int st = RSX_OK;
-  for (int l = 0; l < N_LANES && st == RSX_OK; l++) {
-    st = rsx_cen2019_create(p.device, rows, cols, &h->cen[l]);
-    if (st == RSX_OK) st = rsx_frontend_create(p.device, rows, cols, &p.frontend, &h->fe[l]);
+  for (int l = 0; l < N_LANES; l++) {
+    rsx_cen2019 *cen = nullptr;
+    rsx_frontend *fe = nullptr;
+    RSX_TRY(rsx_cen2019_create(p.device, rows, cols, &cen));
+    h->cen[l].reset(cen);
+    RSX_TRY(rsx_frontend_create(p.device, rows, cols, &p.frontend, &fe));
+    h->fe[l].reset(fe);
   }
-  if (st == RSX_OK) st = rsx_orora_create(p.device, &h->reg);
-  if (st == RSX_OK && (p.orora.flags & RSX_ORORA_PMC)) st = rsx_orora_reserve(h->reg, (int64_t)MAX_WINDOW * p.max_keypoints);
-  if (st == RSX_OK) {
-    hipError_t e = hipSetDevice(p.device);
-    for (hipStream_t &ls : h->lane_stream)
-      if (e == hipSuccess) e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->match_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming);
-    for (int i = 0; i < N_SETS; i++) {
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_e[i], hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_m[i], hipEventDisableTiming);
-      if (e == hipSuccess) e = hipHostMalloc(&h->set[i].pin, pin_bytes(h), hipHostMallocDefault);
-    }
-    if (e != hipSuccess) st = fail(e == hipErrorOutOfMemory ? RSX_ERR_OOM : RSX_ERR_HIP, "odometry create: %s", hipGetErrorString(e));
+  rsx_orora *reg = nullptr;
+  RSX_TRY(rsx_orora_create(p.device, &reg));
+  h->reg.reset(reg);
+  if (p.orora.flags & RSX_ORORA_PMC) RSX_TRY(rsx_orora_reserve(reg, (int64_t)MAX_WINDOW * p.max_keypoints));
+  hipError_t e = hipSetDevice(p.device);
+  for (rsx::Stream &ls : h->lane_stream)
+    if (e == hipSuccess) e = ls.create();
+  if (e == hipSuccess) e = h->match_stream.create();
+  if (e == hipSuccess) e = h->copy_stream.create();
+  if (e == hipSuccess) e = h->ev_up.create();
+  for (int i = 0; i < N_SETS; i++) {
+    if (e == hipSuccess) e = h->ev_e[i].create();
+    if (e == hipSuccess) e = h->ev_m[i].create();
   }
-  if (st != RSX_OK) {
-    rsx_odometry_destroy(h);
-    return st;
-  }
-  *out = h;
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RSX_ERR_OOM : RSX_ERR_HIP, "odometry create: %s", hipGetErrorString(e));
+  for (OdoSet &q : h->set) RSX_TRY(q.pin.reserve(pin_bytes(h.get())));
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -357,27 +356,6 @@ int rsx_odometry_destroy(rsx_odometry *h) try {
     if (ls) (void)hipStreamSynchronize(ls);
   if (h->match_stream) (void)hipStreamSynchronize(h->match_stream);
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-  for (rsx::DevBuf &b : h->imgs) b.release();
-  for (rsx::DevBuf *b : {&h->fwd, &h->bwd, &h->stage_src, &h->stage_dst, &h->pair_cnt, &h->src, &h->dst, &h->offsets, &h->results})
-    b->release();
-  for (OdoSet &q : h->set) {
-    for (rsx::DevBuf *b : {&q.az, &q.targets, &q.xy, &q.counts, &q.desc, &q.valid}) b->release();
-    if (q.pin) (void)hipHostFree(q.pin);
-  }
-  for (int l = 0; l < N_LANES; l++) {
-    rsx_cen2019_destroy(h->cen[l]);
-    rsx_frontend_destroy(h->fe[l]);
-  }
-  rsx_orora_destroy(h->reg);
-  if (h->ev_up) (void)hipEventDestroy(h->ev_up);
-  for (int i = 0; i < N_SETS; i++) {
-    if (h->ev_e[i]) (void)hipEventDestroy(h->ev_e[i]);
-    if (h->ev_m[i]) (void)hipEventDestroy(h->ev_m[i]);
-  }
-  if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-  if (h->match_stream) (void)hipStreamDestroy(h->match_stream);
-  for (hipStream_t ls : h->lane_stream)
-    if (ls) (void)hipStreamDestroy(ls);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL

@@ -785,7 +785,7 @@ __global__ __launch_bounds__(1024) void orora_register_big_kernel(const float2 *
 struct rsx_orora {
   int device = 0;
   std::mutex mu;
-  hipStream_t stream = nullptr;
+  rsx::Stream stream;
   rsx::DevBuf src, dst, off, res;
   rsx::DevBuf big_list, big_ws;  // pairs of more than 2048 matches: their indices, and the HBM arrays of the workgroups that score them
   // RSX_ORORA_PMC: the selection's workspaces (csrc/pmc.hip) and what it hands to the solver
@@ -828,19 +828,14 @@ int rsx_orora_max_correspondences(void) { return MAXK_BIG; }
 int rsx_orora_create(int device, rsx_orora **out) try {
   if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
   *out = nullptr;
-  int ndev = rsx_device_count();
-  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
-  rsx_orora *h = new (std::nothrow) rsx_orora();
+  RSX_TRY(rsx::check_device(device));
+  std::unique_ptr<rsx_orora> h(new (std::nothrow) rsx_orora());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->device = device;
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  if (e == hipSuccess) e = h->stream.create();
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -848,15 +843,6 @@ int rsx_orora_destroy(rsx_orora *h) try {
   if (!h) return RSX_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->src.release();
-  h->dst.release();
-  h->off.release();
-  h->res.release();
-  h->big_list.release();
-  h->big_ws.release();
-  h->pmc_ws.release();
-  for (rsx::DevBuf *b : {&h->sel_src, &h->sel_dst, &h->sel_cnt, &h->pmc_info, &h->member}) b->release();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL

@@ -18,10 +18,6 @@ constexpr int CHUNK = 4096;                      // pairs per launch group (2 Gi
 struct Workspace {
   rsx::DevBuf slabs;  // one adjacency slab per pair of a chunk
   rsx::DevBuf meta;   // one record per pair of a chunk
-  void release() {
-    slabs.release();
-    meta.release();
-  }
 };
 
 // member (optional): 1 / 0 per match, laid out like the matches; info (optional): one per pair; sel_src / sel_dst / sel_cnt

@@ -1,13 +1,15 @@
-// rsx_common.h -- shared host-side plumbing of librsx.so (error reporting, HIP checks).
+// rsx_common.h -- shared host-side plumbing of librsx.so (error reporting, HIP checks, owning HIP resources).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 #include "rsx.h"
 #include "rsx_diag.h"
@@ -83,10 +85,31 @@ inline int on_exception() noexcept {
     if (_s != RSX_OK) return _s; \
   } while (0)
 
+// the device checks every rsx_*_create starts with
+inline int check_device(int device) {
+  const int ndev = rsx_device_count();
+  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
+  return RSX_OK;
+}
+
+// Owning HIP resources (DevBuf, PinnedBuf, Stream, Event): each frees what it holds when it goes, so a handle's destroy is
+// "synchronise its streams, delete".  Move-only; moving swaps, so what the target held goes with the source.
+
 // growable device buffer (never shrinks); contents preserved on growth when keep=true
 struct DevBuf {
   void *p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
   int reserve(size_t want, hipStream_t s, bool keep) {
     if (want <= bytes) return RSX_OK;
     size_t nb = bytes ? bytes : 4096;
@@ -112,15 +135,79 @@ struct DevBuf {
     bytes = nb;
     return RSX_OK;
   }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
   template <typename T>
   T *as() const {
     return static_cast<T *>(p);
   }
 };
+
+// pinned host buffer; reserve(want) frees and allocates exactly `want` bytes when it holds fewer (contents not kept: the
+// caller picks the size policy)
+struct PinnedBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf &&o) noexcept { *this = std::move(o); }
+  PinnedBuf &operator=(PinnedBuf &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  int reserve(size_t want) {
+    if (want <= bytes) return RSX_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+    RSX_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
+    bytes = want;
+    return RSX_OK;
+  }
+};
+
+// non-blocking stream; null until create()
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(Stream &&o) noexcept { *this = std::move(o); }
+  Stream &operator=(Stream &&o) noexcept {
+    std::swap(s, o.s);
+    return *this;
+  }
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s; }
+};
+
+// event without timing (timing = true: with, for hipEventElapsedTime); null until create()
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept { *this = std::move(o); }
+  Event &operator=(Event &&o) noexcept {
+    std::swap(e, o.e);
+    return *this;
+  }
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create(bool timing = false) { return timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+  operator hipEvent_t() const { return e; }
+};
+
+// a librsx handle owned by another one, freed by its own rsx_*_destroy: Owned<rsx_icp, rsx_icp_destroy>
+template <auto Destroy>
+struct Destroyer {
+  template <typename T>
+  void operator()(T *h) const {
+    (void)Destroy(h);
+  }
+};
+template <typename T, auto Destroy>
+using Owned = std::unique_ptr<T, Destroyer<Destroy>>;
 
 }  // namespace rsx

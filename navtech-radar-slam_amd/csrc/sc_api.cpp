@@ -30,7 +30,7 @@ using namespace rsx::sc;
 struct rsx_sc {
   rsx_sc_params p;
   std::mutex mu;
-  hipStream_t stream = nullptr;
+  Stream stream;
   // database shard (SoA in HBM)
   int64_t n_global = 0, n_local = 0, cap = 0;
   DevBuf desc, vkey, norm, rkey;
@@ -59,7 +59,6 @@ struct rsx_sc {
     DevBuf q_vkey, q_norm, q_rkey, partial;
     DevBuf f_qimg, f_lb, f_cand, f_cnt, f_thr, f_plan;  // filter path
     DevBuf f_wimg, f_win;                               // window previews of the short lists (sc_window.hip)
-    DevBuf *all[12] = {&q_vkey, &q_norm, &q_rkey, &partial, &f_qimg, &f_lb, &f_cand, &f_cnt, &f_thr, &f_plan, &f_wimg, &f_win};
   } ws[2];
   QueryWs *w = &ws[0];  // the set the calls below work in (guarded by mu like the rest)
   PairProfiler prof;
@@ -77,8 +76,7 @@ struct rsx_sc {
   DevBuf q1_ws, q1_ticket;
   DevBuf helper_ws;   // staging of the stateless helper calls (Scancontext.h:60-66)
   DevBuf stats;       // profiling only: RESCORE_STAT_COPIES blocks of counters (sc_kernels.h), summed by the host when read
-  void *pinned = nullptr;  // small pinned host staging (results)
-  size_t pinned_bytes = 0;
+  PinnedBuf pinned;  // small pinned host staging (results)
   // upload pipeline of the host-buffer entry (rsx_sc_query): pieces of the query batch go up on their own stream while
   // the pieces before them are scored
   static constexpr int kMaxPieces = 8;
@@ -87,9 +85,8 @@ struct rsx_sc {
   // stream is ordered behind the latest insert (use_stream)
   static constexpr int kInsSlots = 8;
   struct InsSlot {
-    void *host = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
+    PinnedBuf host;
+    Event done;
     bool used = false;
   } ins[kInsSlots];
   int ins_next = 0;
@@ -97,9 +94,9 @@ struct rsx_sc {
   // the handle's workspaces (and the single-query path's arrival tickets, which must be zero between launches) are shared by
   // every call: when a call arrives on another stream than the previous one, the new stream is ordered behind the old
   hipStream_t last_user_stream = nullptr;
-  hipEvent_t stream_switch = nullptr;
-  hipStream_t up_stream = nullptr, stream_b = nullptr;
-  hipEvent_t up_ev[kMaxPieces] = {}, lane_ev = nullptr;
+  Event stream_switch;
+  Stream up_stream, stream_b;
+  Event up_ev[kMaxPieces], lane_ev;
 };
 
 namespace {
@@ -116,7 +113,7 @@ int use_stream(rsx_sc *h, void *stream, hipStream_t *s) {
   *s = stream ? static_cast<hipStream_t>(stream) : h->stream;
   if (*s != h->stream && h->last_insert) RSX_HIP(hipStreamWaitEvent(*s, h->last_insert, 0));
   if (h->last_user_stream && h->last_user_stream != *s) {
-    if (!h->stream_switch) RSX_HIP(hipEventCreateWithFlags(&h->stream_switch, hipEventDisableTiming));
+    if (!h->stream_switch) RSX_HIP(h->stream_switch.create());
     // (a previous stream the caller has destroyed in the meantime has drained: nothing to wait for)
     if (hipEventRecord(h->stream_switch, h->last_user_stream) == hipSuccess) RSX_HIP(hipStreamWaitEvent(*s, h->stream_switch, 0));
     else (void)hipGetLastError();
@@ -199,15 +196,10 @@ float yaw_from_shift(int shift) {
 }
 
 int ensure_pinned(rsx_sc *h, size_t bytes) {
-  if (bytes <= h->pinned_bytes) return RSX_OK;
-  if (h->pinned) (void)hipHostFree(h->pinned);
-  h->pinned = nullptr;
-  h->pinned_bytes = 0;
+  if (bytes <= h->pinned.bytes) return RSX_OK;
   size_t nb = 4096;
   while (nb < bytes) nb *= 2;
-  RSX_HIP(hipHostMalloc(&h->pinned, nb, hipHostMallocDefault));
-  h->pinned_bytes = nb;
-  return RSX_OK;
+  return h->pinned.reserve(nb);
 }
 
 // keys for nq query descriptors already in h->q_desc (or external device pointer)
@@ -581,7 +573,7 @@ int score_candidates_and_finish(rsx_sc *h, const QueryView &qv, const float *d_q
     int32_t *d_shift = reinterpret_cast<int32_t *>(h->small.as<char>() + 2048);
     RSX_TRY(launch_pairs(db_view(h), qv, d_idx, 0, k, -1, nullptr, d_dist, d_shift, nullptr, nullptr, 0, s));
     RSX_TRY(ensure_pinned(h, 4096));
-    char *hp = static_cast<char *>(h->pinned);
+    char *hp = static_cast<char *>(h->pinned.p);
     RSX_HIP(hipMemcpyAsync(hp, h->small.p, 2048 + 256, hipMemcpyDeviceToHost, s));
     RSX_HIP(hipStreamSynchronize(s));
     const int32_t *ci = reinterpret_cast<const int32_t *>(hp);
@@ -597,9 +589,9 @@ int score_candidates_and_finish(rsx_sc *h, const QueryView &qv, const float *d_q
   } else {
     // the one record goes straight into pinned host memory (device-visible): no copy to enqueue
     RSX_TRY(ensure_pinned(h, 4096));
-    RSX_TRY(run_topk(h, qv, n_search, n_search, nullptr, 1, static_cast<rsx_sc_hit *>(h->pinned), s));
+    RSX_TRY(run_topk(h, qv, n_search, n_search, nullptr, 1, static_cast<rsx_sc_hit *>(h->pinned.p), s));
     RSX_HIP(hipStreamSynchronize(s));
-    const rsx_sc_hit *r = static_cast<const rsx_sc_hit *>(h->pinned);
+    const rsx_sc_hit *r = static_cast<const rsx_sc_hit *>(h->pinned.p);
     if (r->dist < best_d) {
       best_d = r->dist;
       best_align = r->shift;
@@ -679,52 +671,23 @@ int rsx_sc_create(const rsx_sc_params *p, rsx_sc **out) try {
   if (d.sum_order < 0 || d.sum_order > RSX_SC_SUM_EIGEN34_AVX_FMA) return fail(RSX_ERR_BAD_ARG, "sum_order must be RSX_SC_SUM_EIGEN_SSE2, _SEQ, _EIGEN_AVX_FMA or _EIGEN34_AVX_FMA");
   if (d.filter_kind < 0 || d.filter_kind > 3)
     return fail(RSX_ERR_BAD_ARG, "filter_kind must be 0 (auto), 1 (direct), 2 (spectral) or 3 (spectral, two waves per SIMD)");
-  int ndev = rsx_device_count();
-  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
-  if (d.device < 0 || d.device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", d.device, ndev);
-  rsx_sc *h = new (std::nothrow) rsx_sc();
+  RSX_TRY(check_device(d.device));
+  std::unique_ptr<rsx_sc> h(new (std::nothrow) rsx_sc());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->p = d;
-  int st = set_device(h);
-  if (st == RSX_OK) {
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) st = fail(RSX_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  if (st == RSX_OK) st = ensure_capacity(h, d.capacity_hint > 0 ? d.capacity_hint : 1024);
-  if (st != RSX_OK) {
-    rsx_sc_destroy(h);
-    return st;
-  }
-  *out = h;
+  RSX_TRY(set_device(h.get()));
+  hipError_t e = h->stream.create();
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
+  RSX_TRY(ensure_capacity(h.get(), d.capacity_hint > 0 ? d.capacity_hint : 1024));
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
 int rsx_sc_destroy(rsx_sc *h) try {
   if (!h) return RSX_OK;
   (void)hipSetDevice(h->p.device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (DevBuf *b : {&h->hn, &h->cmask, &h->sp, &h->sp_aux, &h->hnr, &h->vk16, &h->vk_n, &h->st_partial, &h->stats, &h->helper_ws, &h->tree.nodes, &h->tree.vind,
-                    &h->tree_batch.nodes, &h->tree_batch.vind, &h->q1_ws, &h->q1_ticket}) b->release();
-  for (DevBuf *b : {&h->desc, &h->vkey, &h->norm, &h->rkey, &h->pts_ws, &h->q_desc, &h->topk, &h->knn_ws, &h->small, &h->pair_out, &h->q_elig})
-    b->release();
-  for (auto &w : h->ws)
-    for (DevBuf *b : w.all) b->release();
-  if (h->pinned) (void)hipHostFree(h->pinned);
-  if (h->prof.ev) {
-    for (int i = 0; i < 2 * PairProfiler::kMax; i++) (void)hipEventDestroy(h->prof.ev[i]);
-    delete[] h->prof.ev;
-  }
-  for (auto e : h->up_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &sl : h->ins) {
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
-  if (h->lane_ev) (void)hipEventDestroy(h->lane_ev);
-  if (h->stream_switch) (void)hipEventDestroy(h->stream_switch);
-  if (h->up_stream) (void)hipStreamDestroy(h->up_stream);
-  if (h->stream_b) (void)hipStreamDestroy(h->stream_b);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  for (hipStream_t s : {h->stream.s, h->up_stream.s, h->stream_b.s})
+    if (s) (void)hipStreamSynchronize(s);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -780,19 +743,15 @@ int rsx_sc_add_points(rsx_sc *h, const void *pts, size_t n, size_t stride_bytes,
     rsx_sc::InsSlot &sl = h->ins[h->ins_next];
     h->ins_next = (h->ins_next + 1) % rsx_sc::kInsSlots;
     if (sl.used) RSX_HIP(hipEventSynchronize(sl.done));  // the insert that used this slot 8 calls ago
-    if (bytes > sl.cap) {
-      if (sl.host) (void)hipHostFree(sl.host);
-      sl.host = nullptr;
-      sl.cap = 0;
+    if (bytes > sl.host.bytes) {
       size_t cap = 32768;
       while (cap < bytes) cap *= 2;
-      RSX_HIP(hipHostMalloc(&sl.host, cap, hipHostMallocDefault));
-      sl.cap = cap;
+      RSX_TRY(sl.host.reserve(cap));
     }
-    if (!sl.done) RSX_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    if (bytes) std::memcpy(sl.host, pts, bytes);  // the caller's buffer is free again when this call returns
+    if (!sl.done) RSX_HIP(sl.done.create());
+    if (bytes) std::memcpy(sl.host.p, pts, bytes);  // the caller's buffer is free again when this call returns
     // the kernel reads the points out of the pinned slot itself (each once, 12 of stride_bytes bytes): no copy to enqueue
-    RSX_TRY(insert_cloud(h, sl.host, (int64_t)n, (int64_t)stride_bytes, slot, h->stream));
+    RSX_TRY(insert_cloud(h, sl.host.p, (int64_t)n, (int64_t)stride_bytes, slot, h->stream));
     RSX_HIP(hipEventRecord(sl.done, h->stream));
     sl.used = true;
     h->last_insert = sl.done;
@@ -1306,13 +1265,13 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
     RSX_TRY(ensure_pinned(h, 4096 + (small_q ? q_bytes : 0)));
     const void *src = q;
     if (small_q) {
-      std::memcpy(static_cast<char *>(h->pinned) + 4096, q, q_bytes);
-      src = static_cast<char *>(h->pinned) + 4096;
+      std::memcpy(static_cast<char *>(h->pinned.p) + 4096, q, q_bytes);
+      src = static_cast<char *>(h->pinned.p) + 4096;
     }
     RSX_HIP(hipMemcpyAsync(h->q_desc.p, src, q_bytes, hipMemcpyHostToDevice, h->stream));
-    RSX_TRY(query_device_locked(h, h->q_desc.as<float>(), nq, k, n_eligible, static_cast<rsx_sc_hit *>(h->pinned), h->stream));
+    RSX_TRY(query_device_locked(h, h->q_desc.as<float>(), nq, k, n_eligible, static_cast<rsx_sc_hit *>(h->pinned.p), h->stream));
     RSX_HIP(hipStreamSynchronize(h->stream));
-    std::memcpy(out, h->pinned, out_bytes);
+    std::memcpy(out, h->pinned.p, out_bytes);
     return RSX_OK;
   }
   if (np == 1) {
@@ -1327,10 +1286,10 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
     // kernels (select, window previews, re-scoring rounds: latency, not throughput) that the next piece's filter
     // launch fills in -- in one stream the pieces of the bench batch cost 3.27 ms of kernels against 2.80 ms whole.
     if (!h->up_stream) {
-      RSX_HIP(hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
-      RSX_HIP(hipStreamCreateWithFlags(&h->stream_b, hipStreamNonBlocking));
-      for (auto &e : h->up_ev) RSX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      RSX_HIP(hipEventCreateWithFlags(&h->lane_ev, hipEventDisableTiming));
+      RSX_HIP(h->up_stream.create());
+      RSX_HIP(h->stream_b.create());
+      for (Event &e : h->up_ev) RSX_HIP(e.create());
+      RSX_HIP(h->lane_ev.create());
     }
     auto upload = [&](int c, int64_t q0) -> int {
       RSX_HIP(hipMemcpyAsync(h->q_desc.as<float>() + q0 * DS, q + q0 * DS, (size_t)sizes[c] * DS * sizeof(float),
@@ -1724,9 +1683,9 @@ int rsx_sc_profile_enable(rsx_sc *h, int on) try {
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_TRY(set_device(h));
   if (on && !h->prof.ev) {
-    h->prof.ev = new (std::nothrow) hipEvent_t[2 * PairProfiler::kMax];
+    h->prof.ev.reset(new (std::nothrow) Event[2 * PairProfiler::kMax]);
     if (!h->prof.ev) return fail(RSX_ERR_OOM, "host alloc");
-    for (int i = 0; i < 2 * PairProfiler::kMax; i++) RSX_HIP(hipEventCreate(&h->prof.ev[i]));
+    for (int i = 0; i < 2 * PairProfiler::kMax; i++) RSX_HIP(h->prof.ev[i].create(true));
   }
   if (on) {
     RSX_TRY(h->stats.reserve(kStatBytes, h->stream, false));

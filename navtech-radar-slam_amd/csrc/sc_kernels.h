@@ -4,8 +4,7 @@
 
 #include <cstdint>
 
-#include "rsx.h"
-#include "rsx_diag.h"
+#include "rsx_common.h"
 
 namespace rsx {
 namespace sc {
@@ -227,7 +226,7 @@ int launch_helper(int op, const double *d_a, const double *d_b, double *d_out_d,
 struct PairProfiler {
   bool on = false;
   static constexpr int kMax = 4096;
-  hipEvent_t *ev = nullptr;  // 2*kMax events, created lazily
+  std::unique_ptr<Event[]> ev;  // 2*kMax events with timing, created lazily
   int used = 0;
 };
 void set_pair_profiler(PairProfiler *p);  // thread-local hook consulted by launch_pairs

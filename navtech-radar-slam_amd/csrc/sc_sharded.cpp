@@ -73,10 +73,10 @@ int load_rccl(Rccl **out) {
   } while (0)
 
 struct Shard {
-  rsx_sc *h = nullptr;
+  Owned<rsx_sc, rsx_sc_destroy> h;
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;
+  Stream stream;
+  Event ev;
   void *comm = nullptr;             // RCCL communicator of this device inside its query group
   DevBuf q, part, bound, out, all;  // all: the gathered lists of the group (RCCL exchange: on every shard)
 };
@@ -84,7 +84,7 @@ struct Shard {
 struct Group {                // one query group = S consecutive shards
   int first = 0;              // index of its first shard (the "leader": merges, returns the result)
   DevBuf all, merged;         // on the leader's device
-  hipEvent_t ev_merged = nullptr;
+  Event ev_merged;
 };
 
 }  // namespace
@@ -166,7 +166,7 @@ int exchange(rsx_scs *h, Group &gr, bool from_out, int32_t nq, int32_t k, bool t
         RSX_TRY(gr.merged.reserve(bytes, s.stream, false));
         dst = gr.merged.as<rsx_sc_hit>();
       }
-      RSX_TRY(rsx_sc_merge_topk_device(s.h, s.all.as<rsx_sc_hit>(), S, nq, k, dst, s.stream));
+      RSX_TRY(rsx_sc_merge_topk_device(s.h.get(), s.all.as<rsx_sc_hit>(), S, nq, k, dst, s.stream));
     }
     return RSX_OK;
   }
@@ -178,7 +178,7 @@ int exchange(rsx_scs *h, Group &gr, bool from_out, int32_t nq, int32_t k, bool t
     RSX_HIP(hipStreamWaitEvent(s0.stream, s.ev, 0));
     RSX_HIP(hipMemcpyPeerAsync(static_cast<char *>(gr.all.p) + bytes * g, s0.device, from_out ? s.out.p : s.part.p, s.device, bytes, s0.stream));
   }
-  RSX_TRY(rsx_sc_merge_topk_device(s0.h, gr.all.as<rsx_sc_hit>(), S, nq, k, gr.merged.as<rsx_sc_hit>(), s0.stream));
+  RSX_TRY(rsx_sc_merge_topk_device(s0.h.get(), gr.all.as<rsx_sc_hit>(), S, nq, k, gr.merged.as<rsx_sc_hit>(), s0.stream));
   RSX_HIP(hipEventRecord(gr.ev_merged, s0.stream));
   if (to_bound) {
     for (int g = 0; g < S; g++) {
@@ -206,19 +206,19 @@ int query_group(rsx_scs *h, Group &gr, const float *q, int32_t nq, int32_t k, in
     RSX_TRY(s.out.reserve(bytes, s.stream, false));
     RSX_HIP(hipMemcpyAsync(s.q.p, q, qbytes, hipMemcpyHostToDevice, s.stream));
     if (single) {
-      RSX_TRY(rsx_sc_query_device(s.h, s.q.as<float>(), nq, k, n_eligible, s.out.as<rsx_sc_hit>(), s.stream));
+      RSX_TRY(rsx_sc_query_device(s.h.get(), s.q.as<float>(), nq, k, n_eligible, s.out.as<rsx_sc_hit>(), s.stream));
       *d_result = s.out.as<rsx_sc_hit>();
       return RSX_OK;
     }
     // stage 1 on every device of the group (asynchronous: the devices work concurrently)
-    RSX_TRY(rsx_sc_query_stage1_device(s.h, s.q.as<float>(), nq, k, n_eligible, s.part.as<rsx_sc_hit>(), s.stream));
+    RSX_TRY(rsx_sc_query_stage1_device(s.h.get(), s.q.as<float>(), nq, k, n_eligible, s.part.as<rsx_sc_hit>(), s.stream));
     RSX_HIP(hipEventRecord(s.ev, s.stream));
   }
   RSX_TRY(exchange(h, gr, false, nq, k, true));  // the k-th distance of the merged lists = the group's bound tau
   for (int g = 0; g < S; g++) {                  // stage 2: what tau still admits
     Shard &s = h->sh[(size_t)(gr.first + g)];
     RSX_TRY(use(s));
-    RSX_TRY(rsx_sc_query_stage2_device(s.h, nq, k, s.bound.as<rsx_sc_hit>(), s.out.as<rsx_sc_hit>(), s.stream));
+    RSX_TRY(rsx_sc_query_stage2_device(s.h.get(), nq, k, s.bound.as<rsx_sc_hit>(), s.out.as<rsx_sc_hit>(), s.stream));
     RSX_HIP(hipEventRecord(s.ev, s.stream));
   }
   // (peer copies: the leader must not overwrite `merged` before every shard has copied it: its stream waits for the
@@ -286,7 +286,7 @@ int rsx_scs_create_layout(const rsx_sc_params *p, const int32_t *devices, int32_
   *out = nullptr;
   if (query_groups < 1 || n_devices % query_groups) return fail(RSX_ERR_BAD_ARG, "query_groups %d does not divide %d devices", query_groups, n_devices);
   if (exchange_kind != RSX_SCS_EXCHANGE_PEER_COPY && exchange_kind != RSX_SCS_EXCHANGE_RCCL) return fail(RSX_ERR_BAD_ARG, "bad exchange kind %d", exchange_kind);
-  rsx_scs *h = new (std::nothrow) rsx_scs();
+  Owned<rsx_scs, rsx_scs_destroy> h(new (std::nothrow) rsx_scs());  // (a failure frees each shard on its device)
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   rsx_sc_default_params(&h->p);
   if (p) h->p = *p;
@@ -305,11 +305,13 @@ int rsx_scs_create_layout(const rsx_sc_params *p, const int32_t *devices, int32_
     sp.shard_rank = g % S;
     sp.shard_world = S;
     if (sp.capacity_hint > 0) sp.capacity_hint = sp.capacity_hint / S + 32;
-    st = rsx_sc_create(&sp, &s.h);
+    rsx_sc *shard = nullptr;
+    st = rsx_sc_create(&sp, &shard);
     if (st != RSX_OK) break;
+    s.h.reset(shard);
     hipError_t e = hipSetDevice(s.device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = s.stream.create();
+    if (e == hipSuccess) e = s.ev.create();
     if (e != hipSuccess) st = fail(RSX_ERR_HIP, "stream/event on device %d: %s", s.device, hipGetErrorString(e));
     for (int o = (g / S) * S; o < g && st == RSX_OK; o++) {  // direct xGMI copies inside a group where the topology allows
       const int od = h->sh[(size_t)o].device;
@@ -328,7 +330,7 @@ int rsx_scs_create_layout(const rsx_sc_params *p, const int32_t *devices, int32_
     Group &gr = h->gr[(size_t)g];
     gr.first = g * S;
     hipError_t e = hipSetDevice(h->sh[(size_t)gr.first].device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&gr.ev_merged, hipEventDisableTiming);
+    if (e == hipSuccess) e = gr.ev_merged.create();
     if (e != hipSuccess) st = fail(RSX_ERR_HIP, "event: %s", hipGetErrorString(e));
     if (st == RSX_OK && exchange_kind == RSX_SCS_EXCHANGE_RCCL) {
       std::vector<int> devs;
@@ -350,13 +352,8 @@ int rsx_scs_create_layout(const rsx_sc_params *p, const int32_t *devices, int32_
       }
     }
   }
-  if (st != RSX_OK) {
-    const std::string keep = last_error();
-    rsx_scs_destroy(h);
-    last_error() = keep;
-    return st;
-  }
-  *out = h;
+  if (st != RSX_OK) return st;
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -366,20 +363,19 @@ int rsx_scs_create(const rsx_sc_params *p, const int32_t *devices, int32_t n_dev
 
 int rsx_scs_destroy(rsx_scs *h) try {
   if (!h) return RSX_OK;
+  // each shard's and each group's resources go with that shard's device current (not on whichever is current at `delete h`);
+  // a shard or group a failed create did not reach holds nothing, and its device may not exist
   for (Shard &s : h->sh) {
+    if (!s.h) continue;
     (void)hipSetDevice(s.device);
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.comm && h->rccl) (void)h->rccl->CommDestroy(s.comm);
-    for (DevBuf *b : {&s.q, &s.part, &s.bound, &s.out, &s.all}) b->release();
-    if (s.ev) (void)hipEventDestroy(s.ev);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    if (s.h) rsx_sc_destroy(s.h);
+    s = Shard();
   }
   for (Group &g : h->gr) {
-    if ((size_t)g.first < h->sh.size()) (void)hipSetDevice(h->sh[(size_t)g.first].device);
-    g.all.release();
-    g.merged.release();
-    if (g.ev_merged) (void)hipEventDestroy(g.ev_merged);
+    if (!g.ev_merged) continue;
+    (void)hipSetDevice(h->sh[(size_t)g.first].device);
+    g = Group();
   }
   delete h;
   return RSX_OK;
@@ -392,14 +388,14 @@ int rsx_scs_set_dist_thres(rsx_scs *h, double thres) try {
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
   std::lock_guard<std::mutex> lk(h->mu);
   h->p.dist_thres = thres;
-  for (Shard &s : h->sh) RSX_TRY(rsx_sc_set_dist_thres(s.h, thres));
+  for (Shard &s : h->sh) RSX_TRY(rsx_sc_set_dist_thres(s.h.get(), thres));
   return RSX_OK;
 } RSX_CATCH_ALL
 
 int rsx_scs_size(rsx_scs *h, int64_t *n_global) try {
   if (!h || !n_global) return fail(RSX_ERR_BAD_ARG, "null arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  return rsx_sc_size(h->sh[0].h, n_global);
+  return rsx_sc_size(h->sh[0].h.get(), n_global);
 } RSX_CATCH_ALL
 
 // every shard sees every keyframe (the owner builds and stores it, the others advance their count)
@@ -407,7 +403,7 @@ int rsx_scs_add_points(rsx_scs *h, const void *pts, size_t n, size_t stride_byte
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
   std::lock_guard<std::mutex> lk(h->mu);
   int32_t idx = 0;
-  RSX_TRY(add_to_all(h, [&](Shard &s) { return rsx_sc_add_points(s.h, pts, n, stride_bytes, &idx); }));
+  RSX_TRY(add_to_all(h, [&](Shard &s) { return rsx_sc_add_points(s.h.get(), pts, n, stride_bytes, &idx); }));
   if (out_index) *out_index = idx;
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -415,14 +411,14 @@ int rsx_scs_add_points(rsx_scs *h, const void *pts, size_t n, size_t stride_byte
 int rsx_scs_add_descriptors_f32(rsx_scs *h, const float *descs, int64_t n) try {
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
   std::lock_guard<std::mutex> lk(h->mu);
-  return add_to_all(h, [&](Shard &s) { return rsx_sc_add_descriptors_f32(s.h, descs, n); });
+  return add_to_all(h, [&](Shard &s) { return rsx_sc_add_descriptors_f32(s.h.get(), descs, n); });
 } RSX_CATCH_ALL
 
 int rsx_scs_get_descriptor(rsx_scs *h, int64_t index, double *out_colmajor) try {
   if (!h || !out_colmajor) return fail(RSX_ERR_BAD_ARG, "null arg");
   std::lock_guard<std::mutex> lk(h->mu);
   if (index < 0) return fail(RSX_ERR_RANGE, "index %lld out of range", (long long)index);
-  return rsx_sc_get_descriptor(h->sh[(size_t)(index % (int64_t)h->n_shards)].h, index, out_colmajor);  // query group 0's copy
+  return rsx_sc_get_descriptor(h->sh[(size_t)(index % (int64_t)h->n_shards)].h.get(), index, out_colmajor);  // query group 0's copy
 } RSX_CATCH_ALL
 
 int rsx_scs_query(rsx_scs *h, const float *q_descs, int32_t nq, int32_t k, int64_t n_eligible, rsx_sc_hit *out) try {
@@ -440,7 +436,7 @@ int rsx_scs_detect_loop_closure(rsx_scs *h, rsx_sc_detection *out) try {
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_TRY(usable(h));
   int64_t N = 0;
-  RSX_TRY(rsx_sc_size(h->sh[0].h, &N));
+  RSX_TRY(rsx_sc_size(h->sh[0].h.get(), &N));
   out->loop_id = -1;
   out->yaw_diff_rad = 0.0f;
   out->min_dist = 10000000;
@@ -454,7 +450,7 @@ int rsx_scs_detect_loop_closure(rsx_scs *h, rsx_sc_detection *out) try {
   h->tree_counter = h->tree_counter + 1;                                                             // SC.cpp:360
   double d[RSX_SC_DESC_SIZE];
   float f[RSX_SC_DESC_SIZE];
-  RSX_TRY(rsx_sc_get_descriptor(h->sh[(size_t)((N - 1) % (int64_t)h->n_shards)].h, N - 1, d));       // SC.cpp:336
+  RSX_TRY(rsx_sc_get_descriptor(h->sh[(size_t)((N - 1) % (int64_t)h->n_shards)].h.get(), N - 1, d));       // SC.cpp:336
   for (int i = 0; i < RSX_SC_DESC_SIZE; i++) f[i] = (float)d[i];  // stored as fp32: exact
   rsx_sc_hit hit;
   RSX_TRY(query_locked(h, f, 1, 1, h->tree_size, &hit));
@@ -463,7 +459,7 @@ int rsx_scs_detect_loop_closure(rsx_scs *h, rsx_sc_detection *out) try {
     out->min_dist = hit.dist;
     out->nn_idx = hit.index;
   }
-  RSX_TRY(rsx_sc_hit_to_loop(h->sh[0].h, &hit, &out->loop_id, &out->yaw_diff_rad));                  // SC.cpp:401-417
+  RSX_TRY(rsx_sc_hit_to_loop(h->sh[0].h.get(), &hit, &out->loop_id, &out->yaw_diff_rad));                  // SC.cpp:401-417
   if (!(hit.dist < 10000000)) out->yaw_diff_rad = 0.0f;
   return RSX_OK;
 } RSX_CATCH_ALL

@@ -748,7 +748,7 @@ __global__ __launch_bounds__(CO_NT) void vg_coop_kernel(CoJob a, CoJob b) {
 struct rsx_voxelgrid {
   int device = 0;
   std::mutex mu;
-  hipStream_t stream = nullptr;
+  rsx::Stream stream;
   rsx::DevBuf pts, keys, keys2, vals, vals2, hist, part, bar, out, params;
 };
 
@@ -888,19 +888,14 @@ extern "C" {
 int rsx_voxelgrid_create(int device, rsx_voxelgrid **out) try {
   if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
   *out = nullptr;
-  int ndev = rsx_device_count();
-  if (ndev <= 0) return fail(RSX_ERR_NO_DEVICE, "no HIP device visible (librsx has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(RSX_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
-  rsx_voxelgrid *h = new (std::nothrow) rsx_voxelgrid();
+  RSX_TRY(rsx::check_device(device));
+  std::unique_ptr<rsx_voxelgrid> h(new (std::nothrow) rsx_voxelgrid());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");
   h->device = device;
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  if (e == hipSuccess) e = h->stream.create();
+  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
+  *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -908,9 +903,6 @@ int rsx_voxelgrid_destroy(rsx_voxelgrid *h) try {
   if (!h) return RSX_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (rsx::DevBuf *b : {&h->pts, &h->keys, &h->keys2, &h->vals, &h->vals2, &h->hist, &h->part, &h->bar, &h->out, &h->params})
-    b->release();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return RSX_OK;
 } RSX_CATCH_ALL

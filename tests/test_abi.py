@@ -54,8 +54,12 @@ def test_no_cpu_fallback(rsx):
     with pytest.raises(rsx.RsxError):
         scancontext.SCManager()
     L = rsx.lib()
+    devs = (C.c_int32 * 1)(0)
     for create in (lambda: L.rsx_orora_create(0, C.byref(h)), lambda: L.rsx_cen2019_create(0, 400, 3360, C.byref(h)),
-                   lambda: L.rsx_voxelgrid_create(0, C.byref(h)), lambda: L.rsx_icp_create(0, C.byref(h))):
+                   lambda: L.rsx_voxelgrid_create(0, C.byref(h)), lambda: L.rsx_icp_create(0, C.byref(h)),
+                   lambda: L.rsx_frontend_create(0, 400, 3360, None, C.byref(h)), lambda: L.rsx_kfstore_create(0, C.byref(h)),
+                   lambda: L.rsx_odometry_create(None, 400, 3360, C.byref(h)), lambda: L.rsx_scs_create(None, devs, 1, C.byref(h))):
+        h.value = 1  # a create that fails must also clear *out
         assert create() == -2 and not h.value
 
 
@@ -148,6 +152,38 @@ def test_exception_firewall_is_on_every_status_entry():
             assert lines[k].startswith("} RSX_CATCH_ALL"), f"{os.path.basename(f)}:{k + 1}"
             n += 1
     assert n >= 100
+
+
+def test_handles_own_their_hip_resources():
+    """Every HIP buffer, stream and event of a handle is owned by a type of rsx_common.h (DevBuf, PinnedBuf, Stream,
+    Event) that frees it, and the creates share rsx::check_device: static check over the sources, so nothing is freed by
+    hand again.  Outside rsx_common.h no source frees device memory, streams or events, pinned memory is freed only by
+    rsx_host_free_pinned, the "no device" message is written only by rsx_host_alloc_pinned, and the only release() is the
+    create paths' hand-out of a finished handle (DevBuf has no release)."""
+    import glob
+    csrc = os.path.join(ROOT, "navtech-radar-slam_amd", "csrc")
+    common = open(os.path.join(csrc, "rsx_common.h")).read()
+    devbuf = re.search(r"\nstruct DevBuf \{.*?\n\};", common, flags=re.S).group(0)
+    assert "release" not in devbuf
+    allowed = {"hipHostFree(": "rsx_host_free_pinned", "no HIP device visible": "rsx_host_alloc_pinned"}
+    n_release = 0
+    for f in sorted(glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))):
+        if os.path.basename(f) == "rsx_common.h":
+            continue
+        entry = None
+        for i, line in enumerate(open(f).read().split("\n")):
+            where = f"{os.path.basename(f)}:{i + 1}: {line.strip()}"
+            m = re.match(r"^int (rsx_\w+)\(", line)
+            if m:
+                entry = m.group(1)
+            for word in ("hipFree(", "hipStreamDestroy(", "hipEventDestroy("):
+                assert word not in line, where
+            for word, owner in allowed.items():
+                assert word not in line or entry == owner, where
+            if "release()" in line:
+                assert line.strip() == "*out = h.release();", where
+                n_release += 1
+    assert n_release >= 9  # one per handle type
 
 
 def test_exceptions_thrown_inside_the_library_come_back_as_statuses(rsx):
