@@ -423,6 +423,44 @@ int rsx_cen2019_extract_batch_device(rsx_cen2019 *h, const uint8_t *d_imgs, int3
                                      int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                      int32_t *d_counts, void *stream);
 
+/* ============================== cen2018 keypoint extraction ============================
+ * The other keypoint extractor of the upstream file-based `odometry.cpp` entry (yeti_radar_odometry's
+ * keypoint_extraction = 0, Cen & Newman ICRA 2018).  Source absent from the reference checkout (empty submodule): follows
+ * the method as restated in tests/cen2018_np.py -- parity unpinned.  Per azimuth row: q = fft - mean(fft), p = q smoothed
+ * along range by a 1 x (3 sigma_gauss) Gaussian (reflect 101), sigma = the noise level of the negative q, and one keypoint
+ * at the median bin of every run of consecutive range bins >= min_range with y = q (1 - nqp) + p (nqp - npp) > zq * sigma.
+ * Same argument shapes, output layout (row-major (azimuth idx, range idx), x = (r+0.5)*resolution*cos(az), ...) and
+ * truncation rules as the cen2019 group above; *out_count / out_counts report every keypoint found.
+ * Invalid parameters (an even or non-positive sigma_gauss or one above 85, a negative min_range, a zq that is not finite)
+ * return RSX_ERR_BAD_ARG.  Device workspace per handle: rows x (cols / 2 + 1) x 2 bytes of per-row keypoints + rows x 4
+ * bytes of counts per image of a sub-batch (<= 128 images: 172 MB for 400 x 3360 scans), plus the host entries' staging
+ * (images, keypoints, points of one sub-batch). */
+
+typedef struct rsx_cen2018 rsx_cen2018;
+
+typedef struct {
+  float zq;            /* threshold in noise sigmas (3.0) */
+  int32_t sigma_gauss; /* Gaussian sigma in range bins, odd, 1 .. 85; the filter has 3 sigma_gauss taps (17) */
+  int32_t min_range;   /* first range bin considered for keypoints (58) */
+  int32_t reserved;    /* 0 */
+} rsx_cen2018_params;
+
+int rsx_cen2018_default_params(rsx_cen2018_params *p);
+/* one handle per image shape: rows (1 .. 4096) azimuths x cols (1 .. 8192) range bins */
+int rsx_cen2018_create(int device, int32_t rows, int32_t cols, rsx_cen2018 **out);
+int rsx_cen2018_destroy(rsx_cen2018 *h);
+int rsx_cen2018_extract(rsx_cen2018 *h, const uint8_t *img, int32_t row_stride, int32_t col_offset,
+                        const rsx_cen2018_params *params, const float *azimuths, float resolution,
+                        int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_count);
+int rsx_cen2018_extract_batch(rsx_cen2018 *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                              int32_t col_offset, const rsx_cen2018_params *params, const float *azimuths, int32_t azimuths_per_image,
+                              float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_counts);
+/* two launches per 128 images, no host synchronisation */
+int rsx_cen2018_extract_batch_device(rsx_cen2018 *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes,
+                                     int32_t row_stride, int32_t col_offset, const rsx_cen2018_params *params, const float *d_azimuths,
+                                     int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
+                                     int32_t *d_counts, void *stream);
+
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;
  * SURVEY 8f rank 3): polar -> Cartesian image, ORB-style binary descriptors at the keypoints, brute-force Hamming
@@ -508,7 +546,7 @@ typedef struct {
 typedef struct {
   rsx_orora_result reg;  /* motion between the previous scan and this one: p_previous = R(yaw) p_this + (x, y);
                             reg.status = 3 for the first scan of a sequence (nothing to register against) */
-  int32_t n_keypoints;   /* cen2019 keypoints of this scan (only the first max_keypoints are used) */
+  int32_t n_keypoints;   /* keypoints of this scan (cen2019, or cen2018: rsx_odometry_set_cen2018; only the first max_keypoints are used) */
   int32_t n_matches;     /* cross-checked ratio matches handed to ORORA */
 } rsx_odometry_scan;
 
@@ -519,6 +557,10 @@ int rsx_odometry_create(const rsx_odometry_params *params, int32_t rows, int32_t
 int rsx_odometry_destroy(rsx_odometry *h);
 int rsx_odometry_reset(rsx_odometry *h); /* forget the previous scan: the next scan starts a new sequence */
 int rsx_odometry_window(void);           /* scans per internal launch chain (longer calls are cut into such windows) */
+/* keypoints by cen2018 with these settings instead of cen2019 (params = NULL: back to cen2019, the default).  Only while
+ * the handle holds no scan -- freshly created or after rsx_odometry_reset -- so that no pair is registered from keypoints of
+ * two extractors; otherwise RSX_ERR_BAD_ARG.  rsx_odometry_scan.n_keypoints then counts cen2018 keypoints. */
+int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params);
 /* n_scans consecutive scans, host images image_stride_bytes apart (rows x row_stride bytes each); azimuths: rows floats
  * (rad, increasing) shared by all scans or n_scans x rows when azimuths_per_image != 0.  out [n_scans]; out_xy
  * (optional) [n_scans][max_xy][2]: the scan's keypoints in metres in the sensor frame (/orora/cloud_local).  Synchronous. */

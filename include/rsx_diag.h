@@ -27,6 +27,15 @@ int rsx_selftest_firewall(int kind);
  * observable through the descriptors that sample it (oracle/frontend_ref.c: feref_cart_remap, feref_blur). */
 int rsx_frontend_read_images(rsx_frontend *h, int32_t image, float *out_cart, float *out_blur);
 
+/* Parity helpers of cen2018 (csrc/cen2018.hip, tests/cen2018_np.py).  rsx_cen2018_gauss_weights: the 3 sigma_gauss
+ * normalised filter taps the extraction uses (libm exp in double, float sum ascending, float division); max >= 3 sigma_gauss.
+ * rsx_cen2018_debug_image: ONE host image through the production row kernel's own device functions, with what the production
+ * path never stores: per row mean and sigma (rows floats each), and the smoothed image p and the statistic y (rows x cols
+ * floats each; y for every bin, min_range ignored).  Synchronous. */
+int rsx_cen2018_gauss_weights(int32_t sigma_gauss, float *out, int32_t max);
+int rsx_cen2018_debug_image(rsx_cen2018 *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2018_params *params,
+                            float *out_mean, float *out_sigma, float *out_p, float *out_y);
+
 /* Introspection of the candidate stage (host only, no device needed): the ring-key search tree the detector would build
  * over `n` keys of 20 floats -- nanoflann's tree (KDTreeVectorOfVectorsAdaptor.h:49-117, leaf size 10, Scancontext.cpp:284,356)
  * rebuilt node for node, because the order in which tied neighbours come back is the order of its leaves.  out_vind[n] =

@@ -97,6 +97,10 @@ class Cen2019Params(C.Structure):
     _fields_ = [("max_points", C.c_int32), ("min_range", C.c_int32)]
 
 
+class Cen2018Params(C.Structure):
+    _fields_ = [("zq", C.c_float), ("sigma_gauss", C.c_int32), ("min_range", C.c_int32), ("reserved", C.c_int32)]
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -140,6 +144,9 @@ SYMBOLS = [
     "rsx_orora_max_clique_batch", "rsx_orora_max_clique_batch_device", "rsx_orora_last_pmc_info",
     "rsx_cen2019_default_params", "rsx_cen2019_create", "rsx_cen2019_destroy", "rsx_cen2019_extract",
     "rsx_cen2019_extract_batch", "rsx_cen2019_extract_batch_device",
+    "rsx_cen2018_default_params", "rsx_cen2018_create", "rsx_cen2018_destroy", "rsx_cen2018_extract",
+    "rsx_cen2018_extract_batch", "rsx_cen2018_extract_batch_device", "rsx_cen2018_gauss_weights", "rsx_cen2018_debug_image",
+    "rsx_odometry_set_cen2018",
     "rsx_frontend_default_params", "rsx_frontend_create", "rsx_frontend_destroy", "rsx_frontend_cartesian",
     "rsx_frontend_describe", "rsx_frontend_match",
     "rsx_frontend_cartesian_batch_device", "rsx_frontend_cartesian_batch_device_az", "rsx_frontend_describe_batch_device", "rsx_frontend_match_consecutive_device",
@@ -248,6 +255,16 @@ def lib():
         L.rsx_cen2019_extract_batch.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(Cen2019Params), vp, i32, C.c_float, vp, vp, i32, vp]
         L.rsx_cen2019_extract_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(Cen2019Params), vp, i32, C.c_float, vp, vp,
                                                        i32, vp, vp]
+        L.rsx_cen2018_default_params.argtypes = [C.POINTER(Cen2018Params)]
+        L.rsx_cen2018_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+        L.rsx_cen2018_destroy.argtypes = [vp]
+        L.rsx_cen2018_extract.argtypes = [vp, vp, i32, i32, C.POINTER(Cen2018Params), vp, C.c_float, vp, vp, i32, C.POINTER(i32)]
+        L.rsx_cen2018_extract_batch.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(Cen2018Params), vp, i32, C.c_float, vp, vp, i32, vp]
+        L.rsx_cen2018_extract_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(Cen2018Params), vp, i32, C.c_float, vp, vp,
+                                                       i32, vp, vp]
+        L.rsx_cen2018_gauss_weights.argtypes = [i32, vp, i32]
+        L.rsx_cen2018_debug_image.argtypes = [vp, vp, i32, i32, C.POINTER(Cen2018Params), vp, vp, vp, vp]
+        L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_frontend_default_params.argtypes = [C.POINTER(FrontendParams)]
         L.rsx_frontend_create.argtypes = [C.c_int, i32, i32, C.POINTER(FrontendParams), C.POINTER(vp)]
         L.rsx_frontend_destroy.argtypes = [vp]

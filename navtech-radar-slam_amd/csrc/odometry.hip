@@ -5,7 +5,8 @@
 // -> ORB descriptors -> BFMatcher knnMatch(2) + ratio against the previous scan -> ORORA (GNC rotation, A-COTE
 // translation) -> pose composition.  The sequence is on disk, so every scan and every consecutive pair is independent
 // until the final composition: a WINDOW of n scans goes through each stage in ONE launch chain --
-//     rsx_cen2019_extract_batch_device          n images   (csrc/cen2019.hip)
+//     rsx_cen2019_extract_batch_device          n images   (csrc/cen2019.hip; or rsx_cen2018_extract_batch_device, csrc/cen2018.hip,
+//                                               after rsx_odometry_set_cen2018)
 //     rsx_frontend_cartesian_batch_device       n images   (csrc/frontend.hip)
 //     rsx_frontend_describe_batch_device        n keypoint sets
 //     rsx_frontend_match_consecutive_device     all consecutive pairs, both directions
@@ -22,6 +23,7 @@
 #include <mutex>
 #include <new>
 
+#include "cen2018.h"
 #include "rsx_common.h"
 
 namespace {
@@ -121,6 +123,9 @@ struct rsx_odometry {
   rsx::Stream lane_stream[N_LANES], match_stream, copy_stream;
   rsx::Event ev_up, ev_e[N_SETS], ev_m[N_SETS];
   rsx::Owned<rsx_cen2019, rsx_cen2019_destroy> cen[N_LANES];
+  rsx::Owned<rsx_cen2018, rsx_cen2018_destroy> cen18[N_LANES];  // created at the first rsx_odometry_set_cen2018
+  bool use_cen2018 = false;
+  rsx_cen2018_params cen18_prm{};
   rsx::Owned<rsx_frontend, rsx_frontend_destroy> fe[N_LANES];
   rsx::Owned<rsx_orora, rsx_orora_destroy> reg;
   OdoSet set[N_SETS];
@@ -160,7 +165,7 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
   return RSX_OK;
 }
 
-// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through cen2019, the Cartesian images and the
+// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through cen2019 (or cen2018), the Cartesian images and the
 // descriptors into set g % 3, then its last scan into slot 0 of the next set.  Asynchronous on the stream of lane g & 1.
 int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, int64_t img_stride, int32_t row_stride, const float *azimuths,
                     int32_t azimuths_per_image) {
@@ -177,9 +182,14 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   std::memcpy(paz, azimuths, na * 4);
   RSX_HIP(hipMemcpyAsync(q.az.p, paz, na * 4, hipMemcpyHostToDevice, s));
   int32_t *d_counts = q.counts.as<int32_t>();
-  RSX_TRY(rsx_cen2019_extract_batch_device(h->cen[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, &h->prm.cen, q.az.as<float>(),
-                                           azimuths_per_image, h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy,
-                                           q.xy.as<float>() + slot_xy, K, d_counts + 1, s));
+  if (h->use_cen2018)
+    RSX_TRY(rsx_cen2018_extract_batch_device(h->cen18[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, &h->cen18_prm, q.az.as<float>(),
+                                             azimuths_per_image, h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy,
+                                             q.xy.as<float>() + slot_xy, K, d_counts + 1, s));
+  else
+    RSX_TRY(rsx_cen2019_extract_batch_device(h->cen[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, &h->prm.cen, q.az.as<float>(),
+                                             azimuths_per_image, h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy,
+                                             q.xy.as<float>() + slot_xy, K, d_counts + 1, s));
   // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
   // how the sequence is cut into windows, and nothing about the grids is looked at on the host
   RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
@@ -368,6 +378,26 @@ int rsx_odometry_reset(rsx_odometry *h) try {
 } RSX_CATCH_ALL
 
 int rsx_odometry_window(void) { return MAX_WINDOW; }
+
+int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one pair, one extractor)");
+  if (!params) {
+    h->use_cen2018 = false;
+    return RSX_OK;
+  }
+  RSX_TRY(rsx::cen2018_check_params(*params));
+  for (int l = 0; l < N_LANES; l++) {
+    if (h->cen18[l]) continue;
+    rsx_cen2018 *c = nullptr;
+    RSX_TRY(rsx_cen2018_create(h->device, h->rows, h->cols, &c));
+    h->cen18[l].reset(c);
+  }
+  h->cen18_prm = *params;
+  h->use_cen2018 = true;
+  return RSX_OK;
+} RSX_CATCH_ALL
 
 int rsx_odometry_push_device(rsx_odometry *h, const uint8_t *d_imgs, int32_t n_scans, int64_t image_stride_bytes, int32_t row_stride,
                              const float *azimuths, int32_t azimuths_per_image, rsx_odometry_scan *out, float *out_xy, int32_t max_xy) try {

@@ -20,6 +20,8 @@
 // with the PMC library (round 6: csrc/pmc.hip behind RSX_ORORA_PMC, on by default; `--no-pmc` feeds the solver every
 // cross-checked ratio match, the pipeline of rounds 3-5).
 // `--matcher nn` selects the round-1 stand-in instead (mutual nearest neighbours in the sensor frame, no descriptors).
+// `--keypoints cen2018` (with `--zq`, `--sigma-gauss`; min_range stays 58) finds the keypoints with cen2018 instead of cen2019
+// (upstream's keypoint_extraction = 0: rsx_odometry_set_cen2018 on the windowed path, rsx_cen2018_extract on --per-scan).
 //
 // Output: one line per frame on stdout / --out file:  stamp_ns x y yaw n_keypoints n_matches
 // With -DRSX_WITH_ROS (ROS 1 present) the same data is also published on /orora/odom and
@@ -124,11 +126,13 @@ void associate(const Scan &prev, const Scan &cur, float gate, std::vector<float>
 
 int main(int argc, char **argv) {
   try {
-    std::string seq_dir, out_path, record_path, matcher = "orb";
+    std::string seq_dir, out_path, record_path, matcher = "orb", keypoints = "cen2019";
     int max_frames = -1, device = 0, window = 0, threads = 0;
     bool per_scan = false, timing = false, use_pmc = true;
     double rate_hz = 0.0;
     float gate = 6.0f;
+    rsx_cen2018_params c18;
+    rsx_cen2018_default_params(&c18);
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       if (a == "--out" && i + 1 < argc) out_path = argv[++i];
@@ -138,6 +142,9 @@ int main(int argc, char **argv) {
       else if (a == "--matcher" && i + 1 < argc) matcher = argv[++i];  // orb (default) | nn
       else if (a == "--window" && i + 1 < argc) window = std::atoi(argv[++i]);    // scans per rsx_odometry_push (default: two of the library's windows)
       else if (a == "--threads" && i + 1 < argc) threads = std::atoi(argv[++i]);  // PNG decode threads (default: twice the usable cores, <= 64)
+      else if (a == "--keypoints" && i + 1 < argc) keypoints = argv[++i];         // cen2019 (default) | cen2018
+      else if (a == "--zq" && i + 1 < argc) c18.zq = (float)std::atof(argv[++i]);  // cen2018: threshold in noise sigmas (3.0)
+      else if (a == "--sigma-gauss" && i + 1 < argc) c18.sigma_gauss = std::atoi(argv[++i]);  // cen2018: Gaussian sigma in range bins, odd (17)
       else if (a == "--no-pmc") use_pmc = false;                                   // skip the max-clique inlier selection before the solver
       else if (a == "--per-scan") per_scan = true;                                // the round-2 loop: one scan per call, host vectors in between
       else if (a == "--timing") timing = true;                                    // decode / pipeline seconds on stderr
@@ -150,7 +157,8 @@ int main(int argc, char **argv) {
     }
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
-      die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--window W] [--threads T] [--per-scan] [--no-pmc] [--timing]");
+      die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018] [--zq Z] [--sigma-gauss S] [--window W] [--threads T] "
+          "[--per-scan] [--no-pmc] [--timing]");
     const std::string dir = seq_dir + "/polar_oxford_form";
     std::vector<std::string> files;
     if (DIR *d = opendir(dir.c_str())) {
@@ -240,6 +248,8 @@ int main(int argc, char **argv) {
       pyaw += r.yaw;
     };
     if (matcher != "nn" && matcher != "orb") die("--matcher must be orb or nn");
+    if (keypoints != "cen2019" && keypoints != "cen2018") die("--keypoints must be cen2019 or cen2018");
+    const bool use_c18 = keypoints == "cen2018";
 
     if (matcher == "orb" && !per_scan) {
       // ---------------- windows of scans through rsx_odometry_push ----------------
@@ -256,6 +266,7 @@ int main(int argc, char **argv) {
       if (!use_pmc) op.orora.flags &= ~RSX_ORORA_PMC;
       rsx_odometry *odo = nullptr;
       check(rsx_odometry_create(&op, rows, cols, &odo), "rsx_odometry_create");
+      if (use_c18) check(rsx_odometry_set_cen2018(odo, &c18), "rsx_odometry_set_cen2018");
       // scans per rsx_odometry_push: two of the library's internal windows, so that inside a call the upload and the extraction of
       // the second overlap the matching of the first (the pinned buffers are 2 x W images)
       const int W = window > 0 ? std::min(window, 4096) : 2 * rsx_odometry_window();
@@ -416,6 +427,7 @@ int main(int argc, char **argv) {
 
     // ---------------- one scan per call (round-2 loop; also the `nn` stand-in matcher) ----------------
     rsx_cen2019 *cen = nullptr;
+    rsx_cen2018 *cen18 = nullptr;
     rsx_orora *reg = nullptr;
     rsx_frontend *fe = nullptr;
     const bool use_orb = matcher != "nn";
@@ -429,10 +441,11 @@ int main(int argc, char **argv) {
     for (size_t fi = 0; fi < files.size(); fi++) {
       int w = 0, h = 0;
       const std::vector<uint8_t> img = read_png_gray8(dir + "/" + files[fi], &w, &h);
-      if (!cen) {
+      if (!cen && !cen18) {
         rows = h;
         cols = w - kMeta;
-        check(rsx_cen2019_create(device, rows, cols, &cen), "rsx_cen2019_create");
+        if (use_c18) check(rsx_cen2018_create(device, rows, cols, &cen18), "rsx_cen2018_create");
+        else check(rsx_cen2019_create(device, rows, cols, &cen), "rsx_cen2019_create");
         if (use_orb) check(rsx_frontend_create(device, rows, cols, nullptr, &fe), "rsx_frontend_create");
         az.resize((size_t)rows);
       } else if (h != rows || w - kMeta != cols) {
@@ -447,8 +460,12 @@ int main(int argc, char **argv) {
         az[(size_t)a] = (float)((double)cnt * 2.0 * M_PI / 5600.0);
       }
       int32_t n = 0;
-      check(rsx_cen2019_extract(cen, img.data(), w, kMeta, &cp, az.data(), kResolution, targets.data(), xy.data(), 200000, &n),
-            "rsx_cen2019_extract");
+      if (use_c18)
+        check(rsx_cen2018_extract(cen18, img.data(), w, kMeta, &c18, az.data(), kResolution, targets.data(), xy.data(), 200000, &n),
+              "rsx_cen2018_extract");
+      else
+        check(rsx_cen2019_extract(cen, img.data(), w, kMeta, &cp, az.data(), kResolution, targets.data(), xy.data(), 200000, &n),
+              "rsx_cen2019_extract");
       n = std::min(n, 200000);
       cur.xy.assign(xy.begin(), xy.begin() + 2 * (size_t)n);
       if (use_orb) {
@@ -509,6 +526,7 @@ int main(int argc, char **argv) {
     if (out != stdout) std::fclose(out);
     if (rec) std::fclose(rec);
     rsx_cen2019_destroy(cen);
+    rsx_cen2018_destroy(cen18);
     rsx_orora_destroy(reg);
     rsx_frontend_destroy(fe);
     return 0;

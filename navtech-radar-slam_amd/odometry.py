@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import ODOMETRY_SCAN_DTYPE, OdometryParams, check, lib
+from ._rsx import ODOMETRY_SCAN_DTYPE, Cen2018Params, OdometryParams, check, lib
 
 
 def default_params():
@@ -14,13 +14,30 @@ def default_params():
 
 
 class Odometry:
-    def __init__(self, rows=400, cols=3360, params=None, device=0):
+    """keypoints: "cen2019" (default) or "cen2018"; cen2018: its Cen2018Params (None: cen2018.default_params())."""
+
+    def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None):
+        if keypoints not in ("cen2019", "cen2018"):
+            raise ValueError("keypoints must be cen2019 or cen2018")
         self._L = lib()
         self.rows, self.cols = rows, cols
         self.params = params if params is not None else default_params()
         self.params.device = device
         self._h = C.c_void_p()
         check(self._L.rsx_odometry_create(C.byref(self.params), rows, cols, C.byref(self._h)))
+        if keypoints == "cen2018":
+            self.set_cen2018(cen2018)
+
+    def set_cen2018(self, cen2018=None, off=False):
+        """Switch to cen2018 keypoints (cen2018: Cen2018Params or None for the defaults), or back to cen2019 with off=True.
+        Only while the handle holds no scan (fresh, or after reset())."""
+        if off:
+            check(self._L.rsx_odometry_set_cen2018(self._h, None))
+            return
+        p = cen2018 if cen2018 is not None else Cen2018Params()
+        if cen2018 is None:
+            check(self._L.rsx_cen2018_default_params(C.byref(p)))
+        check(self._L.rsx_odometry_set_cen2018(self._h, C.byref(p)))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

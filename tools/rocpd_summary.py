@@ -18,7 +18,7 @@ def main(root, all_grids=False):
             print(f"{calls:7d} {total:14.3f} {avg:12.3f} {pct:7.2f}  {name[:110]}")
         print("\n== per-dispatch durations of the dominant kernel (largest grids first) ==")
         q = ("select name, grid_x*grid_y*grid_z as g, count(*), avg(duration)/1000.0, min(duration)/1000.0, max(duration)/1000.0 "
-             "from kernels where (name like '%_kernel%' or name like '%cen_%' or name like '%fe_%' or name like '%odo_%' or name like '%icp_%' or name like '%vg_%' or name like '%lv_%' or name like '%orora%' or name like '%pmc_%') "
+             "from kernels where (name like '%_kernel%' or name like '%cen_%' or name like '%c18_%' or name like '%fe_%' or name like '%odo_%' or name like '%icp_%' or name like '%vg_%' or name like '%lv_%' or name like '%orora%' or name like '%pmc_%') "
              "group by name, g order by avg(duration) desc limit " + ("40" if all_grids else "8"))
         try:
             for name, grid, n, avg, mn, mx in con.execute(q):
