@@ -4,6 +4,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._keypoints import _Extractor
 from ._rsx import Cen2018Params, check, lib
 
 
@@ -33,23 +34,8 @@ def gauss_weights(sigma_gauss):
     return w
 
 
-class Cen2018:
-    def __init__(self, rows=400, cols=3360, device=0):
-        self._L = lib()
-        self.rows, self.cols = rows, cols
-        self._h = C.c_void_p()
-        check(self._L.rsx_cen2018_create(device, rows, cols, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.rsx_cen2018_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class Cen2018(_Extractor):
+    _name = "cen2018"
 
     @staticmethod
     def default_params():
@@ -58,18 +44,8 @@ class Cen2018:
     def extract(self, img, col_offset=11, zq=3.0, sigma_gauss=17, min_range=58, azimuths=None, resolution=0.0595,
                 max_targets=200000, return_count=False):
         """img: (rows, row_stride) uint8.  -> targets (n,2) int32 [, xy (n,2) float32 if azimuths] [, the full count]."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        assert img.shape[0] == self.rows
-        p = Cen2018Params(zq, sigma_gauss, min_range, 0)
-        out = np.zeros((max(max_targets, 1), 2), dtype=np.int32)
-        xy = np.zeros((max(max_targets, 1), 2), dtype=np.float32) if azimuths is not None else None
-        az = np.ascontiguousarray(azimuths, dtype=np.float32) if azimuths is not None else None
-        n = C.c_int32()
-        check(self._L.rsx_cen2018_extract(self._h, img.ctypes.data, img.shape[1], col_offset, C.byref(p),
-                                          az.ctypes.data if az is not None else None, resolution, out.ctypes.data,
-                                          xy.ctypes.data if xy is not None else None, max_targets, C.byref(n)))
-        k = min(n.value, max_targets)
-        res = (out[:k].copy(),) + ((xy[:k].copy(),) if xy is not None else ()) + ((n.value,) if return_count else ())
+        tg, xy, count = self._extract(img, Cen2018Params(zq, sigma_gauss, min_range, 0), col_offset, azimuths, resolution, max_targets)
+        res = (tg,) + ((xy,) if xy is not None else ()) + ((count,) if return_count else ())
         return res if len(res) > 1 else res[0]
 
     def extract_batch(self, imgs, col_offset=11, zq=3.0, sigma_gauss=17, min_range=58, azimuths=None, resolution=0.0595,
@@ -80,24 +56,9 @@ class Cen2018:
         imgs = np.asarray(imgs, dtype=np.uint8)
         if imgs.strides[1:] != (imgs.shape[2], 1):
             imgs = np.ascontiguousarray(imgs)
-        n = imgs.shape[0]
-        assert imgs.shape[1] == self.rows
-        p = Cen2018Params(zq, sigma_gauss, min_range, 0)
-        mt = max(max_targets, 1)
-        out = np.zeros((n, mt, 2), dtype=np.int32)
-        az = np.ascontiguousarray(azimuths, dtype=np.float32) if azimuths is not None else None
-        xy = np.zeros((n, mt, 2), dtype=np.float32) if az is not None else None
-        counts = np.zeros(n, dtype=np.int32)
-        check(self._L.rsx_cen2018_extract_batch(self._h, imgs.ctypes.data, n, imgs.strides[0], imgs.shape[2], col_offset,
-                                                C.byref(p), az.ctypes.data if az is not None else None,
-                                                1 if (az is not None and az.ndim == 2) else 0, resolution, out.ctypes.data,
-                                                xy.ctypes.data if xy is not None else None, max_targets, counts.ctypes.data))
-        ks = np.minimum(counts, max_targets)
-        res = ([out[i, :ks[i]].copy() for i in range(n)],)
-        if xy is not None:
-            res += ([xy[i, :ks[i]].copy() for i in range(n)],)
-        if return_counts:
-            res += (counts,)
+        tg, xy, counts = self._extract_batch(imgs, Cen2018Params(zq, sigma_gauss, min_range, 0), col_offset, azimuths, resolution,
+                                             max_targets)
+        res = (tg,) + ((xy,) if xy is not None else ()) + ((counts,) if return_counts else ())
         return res if len(res) > 1 else res[0]
 
     def debug_image(self, img, col_offset=11, zq=3.0, sigma_gauss=17, min_range=58):

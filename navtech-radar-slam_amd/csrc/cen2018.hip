@@ -13,8 +13,8 @@
 //              into LDS, the smoothing (each lane two range bins 64 apart per step, packed fp32), the screen and the
 //              threshold, per-chunk ballots of the decisions -> runs and their medians (scalar bit scans) -> per-row
 //              keypoints + per-row count
-//   c18_pack   one wavefront per (azimuth, image): row-major packing of the rows' keypoints + polar -> Cartesian (the
-//              expression cen_pack uses)
+//   kp_pack    (keypoints_host.h, shared with cen2019) one wavefront per (azimuth, image): row-major packing of the rows'
+//              keypoints + polar -> Cartesian
 // Arithmetic: every fp32 operation separately rounded (-ffp-contract=off, explicit __f*_rn), the smoothing in ascending
 // tap order, sigma's sum sequential in fp64 over the byte values ascending: bit-identical to the restatement up to the
 // two fp64 exp per pixel (a device exp and a host exp may differ by an ulp; see tests/test_gpu_cen2018.py).
@@ -27,14 +27,13 @@
 #include <new>
 
 #include "cen2018.h"
-#include "rsx_common.h"
+#include "keypoints_host.h"
 
 namespace {
 
 constexpr int MAX_TAPS = 255;       // fsize = 3 sigma_gauss: sigma_gauss <= 85
 constexpr int MAX_COLS = 8192;      // LDS of c18_rows: 4 (cols + 128 + 255) + cols + 2048 bytes <= 43 KB
 constexpr int MAX_ROWS = 4096;
-constexpr int MAX_SUB_BATCH = 128;  // images per internal launch pair
 constexpr float SIGMA_NONE = 0.034f;  // sigma of a row without a negative q (upstream's fallback)
 
 struct Taps {  // passed by value: every lane reads w[k] at the same k, a uniform load from the kernel arguments
@@ -220,38 +219,6 @@ __global__ __launch_bounds__(64) void c18_rows(const uint8_t *__restrict__ imgs,
   }
 }
 
-// one wavefront per (azimuth, image): row-major packing of the rows' keypoints, polar -> Cartesian
-constexpr int PACK_WAVES = 4;  // azimuths per workgroup
-__global__ __launch_bounds__(64 * PACK_WAVES) void c18_pack(int rows, int row_cap, const uint16_t *__restrict__ row_kp,
-                                                            const unsigned *__restrict__ row_n, const float *__restrict__ az, int64_t az_stride,
-                                                            float resolution, int max_targets, int *__restrict__ targets, float *__restrict__ xy,
-                                                            int *__restrict__ counts) {
-  const int a = (int)blockIdx.x * PACK_WAVES + (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), img = blockIdx.y, lane = threadIdx.x & 63;
-  if (a >= rows) return;  // (wave-uniform; no barrier in this kernel)
-  const unsigned *rn = row_n + (int64_t)img * rows;
-  unsigned before = 0;
-  for (int r = lane; r < a; r += 64) before += rn[r];
-  before = wave_sum_u32(before);
-  const unsigned n = rn[a];
-  int *tg = targets + (int64_t)img * max_targets * 2;
-  float *pxy = xy ? xy + (int64_t)img * max_targets * 2 : nullptr;
-  const float *azi = az ? az + (int64_t)img * az_stride : nullptr;
-  const uint16_t *kp = row_kp + ((int64_t)img * rows + a) * row_cap;
-  for (unsigned i = lane; i < n; i += 64) {
-    const unsigned d = before + i;
-    if (d >= (unsigned)max_targets) break;
-    const int r = kp[i];
-    tg[2 * d] = a;
-    tg[2 * d + 1] = r;
-    if (pxy && azi) {
-      const float range = __fmul_rn(__fadd_rn((float)r, 0.5f), resolution);
-      pxy[2 * d] = __fmul_rn(range, cosf(azi[a]));
-      pxy[2 * d + 1] = __fmul_rn(range, sinf(azi[a]));
-    }
-  }
-  if (a == rows - 1 && lane == 0 && counts) counts[img] = (int)(before + n);
-}
-
 // the Gaussian of step 2 on the host: libm exp in double, float sum ascending, float division
 void gauss_weights(int sigma_gauss, float *w) {
   const int fsize = 3 * sigma_gauss, mu = fsize / 2;
@@ -270,10 +237,9 @@ struct rsx_cen2018 {
   int device = 0, rows = 0, cols = 0;
   std::mutex mu;
   rsx::Stream stream;
-  rsx::DevBuf img, row_kp, row_n, targets, xy, az, counts, dbg;
-  // the workspaces are shared by every call: a call on another stream than the previous one is ordered behind it
-  hipStream_t last_user_stream = nullptr;
-  rsx::Event stream_switch;
+  rsx::DevBuf row_kp, row_n, dbg;
+  rsx::KeypointStaging stage;
+  rsx::StreamOrder order;
 };
 
 using rsx::fail;
@@ -288,29 +254,10 @@ int rsx::cen2018_check_params(const rsx_cen2018_params &p) {
 
 namespace {
 
-int use_stream(rsx_cen2018 *h, void *stream, hipStream_t *s) {
-  *s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (h->last_user_stream && h->last_user_stream != *s) {
-    if (!h->stream_switch) RSX_HIP(h->stream_switch.create());
-    // (a previous stream the caller has destroyed in the meantime has drained: nothing to wait for)
-    if (hipEventRecord(h->stream_switch, h->last_user_stream) == hipSuccess) RSX_HIP(hipStreamWaitEvent(*s, h->stream_switch, 0));
-    else (void)hipGetLastError();
-  }
-  h->last_user_stream = *s;
-  return RSX_OK;
-}
-
 int get_params(const rsx_cen2018_params *params, rsx_cen2018_params *p) {
   rsx_cen2018_default_params(p);
   if (params) *p = *params;
   return rsx::cen2018_check_params(*p);
-}
-
-int check_layout(const rsx_cen2018 *h, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride, int32_t col_offset) {
-  if (col_offset < 0 || row_stride < col_offset + h->cols)
-    return fail(RSX_ERR_BAD_ARG, "row_stride %d too small for offset %d + %d columns", row_stride, col_offset, h->cols);
-  if (n_images > 1 && image_stride_bytes < (int64_t)h->rows * row_stride) return fail(RSX_ERR_BAD_ARG, "image_stride_bytes smaller than an image");
-  return RSX_OK;
 }
 
 Taps make_taps(const rsx_cen2018_params &p) {
@@ -329,17 +276,17 @@ int extract_device(rsx_cen2018 *h, const uint8_t *d_imgs, int64_t img_stride, in
   const Taps taps = make_taps(p);
   const int fsize = 3 * p.sigma_gauss;
   const size_t lds = c18_lds_bytes(cols, fsize);
-  for (int b0 = 0; b0 < nb; b0 += MAX_SUB_BATCH) {
-    const int n = nb - b0 < MAX_SUB_BATCH ? nb - b0 : MAX_SUB_BATCH;
+  for (int b0 = 0; b0 < nb; b0 += rsx::MAX_SUB_BATCH) {
+    const int n = nb - b0 < rsx::MAX_SUB_BATCH ? nb - b0 : rsx::MAX_SUB_BATCH;
     RSX_TRY(h->row_kp.reserve((size_t)n * rows * row_cap * 2, s, false));
     RSX_TRY(h->row_n.reserve((size_t)n * rows * 4, s, false));
     hipLaunchKernelGGL(c18_rows<false>, dim3((unsigned)rows, (unsigned)n), dim3(64), lds, s, d_imgs + (int64_t)b0 * img_stride, img_stride, rows, cols,
                        stride, off, taps, fsize, p.zq, p.min_range, row_cap, h->row_kp.as<uint16_t>(), h->row_n.as<unsigned>(), nullptr, nullptr,
                        nullptr, nullptr);
-    hipLaunchKernelGGL(c18_pack, dim3((unsigned)((rows + PACK_WAVES - 1) / PACK_WAVES), (unsigned)n), dim3(64 * PACK_WAVES), 0, s, rows, row_cap,
-                       h->row_kp.as<uint16_t>(), h->row_n.as<unsigned>(), d_az ? d_az + (int64_t)b0 * az_stride : nullptr, az_stride, resolution,
-                       max_targets, d_targets + (int64_t)b0 * max_targets * 2, d_xy ? d_xy + (int64_t)b0 * max_targets * 2 : nullptr,
-                       d_counts ? d_counts + b0 : nullptr);
+    hipLaunchKernelGGL(rsx::kp_pack<uint16_t>, dim3((unsigned)((rows + rsx::PACK_WAVES - 1) / rsx::PACK_WAVES), (unsigned)n), dim3(64 * rsx::PACK_WAVES),
+                       0, s, rows, row_cap, h->row_kp.as<uint16_t>(), h->row_n.as<unsigned>(), d_az ? d_az + (int64_t)b0 * az_stride : nullptr, az_stride,
+                       resolution, max_targets, d_targets + (int64_t)b0 * max_targets * 2, d_xy ? d_xy + (int64_t)b0 * max_targets * 2 : nullptr,
+                       d_counts ? d_counts + b0 : nullptr, nullptr, 0);
     RSX_HIP(hipGetLastError());
   }
   return RSX_OK;
@@ -388,15 +335,15 @@ int rsx_cen2018_extract_batch_device(rsx_cen2018 *h, const uint8_t *d_imgs, int3
                                      int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                      int32_t *d_counts, void *stream) try {
   if (!h || !d_imgs || !d_targets || n_images < 0 || max_targets < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  RSX_TRY(check_layout(h, n_images, image_stride_bytes, row_stride, col_offset));
+  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
   if (d_xy && !d_azimuths) return fail(RSX_ERR_BAD_ARG, "d_xy needs d_azimuths");
   rsx_cen2018_params p;
   RSX_TRY(get_params(params, &p));
   if (n_images == 0) return RSX_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s;
-  RSX_TRY(use_stream(h, stream, &s));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   return extract_device(h, d_imgs, image_stride_bytes, n_images, row_stride, col_offset, p, d_azimuths, azimuths_per_image ? h->rows : 0,
                         resolution, max_targets, d_targets, d_xy, d_counts, s);
 } RSX_CATCH_ALL
@@ -405,54 +352,22 @@ int rsx_cen2018_extract_batch(rsx_cen2018 *h, const uint8_t *imgs, int32_t n_ima
                               int32_t col_offset, const rsx_cen2018_params *params, const float *azimuths, int32_t azimuths_per_image,
                               float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_counts) try {
   if (!h || !imgs || !out_targets || !out_counts || n_images < 0 || max_targets < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  RSX_TRY(check_layout(h, n_images, image_stride_bytes, row_stride, col_offset));
+  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
   if (out_xy && !azimuths) return fail(RSX_ERR_BAD_ARG, "out_xy needs azimuths");
   rsx_cen2018_params p;
   RSX_TRY(get_params(params, &p));
   if (n_images == 0) return RSX_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s;
-  RSX_TRY(use_stream(h, nullptr, &s));
-  const size_t ibytes = (size_t)h->rows * row_stride;
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
   const int mt = max_targets > 0 ? max_targets : 1;
-  // sub-batches bound the staging memory; each one is a single upload, one launch pair, one download
-  for (int b0 = 0; b0 < n_images; b0 += MAX_SUB_BATCH) {
-    const int n = n_images - b0 < MAX_SUB_BATCH ? n_images - b0 : MAX_SUB_BATCH;
-    RSX_TRY(h->img.reserve(ibytes * n, s, false));
-    RSX_TRY(h->targets.reserve((size_t)n * mt * 8, s, false));
-    RSX_TRY(h->xy.reserve((size_t)n * mt * 8, s, false));
-    RSX_TRY(h->counts.reserve((size_t)n * 4, s, false));
-    if (n == 1 || image_stride_bytes == (int64_t)ibytes) {
-      RSX_HIP(hipMemcpyAsync(h->img.p, imgs + (int64_t)b0 * image_stride_bytes, ibytes * n, hipMemcpyHostToDevice, s));
-    } else {
-      RSX_HIP(hipMemcpy2DAsync(h->img.p, ibytes, imgs + (int64_t)b0 * image_stride_bytes, (size_t)image_stride_bytes, ibytes, (size_t)n,
-                               hipMemcpyHostToDevice, s));
-    }
-    const float *d_az = nullptr;
-    if (azimuths) {
-      const size_t na = (size_t)h->rows * (azimuths_per_image ? n : 1);
-      RSX_TRY(h->az.reserve(na * 4, s, false));
-      RSX_HIP(hipMemcpyAsync(h->az.p, azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), na * 4, hipMemcpyHostToDevice, s));
-      d_az = h->az.as<float>();
-    }
-    RSX_TRY(extract_device(h, h->img.as<uint8_t>(), (int64_t)ibytes, n, row_stride, col_offset, p, d_az, azimuths_per_image ? h->rows : 0, resolution,
-                           mt, h->targets.as<int>(), d_az ? h->xy.as<float>() : nullptr, h->counts.as<int>(), s));
-    RSX_HIP(hipMemcpyAsync(out_counts + b0, h->counts.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    RSX_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < n; i++) {
-      const unsigned cnt = (unsigned)out_counts[b0 + i];
-      const unsigned w = cnt < (unsigned)max_targets ? cnt : (unsigned)max_targets;
-      if (!w) continue;
-      RSX_HIP(hipMemcpyAsync(out_targets + (int64_t)(b0 + i) * max_targets * 2, h->targets.as<int>() + (int64_t)i * mt * 2, (size_t)w * 8,
-                             hipMemcpyDeviceToHost, s));
-      if (out_xy)
-        RSX_HIP(hipMemcpyAsync(out_xy + (int64_t)(b0 + i) * max_targets * 2, h->xy.as<float>() + (int64_t)i * mt * 2, (size_t)w * 8,
-                               hipMemcpyDeviceToHost, s));
-    }
-    RSX_HIP(hipStreamSynchronize(s));
-  }
-  return RSX_OK;
+  auto extract = [&](const uint8_t *d_imgs, int n, const float *d_az, int *d_targets, float *d_xy, int *d_counts, hipStream_t st) {
+    return extract_device(h, d_imgs, (int64_t)h->rows * row_stride, n, row_stride, col_offset, p, d_az, azimuths_per_image ? h->rows : 0, resolution, mt, d_targets,
+                          d_xy, d_counts, st);
+  };
+  return h->stage.extract_batch(h->rows, imgs, n_images, image_stride_bytes, row_stride, azimuths, azimuths_per_image, out_targets, out_xy, max_targets,
+                                out_counts, s, extract);
 } RSX_CATCH_ALL
 
 int rsx_cen2018_extract(rsx_cen2018 *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2018_params *params,
@@ -476,22 +391,22 @@ int rsx_cen2018_gauss_weights(int32_t sigma_gauss, float *out, int32_t max) try 
 int rsx_cen2018_debug_image(rsx_cen2018 *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2018_params *params,
                             float *out_mean, float *out_sigma, float *out_p, float *out_y) try {
   if (!h || !img || !out_mean || !out_sigma || !out_p || !out_y) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  RSX_TRY(check_layout(h, 1, 0, row_stride, col_offset));
+  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, 1, 0, row_stride, col_offset));
   rsx_cen2018_params p;
   RSX_TRY(get_params(params, &p));
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s;
-  RSX_TRY(use_stream(h, nullptr, &s));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
   const int rows = h->rows, cols = h->cols, row_cap = cols / 2 + 1, fsize = 3 * p.sigma_gauss;
   const size_t ibytes = (size_t)rows * row_stride, px = (size_t)rows * cols * 4;
-  RSX_TRY(h->img.reserve(ibytes, s, false));
+  RSX_TRY(h->stage.img.reserve(ibytes, s, false));
   RSX_TRY(h->row_kp.reserve((size_t)rows * row_cap * 2, s, false));
   RSX_TRY(h->row_n.reserve((size_t)rows * 4, s, false));
   RSX_TRY(h->dbg.reserve(2 * px + (size_t)rows * 8, s, false));
-  RSX_HIP(hipMemcpyAsync(h->img.p, img, ibytes, hipMemcpyHostToDevice, s));
+  RSX_HIP(hipMemcpyAsync(h->stage.img.p, img, ibytes, hipMemcpyHostToDevice, s));
   float *dp = h->dbg.as<float>(), *dy = dp + (size_t)rows * cols, *dm = dy + (size_t)rows * cols, *ds = dm + rows;
-  hipLaunchKernelGGL(c18_rows<true>, dim3((unsigned)rows, 1u), dim3(64), c18_lds_bytes(cols, fsize), s, h->img.as<uint8_t>(), (int64_t)ibytes, rows, cols,
+  hipLaunchKernelGGL(c18_rows<true>, dim3((unsigned)rows, 1u), dim3(64), c18_lds_bytes(cols, fsize), s, h->stage.img.as<uint8_t>(), (int64_t)ibytes, rows, cols,
                      row_stride, col_offset, make_taps(p), fsize, p.zq, p.min_range, row_cap, h->row_kp.as<uint16_t>(), h->row_n.as<unsigned>(), dm, ds,
                      dp, dy);
   RSX_HIP(hipGetLastError());

@@ -28,7 +28,7 @@
 //   cen_runs     per azimuth: marks = OR over run flags (a hit sets the flag of the run(s) it touches); closed runs of marks
 //                and their arg-max by two plain max-scans; mark bits
 //   cen_adjacent per azimuth: keep the runs that meet a mark of the azimuth above or below, ordered compaction
-//   cen_pack     row-major packing of the rows' keypoints (+ polar -> Cartesian)
+//   kp_pack      (keypoints_host.h) row-major packing of the rows' keypoints (+ polar -> Cartesian)
 // One workgroup per (azimuth, image): a launch over a batch of B images is B x rows workgroups, every
 // dependency between passes is a kernel boundary, nothing returns to the host.  (A first version
 // folded the three small kernels into "last block done" tickets: a device-scope __threadfence per
@@ -44,14 +44,14 @@
 #include <new>
 #include <type_traits>
 
-#include "rsx_common.h"
+#include "keypoints_host.h"
 
 namespace {
 
 constexpr int NBIN = 4096;               // histogram of h over [-1, 1]
 constexpr double FIX = 1099511627776.0;  // 2^40
 constexpr unsigned long long KINF = ~0ull;
-constexpr int MAX_SUB_BATCH = 128;       // images per internal launch group (workspace = 14 MB per image)
+using rsx::MAX_SUB_BATCH;                // images per internal launch group (workspace = 14 MB per image)
 
 struct Scal {  // per image
   unsigned long long sum_bytes;
@@ -1654,48 +1654,14 @@ __global__ __launch_bounds__(64 * ADJ_WAVES) void cen_adjacent(int rows, int col
   if (lane == 0) row_n[(int64_t)img * rows + a] = done;
 }
 
-// one wavefront per (azimuth, image): row-major packing of the rows' keypoints, polar -> Cartesian
-constexpr int PACK_WAVES = 4;  // azimuths per workgroup
-__global__ __launch_bounds__(64 * PACK_WAVES) void cen_pack(Scal *scal, int rows, int row_cap, const int *__restrict__ row_out,
-                                                            const unsigned *__restrict__ row_n, const float *__restrict__ az, int64_t az_stride,
-                                                            float resolution, int max_targets, int *__restrict__ targets, float *__restrict__ xy,
-                                                            int *__restrict__ counts) {
-  const int a = (int)blockIdx.x * PACK_WAVES + (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), img = blockIdx.y, lane = threadIdx.x & 63;
-  if (a >= rows) return;  // (wave-uniform; no barrier in this kernel)
-  const unsigned *rn = row_n + (int64_t)img * rows;
-  unsigned before = 0;
-  for (int r = lane; r < a; r += 64) before += rn[r];
-  for (int o = 32; o >= 1; o >>= 1) before += __shfl_xor(before, o);
-  const unsigned n = rn[a];
-  int *tg = targets + (int64_t)img * max_targets * 2;
-  float *pxy = xy ? xy + (int64_t)img * max_targets * 2 : nullptr;
-  const float *azi = az ? az + (int64_t)img * az_stride : nullptr;
-  const int *ro = row_out + ((int64_t)img * rows + a) * row_cap;
-  for (unsigned i = lane; i < n; i += 64) {
-    const unsigned d = before + i;
-    if (d >= (unsigned)max_targets) break;
-    const int r = ro[i];
-    tg[2 * d] = a;
-    tg[2 * d + 1] = r;
-    if (pxy && azi) {
-      const float range = __fmul_rn(__fadd_rn((float)r, 0.5f), resolution);
-      pxy[2 * d] = __fmul_rn(range, cosf(azi[a]));
-      pxy[2 * d + 1] = __fmul_rn(range, sinf(azi[a]));
-    }
-  }
-  if (a == rows - 1 && lane == 0) {
-    scal[img].n_targets = before + n;
-    if (counts) counts[img] = (int)(before + n);
-  }
-}
-
 }  // namespace
 
 struct rsx_cen2019 {
   int device = 0, rows = 0, cols = 0;
   std::mutex mu;
   rsx::Stream stream;
-  rsx::DevBuf img, scal, hist, list, row_out, row_n, targets, xy, az, counts, opener, row_runs, row_nruns, markbits, wavemax, negmax;
+  rsx::DevBuf scal, hist, list, row_out, row_n, opener, row_runs, row_nruns, markbits, wavemax, negmax;
+  rsx::KeypointStaging stage;
   rsx::DevBuf one;          // single-scan entry: [count | targets | xy] in one piece, read back with one copy
   rsx::PinnedBuf one_host;  // its pinned mirror
 };
@@ -1749,8 +1715,9 @@ void launch_chain(rsx_cen2019 *h, const uint8_t *d_imgs, int64_t img_stride, int
                        h->markbits.as<MarkT<C>>(), h->wavemax.as<unsigned>(), rrpb);
   hipLaunchKernelGGL((cen_adjacent<C, NT>), dim3((unsigned)((rows + ADJ_WAVES - 1) / ADJ_WAVES), (unsigned)nb), dim3(64 * ADJ_WAVES), 0, s, rows, cols, row_cap, h->row_runs.as<uint2>(), h->row_nruns.as<unsigned>(),
                      h->markbits.as<MarkT<C>>(), h->row_out.as<int>(), h->row_n.as<unsigned>());
-  hipLaunchKernelGGL(cen_pack, dim3((unsigned)((rows + PACK_WAVES - 1) / PACK_WAVES), (unsigned)nb), dim3(64 * PACK_WAVES), 0, s, sc, rows, row_cap, h->row_out.as<int>(), h->row_n.as<unsigned>(), d_az, az_stride,
-                     resolution, max_targets, d_targets, d_xy, d_counts);
+  hipLaunchKernelGGL(rsx::kp_pack<int>, dim3((unsigned)((rows + rsx::PACK_WAVES - 1) / rsx::PACK_WAVES), (unsigned)nb), dim3(64 * rsx::PACK_WAVES), 0, s, rows,
+                     row_cap, h->row_out.as<int>(), h->row_n.as<unsigned>(), d_az, az_stride, resolution, max_targets, d_targets, d_xy, d_counts,
+                     &sc->n_targets, (int64_t)sizeof(Scal));
 }
 
 // d_imgs: nb device images img_stride bytes apart; results stay on the device: d_targets [nb][max_targets][2] int32,
@@ -1838,8 +1805,7 @@ int rsx_cen2019_extract_batch_device(rsx_cen2019 *h, const uint8_t *d_imgs, int3
                                      int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                      int32_t *d_counts, void *stream) try {
   if (!h || !d_imgs || !d_targets || n_images < 0 || max_targets < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (col_offset < 0 || row_stride < col_offset + h->cols) return fail(RSX_ERR_BAD_ARG, "row_stride %d too small for offset %d + %d columns", row_stride, col_offset, h->cols);
-  if (image_stride_bytes < (int64_t)h->rows * row_stride && n_images > 1) return fail(RSX_ERR_BAD_ARG, "image_stride_bytes smaller than an image");
+  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
   if (d_xy && !d_azimuths) return fail(RSX_ERR_BAD_ARG, "d_xy needs d_azimuths");
   if (n_images == 0) return RSX_OK;
   rsx_cen2019_params p;
@@ -1856,8 +1822,7 @@ int rsx_cen2019_extract_batch(rsx_cen2019 *h, const uint8_t *imgs, int32_t n_ima
                               int32_t col_offset, const rsx_cen2019_params *params, const float *azimuths, int32_t azimuths_per_image,
                               float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_counts) try {
   if (!h || !imgs || !out_targets || !out_counts || n_images < 0 || max_targets < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (col_offset < 0 || row_stride < col_offset + h->cols) return fail(RSX_ERR_BAD_ARG, "row_stride %d too small for offset %d + %d columns", row_stride, col_offset, h->cols);
-  if (n_images > 1 && image_stride_bytes < (int64_t)h->rows * row_stride) return fail(RSX_ERR_BAD_ARG, "image_stride_bytes smaller than an image");
+  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
   if (out_xy && !azimuths) return fail(RSX_ERR_BAD_ARG, "out_xy needs azimuths");
   if (n_images == 0) return RSX_OK;
   rsx_cen2019_params p;
@@ -1873,18 +1838,18 @@ int rsx_cen2019_extract_batch(rsx_cen2019 *h, const uint8_t *imgs, int32_t n_ima
     // rsx_host_alloc_pinned), the count and every keypoint slot come back in ONE copy into pinned memory, one synchronise
     // (before round 4: the count first, a synchronise, then the keypoints, a second synchronise)
     const size_t kp = (size_t)mt * 8, total = 256 + 2 * kp;
-    RSX_TRY(h->img.reserve(ibytes, s, false));
+    RSX_TRY(h->stage.img.reserve(ibytes, s, false));
     RSX_TRY(h->one.reserve(total, s, false));
     RSX_TRY(h->one_host.reserve(total));
-    RSX_HIP(hipMemcpyAsync(h->img.p, imgs, ibytes, hipMemcpyHostToDevice, s));
+    RSX_HIP(hipMemcpyAsync(h->stage.img.p, imgs, ibytes, hipMemcpyHostToDevice, s));
     const float *d_az = nullptr;
     if (azimuths) {
-      RSX_TRY(h->az.reserve((size_t)h->rows * 4, s, false));
-      RSX_HIP(hipMemcpyAsync(h->az.p, azimuths, (size_t)h->rows * 4, hipMemcpyHostToDevice, s));
-      d_az = h->az.as<float>();
+      RSX_TRY(h->stage.az.reserve((size_t)h->rows * 4, s, false));
+      RSX_HIP(hipMemcpyAsync(h->stage.az.p, azimuths, (size_t)h->rows * 4, hipMemcpyHostToDevice, s));
+      d_az = h->stage.az.as<float>();
     }
     char *d_one = h->one.as<char>();
-    RSX_TRY(extract_device(h, h->img.as<uint8_t>(), (int64_t)ibytes, 1, row_stride, col_offset, p, d_az, 0, resolution, mt,
+    RSX_TRY(extract_device(h, h->stage.img.as<uint8_t>(), (int64_t)ibytes, 1, row_stride, col_offset, p, d_az, 0, resolution, mt,
                            reinterpret_cast<int *>(d_one + 256), d_az ? reinterpret_cast<float *>(d_one + 256 + kp) : nullptr,
                            reinterpret_cast<int *>(d_one), s));
     // the count and the first 16 384 keypoint slots (a scan yields ~3 000) in one copy; a longer list takes a second one
@@ -1906,43 +1871,12 @@ int rsx_cen2019_extract_batch(rsx_cen2019 *h, const uint8_t *imgs, int32_t n_ima
     }
     return RSX_OK;
   }
-  // sub-batches bound the staging memory; each one is a single upload, one launch chain, one download
-  for (int b0 = 0; b0 < n_images; b0 += MAX_SUB_BATCH) {
-    const int n = n_images - b0 < MAX_SUB_BATCH ? n_images - b0 : MAX_SUB_BATCH;
-    RSX_TRY(h->img.reserve(ibytes * n, s, false));
-    RSX_TRY(h->targets.reserve((size_t)n * mt * 8, s, false));
-    RSX_TRY(h->xy.reserve((size_t)n * mt * 8, s, false));
-    RSX_TRY(h->counts.reserve((size_t)n * 4, s, false));
-    if (n == 1 || image_stride_bytes == (int64_t)ibytes) {
-      RSX_HIP(hipMemcpyAsync(h->img.p, imgs + (int64_t)b0 * image_stride_bytes, ibytes * n, hipMemcpyHostToDevice, s));
-    } else {
-      RSX_HIP(hipMemcpy2DAsync(h->img.p, ibytes, imgs + (int64_t)b0 * image_stride_bytes, (size_t)image_stride_bytes, ibytes, (size_t)n,
-                               hipMemcpyHostToDevice, s));
-    }
-    const float *d_az = nullptr;
-    if (azimuths) {
-      const size_t na = (size_t)h->rows * (azimuths_per_image ? n : 1);
-      RSX_TRY(h->az.reserve(na * 4, s, false));
-      RSX_HIP(hipMemcpyAsync(h->az.p, azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), na * 4, hipMemcpyHostToDevice, s));
-      d_az = h->az.as<float>();
-    }
-    RSX_TRY(extract_device(h, h->img.as<uint8_t>(), (int64_t)ibytes, n, row_stride, col_offset, p, d_az, azimuths_per_image ? h->rows : 0, resolution,
-                           mt, h->targets.as<int>(), d_az ? h->xy.as<float>() : nullptr, h->counts.as<int>(), s));
-    RSX_HIP(hipMemcpyAsync(out_counts + b0, h->counts.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    RSX_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < n; i++) {
-      const unsigned cnt = (unsigned)out_counts[b0 + i];
-      const unsigned w = cnt < (unsigned)max_targets ? cnt : (unsigned)max_targets;
-      if (!w) continue;
-      RSX_HIP(hipMemcpyAsync(out_targets + (int64_t)(b0 + i) * max_targets * 2, h->targets.as<int>() + (int64_t)i * mt * 2, (size_t)w * 8,
-                             hipMemcpyDeviceToHost, s));
-      if (out_xy)
-        RSX_HIP(hipMemcpyAsync(out_xy + (int64_t)(b0 + i) * max_targets * 2, h->xy.as<float>() + (int64_t)i * mt * 2, (size_t)w * 8,
-                               hipMemcpyDeviceToHost, s));
-    }
-    RSX_HIP(hipStreamSynchronize(s));
-  }
-  return RSX_OK;
+  auto extract = [&](const uint8_t *d_imgs, int n, const float *d_az, int *d_targets, float *d_xy, int *d_counts, hipStream_t st) {
+    return extract_device(h, d_imgs, (int64_t)ibytes, n, row_stride, col_offset, p, d_az, azimuths_per_image ? h->rows : 0, resolution, mt, d_targets,
+                          d_xy, d_counts, st);
+  };
+  return h->stage.extract_batch(h->rows, imgs, n_images, image_stride_bytes, row_stride, azimuths, azimuths_per_image, out_targets, out_xy, max_targets,
+                                out_counts, s, extract);
 } RSX_CATCH_ALL
 
 int rsx_cen2019_extract(rsx_cen2019 *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2019_params *params,

@@ -24,7 +24,7 @@
 #include <new>
 
 #include "cen2018.h"
-#include "rsx_common.h"
+#include "keypoints_host.h"
 
 namespace {
 
@@ -182,14 +182,12 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   std::memcpy(paz, azimuths, na * 4);
   RSX_HIP(hipMemcpyAsync(q.az.p, paz, na * 4, hipMemcpyHostToDevice, s));
   int32_t *d_counts = q.counts.as<int32_t>();
-  if (h->use_cen2018)
-    RSX_TRY(rsx_cen2018_extract_batch_device(h->cen18[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, &h->cen18_prm, q.az.as<float>(),
-                                             azimuths_per_image, h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy,
-                                             q.xy.as<float>() + slot_xy, K, d_counts + 1, s));
-  else
-    RSX_TRY(rsx_cen2019_extract_batch_device(h->cen[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, &h->prm.cen, q.az.as<float>(),
-                                             azimuths_per_image, h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy,
-                                             q.xy.as<float>() + slot_xy, K, d_counts + 1, s));
+  auto keypoints = [&](auto extract_batch_device, auto *cen, const auto *prm) {
+    return extract_batch_device(cen, d_imgs, n, img_stride, row_stride, h->prm.col_offset, prm, q.az.as<float>(), azimuths_per_image,
+                                h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy, q.xy.as<float>() + slot_xy, K, d_counts + 1, s);
+  };
+  RSX_TRY(h->use_cen2018 ? keypoints(rsx_cen2018_extract_batch_device, h->cen18[lane].get(), &h->cen18_prm)
+                         : keypoints(rsx_cen2019_extract_batch_device, h->cen[lane].get(), &h->prm.cen));
   // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
   // how the sequence is cut into windows, and nothing about the grids is looked at on the host
   RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
@@ -280,12 +278,6 @@ void abandon(rsx_odometry *h) {
   h->have_prev = false;
 }
 
-int check_layout(rsx_odometry *h, int32_t n, int64_t image_stride_bytes, int32_t row_stride) {
-  if (row_stride < h->prm.col_offset + h->cols) return fail(RSX_ERR_BAD_ARG, "row_stride %d too small for offset %d + %d columns", row_stride, h->prm.col_offset, h->cols);
-  if (n > 1 && image_stride_bytes < (int64_t)h->rows * row_stride) return fail(RSX_ERR_BAD_ARG, "image_stride_bytes smaller than an image");
-  return RSX_OK;
-}
-
 // the azimuth grids are host arrays here: every grid must ascend (the Cartesian remap divides by az[1] - az[0] on the
 // device, frontend.hip az_row_of: a zero or negative step would give NaN row indices and NaN images instead of a status)
 int check_azimuths(const rsx_odometry *h, const float *azimuths, int32_t per_image, int32_t n_scans) {
@@ -296,6 +288,40 @@ int check_azimuths(const rsx_odometry *h, const float *azimuths, int32_t per_ima
     if (!((double)az[1] - (double)az[0] > 0.0)) return fail(RSX_ERR_BAD_ARG, "azimuths must increase (scan %d)", g);
   }
   return RSX_OK;
+}
+
+// the arguments of rsx_odometry_push / rsx_odometry_push_device (imgs: host or device)
+int check_push(rsx_odometry *h, const uint8_t *imgs, int32_t n_scans, int64_t image_stride_bytes, int32_t row_stride, const float *azimuths,
+               int32_t azimuths_per_image, const rsx_odometry_scan *out, int32_t max_xy) {
+  if (!h || !imgs || !azimuths || !out || n_scans < 0 || max_xy < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  if (n_scans == 0) return RSX_OK;
+  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_scans, image_stride_bytes, row_stride, h->prm.col_offset));
+  return check_azimuths(h, azimuths, azimuths_per_image, n_scans);
+}
+
+// the windows of one call, three in flight: E(0), E(1), then per window M(g), E(g + 2) -- two extractions run beside this window's
+// matching -- and the wait for M(g).  stage(w, g, b0, n) enqueues E(g) of the call's window w (scans b0 .. b0 + n) once its images
+// are where the extraction can read them
+template <typename Stage>
+int push_windows(rsx_odometry *h, int32_t n_scans, rsx_odometry_scan *out, float *out_xy, int32_t max_xy, Stage &&stage) {
+  const int nwin = (n_scans + MAX_WINDOW - 1) / MAX_WINDOW;
+  auto extract = [&](int w, uint64_t g) -> int {
+    const int b0 = w * MAX_WINDOW;
+    return stage(w, g, b0, n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW);
+  };
+  int st = extract(0, h->windows);
+  if (st == RSX_OK && nwin > 1) st = extract(1, h->windows + 1);
+  for (int w = 0; w < nwin && st == RSX_OK; w++) {
+    const uint64_t g = h->windows + (uint64_t)w;
+    const int b0 = w * MAX_WINDOW, n = n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW;
+    int first = 0;
+    st = enqueue_match(h, g, n, &first);
+    if (st == RSX_OK && w + 2 < nwin) st = extract(w + 2, g + 2);
+    if (st == RSX_OK) st = finish_window(h, g, n, first, out + b0, out_xy ? out_xy + (size_t)b0 * max_xy * 2 : nullptr, max_xy);
+  }
+  h->windows += (uint64_t)nwin;
+  if (st != RSX_OK) abandon(h);
+  return st;
 }
 
 }  // namespace
@@ -401,40 +427,21 @@ int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params) 
 
 int rsx_odometry_push_device(rsx_odometry *h, const uint8_t *d_imgs, int32_t n_scans, int64_t image_stride_bytes, int32_t row_stride,
                              const float *azimuths, int32_t azimuths_per_image, rsx_odometry_scan *out, float *out_xy, int32_t max_xy) try {
-  if (!h || !d_imgs || !azimuths || !out || n_scans < 0 || max_xy < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  RSX_TRY(check_push(h, d_imgs, n_scans, image_stride_bytes, row_stride, azimuths, azimuths_per_image, out, max_xy));
   if (n_scans == 0) return RSX_OK;
-  RSX_TRY(check_layout(h, n_scans, image_stride_bytes, row_stride));
-  RSX_TRY(check_azimuths(h, azimuths, azimuths_per_image, n_scans));
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   RSX_TRY(reserve_all(h, 0, h->match_stream));
-  auto window = [&](int w, uint64_t g) -> int {  // E(g) of the call's window w
-    const int b0 = w * MAX_WINDOW, n = n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW;
+  return push_windows(h, n_scans, out, out_xy, max_xy, [&](int, uint64_t g, int b0, int n) {
     return enqueue_extract(h, g, d_imgs + (int64_t)b0 * image_stride_bytes, n, image_stride_bytes, row_stride,
                            azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), azimuths_per_image);
-  };
-  const int nwin = (n_scans + MAX_WINDOW - 1) / MAX_WINDOW;
-  int st = window(0, h->windows);
-  if (st == RSX_OK && nwin > 1) st = window(1, h->windows + 1);
-  for (int w = 0; w < nwin && st == RSX_OK; w++) {
-    const uint64_t g = h->windows + (uint64_t)w;
-    const int b0 = w * MAX_WINDOW, n = n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW;
-    int first = 0;
-    st = enqueue_match(h, g, n, &first);
-    if (st == RSX_OK && w + 2 < nwin) st = window(w + 2, g + 2);  // two extractions run beside this window's matching
-    if (st == RSX_OK) st = finish_window(h, g, n, first, out + b0, out_xy ? out_xy + (size_t)b0 * max_xy * 2 : nullptr, max_xy);
-  }
-  h->windows += (uint64_t)nwin;
-  if (st != RSX_OK) abandon(h);
-  return st;
+  });
 } RSX_CATCH_ALL
 
 int rsx_odometry_push(rsx_odometry *h, const uint8_t *imgs, int32_t n_scans, int64_t image_stride_bytes, int32_t row_stride,
                       const float *azimuths, int32_t azimuths_per_image, rsx_odometry_scan *out, float *out_xy, int32_t max_xy) try {
-  if (!h || !imgs || !azimuths || !out || n_scans < 0 || max_xy < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  RSX_TRY(check_push(h, imgs, n_scans, image_stride_bytes, row_stride, azimuths, azimuths_per_image, out, max_xy));
   if (n_scans == 0) return RSX_OK;
-  RSX_TRY(check_layout(h, n_scans, image_stride_bytes, row_stride));
-  RSX_TRY(check_azimuths(h, azimuths, azimuths_per_image, n_scans));
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   const size_t ibytes = (size_t)h->rows * row_stride;
@@ -444,37 +451,13 @@ int rsx_odometry_push(rsx_odometry *h, const uint8_t *imgs, int32_t n_scans, int
     hipStream_t cs;
     ~CopyDone() { (void)hipStreamSynchronize(cs); }
   } copy_done{h->copy_stream};
-  auto upload = [&](int b0, int n, void *dst) -> int {
-    const uint8_t *src = imgs + (int64_t)b0 * image_stride_bytes;
-    if (n == 1 || image_stride_bytes == (int64_t)ibytes) {
-      RSX_HIP(hipMemcpyAsync(dst, src, ibytes * n, hipMemcpyHostToDevice, h->copy_stream));
-    } else {
-      RSX_HIP(hipMemcpy2DAsync(dst, ibytes, src, (size_t)image_stride_bytes, ibytes, (size_t)n, hipMemcpyHostToDevice, h->copy_stream));
-    }
+  return push_windows(h, n_scans, out, out_xy, max_xy, [&](int w, uint64_t g, int b0, int n) -> int {  // E(g) behind its upload
+    uint8_t *d_imgs = h->imgs[w % N_SETS].as<uint8_t>();  // (the buffer was read by the extraction of window w - 3: long done)
+    RSX_TRY(rsx::upload_images(d_imgs, imgs + (int64_t)b0 * image_stride_bytes, n, ibytes, image_stride_bytes, h->copy_stream));
     RSX_HIP(hipEventRecord(h->ev_up, h->copy_stream));
-    return RSX_OK;
-  };
-  auto window = [&](int w, uint64_t g) -> int {  // E(g) of the call's window w, behind its upload
-    const int b0 = w * MAX_WINDOW, n = n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW;
-    RSX_TRY(upload(b0, n, h->imgs[w % N_SETS].p));  // (the buffer was read by the extraction of window w - 3: long done)
     RSX_HIP(hipStreamWaitEvent(h->lane_stream[g & 1], h->ev_up, 0));
-    return enqueue_extract(h, g, h->imgs[w % N_SETS].as<uint8_t>(), n, (int64_t)ibytes, row_stride,
-                           azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), azimuths_per_image);
-  };
-  const int nwin = (n_scans + MAX_WINDOW - 1) / MAX_WINDOW;
-  int st = window(0, h->windows);
-  if (st == RSX_OK && nwin > 1) st = window(1, h->windows + 1);
-  for (int w = 0; w < nwin && st == RSX_OK; w++) {
-    const uint64_t g = h->windows + (uint64_t)w;
-    const int b0 = w * MAX_WINDOW, n = n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW;
-    int first = 0;
-    st = enqueue_match(h, g, n, &first);
-    if (st == RSX_OK && w + 2 < nwin) st = window(w + 2, g + 2);
-    if (st == RSX_OK) st = finish_window(h, g, n, first, out + b0, out_xy ? out_xy + (size_t)b0 * max_xy * 2 : nullptr, max_xy);
-  }
-  h->windows += (uint64_t)nwin;
-  if (st != RSX_OK) abandon(h);
-  return st;
+    return enqueue_extract(h, g, d_imgs, n, (int64_t)ibytes, row_stride, azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), azimuths_per_image);
+  });
 } RSX_CATCH_ALL
 
 int rsx_host_alloc_pinned(size_t bytes, void **out) try {

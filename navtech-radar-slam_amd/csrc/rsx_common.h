@@ -199,6 +199,22 @@ struct Event {
   operator hipEvent_t() const { return e; }
 };
 
+// a handle whose workspaces are shared by every call: a call on another stream than the previous one is ordered behind it
+struct StreamOrder {
+  hipStream_t last = nullptr;
+  Event switched;
+  int enter(hipStream_t s) {
+    if (last && last != s) {
+      if (!switched) RSX_HIP(switched.create());
+      // (a previous stream the caller has destroyed in the meantime has drained: nothing to wait for)
+      if (hipEventRecord(switched, last) == hipSuccess) RSX_HIP(hipStreamWaitEvent(s, switched, 0));
+      else (void)hipGetLastError();
+    }
+    last = s;
+    return RSX_OK;
+  }
+};
+
 // a librsx handle owned by another one, freed by its own rsx_*_destroy: Owned<rsx_icp, rsx_icp_destroy>
 template <auto Destroy>
 struct Destroyer {

@@ -93,8 +93,7 @@ struct rsx_sc {
   hipEvent_t last_insert = nullptr;
   // the handle's workspaces (and the single-query path's arrival tickets, which must be zero between launches) are shared by
   // every call: when a call arrives on another stream than the previous one, the new stream is ordered behind the old
-  hipStream_t last_user_stream = nullptr;
-  Event stream_switch;
+  StreamOrder order;
   Stream up_stream, stream_b;
   Event up_ev[kMaxPieces], lane_ev;
 };
@@ -112,14 +111,7 @@ int set_device(rsx_sc *h) {
 int use_stream(rsx_sc *h, void *stream, hipStream_t *s) {
   *s = stream ? static_cast<hipStream_t>(stream) : h->stream;
   if (*s != h->stream && h->last_insert) RSX_HIP(hipStreamWaitEvent(*s, h->last_insert, 0));
-  if (h->last_user_stream && h->last_user_stream != *s) {
-    if (!h->stream_switch) RSX_HIP(h->stream_switch.create());
-    // (a previous stream the caller has destroyed in the meantime has drained: nothing to wait for)
-    if (hipEventRecord(h->stream_switch, h->last_user_stream) == hipSuccess) RSX_HIP(hipStreamWaitEvent(*s, h->stream_switch, 0));
-    else (void)hipGetLastError();
-  }
-  h->last_user_stream = *s;
-  return RSX_OK;
+  return h->order.enter(*s);
 }
 
 // one new entry from a cloud in device memory, all of it in one launch
