@@ -385,6 +385,56 @@ int rsx_orora_register_batch_device(rsx_orora *h, const float *d_src_xy, const f
                                     const int64_t *d_offsets, int32_t n_pairs, const rsx_orora_params *params,
                                     rsx_orora_result *d_out, void *stream);
 
+/* ============================== RANSAC / motion-compensated RANSAC ======================
+ * The two other motion estimators of the upstream file-based `odometry.cpp` entry (yeti_radar_odometry's Ransac and
+ * MotionDistortedRansac; Burnett et al. 2021 for the latter), beside ORORA.  Their sources are absent from the reference
+ * checkout (empty submodule), so these entries follow the published methods as restated in tests/ransac_np.py, which is the
+ * arithmetic contract -- parity unpinned.  2-D; no Doppler term; conventions of rsx_orora_register_batch (dst = R src + t).
+ * Rigid mode: H two-match hypotheses, closed-form rigid fit, refit over the winner's inliers.  Motion-compensated mode:
+ * every match carries dt = (time src was measured) - (time dst was measured) [s] and dst = exp(dt w) src for a constant
+ * body velocity w = (vx, vy, wz); hypotheses and refit by Gauss-Newton.  The sampler is counter based: a pair's result
+ * depends on its matches, (seed, K) and the parameters only, not on its place in the batch.  A hypothesis h is evaluated up
+ * to the first one whose inlier share exceeds inlier_ratio; the one with the most inliers wins, the lowest h on a tie.
+ * Stateless per call: a handle owns a stream and the staging buffers of the host-buffer entry; the device entry needs no
+ * workspace, so calls on different streams neither allocate nor wait for each other. */
+
+typedef struct rsx_ransac rsx_ransac;
+
+typedef struct {
+  double tolerance;          /* a match is an inlier when its residual is below this [m] (0.35) */
+  double inlier_ratio;       /* stop at the first hypothesis with more than this share of inliers (0.90); (0, 1] */
+  double gn_epsilon;         /* MC: Gauss-Newton stops when the step's norm falls below this (1e-5) */
+  double dt_scan;            /* MC: the reported pose is exp(dt_scan w) (0.25 s: a Navtech head at 4 Hz) */
+  int32_t max_iterations;    /* hypotheses H (100); 1 .. RSX_RANSAC_MAX_ITERATIONS */
+  int32_t max_gn_iterations; /* MC: Gauss-Newton step cap (10); 1 .. 100 */
+  uint64_t seed;
+  int32_t flags;             /* RSX_RANSAC_* */
+  int32_t reserved;
+} rsx_ransac_params;
+#define RSX_RANSAC_MOTION_COMPENSATED 1
+#define RSX_RANSAC_MAX_ITERATIONS 1024
+
+typedef struct {
+  double x, y, yaw;      /* dst = R(yaw) src + (x, y); MC: exp(dt_scan w) */
+  double vx, vy, wz;     /* MC: the body velocity [m/s, m/s, rad/s]; 0 in rigid mode */
+  int32_t inliers;       /* of the winning hypothesis (the refit runs over them) */
+  int32_t hypotheses;    /* evaluated: h_stop + 1 */
+  int32_t gn_iterations; /* MC: Gauss-Newton steps of the refit */
+  int32_t status;        /* 0 ok; 1 fewer than 2 matches; 2 more than 16384 matches; 4 no hypothesis had 2 inliers (1, 2, 4: identity) */
+} rsx_ransac_result;
+
+int rsx_ransac_default_params(rsx_ransac_params *p);
+int rsx_ransac_create(int device, rsx_ransac **out);
+int rsx_ransac_destroy(rsx_ransac *h);
+/* n_pairs scan pairs laid out as for rsx_orora_register_batch; dt [matches] (NULL unless RSX_RANSAC_MOTION_COMPENSATED);
+ * out [n_pairs]; out_inlier (optional) [matches]: 1 for the winner's inliers.  Host buffers, synchronous. */
+int rsx_ransac_estimate_batch(rsx_ransac *h, const float *src_xy, const float *dst_xy, const float *dt, const int64_t *offsets,
+                              int32_t n_pairs, const rsx_ransac_params *params, rsx_ransac_result *out, uint8_t *out_inlier);
+/* device buffers, asynchronous on `stream`; never allocates or synchronises */
+int rsx_ransac_estimate_batch_device(rsx_ransac *h, const float *d_src_xy, const float *d_dst_xy, const float *d_dt,
+                                     const int64_t *d_offsets, int32_t n_pairs, const rsx_ransac_params *params,
+                                     rsx_ransac_result *d_out, uint8_t *d_out_inlier, void *stream);
+
 /* ============================== cen2019 keypoint extraction ============================
  * Replaces the feature-extraction stage of the upstream file-based `odometry.cpp` entry
  * (reference README.md:27,29).  Source absent from the reference checkout (empty submodule):
@@ -561,6 +611,19 @@ int rsx_odometry_window(void);           /* scans per internal launch chain (lon
  * the handle holds no scan -- freshly created or after rsx_odometry_reset -- so that no pair is registered from keypoints of
  * two extractors; otherwise RSX_ERR_BAD_ARG.  rsx_odometry_scan.n_keypoints then counts cen2018 keypoints. */
 int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params);
+/* The motion estimator a pair's cross-checked matches go to: ORORA behind the max-clique selection (the default), rigid
+ * RANSAC or motion-compensated RANSAC (params = NULL: rsx_ransac_default_params; its MOTION_COMPENSATED flag follows
+ * `estimator`).  Independent of the extractor; like it, only accepted while the handle holds no scan.  With a RANSAC
+ * estimator the max-clique selection (an ORORA stage) does not run and rsx_odometry_scan.reg carries x, y, yaw and status
+ * (0, 1, 2 as for ORORA; 4: no hypothesis had 2 inliers), iterations = hypotheses evaluated, rot_inliers = trans_inliers =
+ * inliers.  MC time model: the keypoint on azimuth row a of a scan was measured (a + 0.5) / rows x dt_scan after the
+ * scan's start and scans start dt_scan apart, so a match of row a_cur of this scan with row a_prev of the previous one
+ * has dt = (float)(dt_scan x (1 + (a_cur - a_prev) / rows)); the pose is exp(dt_scan w), so the body velocity is
+ * log(pose) / dt_scan.  Per-row timestamps from the image metadata and dropped scans are not modelled. */
+#define RSX_ESTIMATOR_ORORA 0
+#define RSX_ESTIMATOR_RANSAC 1
+#define RSX_ESTIMATOR_MCRANSAC 2
+int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_params *params);
 /* n_scans consecutive scans, host images image_stride_bytes apart (rows x row_stride bytes each); azimuths: rows floats
  * (rad, increasing) shared by all scans or n_scans x rows when azimuths_per_image != 0.  out [n_scans]; out_xy
  * (optional) [n_scans][max_xy][2]: the scan's keypoints in metres in the sensor frame (/orora/cloud_local).  Synchronous. */

@@ -106,6 +106,18 @@ class OroraResult(C.Structure):
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
 
 
+class RansacParams(C.Structure):
+    _fields_ = [("tolerance", C.c_double), ("inlier_ratio", C.c_double), ("gn_epsilon", C.c_double), ("dt_scan", C.c_double),
+                ("max_iterations", C.c_int32), ("max_gn_iterations", C.c_int32), ("seed", C.c_uint64), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+RANSAC_MOTION_COMPENSATED = 1  # rsx_ransac_params.flags
+ESTIMATOR_ORORA, ESTIMATOR_RANSAC, ESTIMATOR_MCRANSAC = 0, 1, 2  # rsx_odometry_set_estimator
+RANSAC_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("vx", "<f8"), ("vy", "<f8"), ("wz", "<f8"), ("inliers", "<i4"),
+                                ("hypotheses", "<i4"), ("gn_iterations", "<i4"), ("status", "<i4")])
+
+
 class OdometryParams(C.Structure):
     _fields_ = [("cen", Cen2019Params), ("frontend", FrontendParams), ("orora", OroraParams), ("radar_resolution", C.c_float),
                 ("col_offset", C.c_int32), ("max_keypoints", C.c_int32), ("device", C.c_int32)]
@@ -146,7 +158,8 @@ SYMBOLS = [
     "rsx_cen2019_extract_batch", "rsx_cen2019_extract_batch_device",
     "rsx_cen2018_default_params", "rsx_cen2018_create", "rsx_cen2018_destroy", "rsx_cen2018_extract",
     "rsx_cen2018_extract_batch", "rsx_cen2018_extract_batch_device", "rsx_cen2018_gauss_weights", "rsx_cen2018_debug_image",
-    "rsx_odometry_set_cen2018",
+    "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator",
+    "rsx_ransac_default_params", "rsx_ransac_create", "rsx_ransac_destroy", "rsx_ransac_estimate_batch", "rsx_ransac_estimate_batch_device",
     "rsx_frontend_default_params", "rsx_frontend_create", "rsx_frontend_destroy", "rsx_frontend_cartesian",
     "rsx_frontend_describe", "rsx_frontend_match",
     "rsx_frontend_cartesian_batch_device", "rsx_frontend_cartesian_batch_device_az", "rsx_frontend_describe_batch_device", "rsx_frontend_match_consecutive_device",
@@ -265,6 +278,12 @@ def lib():
         L.rsx_cen2018_gauss_weights.argtypes = [i32, vp, i32]
         L.rsx_cen2018_debug_image.argtypes = [vp, vp, i32, i32, C.POINTER(Cen2018Params), vp, vp, vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
+        L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
+        L.rsx_ransac_default_params.argtypes = [C.POINTER(RansacParams)]
+        L.rsx_ransac_create.argtypes = [C.c_int, C.POINTER(vp)]
+        L.rsx_ransac_destroy.argtypes = [vp]
+        L.rsx_ransac_estimate_batch.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(RansacParams), vp, vp]
+        L.rsx_ransac_estimate_batch_device.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(RansacParams), vp, vp, vp]
         L.rsx_frontend_default_params.argtypes = [C.POINTER(FrontendParams)]
         L.rsx_frontend_create.argtypes = [C.c_int, i32, i32, C.POINTER(FrontendParams), C.POINTER(vp)]
         L.rsx_frontend_destroy.argtypes = [vp]

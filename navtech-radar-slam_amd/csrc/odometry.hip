@@ -13,6 +13,8 @@
 //     odo_cross / odo_gather                    cross check (the two directions must agree) + correspondence lists
 //     rsx_orora_register_batch_device           all pairs of the window in one call (csrc/orora.hip): max-clique inlier
 //                                               selection (csrc/pmc.hip, RSX_ORORA_PMC: on by default here) + the solver
+//                                               (or rsx_ransac_estimate_batch_device, csrc/ransac.hip, after
+//                                               rsx_odometry_set_estimator: no selection; MC-RANSAC also gets a dt per match)
 // -- with every intermediate (keypoints, descriptors, matches, correspondences) in HBM; one upload of the images and one
 // download of 48 bytes per scan (+ the keypoints when the caller wants /orora/cloud_local).  The last scan of a window
 // stays on the device as the "previous scan" of the next one.  Pose composition stays on the host (sequential, trivial).
@@ -25,6 +27,7 @@
 
 #include "cen2018.h"
 #include "keypoints_host.h"
+#include "ransac.h"
 
 namespace {
 
@@ -36,9 +39,13 @@ constexpr int MAX_WINDOW = RSX_ODO_WINDOW;  // scans per internal launch chain (
 // one block per consecutive pair j (slots A = first + j, B = A + 1): keep prev keypoint i when fwd[i] = k >= 0 and
 // bwd[k] = i, in ascending i (the order the host loop of round 2 produced); src = the CURRENT scan's point, dst = the
 // previous scan's point, so that ORORA returns the motion of the sensor expressed in the previous frame.
-__global__ __launch_bounds__(256) void odo_cross(const float *__restrict__ xy, const int32_t *__restrict__ counts, int stride, int first,
-                                                 const int32_t *__restrict__ fwd, const int32_t *__restrict__ bwd,
-                                                 float2 *__restrict__ stage_src, float2 *__restrict__ stage_dst, int32_t *__restrict__ pair_cnt) {
+// DT (motion-compensated RANSAC): also the time between the two measurements of a match, from the azimuth rows of its two
+// keypoints (targets [slot][stride][2], row first): dt = (float)(dt_scan (1 + (a_cur - a_prev) / rows)) -- include/rsx.h
+template <bool DT>
+__device__ __forceinline__ void cross_pair(const float *__restrict__ xy, const int32_t *__restrict__ counts, int stride, int first,
+                                           const int32_t *__restrict__ fwd, const int32_t *__restrict__ bwd, float2 *__restrict__ stage_src,
+                                           float2 *__restrict__ stage_dst, int32_t *__restrict__ pair_cnt, const int32_t *__restrict__ targets,
+                                           int rows, double dt_scan, float *__restrict__ stage_dt) {
   __shared__ unsigned s_w[4];
   const int j = blockIdx.x, A = first + j, B = A + 1;
   const int nA = counts[A] < stride ? counts[A] : stride, nB = counts[B] < stride ? counts[B] : stride;
@@ -66,11 +73,28 @@ __global__ __launch_bounds__(256) void odo_cross(const float *__restrict__ xy, c
       const unsigned pos = before + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
       ss[pos] = pb[k];
       sd[pos] = pa[i];
+      if constexpr (DT) {
+        const int a_prev = targets[((int64_t)A * stride + i) * 2], a_cur = targets[((int64_t)B * stride + k) * 2];
+        stage_dt[(int64_t)j * stride + pos] = (float)(dt_scan * (1.0 + (double)(a_cur - a_prev) / (double)rows));
+      }
     }
     run += total;
     __syncthreads();
   }
   if (threadIdx.x == 0) pair_cnt[j] = (int32_t)run;
+}
+
+__global__ __launch_bounds__(256) void odo_cross(const float *__restrict__ xy, const int32_t *__restrict__ counts, int stride, int first,
+                                                 const int32_t *__restrict__ fwd, const int32_t *__restrict__ bwd,
+                                                 float2 *__restrict__ stage_src, float2 *__restrict__ stage_dst, int32_t *__restrict__ pair_cnt) {
+  cross_pair<false>(xy, counts, stride, first, fwd, bwd, stage_src, stage_dst, pair_cnt, nullptr, 0, 0.0, nullptr);
+}
+
+__global__ __launch_bounds__(256) void odo_cross_dt(const float *__restrict__ xy, const int32_t *__restrict__ counts, int stride, int first,
+                                                    const int32_t *__restrict__ fwd, const int32_t *__restrict__ bwd,
+                                                    float2 *__restrict__ stage_src, float2 *__restrict__ stage_dst, int32_t *__restrict__ pair_cnt,
+                                                    const int32_t *__restrict__ targets, int rows, double dt_scan, float *__restrict__ stage_dt) {
+  cross_pair<true>(xy, counts, stride, first, fwd, bwd, stage_src, stage_dst, pair_cnt, targets, rows, dt_scan, stage_dt);
 }
 
 // one block per pair: contiguous correspondence arrays + the offsets rsx_orora_register_batch_device wants
@@ -94,6 +118,29 @@ __global__ __launch_bounds__(256) void odo_gather(const float2 *__restrict__ sta
     offsets[j] = before;
     if (j == n_pairs - 1) offsets[n_pairs] = before + n;
   }
+}
+
+// behind odo_gather (its offsets): the staged dt of every pair to where its matches went
+__global__ __launch_bounds__(256) void odo_gather_dt(const float *__restrict__ stage_dt, const int64_t *__restrict__ offsets, int stride,
+                                                     float *__restrict__ dt) {
+  const int j = blockIdx.x;
+  const int64_t o = offsets[j], n = offsets[j + 1] - o;
+  for (int64_t i = threadIdx.x; i < n; i += 256) dt[o + i] = stage_dt[(int64_t)j * stride + i];
+}
+
+// a RANSAC estimator's results in the records rsx_odometry_scan carries (include/rsx.h, rsx_odometry_set_estimator)
+__global__ __launch_bounds__(64) void odo_ransac_results(const rsx_ransac_result *__restrict__ in, int n_pairs, rsx_orora_result *__restrict__ out) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n_pairs) return;
+  const rsx_ransac_result r = in[j];
+  rsx_orora_result o;
+  o.x = r.x;
+  o.y = r.y;
+  o.yaw = r.yaw;
+  o.iterations = r.hypotheses;
+  o.rot_inliers = o.trans_inliers = r.inliers;
+  o.status = r.status;
+  out[j] = o;
 }
 
 }  // namespace
@@ -128,6 +175,10 @@ struct rsx_odometry {
   rsx_cen2018_params cen18_prm{};
   rsx::Owned<rsx_frontend, rsx_frontend_destroy> fe[N_LANES];
   rsx::Owned<rsx_orora, rsx_orora_destroy> reg;
+  int estimator = RSX_ESTIMATOR_ORORA;
+  rsx::Owned<rsx_ransac, rsx_ransac_destroy> ransac;  // created at the first rsx_odometry_set_estimator that asks for one
+  rsx_ransac_params ransac_prm{};
+  rsx::DevBuf ransac_res, stage_dt, dt;  // allocated only with a RANSAC estimator (stage_dt, dt: MC-RANSAC)
   OdoSet set[N_SETS];
   rsx::DevBuf imgs[N_SETS], fwd, bwd, stage_src, stage_dst, pair_cnt, src, dst, offsets, results;
   uint64_t windows = 0;  // windows enqueued since creation: window g works in set[g % N_SETS] on lane g & 1
@@ -162,6 +213,11 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
   RSX_TRY(h->dst.reserve((size_t)MAX_WINDOW * K * 8, s, false));
   RSX_TRY(h->offsets.reserve((size_t)(MAX_WINDOW + 1) * 8, s, false));
   RSX_TRY(h->results.reserve((size_t)MAX_WINDOW * sizeof(rsx_orora_result), s, false));
+  if (h->estimator != RSX_ESTIMATOR_ORORA) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
+  if (h->estimator == RSX_ESTIMATOR_MCRANSAC) {
+    RSX_TRY(h->stage_dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
+    RSX_TRY(h->dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
+  }
   return RSX_OK;
 }
 
@@ -201,6 +257,8 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   RSX_HIP(hipMemcpyAsync(nx.desc.p, q.desc.as<uint8_t>() + (size_t)n * K * 32, (size_t)K * 32, hipMemcpyDeviceToDevice, s));
   RSX_HIP(hipMemcpyAsync(nx.valid.p, q.valid.as<uint8_t>() + (size_t)n * K, (size_t)K, hipMemcpyDeviceToDevice, s));
   RSX_HIP(hipMemcpyAsync(nx.counts.p, d_counts + n, 4, hipMemcpyDeviceToDevice, s));
+  if (h->estimator == RSX_ESTIMATOR_MCRANSAC)  // the azimuth rows of the previous scan's keypoints: the dt of the straddling pair
+    RSX_HIP(hipMemcpyAsync(nx.targets.p, q.targets.as<int32_t>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
   RSX_HIP(hipEventRecord(h->ev_e[g % N_SETS], s));
   return RSX_OK;
 }
@@ -219,13 +277,29 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out) {
   if (n_pairs > 0) {
     RSX_TRY(rsx_frontend_match_consecutive_device(h->fe[g & 1].get(), q.desc.as<uint8_t>(), q.valid.as<uint8_t>(), d_counts, K, first, n_pairs,
                                                   h->prm.frontend.ratio, h->fwd.as<int32_t>(), h->bwd.as<int32_t>(), s));
-    hipLaunchKernelGGL(odo_cross, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
-                       h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>());
+    const bool mc = h->estimator == RSX_ESTIMATOR_MCRANSAC;
+    if (mc)
+      hipLaunchKernelGGL(odo_cross_dt, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
+                         h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>(),
+                         q.targets.as<int32_t>(), h->rows, h->ransac_prm.dt_scan, h->stage_dt.as<float>());
+    else
+      hipLaunchKernelGGL(odo_cross, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
+                         h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>());
     hipLaunchKernelGGL(odo_gather, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_src.as<float2>(), h->stage_dst.as<float2>(),
                        h->pair_cnt.as<int32_t>(), n_pairs, K, h->src.as<float2>(), h->dst.as<float2>(), h->offsets.as<int64_t>());
+    if (mc)
+      hipLaunchKernelGGL(odo_gather_dt, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_dt.as<float>(), h->offsets.as<int64_t>(), K, h->dt.as<float>());
     RSX_HIP(hipGetLastError());
-    RSX_TRY(rsx_orora_register_batch_device(h->reg.get(), h->src.as<float>(), h->dst.as<float>(), h->offsets.as<int64_t>(), n_pairs, &h->prm.orora,
-                                            h->results.as<rsx_orora_result>(), s));
+    if (h->estimator == RSX_ESTIMATOR_ORORA) {
+      RSX_TRY(rsx_orora_register_batch_device(h->reg.get(), h->src.as<float>(), h->dst.as<float>(), h->offsets.as<int64_t>(), n_pairs, &h->prm.orora,
+                                              h->results.as<rsx_orora_result>(), s));
+    } else {
+      RSX_TRY(rsx_ransac_estimate_batch_device(h->ransac.get(), h->src.as<float>(), h->dst.as<float>(), mc ? h->dt.as<float>() : nullptr,
+                                               h->offsets.as<int64_t>(), n_pairs, &h->ransac_prm, h->ransac_res.as<rsx_ransac_result>(), nullptr, s));
+      hipLaunchKernelGGL(odo_ransac_results, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->ransac_res.as<rsx_ransac_result>(), n_pairs,
+                         h->results.as<rsx_orora_result>());
+      RSX_HIP(hipGetLastError());
+    }
   }
   char *pin = static_cast<char *>(q.pin.p);
   RSX_HIP(hipMemcpyAsync(pin + PIN_COUNTS, d_counts, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, s));
@@ -422,6 +496,32 @@ int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params) 
   }
   h->cen18_prm = *params;
   h->use_cen2018 = true;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_params *params) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  if (estimator != RSX_ESTIMATOR_ORORA && estimator != RSX_ESTIMATOR_RANSAC && estimator != RSX_ESTIMATOR_MCRANSAC)
+    return fail(RSX_ERR_BAD_ARG, "unknown estimator %d", estimator);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
+  if (estimator == RSX_ESTIMATOR_ORORA) {
+    h->estimator = estimator;
+    return RSX_OK;
+  }
+  rsx_ransac_params p;
+  rsx_ransac_default_params(&p);
+  if (params) p = *params;
+  if (estimator == RSX_ESTIMATOR_MCRANSAC) p.flags |= RSX_RANSAC_MOTION_COMPENSATED;
+  else p.flags &= ~RSX_RANSAC_MOTION_COMPENSATED;
+  RSX_TRY(rsx::ransac_check_params(p));
+  if (!h->ransac) {
+    rsx_ransac *r = nullptr;
+    RSX_TRY(rsx_ransac_create(h->device, &r));
+    h->ransac.reset(r);
+  }
+  h->ransac_prm = p;
+  h->estimator = estimator;
   return RSX_OK;
 } RSX_CATCH_ALL
 

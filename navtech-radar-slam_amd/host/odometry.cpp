@@ -22,6 +22,9 @@
 // `--matcher nn` selects the round-1 stand-in instead (mutual nearest neighbours in the sensor frame, no descriptors).
 // `--keypoints cen2018` (with `--zq`, `--sigma-gauss`; min_range stays 58) finds the keypoints with cen2018 instead of cen2019
 // (upstream's keypoint_extraction = 0: rsx_odometry_set_cen2018 on the windowed path, rsx_cen2018_extract on --per-scan).
+// `--estimator ransac|mcransac` (with `--ransac-threshold`, `--ransac-iterations`, `--scan-period`) hands a pair's matches to
+// rigid RANSAC or motion-compensated RANSAC instead of the max-clique selection + ORORA (upstream's other estimators:
+// rsx_odometry_set_estimator, windowed path only; mcransac takes a match's time from the azimuth rows of its keypoints).
 //
 // Output: one line per frame on stdout / --out file:  stamp_ns x y yaw n_keypoints n_matches
 // With -DRSX_WITH_ROS (ROS 1 present) the same data is also published on /orora/odom and
@@ -126,13 +129,15 @@ void associate(const Scan &prev, const Scan &cur, float gate, std::vector<float>
 
 int main(int argc, char **argv) {
   try {
-    std::string seq_dir, out_path, record_path, matcher = "orb", keypoints = "cen2019";
+    std::string seq_dir, out_path, record_path, matcher = "orb", keypoints = "cen2019", estimator = "orora";
     int max_frames = -1, device = 0, window = 0, threads = 0;
     bool per_scan = false, timing = false, use_pmc = true;
     double rate_hz = 0.0;
     float gate = 6.0f;
     rsx_cen2018_params c18;
     rsx_cen2018_default_params(&c18);
+    rsx_ransac_params rsp;
+    rsx_ransac_default_params(&rsp);
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       if (a == "--out" && i + 1 < argc) out_path = argv[++i];
@@ -145,6 +150,10 @@ int main(int argc, char **argv) {
       else if (a == "--keypoints" && i + 1 < argc) keypoints = argv[++i];         // cen2019 (default) | cen2018
       else if (a == "--zq" && i + 1 < argc) c18.zq = (float)std::atof(argv[++i]);  // cen2018: threshold in noise sigmas (3.0)
       else if (a == "--sigma-gauss" && i + 1 < argc) c18.sigma_gauss = std::atoi(argv[++i]);  // cen2018: Gaussian sigma in range bins, odd (17)
+      else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac
+      else if (a == "--ransac-threshold" && i + 1 < argc) rsp.tolerance = std::atof(argv[++i]);        // inlier residual bound [m] (0.35)
+      else if (a == "--ransac-iterations" && i + 1 < argc) rsp.max_iterations = std::atoi(argv[++i]);  // hypotheses (100)
+      else if (a == "--scan-period" && i + 1 < argc) rsp.dt_scan = std::atof(argv[++i]);               // mcransac: seconds per scan (0.25)
       else if (a == "--no-pmc") use_pmc = false;                                   // skip the max-clique inlier selection before the solver
       else if (a == "--per-scan") per_scan = true;                                // the round-2 loop: one scan per call, host vectors in between
       else if (a == "--timing") timing = true;                                    // decode / pipeline seconds on stderr
@@ -158,7 +167,7 @@ int main(int argc, char **argv) {
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018] [--zq Z] [--sigma-gauss S] [--window W] [--threads T] "
-          "[--per-scan] [--no-pmc] [--timing]");
+          "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--per-scan] [--no-pmc] [--timing]");
     const std::string dir = seq_dir + "/polar_oxford_form";
     std::vector<std::string> files;
     if (DIR *d = opendir(dir.c_str())) {
@@ -250,6 +259,8 @@ int main(int argc, char **argv) {
     if (matcher != "nn" && matcher != "orb") die("--matcher must be orb or nn");
     if (keypoints != "cen2019" && keypoints != "cen2018") die("--keypoints must be cen2019 or cen2018");
     const bool use_c18 = keypoints == "cen2018";
+    if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac") die("--estimator must be orora, ransac or mcransac");
+    if (estimator != "orora" && (matcher != "orb" || per_scan)) die("--estimator " + estimator + " runs on the windowed path only (not with --per-scan / --matcher nn)");
 
     if (matcher == "orb" && !per_scan) {
       // ---------------- windows of scans through rsx_odometry_push ----------------
@@ -267,6 +278,8 @@ int main(int argc, char **argv) {
       rsx_odometry *odo = nullptr;
       check(rsx_odometry_create(&op, rows, cols, &odo), "rsx_odometry_create");
       if (use_c18) check(rsx_odometry_set_cen2018(odo, &c18), "rsx_odometry_set_cen2018");
+      if (estimator != "orora")
+        check(rsx_odometry_set_estimator(odo, estimator == "ransac" ? RSX_ESTIMATOR_RANSAC : RSX_ESTIMATOR_MCRANSAC, &rsp), "rsx_odometry_set_estimator");
       // scans per rsx_odometry_push: two of the library's internal windows, so that inside a call the upload and the extraction of
       // the second overlap the matching of the first (the pinned buffers are 2 x W images)
       const int W = window > 0 ? std::min(window, 4096) : 2 * rsx_odometry_window();

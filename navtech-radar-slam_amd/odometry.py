@@ -4,7 +4,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import ODOMETRY_SCAN_DTYPE, Cen2018Params, OdometryParams, check, lib
+from ._rsx import ODOMETRY_SCAN_DTYPE, Cen2018Params, OdometryParams, RansacParams, check, lib
+
+ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_*
 
 
 def default_params():
@@ -14,11 +16,14 @@ def default_params():
 
 
 class Odometry:
-    """keypoints: "cen2019" (default) or "cen2018"; cen2018: its Cen2018Params (None: cen2018.default_params())."""
+    """keypoints: "cen2019" (default) or "cen2018"; cen2018: its Cen2018Params (None: cen2018.default_params()).
+    estimator: "orora" (default), "ransac" or "mcransac"; ransac: their RansacParams (None: ransac.default_params())."""
 
-    def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None):
+    def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None):
         if keypoints not in ("cen2019", "cen2018"):
             raise ValueError("keypoints must be cen2019 or cen2018")
+        if estimator not in ESTIMATORS:
+            raise ValueError("estimator must be orora, ransac or mcransac")
         self._L = lib()
         self.rows, self.cols = rows, cols
         self.params = params if params is not None else default_params()
@@ -27,6 +32,14 @@ class Odometry:
         check(self._L.rsx_odometry_create(C.byref(self.params), rows, cols, C.byref(self._h)))
         if keypoints == "cen2018":
             self.set_cen2018(cen2018)
+        if estimator != "orora":
+            self.set_estimator(estimator, ransac)
+
+    def set_estimator(self, estimator, ransac=None):
+        """Switch the motion estimator (ransac: RansacParams or None for the defaults).  Only while the handle holds no scan."""
+        if ransac is not None and not isinstance(ransac, RansacParams):
+            raise TypeError("ransac must be RansacParams")
+        check(self._L.rsx_odometry_set_estimator(self._h, ESTIMATORS[estimator], C.byref(ransac) if ransac is not None else None))
 
     def set_cen2018(self, cen2018=None, off=False):
         """Switch to cen2018 keypoints (cen2018: Cen2018Params or None for the defaults), or back to cen2019 with off=True.

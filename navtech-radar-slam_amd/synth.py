@@ -169,6 +169,45 @@ def orora_pairs(seed, n_pairs, k_range=(300, 1500), outlier_range=(0.2, 0.6), ma
     return src, dst, offsets, truth
 
 
+def motion_distorted_pairs(seed, n_pairs, k=600, outlier=0.4, speed=(5.0, 20.0), max_wz=0.5, rows=400, dt_scan=0.25, max_range=150.0,
+                           max_row_step=3):
+    """n_pairs match sets of a sensor that moves at a constant body velocity w = (vx, vy, wz) WHILE it scans (what
+    motion-compensated RANSAC models): match i was measured on azimuth row a_prev of the previous scan and row
+    a_cur = a_prev +- a few of the current one, dt = (float)(dt_scan (1 + (a_cur - a_prev) / rows)) apart, and
+    dst = exp(dt w) src exactly before the inputs are rounded to fp32; a share `outlier` of the sources is replaced by
+    random points.  Speed |(vx, vy)| within `speed` m/s, heading within 0.2 rad of the x axis, |wz| <= max_wz rad/s.
+    -> src (M,2) f32, dst (M,2) f32, dt (M,) f32, offsets i64, truth (n_pairs,3) f64 = w, inlier (M,) bool."""
+    rng = np.random.default_rng(seed)
+    offsets = np.arange(n_pairs + 1, dtype=np.int64) * k
+    src = np.empty((n_pairs * k, 2), dtype=np.float32)
+    dst = np.empty((n_pairs * k, 2), dtype=np.float32)
+    dts = np.empty(n_pairs * k, dtype=np.float32)
+    inl = np.ones(n_pairs * k, dtype=bool)
+    truth = np.empty((n_pairs, 3))
+    for i in range(n_pairs):
+        v, head, wz = rng.uniform(*speed), rng.uniform(-0.2, 0.2), rng.uniform(-max_wz, max_wz)
+        vx, vy = v * np.cos(head), v * np.sin(head)
+        r, th = rng.uniform(4.0, max_range, k), rng.uniform(0.0, 2 * np.pi, k)
+        q = np.stack([r * np.cos(th), r * np.sin(th)], axis=1)
+        a_prev = rng.integers(0, rows, k)
+        a_cur = np.clip(a_prev + rng.integers(-max_row_step, max_row_step + 1, k), 0, rows - 1)
+        dt = (dt_scan * (1.0 + (a_cur - a_prev) / rows)).astype(np.float32)
+        t = wz * dt.astype(np.float64)
+        tt = np.where(np.abs(t) < 1e-9, 1.0, t)
+        A = np.where(np.abs(t) < 1e-9, 1.0, np.sin(t) / tt)
+        B = np.where(np.abs(t) < 1e-9, t / 2, (1 - np.cos(t)) / tt)
+        ux, uy = q[:, 0] - (A * vx - B * vy) * dt, q[:, 1] - (B * vx + A * vy) * dt   # q - V(t) (vx, vy) dt
+        p = np.stack([np.cos(t) * ux + np.sin(t) * uy, -np.sin(t) * ux + np.cos(t) * uy], axis=1)   # R(-t) .
+        out_idx = rng.choice(k, int(outlier * k), replace=False)
+        ro, to = rng.uniform(4.0, max_range, len(out_idx)), rng.uniform(0.0, 2 * np.pi, len(out_idx))
+        p[out_idx] = np.stack([ro * np.cos(to), ro * np.sin(to)], axis=1)
+        sl = slice(i * k, (i + 1) * k)
+        src[sl], dst[sl], dts[sl] = p, q, dt
+        inl[i * k + out_idx] = False
+        truth[i] = (vx, vy, wz)
+    return src, dst, dts, offsets, truth, inl
+
+
 # ---------------------------------------------------------------------------------------------
 # polar radar images in MulRan "polar_oxford_form" (SURVEY.md B.1): one row per azimuth,
 # bytes 0-7 int64 timestamp, 8-9 uint16 encoder count (azimuth = count * 2 pi / 5600), 10 valid
