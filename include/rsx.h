@@ -335,6 +335,10 @@ typedef struct {
                                       pruned to a maximum clique of the consistency graph  i ~ j  <=>
                                       | ||src_i - src_j|| - ||dst_i - dst_j|| | < tim_noise_bound  (csrc/pmc.hip, oracle/pmc_ref.h).
                                       rsx_odometry_default_params turns it on; the device entry needs rsx_orora_reserve first */
+#define RSX_ORORA_PMC_EXACT 8      /* (only with RSX_ORORA_PMC; a bad argument without it) the selection is exact: a branch-and-bound search
+                                      after the greedy stage returns a MAXIMUM clique -- the greedy one where it already is one, otherwise the
+                                      maximum clique first in the order (core number descending, index ascending) -- within
+                                      rsx_orora_clique_node_budget() search nodes per pair.  Off by default everywhere */
 
 typedef struct {
   double x, y, yaw;      /* dst = R(yaw) src + (x, y) */
@@ -356,6 +360,9 @@ typedef struct {
 #define RSX_ORORA_PMC_PROVEN 1       /* size == max_core + 1: the clique is a maximum one */
 #define RSX_ORORA_PMC_PASSTHROUGH 2  /* fewer than 2 or more than rsx_orora_max_clique_matches() matches: not pruned */
 #define RSX_ORORA_PMC_NO_WORKSPACE 4 /* (with PASSTHROUGH) the pair did not fit what rsx_orora_reserve sized: not pruned */
+#define RSX_ORORA_PMC_MAXIMUM 8      /* RSX_ORORA_PMC_EXACT: the clique is a maximum one (the search completed, or a bound proved it: set
+                                        beside PROVEN as well) */
+#define RSX_ORORA_PMC_BUDGET 16      /* RSX_ORORA_PMC_EXACT: the node budget ran out; the pair keeps its greedy clique */
 
 int rsx_orora_default_params(rsx_orora_params *p);
 int rsx_orora_max_correspondences(void);
@@ -374,6 +381,10 @@ int rsx_orora_max_clique_batch_device(rsx_orora *h, const float *d_src_xy, const
 /* the info records of the last rsx_orora_register_batch{,_device} call that ran with RSX_ORORA_PMC (synchronises the handle's
  * last stream; n_pairs as in that call) */
 int rsx_orora_last_pmc_info(rsx_orora *h, rsx_orora_pmc_info *out_info, int32_t n_pairs);
+/* RSX_ORORA_PMC_EXACT: the search nodes one pair may cost before it keeps its greedy clique (RSX_ORORA_PMC_BUDGET); a node = one
+ * branching vertex of the search.  Default 262144; nodes <= 0 is a bad argument */
+int rsx_orora_set_clique_node_budget(rsx_orora *h, int64_t nodes);
+int rsx_orora_clique_node_budget(rsx_orora *h, int64_t *out_nodes);
 int rsx_orora_create(int device, rsx_orora **out);
 int rsx_orora_destroy(rsx_orora *h);
 /* n_pairs scan pairs; pair i owns matches [offsets[i], offsets[i+1]) of the concatenated

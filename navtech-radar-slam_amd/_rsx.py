@@ -53,7 +53,8 @@ class RescoringStats(C.Structure):  # rsx_sc_rescoring_stats (include/rsx_diag.h
 
 
 ORORA_PMC = 4  # rsx_orora_params.flags: max-clique inlier selection before the solver
-ORORA_PMC_PROVEN, ORORA_PMC_PASSTHROUGH, ORORA_PMC_NO_WORKSPACE = 1, 2, 4
+ORORA_PMC_EXACT = 8  # (with ORORA_PMC) exact maximum clique within the handle's node budget
+ORORA_PMC_PROVEN, ORORA_PMC_PASSTHROUGH, ORORA_PMC_NO_WORKSPACE, ORORA_PMC_MAXIMUM, ORORA_PMC_BUDGET = 1, 2, 4, 8, 16
 PMC_INFO_DTYPE = np.dtype([("size", "<i4"), ("max_core", "<i4"), ("seeds", "<i4"), ("flags", "<i4")])
 
 
@@ -154,6 +155,7 @@ SYMBOLS = [
     "rsx_orora_default_params", "rsx_orora_max_correspondences", "rsx_orora_create", "rsx_orora_destroy",
     "rsx_orora_register_batch", "rsx_orora_register_batch_device", "rsx_orora_max_clique_matches", "rsx_orora_reserve",
     "rsx_orora_max_clique_batch", "rsx_orora_max_clique_batch_device", "rsx_orora_last_pmc_info",
+    "rsx_orora_set_clique_node_budget", "rsx_orora_clique_node_budget",
     "rsx_cen2019_default_params", "rsx_cen2019_create", "rsx_cen2019_destroy", "rsx_cen2019_extract",
     "rsx_cen2019_extract_batch", "rsx_cen2019_extract_batch_device",
     "rsx_cen2018_default_params", "rsx_cen2018_create", "rsx_cen2018_destroy", "rsx_cen2018_extract",
@@ -260,6 +262,8 @@ def lib():
         L.rsx_orora_max_clique_batch.argtypes = [vp, vp, vp, vp, i32, C.POINTER(OroraParams), vp, vp]
         L.rsx_orora_max_clique_batch_device.argtypes = [vp, vp, vp, vp, i32, C.POINTER(OroraParams), vp, vp, vp]
         L.rsx_orora_last_pmc_info.argtypes = [vp, vp, i32]
+        L.rsx_orora_set_clique_node_budget.argtypes = [vp, i64]
+        L.rsx_orora_clique_node_budget.argtypes = [vp, C.POINTER(i64)]
         L.rsx_cen2019_default_params.argtypes = [C.POINTER(Cen2019Params)]
         L.rsx_cen2019_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
         L.rsx_cen2019_destroy.argtypes = [vp]

@@ -794,6 +794,7 @@ struct rsx_orora {
   int64_t sel_cap = 0;             // matches sel_src / sel_dst hold (rsx_orora_reserve)
   hipStream_t last_stream = nullptr;  // of the last PMC call (rsx_orora_last_pmc_info waits for it)
   int32_t last_pmc_pairs = 0;
+  int64_t clique_node_budget = rsx::pmc::DEFAULT_NODE_BUDGET;  // RSX_ORORA_PMC_EXACT: search nodes per pair
   bool attr_set = false;
 };
 
@@ -855,6 +856,7 @@ int rsx_orora_register_batch_device(rsx_orora *h, const float *d_src_xy, const f
   rsx_orora_default_params(&dp);
   if (params) dp = *params;
   if (dp.max_iterations < 1 || !(dp.gnc_factor > 1.0)) return fail(RSX_ERR_BAD_ARG, "bad GNC params");
+  if ((dp.flags & RSX_ORORA_PMC_EXACT) && !(dp.flags & RSX_ORORA_PMC)) return fail(RSX_ERR_BAD_ARG, "RSX_ORORA_PMC_EXACT needs RSX_ORORA_PMC");
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   if (!h->attr_set) {
@@ -886,7 +888,8 @@ int rsx_orora_register_batch_device(rsx_orora *h, const float *d_src_xy, const f
     RSX_TRY(h->pmc_info.reserve((size_t)n_pairs * sizeof(rsx_orora_pmc_info), s, false));
     RSX_TRY(rsx::pmc::launch(h->pmc_ws, h->device, reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy),
                              d_offsets, n_pairs, dp.tim_noise_bound, nullptr, h->pmc_info.as<rsx_orora_pmc_info>(), h->sel_src.as<float2>(),
-                             h->sel_dst.as<float2>(), h->sel_cnt.as<int32_t>(), h->sel_cap, s));
+                             h->sel_dst.as<float2>(), h->sel_cnt.as<int32_t>(), h->sel_cap, s,
+                             (dp.flags & RSX_ORORA_PMC_EXACT) ? h->clique_node_budget : 0));
     sel = Selection{h->sel_src.as<float2>(), h->sel_dst.as<float2>(), h->sel_cnt.as<int32_t>()};
     h->last_stream = s;
     h->last_pmc_pairs = n_pairs;
@@ -957,11 +960,13 @@ int rsx_orora_max_clique_batch_device(rsx_orora *h, const float *d_src_xy, const
   rsx_orora_params dp;
   rsx_orora_default_params(&dp);
   if (params) dp = *params;
+  if ((dp.flags & RSX_ORORA_PMC_EXACT) && !(dp.flags & RSX_ORORA_PMC)) return fail(RSX_ERR_BAD_ARG, "RSX_ORORA_PMC_EXACT needs RSX_ORORA_PMC");
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
   return rsx::pmc::launch(h->pmc_ws, h->device, reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets,
-                          n_pairs, dp.tim_noise_bound, d_member, d_info, nullptr, nullptr, nullptr, 0, s);
+                          n_pairs, dp.tim_noise_bound, d_member, d_info, nullptr, nullptr, nullptr, 0, s,
+                          (dp.flags & RSX_ORORA_PMC_EXACT) ? h->clique_node_budget : 0);
 } RSX_CATCH_ALL
 
 int rsx_orora_max_clique_batch(rsx_orora *h, const float *src_xy, const float *dst_xy, const int64_t *offsets, int32_t n_pairs,
@@ -991,6 +996,20 @@ int rsx_orora_max_clique_batch(rsx_orora *h, const float *src_xy, const float *d
   if (out_member && m) RSX_HIP(hipMemcpyAsync(out_member, h->member.p, (size_t)m, hipMemcpyDeviceToHost, h->stream));
   if (out_info) RSX_HIP(hipMemcpyAsync(out_info, h->pmc_info.p, (size_t)n_pairs * sizeof(rsx_orora_pmc_info), hipMemcpyDeviceToHost, h->stream));
   RSX_HIP(hipStreamSynchronize(h->stream));
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_orora_set_clique_node_budget(rsx_orora *h, int64_t nodes) try {
+  if (!h || nodes <= 0) return fail(RSX_ERR_BAD_ARG, "the node budget must be positive");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->clique_node_budget = nodes;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_orora_clique_node_budget(rsx_orora *h, int64_t *out_nodes) try {
+  if (!h || !out_nodes) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  std::lock_guard<std::mutex> lk(h->mu);
+  *out_nodes = h->clique_node_budget;
   return RSX_OK;
 } RSX_CATCH_ALL
 

@@ -27,6 +27,8 @@
 //                      tested against P at once (ds_bpermute + ballot), the rows of the next eight members are loaded
 //                      together, each is re-tested against the shrinking P before it joins; then member flags, the selected
 //                      matches compacted in their original order for the solver, one info record
+//   pmc_exact_kernel   (only with RSX_ORORA_PMC_EXACT, after the walk) core pruning, universal vertices, then a branch-and-bound
+//                      search of the residual graph in rank order: a maximum clique per pair, see the comment above it
 // Roofline: the build is VALU-issue bound (SQ_ACTIVE_INST_VALU = 100 % of the SIMD cycles at ~31 instructions per pair of
 // matches: 2.4 of the 3.8 ms); peeling and walk are dependent chains per pair (barrier / load row -> and -> popcount) that last
 // as long as the longest pair's, hidden by the number of pairs in flight (0.9 + 0.6 ms).
@@ -296,7 +298,11 @@ __global__ __launch_bounds__(NT) void pmc_cores_kernel(Args a) {
   if (tid == 0) *reinterpret_cast<int *>(meta + META_HDR) = L.max_core;
 }
 
-__global__ __launch_bounds__(64) void pmc_walk_kernel(Args a) {
+// (KEEP: the exact mode's instance also leaves the greedy clique -- its 64 words and its size -- in the pair's record, where the
+// degrees were; the instance every other call enqueues compiles to what it was)
+constexpr int META_KEEP = META_DEG;
+template <bool KEEP>
+__device__ __forceinline__ void pmc_walk(const Args &a) {
   __shared__ uint16_t s_core[MAX_K], s_order[MAX_K];
   const int lane = threadIdx.x;
   Pair p;
@@ -407,6 +413,280 @@ __global__ __launch_bounds__(64) void pmc_walk_kernel(Args a) {
     if (a.sel_cnt) a.sel_cnt[p.pair] = best_n;
     if (a.info) a.info[p.pair] = rsx_orora_pmc_info{best_n, max_core, seeds, best_n == max_core + 1 ? RSX_ORORA_PMC_PROVEN : 0};
   }
+  if (KEEP) {
+    uint32_t *keep = reinterpret_cast<uint32_t *>(a.meta + (size_t)blockIdx.x * META_BYTES + META_KEEP);
+    keep[lane] = best;
+    if (lane == 0) keep[ROWW] = (uint32_t)best_n;
+  }
+}
+__global__ __launch_bounds__(64) void pmc_walk_kernel(Args a) { pmc_walk<false>(a); }
+__global__ __launch_bounds__(64) void pmc_walk_keep_kernel(Args a) { pmc_walk<true>(a); }
+
+// ---- RSX_ORORA_PMC_EXACT: from the greedy clique to THE maximum clique (tests/pmc_exact_np.py restates every step) ----
+// pmc_exact_kernel runs after pmc_walk_keep_kernel, ONE WAVEFRONT per pair at a time (a fixed number of workgroups stride over
+// the pairs: the HBM stack is per workgroup, not per pair).  g = the greedy size.
+//   proven (g == max core + 1) or |R| <= g, R = {core >= g}      -> a flag, nothing else (a few scalar loads)
+//   U = the vertices of R adjacent to all of R (rows loaded eight at a time), S = R \ U in rank order, n = |S|
+//   the adjacency of S re-indexed BY RANK: vertex r of S = bit r % 32 of lane r / 32, so that "the first vertex of a set in
+//   rank order" is a ballot, two s_ff1 and a v_readlane -- in LDS when n <= 512 (rows of 16 words), otherwise written over the
+//   row of the same vertex in the slab (row i reads only the old row of S[i]: in place)
+//   greedy colouring at the root, then the depth-first search in rank order with an explicit stack of candidate sets (LDS
+//   when it fits, otherwise the workgroup's HBM stack), the node budget checked in that loop -- the only one that can run long:
+//   every other loop removes a vertex from a set of <= 2048 per turn.
+// Every decision is a scalar (ballot / readlane / readfirstlane); no barrier; a wavefront waits for nobody.
+constexpr int EX_LDS_N = 512;               // residual vertices whose adjacency fits LDS
+constexpr int EX_LDS_W = EX_LDS_N / 32;     // words per row there
+constexpr int EX_LDS_LEVELS = 256;          // stack levels in LDS
+
+struct ExactArgs {
+  long long budget;  // nodes per pair
+  uint32_t *stack;   // [gridDim.x][MAX_K][ROWW]
+  int n;             // pairs of this launch
+};
+
+struct ExactLds {
+  uint32_t rows[EX_LDS_N * EX_LDS_W];
+  uint32_t stk[EX_LDS_LEVELS * EX_LDS_W];
+  uint16_t S[MAX_K];  // vertex r of S -> match of the pair
+  uint16_t C[MAX_K];  // the clique in hand, by depth (vertices of S)
+};
+
+__device__ __forceinline__ int set_count(uint32_t x) { return __builtin_amdgcn_readfirstlane(wave_sum_i(__popc(x))); }
+__device__ __forceinline__ int set_first(uint32_t x) {  // the first vertex of a set over S, -1 = empty
+  const unsigned long long m = __ballot(x != 0u);
+  if (m == 0ull) return -1;
+  const int t = __ffsll((long long)m) - 1;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)x, t);
+  return __builtin_amdgcn_readfirstlane(32 * t + (__ffs((int)w) - 1));
+}
+__device__ __forceinline__ uint32_t set_bit(int v, int lane) { return lane == (v >> 5) ? 1u << (v & 31) : 0u; }
+
+struct ExactRows {
+  const ExactLds *L;
+  const uint32_t *adj;
+  bool in_lds;
+  __device__ __forceinline__ uint32_t row(int v, int lane) const {
+    if (in_lds) return lane < EX_LDS_W ? L->rows[v * EX_LDS_W + lane] : 0u;
+    return adj[(size_t)L->S[v] * ROWW + lane];
+  }
+};
+
+// greedy sequential colouring of q in rank order; stops once more than `limit` colours are needed
+__device__ __forceinline__ int ex_colours(const ExactRows &R, uint32_t q, int limit, int lane) {
+  int k = 0;
+  while (__ballot(q != 0u) != 0ull) {
+    k++;
+    if (k > limit) break;
+    uint32_t c = q;
+    for (int v = set_first(c); v >= 0; v = set_first(c)) {
+      const uint32_t bit = set_bit(v, lane);
+      c &= ~R.row(v, lane) & ~bit;
+      q &= ~bit;
+    }
+  }
+  return k;
+}
+
+__device__ __forceinline__ void ex_flag(const Args &a, int pair, int flags, int lane) {
+  if (lane == 0 && a.info) a.info[pair].flags = flags;
+}
+
+__device__ __forceinline__ void exact_pair(const Args &a, const ExactArgs &x, int b, ExactLds &L, int lane) {
+  const int pair = a.first + b;
+  const int64_t o = a.offsets[pair], K64 = a.offsets[pair + 1] - o;
+  if (K64 < 2 || K64 > MAX_K || (a.sel_src && o + K64 > a.sel_cap)) return;  // passed through by the walk
+  const int K = __builtin_amdgcn_readfirstlane((int)K64), nc = (K + 63) >> 6;
+  uint32_t *adj = a.slabs + (size_t)b * (rsx::pmc::SLAB_BYTES / 4);
+  const char *meta = a.meta + (size_t)b * META_BYTES;
+  const uint16_t *g_core = reinterpret_cast<const uint16_t *>(meta + META_CORE), *g_order = reinterpret_cast<const uint16_t *>(meta + META_ORDER);
+  const uint32_t *keep = reinterpret_cast<const uint32_t *>(meta + META_KEEP);
+  const int max_core = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int *>(meta + META_HDR));
+  const int g = __builtin_amdgcn_readfirstlane((int)keep[ROWW]);
+  if (g == max_core + 1) return ex_flag(a, pair, RSX_ORORA_PMC_PROVEN | RSX_ORORA_PMC_MAXIMUM, lane);
+
+  // 1. R = the vertices of core number >= g: the first nR entries of `order`
+  uint32_t Rm = 0;
+  for (int c = 0; c < nc; c++) {
+    const int v = c * 64 + lane;
+    if (v < K && (int)g_core[v] >= g) Rm |= 1u << c;
+  }
+  const int nR = set_count(Rm);
+  if (nR <= g) return ex_flag(a, pair, RSX_ORORA_PMC_MAXIMUM, lane);
+
+  // 2. U = adjacent to all of R (into the clique), S = the rest, in rank order
+  uint32_t Um = 0;
+  int n = 0;
+  for (int i0 = 0; i0 < nR; i0 += 8) {
+    int vv[8];
+    uint32_t rw[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      vv[q] = 0;
+      rw[q] = 0;
+      if (i0 + q < nR) {
+        vv[q] = __builtin_amdgcn_readfirstlane((int)g_order[i0 + q]);
+        rw[q] = adj[(size_t)vv[q] * ROWW + lane];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      if (i0 + q < nR) {
+        const int v = vv[q];
+        if (set_count(rw[q] & Rm) == nR - 1) {
+          if (lane == (v & 63)) Um |= 1u << (v >> 6);
+        } else {
+          if (lane == 0) L.S[n] = (uint16_t)v;
+          n++;
+        }
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  const int u = nR - n, need = g - u;
+  int best = need > 0 ? need : 0;
+  bool improved = need < 0, exhausted = false;  // need < 0: U alone is larger than the greedy clique
+  uint32_t bestm = 0;
+
+  if (n > 0) {
+    // 3. the adjacency of S by rank
+    const bool in_lds = n <= EX_LDS_N;
+    int levels = (n < max_core + 1 - u ? n : max_core + 1 - u) + 1;  // depth <= the largest clique of S
+    if (levels > MAX_K) levels = MAX_K;                               // (what the workgroup's HBM stack holds)
+    const bool stk_lds = in_lds && levels <= EX_LDS_LEVELS;
+    uint32_t *gstk = x.stack + (size_t)blockIdx.x * ((size_t)MAX_K * ROWW);
+    for (int i0 = 0; i0 < n; i0 += 4) {
+      int vv[4];
+      uint32_t rw[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        vv[q] = 0;
+        rw[q] = 0;
+        if (i0 + q < n) {
+          vv[q] = __builtin_amdgcn_readfirstlane((int)L.S[i0 + q]);
+          rw[q] = adj[(size_t)vv[q] * ROWW + lane];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        if (i0 + q < n) {
+          uint32_t nw = 0;
+          for (int c = 0; c * 64 < n; c++) {
+            const int j = c * 64 + lane;
+            const int w = j < n ? (int)L.S[j] : 0;
+            const uint32_t word = (uint32_t)__shfl((int)rw[q], w & 63);
+            const unsigned long long m = __ballot(j < n && ((word >> (w >> 6)) & 1u));
+            if (lane == 2 * c) nw = (uint32_t)m;
+            if (lane == 2 * c + 1) nw = (uint32_t)(m >> 32);
+          }
+          if (in_lds) {
+            if (lane < EX_LDS_W) L.rows[(i0 + q) * EX_LDS_W + lane] = nw;
+          } else {
+            adj[(size_t)vv[q] * ROWW + lane] = nw;
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const ExactRows R{&L, adj, in_lds};
+    // candidates need core >= u + best: a prefix of S
+    auto alive_of = [&](int bst) {
+      int cnt = 0;
+      for (int i = lane; i < n; i += 64) cnt += (int)g_core[L.S[i]] >= u + bst ? 1 : 0;
+      const int m = __builtin_amdgcn_readfirstlane(wave_sum_i(cnt)) - 32 * lane;
+      return m >= 32 ? 0xffffffffu : m <= 0 ? 0u : (1u << m) - 1u;
+    };
+    auto stk_get = [&](int d) { return stk_lds ? (lane < EX_LDS_W ? L.stk[d * EX_LDS_W + lane] : 0u) : gstk[(size_t)d * ROWW + lane]; };
+    auto stk_put = [&](int d, uint32_t P) {
+      if (stk_lds) {
+        if (lane < EX_LDS_W) L.stk[d * EX_LDS_W + lane] = P;
+      } else {
+        gstk[(size_t)d * ROWW + lane] = P;
+      }
+    };
+    uint32_t alive = alive_of(best);
+    if (ex_colours(R, alive, best, lane) > best) {
+      // 4. depth-first in rank order; Cm = the clique in hand = C[0 .. d)
+      long long nodes = 0;
+      uint32_t Cm = 0;
+      int d = 0;
+      stk_put(0, alive);
+      for (;;) {
+        uint32_t Pd = stk_get(d) & alive;
+        const int np = set_count(Pd);
+        if (np == 0 || d + np <= best) {
+          if (d == 0) break;
+          d--;
+          Cm &= ~set_bit(__builtin_amdgcn_readfirstlane((int)L.C[d]), lane);
+          continue;
+        }
+        if (nodes >= x.budget) {
+          exhausted = true;
+          break;
+        }
+        nodes++;
+        const int v = set_first(Pd);
+        const uint32_t bit = set_bit(v, lane);
+        Pd &= ~bit;
+        stk_put(d, Pd);
+        if (d + 1 > best) {
+          best = d + 1;
+          improved = true;
+          bestm = Cm | bit;
+          alive = alive_of(best);
+        }
+        const uint32_t Pn = Pd & R.row(v, lane) & alive;
+        const int nn = set_count(Pn);
+        if (nn == 0 || d + 1 + nn <= best) continue;
+        if (d + 1 + ex_colours(R, Pn, best - d - 1, lane) <= best) continue;
+        if (d + 2 > levels) continue;  // (cannot happen: a clique of S larger than the core bound allows)
+        if (lane == 0) L.C[d] = (uint16_t)v;
+        __builtin_amdgcn_wave_barrier();
+        Cm |= bit;
+        d++;
+        stk_put(d, Pn);
+      }
+    }
+  }
+  if (exhausted) return ex_flag(a, pair, RSX_ORORA_PMC_BUDGET, lane);
+  if (!improved) return ex_flag(a, pair, RSX_ORORA_PMC_MAXIMUM, lane);
+
+  // ---- a larger clique: U + the clique of S, back in the pair's own numbering; flags, compaction and info as the walk's ----
+  uint32_t cl = Um;
+  for (int i = set_first(bestm); i >= 0; i = set_first(bestm)) {
+    bestm &= ~set_bit(i, lane);
+    const int v = __builtin_amdgcn_readfirstlane((int)L.S[i]);
+    if (lane == (v & 63)) cl |= 1u << (v >> 6);
+  }
+  const int size = u + best;
+  int run = 0;
+  for (int c = 0; c < nc; c++) {
+    const int v = c * 64 + lane;
+    const bool sel = v < K && ((cl >> c) & 1u);
+    if (v < K && a.member) a.member[o + v] = sel ? 1 : 0;
+    const unsigned long long bal = __ballot(sel);
+    if (sel && a.sel_src) {
+      const int pos = run + __popcll(bal & ((1ull << lane) - 1ull));
+      a.sel_src[o + pos] = a.src[o + v];
+      a.sel_dst[o + pos] = a.dst[o + v];
+    }
+    run += __popcll(bal);
+  }
+  if (lane == 0) {
+    if (a.sel_cnt) a.sel_cnt[pair] = size;
+    if (a.info) {
+      a.info[pair].size = size;
+      a.info[pair].flags = RSX_ORORA_PMC_MAXIMUM | (size == max_core + 1 ? RSX_ORORA_PMC_PROVEN : 0);
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void pmc_exact_kernel(Args a, ExactArgs x) {
+  __shared__ ExactLds L;
+  const int lane = threadIdx.x;
+  for (int b = blockIdx.x; b < x.n; b += gridDim.x) {
+    exact_pair(a, x, b, L, lane);
+    __builtin_amdgcn_wave_barrier();  // (the next pair's S / rows / stack are written after this pair's last read)
+  }
 }
 
 }  // namespace
@@ -420,13 +700,17 @@ namespace pmc {
 // pairs (0.5 - 0.65 ms each for 875 pairs as for 2 048), so four chunks of 875 pairs cost 5.3 ms against 5.0 ms for two
 // chunks in sequence, and one chunk of all 3 500 is the fastest.)
 int launch(Workspace &ws, int device, const float2 *d_src, const float2 *d_dst, const int64_t *d_offsets, int n_pairs, double tau,
-           uint8_t *d_member, rsx_orora_pmc_info *d_info, float2 *d_sel_src, float2 *d_sel_dst, int32_t *d_sel_cnt, int64_t sel_cap, hipStream_t s) {
+           uint8_t *d_member, rsx_orora_pmc_info *d_info, float2 *d_sel_src, float2 *d_sel_dst, int32_t *d_sel_cnt, int64_t sel_cap, hipStream_t s,
+           int64_t exact_budget) {
   (void)device;
   if (n_pairs <= 0) return RSX_OK;
   if (!(tau > 0.0)) return rsx::fail(RSX_ERR_BAD_ARG, "the consistency bound (tim_noise_bound) must be positive");
   const int chunk = n_pairs < CHUNK ? n_pairs : CHUNK;
   RSX_TRY(ws.slabs.reserve((size_t)chunk * SLAB_BYTES, s, false));
   RSX_TRY(ws.meta.reserve((size_t)chunk * META_BYTES, s, false));
+  const bool exact = exact_budget > 0;
+  const int slots = chunk < EXACT_SLOTS ? chunk : EXACT_SLOTS;
+  if (exact) RSX_TRY(ws.stack.reserve((size_t)slots * SLAB_BYTES, s, false));
   Args a;
   a.src = d_src;
   a.dst = d_dst;
@@ -446,7 +730,13 @@ int launch(Workspace &ws, int device, const float2 *d_src, const float2 *d_dst, 
     a.first = first;
     hipLaunchKernelGGL(pmc_build_kernel, dim3((unsigned)n, (unsigned)(MAX_K / BUILD_ROWS)), dim3(NT), 0, s, a);
     hipLaunchKernelGGL(pmc_cores_kernel, dim3((unsigned)n), dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(pmc_walk_kernel, dim3((unsigned)n), dim3(64), 0, s, a);
+    if (!exact) {
+      hipLaunchKernelGGL(pmc_walk_kernel, dim3((unsigned)n), dim3(64), 0, s, a);
+    } else {
+      hipLaunchKernelGGL(pmc_walk_keep_kernel, dim3((unsigned)n), dim3(64), 0, s, a);
+      const ExactArgs x{(long long)exact_budget, ws.stack.as<uint32_t>(), n};
+      hipLaunchKernelGGL(pmc_exact_kernel, dim3((unsigned)(n < slots ? n : slots)), dim3(64), 0, s, a, x);
+    }
   }
   RSX_HIP(hipGetLastError());
   return RSX_OK;

@@ -131,7 +131,7 @@ int main(int argc, char **argv) {
   try {
     std::string seq_dir, out_path, record_path, matcher = "orb", keypoints = "cen2019", estimator = "orora";
     int max_frames = -1, device = 0, window = 0, threads = 0;
-    bool per_scan = false, timing = false, use_pmc = true;
+    bool per_scan = false, timing = false, use_pmc = true, exact_clique = false;
     double rate_hz = 0.0;
     float gate = 6.0f;
     rsx_cen2018_params c18;
@@ -155,6 +155,7 @@ int main(int argc, char **argv) {
       else if (a == "--ransac-iterations" && i + 1 < argc) rsp.max_iterations = std::atoi(argv[++i]);  // hypotheses (100)
       else if (a == "--scan-period" && i + 1 < argc) rsp.dt_scan = std::atof(argv[++i]);               // mcransac: seconds per scan (0.25)
       else if (a == "--no-pmc") use_pmc = false;                                   // skip the max-clique inlier selection before the solver
+      else if (a == "--exact-clique") exact_clique = true;                        // RSX_ORORA_PMC_EXACT: the selection returns a maximum clique
       else if (a == "--per-scan") per_scan = true;                                // the round-2 loop: one scan per call, host vectors in between
       else if (a == "--timing") timing = true;                                    // decode / pipeline seconds on stderr
       else if (a.rfind("seq_dir:=", 0) == 0) seq_dir = a.substr(9);  // roslaunch-style arg
@@ -167,7 +168,8 @@ int main(int argc, char **argv) {
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018] [--zq Z] [--sigma-gauss S] [--window W] [--threads T] "
-          "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--per-scan] [--no-pmc] [--timing]");
+          "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--per-scan] [--no-pmc] [--exact-clique] [--timing]");
+    if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";
     std::vector<std::string> files;
     if (DIR *d = opendir(dir.c_str())) {
@@ -275,6 +277,7 @@ int main(int argc, char **argv) {
       op.radar_resolution = kResolution;
       op.col_offset = kMeta;
       if (!use_pmc) op.orora.flags &= ~RSX_ORORA_PMC;
+      if (exact_clique) op.orora.flags |= RSX_ORORA_PMC_EXACT;
       rsx_odometry *odo = nullptr;
       check(rsx_odometry_create(&op, rows, cols, &odo), "rsx_odometry_create");
       if (use_c18) check(rsx_odometry_set_cen2018(odo, &c18), "rsx_odometry_set_cen2018");
@@ -527,6 +530,7 @@ int main(int argc, char **argv) {
         rsx_orora_params rp;
         check(rsx_orora_default_params(&rp), "rsx_orora_default_params");
         if (use_pmc) rp.flags |= RSX_ORORA_PMC;
+        if (exact_clique) rp.flags |= RSX_ORORA_PMC_EXACT;
         check(rsx_orora_register_batch(reg, dst.data(), src.data(), offsets, 1, &rp, &r), "rsx_orora_register_batch");
         compose(r);
       }

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import ODOMETRY_SCAN_DTYPE, Cen2018Params, OdometryParams, RansacParams, check, lib
+from ._rsx import ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, OdometryParams, RansacParams, check, lib
 
 ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_*
 
@@ -17,9 +17,11 @@ def default_params():
 
 class Odometry:
     """keypoints: "cen2019" (default) or "cen2018"; cen2018: its Cen2018Params (None: cen2018.default_params()).
-    estimator: "orora" (default), "ransac" or "mcransac"; ransac: their RansacParams (None: ransac.default_params())."""
+    estimator: "orora" (default), "ransac" or "mcransac"; ransac: their RansacParams (None: ransac.default_params()).
+    exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT)."""
 
-    def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None):
+    def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
+                 exact_clique=False):
         if keypoints not in ("cen2019", "cen2018"):
             raise ValueError("keypoints must be cen2019 or cen2018")
         if estimator not in ESTIMATORS:
@@ -28,6 +30,10 @@ class Odometry:
         self.rows, self.cols = rows, cols
         self.params = params if params is not None else default_params()
         self.params.device = device
+        if exact_clique:
+            if not self.params.orora.flags & ORORA_PMC:
+                raise ValueError("exact_clique needs the max-clique selection (ORORA_PMC) on")
+            self.params.orora.flags |= ORORA_PMC_EXACT
         self._h = C.c_void_p()
         check(self._L.rsx_odometry_create(C.byref(self.params), rows, cols, C.byref(self._h)))
         if keypoints == "cen2018":

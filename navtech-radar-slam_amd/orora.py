@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _rsx
-from ._rsx import ORORA_PMC, ORORA_RESULT_DTYPE, PMC_INFO_DTYPE, OroraParams, check, lib  # noqa: F401
+from ._rsx import ORORA_PMC, ORORA_PMC_EXACT, ORORA_RESULT_DTYPE, PMC_INFO_DTYPE, OroraParams, check, lib  # noqa: F401
 
 
 def default_params():
@@ -61,8 +61,24 @@ class Orora:
         """sizes the workspaces of the RSX_ORORA_PMC stage for the asynchronous device entry"""
         check(self._L.rsx_orora_reserve(self._h, int(max_total_matches)))
 
-    def max_clique_batch(self, src_xy, dst_xy, offsets, params=None):
-        """the max-clique inlier selection on its own -> (member uint8 (M,), info (n_pairs,) PMC_INFO_DTYPE)"""
+    def set_clique_node_budget(self, nodes):
+        """ORORA_PMC_EXACT: search nodes one pair may cost before it keeps its greedy clique (ORORA_PMC_BUDGET)"""
+        check(self._L.rsx_orora_set_clique_node_budget(self._h, int(nodes)))
+
+    def clique_node_budget(self):
+        n = C.c_int64()
+        check(self._L.rsx_orora_clique_node_budget(self._h, C.byref(n)))
+        return n.value
+
+    def max_clique_batch(self, src_xy, dst_xy, offsets, params=None, exact=False):
+        """the max-clique inlier selection on its own -> (member uint8 (M,), info (n_pairs,) PMC_INFO_DTYPE); exact=True: a
+        maximum clique per pair (ORORA_PMC | ORORA_PMC_EXACT on a copy of params)"""
+        if exact:
+            q = default_params()
+            if params is not None:
+                C.memmove(C.byref(q), C.byref(params), C.sizeof(OroraParams))
+            q.flags |= ORORA_PMC | ORORA_PMC_EXACT
+            params = q
         src = np.ascontiguousarray(src_xy, dtype=np.float32)
         dst = np.ascontiguousarray(dst_xy, dtype=np.float32)
         off = np.ascontiguousarray(offsets, dtype=np.int64)

@@ -169,6 +169,13 @@ def orora_pairs(seed, n_pairs, k_range=(300, 1500), outlier_range=(0.2, 0.6), ma
     return src, dst, offsets, truth
 
 
+def orora_high_outlier_pairs(seed, n_pairs, k_range=(200, 600), outlier_range=(0.9, 0.97), max_range=40.0):
+    """orora_pairs with 90 - 97 % outliers inside 40 m: the consistent set is a few per cent of a dense field of wrong matches.
+    On such pairs the greedy max-clique walk can stop at a quarter of the consistent set (orora_high_outlier_pairs(6, 30): 4 of
+    15, 4 of 12 and 3 of 8), which is what RSX_ORORA_PMC_EXACT is for."""
+    return orora_pairs(seed, n_pairs, k_range=k_range, outlier_range=outlier_range, max_range=max_range)
+
+
 def motion_distorted_pairs(seed, n_pairs, k=600, outlier=0.4, speed=(5.0, 20.0), max_wz=0.5, rows=400, dt_scan=0.25, max_range=150.0,
                            max_row_step=3):
     """n_pairs match sets of a sensor that moves at a constant body velocity w = (vx, vy, wz) WHILE it scans (what
