@@ -17,6 +17,7 @@
  *     stream: callers that mix several handles or other GPU work must pass one explicit stream.
  *     Calls on ONE handle that pass different streams are ordered by the library (the handle's workspaces are shared: a call
  *     arriving on another stream than the previous call makes its stream wait for everything enqueued on the old one).
+ *     The one exemption is rsx_ransac_estimate_batch_device, which uses no workspace of its handle.
  *   - a handle is internally synchronised: every entry point holds the handle's mutex for its whole
  *     duration, so any number of threads may call concurrently (the reference itself races between its
  *     writer, PGO.cpp:492 process_pg, and its reader, PGO.cpp:561 process_lcd).  The one multi-call

@@ -1664,6 +1664,7 @@ struct rsx_cen2019 {
   rsx::KeypointStaging stage;
   rsx::DevBuf one;          // single-scan entry: [count | targets | xy] in one piece, read back with one copy
   rsx::PinnedBuf one_host;  // its pinned mirror
+  rsx::StreamOrder order;
 };
 
 using rsx::fail;
@@ -1814,6 +1815,7 @@ int rsx_cen2019_extract_batch_device(rsx_cen2019 *h, const uint8_t *d_imgs, int3
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   return extract_device(h, d_imgs, image_stride_bytes, n_images, row_stride, col_offset, p, d_azimuths, azimuths_per_image ? h->rows : 0,
                         resolution, max_targets, d_targets, d_xy, d_counts, s);
 } RSX_CATCH_ALL
@@ -1831,6 +1833,7 @@ int rsx_cen2019_extract_batch(rsx_cen2019 *h, const uint8_t *imgs, int32_t n_ima
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
   const size_t ibytes = (size_t)h->rows * row_stride;
   const int mt = max_targets > 0 ? max_targets : 1;
   if (n_images == 1) {

@@ -725,6 +725,7 @@ struct rsx_frontend {
   double map_radar_res = -1.0;
   bool have_image = false;
   int batch_n = 0;  // Cartesian images held by the last rsx_frontend_cartesian* call
+  rsx::StreamOrder order;
   bool three_pass = false;  // RSX_FRONTEND_THREE_PASS: remap and the two blur passes as separate kernels
   bool tiles = false;       // RSX_FRONTEND_TILES: the 32 x 32 tile kernel of round 3 instead of the strip kernel
   bool exact_az = false;    // RSX_FRONTEND_EXACT_AZIMUTH: every azimuth row through the fp64 division
@@ -920,6 +921,7 @@ int rsx_frontend_cartesian(rsx_frontend *h, const uint8_t *img, int32_t row_stri
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
   if (!((double)azimuths[1] - (double)azimuths[0] > 0.0)) return fail(RSX_ERR_BAD_ARG, "azimuths must increase");
   RSX_TRY(ensure_map(h, resolution, s));
   const size_t ibytes = (size_t)h->rows * row_stride;
@@ -941,6 +943,7 @@ int rsx_frontend_cartesian_batch_device(rsx_frontend *h, const uint8_t *d_imgs, 
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   if (!((double)azimuths[1] - (double)azimuths[0] > 0.0)) return fail(RSX_ERR_BAD_ARG, "azimuths must increase");
   RSX_TRY(ensure_map(h, resolution, s));
   RSX_TRY(h->az1.reserve(8, s, false));
@@ -957,6 +960,7 @@ int rsx_frontend_cartesian_batch_device_az(rsx_frontend *h, const uint8_t *d_img
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   RSX_TRY(ensure_map(h, resolution, s));
   return cartesian_device(h, d_imgs, n_images, image_stride_bytes, row_stride, col_offset, d_azimuths, azimuth_stride_floats, s);
 } RSX_CATCH_ALL
@@ -980,6 +984,7 @@ int rsx_frontend_describe(rsx_frontend *h, const float *xy, int32_t n, uint8_t *
   if (!h->have_image) return fail(RSX_ERR_BAD_ARG, "describe before rsx_frontend_cartesian");
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
   // metric keypoint (x forward, y right) -> nearest pixel, in double on the host
   std::vector<int32_t> uv((size_t)2 * n);
   const double cmr = cart_min_range(h->W, h->cart_res);
@@ -1010,6 +1015,7 @@ int rsx_frontend_describe_batch_device(rsx_frontend *h, const float *d_xy, const
   if (!h->have_image || n_images > h->batch_n) return fail(RSX_ERR_BAD_ARG, "describe_batch: %d images, the last Cartesian batch holds %d", n_images, h->batch_n);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   RSX_TRY(h->uv.reserve((size_t)n_images * max_targets * 8, s, false));
   const double cmr = cart_min_range(h->W, h->cart_res);
   hipLaunchKernelGGL(fe_uv, dim3((unsigned)((max_targets + 255) / 256), (unsigned)n_images), dim3(256), 0, s, d_xy, d_counts, max_targets, cmr,
@@ -1036,6 +1042,7 @@ int rsx_frontend_match_consecutive_device(rsx_frontend *h, const uint8_t *d_desc
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   RSX_TRY(h->vidx.reserve((size_t)(n_pairs + 1) * max_targets * 4, s, false));
   RSX_TRY(h->vcount.reserve((size_t)(n_pairs + 1) * 4, s, false));
   hipLaunchKernelGGL(fe_compact_valid, dim3((unsigned)(n_pairs + 1)), dim3(256), 0, s, d_valid, d_counts, max_targets, first_slot,
@@ -1055,6 +1062,7 @@ int rsx_frontend_match(rsx_frontend *h, const uint8_t *q_desc, const uint8_t *q_
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
   RSX_TRY(h->q.reserve((size_t)nq * 32, s, false));
   RSX_TRY(h->qv.reserve((size_t)nq, s, false));
   RSX_TRY(h->t.reserve((size_t)(nt ? nt : 1) * 32, s, false));

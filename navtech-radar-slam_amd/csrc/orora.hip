@@ -136,7 +136,9 @@ struct Red {
 
 __device__ __forceinline__ void aniso_bound(double px, double py, double s_r, double s_t, double &bx, double &by) {
   const double rho = sqrt(px * px + py * py);
-  double c = 1.0, s = 0.0;
+  // a point AT the origin has no azimuth: the radial bound holds along both axes (c = 1, s = 0 there gave a match whose two
+  // points are both the origin a y-bound of exactly 0: weight 1 / 0, inf - inf in the running sums of the sweep)
+  double c = 1.0, s = 1.0;
   if (rho > 0.0) {
     c = fabs(px) / rho;
     s = fabs(py) / rho;
@@ -793,6 +795,7 @@ struct rsx_orora {
   rsx::DevBuf sel_src, sel_dst, sel_cnt, pmc_info, member;
   int64_t sel_cap = 0;             // matches sel_src / sel_dst hold (rsx_orora_reserve)
   hipStream_t last_stream = nullptr;  // of the last PMC call (rsx_orora_last_pmc_info waits for it)
+  rsx::StreamOrder order;             // big_list, big_ws and the selection's buffers are shared by every call
   int32_t last_pmc_pairs = 0;
   int64_t clique_node_budget = rsx::pmc::DEFAULT_NODE_BUDGET;  // RSX_ORORA_PMC_EXACT: search nodes per pair
   bool attr_set = false;
@@ -875,6 +878,7 @@ int rsx_orora_register_batch_device(rsx_orora *h, const float *d_src_xy, const f
   kp.complete_graph = (dp.flags & RSX_ORORA_COMPLETE_GRAPH) ? 1 : 0;
   kp.teaser_cost = (dp.flags & RSX_ORORA_TEASER_COST) ? 1 : 0;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   // the list of pairs too large for the on-chip kernel is built on the device (the offsets may live there only); the
   // large-pair kernel always runs its few workgroups, which return at once when the list is empty
   RSX_TRY(h->big_list.reserve((size_t)(n_pairs + 1) * sizeof(int), s, false));
@@ -925,6 +929,7 @@ int rsx_orora_register_batch(rsx_orora *h, const float *src_xy, const float *dst
     std::lock_guard<std::mutex> lk(h->mu);
     RSX_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    RSX_TRY(h->order.enter(s));
     RSX_TRY(h->src.reserve((size_t)(m ? m : 1) * 8, s, false));
     RSX_TRY(h->dst.reserve((size_t)(m ? m : 1) * 8, s, false));
     RSX_TRY(h->off.reserve((size_t)(n_pairs + 1) * 8, s, false));
@@ -939,6 +944,7 @@ int rsx_orora_register_batch(rsx_orora *h, const float *src_xy, const float *dst
   RSX_TRY(rsx_orora_register_batch_device(h, h->src.as<float>(), h->dst.as<float>(), h->off.as<int64_t>(), n_pairs, params,
                                           h->res.as<rsx_orora_result>(), h->stream));
   std::lock_guard<std::mutex> lk(h->mu);
+  RSX_TRY(h->order.enter(h->stream));
   RSX_HIP(hipMemcpyAsync(out, h->res.p, (size_t)n_pairs * sizeof(rsx_orora_result), hipMemcpyDeviceToHost, h->stream));
   RSX_HIP(hipStreamSynchronize(h->stream));
   return RSX_OK;
@@ -950,6 +956,7 @@ int rsx_orora_reserve(rsx_orora *h, int64_t max_total_matches) try {
   if (!h || max_total_matches < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
+  RSX_TRY(h->order.enter(h->stream));
   return reserve_selection(h, max_total_matches, h->stream);
 } RSX_CATCH_ALL
 
@@ -964,6 +971,7 @@ int rsx_orora_max_clique_batch_device(rsx_orora *h, const float *d_src_xy, const
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
   return rsx::pmc::launch(h->pmc_ws, h->device, reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets,
                           n_pairs, dp.tim_noise_bound, d_member, d_info, nullptr, nullptr, nullptr, 0, s,
                           (dp.flags & RSX_ORORA_PMC_EXACT) ? h->clique_node_budget : 0);
@@ -979,6 +987,7 @@ int rsx_orora_max_clique_batch(rsx_orora *h, const float *src_xy, const float *d
     std::lock_guard<std::mutex> lk(h->mu);
     RSX_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    RSX_TRY(h->order.enter(s));
     RSX_TRY(h->src.reserve((size_t)(m ? m : 1) * 8, s, false));
     RSX_TRY(h->dst.reserve((size_t)(m ? m : 1) * 8, s, false));
     RSX_TRY(h->off.reserve((size_t)(n_pairs + 1) * 8, s, false));
@@ -993,6 +1002,7 @@ int rsx_orora_max_clique_batch(rsx_orora *h, const float *src_xy, const float *d
   RSX_TRY(rsx_orora_max_clique_batch_device(h, h->src.as<float>(), h->dst.as<float>(), h->off.as<int64_t>(), n_pairs, params,
                                             h->member.as<uint8_t>(), h->pmc_info.as<rsx_orora_pmc_info>(), h->stream));
   std::lock_guard<std::mutex> lk(h->mu);
+  RSX_TRY(h->order.enter(h->stream));
   if (out_member && m) RSX_HIP(hipMemcpyAsync(out_member, h->member.p, (size_t)m, hipMemcpyDeviceToHost, h->stream));
   if (out_info) RSX_HIP(hipMemcpyAsync(out_info, h->pmc_info.p, (size_t)n_pairs * sizeof(rsx_orora_pmc_info), hipMemcpyDeviceToHost, h->stream));
   RSX_HIP(hipStreamSynchronize(h->stream));

@@ -114,6 +114,12 @@ int use_stream(rsx_sc *h, void *stream, hipStream_t *s) {
   return h->order.enter(*s);
 }
 
+// a host-buffer entry works on the handle's own stream: ordered behind a device entry that came on the caller's
+int own_stream(rsx_sc *h) {
+  RSX_TRY(set_device(h));
+  return h->order.enter(h->stream);
+}
+
 // one new entry from a cloud in device memory, all of it in one launch
 int insert_cloud(rsx_sc *h, const void *d_pts, int64_t n_pts, int64_t stride, int64_t slot, hipStream_t s) {
   return launch_insert(d_pts, nullptr, n_pts, 1, stride, h->p.lidar_height, h->p.max_radius, slot, h->desc.as<float>(),
@@ -726,7 +732,7 @@ int rsx_sc_add_points(rsx_sc *h, const void *pts, size_t n, size_t stride_bytes,
   if (!h || (!pts && n)) return fail(RSX_ERR_BAD_ARG, "null arg");
   if (stride_bytes < 12 || (stride_bytes & 3)) return fail(RSX_ERR_BAD_ARG, "stride_bytes must be >= 12 and a multiple of 4");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   const int64_t g = h->n_global;
   if (owns(h, g)) {
     const int64_t slot = h->n_local;
@@ -762,7 +768,7 @@ int rsx_sc_add_points_downsampled(rsx_sc *h, rsx_voxelgrid *vg, const void *pts,
   if (rsx::vg::device_of(vg) != h->p.device) return fail(RSX_ERR_BAD_ARG, "voxel grid and ScanContext handles are on different devices");
   std::lock_guard<std::mutex> lk(h->mu);
   std::lock_guard<std::mutex> lkv(rsx::vg::mutex_of(vg));
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   const int64_t g = h->n_global;
   if (owns(h, g)) {
     // intensity is not used by the descriptor (SC.cpp:151-195 reads x, y, z only)
@@ -793,7 +799,7 @@ int rsx_sc_add_keyframe(rsx_sc *h, rsx_voxelgrid *vg, rsx_kfstore *kf, const voi
   std::lock_guard<std::mutex> lk(h->mu);
   std::lock_guard<std::mutex> lkv(rsx::vg::mutex_of(vg));
   std::lock_guard<std::mutex> lkk(rsx::kf::mutex_of(kf));
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   const int64_t g = h->n_global;
   // downSizeFilterScancontext.filter(*thisKeyFrameDS) (PGO.cpp:482-484): every shard keeps the keyframe cloud (the loop
   // verification runs where the pose graph lives), only the owning shard builds the descriptor
@@ -854,7 +860,7 @@ static int add_descriptor_f64(rsx_sc *h, const double *desc, bool allow_rounding
   }
   if (max_err) *max_err = worst;
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   const int64_t g = h->n_global;
   RSX_TRY(add_f32_locked(h, f, 1, false, h->stream));
   if (out_index) *out_index = (int32_t)g;
@@ -873,7 +879,7 @@ int rsx_sc_add_descriptors_f32(rsx_sc *h, const float *descs, int64_t n) try {
   if (!h || (!descs && n) || n < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (n == 0) return RSX_OK;
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   return add_f32_locked(h, descs, n, false, h->stream);
 } RSX_CATCH_ALL
 
@@ -892,7 +898,7 @@ int rsx_sc_export_descriptors_f32(rsx_sc *h, int64_t first_slot, int64_t count, 
   std::lock_guard<std::mutex> lk(h->mu);
   if (first_slot < 0 || count < 0 || first_slot + count > h->n_local) return fail(RSX_ERR_RANGE, "slot range out of bounds");
   if (count == 0) return RSX_OK;
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   RSX_HIP(hipMemcpyAsync(out, h->desc.as<float>() + first_slot * DS, (size_t)count * DS * sizeof(float), hipMemcpyDeviceToHost,
                          h->stream));
   RSX_HIP(hipStreamSynchronize(h->stream));
@@ -919,7 +925,7 @@ static_assert(sizeof(DbFileHeader) == 64, "header layout");
 int rsx_sc_save(rsx_sc *h, const char *path) try {
   if (!h || !path) return fail(RSX_ERR_BAD_ARG, "null arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   std::vector<float> buf((size_t)h->n_local * DS);
   if (h->n_local) {
     RSX_HIP(hipMemcpyAsync(buf.data(), h->desc.p, buf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -984,7 +990,7 @@ int rsx_sc_load(rsx_sc *h, const char *path, int64_t *n_loaded) try {
     if (hd.shard_world != h->p.shard_world || hd.shard_rank != h->p.shard_rank || h->n_global != 0)
       return fail(RSX_ERR_BAD_ARG, "%s holds shard %d/%d: load it into an empty handle of the same shard", path, hd.shard_rank,
                   hd.shard_world);
-    RSX_TRY(set_device(h));
+    RSX_TRY(own_stream(h));
     if (hd.n_local) {
       RSX_TRY(ensure_capacity(h, hd.n_local));
       RSX_HIP(hipMemcpyAsync(h->desc.p, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -994,7 +1000,7 @@ int rsx_sc_load(rsx_sc *h, const char *path, int64_t *n_loaded) try {
     h->n_local = hd.n_local;
     h->n_global = hd.n_global;
   } else {
-    RSX_TRY(set_device(h));
+    RSX_TRY(own_stream(h));
     if (hd.n_local) RSX_TRY(add_f32_locked(h, buf.data(), hd.n_local, false, h->stream));
   }
   if (n_loaded) *n_loaded = hd.n_local;
@@ -1012,7 +1018,7 @@ static int local_slot_of(rsx_sc *h, int64_t index, int64_t *slot) {
 int rsx_sc_get_descriptor(rsx_sc *h, int64_t index, double *out) try {
   if (!h || !out) return fail(RSX_ERR_BAD_ARG, "null arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   int64_t slot;
   RSX_TRY(local_slot_of(h, index, &slot));
   float f[DS];
@@ -1025,7 +1031,7 @@ int rsx_sc_get_descriptor(rsx_sc *h, int64_t index, double *out) try {
 int rsx_sc_get_ringkey(rsx_sc *h, int64_t index, float *out20) try {
   if (!h || !out20) return fail(RSX_ERR_BAD_ARG, "null arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   int64_t slot;
   RSX_TRY(local_slot_of(h, index, &slot));
   RSX_HIP(hipMemcpyAsync(out20, h->rkey.as<float>() + slot * NR, NR * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -1036,7 +1042,7 @@ int rsx_sc_get_ringkey(rsx_sc *h, int64_t index, float *out20) try {
 int rsx_sc_get_sectorkey(rsx_sc *h, int64_t index, double *out60) try {
   if (!h || !out60) return fail(RSX_ERR_BAD_ARG, "null arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   int64_t slot;
   RSX_TRY(local_slot_of(h, index, &slot));
   RSX_HIP(hipMemcpyAsync(out60, h->vkey.as<double>() + slot * NS, NS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1049,7 +1055,7 @@ int rsx_sc_detect_loop_closure_ex(rsx_sc *h, int mode, rsx_sc_detection *out) tr
   if (mode != RSX_SC_MODE_CANDIDATE && mode != RSX_SC_MODE_EXHAUSTIVE) return fail(RSX_ERR_BAD_ARG, "bad mode %d", mode);
   std::unique_lock<std::mutex> lk(h->mu);
   if (h->p.shard_world != 1) return fail(RSX_ERR_BAD_ARG, "detect_loop_closure needs an unsharded handle; use rsx_scs_* or rsx_sc_query_device + merge");
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   const int64_t N = h->n_global;  // snapshot under the lock (the reference races here, PGO.cpp:561)
   out->loop_id = -1;
   out->yaw_diff_rad = 0.0f;
@@ -1096,7 +1102,7 @@ int rsx_sc_detect_loop_closure(rsx_sc *h, int mode, int32_t *loop_id, float *yaw
 static int helper_call(rsx_sc *h, int op, const double *a, size_t na, const double *b, size_t nb, double *out_d, size_t nd,
                        int32_t *out_i) {
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   hipStream_t s = h->stream;
   RSX_TRY(h->helper_ws.reserve((2 * DS + 128) * sizeof(double), s, false));
   double *d_a = h->helper_ws.as<double>(), *d_b = d_a + DS, *d_o = d_b + DS;
@@ -1138,7 +1144,7 @@ int rsx_sc_make_scancontext(rsx_sc *h, const void *pts, size_t n, size_t stride_
   if (!h || (!pts && n) || !out_desc) return fail(RSX_ERR_BAD_ARG, "null arg");
   if (stride_bytes < 12 || (stride_bytes & 3)) return fail(RSX_ERR_BAD_ARG, "stride_bytes must be >= 12 and a multiple of 4");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   hipStream_t s = h->stream;
   const size_t bytes = n * stride_bytes;
   RSX_TRY(h->pts_ws.reserve(bytes ? bytes : 16, s, false));
@@ -1166,7 +1172,7 @@ int rsx_sc_detect_between_session(rsx_sc *h, const float *curr_key20, const doub
   std::unique_lock<std::mutex> lk(h->mu);
   if (h->p.shard_world != 1) return fail(RSX_ERR_BAD_ARG, "unsharded handles only");
   if (h->n_global == 0) return fail(RSX_ERR_RANGE, "empty database");  // reference asserts (KDA.h:61)
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   const int64_t batch = h->batch_made ? h->batch_size : h->n_global;  // SC.cpp:275-284
   RSX_TRY(ensure_tree(h, &h->tree_batch, batch, lk));
   if (batch > h->n_global) return fail(RSX_ERR_RANGE, "the database was replaced while the ring-key tree was being built");
@@ -1237,7 +1243,7 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
   if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k must be in [1,%d]", RSX_SC_MAX_TOPK);
   // one lock for staging, query and read-back: two concurrent callers share q_desc / topk
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   RSX_TRY(h->q_desc.reserve((size_t)nq * DS * sizeof(float), h->stream, false));
   RSX_TRY(h->topk.reserve((size_t)nq * k * sizeof(rsx_sc_hit), h->stream, false));
   int32_t sizes[rsx_sc::kMaxPieces];
@@ -1539,7 +1545,7 @@ int rsx_sc_pair_distances(rsx_sc *h, const float *q_desc, int64_t first, int64_t
   std::lock_guard<std::mutex> lk(h->mu);
   if (first < 0 || count < 0 || first + count > h->n_local) return fail(RSX_ERR_RANGE, "range out of bounds");
   if (count == 0) return RSX_OK;
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   hipStream_t s = h->stream;
   RSX_TRY(h->q_desc.reserve(DS * sizeof(float), s, false));
   RSX_HIP(hipMemcpyAsync(h->q_desc.p, q_desc, DS * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1558,7 +1564,7 @@ int rsx_sc_pair_distances(rsx_sc *h, const float *q_desc, int64_t first, int64_t
 int rsx_sc_filter_bounds(rsx_sc *h, const float *q_descs, int32_t nq, float *out_lb) try {
   if (!h || !q_descs || !out_lb || nq < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   hipStream_t s = h->stream;
   const int64_t n = h->n_local;
   if (n == 0) return RSX_OK;
@@ -1587,7 +1593,7 @@ int rsx_sc_window_previews(rsx_sc *h, const float *q_descs, int32_t nq, int32_t 
     return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k=%d out of range [1,%d]", k, RSX_SC_MAX_TOPK);
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   hipStream_t s = h->stream;
   const int64_t n = h->n_local;
   for (int32_t q = 0; q < nq; q++) out_counts[q] = 0;
@@ -1673,7 +1679,7 @@ int rsx_sc_merge_topk_device(rsx_sc *h, const rsx_sc_hit *d_parts, int32_t npart
 int rsx_sc_profile_enable(rsx_sc *h, int on) try {
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
+  RSX_TRY(own_stream(h));
   if (on && !h->prof.ev) {
     h->prof.ev.reset(new (std::nothrow) Event[2 * PairProfiler::kMax]);
     if (!h->prof.ev) return fail(RSX_ERR_OOM, "host alloc");

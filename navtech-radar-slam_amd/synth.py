@@ -129,13 +129,15 @@ def rotate_descriptor(desc_f32, k):
 # ---------------------------------------------------------------------------------------------
 # ORORA: matched feature pairs between consecutive scans (seed 777)
 # ---------------------------------------------------------------------------------------------
-def orora_pairs(seed, n_pairs, k_range=(300, 1500), outlier_range=(0.2, 0.6), max_range=150.0):
+def orora_pairs(seed, n_pairs, k_range=(300, 1500), outlier_range=(0.2, 0.6), max_range=150.0, yaw_range=0.2):
     """n_pairs scan pairs.  Each: K matches, a fraction of them outliers, inliers perturbed by
     anisotropic polar noise (radial sigma 0.06 m, tangential sigma = range * 0.2 deg).
 
     Returns src (M,2) f32, dst (M,2) f32, offsets (n_pairs+1,) i64, truth (n_pairs,3) f64 with
-    dst = R(yaw) src + (x, y).
+    dst = R(yaw) src + (x, y).  yaw_range: yaw is uniform in [-yaw_range, yaw_range], or in [lo, hi] for a pair (lo, hi)
+    (lo == hi: that yaw exactly).
     """
+    ylo, yhi = (-yaw_range, yaw_range) if np.isscalar(yaw_range) else yaw_range
     rng = np.random.default_rng(seed)
     ks = rng.integers(k_range[0], k_range[1] + 1, n_pairs)
     offsets = np.zeros(n_pairs + 1, dtype=np.int64)
@@ -149,7 +151,7 @@ def orora_pairs(seed, n_pairs, k_range=(300, 1500), outlier_range=(0.2, 0.6), ma
         r = rng.uniform(4.0, max_range, k)
         th = rng.uniform(0.0, 2 * np.pi, k)
         s = np.stack([r * np.cos(th), r * np.sin(th)], axis=1)
-        yaw = rng.uniform(-0.2, 0.2)
+        yaw = rng.uniform(ylo, yhi)
         t = rng.uniform(-2.5, 2.5, 2)
         c, sn = np.cos(yaw), np.sin(yaw)
         d = s @ np.array([[c, sn], [-sn, c]]) + t

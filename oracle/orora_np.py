@@ -17,7 +17,8 @@ CHOICES = (
     "TIMs on the ring of K consecutive matches (flag: complete graph); first-iteration mu = 1 / (2 max r^2 / c^2 - 1) and stop "
     "if mu <= 0; weights updated AFTER the cost of the iteration is taken with the old weights; mu *= 1.4; stop when "
     "|cost - previous cost| < 1e-6; A-COTE bound of a match = sum over its two points (dst, R src) of the radial bound and "
-    "range x tangential bound projected on the axis (|cos|, |sin|); scalar TLS cost normalised per point: sum_C w (x - x^)^2 + "
+    "range x tangential bound projected on the axis (|cos|, |sin|), a point AT the origin (no azimuth) taking the radial bound on "
+    "both axes; scalar TLS cost normalised per point: sum_C w (x - x^)^2 + "
     "#outliers with w = beta^-2 (flag: TEASER++'s mixed-unit form); ties between equal endpoint values: lower endpoints "
     "(+id) after upper endpoints (-id) of smaller index, i.e. ordered by (value, signed id)"
 )
@@ -95,7 +96,7 @@ def _bounds(p, s_r, s_t):
     rho = np.hypot(p[:, 0], p[:, 1])
     with np.errstate(divide="ignore", invalid="ignore"):
         c = np.where(rho > 0, np.abs(p[:, 0]) / rho, 1.0)
-        s = np.where(rho > 0, np.abs(p[:, 1]) / rho, 0.0)
+        s = np.where(rho > 0, np.abs(p[:, 1]) / rho, 1.0)   # at the origin the radial bound holds along both axes
     return c * s_r + s * rho * s_t, s * s_r + c * rho * s_t
 
 

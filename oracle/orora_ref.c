@@ -102,7 +102,9 @@ double ororaref_scalar_tls(const double *x, const double *beta, int32_t n, int32
 
 static void aniso_bound(double px, double py, double s_r, double s_t, double *bx, double *by) {
   const double rho = sqrt(px * px + py * py);
-  double c = 1.0, s = 0.0;
+  /* a point AT the origin has no azimuth: the radial bound holds along both axes (c = 1, s = 0 there gave a match whose
+   * two points are both the origin a y-bound of exactly 0: weight 1 / 0, inf - inf in the running sums of the sweep) */
+  double c = 1.0, s = 1.0;
   if (rho > 0.0) {
     c = fabs(px) / rho;
     s = fabs(py) / rho;

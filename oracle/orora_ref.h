@@ -26,7 +26,7 @@
  *      cost = sum_{C} w (x - x^)^2 + |outliers| (TLS normalised per point), take the minimum.  beta_k is anisotropic: a point at range rho, azimuth
  *      phi has radial bound s_r and tangential bound rho * s_t; projected on the axes and summed
  *      for the two points of the match:
- *        beta_x = sum_{p in {dst_k, R src_k}} |cos phi_p| s_r + |sin phi_p| rho_p s_t   (y: swap)
+ *        beta_x = sum_{p in {dst_k, R src_k}} |cos phi_p| s_r + |sin phi_p| rho_p s_t   (y: swap; rho_p = 0: s_r on both axes)
  */
 #ifndef ORORA_REF_H
 #define ORORA_REF_H

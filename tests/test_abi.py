@@ -186,6 +186,137 @@ def test_handles_own_their_hip_resources():
     assert n_release >= 9  # one per handle type
 
 
+# ---- the one-handle, many-streams contract (include/rsx.h, "Conventions"): static scan ----
+
+_ENQUEUE = re.compile(r"hipLaunchKernelGGL\(|hipMemcpyAsync\(|hipMemsetAsync\(|<<<|(?:\.|->)reserve\([^;]*,[^;]*,\s*(?:true|false)\s*\)")
+_ENTER = re.compile(r"order\.enter\(")
+_NOT_A_FUNCTION = {"if", "for", "while", "switch", "return", "sizeof", "catch", "else", "do", "new", "delete", "defined", "static_assert"}
+
+
+def _functions(csrc):
+    """name -> [(file, parameter text, body text)] for every function DEFINED under csrc (comments stripped; bodies by brace
+    matching).  Member functions of the helper structs (DevBuf::reserve, KeypointStaging::extract_batch) are found too."""
+    import glob
+    defs = {}
+    for f in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "*.h"))):
+        txt = open(f).read()
+        txt = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), txt, flags=re.S)
+        txt = re.sub(r"//[^\n]*", "", txt)
+        for m in re.finditer(r"(?m)^[ \t]*(?:[\w:<>,&*]+[ \t]+)+[*&]?(\w+)\(", txt):
+            name = m.group(1)
+            if name in _NOT_A_FUNCTION or "__global__" in m.group(0) or "__device__" in m.group(0):
+                continue
+            i, depth = m.end(), 1
+            while i < len(txt) and depth:   # the parameter list
+                depth += {"(": 1, ")": -1}.get(txt[i], 0)
+                i += 1
+            head = re.match(r"\s*(?:const\s*)?(?:noexcept\s*)?(?:try\s*)?\{", txt[i:])
+            if not head:
+                continue                    # a declaration, a call, a constructor with initialisers
+            j = i + head.end()
+            k, depth = j, 1
+            while k < len(txt) and depth:
+                depth += {"{": 1, "}": -1}.get(txt[k], 0)
+                k += 1
+            defs.setdefault(name, []).append((os.path.basename(f), txt[m.end():i - 1], txt[j:k - 1]))
+    return defs
+
+
+def _first_event(defs, name, fname, body, seen):
+    """'enter' / 'enqueue' / None: what a function does FIRST in the order of its text, calls into other functions of csrc
+    followed (same file first; where a name has several definitions the least ordered one counts)."""
+    for m in re.finditer(r"order\.enter\(|hipLaunchKernelGGL\(|hipMemcpyAsync\(|hipMemsetAsync\(|<<<|(?:\.|->)reserve\(|\b(\w+)\s*\(", body):
+        tok = m.group(0)
+        if _ENTER.match(tok):
+            return "enter"
+        if tok.endswith("reserve("):
+            if _ENQUEUE.match(body[m.start():body.find(";", m.start()) + 1].replace("\n", " ")):
+                return "enqueue"
+            continue
+        if _ENQUEUE.match(tok):
+            return "enqueue"
+        callee = m.group(1)
+        if callee is None or callee == name or callee not in defs or callee in seen:
+            continue
+        cands = [d for d in defs[callee] if d[0] == fname] or defs[callee]
+        got = {_first_event(defs, callee, d[0], d[2], seen | {callee}) for d in cands}
+        if "enqueue" in got:
+            return "enqueue"
+        if "enter" in got:
+            return "enter"
+    return None
+
+
+def _stream_contract_scan(csrc):
+    """-> (entries inspected, {entry: first event}) over every handle type that has an extern "C" entry with a `void *stream`
+    parameter: each entry of such a type that enqueues work at all (a launch, hipMemcpyAsync, hipMemsetAsync, DevBuf::reserve,
+    directly or through helpers)."""
+    defs = _functions(csrc)
+    entries = {}
+    for name, ds in defs.items():
+        for fname, params, body in ds:
+            m = re.match(r"\s*(?:const\s+)?(rsx_\w+) \*h\b", params)
+            if name.startswith("rsx_") and m and name.startswith(m.group(1) + "_"):
+                entries[name] = (m.group(1), fname, params, body)
+    types = {t for t, _, params, _ in entries.values() if re.search(r"void \*stream\b", params)}
+    result = {}
+    for name, (t, fname, params, body) in entries.items():
+        if t in types:
+            ev = _first_event(defs, name, fname, body, frozenset())
+            if ev:
+                result[name] = (t, ev)
+    return types, entries, result
+
+
+# entry -> why it may enqueue without StreamOrder::enter; every reason is CHECKED below
+_STREAM_ORDER_EXEMPT = {
+    "rsx_ransac_estimate_batch_device": "no-workspace",   # reads and writes the caller's buffers only (ransac.hip, rsx.h)
+    "rsx_ransac_estimate_batch": "own-stream-only-type",  # the type's workspaces are touched by this entry alone, always on h->stream
+}
+
+
+def _unordered_entries(csrc):
+    types, entries, result = _stream_contract_scan(csrc)
+    bad = []
+    for name, (t, ev) in sorted(result.items()):
+        if ev == "enter":
+            continue
+        reason = _STREAM_ORDER_EXEMPT.get(name)
+        body = entries[name][3]
+        members = set(re.findall(r"\bh->(\w+)", body))
+        if reason == "no-workspace":
+            # names no member of the handle but its stream (and the device ordinal it makes current)
+            if members <= {"stream", "device"}:
+                continue
+        elif reason == "own-stream-only-type":
+            # works on h->stream only, and every OTHER enqueuing entry of the type is exempt as workspace-free: the workspaces
+            # never see a second stream
+            others = [n for n, (tt, _) in result.items() if tt == t and n != name]
+            if (not re.search(r"\bstream\s*\?", body) and "void *stream" not in entries[name][2]
+                    and all(_STREAM_ORDER_EXEMPT.get(n) == "no-workspace" for n in others)):
+                continue
+        bad.append(name)
+    return types, result, bad
+
+
+def test_every_stream_taking_handle_orders_its_calls():
+    """include/rsx.h: "Calls on ONE handle that pass different streams are ordered by the library".  Static check over csrc/:
+    for every handle type with an entry that takes a `void *stream`, EVERY entry of the type that enqueues work (the host-buffer
+    entries on the handle's own stream included) passes its stream through rsx::StreamOrder::enter before the first launch,
+    hipMemcpyAsync, hipMemsetAsync or DevBuf::reserve -- directly, or through a helper / another entry that does.  ("Before" is
+    the order of the source text, calls followed.)  Exemptions are listed with a reason the test checks."""
+    csrc = os.path.join(ROOT, "navtech-radar-slam_amd", "csrc")
+    types, result, bad = _unordered_entries(csrc)
+    assert {"rsx_sc", "rsx_orora", "rsx_ransac", "rsx_cen2019", "rsx_cen2018", "rsx_frontend"} <= types, types
+    assert not bad, "entries that enqueue work before StreamOrder::enter: " + ", ".join(bad)
+    for name in _STREAM_ORDER_EXEMPT:
+        assert name in result, name + ": exempt but not found (or it no longer enqueues anything)"
+    # a regex that stops matching must not turn this into a no-op
+    assert len(result) >= 50, len(result)
+    per_type = {t: sum(1 for tt, _ in result.values() if tt == t) for t in types}
+    assert per_type["rsx_orora"] >= 5 and per_type["rsx_cen2019"] >= 3 and per_type["rsx_frontend"] >= 7 and per_type["rsx_cen2018"] >= 4, per_type
+
+
 def test_exceptions_thrown_inside_the_library_come_back_as_statuses(rsx):
     """rsx_selftest_firewall throws inside an extern "C" entry: an impossible std::vector size (std::length_error), a
     std::bad_alloc, a std::runtime_error (what nanoflann throws through the reference's SCManager, NF.hpp:1228,1324) and a

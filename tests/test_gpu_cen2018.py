@@ -189,33 +189,52 @@ def test_bad_arguments(cen):
     assert L.rsx_cen2018_extract(ex._h, img.ctypes.data, 64, 0, C.byref(p), None, 0.05, out.ctypes.data, None, 10, C.byref(n)) == 0
 
 
-def test_one_handle_two_streams(cen):
-    """the same handle used from two streams back to back: each call ordered behind the other's work"""
+def _stream_calls(cen, pool, az, serial):
+    """nine rsx_cen2018_extract_batch_device calls on a FRESH handle, consecutive calls with different images and batch sizes and
+    every call with its own sentinel-filled outputs: rotating over three streams with no host synchronisation in between
+    (serial=False), or on one stream with a synchronise after every call"""
     import torch
-    imgs = np.stack([synth.polar_image(60 + i, n_targets=900)[0] for i in range(4)])
+    from navtech_radar_slam_amd import _rsx
+    ex = cen.Cen2018(400, 3360)
+    d_az = torch.from_numpy(az).cuda()
+    streams = [torch.cuda.Stream() for _ in range(1 if serial else 3)]
+    p = cen.default_params()
+    calls = []
+    for nb, first in ((4, 0), (2, 3), (3, 1), (1, 4), (4, 1), (2, 0), (5, 2), (1, 3), (3, 4)):
+        which = [(first + i) % len(pool) for i in range(nb)]
+        imgs = np.ascontiguousarray(pool[which])
+        calls.append((which, imgs, torch.from_numpy(imgs).cuda(), torch.full((nb, 20000, 2), -1, dtype=torch.int32, device="cuda"),
+                      torch.full((nb,), -1, dtype=torch.int32, device="cuda")))
+    torch.cuda.synchronize()
+    for r, (which, imgs, d_img, tg, cn) in enumerate(calls):
+        s = streams[r % len(streams)]
+        _rsx.check(ex._L.rsx_cen2018_extract_batch_device(ex._h, d_img.data_ptr(), len(which), imgs.strides[0], imgs.shape[2], 11, C.byref(p),
+                                                           d_az.data_ptr(), 0, synth.RADAR_RESOLUTION, tg.data_ptr(), None, 20000,
+                                                           cn.data_ptr(), C.c_void_p(s.cuda_stream)))
+        if serial:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    out = [(which, tg.cpu().numpy(), cn.cpu().numpy()) for which, _, _, tg, cn in calls]
+    ex.close()
+    return out
+
+
+def test_one_handle_two_streams(cen):
+    """the same handle used from several streams back to back: each call ordered behind the other's work.  Nine calls rotate over
+    three streams; consecutive calls carry different images and batch sizes (a workspace clobbered by an IDENTICAL call would
+    go unseen), every call has its own sentinel-filled outputs, and there is no host synchronisation between the calls.  Byte
+    for byte what the same calls give one at a time on a fresh handle, and the host entry's keypoints for every image."""
+    pool = np.stack([synth.polar_image(60 + i, n_targets=700 + 100 * i)[0] for i in range(5)])
     az = synth.polar_image(60)[1]
     ex = cen.Cen2018(400, 3360)
-    want, _ = ex.extract_batch(imgs, azimuths=az, resolution=synth.RADAR_RESOLUTION)
-    from navtech_radar_slam_amd import _rsx
-    d_img = torch.from_numpy(imgs).cuda()
-    d_az = torch.from_numpy(az).cuda()
-    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
-    outs = []
-    p = cen.default_params()
-    torch.cuda.synchronize()
-    for r in range(3):
-        for s in (s1, s2):
-            tg = torch.full((4, 20000, 2), -1, dtype=torch.int32, device="cuda")
-            cn = torch.zeros(4, dtype=torch.int32, device="cuda")
-            _rsx.check(ex._L.rsx_cen2018_extract_batch_device(ex._h, d_img.data_ptr(), 4, imgs.strides[0], imgs.shape[2], 11, C.byref(p),
-                                                               d_az.data_ptr(), 0, synth.RADAR_RESOLUTION, tg.data_ptr(), None, 20000,
-                                                               cn.data_ptr(), C.c_void_p(s.cuda_stream)))
-            outs.append((s, tg, cn))
-    torch.cuda.synchronize()
-    for s, tg, cn in outs:
-        t, c = tg.cpu().numpy(), cn.cpu().numpy()
-        for i in range(4):
-            assert c[i] == len(want[i]) and np.array_equal(t[i, :c[i]], want[i])
+    want, _ = ex.extract_batch(pool, azimuths=az, resolution=synth.RADAR_RESOLUTION)
+    serial = _stream_calls(cen, pool, az, True)
+    got = _stream_calls(cen, pool, az, False)
+    for (which, t, c), (_, st, sc) in zip(got, serial):
+        assert t.tobytes() == st.tobytes() and c.tobytes() == sc.tobytes()
+        for i, w in enumerate(which):
+            assert c[i] == len(want[w]) and np.array_equal(t[i, :c[i]], want[w])
+            assert (t[i, c[i]:] == -1).all()
 
 
 def test_create_use_destroy_leaves_device_memory_as_it_was(cen):

@@ -184,3 +184,53 @@ def test_wavefront_per_azimuth_forms(cen, oracle):
                 assert np.array_equal(tg[b], want), (rows, cols, mp, mr, b, b % 8, len(tg[b]), len(want))
                 if b < 8:  # the same images one by one: the workgroup-per-azimuth forms with their light path (single scans)
                     assert np.array_equal(ex.extract(imgs[b], col_offset=0, max_points=mp, min_range=mr), want), (rows, cols, mp, mr, b, "single")
+
+
+def _three_stream_calls(cen, pool, az, serial):
+    """nine rsx_cen2019_extract_batch_device calls on a FRESH handle, batches of 1 / 3 / 5 scans, each call with its own images and
+    sentinel-filled outputs: rotating over three streams with no host synchronisation (serial=False), or one at a time"""
+    import ctypes as C
+    import torch
+    from navtech_radar_slam_amd import _rsx
+    ex = cen.Cen2019(400, 3360)
+    p = cen.default_params()
+    d_az = torch.from_numpy(np.ascontiguousarray(az, dtype=np.float32)).cuda()
+    streams = [torch.cuda.Stream() for _ in range(1 if serial else 3)]
+    MT = 12000
+    calls = []
+    for c, nb in enumerate((1, 3, 5, 3, 1, 5, 3, 5, 1)):
+        which = [(3 * c + i) % len(pool) for i in range(nb)]
+        imgs = np.ascontiguousarray(pool[which])
+        calls.append((which, imgs, torch.from_numpy(imgs).cuda(), torch.full((nb, MT, 2), -1, dtype=torch.int32, device="cuda"),
+                      torch.full((nb, MT, 2), -1.0, dtype=torch.float32, device="cuda"), torch.full((nb,), -1, dtype=torch.int32, device="cuda")))
+    torch.cuda.synchronize()
+    for c, (which, imgs, d_img, tg, xy, cn) in enumerate(calls):
+        s = streams[c % len(streams)]
+        _rsx.check(ex._L.rsx_cen2019_extract_batch_device(ex._h, d_img.data_ptr(), len(which), imgs.strides[0], imgs.shape[2], 11, C.byref(p),
+                                                           d_az.data_ptr(), 0, synth.RADAR_RESOLUTION, tg.data_ptr(), xy.data_ptr(), MT,
+                                                           cn.data_ptr(), C.c_void_p(s.cuda_stream)))
+        if serial:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    out = [(which, tg.cpu().numpy(), xy.cpu().numpy(), cn.cpu().numpy()) for which, _, _, tg, xy, cn in calls]
+    ex.close()
+    return out
+
+
+def test_one_handle_three_streams(cen, oracle):
+    """include/rsx.h: calls on ONE handle that pass different streams are ordered by the library (the chain works in the handle's
+    scal, hist, list, row_out, row_runs, markbits ...).  Targets, points and counts of every call byte for byte what the same
+    calls give one at a time, and the oracle's keypoints for every scan."""
+    pool = np.stack([synth.polar_image(70 + i, n_targets=500 + 150 * i)[0] for i in range(7)])
+    az = synth.polar_image(70)[1]
+    want = [oracle.cen2019_extract(img) for img in pool]
+    serial = _three_stream_calls(cen, pool, az, True)
+    got = _three_stream_calls(cen, pool, az, False)
+    assert len({len(w) for w in want}) == len(want)     # the scans differ
+    for c, ((which, tg, xy, cn), (_, stg, sxy, scn)) in enumerate(zip(got, serial)):
+        assert cn.tobytes() == scn.tobytes() and tg.tobytes() == stg.tobytes() and xy.tobytes() == sxy.tobytes(), c
+        for i, w in enumerate(which):
+            assert cn[i] == len(want[w]) and np.array_equal(tg[i, :cn[i]], want[w]), (c, i)
+            assert (tg[i, cn[i]:] == -1).all()
+            wxy = oracle.cen2019_to_cartesian(want[w], az, synth.RADAR_RESOLUTION)
+            assert np.allclose(xy[i, :cn[i]], wxy, rtol=1e-5, atol=1e-4)

@@ -236,3 +236,94 @@ def test_consecutive_matching_sizes_and_ties(fe, oracle):
         some += int((f_idx >= 0).sum())
     assert some > 50
     g.close()
+
+
+def _scene(seed, rng, K):
+    img, az, centres = synth.polar_image(seed, n_targets=600, noise_seed=seed + 7)
+    a, r = centres[:, 0], centres[:, 1]
+    rr = (r + 0.5) * synth.RADAR_RESOLUTION
+    pts = np.stack([rr * np.cos(az[a]), rr * np.sin(az[a])], axis=1).astype(np.float32)
+    pts = np.concatenate([pts, rng.uniform(-135, 135, (K, 2)).astype(np.float32)])[:K]
+    return img, az, pts
+
+
+def _frontend_chains(fe, chains, last, W, res, K, serial):
+    """the chains cartesian_batch_device_az -> describe_batch_device -> match_consecutive_device, one chain per stream in rotation
+    on a FRESH handle, then a device cartesian_batch_device (host azimuths) on a caller's stream followed directly by the
+    host-buffer describe on the handle's own stream; no host synchronisation unless serial"""
+    import torch
+    from navtech_radar_slam_amd import _rsx
+    p = fe.default_params()
+    p.cart_pixel_width, p.cart_resolution = W, res
+    g = fe.Frontend(400, 3360, params=p)
+    streams = [torch.cuda.Stream() for _ in range(1 if serial else 3)]
+    bufs = []
+    for imgs, azs, xys, counts in chains:
+        n = len(imgs)
+        bufs.append((n, imgs, torch.from_numpy(imgs).cuda(), torch.from_numpy(azs).cuda(), torch.from_numpy(xys).cuda(), torch.from_numpy(counts).cuda(),
+                     torch.full((n, K, 32), 0xA5, dtype=torch.uint8, device="cuda"), torch.full((n, K), 0xA5, dtype=torch.uint8, device="cuda"),
+                     torch.full((n - 1, K), -7, dtype=torch.int32, device="cuda"), torch.full((n - 1, K), -7, dtype=torch.int32, device="cuda")))
+    l_img, l_az, l_xy = last
+    d_last = torch.from_numpy(l_img).cuda()
+    torch.cuda.synchronize()
+    for c, (n, imgs, d_img, d_az, d_xy, d_cnt, d_desc, d_valid, d_fwd, d_bwd) in enumerate(bufs):
+        s = streams[c % len(streams)].cuda_stream
+        g.cartesian_batch_device(d_img.data_ptr(), n, imgs.strides[0], imgs.shape[2], d_az.data_ptr(), 400, synth.RADAR_RESOLUTION, stream=s)
+        if serial:
+            torch.cuda.synchronize()
+        g.describe_batch_device(d_xy.data_ptr(), d_cnt.data_ptr(), n, K, d_desc.data_ptr(), d_valid.data_ptr(), stream=s)
+        if serial:
+            torch.cuda.synchronize()
+        g.match_consecutive_device(d_desc.data_ptr(), d_valid.data_ptr(), d_cnt.data_ptr(), K, 0, n - 1, 0.8, d_fwd.data_ptr(), d_bwd.data_ptr(), stream=s)
+        if serial:
+            torch.cuda.synchronize()
+    s = streams[len(bufs) % len(streams)].cuda_stream
+    _rsx.check(g._L.rsx_frontend_cartesian_batch_device(g._h, d_last.data_ptr(), 1, l_img.strides[0], l_img.shape[2], 11, l_az.ctypes.data,
+                                                        synth.RADAR_RESOLUTION, s))
+    if serial:
+        torch.cuda.synchronize()
+    host_desc = g.describe(l_xy)      # host buffers, the handle's own stream: must see the NEW image
+    torch.cuda.synchronize()
+    out = [(d_desc.cpu().numpy(), d_valid.cpu().numpy(), d_fwd.cpu().numpy(), d_bwd.cpu().numpy()) for *_, d_desc, d_valid, d_fwd, d_bwd in bufs]
+    g.close()
+    return out, host_desc
+
+
+def test_one_handle_three_streams(fe, oracle):
+    """include/rsx.h: calls on ONE handle that pass different streams are ordered by the library (cart, blur, uv, vidx, vcount, az1
+    and the map are the handle's).  Four chains of three device calls, each chain on the next of three streams with its own
+    images, batch size and sentinel-filled outputs; then a host-buffer describe directly behind a device Cartesian call on a
+    caller's stream.  Byte for byte what the same calls give one at a time, and oracle.FrontendRef for every image."""
+    rows, cols, W, res, K = 400, 3360, 301, 0.9, 640
+    rng = np.random.default_rng(5)
+    chains, seed = [], 100
+    for n, cnts in ((2, (600, 333)), (4, (17, 640, 0, 500)), (3, (450, 1, 620)), (2, (580, 610))):
+        sc = [_scene(seed + i, rng, K) for i in range(n)]
+        seed += n
+        chains.append((np.ascontiguousarray(np.stack([s[0] for s in sc])), np.ascontiguousarray(np.stack([s[1] for s in sc]), dtype=np.float32),
+                       np.ascontiguousarray(np.stack([s[2] for s in sc])), np.array(cnts, dtype=np.int32)))
+    l_img, l_az, l_xy = _scene(seed, rng, K)
+    last = (np.ascontiguousarray(l_img[None]), np.ascontiguousarray(l_az, dtype=np.float32), l_xy)
+    want, want_host = _frontend_chains(fe, chains, last, W, res, K, True)
+    got, got_host = _frontend_chains(fe, chains, last, W, res, K, False)
+    o = oracle.FrontendRef(rows, cols, W, res)
+    o.cartesian(l_img, l_az, synth.RADAR_RESOLUTION)
+    do, vo = o.describe(l_xy)
+    for a, b in zip(got_host, want_host):
+        assert np.array_equal(a, b)
+    assert np.array_equal(got_host[0], do) and np.array_equal(got_host[1], vo) and 0 < vo.sum()
+    for c, ((imgs, azs, xys, counts), g_, w_) in enumerate(zip(chains, got, want)):
+        for a, b in zip(g_, w_):
+            assert a.tobytes() == b.tobytes(), c
+        desc, valid, fwd, bwd = g_
+        ref = []
+        for k in range(len(imgs)):
+            o = oracle.FrontendRef(rows, cols, W, res)
+            o.cartesian(imgs[k], azs[k], synth.RADAR_RESOLUTION)
+            dk, vk = o.describe(xys[k, :counts[k]])
+            assert np.array_equal(valid[k, :counts[k]], vk) and np.array_equal(desc[k, :counts[k]], dk), (c, k)
+            ref.append((dk, vk, o))
+        for j in range(len(imgs) - 1):
+            (qa, va, o), (qb, vb, _) = ref[j], ref[j + 1]
+            assert np.array_equal(fwd[j, :counts[j]], o.match(qa, va, qb, vb, 0.8)[0]), (c, j)
+            assert np.array_equal(bwd[j, :counts[j + 1]], o.match(qb, vb, qa, va, 0.8)[0]), (c, j)

@@ -275,3 +275,48 @@ def test_inserts_do_not_wait_and_later_calls_see_them(sc):
             got = out.cpu().numpy().view(sc.HIT_DTYPE).reshape(8)
             assert np.array_equal(got["index"], np.arange(8)) and np.all(got["dist"] < 1e-12), i   # every query finds itself
     assert np.array_equal(g.export_descriptors_f32(0, len(clouds)), descs)
+
+
+def test_host_entries_are_ordered_behind_device_entries_on_other_streams(sc):
+    """include/rsx.h: calls on ONE handle that pass different streams are ordered by the library -- the host-buffer entries, which
+    work on the handle's own stream in the same workspaces, included.  Device queries on three caller streams, each with its own
+    queries, batch size and sentinel-filled output, alternate with host-buffer queries and bulk inserts (which may move the
+    database to a larger allocation) with no host synchronisation by the caller in between.  Every record equals the one a
+    fresh handle gives for the same calls one at a time, with a synchronise after each."""
+    import torch
+    k, n0 = 3, 900
+    db = synth.random_descriptors(21, n0 + 3 * 700, binary=True)
+    qs = [synth.random_descriptors(30 + c, nq, binary=True) for c, nq in enumerate((700, 64, 1500, 9, 2100, 300, 33, 1100, 5))]
+    for c, q in enumerate(qs):
+        q[::5] = db[(np.arange(len(q[::5])) * (c + 3)) % n0]            # revisits of entries every call can see
+
+    def run(serial):
+        g = sc.SCManager()
+        g.add_descriptors_f32(db[:n0])
+        streams = [torch.cuda.Stream() for _ in range(1 if serial else 3)]
+        d_q = [torch.from_numpy(q).cuda() for q in qs]
+        outs = [torch.full((len(q), k, 2), -3.0, dtype=torch.float64, device="cuda") for q in qs]
+        host = {}
+        torch.cuda.synchronize()
+        n = n0
+        for c, q in enumerate(qs):
+            if c % 3 == 2:       # host buffers, the handle's own stream, straight behind a device call on a caller's stream
+                host[c] = g.query(q, k=k, n_eligible=n0)
+                g.add_descriptors_f32(db[n:n + 700])
+                n += 700
+            else:
+                g.query_device(d_q[c].data_ptr(), len(q), k, outs[c].data_ptr(), n_eligible=n0, stream=streams[c % len(streams)].cuda_stream)
+            if serial:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        res = [host[c] if c in host else outs[c].cpu().numpy().view(sc.HIT_DTYPE).reshape(len(q), k) for c, q in enumerate(qs)]
+        tail = g.export_descriptors_f32(0, n)
+        g.close()
+        return res, tail
+
+    want, want_db = run(True)
+    got, got_db = run(False)
+    assert np.array_equal(got_db, db) and np.array_equal(want_db, db)
+    for c in range(len(qs)):
+        assert got[c].tobytes() == want[c].tobytes(), c
+        assert (got[c]["dist"][::5, 0] < 1e-12).all(), c               # every revisit finds an entry at distance 0
