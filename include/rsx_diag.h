@@ -86,6 +86,9 @@ typedef struct {
   int64_t window_previews;     /* candidates whose alignment + preview came from the matrix-core window kernel (sc_window.hip) */
   int64_t valu_previews;       /* candidates that needed the per-wavefront VALU alignment + fp32 preview */
   int64_t exact_window_shifts; /* window shifts evaluated exactly (<= 7 per exact evaluation, SC.cpp:131-139) */
+  int64_t tail_evals;          /* exact evaluations of short-list positions behind the stored head of the list (csrc/sc_filter.hip
+                                  sc_select_kernel stores RESCORE_HEAD positions; the rest is found in the row of bounds) */
+  int64_t tail_queries;        /* (query, launch) pairs whose walk went behind the head */
 } rsx_sc_rescoring_stats;
 int rsx_sc_profile_read_rescoring(rsx_sc *h, rsx_sc_rescoring_stats *out);
 

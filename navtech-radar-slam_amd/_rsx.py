@@ -52,6 +52,10 @@ class RescoringStats(C.Structure):  # rsx_sc_rescoring_stats (include/rsx_diag.h
                 ("exact_window_shifts", C.c_int64)]
 
 
+class RescoringStatsTail(RescoringStats):  # the same struct with the fields appended since (struct_size tells the library)
+    _fields_ = [("tail_evals", C.c_int64), ("tail_queries", C.c_int64)]
+
+
 ORORA_PMC = 4  # rsx_orora_params.flags: max-clique inlier selection before the solver
 ORORA_PMC_EXACT = 8  # (with ORORA_PMC) exact maximum clique within the handle's node budget
 ORORA_PMC_PROVEN, ORORA_PMC_PASSTHROUGH, ORORA_PMC_NO_WORKSPACE, ORORA_PMC_MAXIMUM, ORORA_PMC_BUDGET = 1, 2, 4, 8, 16

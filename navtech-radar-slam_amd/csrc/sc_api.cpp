@@ -1697,7 +1697,7 @@ int rsx_sc_profile_enable(rsx_sc *h, int on) try {
 
 int rsx_sc_profile_read_rescoring(rsx_sc *h, rsx_sc_rescoring_stats *out) try {
   if (!h || !out || out->struct_size < offsetof(rsx_sc_rescoring_stats, candidates)) return fail(RSX_ERR_BAD_ARG, "null arg / struct_size not set");
-  int64_t out6[6];
+  int64_t out6[8];
   int64_t *const out5 = out6;
   int64_t *candidates = out5, *exact_evals = out5 + 1, *queries_rescored = out5 + 2;
   // copies the fields that fit into the caller's struct_size on every return path
@@ -1707,12 +1707,12 @@ int rsx_sc_profile_read_rescoring(rsx_sc *h, rsx_sc_rescoring_stats *out) try {
     ~Publish() {
       int64_t *dst = &o->candidates;
       const size_t n = (o->struct_size - offsetof(rsx_sc_rescoring_stats, candidates)) / sizeof(int64_t);
-      for (size_t i = 0; i < n && i < 6; i++) dst[i] = v[i];
+      for (size_t i = 0; i < n && i < 8; i++) dst[i] = v[i];
     }
   } publish{out, out6};
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_TRY(set_device(h));
-  for (int i = 0; i < 6; i++) out6[i] = 0;
+  for (int i = 0; i < 8; i++) out6[i] = 0;
   if (!h->stats.p) return RSX_OK;
   RSX_HIP(hipDeviceSynchronize());  // the counters are bumped by kernels on the caller's stream
   unsigned long long v[RESCORE_STAT_WORDS] = {0};
@@ -1735,6 +1735,8 @@ int rsx_sc_profile_read_rescoring(rsx_sc *h, rsx_sc_rescoring_stats *out) try {
   out5[3] = (int64_t)v[3];   // candidates whose alignment + preview came from the window kernel (sc_window.hip)
   out5[4] = (int64_t)v[11];  // candidates that went through the VALU alignment + fp32 preview / exact alignments (wave kernel)
   out6[5] = v[12] ? (int64_t)v[12] : 7 * *exact_evals;  // window shifts evaluated exactly (7 per evaluation without a shift mask)
+  out6[6] = (int64_t)v[15];  // exact evaluations of list positions behind the stored head (found in the row of bounds)
+  out6[7] = (int64_t)v[16];  // (query, launch) pairs that walked behind the head
   return RSX_OK;
 } RSX_CATCH_ALL
 

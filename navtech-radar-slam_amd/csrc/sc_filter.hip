@@ -462,17 +462,10 @@ __global__ __launch_bounds__(256, 1) void sc_filter_kernel(FilterArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// bound histogram: 2048 bins over [0, 1) (bounds outside land in the end bins).  bin(x) <= b  <=>
-// x < (b+1)/2048 exactly (power-of-two scaling), so a "bound < edge" test selects whole bins.
+// bound histogram: lb_bin / lb_bin_edge of sc_kernels.h (the re-scoring kernel bins the same bounds the same way)
 // ------------------------------------------------------------------------------------------
-constexpr int H_BINS = 2048;
+constexpr int H_BINS = RESCORE_BINS;
 constexpr int SEL_U = 5;  // 16-byte loads in flight per thread of sc_select_kernel (a 10 016-entry row of fp16 bounds = 1 piece)
-
-__device__ __forceinline__ int lb_bin(float d) {
-  if (!(d > 0.0f)) return 0;  // negative, -inf, NaN
-  const float x = d * (float)H_BINS;
-  return x >= (float)(H_BINS - 1) ? H_BINS - 1 : (int)x;
-}
 
 // entries [0, n_elig_items(q)) of a row are eligible for query q: local slot i has global index
 // idx_base + i * idx_stride, eligible iff that is < min(n_eligible, q_elig[q])
@@ -496,11 +489,11 @@ __device__ __forceinline__ int64_t n_elig_items(const Elig &el, int q, int64_t n
 // prefix sum, then
 //   t_cap  = edge of the last bin b_cap whose cumulative count still fits RESCORE_SHORTLIST_CAP
 //   t_r    = edge of the first bin with at least target[r] bounds at or below it, clamped to t_cap
-//   slist  = (bound, slot) of every eligible entry in bins <= b_cap  (bound < t_cap)
+//   b_head = the first bin whose cumulative count reaches RESCORE_HEAD, clamped to b_cap
+//   slist  = (bound, slot) of every eligible entry in bins <= b_head: the HEAD of the list "eligible entries in bins
+//            <= b_cap".  The counts and edges describe the whole list; the re-scoring kernel takes what lies behind the head
+//            from the row of bounds (writing all of it was 134 MB per 8192 queries, of which 121 records per query were used)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float bin_edge(int b) {  // upper edge of bin b as a "bound < edge" test
-  return b < 0 ? -INFINITY : (b >= H_BINS - 1 ? INFINITY : (float)(b + 1) / (float)H_BINS);
-}
 
 __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__ lb, int64_t ld, int64_t n_items_all,
                                                         Elig el, int32_t first_target,
@@ -604,21 +597,30 @@ __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__
       if (b > H_BINS - 1) b = H_BINS - 1;
       if (b > b_cap) b = b_cap;
     }
-    thr[(int64_t)q * RESCORE_THR_STRIDE + threadIdx.x] = bin_edge(b);
+    thr[(int64_t)q * RESCORE_THR_STRIDE + threadIdx.x] = lb_bin_edge(b);
     reinterpret_cast<int32_t *>(thr)[(int64_t)q * RESCORE_THR_STRIDE + RESCORE_NUM_THR + threadIdx.x] = b >= 0 ? hist[b] : 0;
   }
-  // compaction of bins <= b_cap, ORDERED BY BIN (counting sort: entry of bin b goes to [cum[b-1], cum[b]),
-  // any order inside a bin): the window records cover the head of the list, and sc_rescore_wave_kernel walks the rest in
-  // ascending-bound order, stopping at the first bin whose lower edge tau excludes
+  // the head: whole bins, at least RESCORE_HEAD positions unless the list is shorter
+  int b_head = first_reaching(RESCORE_HEAD);
+  if (b_head > b_cap) b_head = b_cap;
+  if (threadIdx.x == 0) {
+    int32_t *hd = reinterpret_cast<int32_t *>(thr) + (int64_t)q * RESCORE_THR_STRIDE;
+    hd[RESCORE_THR_HEAD_BIN] = b_head;
+    hd[RESCORE_THR_HEAD_END] = b_head >= 0 ? hist[b_head] : 0;
+  }
+  // compaction of bins <= b_head, ORDERED BY BIN (counting sort: entry of bin b goes to [cum[b-1], cum[b]),
+  // any order inside a bin): the window records cover the first WINDOW_P positions, and sc_rescore_wave_kernel walks the
+  // rest -- the head from these records, then bin by bin from the row -- in ascending-bound order, stopping at the first bin
+  // whose lower edge tau excludes
   RescoreEntry *out = slist + (int64_t)q * RESCORE_SHORTLIST_CAP;
   __shared__ int fill[H_BINS];
   for (int i = threadIdx.x; i < H_BINS; i += 256) fill[i] = i ? hist[i - 1] : 0;  // exclusive prefix = first position
   __syncthreads();
-  if (b_cap >= 0) {
+  if (b_head >= 0) {
     for_row(false, [&](float d, int64_t i) {  // second pass: the kept registers (or, for a long row, a second reading)
       if (d == INFINITY) return;
       const int b = lb_bin(d);
-      if (b > b_cap) return;
+      if (b > b_head) return;
       RescoreEntry e;
       e.lb = d;
       e.slot = (int32_t)i;

@@ -39,9 +39,27 @@ struct DbView {
 // relative looseness (eps is 1.25e-3).
 using lb_t = _Float16;
 typedef _Float16 lb2_t __attribute__((ext_vector_type(2)));
+// Histogram of the bounds the short-list selection and the re-scoring share: RESCORE_BINS bins over [0, 1), bounds outside
+// land in the end bins.  bin(x) <= b  <=>  x < (b + 1) / RESCORE_BINS exactly (power-of-two scaling), so a "bound < edge" test
+// selects whole bins.
+constexpr int RESCORE_BINS = 2048;
 #ifdef __HIPCC__
 __device__ __forceinline__ lb_t lb_pack(float v) {
   return __builtin_bit_cast(lb2_t, __builtin_amdgcn_cvt_pkrtz(v, 0.0f))[0];
+}
+__device__ __forceinline__ int lb_bin(float d) {
+  if (!(d > 0.0f)) return 0;  // negative, -inf, NaN
+  const float x = d * (float)RESCORE_BINS;
+  return x >= (float)(RESCORE_BINS - 1) ? RESCORE_BINS - 1 : (int)x;
+}
+__device__ __forceinline__ float lb_bin_edge(int b) {  // upper edge of bin b as a "bound < edge" test
+  return b < 0 ? -INFINITY : (b >= RESCORE_BINS - 1 ? INFINITY : (float)(b + 1) / (float)RESCORE_BINS);
+}
+__device__ __forceinline__ int lb_edge_bin(float edge) {  // the inverse: the bin whose upper edge this is
+  return edge == -INFINITY ? -1 : (edge == INFINITY ? RESCORE_BINS - 1 : (int)(edge * (float)RESCORE_BINS) - 1);
+}
+__device__ __forceinline__ float lb_bin_lo(int b) {  // lower edge of bin b (bin 0 also takes what is below 0)
+  return b <= 0 ? -INFINITY : (float)b / (float)RESCORE_BINS;
 }
 #endif
 
@@ -99,15 +117,24 @@ int launch_knn(const float *rkeys, int64_t n_search, const float *qkey, int32_t 
                int32_t *out_idx, float *out_dist, int32_t *out_found, hipStream_t s);
 
 // ---- exact re-scoring behind the filter ----
-constexpr int RESCORE_SHORTLIST_CAP = 2048;  // short-list records per query
+constexpr int RESCORE_SHORTLIST_CAP = 2048;  // short-list positions per query (sl_cnt <= this; stride of the record array)
+// Only the HEAD of a short list is stored as records: the bins up to the first one whose cumulative count reaches
+// RESCORE_HEAD (clamped to the last bin of the list).  sc_window_kernel reads positions below min(sl_cnt, WINDOW_P) and
+// nothing else; sc_rescore_wave_kernel re-derives the positions behind the head from the query's row of bounds.
+constexpr int RESCORE_HEAD = 512;
+static_assert(RESCORE_HEAD >= RSX_SC_WINDOW_P && RESCORE_HEAD <= RESCORE_SHORTLIST_CAP,
+              "the head must cover every list position sc_window_kernel may read (WINDOW_P)");
 constexpr int RESCORE_NUM_THR = 6;           // round edges t_0..t_4 and t_cap
 // per query: RESCORE_NUM_THR float edges, then RESCORE_NUM_THR int32 counts (short-list entries below each edge:
-// the list is ordered by bin, so round r is the range [count[r-1], count[r]))
-constexpr int RESCORE_THR_STRIDE = 2 * RESCORE_NUM_THR;
+// the list is ordered by bin, so round r is the range [count[r-1], count[r])), then the head: its last bin (int32, -1 = no
+// head) and its end position = the number of records stored
+constexpr int RESCORE_THR_HEAD_BIN = 2 * RESCORE_NUM_THR, RESCORE_THR_HEAD_END = 2 * RESCORE_NUM_THR + 1;
+constexpr int RESCORE_THR_STRIDE = 16;       // 64 bytes per query
+static_assert(RESCORE_THR_HEAD_END < RESCORE_THR_STRIDE, "layout");
 // the re-scoring kernels' bookkeeping (profiling only): RESCORE_STAT_COPIES blocks of RESCORE_STAT_WORDS u64 counters; a query
 // adds to block (query index % copies) -- one shared block made 8192 waves queue up on a single cache line of atomics (measured:
 // +0.15-0.23 ms on a 3.4 ms step); the host sums the blocks
-constexpr int RESCORE_STAT_WORDS = 16, RESCORE_STAT_COPIES = 64;
+constexpr int RESCORE_STAT_WORDS = 24, RESCORE_STAT_COPIES = 64;
 struct WindowPreview;
 struct RescoreEntry {
   float lb;      // filter bound
@@ -117,11 +144,15 @@ struct RescoreEntry {
 // histogram-bin edge with at most RESCORE_SHORTLIST_CAP bounds below it (+inf when all fit, -inf
 // when not even the first bin fits), and the round edges (first_target << r bounds, r = 0..4)
 // first_target: bounds in round 0; round r covers first_target << r
+// slist receives the records of the head only (positions [0, head end), ordered by bin); sl_cnt, the edges and their
+// counts describe the WHOLE list
 int launch_select(const DbView &db, const lb_t *lb, int64_t ld_lb, int64_t n_items, int32_t nq, int64_t n_eligible,
                   const int64_t *q_elig, int32_t first_target, RescoreEntry *slist, int32_t *sl_cnt, float *thr,
                   hipStream_t s);
 // one wave per query: list positions of rounds [round_begin, round_end) of ascending bound with tau tightening
 // (round_end = RESCORE_ALL_ROUNDS: also the entries beyond the short list); writes the top-k it knows.
+// List positions behind the head launch_select stored are taken from the row of bounds lb (bin by bin, ascending slot
+// inside a bin), so lb, ld_lb, n_items, n_eligible and q_elig must be the ones launch_select got.
 // win: the window records of launch_window for the same short lists (the head of every list);
 // tau_src (optional): a top-k that covers more than this shard -- its k-th distance caps tau;
 // seed (optional): this shard's hits from an earlier stage, merged into the output.

@@ -891,13 +891,13 @@ __global__ __launch_bounds__(1024) void sc_knn_kernel(const float *__restrict__ 
 struct RescoreArgs {
   DbView db;
   QueryView q;
-  const lb_t *lb;  // filter bounds [nq][ld_lb] (only read past the short list)
+  const lb_t *lb;  // filter bounds [nq][ld_lb] (read for what lies behind the head of the short list, and past the list)
   int64_t ld_lb, n_items, n_eligible;
   const int64_t *q_elig;
-  const RescoreEntry *slist;  // [nq][RESCORE_SHORTLIST_CAP]
-  const int32_t *sl_cnt;      // [nq]
+  const RescoreEntry *slist;  // [nq][RESCORE_SHORTLIST_CAP]: the records of the head of each list
+  const int32_t *sl_cnt;      // [nq]: length of the whole list
   const float *thr;           // [nq][RESCORE_THR_STRIDE]: round edges t_0 <= t_1 <= ... (the last one is t_cap), then the
-                              // number of short-list entries below each edge as int32
+                              // number of short-list entries below each edge as int32, then the head's last bin and end
   rsx_sc_hit *out;            // [nq][k]
   const rsx_sc_hit *tau_src;  // optional [nq][k]: a top-k over MORE than this shard (its k-th distance bounds tau)
   const rsx_sc_hit *seed;     // optional [nq][k]: hits this shard already found in an earlier stage
@@ -905,7 +905,7 @@ struct RescoreArgs {
   int32_t k;
   int32_t round_begin, round_end;  // rounds [begin, end) of the short list; end > RESCORE_NUM_THR: also the rest
   unsigned long long *stats;       // optional (bench instrumentation): [0] += candidates looked at, [1] += queries that scored
-                                   // any, [2] += exact window evaluations (phase B)
+                                   // any, [2] += exact window evaluations (phase B), [15] += those of list positions behind the head, [16] += queries that walked behind the head
   const WindowPreview *win;        // [nq][WINDOW_P] records of sc_window.hip; stats[3] += records used, stats[11] += exact alignments
 };
 
@@ -1043,11 +1043,6 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
   return RSX_OK;
 }
 
-__device__ __forceinline__ float bound_bin_lo(float lb) {  // lower edge of the 2048-bin histogram bin of lb
-  if (!(lb > 0.0f)) return -INFINITY;
-  const float x = lb * 2048.0f;
-  return x >= 2047.0f ? 2047.0f / 2048.0f : floorf(x) / 2048.0f;
-}
 
 // ------------------------------------------------------------------------------------------
 // sc_rescore_wave_kernel: exact re-scoring behind the filter AND the window kernel (sc_window.hip), ONE WAVE per
@@ -1108,8 +1103,9 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
   };
   double tau = kth_of(ld);
   bool query_loaded = false;
-  unsigned n_exact = 0, n_looked = 0, n_aligned = 0, n_shifts = 0;  // wave-uniform counters (stats)
+  unsigned n_exact = 0, n_looked = 0, n_aligned = 0, n_shifts = 0, n_tail = 0;  // wave-uniform counters (stats)
   unsigned nl_lane = 0, n_windowed = 0;               // per-lane counters, summed over the wave at the end
+  bool walked_tail = false;
 
   // score one entry exactly (ks < 0: the alignment is not known yet)
   // region cycles for RSX_RESCORE_PROF (experiments builds): [4] query load, [5] records + tau_ub, [6] picking the next
@@ -1342,8 +1338,11 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
   }
 
   // ---- the rest of this launch's list range, ascending bin order: no preview, exact alignment + phase B ----
-  for (int base = pos_next; base < i1 && !done; base += 64) {
-    const int n_here = (i1 - base < 64) ? (i1 - base) : 64;
+  // positions below head_end are records, the ones behind them are found in the row of bounds
+  const int head_bin = rcnt[RESCORE_THR_HEAD_BIN - RESCORE_NUM_THR], head_end = rcnt[RESCORE_THR_HEAD_END - RESCORE_NUM_THR];
+  const int i1h = i1 < head_end ? i1 : head_end;
+  for (int base = pos_next; base < i1h && !done; base += 64) {
+    const int n_here = (i1h - base < 64) ? (i1h - base) : 64;
     RescoreEntry mine;
     mine.lb = INFINITY;
     mine.slot = 0;
@@ -1351,7 +1350,7 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
     for (int i = 0; i < n_here; i++) {
       const float lb = __shfl(mine.lb, i);
       const int32_t slot = __shfl(mine.slot, i);
-      if ((double)bound_bin_lo(lb) - a.eps > tau) {  // every later entry sits in this bin or a higher one
+      if ((double)lb_bin_lo(lb_bin(lb)) - a.eps > tau) {  // every later entry sits in this bin or a higher one
         done = true;
         break;
       }
@@ -1362,6 +1361,66 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       load_entry(a.db, slot, lane, er);
       n_looked++;
       eval(slot, -1, er);
+    }
+  }
+
+  // ---- list positions behind the head: the bins above head_bin (and above the bins of the rounds before this launch) up
+  // to the bin of this launch's last edge, one pass over the eligible part of the row per non-empty bin, ascending slot order
+  // inside a bin (the records had "any" order there).  A pass also finds the next non-empty bin.  Same stop as above: the
+  // first bin whose lower edge tau excludes.  Few queries get here (the head holds >= RESCORE_HEAD positions), so a plain scan
+  if (!done && i1 > head_end) {
+    const lb_t *row = a.lb + (int64_t)qi * a.ld_lb;
+    const int b_to = lb_edge_bin(thr[r_end - 1]);
+    int b = head_bin;  // bins <= b are done (or belong to an earlier launch)
+    if (a.round_begin > 0) {
+      const int b0 = lb_edge_bin(thr[(a.round_begin < RESCORE_NUM_THR ? a.round_begin : RESCORE_NUM_THR) - 1]);
+      b = b0 > b ? b0 : b;
+    }
+    bool take = false;  // the first pass only looks for the first non-empty bin above b
+    walked_tail = b < b_to;
+    while (!done && walked_tail) {  // (b == b_to at the start: the rounds of this launch hold nothing behind the head)
+      int next = RESCORE_BINS;
+      constexpr int U = 4;  // loads in flight per lane
+      for (int64_t pos = 0; pos < n_rows && !done; pos += 64 * U) {
+        float d[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const int64_t i = pos + 64 * u + lane;
+          d[u] = (i < n_rows) ? (float)row[i] : INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const int bin = (d[u] != INFINITY) ? lb_bin(d[u]) : RESCORE_BINS;  // +inf: never a hit, in no bin
+          if (bin > b && bin < next) next = bin;
+          unsigned long long bal = __ballot(take && bin == b);
+          while (bal && !done) {
+            const int l = __ffsll((long long)bal) - 1;
+            bal &= bal - 1;
+            if ((double)lb_bin_lo(b) - a.eps > tau) {  // every later entry sits in this bin or a higher one
+              done = true;
+              break;
+            }
+            const float dl = __shfl(d[u], l);
+            if ((double)dl - a.eps > tau) continue;  // (NaN / -inf bounds: always scored)
+            const int64_t slot = pos + 64 * u + l;
+            EntryRegs er;
+            load_entry(a.db, slot, lane, er);
+            n_looked++;
+            n_tail++;
+            eval(slot, -1, er);
+          }
+        }
+      }
+      if (done) break;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const int o = __shfl_xor(next, off);
+        next = o < next ? o : next;
+      }
+      if (next > b_to) break;  // (RESCORE_BINS: nothing above b)
+      b = next;
+      take = true;
+      if ((double)lb_bin_lo(b) - a.eps > tau) done = true;
     }
   }
 
@@ -1409,6 +1468,8 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       atomicAdd(a.stats + 2, (unsigned long long)n_exact);
       atomicAdd(a.stats + 11, (unsigned long long)n_aligned);
       atomicAdd(a.stats + 12, (unsigned long long)n_shifts);
+      atomicAdd(a.stats + 15, (unsigned long long)n_tail);
+      if (walked_tail) atomicAdd(a.stats + 16, 1ull);
       if (timing) {
         for (int i = 0; i < 6; i++) atomicAdd(a.stats + 4 + i, (unsigned long long)tacc[i]);
         atomicAdd(a.stats + 13, (unsigned long long)tacc[7]);

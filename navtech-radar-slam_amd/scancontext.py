@@ -323,6 +323,16 @@ class SCManager:
         check(self._L.rsx_sc_profile_read_rescoring(self._h, C.byref(st)))
         return (st.candidates, st.exact_evals, st.queries_rescored, st.window_previews, st.valu_previews, st.exact_window_shifts)
 
+    def profile_read_rescoring_tail(self):
+        """profile_read_rescoring() with the two counters of the walk behind the stored head of a short list appended: exact
+        evaluations of list positions found in the row of bounds, and queries whose walk went there."""
+        from ._rsx import RescoringStats, RescoringStatsTail
+        st = RescoringStatsTail()
+        st.struct_size = C.sizeof(RescoringStatsTail)
+        check(self._L.rsx_sc_profile_read_rescoring(self._h, C.cast(C.byref(st), C.POINTER(RescoringStats))))
+        return (st.candidates, st.exact_evals, st.queries_rescored, st.window_previews, st.valu_previews, st.exact_window_shifts,
+                st.tail_evals, st.tail_queries)
+
     def hit_to_loop(self, hit):
         h = np.zeros(1, dtype=HIT_DTYPE)
         h[0] = hit
