@@ -401,7 +401,8 @@ int rsx_orora_register_batch_device(rsx_orora *h, const float *d_src_xy, const f
  * The two other motion estimators of the upstream file-based `odometry.cpp` entry (yeti_radar_odometry's Ransac and
  * MotionDistortedRansac; Burnett et al. 2021 for the latter), beside ORORA.  Their sources are absent from the reference
  * checkout (empty submodule), so these entries follow the published methods as restated in tests/ransac_np.py, which is the
- * arithmetic contract -- parity unpinned.  2-D; no Doppler term; conventions of rsx_orora_register_batch (dst = R src + t).
+ * arithmetic contract -- parity unpinned.  2-D; no Doppler term inside the estimators (rsx_mocomp below corrects keypoints for
+ * it); conventions of rsx_orora_register_batch (dst = R src + t).
  * Rigid mode: H two-match hypotheses, closed-form rigid fit, refit over the winner's inliers.  Motion-compensated mode:
  * every match carries dt = (time src was measured) - (time dst was measured) [s] and dst = exp(dt w) src for a constant
  * body velocity w = (vx, vy, wz); hypotheses and refit by Gauss-Newton.  The sampler is counter based: a pair's result
@@ -446,6 +447,65 @@ int rsx_ransac_estimate_batch(rsx_ransac *h, const float *src_xy, const float *d
 int rsx_ransac_estimate_batch_device(rsx_ransac *h, const float *d_src_xy, const float *d_dst_xy, const float *d_dt,
                                      const int64_t *d_offsets, int32_t n_pairs, const rsx_ransac_params *params,
                                      rsx_ransac_result *d_out, uint8_t *d_out_inlier, void *stream);
+
+/* ============================== motion and Doppler compensation of keypoints ============
+ * The deskewing and Doppler switches of the upstream odometry (ORORA's options, yeti_radar_odometry's --doppler
+ * configuration).  Their sources are absent from the reference checkout (empty submodule), so these entries follow the model
+ * below as restated in tests/mocomp_np.py, which is the arithmetic contract -- parity unpinned.
+ *   Time    the keypoint on azimuth row a was measured tau = (a + 0.5) / rows * dt_scan after its scan's start; scans
+ *           start dt_scan apart (the model of rsx_odometry_set_estimator).
+ *   Doppler (RSX_MOCOMP_DOPPLER, applied first) the measured range r = |p| becomes r + beta (vx x / r + vy y / r) at
+ *           the measured bearing; a point with r = 0 stays.  beta [s] is signed; 0.049 is the value recalled from yeti for
+ *           the Navtech CIR204-H.  Neither the value nor the SIGN CONVENTION could be checked against hardware or against
+ *           upstream here: a sensor whose ranges shorten while it approaches a target has beta > 0 in this convention.
+ *   Deskew  (RSX_MOCOMP_DESKEW) the sensor moves at a constant body velocity w = (vx, vy, wz); the point measured at tau
+ *           is expressed in the sensor frame at the scan's start: p0 = exp(tau w) p = R(th) p + V(th) (vx, vy) tau,
+ *           th = wz tau, V = [[A, -B], [B, A]], A = sin th / th, B = (1 - cos th) / th (the convention of rsx_ransac:
+ *           dst = exp(dt w) src).
+ * sin, cos, A and B are fixed polynomials in th (csrc/mocomp.hip proves their truncation error below 2^-53 relative for
+ * |th| <= 0.5), evaluated in fp64 in a fixed order without fused multiply-adds; no transcendental function is called, so
+ * the fp32 outputs are reproducible bit for bit.  A point with |th| > 0.5 (or a th that is not finite) is left as measured
+ * -- no Doppler correction either -- and sets RSX_MOCOMP_STATUS_ANGLE in its scan's / pair's status word.
+ * A handle owns a stream and the staging of the host-buffer entries; the device entries never allocate or synchronise. */
+
+typedef struct rsx_mocomp rsx_mocomp;
+
+typedef struct {
+  double dt_scan;   /* duration of one revolution [s] (0.25: a Navtech head at 4 Hz); positive */
+  double beta;      /* Doppler range shift per unit of radial velocity [s] (0.049); signed, finite */
+  int32_t rows;     /* azimuth rows per scan (400); positive */
+  int32_t flags;    /* RSX_MOCOMP_DESKEW | RSX_MOCOMP_DOPPLER: at least one, nothing else */
+  int32_t reserved[2]; /* 0 */
+} rsx_mocomp_params;
+#define RSX_MOCOMP_DESKEW 1
+#define RSX_MOCOMP_DOPPLER 2
+#define RSX_MOCOMP_STATUS_ANGLE 1 /* status word: some point had |wz tau| > 0.5, or (matches) the pair's pose has |yaw| > 0.5 or is
+                                     not finite: those points / that pair were left as measured */
+
+int rsx_mocomp_default_params(rsx_mocomp_params *p);
+int rsx_mocomp_create(int device, rsx_mocomp **out);
+int rsx_mocomp_destroy(rsx_mocomp *h);
+/* n_scans clouds in the offsets layout of rsx_orora_register_batch: scan i owns points [offsets[i], offsets[i+1]) of xy
+ * (float x, y per point) and of rows (the azimuth row of each point); w [n_scans][3] doubles: (vx, vy, wz) of each scan.
+ * out_xy: the compensated points, laid out like xy, a buffer of its own; out_status [n_scans] (optional): 0 or
+ * RSX_MOCOMP_STATUS_ANGLE.  params = NULL: rsx_mocomp_default_params (both corrections).  Host buffers, synchronous. */
+int rsx_mocomp_points_batch(rsx_mocomp *h, const float *xy, const int32_t *rows, const int64_t *offsets, int32_t n_scans, const double *w,
+                            const rsx_mocomp_params *params, float *out_xy, int32_t *out_status);
+/* device buffers, asynchronous on `stream`; never allocates or synchronises */
+int rsx_mocomp_points_batch_device(rsx_mocomp *h, const float *d_xy, const int32_t *d_rows, const int64_t *d_offsets, int32_t n_scans,
+                                   const double *d_w, const rsx_mocomp_params *params, float *d_out_xy, int32_t *d_out_status, void *stream);
+/* The matches of n_pairs scan pairs as staged for rsx_orora_register_batch (src = the later scan's points, dst = the earlier
+ * scan's), a_cur / a_prev: the azimuth rows of src / dst, pose [n_pairs][3] doubles: (x, y, yaw) of each pair in the
+ * rsx_orora_result convention (dst = R(yaw) src + (x, y)).  The kernel derives the pair's velocity w = log(pose) / dt_scan
+ * (the polynomials again and one division; |yaw| <= 0.5) and writes both sides compensated with it, each into the start frame
+ * of its own scan: out_src = exp(tau_cur w) src, out_dst = exp(tau_prev w) dst, so that out_dst = exp(dt_scan w) out_src for a
+ * static point.  out_status [n_pairs] (optional).  Host buffers, synchronous. */
+int rsx_mocomp_matches_batch(rsx_mocomp *h, const float *src_xy, const float *dst_xy, const int32_t *a_cur, const int32_t *a_prev,
+                             const int64_t *offsets, int32_t n_pairs, const double *pose, const rsx_mocomp_params *params, float *out_src_xy,
+                             float *out_dst_xy, int32_t *out_status);
+int rsx_mocomp_matches_batch_device(rsx_mocomp *h, const float *d_src_xy, const float *d_dst_xy, const int32_t *d_a_cur, const int32_t *d_a_prev,
+                                    const int64_t *d_offsets, int32_t n_pairs, const double *d_pose, const rsx_mocomp_params *params,
+                                    float *d_out_src_xy, float *d_out_dst_xy, int32_t *d_out_status, void *stream);
 
 /* ============================== cen2019 keypoint extraction ============================
  * Replaces the feature-extraction stage of the upstream file-based `odometry.cpp` entry
@@ -636,6 +696,19 @@ int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params);
 #define RSX_ESTIMATOR_RANSAC 1
 #define RSX_ESTIMATOR_MCRANSAC 2
 int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_params *params);
+/* Motion and Doppler compensation of the keypoints (rsx_mocomp above; params->flags picks the corrections, params->rows is
+ * ignored: the handle's rows count).  NULL switches it off, which is the default.  Accepted only while the handle holds no
+ * scan, with RSX_ESTIMATOR_ORORA and RSX_ESTIMATOR_RANSAC; RSX_ERR_BAD_ARG with RSX_ESTIMATOR_MCRANSAC, which has its own
+ * motion model (and rsx_odometry_set_estimator refuses MC-RANSAC while compensation is on).  With it a pair is estimated,
+ * compensated with its own estimate and estimated again, all pairs of a window in one batch each time: pass 1 as without
+ * compensation; the matches of every pair are then compensated with the velocity log(pose) / dt_scan of the pose pass 1 gave
+ * that pair; the same estimator (max-clique selection and solver, or RANSAC) runs once more on the compensated matches, and
+ * rsx_odometry_scan.reg is that second result.  A pair whose first pass has status != 0 is not compensated and keeps its
+ * first result; so does, in effect, a pair with |yaw| > 0.5 (RSX_MOCOMP_STATUS_ANGLE: its matches stay as measured).  One
+ * round only.  out_xy carries scan i's keypoints compensated with the velocity of the pair (i-1, i) (the second result;
+ * uncompensated when that pair's status != 0 and for the first scan of a sequence); what is matched and carried to the next
+ * window stays uncompensated.  Results do not depend on how the sequence is cut into calls. */
+int rsx_odometry_set_compensation(rsx_odometry *h, const rsx_mocomp_params *params);
 /* n_scans consecutive scans, host images image_stride_bytes apart (rows x row_stride bytes each); azimuths: rows floats
  * (rad, increasing) shared by all scans or n_scans x rows when azimuths_per_image != 0.  out [n_scans]; out_xy
  * (optional) [n_scans][max_xy][2]: the scan's keypoints in metres in the sensor frame (/orora/cloud_local).  Synchronous. */

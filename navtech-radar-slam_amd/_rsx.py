@@ -123,6 +123,14 @@ RANSAC_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("vx
                                 ("hypotheses", "<i4"), ("gn_iterations", "<i4"), ("status", "<i4")])
 
 
+class MocompParams(C.Structure):
+    _fields_ = [("dt_scan", C.c_double), ("beta", C.c_double), ("rows", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+MOCOMP_DESKEW, MOCOMP_DOPPLER = 1, 2  # rsx_mocomp_params.flags
+MOCOMP_STATUS_ANGLE = 1
+
+
 class OdometryParams(C.Structure):
     _fields_ = [("cen", Cen2019Params), ("frontend", FrontendParams), ("orora", OroraParams), ("radar_resolution", C.c_float),
                 ("col_offset", C.c_int32), ("max_keypoints", C.c_int32), ("device", C.c_int32)]
@@ -164,7 +172,9 @@ SYMBOLS = [
     "rsx_cen2019_extract_batch", "rsx_cen2019_extract_batch_device",
     "rsx_cen2018_default_params", "rsx_cen2018_create", "rsx_cen2018_destroy", "rsx_cen2018_extract",
     "rsx_cen2018_extract_batch", "rsx_cen2018_extract_batch_device", "rsx_cen2018_gauss_weights", "rsx_cen2018_debug_image",
-    "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator",
+    "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
+    "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
+    "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
     "rsx_ransac_default_params", "rsx_ransac_create", "rsx_ransac_destroy", "rsx_ransac_estimate_batch", "rsx_ransac_estimate_batch_device",
     "rsx_frontend_default_params", "rsx_frontend_create", "rsx_frontend_destroy", "rsx_frontend_cartesian",
     "rsx_frontend_describe", "rsx_frontend_match",
@@ -287,6 +297,14 @@ def lib():
         L.rsx_cen2018_debug_image.argtypes = [vp, vp, i32, i32, C.POINTER(Cen2018Params), vp, vp, vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
+        L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]
+        L.rsx_mocomp_default_params.argtypes = [C.POINTER(MocompParams)]
+        L.rsx_mocomp_create.argtypes = [C.c_int, C.POINTER(vp)]
+        L.rsx_mocomp_destroy.argtypes = [vp]
+        L.rsx_mocomp_points_batch.argtypes = [vp, vp, vp, vp, i32, vp, C.POINTER(MocompParams), vp, vp]
+        L.rsx_mocomp_points_batch_device.argtypes = [vp, vp, vp, vp, i32, vp, C.POINTER(MocompParams), vp, vp, vp]
+        L.rsx_mocomp_matches_batch.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(MocompParams), vp, vp, vp]
+        L.rsx_mocomp_matches_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(MocompParams), vp, vp, vp, vp]
         L.rsx_ransac_default_params.argtypes = [C.POINTER(RansacParams)]
         L.rsx_ransac_create.argtypes = [C.c_int, C.POINTER(vp)]
         L.rsx_ransac_destroy.argtypes = [vp]

@@ -15,6 +15,9 @@
 //                                               selection (csrc/pmc.hip, RSX_ORORA_PMC: on by default here) + the solver
 //                                               (or rsx_ransac_estimate_batch_device, csrc/ransac.hip, after
 //                                               rsx_odometry_set_estimator: no selection; MC-RANSAC also gets a dt per match)
+//     (rsx_odometry_set_compensation only)      the matches of every pair compensated with the pose the estimator just gave that
+//                                               pair (csrc/mocomp.hip), the estimator once more on them, and the keypoints of
+//                                               every scan compensated with its pair's second pose for out_xy
 // -- with every intermediate (keypoints, descriptors, matches, correspondences) in HBM; one upload of the images and one
 // download of 48 bytes per scan (+ the keypoints when the caller wants /orora/cloud_local).  The last scan of a window
 // stays on the device as the "previous scan" of the next one.  Pose composition stays on the host (sequential, trivial).
@@ -27,6 +30,7 @@
 
 #include "cen2018.h"
 #include "keypoints_host.h"
+#include "mocomp.h"
 #include "ransac.h"
 
 namespace {
@@ -41,11 +45,13 @@ constexpr int MAX_WINDOW = RSX_ODO_WINDOW;  // scans per internal launch chain (
 // previous scan's point, so that ORORA returns the motion of the sensor expressed in the previous frame.
 // DT (motion-compensated RANSAC): also the time between the two measurements of a match, from the azimuth rows of its two
 // keypoints (targets [slot][stride][2], row first): dt = (float)(dt_scan (1 + (a_cur - a_prev) / rows)) -- include/rsx.h
-template <bool DT>
+// AZ (rsx_odometry_set_compensation): the two azimuth rows themselves, for csrc/mocomp.hip
+template <bool DT, bool AZ = false>
 __device__ __forceinline__ void cross_pair(const float *__restrict__ xy, const int32_t *__restrict__ counts, int stride, int first,
                                            const int32_t *__restrict__ fwd, const int32_t *__restrict__ bwd, float2 *__restrict__ stage_src,
                                            float2 *__restrict__ stage_dst, int32_t *__restrict__ pair_cnt, const int32_t *__restrict__ targets,
-                                           int rows, double dt_scan, float *__restrict__ stage_dt) {
+                                           int rows, double dt_scan, float *__restrict__ stage_dt, int32_t *__restrict__ stage_acur = nullptr,
+                                           int32_t *__restrict__ stage_aprev = nullptr) {
   __shared__ unsigned s_w[4];
   const int j = blockIdx.x, A = first + j, B = A + 1;
   const int nA = counts[A] < stride ? counts[A] : stride, nB = counts[B] < stride ? counts[B] : stride;
@@ -77,6 +83,10 @@ __device__ __forceinline__ void cross_pair(const float *__restrict__ xy, const i
         const int a_prev = targets[((int64_t)A * stride + i) * 2], a_cur = targets[((int64_t)B * stride + k) * 2];
         stage_dt[(int64_t)j * stride + pos] = (float)(dt_scan * (1.0 + (double)(a_cur - a_prev) / (double)rows));
       }
+      if constexpr (AZ) {
+        stage_aprev[(int64_t)j * stride + pos] = targets[((int64_t)A * stride + i) * 2];
+        stage_acur[(int64_t)j * stride + pos] = targets[((int64_t)B * stride + k) * 2];
+      }
     }
     run += total;
     __syncthreads();
@@ -95,6 +105,14 @@ __global__ __launch_bounds__(256) void odo_cross_dt(const float *__restrict__ xy
                                                     float2 *__restrict__ stage_src, float2 *__restrict__ stage_dst, int32_t *__restrict__ pair_cnt,
                                                     const int32_t *__restrict__ targets, int rows, double dt_scan, float *__restrict__ stage_dt) {
   cross_pair<true>(xy, counts, stride, first, fwd, bwd, stage_src, stage_dst, pair_cnt, targets, rows, dt_scan, stage_dt);
+}
+
+__global__ __launch_bounds__(256) void odo_cross_az(const float *__restrict__ xy, const int32_t *__restrict__ counts, int stride, int first,
+                                                    const int32_t *__restrict__ fwd, const int32_t *__restrict__ bwd,
+                                                    float2 *__restrict__ stage_src, float2 *__restrict__ stage_dst, int32_t *__restrict__ pair_cnt,
+                                                    const int32_t *__restrict__ targets, int32_t *__restrict__ stage_acur,
+                                                    int32_t *__restrict__ stage_aprev) {
+  cross_pair<false, true>(xy, counts, stride, first, fwd, bwd, stage_src, stage_dst, pair_cnt, targets, 0, 0.0, nullptr, stage_acur, stage_aprev);
 }
 
 // one block per pair: contiguous correspondence arrays + the offsets rsx_orora_register_batch_device wants
@@ -126,6 +144,26 @@ __global__ __launch_bounds__(256) void odo_gather_dt(const float *__restrict__ s
   const int j = blockIdx.x;
   const int64_t o = offsets[j], n = offsets[j + 1] - o;
   for (int64_t i = threadIdx.x; i < n; i += 256) dt[o + i] = stage_dt[(int64_t)j * stride + i];
+}
+
+// the same for the staged azimuth rows of both sides
+__global__ __launch_bounds__(256) void odo_gather_az(const int32_t *__restrict__ stage_acur, const int32_t *__restrict__ stage_aprev,
+                                                     const int64_t *__restrict__ offsets, int stride, int32_t *__restrict__ a_cur,
+                                                     int32_t *__restrict__ a_prev) {
+  const int j = blockIdx.x;
+  const int64_t o = offsets[j], n = offsets[j + 1] - o;
+  for (int64_t i = threadIdx.x; i < n; i += 256) {
+    a_cur[o + i] = stage_acur[(int64_t)j * stride + i];
+    a_prev[o + i] = stage_aprev[(int64_t)j * stride + i];
+  }
+}
+
+// compensation: a pair whose first pass has status != 0 keeps its first result
+__global__ __launch_bounds__(64) void odo_keep_first(const rsx_orora_result *__restrict__ pass1, int n_pairs, rsx_orora_result *__restrict__ pass2) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n_pairs) return;
+  const rsx_orora_result r = pass1[j];
+  if (r.status != 0) pass2[j] = r;
 }
 
 // a RANSAC estimator's results in the records rsx_odometry_scan carries (include/rsx.h, rsx_odometry_set_estimator)
@@ -179,6 +217,9 @@ struct rsx_odometry {
   rsx::Owned<rsx_ransac, rsx_ransac_destroy> ransac;  // created at the first rsx_odometry_set_estimator that asks for one
   rsx_ransac_params ransac_prm{};
   rsx::DevBuf ransac_res, stage_dt, dt;  // allocated only with a RANSAC estimator (stage_dt, dt: MC-RANSAC)
+  bool comp_on = false;  // rsx_odometry_set_compensation
+  rsx_mocomp_params comp_prm{};
+  rsx::DevBuf stage_acur, stage_aprev, a_cur, a_prev, src2, dst2, results2, xy_comp;  // allocated only with compensation
   OdoSet set[N_SETS];
   rsx::DevBuf imgs[N_SETS], fwd, bwd, stage_src, stage_dst, pair_cnt, src, dst, offsets, results;
   uint64_t windows = 0;  // windows enqueued since creation: window g works in set[g % N_SETS] on lane g & 1
@@ -217,6 +258,11 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
   if (h->estimator == RSX_ESTIMATOR_MCRANSAC) {
     RSX_TRY(h->stage_dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
     RSX_TRY(h->dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
+  }
+  if (h->comp_on) {
+    for (rsx::DevBuf *b : {&h->stage_acur, &h->stage_aprev, &h->a_cur, &h->a_prev}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 4, s, false));
+    for (rsx::DevBuf *b : {&h->src2, &h->dst2, &h->xy_comp}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 8, s, false));
+    RSX_TRY(h->results2.reserve((size_t)MAX_WINDOW * sizeof(rsx_orora_result), s, false));
   }
   return RSX_OK;
 }
@@ -257,7 +303,8 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   RSX_HIP(hipMemcpyAsync(nx.desc.p, q.desc.as<uint8_t>() + (size_t)n * K * 32, (size_t)K * 32, hipMemcpyDeviceToDevice, s));
   RSX_HIP(hipMemcpyAsync(nx.valid.p, q.valid.as<uint8_t>() + (size_t)n * K, (size_t)K, hipMemcpyDeviceToDevice, s));
   RSX_HIP(hipMemcpyAsync(nx.counts.p, d_counts + n, 4, hipMemcpyDeviceToDevice, s));
-  if (h->estimator == RSX_ESTIMATOR_MCRANSAC)  // the azimuth rows of the previous scan's keypoints: the dt of the straddling pair
+  if (h->estimator == RSX_ESTIMATOR_MCRANSAC || h->comp_on)  // the azimuth rows of the previous scan's keypoints: the dt (the
+                                                              // compensation) of the straddling pair
     RSX_HIP(hipMemcpyAsync(nx.targets.p, q.targets.as<int32_t>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
   RSX_HIP(hipEventRecord(h->ev_e[g % N_SETS], s));
   return RSX_OK;
@@ -265,7 +312,7 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
 
 // M(g): the consecutive pairs of window g (with the previous scan in slot 0 when there is one) matched, selected and solved,
 // the results on their way to the set's pinned area.  Asynchronous on the matching stream.  *first_out: 0 when slot 0 takes part.
-int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out) {
+int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_xy) {
   hipStream_t s = h->match_stream;
   OdoSet &q = h->set[g % N_SETS];
   const int K = h->prm.max_keypoints;
@@ -278,7 +325,11 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out) {
     RSX_TRY(rsx_frontend_match_consecutive_device(h->fe[g & 1].get(), q.desc.as<uint8_t>(), q.valid.as<uint8_t>(), d_counts, K, first, n_pairs,
                                                   h->prm.frontend.ratio, h->fwd.as<int32_t>(), h->bwd.as<int32_t>(), s));
     const bool mc = h->estimator == RSX_ESTIMATOR_MCRANSAC;
-    if (mc)
+    if (h->comp_on)
+      hipLaunchKernelGGL(odo_cross_az, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
+                         h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>(),
+                         q.targets.as<int32_t>(), h->stage_acur.as<int32_t>(), h->stage_aprev.as<int32_t>());
+    else if (mc)
       hipLaunchKernelGGL(odo_cross_dt, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
                          h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>(),
                          q.targets.as<int32_t>(), h->rows, h->ransac_prm.dt_scan, h->stage_dt.as<float>());
@@ -289,23 +340,39 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out) {
                        h->pair_cnt.as<int32_t>(), n_pairs, K, h->src.as<float2>(), h->dst.as<float2>(), h->offsets.as<int64_t>());
     if (mc)
       hipLaunchKernelGGL(odo_gather_dt, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_dt.as<float>(), h->offsets.as<int64_t>(), K, h->dt.as<float>());
+    if (h->comp_on)
+      hipLaunchKernelGGL(odo_gather_az, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_acur.as<int32_t>(), h->stage_aprev.as<int32_t>(),
+                         h->offsets.as<int64_t>(), K, h->a_cur.as<int32_t>(), h->a_prev.as<int32_t>());
     RSX_HIP(hipGetLastError());
-    if (h->estimator == RSX_ESTIMATOR_ORORA) {
-      RSX_TRY(rsx_orora_register_batch_device(h->reg.get(), h->src.as<float>(), h->dst.as<float>(), h->offsets.as<int64_t>(), n_pairs, &h->prm.orora,
-                                              h->results.as<rsx_orora_result>(), s));
-    } else {
-      RSX_TRY(rsx_ransac_estimate_batch_device(h->ransac.get(), h->src.as<float>(), h->dst.as<float>(), mc ? h->dt.as<float>() : nullptr,
-                                               h->offsets.as<int64_t>(), n_pairs, &h->ransac_prm, h->ransac_res.as<rsx_ransac_result>(), nullptr, s));
-      hipLaunchKernelGGL(odo_ransac_results, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->ransac_res.as<rsx_ransac_result>(), n_pairs,
-                         h->results.as<rsx_orora_result>());
+    auto estimate = [&](const float *d_src, const float *d_dst, rsx_orora_result *d_res) -> int {
+      if (h->estimator == RSX_ESTIMATOR_ORORA)
+        return rsx_orora_register_batch_device(h->reg.get(), d_src, d_dst, h->offsets.as<int64_t>(), n_pairs, &h->prm.orora, d_res, s);
+      RSX_TRY(rsx_ransac_estimate_batch_device(h->ransac.get(), d_src, d_dst, mc ? h->dt.as<float>() : nullptr, h->offsets.as<int64_t>(), n_pairs,
+                                               &h->ransac_prm, h->ransac_res.as<rsx_ransac_result>(), nullptr, s));
+      hipLaunchKernelGGL(odo_ransac_results, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->ransac_res.as<rsx_ransac_result>(), n_pairs, d_res);
+      RSX_HIP(hipGetLastError());
+      return RSX_OK;
+    };
+    RSX_TRY(estimate(h->src.as<float>(), h->dst.as<float>(), h->results.as<rsx_orora_result>()));
+    if (h->comp_on) {  // estimated, compensated with its own estimate, estimated again: every pair of the window in each launch
+      RSX_TRY(rsx::mocomp::launch_matches(h->src.as<float>(), h->dst.as<float>(), h->a_cur.as<int32_t>(), h->a_prev.as<int32_t>(),
+                                          h->offsets.as<int64_t>(), n_pairs, h->results.p, sizeof(rsx_orora_result), offsetof(rsx_orora_result, status),
+                                          h->comp_prm, h->src2.as<float>(), h->dst2.as<float>(), nullptr, s));
+      RSX_TRY(estimate(h->src2.as<float>(), h->dst2.as<float>(), h->results2.as<rsx_orora_result>()));
+      hipLaunchKernelGGL(odo_keep_first, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->results.as<rsx_orora_result>(), n_pairs,
+                         h->results2.as<rsx_orora_result>());
       RSX_HIP(hipGetLastError());
     }
   }
+  const rsx::DevBuf &res = h->comp_on ? h->results2 : h->results;
+  if (h->comp_on && want_xy)  // /orora/cloud_local: scan i under the velocity of the pair (i - 1, i); the first scan of a sequence as measured
+    RSX_TRY(rsx::mocomp::launch_slots(q.xy.as<float>() + (size_t)K * 2, q.targets.as<int32_t>() + (size_t)K * 2, d_counts + 1, K, n, first, res.p,
+                                      sizeof(rsx_orora_result), offsetof(rsx_orora_result, status), h->comp_prm, h->xy_comp.as<float>(), s));
   char *pin = static_cast<char *>(q.pin.p);
   RSX_HIP(hipMemcpyAsync(pin + PIN_COUNTS, d_counts, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, s));
   if (n_pairs > 0) {
     RSX_HIP(hipMemcpyAsync(pin + PIN_PAIRS, h->pair_cnt.p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, s));
-    RSX_HIP(hipMemcpyAsync(pin + PIN_RES, h->results.p, (size_t)n_pairs * sizeof(rsx_orora_result), hipMemcpyDeviceToHost, s));
+    RSX_HIP(hipMemcpyAsync(pin + PIN_RES, res.p, (size_t)n_pairs * sizeof(rsx_orora_result), hipMemcpyDeviceToHost, s));
   }
   RSX_HIP(hipEventRecord(h->ev_m[g % N_SETS], s));
   h->have_prev = true;
@@ -338,7 +405,9 @@ int finish_window(rsx_odometry *h, uint64_t g, int n, int first, rsx_odometry_sc
     for (int i = 0; i < n; i++) {
       const int c = hc[1 + i] < K ? hc[1 + i] : K, wn = c < max_xy ? c : max_xy;
       if (wn > 0)
-        RSX_HIP(hipMemcpyAsync(out_xy + (size_t)i * max_xy * 2, q.xy.as<float>() + (size_t)(1 + i) * slot_xy, (size_t)wn * 8, hipMemcpyDeviceToHost, s));
+        RSX_HIP(hipMemcpyAsync(out_xy + (size_t)i * max_xy * 2,
+                               h->comp_on ? h->xy_comp.as<float>() + (size_t)i * slot_xy : q.xy.as<float>() + (size_t)(1 + i) * slot_xy,
+                               (size_t)wn * 8, hipMemcpyDeviceToHost, s));
     }
     RSX_HIP(hipStreamSynchronize(s));
   }
@@ -389,7 +458,7 @@ int push_windows(rsx_odometry *h, int32_t n_scans, rsx_odometry_scan *out, float
     const uint64_t g = h->windows + (uint64_t)w;
     const int b0 = w * MAX_WINDOW, n = n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW;
     int first = 0;
-    st = enqueue_match(h, g, n, &first);
+    st = enqueue_match(h, g, n, &first, out_xy && max_xy > 0);
     if (st == RSX_OK && w + 2 < nwin) st = extract(w + 2, g + 2);
     if (st == RSX_OK) st = finish_window(h, g, n, first, out + b0, out_xy ? out_xy + (size_t)b0 * max_xy * 2 : nullptr, max_xy);
   }
@@ -505,6 +574,8 @@ int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_
     return fail(RSX_ERR_BAD_ARG, "unknown estimator %d", estimator);
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
+  if (estimator == RSX_ESTIMATOR_MCRANSAC && h->comp_on)
+    return fail(RSX_ERR_BAD_ARG, "compensation is on: motion-compensated RANSAC has its own motion model (rsx_odometry_set_compensation(h, NULL) first)");
   if (estimator == RSX_ESTIMATOR_ORORA) {
     h->estimator = estimator;
     return RSX_OK;
@@ -522,6 +593,23 @@ int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_
   }
   h->ransac_prm = p;
   h->estimator = estimator;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_odometry_set_compensation(rsx_odometry *h, const rsx_mocomp_params *params) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one model)");
+  if (!params) {
+    h->comp_on = false;
+    return RSX_OK;
+  }
+  if (h->estimator == RSX_ESTIMATOR_MCRANSAC) return fail(RSX_ERR_BAD_ARG, "motion-compensated RANSAC has its own motion model");
+  rsx_mocomp_params p = *params;
+  p.rows = h->rows;
+  RSX_TRY(rsx::mocomp::check_params(p));
+  h->comp_prm = p;
+  h->comp_on = true;
   return RSX_OK;
 } RSX_CATCH_ALL
 

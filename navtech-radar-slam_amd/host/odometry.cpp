@@ -25,6 +25,10 @@
 // `--estimator ransac|mcransac` (with `--ransac-threshold`, `--ransac-iterations`, `--scan-period`) hands a pair's matches to
 // rigid RANSAC or motion-compensated RANSAC instead of the max-clique selection + ORORA (upstream's other estimators:
 // rsx_odometry_set_estimator, windowed path only; mcransac takes a match's time from the azimuth rows of its keypoints).
+// `--compensate motion|doppler|both` (with `--doppler-beta`, `--scan-period`) corrects the keypoints for the sensor's motion
+// during the scan and / or the Doppler range shift: every pair is estimated, its matches compensated with that estimate and
+// estimated again, and the published cloud is the compensated one (upstream's deskewing / Doppler switches:
+// rsx_odometry_set_compensation, windowed path only, with orora and ransac).
 //
 // Output: one line per frame on stdout / --out file:  stamp_ns x y yaw n_keypoints n_matches
 // With -DRSX_WITH_ROS (ROS 1 present) the same data is also published on /orora/odom and
@@ -138,6 +142,9 @@ int main(int argc, char **argv) {
     rsx_cen2018_default_params(&c18);
     rsx_ransac_params rsp;
     rsx_ransac_default_params(&rsp);
+    std::string compensate;
+    rsx_mocomp_params mcp;
+    rsx_mocomp_default_params(&mcp);
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       if (a == "--out" && i + 1 < argc) out_path = argv[++i];
@@ -154,6 +161,8 @@ int main(int argc, char **argv) {
       else if (a == "--ransac-threshold" && i + 1 < argc) rsp.tolerance = std::atof(argv[++i]);        // inlier residual bound [m] (0.35)
       else if (a == "--ransac-iterations" && i + 1 < argc) rsp.max_iterations = std::atoi(argv[++i]);  // hypotheses (100)
       else if (a == "--scan-period" && i + 1 < argc) rsp.dt_scan = std::atof(argv[++i]);               // mcransac: seconds per scan (0.25)
+      else if (a == "--compensate" && i + 1 < argc) compensate = argv[++i];       // motion | doppler | both (default: none)
+      else if (a == "--doppler-beta" && i + 1 < argc) mcp.beta = std::atof(argv[++i]);  // Doppler range shift per radial velocity [s] (0.049)
       else if (a == "--no-pmc") use_pmc = false;                                   // skip the max-clique inlier selection before the solver
       else if (a == "--exact-clique") exact_clique = true;                        // RSX_ORORA_PMC_EXACT: the selection returns a maximum clique
       else if (a == "--per-scan") per_scan = true;                                // the round-2 loop: one scan per call, host vectors in between
@@ -168,7 +177,8 @@ int main(int argc, char **argv) {
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018] [--zq Z] [--sigma-gauss S] [--window W] [--threads T] "
-          "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--per-scan] [--no-pmc] [--exact-clique] [--timing]");
+          "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
+          "[--exact-clique] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";
     std::vector<std::string> files;
@@ -263,6 +273,13 @@ int main(int argc, char **argv) {
     const bool use_c18 = keypoints == "cen2018";
     if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac") die("--estimator must be orora, ransac or mcransac");
     if (estimator != "orora" && (matcher != "orb" || per_scan)) die("--estimator " + estimator + " runs on the windowed path only (not with --per-scan / --matcher nn)");
+    if (!compensate.empty()) {
+      if (compensate != "motion" && compensate != "doppler" && compensate != "both") die("--compensate must be motion, doppler or both");
+      if (matcher != "orb" || per_scan) die("--compensate runs on the windowed path only (not with --per-scan / --matcher nn)");
+      if (estimator == "mcransac") die("--compensate does not go with --estimator mcransac, which has its own motion model");
+      mcp.flags = compensate == "motion" ? RSX_MOCOMP_DESKEW : compensate == "doppler" ? RSX_MOCOMP_DOPPLER : RSX_MOCOMP_DESKEW | RSX_MOCOMP_DOPPLER;
+      mcp.dt_scan = rsp.dt_scan;
+    }
 
     if (matcher == "orb" && !per_scan) {
       // ---------------- windows of scans through rsx_odometry_push ----------------
@@ -283,6 +300,7 @@ int main(int argc, char **argv) {
       if (use_c18) check(rsx_odometry_set_cen2018(odo, &c18), "rsx_odometry_set_cen2018");
       if (estimator != "orora")
         check(rsx_odometry_set_estimator(odo, estimator == "ransac" ? RSX_ESTIMATOR_RANSAC : RSX_ESTIMATOR_MCRANSAC, &rsp), "rsx_odometry_set_estimator");
+      if (!compensate.empty()) check(rsx_odometry_set_compensation(odo, &mcp), "rsx_odometry_set_compensation");
       // scans per rsx_odometry_push: two of the library's internal windows, so that inside a call the upload and the extraction of
       // the second overlap the matching of the first (the pinned buffers are 2 x W images)
       const int W = window > 0 ? std::min(window, 4096) : 2 * rsx_odometry_window();

@@ -4,9 +4,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, OdometryParams, RansacParams, check, lib
+from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, MocompParams, OdometryParams,
+                   RansacParams, check, lib)
 
 ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_*
+COMPENSATIONS = {"motion": MOCOMP_DESKEW, "doppler": MOCOMP_DOPPLER, "both": MOCOMP_DESKEW | MOCOMP_DOPPLER}  # rsx_mocomp_params.flags
 
 
 def default_params():
@@ -18,14 +20,19 @@ def default_params():
 class Odometry:
     """keypoints: "cen2019" (default) or "cen2018"; cen2018: its Cen2018Params (None: cen2018.default_params()).
     estimator: "orora" (default), "ransac" or "mcransac"; ransac: their RansacParams (None: ransac.default_params()).
-    exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT)."""
+    exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT).
+    compensate: None (default), "motion", "doppler" or "both": every pair is estimated, its matches compensated with that
+    estimate, and estimated again (rsx_odometry_set_compensation; not with "mcransac"); beta, dt_scan: the Doppler factor and
+    the scan period of the model (None: the library's defaults)."""
 
     def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
-                 exact_clique=False):
+                 exact_clique=False, compensate=None, beta=None, dt_scan=None):
         if keypoints not in ("cen2019", "cen2018"):
             raise ValueError("keypoints must be cen2019 or cen2018")
         if estimator not in ESTIMATORS:
             raise ValueError("estimator must be orora, ransac or mcransac")
+        if compensate is not None and compensate not in COMPENSATIONS:
+            raise ValueError("compensate must be None, motion, doppler or both")
         self._L = lib()
         self.rows, self.cols = rows, cols
         self.params = params if params is not None else default_params()
@@ -40,6 +47,25 @@ class Odometry:
             self.set_cen2018(cen2018)
         if estimator != "orora":
             self.set_estimator(estimator, ransac)
+        if compensate is not None:
+            self.set_compensation(compensate, beta=beta, dt_scan=dt_scan)
+
+    def set_compensation(self, compensate, beta=None, dt_scan=None):
+        """Switch the compensation of keypoints on ("motion", "doppler", "both", or a MocompParams) or off (None).  Only while the
+        handle holds no scan, and not with the "mcransac" estimator."""
+        if compensate is None:
+            check(self._L.rsx_odometry_set_compensation(self._h, None))
+            return
+        p = compensate
+        if not isinstance(p, MocompParams):
+            p = MocompParams()
+            check(self._L.rsx_mocomp_default_params(C.byref(p)))
+            p.flags = COMPENSATIONS[compensate]
+            if beta is not None:
+                p.beta = beta
+            if dt_scan is not None:
+                p.dt_scan = dt_scan
+        check(self._L.rsx_odometry_set_compensation(self._h, C.byref(p)))
 
     def set_estimator(self, estimator, ransac=None):
         """Switch the motion estimator (ransac: RansacParams or None for the defaults).  Only while the handle holds no scan."""
