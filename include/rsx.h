@@ -372,10 +372,11 @@ int rsx_orora_max_clique_matches(void); /* 2048: pairs with more matches go to t
  * that the asynchronous device entry never allocates.  The host-buffer entries size them by themselves. */
 int rsx_orora_reserve(rsx_orora *h, int64_t max_total_matches);
 /* The selection on its own (params->tim_noise_bound is the consistency bound; NULL = defaults): out_member[m] = 1 for the
- * matches kept, laid out like the matches; out_info[n_pairs] (either may be NULL).  Host buffers, synchronous. */
+ * matches kept, laid out like the matches; out_info[n_pairs] (either may be NULL).  Host buffers, synchronous; offsets as for
+ * rsx_orora_register_batch. */
 int rsx_orora_max_clique_batch(rsx_orora *h, const float *src_xy, const float *dst_xy, const int64_t *offsets, int32_t n_pairs,
                                const rsx_orora_params *params, uint8_t *out_member, rsx_orora_pmc_info *out_info);
-/* device buffers, asynchronous on `stream` */
+/* device buffers, asynchronous on `stream`; d_offsets are trusted (see rsx_orora_register_batch_device) */
 int rsx_orora_max_clique_batch_device(rsx_orora *h, const float *d_src_xy, const float *d_dst_xy, const int64_t *d_offsets,
                                       int32_t n_pairs, const rsx_orora_params *params, uint8_t *d_member, rsx_orora_pmc_info *d_info,
                                       void *stream);
@@ -389,10 +390,14 @@ int rsx_orora_clique_node_budget(rsx_orora *h, int64_t *out_nodes);
 int rsx_orora_create(int device, rsx_orora **out);
 int rsx_orora_destroy(rsx_orora *h);
 /* n_pairs scan pairs; pair i owns matches [offsets[i], offsets[i+1]) of the concatenated
- * src_xy/dst_xy arrays (float x,y per match).  Host buffers, synchronous. */
+ * src_xy/dst_xy arrays (float x,y per match).  Host buffers, synchronous.  offsets[n_pairs + 1] must start at 0 and never
+ * decrease: every host-buffer entry that takes offsets (this one, rsx_orora_max_clique_batch, rsx_ransac_estimate_batch,
+ * rsx_mocomp_points_batch, rsx_mocomp_matches_batch) checks the whole array and refuses anything else with RSX_ERR_BAD_ARG
+ * before it copies or writes anything. */
 int rsx_orora_register_batch(rsx_orora *h, const float *src_xy, const float *dst_xy, const int64_t *offsets,
                              int32_t n_pairs, const rsx_orora_params *params, rsx_orora_result *out);
-/* device buffers, asynchronous on `stream` */
+/* device buffers, asynchronous on `stream`.  A device entry cannot look at d_offsets: they must obey the same rule, or the
+ * kernels read outside the arrays */
 int rsx_orora_register_batch_device(rsx_orora *h, const float *d_src_xy, const float *d_dst_xy,
                                     const int64_t *d_offsets, int32_t n_pairs, const rsx_orora_params *params,
                                     rsx_orora_result *d_out, void *stream);
@@ -439,11 +444,11 @@ typedef struct {
 int rsx_ransac_default_params(rsx_ransac_params *p);
 int rsx_ransac_create(int device, rsx_ransac **out);
 int rsx_ransac_destroy(rsx_ransac *h);
-/* n_pairs scan pairs laid out as for rsx_orora_register_batch; dt [matches] (NULL unless RSX_RANSAC_MOTION_COMPENSATED);
+/* n_pairs scan pairs laid out as for rsx_orora_register_batch (offsets checked likewise); dt [matches] (NULL unless RSX_RANSAC_MOTION_COMPENSATED);
  * out [n_pairs]; out_inlier (optional) [matches]: 1 for the winner's inliers.  Host buffers, synchronous. */
 int rsx_ransac_estimate_batch(rsx_ransac *h, const float *src_xy, const float *dst_xy, const float *dt, const int64_t *offsets,
                               int32_t n_pairs, const rsx_ransac_params *params, rsx_ransac_result *out, uint8_t *out_inlier);
-/* device buffers, asynchronous on `stream`; never allocates or synchronises */
+/* device buffers, asynchronous on `stream`; never allocates or synchronises; d_offsets are trusted */
 int rsx_ransac_estimate_batch_device(rsx_ransac *h, const float *d_src_xy, const float *d_dst_xy, const float *d_dt,
                                      const int64_t *d_offsets, int32_t n_pairs, const rsx_ransac_params *params,
                                      rsx_ransac_result *d_out, uint8_t *d_out_inlier, void *stream);
@@ -485,13 +490,13 @@ typedef struct {
 int rsx_mocomp_default_params(rsx_mocomp_params *p);
 int rsx_mocomp_create(int device, rsx_mocomp **out);
 int rsx_mocomp_destroy(rsx_mocomp *h);
-/* n_scans clouds in the offsets layout of rsx_orora_register_batch: scan i owns points [offsets[i], offsets[i+1]) of xy
+/* n_scans clouds in the offsets layout of rsx_orora_register_batch (checked likewise): scan i owns points [offsets[i], offsets[i+1]) of xy
  * (float x, y per point) and of rows (the azimuth row of each point); w [n_scans][3] doubles: (vx, vy, wz) of each scan.
  * out_xy: the compensated points, laid out like xy, a buffer of its own; out_status [n_scans] (optional): 0 or
  * RSX_MOCOMP_STATUS_ANGLE.  params = NULL: rsx_mocomp_default_params (both corrections).  Host buffers, synchronous. */
 int rsx_mocomp_points_batch(rsx_mocomp *h, const float *xy, const int32_t *rows, const int64_t *offsets, int32_t n_scans, const double *w,
                             const rsx_mocomp_params *params, float *out_xy, int32_t *out_status);
-/* device buffers, asynchronous on `stream`; never allocates or synchronises */
+/* device buffers, asynchronous on `stream`; never allocates or synchronises; d_offsets are trusted */
 int rsx_mocomp_points_batch_device(rsx_mocomp *h, const float *d_xy, const int32_t *d_rows, const int64_t *d_offsets, int32_t n_scans,
                                    const double *d_w, const rsx_mocomp_params *params, float *d_out_xy, int32_t *d_out_status, void *stream);
 /* The matches of n_pairs scan pairs as staged for rsx_orora_register_batch (src = the later scan's points, dst = the earlier
@@ -499,7 +504,8 @@ int rsx_mocomp_points_batch_device(rsx_mocomp *h, const float *d_xy, const int32
  * rsx_orora_result convention (dst = R(yaw) src + (x, y)).  The kernel derives the pair's velocity w = log(pose) / dt_scan
  * (the polynomials again and one division; |yaw| <= 0.5) and writes both sides compensated with it, each into the start frame
  * of its own scan: out_src = exp(tau_cur w) src, out_dst = exp(tau_prev w) dst, so that out_dst = exp(dt_scan w) out_src for a
- * static point.  out_status [n_pairs] (optional).  Host buffers, synchronous. */
+ * static point.  out_status [n_pairs] (optional).  Host buffers, synchronous; offsets checked as above.  The device entry
+ * trusts d_offsets. */
 int rsx_mocomp_matches_batch(rsx_mocomp *h, const float *src_xy, const float *dst_xy, const int32_t *a_cur, const int32_t *a_prev,
                              const int64_t *offsets, int32_t n_pairs, const double *pose, const rsx_mocomp_params *params, float *out_src_xy,
                              float *out_dst_xy, int32_t *out_status);

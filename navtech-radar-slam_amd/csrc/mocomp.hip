@@ -32,6 +32,7 @@
 #include <new>
 
 #include "mocomp.h"
+#include "ragged_host.h"
 
 #pragma STDC FP_CONTRACT OFF
 
@@ -264,13 +265,6 @@ int resolve_params(const rsx_mocomp_params *params, rsx_mocomp_params &dp) {
   return rsx::mocomp::check_params(dp);
 }
 
-int check_offsets(const int64_t *offsets, int32_t n) {
-  if (offsets[0] != 0) return fail(RSX_ERR_BAD_ARG, "offsets must start at 0");
-  for (int32_t i = 0; i < n; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(RSX_ERR_BAD_ARG, "offsets must be non-decreasing (entry %d)", i);
-  return RSX_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -329,28 +323,22 @@ int rsx_mocomp_points_batch(rsx_mocomp *h, const float *xy, const int32_t *rows,
   RSX_TRY(resolve_params(params, dp));
   if (n_scans == 0) return RSX_OK;
   if (n_scans > MAX_GROUPS) return fail(RSX_ERR_BAD_ARG, "n_scans above %d", MAX_GROUPS);
-  RSX_TRY(check_offsets(offsets, n_scans));
-  const size_t m = (size_t)offsets[n_scans], mm = m ? m : 1;
+  RSX_TRY(rsx::check_offsets(offsets, n_scans, "rsx_mocomp_points_batch"));
+  const size_t m = (size_t)offsets[n_scans], n = (size_t)n_scans;
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   RSX_TRY(h->order.enter(s));
-  RSX_TRY(h->in0.reserve(mm * 8, s, false));
-  RSX_TRY(h->a0.reserve(mm * 4, s, false));
-  RSX_TRY(h->out0.reserve(mm * 8, s, false));
-  RSX_TRY(h->off.reserve((size_t)(n_scans + 1) * 8, s, false));
-  RSX_TRY(h->vel.reserve((size_t)n_scans * 24, s, false));
-  RSX_TRY(h->st.reserve((size_t)n_scans * 4, s, false));
-  if (m) {
-    RSX_HIP(hipMemcpyAsync(h->in0.p, xy, m * 8, hipMemcpyHostToDevice, s));
-    RSX_HIP(hipMemcpyAsync(h->a0.p, rows, m * 4, hipMemcpyHostToDevice, s));
-  }
-  RSX_HIP(hipMemcpyAsync(h->off.p, offsets, (size_t)(n_scans + 1) * 8, hipMemcpyHostToDevice, s));
-  RSX_HIP(hipMemcpyAsync(h->vel.p, w, (size_t)n_scans * 24, hipMemcpyHostToDevice, s));
+  RSX_TRY(rsx::stage_up(h->in0, xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->a0, rows, m * 4, s));
+  RSX_TRY(rsx::stage_up(h->off, offsets, (n + 1) * 8, s));
+  RSX_TRY(rsx::stage_up(h->vel, w, n * 24, s));
+  RSX_TRY(rsx::stage_room(h->out0, m * 8, s));
+  RSX_TRY(rsx::stage_room(h->st, n * 4, s));
   RSX_TRY(launch_points(h->in0.as<float>(), h->a0.as<int32_t>(), h->off.as<int64_t>(), n_scans, h->vel.as<double>(), dp, h->out0.as<float>(),
                         h->st.as<int32_t>(), s));
-  if (m) RSX_HIP(hipMemcpyAsync(out_xy, h->out0.p, m * 8, hipMemcpyDeviceToHost, s));
-  if (out_status) RSX_HIP(hipMemcpyAsync(out_status, h->st.p, (size_t)n_scans * 4, hipMemcpyDeviceToHost, s));
+  RSX_TRY(rsx::stage_down(out_xy, h->out0, m * 8, s));
+  RSX_TRY(rsx::stage_down(out_status, h->st, n * 4, s));
   RSX_HIP(hipStreamSynchronize(s));
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -381,36 +369,26 @@ int rsx_mocomp_matches_batch(rsx_mocomp *h, const float *src_xy, const float *ds
   rsx_mocomp_params dp;
   RSX_TRY(resolve_params(params, dp));
   if (n_pairs == 0) return RSX_OK;
-  RSX_TRY(check_offsets(offsets, n_pairs));
-  const size_t m = (size_t)offsets[n_pairs], mm = m ? m : 1;
+  RSX_TRY(rsx::check_offsets(offsets, n_pairs, "rsx_mocomp_matches_batch"));
+  const size_t m = (size_t)offsets[n_pairs], n = (size_t)n_pairs;
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   RSX_TRY(h->order.enter(s));
-  RSX_TRY(h->in0.reserve(mm * 8, s, false));
-  RSX_TRY(h->in1.reserve(mm * 8, s, false));
-  RSX_TRY(h->a0.reserve(mm * 4, s, false));
-  RSX_TRY(h->a1.reserve(mm * 4, s, false));
-  RSX_TRY(h->out0.reserve(mm * 8, s, false));
-  RSX_TRY(h->out1.reserve(mm * 8, s, false));
-  RSX_TRY(h->off.reserve((size_t)(n_pairs + 1) * 8, s, false));
-  RSX_TRY(h->vel.reserve((size_t)n_pairs * 24, s, false));
-  RSX_TRY(h->st.reserve((size_t)n_pairs * 4, s, false));
-  if (m) {
-    RSX_HIP(hipMemcpyAsync(h->in0.p, src_xy, m * 8, hipMemcpyHostToDevice, s));
-    RSX_HIP(hipMemcpyAsync(h->in1.p, dst_xy, m * 8, hipMemcpyHostToDevice, s));
-    RSX_HIP(hipMemcpyAsync(h->a0.p, a_cur, m * 4, hipMemcpyHostToDevice, s));
-    RSX_HIP(hipMemcpyAsync(h->a1.p, a_prev, m * 4, hipMemcpyHostToDevice, s));
-  }
-  RSX_HIP(hipMemcpyAsync(h->off.p, offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, s));
-  RSX_HIP(hipMemcpyAsync(h->vel.p, pose, (size_t)n_pairs * 24, hipMemcpyHostToDevice, s));
+  RSX_TRY(rsx::stage_up(h->in0, src_xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->in1, dst_xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->a0, a_cur, m * 4, s));
+  RSX_TRY(rsx::stage_up(h->a1, a_prev, m * 4, s));
+  RSX_TRY(rsx::stage_up(h->off, offsets, (n + 1) * 8, s));
+  RSX_TRY(rsx::stage_up(h->vel, pose, n * 24, s));
+  RSX_TRY(rsx::stage_room(h->out0, m * 8, s));
+  RSX_TRY(rsx::stage_room(h->out1, m * 8, s));
+  RSX_TRY(rsx::stage_room(h->st, n * 4, s));
   RSX_TRY(rsx::mocomp::launch_matches(h->in0.as<float>(), h->in1.as<float>(), h->a0.as<int32_t>(), h->a1.as<int32_t>(), h->off.as<int64_t>(), n_pairs,
                                       h->vel.p, 24, -1, dp, h->out0.as<float>(), h->out1.as<float>(), h->st.as<int32_t>(), s));
-  if (m) {
-    RSX_HIP(hipMemcpyAsync(out_src_xy, h->out0.p, m * 8, hipMemcpyDeviceToHost, s));
-    RSX_HIP(hipMemcpyAsync(out_dst_xy, h->out1.p, m * 8, hipMemcpyDeviceToHost, s));
-  }
-  if (out_status) RSX_HIP(hipMemcpyAsync(out_status, h->st.p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, s));
+  RSX_TRY(rsx::stage_down(out_src_xy, h->out0, m * 8, s));
+  RSX_TRY(rsx::stage_down(out_dst_xy, h->out1, m * 8, s));
+  RSX_TRY(rsx::stage_down(out_status, h->st, n * 4, s));
   RSX_HIP(hipStreamSynchronize(s));
   return RSX_OK;
 } RSX_CATCH_ALL

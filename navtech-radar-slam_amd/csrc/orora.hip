@@ -20,6 +20,7 @@
 
 #include "rsx_common.h"
 #include "pmc.h"
+#include "ragged_host.h"
 
 namespace {
 
@@ -801,17 +802,97 @@ struct rsx_orora {
   bool attr_set = false;
 };
 
+using rsx::fail;
+
 namespace {
+
+// room for the selected matches of a call of `total` matches (at least one, so that sel_cap says "reserved")
 int reserve_selection(rsx_orora *h, int64_t total, hipStream_t s) {
+  if (total < 1) total = 1;
   if (total <= h->sel_cap) return RSX_OK;
   RSX_TRY(h->sel_src.reserve((size_t)total * 8, s, false));
   RSX_TRY(h->sel_dst.reserve((size_t)total * 8, s, false));
   h->sel_cap = (int64_t)(h->sel_src.bytes < h->sel_dst.bytes ? h->sel_src.bytes : h->sel_dst.bytes) / 8;
   return RSX_OK;
 }
-}  // namespace
 
-using rsx::fail;
+// the defaults, then the caller's; solver: the call runs the GNC solver (the selection on its own does not read its fields)
+int resolve_params(const rsx_orora_params *params, bool solver, rsx_orora_params &dp) {
+  rsx_orora_default_params(&dp);
+  if (params) dp = *params;
+  if (solver && (dp.max_iterations < 1 || !(dp.gnc_factor > 1.0))) return fail(RSX_ERR_BAD_ARG, "bad GNC params");
+  if ((dp.flags & RSX_ORORA_PMC_EXACT) && !(dp.flags & RSX_ORORA_PMC)) return fail(RSX_ERR_BAD_ARG, "RSX_ORORA_PMC_EXACT needs RSX_ORORA_PMC");
+  return RSX_OK;
+}
+
+// What the two registration entries enqueue on s.  The caller holds h->mu, has made h->device current and has passed s
+// through h->order
+int register_locked(rsx_orora *h, const float *d_src_xy, const float *d_dst_xy, const int64_t *d_offsets, int32_t n_pairs,
+                    const rsx_orora_params &dp, rsx_orora_result *d_out, hipStream_t s) {
+  if (!h->attr_set) {
+    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&orora_register_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
+    h->attr_set = true;
+  }
+  Params kp;
+  kp.c2 = dp.tim_noise_bound * dp.tim_noise_bound;
+  if (kp.c2 < 1e-16) kp.c2 = 1e-2;
+  kp.s_r = dp.noise_bound_radial;
+  kp.s_t = dp.noise_bound_tangential;
+  kp.gnc_factor = dp.gnc_factor;
+  kp.cost_threshold = dp.cost_threshold;
+  kp.max_iterations = dp.max_iterations;
+  kp.complete_graph = (dp.flags & RSX_ORORA_COMPLETE_GRAPH) ? 1 : 0;
+  kp.teaser_cost = (dp.flags & RSX_ORORA_TEASER_COST) ? 1 : 0;
+  // the list of pairs too large for the on-chip kernel is built on the device (the offsets may live there only); the
+  // large-pair kernel always runs its few workgroups, which return at once when the list is empty
+  RSX_TRY(h->big_list.reserve((size_t)(n_pairs + 1) * sizeof(int), s, false));
+  RSX_TRY(h->big_ws.reserve((size_t)BIG_BLOCKS * BigLayout::TOTAL, s, false));
+  RSX_HIP(hipMemsetAsync(h->big_list.p, 0, sizeof(int), s));
+  Selection sel{nullptr, nullptr, nullptr};
+  if (dp.flags & RSX_ORORA_PMC) {
+    // max-clique inlier selection first (csrc/pmc.hip): the solver then reads each pair's selected matches
+    if (h->sel_cap <= 0) return fail(RSX_ERR_BAD_ARG, "RSX_ORORA_PMC on the device entry needs rsx_orora_reserve(max_total_matches) first");
+    RSX_TRY(h->sel_cnt.reserve((size_t)n_pairs * 4, s, false));
+    RSX_TRY(h->pmc_info.reserve((size_t)n_pairs * sizeof(rsx_orora_pmc_info), s, false));
+    RSX_TRY(rsx::pmc::launch(h->pmc_ws, h->device, reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy),
+                             d_offsets, n_pairs, dp.tim_noise_bound, nullptr, h->pmc_info.as<rsx_orora_pmc_info>(), h->sel_src.as<float2>(),
+                             h->sel_dst.as<float2>(), h->sel_cnt.as<int32_t>(), h->sel_cap, s,
+                             (dp.flags & RSX_ORORA_PMC_EXACT) ? h->clique_node_budget : 0));
+    sel = Selection{h->sel_src.as<float2>(), h->sel_dst.as<float2>(), h->sel_cnt.as<int32_t>()};
+    h->last_stream = s;
+    h->last_pmc_pairs = n_pairs;
+  }
+  hipLaunchKernelGGL(orora_register_kernel, dim3(n_pairs), dim3(256), LDS_TOTAL, s,
+                     reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets,
+                     n_pairs, kp, d_out, h->big_list.as<int>(), sel);
+  hipLaunchKernelGGL(orora_register_big_kernel, dim3(BIG_BLOCKS), dim3(1024), 0, s,
+                     reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets, kp, d_out,
+                     h->big_list.as<int>(), h->big_ws.as<char>(), sel);
+  RSX_HIP(hipGetLastError());
+#if RSX_ORORA_PROF
+  {
+    unsigned long long v[8] = {0}, z[8] = {0};
+    RSX_HIP(hipStreamSynchronize(s));
+    RSX_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_orora_prof), sizeof(v)));
+    RSX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_orora_prof), z, sizeof(z)));
+    const double n = n_pairs;
+    fprintf(stderr, "[orora prof] per pair (cycles): gnc %.0f (%.1f iterations)  bounds %.0f  tls x+y %.0f (sorts %.0f)  rest %.0f\n",
+            v[0] / n, v[6] / n, v[1] / n, v[2] / n, v[4] / n, v[3] / n);
+  }
+#endif
+  return RSX_OK;
+}
+
+// the selection on its own, under the same conditions
+int max_clique_locked(rsx_orora *h, const float *d_src_xy, const float *d_dst_xy, const int64_t *d_offsets, int32_t n_pairs,
+                      const rsx_orora_params &dp, uint8_t *d_member, rsx_orora_pmc_info *d_info, hipStream_t s) {
+  return rsx::pmc::launch(h->pmc_ws, h->device, reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets,
+                          n_pairs, dp.tim_noise_bound, d_member, d_info, nullptr, nullptr, nullptr, 0, s,
+                          (dp.flags & RSX_ORORA_PMC_EXACT) ? h->clique_node_budget : 0);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -856,97 +937,34 @@ int rsx_orora_register_batch_device(rsx_orora *h, const float *d_src_xy, const f
   if (!h || !d_src_xy || !d_dst_xy || !d_offsets || !d_out || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (n_pairs == 0) return RSX_OK;
   rsx_orora_params dp;
-  rsx_orora_default_params(&dp);
-  if (params) dp = *params;
-  if (dp.max_iterations < 1 || !(dp.gnc_factor > 1.0)) return fail(RSX_ERR_BAD_ARG, "bad GNC params");
-  if ((dp.flags & RSX_ORORA_PMC_EXACT) && !(dp.flags & RSX_ORORA_PMC)) return fail(RSX_ERR_BAD_ARG, "RSX_ORORA_PMC_EXACT needs RSX_ORORA_PMC");
+  RSX_TRY(resolve_params(params, true, dp));
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
-  if (!h->attr_set) {
-    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&orora_register_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    h->attr_set = true;
-  }
-  Params kp;
-  kp.c2 = dp.tim_noise_bound * dp.tim_noise_bound;
-  if (kp.c2 < 1e-16) kp.c2 = 1e-2;
-  kp.s_r = dp.noise_bound_radial;
-  kp.s_t = dp.noise_bound_tangential;
-  kp.gnc_factor = dp.gnc_factor;
-  kp.cost_threshold = dp.cost_threshold;
-  kp.max_iterations = dp.max_iterations;
-  kp.complete_graph = (dp.flags & RSX_ORORA_COMPLETE_GRAPH) ? 1 : 0;
-  kp.teaser_cost = (dp.flags & RSX_ORORA_TEASER_COST) ? 1 : 0;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
   RSX_TRY(h->order.enter(s));
-  // the list of pairs too large for the on-chip kernel is built on the device (the offsets may live there only); the
-  // large-pair kernel always runs its few workgroups, which return at once when the list is empty
-  RSX_TRY(h->big_list.reserve((size_t)(n_pairs + 1) * sizeof(int), s, false));
-  RSX_TRY(h->big_ws.reserve((size_t)BIG_BLOCKS * BigLayout::TOTAL, s, false));
-  RSX_HIP(hipMemsetAsync(h->big_list.p, 0, sizeof(int), s));
-  Selection sel{nullptr, nullptr, nullptr};
-  if (dp.flags & RSX_ORORA_PMC) {
-    // max-clique inlier selection first (csrc/pmc.hip): the solver then reads each pair's selected matches
-    if (h->sel_cap <= 0) return fail(RSX_ERR_BAD_ARG, "RSX_ORORA_PMC on the device entry needs rsx_orora_reserve(max_total_matches) first");
-    RSX_TRY(h->sel_cnt.reserve((size_t)n_pairs * 4, s, false));
-    RSX_TRY(h->pmc_info.reserve((size_t)n_pairs * sizeof(rsx_orora_pmc_info), s, false));
-    RSX_TRY(rsx::pmc::launch(h->pmc_ws, h->device, reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy),
-                             d_offsets, n_pairs, dp.tim_noise_bound, nullptr, h->pmc_info.as<rsx_orora_pmc_info>(), h->sel_src.as<float2>(),
-                             h->sel_dst.as<float2>(), h->sel_cnt.as<int32_t>(), h->sel_cap, s,
-                             (dp.flags & RSX_ORORA_PMC_EXACT) ? h->clique_node_budget : 0));
-    sel = Selection{h->sel_src.as<float2>(), h->sel_dst.as<float2>(), h->sel_cnt.as<int32_t>()};
-    h->last_stream = s;
-    h->last_pmc_pairs = n_pairs;
-  }
-  hipLaunchKernelGGL(orora_register_kernel, dim3(n_pairs), dim3(256), LDS_TOTAL, s,
-                     reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets,
-                     n_pairs, kp, d_out, h->big_list.as<int>(), sel);
-  hipLaunchKernelGGL(orora_register_big_kernel, dim3(BIG_BLOCKS), dim3(1024), 0, s,
-                     reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets, kp, d_out,
-                     h->big_list.as<int>(), h->big_ws.as<char>(), sel);
-  RSX_HIP(hipGetLastError());
-#if RSX_ORORA_PROF
-  {
-    unsigned long long v[8] = {0}, z[8] = {0};
-    RSX_HIP(hipStreamSynchronize(s));
-    RSX_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_orora_prof), sizeof(v)));
-    RSX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_orora_prof), z, sizeof(z)));
-    const double n = n_pairs;
-    fprintf(stderr, "[orora prof] per pair (cycles): gnc %.0f (%.1f iterations)  bounds %.0f  tls x+y %.0f (sorts %.0f)  rest %.0f\n",
-            v[0] / n, v[6] / n, v[1] / n, v[2] / n, v[4] / n, v[3] / n);
-  }
-#endif
-  return RSX_OK;
+  return register_locked(h, d_src_xy, d_dst_xy, d_offsets, n_pairs, dp, d_out, s);
 } RSX_CATCH_ALL
 
 int rsx_orora_register_batch(rsx_orora *h, const float *src_xy, const float *dst_xy, const int64_t *offsets, int32_t n_pairs,
                              const rsx_orora_params *params, rsx_orora_result *out) try {
   if (!h || !src_xy || !dst_xy || !offsets || !out || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (n_pairs == 0) return RSX_OK;
-  const int64_t m = offsets[n_pairs];
-  if (m < 0 || offsets[0] != 0) return fail(RSX_ERR_BAD_ARG, "offsets must start at 0 and be non-decreasing");
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    RSX_HIP(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    RSX_TRY(h->order.enter(s));
-    RSX_TRY(h->src.reserve((size_t)(m ? m : 1) * 8, s, false));
-    RSX_TRY(h->dst.reserve((size_t)(m ? m : 1) * 8, s, false));
-    RSX_TRY(h->off.reserve((size_t)(n_pairs + 1) * 8, s, false));
-    RSX_TRY(h->res.reserve((size_t)n_pairs * sizeof(rsx_orora_result), s, false));
-    if (params && (params->flags & RSX_ORORA_PMC)) RSX_TRY(reserve_selection(h, m ? m : 1, s));
-    if (m) {
-      RSX_HIP(hipMemcpyAsync(h->src.p, src_xy, (size_t)m * 8, hipMemcpyHostToDevice, s));
-      RSX_HIP(hipMemcpyAsync(h->dst.p, dst_xy, (size_t)m * 8, hipMemcpyHostToDevice, s));
-    }
-    RSX_HIP(hipMemcpyAsync(h->off.p, offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, s));
-  }
-  RSX_TRY(rsx_orora_register_batch_device(h, h->src.as<float>(), h->dst.as<float>(), h->off.as<int64_t>(), n_pairs, params,
-                                          h->res.as<rsx_orora_result>(), h->stream));
+  rsx_orora_params dp;
+  RSX_TRY(resolve_params(params, true, dp));
+  RSX_TRY(rsx::check_offsets(offsets, n_pairs, "rsx_orora_register_batch"));
+  const size_t m = (size_t)offsets[n_pairs], res_bytes = (size_t)n_pairs * sizeof(rsx_orora_result);
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(h->order.enter(h->stream));
-  RSX_HIP(hipMemcpyAsync(out, h->res.p, (size_t)n_pairs * sizeof(rsx_orora_result), hipMemcpyDeviceToHost, h->stream));
-  RSX_HIP(hipStreamSynchronize(h->stream));
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(rsx::stage_up(h->src, src_xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->dst, dst_xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->off, offsets, (size_t)(n_pairs + 1) * 8, s));
+  RSX_TRY(rsx::stage_room(h->res, res_bytes, s));
+  if (dp.flags & RSX_ORORA_PMC) RSX_TRY(reserve_selection(h, (int64_t)m, s));
+  RSX_TRY(register_locked(h, h->src.as<float>(), h->dst.as<float>(), h->off.as<int64_t>(), n_pairs, dp, h->res.as<rsx_orora_result>(), s));
+  RSX_TRY(rsx::stage_down(out, h->res, res_bytes, s));
+  RSX_HIP(hipStreamSynchronize(s));
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -965,47 +983,36 @@ int rsx_orora_max_clique_batch_device(rsx_orora *h, const float *d_src_xy, const
   if (!h || !d_src_xy || !d_dst_xy || !d_offsets || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (n_pairs == 0) return RSX_OK;
   rsx_orora_params dp;
-  rsx_orora_default_params(&dp);
-  if (params) dp = *params;
-  if ((dp.flags & RSX_ORORA_PMC_EXACT) && !(dp.flags & RSX_ORORA_PMC)) return fail(RSX_ERR_BAD_ARG, "RSX_ORORA_PMC_EXACT needs RSX_ORORA_PMC");
+  RSX_TRY(resolve_params(params, false, dp));
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
   RSX_TRY(h->order.enter(s));
-  return rsx::pmc::launch(h->pmc_ws, h->device, reinterpret_cast<const float2 *>(d_src_xy), reinterpret_cast<const float2 *>(d_dst_xy), d_offsets,
-                          n_pairs, dp.tim_noise_bound, d_member, d_info, nullptr, nullptr, nullptr, 0, s,
-                          (dp.flags & RSX_ORORA_PMC_EXACT) ? h->clique_node_budget : 0);
+  return max_clique_locked(h, d_src_xy, d_dst_xy, d_offsets, n_pairs, dp, d_member, d_info, s);
 } RSX_CATCH_ALL
 
 int rsx_orora_max_clique_batch(rsx_orora *h, const float *src_xy, const float *dst_xy, const int64_t *offsets, int32_t n_pairs,
                                const rsx_orora_params *params, uint8_t *out_member, rsx_orora_pmc_info *out_info) try {
   if (!h || !src_xy || !dst_xy || !offsets || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (n_pairs == 0) return RSX_OK;
-  const int64_t m = offsets[n_pairs];
-  if (m < 0 || offsets[0] != 0) return fail(RSX_ERR_BAD_ARG, "offsets must start at 0 and be non-decreasing");
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    RSX_HIP(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    RSX_TRY(h->order.enter(s));
-    RSX_TRY(h->src.reserve((size_t)(m ? m : 1) * 8, s, false));
-    RSX_TRY(h->dst.reserve((size_t)(m ? m : 1) * 8, s, false));
-    RSX_TRY(h->off.reserve((size_t)(n_pairs + 1) * 8, s, false));
-    RSX_TRY(h->member.reserve((size_t)(m ? m : 1), s, false));
-    RSX_TRY(h->pmc_info.reserve((size_t)n_pairs * sizeof(rsx_orora_pmc_info), s, false));
-    if (m) {
-      RSX_HIP(hipMemcpyAsync(h->src.p, src_xy, (size_t)m * 8, hipMemcpyHostToDevice, s));
-      RSX_HIP(hipMemcpyAsync(h->dst.p, dst_xy, (size_t)m * 8, hipMemcpyHostToDevice, s));
-    }
-    RSX_HIP(hipMemcpyAsync(h->off.p, offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, s));
-  }
-  RSX_TRY(rsx_orora_max_clique_batch_device(h, h->src.as<float>(), h->dst.as<float>(), h->off.as<int64_t>(), n_pairs, params,
-                                            h->member.as<uint8_t>(), h->pmc_info.as<rsx_orora_pmc_info>(), h->stream));
+  rsx_orora_params dp;
+  RSX_TRY(resolve_params(params, false, dp));
+  RSX_TRY(rsx::check_offsets(offsets, n_pairs, "rsx_orora_max_clique_batch"));
+  const size_t m = (size_t)offsets[n_pairs], info_bytes = (size_t)n_pairs * sizeof(rsx_orora_pmc_info);
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(h->order.enter(h->stream));
-  if (out_member && m) RSX_HIP(hipMemcpyAsync(out_member, h->member.p, (size_t)m, hipMemcpyDeviceToHost, h->stream));
-  if (out_info) RSX_HIP(hipMemcpyAsync(out_info, h->pmc_info.p, (size_t)n_pairs * sizeof(rsx_orora_pmc_info), hipMemcpyDeviceToHost, h->stream));
-  RSX_HIP(hipStreamSynchronize(h->stream));
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(rsx::stage_up(h->src, src_xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->dst, dst_xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->off, offsets, (size_t)(n_pairs + 1) * 8, s));
+  RSX_TRY(rsx::stage_room(h->member, m, s));
+  RSX_TRY(rsx::stage_room(h->pmc_info, info_bytes, s));
+  RSX_TRY(max_clique_locked(h, h->src.as<float>(), h->dst.as<float>(), h->off.as<int64_t>(), n_pairs, dp, h->member.as<uint8_t>(),
+                            h->pmc_info.as<rsx_orora_pmc_info>(), s));
+  RSX_TRY(rsx::stage_down(out_member, h->member, m, s));
+  RSX_TRY(rsx::stage_down(out_info, h->pmc_info, info_bytes, s));
+  RSX_HIP(hipStreamSynchronize(s));
   return RSX_OK;
 } RSX_CATCH_ALL
 

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <new>
 
+#include "ragged_host.h"
 #include "ransac.h"
 
 namespace {
@@ -409,6 +410,19 @@ int rsx::ransac_check_params(const rsx_ransac_params &p) {
   return RSX_OK;
 }
 
+namespace {
+
+// the defaults, then the caller's, checked; dt: the per-match times of the call (the motion-compensated estimator needs them)
+int resolve_params(const rsx_ransac_params *params, const float *dt, rsx_ransac_params &dp) {
+  rsx_ransac_default_params(&dp);
+  if (params) dp = *params;
+  RSX_TRY(rsx::ransac_check_params(dp));
+  if ((dp.flags & RSX_RANSAC_MOTION_COMPENSATED) && !dt) return fail(RSX_ERR_BAD_ARG, "RSX_RANSAC_MOTION_COMPENSATED needs dt");
+  return RSX_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int rsx_ransac_default_params(rsx_ransac_params *p) try {
@@ -452,10 +466,7 @@ int rsx_ransac_estimate_batch_device(rsx_ransac *h, const float *d_src_xy, const
                                      void *stream) try {
   if (!h || !d_src_xy || !d_dst_xy || !d_offsets || !d_out || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   rsx_ransac_params dp;
-  rsx_ransac_default_params(&dp);
-  if (params) dp = *params;
-  RSX_TRY(rsx::ransac_check_params(dp));
-  if ((dp.flags & RSX_RANSAC_MOTION_COMPENSATED) && !d_dt) return fail(RSX_ERR_BAD_ARG, "RSX_RANSAC_MOTION_COMPENSATED needs dt");
+  RSX_TRY(resolve_params(params, d_dt, dp));
   if (n_pairs == 0) return RSX_OK;
   // No rsx::StreamOrder and no lock: the launch reads and writes the caller's buffers only -- the handle has no workspace that
   // calls on different streams could share, so there is nothing to order and they may run side by side
@@ -467,35 +478,24 @@ int rsx_ransac_estimate_batch(rsx_ransac *h, const float *src_xy, const float *d
                               const rsx_ransac_params *params, rsx_ransac_result *out, uint8_t *out_inlier) try {
   if (!h || !src_xy || !dst_xy || !offsets || !out || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   rsx_ransac_params dp;
-  rsx_ransac_default_params(&dp);
-  if (params) dp = *params;
-  RSX_TRY(rsx::ransac_check_params(dp));
-  const bool mc = (dp.flags & RSX_RANSAC_MOTION_COMPENSATED) != 0;
-  if (mc && !dt) return fail(RSX_ERR_BAD_ARG, "RSX_RANSAC_MOTION_COMPENSATED needs dt");
+  RSX_TRY(resolve_params(params, dt, dp));
   if (n_pairs == 0) return RSX_OK;
-  if (offsets[0] != 0) return fail(RSX_ERR_BAD_ARG, "offsets must start at 0");
-  for (int32_t i = 0; i < n_pairs; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(RSX_ERR_BAD_ARG, "offsets must be non-decreasing (pair %d)", i);
-  const size_t m = (size_t)offsets[n_pairs], mm = m ? m : 1;
+  RSX_TRY(rsx::check_offsets(offsets, n_pairs, "rsx_ransac_estimate_batch"));
+  const bool mc = (dp.flags & RSX_RANSAC_MOTION_COMPENSATED) != 0;
+  const size_t m = (size_t)offsets[n_pairs], res_bytes = (size_t)n_pairs * sizeof(rsx_ransac_result);
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  RSX_TRY(h->src.reserve(mm * 8, s, false));
-  RSX_TRY(h->dst.reserve(mm * 8, s, false));
-  if (mc) RSX_TRY(h->dt.reserve(mm * 4, s, false));
-  RSX_TRY(h->off.reserve((size_t)(n_pairs + 1) * 8, s, false));
-  RSX_TRY(h->res.reserve((size_t)n_pairs * sizeof(rsx_ransac_result), s, false));
-  if (out_inlier) RSX_TRY(h->inl.reserve(mm, s, false));
-  if (m) {
-    RSX_HIP(hipMemcpyAsync(h->src.p, src_xy, m * 8, hipMemcpyHostToDevice, s));
-    RSX_HIP(hipMemcpyAsync(h->dst.p, dst_xy, m * 8, hipMemcpyHostToDevice, s));
-    if (mc) RSX_HIP(hipMemcpyAsync(h->dt.p, dt, m * 4, hipMemcpyHostToDevice, s));
-  }
-  RSX_HIP(hipMemcpyAsync(h->off.p, offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, s));
+  RSX_TRY(rsx::stage_up(h->src, src_xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->dst, dst_xy, m * 8, s));
+  if (mc) RSX_TRY(rsx::stage_up(h->dt, dt, m * 4, s));
+  RSX_TRY(rsx::stage_up(h->off, offsets, (size_t)(n_pairs + 1) * 8, s));
+  RSX_TRY(rsx::stage_room(h->res, res_bytes, s));
+  if (out_inlier) RSX_TRY(rsx::stage_room(h->inl, m, s));
   RSX_TRY(launch(h->src.as<float>(), h->dst.as<float>(), mc ? h->dt.as<float>() : nullptr, h->off.as<int64_t>(), n_pairs, dp,
                  h->res.as<rsx_ransac_result>(), out_inlier ? h->inl.as<uint8_t>() : nullptr, s));
-  RSX_HIP(hipMemcpyAsync(out, h->res.p, (size_t)n_pairs * sizeof(rsx_ransac_result), hipMemcpyDeviceToHost, s));
-  if (out_inlier && m) RSX_HIP(hipMemcpyAsync(out_inlier, h->inl.p, m, hipMemcpyDeviceToHost, s));
+  RSX_TRY(rsx::stage_down(out, h->res, res_bytes, s));
+  RSX_TRY(rsx::stage_down(out_inlier, h->inl, m, s));
   RSX_HIP(hipStreamSynchronize(s));
   return RSX_OK;
 } RSX_CATCH_ALL

@@ -189,6 +189,33 @@ def test_argument_rules(mo, clouds):
     bad_off[0] = 1
     assert L.rsx_mocomp_points_batch(mo._h, xy.ctypes.data, rows.ctypes.data, bad_off.ctypes.data, len(SIZES), w.ctypes.data, None, out.ctypes.data,
                                      None) == -1
+    # offsets that decrease in the middle, or go negative: both host entries refuse them before anything is written
+    decreasing, negative = off.copy(), off.copy()
+    decreasing[2] = 100                                        # 0, 0, 100, 64, ..
+    negative[1] = -1
+    out7, st7 = np.full_like(xy, 7.0), np.full(len(SIZES), 99, dtype=np.int32)
+    for bad_off in (decreasing, negative):
+        assert L.rsx_mocomp_points_batch(mo._h, xy.ctypes.data, rows.ctypes.data, bad_off.ctypes.data, len(SIZES), w.ctypes.data, None,
+                                         out7.ctypes.data, st7.ctypes.data) == -1
+        assert b"offsets" in L.rsx_last_error_string()
+    assert (out7 == 7.0).all() and (st7 == 99).all()
+    assert L.rsx_mocomp_points_batch(mo._h, xy.ctypes.data, rows.ctypes.data, off.ctypes.data, len(SIZES), w.ctypes.data, None, out7.ctypes.data,
+                                     st7.ctypes.data) == 0
+    assert mn.same_bits(out7, mn.points_batch(xy, rows, off, w, 3)[0])
+    src, dst, a_cur, a_prev, moff, pose = _match_set()
+    pose, m = np.ascontiguousarray(pose), int(moff[-1])
+    os7, od7, mst7 = np.full_like(src, 7.0), np.full_like(dst, 7.0), np.full(3, 99, dtype=np.int32)
+
+    def matches(o):
+        return L.rsx_mocomp_matches_batch(mo._h, src.ctypes.data, dst.ctypes.data, a_cur.ctypes.data, a_prev.ctypes.data, o.ctypes.data, 3,
+                                          pose.ctypes.data, None, os7.ctypes.data, od7.ctypes.data, mst7.ctypes.data)
+
+    for bad_off in ([0, 60, 40, m], [0, -1, 40, m], [1, 5, 305, m]):
+        assert matches(np.array(bad_off, dtype=np.int64)) == -1 and b"offsets" in L.rsx_last_error_string(), bad_off
+    assert (os7 == 7.0).all() and (od7 == 7.0).all() and (mst7 == 99).all()
+    assert matches(moff) == 0
+    ws, wd, wst = mn.matches_batch(src, dst, a_cur, a_prev, moff, pose, 3)
+    assert mn.same_bits(os7, ws) and mn.same_bits(od7, wd) and np.array_equal(mst7, wst)
     # zero scans: nothing to do
     assert L.rsx_mocomp_points_batch(mo._h, xy.ctypes.data, rows.ctypes.data, off.ctypes.data, 0, w.ctypes.data, None, out.ctypes.data, None) == 0
     p = _rsx.MocompParams()

@@ -281,14 +281,32 @@ def test_bad_arguments(reg, oracle):
     assert host(ok, npairs=0) == 0 and dev(ok, npairs=0) == 0
     shifted = off + 5
     assert host(ok, o=shifted.ctypes.data) == -1
+    # offsets that decrease in the middle, or go negative: refused by both host entries (the selection on its own included)
+    m = int(off[-1])
+    member = np.full(m, SENTINEL, dtype=np.uint8)
+    info = np.full(n, 7, dtype=_rsx.PMC_INFO_DTYPE)
+
+    def clique(o):
+        return L.rsx_orora_max_clique_batch(reg._h, src.ctypes.data, dst.ctypes.data, o.ctypes.data, n, None, member.ctypes.data, info.ctypes.data)
+
+    assert clique(shifted) == -1
+    for bad_off in ([0, 60, 40, m], [0, -1, 40, m], [0, 40, 60, -1]):
+        bad_off = np.array(bad_off, dtype=np.int64)
+        assert host(ok, o=bad_off.ctypes.data) == -1 and b"offsets" in L.rsx_last_error_string(), bad_off
+        assert clique(bad_off) == -1 and b"offsets" in L.rsx_last_error_string(), bad_off
     torch.cuda.synchronize()
     assert (out.view(np.uint8) == np.full(n, 7, dtype=_rsx.ORORA_RESULT_DTYPE).view(np.uint8)).all()     # nothing was written
     assert (b.d_out.cpu().numpy() == SENTINEL).all()
+    assert (member == SENTINEL).all() and (info.view(np.uint8) == np.full(n, 7, dtype=_rsx.PMC_INFO_DTYPE).view(np.uint8)).all()
     want = oracle.orora_register_batch(src, dst, off)
     assert host(ok) == 0 and dev(None) == 0
     torch.cuda.synchronize()
     _check(out, want)
     assert b.result().tobytes() == out.tobytes()
+    wm, winfo = oracle.pmc_select_batch(src, dst, off, ok.tim_noise_bound)
+    assert clique(off) == 0 and np.array_equal(member, wm)
+    for f in ("size", "max_core", "seeds", "flags"):
+        assert np.array_equal(info[f], winfo[f]), f
 
 
 def test_one_nan_match_leaves_the_other_pairs_alone(reg):
@@ -315,6 +333,76 @@ def test_one_nan_match_leaves_the_other_pairs_alone(reg):
         torch.cuda.synchronize()
         assert b.result()[rest].tobytes() == without.tobytes()
         print(f"[orora nan] pair of {off[victim + 1] - off[victim]} matches, NaN in {where}: {got[victim]}")
+
+
+# ---- one handle, two threads ----
+
+def _common_offsets(a, b):
+    """two batches of as many pairs, cut to ONE offsets array: pair i keeps the first min(K_a, K_b) matches of each"""
+    k = np.minimum(np.diff(a[2]), np.diff(b[2]))
+
+    def cut(s):
+        return _concat([(s[0][s[2][i]:s[2][i] + k[i]], s[1][s[2][i]:s[2][i] + k[i]], np.array([0, k[i]])) for i in range(len(k))])
+    return cut(a), cut(b)
+
+
+def test_two_threads_on_one_handle(reg):
+    """include/rsx.h: "every entry point holds the handle's mutex for its whole duration, so any number of threads may call
+    concurrently".  Two threads share one handle and call a host-buffer entry 200 times each (ctypes releases the GIL), each
+    with its own batch: the batches differ in every coordinate but share one offsets array, so a call that read the other
+    thread's staged input, or downloaded the other thread's result, returns wrong bytes with status 0 -- never wrong sizes.
+    Every call returns, byte for byte, what its batch gave alone before the threads started: rsx_orora_register_batch against
+    itself, rsx_orora_max_clique_batch against itself (member bytes and info records), and one against the other with
+    RSX_ORORA_PMC on the registration (they share the selection's workspace)."""
+    import threading
+    from navtech_radar_slam_amd import orora, _rsx
+    L = _rsx.lib()
+    a, b = _common_offsets(synth.orora_pairs(41, 3, k_range=(40, 80)), synth.orora_pairs(42, 3, k_range=(40, 80)))
+    assert np.array_equal(a[2], b[2]) and not np.array_equal(a[0], b[0])
+    n, m = 3, int(a[2][-1])
+    plain, pmc = orora.default_params(), orora.default_params()
+    pmc.flags |= _rsx.ORORA_PMC
+
+    def register(batch, p):
+        out = np.full(n, 7, dtype=_rsx.ORORA_RESULT_DTYPE)
+        st = L.rsx_orora_register_batch(reg._h, batch[0].ctypes.data, batch[1].ctypes.data, batch[2].ctypes.data, n, C.byref(p), out.ctypes.data)
+        return st, out.tobytes()
+
+    def clique(batch, p):
+        member = np.full(m, SENTINEL, dtype=np.uint8)
+        info = np.full(n, 7, dtype=_rsx.PMC_INFO_DTYPE)
+        st = L.rsx_orora_max_clique_batch(reg._h, batch[0].ctypes.data, batch[1].ctypes.data, batch[2].ctypes.data, n, C.byref(p), member.ctypes.data,
+                                          info.ctypes.data)
+        return st, member.tobytes() + info.tobytes()
+
+    def race(jobs):
+        want = [call(batch, p) for call, batch, p in jobs]      # alone, before the threads start
+        assert all(w[0] == 0 for w in want)
+        wrong = [[] for _ in jobs]
+        start = threading.Barrier(len(jobs))
+
+        def run(i):
+            call, batch, p = jobs[i]
+            try:
+                start.wait()
+                for c in range(200):
+                    if call(batch, p) != want[i]:
+                        wrong[i].append(c)
+            except Exception as e:  # noqa: BLE001
+                wrong[i].append(repr(e))
+        threads = [threading.Thread(target=run, args=(i,)) for i in range(len(jobs))]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert wrong == [[] for _ in jobs], [w[:5] for w in wrong]
+        return want
+
+    want = race([(register, a, plain), (register, b, plain)])
+    assert want[0] != want[1]                                   # a mix-up would show
+    want = race([(clique, a, plain), (clique, b, plain)])
+    assert want[0] != want[1]
+    race([(register, a, pmc), (clique, b, plain)])
 
 
 # ---- one handle, three streams ----

@@ -182,6 +182,18 @@ def test_bad_arguments(est):
         with pytest.raises(_rsx.RsxError):
             est.estimate_batch(src, dst, np.array(bad, dtype=np.int64))
     L = _rsx.lib()
+    # offsets that decrease in the middle, or go negative: refused before anything is written
+    s3, d3, o3, _ = synth.orora_pairs(12, 3, k_range=(40, 80))
+    m = int(o3[-1])
+    res, inl = np.full(3, 7, dtype=_rsx.RANSAC_RESULT_DTYPE), np.full(m, 0xA5, dtype=np.uint8)
+    for bad in ([0, 60, 40, m], [0, -1, 40, m], [0, 40, 60, -1]):
+        bad = np.array(bad, dtype=np.int64)
+        assert L.rsx_ransac_estimate_batch(est._h, s3.ctypes.data, d3.ctypes.data, None, bad.ctypes.data, 3, None, res.ctypes.data, inl.ctypes.data) == -1
+        assert b"offsets" in L.rsx_last_error_string(), bad
+    assert (res.view(np.uint8) == np.full(3, 7, dtype=_rsx.RANSAC_RESULT_DTYPE).view(np.uint8)).all() and (inl == 0xA5).all()
+    assert L.rsx_ransac_estimate_batch(est._h, s3.ctypes.data, d3.ctypes.data, None, o3.ctypes.data, 3, None, res.ctypes.data, inl.ctypes.data) == 0
+    want, wmask = est.estimate_batch(s3, d3, o3)
+    assert res.tobytes() == want.tobytes() and np.array_equal(inl.astype(bool), wmask.astype(bool)) and np.all(res["status"] == 0)
     assert L.rsx_ransac_estimate_batch(None, None, None, None, None, 1, None, None, None) == -1
     assert L.rsx_ransac_estimate_batch_device(None, None, None, None, None, 1, None, None, None, None) == -1
     assert L.rsx_ransac_default_params(None) == -1 and L.rsx_ransac_create(0, None) == -1
