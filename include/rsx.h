@@ -15,6 +15,8 @@
  *     handle's GPU and are used asynchronously on the given hipStream_t (passed as void*).
  *     A NULL stream selects the handle's own private (non-blocking) stream, NOT the legacy default
  *     stream: callers that mix several handles or other GPU work must pass one explicit stream.
+ *     (The rsx_sc device entries start a NULL-stream call behind what the legacy default stream holds at the call, so that
+ *     buffers a framework filled on its default stream are complete; nothing orders the legacy stream behind the library.)
  *     Calls on ONE handle that pass different streams are ordered by the library (the handle's workspaces are shared: a call
  *     arriving on another stream than the previous call makes its stream wait for everything enqueued on the old one).
  *     The one exemption is rsx_ransac_estimate_batch_device, which uses no workspace of its handle.
@@ -588,6 +590,58 @@ int rsx_cen2018_extract_batch_device(rsx_cen2018 *h, const uint8_t *d_imgs, int3
                                      int32_t row_stride, int32_t col_offset, const rsx_cen2018_params *params, const float *d_azimuths,
                                      int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                      int32_t *d_counts, void *stream);
+
+/* ============================== radar scan context ====================================
+ * The "radar scan context" of the MulRan paper (Kim et al., ICRA 2020; reference README.md:28-29): the 20 x 60 polar grid
+ * of the ScanContext descriptor filled with received power straight from the polar image -- dense where the descriptors of
+ * the z = 0 keypoint cloud are binary, no keypoint extractor involved.  MulRan's own builder is not part of the reference
+ * checkout: the rule below is restated in tests/radarsc_np.py, which is the arithmetic contract -- parity unpinned.
+ *   ring    of range bin j (SC.cpp:175,178, fp64): r = (j + 0.5) * (double)resolution; none when j < min_range or
+ *           r > max_radius, else max(min(20, (int)ceil(r / max_radius * 20)), 1) - 1
+ *   sector  of azimuth row a (SC.cpp:179, fp64): th = (double)az[a] * 57.29577951308232, t = th / 360 - floor(th / 360),
+ *           max(min(60, (int)ceil(t * 60)), 1) - 1; none when az[a] is not finite.  The grid need not increase or lie in
+ *           [0, 2 pi)
+ *   sample  v = max(p - power_floor, 0) on integers
+ *   cell    RSX_RADARSC_MEAN: (float)((double)sum / (double)count) over every sample of the cell (integer sum), 0 when empty;
+ *           RSX_RADARSC_MAX: (float)max, 0 when empty
+ * Integer sums: a descriptor does not depend on the order of the reduction and equals the restatement bit for bit.
+ * Output: "f32 sector-major", 1200 floats per scan -- what rsx_sc_add_descriptors_f32_device and rsx_sc_query_device take.
+ * One launch per batch; per 400 x 3360 scan the kernel reads the 0.51 MB between min_range and the last bin inside
+ * max_radius and writes 4.8 kB.  Image and azimuth arguments as for rsx_cen2019_extract_batch; the azimuths are required. */
+
+typedef struct rsx_radarsc rsx_radarsc;
+
+#define RSX_RADARSC_MEAN 0
+#define RSX_RADARSC_MAX 1
+
+typedef struct {
+  double max_radius;   /* outer edge of ring 19 [m] (80: SC.h:87 PC_MAX_RADIUS); positive, finite */
+  float resolution;    /* metres per range bin (0.0595); positive */
+  int32_t min_range;   /* first range bin used (58); >= 0 */
+  int32_t power_floor; /* subtracted from every sample, clamped at 0 (0); 0 .. 255 */
+  int32_t stat;        /* RSX_RADARSC_MEAN (default) or RSX_RADARSC_MAX */
+} rsx_radarsc_params;
+
+int rsx_radarsc_default_params(rsx_radarsc_params *p);
+/* one handle per image shape (rows 1 .. 4096 azimuths x cols 1 .. 8192 range bins) and parameter set (NULL: the defaults);
+ * anything else is RSX_ERR_BAD_ARG */
+int rsx_radarsc_create(int device, int32_t rows, int32_t cols, const rsx_radarsc_params *params, rsx_radarsc **out);
+int rsx_radarsc_destroy(rsx_radarsc *h);
+/* n_images host images -> out_descs [n_images][1200].  Synchronous. */
+int rsx_radarsc_build_batch(rsx_radarsc *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                            int32_t col_offset, const float *azimuths, int32_t azimuths_per_image, float *out_descs);
+/* device buffers, asynchronous on `stream`: one launch, no host synchronisation, the (per-image) grids are read on the
+ * device.  Only bytes inside each image's rows x row_stride bytes are read, whatever the alignment of d_imgs. */
+int rsx_radarsc_build_batch_device(rsx_radarsc *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                                   int32_t col_offset, const float *d_azimuths, int32_t azimuths_per_image, float *d_descs, void *stream);
+/* build + insert without leaving the GPU: the descriptors of n_images device images become the next n_images keyframes of
+ * the database (a sharded handle keeps those of its residue class; every rank calls this with every scan, as for
+ * rsx_sc_add_points).  Both handles on the same device. */
+int rsx_sc_add_polar_batch_device(rsx_sc *h, rsx_radarsc *rc, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes,
+                                  int32_t row_stride, int32_t col_offset, const float *d_azimuths, int32_t azimuths_per_image, void *stream);
+/* one host image (rows x row_stride bytes) and its grid (rows floats); out_index (optional) = its global keyframe index */
+int rsx_sc_add_polar(rsx_sc *h, rsx_radarsc *rc, const uint8_t *img, int32_t row_stride, int32_t col_offset, const float *azimuths,
+                     int32_t *out_index);
 
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;

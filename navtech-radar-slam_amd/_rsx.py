@@ -106,6 +106,14 @@ class Cen2018Params(C.Structure):
     _fields_ = [("zq", C.c_float), ("sigma_gauss", C.c_int32), ("min_range", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RadarScParams(C.Structure):
+    _fields_ = [("max_radius", C.c_double), ("resolution", C.c_float), ("min_range", C.c_int32), ("power_floor", C.c_int32),
+                ("stat", C.c_int32)]
+
+
+RADARSC_MEAN, RADARSC_MAX = 0, 1  # rsx_radarsc_params.stat
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -172,6 +180,8 @@ SYMBOLS = [
     "rsx_cen2019_extract_batch", "rsx_cen2019_extract_batch_device",
     "rsx_cen2018_default_params", "rsx_cen2018_create", "rsx_cen2018_destroy", "rsx_cen2018_extract",
     "rsx_cen2018_extract_batch", "rsx_cen2018_extract_batch_device", "rsx_cen2018_gauss_weights", "rsx_cen2018_debug_image",
+    "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
+    "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
     "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
     "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
@@ -295,6 +305,13 @@ def lib():
                                                        i32, vp, vp]
         L.rsx_cen2018_gauss_weights.argtypes = [i32, vp, i32]
         L.rsx_cen2018_debug_image.argtypes = [vp, vp, i32, i32, C.POINTER(Cen2018Params), vp, vp, vp, vp]
+        L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
+        L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
+        L.rsx_radarsc_destroy.argtypes = [vp]
+        L.rsx_radarsc_build_batch.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, vp]
+        L.rsx_radarsc_build_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, vp, vp]
+        L.rsx_sc_add_polar_batch_device.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, i32, vp]
+        L.rsx_sc_add_polar.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(i32)]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
         L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]

@@ -15,6 +15,7 @@
 #include "sc_plan.h"
 #include "sc_kdtree.h"
 #include "loopverify.h"
+#include "radarsc.h"
 #include "voxelgrid.h"
 
 namespace rsx {
@@ -94,6 +95,7 @@ struct rsx_sc {
   // the handle's workspaces (and the single-query path's arrival tickets, which must be zero between launches) are shared by
   // every call: when a call arrives on another stream than the previous one, the new stream is ordered behind the old
   StreamOrder order;
+  Event legacy_ev;  // use_stream: what the legacy default stream holds when a device entry is called without a stream
   Stream up_stream, stream_b;
   Event up_ev[kMaxPieces], lane_ev;
 };
@@ -110,6 +112,15 @@ int set_device(rsx_sc *h) {
 // the stream a device entry works on: the caller's, ordered behind the inserts still in flight on the handle's own
 int use_stream(rsx_sc *h, void *stream, hipStream_t *s) {
   *s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  if (!stream) {
+    // no stream named: the caller's device buffers may still be in the making on the legacy default stream (a framework's
+    // default stream: torch.zeros for the output, a copy for the queries), which does not order itself against a non-blocking
+    // stream -- and whether the two share a hardware queue, i.e. run in submission order anyway, changes with the streams a
+    // process has created before.  The private stream starts behind what the legacy stream holds now
+    if (!h->legacy_ev) RSX_HIP(h->legacy_ev.create());
+    RSX_HIP(hipEventRecord(h->legacy_ev, nullptr));
+    RSX_HIP(hipStreamWaitEvent(h->stream, h->legacy_ev, 0));
+  }
   if (*s != h->stream && h->last_insert) RSX_HIP(hipStreamWaitEvent(*s, h->last_insert, 0));
   return h->order.enter(*s);
 }
@@ -891,6 +902,41 @@ int rsx_sc_add_descriptors_f32_device(rsx_sc *h, const float *d_descs, int64_t n
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
   return add_f32_locked(h, d_descs, n, true, s);
+} RSX_CATCH_ALL
+
+int rsx_sc_add_polar_batch_device(rsx_sc *h, rsx_radarsc *rc, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes,
+                                  int32_t row_stride, int32_t col_offset, const float *d_azimuths, int32_t azimuths_per_image, void *stream) try {
+  if (!h || !rc || n_images < 0 || (n_images && (!d_imgs || !d_azimuths))) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  if (rsx::rc::device_of(rc) != h->p.device) return fail(RSX_ERR_BAD_ARG, "radar scan-context and ScanContext handles are on different devices");
+  if (n_images == 0) return RSX_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::lock_guard<std::mutex> lkr(rsx::rc::mutex_of(rc));
+  RSX_TRY(set_device(h));
+  hipStream_t s;
+  RSX_TRY(use_stream(h, stream, &s));
+  // the descriptors stay in rc's scratch, which rc orders behind s for its next call
+  const float *d_descs = nullptr;
+  RSX_TRY(rsx::rc::build_scratch_device(rc, d_imgs, n_images, image_stride_bytes, row_stride, col_offset, d_azimuths, azimuths_per_image, s, &d_descs));
+  return add_f32_locked(h, d_descs, n_images, true, s);
+} RSX_CATCH_ALL
+
+int rsx_sc_add_polar(rsx_sc *h, rsx_radarsc *rc, const uint8_t *img, int32_t row_stride, int32_t col_offset, const float *azimuths,
+                     int32_t *out_index) try {
+  if (!h || !rc || !img || !azimuths) return fail(RSX_ERR_BAD_ARG, "null arg");
+  if (rsx::rc::device_of(rc) != h->p.device) return fail(RSX_ERR_BAD_ARG, "radar scan-context and ScanContext handles are on different devices");
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::lock_guard<std::mutex> lkr(rsx::rc::mutex_of(rc));
+  RSX_TRY(own_stream(h));
+  const int64_t g = h->n_global;
+  if (owns(h, g)) {
+    const float *d_desc = nullptr;
+    RSX_TRY(rsx::rc::upload_and_build(rc, img, row_stride, col_offset, azimuths, h->stream, &d_desc));
+    RSX_TRY(add_f32_locked(h, d_desc, 1, true, h->stream));  // (synchronises: img and azimuths are free again)
+  } else {
+    h->n_global = g + 1;
+  }
+  if (out_index) *out_index = (int32_t)g;
+  return RSX_OK;
 } RSX_CATCH_ALL
 
 int rsx_sc_export_descriptors_f32(rsx_sc *h, int64_t first_slot, int64_t count, float *out) try {

@@ -29,6 +29,9 @@
 // during the scan and / or the Doppler range shift: every pair is estimated, its matches compensated with that estimate and
 // estimated again, and the published cloud is the compensated one (upstream's deskewing / Doppler switches:
 // rsx_odometry_set_compensation, windowed path only, with orora and ransac).
+// `--radar-context FILE` (with `--rc-floor`, `--rc-stat mean|max`, `--rc-max-radius`; windowed path only) also builds the radar scan
+// context of every scan -- the 20 x 60 grid of received power, rsx_radarsc_build_batch on the window handed to
+// rsx_odometry_push -- into a ScanContext database and writes it to FILE (rsx_sc_save) at the end.
 //
 // Output: one line per frame on stdout / --out file:  stamp_ns x y yaw n_keypoints n_matches
 // With -DRSX_WITH_ROS (ROS 1 present) the same data is also published on /orora/odom and
@@ -145,6 +148,9 @@ int main(int argc, char **argv) {
     std::string compensate;
     rsx_mocomp_params mcp;
     rsx_mocomp_default_params(&mcp);
+    std::string rc_path, rc_stat = "mean";
+    rsx_radarsc_params rcp;
+    rsx_radarsc_default_params(&rcp);
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       if (a == "--out" && i + 1 < argc) out_path = argv[++i];
@@ -163,6 +169,10 @@ int main(int argc, char **argv) {
       else if (a == "--scan-period" && i + 1 < argc) rsp.dt_scan = std::atof(argv[++i]);               // mcransac: seconds per scan (0.25)
       else if (a == "--compensate" && i + 1 < argc) compensate = argv[++i];       // motion | doppler | both (default: none)
       else if (a == "--doppler-beta" && i + 1 < argc) mcp.beta = std::atof(argv[++i]);  // Doppler range shift per radial velocity [s] (0.049)
+      else if (a == "--radar-context" && i + 1 < argc) rc_path = argv[++i];       // write the scans' radar scan contexts to this database file
+      else if (a == "--rc-floor" && i + 1 < argc) rcp.power_floor = std::atoi(argv[++i]);  // radar context: power subtracted from every sample (0)
+      else if (a == "--rc-stat" && i + 1 < argc) rc_stat = argv[++i];             // radar context: mean (default) | max
+      else if (a == "--rc-max-radius" && i + 1 < argc) rcp.max_radius = std::atof(argv[++i]);  // radar context: outer ring edge [m] (80)
       else if (a == "--no-pmc") use_pmc = false;                                   // skip the max-clique inlier selection before the solver
       else if (a == "--exact-clique") exact_clique = true;                        // RSX_ORORA_PMC_EXACT: the selection returns a maximum clique
       else if (a == "--per-scan") per_scan = true;                                // the round-2 loop: one scan per call, host vectors in between
@@ -178,7 +188,7 @@ int main(int argc, char **argv) {
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018] [--zq Z] [--sigma-gauss S] [--window W] [--threads T] "
           "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
-          "[--exact-clique] [--timing]");
+          "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";
     std::vector<std::string> files;
@@ -280,6 +290,12 @@ int main(int argc, char **argv) {
       mcp.flags = compensate == "motion" ? RSX_MOCOMP_DESKEW : compensate == "doppler" ? RSX_MOCOMP_DOPPLER : RSX_MOCOMP_DESKEW | RSX_MOCOMP_DOPPLER;
       mcp.dt_scan = rsp.dt_scan;
     }
+    if (!rc_path.empty()) {
+      if (rc_stat != "mean" && rc_stat != "max") die("--rc-stat must be mean or max");
+      if (matcher != "orb" || per_scan) die("--radar-context runs on the windowed path only (not with --per-scan / --matcher nn)");
+      rcp.stat = rc_stat == "max" ? RSX_RADARSC_MAX : RSX_RADARSC_MEAN;
+      rcp.resolution = kResolution;
+    }
 
     if (matcher == "orb" && !per_scan) {
       // ---------------- windows of scans through rsx_odometry_push ----------------
@@ -301,6 +317,16 @@ int main(int argc, char **argv) {
       if (estimator != "orora")
         check(rsx_odometry_set_estimator(odo, estimator == "ransac" ? RSX_ESTIMATOR_RANSAC : RSX_ESTIMATOR_MCRANSAC, &rsp), "rsx_odometry_set_estimator");
       if (!compensate.empty()) check(rsx_odometry_set_compensation(odo, &mcp), "rsx_odometry_set_compensation");
+      rsx_radarsc *rctx = nullptr;
+      rsx_sc *rc_db = nullptr;
+      std::vector<float> rc_descs;
+      if (!rc_path.empty()) {
+        check(rsx_radarsc_create(device, rows, cols, &rcp, &rctx), "rsx_radarsc_create");
+        rsx_sc_params sp;
+        check(rsx_sc_default_params(&sp), "rsx_sc_default_params");
+        sp.device = device;
+        check(rsx_sc_create(&sp, &rc_db), "rsx_sc_create");
+      }
       // scans per rsx_odometry_push: two of the library's internal windows, so that inside a call the upload and the extraction of
       // the second overlap the matching of the first (the pinned buffers are 2 x W images)
       const int W = window > 0 ? std::min(window, 4096) : 2 * rsx_odometry_window();
@@ -435,6 +461,11 @@ int main(int argc, char **argv) {
         const auto tp = clk::now();
         check(rsx_odometry_push(odo, wn.img, wn.n, (int64_t)ibytes, w0, wn.az.data(), 1, res.data(), want_xy ? xy.data() : nullptr, max_xy),
               "rsx_odometry_push");
+        if (rctx) {  // the same window once more (a second upload of its images)
+          rc_descs.resize((size_t)wn.n * RSX_SC_DESC_SIZE);
+          check(rsx_radarsc_build_batch(rctx, wn.img, wn.n, (int64_t)ibytes, w0, kMeta, wn.az.data(), 1, rc_descs.data()), "rsx_radarsc_build_batch");
+          check(rsx_sc_add_descriptors_f32(rc_db, rc_descs.data(), wn.n), "rsx_sc_add_descriptors_f32");
+        }
         push_s += std::chrono::duration<double>(clk::now() - tp).count();
         for (int i = 0; i < wn.n; i++, fi++) {
           compose(res[(size_t)i].reg);
@@ -452,7 +483,10 @@ int main(int argc, char **argv) {
                      "pipeline_s=%.4f pipeline_scans_per_s=%.1f total_s=%.4f total_scans_per_s=%.1f\n",
                      files.size(), W, T, decode_cpu, 1e3 * decode_cpu / (double)files.size(), decode_wait, push_s, (double)files.size() / push_s,
                      all_s, (double)files.size() / all_s);
+      if (rc_db) check(rsx_sc_save(rc_db, rc_path.c_str()), "rsx_sc_save");
       for (Win &wn : wins) rsx_host_free_pinned(wn.img);
+      rsx_sc_destroy(rc_db);
+      rsx_radarsc_destroy(rctx);
       rsx_odometry_destroy(odo);
       if (out != stdout) std::fclose(out);
       if (rec) std::fclose(rec);

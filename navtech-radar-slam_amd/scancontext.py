@@ -210,6 +210,22 @@ class SCManager:
     def add_descriptors_device(self, dev_ptr, n, stream=0):
         check(self._L.rsx_sc_add_descriptors_f32_device(self._h, dev_ptr, n, stream))
 
+    def add_polar(self, radar_context, img, azimuths, col_offset=11):
+        """One polar scan (rows, row_stride) uint8 + its grid (rows,) -> its radar scan context becomes the next keyframe
+        (rsx_sc_add_polar); radar_context: navtech_radar_slam_amd.radar_context.RadarContext.  Returns the global index."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        az = np.ascontiguousarray(azimuths, dtype=np.float32)
+        assert img.shape[0] == radar_context.rows and az.shape == (radar_context.rows,)
+        idx = C.c_int32()
+        check(self._L.rsx_sc_add_polar(self._h, radar_context._h, img.ctypes.data, img.shape[1], col_offset, az.ctypes.data, C.byref(idx)))
+        return idx.value
+
+    def add_polar_batch_device(self, radar_context, imgs_ptr, n, image_stride_bytes, row_stride, az_ptr, col_offset=11,
+                               azimuths_per_image=False, stream=0):
+        """n polar scans in device memory -> the next n keyframes, built and inserted on the GPU (rsx_sc_add_polar_batch_device)."""
+        check(self._L.rsx_sc_add_polar_batch_device(self._h, radar_context._h, imgs_ptr, n, image_stride_bytes, row_stride, col_offset,
+                                                    az_ptr, 1 if azimuths_per_image else 0, stream))
+
     def export_descriptors_f32(self, first_slot=0, count=None):
         """f32 sector-major descriptors of local slots [first_slot, first_slot + count) -> (count, 1200)."""
         if count is None:
