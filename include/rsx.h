@@ -591,6 +591,63 @@ int rsx_cen2018_extract_batch_device(rsx_cen2018 *h, const uint8_t *d_imgs, int3
                                      int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                      int32_t *d_counts, void *stream);
 
+/* ============================== k-strongest keypoint extraction ========================
+ * The detector of CFEAR radar odometry (Adolfsson et al.: k = 12, z_min = 60) with a separation rule: on every azimuth the
+ * k strongest returns above a fixed power floor.  No noise model, one read of the image, and a hard budget of rows x k
+ * keypoints per scan.  Not part of the reference; the rule below is restated in tests/kstrongest_np.py, which is the
+ * arithmetic contract.  Integers only: the keypoints equal the restatement's bit for bit.
+ * Per azimuth row, v[j] = the power byte of range bin j, 0 <= j < cols, s = min_separation:
+ *   1. key[j] = (v[j] << 16) | (0xFFFF - j): unique within a row; a higher key is stronger, on equal power the nearer bin wins
+ *   2. win[j] = max key[i] over max(0, j - s) <= i <= min(cols - 1, j + s): the window is cut at the row's ends (it never sees
+ *      metadata bytes, row padding or another row) and runs over raw power whatever z_min / min_range say
+ *   3. bin j is a candidate iff key[j] == win[j], v[j] >= z_min and min_range <= j < hi, hi = cols when max_range == 0, else
+ *      min(max_range, cols)
+ *   4. the row's keypoints are the min(k, #candidates) candidates of highest key, written in ascending j
+ *   5. the image's keypoints are the rows' keypoints in row-major order
+ * So s = 0 is CFEAR's plain rule, and with s > 0 any two keypoints of a row are more than s bins apart.
+ * Why the default is s = 5: the plain rule picks runs of adjacent range bins on a strong reflector.  In the odometry
+ * pipeline a Cartesian pixel is 0.2592 m and a range bin 0.0595 m, so adjacent bins get identical ORB-style descriptors and
+ * the ratio test of knnMatch drops them all.  Measured on the CPU (restatement -> oracle front end -> cross-checked ratio
+ * matches -> max-clique selection -> ORORA; synth.polar_sequence(11, 5), k = 12, z_min = 60; 4800 keypoints per scan with
+ * every rule; every pair status 0):
+ *     min_separation   cross-checked matches per pair   worst pair error
+ *     0 (plain rule)   59 - 73                          0.056 m / 4.1e-3 rad
+ *     1                525 - 715                        0.046 m / 4.2e-3 rad
+ *     5                550 - 722                        0.045 m / 3.9e-3 rad
+ * Same argument shapes, output layout ((azimuth idx, range idx) int32 pairs, x = (r+0.5)*resolution*cos(az), ...) and
+ * truncation rules as the cen2019 group above; *out_count / out_counts report every keypoint found, only the first
+ * max_targets are written.  Parameters out of range return RSX_ERR_BAD_ARG.  Device workspace per handle: rows x k x 2 bytes
+ * of per-row keypoints + rows x 4 bytes of counts per image of a sub-batch (<= 128 images: 1.4 MB for 400 x 3360 scans at
+ * k = 12), plus the host entries' staging (images, keypoints, points of one sub-batch). */
+
+typedef struct rsx_kstrongest rsx_kstrongest;
+
+typedef struct {
+  int32_t k;              /* keypoints per azimuth at most, 1 .. 128 (12) */
+  int32_t z_min;          /* power floor, 0 .. 255 (60) */
+  int32_t min_range;      /* first range bin considered for keypoints, >= 0 (58) */
+  int32_t max_range;      /* one past the last range bin considered, >= 0; 0 = cols (0) */
+  int32_t min_separation; /* s, 0 .. 32; 0 = CFEAR's plain rule (5) */
+  int32_t reserved;       /* 0 */
+} rsx_kstrongest_params;
+
+int rsx_kstrongest_default_params(rsx_kstrongest_params *p);
+/* one handle per image shape: rows (1 .. 4096) azimuths x cols (1 .. 8192) range bins */
+int rsx_kstrongest_create(int device, int32_t rows, int32_t cols, rsx_kstrongest **out);
+int rsx_kstrongest_destroy(rsx_kstrongest *h);
+int rsx_kstrongest_extract(rsx_kstrongest *h, const uint8_t *img, int32_t row_stride, int32_t col_offset,
+                           const rsx_kstrongest_params *params, const float *azimuths, float resolution,
+                           int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_count);
+int rsx_kstrongest_extract_batch(rsx_kstrongest *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                                 int32_t col_offset, const rsx_kstrongest_params *params, const float *azimuths, int32_t azimuths_per_image,
+                                 float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_counts);
+/* two launches per 128 images, no host synchronisation.  Only bytes inside each image's rows x row_stride bytes are read,
+ * whatever the alignment of d_imgs. */
+int rsx_kstrongest_extract_batch_device(rsx_kstrongest *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes,
+                                        int32_t row_stride, int32_t col_offset, const rsx_kstrongest_params *params, const float *d_azimuths,
+                                        int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
+                                        int32_t *d_counts, void *stream);
+
 /* ============================== radar scan context ====================================
  * The "radar scan context" of the MulRan paper (Kim et al., ICRA 2020; reference README.md:28-29): the 20 x 60 polar grid
  * of the ScanContext descriptor filled with received power straight from the polar image -- dense where the descriptors of
@@ -728,7 +785,7 @@ typedef struct {
 typedef struct {
   rsx_orora_result reg;  /* motion between the previous scan and this one: p_previous = R(yaw) p_this + (x, y);
                             reg.status = 3 for the first scan of a sequence (nothing to register against) */
-  int32_t n_keypoints;   /* keypoints of this scan (cen2019, or cen2018: rsx_odometry_set_cen2018; only the first max_keypoints are used) */
+  int32_t n_keypoints;   /* keypoints of this scan (cen2019, or cen2018 / k-strongest: rsx_odometry_set_cen2018 / _set_kstrongest; only the first max_keypoints are used) */
   int32_t n_matches;     /* cross-checked ratio matches handed to ORORA */
 } rsx_odometry_scan;
 
@@ -743,6 +800,11 @@ int rsx_odometry_window(void);           /* scans per internal launch chain (lon
  * the handle holds no scan -- freshly created or after rsx_odometry_reset -- so that no pair is registered from keypoints of
  * two extractors; otherwise RSX_ERR_BAD_ARG.  rsx_odometry_scan.n_keypoints then counts cen2018 keypoints. */
 int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params);
+/* keypoints by k-strongest with these settings (rsx_kstrongest above).  Either setter selects its extractor in place of
+ * whichever was selected, and params = NULL in either goes back to cen2019.  The same rule: only while the handle holds no
+ * scan.  Independent of estimator and compensation.  At most rows x k keypoints per scan, of which the first max_keypoints
+ * are used. */
+int rsx_odometry_set_kstrongest(rsx_odometry *h, const rsx_kstrongest_params *params);
 /* The motion estimator a pair's cross-checked matches go to: ORORA behind the max-clique selection (the default), rigid
  * RANSAC or motion-compensated RANSAC (params = NULL: rsx_ransac_default_params; its MOTION_COMPENSATED flag follows
  * `estimator`).  Independent of the extractor; like it, only accepted while the handle holds no scan.  With a RANSAC

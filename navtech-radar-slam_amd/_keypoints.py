@@ -1,4 +1,4 @@
-"""What the host-side wrappers of the keypoint extractors (cen2018.Cen2018, cen2019.Cen2019) share: the handle and the
+"""What the host-side wrappers of the keypoint extractors (cen2018.Cen2018, cen2019.Cen2019, kstrongest.KStrongest) share: the handle and the
 calls of rsx_<name>_extract / rsx_<name>_extract_batch with their output arrays."""
 import ctypes as C
 

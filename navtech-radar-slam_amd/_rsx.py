@@ -106,6 +106,11 @@ class Cen2018Params(C.Structure):
     _fields_ = [("zq", C.c_float), ("sigma_gauss", C.c_int32), ("min_range", C.c_int32), ("reserved", C.c_int32)]
 
 
+class KStrongestParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("z_min", C.c_int32), ("min_range", C.c_int32), ("max_range", C.c_int32),
+                ("min_separation", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RadarScParams(C.Structure):
     _fields_ = [("max_radius", C.c_double), ("resolution", C.c_float), ("min_range", C.c_int32), ("power_floor", C.c_int32),
                 ("stat", C.c_int32)]
@@ -180,6 +185,8 @@ SYMBOLS = [
     "rsx_cen2019_extract_batch", "rsx_cen2019_extract_batch_device",
     "rsx_cen2018_default_params", "rsx_cen2018_create", "rsx_cen2018_destroy", "rsx_cen2018_extract",
     "rsx_cen2018_extract_batch", "rsx_cen2018_extract_batch_device", "rsx_cen2018_gauss_weights", "rsx_cen2018_debug_image",
+    "rsx_kstrongest_default_params", "rsx_kstrongest_create", "rsx_kstrongest_destroy", "rsx_kstrongest_extract",
+    "rsx_kstrongest_extract_batch", "rsx_kstrongest_extract_batch_device", "rsx_odometry_set_kstrongest",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
@@ -305,6 +312,14 @@ def lib():
                                                        i32, vp, vp]
         L.rsx_cen2018_gauss_weights.argtypes = [i32, vp, i32]
         L.rsx_cen2018_debug_image.argtypes = [vp, vp, i32, i32, C.POINTER(Cen2018Params), vp, vp, vp, vp]
+        L.rsx_kstrongest_default_params.argtypes = [C.POINTER(KStrongestParams)]
+        L.rsx_kstrongest_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+        L.rsx_kstrongest_destroy.argtypes = [vp]
+        L.rsx_kstrongest_extract.argtypes = [vp, vp, i32, i32, C.POINTER(KStrongestParams), vp, C.c_float, vp, vp, i32, C.POINTER(i32)]
+        L.rsx_kstrongest_extract_batch.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(KStrongestParams), vp, i32, C.c_float, vp, vp, i32, vp]
+        L.rsx_kstrongest_extract_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(KStrongestParams), vp, i32, C.c_float, vp, vp,
+                                                          i32, vp, vp]
+        L.rsx_odometry_set_kstrongest.argtypes = [vp, C.POINTER(KStrongestParams)]
         L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
         L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
         L.rsx_radarsc_destroy.argtypes = [vp]

@@ -1,4 +1,4 @@
-// keypoints_host.h -- what the keypoint extractors (cen2018.hip, cen2019.hip) and the odometry share: the check of a polar image
+// keypoints_host.h -- what the keypoint extractors (cen2018.hip, cen2019.hip, kstrongest.hip) and the odometry share: the check of a polar image
 // layout, the image upload, the kernel that packs the per-row keypoints, and the host path of rsx_cen201x_extract_batch.
 #pragma once
 #include <hip/hip_runtime.h>

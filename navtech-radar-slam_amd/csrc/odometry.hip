@@ -6,7 +6,8 @@
 // translation) -> pose composition.  The sequence is on disk, so every scan and every consecutive pair is independent
 // until the final composition: a WINDOW of n scans goes through each stage in ONE launch chain --
 //     rsx_cen2019_extract_batch_device          n images   (csrc/cen2019.hip; or rsx_cen2018_extract_batch_device, csrc/cen2018.hip,
-//                                               after rsx_odometry_set_cen2018)
+//                                               after rsx_odometry_set_cen2018; or rsx_kstrongest_extract_batch_device,
+//                                               csrc/kstrongest.hip, after rsx_odometry_set_kstrongest)
 //     rsx_frontend_cartesian_batch_device       n images   (csrc/frontend.hip)
 //     rsx_frontend_describe_batch_device        n keypoint sets
 //     rsx_frontend_match_consecutive_device     all consecutive pairs, both directions
@@ -30,6 +31,7 @@
 
 #include "cen2018.h"
 #include "keypoints_host.h"
+#include "kstrongest.h"
 #include "mocomp.h"
 #include "ransac.h"
 
@@ -211,6 +213,9 @@ struct rsx_odometry {
   rsx::Owned<rsx_cen2018, rsx_cen2018_destroy> cen18[N_LANES];  // created at the first rsx_odometry_set_cen2018
   bool use_cen2018 = false;
   rsx_cen2018_params cen18_prm{};
+  rsx::Owned<rsx_kstrongest, rsx_kstrongest_destroy> kstr[N_LANES];  // created at the first rsx_odometry_set_kstrongest
+  bool use_kstrongest = false;  // (never together with use_cen2018)
+  rsx_kstrongest_params kstr_prm{};
   rsx::Owned<rsx_frontend, rsx_frontend_destroy> fe[N_LANES];
   rsx::Owned<rsx_orora, rsx_orora_destroy> reg;
   int estimator = RSX_ESTIMATOR_ORORA;
@@ -267,7 +272,7 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
   return RSX_OK;
 }
 
-// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through cen2019 (or cen2018), the Cartesian images and the
+// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through cen2019 (or cen2018, or k-strongest), the Cartesian images and the
 // descriptors into set g % 3, then its last scan into slot 0 of the next set.  Asynchronous on the stream of lane g & 1.
 int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, int64_t img_stride, int32_t row_stride, const float *azimuths,
                     int32_t azimuths_per_image) {
@@ -288,8 +293,9 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
     return extract_batch_device(cen, d_imgs, n, img_stride, row_stride, h->prm.col_offset, prm, q.az.as<float>(), azimuths_per_image,
                                 h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy, q.xy.as<float>() + slot_xy, K, d_counts + 1, s);
   };
-  RSX_TRY(h->use_cen2018 ? keypoints(rsx_cen2018_extract_batch_device, h->cen18[lane].get(), &h->cen18_prm)
-                         : keypoints(rsx_cen2019_extract_batch_device, h->cen[lane].get(), &h->prm.cen));
+  RSX_TRY(h->use_kstrongest ? keypoints(rsx_kstrongest_extract_batch_device, h->kstr[lane].get(), &h->kstr_prm)
+          : h->use_cen2018  ? keypoints(rsx_cen2018_extract_batch_device, h->cen18[lane].get(), &h->cen18_prm)
+                            : keypoints(rsx_cen2019_extract_batch_device, h->cen[lane].get(), &h->prm.cen));
   // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
   // how the sequence is cut into windows, and nothing about the grids is looked at on the host
   RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
@@ -553,7 +559,7 @@ int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params) 
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one pair, one extractor)");
   if (!params) {
-    h->use_cen2018 = false;
+    h->use_cen2018 = h->use_kstrongest = false;
     return RSX_OK;
   }
   RSX_TRY(rsx::cen2018_check_params(*params));
@@ -565,6 +571,28 @@ int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params) 
   }
   h->cen18_prm = *params;
   h->use_cen2018 = true;
+  h->use_kstrongest = false;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_odometry_set_kstrongest(rsx_odometry *h, const rsx_kstrongest_params *params) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one pair, one extractor)");
+  if (!params) {
+    h->use_cen2018 = h->use_kstrongest = false;
+    return RSX_OK;
+  }
+  RSX_TRY(rsx::kstrongest_check_params(*params));
+  for (int l = 0; l < N_LANES; l++) {
+    if (h->kstr[l]) continue;
+    rsx_kstrongest *c = nullptr;
+    RSX_TRY(rsx_kstrongest_create(h->device, h->rows, h->cols, &c));
+    h->kstr[l].reset(c);
+  }
+  h->kstr_prm = *params;
+  h->use_kstrongest = true;
+  h->use_cen2018 = false;
   return RSX_OK;
 } RSX_CATCH_ALL
 

@@ -22,6 +22,8 @@
 // `--matcher nn` selects the round-1 stand-in instead (mutual nearest neighbours in the sensor frame, no descriptors).
 // `--keypoints cen2018` (with `--zq`, `--sigma-gauss`; min_range stays 58) finds the keypoints with cen2018 instead of cen2019
 // (upstream's keypoint_extraction = 0: rsx_odometry_set_cen2018 on the windowed path, rsx_cen2018_extract on --per-scan).
+// `--keypoints kstrongest` (with `--k`, `--z-min`, `--min-separation`; min_range stays 58) keeps on every azimuth the k strongest
+// returns above a power floor (rsx_odometry_set_kstrongest on the windowed path, rsx_kstrongest_extract on --per-scan).
 // `--estimator ransac|mcransac` (with `--ransac-threshold`, `--ransac-iterations`, `--scan-period`) hands a pair's matches to
 // rigid RANSAC or motion-compensated RANSAC instead of the max-clique selection + ORORA (upstream's other estimators:
 // rsx_odometry_set_estimator, windowed path only; mcransac takes a match's time from the azimuth rows of its keypoints).
@@ -143,6 +145,8 @@ int main(int argc, char **argv) {
     float gate = 6.0f;
     rsx_cen2018_params c18;
     rsx_cen2018_default_params(&c18);
+    rsx_kstrongest_params ksp;
+    rsx_kstrongest_default_params(&ksp);
     rsx_ransac_params rsp;
     rsx_ransac_default_params(&rsp);
     std::string compensate;
@@ -160,9 +164,12 @@ int main(int argc, char **argv) {
       else if (a == "--matcher" && i + 1 < argc) matcher = argv[++i];  // orb (default) | nn
       else if (a == "--window" && i + 1 < argc) window = std::atoi(argv[++i]);    // scans per rsx_odometry_push (default: two of the library's windows)
       else if (a == "--threads" && i + 1 < argc) threads = std::atoi(argv[++i]);  // PNG decode threads (default: twice the usable cores, <= 64)
-      else if (a == "--keypoints" && i + 1 < argc) keypoints = argv[++i];         // cen2019 (default) | cen2018
+      else if (a == "--keypoints" && i + 1 < argc) keypoints = argv[++i];         // cen2019 (default) | cen2018 | kstrongest
       else if (a == "--zq" && i + 1 < argc) c18.zq = (float)std::atof(argv[++i]);  // cen2018: threshold in noise sigmas (3.0)
       else if (a == "--sigma-gauss" && i + 1 < argc) c18.sigma_gauss = std::atoi(argv[++i]);  // cen2018: Gaussian sigma in range bins, odd (17)
+      else if (a == "--k" && i + 1 < argc) ksp.k = std::atoi(argv[++i]);          // kstrongest: keypoints per azimuth at most (12)
+      else if (a == "--z-min" && i + 1 < argc) ksp.z_min = std::atoi(argv[++i]);  // kstrongest: power floor (60)
+      else if (a == "--min-separation" && i + 1 < argc) ksp.min_separation = std::atoi(argv[++i]);  // kstrongest: range bins between two keypoints of an azimuth (5)
       else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac
       else if (a == "--ransac-threshold" && i + 1 < argc) rsp.tolerance = std::atof(argv[++i]);        // inlier residual bound [m] (0.35)
       else if (a == "--ransac-iterations" && i + 1 < argc) rsp.max_iterations = std::atoi(argv[++i]);  // hypotheses (100)
@@ -186,7 +193,7 @@ int main(int argc, char **argv) {
     }
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
-      die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018] [--zq Z] [--sigma-gauss S] [--window W] [--threads T] "
+      die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--window W] [--threads T] "
           "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
           "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
@@ -279,8 +286,8 @@ int main(int argc, char **argv) {
       pyaw += r.yaw;
     };
     if (matcher != "nn" && matcher != "orb") die("--matcher must be orb or nn");
-    if (keypoints != "cen2019" && keypoints != "cen2018") die("--keypoints must be cen2019 or cen2018");
-    const bool use_c18 = keypoints == "cen2018";
+    if (keypoints != "cen2019" && keypoints != "cen2018" && keypoints != "kstrongest") die("--keypoints must be cen2019, cen2018 or kstrongest");
+    const bool use_c18 = keypoints == "cen2018", use_ks = keypoints == "kstrongest";
     if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac") die("--estimator must be orora, ransac or mcransac");
     if (estimator != "orora" && (matcher != "orb" || per_scan)) die("--estimator " + estimator + " runs on the windowed path only (not with --per-scan / --matcher nn)");
     if (!compensate.empty()) {
@@ -314,6 +321,7 @@ int main(int argc, char **argv) {
       rsx_odometry *odo = nullptr;
       check(rsx_odometry_create(&op, rows, cols, &odo), "rsx_odometry_create");
       if (use_c18) check(rsx_odometry_set_cen2018(odo, &c18), "rsx_odometry_set_cen2018");
+      if (use_ks) check(rsx_odometry_set_kstrongest(odo, &ksp), "rsx_odometry_set_kstrongest");
       if (estimator != "orora")
         check(rsx_odometry_set_estimator(odo, estimator == "ransac" ? RSX_ESTIMATOR_RANSAC : RSX_ESTIMATOR_MCRANSAC, &rsp), "rsx_odometry_set_estimator");
       if (!compensate.empty()) check(rsx_odometry_set_compensation(odo, &mcp), "rsx_odometry_set_compensation");
@@ -496,6 +504,7 @@ int main(int argc, char **argv) {
     // ---------------- one scan per call (round-2 loop; also the `nn` stand-in matcher) ----------------
     rsx_cen2019 *cen = nullptr;
     rsx_cen2018 *cen18 = nullptr;
+    rsx_kstrongest *kstr = nullptr;
     rsx_orora *reg = nullptr;
     rsx_frontend *fe = nullptr;
     const bool use_orb = matcher != "nn";
@@ -509,10 +518,11 @@ int main(int argc, char **argv) {
     for (size_t fi = 0; fi < files.size(); fi++) {
       int w = 0, h = 0;
       const std::vector<uint8_t> img = read_png_gray8(dir + "/" + files[fi], &w, &h);
-      if (!cen && !cen18) {
+      if (!cen && !cen18 && !kstr) {
         rows = h;
         cols = w - kMeta;
-        if (use_c18) check(rsx_cen2018_create(device, rows, cols, &cen18), "rsx_cen2018_create");
+        if (use_ks) check(rsx_kstrongest_create(device, rows, cols, &kstr), "rsx_kstrongest_create");
+        else if (use_c18) check(rsx_cen2018_create(device, rows, cols, &cen18), "rsx_cen2018_create");
         else check(rsx_cen2019_create(device, rows, cols, &cen), "rsx_cen2019_create");
         if (use_orb) check(rsx_frontend_create(device, rows, cols, nullptr, &fe), "rsx_frontend_create");
         az.resize((size_t)rows);
@@ -528,7 +538,10 @@ int main(int argc, char **argv) {
         az[(size_t)a] = (float)((double)cnt * 2.0 * M_PI / 5600.0);
       }
       int32_t n = 0;
-      if (use_c18)
+      if (use_ks)
+        check(rsx_kstrongest_extract(kstr, img.data(), w, kMeta, &ksp, az.data(), kResolution, targets.data(), xy.data(), 200000, &n),
+              "rsx_kstrongest_extract");
+      else if (use_c18)
         check(rsx_cen2018_extract(cen18, img.data(), w, kMeta, &c18, az.data(), kResolution, targets.data(), xy.data(), 200000, &n),
               "rsx_cen2018_extract");
       else
@@ -596,6 +609,7 @@ int main(int argc, char **argv) {
     if (rec) std::fclose(rec);
     rsx_cen2019_destroy(cen);
     rsx_cen2018_destroy(cen18);
+    rsx_kstrongest_destroy(kstr);
     rsx_orora_destroy(reg);
     rsx_frontend_destroy(fe);
     return 0;

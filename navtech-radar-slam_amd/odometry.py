@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, MocompParams, OdometryParams,
-                   RansacParams, check, lib)
+from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, KStrongestParams, MocompParams,
+                   OdometryParams, RansacParams, check, lib)
 
 ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_*
 COMPENSATIONS = {"motion": MOCOMP_DESKEW, "doppler": MOCOMP_DOPPLER, "both": MOCOMP_DESKEW | MOCOMP_DOPPLER}  # rsx_mocomp_params.flags
@@ -18,7 +18,8 @@ def default_params():
 
 
 class Odometry:
-    """keypoints: "cen2019" (default) or "cen2018"; cen2018: its Cen2018Params (None: cen2018.default_params()).
+    """keypoints: "cen2019" (default), "cen2018" or "kstrongest"; cen2018: its Cen2018Params (None: cen2018.default_params());
+    kstrongest: its KStrongestParams (None: kstrongest.default_params()).
     estimator: "orora" (default), "ransac" or "mcransac"; ransac: their RansacParams (None: ransac.default_params()).
     exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT).
     compensate: None (default), "motion", "doppler" or "both": every pair is estimated, its matches compensated with that
@@ -26,9 +27,9 @@ class Odometry:
     the scan period of the model (None: the library's defaults)."""
 
     def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
-                 exact_clique=False, compensate=None, beta=None, dt_scan=None):
-        if keypoints not in ("cen2019", "cen2018"):
-            raise ValueError("keypoints must be cen2019 or cen2018")
+                 exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None):
+        if keypoints not in ("cen2019", "cen2018", "kstrongest"):
+            raise ValueError("keypoints must be cen2019, cen2018 or kstrongest")
         if estimator not in ESTIMATORS:
             raise ValueError("estimator must be orora, ransac or mcransac")
         if compensate is not None and compensate not in COMPENSATIONS:
@@ -45,6 +46,8 @@ class Odometry:
         check(self._L.rsx_odometry_create(C.byref(self.params), rows, cols, C.byref(self._h)))
         if keypoints == "cen2018":
             self.set_cen2018(cen2018)
+        if keypoints == "kstrongest":
+            self.set_kstrongest(kstrongest)
         if estimator != "orora":
             self.set_estimator(estimator, ransac)
         if compensate is not None:
@@ -83,6 +86,17 @@ class Odometry:
         if cen2018 is None:
             check(self._L.rsx_cen2018_default_params(C.byref(p)))
         check(self._L.rsx_odometry_set_cen2018(self._h, C.byref(p)))
+
+    def set_kstrongest(self, kstrongest=None, off=False):
+        """Switch to k-strongest keypoints (kstrongest: KStrongestParams or None for the defaults) in place of whichever extractor
+        was selected, or back to cen2019 with off=True.  Only while the handle holds no scan (fresh, or after reset())."""
+        if off:
+            check(self._L.rsx_odometry_set_kstrongest(self._h, None))
+            return
+        p = kstrongest if kstrongest is not None else KStrongestParams()
+        if kstrongest is None:
+            check(self._L.rsx_kstrongest_default_params(C.byref(p)))
+        check(self._L.rsx_odometry_set_kstrongest(self._h, C.byref(p)))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
