@@ -648,6 +648,96 @@ int rsx_kstrongest_extract_batch_device(rsx_kstrongest *h, const uint8_t *d_imgs
                                         int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                         int32_t *d_counts, void *stream);
 
+/* ============================== CFEAR surface points and registration ==================
+ * What the k-strongest detector feeds in CFEAR radar odometry (Adolfsson et al.): no descriptors and no matcher.  The
+ * filtered returns of a scan are summarised as ORIENTED SURFACE POINTS -- the mean and the surface normal of the returns
+ * within a radius -- and two scans are registered by minimising a robust POINT-TO-LINE cost between their surface points.
+ * CFEAR's own code is not part of the reference checkout: the rules below are restated in tests/cfear_np.py, which is the
+ * arithmetic contract -- parity unpinned.
+ * Surface points of one cloud (n <= RSX_CFEAR_MAX_POINTS points, float x, y, sensor frame), r = radius, all in fp64:
+ *   - cell of a point: ix = floor(x / r), iy = floor(y / r); a point with ix or iy outside [-64, 64) (non-finite included) is
+ *     ignored and sets RSX_CFEAR_STATUS_RANGE (+-224 m at r = 3.5)
+ *   - per occupied cell, in ascending (iy, ix): c = the mean of the cell's own points; the neighbours are the points p of
+ *     the 3 x 3 block of cells with |p - c|^2 <= r^2 (dy outer, dx inner, input order inside a cell); fewer than min_points:
+ *     no surface point; mu = their mean, S = their sample covariance (divided by m - 1); lambda_max/min = h +- sqrt(((sxx -
+ *     syy) / 2)^2 + sxy^2), h = (sxx + syy) / 2; kept iff lambda_min > 0 and lambda_max <= max_condition x lambda_min; the
+ *     normal is the unit eigenvector of lambda_min (from the row of S - lambda_min I with the larger pivot), turned to face
+ *     the sensor (n.mu <= 0)
+ *   - every sum runs sequentially in the order above, nothing is fused: the records equal the restatement's bit for bit.
+ *     Two cells that see the same neighbour set give the same record but for `cell`; both are kept
+ * Registration of a pair (src = the later scan's records, dst = the earlier scan's; dst = R(yaw) src + (x, y), as for
+ * rsx_orora_result), Gauss-Newton from the start pose, per iteration: q = R mu_i + t, m = R n_i; the correspondence of src
+ * record i is the dst record j of smallest |q - mu_j|^2 among those with |q - mu_j|^2 <= radius^2 and m.n_j >=
+ * cos_max_normal_angle (lowest j on a tie; none is allowed); residual e = n_j.(q - mu_j), Huber weight 1 for |e| <=
+ * huber_delta else huber_delta / |e|; the 3 x 3 normal equations are solved by LDL^T without pivoting in the order (x, y,
+ * yaw); the loop ends when the step's norm is < step_epsilon, or at max_iterations.  A pair's result does not depend on its
+ * place in the batch; no host round trip inside the loop. */
+
+typedef struct rsx_cfear rsx_cfear;
+
+#define RSX_CFEAR_MAX_POINTS 16384        /* points of one scan */
+#define RSX_CFEAR_MAX_SURFACE_POINTS 4096 /* records written per scan, and records of one side of a registered pair */
+#define RSX_CFEAR_STATUS_RANGE 1          /* scan status word: some point lay outside the 128 x 128 cell grid (or was not finite) */
+#define RSX_CFEAR_STATUS_POINTS 2         /* scan status word (device entry only): more than RSX_CFEAR_MAX_POINTS points, no record
+                                             (the host entry refuses such a scan with RSX_ERR_BAD_ARG) */
+
+typedef struct {
+  double radius;               /* r: cell side, neighbourhood radius and correspondence radius [m], > 0 (3.5) */
+  double max_condition;        /* lambda_max / lambda_min at most, >= 1 (1e5) */
+  double cos_max_normal_angle; /* correspondences need m.n_j >= this, in [-1, 1] (cos 30 deg) */
+  double huber_delta;          /* [m], > 0 (0.1) */
+  double step_epsilon;         /* the loop ends when |step| < this, >= 0 (1e-6) */
+  int32_t min_points;          /* neighbours a surface point needs, >= 2 (6) */
+  int32_t max_iterations;      /* 1 .. 200 (50) */
+  int32_t min_correspondences; /* >= 1 (6) */
+  int32_t reserved[3];         /* 0 */
+} rsx_cfear_params;
+
+typedef struct {
+  float x, y;                   /* mean of the neighbours */
+  float nx, ny;                 /* unit normal, facing the sensor */
+  float lambda_max, lambda_min; /* eigenvalues of the sample covariance */
+  int32_t n_points;             /* neighbours */
+  int32_t cell;                 /* (iy + 64) * 128 + (ix + 64) */
+} rsx_cfear_surface_point;      /* 32 bytes */
+
+typedef struct {
+  double x, y, yaw;        /* dst = R(yaw) src + (x, y) */
+  double cost;             /* Huber loss of the last linearisation made */
+  int32_t iterations;      /* steps taken */
+  int32_t correspondences; /* of the last linearisation made */
+  int32_t status;          /* 0 ok; 1 a side has no surface points; 2 a side has more than RSX_CFEAR_MAX_SURFACE_POINTS; 4 fewer than
+                              min_correspondences; 5 degenerate normal equations (a pivot not > 1e-12 x its diagonal entry); 8
+                              max_iterations reached (the pose is still returned).  1, 2: the start pose; 4, 5: the pose reached so far */
+  int32_t reserved;
+} rsx_cfear_result;
+
+int rsx_cfear_default_params(rsx_cfear_params *p);
+int rsx_cfear_create(int device, rsx_cfear **out);
+int rsx_cfear_destroy(rsx_cfear *h);
+/* n_scans clouds; scan i owns points [offsets[i], offsets[i + 1]) of xy (float x, y per point); offsets as for
+ * rsx_orora_register_batch (checked), and no scan may hold more than RSX_CFEAR_MAX_POINTS points.  Scan i's records go to
+ * out_records + i * max_records (1 <= max_records <= RSX_CFEAR_MAX_SURFACE_POINTS); out_counts[i] reports every record found,
+ * only the first max_records are written; out_status[i] is the scan's status word (either may be NULL).  Host buffers,
+ * synchronous.  One workgroup per scan, one launch. */
+int rsx_cfear_surface_points_batch(rsx_cfear *h, const float *xy, const int64_t *offsets, int32_t n_scans, const rsx_cfear_params *params,
+                                   rsx_cfear_surface_point *out_records, int32_t max_records, int32_t *out_counts, int32_t *out_status);
+/* device buffers, asynchronous on `stream`, no allocation; d_offsets are trusted (a scan above the cap gets
+ * RSX_CFEAR_STATUS_POINTS and no record).  d_counts is required here */
+int rsx_cfear_surface_points_batch_device(rsx_cfear *h, const float *d_xy, const int64_t *d_offsets, int32_t n_scans,
+                                          const rsx_cfear_params *params, rsx_cfear_surface_point *d_records, int32_t max_records,
+                                          int32_t *d_counts, int32_t *d_status, void *stream);
+/* n_pairs pairs; pair i registers src records [src_offsets[i], src_offsets[i + 1]) to dst records [dst_offsets[i],
+ * dst_offsets[i + 1]); init: [n_pairs][3] doubles x, y, yaw, NULL = identity.  Host buffers, synchronous.  One workgroup per
+ * pair, one launch. */
+int rsx_cfear_register_batch(rsx_cfear *h, const rsx_cfear_surface_point *src, const int64_t *src_offsets,
+                             const rsx_cfear_surface_point *dst, const int64_t *dst_offsets, int32_t n_pairs, const double *init,
+                             const rsx_cfear_params *params, rsx_cfear_result *out);
+/* device buffers (d_init too, or NULL), asynchronous on `stream`, no allocation; the offsets are trusted */
+int rsx_cfear_register_batch_device(rsx_cfear *h, const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets,
+                                    const rsx_cfear_surface_point *d_dst, const int64_t *d_dst_offsets, int32_t n_pairs,
+                                    const double *d_init, const rsx_cfear_params *params, rsx_cfear_result *d_out, void *stream);
+
 /* ============================== radar scan context ====================================
  * The "radar scan context" of the MulRan paper (Kim et al., ICRA 2020; reference README.md:28-29): the 20 x 60 polar grid
  * of the ScanContext descriptor filled with received power straight from the polar image -- dense where the descriptors of
@@ -831,6 +921,19 @@ int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_
  * uncompensated when that pair's status != 0 and for the first scan of a sequence); what is matched and carried to the next
  * window stays uncompensated.  Results do not depend on how the sequence is cut into calls. */
 int rsx_odometry_set_compensation(rsx_odometry *h, const rsx_mocomp_params *params);
+/* CFEAR's own pipeline (rsx_cfear above) in place of the descriptors, the matcher and the estimator: after the keypoint
+ * extractor the surface points of every scan are built, and the consecutive pairs of a window are registered point-to-line,
+ * src = this scan, dst = the previous one, identity start.  The Cartesian image, the descriptors, the matcher, the cross
+ * check and the max-clique selection do not run.  params = NULL goes back to ORORA.  Accepted only while the handle holds no
+ * scan; RSX_ERR_BAD_ARG while compensation is on (and rsx_odometry_set_compensation refuses while CFEAR is selected: the
+ * MC-RANSAC rule).  rsx_odometry_set_estimator leaves CFEAR as it leaves any other estimator, but refuses RSX_ESTIMATOR_CFEAR
+ * itself: this setter carries the parameters.  Independent of the extractor; the documented pairing is k-strongest with
+ * min_separation = 0.  rsx_odometry_scan.reg carries x, y, yaw and status of the rsx_cfear_result, iterations = its
+ * iterations, rot_inliers = trans_inliers = n_matches = its correspondences.  A scan with more than
+ * RSX_CFEAR_MAX_SURFACE_POINTS surface points gives its pairs status 2.  Results do not depend on how the sequence is cut
+ * into calls. */
+#define RSX_ESTIMATOR_CFEAR 3
+int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params);
 /* n_scans consecutive scans, host images image_stride_bytes apart (rows x row_stride bytes each); azimuths: rows floats
  * (rad, increasing) shared by all scans or n_scans x rows when azimuths_per_image != 0.  out [n_scans]; out_xy
  * (optional) [n_scans][max_xy][2]: the scan's keypoints in metres in the sensor frame (/orora/cloud_local).  Synchronous. */

@@ -111,6 +111,20 @@ class KStrongestParams(C.Structure):
                 ("min_separation", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CfearParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("max_condition", C.c_double), ("cos_max_normal_angle", C.c_double), ("huber_delta", C.c_double),
+                ("step_epsilon", C.c_double), ("min_points", C.c_int32), ("max_iterations", C.c_int32), ("min_correspondences", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+CFEAR_MAX_POINTS, CFEAR_MAX_SURFACE_POINTS = 16384, 4096
+CFEAR_STATUS_RANGE, CFEAR_STATUS_POINTS = 1, 2  # scan status word
+CFEAR_SURFACE_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("lambda_max", "<f4"), ("lambda_min", "<f4"),
+                                      ("n_points", "<i4"), ("cell", "<i4")])
+CFEAR_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("cost", "<f8"), ("iterations", "<i4"), ("correspondences", "<i4"),
+                               ("status", "<i4"), ("reserved", "<i4")])
+
+
 class RadarScParams(C.Structure):
     _fields_ = [("max_radius", C.c_double), ("resolution", C.c_float), ("min_range", C.c_int32), ("power_floor", C.c_int32),
                 ("stat", C.c_int32)]
@@ -132,6 +146,7 @@ class RansacParams(C.Structure):
 
 RANSAC_MOTION_COMPENSATED = 1  # rsx_ransac_params.flags
 ESTIMATOR_ORORA, ESTIMATOR_RANSAC, ESTIMATOR_MCRANSAC = 0, 1, 2  # rsx_odometry_set_estimator
+ESTIMATOR_CFEAR = 3  # selected by rsx_odometry_set_cfear
 RANSAC_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("vx", "<f8"), ("vy", "<f8"), ("wz", "<f8"), ("inliers", "<i4"),
                                 ("hypotheses", "<i4"), ("gn_iterations", "<i4"), ("status", "<i4")])
 
@@ -187,6 +202,8 @@ SYMBOLS = [
     "rsx_cen2018_extract_batch", "rsx_cen2018_extract_batch_device", "rsx_cen2018_gauss_weights", "rsx_cen2018_debug_image",
     "rsx_kstrongest_default_params", "rsx_kstrongest_create", "rsx_kstrongest_destroy", "rsx_kstrongest_extract",
     "rsx_kstrongest_extract_batch", "rsx_kstrongest_extract_batch_device", "rsx_odometry_set_kstrongest",
+    "rsx_cfear_default_params", "rsx_cfear_create", "rsx_cfear_destroy", "rsx_cfear_surface_points_batch",
+    "rsx_cfear_surface_points_batch_device", "rsx_cfear_register_batch", "rsx_cfear_register_batch_device", "rsx_odometry_set_cfear",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
@@ -320,6 +337,14 @@ def lib():
         L.rsx_kstrongest_extract_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(KStrongestParams), vp, i32, C.c_float, vp, vp,
                                                           i32, vp, vp]
         L.rsx_odometry_set_kstrongest.argtypes = [vp, C.POINTER(KStrongestParams)]
+        L.rsx_cfear_default_params.argtypes = [C.POINTER(CfearParams)]
+        L.rsx_cfear_create.argtypes = [C.c_int, C.POINTER(vp)]
+        L.rsx_cfear_destroy.argtypes = [vp]
+        L.rsx_cfear_surface_points_batch.argtypes = [vp, vp, vp, i32, C.POINTER(CfearParams), vp, i32, vp, vp]
+        L.rsx_cfear_surface_points_batch_device.argtypes = [vp, vp, vp, i32, C.POINTER(CfearParams), vp, i32, vp, vp, vp]
+        L.rsx_cfear_register_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.POINTER(CfearParams), vp]
+        L.rsx_cfear_register_batch_device.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.POINTER(CfearParams), vp, vp]
+        L.rsx_odometry_set_cfear.argtypes = [vp, C.POINTER(CfearParams)]
         L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
         L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
         L.rsx_radarsc_destroy.argtypes = [vp]

@@ -1,0 +1,107 @@
+"""Host-side wrapper of the CFEAR entry points of librsx.so (include/rsx.h, rsx_cfear_*): keypoint clouds in, oriented surface
+points out; pairs of surface-point sets in, the point-to-line registration of each pair out."""
+import ctypes as C
+
+import numpy as np
+
+from ._rsx import CFEAR_MAX_SURFACE_POINTS, CFEAR_RESULT_DTYPE, CFEAR_SURFACE_POINT_DTYPE, CfearParams, check, lib
+
+
+def default_params():
+    """radius 3.5 m, min_points 6, max_condition 1e5, cos_max_normal_angle cos 30 deg, huber_delta 0.1 m, step_epsilon 1e-6,
+    max_iterations 50, min_correspondences 6."""
+    p = CfearParams()
+    check(lib().rsx_cfear_default_params(C.byref(p)))
+    return p
+
+
+def params(**fields):
+    """default_params() with the given fields replaced."""
+    p = default_params()
+    for name, value in fields.items():
+        if not hasattr(p, name):
+            raise TypeError("rsx_cfear_params has no field " + name)
+        setattr(p, name, value)
+    return p
+
+
+def ragged(parts, dtype, width=None):
+    """list of arrays -> (concatenation, offsets int64 [n + 1])"""
+    parts = [np.ascontiguousarray(a, dtype=dtype).reshape((-1,) + ((width,) if width else ())) for a in parts]
+    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([len(a) for a in parts])
+    flat = np.concatenate(parts) if parts else np.zeros((0,) + ((width,) if width else ()), dtype=dtype)
+    return np.ascontiguousarray(flat), offsets
+
+
+class Cfear:
+    def __init__(self, device=0):
+        self._L = lib()
+        self._h = C.c_void_p()
+        check(self._L.rsx_cfear_create(device, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.rsx_cfear_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def surface_points(self, clouds, params=None, max_records=CFEAR_MAX_SURFACE_POINTS, raw=False):
+        """clouds: list of (n_i, 2) float32 -> (list of records (k_i,) CFEAR_SURFACE_POINT_DTYPE, counts, status words).
+        raw: the whole (n, max_records) record buffer in place of the list."""
+        xy, offsets = ragged(clouds, np.float32, 2)
+        n = len(clouds)
+        rec = np.zeros((n, max_records), dtype=CFEAR_SURFACE_POINT_DTYPE)
+        counts, status = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        check(self._L.rsx_cfear_surface_points_batch(self._h, xy.ctypes.data, offsets.ctypes.data, n, C.byref(params) if params is not None else None,
+                                                     rec.ctypes.data, max_records, counts.ctypes.data, status.ctypes.data))
+        if raw:
+            return rec, counts, status
+        return [rec[i, :min(int(counts[i]), max_records)].copy() for i in range(n)], counts, status
+
+    def register(self, src, dst, init=None, params=None):
+        """src, dst: lists of record arrays (pair i registers src[i] to dst[i]); init: (n, 3) float64 or None
+        -> (n,) CFEAR_RESULT_DTYPE"""
+        s, so = ragged(src, CFEAR_SURFACE_POINT_DTYPE)
+        d, do = ragged(dst, CFEAR_SURFACE_POINT_DTYPE)
+        n = len(src)
+        assert len(dst) == n
+        out = np.zeros(n, dtype=CFEAR_RESULT_DTYPE)
+        if init is not None:
+            init = np.ascontiguousarray(init, dtype=np.float64).reshape(n, 3)
+        check(self._L.rsx_cfear_register_batch(self._h, s.ctypes.data, so.ctypes.data, d.ctypes.data, do.ctypes.data, n,
+                                               init.ctypes.data if init is not None else None, C.byref(params) if params is not None else None,
+                                               out.ctypes.data))
+        return out
+
+    # device entries: raw HBM addresses, asynchronous on `stream` (None: the handle's own)
+    def surface_points_device(self, d_xy, d_offsets, n_scans, d_records, max_records, d_counts, d_status=None, params=None, stream=None):
+        check(self._L.rsx_cfear_surface_points_batch_device(self._h, d_xy, d_offsets, n_scans, C.byref(params) if params is not None else None,
+                                                            d_records, max_records, d_counts, d_status, stream))
+
+    def register_device(self, d_src, d_src_offsets, d_dst, d_dst_offsets, n_pairs, d_out, d_init=None, params=None, stream=None):
+        check(self._L.rsx_cfear_register_batch_device(self._h, d_src, d_src_offsets, d_dst, d_dst_offsets, n_pairs, d_init,
+                                                      C.byref(params) if params is not None else None, d_out, stream))
+
+
+def surface_points(clouds, params=None, device=0):
+    """one-shot Cfear(device).surface_points(clouds, params)"""
+    h = Cfear(device)
+    try:
+        return h.surface_points(clouds, params)
+    finally:
+        h.close()
+
+
+def register(src, dst, init=None, params=None, device=0):
+    """one-shot Cfear(device).register(src, dst, init, params)"""
+    h = Cfear(device)
+    try:
+        return h.register(src, dst, init, params)
+    finally:
+        h.close()

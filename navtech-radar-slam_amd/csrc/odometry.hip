@@ -16,6 +16,10 @@
 //                                               selection (csrc/pmc.hip, RSX_ORORA_PMC: on by default here) + the solver
 //                                               (or rsx_ransac_estimate_batch_device, csrc/ransac.hip, after
 //                                               rsx_odometry_set_estimator: no selection; MC-RANSAC also gets a dt per match)
+//     (rsx_odometry_set_cfear: CFEAR's own pipeline, csrc/cfear.hip)   after the extractor the surface points of every scan
+//                                               (one launch per window); the Cartesian images, the descriptors, the matcher, the
+//                                               cross check and the selection do not run, and the consecutive pairs are
+//                                               registered point-to-line in one launch, src = this scan, dst = the previous one
 //     (rsx_odometry_set_compensation only)      the matches of every pair compensated with the pose the estimator just gave that
 //                                               pair (csrc/mocomp.hip), the estimator once more on them, and the keypoints of
 //                                               every scan compensated with its pair's second pose for out_xy
@@ -30,6 +34,7 @@
 #include <new>
 
 #include "cen2018.h"
+#include "cfear.h"
 #include "keypoints_host.h"
 #include "kstrongest.h"
 #include "mocomp.h"
@@ -183,6 +188,35 @@ __global__ __launch_bounds__(64) void odo_ransac_results(const rsx_ransac_result
   out[j] = o;
 }
 
+// CFEAR: group i of a slot layout owns elements [i * stride, i * stride + counts[i]) (clamp: at most stride of them): the
+// ranges csrc/cfear.hip's launches read
+__global__ __launch_bounds__(64) void odo_cfear_ranges(const int32_t *__restrict__ counts, int n, int64_t stride, int clamp,
+                                                       int64_t *__restrict__ begin, int64_t *__restrict__ end) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  int64_t c = counts[i] > 0 ? counts[i] : 0;
+  if (clamp && c > stride) c = stride;
+  begin[i] = (int64_t)i * stride;
+  end[i] = (int64_t)i * stride + c;
+}
+
+// CFEAR's results in the records rsx_odometry_scan carries (include/rsx.h, rsx_odometry_set_cfear)
+__global__ __launch_bounds__(64) void odo_cfear_results(const rsx_cfear_result *__restrict__ in, int n_pairs, rsx_orora_result *__restrict__ out,
+                                                        int32_t *__restrict__ pair_cnt) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n_pairs) return;
+  const rsx_cfear_result r = in[j];
+  rsx_orora_result o;
+  o.x = r.x;
+  o.y = r.y;
+  o.yaw = r.yaw;
+  o.iterations = r.iterations;
+  o.rot_inliers = o.trans_inliers = r.correspondences;
+  o.status = r.status;
+  out[j] = o;
+  pair_cnt[j] = r.correspondences;
+}
+
 }  // namespace
 
 // Round 6: several windows in flight.  A window is two stages: EXTRACTION (cen2019, Cartesian images, descriptors: the wide
@@ -200,6 +234,7 @@ __global__ __launch_bounds__(64) void odo_ransac_results(const rsx_ransac_result
 constexpr int N_SETS = 3, N_LANES = 2;
 struct OdoSet {
   rsx::DevBuf az, targets, xy, counts, desc, valid;  // slot 0 = the previous scan, slots 1 .. MAX_WINDOW = the window
+  rsx::DevBuf sp, sp_counts, pt_begin, pt_end;  // CFEAR only: surface points [slot][RSX_CFEAR_MAX_SURFACE_POINTS], their counts, the point ranges
   rsx::PinnedBuf pin;  // pinned: counts[MAX_WINDOW + 1], pair_cnt[MAX_WINDOW], results[MAX_WINDOW], then the staged azimuth grids
 };
 
@@ -222,6 +257,8 @@ struct rsx_odometry {
   rsx::Owned<rsx_ransac, rsx_ransac_destroy> ransac;  // created at the first rsx_odometry_set_estimator that asks for one
   rsx_ransac_params ransac_prm{};
   rsx::DevBuf ransac_res, stage_dt, dt;  // allocated only with a RANSAC estimator (stage_dt, dt: MC-RANSAC)
+  rsx_cfear_params cfear_prm{};  // estimator == RSX_ESTIMATOR_CFEAR (rsx_odometry_set_cfear)
+  rsx::DevBuf cfear_res, sp_begin, sp_end;  // allocated only with CFEAR: results of a window, the record ranges of its slots
   bool comp_on = false;  // rsx_odometry_set_compensation
   rsx_mocomp_params comp_prm{};
   rsx::DevBuf stage_acur, stage_aprev, a_cur, a_prev, src2, dst2, results2, xy_comp;  // allocated only with compensation
@@ -249,6 +286,12 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
     RSX_TRY(q.counts.reserve(S * 4, s, true));
     RSX_TRY(q.desc.reserve(S * K * 32, s, true));
     RSX_TRY(q.valid.reserve(S * K, s, true));
+    if (h->estimator == RSX_ESTIMATOR_CFEAR) {
+      RSX_TRY(q.sp.reserve(S * RSX_CFEAR_MAX_SURFACE_POINTS * sizeof(rsx_cfear_surface_point), s, true));
+      RSX_TRY(q.sp_counts.reserve(S * 4, s, true));
+      RSX_TRY(q.pt_begin.reserve((size_t)MAX_WINDOW * 8, s, false));
+      RSX_TRY(q.pt_end.reserve((size_t)MAX_WINDOW * 8, s, false));
+    }
   }
   RSX_TRY(h->fwd.reserve((size_t)MAX_WINDOW * K * 4, s, false));
   RSX_TRY(h->bwd.reserve((size_t)MAX_WINDOW * K * 4, s, false));
@@ -259,7 +302,11 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
   RSX_TRY(h->dst.reserve((size_t)MAX_WINDOW * K * 8, s, false));
   RSX_TRY(h->offsets.reserve((size_t)(MAX_WINDOW + 1) * 8, s, false));
   RSX_TRY(h->results.reserve((size_t)MAX_WINDOW * sizeof(rsx_orora_result), s, false));
-  if (h->estimator != RSX_ESTIMATOR_ORORA) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
+  if (h->estimator == RSX_ESTIMATOR_CFEAR) {
+    RSX_TRY(h->cfear_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_cfear_result), s, false));
+    RSX_TRY(h->sp_begin.reserve(S * 8, s, false));
+    RSX_TRY(h->sp_end.reserve(S * 8, s, false));
+  } else if (h->estimator != RSX_ESTIMATOR_ORORA) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
   if (h->estimator == RSX_ESTIMATOR_MCRANSAC) {
     RSX_TRY(h->stage_dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
     RSX_TRY(h->dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
@@ -296,6 +343,20 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   RSX_TRY(h->use_kstrongest ? keypoints(rsx_kstrongest_extract_batch_device, h->kstr[lane].get(), &h->kstr_prm)
           : h->use_cen2018  ? keypoints(rsx_cen2018_extract_batch_device, h->cen18[lane].get(), &h->cen18_prm)
                             : keypoints(rsx_cen2019_extract_batch_device, h->cen[lane].get(), &h->prm.cen));
+  if (h->estimator == RSX_ESTIMATOR_CFEAR) {  // the surface points of every scan; no Cartesian image, no descriptors
+    constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
+    hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 63) / 64), dim3(64), 0, s, d_counts + 1, n, (int64_t)K, 1, q.pt_begin.as<int64_t>(),
+                       q.pt_end.as<int64_t>());
+    RSX_HIP(hipGetLastError());
+    RSX_TRY(rsx::cfear::launch_surface(q.xy.as<float>() + slot_xy, q.pt_begin.as<int64_t>(), q.pt_end.as<int64_t>(), n, h->cfear_prm,
+                                       q.sp.as<rsx_cfear_surface_point>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
+    RSX_HIP(hipStreamWaitEvent(s, h->ev_m[(g + 1) % N_SETS], 0));  // the carry, as below
+    RSX_HIP(hipMemcpyAsync(nx.sp.p, q.sp.as<rsx_cfear_surface_point>() + (size_t)n * SP, SP * sizeof(rsx_cfear_surface_point),
+                           hipMemcpyDeviceToDevice, s));
+    RSX_HIP(hipMemcpyAsync(nx.sp_counts.p, q.sp_counts.as<int32_t>() + n, 4, hipMemcpyDeviceToDevice, s));
+    RSX_HIP(hipEventRecord(h->ev_e[g % N_SETS], s));
+    return RSX_OK;
+  }
   // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
   // how the sequence is cut into windows, and nothing about the grids is looked at on the host
   RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
@@ -327,7 +388,18 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
   int32_t *d_counts = q.counts.as<int32_t>();
   const int first = h->have_prev ? 0 : 1, n_pairs = n - first;
   *first_out = first;
-  if (n_pairs > 0) {
+  if (n_pairs > 0 && h->estimator == RSX_ESTIMATOR_CFEAR) {  // one registration launch over the pairs; src = slot first + j + 1, dst = slot first + j
+    int64_t *b = h->sp_begin.as<int64_t>(), *e = h->sp_end.as<int64_t>();
+    hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 1 + 63) / 64), dim3(64), 0, s, q.sp_counts.as<int32_t>(), n + 1,
+                       (int64_t)RSX_CFEAR_MAX_SURFACE_POINTS, 0, b, e);
+    RSX_HIP(hipGetLastError());
+    const rsx_cfear_surface_point *sp = q.sp.as<rsx_cfear_surface_point>();
+    RSX_TRY(rsx::cfear::launch_register(sp, b + first + 1, e + first + 1, sp, b + first, e + first, n_pairs, nullptr, h->cfear_prm,
+                                        h->cfear_res.as<rsx_cfear_result>(), s));
+    hipLaunchKernelGGL(odo_cfear_results, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->cfear_res.as<rsx_cfear_result>(), n_pairs,
+                       h->results.as<rsx_orora_result>(), h->pair_cnt.as<int32_t>());
+    RSX_HIP(hipGetLastError());
+  } else if (n_pairs > 0) {
     RSX_TRY(rsx_frontend_match_consecutive_device(h->fe[g & 1].get(), q.desc.as<uint8_t>(), q.valid.as<uint8_t>(), d_counts, K, first, n_pairs,
                                                   h->prm.frontend.ratio, h->fwd.as<int32_t>(), h->bwd.as<int32_t>(), s));
     const bool mc = h->estimator == RSX_ESTIMATOR_MCRANSAC;
@@ -598,6 +670,7 @@ int rsx_odometry_set_kstrongest(rsx_odometry *h, const rsx_kstrongest_params *pa
 
 int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_params *params) try {
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  if (estimator == RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "RSX_ESTIMATOR_CFEAR is selected with rsx_odometry_set_cfear, which carries its parameters");
   if (estimator != RSX_ESTIMATOR_ORORA && estimator != RSX_ESTIMATOR_RANSAC && estimator != RSX_ESTIMATOR_MCRANSAC)
     return fail(RSX_ERR_BAD_ARG, "unknown estimator %d", estimator);
   std::lock_guard<std::mutex> lk(h->mu);
@@ -633,11 +706,27 @@ int rsx_odometry_set_compensation(rsx_odometry *h, const rsx_mocomp_params *para
     return RSX_OK;
   }
   if (h->estimator == RSX_ESTIMATOR_MCRANSAC) return fail(RSX_ERR_BAD_ARG, "motion-compensated RANSAC has its own motion model");
+  if (h->estimator == RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is selected: it has no matches to compensate (rsx_odometry_set_cfear(h, NULL) first)");
   rsx_mocomp_params p = *params;
   p.rows = h->rows;
   RSX_TRY(rsx::mocomp::check_params(p));
   h->comp_prm = p;
   h->comp_on = true;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
+  if (!params) {
+    h->estimator = RSX_ESTIMATOR_ORORA;
+    return RSX_OK;
+  }
+  if (h->comp_on) return fail(RSX_ERR_BAD_ARG, "compensation is on: CFEAR registration has no matches to compensate (rsx_odometry_set_compensation(h, NULL) first)");
+  RSX_TRY(rsx::cfear::check_params(*params));
+  h->cfear_prm = *params;
+  h->estimator = RSX_ESTIMATOR_CFEAR;
   return RSX_OK;
 } RSX_CATCH_ALL
 

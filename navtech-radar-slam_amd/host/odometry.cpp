@@ -27,6 +27,10 @@
 // `--estimator ransac|mcransac` (with `--ransac-threshold`, `--ransac-iterations`, `--scan-period`) hands a pair's matches to
 // rigid RANSAC or motion-compensated RANSAC instead of the max-clique selection + ORORA (upstream's other estimators:
 // rsx_odometry_set_estimator, windowed path only; mcransac takes a match's time from the azimuth rows of its keypoints).
+// `--estimator cfear` (with `--cfear-radius`, `--cfear-normal-angle`, `--cfear-huber`, `--cfear-max-iterations`) runs CFEAR's own
+// pipeline: oriented surface points of the keypoints and a point-to-line registration of consecutive scans, no Cartesian image,
+// descriptors or matcher (rsx_odometry_set_cfear, windowed path only, not with --compensate; meant for `--keypoints kstrongest
+// --min-separation 0`).  n_matches is then the number of correspondences of the last iteration.
 // `--compensate motion|doppler|both` (with `--doppler-beta`, `--scan-period`) corrects the keypoints for the sensor's motion
 // during the scan and / or the Doppler range shift: every pair is estimated, its matches compensated with that estimate and
 // estimated again, and the published cloud is the compensated one (upstream's deskewing / Doppler switches:
@@ -149,6 +153,8 @@ int main(int argc, char **argv) {
     rsx_kstrongest_default_params(&ksp);
     rsx_ransac_params rsp;
     rsx_ransac_default_params(&rsp);
+    rsx_cfear_params cfp;
+    rsx_cfear_default_params(&cfp);
     std::string compensate;
     rsx_mocomp_params mcp;
     rsx_mocomp_default_params(&mcp);
@@ -170,7 +176,11 @@ int main(int argc, char **argv) {
       else if (a == "--k" && i + 1 < argc) ksp.k = std::atoi(argv[++i]);          // kstrongest: keypoints per azimuth at most (12)
       else if (a == "--z-min" && i + 1 < argc) ksp.z_min = std::atoi(argv[++i]);  // kstrongest: power floor (60)
       else if (a == "--min-separation" && i + 1 < argc) ksp.min_separation = std::atoi(argv[++i]);  // kstrongest: range bins between two keypoints of an azimuth (5)
-      else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac
+      else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac | cfear
+      else if (a == "--cfear-radius" && i + 1 < argc) cfp.radius = std::atof(argv[++i]);               // cfear: cell side and search radius [m] (3.5)
+      else if (a == "--cfear-normal-angle" && i + 1 < argc) cfp.cos_max_normal_angle = std::cos(std::atof(argv[++i]) * 3.14159265358979323846 / 180.0);  // cfear: largest angle between matched normals [deg] (30)
+      else if (a == "--cfear-huber" && i + 1 < argc) cfp.huber_delta = std::atof(argv[++i]);           // cfear: Huber threshold [m] (0.1)
+      else if (a == "--cfear-max-iterations" && i + 1 < argc) cfp.max_iterations = std::atoi(argv[++i]);  // cfear: Gauss-Newton iterations at most (50)
       else if (a == "--ransac-threshold" && i + 1 < argc) rsp.tolerance = std::atof(argv[++i]);        // inlier residual bound [m] (0.35)
       else if (a == "--ransac-iterations" && i + 1 < argc) rsp.max_iterations = std::atoi(argv[++i]);  // hypotheses (100)
       else if (a == "--scan-period" && i + 1 < argc) rsp.dt_scan = std::atof(argv[++i]);               // mcransac: seconds per scan (0.25)
@@ -194,7 +204,7 @@ int main(int argc, char **argv) {
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--window W] [--threads T] "
-          "[--estimator orora|ransac|mcransac] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
+          "[--estimator orora|ransac|mcransac|cfear] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-max-iterations N] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
           "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";
@@ -279,7 +289,7 @@ int main(int argc, char **argv) {
 #endif
     };
     auto compose = [&](const rsx_orora_result &r) {
-      if (r.status != 0) return;
+      if (r.status != 0 && !(estimator == "cfear" && r.status == 8)) return;  // (cfear's status 8, max_iterations reached, still carries a pose)
       const double c = std::cos(pyaw), s = std::sin(pyaw);
       px += c * r.x - s * r.y;
       py += s * r.x + c * r.y;
@@ -288,12 +298,13 @@ int main(int argc, char **argv) {
     if (matcher != "nn" && matcher != "orb") die("--matcher must be orb or nn");
     if (keypoints != "cen2019" && keypoints != "cen2018" && keypoints != "kstrongest") die("--keypoints must be cen2019, cen2018 or kstrongest");
     const bool use_c18 = keypoints == "cen2018", use_ks = keypoints == "kstrongest";
-    if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac") die("--estimator must be orora, ransac or mcransac");
+    if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac" && estimator != "cfear") die("--estimator must be orora, ransac, mcransac or cfear");
     if (estimator != "orora" && (matcher != "orb" || per_scan)) die("--estimator " + estimator + " runs on the windowed path only (not with --per-scan / --matcher nn)");
     if (!compensate.empty()) {
       if (compensate != "motion" && compensate != "doppler" && compensate != "both") die("--compensate must be motion, doppler or both");
       if (matcher != "orb" || per_scan) die("--compensate runs on the windowed path only (not with --per-scan / --matcher nn)");
       if (estimator == "mcransac") die("--compensate does not go with --estimator mcransac, which has its own motion model");
+      if (estimator == "cfear") die("--compensate does not go with --estimator cfear, which has no matches to compensate");
       mcp.flags = compensate == "motion" ? RSX_MOCOMP_DESKEW : compensate == "doppler" ? RSX_MOCOMP_DOPPLER : RSX_MOCOMP_DESKEW | RSX_MOCOMP_DOPPLER;
       mcp.dt_scan = rsp.dt_scan;
     }
@@ -322,7 +333,8 @@ int main(int argc, char **argv) {
       check(rsx_odometry_create(&op, rows, cols, &odo), "rsx_odometry_create");
       if (use_c18) check(rsx_odometry_set_cen2018(odo, &c18), "rsx_odometry_set_cen2018");
       if (use_ks) check(rsx_odometry_set_kstrongest(odo, &ksp), "rsx_odometry_set_kstrongest");
-      if (estimator != "orora")
+      if (estimator == "cfear") check(rsx_odometry_set_cfear(odo, &cfp), "rsx_odometry_set_cfear");
+      else if (estimator != "orora")
         check(rsx_odometry_set_estimator(odo, estimator == "ransac" ? RSX_ESTIMATOR_RANSAC : RSX_ESTIMATOR_MCRANSAC, &rsp), "rsx_odometry_set_estimator");
       if (!compensate.empty()) check(rsx_odometry_set_compensation(odo, &mcp), "rsx_odometry_set_compensation");
       rsx_radarsc *rctx = nullptr;

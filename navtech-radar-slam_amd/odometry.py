@@ -4,10 +4,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, KStrongestParams, MocompParams,
+from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, CfearParams, KStrongestParams, MocompParams,
                    OdometryParams, RansacParams, check, lib)
 
-ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_*
+ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_* ("cfear", RSX_ESTIMATOR_CFEAR, has a setter of its own)
 COMPENSATIONS = {"motion": MOCOMP_DESKEW, "doppler": MOCOMP_DOPPLER, "both": MOCOMP_DESKEW | MOCOMP_DOPPLER}  # rsx_mocomp_params.flags
 
 
@@ -20,18 +20,21 @@ def default_params():
 class Odometry:
     """keypoints: "cen2019" (default), "cen2018" or "kstrongest"; cen2018: its Cen2018Params (None: cen2018.default_params());
     kstrongest: its KStrongestParams (None: kstrongest.default_params()).
-    estimator: "orora" (default), "ransac" or "mcransac"; ransac: their RansacParams (None: ransac.default_params()).
+    estimator: "orora" (default), "ransac", "mcransac" or "cfear"; ransac: the RANSAC estimators' RansacParams (None:
+    ransac.default_params()); cfear: CfearParams (None: cfear.default_params()): CFEAR's surface points and point-to-line
+    registration in place of descriptors, matcher and estimator (rsx_odometry_set_cfear; pair it with keypoints="kstrongest",
+    min_separation = 0; not with compensate).
     exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT).
     compensate: None (default), "motion", "doppler" or "both": every pair is estimated, its matches compensated with that
     estimate, and estimated again (rsx_odometry_set_compensation; not with "mcransac"); beta, dt_scan: the Doppler factor and
     the scan period of the model (None: the library's defaults)."""
 
     def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
-                 exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None):
+                 exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None, cfear=None):
         if keypoints not in ("cen2019", "cen2018", "kstrongest"):
             raise ValueError("keypoints must be cen2019, cen2018 or kstrongest")
-        if estimator not in ESTIMATORS:
-            raise ValueError("estimator must be orora, ransac or mcransac")
+        if estimator not in ESTIMATORS and estimator != "cfear":
+            raise ValueError("estimator must be orora, ransac, mcransac or cfear")
         if compensate is not None and compensate not in COMPENSATIONS:
             raise ValueError("compensate must be None, motion, doppler or both")
         self._L = lib()
@@ -48,7 +51,9 @@ class Odometry:
             self.set_cen2018(cen2018)
         if keypoints == "kstrongest":
             self.set_kstrongest(kstrongest)
-        if estimator != "orora":
+        if estimator == "cfear":
+            self.set_cfear(cfear)
+        elif estimator != "orora":
             self.set_estimator(estimator, ransac)
         if compensate is not None:
             self.set_compensation(compensate, beta=beta, dt_scan=dt_scan)
@@ -75,6 +80,17 @@ class Odometry:
         if ransac is not None and not isinstance(ransac, RansacParams):
             raise TypeError("ransac must be RansacParams")
         check(self._L.rsx_odometry_set_estimator(self._h, ESTIMATORS[estimator], C.byref(ransac) if ransac is not None else None))
+
+    def set_cfear(self, cfear=None, off=False):
+        """Switch to CFEAR surface points and point-to-line registration (cfear: CfearParams or None for the defaults), or back to
+        ORORA with off=True.  Only while the handle holds no scan, and not while compensation is on."""
+        if off:
+            check(self._L.rsx_odometry_set_cfear(self._h, None))
+            return
+        p = cfear if cfear is not None else CfearParams()
+        if cfear is None:
+            check(self._L.rsx_cfear_default_params(C.byref(p)))
+        check(self._L.rsx_odometry_set_cfear(self._h, C.byref(p)))
 
     def set_cen2018(self, cen2018=None, off=False):
         """Switch to cen2018 keypoints (cen2018: Cen2018Params or None for the defaults), or back to cen2019 with off=True.
