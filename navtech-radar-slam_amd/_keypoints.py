@@ -1,5 +1,5 @@
-"""What the host-side wrappers of the keypoint extractors (cen2018.Cen2018, cen2019.Cen2019, kstrongest.KStrongest) share: the handle and the
-calls of rsx_<name>_extract / rsx_<name>_extract_batch with their output arrays."""
+"""What the host-side wrappers of the keypoint extractors (cen2018.Cen2018, cen2019.Cen2019, kstrongest.KStrongest) share: the handle, the
+calls of rsx_<name>_extract / rsx_<name>_extract_batch with their output arrays, and how the results are returned."""
 import ctypes as C
 
 import numpy as np
@@ -30,8 +30,14 @@ class _Extractor:
         except Exception:
             pass
 
-    def _extract(self, img, p, col_offset, azimuths, resolution, max_targets):
-        """img: (rows, row_stride) uint8, p: the params struct.  -> targets (k, 2) int32, xy (k, 2) float32 or None, the full count."""
+    @staticmethod
+    def _result(targets, xy, counts, want_counts):
+        """-> targets [, xy if there is one] [, counts if wanted]: a tuple, or targets alone."""
+        res = (targets,) + ((xy,) if xy is not None else ()) + ((counts,) if want_counts else ())
+        return res if len(res) > 1 else res[0]
+
+    def _extract(self, img, p, col_offset, azimuths, resolution, max_targets, return_count=False):
+        """img: (rows, row_stride) uint8, p: the params struct.  -> targets (k, 2) int32 [, xy (k, 2) float32 if azimuths] [, the full count]."""
         img = np.ascontiguousarray(img, dtype=np.uint8)
         assert img.shape[0] == self.rows
         out = np.zeros((max(max_targets, 1), 2), dtype=np.int32)
@@ -42,11 +48,14 @@ class _Extractor:
                                   az.ctypes.data if az is not None else None, resolution, out.ctypes.data,
                                   xy.ctypes.data if xy is not None else None, max_targets, C.byref(n)))
         k = min(n.value, max_targets)
-        return out[:k].copy(), xy[:k].copy() if xy is not None else None, n.value
+        return self._result(out[:k].copy(), xy[:k].copy() if xy is not None else None, n.value, return_count)
 
-    def _extract_batch(self, imgs, p, col_offset, azimuths, resolution, max_targets):
-        """imgs: (n, rows, row_stride) uint8 with contiguous images.  -> list of targets (k_i, 2) int32, list of xy (k_i, 2)
-        float32 or None, counts (n,) int32."""
+    def _extract_batch(self, imgs, p, col_offset, azimuths, resolution, max_targets, return_counts=False):
+        """imgs: (n, rows, row_stride) uint8 (any image stride; copied when a row or a bin is strided).  -> list of targets
+        (k_i, 2) int32 [, list of xy (k_i, 2) float32 if azimuths] [, counts (n,) int32]."""
+        imgs = np.asarray(imgs, dtype=np.uint8)
+        if imgs.strides[1:] != (imgs.shape[2], 1):
+            imgs = np.ascontiguousarray(imgs)
         n = imgs.shape[0]
         assert imgs.shape[1] == self.rows
         mt = max(max_targets, 1)
@@ -59,5 +68,5 @@ class _Extractor:
                                         1 if (az is not None and az.ndim == 2) else 0, resolution, out.ctypes.data,
                                         xy.ctypes.data if xy is not None else None, max_targets, counts.ctypes.data))
         ks = np.minimum(counts, max_targets)
-        return ([out[i, :ks[i]].copy() for i in range(n)],
-                [xy[i, :ks[i]].copy() for i in range(n)] if xy is not None else None, counts)
+        return self._result([out[i, :ks[i]].copy() for i in range(n)],
+                            [xy[i, :ks[i]].copy() for i in range(n)] if xy is not None else None, counts, return_counts)

@@ -44,22 +44,15 @@ class Cen2018(_Extractor):
     def extract(self, img, col_offset=11, zq=3.0, sigma_gauss=17, min_range=58, azimuths=None, resolution=0.0595,
                 max_targets=200000, return_count=False):
         """img: (rows, row_stride) uint8.  -> targets (n,2) int32 [, xy (n,2) float32 if azimuths] [, the full count]."""
-        tg, xy, count = self._extract(img, Cen2018Params(zq, sigma_gauss, min_range, 0), col_offset, azimuths, resolution, max_targets)
-        res = (tg,) + ((xy,) if xy is not None else ()) + ((count,) if return_count else ())
-        return res if len(res) > 1 else res[0]
+        return self._extract(img, Cen2018Params(zq, sigma_gauss, min_range, 0), col_offset, azimuths, resolution, max_targets, return_count)
 
     def extract_batch(self, imgs, col_offset=11, zq=3.0, sigma_gauss=17, min_range=58, azimuths=None, resolution=0.0595,
                       max_targets=20000, return_counts=False):
         """imgs: (n, rows, row_stride) uint8 (any image stride) -> list of targets (k_i, 2) int32 [, list of xy (k_i, 2)
         float32] [, counts]; one chain of launches for the whole batch (rsx_cen2018_extract_batch).  azimuths: (rows,)
         shared or (n, rows)."""
-        imgs = np.asarray(imgs, dtype=np.uint8)
-        if imgs.strides[1:] != (imgs.shape[2], 1):
-            imgs = np.ascontiguousarray(imgs)
-        tg, xy, counts = self._extract_batch(imgs, Cen2018Params(zq, sigma_gauss, min_range, 0), col_offset, azimuths, resolution,
-                                             max_targets)
-        res = (tg,) + ((xy,) if xy is not None else ()) + ((counts,) if return_counts else ())
-        return res if len(res) > 1 else res[0]
+        return self._extract_batch(imgs, Cen2018Params(zq, sigma_gauss, min_range, 0), col_offset, azimuths, resolution, max_targets,
+                                   return_counts)
 
     def debug_image(self, img, col_offset=11, zq=3.0, sigma_gauss=17, min_range=58):
         """rsx_cen2018_debug_image: -> dict(mean (rows,), sigma (rows,), p (rows, cols), y (rows, cols)) of one image."""

@@ -20,13 +20,11 @@ class Cen2019(_Extractor):
     def extract(self, img, col_offset=11, max_points=10000, min_range=58, azimuths=None, resolution=0.0595,
                 max_targets=200000):
         """img: (rows, row_stride) uint8.  -> targets (n,2) int32 [, xy (n,2) float32 if azimuths]."""
-        tg, xy, _ = self._extract(img, Cen2019Params(max_points, min_range), col_offset, azimuths, resolution, max_targets)
-        return (tg, xy) if xy is not None else tg
+        return self._extract(img, Cen2019Params(max_points, min_range), col_offset, azimuths, resolution, max_targets)
 
     def extract_batch(self, imgs, col_offset=11, max_points=10000, min_range=58, azimuths=None, resolution=0.0595,
                       max_targets=20000):
         """imgs: (n, rows, row_stride) uint8 -> list of targets (k_i, 2) int32 [, list of xy (k_i, 2) float32]; one chain
         of launches for the whole batch (rsx_cen2019_extract_batch).  azimuths: (rows,) shared or (n, rows)."""
-        tg, xy, _ = self._extract_batch(np.ascontiguousarray(imgs, dtype=np.uint8), Cen2019Params(max_points, min_range), col_offset,
-                                        azimuths, resolution, max_targets)
-        return (tg, xy) if xy is not None else tg
+        return self._extract_batch(np.ascontiguousarray(imgs, dtype=np.uint8), Cen2019Params(max_points, min_range), col_offset, azimuths,
+                                   resolution, max_targets)

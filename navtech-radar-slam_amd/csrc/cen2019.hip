@@ -1656,15 +1656,12 @@ __global__ __launch_bounds__(64 * ADJ_WAVES) void cen_adjacent(int rows, int col
 
 }  // namespace
 
-struct rsx_cen2019 {
-  int device = 0, rows = 0, cols = 0;
-  std::mutex mu;
-  rsx::Stream stream;
+struct rsx_cen2019 : rsx::KeypointHandle {
   rsx::DevBuf scal, hist, list, row_out, row_n, opener, row_runs, row_nruns, markbits, wavemax, negmax;
-  rsx::KeypointStaging stage;
   rsx::DevBuf one;          // single-scan entry: [count | targets | xy] in one piece, read back with one copy
   rsx::PinnedBuf one_host;  // its pinned mirror
-  rsx::StreamOrder order;
+  int single_scan(const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2019_params &p, const float *azimuths, float resolution,
+                  int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_count, hipStream_t s);
 };
 
 using rsx::fail;
@@ -1765,7 +1762,56 @@ int extract_device(rsx_cen2019 *h, const uint8_t *d_imgs, int64_t img_stride, in
   return RSX_OK;
 }
 
+// the resolve step of the scaffold (keypoints_host.h): the defaults, *params over them; nothing to check
+int get_params(const rsx_cen2019_params *params, rsx_cen2019_params *p) {
+  rsx_cen2019_default_params(p);
+  if (params) *p = *params;
+  return RSX_OK;
+}
+
 }  // namespace
+
+// the live single-scan entry (the scaffold's hook for n_images == 1): the image goes up in one copy (asynchronous when the
+// caller's buffer is pinned, rsx_host_alloc_pinned), the count and every keypoint slot come back in ONE copy into pinned memory,
+// one synchronise (before round 4: the count first, a synchronise, then the keypoints, a second synchronise)
+int rsx_cen2019::single_scan(const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2019_params &p, const float *azimuths,
+                             float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_count, hipStream_t s) {
+  const size_t ibytes = (size_t)rows * row_stride;
+  const int mt = max_targets > 0 ? max_targets : 1;
+  const size_t kp = (size_t)mt * 8, total = 256 + 2 * kp;
+  RSX_TRY(stage.img.reserve(ibytes, s, false));
+  RSX_TRY(one.reserve(total, s, false));
+  RSX_TRY(one_host.reserve(total));
+  RSX_HIP(hipMemcpyAsync(stage.img.p, img, ibytes, hipMemcpyHostToDevice, s));
+  const float *d_az = nullptr;
+  if (azimuths) {
+    RSX_TRY(stage.az.reserve((size_t)rows * 4, s, false));
+    RSX_HIP(hipMemcpyAsync(stage.az.p, azimuths, (size_t)rows * 4, hipMemcpyHostToDevice, s));
+    d_az = stage.az.as<float>();
+  }
+  char *d_one = one.as<char>();
+  RSX_TRY(extract_device(this, stage.img.as<uint8_t>(), (int64_t)ibytes, 1, row_stride, col_offset, p, d_az, 0, resolution, mt,
+                         reinterpret_cast<int *>(d_one + 256), d_az ? reinterpret_cast<float *>(d_one + 256 + kp) : nullptr,
+                         reinterpret_cast<int *>(d_one), s));
+  // the count and the first 16 384 keypoint slots (a scan yields ~3 000) in one copy; a longer list takes a second one
+  const size_t first = mt < 16384 ? (size_t)mt : 16384, fb = first * 8;
+  RSX_HIP(hipMemcpyAsync(one_host.p, d_one, 256 + fb, hipMemcpyDeviceToHost, s));
+  if (out_xy) RSX_HIP(hipMemcpyAsync(static_cast<char *>(one_host.p) + 256 + kp, d_one + 256 + kp, fb, hipMemcpyDeviceToHost, s));
+  RSX_HIP(hipStreamSynchronize(s));
+  const char *hp = static_cast<const char *>(one_host.p);
+  const unsigned cnt = *reinterpret_cast<const unsigned *>(hp);
+  out_count[0] = (int32_t)cnt;
+  const unsigned w = cnt < (unsigned)max_targets ? cnt : (unsigned)max_targets;
+  if (w > first) {
+    RSX_HIP(hipMemcpyAsync(one_host.p, d_one, out_xy ? total : 256 + kp, hipMemcpyDeviceToHost, s));
+    RSX_HIP(hipStreamSynchronize(s));
+  }
+  if (w) {
+    std::memcpy(out_targets, hp + 256, (size_t)w * 8);
+    if (out_xy) std::memcpy(out_xy, hp + 256 + kp, (size_t)w * 8);
+  }
+  return RSX_OK;
+}
 
 extern "C" {
 
@@ -1777,117 +1823,33 @@ int rsx_cen2019_default_params(rsx_cen2019_params *p) try {
 } RSX_CATCH_ALL
 
 int rsx_cen2019_create(int device, int32_t rows, int32_t cols, rsx_cen2019 **out) try {
-  if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
-  *out = nullptr;
-  if (rows < 1 || rows > 1024 || cols < 2 || cols > 16384) return fail(RSX_ERR_BAD_ARG, "image shape %d x %d unsupported", rows, cols);
-  RSX_TRY(rsx::check_device(device));
-  std::unique_ptr<rsx_cen2019> h(new (std::nothrow) rsx_cen2019());
-  if (!h) return fail(RSX_ERR_OOM, "host alloc");
-  h->device = device;
-  h->rows = rows;
-  h->cols = cols;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = h->stream.create();
-  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  *out = h.release();
-  return RSX_OK;
+  return rsx::keypoints_create(rows >= 1 && rows <= 1024 && cols >= 2 && cols <= 16384, device, rows, cols, out);
 } RSX_CATCH_ALL
 
 int rsx_cen2019_destroy(rsx_cen2019 *h) try {
-  if (!h) return RSX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  delete h;
-  return RSX_OK;
+  return rsx::keypoints_destroy(h);
 } RSX_CATCH_ALL
 
 int rsx_cen2019_extract_batch_device(rsx_cen2019 *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
                                      int32_t col_offset, const rsx_cen2019_params *params, const float *d_azimuths,
                                      int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                      int32_t *d_counts, void *stream) try {
-  if (!h || !d_imgs || !d_targets || n_images < 0 || max_targets < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
-  if (d_xy && !d_azimuths) return fail(RSX_ERR_BAD_ARG, "d_xy needs d_azimuths");
-  if (n_images == 0) return RSX_OK;
-  rsx_cen2019_params p;
-  rsx_cen2019_default_params(&p);
-  if (params) p = *params;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  RSX_TRY(h->order.enter(s));
-  return extract_device(h, d_imgs, image_stride_bytes, n_images, row_stride, col_offset, p, d_azimuths, azimuths_per_image ? h->rows : 0,
-                        resolution, max_targets, d_targets, d_xy, d_counts, s);
+  return rsx::keypoints_extract_batch_device(h, get_params, extract_device, d_imgs, n_images, image_stride_bytes, row_stride, col_offset, params,
+                                             d_azimuths, azimuths_per_image, resolution, d_targets, d_xy, max_targets, d_counts, stream);
 } RSX_CATCH_ALL
 
 int rsx_cen2019_extract_batch(rsx_cen2019 *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
                               int32_t col_offset, const rsx_cen2019_params *params, const float *azimuths, int32_t azimuths_per_image,
                               float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_counts) try {
-  if (!h || !imgs || !out_targets || !out_counts || n_images < 0 || max_targets < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
-  if (out_xy && !azimuths) return fail(RSX_ERR_BAD_ARG, "out_xy needs azimuths");
-  if (n_images == 0) return RSX_OK;
-  rsx_cen2019_params p;
-  rsx_cen2019_default_params(&p);
-  if (params) p = *params;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  RSX_TRY(h->order.enter(s));
-  const size_t ibytes = (size_t)h->rows * row_stride;
-  const int mt = max_targets > 0 ? max_targets : 1;
-  if (n_images == 1) {
-    // the live single-scan entry: the image goes up in one copy (asynchronous when the caller's buffer is pinned,
-    // rsx_host_alloc_pinned), the count and every keypoint slot come back in ONE copy into pinned memory, one synchronise
-    // (before round 4: the count first, a synchronise, then the keypoints, a second synchronise)
-    const size_t kp = (size_t)mt * 8, total = 256 + 2 * kp;
-    RSX_TRY(h->stage.img.reserve(ibytes, s, false));
-    RSX_TRY(h->one.reserve(total, s, false));
-    RSX_TRY(h->one_host.reserve(total));
-    RSX_HIP(hipMemcpyAsync(h->stage.img.p, imgs, ibytes, hipMemcpyHostToDevice, s));
-    const float *d_az = nullptr;
-    if (azimuths) {
-      RSX_TRY(h->stage.az.reserve((size_t)h->rows * 4, s, false));
-      RSX_HIP(hipMemcpyAsync(h->stage.az.p, azimuths, (size_t)h->rows * 4, hipMemcpyHostToDevice, s));
-      d_az = h->stage.az.as<float>();
-    }
-    char *d_one = h->one.as<char>();
-    RSX_TRY(extract_device(h, h->stage.img.as<uint8_t>(), (int64_t)ibytes, 1, row_stride, col_offset, p, d_az, 0, resolution, mt,
-                           reinterpret_cast<int *>(d_one + 256), d_az ? reinterpret_cast<float *>(d_one + 256 + kp) : nullptr,
-                           reinterpret_cast<int *>(d_one), s));
-    // the count and the first 16 384 keypoint slots (a scan yields ~3 000) in one copy; a longer list takes a second one
-    const size_t first = mt < 16384 ? (size_t)mt : 16384, fb = first * 8;
-    RSX_HIP(hipMemcpyAsync(h->one_host.p, d_one, 256 + fb, hipMemcpyDeviceToHost, s));
-    if (out_xy) RSX_HIP(hipMemcpyAsync(static_cast<char *>(h->one_host.p) + 256 + kp, d_one + 256 + kp, fb, hipMemcpyDeviceToHost, s));
-    RSX_HIP(hipStreamSynchronize(s));
-    const char *hp = static_cast<const char *>(h->one_host.p);
-    const unsigned cnt = *reinterpret_cast<const unsigned *>(hp);
-    out_counts[0] = (int32_t)cnt;
-    const unsigned w = cnt < (unsigned)max_targets ? cnt : (unsigned)max_targets;
-    if (w > first) {
-      RSX_HIP(hipMemcpyAsync(h->one_host.p, d_one, out_xy ? total : 256 + kp, hipMemcpyDeviceToHost, s));
-      RSX_HIP(hipStreamSynchronize(s));
-    }
-    if (w) {
-      std::memcpy(out_targets, hp + 256, (size_t)w * 8);
-      if (out_xy) std::memcpy(out_xy, hp + 256 + kp, (size_t)w * 8);
-    }
-    return RSX_OK;
-  }
-  auto extract = [&](const uint8_t *d_imgs, int n, const float *d_az, int *d_targets, float *d_xy, int *d_counts, hipStream_t st) {
-    return extract_device(h, d_imgs, (int64_t)ibytes, n, row_stride, col_offset, p, d_az, azimuths_per_image ? h->rows : 0, resolution, mt, d_targets,
-                          d_xy, d_counts, st);
-  };
-  return h->stage.extract_batch(h->rows, imgs, n_images, image_stride_bytes, row_stride, azimuths, azimuths_per_image, out_targets, out_xy, max_targets,
-                                out_counts, s, extract);
+  return rsx::keypoints_extract_batch(h, get_params, extract_device, imgs, n_images, image_stride_bytes, row_stride, col_offset, params, azimuths,
+                                      azimuths_per_image, resolution, out_targets, out_xy, max_targets, out_counts);
 } RSX_CATCH_ALL
 
 int rsx_cen2019_extract(rsx_cen2019 *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2019_params *params,
                         const float *azimuths, float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets,
                         int32_t *out_count) try {
-  if (!h || !img || !out_targets || !out_count || max_targets < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  return rsx_cen2019_extract_batch(h, img, 1, (int64_t)h->rows * row_stride, row_stride, col_offset, params, azimuths, 0, resolution, out_targets,
-                                   out_xy, max_targets, out_count);
+  return rsx::keypoints_extract(h, get_params, extract_device, img, row_stride, col_offset, params, azimuths, resolution, out_targets, out_xy,
+                                max_targets, out_count);
 } RSX_CATCH_ALL
 
 #ifdef RSX_EXPERIMENTS

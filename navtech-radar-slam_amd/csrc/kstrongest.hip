@@ -222,13 +222,8 @@ __global__ __launch_bounds__(64) void ks_rows(const uint8_t *__restrict__ imgs, 
 
 }  // namespace
 
-struct rsx_kstrongest {
-  int device = 0, rows = 0, cols = 0;
-  std::mutex mu;
-  rsx::Stream stream;
+struct rsx_kstrongest : rsx::KeypointHandle {
   rsx::DevBuf row_kp, row_n;
-  rsx::KeypointStaging stage;
-  rsx::StreamOrder order;
 };
 
 using rsx::fail;
@@ -244,6 +239,7 @@ int rsx::kstrongest_check_params(const rsx_kstrongest_params &p) {
 
 namespace {
 
+// the resolve step of the scaffold (keypoints_host.h): the defaults, *params over them, the check
 int get_params(const rsx_kstrongest_params *params, rsx_kstrongest_params *p) {
   rsx_kstrongest_default_params(p);
   if (params) *p = *params;
@@ -251,27 +247,17 @@ int get_params(const rsx_kstrongest_params *params, rsx_kstrongest_params *p) {
 }
 
 // d_imgs: nb device images img_stride bytes apart -> d_targets [nb][max_targets][2], d_xy (optional, needs d_az), d_counts
-// (optional).  Two launches per sub-batch, nothing read on the host.
+// (optional).  Two launches per sub-batch (rsx::rows_then_pack; row_cap = k), nothing read on the host.
 int extract_device(rsx_kstrongest *h, const uint8_t *d_imgs, int64_t img_stride, int nb, int32_t stride, int32_t off, const rsx_kstrongest_params &p,
                    const float *d_az, int64_t az_stride, float resolution, int32_t max_targets, int *d_targets, float *d_xy, int *d_counts,
                    hipStream_t s) {
   const int rows = h->rows, cols = h->cols;
-  const int row_cap = p.k;
   const int lo = p.min_range < cols ? p.min_range : cols, hi = p.max_range == 0 || p.max_range > cols ? cols : p.max_range;
   const size_t lds = ks_lds_bytes(cols, p.min_separation);
-  for (int b0 = 0; b0 < nb; b0 += rsx::MAX_SUB_BATCH) {
-    const int n = nb - b0 < rsx::MAX_SUB_BATCH ? nb - b0 : rsx::MAX_SUB_BATCH;
-    RSX_TRY(h->row_kp.reserve((size_t)n * rows * row_cap * 2, s, false));
-    RSX_TRY(h->row_n.reserve((size_t)n * rows * 4, s, false));
+  return rsx::rows_then_pack(h, p.k, nb, d_az, az_stride, resolution, max_targets, d_targets, d_xy, d_counts, s, [&](int b0, int n) {
     hipLaunchKernelGGL(ks_rows, dim3((unsigned)rows, (unsigned)n), dim3(64), lds, s, d_imgs + (int64_t)b0 * img_stride, img_stride, rows, cols, stride, off,
                        p.k, p.z_min, lo, hi, p.min_separation, h->row_kp.as<uint16_t>(), h->row_n.as<unsigned>());
-    hipLaunchKernelGGL(rsx::kp_pack<uint16_t>, dim3((unsigned)((rows + rsx::PACK_WAVES - 1) / rsx::PACK_WAVES), (unsigned)n), dim3(64 * rsx::PACK_WAVES),
-                       0, s, rows, row_cap, h->row_kp.as<uint16_t>(), h->row_n.as<unsigned>(), d_az ? d_az + (int64_t)b0 * az_stride : nullptr, az_stride,
-                       resolution, max_targets, d_targets + (int64_t)b0 * max_targets * 2, d_xy ? d_xy + (int64_t)b0 * max_targets * 2 : nullptr,
-                       d_counts ? d_counts + b0 : nullptr, nullptr, 0);
-    RSX_HIP(hipGetLastError());
-  }
-  return RSX_OK;
+  });
 }
 
 }  // namespace
@@ -290,76 +276,33 @@ int rsx_kstrongest_default_params(rsx_kstrongest_params *p) try {
 } RSX_CATCH_ALL
 
 int rsx_kstrongest_create(int device, int32_t rows, int32_t cols, rsx_kstrongest **out) try {
-  if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
-  *out = nullptr;
-  if (rows < 1 || rows > MAX_ROWS || cols < 1 || cols > MAX_COLS) return fail(RSX_ERR_BAD_ARG, "image shape %d x %d unsupported", rows, cols);
-  RSX_TRY(rsx::check_device(device));
-  std::unique_ptr<rsx_kstrongest> h(new (std::nothrow) rsx_kstrongest());
-  if (!h) return fail(RSX_ERR_OOM, "host alloc");
-  h->device = device;
-  h->rows = rows;
-  h->cols = cols;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = h->stream.create();
-  if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  *out = h.release();
-  return RSX_OK;
+  return rsx::keypoints_create(rows >= 1 && rows <= MAX_ROWS && cols >= 1 && cols <= MAX_COLS, device, rows, cols, out);
 } RSX_CATCH_ALL
 
 int rsx_kstrongest_destroy(rsx_kstrongest *h) try {
-  if (!h) return RSX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  delete h;
-  return RSX_OK;
+  return rsx::keypoints_destroy(h);
 } RSX_CATCH_ALL
 
 int rsx_kstrongest_extract_batch_device(rsx_kstrongest *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
                                         int32_t col_offset, const rsx_kstrongest_params *params, const float *d_azimuths,
                                         int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                         int32_t *d_counts, void *stream) try {
-  if (!h || !d_imgs || !d_targets || n_images < 0 || max_targets < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
-  if (d_xy && !d_azimuths) return fail(RSX_ERR_BAD_ARG, "d_xy needs d_azimuths");
-  rsx_kstrongest_params p;
-  RSX_TRY(get_params(params, &p));
-  if (n_images == 0) return RSX_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  RSX_TRY(h->order.enter(s));
-  return extract_device(h, d_imgs, image_stride_bytes, n_images, row_stride, col_offset, p, d_azimuths, azimuths_per_image ? h->rows : 0,
-                        resolution, max_targets, d_targets, d_xy, d_counts, s);
+  return rsx::keypoints_extract_batch_device(h, get_params, extract_device, d_imgs, n_images, image_stride_bytes, row_stride, col_offset, params,
+                                             d_azimuths, azimuths_per_image, resolution, d_targets, d_xy, max_targets, d_counts, stream);
 } RSX_CATCH_ALL
 
 int rsx_kstrongest_extract_batch(rsx_kstrongest *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
                                  int32_t col_offset, const rsx_kstrongest_params *params, const float *azimuths, int32_t azimuths_per_image,
                                  float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_counts) try {
-  if (!h || !imgs || !out_targets || !out_counts || n_images < 0 || max_targets < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  RSX_TRY(rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset));
-  if (out_xy && !azimuths) return fail(RSX_ERR_BAD_ARG, "out_xy needs azimuths");
-  rsx_kstrongest_params p;
-  RSX_TRY(get_params(params, &p));
-  if (n_images == 0) return RSX_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  RSX_TRY(h->order.enter(s));
-  const int mt = max_targets > 0 ? max_targets : 1;
-  auto extract = [&](const uint8_t *d_imgs, int n, const float *d_az, int *d_targets, float *d_xy, int *d_counts, hipStream_t st) {
-    return extract_device(h, d_imgs, (int64_t)h->rows * row_stride, n, row_stride, col_offset, p, d_az, azimuths_per_image ? h->rows : 0, resolution, mt, d_targets,
-                          d_xy, d_counts, st);
-  };
-  return h->stage.extract_batch(h->rows, imgs, n_images, image_stride_bytes, row_stride, azimuths, azimuths_per_image, out_targets, out_xy, max_targets,
-                                out_counts, s, extract);
+  return rsx::keypoints_extract_batch(h, get_params, extract_device, imgs, n_images, image_stride_bytes, row_stride, col_offset, params, azimuths,
+                                      azimuths_per_image, resolution, out_targets, out_xy, max_targets, out_counts);
 } RSX_CATCH_ALL
 
 int rsx_kstrongest_extract(rsx_kstrongest *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_kstrongest_params *params,
                            const float *azimuths, float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets,
                            int32_t *out_count) try {
-  if (!h || !img || !out_targets || !out_count || max_targets < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  return rsx_kstrongest_extract_batch(h, img, 1, (int64_t)h->rows * row_stride, row_stride, col_offset, params, azimuths, 0, resolution, out_targets,
-                                      out_xy, max_targets, out_count);
+  return rsx::keypoints_extract(h, get_params, extract_device, img, row_stride, col_offset, params, azimuths, resolution, out_targets, out_xy,
+                                max_targets, out_count);
 } RSX_CATCH_ALL
 
 }  // extern "C"

@@ -5,9 +5,9 @@
 // -> ORB descriptors -> BFMatcher knnMatch(2) + ratio against the previous scan -> ORORA (GNC rotation, A-COTE
 // translation) -> pose composition.  The sequence is on disk, so every scan and every consecutive pair is independent
 // until the final composition: a WINDOW of n scans goes through each stage in ONE launch chain --
-//     rsx_cen2019_extract_batch_device          n images   (csrc/cen2019.hip; or rsx_cen2018_extract_batch_device, csrc/cen2018.hip,
-//                                               after rsx_odometry_set_cen2018; or rsx_kstrongest_extract_batch_device,
-//                                               csrc/kstrongest.hip, after rsx_odometry_set_kstrongest)
+//     rsx_<extractor>_extract_batch_device      n images   the ONE selected extractor (rsx_odometry::keypoints): cen2019
+//                                               (csrc/cen2019.hip) until rsx_odometry_set_cen2018 (csrc/cen2018.hip) or
+//                                               rsx_odometry_set_kstrongest (csrc/kstrongest.hip) selects another
 //     rsx_frontend_cartesian_batch_device       n images   (csrc/frontend.hip)
 //     rsx_frontend_describe_batch_device        n keypoint sets
 //     rsx_frontend_match_consecutive_device     all consecutive pairs, both directions
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(64) void odo_cfear_results(const rsx_cfear_result *
 // The host enqueues M(g), then E(g + 2), and only then waits for M(g).
 constexpr int N_SETS = 3, N_LANES = 2;
 struct OdoSet {
-  rsx::DevBuf az, targets, xy, counts, desc, valid;  // slot 0 = the previous scan, slots 1 .. MAX_WINDOW = the window
+  rsx::DevBuf az, targets, xy, counts, desc, valid;  // slot 0 = the previous scan, slots 1 .. MAX_WINDOW = the window (whichever extractor wrote them)
   rsx::DevBuf sp, sp_counts, pt_begin, pt_end;  // CFEAR only: surface points [slot][RSX_CFEAR_MAX_SURFACE_POINTS], their counts, the point ranges
   rsx::PinnedBuf pin;  // pinned: counts[MAX_WINDOW + 1], pair_cnt[MAX_WINDOW], results[MAX_WINDOW], then the staged azimuth grids
 };
@@ -244,12 +244,11 @@ struct rsx_odometry {
   std::mutex mu;
   rsx::Stream lane_stream[N_LANES], match_stream, copy_stream;
   rsx::Event ev_up, ev_e[N_SETS], ev_m[N_SETS];
-  rsx::Owned<rsx_cen2019, rsx_cen2019_destroy> cen[N_LANES];
-  rsx::Owned<rsx_cen2018, rsx_cen2018_destroy> cen18[N_LANES];  // created at the first rsx_odometry_set_cen2018
-  bool use_cen2018 = false;
+  enum class Keypoints { cen2019, cen2018, kstrongest } keypoints = Keypoints::cen2019;  // the extractor E(g) runs (set_keypoints)
+  rsx::Owned<rsx_cen2019, rsx_cen2019_destroy> cen[N_LANES];  // (its parameters: prm.cen)
+  rsx::Owned<rsx_cen2018, rsx_cen2018_destroy> cen18[N_LANES];  // created at the first rsx_odometry_set_cen2018, kept across switches
   rsx_cen2018_params cen18_prm{};
-  rsx::Owned<rsx_kstrongest, rsx_kstrongest_destroy> kstr[N_LANES];  // created at the first rsx_odometry_set_kstrongest
-  bool use_kstrongest = false;  // (never together with use_cen2018)
+  rsx::Owned<rsx_kstrongest, rsx_kstrongest_destroy> kstr[N_LANES];  // created at the first rsx_odometry_set_kstrongest, kept across switches
   rsx_kstrongest_params kstr_prm{};
   rsx::Owned<rsx_frontend, rsx_frontend_destroy> fe[N_LANES];
   rsx::Owned<rsx_orora, rsx_orora_destroy> reg;
@@ -269,6 +268,7 @@ struct rsx_odometry {
 };
 
 using rsx::fail;
+using Keypoints = rsx_odometry::Keypoints;
 
 namespace {
 
@@ -319,8 +319,9 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
   return RSX_OK;
 }
 
-// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through cen2019 (or cen2018, or k-strongest), the Cartesian images and the
-// descriptors into set g % 3, then its last scan into slot 0 of the next set.  Asynchronous on the stream of lane g & 1.
+// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through the selected extractor, the Cartesian images and the
+// descriptors (CFEAR: the surface points) into set g % 3, then its last scan into slot 0 of the next set.  Asynchronous on the
+// stream of lane g & 1.
 int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, int64_t img_stride, int32_t row_stride, const float *azimuths,
                     int32_t azimuths_per_image) {
   const int lane = (int)(g & 1);
@@ -340,39 +341,43 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
     return extract_batch_device(cen, d_imgs, n, img_stride, row_stride, h->prm.col_offset, prm, q.az.as<float>(), azimuths_per_image,
                                 h->prm.radar_resolution, q.targets.as<int32_t>() + slot_xy, q.xy.as<float>() + slot_xy, K, d_counts + 1, s);
   };
-  RSX_TRY(h->use_kstrongest ? keypoints(rsx_kstrongest_extract_batch_device, h->kstr[lane].get(), &h->kstr_prm)
-          : h->use_cen2018  ? keypoints(rsx_cen2018_extract_batch_device, h->cen18[lane].get(), &h->cen18_prm)
-                            : keypoints(rsx_cen2019_extract_batch_device, h->cen[lane].get(), &h->prm.cen));
-  if (h->estimator == RSX_ESTIMATOR_CFEAR) {  // the surface points of every scan; no Cartesian image, no descriptors
-    constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
+  switch (h->keypoints) {
+    case Keypoints::cen2019: RSX_TRY(keypoints(rsx_cen2019_extract_batch_device, h->cen[lane].get(), &h->prm.cen)); break;
+    case Keypoints::cen2018: RSX_TRY(keypoints(rsx_cen2018_extract_batch_device, h->cen18[lane].get(), &h->cen18_prm)); break;
+    case Keypoints::kstrongest: RSX_TRY(keypoints(rsx_kstrongest_extract_batch_device, h->kstr[lane].get(), &h->kstr_prm)); break;
+  }
+  const bool cfear = h->estimator == RSX_ESTIMATOR_CFEAR;
+  constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
+  if (cfear) {  // the surface points of every scan; no Cartesian image, no descriptors
     hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 63) / 64), dim3(64), 0, s, d_counts + 1, n, (int64_t)K, 1, q.pt_begin.as<int64_t>(),
                        q.pt_end.as<int64_t>());
     RSX_HIP(hipGetLastError());
     RSX_TRY(rsx::cfear::launch_surface(q.xy.as<float>() + slot_xy, q.pt_begin.as<int64_t>(), q.pt_end.as<int64_t>(), n, h->cfear_prm,
                                        q.sp.as<rsx_cfear_surface_point>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
-    RSX_HIP(hipStreamWaitEvent(s, h->ev_m[(g + 1) % N_SETS], 0));  // the carry, as below
-    RSX_HIP(hipMemcpyAsync(nx.sp.p, q.sp.as<rsx_cfear_surface_point>() + (size_t)n * SP, SP * sizeof(rsx_cfear_surface_point),
-                           hipMemcpyDeviceToDevice, s));
-    RSX_HIP(hipMemcpyAsync(nx.sp_counts.p, q.sp_counts.as<int32_t>() + n, 4, hipMemcpyDeviceToDevice, s));
-    RSX_HIP(hipEventRecord(h->ev_e[g % N_SETS], s));
-    return RSX_OK;
+  } else {
+    // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
+    // how the sequence is cut into windows, and nothing about the grids is looked at on the host
+    RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
+                                                   azimuths_per_image ? (int64_t)h->rows : 0, h->prm.radar_resolution, s));
+    RSX_TRY(rsx_frontend_describe_batch_device(h->fe[lane].get(), q.xy.as<float>() + slot_xy, d_counts + 1, n, K, q.desc.as<uint8_t>() + (size_t)K * 32,
+                                               q.valid.as<uint8_t>() + (size_t)K, s));
   }
-  // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
-  // how the sequence is cut into windows, and nothing about the grids is looked at on the host
-  RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
-                                                 azimuths_per_image ? (int64_t)h->rows : 0, h->prm.radar_resolution, s));
-  RSX_TRY(rsx_frontend_describe_batch_device(h->fe[lane].get(), q.xy.as<float>() + slot_xy, d_counts + 1, n, K, q.desc.as<uint8_t>() + (size_t)K * 32,
-                                             q.valid.as<uint8_t>() + (size_t)K, s));
   // the last scan of the window becomes the previous scan of the next one (slot 0 of the next set, which M(g - 2) read; the
   // next window's own extraction, on the other lane, writes slots 1 .. n of that set only)
   RSX_HIP(hipStreamWaitEvent(s, h->ev_m[(g + 1) % N_SETS], 0));
-  RSX_HIP(hipMemcpyAsync(nx.xy.p, q.xy.as<float>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
-  RSX_HIP(hipMemcpyAsync(nx.desc.p, q.desc.as<uint8_t>() + (size_t)n * K * 32, (size_t)K * 32, hipMemcpyDeviceToDevice, s));
-  RSX_HIP(hipMemcpyAsync(nx.valid.p, q.valid.as<uint8_t>() + (size_t)n * K, (size_t)K, hipMemcpyDeviceToDevice, s));
-  RSX_HIP(hipMemcpyAsync(nx.counts.p, d_counts + n, 4, hipMemcpyDeviceToDevice, s));
-  if (h->estimator == RSX_ESTIMATOR_MCRANSAC || h->comp_on)  // the azimuth rows of the previous scan's keypoints: the dt (the
-                                                              // compensation) of the straddling pair
-    RSX_HIP(hipMemcpyAsync(nx.targets.p, q.targets.as<int32_t>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
+  if (cfear) {
+    RSX_HIP(hipMemcpyAsync(nx.sp.p, q.sp.as<rsx_cfear_surface_point>() + (size_t)n * SP, SP * sizeof(rsx_cfear_surface_point),
+                           hipMemcpyDeviceToDevice, s));
+    RSX_HIP(hipMemcpyAsync(nx.sp_counts.p, q.sp_counts.as<int32_t>() + n, 4, hipMemcpyDeviceToDevice, s));
+  } else {
+    RSX_HIP(hipMemcpyAsync(nx.xy.p, q.xy.as<float>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
+    RSX_HIP(hipMemcpyAsync(nx.desc.p, q.desc.as<uint8_t>() + (size_t)n * K * 32, (size_t)K * 32, hipMemcpyDeviceToDevice, s));
+    RSX_HIP(hipMemcpyAsync(nx.valid.p, q.valid.as<uint8_t>() + (size_t)n * K, (size_t)K, hipMemcpyDeviceToDevice, s));
+    RSX_HIP(hipMemcpyAsync(nx.counts.p, d_counts + n, 4, hipMemcpyDeviceToDevice, s));
+    if (h->estimator == RSX_ESTIMATOR_MCRANSAC || h->comp_on)  // the azimuth rows of the previous scan's keypoints: the dt (the
+                                                                // compensation) of the straddling pair
+      RSX_HIP(hipMemcpyAsync(nx.targets.p, q.targets.as<int32_t>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
+  }
   RSX_HIP(hipEventRecord(h->ev_e[g % N_SETS], s));
   return RSX_OK;
 }
@@ -545,6 +550,30 @@ int push_windows(rsx_odometry *h, int32_t n_scans, rsx_odometry_scan *out, float
   return st;
 }
 
+// rsx_odometry_set_cen2018 / rsx_odometry_set_kstrongest: params == NULL selects cen2019 again; otherwise extractor `which` with
+// *params (checked), its handle of every lane (h->*lanes) created when first needed and kept across later switches
+template <typename P, typename H, auto Destroy>
+int set_keypoints(rsx_odometry *h, Keypoints which, const P *params, int (*check_params)(const P &), int (*create)(int, int32_t, int32_t, H **),
+                  rsx::Owned<H, Destroy> (rsx_odometry::*lanes)[N_LANES], P rsx_odometry::*prm) {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one pair, one extractor)");
+  if (!params) {
+    h->keypoints = Keypoints::cen2019;
+    return RSX_OK;
+  }
+  RSX_TRY(check_params(*params));
+  for (auto &lane : h->*lanes) {
+    if (lane) continue;
+    H *c = nullptr;
+    RSX_TRY(create(h->device, h->rows, h->cols, &c));
+    lane.reset(c);
+  }
+  h->*prm = *params;
+  h->keypoints = which;
+  return RSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -627,45 +656,11 @@ int rsx_odometry_reset(rsx_odometry *h) try {
 int rsx_odometry_window(void) { return MAX_WINDOW; }
 
 int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params) try {
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one pair, one extractor)");
-  if (!params) {
-    h->use_cen2018 = h->use_kstrongest = false;
-    return RSX_OK;
-  }
-  RSX_TRY(rsx::cen2018_check_params(*params));
-  for (int l = 0; l < N_LANES; l++) {
-    if (h->cen18[l]) continue;
-    rsx_cen2018 *c = nullptr;
-    RSX_TRY(rsx_cen2018_create(h->device, h->rows, h->cols, &c));
-    h->cen18[l].reset(c);
-  }
-  h->cen18_prm = *params;
-  h->use_cen2018 = true;
-  h->use_kstrongest = false;
-  return RSX_OK;
+  return set_keypoints(h, Keypoints::cen2018, params, rsx::cen2018_check_params, rsx_cen2018_create, &rsx_odometry::cen18, &rsx_odometry::cen18_prm);
 } RSX_CATCH_ALL
 
 int rsx_odometry_set_kstrongest(rsx_odometry *h, const rsx_kstrongest_params *params) try {
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one pair, one extractor)");
-  if (!params) {
-    h->use_cen2018 = h->use_kstrongest = false;
-    return RSX_OK;
-  }
-  RSX_TRY(rsx::kstrongest_check_params(*params));
-  for (int l = 0; l < N_LANES; l++) {
-    if (h->kstr[l]) continue;
-    rsx_kstrongest *c = nullptr;
-    RSX_TRY(rsx_kstrongest_create(h->device, h->rows, h->cols, &c));
-    h->kstr[l].reset(c);
-  }
-  h->kstr_prm = *params;
-  h->use_kstrongest = true;
-  h->use_cen2018 = false;
-  return RSX_OK;
+  return set_keypoints(h, Keypoints::kstrongest, params, rsx::kstrongest_check_params, rsx_kstrongest_create, &rsx_odometry::kstr, &rsx_odometry::kstr_prm);
 } RSX_CATCH_ALL
 
 int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_params *params) try {

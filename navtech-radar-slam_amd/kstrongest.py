@@ -3,8 +3,6 @@ radar power image in, on every azimuth the k strongest returns above a power flo
 Cartesian points out.  Same shapes as cen2018.Cen2018 and cen2019.Cen2019."""
 import ctypes as C
 
-import numpy as np
-
 from ._keypoints import _Extractor
 from ._rsx import KStrongestParams, check, lib
 
@@ -35,20 +33,13 @@ class KStrongest(_Extractor):
     def extract(self, img, col_offset=11, k=12, z_min=60, min_range=58, max_range=0, min_separation=5, azimuths=None, resolution=0.0595,
                 max_targets=200000, return_count=False):
         """img: (rows, row_stride) uint8.  -> targets (n,2) int32 [, xy (n,2) float32 if azimuths] [, the full count]."""
-        tg, xy, count = self._extract(img, KStrongestParams(k, z_min, min_range, max_range, min_separation, 0), col_offset, azimuths, resolution,
-                                      max_targets)
-        res = (tg,) + ((xy,) if xy is not None else ()) + ((count,) if return_count else ())
-        return res if len(res) > 1 else res[0]
+        return self._extract(img, KStrongestParams(k, z_min, min_range, max_range, min_separation, 0), col_offset, azimuths, resolution,
+                             max_targets, return_count)
 
     def extract_batch(self, imgs, col_offset=11, k=12, z_min=60, min_range=58, max_range=0, min_separation=5, azimuths=None,
                       resolution=0.0595, max_targets=20000, return_counts=False):
         """imgs: (n, rows, row_stride) uint8 (any image stride) -> list of targets (k_i, 2) int32 [, list of xy (k_i, 2)
         float32] [, counts]; one chain of launches for the whole batch (rsx_kstrongest_extract_batch).  azimuths: (rows,)
         shared or (n, rows)."""
-        imgs = np.asarray(imgs, dtype=np.uint8)
-        if imgs.strides[1:] != (imgs.shape[2], 1):
-            imgs = np.ascontiguousarray(imgs)
-        tg, xy, counts = self._extract_batch(imgs, KStrongestParams(k, z_min, min_range, max_range, min_separation, 0), col_offset, azimuths,
-                                             resolution, max_targets)
-        res = (tg,) + ((xy,) if xy is not None else ()) + ((counts,) if return_counts else ())
-        return res if len(res) > 1 else res[0]
+        return self._extract_batch(imgs, KStrongestParams(k, z_min, min_range, max_range, min_separation, 0), col_offset, azimuths,
+                                   resolution, max_targets, return_counts)

@@ -81,38 +81,31 @@ class Odometry:
             raise TypeError("ransac must be RansacParams")
         check(self._L.rsx_odometry_set_estimator(self._h, ESTIMATORS[estimator], C.byref(ransac) if ransac is not None else None))
 
+    def _set(self, setter, default_params, params_type, params, off):
+        """One extractor / CFEAR setter of the library: off -> its NULL form; params None -> the library's defaults."""
+        if off:
+            check(setter(self._h, None))
+            return
+        p = params
+        if p is None:
+            p = params_type()
+            check(default_params(C.byref(p)))
+        check(setter(self._h, C.byref(p)))
+
     def set_cfear(self, cfear=None, off=False):
         """Switch to CFEAR surface points and point-to-line registration (cfear: CfearParams or None for the defaults), or back to
         ORORA with off=True.  Only while the handle holds no scan, and not while compensation is on."""
-        if off:
-            check(self._L.rsx_odometry_set_cfear(self._h, None))
-            return
-        p = cfear if cfear is not None else CfearParams()
-        if cfear is None:
-            check(self._L.rsx_cfear_default_params(C.byref(p)))
-        check(self._L.rsx_odometry_set_cfear(self._h, C.byref(p)))
+        self._set(self._L.rsx_odometry_set_cfear, self._L.rsx_cfear_default_params, CfearParams, cfear, off)
 
     def set_cen2018(self, cen2018=None, off=False):
         """Switch to cen2018 keypoints (cen2018: Cen2018Params or None for the defaults), or back to cen2019 with off=True.
         Only while the handle holds no scan (fresh, or after reset())."""
-        if off:
-            check(self._L.rsx_odometry_set_cen2018(self._h, None))
-            return
-        p = cen2018 if cen2018 is not None else Cen2018Params()
-        if cen2018 is None:
-            check(self._L.rsx_cen2018_default_params(C.byref(p)))
-        check(self._L.rsx_odometry_set_cen2018(self._h, C.byref(p)))
+        self._set(self._L.rsx_odometry_set_cen2018, self._L.rsx_cen2018_default_params, Cen2018Params, cen2018, off)
 
     def set_kstrongest(self, kstrongest=None, off=False):
         """Switch to k-strongest keypoints (kstrongest: KStrongestParams or None for the defaults) in place of whichever extractor
         was selected, or back to cen2019 with off=True.  Only while the handle holds no scan (fresh, or after reset())."""
-        if off:
-            check(self._L.rsx_odometry_set_kstrongest(self._h, None))
-            return
-        p = kstrongest if kstrongest is not None else KStrongestParams()
-        if kstrongest is None:
-            check(self._L.rsx_kstrongest_default_params(C.byref(p)))
-        check(self._L.rsx_odometry_set_kstrongest(self._h, C.byref(p)))
+        self._set(self._L.rsx_odometry_set_kstrongest, self._L.rsx_kstrongest_default_params, KStrongestParams, kstrongest, off)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
