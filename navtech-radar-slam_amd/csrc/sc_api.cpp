@@ -59,7 +59,7 @@ struct rsx_sc {
   struct QueryWs {
     DevBuf q_vkey, q_norm, q_rkey, partial;
     DevBuf f_qimg, f_lb, f_cand, f_cnt, f_thr, f_plan;  // filter path
-    DevBuf f_wimg, f_win;                               // window previews of the short lists (sc_window.hip)
+    DevBuf f_wimg, f_win, f_surv;                       // window previews of the short lists and what is left of them to score (sc_window.hip)
   } ws[2];
   QueryWs *w = &ws[0];  // the set the calls below work in (guarded by mu like the rest)
   PairProfiler prof;
@@ -331,6 +331,7 @@ int filter_reserve(rsx_sc *h, int64_t n_items, int64_t qb, hipStream_t s) {
   RSX_TRY(h->w->f_thr.reserve((size_t)qb * RESCORE_THR_STRIDE * sizeof(float), s, false));
   RSX_TRY(h->w->f_wimg.reserve(window_qimg_bytes((int32_t)qb), s, false));
   RSX_TRY(h->w->f_win.reserve((size_t)qb * WINDOW_P * sizeof(WindowPreview), s, false));
+  RSX_TRY(h->w->f_surv.reserve((size_t)qb * WINDOW_LIST_STRIDE * sizeof(WindowSurvivor), s, false));
   return RSX_OK;
 }
 
@@ -351,7 +352,7 @@ int filter_and_select(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_
   // alignment + window preview of the head of every short list on the matrix cores (what re-scoring would otherwise
   // do on the VALU, one entry per wavefront)
   return launch_window(db, q, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                       h->w->f_win.as<WindowPreview>(), s);
+                       h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s);
 }
 
 int rescore(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, const int64_t *elig, int32_t round_begin,
@@ -361,7 +362,7 @@ int rescore(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, 
   return launch_rescore(db_view(h), q, h->w->f_lb.as<lb_t>(), ld, n_items, n_eligible, elig, h->w->f_cand.as<RescoreEntry>(),
                         h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), filter_eps(), round_begin, round_end, tau_src,
                         seed, d_out, k, s, (h->prof.on && h->stats.p) ? h->stats.as<unsigned long long>() : nullptr,
-                        h->w->f_win.as<WindowPreview>());
+                        h->w->f_surv.as<WindowSurvivor>());
 }
 
 int32_t first_round_target() {
@@ -1383,7 +1384,7 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
       RSX_TRY(launch_select(db, lb, ld, items, nq, elig_all, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
                             h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
       RSX_TRY(launch_window(db, all, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                            h->w->f_win.as<WindowPreview>(), s));
+                            h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s));
       return rescore(h, all, items, elig_all, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, h->topk.as<rsx_sc_hit>(), s);
     };
     auto all_pieces = [&]() -> int {
@@ -1477,7 +1478,7 @@ int rsx_sc_query_bounds_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t 
     RSX_TRY(launch_select(db, h->w->f_lb.as<lb_t>(), ld, n_items, q.nq, n_elig, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
                           h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
     RSX_TRY(launch_window(db, q, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                          h->w->f_win.as<WindowPreview>(), s));
+                          h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s));
     RSX_TRY(rescore(h, q, n_items, n_elig, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, d_out + b0 * k, s));
   }
   return RSX_OK;
@@ -1769,12 +1770,10 @@ int rsx_sc_profile_read_rescoring(rsx_sc *h, rsx_sc_rescoring_stats *out) try {
     for (int c = 0; c < RESCORE_STAT_COPIES; c++)
       for (int i = 0; i < RESCORE_STAT_WORDS; i++) v[i] += all[(size_t)c * RESCORE_STAT_WORDS + i];
   }
-  if (rsx::exp_env("RSX_RESCORE_PROF") && v[1])  // region cycles of wave 0, averaged per scoring workgroup
-    fprintf(stderr, "[sc_rescore prof] per query (cycles of wave 0): load %.0f  phaseA %.0f  mergeA %.0f  phaseB %.0f  mergeX %.0f  gather %.0f  total %.0f\n",
+  if (rsx::exp_env("RSX_RESCORE_PROF") && v[1])  // region cycles of the re-scoring wave, averaged per query that scored
+    fprintf(stderr, "[sc_rescore prof] per query (cycles): start loads %.0f  round filter + touch %.0f  pick %.0f  phaseB %.0f  align %.0f  entry wait %.0f  total %.0f\n",
             (double)v[4] / v[1], (double)v[5] / v[1], (double)v[6] / v[1], (double)v[7] / v[1], (double)v[8] / v[1], (double)v[9] / v[1],
             (double)v[10] / v[1]);
-  if (rsx::exp_env("RSX_RESCORE_PROF") && v[1] && v[13])
-    fprintf(stderr, "[sc_rescore prof] wave kernel: header %.0f  records %.0f (then tau_ub = the 'phaseA' figure)\n", (double)v[13] / v[1], (double)v[14] / v[1]);
   *candidates = (int64_t)v[0];
   *exact_evals = v[2] ? (int64_t)v[2] : (int64_t)v[0];  // one-pass scoring: every candidate is an exact evaluation
   *queries_rescored = (int64_t)v[1];

@@ -136,6 +136,7 @@ static_assert(RESCORE_THR_HEAD_END < RESCORE_THR_STRIDE, "layout");
 // +0.15-0.23 ms on a 3.4 ms step); the host sums the blocks
 constexpr int RESCORE_STAT_WORDS = 24, RESCORE_STAT_COPIES = 64;
 struct WindowPreview;
+struct WindowSurvivor;
 struct RescoreEntry {
   float lb;      // filter bound
   int32_t slot;  // local DB slot
@@ -153,7 +154,7 @@ int launch_select(const DbView &db, const lb_t *lb, int64_t ld_lb, int64_t n_ite
 // (round_end = RESCORE_ALL_ROUNDS: also the entries beyond the short list); writes the top-k it knows.
 // List positions behind the head launch_select stored are taken from the row of bounds lb (bin by bin, ascending slot
 // inside a bin), so lb, ld_lb, n_items, n_eligible and q_elig must be the ones launch_select got.
-// win: the window records of launch_window for the same short lists (the head of every list);
+// surv: the survivor lists launch_window wrote for the same short lists (what of the head of every list is left to score);
 // tau_src (optional): a top-k that covers more than this shard -- its k-th distance caps tau;
 // seed (optional): this shard's hits from an earlier stage, merged into the output.
 constexpr int RESCORE_ALL_ROUNDS = RESCORE_NUM_THR + 1;
@@ -161,7 +162,7 @@ int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t
                    int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
                    const float *thr, double eps, int32_t round_begin, int32_t round_end, const rsx_sc_hit *tau_src,
                    const rsx_sc_hit *seed, rsx_sc_hit *d_out, int32_t k, hipStream_t s, unsigned long long *d_stats,
-                   const WindowPreview *win);
+                   const WindowSurvivor *surv);
 
 // ---- MFMA lower-bound filter (sc_filter.hip) ----
 constexpr int FILTER_QIMG_BYTES = 9984;  // LDS image of one query (two displaced fp16 copies)
@@ -226,12 +227,32 @@ struct WindowPreview {
                // (the others are more than 2 margins above the best preview); -1: not unique within the error bound -- pv is
                // then a lower bound only (union of the windows); -2: no record
 };
+// What the window kernel hands to the re-scoring kernel: per query one header and, behind it, the list positions below
+// min(sl_cnt, WINDOW_P) that can still reach the top-k, in any order.  tau_ub is the k-th smallest pv + WINDOW_MARGIN over ALL
+// records of the query with a unique alignment and a finite preview (+inf with fewer than k of them): every such record is a
+// distinct eligible entry of this shard's list, so tau_ub is an upper bound of the shard's final k-th best distance.  A
+// position is listed when pv - WINDOW_MARGIN <= tau_ub and its filter bound - eps <= tau_ub, or when its preview is NaN.
+struct WindowSurvivor {
+  float lo;      // pv - WINDOW_MARGIN: a lower bound of the pair distance; -inf: no preview (non-finite data), must be scored
+  int32_t slot;  // local DB slot
+  int32_t ks;    // (k* | shift mask << 8) as in WindowPreview, or -1: the alignment is not known
+  int32_t pos;   // short-list position (the rounds of a launch are position ranges)
+};
+struct WindowListHeader {
+  int32_t count;    // survivors behind the header
+  float tau_ub;     // see above
+  int32_t n_cand;   // (statistics) positions whose filter bound - eps does not exceed tau_ub and whose preview is not +inf
+  int32_t n_prev;   // (statistics) those of them with a preview
+};
+static_assert(sizeof(WindowSurvivor) == 16 && sizeof(WindowListHeader) == 16, "one 16-byte load each");
+constexpr int WINDOW_LIST_STRIDE = WINDOW_P + 1;  // 16-byte units per query: the header, then up to WINDOW_P survivors
 size_t window_qimg_bytes(int32_t nq);  // direct-filter images + key images of a query batch
 int launch_window_db_keys(const double *vkey, int64_t first, int64_t count, void *vk16, float *vk_n, hipStream_t s);
-// qimg: window_qimg_bytes(nq) of workspace (filled here); out: [nq][WINDOW_P]
+// qimg: window_qimg_bytes(nq) of workspace (filled here); out: [nq][WINDOW_P]; surv: [nq][WINDOW_LIST_STRIDE], the header of
+// EVERY query is written (an empty list included)
 // k: the top-k the query batch asks for; eps: the filter's error budget (filter_eps())
 int launch_window(const DbView &db, const QueryView &q, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt,
-                  int32_t k, double eps, WindowPreview *out, hipStream_t s);
+                  int32_t k, double eps, WindowPreview *out, WindowSurvivor *surv, hipStream_t s);
 const char *window_kernel_name();
 
 // ---- one query in one launch (sc_q1.hip): the live detector's regime, nq <= Q1_MAX_NQ ----

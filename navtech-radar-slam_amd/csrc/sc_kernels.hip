@@ -906,7 +906,7 @@ struct RescoreArgs {
   int32_t round_begin, round_end;  // rounds [begin, end) of the short list; end > RESCORE_NUM_THR: also the rest
   unsigned long long *stats;       // optional (bench instrumentation): [0] += candidates looked at, [1] += queries that scored
                                    // any, [2] += exact window evaluations (phase B), [15] += those of list positions behind the head, [16] += queries that walked behind the head
-  const WindowPreview *win;        // [nq][WINDOW_P] records of sc_window.hip; stats[3] += records used, stats[11] += exact alignments
+  const WindowSurvivor *surv;      // [nq][WINDOW_LIST_STRIDE] survivor lists of sc_window.hip; stats[3] += records used, stats[11] += exact alignments
 };
 
 template <int B, int W, int SO>
@@ -1046,10 +1046,10 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
 
 // ------------------------------------------------------------------------------------------
 // sc_rescore_wave_kernel: exact re-scoring behind the filter AND the window kernel (sc_window.hip), ONE WAVE per
-// query.  With the alignment k* and a preview of the pair distance already there for the head of the short list, what is
-// left per query is: pick the k-th smallest preview upper bound (an upper bound of the final k-th best distance), and
-// evaluate exactly -- phase B, ~13 entries per query -- the few entries whose preview lower bound does not exceed it, in
-// ascending order of that lower bound so that the exact k-th best takes over as early as possible.  No barriers, no
+// query.  The window kernel has the alignment k* and a preview of the pair distance for the head of the short list, takes the
+// k-th smallest preview upper bound (an upper bound of the final k-th best distance) and lists what can still reach it; what
+// is left per query is to evaluate exactly -- phase B, ~13 entries per query -- the listed entries, in
+// ascending order of their lower bound so that the exact k-th best takes over as early as possible.  No barriers, no
 // merges between waves, no imbalance between them (the 4-wave workgroup this kernel replaced spent 64 % of its wave
 // cycles waiting once its phase A was gone), and 9.0 KiB of LDS per query (the query image stays in fp32 and is
 // converted on the fly) instead of 40 KiB: 12 queries per CU in flight instead of 4.
@@ -1059,8 +1059,6 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
 // round_end), start from a tau bound over more shards (tau_src) and merge hits of an earlier stage (seed): the two stages
 // of a DB shard.
 // ------------------------------------------------------------------------------------------
-constexpr int RW_CH = (WINDOW_P + 63) / 64;  // window records per lane
-
 
 #ifndef RW_OCC
 #define RW_OCC 3  // waves per SIMD the register budget is set for (168 VGPRs, 13 spilled; 4 = 128 VGPRs with 98 spilled: 0.42 against 0.24 ms)
@@ -1072,6 +1070,44 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
   const int lane = threadIdx.x;
   const int qi = blockIdx.x;
   char *wsm = smem + WaveLds::OFF_ENT;
+
+  // ---- everything the wave needs first, requested together: the headers, this lane's survivor, the query ----
+  const int sl_cnt = a.sl_cnt[qi];
+  const float *thr = a.thr + (int64_t)qi * RESCORE_THR_STRIDE;
+  const int32_t *rcnt = reinterpret_cast<const int32_t *>(thr) + RESCORE_NUM_THR;
+  const float t_cap = thr[RESCORE_NUM_THR - 1];
+  const WindowSurvivor *sv = a.surv ? a.surv + (int64_t)qi * WINDOW_LIST_STRIDE : nullptr;
+  WindowListHeader hdr;
+  hdr.count = 0;
+  hdr.tau_ub = INFINITY;
+  hdr.n_cand = 0;
+  hdr.n_prev = 0;
+  WindowSurvivor first;  // list entry `lane` (whatever is there beyond the count is never looked at)
+  first.lo = INFINITY;
+  first.slot = 0;
+  first.ks = -1;
+  first.pos = 0;
+  if (sv) {
+    hdr = *reinterpret_cast<const WindowListHeader *>(sv);
+    first = sv[1 + lane];
+  }
+  {
+    const float4 *src = reinterpret_cast<const float4 *>(a.q.desc + (int64_t)qi * DS);
+    float4 *dst = reinterpret_cast<float4 *>(smem + WaveLds::OFF_QF32);
+    float4 x[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) x[i] = (lane + 64 * i < DS / 4) ? src[lane + 64 * i] : float4{0.f, 0.f, 0.f, 0.f};
+    const double kn = lane < NS ? a.q.norm[(int64_t)qi * NS + lane] : 0.0;
+    const double kv = lane < NS ? a.q.vkey[(int64_t)qi * NS + lane] : 0.0;
+#pragma unroll
+    for (int i = 0; i < 5; i++)
+      if (lane + 64 * i < DS / 4) dst[lane + 64 * i] = x[i];
+    if (lane < NS) {
+      reinterpret_cast<double *>(smem + WaveLds::OFF_QN1)[lane] = kn;
+      reinterpret_cast<double *>(smem + WaveLds::OFF_QV1)[lane] = kv;
+    }
+    wave_lds_fence();
+  }
 
   int64_t n_elig = a.n_eligible;
   if (a.q_elig) {
@@ -1102,20 +1138,20 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
     return t < tau_init ? t : tau_init;
   };
   double tau = kth_of(ld);
-  bool query_loaded = false;
   unsigned n_exact = 0, n_looked = 0, n_aligned = 0, n_shifts = 0, n_tail = 0;  // wave-uniform counters (stats)
-  unsigned nl_lane = 0, n_windowed = 0;               // per-lane counters, summed over the wave at the end
+  unsigned n_listed = 0, n_windowed = 0;  // (stats) from the list header: positions the window kernel's bound admits / with a preview
   bool walked_tail = false;
 
   // score one entry exactly (ks < 0: the alignment is not known yet)
-  // region cycles for RSX_RESCORE_PROF (experiments builds): [4] query load, [5] records + tau_ub, [6] picking the next
-  // survivor, [7] phase B, [8] exact alignments, [9] waiting for the entry's registers, [10] the whole wave
+  // region cycles for RSX_RESCORE_PROF (experiments builds): [4] headers + survivor + query load, [5] filtering + touching a
+  // round of survivors, [6] picking the next survivor, [7] phase B, [8] exact alignments, [9] waiting for the entry's
+  // registers, [10] the whole wave
 #ifdef RSX_EXPERIMENTS
   const bool timing = a.stats != nullptr;
 #else
   constexpr bool timing = false;
 #endif
-  long long tacc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  long long tacc[6] = {0, 0, 0, 0, 0, 0};
   long long t_mark = timing ? clock64() : 0;
   const long long t_begin = t_mark;
   auto lap = [&](int slot_) {
@@ -1136,25 +1172,6 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       ks = ksm & 63;
       const unsigned m7 = ((unsigned)ksm >> 8) & 0x7fu;
       if (m7) tmask = m7;
-    }
-    if (!query_loaded) {
-      const float4 *src = reinterpret_cast<const float4 *>(a.q.desc + (int64_t)qi * DS);
-      float4 *dst = reinterpret_cast<float4 *>(smem + WaveLds::OFF_QF32);
-      float4 x[5];
-#pragma unroll
-      for (int i = 0; i < 5; i++) x[i] = (lane + 64 * i < DS / 4) ? src[lane + 64 * i] : float4{0.f, 0.f, 0.f, 0.f};
-      const double kn = lane < NS ? a.q.norm[(int64_t)qi * NS + lane] : 0.0;
-      const double kv = lane < NS ? a.q.vkey[(int64_t)qi * NS + lane] : 0.0;
-#pragma unroll
-      for (int i = 0; i < 5; i++)
-        if (lane + 64 * i < DS / 4) dst[lane + 64 * i] = x[i];
-      if (lane < NS) {
-        reinterpret_cast<double *>(smem + WaveLds::OFF_QN1)[lane] = kn;
-        reinterpret_cast<double *>(smem + WaveLds::OFF_QV1)[lane] = kv;
-      }
-      query_loaded = true;
-      wave_lds_fence();
-      lap(0);  // [4]
     }
     if (ks < 0) {
       ks = align_exact<SO>(reinterpret_cast<const double *>(smem + WaveLds::OFF_QV1), wsm, lane, er.v);
@@ -1178,11 +1195,7 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
   };
 
   // ---- this launch's part of the short list: rounds [round_begin, round_end) = positions [i0, i1) ----
-  const int sl_cnt = a.sl_cnt[qi];
   const RescoreEntry *sl = a.slist + (int64_t)qi * RESCORE_SHORTLIST_CAP;
-  const float *thr = a.thr + (int64_t)qi * RESCORE_THR_STRIDE;
-  const int32_t *rcnt = reinterpret_cast<const int32_t *>(thr) + RESCORE_NUM_THR;
-  const float t_cap = thr[RESCORE_NUM_THR - 1];
   const int r_end = a.round_end < RESCORE_NUM_THR ? a.round_end : RESCORE_NUM_THR;
   auto upto = [&](int r) {  // list positions below round edge r - 1
     if (r <= 0) return 0;
@@ -1193,121 +1206,50 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
   if (timing) {
     int keep = i0 + i1;
     asm volatile("" : "+s"(keep));
-    lap(7);  // [13] header loads
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lap(0);  // [4] everything requested at wave start has arrived
   }
   bool done = false;  // some list entry's bound already exceeds tau: everything after it does too
 
-  // ---- the head of the list: window records (k*, preview) ----
+  // ---- the head of the list: what sc_window_kernel left of it (its survivor list) ----
+  // Why the window kernel's bound may be trusted.  Every pv + margin that enters hdr.tau_ub belongs to a DISTINCT entry of this
+  // shard's short list with a unique alignment and a finite preview, so its exact distance is at most that value; launch_select
+  // lists eligible entries only and the callers hand both launches the same limits, so each of them can be a hit of this query.
+  // The k-th smallest of them is therefore at least this shard's final k-th best distance -- whatever rounds this launch covers
+  // (stage 2: round_begin > 0), whatever seed / tau_src it starts from (they only lower tau), and for every caller (one batch,
+  // the host-buffer pieces, the self queries with per-query limits, bounds from filter shards).  An entry with dist >= lo >
+  // tau_ub is strictly worse than k others: no tie rule can involve it.  A position that is not in the list has lo > tau_ub, or
+  // a filter bound - eps > tau_ub (the positions pass 2 did not admit are of this kind: their bound exceeds the head's k-th
+  // upper bound, which is never below tau_ub), or a +inf preview (no effective column: never a hit).  NaN previews are listed
+  // with lo = -inf, NaN / -inf filter bounds never exclude, and the eligibility check stays at the evaluation.
   int pos_next = i0;
-  if (a.win && i0 < WINDOW_P && i0 < i1) {
-    const WindowPreview *wp = a.win + (int64_t)qi * WINDOW_P;
+  if (sv && i0 < WINDOW_P && i0 < i1) {
     const int pw = i1 < WINDOW_P ? i1 : WINDOW_P;
-    // per lane RW_CH records (positions i0 + lane + 64 j); only their lower bounds stay in registers -- the slot and k*
-    // of a survivor are read again when its turn comes (one uniform load, a candidate ahead of its use)
-    float lo[RW_CH], ub[RW_CH], flb[RW_CH];
-#pragma unroll
-    for (int j = 0; j < RW_CH; j++) {
-      const int pos = i0 + lane + 64 * j;
-      lo[j] = INFINITY;
-      ub[j] = INFINITY;
-      flb[j] = INFINITY;
-      if (pos < pw) {  // (chunks past pw cost one compare)
-        const RescoreEntry e = sl[pos];
-        const WindowPreview w = wp[pos];
-        const int64_t gidx = a.db.idx_base + (int64_t)e.slot * a.db.idx_stride;
-        if (gidx < n_elig && !((double)e.lb - a.eps > tau)) {
-          flb[j] = e.lb;
-          if (!(w.pv == w.pv)) {
-            lo[j] = -INFINITY;  // no preview (non-finite data, or no record: decided below): must be looked at
-          } else {
-            lo[j] = w.pv - WINDOW_MARGIN;  // +inf stays +inf: no effective column in the window, never a hit
-            if (w.ks >= 0 && w.pv < 3.0e38f) ub[j] = w.pv + WINDOW_MARGIN;
-          }
-        }
-      }
+    const int n_list = hdr.count < WINDOW_P ? hdr.count : WINDOW_P;
+    const double tau_ub = (double)hdr.tau_ub;
+    if (i0 == 0) {  // (stats) the launch that starts the list accounts for its records
+      n_listed = (unsigned)hdr.n_cand;
+      n_windowed = (unsigned)hdr.n_prev;
     }
-    if (timing) {
-      asm volatile("" : "+v"(lo[0]), "+v"(ub[0]));
-      lap(8);  // [14] record loads
-    }
-    // the k-th smallest of {exact hits so far} u {preview upper bounds}: an upper bound of the final k-th best
-    double ud = ld;
-    int ui = li, us = ls;
-    for (int it = 0; it < a.k; it++) {
-      float m = ub[0];
-#pragma unroll
-      for (int j = 1; j < RW_CH; j++) m = fminf(m, ub[j]);
-      const float wm = wave_min_f32(m);
-      if (!((double)wm < __shfl(ud, a.k - 1))) break;
-      const unsigned long long bal = __ballot(m == wm);
-      const int src = __ffsll((long long)bal) - 1;
-      if (lane == src) {
-        bool gone = false;
-#pragma unroll
-        for (int j = 0; j < RW_CH; j++)
-          if (!gone && ub[j] == wm) {
-            ub[j] = INFINITY;
-            gone = true;
-          }
-      }
-      topk_insert(ud, ui, us, lane, a.k, (double)wm, 0x40000000 + it, 0);  // the index only orders ties
-    }
-    const double tau_ub = kth_of(ud);
-    lap(1);  // [5]
-    // the filter bound once more, against the bound the previews give: this is what removes the entries the window
-    // kernel left without a record (their bound exceeds ITS k-th smallest upper bound, which is never below this one
-    // when this launch starts at the head of the list)
-#pragma unroll
-    for (int j = 0; j < RW_CH; j++)
-      if ((double)flb[j] - a.eps > tau_ub) lo[j] = INFINITY;  // flb = +inf: nothing here
-#pragma unroll
-    for (int j = 0; j < RW_CH; j++) {  // (stats) entries whose filter bound still admits them / those with a window record
-      nl_lane += (lo[j] < INFINITY) ? 1u : 0u;
-      n_windowed += (lo[j] > -INFINITY && lo[j] < INFINITY) ? 1u : 0u;
-    }
-    // Survivors.  A memory round trip costs this kernel ~10 k cycles (random 4.8-KB rows of a 48 MB array: RSX_RESCORE_PROF
-    // showed 25 k cycles per survivor when each one's records and registers were requested only when its turn came), so the
-    // survivors are first compacted into lanes (64 per round), their slots / k* fetched in ONE parallel round trip, the
-    // cache lines of ALL of them requested at once, and only then are they evaluated -- in ascending order of their lower
-    // bound, the registers of the next one in flight while the current one is evaluated.
-    struct Packed {
-      float lo;
-      int pos;
-    };
-    Packed *cbuf = reinterpret_cast<Packed *>(wsm);  // the entry region is free until the first evaluation of a round
-    for (;;) {
+    // Rounds of 64 survivors, one per lane.  A memory round trip costs this kernel ~10 k cycles (random 4.8-KB rows of a 48 MB
+    // array), so the cache lines of ALL survivors of a round are requested at once, and only then are they evaluated -- in
+    // ascending order of their lower bound, the registers of the next one in flight while the current one is evaluated.
+    for (int base = 0; base < n_list; base += 64) {
+      WindowSurvivor e = first;
+      if (base > 0 && base + lane < n_list) e = sv[1 + base + lane];
       const double t_now = tau < tau_ub ? tau : tau_ub;
-      int nsurv = 0;
-#pragma unroll
-      for (int j = 0; j < RW_CH; j++) {
-        const bool sv = lo[j] < INFINITY && !((double)lo[j] > t_now);
-        const unsigned long long bal = __ballot(sv);
-        const int rank = nsurv + __popcll(bal & ((1ull << lane) - 1ull));
-        if (sv && rank < 64) {
-          cbuf[rank] = Packed{lo[j], i0 + lane + 64 * j};
-          lo[j] = INFINITY;  // taken
-        }
-        nsurv += __popcll(bal);
-      }
-      if (nsurv == 0) break;  // (uniform)
-      nsurv = nsurv < 64 ? nsurv : 64;
-      wave_lds_fence();
-      float mylo = INFINITY;
-      int32_t myslot = 0;
-      int myks = -1;
-      if (lane < nsurv) {
-        const Packed c = cbuf[lane];
-        mylo = c.lo;
-        myslot = sl[c.pos].slot;
-        const int k_ = wp[c.pos].ks;
-        myks = k_ >= 0 ? k_ : -1;  // (k* | shift mask << 8) or "alignment unknown"
-      }
-      wave_lds_fence();
+      const bool mine = base + lane < n_list && e.pos >= i0 && e.pos < pw && !((double)e.lo > t_now);
+      float mylo = mine ? e.lo : INFINITY;
+      const int32_t myslot = e.slot;
+      const int myks = e.ks;  // (k* | shift mask << 8) or -1: alignment unknown
+      unsigned long long todo = __ballot(mine);
+      if (!todo) continue;  // (uniform)
       {
         Touch tch;
-        for (int i = 0; i < nsurv; i++) touch_entry(a.db, __shfl(myslot, i), lane, tch);
+        for (; todo; todo &= todo - 1) touch_entry(a.db, __shfl(myslot, __ffsll((long long)todo) - 1), lane, tch);
         touch_wait(tch);  // ONE round trip for all of them (they overlap); from here on the entries come out of the L2
       }
+      lap(1);  // [5]
       auto pick = [&](int32_t &slot, int &ks) -> float {  // the smallest lower bound left in this round
         const float wm = wave_min_f32(mylo);
         if (wm == INFINITY) return wm;
@@ -1456,15 +1398,9 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
     a.out[(int64_t)qi * a.k + lane] = h;
   }
   if (a.stats) {
-    unsigned lk = nl_lane, wd = n_windowed;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      lk += __shfl_xor(lk, off);
-      wd += __shfl_xor(wd, off);
-    }
     if (lane == 0) {
-      atomicAdd(a.stats, (unsigned long long)(lk + n_looked));
-      atomicAdd(a.stats + 3, (unsigned long long)wd);
+      atomicAdd(a.stats, (unsigned long long)(n_listed + n_looked));
+      atomicAdd(a.stats + 3, (unsigned long long)n_windowed);
       atomicAdd(a.stats + 2, (unsigned long long)n_exact);
       atomicAdd(a.stats + 11, (unsigned long long)n_aligned);
       atomicAdd(a.stats + 12, (unsigned long long)n_shifts);
@@ -1472,8 +1408,6 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       if (walked_tail) atomicAdd(a.stats + 16, 1ull);
       if (timing) {
         for (int i = 0; i < 6; i++) atomicAdd(a.stats + 4 + i, (unsigned long long)tacc[i]);
-        atomicAdd(a.stats + 13, (unsigned long long)tacc[7]);
-        atomicAdd(a.stats + 14, (unsigned long long)tacc[8]);
         atomicAdd(a.stats + 10, (unsigned long long)(clock64() - t_begin));
       }
       if (n_exact) atomicAdd(a.stats + 1, 1ull);
@@ -1485,7 +1419,7 @@ int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t
                    int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
                    const float *thr, double eps, int32_t round_begin, int32_t round_end, const rsx_sc_hit *tau_src,
                    const rsx_sc_hit *seed, rsx_sc_hit *d_out, int32_t k, hipStream_t s, unsigned long long *d_stats,
-                   const WindowPreview *win) {
+                   const WindowSurvivor *surv) {
   if (q.nq <= 0) return RSX_OK;
   if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k=%d out of range [1,%d]", k, RSX_SC_MAX_TOPK);
   RescoreArgs a;
@@ -1507,7 +1441,7 @@ int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t
   a.round_begin = round_begin;
   a.round_end = round_end;
   a.stats = d_stats;
-  a.win = win;
+  a.surv = surv;
   RSX_SO_DISPATCH(db.sum_order, hipLaunchKernelGGL(sc_rescore_wave_kernel<SO>, dim3(q.nq), dim3(64), WaveLds::SIZE, s, a));
   RSX_HIP(hipGetLastError());
   return RSX_OK;

@@ -21,6 +21,9 @@
 //     epilogue takes the minimum of d_k = 1 - S_k / n_eff(k) over the window of k* only.  |pv - dist| <= WINDOW_MARGIN
 //     (= the direct filter's error budget, sc_filter.hip: 2u + u^2 from the fp16 operands + 1200 * 2^-23 from the fp32
 //     accumulation + epilogue < 1.13e-3; shifts without an effective column are ignored on both sides).
+// Hand-over: the kernel ends by taking tau_ub_w, the k-th smallest pv + margin over all its records of the query, and writing the
+// positions that can still reach it as a dense survivor list behind a header (WindowSurvivor / WindowListHeader, sc_kernels.h),
+// which is all sc_rescore_wave_kernel reads of the head of the list.
 // Cost: 8192 queries x ~146 entries = 1.2 M pairs at 174 MFMAs per 32 = 0.21 Tflop: ~0.1 ms of matrix-core time against
 // the ~1.2 ms of VALU time it replaces.  The entries are gathered (2400 + 256 B each, whole rows of the entry-major
 // image hnR): 3.1 GB per batch out of a 27 MB database image, i.e. from L2 / MALL -- which is what bounds the kernel
@@ -106,6 +109,7 @@ struct WindowArgs {
   const RescoreEntry *slist;
   const int32_t *sl_cnt;
   WindowPreview *out;
+  WindowSurvivor *surv;  // [nq][WINDOW_LIST_STRIDE]: header + survivor list of every query
   double eps;  // the filter's error budget, as the re-scoring kernel applies it to a bound
   int32_t k;
 };
@@ -115,10 +119,26 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   __shared__ float s_ub[WINDOW_HEAD];
   __shared__ int s_pos[WINDOW_P];
   __shared__ int s_n2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ float s_tau;  // the head's k-th smallest upper bound, kept for the tail (a register across pass 2 would be spilled)
+  // what the workgroup knows of list position p once its group is done (filter bound, slot, preview, k* | shift mask); the
+  // positions no group takes are never read: they are not survivors
+  __shared__ float s_lb[WINDOW_P], s_pv[WINDOW_P], s_cand[WINDOW_P];
+  __shared__ int s_slot[WINDOW_P], s_ks[WINDOW_P];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: group counters in SGPRs)
   const int qi = blockIdx.x;
   const int sl_cnt = a.sl_cnt[qi];
-  if (sl_cnt <= 0) return;  // uniform
+  WindowSurvivor *list = a.surv + (int64_t)qi * WINDOW_LIST_STRIDE;
+  if (sl_cnt <= 0) {  // uniform; the re-scoring kernel still reads the header
+    if (threadIdx.x == 0) {
+      WindowListHeader h;
+      h.count = 0;
+      h.tau_ub = INFINITY;
+      h.n_cand = 0;
+      h.n_prev = 0;
+      *reinterpret_cast<WindowListHeader *>(list) = h;
+    }
+    return;
+  }
   {
     const uint4 *g0 = reinterpret_cast<const uint4 *>(a.qimg + (int64_t)qi * FILTER_QIMG_BYTES);
     const uint4 *g1 = reinterpret_cast<const uint4 *>(a.qkimg + (int64_t)qi * WINDOW_QK_BYTES);
@@ -135,10 +155,17 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   const char *ap = smem + ((n & 1) ? (FILTER_QIMG_ODD + 40 * n - 8) : (40 * n)) + 16 * hh;
   const char *kp = smem + FILTER_QIMG_BYTES + (n & 7) * QK_COPY + ((n & ~7) + 8 * hh) * 2;  // tile 1: + 64 B
 
-  // one group of 32 short-list entries (lane n and n + 32: entry at list position `pos`; have = the lane has one, else it
+  // the lane index as a value the compiler cannot follow: what is derived from it is computed again where it is used instead
+  // of being carried (and spilled) across the K loops
+  auto lane_again = [&]() -> int {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t & 31;
+  };
+  // one group of 32 short-list entries (lane n and n + 32: entry at list position pos_of(); have = the lane has one, else it
   // shadows position pos_any): writes the record, returns the upper bound of the pair distance the record implies
-  auto do_group = [&](int pos, bool have, int pos_any) -> float {
-    const int64_t slot = sl[have ? pos : pos_any].slot;
+  auto do_group = [&](auto pos_of, bool have, int pos_any) -> float {
+    const int64_t slot = sl[have ? pos_of() : pos_any].slot;
 
     // ---- alignment: 2 tiles x (hi*hi + hi*lo + lo*hi) x 4 K-steps ----
     floatx16 k0 = {0}, k1 = {0};
@@ -204,14 +231,93 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
     // ---- epilogue: max of S_k / n_eff(k) over the window of k* (n_eff from the two column masks, as the filter) ----
     __builtin_amdgcn_sched_barrier(0);
     const u64 em = a.cmask[slot];
-    const float pv = win::preview_of(acc0, acc1, qm, em, win, kstar, hh);
+    // (the query mask as a value the compiler cannot follow: its rotations are then formed here, per group, instead of once
+    // before pass 2 -- a dozen registers that did not fit and were spilled)
+    u64 qmg = qm;
+    asm volatile("" : "+v"(qmg));
+    const float pv = win::preview_of(acc0, acc1, qmg, em, win, kstar, hh);
     if (have && hh == 0) {
+      const int pos = pos_of();
       WindowPreview o;
       o.pv = pv;
       o.ks = kstar;
       a.out[(int64_t)qi * WINDOW_P + pos] = o;
+      s_slot[pos] = (int)slot;
+      s_pv[pos] = pv;
+      s_ks[pos] = kstar;
     }
     return (have && kstar >= 0 && pv < 3.0e38f) ? pv + WINDOW_MARGIN : INFINITY;  // NaN fails the compare
+  };
+
+  // ---- the tail (wave 0, after a barrier behind the last group): tau_ub_w = the k-th smallest upper bound over ALL records
+  // of the query, then the survivor list and its header.  tau_head: the k-th smallest upper bound of the head (+inf: not
+  // known) -- at least k upper bounds lie at or below it, so the k-th smallest of all is among those ----
+  auto write_list = [&](float tau_head, int n2) {
+    const int lim = sl_cnt < WINDOW_P ? sl_cnt : WINDOW_P;
+    const int nh = lim < WINDOW_HEAD ? lim : WINDOW_HEAD;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // the positions with a record, 64 at a time: the head, then what pass 2 admitted (s_pos); f(position, the lane has one)
+    auto records = [&](auto f) {
+      for (int p0 = 0; p0 < nh; p0 += 64) f(p0 + lane, p0 + lane < nh);
+      for (int c0 = 0; c0 < n2; c0 += 64) f(c0 + lane < n2 ? s_pos[c0 + lane] : 0, c0 + lane < n2);
+    };
+    int nc = 0;
+    records([&](int pos, bool in) {
+      const float pv = s_pv[pos];
+      const float ub = pv + WINDOW_MARGIN;
+      const bool c = in && s_ks[pos] >= 0 && pv < 3.0e38f && ub <= tau_head;  // NaN fails the compares
+      const unsigned long long bal = __ballot(c);
+      if (c) s_cand[nc + __popcll(bal & below)] = ub;
+      nc += __popcll(bal);
+    });
+    dev::wave_lds_fence();
+    float tau_w = INFINITY;
+    if (nc >= a.k) {  // rank by counting, as for the head; the ranks are a permutation of 0 .. nc - 1
+      for (int c0 = 0; c0 < nc; c0 += 64) {
+        const int i = c0 + lane;
+        const float v = i < nc ? s_cand[i] : INFINITY;
+        int r = 0;
+        for (int j = 0; j < nc; j++) {
+          const float x = s_cand[j];
+          r += (x < v || (x == v && j < i)) ? 1 : 0;
+        }
+        const unsigned long long b = __ballot(i < nc && r == a.k - 1);
+        if (b) {
+          tau_w = __shfl(v, __ffsll((long long)b) - 1);
+          break;
+        }
+      }
+    }
+    int ns = 0, n_cand = 0, n_prev = 0;
+    records([&](int pos, bool in) {
+      const float pv = s_pv[pos];
+      const int ks = s_ks[pos];
+      const bool none = in && !(pv == pv);  // no preview (non-finite data): must be looked at
+      const bool lb_ok = !((double)s_lb[pos] - a.eps > (double)tau_w);  // NaN / -inf bounds: always
+      const bool cand = in && (none || (pv < INFINITY && lb_ok));  // +inf: no effective column in the window, never a hit
+      const float lo = none ? -INFINITY : pv - WINDOW_MARGIN;
+      const bool sv = cand && !(lo > tau_w);
+      const unsigned long long bal = __ballot(sv);
+      if (sv) {
+        WindowSurvivor e;
+        e.lo = lo;
+        e.slot = s_slot[pos];
+        e.ks = (none || ks < 0) ? -1 : ks;
+        e.pos = pos;
+        list[1 + ns + __popcll(bal & below)] = e;
+      }
+      ns += __popcll(bal);
+      n_cand += __popcll(__ballot(cand));
+      n_prev += __popcll(__ballot(cand && !none));
+    });
+    if (lane == 0) {
+      WindowListHeader h;
+      h.count = ns;
+      h.tau_ub = tau_w;
+      h.n_cand = n_cand;
+      h.n_prev = n_prev;
+      *reinterpret_cast<WindowListHeader *>(list) = h;
+    }
   };
 
   // ---- pass 1: the head of the list ----
@@ -219,10 +325,24 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   {
     const int cnt1 = sl_cnt < WINDOW_HEAD ? sl_cnt : WINDOW_HEAD;
     float ub = INFINITY;
-    if (wave * 32 < cnt1) ub = do_group(wave * 32 + n, wave * 32 + n < cnt1, wave * 32);
+    if (wave * 32 < cnt1) ub = do_group([&] { return wave * 32 + lane_again(); }, wave * 32 + n < cnt1, wave * 32);
     if (hh == 0) s_ub[wave * 32 + n] = ub;
     __syncthreads();
-    if (sl_cnt <= WINDOW_HEAD) return;  // uniform
+    // the head's filter bounds for the tail: requested by the wave that runs it, here, so that no group waits for them
+    float lbh0 = INFINITY, lbh1 = INFINITY;
+    if (wave == 0) {
+      if (lane < cnt1) lbh0 = sl[lane].lb;
+      if (lane + 64 < cnt1) lbh1 = sl[lane + 64].lb;
+    }
+    if (sl_cnt <= WINDOW_HEAD) {  // uniform
+      if (wave == 0) {
+        s_lb[lane] = lbh0;
+        s_lb[lane + 64] = lbh1;
+        dev::wave_lds_fence();
+        write_list(INFINITY, 0);
+      }
+      return;
+    }
 
     // ---- the k-th smallest upper bound of the head: an upper bound of the final k-th best distance.  Only entries whose
     // filter bound does not exceed it can matter to the re-scoring kernel (whose own bound is at least as tight) ----
@@ -246,6 +366,10 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
       const float c0 = __shfl(v0, b0 ? __ffsll((long long)b0) - 1 : 0), c1 = __shfl(v1, b1 ? __ffsll((long long)b1) - 1 : 0);
       tau_ub = b0 ? c0 : c1;  // ranks are a permutation of 0..127: exactly one of the two ballots has a bit
     }
+    if (wave == 0) {
+      s_lb[lane] = lbh0;
+      s_lb[lane + 64] = lbh1;
+    }
   }
   // ---- pass 2: list positions WINDOW_HEAD .. WINDOW_P - 1 whose bound can still matter; the others get "no record" ----
   if (wave == 0) {
@@ -256,6 +380,7 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
       bool pass = false;
       if (pos < lim) {
         const float lb = sl[pos].lb;
+        s_lb[pos] = lb;
         pass = !((double)lb - a.eps > (double)tau_ub);  // NaN / -inf bounds: always
         if (!pass) {
           WindowPreview o;
@@ -268,14 +393,19 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
       if (pass) s_pos[n2 + __popcll(bal & ((1ull << lane) - 1ull))] = pos;
       n2 += __popcll(bal);
     }
-    if (lane == 0) s_n2 = n2;
+    if (lane == 0) {
+      s_n2 = n2;
+      s_tau = tau_ub;
+    }
   }
   __syncthreads();
   const int n2 = s_n2;
   for (int g = wave; g * 32 < n2; g += 4) {
     const bool have = g * 32 + n < n2;
-    (void)do_group(s_pos[have ? g * 32 + n : g * 32], have, s_pos[g * 32]);
+    (void)do_group([&] { return s_pos[g * 32 + lane_again()]; }, have, s_pos[g * 32]);  // (only lanes that have one ask)
   }
+  __syncthreads();
+  if (wave == 0) write_list(s_tau, n2);
 }
 
 }  // namespace
@@ -291,7 +421,7 @@ int launch_window_db_keys(const double *vkey, int64_t first, int64_t count, void
 }
 
 int launch_window(const DbView &db, const QueryView &q, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt,
-                  int32_t k, double eps, WindowPreview *out, hipStream_t s) {
+                  int32_t k, double eps, WindowPreview *out, WindowSurvivor *surv, hipStream_t s) {
   if (q.nq <= 0) return RSX_OK;
   char *img = static_cast<char *>(qimg);
   char *kimg = img + (size_t)q.nq * FILTER_QIMG_BYTES;
@@ -308,6 +438,7 @@ int launch_window(const DbView &db, const QueryView &q, void *qimg, const Rescor
   a.slist = slist;
   a.sl_cnt = sl_cnt;
   a.out = out;
+  a.surv = surv;
   a.eps = eps;
   a.k = k < 1 ? 1 : (k > WINDOW_HEAD ? WINDOW_HEAD : k);
   hipLaunchKernelGGL(sc_window_kernel, dim3((unsigned)q.nq), dim3(256), W_LDS, s, a);
