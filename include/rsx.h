@@ -738,6 +738,80 @@ int rsx_cfear_register_batch_device(rsx_cfear *h, const rsx_cfear_surface_point 
                                     const rsx_cfear_surface_point *d_dst, const int64_t *d_dst_offsets, int32_t n_pairs,
                                     const double *d_init, const rsx_cfear_params *params, rsx_cfear_result *d_out, void *stream);
 
+/* ---- CFEAR scan-to-keyframes registration and the keyframe tracker (csrc/cfear_track.hip) ----
+ * CFEAR registers a scan JOINTLY against the last few keyframes, from a constant-velocity prediction, and makes a new keyframe
+ * only after enough motion.  The rules are restated in tests/cfear_track_np.py (the arithmetic contract; parity unpinned).
+ * Poses are (x, y, yaw) with map = R(yaw) p + (x, y); A o B = (A.x + (c B.x - s B.y), A.y + (s B.x + c B.y), A.yaw + B.yaw) and
+ * A^-1 o B = (c dx + s dy, c dy - s dx, B.yaw - A.yaw) with c, s = cos, sin(A.yaw), (dx, dy) = B's position - A's; no yaw is wrapped.
+ * Joint registration: K keyframes (1 .. RSX_CFEAR_MAX_KEYFRAMES), each with records and a pose P_k in the map frame; the result
+ * is the scan's pose in the map frame.  Per iteration and keyframe the scan's pose is taken in the keyframe's frame (yaw_r = yaw -
+ * yaw_k, t_r = R(-yaw_k)((x, y) - (x_k, y_k))), correspondence, residual and weight are the pair rule's above, J = (R(yaw_k) n_j,
+ * n_j.(R'(yaw_r) mu_i)); H, g, cost and the correspondence count are summed over every (record, keyframe); then the pair rule's
+ * solve, step test and statuses.  Status 1: the src or every keyframe is empty (an empty keyframe among others is skipped); 2: a
+ * side above RSX_CFEAR_MAX_SURFACE_POINTS.  With K = 1 and P_1 = (0, 0, 0) the result equals rsx_cfear_register_batch's byte for
+ * byte.  The correspondence search goes through a 128 x 128 cell index of each keyframe (cell side = radius, built once per
+ * keyframe) or, search = 1, by brute force as in the pair kernel: the same bytes either way.
+ * Tracker, per sequence: state = the last pose P, the last motion M, a ring of at most n_keyframes keyframes.  Scan 0: P = 0, it is
+ * the first keyframe (flag 1), its registration result is all zero.  Scan i: start = P o M (predict) or P; registered against the
+ * ring.  Status 0 / 8: M = P^-1 o P_new, P = P_new, and the scan becomes a keyframe (flag 1, evicting the oldest of a full ring)
+ * when its distance from the NEWEST keyframe's pose is > keyframe_distance or |remainder(yaw - yaw_kf, 2 pi)| > keyframe_rotation.
+ * Status 1, 2, 4, 5: P = start, M stays, and a scan of 1 .. RSX_CFEAR_MAX_SURFACE_POINTS records becomes the ring's only entry
+ * at `start` (flag 2, re-anchored). */
+#define RSX_CFEAR_MAX_KEYFRAMES 4
+#define RSX_CFEAR_SEARCH_CELLS 0 /* rsx_cfear_track_params.search: the keyframe's cell index */
+#define RSX_CFEAR_SEARCH_BRUTE 1 /* every record of the keyframe */
+
+typedef struct {
+  double keyframe_distance; /* [m], >= 0 (1.5) */
+  double keyframe_rotation; /* [rad], >= 0 (5 deg) */
+  int32_t n_keyframes;      /* ring size, 1 .. RSX_CFEAR_MAX_KEYFRAMES (3) */
+  int32_t predict;          /* 1: start from the constant-velocity prediction P o M; 0: from P (1) */
+  int32_t search;           /* RSX_CFEAR_SEARCH_* (RSX_CFEAR_SEARCH_CELLS) */
+  int32_t reserved[3];      /* 0 */
+} rsx_cfear_track_params;
+
+typedef struct {
+  double x, y, yaw;     /* the scan's pose in the frame of the sequence's first scan */
+  rsx_cfear_result reg; /* of its registration against the ring (x, y, yaw: the pose it returned in that frame); scan 0: zeros */
+  int32_t keyframe;     /* 0 no; 1 the scan became a keyframe; 2 re-anchored: the ring was replaced by this scan */
+  int32_t n_keyframes;  /* keyframes it was registered against */
+} rsx_cfear_track_result; /* 80 bytes */
+
+int rsx_cfear_default_track_params(rsx_cfear_track_params *p);
+/* n_jobs jobs; job i registers src records [src_offsets[i], src_offsets[i + 1]) jointly to the keyframes [kf_job_offsets[i],
+ * kf_job_offsets[i + 1]) (1 .. RSX_CFEAR_MAX_KEYFRAMES of them, checked); keyframe g owns records [kf_offsets[g], kf_offsets[g + 1])
+ * of kf and the pose kf_poses[3 g ..]; init: [n_jobs][3] start poses in the map frame, NULL = identity.  Of `track` (NULL = the
+ * defaults) only `search` acts here.  Host buffers, synchronous.  One workgroup per job, one launch. */
+int rsx_cfear_register_keyframes_batch(rsx_cfear *h, const rsx_cfear_surface_point *src, const int64_t *src_offsets,
+                                       const rsx_cfear_surface_point *kf, const int64_t *kf_offsets, const int64_t *kf_job_offsets,
+                                       const double *kf_poses, int32_t n_jobs, const double *init, const rsx_cfear_params *params,
+                                       const rsx_cfear_track_params *track, rsx_cfear_result *out);
+/* device buffers, asynchronous on `stream`; the offsets are trusted: a job without a keyframe gets status 1, one with more than
+ * RSX_CFEAR_MAX_KEYFRAMES status 2.  The handle's index workspace grows with min(n_jobs, 256); no allocation otherwise */
+int rsx_cfear_register_keyframes_batch_device(rsx_cfear *h, const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets,
+                                              const rsx_cfear_surface_point *d_kf, const int64_t *d_kf_offsets,
+                                              const int64_t *d_kf_job_offsets, const double *d_kf_poses, int32_t n_jobs,
+                                              const double *d_init, const rsx_cfear_params *params,
+                                              const rsx_cfear_track_params *track, rsx_cfear_result *d_out, void *stream);
+
+/* n_sequences independent sequences tracked side by side, one workgroup each, the state (pose, motion, ring with its cell
+ * index) resident in HBM between calls */
+typedef struct rsx_cfear_tracker rsx_cfear_tracker;
+int rsx_cfear_tracker_create(int device, int32_t n_sequences, rsx_cfear_tracker **out);
+int rsx_cfear_tracker_destroy(rsx_cfear_tracker *h);
+/* every sequence starts again at its scan 0; the next push may carry other parameters */
+int rsx_cfear_tracker_reset(rsx_cfear_tracker *h);
+/* sequence q continues with its next n_scans[q] >= 0 scans; the scans lie sequence after sequence: scan j of this call's sum
+ * n_scans owns records [offsets[j], offsets[j + 1]) and gets out[j].  One launch over all scans of all sequences, no host round
+ * trip between scans.  Results do not depend on how a sequence is cut into pushes; params and track (NULL = defaults) must equal
+ * those of the previous push since create / reset (RSX_ERR_BAD_ARG otherwise).  Host buffers, synchronous. */
+int rsx_cfear_tracker_push(rsx_cfear_tracker *h, const rsx_cfear_surface_point *records, const int64_t *offsets, const int32_t *n_scans,
+                           const rsx_cfear_params *params, const rsx_cfear_track_params *track, rsx_cfear_track_result *out);
+/* device buffers (d_n_scans too), asynchronous on `stream`, no allocation; offsets trusted */
+int rsx_cfear_tracker_push_device(rsx_cfear_tracker *h, const rsx_cfear_surface_point *d_records, const int64_t *d_offsets,
+                                  const int32_t *d_n_scans, const rsx_cfear_params *params, const rsx_cfear_track_params *track,
+                                  rsx_cfear_track_result *d_out, void *stream);
+
 /* ============================== radar scan context ====================================
  * The "radar scan context" of the MulRan paper (Kim et al., ICRA 2020; reference README.md:28-29): the 20 x 60 polar grid
  * of the ScanContext descriptor filled with received power straight from the polar image -- dense where the descriptors of
@@ -934,6 +1008,14 @@ int rsx_odometry_set_compensation(rsx_odometry *h, const rsx_mocomp_params *para
  * into calls. */
 #define RSX_ESTIMATOR_CFEAR 3
 int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params);
+/* CFEAR's keyframe tracker (rsx_cfear_tracker above) in place of the registration of consecutive pairs: in a window ONE tracker
+ * launch over the window's scans replaces the registration launch; its state (pose, motion, ring of keyframes) lives in the handle
+ * and starts again with every new sequence (rsx_odometry_reset).  Accepted only while CFEAR is selected and the handle holds no
+ * scan; params = NULL goes back to pairs (as does leaving CFEAR); without this call nothing changes.  rsx_odometry_scan.reg carries
+ * the relative motion P_{i-1}^-1 o P_i of the tracked poses, with status, iterations and correspondences of the scan's registration
+ * against its keyframes as above (status 1, 2, 4, 5: the motion is the prediction's); the first scan's status stays 3.  Results do
+ * not depend on how the sequence is cut into calls. */
+int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_params *params);
 /* n_scans consecutive scans, host images image_stride_bytes apart (rows x row_stride bytes each); azimuths: rows floats
  * (rad, increasing) shared by all scans or n_scans x rows when azimuths_per_image != 0.  out [n_scans]; out_xy
  * (optional) [n_scans][max_xy][2]: the scan's keypoints in metres in the sensor frame (/orora/cloud_local).  Synchronous. */

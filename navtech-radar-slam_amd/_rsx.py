@@ -117,12 +117,21 @@ class CfearParams(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class CfearTrackParams(C.Structure):
+    _fields_ = [("keyframe_distance", C.c_double), ("keyframe_rotation", C.c_double), ("n_keyframes", C.c_int32), ("predict", C.c_int32),
+                ("search", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 CFEAR_MAX_POINTS, CFEAR_MAX_SURFACE_POINTS = 16384, 4096
+CFEAR_MAX_KEYFRAMES = 4
+CFEAR_SEARCH_CELLS, CFEAR_SEARCH_BRUTE = 0, 1  # rsx_cfear_track_params.search
 CFEAR_STATUS_RANGE, CFEAR_STATUS_POINTS = 1, 2  # scan status word
 CFEAR_SURFACE_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("lambda_max", "<f4"), ("lambda_min", "<f4"),
                                       ("n_points", "<i4"), ("cell", "<i4")])
 CFEAR_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("cost", "<f8"), ("iterations", "<i4"), ("correspondences", "<i4"),
                                ("status", "<i4"), ("reserved", "<i4")])
+CFEAR_TRACK_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("reg", CFEAR_RESULT_DTYPE), ("keyframe", "<i4"),
+                                     ("n_keyframes", "<i4")])
 
 
 class RadarScParams(C.Structure):
@@ -203,7 +212,9 @@ SYMBOLS = [
     "rsx_kstrongest_default_params", "rsx_kstrongest_create", "rsx_kstrongest_destroy", "rsx_kstrongest_extract",
     "rsx_kstrongest_extract_batch", "rsx_kstrongest_extract_batch_device", "rsx_odometry_set_kstrongest",
     "rsx_cfear_default_params", "rsx_cfear_create", "rsx_cfear_destroy", "rsx_cfear_surface_points_batch",
-    "rsx_cfear_surface_points_batch_device", "rsx_cfear_register_batch", "rsx_cfear_register_batch_device", "rsx_odometry_set_cfear",
+    "rsx_cfear_surface_points_batch_device", "rsx_cfear_register_batch", "rsx_cfear_register_batch_device", "rsx_odometry_set_cfear", "rsx_odometry_set_cfear_tracking",
+    "rsx_cfear_default_track_params", "rsx_cfear_register_keyframes_batch", "rsx_cfear_register_keyframes_batch_device",
+    "rsx_cfear_tracker_create", "rsx_cfear_tracker_destroy", "rsx_cfear_tracker_reset", "rsx_cfear_tracker_push", "rsx_cfear_tracker_push_device",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
@@ -345,6 +356,16 @@ def lib():
         L.rsx_cfear_register_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.POINTER(CfearParams), vp]
         L.rsx_cfear_register_batch_device.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.POINTER(CfearParams), vp, vp]
         L.rsx_odometry_set_cfear.argtypes = [vp, C.POINTER(CfearParams)]
+        L.rsx_odometry_set_cfear_tracking.argtypes = [vp, C.POINTER(CfearTrackParams)]
+        L.rsx_cfear_default_track_params.argtypes = [C.POINTER(CfearTrackParams)]
+        L.rsx_cfear_register_keyframes_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp]
+        L.rsx_cfear_register_keyframes_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(CfearParams),
+                                                                C.POINTER(CfearTrackParams), vp, vp]
+        L.rsx_cfear_tracker_create.argtypes = [C.c_int, i32, C.POINTER(vp)]
+        L.rsx_cfear_tracker_destroy.argtypes = [vp]
+        L.rsx_cfear_tracker_reset.argtypes = [vp]
+        L.rsx_cfear_tracker_push.argtypes = [vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp]
+        L.rsx_cfear_tracker_push_device.argtypes = [vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp, vp]
         L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
         L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
         L.rsx_radarsc_destroy.argtypes = [vp]

@@ -1,6 +1,18 @@
-// cfear.h -- what csrc/odometry.hip shares with csrc/cfear.hip beside the public entries of include/rsx.h.
+// cfear.h -- what csrc/cfear.hip, csrc/cfear_track.hip and csrc/odometry.hip share beside the public entries of include/rsx.h.
 #pragma once
+#include <mutex>
+
 #include "rsx_common.h"
+
+// the handle of the rsx_cfear entries (csrc/cfear.hip; the keyframe entries of csrc/cfear_track.hip work on it too)
+struct rsx_cfear {
+  int device = 0;
+  std::mutex mu;
+  rsx::Stream stream;
+  rsx::StreamOrder order;  // the staging buffers are shared by every host-buffer call
+  rsx::DevBuf in0, in1, off0, off1, init, out, cnt, st;  // staging of the host-buffer entries
+  rsx::DevBuf job_off, poses, index;  // keyframe entries: the jobs' keyframe ranges and poses (staging), the cell-index workspace
+};
 
 namespace rsx {
 namespace cfear {
@@ -17,6 +29,25 @@ int launch_surface(const float *d_xy, const int64_t *d_begin, const int64_t *d_e
 int launch_register(const rsx_cfear_surface_point *d_src, const int64_t *d_src_begin, const int64_t *d_src_end,
                     const rsx_cfear_surface_point *d_dst, const int64_t *d_dst_begin, const int64_t *d_dst_end, int32_t n_pairs,
                     const double *d_init, const rsx_cfear_params &p, rsx_cfear_result *d_out, hipStream_t s);
+
+
+// ---- csrc/cfear_track.hip: registration against keyframes, and the tracker ----
+int check_track_params(const rsx_cfear_track_params &p);
+// bytes of cell-index workspace launch_register_keyframes wants for n_jobs jobs
+size_t keyframe_index_bytes(int32_t n_jobs);
+// job i registers src group i jointly to the keyframes [d_kf_job_offsets[i], d_kf_job_offsets[i + 1]) (keyframe g owns records
+// [d_kf_offsets[g], d_kf_offsets[g + 1]) of d_kf and pose d_kf_poses[3 g ..]); d_init: [n_jobs][3] or null (identity)
+int launch_register_keyframes(const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets, const rsx_cfear_surface_point *d_kf,
+                              const int64_t *d_kf_offsets, const int64_t *d_kf_job_offsets, const double *d_kf_poses, int32_t n_jobs,
+                              const double *d_init, const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_index,
+                              rsx_cfear_result *d_out, hipStream_t s);
+// bytes of tracker state of one sequence (zero = a sequence that has seen no scan)
+size_t track_state_bytes();
+// sequence q (one workgroup) runs its d_n_scans[q] scans -- group sum(d_n_scans[0 .. q)) + i of (d_records, d_begin, d_end) is its
+// scan i -- through the tracker and writes one rsx_cfear_track_result per scan at the same index of d_out
+int launch_track(const rsx_cfear_surface_point *d_records, const int64_t *d_begin, const int64_t *d_end, const int32_t *d_n_scans,
+                 int32_t n_sequences, const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_state,
+                 rsx_cfear_track_result *d_out, hipStream_t s);
 
 }  // namespace cfear
 }  // namespace rsx

@@ -437,14 +437,6 @@ int rsx::cfear::launch_register(const rsx_cfear_surface_point *d_src, const int6
   return RSX_OK;
 }
 
-struct rsx_cfear {
-  int device = 0;
-  std::mutex mu;
-  rsx::Stream stream;
-  rsx::StreamOrder order;  // the staging buffers are shared by every host-buffer call
-  rsx::DevBuf in0, in1, off0, off1, init, out, cnt, st;  // staging of the host-buffer entries
-};
-
 namespace {
 
 int resolve_params(const rsx_cfear_params *params, rsx_cfear_params &dp) {

@@ -217,6 +217,35 @@ __global__ __launch_bounds__(64) void odo_cfear_results(const rsx_cfear_result *
   pair_cnt[j] = r.correspondences;
 }
 
+// CFEAR with keyframe tracking: the tracker's poses of the n scans of a window as the relative motions rsx_odometry_scan carries.
+// Pair (scan i - 1, scan i) gets P_{i-1}^-1 o P_i; the pose before scan 0 is prev (the last scan of the window before), which is then
+// replaced by this window's last pose.  One workgroup
+__global__ __launch_bounds__(64) void odo_cfear_track_results(const rsx_cfear_track_result *__restrict__ tr, int n, int first, double *prev,
+                                                              rsx_orora_result *__restrict__ out, int32_t *__restrict__ pair_cnt) {
+  for (int i = first + (int)threadIdx.x; i < n; i += 64) {
+    const rsx_cfear_track_result c = tr[i];
+    const double px = i > 0 ? tr[i - 1].x : prev[0], py = i > 0 ? tr[i - 1].y : prev[1], pyaw = i > 0 ? tr[i - 1].yaw : prev[2];
+    double sn, cs;
+    sincos(pyaw, &sn, &cs);
+    const double dx = c.x - px, dy = c.y - py;
+    rsx_orora_result o;
+    o.x = cs * dx + sn * dy;
+    o.y = cs * dy - sn * dx;
+    o.yaw = c.yaw - pyaw;
+    o.iterations = c.reg.iterations;
+    o.rot_inliers = o.trans_inliers = c.reg.correspondences;
+    o.status = c.reg.status;
+    out[i - first] = o;
+    pair_cnt[i - first] = c.reg.correspondences;
+  }
+  __syncthreads();  // (prev has been read)
+  if (threadIdx.x == 0) {
+    prev[0] = tr[n - 1].x;
+    prev[1] = tr[n - 1].y;
+    prev[2] = tr[n - 1].yaw;
+  }
+}
+
 }  // namespace
 
 // Round 6: several windows in flight.  A window is two stages: EXTRACTION (cen2019, Cartesian images, descriptors: the wide
@@ -258,6 +287,10 @@ struct rsx_odometry {
   rsx::DevBuf ransac_res, stage_dt, dt;  // allocated only with a RANSAC estimator (stage_dt, dt: MC-RANSAC)
   rsx_cfear_params cfear_prm{};  // estimator == RSX_ESTIMATOR_CFEAR (rsx_odometry_set_cfear)
   rsx::DevBuf cfear_res, sp_begin, sp_end;  // allocated only with CFEAR: results of a window, the record ranges of its slots
+  bool track_on = false;  // rsx_odometry_set_cfear_tracking: the keyframe tracker in place of the pair registration
+  rsx_cfear_track_params track_prm{};
+  rsx::DevBuf track_state, track_res, track_n, track_prev;  // allocated only with tracking: the sequence's state (csrc/cfear_track.hip), a
+                                                            // window's results, its scan count, the pose of the scan before it
   bool comp_on = false;  // rsx_odometry_set_compensation
   rsx_mocomp_params comp_prm{};
   rsx::DevBuf stage_acur, stage_aprev, a_cur, a_prev, src2, dst2, results2, xy_comp;  // allocated only with compensation
@@ -306,6 +339,12 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
     RSX_TRY(h->cfear_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_cfear_result), s, false));
     RSX_TRY(h->sp_begin.reserve(S * 8, s, false));
     RSX_TRY(h->sp_end.reserve(S * 8, s, false));
+    if (h->track_on) {
+      RSX_TRY(h->track_state.reserve(rsx::cfear::track_state_bytes(), s, false));
+      RSX_TRY(h->track_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_cfear_track_result), s, false));
+      RSX_TRY(h->track_n.reserve(4, s, false));
+      RSX_TRY(h->track_prev.reserve(24, s, false));
+    }
   } else if (h->estimator != RSX_ESTIMATOR_ORORA) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
   if (h->estimator == RSX_ESTIMATOR_MCRANSAC) {
     RSX_TRY(h->stage_dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
@@ -393,7 +432,19 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
   int32_t *d_counts = q.counts.as<int32_t>();
   const int first = h->have_prev ? 0 : 1, n_pairs = n - first;
   *first_out = first;
-  if (n_pairs > 0 && h->estimator == RSX_ESTIMATOR_CFEAR) {  // one registration launch over the pairs; src = slot first + j + 1, dst = slot first + j
+  if (h->estimator == RSX_ESTIMATOR_CFEAR && h->track_on) {  // one tracker launch over the window's scans (slots 1 .. n), its state in the handle
+    int64_t *b = h->sp_begin.as<int64_t>(), *e = h->sp_end.as<int64_t>();
+    if (!h->have_prev) RSX_HIP(hipMemsetAsync(h->track_state.p, 0, rsx::cfear::track_state_bytes(), s));  // a new sequence
+    hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 1 + 63) / 64), dim3(64), 0, s, q.sp_counts.as<int32_t>(), n + 1,
+                       (int64_t)RSX_CFEAR_MAX_SURFACE_POINTS, 0, b, e);
+    RSX_HIP(hipGetLastError());
+    RSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->track_n.p), n, 1, s));
+    RSX_TRY(rsx::cfear::launch_track(q.sp.as<rsx_cfear_surface_point>(), b + 1, e + 1, h->track_n.as<int32_t>(), 1, h->cfear_prm, h->track_prm,
+                                     h->track_state.p, h->track_res.as<rsx_cfear_track_result>(), s));
+    hipLaunchKernelGGL(odo_cfear_track_results, dim3(1), dim3(64), 0, s, h->track_res.as<rsx_cfear_track_result>(), n, first,
+                       h->track_prev.as<double>(), h->results.as<rsx_orora_result>(), h->pair_cnt.as<int32_t>());
+    RSX_HIP(hipGetLastError());
+  } else if (n_pairs > 0 && h->estimator == RSX_ESTIMATOR_CFEAR) {  // one registration launch over the pairs; src = slot first + j + 1, dst = slot first + j
     int64_t *b = h->sp_begin.as<int64_t>(), *e = h->sp_end.as<int64_t>();
     hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 1 + 63) / 64), dim3(64), 0, s, q.sp_counts.as<int32_t>(), n + 1,
                        (int64_t)RSX_CFEAR_MAX_SURFACE_POINTS, 0, b, e);
@@ -672,6 +723,7 @@ int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_
   if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
   if (estimator == RSX_ESTIMATOR_MCRANSAC && h->comp_on)
     return fail(RSX_ERR_BAD_ARG, "compensation is on: motion-compensated RANSAC has its own motion model (rsx_odometry_set_compensation(h, NULL) first)");
+  h->track_on = false;  // (tracking belongs to CFEAR)
   if (estimator == RSX_ESTIMATOR_ORORA) {
     h->estimator = estimator;
     return RSX_OK;
@@ -716,12 +768,28 @@ int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params) try 
   if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
   if (!params) {
     h->estimator = RSX_ESTIMATOR_ORORA;
+    h->track_on = false;
     return RSX_OK;
   }
   if (h->comp_on) return fail(RSX_ERR_BAD_ARG, "compensation is on: CFEAR registration has no matches to compensate (rsx_odometry_set_compensation(h, NULL) first)");
   RSX_TRY(rsx::cfear::check_params(*params));
   h->cfear_prm = *params;
   h->estimator = RSX_ESTIMATOR_CFEAR;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_params *params) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
+  if (!params) {
+    h->track_on = false;
+    return RSX_OK;
+  }
+  if (h->estimator != RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is not selected (rsx_odometry_set_cfear first)");
+  RSX_TRY(rsx::cfear::check_track_params(*params));
+  h->track_prm = *params;
+  h->track_on = true;
   return RSX_OK;
 } RSX_CATCH_ALL
 

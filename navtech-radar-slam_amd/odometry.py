@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, CfearParams, KStrongestParams, MocompParams,
+from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, CfearParams, CfearTrackParams, KStrongestParams, MocompParams,
                    OdometryParams, RansacParams, check, lib)
 
 ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_* ("cfear", RSX_ESTIMATOR_CFEAR, has a setter of its own)
@@ -23,14 +23,16 @@ class Odometry:
     estimator: "orora" (default), "ransac", "mcransac" or "cfear"; ransac: the RANSAC estimators' RansacParams (None:
     ransac.default_params()); cfear: CfearParams (None: cfear.default_params()): CFEAR's surface points and point-to-line
     registration in place of descriptors, matcher and estimator (rsx_odometry_set_cfear; pair it with keypoints="kstrongest",
-    min_separation = 0; not with compensate).
+    min_separation = 0; not with compensate).  cfear_track: True (the defaults) or a CfearTrackParams: CFEAR's keyframe tracker --
+    joint registration against the last keyframes from a constant-velocity prediction -- in place of the registration of
+    consecutive pairs (rsx_odometry_set_cfear_tracking; only with estimator="cfear").
     exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT).
     compensate: None (default), "motion", "doppler" or "both": every pair is estimated, its matches compensated with that
     estimate, and estimated again (rsx_odometry_set_compensation; not with "mcransac"); beta, dt_scan: the Doppler factor and
     the scan period of the model (None: the library's defaults)."""
 
     def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
-                 exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None, cfear=None):
+                 exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None, cfear=None, cfear_track=None):
         if keypoints not in ("cen2019", "cen2018", "kstrongest"):
             raise ValueError("keypoints must be cen2019, cen2018 or kstrongest")
         if estimator not in ESTIMATORS and estimator != "cfear":
@@ -53,6 +55,8 @@ class Odometry:
             self.set_kstrongest(kstrongest)
         if estimator == "cfear":
             self.set_cfear(cfear)
+            if cfear_track is not None and cfear_track is not False:
+                self.set_cfear_tracking(None if cfear_track is True else cfear_track)
         elif estimator != "orora":
             self.set_estimator(estimator, ransac)
         if compensate is not None:
@@ -96,6 +100,11 @@ class Odometry:
         """Switch to CFEAR surface points and point-to-line registration (cfear: CfearParams or None for the defaults), or back to
         ORORA with off=True.  Only while the handle holds no scan, and not while compensation is on."""
         self._set(self._L.rsx_odometry_set_cfear, self._L.rsx_cfear_default_params, CfearParams, cfear, off)
+
+    def set_cfear_tracking(self, track=None, off=False):
+        """Switch CFEAR to its keyframe tracker (track: CfearTrackParams or None for the defaults), or back to consecutive pairs with
+        off=True.  Only while CFEAR is selected and the handle holds no scan."""
+        self._set(self._L.rsx_odometry_set_cfear_tracking, self._L.rsx_cfear_default_track_params, CfearTrackParams, track, off)
 
     def set_cen2018(self, cen2018=None, off=False):
         """Switch to cen2018 keypoints (cen2018: Cen2018Params or None for the defaults), or back to cen2019 with off=True.
