@@ -37,6 +37,7 @@ struct rsx_sc {
   DevBuf desc, vkey, norm, rkey;
   DevBuf hn, cmask;  // fp16 filter image (tile-major) + column masks (sc_filter.hip)
   DevBuf sp, sp_aux; // fp16 spectral filter image + per-entry error-budget scalar (sc_spec.hip)
+  DevBuf sp_tw;      // the twiddle table its image kernels read, filled when the handle is created
   DevBuf hnr, vk16, vk_n;  // entry-major fp16 image + fp16 hi/lo sector keys and their norms (sc_window.hip)
   // detector state (SC.h:104,117-120)
   int tree_counter = 0;
@@ -59,7 +60,7 @@ struct rsx_sc {
   struct QueryWs {
     DevBuf q_vkey, q_norm, q_rkey, partial;
     DevBuf f_qimg, f_lb, f_cand, f_cnt, f_thr, f_plan;  // filter path
-    DevBuf f_wimg, f_win, f_surv;                       // window previews of the short lists and what is left of them to score (sc_window.hip)
+    DevBuf f_win, f_surv;                               // window previews of the short lists and what is left of them to score (sc_window.hip)
   } ws[2];
   QueryWs *w = &ws[0];  // the set the calls below work in (guarded by mu like the rest)
   PairProfiler prof;
@@ -135,7 +136,8 @@ int own_stream(rsx_sc *h) {
 int insert_cloud(rsx_sc *h, const void *d_pts, int64_t n_pts, int64_t stride, int64_t slot, hipStream_t s) {
   return launch_insert(d_pts, nullptr, n_pts, 1, stride, h->p.lidar_height, h->p.max_radius, slot, h->desc.as<float>(),
                        h->vkey.as<double>(), h->norm.as<double>(), h->rkey.as<float>(), h->hn.p, h->hnr.p,
-                       h->cmask.as<uint64_t>(), h->sp.p, h->sp_aux.as<float>(), h->vk16.p, h->vk_n.as<float>(), s, h->p.sum_order);
+                       h->cmask.as<uint64_t>(), h->sp.p, h->sp_aux.as<float>(), h->sp_tw.as<double>(), h->vk16.p, h->vk_n.as<float>(), s,
+                       h->p.sum_order);
 }
 
 int ensure_capacity(rsx_sc *h, int64_t want_local) {
@@ -181,7 +183,8 @@ DbView db_view(const rsx_sc *h) {
 int build_db_images(rsx_sc *h, int64_t slot, int64_t count, hipStream_t s) {
   RSX_TRY(launch_db_images(h->desc.as<float>(), h->norm.as<double>(), slot, count, h->hn.p, h->hnr.p, h->cmask.as<uint64_t>(), s));
   RSX_TRY(launch_window_db_keys(h->vkey.as<double>(), slot, count, h->vk16.p, h->vk_n.as<float>(), s));
-  RSX_TRY(launch_spec_db_images(h->desc.as<float>(), h->norm.as<double>(), slot, count, h->sp.p, h->sp_aux.as<float>(), s));
+  RSX_TRY(launch_spec_db_images(h->desc.as<float>(), h->norm.as<double>(), slot, count, h->sp.p, h->sp_aux.as<float>(),
+                                h->sp_tw.as<double>(), s));
   RSX_HIP(hipStreamSynchronize(s));
   return RSX_OK;
 }
@@ -300,7 +303,7 @@ int run_filter(rsx_sc *h, const QueryView &q, int64_t n_items, lb_t *lb, int64_t
   if (filter_kind_of(h) >= 1) {
     const bool two_waves = filter_kind_of(h) == 2;
     h->prof_kernel = two_waves ? spec2_filter_kernel_name() : spec_filter_kernel_name();
-    RSX_TRY(launch_spec_query_images(q.desc, q.norm, q.nq, h->w->f_qimg.p, s));
+    RSX_TRY(launch_spec_query_images(q.desc, q.norm, q.nq, h->w->f_qimg.p, h->sp_tw.as<double>(), s));
     const int32_t *qmin = nullptr;
     const int64_t *cum = nullptr;
     if (plan) RSX_TRY(launch_filter_plan(db, *plan, q.nq, n_items, 4, h->w->f_plan.p, &qmin, &cum, s));
@@ -329,7 +332,6 @@ int filter_reserve(rsx_sc *h, int64_t n_items, int64_t qb, hipStream_t s) {
   RSX_TRY(h->w->f_cand.reserve((size_t)qb * RESCORE_SHORTLIST_CAP * sizeof(RescoreEntry), s, false));
   RSX_TRY(h->w->f_cnt.reserve((size_t)qb * sizeof(int32_t), s, false));
   RSX_TRY(h->w->f_thr.reserve((size_t)qb * RESCORE_THR_STRIDE * sizeof(float), s, false));
-  RSX_TRY(h->w->f_wimg.reserve(window_qimg_bytes((int32_t)qb), s, false));
   RSX_TRY(h->w->f_win.reserve((size_t)qb * WINDOW_P * sizeof(WindowPreview), s, false));
   RSX_TRY(h->w->f_surv.reserve((size_t)qb * WINDOW_LIST_STRIDE * sizeof(WindowSurvivor), s, false));
   return RSX_OK;
@@ -351,7 +353,7 @@ int filter_and_select(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_
                         h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
   // alignment + window preview of the head of every short list on the matrix cores (what re-scoring would otherwise
   // do on the VALU, one entry per wavefront)
-  return launch_window(db, q, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
+  return launch_window(db, q, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
                        h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s);
 }
 
@@ -689,6 +691,10 @@ int rsx_sc_create(const rsx_sc_params *p, rsx_sc **out) try {
   hipError_t e = h->stream.create();
   if (e != hipSuccess) return fail(RSX_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
   RSX_TRY(ensure_capacity(h.get(), d.capacity_hint > 0 ? d.capacity_hint : 1024));
+  // the spectra's twiddle table: once per handle, complete before any other stream can ask for it
+  RSX_TRY(h->sp_tw.reserve(SPEC_TWIDDLE_DOUBLES * sizeof(double), h->stream, false));
+  RSX_TRY(launch_spec_twiddles(h->sp_tw.as<double>(), h->stream));
+  RSX_HIP(hipStreamSynchronize(h->stream));
   *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -1383,7 +1389,7 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
       const DbView db = db_view(h);
       RSX_TRY(launch_select(db, lb, ld, items, nq, elig_all, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
                             h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
-      RSX_TRY(launch_window(db, all, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
+      RSX_TRY(launch_window(db, all, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
                             h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s));
       return rescore(h, all, items, elig_all, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, h->topk.as<rsx_sc_hit>(), s);
     };
@@ -1477,7 +1483,7 @@ int rsx_sc_query_bounds_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t 
     RSX_TRY(launch_gather_bounds(reinterpret_cast<const lb_t *>(d_lb_blocks), block_ld, block_stride, b0, q.nq, h->w->f_lb.as<lb_t>(), ld, s));
     RSX_TRY(launch_select(db, h->w->f_lb.as<lb_t>(), ld, n_items, q.nq, n_elig, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
                           h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
-    RSX_TRY(launch_window(db, q, h->w->f_wimg.p, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
+    RSX_TRY(launch_window(db, q, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
                           h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s));
     RSX_TRY(rescore(h, q, n_items, n_elig, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, d_out + b0 * k, s));
   }

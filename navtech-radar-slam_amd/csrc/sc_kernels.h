@@ -99,8 +99,8 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
 // (d_offs = nullptr: one cloud of n_pts points)
 int launch_insert(const void *d_pts, const int64_t *d_offs, int64_t n_pts, int64_t n_clouds, int64_t stride_bytes,
                   double lidar_height, double max_radius, int64_t first_slot, float *desc, double *vkey, double *norm,
-                  float *rkey, void *hnT, void *hnR, uint64_t *cmask, void *spT, float *aux, void *vk16, float *vk_n,
-                  hipStream_t s, int sum_order);
+                  float *rkey, void *hnT, void *hnR, uint64_t *cmask, void *spT, float *aux, const double *tw, void *vk16,
+                  float *vk_n, hipStream_t s, int sum_order);
 
 // merge [nparts][nq][k] -> [nq][k]
 int launch_merge(const rsx_sc_hit *d_parts, int32_t nparts, int32_t nq, int32_t k, rsx_sc_hit *d_out,
@@ -199,9 +199,13 @@ const char *filter_kernel_name();
 constexpr int SPEC_QIMG_BYTES = 4736;       // stream image of a query (sc_spec.hip); the mask image and flag byte follow the images
 constexpr int SPEC_DB_BYTES_PER_ENTRY = 2432;
 size_t spec_qimg_bytes(int32_t nq);
+// tw: the twiddle table of the spectra, SPEC_TWIDDLE_DOUBLES doubles of device memory filled once by launch_spec_twiddles (with
+// the device's own cospi / sinpi: every image kernel below reads it instead of evaluating the 15 factors per wavefront)
+constexpr int SPEC_TWIDDLE_DOUBLES = 32;
+int launch_spec_twiddles(double *tw, hipStream_t s);
 int launch_spec_db_images(const float *desc, const double *norm, int64_t first, int64_t count, void *spT, float *aux,
-                          hipStream_t s);
-int launch_spec_query_images(const float *desc, const double *norm, int32_t nq, void *qimg, hipStream_t s);
+                          const double *tw, hipStream_t s);
+int launch_spec_query_images(const float *desc, const double *norm, int32_t nq, void *qimg, const double *tw, hipStream_t s);
 // two_waves: sc_spec2_filter_kernel (two waves per SIMD, the entry tile split by frequency) instead of sc_spec_filter_kernel;
 // same images, same bounds bit for bit
 int launch_spec_filter(const DbView &db, const void *qimg, int32_t nq, int64_t n_items, lb_t *lb, int64_t ld_lb,
@@ -246,12 +250,11 @@ struct WindowListHeader {
 };
 static_assert(sizeof(WindowSurvivor) == 16 && sizeof(WindowListHeader) == 16, "one 16-byte load each");
 constexpr int WINDOW_LIST_STRIDE = WINDOW_P + 1;  // 16-byte units per query: the header, then up to WINDOW_P survivors
-size_t window_qimg_bytes(int32_t nq);  // direct-filter images + key images of a query batch
 int launch_window_db_keys(const double *vkey, int64_t first, int64_t count, void *vk16, float *vk_n, hipStream_t s);
-// qimg: window_qimg_bytes(nq) of workspace (filled here); out: [nq][WINDOW_P]; surv: [nq][WINDOW_LIST_STRIDE], the header of
-// EVERY query is written (an empty list included)
+// q: the kernel builds the queries' fp16 image and key image itself, in LDS, from q.desc / q.norm / q.vkey; out: [nq][WINDOW_P];
+// surv: [nq][WINDOW_LIST_STRIDE], the header of EVERY query is written (an empty list included)
 // k: the top-k the query batch asks for; eps: the filter's error budget (filter_eps())
-int launch_window(const DbView &db, const QueryView &q, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt,
+int launch_window(const DbView &db, const QueryView &q, const RescoreEntry *slist, const int32_t *sl_cnt,
                   int32_t k, double eps, WindowPreview *out, WindowSurvivor *surv, hipStream_t s);
 const char *window_kernel_name();
 

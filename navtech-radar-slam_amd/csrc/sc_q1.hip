@@ -9,7 +9,8 @@
 //
 // One launch, a grid of <= 512 four-wave workgroups (two per CU), each walking the 32-entry tiles b, b + G, b + 2G, ...:
 //   prep      every workgroup builds the query's images in LDS itself (sector key, column norms, the fp16 image of the
-//             direct filter and the fp16 hi/lo key circulant: the bodies of sc_keys / sc_img_query / sc_win_query_keys),
+//             direct filter and the fp16 hi/lo key circulant: the device functions behind sc_keys_kernel, sc_img_query_kernel
+//             and the prologue of sc_window_kernel),
 //             while the first tile's database fragments are already in flight;
 //   stream    per tile the fp16 image of the 32 entries (tile-major hnT: 75 coalesced 1-KiB fragments, 2400 B per entry)
 //             is cut BY K over the four waves (19 K-steps each: every wave has its whole share in flight at once -- one
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
   };
   if (b < ntiles) issue(b, 0);
 
-  // ---- the query's images, built here (what sc_keys / sc_img_query / sc_win_query_keys do for a batch): wave 0 the column
+  // ---- the query's images, built here (what sc_keys_kernel, sc_img_query_kernel and the window kernel's prologue do for a batch): wave 0 the column
   // norms + normalised columns (and the fp32 copy the exact evaluation reads), wave 1 the doubled hi / lo key, then every
   // thread a share of the two displaced image copies and the 16 displaced key copies ----
   if (tid < 32) s_ub[tid] = INFINITY;

@@ -180,40 +180,81 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // ------------------------------------------------------------------------------------------
-// spectra of one descriptor (one wave): xn = column-normalised image (fp64, in LDS), kv = the 1216
+// the 15 twiddle factors e^(-2 pi i m / 15) of the Z15 transform: [0..15) cos, [16..31) sin, 32 doubles per device, filled once
+// per handle by the device's own cospi / sinpi (the values spectra_of used to evaluate in every wavefront; the host's libm is
+// not the device's, so the table is never computed on the host)
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void sc_spec_twiddle_kernel(double *__restrict__ tw) {
+  const int lane = threadIdx.x;
+  if (lane < 15) {
+    tw[lane] = cospi(2.0 * lane / 15.0);
+    tw[16 + lane] = sinpi(2.0 * lane / 15.0);
+  } else if (lane == 15 || lane == 31) {
+    tw[lane] = 0.0;
+  }
+}
+
+// what one wave stages of its descriptor: the elements as they are and one reciprocal norm per column (5280 B; until round 9
+// the normalised image as doubles, 9.9 KB, which held sc_spec_query_kernel to two waves per SIMD)
+struct alignas(16) SpecStage {
+  float d[DS];    // [column][ring], as in global memory
+  double rn[NS];  // 1 / column norm
+};
+// the staging of sc_insert_kernel, where ONE wave per launch runs the transform and LDS is not what limits anything: the
+// normalised image as doubles, [ring][column], so that the transform reads a value with one ds_read_b64 (with SpecStage that
+// wave's chain was 1.4 us longer per insert, 18.9 us against 17.5; this way 17.3)
+struct SpecStage64 {
+  double x[DS];
+};
+
+// ------------------------------------------------------------------------------------------
+// spectra of one descriptor (one wave): st = staging (LDS), tw = the twiddle table, kv = the 1216
 // fp16 K-vector  [ f = 0: 4 x (20 values + 4 zeros) | f = 1..7: 4 x (20 re + 20 im) ]
 // returns the column mask (bit j = column j non-zero, bit 63 = non-finite element)
 // ------------------------------------------------------------------------------------------
 // QIMG: kv is the stream image of a query instead (f = 0: the same 96 halves; f >= 1: 320 halves, the re stream
 // 4 x [re 20 | im 20] followed by the im stream 4 x [im 20 | -re 20])
-template <bool QIMG>
-__device__ __forceinline__ u64 spectra_of(const float *__restrict__ d, const double *__restrict__ nrm, double *xn,
-                                          _Float16 *kv, int lane, float &sqrt_a) {
+template <bool QIMG, typename Stage>
+__device__ __forceinline__ u64 spectra_of(const float *__restrict__ d, const double *__restrict__ nrm,
+                                          const double *__restrict__ tw, Stage *st, _Float16 *kv, int lane, float &sqrt_a) {
+  constexpr bool kStage64 = std::is_same<Stage, SpecStage64>::value;
   bool nonzero = false, bad = false;
   if (lane < NS) {
     const double n = nrm[lane];
     nonzero = !(n == 0.0);  // SC.cpp:78: a column takes part unless its norm == 0
     const double rn = 1.0 / n;  // one division per column (x * (1 / n): 2 ulp of fp64 from x / n, the image is fp16)
+    if constexpr (kStage64) {
 #pragma unroll
-    for (int r = 0; r < NR; r++) {
-      const double y = nonzero ? (double)d[lane * NR + r] * rn : 0.0;
-      bad |= !(fabs(y) <= 1.0000001);  // NaN, inf (or a norm that is not the column's)
-      xn[r * NS + lane] = y;
+      for (int r = 0; r < NR; r++) {
+        const double y = nonzero ? (double)d[lane * NR + r] * rn : 0.0;
+        bad |= !(fabs(y) <= 1.0000001);  // NaN, inf (or a norm that is not the column's)
+        st->x[r * NS + lane] = y;
+      }
+    } else {
+      const float4 *src = reinterpret_cast<const float4 *>(d + lane * NR);
+      float4 *dst = reinterpret_cast<float4 *>(&st->d[lane * NR]);
+#pragma unroll
+      for (int i = 0; i < NR / 4; i++) {
+        const float4 v = src[i];
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const double y = nonzero ? (double)e[j] * rn : 0.0;
+          bad |= !(fabs(y) <= 1.0000001);  // NaN, inf (or a norm that is not the column's)
+        }
+        dst[i] = v;
+      }
+      st->rn[lane] = rn;
     }
   }
   u64 m = __ballot(nonzero && lane < NS);
   if (__ballot(bad && lane < NS)) m |= kNonFinite;
   wave_lds_fence();
-  // twiddles e^(-2 pi i m / 15), in the tail of the (now consumed-in-place) scratch: xn has DS doubles, tw sits behind
-  double *tw = xn + DS;  // [0..15) cos, [16..31) sin
-  if (lane < 15) {
-    tw[lane] = cospi(2.0 * lane / 15.0);
-    tw[16 + lane] = sinpi(2.0 * lane / 15.0);
-  }
-  wave_lds_fence();
   double dc_energy = 0.0;  // this lane's share of sum |X_0|^2
   // One (a, r) pair per lane and pass (80 pairs: lanes 0..63, then 0..15): the pair's 15 column values are read from LDS once
-  // and serve all 8 frequencies, the twiddles sit in registers.  (Until round 4 a lane took one (f, a, r) output at a time and
+  // and serve all 8 frequencies; a value is normalised where it is read, with the two operations of the first pass
+  // (nonzero ? (double)d * rn : 0.0: the same double).  The twiddles come from the table at constant offsets of a uniform
+  // pointer, i.e. through the scalar cache (sc_insert_kernel hands in a copy in LDS).  (Until round 4 a lane took one (f, a, r) output at a time and
   // read x and two twiddles from LDS for every term: 450 ds_read_b64 per lane instead of 30 + 30.)  Every output is the same
   // left-to-right sum over b as before, and the f = 0 outputs stay on the same lanes in the same order: the image and
   // dc_energy are bit-identical.
@@ -232,7 +273,8 @@ __device__ __forceinline__ u64 spectra_of(const float *__restrict__ d, const dou
     double x[15];
 #pragma unroll
     for (int bb = 0; bb < 15; bb++) {
-      x[bb] = xn[r * NS + c];
+      if constexpr (kStage64) x[bb] = st->x[r * NS + c];
+      else x[bb] = ((m >> c) & 1ull) ? (double)st->d[c * NR + r] * st->rn[c] : 0.0;
       c += 16;
       c -= (c >= 60) ? 60 : 0;
     }
@@ -274,16 +316,16 @@ __device__ __forceinline__ u64 spectra_of(const float *__restrict__ d, const dou
 
 // database image: tile-major [tile of 32 entries][76 K-steps][64 lanes][8 halves]
 __global__ __launch_bounds__(256) void sc_spec_db_kernel(const float *__restrict__ desc, const double *__restrict__ norm,
-                                                         int64_t first, int64_t count, uint4 *__restrict__ spT,
-                                                         float *__restrict__ aux) {
-  __shared__ double xn[4][DS + 32];
+                                                         const double *__restrict__ tw, int64_t first, int64_t count,
+                                                         uint4 *__restrict__ spT, float *__restrict__ aux) {
+  __shared__ SpecStage stage[4];
   __shared__ __attribute__((aligned(16))) _Float16 kv[4][SP_KV];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t it = (int64_t)blockIdx.x * 4 + wave;
   if (it >= count) return;
   const int64_t slot = first + it;
   float sqrt_a;
-  (void)spectra_of<false>(desc + slot * DS, norm + slot * NS, xn[wave], kv[wave], lane, sqrt_a);
+  (void)spectra_of<false>(desc + slot * DS, norm + slot * NS, tw, &stage[wave], kv[wave], lane, sqrt_a);
   if (lane == 0) aux[slot] = sqrt_a;
   const int64_t tile = slot >> 5;
   const int col = (int)(slot & 31);
@@ -312,6 +354,7 @@ struct InsertArgs {
   u64 *cmask;
   uint4 *spT;
   float *aux;
+  const double *tw;  // the twiddle table of the spectra
   _Float16 *vk16;
   float *vk_n;
 };
@@ -319,11 +362,15 @@ struct InsertArgs {
 template <int SO>
 __global__ __launch_bounds__(256) void sc_insert_kernel(InsertArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned bins[DS];
-  __shared__ double xn[DS + 32];
+  __shared__ SpecStage64 stage;
+  __shared__ double s_tw[SPEC_TWIDDLE_DOUBLES];
   __shared__ __attribute__((aligned(16))) _Float16 kv[SP_KV];
   __shared__ __attribute__((aligned(16))) _Float16 st[DS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t slot = a.first + blockIdx.x;
+  // the twiddle table into LDS while the descriptor is built, so that wave 0 does not wait for it behind the barriers below
+  // (one block per launch: nothing else hides a round trip to memory); the barriers of build_block publish it
+  if (threadIdx.x < SPEC_TWIDDLE_DOUBLES) s_tw[threadIdx.x] = a.tw[threadIdx.x];
   const int64_t p0 = a.offs ? a.offs[blockIdx.x] : 0, p1 = a.offs ? a.offs[blockIdx.x + 1] : a.n_pts;
   dev::build_block<SO>(a.pts + p0 * a.stride, p1 - p0, a.stride, a.lidar_height, a.max_radius, bins, a.desc + slot * DS,
                    a.vkey + slot * NS, a.norm + slot * NS, a.rkey + slot * NR);
@@ -333,7 +380,7 @@ __global__ __launch_bounds__(256) void sc_insert_kernel(InsertArgs a) {
   __syncthreads();
   if (wave == 0) {
     float sqrt_a;
-    (void)spectra_of<false>(a.desc + slot * DS, a.norm + slot * NS, xn, kv, lane, sqrt_a);
+    (void)spectra_of<false>(a.desc + slot * DS, a.norm + slot * NS, s_tw, &stage, kv, lane, sqrt_a);
     if (lane == 0) a.aux[slot] = sqrt_a;
     const int64_t tile = slot >> 5;
     const int col = (int)(slot & 31);
@@ -352,14 +399,15 @@ __global__ __launch_bounds__(256) void sc_insert_kernel(InsertArgs a) {
 //   [4672, 4688)              n_q, flags, sqrt(n_q), sqrt(a_q)
 // mask image = 16 displaced copies of the column-mask byte stream; flag byte = the query has an empty column
 __global__ __launch_bounds__(256) void sc_spec_query_kernel(const float *__restrict__ desc, const double *__restrict__ norm,
-                                                            int32_t nq, char *__restrict__ qimg) {
-  __shared__ double xn[4][DS + 32];
+                                                            const double *__restrict__ tw, int32_t nq,
+                                                            char *__restrict__ qimg) {
+  __shared__ SpecStage stage[4];
   __shared__ __attribute__((aligned(16))) _Float16 img[4][SP_TAIL / 2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.x * 4 + wave;
   if (q >= nq) return;
   float sqrt_a;
-  const u64 m = spectra_of<true>(desc + (int64_t)q * DS, norm + (int64_t)q * NS, xn[wave], img[wave], lane, sqrt_a);
+  const u64 m = spectra_of<true>(desc + (int64_t)q * DS, norm + (int64_t)q * NS, tw, &stage[wave], img[wave], lane, sqrt_a);
   const int n = __popcll(m & kMask60);
   uint4 *out = reinterpret_cast<uint4 *>(qimg + (int64_t)q * SP_QS);
   for (int c = lane; c < SP_QS / 16; c += 64) {
@@ -1700,18 +1748,24 @@ __global__ __launch_bounds__(512, 2) void sc_spec2_filter_kernel(SpecArgs a) {
 
 size_t spec_qimg_bytes(int32_t nq) { return (size_t)(sp_flags_at(nq) + sp_nq4(nq)) + 1024; }  // + slack: the filter reads flag words up to 3 tiles ahead
 
+int launch_spec_twiddles(double *tw, hipStream_t s) {
+  hipLaunchKernelGGL(sc_spec_twiddle_kernel, dim3(1), dim3(64), 0, s, tw);
+  RSX_HIP(hipGetLastError());
+  return RSX_OK;
+}
+
 int launch_spec_db_images(const float *desc, const double *norm, int64_t first, int64_t count, void *spT, float *aux,
-                          hipStream_t s) {
+                          const double *tw, hipStream_t s) {
   if (count <= 0) return RSX_OK;
-  hipLaunchKernelGGL(sc_spec_db_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, desc, norm, first, count,
+  hipLaunchKernelGGL(sc_spec_db_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, desc, norm, tw, first, count,
                      static_cast<uint4 *>(spT), aux);
   RSX_HIP(hipGetLastError());
   return RSX_OK;
 }
 
-int launch_spec_query_images(const float *desc, const double *norm, int32_t nq, void *qimg, hipStream_t s) {
+int launch_spec_query_images(const float *desc, const double *norm, int32_t nq, void *qimg, const double *tw, hipStream_t s) {
   if (nq <= 0) return RSX_OK;
-  hipLaunchKernelGGL(sc_spec_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, desc, norm, nq,
+  hipLaunchKernelGGL(sc_spec_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, desc, norm, tw, nq,
                      static_cast<char *>(qimg));
   RSX_HIP(hipGetLastError());
   return RSX_OK;
@@ -1719,8 +1773,8 @@ int launch_spec_query_images(const float *desc, const double *norm, int32_t nq, 
 
 int launch_insert(const void *d_pts, const int64_t *d_offs, int64_t n_pts, int64_t n_clouds, int64_t stride_bytes,
                   double lidar_height, double max_radius, int64_t first_slot, float *desc, double *vkey, double *norm,
-                  float *rkey, void *hnT, void *hnR, uint64_t *cmask, void *spT, float *aux, void *vk16, float *vk_n,
-                  hipStream_t s, int sum_order) {
+                  float *rkey, void *hnT, void *hnR, uint64_t *cmask, void *spT, float *aux, const double *tw, void *vk16,
+                  float *vk_n, hipStream_t s, int sum_order) {
   if (n_clouds <= 0) return RSX_OK;
   InsertArgs a;
   a.pts = static_cast<const char *>(d_pts);
@@ -1739,6 +1793,7 @@ int launch_insert(const void *d_pts, const int64_t *d_offs, int64_t n_pts, int64
   a.cmask = reinterpret_cast<u64 *>(cmask);
   a.spT = static_cast<uint4 *>(spT);
   a.aux = aux;
+  a.tw = tw;
   a.vk16 = static_cast<_Float16 *>(vk16);
   a.vk_n = vk_n;
   RSX_SO_DISPATCH(sum_order, hipLaunchKernelGGL(sc_insert_kernel<SO>, dim3((unsigned)n_clouds), dim3(256), 0, s, a));

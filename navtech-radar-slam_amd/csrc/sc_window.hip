@@ -65,6 +65,10 @@ using win::QK_LO;
 using win::QK_NORM;
 using win::W_LDS;
 
+// the prologue's staging area inside the per-position arrays (s_rec): the normalised columns, the doubled key, the column mask
+constexpr int W_ST2_OFF = DS * 2, W_QM_OFF = W_ST2_OFF + 2 * 128 * 2;
+static_assert(W_ST2_OFF % 16 == 0 && W_QM_OFF % 8 == 0 && W_QM_OFF + 8 <= 5 * WINDOW_P * 4, "staging fits the arrays it aliases");
+
 #ifndef WIN_OCC
 #define WIN_OCC 4  // waves per SIMD the register budget is set for
 #endif
@@ -83,20 +87,6 @@ __global__ __launch_bounds__(256) void sc_win_db_keys_kernel(const double *__res
 }
 
 // ------------------------------------------------------------------------------------------
-// query side: row k of the circulant reads the doubled key q2[k .. k + 63] (q2[i] = key[i % 60]); 8 copies displaced
-// by one element each keep that read 16-byte aligned (row k: copy k % 8 at element k - k % 8), and the copy stride
-// of 18 sixteen-byte slots keeps the 16 rows a ds_read_b128 serves together on 16 different slots mod 16
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sc_win_query_keys_kernel(const double *__restrict__ vkey, int32_t nq,
-                                                                char *__restrict__ qk) {
-  __shared__ _Float16 st[4][2][128];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int q = blockIdx.x * 4 + wave;
-  if (q >= nq) return;
-  win::query_keys_image(lane < NS ? vkey[(int64_t)q * NS + lane] : 0.0, st[wave], qk + (int64_t)q * WINDOW_QK_BYTES, lane);
-}
-
-// ------------------------------------------------------------------------------------------
 // the window kernel: one workgroup per query, wave w takes short-list positions 32 w .. 32 w + 31 (then + 128, ...)
 // ------------------------------------------------------------------------------------------
 struct WindowArgs {
@@ -104,8 +94,9 @@ struct WindowArgs {
   const char *vk16;
   const float *vk_n;
   const u64 *cmask;
-  const char *qimg;   // [nq][FILTER_QIMG_BYTES]
-  const char *qkimg;  // [nq][WINDOW_QK_BYTES]
+  const float *qdesc;   // [nq][DS]: the queries; their two images are built in LDS by the kernel's prologue
+  const double *qnorm;  // [nq][NS]
+  const double *qvkey;  // [nq][NS]
   const RescoreEntry *slist;
   const int32_t *sl_cnt;
   WindowPreview *out;
@@ -122,8 +113,10 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   __shared__ float s_tau;  // the head's k-th smallest upper bound, kept for the tail (a register across pass 2 would be spilled)
   // what the workgroup knows of list position p once its group is done (filter bound, slot, preview, k* | shift mask); the
   // positions no group takes are never read: they are not survivors
-  __shared__ float s_lb[WINDOW_P], s_pv[WINDOW_P], s_cand[WINDOW_P];
-  __shared__ int s_slot[WINDOW_P], s_ks[WINDOW_P];
+  // (one block, because the prologue stages the query in it before the first group touches any of the five)
+  __shared__ __attribute__((aligned(16))) char s_rec[5 * WINDOW_P * 4];
+  float *const s_lb = reinterpret_cast<float *>(s_rec), *const s_pv = s_lb + WINDOW_P, *const s_cand = s_pv + WINDOW_P;
+  int *const s_slot = reinterpret_cast<int *>(s_cand + WINDOW_P), *const s_ks = s_slot + WINDOW_P;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: group counters in SGPRs)
   const int qi = blockIdx.x;
   const int sl_cnt = a.sl_cnt[qi];
@@ -139,11 +132,28 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
     }
     return;
   }
+  // ---- the query's two images, built here from its descriptor, column norms and sector key (what sc_img_query_kernel and a
+  // key-image kernel used to write to global memory for this kernel to copy back): wave 0 the normalised columns and the
+  // column mask, wave 1 the doubled hi / lo key, into the staging area; then every thread a share of the two displaced image
+  // copies and the 16 displaced key copies.  Element for element the arithmetic of dev::normalise_column / split_key ----
   {
-    const uint4 *g0 = reinterpret_cast<const uint4 *>(a.qimg + (int64_t)qi * FILTER_QIMG_BYTES);
-    const uint4 *g1 = reinterpret_cast<const uint4 *>(a.qkimg + (int64_t)qi * WINDOW_QK_BYTES);
-    uint4 *l = reinterpret_cast<uint4 *>(smem);
-    for (int i = threadIdx.x; i < W_LDS / 16; i += 256) l[i] = i < FILTER_QIMG_BYTES / 16 ? g0[i] : g1[i - FILTER_QIMG_BYTES / 16];
+    _Float16 *st = reinterpret_cast<_Float16 *>(s_rec);                                        // DS halves
+    _Float16(*st2)[128] = reinterpret_cast<_Float16(*)[128]>(s_rec + W_ST2_OFF);               // 2 x 128 halves
+    u64 *s_qm = reinterpret_cast<u64 *>(s_rec + W_QM_OFF);
+    dev::KeySplit ksplit{};
+    if (wave == 0) {
+      bool nonzero = false, bad = false;
+      if (lane < NS) dev::normalise_column(a.qdesc + (int64_t)qi * DS + lane * NR, a.qnorm[(int64_t)qi * NS + lane], &st[lane * NR], nonzero, bad);
+      u64 m = __ballot(nonzero && lane < NS);
+      if (__ballot(bad && lane < NS)) m |= kNonFinite;
+      if (lane == 0) *s_qm = m;
+    } else if (wave == 1) {
+      ksplit = win::query_keys_stage(lane < NS ? a.qvkey[(int64_t)qi * NS + lane] : 0.0, st2, lane);
+    }
+    __syncthreads();
+    dev::img_query_image(st, *s_qm, reinterpret_cast<uint4 *>(smem), threadIdx.x, 256);
+    win::query_keys_copies(st2, smem + FILTER_QIMG_BYTES, threadIdx.x, 256);
+    if (wave == 1) win::query_keys_norms(ksplit, smem + FILTER_QIMG_BYTES, lane);
   }
   __syncthreads();
   const int n = lane & 31, hh = lane >> 5;
@@ -410,8 +420,6 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
 
 }  // namespace
 
-size_t window_qimg_bytes(int32_t nq) { return (size_t)nq * (FILTER_QIMG_BYTES + WINDOW_QK_BYTES) + 1024; }
-
 int launch_window_db_keys(const double *vkey, int64_t first, int64_t count, void *vk16, float *vk_n, hipStream_t s) {
   if (count <= 0) return RSX_OK;
   hipLaunchKernelGGL(sc_win_db_keys_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, vkey, first, count,
@@ -420,21 +428,17 @@ int launch_window_db_keys(const double *vkey, int64_t first, int64_t count, void
   return RSX_OK;
 }
 
-int launch_window(const DbView &db, const QueryView &q, void *qimg, const RescoreEntry *slist, const int32_t *sl_cnt,
+int launch_window(const DbView &db, const QueryView &q, const RescoreEntry *slist, const int32_t *sl_cnt,
                   int32_t k, double eps, WindowPreview *out, WindowSurvivor *surv, hipStream_t s) {
   if (q.nq <= 0) return RSX_OK;
-  char *img = static_cast<char *>(qimg);
-  char *kimg = img + (size_t)q.nq * FILTER_QIMG_BYTES;
-  RSX_TRY(launch_query_images(q.desc, q.norm, q.nq, img, s));
-  hipLaunchKernelGGL(sc_win_query_keys_kernel, dim3((unsigned)((q.nq + 3) / 4)), dim3(256), 0, s, q.vkey, q.nq, kimg);
-  RSX_HIP(hipGetLastError());
   WindowArgs a;
   a.hnR = static_cast<const char *>(db.hnR);
   a.vk16 = static_cast<const char *>(db.vk16);
   a.vk_n = db.vk_n;
   a.cmask = reinterpret_cast<const u64 *>(db.cmask);
-  a.qimg = img;
-  a.qkimg = kimg;
+  a.qdesc = q.desc;
+  a.qnorm = q.norm;
+  a.qvkey = q.vkey;
   a.slist = slist;
   a.sl_cnt = sl_cnt;
   a.out = out;

@@ -49,7 +49,8 @@ __device__ __forceinline__ dev::KeySplit query_keys_stage(double v, _Float16 (*s
   }
   return k;
 }
-// the 2 x 8 displaced copies from st: element i = first, first + step, ... by this thread; out = WINDOW_QK_BYTES (global or LDS)
+// the 2 x 8 displaced copies from st: element i = first, first + step, ... by this thread (after a barrier behind the stage);
+// out = WINDOW_QK_BYTES of LDS
 __device__ __forceinline__ void query_keys_copies(const _Float16 (*st)[128], char *out, int first, int step) {
   for (int i = first; i < 2 * 8 * (QK_COPY / 2); i += step) {
     const int part = i / (8 * (QK_COPY / 2));
@@ -62,14 +63,6 @@ __device__ __forceinline__ void query_keys_copies(const _Float16 (*st)[128], cha
 }
 __device__ __forceinline__ void query_keys_norms(const dev::KeySplit &k, char *out, int lane) {
   if (lane < 4) *reinterpret_cast<float *>(out + QK_NORM + lane * 4) = lane == 0 ? k.nrm : (lane == 1 ? k.unrm : 0.0f);
-}
-// all of it by one wave
-__device__ __forceinline__ void query_keys_image(double v, _Float16 (*st)[128], char *out, int lane) {
-  const dev::KeySplit k = query_keys_stage(v, st, lane);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  query_keys_copies(st, out, lane, 64);
-  query_keys_norms(k, out, lane);
 }
 
 // admissible alignments of the lane's entry (lane n and n + 32 hold the two halves of entry n's 64 shift rows): every shift
