@@ -728,12 +728,13 @@ int rsx_cfear_surface_points_batch_device(rsx_cfear *h, const float *d_xy, const
                                           const rsx_cfear_params *params, rsx_cfear_surface_point *d_records, int32_t max_records,
                                           int32_t *d_counts, int32_t *d_status, void *stream);
 /* n_pairs pairs; pair i registers src records [src_offsets[i], src_offsets[i + 1]) to dst records [dst_offsets[i],
- * dst_offsets[i + 1]); init: [n_pairs][3] doubles x, y, yaw, NULL = identity.  Host buffers, synchronous.  One workgroup per
- * pair, one launch. */
+ * dst_offsets[i + 1]); init: [n_pairs][3] doubles x, y, yaw, NULL = identity.  Host buffers, synchronous.  One launch: the joint
+ * registration below with dst i as the one keyframe of job i at the identity pose, through the cell index. */
 int rsx_cfear_register_batch(rsx_cfear *h, const rsx_cfear_surface_point *src, const int64_t *src_offsets,
                              const rsx_cfear_surface_point *dst, const int64_t *dst_offsets, int32_t n_pairs, const double *init,
                              const rsx_cfear_params *params, rsx_cfear_result *out);
-/* device buffers (d_init too, or NULL), asynchronous on `stream`, no allocation; the offsets are trusted */
+/* device buffers (d_init too, or NULL), asynchronous on `stream`; the offsets are trusted.  The handle's index workspace grows
+ * with min(n_pairs, 256); no allocation otherwise */
 int rsx_cfear_register_batch_device(rsx_cfear *h, const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets,
                                     const rsx_cfear_surface_point *d_dst, const int64_t *d_dst_offsets, int32_t n_pairs,
                                     const double *d_init, const rsx_cfear_params *params, rsx_cfear_result *d_out, void *stream);
@@ -750,7 +751,7 @@ int rsx_cfear_register_batch_device(rsx_cfear *h, const rsx_cfear_surface_point 
  * solve, step test and statuses.  Status 1: the src or every keyframe is empty (an empty keyframe among others is skipped); 2: a
  * side above RSX_CFEAR_MAX_SURFACE_POINTS.  With K = 1 and P_1 = (0, 0, 0) the result equals rsx_cfear_register_batch's byte for
  * byte.  The correspondence search goes through a 128 x 128 cell index of each keyframe (cell side = radius, built once per
- * keyframe) or, search = 1, by brute force as in the pair kernel: the same bytes either way.
+ * keyframe) or, search = 1, by brute force over the keyframe's records in ascending index: the same bytes either way.
  * Tracker, per sequence: state = the last pose P, the last motion M, a ring of at most n_keyframes keyframes.  Scan 0: P = 0, it is
  * the first keyframe (flag 1), its registration result is all zero.  Scan i: start = P o M (predict) or P; registered against the
  * ring.  Status 0 / 8: M = P^-1 o P_new, P = P_new, and the scan becomes a keyframe (flag 1, evicting the oldest of a full ring)

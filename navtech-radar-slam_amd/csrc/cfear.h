@@ -4,14 +4,14 @@
 
 #include "rsx_common.h"
 
-// the handle of the rsx_cfear entries (csrc/cfear.hip; the keyframe entries of csrc/cfear_track.hip work on it too)
+// the handle of the rsx_cfear entries (csrc/cfear.hip; the registration entries of csrc/cfear_track.hip work on it too)
 struct rsx_cfear {
   int device = 0;
   std::mutex mu;
   rsx::Stream stream;
   rsx::StreamOrder order;  // the staging buffers are shared by every host-buffer call
   rsx::DevBuf in0, in1, off0, off1, init, out, cnt, st;  // staging of the host-buffer entries
-  rsx::DevBuf job_off, poses, index;  // keyframe entries: the jobs' keyframe ranges and poses (staging), the cell-index workspace
+  rsx::DevBuf job_off, poses, index;  // registration: the jobs' keyframe ranges and poses (staging), the cell-index workspace
 };
 
 namespace rsx {
@@ -19,28 +19,30 @@ namespace cfear {
 
 // the parameter rules of the rsx_cfear entries (RSX_ERR_BAD_ARG + message, or RSX_OK)
 int check_params(const rsx_cfear_params &p);
+// dp = *params or the defaults, checked; with dt, *dt = *track or the defaults, checked as well
+int resolve(const rsx_cfear_params *params, const rsx_cfear_track_params *track, rsx_cfear_params &dp, rsx_cfear_track_params *dt);
 
 // The launches behind the device entries; they touch no handle.  Group i owns elements [d_begin[i], d_end[i]) of its array:
 // a ragged batch passes (offsets, offsets + 1), the odometry the ranges of its slots.
 // scan i's records to d_out + i * max_records, d_counts[i] every record found, d_status[i] (may be null) the status word
 int launch_surface(const float *d_xy, const int64_t *d_begin, const int64_t *d_end, int32_t n_scans, const rsx_cfear_params &p,
                    rsx_cfear_surface_point *d_out, int32_t max_records, int32_t *d_counts, int32_t *d_status, hipStream_t s);
-// d_init: [n_pairs][3] doubles or null (identity)
+
+// ---- csrc/cfear_track.hip: registration, and the tracker ----
+int check_track_params(const rsx_cfear_track_params &p);
+// bytes of cell-index workspace (d_index) a registration launch wants for n_jobs jobs
+size_t keyframe_index_bytes(int32_t n_jobs);
+// job i registers src group i jointly to the keyframes [d_kf_job_offsets[i], d_kf_job_offsets[i + 1]) -- null: keyframe i alone --
+// where keyframe g owns records [d_kf_begin[g], d_kf_end[g]) of d_kf and pose d_kf_poses[3 g ..] (null: every keyframe at the
+// identity); d_init: [n_jobs][3] doubles or null (identity)
+int launch_register_keyframes(const rsx_cfear_surface_point *d_src, const int64_t *d_src_begin, const int64_t *d_src_end,
+                              const rsx_cfear_surface_point *d_kf, const int64_t *d_kf_begin, const int64_t *d_kf_end,
+                              const int64_t *d_kf_job_offsets, const double *d_kf_poses, int32_t n_jobs, const double *d_init,
+                              const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_index, rsx_cfear_result *d_out, hipStream_t s);
+// pair i registers src group i to dst group i: the launch above with one keyframe per job at the identity, through the cell index
 int launch_register(const rsx_cfear_surface_point *d_src, const int64_t *d_src_begin, const int64_t *d_src_end,
                     const rsx_cfear_surface_point *d_dst, const int64_t *d_dst_begin, const int64_t *d_dst_end, int32_t n_pairs,
-                    const double *d_init, const rsx_cfear_params &p, rsx_cfear_result *d_out, hipStream_t s);
-
-
-// ---- csrc/cfear_track.hip: registration against keyframes, and the tracker ----
-int check_track_params(const rsx_cfear_track_params &p);
-// bytes of cell-index workspace launch_register_keyframes wants for n_jobs jobs
-size_t keyframe_index_bytes(int32_t n_jobs);
-// job i registers src group i jointly to the keyframes [d_kf_job_offsets[i], d_kf_job_offsets[i + 1]) (keyframe g owns records
-// [d_kf_offsets[g], d_kf_offsets[g + 1]) of d_kf and pose d_kf_poses[3 g ..]); d_init: [n_jobs][3] or null (identity)
-int launch_register_keyframes(const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets, const rsx_cfear_surface_point *d_kf,
-                              const int64_t *d_kf_offsets, const int64_t *d_kf_job_offsets, const double *d_kf_poses, int32_t n_jobs,
-                              const double *d_init, const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_index,
-                              rsx_cfear_result *d_out, hipStream_t s);
+                    const double *d_init, const rsx_cfear_params &p, void *d_index, rsx_cfear_result *d_out, hipStream_t s);
 // bytes of tracker state of one sequence (zero = a sequence that has seen no scan)
 size_t track_state_bytes();
 // sequence q (one workgroup) runs its d_n_scans[q] scans -- group sum(d_n_scans[0 .. q)) + i of (d_records, d_begin, d_end) is its

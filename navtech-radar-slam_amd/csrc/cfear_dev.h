@@ -1,0 +1,47 @@
+// cfear_dev.h -- the device code csrc/cfear.hip (surface points) and csrc/cfear_track.hip (registration) both need: the
+// 128 x 128 grid of cells of one radius, and points / records sorted by cell in LDS.  A key is cell << IDX_BITS | index, all
+// ones for an element outside the grid; sorted keys order the elements by cell and, inside a cell, by index.  Everything is
+// __forceinline__: a kernel keeps the instruction sequence it had with the code written out in place.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace rsx {
+namespace cfear {
+
+constexpr int GRID = 128, HALF = 64, NCELL = GRID * GRID;
+constexpr unsigned NO_KEY = 0xFFFFFFFFu;
+constexpr unsigned short NO_CELL = 0xFFFF;
+
+// bitonic sort of keys[0 .. n2) in LDS, ascending, by a workgroup of NT threads (thread t); n2 a power of two >= NT.  Called
+// behind a barrier, ends behind one
+template <int NT>
+__device__ __forceinline__ void bitonic_sort_lds(unsigned *keys, unsigned n2, int t) {
+  for (unsigned kk = 2; kk <= n2; kk <<= 1)
+    for (unsigned j = kk >> 1; j > 0; j >>= 1) {
+      for (unsigned i = t; i < n2; i += NT) {
+        const unsigned l = i ^ j;
+        if (l > i) {
+          const unsigned a = keys[i], c = keys[l];
+          if ((a > c) == ((i & kk) == 0)) {
+            keys[i] = c;
+            keys[l] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+}
+
+// table[cell] = the first sorted position of the cell, from the sorted keys[0 .. n) (LDS or HBM); the other entries of the
+// table (NO_CELL: an empty cell) stay.  OUTSIDE: some of the n keys may be NO_KEY (they sort to the end and have no cell).  No barrier
+template <int NT, unsigned IDX_BITS, bool OUTSIDE>
+__device__ __forceinline__ void fill_cell_table(const unsigned *keys, int n, unsigned short *table, int t) {
+  for (int i = t; i < n; i += NT) {
+    const unsigned key = keys[i];
+    if (OUTSIDE && key == NO_KEY) continue;
+    if (i == 0 || (keys[i - 1] >> IDX_BITS) != (key >> IDX_BITS)) table[key >> IDX_BITS] = (unsigned short)i;
+  }
+}
+
+}  // namespace cfear
+}  // namespace rsx

@@ -1,14 +1,18 @@
-// cfear_track.hip -- CFEAR scan-to-keyframes registration and the keyframe tracker (Adolfsson et al., CFEAR radar odometry): a
-// scan is registered JOINTLY against the last few keyframes, from a constant-velocity prediction, and becomes a keyframe itself
-// only after enough motion.  The rules are written in include/rsx.h and restated in tests/cfear_track_np.py (PARITY UNPINNED);
-// that file is the arithmetic contract.  fp64 throughout, nothing fused, as in csrc/cfear.hip, whose kernels stay as they are.
+// cfear_track.hip -- CFEAR point-to-line registration and the keyframe tracker (Adolfsson et al., CFEAR radar odometry): a scan is
+// registered JOINTLY against the last few keyframes, from a constant-velocity prediction, and becomes a keyframe itself only
+// after enough motion; the registration of a PAIR of scans (rsx_cfear_register_batch, the odometry without tracking) is the same
+// with one keyframe at the identity pose.  The rules are written in include/rsx.h and restated in tests/cfear_np.py (pairs) and
+// tests/cfear_track_np.py (PARITY UNPINNED); those files are the arithmetic contract.  fp64 throughout, nothing fused, as in
+// csrc/cfear.hip, which makes the surface points.
 //
-// joint_register: the one device function both kernels call.  512 threads (the fp64 sincos wants the 256 VGPRs of two waves per
+// joint_register: the one Gauss-Newton loop of the library, the device function both kernels call.  512 threads (the fp64 sincos wants the 256 VGPRs of two waves per
 //   SIMD).  Per Gauss-Newton iteration: threads 0 .. K-1 take the scan's pose in their keyframe's frame (one sincos each) and
 //   leave it in LDS; the items (record i, keyframe c) are strided over the threads as item = i * K + c (so a thread's items ascend
-//   in i and, inside, in ring order, and with K = 1 a thread has the pair kernel's records); a thread finds the correspondence of
-//   each of its items and adds its term; the sums go through the butterfly over a wavefront and the 8 wavefront sums in
-//   ascending order, exactly as in cfear_register_kernel -- with K = 1 at the identity pose the bytes are that kernel's.
+//   in i and, inside, in ring order, and with K = 1 a thread has records t, t + 512, ...); a thread finds the correspondence of
+//   each of its items and adds its term; the sums are taken per thread in ascending item, then by a butterfly over the lanes of
+//   a wavefront, then over the 8 wavefront sums in ascending order; every thread holds the same 3 x 3 system and solves it
+//   itself, so the loop needs no host and its branches are uniform.  With K = 1 at the identity pose every expression reduces
+//   to the pair rule's of tests/cfear_np.py (tests/golden/cfear_pairs_parent.npz pins the bytes).
 //   The correspondence of (record, keyframe) comes from one of two searches that give the same record, hence the same bytes:
 //   search 0  the keyframe's CELL INDEX: its records binned by floor(mu / radius), clamped into the 128 x 128 grid (a clamp is
 //             monotone and 1-Lipschitz: two records within the radius stay in adjacent cells, and a query far outside finds only
@@ -21,7 +25,8 @@
 //   search 1  brute force: one keyframe at a time staged in LDS, every lane reads the same address; the chosen index per (record,
 //             keyframe) is parked in LDS (16 bit) so that the sums run in the one order above
 // cfear_joint_kernel: a workgroup takes jobs blockIdx.x, blockIdx.x + gridDim.x, ...; it bins the job's keyframes into its
-//   own slice of the index workspace, then registers.  cfear_track_kernel: one workgroup per sequence loops over the sequence's
+//   own slice of the index workspace, then registers.  Without job offsets job i has keyframe i alone, without poses every
+//   keyframe is at the identity: the pair entries.  cfear_track_kernel: one workgroup per sequence loops over the sequence's
 //   scans with no host round trip; the ring (records, poses, sorted keys and records) lives in the sequence's state in HBM, the
 //   header is read at the start and written back at the end, the LDS tables are rebuilt from the sorted keys at the start.  A
 //   workgroup reads back what it wrote to HBM only behind __threadfence_block() + __syncthreads(); no workgroup reads another's.
@@ -35,6 +40,7 @@
 #include <new>
 
 #include "cfear.h"
+#include "cfear_dev.h"
 #include "ragged_host.h"
 
 #pragma STDC FP_CONTRACT OFF
@@ -42,10 +48,10 @@
 namespace {
 
 constexpr int NT = 512, NW = NT / 64;
-constexpr int GRID = 128, HALF = 64, NCELL = GRID * GRID;
+using namespace rsx::cfear;  // the grid, the keys and the sort of cfear_dev.h
 constexpr int CAP = RSX_CFEAR_MAX_SURFACE_POINTS, MAXK = RSX_CFEAR_MAX_KEYFRAMES;
-constexpr unsigned NO_KEY = 0xFFFFFFFFu, IDX_BITS = 12, IDX_MASK = (1u << IDX_BITS) - 1u;
-constexpr unsigned short NO_CELL = 0xFFFF, NO_BEST = 0xFFFF;
+constexpr unsigned IDX_BITS = 12, IDX_MASK = (1u << IDX_BITS) - 1u;
+constexpr unsigned short NO_BEST = 0xFFFF;
 constexpr int N_SUMS = 11;  // H00 H10 H11 H20 H21 H22 g0 g1 g2 cost count
 static_assert(CAP == (1 << IDX_BITS) && NCELL == (1 << 14), "a key is cell << 12 | record index");
 static_assert(sizeof(rsx_cfear_surface_point) == 32 && sizeof(rsx_cfear_result) == 48 && sizeof(rsx_cfear_track_result) == 80 &&
@@ -97,14 +103,6 @@ __device__ __forceinline__ int cell_coord(double v, double r) {
   return !(f >= -(double)HALF) ? 0 : (f >= (double)HALF ? GRID - 1 : (int)f + HALF);  // (a NaN lands in cell 0 and is never matched)
 }
 
-// start[cell] = the first sorted position of the cell, from sorted keys (LDS or HBM)
-__device__ __forceinline__ void fill_table(const unsigned *keys, int n, unsigned short *table, int t) {
-  for (int i = t; i < n; i += NT) {
-    const unsigned key = keys[i];
-    if (i == 0 || (keys[i - 1] >> IDX_BITS) != (key >> IDX_BITS)) table[key >> IDX_BITS] = (unsigned short)i;
-  }
-}
-
 // the cell index of one keyframe of 1 <= n <= CAP records: table in LDS, sorted keys and records to HBM; ends behind a barrier
 __device__ void build_index(const float4 *orig, int stride, int n, unsigned *keys_out, float4 *sorted_out, unsigned short *table,
                             unsigned *sortbuf, double r, int t) {
@@ -120,21 +118,8 @@ __device__ void build_index(const float4 *orig, int stride, int n, unsigned *key
   }
   for (int c = t; c < NCELL; c += NT) table[c] = NO_CELL;
   __syncthreads();
-  for (unsigned kk = 2; kk <= n2; kk <<= 1)
-    for (unsigned j = kk >> 1; j > 0; j >>= 1) {
-      for (unsigned i = t; i < n2; i += NT) {
-        const unsigned l = i ^ j;
-        if (l > i) {
-          const unsigned a = sortbuf[i], c = sortbuf[l];
-          if ((a > c) == ((i & kk) == 0)) {
-            sortbuf[i] = c;
-            sortbuf[l] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  fill_table(sortbuf, n, table, t);
+  bitonic_sort_lds<NT>(sortbuf, n2, t);
+  fill_cell_table<NT, IDX_BITS, false>(sortbuf, n, table, t);  // (every record has a cell: cell_coord clamps)
   for (int i = t; i < n; i += NT) {
     const unsigned key = sortbuf[i];
     keys_out[i] = key;
@@ -379,8 +364,10 @@ __device__ void joint_register(const float4 *sp, int sstride, int64_t ns64, int 
 
 __device__ __forceinline__ int clamp_count(int64_t n) { return n <= 0 ? 0 : (n > CAP ? CAP + 1 : (int)n); }
 
-__global__ __launch_bounds__(NT) void cfear_joint_kernel(const rsx_cfear_surface_point *__restrict__ src, const int64_t *__restrict__ src_off,
-                                                         const rsx_cfear_surface_point *__restrict__ kfrec, const int64_t *__restrict__ kf_off,
+// kf_job_off null: job i has keyframe i alone; poses null: every keyframe at the identity
+__global__ __launch_bounds__(NT) void cfear_joint_kernel(const rsx_cfear_surface_point *__restrict__ src, const int64_t *__restrict__ src_begin,
+                                                         const int64_t *__restrict__ src_end, const rsx_cfear_surface_point *__restrict__ kfrec,
+                                                         const int64_t *__restrict__ kf_begin, const int64_t *__restrict__ kf_end,
                                                          const int64_t *__restrict__ kf_job_off, const double *__restrict__ poses,
                                                          const double *__restrict__ init, int n_jobs, RgConsts k, int search,
                                                          unsigned char *index, rsx_cfear_result *__restrict__ out) {
@@ -394,8 +381,12 @@ __global__ __launch_bounds__(NT) void cfear_joint_kernel(const rsx_cfear_surface
   unsigned *ws_keys = reinterpret_cast<unsigned *>(index + (size_t)blockIdx.x * WS_BYTES + WS_SORTED);
   const int t = threadIdx.x;
   for (int job = blockIdx.x; job < n_jobs; job += gridDim.x) {
-    const int64_t g0 = kf_job_off[job], k64 = kf_job_off[job + 1] - g0;
-    const int64_t sb = src_off[job], ns64 = src_off[job + 1] - sb;
+    int64_t g0 = job, k64 = 1;
+    if (kf_job_off) {
+      g0 = kf_job_off[job];
+      k64 = kf_job_off[job + 1] - g0;
+    }
+    const int64_t sb = src_begin[job], ns64 = src_end[job] - sb;
     double x = 0.0, y = 0.0, yaw = 0.0;
     if (init) {
       x = init[3 * (int64_t)job];
@@ -416,17 +407,21 @@ __global__ __launch_bounds__(NT) void cfear_joint_kernel(const rsx_cfear_surface
     const int K = k64 < 0 ? 0 : (int)k64;
     __syncthreads();  // (the previous job's descriptors and tables are done with)
     if (t < K) {
-      const int64_t g = g0 + t, b = kf_off[g];
+      const int64_t g = g0 + t, b = kf_begin[g];
       KfDesc f;
       f.orig = reinterpret_cast<const float4 *>(kfrec + b);
       f.stride = 2;  // x, y, nx, ny: the first 16 bytes of a 32-byte record
-      f.n = clamp_count(kf_off[g + 1] - b);
+      f.n = clamp_count(kf_end[g] - b);
       f.sorted = ws_sorted + (size_t)t * CAP;
       f.keys = ws_keys + (size_t)t * CAP;
-      f.x = poses[3 * g];
-      f.y = poses[3 * g + 1];
-      f.yaw = poses[3 * g + 2];
-      sincos(f.yaw, &f.s, &f.c);
+      f.x = f.y = f.yaw = f.s = 0.0;
+      f.c = 1.0;
+      if (poses) {
+        f.x = poses[3 * g];
+        f.y = poses[3 * g + 1];
+        f.yaw = poses[3 * g + 2];
+        sincos(f.yaw, &f.s, &f.c);
+      }
       f.slot = t;
       s_kf[t] = f;
     }
@@ -473,7 +468,7 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
     __syncthreads();
     for (int c = 0; c < n_ring; c++) {
       const int slot = (head + c) % NK, cnt = hdr->kf_n[slot];
-      if (cnt >= 1 && cnt <= CAP) fill_table(keys + (size_t)slot * CAP, cnt, tables + (size_t)slot * NCELL, t);
+      if (cnt >= 1 && cnt <= CAP) fill_cell_table<NT, IDX_BITS, false>(keys + (size_t)slot * CAP, cnt, tables + (size_t)slot * NCELL, t);
     }
   }
   for (int s = 0; s < n; s++) {
@@ -617,17 +612,28 @@ size_t rsx::cfear::keyframe_index_bytes(int32_t n_jobs) { return (size_t)(n_jobs
 
 size_t rsx::cfear::track_state_bytes() { return ST_BYTES; }
 
-int rsx::cfear::launch_register_keyframes(const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets, const rsx_cfear_surface_point *d_kf,
-                                          const int64_t *d_kf_offsets, const int64_t *d_kf_job_offsets, const double *d_kf_poses, int32_t n_jobs,
-                                          const double *d_init, const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_index,
-                                          rsx_cfear_result *d_out, hipStream_t s) {
+int rsx::cfear::launch_register_keyframes(const rsx_cfear_surface_point *d_src, const int64_t *d_src_begin, const int64_t *d_src_end,
+                                          const rsx_cfear_surface_point *d_kf, const int64_t *d_kf_begin, const int64_t *d_kf_end,
+                                          const int64_t *d_kf_job_offsets, const double *d_kf_poses, int32_t n_jobs, const double *d_init,
+                                          const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_index, rsx_cfear_result *d_out,
+                                          hipStream_t s) {
   if (n_jobs < 1) return fail(RSX_ERR_BAD_ARG, "n_jobs %d below 1", n_jobs);
   RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfear_joint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
   const int blocks = n_jobs < MAX_JOINT_BLOCKS ? n_jobs : MAX_JOINT_BLOCKS;
-  hipLaunchKernelGGL(cfear_joint_kernel, dim3((unsigned)blocks), dim3(NT), LDS_BYTES, s, d_src, d_src_offsets, d_kf, d_kf_offsets, d_kf_job_offsets,
-                     d_kf_poses, d_init, (int)n_jobs, rg_consts(p), (int)tp.search, static_cast<unsigned char *>(d_index), d_out);
+  hipLaunchKernelGGL(cfear_joint_kernel, dim3((unsigned)blocks), dim3(NT), LDS_BYTES, s, d_src, d_src_begin, d_src_end, d_kf, d_kf_begin, d_kf_end,
+                     d_kf_job_offsets, d_kf_poses, d_init, (int)n_jobs, rg_consts(p), (int)tp.search, static_cast<unsigned char *>(d_index), d_out);
   RSX_HIP(hipGetLastError());
   return RSX_OK;
+}
+
+int rsx::cfear::launch_register(const rsx_cfear_surface_point *d_src, const int64_t *d_src_begin, const int64_t *d_src_end,
+                                const rsx_cfear_surface_point *d_dst, const int64_t *d_dst_begin, const int64_t *d_dst_end, int32_t n_pairs,
+                                const double *d_init, const rsx_cfear_params &p, void *d_index, rsx_cfear_result *d_out, hipStream_t s) {
+  if (n_pairs < 1) return fail(RSX_ERR_BAD_ARG, "n_pairs %d below 1", n_pairs);
+  rsx_cfear_track_params tp;
+  rsx_cfear_default_track_params(&tp);  // (only `search` acts: RSX_CFEAR_SEARCH_CELLS)
+  return launch_register_keyframes(d_src, d_src_begin, d_src_end, d_dst, d_dst_begin, d_dst_end, nullptr, nullptr, n_pairs, d_init, p, tp, d_index,
+                                   d_out, s);
 }
 
 int rsx::cfear::launch_track(const rsx_cfear_surface_point *d_records, const int64_t *d_begin, const int64_t *d_end, const int32_t *d_n_scans,
@@ -662,13 +668,54 @@ struct rsx_cfear_tracker {
 
 namespace {
 
-int resolve(const rsx_cfear_params *params, const rsx_cfear_track_params *track, rsx_cfear_params &dp, rsx_cfear_track_params &dt) {
-  rsx_cfear_default_params(&dp);
-  if (params) dp = *params;
-  RSX_TRY(rsx::cfear::check_params(dp));
-  rsx_cfear_default_track_params(&dt);
-  if (track) dt = *track;
-  return rsx::cfear::check_track_params(dt);
+// A batch of registration jobs as the launch takes it, in host or in device memory; job_off and poses null: the pair entries
+struct RegJobs {
+  const rsx_cfear_surface_point *src, *kf;
+  const int64_t *src_off, *kf_off, *job_off;
+  const double *poses, *init;
+  int32_t n, n_kf;  // jobs, keyframes in all
+  rsx_cfear_result *out;
+};
+
+// the host-buffer forms: j's arrays into the handle's staging buffers; j names those afterwards
+int stage_jobs(rsx_cfear *h, RegJobs &j, hipStream_t s) {
+  const size_t n = (size_t)j.n, nk = (size_t)j.n_kf;
+  RSX_TRY(rsx::stage_up(h->in0, j.src, (size_t)j.src_off[j.n] * sizeof(rsx_cfear_surface_point), s));
+  RSX_TRY(rsx::stage_up(h->in1, j.kf, (size_t)j.kf_off[j.n_kf] * sizeof(rsx_cfear_surface_point), s));
+  RSX_TRY(rsx::stage_up(h->off0, j.src_off, (n + 1) * 8, s));
+  RSX_TRY(rsx::stage_up(h->off1, j.kf_off, (nk + 1) * 8, s));
+  if (j.job_off) RSX_TRY(rsx::stage_up(h->job_off, j.job_off, (n + 1) * 8, s));
+  if (j.poses) RSX_TRY(rsx::stage_up(h->poses, j.poses, nk * 24, s));
+  if (j.init) RSX_TRY(rsx::stage_up(h->init, j.init, n * 24, s));
+  RSX_TRY(rsx::stage_room(h->out, n * sizeof(rsx_cfear_result), s));
+  j.src = h->in0.as<rsx_cfear_surface_point>();
+  j.kf = h->in1.as<rsx_cfear_surface_point>();
+  j.src_off = h->off0.as<int64_t>();
+  j.kf_off = h->off1.as<int64_t>();
+  if (j.job_off) j.job_off = h->job_off.as<int64_t>();
+  if (j.poses) j.poses = h->poses.as<double>();
+  if (j.init) j.init = h->init.as<double>();
+  j.out = h->out.as<rsx_cfear_result>();
+  return RSX_OK;
+}
+
+// The one path of the four registration entries: lock, device, stream order, (staging,) the index workspace, the launch.
+// host: j is in host memory, the call goes through the handle's stream and returns with the results; otherwise j is in device
+// memory and the call is asynchronous on `stream` (null: the handle's)
+int register_jobs(rsx_cfear *h, RegJobs j, bool host, void *stream, const rsx_cfear_params &dp, const rsx_cfear_track_params &dt) {
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
+  rsx_cfear_result *host_out = j.out;
+  if (host) RSX_TRY(stage_jobs(h, j, s));
+  RSX_TRY(h->index.reserve(rsx::cfear::keyframe_index_bytes(j.n), s, false));
+  RSX_TRY(rsx::cfear::launch_register_keyframes(j.src, j.src_off, j.src_off + 1, j.kf, j.kf_off, j.kf_off + 1, j.job_off, j.poses, j.n, j.init, dp, dt,
+                                                h->index.p, j.out, s));
+  if (!host) return RSX_OK;
+  RSX_TRY(rsx::stage_down(host_out, h->out, (size_t)j.n * sizeof(rsx_cfear_result), s));
+  RSX_HIP(hipStreamSynchronize(s));
+  return RSX_OK;
 }
 
 // the parameters of a sequence stay: the first push since create / reset sets them
@@ -696,6 +743,30 @@ int rsx_cfear_default_track_params(rsx_cfear_track_params *p) try {
   return RSX_OK;
 } RSX_CATCH_ALL
 
+int rsx_cfear_register_batch_device(rsx_cfear *h, const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets,
+                                    const rsx_cfear_surface_point *d_dst, const int64_t *d_dst_offsets, int32_t n_pairs,
+                                    const double *d_init, const rsx_cfear_params *params, rsx_cfear_result *d_out, void *stream) try {
+  if (!h || !d_src || !d_src_offsets || !d_dst || !d_dst_offsets || !d_out || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  rsx_cfear_params dp;
+  rsx_cfear_track_params dt;
+  RSX_TRY(resolve(params, nullptr, dp, &dt));
+  if (n_pairs == 0) return RSX_OK;
+  return register_jobs(h, {d_src, d_dst, d_src_offsets, d_dst_offsets, nullptr, nullptr, d_init, n_pairs, n_pairs, d_out}, false, stream, dp, dt);
+} RSX_CATCH_ALL
+
+int rsx_cfear_register_batch(rsx_cfear *h, const rsx_cfear_surface_point *src, const int64_t *src_offsets,
+                             const rsx_cfear_surface_point *dst, const int64_t *dst_offsets, int32_t n_pairs, const double *init,
+                             const rsx_cfear_params *params, rsx_cfear_result *out) try {
+  if (!h || !src || !src_offsets || !dst || !dst_offsets || !out || n_pairs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  rsx_cfear_params dp;
+  rsx_cfear_track_params dt;
+  RSX_TRY(resolve(params, nullptr, dp, &dt));
+  if (n_pairs == 0) return RSX_OK;
+  RSX_TRY(rsx::check_offsets(src_offsets, n_pairs, "rsx_cfear_register_batch (src)"));
+  RSX_TRY(rsx::check_offsets(dst_offsets, n_pairs, "rsx_cfear_register_batch (dst)"));
+  return register_jobs(h, {src, dst, src_offsets, dst_offsets, nullptr, nullptr, init, n_pairs, n_pairs, out}, true, nullptr, dp, dt);
+} RSX_CATCH_ALL
+
 int rsx_cfear_register_keyframes_batch_device(rsx_cfear *h, const rsx_cfear_surface_point *d_src, const int64_t *d_src_offsets,
                                               const rsx_cfear_surface_point *d_kf, const int64_t *d_kf_offsets,
                                               const int64_t *d_kf_job_offsets, const double *d_kf_poses, int32_t n_jobs,
@@ -705,15 +776,9 @@ int rsx_cfear_register_keyframes_batch_device(rsx_cfear *h, const rsx_cfear_surf
     return fail(RSX_ERR_BAD_ARG, "bad arg");
   rsx_cfear_params dp;
   rsx_cfear_track_params dt;
-  RSX_TRY(resolve(params, track, dp, dt));
+  RSX_TRY(resolve(params, track, dp, &dt));
   if (n_jobs == 0) return RSX_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  RSX_TRY(h->order.enter(s));
-  RSX_TRY(h->index.reserve(rsx::cfear::keyframe_index_bytes(n_jobs), s, false));
-  return rsx::cfear::launch_register_keyframes(d_src, d_src_offsets, d_kf, d_kf_offsets, d_kf_job_offsets, d_kf_poses, n_jobs, d_init, dp, dt,
-                                               h->index.p, d_out, s);
+  return register_jobs(h, {d_src, d_kf, d_src_offsets, d_kf_offsets, d_kf_job_offsets, d_kf_poses, d_init, n_jobs, 0, d_out}, false, stream, dp, dt);
 } RSX_CATCH_ALL
 
 int rsx_cfear_register_keyframes_batch(rsx_cfear *h, const rsx_cfear_surface_point *src, const int64_t *src_offsets,
@@ -723,7 +788,7 @@ int rsx_cfear_register_keyframes_batch(rsx_cfear *h, const rsx_cfear_surface_poi
   if (!h || !src || !src_offsets || !kf || !kf_offsets || !kf_job_offsets || !kf_poses || !out || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   rsx_cfear_params dp;
   rsx_cfear_track_params dt;
-  RSX_TRY(resolve(params, track, dp, dt));
+  RSX_TRY(resolve(params, track, dp, &dt));
   if (n_jobs == 0) return RSX_OK;
   RSX_TRY(rsx::check_offsets(src_offsets, n_jobs, "rsx_cfear_register_keyframes_batch (src)"));
   RSX_TRY(rsx::check_offsets(kf_job_offsets, n_jobs, "rsx_cfear_register_keyframes_batch (jobs)"));
@@ -735,26 +800,7 @@ int rsx_cfear_register_keyframes_batch(rsx_cfear *h, const rsx_cfear_surface_poi
   if (kf_job_offsets[n_jobs] > INT32_MAX) return fail(RSX_ERR_BAD_ARG, "too many keyframes");
   const int32_t n_kf = (int32_t)kf_job_offsets[n_jobs];
   RSX_TRY(rsx::check_offsets(kf_offsets, n_kf, "rsx_cfear_register_keyframes_batch (keyframes)"));
-  const size_t ms = (size_t)src_offsets[n_jobs], mk = (size_t)kf_offsets[n_kf], n = (size_t)n_jobs, nk = (size_t)n_kf;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  RSX_TRY(h->order.enter(s));
-  RSX_TRY(rsx::stage_up(h->in0, src, ms * sizeof(rsx_cfear_surface_point), s));
-  RSX_TRY(rsx::stage_up(h->in1, kf, mk * sizeof(rsx_cfear_surface_point), s));
-  RSX_TRY(rsx::stage_up(h->off0, src_offsets, (n + 1) * 8, s));
-  RSX_TRY(rsx::stage_up(h->off1, kf_offsets, (nk + 1) * 8, s));
-  RSX_TRY(rsx::stage_up(h->job_off, kf_job_offsets, (n + 1) * 8, s));
-  RSX_TRY(rsx::stage_up(h->poses, kf_poses, nk * 24, s));
-  if (init) RSX_TRY(rsx::stage_up(h->init, init, n * 24, s));
-  RSX_TRY(rsx::stage_room(h->out, n * sizeof(rsx_cfear_result), s));
-  RSX_TRY(rsx::stage_room(h->index, rsx::cfear::keyframe_index_bytes(n_jobs), s));
-  RSX_TRY(rsx::cfear::launch_register_keyframes(h->in0.as<rsx_cfear_surface_point>(), h->off0.as<int64_t>(), h->in1.as<rsx_cfear_surface_point>(),
-                                                h->off1.as<int64_t>(), h->job_off.as<int64_t>(), h->poses.as<double>(), n_jobs,
-                                                init ? h->init.as<double>() : nullptr, dp, dt, h->index.p, h->out.as<rsx_cfear_result>(), s));
-  RSX_TRY(rsx::stage_down(out, h->out, n * sizeof(rsx_cfear_result), s));
-  RSX_HIP(hipStreamSynchronize(s));
-  return RSX_OK;
+  return register_jobs(h, {src, kf, src_offsets, kf_offsets, kf_job_offsets, kf_poses, init, n_jobs, n_kf, out}, true, nullptr, dp, dt);
 } RSX_CATCH_ALL
 
 int rsx_cfear_tracker_create(int device, int32_t n_sequences, rsx_cfear_tracker **out) try {
@@ -804,7 +850,7 @@ int rsx_cfear_tracker_push_device(rsx_cfear_tracker *h, const rsx_cfear_surface_
   if (!h || !d_records || !d_offsets || !d_n_scans || !d_out) return fail(RSX_ERR_BAD_ARG, "bad arg");
   rsx_cfear_params dp;
   rsx_cfear_track_params dt;
-  RSX_TRY(resolve(params, track, dp, dt));
+  RSX_TRY(resolve(params, track, dp, &dt));
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_TRY(same_params(h, dp, dt));
   RSX_HIP(hipSetDevice(h->device));
@@ -818,7 +864,7 @@ int rsx_cfear_tracker_push(rsx_cfear_tracker *h, const rsx_cfear_surface_point *
   if (!h || !records || !offsets || !n_scans || !out) return fail(RSX_ERR_BAD_ARG, "bad arg");
   rsx_cfear_params dp;
   rsx_cfear_track_params dt;
-  RSX_TRY(resolve(params, track, dp, dt));
+  RSX_TRY(resolve(params, track, dp, &dt));
   int64_t total = 0;
   for (int32_t q = 0; q < h->n_sequences; q++) {
     if (n_scans[q] < 0) return fail(RSX_ERR_BAD_ARG, "n_scans[%d] = %d is negative", q, n_scans[q]);

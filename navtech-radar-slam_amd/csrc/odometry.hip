@@ -287,6 +287,7 @@ struct rsx_odometry {
   rsx::DevBuf ransac_res, stage_dt, dt;  // allocated only with a RANSAC estimator (stage_dt, dt: MC-RANSAC)
   rsx_cfear_params cfear_prm{};  // estimator == RSX_ESTIMATOR_CFEAR (rsx_odometry_set_cfear)
   rsx::DevBuf cfear_res, sp_begin, sp_end;  // allocated only with CFEAR: results of a window, the record ranges of its slots
+  rsx::DevBuf cfear_index;  // CFEAR without tracking: the cell-index workspace of a window's pair registration (20 MiB)
   bool track_on = false;  // rsx_odometry_set_cfear_tracking: the keyframe tracker in place of the pair registration
   rsx_cfear_track_params track_prm{};
   rsx::DevBuf track_state, track_res, track_n, track_prev;  // allocated only with tracking: the sequence's state (csrc/cfear_track.hip), a
@@ -344,7 +345,7 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
       RSX_TRY(h->track_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_cfear_track_result), s, false));
       RSX_TRY(h->track_n.reserve(4, s, false));
       RSX_TRY(h->track_prev.reserve(24, s, false));
-    }
+    } else RSX_TRY(h->cfear_index.reserve(rsx::cfear::keyframe_index_bytes(MAX_WINDOW), s, false));
   } else if (h->estimator != RSX_ESTIMATOR_ORORA) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
   if (h->estimator == RSX_ESTIMATOR_MCRANSAC) {
     RSX_TRY(h->stage_dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
@@ -451,7 +452,7 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
     RSX_HIP(hipGetLastError());
     const rsx_cfear_surface_point *sp = q.sp.as<rsx_cfear_surface_point>();
     RSX_TRY(rsx::cfear::launch_register(sp, b + first + 1, e + first + 1, sp, b + first, e + first, n_pairs, nullptr, h->cfear_prm,
-                                        h->cfear_res.as<rsx_cfear_result>(), s));
+                                        h->cfear_index.p, h->cfear_res.as<rsx_cfear_result>(), s));
     hipLaunchKernelGGL(odo_cfear_results, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->cfear_res.as<rsx_cfear_result>(), n_pairs,
                        h->results.as<rsx_orora_result>(), h->pair_cnt.as<int32_t>());
     RSX_HIP(hipGetLastError());

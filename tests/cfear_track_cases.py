@@ -1,5 +1,5 @@
 """Inputs shared by the CFEAR tracking tests (tests/test_cfear_track_restatement.py, tests/test_gpu_cfear_track.py,
-tests/test_gpu_odometry_cfear_track.py): surface points of the synthetic sequences through the CPU chain k-strongest ->
+tests/test_gpu_odometry_cfear_track.py, tests/test_gpu_cfear_pair_pin.py and its recorder tools/make_cfear_pairs_golden.py): surface points of the synthetic sequences through the CPU chain k-strongest ->
 cfear_np.surface_points, the room of test_cfear_restatement.py as records, and the restatement's tracks.  Everything is
 computed once per process (functools.lru_cache) and must be left unchanged by its users."""
 import functools
@@ -92,6 +92,37 @@ def small_track():
 @functools.lru_cache(maxsize=None)
 def small_pairs_track():
     return ct.track(small()[0], n_keyframes=1, keyframe_distance=0.0, keyframe_rotation=0.0, predict=0)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_cases():
+    """the pairs of tests/test_gpu_cfear.py: (name, src, dst, init, parameter overrides, expected status)"""
+    recs = drive()[0]
+    room = as_records(room64())
+    flat = room.copy()
+    flat["nx"], flat["ny"] = 1.0, 0.0
+    over = np.zeros(cf.MAX_SURFACE_POINTS + 1, dtype=cf.SP_DTYPE)
+    over["nx"] = 1.0
+    return tuple((f"drive pair {i}", recs[i], recs[i - 1], None, {}, 0) for i in (1, 2, 3)) + (
+        ("identical sets", recs[0], recs[0], None, {}, 0),
+        ("room moved", room, cf.transform(room, (0.4, -0.3, 0.02)), None, {}, 0),
+        ("non-identity init", recs[1], recs[0], (0.9, 0.1, 0.05), {}, 0),
+        ("100 m apart", room, cf.transform(room, (100.0, 0.0, 0.0)), (0.5, 0.25, 0.125), {}, 4),
+        ("normals (1, 0)", flat, flat, None, {}, 5),
+        ("two iterations", recs[1], recs[0], None, {"max_iterations": 2}, 8),
+        ("empty src", room[:0], room, (1.0, 2.0, 0.5), {}, 1),
+        ("empty dst", room, room[:0], None, {}, 1),
+        ("src over the cap", over, room, (1.0, 2.0, 0.5), {}, 2),
+        ("dst at the cap", room, over[:-1], None, {}, 4),
+    )
+
+
+def pair_groups():
+    """pair_cases() grouped by their parameter overrides, in first-seen order: [(sorted override items, cases, inits (n, 3))]"""
+    by_params = {}
+    for c in pair_cases():
+        by_params.setdefault(tuple(sorted(c[4].items())), []).append(c)
+    return [(key, cs, np.array([c[3] if c[3] is not None else (0.0, 0.0, 0.0) for c in cs])) for key, cs in by_params.items()]
 
 
 ROOM_POSES = ((0.0, 0.0, 0.0), (0.9, -0.4, 0.03), (1.7, -0.6, 0.07))  # two keyframes and the scan

@@ -40,39 +40,11 @@ def _search(s):
     return cfear.track_params(search=s)
 
 
-def _pair_cases():
-    """the pairs of tests/test_gpu_cfear.py: (name, src, dst, init, parameter overrides, expected status)"""
-    recs = cases.drive()[0]
-    room = cases.as_records(cases.room64())
-    flat = room.copy()
-    flat["nx"], flat["ny"] = 1.0, 0.0
-    over = np.zeros(cf.MAX_SURFACE_POINTS + 1, dtype=cf.SP_DTYPE)
-    over["nx"] = 1.0
-    out = [(f"drive pair {i}", recs[i], recs[i - 1], None, {}, 0) for i in (1, 2, 3)]
-    out += [
-        ("identical sets", recs[0], recs[0], None, {}, 0),
-        ("room moved", room, cf.transform(room, (0.4, -0.3, 0.02)), None, {}, 0),
-        ("non-identity init", recs[1], recs[0], (0.9, 0.1, 0.05), {}, 0),
-        ("100 m apart", room, cf.transform(room, (100.0, 0.0, 0.0)), (0.5, 0.25, 0.125), {}, 4),
-        ("normals (1, 0)", flat, flat, None, {}, 5),
-        ("two iterations", recs[1], recs[0], None, {"max_iterations": 2}, 8),
-        ("empty src", room[:0], room, (1.0, 2.0, 0.5), {}, 1),
-        ("empty dst", room, room[:0], None, {}, 1),
-        ("src over the cap", over, room, (1.0, 2.0, 0.5), {}, 2),
-        ("dst at the cap", room, over[:-1], None, {}, 4),
-    ]
-    return out
-
-
 def test_one_keyframe_at_the_identity_is_the_pair_kernel(handle):
     """2a: K = 1, pose (0, 0, 0), either search: the bytes of rsx_cfear_register_batch"""
     from navtech_radar_slam_amd import cfear
-    by_params = {}
-    for c in _pair_cases():
-        by_params.setdefault(tuple(sorted(c[4].items())), []).append(c)
-    for key, cs in by_params.items():
+    for key, cs, init in cases.pair_groups():
         prm = cfear.params(**dict(key))
-        init = np.array([c[3] if c[3] is not None else ID for c in cs])
         pair = handle.register([c[1] for c in cs], [c[2] for c in cs], init, prm)
         assert [int(p["status"]) for p in pair] == [c[5] for c in cs]
         for s in (0, 1):
@@ -80,7 +52,7 @@ def test_one_keyframe_at_the_identity_is_the_pair_kernel(handle):
             for c, g, p in zip(cs, got, pair):
                 assert g.tobytes() == p.tobytes(), (c[0], s, g, p)
     # init = NULL is the identity
-    c = _pair_cases()[0]
+    c = cases.pair_cases()[0]
     assert handle.register_keyframes([c[1]], [[c[2]]], [[ID]]).tobytes() == handle.register([c[1]], [c[2]]).tobytes()
 
 
