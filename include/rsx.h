@@ -768,7 +768,8 @@ typedef struct {
   int32_t n_keyframes;      /* ring size, 1 .. RSX_CFEAR_MAX_KEYFRAMES (3) */
   int32_t predict;          /* 1: start from the constant-velocity prediction P o M; 0: from P (1) */
   int32_t search;           /* RSX_CFEAR_SEARCH_* (RSX_CFEAR_SEARCH_CELLS) */
-  int32_t reserved[3];      /* 0 */
+  int32_t reserved[2];      /* 0 */
+  int32_t compensate;       /* 1: motion compensation inside the tracker (below; the timed pushes only); 0: none (0) */
 } rsx_cfear_track_params;
 
 typedef struct {
@@ -812,6 +813,66 @@ int rsx_cfear_tracker_push(rsx_cfear_tracker *h, const rsx_cfear_surface_point *
 int rsx_cfear_tracker_push_device(rsx_cfear_tracker *h, const rsx_cfear_surface_point *d_records, const int64_t *d_offsets,
                                   const int32_t *d_n_scans, const rsx_cfear_params *params, const rsx_cfear_track_params *track,
                                   rsx_cfear_track_result *d_out, void *stream);
+
+/* ---- CFEAR motion compensation: surface points with times, compensation of records, the two-pass tracker ----
+ * A spinning radar measures a scan over one revolution; the sensor's motion during it shears the scan.  The rules are restated in
+ * tests/cfear_mocomp_np.py (the arithmetic contract; parity unpinned).  Doppler on records is out of scope.
+ * Time of a record: the timed surface-point entries take the azimuth row of every point (0 .. n_rows - 1, as for
+ * rsx_mocomp_points_batch; 1 <= n_rows <= 65536) and give every record tau in [0, 1], the fraction of the revolution at which it
+ * was measured: the CIRCULAR mean of its neighbours' rows.  With the neighbours in the order of the surface-point rule, rows
+ * a_1 .. a_m, and h = n_rows / 2 (integer division): d_k = ((a_k - a_1 + h) mod n_rows, non-negative) - h, S = sum d_k (integers),
+ * u = ((double)a_1 + (double)S / (double)m) + 0.5, wrapped once into [0, n_rows) (u < 0: u + n_rows; else u >= n_rows: u - n_rows),
+ * tau = (float)(u / n_rows).  Neighbours on both sides of the row 0 / row n_rows - 1 seam give a time near the seam, not 0.5.
+ * The records are rsx_cfear_surface_points_batch's byte for byte.
+ * Compensation of a record measured at tau under `motion` = (x, y, yaw), the sensor's motion over one scan period in the
+ * rsx_orora_result convention: rsx_mocomp's deskewing with dt_scan = 1 and no Doppler term.  (vx, vy, wz) = the velocity of the
+ * motion (rsx_mocomp above, dt_scan = 1); th = wz tau; sn, cs, A, B = rsx_mocomp's fixed polynomials at th;
+ *   x' = (cs x - sn y) + (A vx - B vy) tau,  y' = (sn x + cs y) + (B vx + A vy) tau,  n' = (cs nx - sn ny, sn nx + cs ny),
+ * fp64 in this order, nothing fused, rounded to the record's floats once; every other field is copied.  A motion with not
+ * |yaw| <= 0.5 or a non-finite component leaves the scan's records as they are and sets the scan's status word to 1
+ * (the RSX_MOCOMP_STATUS_ANGLE rule); a motion that is exactly (0, 0, 0) copies the records: the input's bytes.
+ * Tracker with rsx_cfear_track_params.compensate = 1 (rsx_cfear_tracker_push_timed only; P, M and the ring as above, comp(records,
+ * M) the compensation just described).  Compensating with the PREDICTED motion alone is unstable (an error of the motion
+ * becomes an error of the compensation and then of the next motion), so every scan is registered twice:
+ *   scan 0   the first keyframe, as measured; the state remembers that (`first`) and keeps the scan's times
+ *   scan i   pass 1: C0 = comp(scan, M), registered against the ring from the start pose of the rule above -> reg1
+ *     reg1 status 1, 2, 4, 5: the failure rule above with C0 as the scan; `first` is cleared; reg = reg1
+ *     reg1 status 0, 8: P1 = its pose, M1 = P^-1 o P1.  If `first`: the ring's only keyframe becomes comp(its records, its times,
+ *       M1) at its pose, is binned again, and `first` is cleared.  C1 = comp(scan, M1); pass 2: C1 registered against the ring
+ *       from P1 -> reg2
+ *         reg2 status 0, 8: M = P^-1 o P2, P = P2; the keyframe decision above, with C1 as the keyframe's records
+ *         reg2 fails: P = P1, M = M1, and C1 becomes the ring's only entry at P1 (flag 2)
+ *       reg = reg2 in both cases, with reg.reserved = the iterations of pass 1
+ * The scan is compensated once per pass, outside the Gauss-Newton loop.  As without compensation, results depend neither on how
+ * a sequence is cut into pushes (the cut between scan 0 and scan 1 included) nor on how many sequences run side by side. */
+/* rsx_cfear_surface_points_batch plus rows (int32 per point, checked to lie in [0, n_rows): RSX_ERR_BAD_ARG otherwise) and out_tau
+ * (one float per record slot, laid out like out_records: scan i's at out_tau + i * max_records) */
+int rsx_cfear_surface_points_timed_batch(rsx_cfear *h, const float *xy, const int32_t *rows, int32_t n_rows, const int64_t *offsets,
+                                         int32_t n_scans, const rsx_cfear_params *params, rsx_cfear_surface_point *out_records,
+                                         float *out_tau, int32_t max_records, int32_t *out_counts, int32_t *out_status);
+/* device buffers, asynchronous on `stream`, no allocation; offsets and rows are trusted (a row outside [0, n_rows) gives a
+ * meaningless time, nothing else) */
+int rsx_cfear_surface_points_timed_batch_device(rsx_cfear *h, const float *d_xy, const int32_t *d_rows, int32_t n_rows,
+                                                const int64_t *d_offsets, int32_t n_scans, const rsx_cfear_params *params,
+                                                rsx_cfear_surface_point *d_records, float *d_tau, int32_t max_records, int32_t *d_counts,
+                                                int32_t *d_status, void *stream);
+/* n_scans scans in the ragged layout: scan i owns records (and times) [offsets[i], offsets[i + 1]) and is compensated with
+ * motion[3 i ..]; out_status[i] (may be NULL) 0 or 1.  out_records may be records.  Host buffers, synchronous.  One launch, one
+ * thread per record. */
+int rsx_cfear_compensate_batch(rsx_cfear *h, const rsx_cfear_surface_point *records, const float *tau, const int64_t *offsets,
+                               int32_t n_scans, const double *motion, rsx_cfear_surface_point *out_records, int32_t *out_status);
+/* device buffers, asynchronous on `stream`, no allocation; offsets trusted */
+int rsx_cfear_compensate_batch_device(rsx_cfear *h, const rsx_cfear_surface_point *d_records, const float *d_tau, const int64_t *d_offsets,
+                                      int32_t n_scans, const double *d_motion, rsx_cfear_surface_point *d_out_records,
+                                      int32_t *d_out_status, void *stream);
+/* rsx_cfear_tracker_push with the records' times (tau[j] beside records[j]).  compensate = 0: rsx_cfear_tracker_push's bytes (tau
+ * is not read).  rsx_cfear_tracker_push itself refuses compensate = 1 (RSX_ERR_BAD_ARG) */
+int rsx_cfear_tracker_push_timed(rsx_cfear_tracker *h, const rsx_cfear_surface_point *records, const float *tau, const int64_t *offsets,
+                                 const int32_t *n_scans, const rsx_cfear_params *params, const rsx_cfear_track_params *track,
+                                 rsx_cfear_track_result *out);
+int rsx_cfear_tracker_push_timed_device(rsx_cfear_tracker *h, const rsx_cfear_surface_point *d_records, const float *d_tau,
+                                        const int64_t *d_offsets, const int32_t *d_n_scans, const rsx_cfear_params *params,
+                                        const rsx_cfear_track_params *track, rsx_cfear_track_result *d_out, void *stream);
 
 /* ============================== radar scan context ====================================
  * The "radar scan context" of the MulRan paper (Kim et al., ICRA 2020; reference README.md:28-29): the 20 x 60 polar grid
@@ -1015,7 +1076,11 @@ int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params);
  * scan; params = NULL goes back to pairs (as does leaving CFEAR); without this call nothing changes.  rsx_odometry_scan.reg carries
  * the relative motion P_{i-1}^-1 o P_i of the tracked poses, with status, iterations and correspondences of the scan's registration
  * against its keyframes as above (status 1, 2, 4, 5: the motion is the prediction's); the first scan's status stays 3.  Results do
- * not depend on how the sequence is cut into calls. */
+ * not depend on how the sequence is cut into calls.
+ * params->compensate = 1: the window builds the surface points with their times (rsx_cfear_surface_points_timed_batch: the rows of
+ * the extractor's targets, n_rows = the image's rows, at most 65536) and runs the tracker's two-pass rule on them
+ * (rsx_cfear_tracker_push_timed).  out_xy stays the keypoints as measured: what compensation would mean for the published cloud
+ * is out of scope.  rsx_odometry_set_compensation, which compensates MATCHES, still refuses while CFEAR is selected. */
 int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_params *params);
 /* n_scans consecutive scans, host images image_stride_bytes apart (rows x row_stride bytes each); azimuths: rows floats
  * (rad, increasing) shared by all scans or n_scans x rows when azimuths_per_image != 0.  out [n_scans]; out_xy

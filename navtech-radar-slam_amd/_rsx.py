@@ -119,7 +119,7 @@ class CfearParams(C.Structure):
 
 class CfearTrackParams(C.Structure):
     _fields_ = [("keyframe_distance", C.c_double), ("keyframe_rotation", C.c_double), ("n_keyframes", C.c_int32), ("predict", C.c_int32),
-                ("search", C.c_int32), ("reserved", C.c_int32 * 3)]
+                ("search", C.c_int32), ("reserved", C.c_int32 * 2), ("compensate", C.c_int32)]
 
 
 CFEAR_MAX_POINTS, CFEAR_MAX_SURFACE_POINTS = 16384, 4096
@@ -215,6 +215,8 @@ SYMBOLS = [
     "rsx_cfear_surface_points_batch_device", "rsx_cfear_register_batch", "rsx_cfear_register_batch_device", "rsx_odometry_set_cfear", "rsx_odometry_set_cfear_tracking",
     "rsx_cfear_default_track_params", "rsx_cfear_register_keyframes_batch", "rsx_cfear_register_keyframes_batch_device",
     "rsx_cfear_tracker_create", "rsx_cfear_tracker_destroy", "rsx_cfear_tracker_reset", "rsx_cfear_tracker_push", "rsx_cfear_tracker_push_device",
+    "rsx_cfear_surface_points_timed_batch", "rsx_cfear_surface_points_timed_batch_device", "rsx_cfear_compensate_batch",
+    "rsx_cfear_compensate_batch_device", "rsx_cfear_tracker_push_timed", "rsx_cfear_tracker_push_timed_device",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
@@ -366,6 +368,12 @@ def lib():
         L.rsx_cfear_tracker_reset.argtypes = [vp]
         L.rsx_cfear_tracker_push.argtypes = [vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp]
         L.rsx_cfear_tracker_push_device.argtypes = [vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp, vp]
+        L.rsx_cfear_surface_points_timed_batch.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(CfearParams), vp, vp, i32, vp, vp]
+        L.rsx_cfear_surface_points_timed_batch_device.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(CfearParams), vp, vp, i32, vp, vp, vp]
+        L.rsx_cfear_compensate_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+        L.rsx_cfear_compensate_batch_device.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.rsx_cfear_tracker_push_timed.argtypes = [vp, vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp]
+        L.rsx_cfear_tracker_push_timed_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp, vp]
         L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
         L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
         L.rsx_radarsc_destroy.argtypes = [vp]

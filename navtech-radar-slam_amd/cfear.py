@@ -28,7 +28,7 @@ def params(**fields):
 
 
 def default_track_params():
-    """n_keyframes 3, keyframe_distance 1.5 m, keyframe_rotation 5 deg, predict 1, search 0 (the cell index)."""
+    """n_keyframes 3, keyframe_distance 1.5 m, keyframe_rotation 5 deg, predict 1, search 0 (the cell index), compensate 0."""
     p = CfearTrackParams()
     check(lib().rsx_cfear_default_track_params(C.byref(p)))
     return p
@@ -87,6 +87,34 @@ class Cfear:
             return rec, counts, status
         return [rec[i, :min(int(counts[i]), max_records)].copy() for i in range(n)], counts, status
 
+    def surface_points_timed(self, clouds, rows, n_rows, params=None, max_records=CFEAR_MAX_SURFACE_POINTS):
+        """surface_points with the azimuth row of every point (rows: list of (n_i,) int32 in [0, n_rows))
+        -> (list of records, list of times (k_i,) float32, counts, status words)"""
+        xy, offsets = ragged(clouds, np.float32, 2)
+        a, _ = ragged(rows, np.int32)
+        assert len(a) == len(xy)
+        n = len(clouds)
+        rec = np.zeros((n, max_records), dtype=CFEAR_SURFACE_POINT_DTYPE)
+        tau = np.zeros((n, max_records), dtype=np.float32)
+        counts, status = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        check(self._L.rsx_cfear_surface_points_timed_batch(self._h, xy.ctypes.data, a.ctypes.data, n_rows, offsets.ctypes.data, n, _ref(params),
+                                                           rec.ctypes.data, tau.ctypes.data, max_records, counts.ctypes.data, status.ctypes.data))
+        keep = [min(int(c), max_records) for c in counts]
+        return [rec[i, :k].copy() for i, k in enumerate(keep)], [tau[i, :k].copy() for i, k in enumerate(keep)], counts, status
+
+    def compensate(self, records, taus, motions):
+        """scan i's records (measured at taus[i], fractions of the scan period) compensated with motions[i] = (x, y, yaw), the
+        sensor's motion over one scan period -> (list of records, status words: 1 = left as measured)"""
+        rec, offsets = ragged(records, CFEAR_SURFACE_POINT_DTYPE)
+        tau, _ = ragged(taus, np.float32)
+        assert len(tau) == len(rec)
+        n = len(records)
+        motions = np.ascontiguousarray(motions, dtype=np.float64).reshape(n, 3)
+        out, status = np.zeros_like(rec), np.zeros(n, dtype=np.int32)
+        check(self._L.rsx_cfear_compensate_batch(self._h, rec.ctypes.data, tau.ctypes.data, offsets.ctypes.data, n, motions.ctypes.data,
+                                                 out.ctypes.data, status.ctypes.data))
+        return [out[offsets[i]:offsets[i + 1]] for i in range(n)], status
+
     def register(self, src, dst, init=None, params=None):
         """src, dst: lists of record arrays (pair i registers src[i] to dst[i]); init: (n, 3) float64 or None
         -> (n,) CFEAR_RESULT_DTYPE"""
@@ -132,6 +160,14 @@ class Cfear:
         check(self._L.rsx_cfear_surface_points_batch_device(self._h, d_xy, d_offsets, n_scans, C.byref(params) if params is not None else None,
                                                             d_records, max_records, d_counts, d_status, stream))
 
+    def surface_points_timed_device(self, d_xy, d_rows, n_rows, d_offsets, n_scans, d_records, d_tau, max_records, d_counts, d_status=None,
+                                    params=None, stream=None):
+        check(self._L.rsx_cfear_surface_points_timed_batch_device(self._h, d_xy, d_rows, n_rows, d_offsets, n_scans, _ref(params), d_records, d_tau,
+                                                                  max_records, d_counts, d_status, stream))
+
+    def compensate_device(self, d_records, d_tau, d_offsets, n_scans, d_motion, d_out, d_status=None, stream=None):
+        check(self._L.rsx_cfear_compensate_batch_device(self._h, d_records, d_tau, d_offsets, n_scans, d_motion, d_out, d_status, stream))
+
     def register_device(self, d_src, d_src_offsets, d_dst, d_dst_offsets, n_pairs, d_out, d_init=None, params=None, stream=None):
         check(self._L.rsx_cfear_register_batch_device(self._h, d_src, d_src_offsets, d_dst, d_dst_offsets, n_pairs, d_init,
                                                       C.byref(params) if params is not None else None, d_out, stream))
@@ -176,6 +212,26 @@ class Tracker:
         ends = np.cumsum(n_scans)
         parts = [out[e - m:e] for e, m in zip(ends, n_scans)]
         return parts[0] if single else parts
+
+    def push_timed(self, scans, taus):
+        """push with the records' times (taus: laid out like scans, (k,) float32 per scan); what track.compensate = 1 needs"""
+        single = self.n_sequences == 1 and (len(scans) == 0 or isinstance(scans[0], np.ndarray))
+        seqs, tseqs = ([scans], [taus]) if single else (scans, taus)
+        assert len(seqs) == self.n_sequences and len(tseqs) == self.n_sequences
+        rec, off = ragged([s for q in seqs for s in q], CFEAR_SURFACE_POINT_DTYPE)
+        tau, _ = ragged([u for q in tseqs for u in q], np.float32)
+        assert len(tau) == len(rec)
+        n_scans = np.array([len(q) for q in seqs], dtype=np.int32)
+        out = np.zeros(int(n_scans.sum()), dtype=CFEAR_TRACK_RESULT_DTYPE)
+        check(self._L.rsx_cfear_tracker_push_timed(self._h, rec.ctypes.data, tau.ctypes.data, off.ctypes.data, n_scans.ctypes.data,
+                                                   _ref(self.params), _ref(self.track), out.ctypes.data))
+        ends = np.cumsum(n_scans)
+        parts = [out[e - m:e] for e, m in zip(ends, n_scans)]
+        return parts[0] if single else parts
+
+    def push_timed_device(self, d_records, d_tau, d_offsets, d_n_scans, d_out, stream=None):
+        check(self._L.rsx_cfear_tracker_push_timed_device(self._h, d_records, d_tau, d_offsets, d_n_scans, _ref(self.params), _ref(self.track),
+                                                          d_out, stream))
 
     def push_device(self, d_records, d_offsets, d_n_scans, d_out, stream=None):
         """raw HBM addresses, asynchronous on `stream` (None: the handle's own)"""

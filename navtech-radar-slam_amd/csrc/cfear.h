@@ -10,7 +10,7 @@ struct rsx_cfear {
   std::mutex mu;
   rsx::Stream stream;
   rsx::StreamOrder order;  // the staging buffers are shared by every host-buffer call
-  rsx::DevBuf in0, in1, off0, off1, init, out, cnt, st;  // staging of the host-buffer entries
+  rsx::DevBuf in0, in1, off0, off1, init, out, cnt, st, tau;  // staging of the host-buffer entries
   rsx::DevBuf job_off, poses, index;  // registration: the jobs' keyframe ranges and poses (staging), the cell-index workspace
 };
 
@@ -27,6 +27,11 @@ int resolve(const rsx_cfear_params *params, const rsx_cfear_track_params *track,
 // scan i's records to d_out + i * max_records, d_counts[i] every record found, d_status[i] (may be null) the status word
 int launch_surface(const float *d_xy, const int64_t *d_begin, const int64_t *d_end, int32_t n_scans, const rsx_cfear_params &p,
                    rsx_cfear_surface_point *d_out, int32_t max_records, int32_t *d_counts, int32_t *d_status, hipStream_t s);
+// the same with the records' times: point j of group i was measured on azimuth row d_rows[(d_begin[i] + j) * row_stride] of n_rows
+// (1 .. 65536, checked); scan i's times to d_out_tau + i * max_records.  The records are launch_surface's bytes
+int launch_surface_timed(const float *d_xy, const int32_t *d_rows, int32_t row_stride, int32_t n_rows, const int64_t *d_begin,
+                         const int64_t *d_end, int32_t n_scans, const rsx_cfear_params &p, rsx_cfear_surface_point *d_out, float *d_out_tau,
+                         int32_t max_records, int32_t *d_counts, int32_t *d_status, hipStream_t s);
 
 // ---- csrc/cfear_track.hip: registration, and the tracker ----
 int check_track_params(const rsx_cfear_track_params &p);
@@ -46,8 +51,9 @@ int launch_register(const rsx_cfear_surface_point *d_src, const int64_t *d_src_b
 // bytes of tracker state of one sequence (zero = a sequence that has seen no scan)
 size_t track_state_bytes();
 // sequence q (one workgroup) runs its d_n_scans[q] scans -- group sum(d_n_scans[0 .. q)) + i of (d_records, d_begin, d_end) is its
-// scan i -- through the tracker and writes one rsx_cfear_track_result per scan at the same index of d_out
-int launch_track(const rsx_cfear_surface_point *d_records, const int64_t *d_begin, const int64_t *d_end, const int32_t *d_n_scans,
+// scan i -- through the tracker and writes one rsx_cfear_track_result per scan at the same index of d_out.  d_tau: the records'
+// times, element for element beside d_records; read only with tp.compensate (null without)
+int launch_track(const rsx_cfear_surface_point *d_records, const float *d_tau, const int64_t *d_begin, const int64_t *d_end, const int32_t *d_n_scans,
                  int32_t n_sequences, const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_state,
                  rsx_cfear_track_result *d_out, hipStream_t s);
 

@@ -15,6 +15,10 @@
 //      block twice (count and mean, then the covariance) in the contract's order; the points themselves are read from HBM
 //      through the sorted indices (the whole cloud is at most 128 KiB: it stays in cache, and it would not fit beside the keys)
 //   5. per 1024 positions the kept cells are compacted in cell order: a ballot per wavefront, the wavefronts' counts scanned
+// cfear_surface_kernel<true> (rsx_cfear_surface_points_timed_batch) also gives every record the time it was measured: the owner
+//   lane reads the neighbours' azimuth rows in its second walk and takes their circular mean.  cfear_compensate_kernel deskews
+//   records with the motion of their scan (csrc/cfear_dev.h: comp_record, on csrc/mocomp_dev.h's polynomials); the contract of both
+//   is tests/cfear_mocomp_np.py.
 // The registration of surface-point sets is csrc/cfear_track.hip's, the pair entries included; this file keeps the handle and the
 // parameter rules they share.
 #include <hip/hip_runtime.h>
@@ -30,6 +34,8 @@
 #include "ragged_host.h"
 
 #pragma STDC FP_CONTRACT OFF
+
+using rsx::fail;
 
 namespace {
 
@@ -59,10 +65,15 @@ __device__ __forceinline__ void for_block(const unsigned *keys, const unsigned s
     }
 }
 
+// TIMED: point i of the scan was measured on azimuth row rows[(begin + i) * row_stride] of n_rows; a record's time, the circular
+// mean of its neighbours' rows as a fraction of the revolution, goes to out_tau (laid out like out).  Untimed, the kernel is the
+// code it was: everything timed sits behind if constexpr
+template <bool TIMED>
 __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restrict__ xy, const int64_t *__restrict__ begin,
                                                            const int64_t *__restrict__ end, SpConsts k,
                                                            rsx_cfear_surface_point *__restrict__ out, int32_t *__restrict__ counts,
-                                                           int32_t *__restrict__ status) {
+                                                           int32_t *__restrict__ status, const int32_t *__restrict__ rows, int row_stride,
+                                                           int n_rows, float *__restrict__ out_tau) {
   extern __shared__ __attribute__((aligned(16))) unsigned char cf_lds[];
   unsigned *keys = reinterpret_cast<unsigned *>(cf_lds);                                             // [<= 16384]
   unsigned short *start = reinterpret_cast<unsigned short *>(cf_lds + (size_t)RSX_CFEAR_MAX_POINTS * 4);  // [16384]
@@ -108,6 +119,7 @@ __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restr
     const unsigned i = base + t;
     bool keep = false;
     rsx_cfear_surface_point rec;
+    float tau = 0.f;
     if (i < n) {
       const unsigned key = keys[i];
       if (key != NO_KEY && (i == 0 || (keys[i - 1] >> IDX_BITS) != (key >> IDX_BITS))) {
@@ -136,6 +148,8 @@ __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restr
         if (m >= k.min_points) {
           const double mx = sx / (double)m, my = sy / (double)m;
           double sxx = 0.0, syy = 0.0, sxy = 0.0;
+          int a1 = -1, dsum = 0;  // the first neighbour's row; the sum of the others' signed row distances from it (|d| <= 32768,
+                                  // m <= 16384: an int holds it)
           for_block(keys, start, n, ix, iy, [&](unsigned idx) {
             const float2 q = p[idx];
             const double ex = (double)q.x - cx, ey = (double)q.y - cy;
@@ -144,8 +158,23 @@ __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restr
               sxx = sxx + ux * ux;
               syy = syy + uy * uy;
               sxy = sxy + ux * uy;
+              if constexpr (TIMED) {
+                const int a = rows[(b + (int64_t)idx) * row_stride], half = n_rows / 2;
+                if (a1 < 0) a1 = a;
+                int d = (a - a1 + half) % n_rows;
+                d = d < 0 ? d + n_rows : d;
+                dsum += d - half;
+              }
             }
           });
+          if constexpr (TIMED) {
+            double u = ((double)a1 + (double)dsum / (double)m) + 0.5;
+            if (u < 0.0)
+              u = u + (double)n_rows;
+            else if (u >= (double)n_rows)
+              u = u - (double)n_rows;
+            tau = (float)(u / (double)n_rows);
+          }
           const double m1 = (double)(m - 1);
           sxx = sxx / m1;
           syy = syy / m1;
@@ -196,7 +225,10 @@ __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restr
     }
     if (keep) {
       const unsigned pos = before + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-      if (pos < (unsigned)k.max_records) o[pos] = rec;
+      if (pos < (unsigned)k.max_records) {
+        o[pos] = rec;
+        if constexpr (TIMED) out_tau[(int64_t)scan * k.max_records + pos] = tau;
+      }
     }
     run += total;
     __syncthreads();
@@ -208,8 +240,6 @@ __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restr
 }
 
 }  // namespace
-
-using rsx::fail;
 
 int rsx::cfear::check_params(const rsx_cfear_params &p) {
   if (!(p.radius > 0.0) || !std::isfinite(p.radius)) return fail(RSX_ERR_BAD_ARG, "radius must be positive");
@@ -223,22 +253,74 @@ int rsx::cfear::check_params(const rsx_cfear_params &p) {
   return RSX_OK;
 }
 
-int rsx::cfear::launch_surface(const float *d_xy, const int64_t *d_begin, const int64_t *d_end, int32_t n_scans, const rsx_cfear_params &p,
-                               rsx_cfear_surface_point *d_out, int32_t max_records, int32_t *d_counts, int32_t *d_status, hipStream_t s) {
+namespace {
+
+template <bool TIMED>
+int launch_surface_t(const float *d_xy, const int64_t *d_begin, const int64_t *d_end, int32_t n_scans, const rsx_cfear_params &p,
+                     rsx_cfear_surface_point *d_out, int32_t max_records, int32_t *d_counts, int32_t *d_status, const int32_t *d_rows,
+                     int32_t row_stride, int32_t n_rows, float *d_out_tau, hipStream_t s) {
   if (n_scans < 1) return fail(RSX_ERR_BAD_ARG, "n_scans %d below 1", n_scans);
   if (max_records < 1 || max_records > RSX_CFEAR_MAX_SURFACE_POINTS)
     return fail(RSX_ERR_BAD_ARG, "max_records %d outside [1, %d]", max_records, RSX_CFEAR_MAX_SURFACE_POINTS);
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfear_surface_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SP_LDS));
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfear_surface_kernel<TIMED>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)SP_LDS));
   SpConsts k;
   k.r = p.radius;
   k.r2 = p.radius * p.radius;
   k.max_condition = p.max_condition;
   k.min_points = p.min_points;
   k.max_records = max_records;
-  hipLaunchKernelGGL(cfear_surface_kernel, dim3((unsigned)n_scans), dim3(NT), SP_LDS, s, reinterpret_cast<const float2 *>(d_xy), d_begin, d_end, k,
-                     d_out, d_counts, d_status);
+  hipLaunchKernelGGL(cfear_surface_kernel<TIMED>, dim3((unsigned)n_scans), dim3(NT), SP_LDS, s, reinterpret_cast<const float2 *>(d_xy), d_begin,
+                     d_end, k, d_out, d_counts, d_status, d_rows, (int)row_stride, (int)n_rows, d_out_tau);
   RSX_HIP(hipGetLastError());
   return RSX_OK;
+}
+
+// cfear_compensate_kernel: one thread per record, CHUNKS workgroups per scan (4096 records a sweep); the scan's motion is read
+// through a wave-uniform address.  A record is two 16-byte halves: (x, y, nx, ny), which compensation rewrites, and the rest,
+// copied.  No LDS, no barrier; the status word is written by one thread.  out may be the input
+constexpr int CNT = 256, CHUNKS = 16;
+constexpr int32_t MAX_COMP_SCANS = 0x7fffffff / CHUNKS;
+
+__global__ __launch_bounds__(CNT) void cfear_compensate_kernel(const float4 *rec, const float *__restrict__ tau, const int64_t *__restrict__ offsets,
+                                                               const double *__restrict__ motion, float4 *out, int32_t *__restrict__ status) {
+  const int scan = blockIdx.x / CHUNKS, chunk = blockIdx.x % CHUNKS;
+  const int64_t o = offsets[scan], n = offsets[scan + 1] - o;
+  const CompMotion m = comp_motion(motion[3 * (int64_t)scan], motion[3 * (int64_t)scan + 1], motion[3 * (int64_t)scan + 2]);
+  if (status && chunk == 0 && threadIdx.x == 0) status[scan] = m.how == 2 ? 1 : 0;
+  for (int64_t i = (int64_t)chunk * CNT + threadIdx.x; i < n; i += (int64_t)CHUNKS * CNT) {
+    const float4 q = rec[2 * (o + i)], rest = rec[2 * (o + i) + 1];
+    out[2 * (o + i)] = m.how == 0 ? comp_record(q, tau[o + i], m) : q;
+    out[2 * (o + i) + 1] = rest;
+  }
+}
+
+int launch_compensate(const rsx_cfear_surface_point *d_rec, const float *d_tau, const int64_t *d_offsets, int32_t n_scans, const double *d_motion,
+                      rsx_cfear_surface_point *d_out, int32_t *d_status, hipStream_t s) {
+  if (n_scans < 1 || n_scans > MAX_COMP_SCANS) return fail(RSX_ERR_BAD_ARG, "n_scans %d outside [1, %d]", n_scans, MAX_COMP_SCANS);
+  hipLaunchKernelGGL(cfear_compensate_kernel, dim3((unsigned)n_scans * CHUNKS), dim3(CNT), 0, s, reinterpret_cast<const float4 *>(d_rec), d_tau,
+                     d_offsets, d_motion, reinterpret_cast<float4 *>(d_out), d_status);
+  RSX_HIP(hipGetLastError());
+  return RSX_OK;
+}
+
+int check_n_rows(int32_t n_rows) {
+  if (n_rows < 1 || n_rows > 65536) return fail(RSX_ERR_BAD_ARG, "n_rows %d outside [1, 65536]", n_rows);
+  return RSX_OK;
+}
+
+}  // namespace
+
+int rsx::cfear::launch_surface(const float *d_xy, const int64_t *d_begin, const int64_t *d_end, int32_t n_scans, const rsx_cfear_params &p,
+                               rsx_cfear_surface_point *d_out, int32_t max_records, int32_t *d_counts, int32_t *d_status, hipStream_t s) {
+  return launch_surface_t<false>(d_xy, d_begin, d_end, n_scans, p, d_out, max_records, d_counts, d_status, nullptr, 1, 1, nullptr, s);
+}
+
+int rsx::cfear::launch_surface_timed(const float *d_xy, const int32_t *d_rows, int32_t row_stride, int32_t n_rows, const int64_t *d_begin,
+                                     const int64_t *d_end, int32_t n_scans, const rsx_cfear_params &p, rsx_cfear_surface_point *d_out,
+                                     float *d_out_tau, int32_t max_records, int32_t *d_counts, int32_t *d_status, hipStream_t s) {
+  RSX_TRY(check_n_rows(n_rows));
+  return launch_surface_t<true>(d_xy, d_begin, d_end, n_scans, p, d_out, max_records, d_counts, d_status, d_rows, row_stride, n_rows, d_out_tau, s);
 }
 
 int rsx::cfear::resolve(const rsx_cfear_params *params, const rsx_cfear_track_params *track, rsx_cfear_params &dp, rsx_cfear_track_params *dt) {
@@ -332,6 +414,101 @@ int rsx_cfear_surface_points_batch(rsx_cfear *h, const float *xy, const int64_t 
                                      h->out.as<rsx_cfear_surface_point>(), max_records, h->cnt.as<int32_t>(), h->st.as<int32_t>(), s));
   RSX_TRY(rsx::stage_down(out_records, h->out, ob, s));
   RSX_TRY(rsx::stage_down(out_counts, h->cnt, n * 4, s));
+  RSX_TRY(rsx::stage_down(out_status, h->st, n * 4, s));
+  RSX_HIP(hipStreamSynchronize(s));
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_cfear_surface_points_timed_batch_device(rsx_cfear *h, const float *d_xy, const int32_t *d_rows, int32_t n_rows, const int64_t *d_offsets,
+                                                int32_t n_scans, const rsx_cfear_params *params, rsx_cfear_surface_point *d_records,
+                                                float *d_tau, int32_t max_records, int32_t *d_counts, int32_t *d_status, void *stream) try {
+  if (!h || !d_xy || !d_rows || !d_offsets || !d_records || !d_tau || !d_counts || n_scans < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  rsx_cfear_params dp;
+  RSX_TRY(rsx::cfear::resolve(params, nullptr, dp, nullptr));
+  RSX_TRY(check_n_rows(n_rows));
+  if (max_records < 1 || max_records > RSX_CFEAR_MAX_SURFACE_POINTS)
+    return fail(RSX_ERR_BAD_ARG, "max_records %d outside [1, %d]", max_records, RSX_CFEAR_MAX_SURFACE_POINTS);
+  if (n_scans == 0) return RSX_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
+  return rsx::cfear::launch_surface_timed(d_xy, d_rows, 1, n_rows, d_offsets, d_offsets + 1, n_scans, dp, d_records, d_tau, max_records, d_counts,
+                                          d_status, s);
+} RSX_CATCH_ALL
+
+int rsx_cfear_surface_points_timed_batch(rsx_cfear *h, const float *xy, const int32_t *rows, int32_t n_rows, const int64_t *offsets, int32_t n_scans,
+                                         const rsx_cfear_params *params, rsx_cfear_surface_point *out_records, float *out_tau,
+                                         int32_t max_records, int32_t *out_counts, int32_t *out_status) try {
+  if (!h || !xy || !rows || !offsets || !out_records || !out_tau || n_scans < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  rsx_cfear_params dp;
+  RSX_TRY(rsx::cfear::resolve(params, nullptr, dp, nullptr));
+  RSX_TRY(check_n_rows(n_rows));
+  if (max_records < 1 || max_records > RSX_CFEAR_MAX_SURFACE_POINTS)
+    return fail(RSX_ERR_BAD_ARG, "max_records %d outside [1, %d]", max_records, RSX_CFEAR_MAX_SURFACE_POINTS);
+  if (n_scans == 0) return RSX_OK;
+  RSX_TRY(rsx::check_offsets(offsets, n_scans, "rsx_cfear_surface_points_timed_batch"));
+  for (int32_t i = 0; i < n_scans; i++)
+    if (offsets[i + 1] - offsets[i] > RSX_CFEAR_MAX_POINTS)
+      return fail(RSX_ERR_BAD_ARG, "scan %d has %lld points, more than %d", i, (long long)(offsets[i + 1] - offsets[i]), RSX_CFEAR_MAX_POINTS);
+  const size_t m = (size_t)offsets[n_scans], n = (size_t)n_scans, slots = n * (size_t)max_records, ob = slots * sizeof(rsx_cfear_surface_point);
+  for (size_t i = 0; i < m; i++)
+    if (rows[i] < 0 || rows[i] >= n_rows) return fail(RSX_ERR_BAD_ARG, "rows[%lld] = %d outside [0, %d)", (long long)i, rows[i], n_rows);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(rsx::stage_up(h->in0, xy, m * 8, s));
+  RSX_TRY(rsx::stage_up(h->in1, rows, m * 4, s));
+  RSX_TRY(rsx::stage_up(h->off0, offsets, (n + 1) * 8, s));
+  RSX_TRY(rsx::stage_room(h->out, ob, s));
+  RSX_TRY(rsx::stage_room(h->tau, slots * 4, s));
+  RSX_TRY(rsx::stage_room(h->cnt, n * 4, s));
+  RSX_TRY(rsx::stage_room(h->st, n * 4, s));
+  RSX_HIP(hipMemsetAsync(h->out.p, 0, ob, s));  // (the slots past a scan's count come back as zeros)
+  RSX_HIP(hipMemsetAsync(h->tau.p, 0, slots * 4, s));
+  RSX_TRY(rsx::cfear::launch_surface_timed(h->in0.as<float>(), h->in1.as<int32_t>(), 1, n_rows, h->off0.as<int64_t>(), h->off0.as<int64_t>() + 1,
+                                           n_scans, dp, h->out.as<rsx_cfear_surface_point>(), h->tau.as<float>(), max_records, h->cnt.as<int32_t>(),
+                                           h->st.as<int32_t>(), s));
+  RSX_TRY(rsx::stage_down(out_records, h->out, ob, s));
+  RSX_TRY(rsx::stage_down(out_tau, h->tau, slots * 4, s));
+  RSX_TRY(rsx::stage_down(out_counts, h->cnt, n * 4, s));
+  RSX_TRY(rsx::stage_down(out_status, h->st, n * 4, s));
+  RSX_HIP(hipStreamSynchronize(s));
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_cfear_compensate_batch_device(rsx_cfear *h, const rsx_cfear_surface_point *d_records, const float *d_tau, const int64_t *d_offsets,
+                                      int32_t n_scans, const double *d_motion, rsx_cfear_surface_point *d_out_records, int32_t *d_out_status,
+                                      void *stream) try {
+  if (!h || !d_records || !d_tau || !d_offsets || !d_motion || !d_out_records || n_scans < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  if (n_scans == 0) return RSX_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
+  return launch_compensate(d_records, d_tau, d_offsets, n_scans, d_motion, d_out_records, d_out_status, s);
+} RSX_CATCH_ALL
+
+int rsx_cfear_compensate_batch(rsx_cfear *h, const rsx_cfear_surface_point *records, const float *tau, const int64_t *offsets, int32_t n_scans,
+                               const double *motion, rsx_cfear_surface_point *out_records, int32_t *out_status) try {
+  if (!h || !records || !tau || !offsets || !motion || !out_records || n_scans < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  if (n_scans == 0) return RSX_OK;
+  RSX_TRY(rsx::check_offsets(offsets, n_scans, "rsx_cfear_compensate_batch"));
+  const size_t m = (size_t)offsets[n_scans], n = (size_t)n_scans, rb = m * sizeof(rsx_cfear_surface_point);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(rsx::stage_up(h->in0, records, rb, s));
+  RSX_TRY(rsx::stage_up(h->in1, tau, m * 4, s));
+  RSX_TRY(rsx::stage_up(h->off0, offsets, (n + 1) * 8, s));
+  RSX_TRY(rsx::stage_up(h->init, motion, n * 24, s));
+  RSX_TRY(rsx::stage_room(h->out, rb, s));
+  RSX_TRY(rsx::stage_room(h->st, n * 4, s));
+  RSX_TRY(launch_compensate(h->in0.as<rsx_cfear_surface_point>(), h->in1.as<float>(), h->off0.as<int64_t>(), n_scans, h->init.as<double>(),
+                            h->out.as<rsx_cfear_surface_point>(), h->st.as<int32_t>(), s));
+  RSX_TRY(rsx::stage_down(out_records, h->out, rb, s));
   RSX_TRY(rsx::stage_down(out_status, h->st, n * 4, s));
   RSX_HIP(hipStreamSynchronize(s));
   return RSX_OK;

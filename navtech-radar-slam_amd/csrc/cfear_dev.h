@@ -1,9 +1,11 @@
 // cfear_dev.h -- the device code csrc/cfear.hip (surface points) and csrc/cfear_track.hip (registration) both need: the
-// 128 x 128 grid of cells of one radius, and points / records sorted by cell in LDS.  A key is cell << IDX_BITS | index, all
+// 128 x 128 grid of cells of one radius, points / records sorted by cell in LDS, and the motion compensation of a record.  A key is cell << IDX_BITS | index, all
 // ones for an element outside the grid; sorted keys order the elements by cell and, inside a cell, by index.  Everything is
 // __forceinline__: a kernel keeps the instruction sequence it had with the code written out in place.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "mocomp_dev.h"
 
 namespace rsx {
 namespace cfear {
@@ -41,6 +43,29 @@ __device__ __forceinline__ void fill_cell_table(const unsigned *keys, int n, uns
     if (OUTSIDE && key == NO_KEY) continue;
     if (i == 0 || (keys[i - 1] >> IDX_BITS) != (key >> IDX_BITS)) table[key >> IDX_BITS] = (unsigned short)i;
   }
+}
+
+// Motion compensation of surface-point records (include/rsx.h, rsx_cfear_compensate_batch; tests/cfear_mocomp_np.py): the
+// deskewing of csrc/mocomp.hip with dt_scan = 1 and no Doppler term, on a record's mean and normal.
+struct CompMotion {
+  double vx, vy, wz;
+  int how;  // 0 compensate; 1 copy (the motion is exactly zero); 2 copy and flag (not |yaw| <= 1/2, or not finite)
+};
+
+__device__ __forceinline__ CompMotion comp_motion(double x, double y, double yaw) {
+  CompMotion m;
+  m.how = rsx::mocomp::velocity_of(x, y, yaw, 1.0, m.vx, m.vy, m.wz) ? 0 : 2;
+  if (x == 0.0 && y == 0.0 && yaw == 0.0) m.how = 1;
+  return m;
+}
+
+// q = (x, y, nx, ny) measured at tau (a fraction of the scan period) under m (how == 0)
+__device__ __forceinline__ float4 comp_record(float4 q, float tau_f, const CompMotion &m) {
+  const double x = (double)q.x, y = (double)q.y, nx = (double)q.z, ny = (double)q.w, tau = (double)tau_f;
+  const rsx::mocomp::Poly f = rsx::mocomp::poly(m.wz * tau);
+  const double x0 = (f.cs * x - f.sn * y) + (f.A * m.vx - f.B * m.vy) * tau;
+  const double y0 = (f.sn * x + f.cs * y) + (f.B * m.vx + f.A * m.vy) * tau;
+  return make_float4((float)x0, (float)y0, (float)(f.cs * nx - f.sn * ny), (float)(f.sn * nx + f.cs * ny));
 }
 
 }  // namespace cfear

@@ -30,6 +30,9 @@
 //   scans with no host round trip; the ring (records, poses, sorted keys and records) lives in the sequence's state in HBM, the
 //   header is read at the start and written back at the end, the LDS tables are rebuilt from the sorted keys at the start.  A
 //   workgroup reads back what it wrote to HBM only behind __threadfence_block() + __syncthreads(); no workgroup reads another's.
+//   cfear_track_kernel<true> (rsx_cfear_track_params.compensate, tests/cfear_mocomp_np.py): the scan is compensated for the sensor's
+//   motion into a copy in the state before each of two registrations -- with the motion before it, then with the motion the first
+//   registration found -- and the first keyframe once the first motion is known; joint_register itself knows nothing of it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -93,9 +96,12 @@ struct TrackHeader {
   double P[3], M[3];
   double kf_pose[MAXK][3];
   int32_t kf_n[MAXK];  // records of the slot's keyframe (RSX_CFEAR_MAX_SURFACE_POINTS + 1: more, none stored)
-  int32_t head, n_ring, started, pad;
+  int32_t head, n_ring, started;
+  int32_t first;  // compensation: the ring's only keyframe is the sequence's first scan, still as measured (its times: ST_TAU0)
 };
-constexpr size_t ST_HEADER = 256, ST_ORIG = ST_HEADER, ST_INDEX = ST_ORIG + (size_t)MAXK * CAP * 16, ST_BYTES = ST_INDEX + WS_BYTES;
+// ... then, for compensation: the times of the first scan's records, and the current scan compensated (x, y, nx, ny per record)
+constexpr size_t ST_HEADER = 256, ST_ORIG = ST_HEADER, ST_INDEX = ST_ORIG + (size_t)MAXK * CAP * 16, ST_TAU0 = ST_INDEX + WS_BYTES,
+                 ST_COMP = ST_TAU0 + (size_t)CAP * 4, ST_BYTES = ST_COMP + (size_t)CAP * 16;
 static_assert(sizeof(TrackHeader) <= ST_HEADER, "header room");
 
 __device__ __forceinline__ int cell_coord(double v, double r) {
@@ -437,8 +443,12 @@ __global__ __launch_bounds__(NT) void cfear_joint_kernel(const rsx_cfear_surface
   }
 }
 
-__global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface_point *__restrict__ rec, const int64_t *__restrict__ begin,
-                                                         const int64_t *__restrict__ end, const int32_t *__restrict__ n_scans, RgConsts k,
+// COMP: rsx_cfear_track_params.compensate as a template parameter: without it the kernel is the code it was (everything about compensation sits behind
+// if constexpr), with it a scan is compensated into the state's copy before each of its two registrations
+template <bool COMP>
+__global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface_point *__restrict__ rec, const float *__restrict__ tau,
+                                                         const int64_t *__restrict__ begin, const int64_t *__restrict__ end,
+                                                         const int32_t *__restrict__ n_scans, RgConsts k,
                                                          TrConsts tc, unsigned char *state, rsx_cfear_track_result *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ct_lds[];
   __shared__ double s_red[NW * N_SUMS];
@@ -456,13 +466,15 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
   float4 *orig = reinterpret_cast<float4 *>(st + ST_ORIG);
   float4 *sorted = reinterpret_cast<float4 *>(st + ST_INDEX);
   unsigned *keys = reinterpret_cast<unsigned *>(st + ST_INDEX + WS_SORTED);
+  float *tau0 = reinterpret_cast<float *>(st + ST_TAU0);
+  float4 *cbuf = reinterpret_cast<float4 *>(st + ST_COMP);
   const int NK = tc.n_keyframes;
   double P[3], M[3];
   for (int a = 0; a < 3; a++) {
     P[a] = hdr->P[a];
     M[a] = hdr->M[a];
   }
-  int head = hdr->head, n_ring = hdr->n_ring, started = hdr->started;
+  int head = hdr->head, n_ring = hdr->n_ring, started = hdr->started, first_kf = COMP ? hdr->first : 0;
   if (tc.search == RSX_CFEAR_SEARCH_CELLS && started) {  // the tables of the ring this launch continues with
     for (int c = t; c < MAXK * NCELL; c += NT) tables[c] = NO_CELL;
     __syncthreads();
@@ -480,12 +492,19 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
     r.keyframe = 0;
     r.n_keyframes = 0;
     bool insert = false;
+    const float4 *cur = sp;  // the records the scan is registered with and, as a keyframe, stored as: sp, or its compensated copy
+    int cstride = 2;         // x, y, nx, ny: the first 16 bytes of a 32-byte record
     if (!started) {
       started = 1;
       for (int a = 0; a < 3; a++) P[a] = M[a] = 0.0;
       head = n_ring = 0;
       r.keyframe = 1;
       insert = true;
+      if constexpr (COMP) {  // the first keyframe stays as measured until the first motion is known
+        first_kf = 1;
+        if (ns64 <= CAP)
+          for (int j = t; j < (int)ns64; j += NT) tau0[j] = tau[b + j];
+      }
     } else {
       double start[3] = {P[0], P[1], P[2]};
       if (tc.predict) {
@@ -512,9 +531,59 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
         s_kf[t] = f;
       }
       __syncthreads();
-      joint_register(sp, 2, ns64, n_ring, s_kf, tc.search, ct_lds, s_red, s_fr, k, start[0], start[1], start[2], r.reg);
+      // Compensation (pass = 0, 1 are include/rsx.h's pass 1 and pass 2): pass 0 registers the scan compensated with the motion before it, from `start`.  After a pass 0 that succeeded M
+      // becomes the motion it found and `start` the pose it found, and pass 1 registers the scan compensated with that M from that
+      // `start`: a pass 1 that fails then leaves exactly them behind, by the failure rule below.  Without compensation there is pass 0
+      // alone, on sp
+      const bool comp = COMP && ns64 >= 1 && ns64 <= CAP;  // (otherwise pass 0 ends with status 1 or 2 and reads no record)
+      int pass = 0, it0 = 0;
+      bool ok;
+      for (;; pass++) {
+        if (COMP && comp) {
+          const CompMotion m = comp_motion(M[0], M[1], M[2]);
+          for (int j = t; j < (int)ns64; j += NT) {
+            const float4 q = sp[2 * (size_t)j];
+            cbuf[j] = m.how == 0 ? comp_record(q, tau[b + j], m) : q;
+          }
+          __threadfence_block();  // the workgroup reads the copy
+          __syncthreads();
+          cur = cbuf;
+          cstride = 1;
+        }
+        joint_register(cur, cstride, ns64, n_ring, s_kf, tc.search, ct_lds, s_red, s_fr, k, start[0], start[1], start[2], r.reg);
+        ok = r.reg.status == 0 || r.reg.status == 8;
+        if (!COMP || !ok || pass == 1) break;  // (uniform)
+        it0 = r.reg.iterations;
+        {
+          double sn, cs;
+          sincos(P[2], &sn, &cs);
+          const double dx = r.reg.x - P[0], dy = r.reg.y - P[1];
+          M[0] = cs * dx + sn * dy;
+          M[1] = cs * dy - sn * dx;
+          M[2] = r.reg.yaw - P[2];
+          start[0] = r.reg.x;
+          start[1] = r.reg.y;
+          start[2] = r.reg.yaw;
+        }
+        if (first_kf) {  // the ring's only keyframe is the first scan as measured: compensated now, at its pose, and binned again
+          const int slot = s_kf[0].slot, cnt = s_kf[0].n;
+          if (cnt >= 1 && cnt <= CAP) {
+            const CompMotion m = comp_motion(M[0], M[1], M[2]);
+            if (m.how == 0)
+              for (int j = t; j < cnt; j += NT) orig[(size_t)slot * CAP + j] = comp_record(orig[(size_t)slot * CAP + j], tau0[j], m);
+            __threadfence_block();
+            __syncthreads();
+            if (tc.search == RSX_CFEAR_SEARCH_CELLS)
+              build_index(orig + (size_t)slot * CAP, 1, cnt, keys + (size_t)slot * CAP, sorted + (size_t)slot * CAP,
+                          tables + (size_t)slot * NCELL, sortbuf, k.r, t);
+          }
+          first_kf = 0;
+        }
+      }
+      first_kf = 0;
       r.n_keyframes = n_ring;
-      if (r.reg.status == 0 || r.reg.status == 8) {
+      if (pass == 1) r.reg.reserved = it0;
+      if (ok) {
         double sn, cs;
         sincos(P[2], &sn, &cs);
         const double dx = r.reg.x - P[0], dy = r.reg.y - P[1];
@@ -555,7 +624,7 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
         hdr->kf_n[slot] = cnt;
       }
       if (cnt <= CAP)
-        for (int j = t; j < cnt; j += NT) orig[(size_t)slot * CAP + j] = sp[2 * (size_t)j];
+        for (int j = t; j < cnt; j += NT) orig[(size_t)slot * CAP + j] = cur[(size_t)cstride * j];
       __threadfence_block();  // the workgroup reads the header and the records again
       __syncthreads();
       if (tc.search == RSX_CFEAR_SEARCH_CELLS && cnt >= 1 && cnt <= CAP)
@@ -577,7 +646,7 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
     hdr->head = head;
     hdr->n_ring = n_ring;
     hdr->started = started;
-    hdr->pad = 0;
+    hdr->first = first_kf;  // (without COMP: 0, the pad it was)
   }
 }
 
@@ -604,7 +673,8 @@ int rsx::cfear::check_track_params(const rsx_cfear_track_params &p) {
   if (!(p.keyframe_rotation >= 0.0) || !std::isfinite(p.keyframe_rotation)) return fail(RSX_ERR_BAD_ARG, "keyframe_rotation must not be negative");
   if (p.predict != 0 && p.predict != 1) return fail(RSX_ERR_BAD_ARG, "predict %d is neither 0 nor 1", p.predict);
   if (p.search != RSX_CFEAR_SEARCH_CELLS && p.search != RSX_CFEAR_SEARCH_BRUTE) return fail(RSX_ERR_BAD_ARG, "search %d is neither 0 nor 1", p.search);
-  if (p.reserved[0] || p.reserved[1] || p.reserved[2]) return fail(RSX_ERR_BAD_ARG, "reserved words of rsx_cfear_track_params must be 0");
+  if (p.reserved[0] || p.reserved[1]) return fail(RSX_ERR_BAD_ARG, "reserved words of rsx_cfear_track_params must be 0");
+  if (p.compensate != 0 && p.compensate != 1) return fail(RSX_ERR_BAD_ARG, "compensate %d is neither 0 nor 1", p.compensate);
   return RSX_OK;
 }
 
@@ -636,18 +706,21 @@ int rsx::cfear::launch_register(const rsx_cfear_surface_point *d_src, const int6
                                    d_out, s);
 }
 
-int rsx::cfear::launch_track(const rsx_cfear_surface_point *d_records, const int64_t *d_begin, const int64_t *d_end, const int32_t *d_n_scans,
+int rsx::cfear::launch_track(const rsx_cfear_surface_point *d_records, const float *d_tau, const int64_t *d_begin, const int64_t *d_end,
+                             const int32_t *d_n_scans,
                              int32_t n_sequences, const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_state,
                              rsx_cfear_track_result *d_out, hipStream_t s) {
   if (n_sequences < 1) return fail(RSX_ERR_BAD_ARG, "n_sequences %d below 1", n_sequences);
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfear_track_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+  if (tp.compensate && !d_tau) return fail(RSX_ERR_BAD_ARG, "compensate = 1 needs the records' times");
+  auto kernel = tp.compensate ? &cfear_track_kernel<true> : &cfear_track_kernel<false>;
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
   TrConsts tc;
   tc.keyframe_distance = tp.keyframe_distance;
   tc.keyframe_rotation = tp.keyframe_rotation;
   tc.n_keyframes = tp.n_keyframes;
   tc.predict = tp.predict;
   tc.search = tp.search;
-  hipLaunchKernelGGL(cfear_track_kernel, dim3((unsigned)n_sequences), dim3(NT), LDS_BYTES, s, d_records, d_begin, d_end, d_n_scans, rg_consts(p), tc,
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_sequences), dim3(NT), LDS_BYTES, s, d_records, d_tau, d_begin, d_end, d_n_scans, rg_consts(p), tc,
                      static_cast<unsigned char *>(d_state), d_out);
   RSX_HIP(hipGetLastError());
   return RSX_OK;
@@ -660,7 +733,7 @@ struct rsx_cfear_tracker {
   rsx::Stream stream;
   rsx::StreamOrder order;  // the state and the staging buffers are shared by every call
   rsx::DevBuf state;       // [n_sequences][track_state_bytes()]
-  rsx::DevBuf in, off, nsc, out;  // staging of the host-buffer entry
+  rsx::DevBuf in, in_tau, off, nsc, out;  // staging of the host-buffer entries
   bool have_params = false;  // since create / reset
   rsx_cfear_params prm{};
   rsx_cfear_track_params tprm{};
@@ -728,6 +801,62 @@ int same_params(rsx_cfear_tracker *h, const rsx_cfear_params &dp, const rsx_cfea
   return RSX_OK;
 }
 
+// the untimed entries pass tau = null and refuse compensation: they have no times to compensate with
+int untimed_ok(const float *tau, const rsx_cfear_track_params &dt) {
+  if (!tau && dt.compensate) return fail(RSX_ERR_BAD_ARG, "compensate = 1 needs the records' times (rsx_cfear_tracker_push_timed)");
+  return RSX_OK;
+}
+
+int push_device(rsx_cfear_tracker *h, const rsx_cfear_surface_point *d_records, const float *d_tau, const int64_t *d_offsets,
+                const int32_t *d_n_scans, const rsx_cfear_params *params, const rsx_cfear_track_params *track, rsx_cfear_track_result *d_out,
+                void *stream) {
+  if (!h || !d_records || !d_offsets || !d_n_scans || !d_out) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  rsx_cfear_params dp;
+  rsx_cfear_track_params dt;
+  RSX_TRY(rsx::cfear::resolve(params, track, dp, &dt));
+  RSX_TRY(untimed_ok(d_tau, dt));
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_TRY(same_params(h, dp, dt));
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
+  return rsx::cfear::launch_track(d_records, d_tau, d_offsets, d_offsets + 1, d_n_scans, h->n_sequences, dp, dt, h->state.p, d_out, s);
+}
+
+int push_host(rsx_cfear_tracker *h, const rsx_cfear_surface_point *records, const float *tau, const int64_t *offsets, const int32_t *n_scans,
+              const rsx_cfear_params *params, const rsx_cfear_track_params *track, rsx_cfear_track_result *out, const char *what) {
+  if (!h || !records || !offsets || !n_scans || !out) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  rsx_cfear_params dp;
+  rsx_cfear_track_params dt;
+  RSX_TRY(rsx::cfear::resolve(params, track, dp, &dt));
+  RSX_TRY(untimed_ok(tau, dt));
+  int64_t total = 0;
+  for (int32_t q = 0; q < h->n_sequences; q++) {
+    if (n_scans[q] < 0) return fail(RSX_ERR_BAD_ARG, "n_scans[%d] = %d is negative", q, n_scans[q]);
+    total += n_scans[q];
+  }
+  if (total > INT32_MAX) return fail(RSX_ERR_BAD_ARG, "too many scans");
+  if (total > 0) RSX_TRY(rsx::check_offsets(offsets, (int32_t)total, what));
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_TRY(same_params(h, dp, dt));
+  if (total == 0) return RSX_OK;
+  const size_t n = (size_t)total, m = (size_t)offsets[total];
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(rsx::stage_up(h->in, records, m * sizeof(rsx_cfear_surface_point), s));
+  if (tau) RSX_TRY(rsx::stage_up(h->in_tau, tau, m * 4, s));
+  RSX_TRY(rsx::stage_up(h->off, offsets, (n + 1) * 8, s));
+  RSX_TRY(rsx::stage_up(h->nsc, n_scans, (size_t)h->n_sequences * 4, s));
+  RSX_TRY(rsx::stage_room(h->out, n * sizeof(rsx_cfear_track_result), s));
+  RSX_TRY(rsx::cfear::launch_track(h->in.as<rsx_cfear_surface_point>(), tau ? h->in_tau.as<float>() : nullptr, h->off.as<int64_t>(),
+                                   h->off.as<int64_t>() + 1, h->nsc.as<int32_t>(), h->n_sequences, dp, dt, h->state.p,
+                                   h->out.as<rsx_cfear_track_result>(), s));
+  RSX_TRY(rsx::stage_down(out, h->out, n * sizeof(rsx_cfear_track_result), s));
+  RSX_HIP(hipStreamSynchronize(s));
+  return RSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -739,7 +868,8 @@ int rsx_cfear_default_track_params(rsx_cfear_track_params *p) try {
   p->n_keyframes = 3;
   p->predict = 1;
   p->search = RSX_CFEAR_SEARCH_CELLS;
-  p->reserved[0] = p->reserved[1] = p->reserved[2] = 0;
+  p->reserved[0] = p->reserved[1] = 0;
+  p->compensate = 0;
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -847,47 +977,26 @@ int rsx_cfear_tracker_reset(rsx_cfear_tracker *h) try {
 int rsx_cfear_tracker_push_device(rsx_cfear_tracker *h, const rsx_cfear_surface_point *d_records, const int64_t *d_offsets,
                                   const int32_t *d_n_scans, const rsx_cfear_params *params, const rsx_cfear_track_params *track,
                                   rsx_cfear_track_result *d_out, void *stream) try {
-  if (!h || !d_records || !d_offsets || !d_n_scans || !d_out) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  rsx_cfear_params dp;
-  rsx_cfear_track_params dt;
-  RSX_TRY(resolve(params, track, dp, &dt));
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(same_params(h, dp, dt));
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  RSX_TRY(h->order.enter(s));
-  return rsx::cfear::launch_track(d_records, d_offsets, d_offsets + 1, d_n_scans, h->n_sequences, dp, dt, h->state.p, d_out, s);
+  return push_device(h, d_records, nullptr, d_offsets, d_n_scans, params, track, d_out, stream);
 } RSX_CATCH_ALL
 
 int rsx_cfear_tracker_push(rsx_cfear_tracker *h, const rsx_cfear_surface_point *records, const int64_t *offsets, const int32_t *n_scans,
                            const rsx_cfear_params *params, const rsx_cfear_track_params *track, rsx_cfear_track_result *out) try {
-  if (!h || !records || !offsets || !n_scans || !out) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  rsx_cfear_params dp;
-  rsx_cfear_track_params dt;
-  RSX_TRY(resolve(params, track, dp, &dt));
-  int64_t total = 0;
-  for (int32_t q = 0; q < h->n_sequences; q++) {
-    if (n_scans[q] < 0) return fail(RSX_ERR_BAD_ARG, "n_scans[%d] = %d is negative", q, n_scans[q]);
-    total += n_scans[q];
-  }
-  if (total > INT32_MAX) return fail(RSX_ERR_BAD_ARG, "too many scans");
-  if (total > 0) RSX_TRY(rsx::check_offsets(offsets, (int32_t)total, "rsx_cfear_tracker_push"));
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(same_params(h, dp, dt));
-  if (total == 0) return RSX_OK;
-  const size_t n = (size_t)total, m = (size_t)offsets[total];
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  RSX_TRY(h->order.enter(s));
-  RSX_TRY(rsx::stage_up(h->in, records, m * sizeof(rsx_cfear_surface_point), s));
-  RSX_TRY(rsx::stage_up(h->off, offsets, (n + 1) * 8, s));
-  RSX_TRY(rsx::stage_up(h->nsc, n_scans, (size_t)h->n_sequences * 4, s));
-  RSX_TRY(rsx::stage_room(h->out, n * sizeof(rsx_cfear_track_result), s));
-  RSX_TRY(rsx::cfear::launch_track(h->in.as<rsx_cfear_surface_point>(), h->off.as<int64_t>(), h->off.as<int64_t>() + 1, h->nsc.as<int32_t>(),
-                                   h->n_sequences, dp, dt, h->state.p, h->out.as<rsx_cfear_track_result>(), s));
-  RSX_TRY(rsx::stage_down(out, h->out, n * sizeof(rsx_cfear_track_result), s));
-  RSX_HIP(hipStreamSynchronize(s));
-  return RSX_OK;
+  return push_host(h, records, nullptr, offsets, n_scans, params, track, out, "rsx_cfear_tracker_push");
+} RSX_CATCH_ALL
+
+int rsx_cfear_tracker_push_timed_device(rsx_cfear_tracker *h, const rsx_cfear_surface_point *d_records, const float *d_tau,
+                                        const int64_t *d_offsets, const int32_t *d_n_scans, const rsx_cfear_params *params,
+                                        const rsx_cfear_track_params *track, rsx_cfear_track_result *d_out, void *stream) try {
+  if (!d_tau) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  return push_device(h, d_records, d_tau, d_offsets, d_n_scans, params, track, d_out, stream);
+} RSX_CATCH_ALL
+
+int rsx_cfear_tracker_push_timed(rsx_cfear_tracker *h, const rsx_cfear_surface_point *records, const float *tau, const int64_t *offsets,
+                                 const int32_t *n_scans, const rsx_cfear_params *params, const rsx_cfear_track_params *track,
+                                 rsx_cfear_track_result *out) try {
+  if (!tau) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  return push_host(h, records, tau, offsets, n_scans, params, track, out, "rsx_cfear_tracker_push_timed");
 } RSX_CATCH_ALL
 
 }  // extern "C"

@@ -264,6 +264,7 @@ constexpr int N_SETS = 3, N_LANES = 2;
 struct OdoSet {
   rsx::DevBuf az, targets, xy, counts, desc, valid;  // slot 0 = the previous scan, slots 1 .. MAX_WINDOW = the window (whichever extractor wrote them)
   rsx::DevBuf sp, sp_counts, pt_begin, pt_end;  // CFEAR only: surface points [slot][RSX_CFEAR_MAX_SURFACE_POINTS], their counts, the point ranges
+  rsx::DevBuf sp_tau;  // CFEAR tracking with compensation only: the records' times, laid out like sp
   rsx::PinnedBuf pin;  // pinned: counts[MAX_WINDOW + 1], pair_cnt[MAX_WINDOW], results[MAX_WINDOW], then the staged azimuth grids
 };
 
@@ -325,6 +326,7 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
       RSX_TRY(q.sp_counts.reserve(S * 4, s, true));
       RSX_TRY(q.pt_begin.reserve((size_t)MAX_WINDOW * 8, s, false));
       RSX_TRY(q.pt_end.reserve((size_t)MAX_WINDOW * 8, s, false));
+      if (h->track_on && h->track_prm.compensate) RSX_TRY(q.sp_tau.reserve(S * RSX_CFEAR_MAX_SURFACE_POINTS * 4, s, false));
     }
   }
   RSX_TRY(h->fwd.reserve((size_t)MAX_WINDOW * K * 4, s, false));
@@ -392,8 +394,13 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
     hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 63) / 64), dim3(64), 0, s, d_counts + 1, n, (int64_t)K, 1, q.pt_begin.as<int64_t>(),
                        q.pt_end.as<int64_t>());
     RSX_HIP(hipGetLastError());
-    RSX_TRY(rsx::cfear::launch_surface(q.xy.as<float>() + slot_xy, q.pt_begin.as<int64_t>(), q.pt_end.as<int64_t>(), n, h->cfear_prm,
-                                       q.sp.as<rsx_cfear_surface_point>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
+    if (h->track_on && h->track_prm.compensate)  // with the records' times: a keypoint's azimuth row is the first word of its target
+      RSX_TRY(rsx::cfear::launch_surface_timed(q.xy.as<float>() + slot_xy, q.targets.as<int32_t>() + slot_xy, 2, h->rows, q.pt_begin.as<int64_t>(),
+                                               q.pt_end.as<int64_t>(), n, h->cfear_prm, q.sp.as<rsx_cfear_surface_point>() + SP,
+                                               q.sp_tau.as<float>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
+    else
+      RSX_TRY(rsx::cfear::launch_surface(q.xy.as<float>() + slot_xy, q.pt_begin.as<int64_t>(), q.pt_end.as<int64_t>(), n, h->cfear_prm,
+                                         q.sp.as<rsx_cfear_surface_point>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
   } else {
     // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
     // how the sequence is cut into windows, and nothing about the grids is looked at on the host
@@ -440,7 +447,7 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
                        (int64_t)RSX_CFEAR_MAX_SURFACE_POINTS, 0, b, e);
     RSX_HIP(hipGetLastError());
     RSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->track_n.p), n, 1, s));
-    RSX_TRY(rsx::cfear::launch_track(q.sp.as<rsx_cfear_surface_point>(), b + 1, e + 1, h->track_n.as<int32_t>(), 1, h->cfear_prm, h->track_prm,
+    RSX_TRY(rsx::cfear::launch_track(q.sp.as<rsx_cfear_surface_point>(), h->track_prm.compensate ? q.sp_tau.as<float>() : nullptr, b + 1, e + 1, h->track_n.as<int32_t>(), 1, h->cfear_prm, h->track_prm,
                                      h->track_state.p, h->track_res.as<rsx_cfear_track_result>(), s));
     hipLaunchKernelGGL(odo_cfear_track_results, dim3(1), dim3(64), 0, s, h->track_res.as<rsx_cfear_track_result>(), n, first,
                        h->track_prev.as<double>(), h->results.as<rsx_orora_result>(), h->pair_cnt.as<int32_t>());
@@ -789,6 +796,7 @@ int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_param
   }
   if (h->estimator != RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is not selected (rsx_odometry_set_cfear first)");
   RSX_TRY(rsx::cfear::check_track_params(*params));
+  if (params->compensate && h->rows > 65536) return fail(RSX_ERR_BAD_ARG, "compensate = 1 takes images of at most 65536 rows");
   h->track_prm = *params;
   h->track_on = true;
   return RSX_OK;

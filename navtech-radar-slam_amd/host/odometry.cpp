@@ -34,7 +34,9 @@
 // `--cfear-keyframes S` (with `--cfear-keyframe-distance M`, `--cfear-keyframe-rotation DEG`, `--cfear-no-prediction`; any of them
 // switches it on, S = 3 by default) runs CFEAR's keyframe tracker instead of consecutive pairs: every scan is registered jointly
 // against the last S keyframes from a constant-velocity prediction, and becomes a keyframe after M metres or DEG degrees
-// (rsx_odometry_set_cfear_tracking; only with `--estimator cfear`).
+// (rsx_odometry_set_cfear_tracking; only with `--estimator cfear`).  `--cfear-compensate` (it switches the tracker on as well)
+// compensates the sensor's motion during a revolution inside the tracker: surface points with times, every scan registered
+// twice (rsx_cfear_track_params.compensate); the published cloud stays as measured.
 // `--compensate motion|doppler|both` (with `--doppler-beta`, `--scan-period`) corrects the keypoints for the sensor's motion
 // during the scan and / or the Doppler range shift: every pair is estimated, its matches compensated with that estimate and
 // estimated again, and the published cloud is the compensated one (upstream's deskewing / Doppler switches:
@@ -191,6 +193,7 @@ int main(int argc, char **argv) {
       else if (a == "--cfear-keyframes" && i + 1 < argc) { ctp.n_keyframes = std::atoi(argv[++i]); cfear_track = true; }  // cfear: track against the last S keyframes (off: consecutive pairs)
       else if (a == "--cfear-keyframe-distance" && i + 1 < argc) { ctp.keyframe_distance = std::atof(argv[++i]); cfear_track = true; }  // cfear tracking: a new keyframe after this many metres (1.5)
       else if (a == "--cfear-keyframe-rotation" && i + 1 < argc) { ctp.keyframe_rotation = std::atof(argv[++i]) * 3.14159265358979323846 / 180.0; cfear_track = true; }  // ... or degrees (5)
+      else if (a == "--cfear-compensate") { ctp.compensate = 1; cfear_track = true; }  // cfear tracking: motion compensation of the surface points inside the tracker
       else if (a == "--cfear-no-prediction") { ctp.predict = 0; cfear_track = true; }  // cfear tracking: start from the previous pose, not the constant-velocity prediction
       else if (a == "--ransac-threshold" && i + 1 < argc) rsp.tolerance = std::atof(argv[++i]);        // inlier residual bound [m] (0.35)
       else if (a == "--ransac-iterations" && i + 1 < argc) rsp.max_iterations = std::atoi(argv[++i]);  // hypotheses (100)
@@ -215,7 +218,7 @@ int main(int argc, char **argv) {
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--window W] [--threads T] "
-          "[--estimator orora|ransac|mcransac|cfear] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
+          "[--estimator orora|ransac|mcransac|cfear] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--cfear-compensate] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
           "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";
@@ -311,7 +314,7 @@ int main(int argc, char **argv) {
     const bool use_c18 = keypoints == "cen2018", use_ks = keypoints == "kstrongest";
     if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac" && estimator != "cfear") die("--estimator must be orora, ransac, mcransac or cfear");
     if (estimator != "orora" && (matcher != "orb" || per_scan)) die("--estimator " + estimator + " runs on the windowed path only (not with --per-scan / --matcher nn)");
-    if (cfear_track && estimator != "cfear") die("--cfear-keyframes, --cfear-keyframe-distance, --cfear-keyframe-rotation and --cfear-no-prediction need --estimator cfear");
+    if (cfear_track && estimator != "cfear") die("--cfear-keyframes, --cfear-keyframe-distance, --cfear-keyframe-rotation, --cfear-no-prediction and --cfear-compensate need --estimator cfear");
     if (!compensate.empty()) {
       if (compensate != "motion" && compensate != "doppler" && compensate != "both") die("--compensate must be motion, doppler or both");
       if (matcher != "orb" || per_scan) die("--compensate runs on the windowed path only (not with --per-scan / --matcher nn)");

@@ -25,14 +25,17 @@ class Odometry:
     registration in place of descriptors, matcher and estimator (rsx_odometry_set_cfear; pair it with keypoints="kstrongest",
     min_separation = 0; not with compensate).  cfear_track: True (the defaults) or a CfearTrackParams: CFEAR's keyframe tracker --
     joint registration against the last keyframes from a constant-velocity prediction -- in place of the registration of
-    consecutive pairs (rsx_odometry_set_cfear_tracking; only with estimator="cfear").
+    consecutive pairs (rsx_odometry_set_cfear_tracking; only with estimator="cfear").  cfear_compensate: True switches on the
+    tracker's motion compensation (CfearTrackParams.compensate = 1: surface points with times, every scan registered twice; the
+    published cloud stays as measured); it implies cfear_track.
     exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT).
     compensate: None (default), "motion", "doppler" or "both": every pair is estimated, its matches compensated with that
     estimate, and estimated again (rsx_odometry_set_compensation; not with "mcransac"); beta, dt_scan: the Doppler factor and
     the scan period of the model (None: the library's defaults)."""
 
     def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
-                 exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None, cfear=None, cfear_track=None):
+                 exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None, cfear=None, cfear_track=None,
+                 cfear_compensate=False):
         if keypoints not in ("cen2019", "cen2018", "kstrongest"):
             raise ValueError("keypoints must be cen2019, cen2018 or kstrongest")
         if estimator not in ESTIMATORS and estimator != "cfear":
@@ -53,8 +56,18 @@ class Odometry:
             self.set_cen2018(cen2018)
         if keypoints == "kstrongest":
             self.set_kstrongest(kstrongest)
+        if cfear_compensate and estimator != "cfear":
+            raise ValueError("cfear_compensate needs estimator=\"cfear\"")
         if estimator == "cfear":
             self.set_cfear(cfear)
+            if cfear_compensate:
+                track = CfearTrackParams()
+                if cfear_track is None or cfear_track is True or cfear_track is False:
+                    check(self._L.rsx_cfear_default_track_params(C.byref(track)))
+                else:
+                    C.memmove(C.byref(track), C.byref(cfear_track), C.sizeof(track))
+                track.compensate = 1
+                cfear_track = track
             if cfear_track is not None and cfear_track is not False:
                 self.set_cfear_tracking(None if cfear_track is True else cfear_track)
         elif estimator != "orora":

@@ -13,6 +13,9 @@ of the synthetic drive synth.polar_sequence(11, n), MulRan shape (400 x 3360).  
   (d) the windowed odometry (rsx_odometry_push, host images) with k-strongest + CFEAR, tracking on and off
   (e) accuracy against the true poses: consecutive pairs from the identity, 3 keyframes started at the previous pose, 3 keyframes
       started at the constant-velocity prediction
+  (f) the timed tracker (rsx_cfear_tracker_push_timed_device, the records' times from rsx_cfear_surface_points_timed_batch) with
+      compensate = 0 and compensate = 1, alternating with the untimed tracker of (c), one sequence and 16; and the odometry of (d)
+      with compensation on.  The synthetic images are not distorted by the motion, so (f) measures cost, not accuracy
 Prints microseconds per call and scans/s; every timed window ends in a device synchronise.
 
 usage: bench_cfear_track.py [n_scans=256] [reps=5] [odometry_reps=3]"""
@@ -40,10 +43,13 @@ imgs, az, poses, _ = synth.polar_sequence(11, n_scans)
 print(f"{n_scans} consecutive scans generated in {time.perf_counter() - t0:.0f} s", flush=True)
 ks = kstrongest.KStrongest(400, 3360)
 h = cfear.Cfear()
-records = []
+records, taus = [], []
 for b in range(0, n_scans, batch):
-    _, xy = ks.extract_batch(imgs[b:b + batch], min_separation=0, azimuths=az if np.ndim(az) == 1 else az[b:b + batch])
+    tg, xy = ks.extract_batch(imgs[b:b + batch], min_separation=0, azimuths=az if np.ndim(az) == 1 else az[b:b + batch])
     records += h.surface_points(xy)[0]
+    timed_rec, tau, _, _ = h.surface_points_timed(xy, [np.ascontiguousarray(t[:, 0]) for t in tg], 400)
+    assert all(a.tobytes() == b_.tobytes() for a, b_ in zip(timed_rec, records[b:]))
+    taus += tau
 print(f"surface points: {np.mean([len(r) for r in records]):.0f} per scan (min {min(len(r) for r in records)}, max {max(len(r) for r in records)})", flush=True)
 stream = torch.cuda.current_stream().cuda_stream
 nb = n_scans // batch
@@ -95,6 +101,52 @@ for s in (0, 1):
 assert track_out[0].tobytes() == track_out[1].tobytes()
 tracked = track_out[0]
 pose = [(float(r["x"]), float(r["y"]), float(r["yaw"])) for r in tracked]
+
+
+
+# ---- (f) the timed tracker, compensation off and on, against the untimed one: alternating ----
+def make_leg(n_seq, tp, timed_push):
+    t = cfear.Tracker(n_seq, track=tp)
+    rec, off = cfear.ragged(records * n_seq, SP)
+    d = [dev(rec), dev(off), dev(np.full(n_seq, n_scans, dtype=np.int32)), dev(np.concatenate(taus * n_seq))]
+    d_out = torch.zeros(n_seq * n_scans * 80, dtype=torch.uint8, device="cuda")
+
+    def run():
+        t.reset(track=tp)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if timed_push:
+            t.push_timed_device(d[0].data_ptr(), d[3].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d_out.data_ptr(), stream=stream)
+        else:
+            t.push_device(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d_out.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    return run, d_out, t
+
+
+for n_seq in (1, 16):
+    legs = {"untimed push": make_leg(n_seq, cfear.track_params(), False), "timed push, compensate 0": make_leg(n_seq, cfear.track_params(), True),
+            "timed push, compensate 1": make_leg(n_seq, cfear.track_params(compensate=1), True)}
+    for run, _, _ in legs.values():
+        run()  # warm-up
+    ts = {k: [] for k in legs}
+    for r in range(reps):
+        for k, (run, _, _) in legs.items():  # alternating
+            ts[k].append(run())
+    base = float(np.median(ts["untimed push"]))
+    res = {k: v[1].cpu().numpy().view(_rsx.CFEAR_TRACK_RESULT_DTYPE).reshape(n_seq, n_scans)[0] for k, v in legs.items()}
+    assert res["timed push, compensate 0"].tobytes() == res["untimed push"].tobytes() == tracked.tobytes()
+    for k, v in ts.items():
+        m = float(np.median(v))
+        print(f"(f) tracker, {k}, {n_seq} sequence(s) of {n_scans} scans: {m * 1e3:.1f} ms (fastest {min(v) * 1e3:.1f}, slowest {max(v) * 1e3:.1f}; "
+              f"median of {reps}) = {m / n_scans * 1e6:.0f} us per scan of a sequence, {m / base:.2f} x the untimed push", flush=True)
+    o = res["timed push, compensate 1"]
+    print(f"    compensate 1: iterations mean {o['reg']['reserved'][1:].mean():.1f} (pass 1) + {o['reg']['iterations'][1:].mean():.1f} (pass 2) against "
+          f"{tracked['reg']['iterations'][1:].mean():.1f} without; status != 0: {int(np.sum(o['reg']['status'][1:] != 0))}, keyframes "
+          f"{int(np.sum(o['keyframe'] == 1))}, re-anchored {int(np.sum(o['keyframe'] == 2))}", flush=True)
+    for _, _, t in legs.values():
+        t.close()
 
 # ---- (a) and (b): batches of 64 jobs ----
 pairs = [(records[(i + 1) % n_scans], records[i]) for i in range(n_scans)]  # (the last pair wraps round: far apart, status 4 at once)
@@ -197,7 +249,8 @@ for name, tp in (("3 keyframes, start at the previous pose", cfear.track_params(
 
 # ---- (d) the odometry ----
 kw = dict(keypoints="kstrongest", kstrongest=kstrongest.params(min_separation=0), estimator="cfear")
-ods = {"tracking off (pairs)": odometry.Odometry(400, 3360, **kw), "tracking on": odometry.Odometry(400, 3360, cfear_track=True, **kw)} if odo_reps > 0 else {}
+ods = {"tracking off (pairs)": odometry.Odometry(400, 3360, **kw), "tracking on": odometry.Odometry(400, 3360, cfear_track=True, **kw),
+       "tracking on, compensation on": odometry.Odometry(400, 3360, cfear_track=True, cfear_compensate=True, **kw)} if odo_reps > 0 else {}
 out, best = {}, {}
 for k, od in ods.items():
     out[k] = od.push(imgs, az)  # warm-up: workspaces
