@@ -671,9 +671,36 @@ int rsx_kstrongest_extract_batch_device(rsx_kstrongest *h, const uint8_t *d_imgs
  * cos_max_normal_angle (lowest j on a tie; none is allowed); residual e = n_j.(q - mu_j), Huber weight 1 for |e| <=
  * huber_delta else huber_delta / |e|; the 3 x 3 normal equations are solved by LDL^T without pivoting in the order (x, y,
  * yaw); the loop ends when the step's norm is < step_epsilon, or at max_iterations.  A pair's result does not depend on its
- * place in the batch; no host round trip inside the loop. */
+ * place in the batch; no host round trip inside the loop.
+ * The objective: that is CFEAR's point-to-line cost with the Huber loss and no weights, the default.  rsx_cfear_params.cost, loss
+ * and weights choose among the family CFEAR publishes, in every entry that takes the struct (pairs, keyframes, the tracker pushes,
+ * rsx_odometry_set_cfear); the rules are restated in tests/cfear_cost_np.py (the arithmetic contract; parity unpinned).  The
+ * correspondence rule stays as above.  For a correspondence (src record i, dst record j of a keyframe k; a pair is one keyframe at
+ * the identity): d = q - mu_j, m = the src normal in the keyframe's frame, t_j = (-n_jy, n_jx), p' = R'(yaw_r) mu_i (the derivative
+ * of R(yaw_r) mu_i in yaw_r).  A residual row along a direction u with scale s has e = s (u.d) and J = (s R(yaw_k) u, s (u.p')).
+ *   cost    RSX_CFEAR_COST_P2L: one row (n_j, 1).  RSX_CFEAR_COST_P2P: two rows, (n_j, 1) then (t_j, 1): the whole of d.
+ *           RSX_CFEAR_COST_P2D: two rows, (n_j, 1 / sqrt(lambda_min_j)) then (t_j, 1 / sqrt(lambda_max_j)): the Mahalanobis distance of
+ *           q under the dst record's distribution.  A record is VALID when lambda_min > 0, lambda_max >= lambda_min and both are
+ *           finite; under P2D a correspondence whose dst record is not valid is skipped and not counted
+ *   loss    on s2 = the sum of the rows' e^2, a = sqrt(s2) (one row: |e|), delta = huber_delta -- under P2D a dimensionless threshold
+ *           on the Mahalanobis distance, not metres.  RSX_CFEAR_LOSS_HUBER: w = 1 if a <= delta else delta / a, rho = s2 / 2 inside,
+ *           delta (a - delta / 2) outside.  RSX_CFEAR_LOSS_CAUCHY: w = 1 / (1 + s2 / delta^2), rho = (delta^2 / 2) log(1 + s2 / delta^2).
+ *           RSX_CFEAR_LOSS_NONE: w = 1, rho = s2 / 2
+ *   weights 0: v = 1.  1: v = w_dir w_plan w_num, how well the two surface points resemble each other: w_dir = max(m.n_j, 0); w_plan =
+ *           2 min(p_i, p_j) / (p_i + p_j) with p = log(1 + lambda_max / lambda_min) of a record; w_num = 2 min(N_i, N_j) / (N_i + N_j)
+ *           with N = n_points.  With weights a correspondence whose src or dst record is not valid is skipped and not counted
+ * H += v w J J^T and g += v w J e over the rows (n first, then t), cost += v rho, correspondences += 1.  The solve, the pivot and step
+ * tests and the statuses are the same for every objective.  A wall whose records share one normal is status 5 under P2L (nothing
+ * constrains motion along it) and registers under P2P and P2D. */
 
 typedef struct rsx_cfear rsx_cfear;
+
+#define RSX_CFEAR_COST_P2L 0    /* rsx_cfear_params.cost: point-to-line */
+#define RSX_CFEAR_COST_P2P 1    /* point-to-point */
+#define RSX_CFEAR_COST_P2D 2    /* point-to-distribution */
+#define RSX_CFEAR_LOSS_HUBER 0  /* rsx_cfear_params.loss */
+#define RSX_CFEAR_LOSS_CAUCHY 1
+#define RSX_CFEAR_LOSS_NONE 2   /* least squares */
 
 #define RSX_CFEAR_MAX_POINTS 16384        /* points of one scan */
 #define RSX_CFEAR_MAX_SURFACE_POINTS 4096 /* records written per scan, and records of one side of a registered pair */
@@ -685,12 +712,14 @@ typedef struct {
   double radius;               /* r: cell side, neighbourhood radius and correspondence radius [m], > 0 (3.5) */
   double max_condition;        /* lambda_max / lambda_min at most, >= 1 (1e5) */
   double cos_max_normal_angle; /* correspondences need m.n_j >= this, in [-1, 1] (cos 30 deg) */
-  double huber_delta;          /* [m], > 0 (0.1) */
+  double huber_delta;          /* delta of the loss, Huber's or Cauchy's, > 0 (0.1): [m], under RSX_CFEAR_COST_P2D dimensionless */
   double step_epsilon;         /* the loop ends when |step| < this, >= 0 (1e-6) */
   int32_t min_points;          /* neighbours a surface point needs, >= 2 (6) */
   int32_t max_iterations;      /* 1 .. 200 (50) */
   int32_t min_correspondences; /* >= 1 (6) */
-  int32_t reserved[3];         /* 0 */
+  int32_t cost;                /* RSX_CFEAR_COST_* (RSX_CFEAR_COST_P2L) */
+  int32_t loss;                /* RSX_CFEAR_LOSS_* (RSX_CFEAR_LOSS_HUBER) */
+  int32_t weights;             /* 1: weigh every correspondence by the resemblance of its surface points; 0: no (0) */
 } rsx_cfear_params;
 
 typedef struct {
@@ -703,7 +732,7 @@ typedef struct {
 
 typedef struct {
   double x, y, yaw;        /* dst = R(yaw) src + (x, y) */
-  double cost;             /* Huber loss of the last linearisation made */
+  double cost;             /* the loss (Huber's by default) summed over the last linearisation made */
   int32_t iterations;      /* steps taken */
   int32_t correspondences; /* of the last linearisation made */
   int32_t status;          /* 0 ok; 1 a side has no surface points; 2 a side has more than RSX_CFEAR_MAX_SURFACE_POINTS; 4 fewer than

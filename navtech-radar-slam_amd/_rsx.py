@@ -114,7 +114,7 @@ class KStrongestParams(C.Structure):
 class CfearParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("max_condition", C.c_double), ("cos_max_normal_angle", C.c_double), ("huber_delta", C.c_double),
                 ("step_epsilon", C.c_double), ("min_points", C.c_int32), ("max_iterations", C.c_int32), ("min_correspondences", C.c_int32),
-                ("reserved", C.c_int32 * 3)]
+                ("cost", C.c_int32), ("loss", C.c_int32), ("weights", C.c_int32)]
 
 
 class CfearTrackParams(C.Structure):
@@ -125,6 +125,8 @@ class CfearTrackParams(C.Structure):
 CFEAR_MAX_POINTS, CFEAR_MAX_SURFACE_POINTS = 16384, 4096
 CFEAR_MAX_KEYFRAMES = 4
 CFEAR_SEARCH_CELLS, CFEAR_SEARCH_BRUTE = 0, 1  # rsx_cfear_track_params.search
+CFEAR_COST_P2L, CFEAR_COST_P2P, CFEAR_COST_P2D = 0, 1, 2  # rsx_cfear_params.cost
+CFEAR_LOSS_HUBER, CFEAR_LOSS_CAUCHY, CFEAR_LOSS_NONE = 0, 1, 2  # rsx_cfear_params.loss
 CFEAR_STATUS_RANGE, CFEAR_STATUS_POINTS = 1, 2  # scan status word
 CFEAR_SURFACE_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("lambda_max", "<f4"), ("lambda_min", "<f4"),
                                       ("n_points", "<i4"), ("cell", "<i4")])

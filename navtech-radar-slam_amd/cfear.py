@@ -11,7 +11,8 @@ from ._rsx import (CFEAR_MAX_SURFACE_POINTS, CFEAR_RESULT_DTYPE, CFEAR_SURFACE_P
 
 def default_params():
     """radius 3.5 m, min_points 6, max_condition 1e5, cos_max_normal_angle cos 30 deg, huber_delta 0.1 m, step_epsilon 1e-6,
-    max_iterations 50, min_correspondences 6."""
+    max_iterations 50, min_correspondences 6; cost 0 (CFEAR_COST_P2L), loss 0 (CFEAR_LOSS_HUBER), weights 0: the objective of the
+    registration, chosen among CFEAR_COST_* x CFEAR_LOSS_* x weights 0 / 1 (include/rsx.h)."""
     p = CfearParams()
     check(lib().rsx_cfear_default_params(C.byref(p)))
     return p

@@ -250,6 +250,9 @@ int rsx::cfear::check_params(const rsx_cfear_params &p) {
   if (p.min_points < 2) return fail(RSX_ERR_BAD_ARG, "min_points %d below 2", p.min_points);
   if (p.max_iterations < 1 || p.max_iterations > 200) return fail(RSX_ERR_BAD_ARG, "max_iterations %d outside [1, 200]", p.max_iterations);
   if (p.min_correspondences < 1) return fail(RSX_ERR_BAD_ARG, "min_correspondences %d below 1", p.min_correspondences);
+  if (p.cost < RSX_CFEAR_COST_P2L || p.cost > RSX_CFEAR_COST_P2D) return fail(RSX_ERR_BAD_ARG, "cost %d is none of RSX_CFEAR_COST_*", p.cost);
+  if (p.loss < RSX_CFEAR_LOSS_HUBER || p.loss > RSX_CFEAR_LOSS_NONE) return fail(RSX_ERR_BAD_ARG, "loss %d is none of RSX_CFEAR_LOSS_*", p.loss);
+  if (p.weights != 0 && p.weights != 1) return fail(RSX_ERR_BAD_ARG, "weights %d is neither 0 nor 1", p.weights);
   return RSX_OK;
 }
 
@@ -345,7 +348,9 @@ int rsx_cfear_default_params(rsx_cfear_params *p) try {
   p->min_points = 6;
   p->max_iterations = 50;
   p->min_correspondences = 6;
-  p->reserved[0] = p->reserved[1] = p->reserved[2] = 0;
+  p->cost = RSX_CFEAR_COST_P2L;
+  p->loss = RSX_CFEAR_LOSS_HUBER;
+  p->weights = 0;
   return RSX_OK;
 } RSX_CATCH_ALL
 

@@ -30,9 +30,15 @@
 //   scans with no host round trip; the ring (records, poses, sorted keys and records) lives in the sequence's state in HBM, the
 //   header is read at the start and written back at the end, the LDS tables are rebuilt from the sorted keys at the start.  A
 //   workgroup reads back what it wrote to HBM only behind __threadfence_block() + __syncthreads(); no workgroup reads another's.
-//   cfear_track_kernel<true> (rsx_cfear_track_params.compensate, tests/cfear_mocomp_np.py): the scan is compensated for the sensor's
+//   cfear_track_kernel<COMP = true> (rsx_cfear_track_params.compensate, tests/cfear_mocomp_np.py): the scan is compensated for the sensor's
 //   motion into a copy in the state before each of two registrations -- with the motion before it, then with the motion the first
 //   registration found -- and the first keyframe once the first motion is known; joint_register itself knows nothing of it.
+// GENERAL (joint_register and both kernels; the host takes it when rsx_cfear_params.cost | loss | weights != 0): the term a
+//   correspondence adds is chosen among point-to-line / point-to-point / point-to-distribution, Huber / Cauchy / none, weighted or
+//   not (include/rsx.h, tests/cfear_cost_np.py) by uniform branches on three integers of the kernel's constants (RgGeneral) -- one instance for all
+//   seventeen combinations.  Two rows add into the same eleven sums.  What the other objectives read beside x, y, nx, ny -- the
+//   second 16 bytes of the CHOSEN record and of the src record -- is fetched by record index after the search; the searches, the
+//   index and the staged keyframes stay at 16 bytes per candidate.  The instances without GENERAL are the code they were.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,6 +47,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <type_traits>
 
 #include "cfear.h"
 #include "cfear_dev.h"
@@ -73,6 +80,13 @@ struct RgConsts {
   double r, r2, cos_max, delta, step_epsilon;
   int max_iterations, min_correspondences;
 };
+// ... of the GENERAL instances: with rsx_cfear_params' cost, loss and weights.  A type of its own, so that the kernel arguments of
+// the instances without GENERAL keep their layout, and with it the code the compiler makes of them
+struct RgGeneral : RgConsts {
+  int cost, loss, weights;
+};
+template <bool GENERAL>
+using Rg = std::conditional_t<GENERAL, RgGeneral, RgConsts>;
 
 struct TrConsts {
   double keyframe_distance, keyframe_rotation;
@@ -99,10 +113,27 @@ struct TrackHeader {
   int32_t head, n_ring, started;
   int32_t first;  // compensation: the ring's only keyframe is the sequence's first scan, still as measured (its times: ST_TAU0)
 };
-// ... then, for compensation: the times of the first scan's records, and the current scan compensated (x, y, nx, ny per record)
+// ... then, for compensation: the times of the first scan's records, and the current scan compensated (x, y, nx, ny per record);
+// then, for the GENERAL instances: the second halves (lambda_max, lambda_min, n_points, cell) of the ring's records, slot by slot as
+// ST_ORIG holds the first halves; written where a keyframe is inserted and never by compensation (a rigid motion leaves them)
 constexpr size_t ST_HEADER = 256, ST_ORIG = ST_HEADER, ST_INDEX = ST_ORIG + (size_t)MAXK * CAP * 16, ST_TAU0 = ST_INDEX + WS_BYTES,
-                 ST_COMP = ST_TAU0 + (size_t)CAP * 4, ST_BYTES = ST_COMP + (size_t)CAP * 16;
+                 ST_COMP = ST_TAU0 + (size_t)CAP * 4, ST_EXTRA = ST_COMP + (size_t)CAP * 16, ST_BYTES = ST_EXTRA + (size_t)MAXK * CAP * 16;
 static_assert(sizeof(TrackHeader) <= ST_HEADER, "header room");
+static_assert(ST_ORIG % 16 == 0 && ST_EXTRA % 16 == 0 && ST_BYTES % 16 == 0, "float4 regions");
+
+// the second half of a surface-point record as the GENERAL instances read it
+struct SpExtra {
+  double lmax, lmin, n;
+  bool valid;  // include/rsx.h: lambda_min > 0, lambda_max >= lambda_min, both finite
+};
+__device__ __forceinline__ SpExtra sp_extra(const float4 &h) {
+  SpExtra e;
+  e.lmax = (double)h.x;
+  e.lmin = (double)h.y;
+  e.n = (double)__float_as_int(h.z);
+  e.valid = h.y > 0.f && h.x >= h.y && fabsf(h.x) < INFINITY && fabsf(h.y) < INFINITY;
+  return e;
+}
 
 __device__ __forceinline__ int cell_coord(double v, double r) {
   const double f = floor(v / r);
@@ -138,8 +169,14 @@ __device__ void build_index(const float4 *orig, int stride, int n, unsigned *key
 // The joint registration of one scan (ns64 records at sp[i * sstride]) against kf[0 .. K) (LDS, ring order; K <= MAXK; search 0:
 // every keyframe of 1 .. CAP records has its index built) from (x, y, yaw).  Called by all threads behind a barrier; every thread
 // returns the same result.  s_red: [NW][N_SUMS], s_fr: [MAXK]
-__device__ void joint_register(const float4 *sp, int sstride, int64_t ns64, int K, const KfDesc *kf, int search, unsigned char *lds,
-                               double *s_red, KfFrame *s_fr, const RgConsts &k, double x, double y, double yaw, rsx_cfear_result &res) {
+// GENERAL: the objective is chosen by k.cost, k.loss and k.weights (include/rsx.h; tests/cfear_cost_np.py) with workgroup-uniform
+// branches; without it the code is the point-to-line / Huber / unweighted one it was, and sx, sxstride and kf_xoff are not read.
+// The second half of src record i is sx[i * sxstride] (the input record's, also when sp is a compensated copy), that of record j of
+// keyframe c is kf[c].orig[j * kf[c].stride + kf_xoff]; only the chosen record's is fetched, the searches read what they read
+template <bool GENERAL>
+__device__ void joint_register(const float4 *sp, int sstride, const float4 *sx, int sxstride, int64_t ns64, int K, const KfDesc *kf,
+                               ptrdiff_t kf_xoff, int search, unsigned char *lds, double *s_red, KfFrame *s_fr, const Rg<GENERAL> &k, double x,
+                               double y, double yaw, rsx_cfear_result &res) {
   const int t = threadIdx.x;
   res.x = x;
   res.y = y;
@@ -224,10 +261,12 @@ __device__ void joint_register(const float4 *sp, int sstride, int64_t ns64, int 
       const KfFrame fr = s_fr[c];
       const double qx = (fr.cs * px - fr.sn * py) + fr.tx, qy = (fr.sn * px + fr.cs * py) + fr.ty;
       float4 d;
+      unsigned jsel = 0;  // (GENERAL) the chosen record's index
       if (search == RSX_CFEAR_SEARCH_BRUTE) {
         const unsigned short j = parked[item];
         if (j == NO_BEST) continue;
         d = kf[c].orig[(size_t)j * kf[c].stride];
+        if constexpr (GENERAL) jsel = j;
       } else {
         const double mx = fr.cs * pnx - fr.sn * pny, my = fr.sn * pnx + fr.cs * pny;
         const unsigned short *table = tables + (size_t)kf[c].slot * NCELL;
@@ -283,8 +322,84 @@ __device__ void joint_register(const float4 *sp, int sstride, int64_t ns64, int 
             }
         }
         if (!found) continue;
+        if constexpr (GENERAL) jsel = best_j;
       }
       const double nx = (double)d.z, ny = (double)d.w;
+      if constexpr (GENERAL) {
+        double sc0 = 1.0, sc1 = 1.0, v = 1.0;
+        if (k.cost == RSX_CFEAR_COST_P2D || k.weights) {  // (uniform)
+          const SpExtra dj = sp_extra(kf[c].orig[(size_t)jsel * kf[c].stride + kf_xoff]);
+          if (!dj.valid) continue;
+          if (k.cost == RSX_CFEAR_COST_P2D) {
+            sc0 = 1.0 / sqrt(dj.lmin);
+            sc1 = 1.0 / sqrt(dj.lmax);
+          }
+          if (k.weights) {
+            const SpExtra si = sp_extra(sx[(size_t)i * sxstride]);
+            if (!si.valid) continue;
+            const double mx = fr.cs * pnx - fr.sn * pny, my = fr.sn * pnx + fr.cs * pny;
+            const double w_dir = fmax(mx * nx + my * ny, 0.0);
+            const double p_i = log(1.0 + si.lmax / si.lmin), p_j = log(1.0 + dj.lmax / dj.lmin);
+            const double w_plan = (2.0 * fmin(p_i, p_j)) / (p_i + p_j), w_num = (2.0 * fmin(si.n, dj.n)) / (si.n + dj.n);
+            v = (w_dir * w_plan) * w_num;
+          }
+        }
+        const double ex = qx - (double)d.x, ey = qy - (double)d.y;
+        const double ppx = -fr.sn * px - fr.cs * py, ppy = fr.cs * px - fr.sn * py;  // R'(yaw_r) mu_i
+        const double kc = kf[c].c, ks = kf[c].s;
+        const double e0 = sc0 * (nx * ex + ny * ey);
+        const double a0 = sc0 * (kc * nx - ks * ny), a1 = sc0 * (ks * nx + kc * ny), a2 = sc0 * (nx * ppx + ny * ppy);
+        const bool two = k.cost != RSX_CFEAR_COST_P2L;  // (uniform) the second row, along t_j = (-n_jy, n_jx)
+        const double ux = -ny, uy = nx;
+        const double e1 = sc1 * (ux * ex + uy * ey);
+        const double b0 = sc1 * (kc * ux - ks * uy), b1 = sc1 * (ks * ux + kc * uy), b2 = sc1 * (ux * ppx + uy * ppy);
+        double s2, a, half;
+        if (two) {
+          s2 = e0 * e0 + e1 * e1;
+          a = sqrt(s2);
+          half = 0.5 * s2;
+        } else {
+          s2 = e0 * e0;
+          a = fabs(e0);
+          half = 0.5 * e0 * e0;
+        }
+        double wt, rho;
+        if (k.loss == RSX_CFEAR_LOSS_HUBER) {
+          wt = a <= k.delta ? 1.0 : k.delta / a;
+          rho = a <= k.delta ? half : k.delta * (a - 0.5 * k.delta);
+        } else if (k.loss == RSX_CFEAR_LOSS_CAUCHY) {
+          const double dd = k.delta * k.delta, z = 1.0 + s2 / dd;
+          wt = 1.0 / z;
+          rho = (0.5 * dd) * log(z);
+        } else {
+          wt = 1.0;
+          rho = half;
+        }
+        const double vw = v * wt;
+        acc[0] += vw * a0 * a0;
+        acc[1] += vw * a1 * a0;
+        acc[2] += vw * a1 * a1;
+        acc[3] += vw * a2 * a0;
+        acc[4] += vw * a2 * a1;
+        acc[5] += vw * a2 * a2;
+        acc[6] += vw * a0 * e0;
+        acc[7] += vw * a1 * e0;
+        acc[8] += vw * a2 * e0;
+        if (two) {
+          acc[0] += vw * b0 * b0;
+          acc[1] += vw * b1 * b0;
+          acc[2] += vw * b1 * b1;
+          acc[3] += vw * b2 * b0;
+          acc[4] += vw * b2 * b1;
+          acc[5] += vw * b2 * b2;
+          acc[6] += vw * b0 * e1;
+          acc[7] += vw * b1 * e1;
+          acc[8] += vw * b2 * e1;
+        }
+        acc[9] += v * rho;
+        acc[10] += 1.0;
+        continue;
+      }
       const double e = nx * (qx - (double)d.x) + ny * (qy - (double)d.y);
       const double ae = fabs(e);
       const double wt = ae <= k.delta ? 1.0 : k.delta / ae;
@@ -371,11 +486,13 @@ __device__ void joint_register(const float4 *sp, int sstride, int64_t ns64, int 
 __device__ __forceinline__ int clamp_count(int64_t n) { return n <= 0 ? 0 : (n > CAP ? CAP + 1 : (int)n); }
 
 // kf_job_off null: job i has keyframe i alone; poses null: every keyframe at the identity
+// GENERAL: joint_register's; the second halves are the second float4 of the 32-byte input records
+template <bool GENERAL>
 __global__ __launch_bounds__(NT) void cfear_joint_kernel(const rsx_cfear_surface_point *__restrict__ src, const int64_t *__restrict__ src_begin,
                                                          const int64_t *__restrict__ src_end, const rsx_cfear_surface_point *__restrict__ kfrec,
                                                          const int64_t *__restrict__ kf_begin, const int64_t *__restrict__ kf_end,
                                                          const int64_t *__restrict__ kf_job_off, const double *__restrict__ poses,
-                                                         const double *__restrict__ init, int n_jobs, RgConsts k, int search,
+                                                         const double *__restrict__ init, int n_jobs, Rg<GENERAL> k, int search,
                                                          unsigned char *index, rsx_cfear_result *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ct_lds[];
   __shared__ double s_red[NW * N_SUMS];
@@ -438,17 +555,19 @@ __global__ __launch_bounds__(NT) void cfear_joint_kernel(const rsx_cfear_surface
         if (n >= 1 && n <= CAP)
           build_index(s_kf[c].orig, 2, n, ws_keys + (size_t)c * CAP, ws_sorted + (size_t)c * CAP, tables + (size_t)c * NCELL, sortbuf, k.r, t);
       }
-    joint_register(reinterpret_cast<const float4 *>(src + sb), 2, ns64, K, s_kf, search, ct_lds, s_red, s_fr, k, x, y, yaw, res);
+    joint_register<GENERAL>(reinterpret_cast<const float4 *>(src + sb), 2, reinterpret_cast<const float4 *>(src + sb) + 1, 2, ns64, K, s_kf, 1, search,
+                            ct_lds, s_red, s_fr, k, x, y, yaw, res);
     if (t == 0) out[job] = res;
   }
 }
 
 // COMP: rsx_cfear_track_params.compensate as a template parameter: without it the kernel is the code it was (everything about compensation sits behind
 // if constexpr), with it a scan is compensated into the state's copy before each of its two registrations
-template <bool COMP>
+// GENERAL: joint_register's; the ring keeps its records' second halves at ST_EXTRA, written by these instances alone
+template <bool COMP, bool GENERAL>
 __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface_point *__restrict__ rec, const float *__restrict__ tau,
                                                          const int64_t *__restrict__ begin, const int64_t *__restrict__ end,
-                                                         const int32_t *__restrict__ n_scans, RgConsts k,
+                                                         const int32_t *__restrict__ n_scans, Rg<GENERAL> k,
                                                          TrConsts tc, unsigned char *state, rsx_cfear_track_result *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ct_lds[];
   __shared__ double s_red[NW * N_SUMS];
@@ -468,6 +587,7 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
   unsigned *keys = reinterpret_cast<unsigned *>(st + ST_INDEX + WS_SORTED);
   float *tau0 = reinterpret_cast<float *>(st + ST_TAU0);
   float4 *cbuf = reinterpret_cast<float4 *>(st + ST_COMP);
+  float4 *extra = reinterpret_cast<float4 *>(st + ST_EXTRA);
   const int NK = tc.n_keyframes;
   double P[3], M[3];
   for (int a = 0; a < 3; a++) {
@@ -550,7 +670,8 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
           cur = cbuf;
           cstride = 1;
         }
-        joint_register(cur, cstride, ns64, n_ring, s_kf, tc.search, ct_lds, s_red, s_fr, k, start[0], start[1], start[2], r.reg);
+        joint_register<GENERAL>(cur, cstride, sp + 1, 2, ns64, n_ring, s_kf, (ptrdiff_t)((ST_EXTRA - ST_ORIG) / 16), tc.search, ct_lds, s_red, s_fr, k,
+                                start[0], start[1], start[2], r.reg);
         ok = r.reg.status == 0 || r.reg.status == 8;
         if (!COMP || !ok || pass == 1) break;  // (uniform)
         it0 = r.reg.iterations;
@@ -624,7 +745,10 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
         hdr->kf_n[slot] = cnt;
       }
       if (cnt <= CAP)
-        for (int j = t; j < cnt; j += NT) orig[(size_t)slot * CAP + j] = cur[(size_t)cstride * j];
+        for (int j = t; j < cnt; j += NT) {
+          orig[(size_t)slot * CAP + j] = cur[(size_t)cstride * j];
+          if constexpr (GENERAL) extra[(size_t)slot * CAP + j] = sp[2 * (size_t)j + 1];  // (the input record's, also of a compensated copy)
+        }
       __threadfence_block();  // the workgroup reads the header and the records again
       __syncthreads();
       if (tc.search == RSX_CFEAR_SEARCH_CELLS && cnt >= 1 && cnt <= CAP)
@@ -650,8 +774,9 @@ __global__ __launch_bounds__(NT) void cfear_track_kernel(const rsx_cfear_surface
   }
 }
 
-RgConsts rg_consts(const rsx_cfear_params &p) {
-  RgConsts k;
+template <bool GENERAL>
+Rg<GENERAL> rg_consts(const rsx_cfear_params &p) {
+  Rg<GENERAL> k;
   k.r = p.radius;
   k.r2 = p.radius * p.radius;
   k.cos_max = p.cos_max_normal_angle;
@@ -659,8 +784,16 @@ RgConsts rg_consts(const rsx_cfear_params &p) {
   k.step_epsilon = p.step_epsilon;
   k.max_iterations = p.max_iterations;
   k.min_correspondences = p.min_correspondences;
+  if constexpr (GENERAL) {
+    k.cost = p.cost;
+    k.loss = p.loss;
+    k.weights = p.weights;
+  }
   return k;
 }
+
+// the default objective runs the instances that know no other
+bool general(const rsx_cfear_params &p) { return (p.cost | p.loss | p.weights) != 0; }
 
 }  // namespace
 
@@ -688,12 +821,16 @@ int rsx::cfear::launch_register_keyframes(const rsx_cfear_surface_point *d_src, 
                                           const rsx_cfear_params &p, const rsx_cfear_track_params &tp, void *d_index, rsx_cfear_result *d_out,
                                           hipStream_t s) {
   if (n_jobs < 1) return fail(RSX_ERR_BAD_ARG, "n_jobs %d below 1", n_jobs);
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfear_joint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
   const int blocks = n_jobs < MAX_JOINT_BLOCKS ? n_jobs : MAX_JOINT_BLOCKS;
-  hipLaunchKernelGGL(cfear_joint_kernel, dim3((unsigned)blocks), dim3(NT), LDS_BYTES, s, d_src, d_src_begin, d_src_end, d_kf, d_kf_begin, d_kf_end,
-                     d_kf_job_offsets, d_kf_poses, d_init, (int)n_jobs, rg_consts(p), (int)tp.search, static_cast<unsigned char *>(d_index), d_out);
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
+  auto launch = [&](auto gen) {
+    constexpr bool G = decltype(gen)::value;
+    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfear_joint_kernel<G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+    hipLaunchKernelGGL(cfear_joint_kernel<G>, dim3((unsigned)blocks), dim3(NT), LDS_BYTES, s, d_src, d_src_begin, d_src_end, d_kf, d_kf_begin, d_kf_end,
+                       d_kf_job_offsets, d_kf_poses, d_init, (int)n_jobs, rg_consts<G>(p), (int)tp.search, static_cast<unsigned char *>(d_index), d_out);
+    RSX_HIP(hipGetLastError());
+    return (int)RSX_OK;
+  };
+  return general(p) ? launch(std::true_type()) : launch(std::false_type());
 }
 
 int rsx::cfear::launch_register(const rsx_cfear_surface_point *d_src, const int64_t *d_src_begin, const int64_t *d_src_end,
@@ -712,18 +849,22 @@ int rsx::cfear::launch_track(const rsx_cfear_surface_point *d_records, const flo
                              rsx_cfear_track_result *d_out, hipStream_t s) {
   if (n_sequences < 1) return fail(RSX_ERR_BAD_ARG, "n_sequences %d below 1", n_sequences);
   if (tp.compensate && !d_tau) return fail(RSX_ERR_BAD_ARG, "compensate = 1 needs the records' times");
-  auto kernel = tp.compensate ? &cfear_track_kernel<true> : &cfear_track_kernel<false>;
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
   TrConsts tc;
   tc.keyframe_distance = tp.keyframe_distance;
   tc.keyframe_rotation = tp.keyframe_rotation;
   tc.n_keyframes = tp.n_keyframes;
   tc.predict = tp.predict;
   tc.search = tp.search;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n_sequences), dim3(NT), LDS_BYTES, s, d_records, d_tau, d_begin, d_end, d_n_scans, rg_consts(p), tc,
-                     static_cast<unsigned char *>(d_state), d_out);
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
+  auto launch = [&](auto comp, auto gen) {
+    constexpr bool C = decltype(comp)::value, G = decltype(gen)::value;
+    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfear_track_kernel<C, G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+    hipLaunchKernelGGL((cfear_track_kernel<C, G>), dim3((unsigned)n_sequences), dim3(NT), LDS_BYTES, s, d_records, d_tau, d_begin, d_end, d_n_scans,
+                       rg_consts<G>(p), tc, static_cast<unsigned char *>(d_state), d_out);
+    RSX_HIP(hipGetLastError());
+    return (int)RSX_OK;
+  };
+  if (general(p)) return tp.compensate ? launch(std::true_type(), std::true_type()) : launch(std::false_type(), std::true_type());
+  return tp.compensate ? launch(std::true_type(), std::false_type()) : launch(std::false_type(), std::false_type());
 }
 
 struct rsx_cfear_tracker {

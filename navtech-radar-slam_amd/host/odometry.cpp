@@ -31,6 +31,9 @@
 // pipeline: oriented surface points of the keypoints and a point-to-line registration of consecutive scans, no Cartesian image,
 // descriptors or matcher (rsx_odometry_set_cfear, windowed path only, not with --compensate; meant for `--keypoints kstrongest
 // --min-separation 0`).  n_matches is then the number of correspondences of the last iteration.
+// `--cfear-cost p2l|p2p|p2d`, `--cfear-loss huber|cauchy|none` and `--cfear-weights` choose the registration's objective among
+// CFEAR's family (rsx_cfear_params.cost, loss, weights; the default is p2l, huber, no weights), with or without the tracker;
+// `--cfear-huber` is the threshold of either loss, dimensionless under p2d.
 // `--cfear-keyframes S` (with `--cfear-keyframe-distance M`, `--cfear-keyframe-rotation DEG`, `--cfear-no-prediction`; any of them
 // switches it on, S = 3 by default) runs CFEAR's keyframe tracker instead of consecutive pairs: every scan is registered jointly
 // against the last S keyframes from a constant-velocity prediction, and becomes a keyframe after M metres or DEG degrees
@@ -188,7 +191,16 @@ int main(int argc, char **argv) {
       else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac | cfear
       else if (a == "--cfear-radius" && i + 1 < argc) cfp.radius = std::atof(argv[++i]);               // cfear: cell side and search radius [m] (3.5)
       else if (a == "--cfear-normal-angle" && i + 1 < argc) cfp.cos_max_normal_angle = std::cos(std::atof(argv[++i]) * 3.14159265358979323846 / 180.0);  // cfear: largest angle between matched normals [deg] (30)
-      else if (a == "--cfear-huber" && i + 1 < argc) cfp.huber_delta = std::atof(argv[++i]);           // cfear: Huber threshold [m] (0.1)
+      else if (a == "--cfear-huber" && i + 1 < argc) cfp.huber_delta = std::atof(argv[++i]);           // cfear: the loss's threshold, Huber's or Cauchy's [m; with p2d dimensionless] (0.1)
+      else if (a == "--cfear-cost" && i + 1 < argc) {  // cfear: p2l (default) | p2p | p2d, what a correspondence's residual is
+        const std::string v = argv[++i];
+        if (v != "p2l" && v != "p2p" && v != "p2d") die("--cfear-cost must be p2l, p2p or p2d");
+        cfp.cost = v == "p2l" ? RSX_CFEAR_COST_P2L : (v == "p2p" ? RSX_CFEAR_COST_P2P : RSX_CFEAR_COST_P2D);
+      } else if (a == "--cfear-loss" && i + 1 < argc) {  // cfear: huber (default) | cauchy | none
+        const std::string v = argv[++i];
+        if (v != "huber" && v != "cauchy" && v != "none") die("--cfear-loss must be huber, cauchy or none");
+        cfp.loss = v == "huber" ? RSX_CFEAR_LOSS_HUBER : (v == "cauchy" ? RSX_CFEAR_LOSS_CAUCHY : RSX_CFEAR_LOSS_NONE);
+      } else if (a == "--cfear-weights") cfp.weights = 1;  // cfear: weigh a correspondence by how well its two surface points resemble each other
       else if (a == "--cfear-max-iterations" && i + 1 < argc) cfp.max_iterations = std::atoi(argv[++i]);  // cfear: Gauss-Newton iterations at most (50)
       else if (a == "--cfear-keyframes" && i + 1 < argc) { ctp.n_keyframes = std::atoi(argv[++i]); cfear_track = true; }  // cfear: track against the last S keyframes (off: consecutive pairs)
       else if (a == "--cfear-keyframe-distance" && i + 1 < argc) { ctp.keyframe_distance = std::atof(argv[++i]); cfear_track = true; }  // cfear tracking: a new keyframe after this many metres (1.5)
@@ -218,7 +230,7 @@ int main(int argc, char **argv) {
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--window W] [--threads T] "
-          "[--estimator orora|ransac|mcransac|cfear] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--cfear-compensate] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
+          "[--estimator orora|ransac|mcransac|cfear] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-cost p2l|p2p|p2d] [--cfear-loss huber|cauchy|none] [--cfear-weights] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--cfear-compensate] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
           "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";

@@ -16,9 +16,14 @@ of the synthetic drive synth.polar_sequence(11, n), MulRan shape (400 x 3360).  
   (f) the timed tracker (rsx_cfear_tracker_push_timed_device, the records' times from rsx_cfear_surface_points_timed_batch) with
       compensate = 0 and compensate = 1, alternating with the untimed tracker of (c), one sequence and 16; and the odometry of (d)
       with compensation on.  The synthetic images are not distorted by the motion, so (f) measures cost, not accuracy
+  (g) the objectives (rsx_cfear_params.cost x loss x weights, 18 combinations; the first row is the default's, measured in the same
+      run): the pairs of (a) through rsx_cfear_register_batch_device, the combinations alternating sweep by sweep, and the
+      3-keyframe tracker of (c); per combination the time per 64 jobs, mean iterations, status 8, pairs more than 0.7 m off, the
+      median pair error and the end-of-trajectory error, as a table.  Reported, not gated.  objectives = 0 leaves (g) out (a
+      library from before the objectives ignores the three words)
 Prints microseconds per call and scans/s; every timed window ends in a device synchronise.
 
-usage: bench_cfear_track.py [n_scans=256] [reps=5] [odometry_reps=3]"""
+usage: bench_cfear_track.py [n_scans=256] [reps=5] [odometry_reps=3] [objectives=1]"""
 import math
 import os
 import sys
@@ -32,6 +37,7 @@ from navtech_radar_slam_amd import _rsx, cfear, kstrongest, odometry, synth  # n
 n_scans = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 odo_reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+objectives = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 batch = 64
 assert n_scans % batch == 0 and n_scans >= 2 * batch
 
@@ -71,14 +77,14 @@ def between(a, b):
 
 
 # ---- (c) first: the tracked poses are (b)'s keyframe poses ----
-def run_tracker(n_seq, tp, rounds):
-    t = cfear.Tracker(n_seq, track=tp)
+def run_tracker(n_seq, tp, rounds, prm=None):
+    t = cfear.Tracker(n_seq, params=prm, track=tp)
     rec, off = cfear.ragged(records * n_seq, SP)
     d = [dev(rec), dev(off), dev(np.full(n_seq, n_scans, dtype=np.int32))]
     d_out = torch.zeros(n_seq * n_scans * 80, dtype=torch.uint8, device="cuda")
     ts = []
     for r in range(rounds + 1):  # (the first is the warm-up)
-        t.reset(track=tp)
+        t.reset(params=prm, track=tp)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         t.push_device(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d_out.data_ptr(), stream=stream)
@@ -246,6 +252,60 @@ for name, tp in (("3 keyframes, start at the previous pose", cfear.track_params(
     ps = [(float(r["x"]), float(r["y"]), float(r["yaw"])) for r in o]
     report(name, [(0.0, 0.0, 0.0)] + [between(ps[i - 1], ps[i]) for i in range(1, n_scans)], o["reg"]["status"], o["reg"]["iterations"], ps[-1])
     print(f"    keyframes {int(np.sum(o['keyframe'] == 1))}, re-anchored {int(np.sum(o['keyframe'] == 2))}, correspondences mean {o['reg']['correspondences'][1:].mean():.0f}")
+
+
+# ---- (g) the objectives ----
+def errors(rel):
+    return np.array([math.hypot(rel[i][0] - t[0], rel[i][1] - t[1]) for i in range(1, n_scans) for t in [synth.relative_pose(poses[i - 1], poses[i])]])
+
+
+if objectives:
+    COSTS, LOSSES = ("p2l", "p2p", "p2d"), ("huber", "cauchy", "none")
+    combos = [(c, l, w) for c in range(3) for l in range(3) for w in range(2)]
+    prms = {k: cfear.params(cost=k[0], loss=k[1], weights=k[2]) for k in combos}
+    g_res = {k: [torch.zeros(batch * 48, dtype=torch.uint8, device="cuda") for _ in range(nb)] for k in combos}
+
+    def sweep_objective(k):
+        def f():
+            for b in range(nb):
+                s, so, d, do = d_pairs[b]
+                h.register_device(s.data_ptr(), so.data_ptr(), d.data_ptr(), do.data_ptr(), batch, g_res[k][b].data_ptr(), params=prms[k], stream=stream)
+        return f
+
+    g_sweeps = {k: sweep_objective(k) for k in combos}
+    for f in g_sweeps.values():
+        timed(f)  # warm-up
+    g_times = {k: [] for k in combos}
+    for r in range(reps):
+        for k, f in g_sweeps.items():  # alternating
+            g_times[k].append(timed(f))
+    end_truth = synth.relative_pose(poses[0], poses[n_scans - 1])
+    print(f"(g) objectives, {n_scans - 1} consecutive pairs from the identity (us per {batch} pairs: median of {reps} sweeps of {nb} calls) and the 3-keyframe "
+          f"tracker, constant-velocity start (ms per push of {n_scans} scans, us per {batch} scans: median of {reps})")
+    print("| cost | loss | weights | pairs: us per 64 | mean it. | status 8 | other != 0 | > 0.7 m off | median error [m] | end of trajectory [m] "
+          "| tracker: ms per push | us per 64 | mean it. | status 8 | other != 0 | > 0.7 m off | median error [m] | end of trajectory [m] |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for k in combos:
+        p = np.concatenate([r.cpu().numpy().view(_rsx.CFEAR_RESULT_DTYPE) for r in g_res[k]])[:n_scans - 1]
+        if k == (0, 0, 0):
+            assert p.tobytes() == host["pair"][:n_scans - 1].tobytes(), "the default objective is not (a)'s bytes"
+        rel = [(0.0, 0.0, 0.0)] + [(float(v["x"]), float(v["y"]), float(v["yaw"])) for v in p]
+        absolute = (0.0, 0.0, 0.0)
+        for r_ in rel[1:]:
+            absolute = compose(absolute, r_)
+        err = errors(rel)
+        row = [COSTS[k[0]], LOSSES[k[1]], "yes" if k[2] else "no", f"{float(np.median(g_times[k])) / nb * 1e6:.0f}", f"{p['iterations'].mean():.1f}",
+               str(int(np.sum(p["status"] == 8))), str(int(np.sum((p["status"] != 0) & (p["status"] != 8)))), str(int(np.sum(err > 0.7))),
+               f"{np.median(err):.3f}", f"{math.hypot(absolute[0] - end_truth[0], absolute[1] - end_truth[1]):.1f}"]
+        out, ts = run_tracker(1, cfear.track_params(), reps, prms[k])
+        o = out[0]
+        ps = [(float(r["x"]), float(r["y"]), float(r["yaw"])) for r in o]
+        err = errors([(0.0, 0.0, 0.0)] + [between(ps[i - 1], ps[i]) for i in range(1, n_scans)])
+        st = o["reg"]["status"][1:]
+        row += [f"{np.median(ts) * 1e3:.1f}", f"{np.median(ts) / n_scans * batch * 1e6:.0f}", f"{o['reg']['iterations'][1:].mean():.1f}", str(int(np.sum(st == 8))),
+                str(int(np.sum((st != 0) & (st != 8)))), str(int(np.sum(err > 0.7))), f"{np.median(err):.3f}",
+                f"{math.hypot(ps[-1][0] - end_truth[0], ps[-1][1] - end_truth[1]):.1f}"]
+        print("| " + " | ".join(row) + " |", flush=True)
 
 # ---- (d) the odometry ----
 kw = dict(keypoints="kstrongest", kstrongest=kstrongest.params(min_separation=0), estimator="cfear")
