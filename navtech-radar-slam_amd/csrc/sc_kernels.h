@@ -119,8 +119,10 @@ int launch_knn(const float *rkeys, int64_t n_search, const float *qkey, int32_t 
 // ---- exact re-scoring behind the filter ----
 constexpr int RESCORE_SHORTLIST_CAP = 2048;  // short-list positions per query (sl_cnt <= this; stride of the record array)
 // Only the HEAD of a short list is stored as records: the bins up to the first one whose cumulative count reaches
-// RESCORE_HEAD (clamped to the last bin of the list).  sc_window_kernel reads positions below min(sl_cnt, WINDOW_P) and
-// nothing else; sc_rescore_wave_kernel re-derives the positions behind the head from the query's row of bounds.
+// RESCORE_HEAD (clamped to the last bin of the list).  sc_window_kernel uses positions below min(sl_cnt, WINDOW_P) and
+// nothing else (it LOADS all WINDOW_P slots of the query's stride at its start, before it knows sl_cnt, and drops the rest:
+// the array must be allocated at its full stride for every query of a launch, written or not); sc_rescore_wave_kernel
+// re-derives the positions behind the head from the query's row of bounds.
 constexpr int RESCORE_HEAD = 512;
 static_assert(RESCORE_HEAD >= RSX_SC_WINDOW_P && RESCORE_HEAD <= RESCORE_SHORTLIST_CAP,
               "the head must cover every list position sc_window_kernel may read (WINDOW_P)");

@@ -27,7 +27,14 @@
 // Cost: 8192 queries x ~146 entries = 1.2 M pairs at 174 MFMAs per 32 = 0.21 Tflop: ~0.1 ms of matrix-core time against
 // the ~1.2 ms of VALU time it replaces.  The entries are gathered (2400 + 256 B each, whole rows of the entry-major
 // image hnR): 3.1 GB per batch out of a 27 MB database image, i.e. from L2 / MALL -- which is what bounds the kernel
-// (0.37 ms).
+// (0.36 ms).
+// What its time follows (round 10, the region timers below; DESIGN.md "Where round 10 points"): the work the four resident
+// workgroups of a CU put through its gather and VALU pipes, NOT the length of one workgroup's dependent chain -- a
+// cooperative pass 2 cut the chain by 16 % and the kernel by 1 %, and a split that gathered every B fragment twice made it
+// slower.  So the kernel does nothing twice: the list's records are loaded once, with the query (they reach do_group, the
+// pass-2 selection and the tail through LDS), the head's ranking is shared by the four waves instead of repeated by each,
+// the epilogue and the alignment use the lean forms of sc_window_dev.h (identical values), and the key copies are laid
+// out without index divisions.
 //
 // Error bound of KC (scaled keys x, max |x| in [2^9, 2^10); E = sum x^2):
 //   representation  x = hi + lo + r, |r| <= 2^-22 |x| (+ 2^-25 absolute where lo is subnormal)
@@ -43,6 +50,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 
 #include "rsx_common.h"
 #include "sc_kernels.h"
@@ -75,6 +83,29 @@ static_assert(W_ST2_OFF % 16 == 0 && W_QM_OFF % 8 == 0 && W_QM_OFF + 8 <= 5 * WI
 #ifndef WIN_RING
 #define WIN_RING 15  // B fragments of the image GEMM in flight per wave
 #endif
+// Region timers of the kernel's dependent chain: -DRSX_WINDOW_PROF=1 (tools/build_window_prof.sh; neither the product nor the
+// experiments build has them).  Every wave sums s_memtime differences per region -- each lap drains the wave's own memory and
+// LDS queues first, so a region owns the latency it started -- and adds them to block (query % WIN_PROF_COPIES) of a buffer
+// that launch_window prints after every launch (it synchronises the stream: a profiling build).
+#ifdef RSX_WINDOW_PROF
+constexpr bool kWinProf = true;
+#else
+constexpr bool kWinProf = false;
+#endif
+enum WinProfRegion {
+  WP_PROLOGUE = 0,  // start .. the images stand in LDS (the loads of the query and of the list records included)
+  WP_GROUP1,        // the wave's pass-1 group
+  WP_RANK,          // tau_ub of the head by counting
+  WP_SELECT,        // which positions behind the head get a record (wave 0)
+  WP_GROUP2,        // the pass-2 groups
+  WP_TAIL,          // write_list
+  WP_BARRIER,       // waiting at the workgroup's barriers
+  WP_TOTAL,
+  WP_COUNT,         // waves that reported (one per workgroup and wave index)
+  WP_GROUPS2,       // pass-2 groups the wave took part in
+  WIN_PROF_WORDS
+};
+constexpr int WIN_PROF_COPIES = 64;
 // ------------------------------------------------------------------------------------------
 // database side: [slot][hi 0..63 | lo 0..63] fp16 (elements 60..63 zero: the K padding) + the key's scaled norm
 // ------------------------------------------------------------------------------------------
@@ -103,6 +134,7 @@ struct WindowArgs {
   WindowSurvivor *surv;  // [nq][WINDOW_LIST_STRIDE]: header + survivor list of every query
   double eps;  // the filter's error budget, as the re-scoring kernel applies it to a bound
   int32_t k;
+  unsigned long long *prof;  // RSX_WINDOW_PROF builds: [WIN_PROF_COPIES][4 waves][WIN_PROF_WORDS], else nullptr
 };
 
 __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
@@ -110,7 +142,7 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   __shared__ float s_ub[WINDOW_HEAD];
   __shared__ int s_pos[WINDOW_P];
   __shared__ int s_n2;
-  __shared__ float s_tau;  // the head's k-th smallest upper bound, kept for the tail (a register across pass 2 would be spilled)
+  __shared__ float s_tau;  // the head's k-th smallest upper bound: from the lane that ranks it to the selection and the tail
   // what the workgroup knows of list position p once its group is done (filter bound, slot, preview, k* | shift mask); the
   // positions no group takes are never read: they are not survivors
   // (one block, because the prologue stages the query in it before the first group touches any of the five)
@@ -119,6 +151,60 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   int *const s_slot = reinterpret_cast<int *>(s_cand + WINDOW_P), *const s_ks = s_slot + WINDOW_P;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: group counters in SGPRs)
   const int qi = blockIdx.x;
+  // region timers (kWinProf): wave-uniform, so they live in SGPRs; nothing of them is compiled into the product
+  long long t_mark = 0, t_begin = 0, tacc[WP_TOTAL] = {0, 0, 0, 0, 0, 0, 0};
+  int prof_groups2 = 0;
+  if constexpr (kWinProf) t_begin = t_mark = clock64();
+  auto lap = [&](int region) {
+    if constexpr (kWinProf) {
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      const long long t = clock64();
+      tacc[region] += t - t_mark;
+      t_mark = t;
+    }
+  };
+  auto barrier = [&](int region) {  // the region up to the barrier, then the wait
+    lap(region);
+    __syncthreads();
+    lap(WP_BARRIER);
+  };
+  auto prof_flush = [&]() {
+    if constexpr (kWinProf) {
+      if (a.prof && lane == 0) {
+        unsigned long long *o = a.prof + ((size_t)(qi % WIN_PROF_COPIES) * 4 + wave) * WIN_PROF_WORDS;
+#pragma unroll
+        for (int r = 0; r < WP_TOTAL; r++) atomicAdd(o + r, (unsigned long long)tacc[r]);
+        atomicAdd(o + WP_TOTAL, (unsigned long long)(t_mark - t_begin));
+        atomicAdd(o + WP_COUNT, 1ull);
+        atomicAdd(o + WP_GROUPS2, (unsigned long long)prof_groups2);
+      }
+    }
+  };
+  // the query's descriptor column / norm (wave 0) and sector key (wave 1) are requested together with sl_cnt: nothing of the
+  // prologue waits for the list length before its own round trip is on the way
+  float4 qcol[5] = {};
+  double qn = 0.0, qv = 0.0;
+  if (wave == 0) {
+    if (lane < NS) {
+      const float4 *p = reinterpret_cast<const float4 *>(a.qdesc + (int64_t)qi * DS + lane * NR);
+#pragma unroll
+      for (int i = 0; i < 5; i++) qcol[i] = p[i];
+      qn = a.qnorm[(int64_t)qi * NS + lane];
+    }
+  } else if (wave == 1) {
+    if (lane < NS) qv = a.qvkey[(int64_t)qi * NS + lane];
+  }
+  // ... and so are the list records {lb, slot} of every position the kernel may look at, one or two per thread (one 8-byte
+  // load each), whatever the list's length: the record array has RESCORE_SHORTLIST_CAP >= WINDOW_P slots per query, and what
+  // lies behind min(sl_cnt, WINDOW_P) is dropped below.  They stay in registers across the prologue: do_group, the pass-2
+  // selection and the tail read slots and bounds from LDS, so none of them starts with a round trip to the list.
+  static_assert(WINDOW_P <= 2 * 256 && WINDOW_P <= RESCORE_SHORTLIST_CAP, "two positions per thread, inside the query's records");
+  uint2 rec0, rec1 = {0u, 0u};
+  {
+    const uint2 *sl2 = reinterpret_cast<const uint2 *>(a.slist + (int64_t)qi * RESCORE_SHORTLIST_CAP);
+    rec0 = sl2[threadIdx.x];
+    if (threadIdx.x + 256 < WINDOW_P) rec1 = sl2[threadIdx.x + 256];
+  }
   const int sl_cnt = a.sl_cnt[qi];
   WindowSurvivor *list = a.surv + (int64_t)qi * WINDOW_LIST_STRIDE;
   if (sl_cnt <= 0) {  // uniform; the re-scoring kernel still reads the header
@@ -132,6 +218,10 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
     }
     return;
   }
+  // the list records: s_slot lies behind the staging area and is filled before the prologue's second barrier; s_lb aliases the
+  // staging area and is filled behind that barrier (its first reader sits behind the barrier of pass 1)
+  static_assert(3 * WINDOW_P * 4 >= W_QM_OFF + 8, "s_slot clear of the staging area");
+  const int lim = sl_cnt < WINDOW_P ? sl_cnt : WINDOW_P;
   // ---- the query's two images, built here from its descriptor, column norms and sector key (what sc_img_query_kernel and a
   // key-image kernel used to write to global memory for this kernel to copy back): wave 0 the normalised columns and the
   // column mask, wave 1 the doubled hi / lo key, into the staging area; then every thread a share of the two displaced image
@@ -143,21 +233,24 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
     dev::KeySplit ksplit{};
     if (wave == 0) {
       bool nonzero = false, bad = false;
-      if (lane < NS) dev::normalise_column(a.qdesc + (int64_t)qi * DS + lane * NR, a.qnorm[(int64_t)qi * NS + lane], &st[lane * NR], nonzero, bad);
+      if (lane < NS) dev::normalise_column_regs(qcol, qn, &st[lane * NR], nonzero, bad);
       u64 m = __ballot(nonzero && lane < NS);
       if (__ballot(bad && lane < NS)) m |= kNonFinite;
       if (lane == 0) *s_qm = m;
     } else if (wave == 1) {
-      ksplit = win::query_keys_stage(lane < NS ? a.qvkey[(int64_t)qi * NS + lane] : 0.0, st2, lane);
+      ksplit = win::query_keys_stage(lane < NS ? qv : 0.0, st2, lane);
     }
-    __syncthreads();
+    barrier(WP_PROLOGUE);
     dev::img_query_image(st, *s_qm, reinterpret_cast<uint4 *>(smem), threadIdx.x, 256);
-    win::query_keys_copies(st2, smem + FILTER_QIMG_BYTES, threadIdx.x, 256);
+    win::query_keys_copies_256(st2, smem + FILTER_QIMG_BYTES, threadIdx.x);
     if (wave == 1) win::query_keys_norms(ksplit, smem + FILTER_QIMG_BYTES, lane);
   }
-  __syncthreads();
+  if ((int)threadIdx.x < lim) s_slot[threadIdx.x] = (int)rec0.y;
+  if ((int)threadIdx.x + 256 < lim) s_slot[threadIdx.x + 256] = (int)rec1.y;
+  barrier(WP_PROLOGUE);
+  if ((int)threadIdx.x < lim) s_lb[threadIdx.x] = __uint_as_float(rec0.x);
+  if ((int)threadIdx.x + 256 < lim) s_lb[threadIdx.x + 256] = __uint_as_float(rec1.x);
   const int n = lane & 31, hh = lane >> 5;
-  const RescoreEntry *sl = a.slist + (int64_t)qi * RESCORE_SHORTLIST_CAP;
   const u64 qm = *reinterpret_cast<const u64 *>(smem + FILTER_QIMG_MASK_OFF);
   const float nq_key = *reinterpret_cast<const float *>(smem + FILTER_QIMG_BYTES + QK_NORM);
   const float uq_key = *reinterpret_cast<const float *>(smem + FILTER_QIMG_BYTES + QK_NORM + 4);
@@ -175,7 +268,10 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   // one group of 32 short-list entries (lane n and n + 32: entry at list position pos_of(); have = the lane has one, else it
   // shadows position pos_any): writes the record, returns the upper bound of the pair distance the record implies
   auto do_group = [&](auto pos_of, bool have, int pos_any) -> float {
-    const int64_t slot = sl[have ? pos_of() : pos_any].slot;
+    const int64_t slot = s_slot[have ? pos_of() : pos_any];
+    // the entry's column mask and key norms go out with the key rows, in front of the K loop (two registers across it)
+    const u64 em = a.cmask[slot];
+    const float2 en = reinterpret_cast<const float2 *>(a.vk_n)[slot];
 
     // ---- alignment: 2 tiles x (hi*hi + hi*lo + lo*hi) x 4 K-steps ----
     floatx16 k0 = {0}, k1 = {0};
@@ -203,7 +299,9 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
     }
     u64 win;    // the union of the windows of the admissible alignments
     int kstar;  // the alignment when exactly one shift is admissible, else -1
-    win::alignment_of(k0, k1, nq_key, uq_key, reinterpret_cast<const float2 *>(a.vk_n)[slot], hh, win, kstar);
+    // (the lean forms of sc_window_dev.h, here and in the epilogue: the same values as the plain ones with a third of the VALU
+    // instructions -- the kernel's time follows its instruction count, not the length of a workgroup's chain: file header)
+    win::alignment_of<true>(k0, k1, nq_key, uq_key, en, hh, win, kstar);
 
     // ---- the 60 correlation values of the two images (the direct filter's GEMM) ----
     __builtin_amdgcn_sched_barrier(0);  // keep the loads below from being hoisted over the alignment (register pressure)
@@ -240,19 +338,17 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
 
     // ---- epilogue: max of S_k / n_eff(k) over the window of k* (n_eff from the two column masks, as the filter) ----
     __builtin_amdgcn_sched_barrier(0);
-    const u64 em = a.cmask[slot];
     // (the query mask as a value the compiler cannot follow: its rotations are then formed here, per group, instead of once
     // before pass 2 -- a dozen registers that did not fit and were spilled)
     u64 qmg = qm;
     asm volatile("" : "+v"(qmg));
-    const float pv = win::preview_of(acc0, acc1, qmg, em, win, kstar, hh);
+    const float pv = win::preview_of<true>(acc0, acc1, qmg, em, win, kstar, hh);
     if (have && hh == 0) {
       const int pos = pos_of();
       WindowPreview o;
       o.pv = pv;
       o.ks = kstar;
       a.out[(int64_t)qi * WINDOW_P + pos] = o;
-      s_slot[pos] = (int)slot;
       s_pv[pos] = pv;
       s_ks[pos] = kstar;
     }
@@ -263,7 +359,6 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
   // of the query, then the survivor list and its header.  tau_head: the k-th smallest upper bound of the head (+inf: not
   // known) -- at least k upper bounds lie at or below it, so the k-th smallest of all is among those ----
   auto write_list = [&](float tau_head, int n2) {
-    const int lim = sl_cnt < WINDOW_P ? sl_cnt : WINDOW_P;
     const int nh = lim < WINDOW_HEAD ? lim : WINDOW_HEAD;
     const unsigned long long below = (1ull << lane) - 1ull;
     // the positions with a record, 64 at a time: the head, then what pass 2 admitted (s_pos); f(position, the lane has one)
@@ -337,60 +432,48 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
     float ub = INFINITY;
     if (wave * 32 < cnt1) ub = do_group([&] { return wave * 32 + lane_again(); }, wave * 32 + n < cnt1, wave * 32);
     if (hh == 0) s_ub[wave * 32 + n] = ub;
-    __syncthreads();
-    // the head's filter bounds for the tail: requested by the wave that runs it, here, so that no group waits for them
-    float lbh0 = INFINITY, lbh1 = INFINITY;
-    if (wave == 0) {
-      if (lane < cnt1) lbh0 = sl[lane].lb;
-      if (lane + 64 < cnt1) lbh1 = sl[lane + 64].lb;
-    }
+    barrier(WP_GROUP1);
     if (sl_cnt <= WINDOW_HEAD) {  // uniform
-      if (wave == 0) {
-        s_lb[lane] = lbh0;
-        s_lb[lane + 64] = lbh1;
-        dev::wave_lds_fence();
-        write_list(INFINITY, 0);
-      }
+      if (wave == 0) write_list(INFINITY, 0);
+      lap(WP_TAIL);
+      prof_flush();
       return;
     }
 
     // ---- the k-th smallest upper bound of the head: an upper bound of the final k-th best distance.  Only entries whose
-    // filter bound does not exceed it can matter to the re-scoring kernel (whose own bound is at least as tight) ----
+    // filter bound does not exceed it can matter to the re-scoring kernel (whose own bound is at least as tight).  Rank by
+    // counting, shared by the workgroup: wave w ranks its own 32 values, the two lane halves against one half of the head
+    // each (every wave used to rank all 128 for itself, and only wave 0 wanted the result) ----
     {
-      const float v0 = s_ub[lane], v1 = s_ub[lane + 64];
-      int r0 = 0, r1 = 0;
-      const float4 *u4 = reinterpret_cast<const float4 *>(s_ub);
+      const int p = wave * 32 + n;
+      const float v = s_ub[p];
+      int r = 0;
+      const float4 *u4 = reinterpret_cast<const float4 *>(s_ub) + (WINDOW_HEAD / 8) * hh;
 #pragma unroll 4
-      for (int j = 0; j < WINDOW_HEAD / 4; j++) {
+      for (int j = 0; j < WINDOW_HEAD / 8; j++) {
         const float4 u = u4[j];
         const float x[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-          const int idx = 4 * j + e;
-          r0 += (x[e] < v0 || (x[e] == v0 && idx < lane)) ? 1 : 0;
-          r1 += (x[e] < v1 || (x[e] == v1 && idx < lane + 64)) ? 1 : 0;
+          const int idx = (WINDOW_HEAD / 2) * hh + 4 * j + e;
+          r += (x[e] < v || (x[e] == v && idx < p)) ? 1 : 0;
         }
       }
-      const int want = a.k - 1;  // 0 <= want < WINDOW_HEAD (k <= RSX_SC_MAX_TOPK)
-      const unsigned long long b0 = __ballot(r0 == want), b1 = __ballot(r1 == want);
-      const float c0 = __shfl(v0, b0 ? __ffsll((long long)b0) - 1 : 0), c1 = __shfl(v1, b1 ? __ffsll((long long)b1) - 1 : 0);
-      tau_ub = b0 ? c0 : c1;  // ranks are a permutation of 0..127: exactly one of the two ballots has a bit
+      r += __shfl_xor(r, 32);
+      // 0 <= k - 1 < WINDOW_HEAD (k <= RSX_SC_MAX_TOPK) and the ranks are a permutation of 0..127: one lane of the workgroup
+      if (hh == 0 && r == a.k - 1) s_tau = v;
     }
-    if (wave == 0) {
-      s_lb[lane] = lbh0;
-      s_lb[lane + 64] = lbh1;
-    }
+    barrier(WP_RANK);
+    tau_ub = s_tau;
   }
   // ---- pass 2: list positions WINDOW_HEAD .. WINDOW_P - 1 whose bound can still matter; the others get "no record" ----
   if (wave == 0) {
     int n2 = 0;
-    const int lim = sl_cnt < WINDOW_P ? sl_cnt : WINDOW_P;
     for (int p0 = WINDOW_HEAD; p0 < lim; p0 += 64) {
       const int pos = p0 + lane;
       bool pass = false;
       if (pos < lim) {
-        const float lb = sl[pos].lb;
-        s_lb[pos] = lb;
+        const float lb = s_lb[pos];
         pass = !((double)lb - a.eps > (double)tau_ub);  // NaN / -inf bounds: always
         if (!pass) {
           WindowPreview o;
@@ -403,19 +486,19 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
       if (pass) s_pos[n2 + __popcll(bal & ((1ull << lane) - 1ull))] = pos;
       n2 += __popcll(bal);
     }
-    if (lane == 0) {
-      s_n2 = n2;
-      s_tau = tau_ub;
-    }
+    if (lane == 0) s_n2 = n2;
   }
-  __syncthreads();
+  barrier(WP_SELECT);
   const int n2 = s_n2;
   for (int g = wave; g * 32 < n2; g += 4) {
     const bool have = g * 32 + n < n2;
     (void)do_group([&] { return s_pos[g * 32 + lane_again()]; }, have, s_pos[g * 32]);  // (only lanes that have one ask)
+    prof_groups2++;
   }
-  __syncthreads();
+  barrier(WP_GROUP2);
   if (wave == 0) write_list(s_tau, n2);
+  lap(WP_TAIL);
+  prof_flush();
 }
 
 }  // namespace
@@ -445,8 +528,33 @@ int launch_window(const DbView &db, const QueryView &q, const RescoreEntry *slis
   a.surv = surv;
   a.eps = eps;
   a.k = k < 1 ? 1 : (k > WINDOW_HEAD ? WINDOW_HEAD : k);
+  a.prof = nullptr;
+#ifdef RSX_WINDOW_PROF
+  constexpr size_t kProfWords = (size_t)WIN_PROF_COPIES * 4 * WIN_PROF_WORDS;
+  static unsigned long long *d_prof = nullptr;  // (a profiling build: one device, one launch at a time, never freed)
+  if (!d_prof) RSX_HIP(hipMalloc(reinterpret_cast<void **>(&d_prof), kProfWords * 8));
+  RSX_HIP(hipMemsetAsync(d_prof, 0, kProfWords * 8, s));
+  a.prof = d_prof;
+#endif
   hipLaunchKernelGGL(sc_window_kernel, dim3((unsigned)q.nq), dim3(256), W_LDS, s, a);
   RSX_HIP(hipGetLastError());
+#ifdef RSX_WINDOW_PROF
+  {
+    static unsigned long long h[kProfWords];
+    RSX_HIP(hipMemcpyAsync(h, d_prof, kProfWords * 8, hipMemcpyDeviceToHost, s));
+    RSX_HIP(hipStreamSynchronize(s));
+    static const char *const names[WP_TOTAL + 1] = {"prologue", "pass-1 group", "ranking", "pass-2 selection", "pass-2 groups", "tail", "barriers", "total"};
+    for (int w = 0; w < 4; w++) {
+      double v[WIN_PROF_WORDS] = {0};
+      for (int c = 0; c < WIN_PROF_COPIES; c++)
+        for (int i = 0; i < WIN_PROF_WORDS; i++) v[i] += (double)h[((size_t)c * 4 + w) * WIN_PROF_WORDS + i];
+      if (v[WP_COUNT] <= 0) continue;
+      fprintf(stderr, "[sc_window prof] nq %d wave %d (cycles per workgroup, %.0f reported, %.3f pass-2 groups):", (int)q.nq, w, v[WP_COUNT], v[WP_GROUPS2] / v[WP_COUNT]);
+      for (int r = 0; r <= WP_TOTAL; r++) fprintf(stderr, "  %s %.0f", names[r], v[r] / v[WP_COUNT]);
+      fprintf(stderr, "\n");
+    }
+  }
+#endif
   return RSX_OK;
 }
 

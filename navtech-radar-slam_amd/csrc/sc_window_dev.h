@@ -61,6 +61,17 @@ __device__ __forceinline__ void query_keys_copies(const _Float16 (*st)[128], cha
     *reinterpret_cast<_Float16 *>(out + part * QK_LO + c * QK_COPY + el * 2) = v16;
   }
 }
+// the same copies by a workgroup of 256 threads without the index divisions: 16 threads per (part, copy), nine elements each
+__device__ __forceinline__ void query_keys_copies_256(const _Float16 (*st)[128], char *out, int tid) {
+  static_assert(QK_COPY / 2 == 16 * 9, "nine elements per thread");
+  const int part = tid >> 7, c = (tid >> 4) & 7;
+  _Float16 *o = reinterpret_cast<_Float16 *>(out + part * QK_LO + c * QK_COPY);
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    const int el = (tid & 15) + 16 * j, src = c + el;  // copy c holds q2[c + el]
+    o[el] = src < 2 * NS ? st[part][src] : (_Float16)0.0f;
+  }
+}
 __device__ __forceinline__ void query_keys_norms(const dev::KeySplit &k, char *out, int lane) {
   if (lane < 4) *reinterpret_cast<float *>(out + QK_NORM + lane * 4) = lane == 0 ? k.nrm : (lane == 1 ? k.unrm : 0.0f);
 }
@@ -69,7 +80,7 @@ __device__ __forceinline__ void query_keys_norms(const dev::KeySplit &k, char *o
 // whose KC is within the error bound of the maximum (bit m of adm = shift m); all 60 when the keys cannot be compared here
 // (non-finite, too large, too lopsided: see split_key / `balanced`).  win = the union of their windows; kstar = the alignment
 // when exactly one shift is admissible, else -1
-// LEAN (sc_q1.hip): the lane halves are joined with v_permlane32_swap instead of four ds_bpermute round trips
+// LEAN (sc_q1.hip, sc_window.hip): the lane halves are joined with v_permlane32_swap instead of four ds_bpermute round trips
 template <bool LEAN = false>
 __device__ __forceinline__ void alignment_of(const floatx16 &k0, const floatx16 &k1, float nq_key, float uq_key, float2 en,
                                              int hh, u64 &win, int &kstar) {
@@ -138,7 +149,7 @@ __device__ __forceinline__ void alignment_of(const floatx16 &k0, const floatx16 
 // epilogue of the image GEMM: max of S_k / n_eff(k) over the window(s) (n_eff from the two column masks, as the filter);
 // returns the preview pv (NaN: non-finite data; +inf: no effective column in the window) and, for a unique alignment, ORs
 // into kstar (bits 8..14) which of the 7 window shifts can be the minimum at all.  acc0 / acc1 are overwritten.
-// LEAN (sc_q1.hip, whose epilogue sits on the critical path of every tile): the same values with fewer instructions -- a query
+// LEAN (sc_q1.hip, whose epilogue sits on the critical path of every tile, and sc_window.hip since round 10): the same values with fewer instructions -- a query
 // without an empty column meets every entry with n_eff(k) = the entry's column count at every shift (one reciprocal per
 // entry instead of two funnel shifts and two popcounts per value), and the shift mask comes from ONE 60-bit mask of the
 // values above the line, rotated by the window start, instead of a window position per value
