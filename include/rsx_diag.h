@@ -36,6 +36,15 @@ int rsx_cen2018_gauss_weights(int32_t sigma_gauss, float *out, int32_t max);
 int rsx_cen2018_debug_image(rsx_cen2018 *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cen2018_params *params,
                             float *out_mean, float *out_sigma, float *out_p, float *out_y);
 
+/* Parity helper of loop verification (csrc/loopverify.hip): the two downsampled clouds of the SAME launch rsx_loop_verify makes
+ * -- source = keyframe curr_idx alone, target = loop_idx +- params->history_keyframe_search_num, both moved by root_pose6 and
+ * VoxelGrid-filtered by one cooperative kernel on two handles -- instead of the ICP over them (which shows them only through
+ * a pose).  Arguments as rsx_loop_verify (params may be null: the defaults).  *n_src / *n_tgt = the full counts (rsx_loop_verify's
+ * n_source / n_target; 0 for an empty slice); the first min(count, max) points of each, packed x, y, z, intensity, go to
+ * out_src / out_tgt (either may be null with max 0).  Synchronous. */
+int rsx_loop_verify_clouds(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const double *root_pose6, const rsx_loop_verify_params *params,
+                           float *out_src, int64_t max_src, int64_t *n_src, float *out_tgt, int64_t max_tgt, int64_t *n_tgt);
+
 /* Introspection of the candidate stage (host only, no device needed): the ring-key search tree the detector would build
  * over `n` keys of 20 floats -- nanoflann's tree (KDTreeVectorOfVectorsAdaptor.h:49-117, leaf size 10, Scancontext.cpp:284,356)
  * rebuilt node for node, because the order in which tied neighbours come back is the order of its leaves.  out_vind[n] =

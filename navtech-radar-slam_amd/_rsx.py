@@ -234,7 +234,7 @@ SYMBOLS = [
     "rsx_voxelgrid_create", "rsx_voxelgrid_destroy", "rsx_voxelgrid_filter", "rsx_sc_add_points_downsampled",
     "rsx_icp_default_params", "rsx_icp_create", "rsx_icp_destroy", "rsx_icp_align",
     "rsx_kfstore_create", "rsx_kfstore_destroy", "rsx_kfstore_add", "rsx_kfstore_add_device", "rsx_kfstore_size", "rsx_kfstore_get",
-    "rsx_loop_verify_default_params", "rsx_loop_submap", "rsx_loop_verify", "rsx_kfstore_build_map", "rsx_sc_add_keyframe",
+    "rsx_loop_verify_default_params", "rsx_loop_submap", "rsx_loop_verify", "rsx_loop_verify_clouds", "rsx_kfstore_build_map", "rsx_sc_add_keyframe",
 ]
 
 
@@ -435,7 +435,8 @@ def lib():
         L.rsx_loop_verify_default_params.argtypes = [C.POINTER(LoopVerifyParams)]
         L.rsx_loop_submap.argtypes = [vp, i32, i32, vp, C.c_float, vp, i64, C.POINTER(i64)]
         L.rsx_loop_verify.argtypes = [vp, i32, i32, vp, C.POINTER(LoopVerifyParams), C.POINTER(LoopVerifyResult)]
-        L.rsx_kfstore_build_map.argtypes = [vp, vp, i64, i32, C.c_float, vp, i64, C.POINTER(i64)]
+        L.rsx_loop_verify_clouds.argtypes = [vp, i32, i32, vp, C.POINTER(LoopVerifyParams), vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)]
+        L.rsx_kfstore_build_map.argtypes =[vp, vp, i64, i32, C.c_float, vp, i64, C.POINTER(i64)]
         L.rsx_sc_add_keyframe.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, i32, C.c_float, C.POINTER(i32)]
         _lib = L
     return _lib

@@ -168,6 +168,51 @@ int submap_device(rsx_kfstore *h, rsx_voxelgrid *vg, int64_t key, int64_t size, 
   return RSX_OK;
 }
 
+// the VoxelGrid launch of a verification (doICPVirtualRelative, PGO.cpp:361-362): source = keyframe curr alone, target =
+// loop +- history_keyframe_search_num, both moved by the ONE root pose T and filtered by ONE cooperative kernel on stream s,
+// into the store's two VoxelGrid handles; an empty slice (nearKeyframes->empty()) is no job.  The caller holds the mutexes of
+// both handles.  -> per cloud (0 source, 1 target): the slice's size, and the output and its count in device memory (null
+// for an empty slice).  rsx_loop_verify and the diagnostic rsx_loop_verify_clouds both launch through here.
+struct PairClouds {
+  int64_t np[2];
+  const float *d_cloud[2];
+  const long long *d_cnt[2];
+};
+int enqueue_pair(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const Mat34 &T, const rsx_loop_verify_params &p, hipStream_t s,
+                 PairClouds *out) {
+  int64_t first[2];
+  submap_slice(h, curr_idx, 0, &first[0], &out->np[0]);
+  submap_slice(h, loop_idx, p.history_keyframe_search_num, &first[1], &out->np[1]);
+  rsx_voxelgrid *vgs[2] = {h->vg_s.get(), h->vg_t.get()};
+  rsx::vg::JobIn jobs[2];
+  rsx::vg::DeviceCloud dc[2];
+  int which[2], nj = 0;
+  for (int c = 0; c < 2; c++) {
+    out->d_cloud[c] = nullptr;
+    out->d_cnt[c] = nullptr;
+    if (out->np[c] > 0) {
+      jobs[nj] = rsx::vg::JobIn{vgs[c], h->clouds.as<float4>() + first[c], out->np[c], 16, 12, &T, p.leaf, out->np[c]};
+      which[nj++] = c;
+    }
+  }
+  if (nj) RSX_TRY(rsx::vg::enqueue(jobs, nj, s, dc));
+  for (int j = 0; j < nj; j++) {
+    out->d_cloud[which[j]] = dc[j].d_out;
+    out->d_cnt[which[j]] = dc[j].d_count;
+  }
+  return RSX_OK;
+}
+
+// arguments of a verification -> the parameters in force, the keyframe indices checked (the caller holds the store's mutex)
+int verify_args(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const rsx_loop_verify_params *params, rsx_loop_verify_params *p) {
+  rsx_loop_verify_default_params(p);
+  if (params) *p = *params;
+  if (p->history_keyframe_search_num < 0 || !(p->leaf > 0.0f)) return fail(RSX_ERR_BAD_ARG, "bad loop-verification params");
+  const int64_t nkf = (int64_t)h->off.size() - 1;
+  if (loop_idx < 0 || loop_idx >= nkf || curr_idx < 0 || curr_idx >= nkf) return fail(RSX_ERR_RANGE, "keyframe index out of range (%lld stored)", (long long)nkf);
+  return RSX_OK;
+}
+
 }  // namespace
 
 namespace rsx {
@@ -317,46 +362,24 @@ int rsx_loop_verify(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const do
                     rsx_loop_verify_result *out) try {
   if (!h || !root_pose6 || !out) return fail(RSX_ERR_BAD_ARG, "null arg");
   rsx_loop_verify_params p;
-  rsx_loop_verify_default_params(&p);
-  if (params) p = *params;
-  if (p.history_keyframe_search_num < 0 || !(p.leaf > 0.0f)) return fail(RSX_ERR_BAD_ARG, "bad loop-verification params");
   std::memset(out, 0, sizeof(*out));
   std::lock_guard<std::mutex> lk(h->mu);
+  RSX_TRY(verify_args(h, loop_idx, curr_idx, params, &p));
   RSX_HIP(hipSetDevice(h->device));
-  const int64_t nkf = (int64_t)h->off.size() - 1;
-  if (loop_idx < 0 || loop_idx >= nkf || curr_idx < 0 || curr_idx >= nkf) return fail(RSX_ERR_RANGE, "keyframe index out of range (%lld stored)", (long long)nkf);
   const Mat34 T = pose_matrix(root_pose6);  // the ONE root pose both clouds are moved by (PGO.cpp:340,361-362)
   // two launches and one read-back: (1) both submaps -- source = keyframe curr alone (PGO.cpp:361), target = loop +- 25
   // (PGO.cpp:362) -- transformed by the root pose and VoxelGrid-filtered by ONE cooperative kernel, their sizes left in device
   // memory; (2) the persistent ICP kernel, which reads the sizes there.  All on the ICP handle's stream.
-  int64_t first[2], np[2];
-  submap_slice(h, curr_idx, 0, &first[0], &np[0]);
-  submap_slice(h, loop_idx, p.history_keyframe_search_num, &first[1], &np[1]);
-  rsx_voxelgrid *vgs[2] = {h->vg_s.get(), h->vg_t.get()};
   rsx_icp_result ir;
   int64_t ns = 0, nt = 0;
   {
     std::lock_guard<std::mutex> lks(rsx::vg::mutex_of(h->vg_s.get()));
     std::lock_guard<std::mutex> lkt(rsx::vg::mutex_of(h->vg_t.get()));
     std::lock_guard<std::mutex> lki(rsx::icp::mutex_of(h->icp.get()));
-    hipStream_t s = rsx::icp::stream_of(h->icp.get());
-    rsx::vg::JobIn jobs[2];
-    rsx::vg::DeviceCloud dc[2];
-    int which[2], nj = 0;
-    for (int c = 0; c < 2; c++)
-      if (np[c] > 0) {
-        jobs[nj] = rsx::vg::JobIn{vgs[c], h->clouds.as<float4>() + first[c], np[c], 16, 12, &T, p.leaf, np[c]};
-        which[nj++] = c;
-      }
-    if (nj) RSX_TRY(rsx::vg::enqueue(jobs, nj, s, dc));
-    const float *d_cloud[2] = {nullptr, nullptr};
-    const long long *d_cnt[2] = {nullptr, nullptr};
-    for (int j = 0; j < nj; j++) {
-      d_cloud[which[j]] = dc[j].d_out;
-      d_cnt[which[j]] = dc[j].d_count;
-    }
-    RSX_TRY(rsx::icp::align_device_counts_locked(h->icp.get(), d_cloud[0], np[0], d_cnt[0], 16, d_cloud[1], np[1], d_cnt[1], 16, &p.icp, nullptr, &ir,
-                                                 &ns, &nt));
+    PairClouds pc;
+    RSX_TRY(enqueue_pair(h, loop_idx, curr_idx, T, p, rsx::icp::stream_of(h->icp.get()), &pc));
+    RSX_TRY(rsx::icp::align_device_counts_locked(h->icp.get(), pc.d_cloud[0], pc.np[0], pc.d_cnt[0], 16, pc.d_cloud[1], pc.np[1], pc.d_cnt[1], 16,
+                                                 &p.icp, nullptr, &ir, &ns, &nt));
   }
   out->n_source = ns;
   out->n_target = nt;
@@ -386,6 +409,39 @@ int rsx_loop_verify(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const do
   }
   out->relative[12] = out->relative[13] = out->relative[14] = 0.0;
   out->relative[15] = 1.0;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_loop_verify_clouds(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const double *root_pose6, const rsx_loop_verify_params *params,
+                           float *out_src, int64_t max_src, int64_t *n_src, float *out_tgt, int64_t max_tgt, int64_t *n_tgt) try {
+  if (!h || !root_pose6 || !n_src || !n_tgt || (!out_src && max_src > 0) || (!out_tgt && max_tgt > 0)) return fail(RSX_ERR_BAD_ARG, "null arg");
+  *n_src = *n_tgt = 0;
+  rsx_loop_verify_params p;
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_TRY(verify_args(h, loop_idx, curr_idx, params, &p));
+  RSX_HIP(hipSetDevice(h->device));
+  const Mat34 T = pose_matrix(root_pose6);
+  // the launch of rsx_loop_verify, on the stream it uses, then the two clouds instead of the ICP
+  std::lock_guard<std::mutex> lks(rsx::vg::mutex_of(h->vg_s.get()));
+  std::lock_guard<std::mutex> lkt(rsx::vg::mutex_of(h->vg_t.get()));
+  std::lock_guard<std::mutex> lki(rsx::icp::mutex_of(h->icp.get()));
+  hipStream_t s = rsx::icp::stream_of(h->icp.get());
+  PairClouds pc;
+  RSX_TRY(enqueue_pair(h, loop_idx, curr_idx, T, p, s, &pc));
+  long long cnt[2] = {0, 0};
+  for (int c = 0; c < 2; c++)
+    if (pc.d_cnt[c]) RSX_HIP(hipMemcpyAsync(&cnt[c], pc.d_cnt[c], sizeof(cnt[c]), hipMemcpyDeviceToHost, s));
+  RSX_HIP(hipStreamSynchronize(s));
+  if (cnt[0] < 0 || cnt[1] < 0) return fail(RSX_ERR_HIP, "a grid barrier of the cooperative VoxelGrid kernel gave up after 5 s: its workgroups were not all resident");
+  float *outs[2] = {out_src, out_tgt};
+  const int64_t maxs[2] = {max_src, max_tgt};
+  for (int c = 0; c < 2; c++) {
+    const int64_t w = cnt[c] < maxs[c] ? cnt[c] : maxs[c];
+    if (w > 0) RSX_HIP(hipMemcpyAsync(outs[c], pc.d_cloud[c], (size_t)w * 16, hipMemcpyDeviceToHost, s));
+  }
+  RSX_HIP(hipStreamSynchronize(s));
+  *n_src = cnt[0];
+  *n_tgt = cnt[1];
   return RSX_OK;
 } RSX_CATCH_ALL
 

@@ -21,6 +21,10 @@
 //        walk their sub-tiles in order; ranks inside a 64-element chunk by eight ballots) -> barrier.  Stable, so a voxel's
 //        points stay in input order -- the order their floats are added in.
 //        heads -> per-workgroup counts -> barrier -> output slots; the thread of a voxel's first point sums its points
+//        Up to CO_MAX_W x 4 wavefronts x CO_CH x 64 = 128 x 4 x 8 x 64 = 262 144 points a wavefront keeps its share in registers
+//        (`cached`: one fetch per pass, ballot head masks, centroid_chunk); from 262 145 points on -- earlier where the device
+//        keeps fewer than 2 x 128 workgroups resident and resident_half caps W -- shares are walked chunk by chunk, fetched
+//        twice a pass, heads by head_of, one thread per voxel (`centroid`).  tests/test_gpu_voxelgrid_paths.py runs both sides.
 //   Rounds 1-4 ran this as 14 launches around two rocPRIM calls (radix_sort_pairs, exclusive_scan) and a host
 //   synchronisation for the count; the count now stays on the device for whoever runs next (icp.hip).
 #include <hip/hip_runtime.h>

@@ -70,6 +70,18 @@ class KeyframeStore:
                 "xyz_rpy": np.array([r.x, r.y, r.z, r.roll, r.pitch, r.yaw], dtype=np.float32),
                 "relative": np.array(r.relative, dtype=np.float64).reshape(4, 4), "n_source": r.n_source, "n_target": r.n_target}
 
+    def verify_clouds(self, loop_idx, curr_idx, root_pose):
+        """the (source, target) clouds the VoxelGrid launch of verify(loop_idx, curr_idx, root_pose) hands its ICP
+        (rsx_diag.h: rsx_loop_verify_clouds) -> two (m, 4) float32 arrays"""
+        rp = np.ascontiguousarray(root_pose, dtype=np.float64).reshape(6)
+        _, npnt = self.size()
+        src = np.zeros((max(npnt, 1), 4), dtype=np.float32)
+        tgt = np.zeros((max(npnt, 1), 4), dtype=np.float32)
+        ns, nt = C.c_int64(), C.c_int64()
+        check(self._L.rsx_loop_verify_clouds(self._h, loop_idx, curr_idx, rp.ctypes.data, C.byref(self.params), src.ctypes.data,
+                                             C.c_int64(src.shape[0]), C.byref(ns), tgt.ctypes.data, C.c_int64(tgt.shape[0]), C.byref(nt)))
+        return src[:ns.value].copy(), tgt[:nt.value].copy()
+
     def build_map(self, poses, skip=2, leaf=0.4):
         ps = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 6)
         _, npnt = self.size()

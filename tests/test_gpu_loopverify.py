@@ -102,6 +102,73 @@ def test_verify_matches_oracle(lv, oracle, drive, loop, curr, hist):
         assert got["accepted"]
 
 
+ROOT_OFFSET = np.array([0, 0, 0.3, 0.01, -0.02, 0.0])                  # makes a drive's planar pose a full 6-DoF root pose
+
+
+@pytest.mark.parametrize("loop,curr,hist", [(2, 50, 25), (2, 50, 0), (60, 3, 25)])
+def test_verify_clouds_bit_identical(lv, oracle, drive, loop, curr, hist):
+    """the two clouds of the verification's ONE VoxelGrid launch (two jobs, two handles, two barrier blocks; the diagnostic
+    rsx_loop_verify_clouds launches through the helper rsx_loop_verify uses), each bit for bit: the ICP pose above would
+    not show a few wrong centroids in a cloud of the right size"""
+    clouds, pose6 = drive
+    kf = lv.KeyframeStore()
+    for c in clouds:
+        kf.add(c)
+    kf.params.history_keyframe_search_num = hist
+    root = pose6[loop] + ROOT_OFFSET
+    src, tgt = kf.verify_clouds(loop, curr, root)
+    want_s = oracle.loop_submap(clouds, curr, 0, root)
+    want_t = oracle.loop_submap(clouds, loop, hist, root)
+    assert len(want_s) > 100 and len(want_t) >= len(want_s) and (hist == 0 or len(want_t) > 4096)
+    assert same_set(src, want_s) and same_set(tgt, want_t)
+    got = kf.verify(loop, curr, root)
+    assert (got["n_source"], got["n_target"]) == (len(src), len(tgt))
+    assert all(same_set(a, b) for a, b in zip(kf.verify_clouds(loop, curr, root), (src, tgt)))   # same store, same bytes
+
+
+def test_verify_clouds_one_job_leaves_early(lv, oracle, drive):
+    """the two jobs of a launch in different regimes: an all-NaN current keyframe sends job 0 through the early exit while job 1
+    runs its barriers (source empty, target exact), and the store answers an ordinary pair afterwards"""
+    clouds, pose6 = drive
+    cl = list(clouds)
+    cl[50] = np.full_like(clouds[50], np.nan)
+    kf = lv.KeyframeStore()
+    for c in cl:
+        kf.add(c)
+    root = pose6[2] + ROOT_OFFSET
+    src, tgt = kf.verify_clouds(2, 50, root)
+    assert len(oracle.loop_submap(cl, 50, 0, root)) == 0 and len(src) == 0
+    assert same_set(tgt, oracle.loop_submap(cl, 2, 25, root))
+    src, tgt = kf.verify_clouds(2, 49, root)
+    assert len(src) > 100 and same_set(src, oracle.loop_submap(cl, 49, 0, root)) and same_set(tgt, oracle.loop_submap(cl, 2, 25, root))
+
+
+@pytest.mark.parametrize("leaf", [0.01, 0.1])
+def test_verify_clouds_one_job_overflows(lv, oracle, drive, leaf):
+    """a far point in the current keyframe under a small leaf: job 0 takes the overflow guard (its output is its transformed
+    input, in input order); the target is the one the untouched drive gives.  Under 0.01 m the +-25 submap is too wide for
+    2^31 voxels as well (both jobs leave early); under 0.1 m job 1 sorts while job 0 leaves"""
+    clouds, pose6 = drive
+    cl = list(clouds)
+    cl[50] = clouds[50].copy()
+    cl[50][7, :3] = [3e4, 3e4, 3e3]
+    kf = lv.KeyframeStore()
+    for c in cl:
+        kf.add(c)
+    kf.params.leaf = leaf
+    root = pose6[2] + ROOT_OFFSET
+    src, tgt = kf.verify_clouds(2, 50, root)
+    T = oracle.pose_matrix(root)                                        # local2global (PGO.cpp:210-217): float, left to right
+    x, y, z = cl[50][:, 0], cl[50][:, 1], cl[50][:, 2]
+    moved = np.stack([T[r, 0] * x + T[r, 1] * y + T[r, 2] * z + T[r, 3] for r in range(3)] + [cl[50][:, 3]], axis=1)
+    assert moved.dtype == np.float32 and len(cl[50]) > 100
+    assert same_set(src, moved) and same_set(src, oracle.loop_submap(cl, 50, 0, root, leaf=leaf))
+    want_t = oracle.loop_submap(clouds, 2, 25, root, leaf=leaf)
+    n_in = sum(len(c) for c in clouds[:28])
+    assert 4096 < len(want_t) < n_in if leaf == 0.1 else len(want_t) == n_in   # voxels shared: no overflow / the input itself
+    assert same_set(tgt, want_t)
+
+
 @pytest.mark.parametrize("sigma,accepted", [(0.38233837890625, True), (0.38433837890625, True), (0.38633837890625, False)])
 def test_fitness_at_the_gate(lv, oracle, drive, sigma, accepted):
     """the gate is fitness <= 0.3 (PGO.cpp:384): a revisit blurred until its fitness is 0.2976, 0.299994 and 0.3026.  The

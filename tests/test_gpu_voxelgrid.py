@@ -1,6 +1,10 @@
 """GPU parity of the VoxelGrid downsample (voxelgrid.hip through the C-ABI) against the oracle: float
 centroids bit-exact (same float operations in the same order), output order and count identical; and
-the fused downsample + ScanContext build against oracle downsample + oracle build."""
+the fused downsample + ScanContext build against oracle downsample + oracle build.
+
+The cooperative kernel changes path at 262 144 points: CO_MAX_W (128 workgroups) x 4 wavefronts x CO_CH (8 chunks in registers)
+x 64 lanes.  Every cloud here is below it; the clouds above it, the edges of the sort key's width, the one-workgroup kernel's
+padding edges, point layouts and max_out below the output count are in test_gpu_voxelgrid_paths.py."""
 import numpy as np
 import pytest
 
