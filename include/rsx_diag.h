@@ -22,6 +22,18 @@ extern "C" {
  * RSX_ERR_INTERNAL.  Needs no device. */
 int rsx_selftest_firewall(int kind);
 
+/* Self-test of the wavefront primitives every kernel shares (csrc/rsx_wave_dev.h): ONE launch of one wavefront runs each
+ * primitive on each of the n_cases (1 .. 4096) vectors of 64 lane values.  lanes[case][64] are 64-bit patterns; a primitive
+ * sees the view of its type: u64 = the pattern, f64 = its bits, u32 / i32 = the low word, f32 = the bits of the HIGH word.
+ * out[case][RSX_SELFTEST_WAVE_PRIMS][64] = what each lane ends with, as a 64-bit pattern (32-bit results zero-extended), in
+ * this order: 0 dpp quad_perm [1,0,3,2] (u32) | 1 dpp wave_shr:1 (u64) | 2 dpp wave_shl:1 (f64) | 3 dpp row_bcast:15 into
+ * rows 1 and 3 (f32) | 4 readlane 37 (u64) | 5 sum_i32 | 6 max_i32 | 7 max_u32 | 8 minmax_u64<min> | 9 minmax_u64<max> |
+ * 10 min_f32 | 11 sum_f64_rows_seq | 12 sum_f64_rows_pair | 13 sum_f32_bcast | 14 butterfly + (f64) | 15 butterfly_u64 max |
+ * 16 incl_add_u32 | 17 incl_max_u32 | 18, 19 incl_max_f64 forward, reverse, of |f64| under fmax.  The primitives assume
+ * that no lane holds a NaN.  Synchronous; host pointers. */
+#define RSX_SELFTEST_WAVE_PRIMS 20
+int rsx_selftest_wave(int device, const uint64_t *lanes, int32_t n_cases, uint64_t *out);
+
 /* Parity helper of the ORORA front end: Cartesian image `image` of the handle's last rsx_frontend_cartesian* call and its
  * 7 x 7 Gaussian-smoothed copy (W x W floats each; either pointer may be null) -- the smoothed image is otherwise only
  * observable through the descriptors that sample it (oracle/frontend_ref.c: feref_cart_remap, feref_blur). */

@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "keypoints_host.h"
+#include "rsx_wave_dev.h"
 
 namespace {
 
@@ -69,21 +70,6 @@ struct Scal {  // per image
 };
 static_assert(sizeof(Scal) == 64, "Scal layout");
 
-__device__ __forceinline__ int wave_sum_i32(int x) {  // every lane: the sum over the 64 lanes
-  x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, true);  // row_half_mirror
-  x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, true);  // row_mirror: every lane = its row's sum
-  return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48);
-}
-__device__ __forceinline__ int wave_max_i32(int x) {  // every lane: the maximum over the 64 lanes
-  auto mx = [](int a, int b) { return a > b ? a : b; };
-  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xf, 0xf, false));
-  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xf, 0xf, false));
-  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xf, 0xf, false));
-  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xf, 0xf, false));
-  return mx(mx(__builtin_amdgcn_readlane(x, 0), __builtin_amdgcn_readlane(x, 16)), mx(__builtin_amdgcn_readlane(x, 32), __builtin_amdgcn_readlane(x, 48)));
-}
 __device__ __forceinline__ unsigned ord_f32(float f) {
   const unsigned u = __float_as_uint(f);
   return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);  // negative: ~u, otherwise u | sign bit
@@ -203,7 +189,7 @@ __global__ __launch_bounds__(NT) void cen_stats(const uint8_t *__restrict__ imgs
   // D = the WAVEFRONT's largest difference (round 6; before: the block's, through LDS and a barrier -- every wavefront waited for the
   // slowest and then for the one lane that went back to its words).  A wavefront whose D lies below the image's contributes a
   // smaller g: harmless under the maximum.
-  const int D = wave_max_i32(dmax);
+  const int D = rsx::wave::max_i32(dmax);
   float mg = 0.0f;
   if (D > 0 && dmax == D) {  // (a thread or two per block; D = 0: every gradient of the block is exactly 0)
 #pragma unroll
@@ -222,8 +208,8 @@ __global__ __launch_bounds__(NT) void cen_stats(const uint8_t *__restrict__ imgs
       }
     }
   }
-  sb = (unsigned)wave_sum_i32((int)sb);
-  mg = __int_as_float(wave_max_i32(__float_as_int(mg)));  // non-negative floats order like their bits
+  sb = (unsigned)rsx::wave::sum_i32((int)sb);
+  mg = __int_as_float(rsx::wave::max_i32(__float_as_int(mg)));  // non-negative floats order like their bits
   if ((threadIdx.x & 63) == 0) {
     s_sum[threadIdx.x >> 6] = sb;
     s_max[threadIdx.x >> 6] = mg;
@@ -421,84 +407,9 @@ __device__ __forceinline__ double kmax(double a, double b) {
   return r;
 }
 __device__ __forceinline__ unsigned sc_lo(double k) { return (unsigned)(unsigned long long)__double_as_longlong(k); }
-// (bound_ctrl: a lane without a source reads 0 -- no register to clear in front of every DPP move)
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ double dpp_f64(double x) {  // lanes without a source (and rows outside ROWS): 0.0, below every key
-  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, ROWS, 0xf, ROWS == 0xf);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, ROWS, 0xf, ROWS == 0xf);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ unsigned dpp_u32(unsigned x) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xf, ROWS == 0xf);
-}
-__device__ __forceinline__ double readlane_f64(double x, int l) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// inclusive max-scan over the 64 lanes (REV: from lane 63 down): Hillis-Steele inside each row of 16 by DPP; across the rows
-// forward by the two row broadcasts of the ISA (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3), backward --
-// there is no broadcast of a row's FIRST lane -- by three v_readlane
-template <bool REV>
-__device__ __forceinline__ double wave_incl_max(double x, int lane) {
-  if constexpr (!REV) {
-    x = kmax(x, dpp_f64<0x111>(x));  // row_shr:1
-    x = kmax(x, dpp_f64<0x112>(x));  // row_shr:2
-    x = kmax(x, dpp_f64<0x114>(x));  // row_shr:4
-    x = kmax(x, dpp_f64<0x118>(x));  // row_shr:8
-    x = kmax(x, dpp_f64<0x142, 0xa>(x));  // row_bcast:15
-    x = kmax(x, dpp_f64<0x143, 0xc>(x));  // row_bcast:31
-    return x;
-  } else {
-    x = kmax(x, dpp_f64<0x101>(x));  // row_shl:1
-    x = kmax(x, dpp_f64<0x102>(x));
-    x = kmax(x, dpp_f64<0x104>(x));
-    x = kmax(x, dpp_f64<0x108>(x));
-    const double t3 = readlane_f64(x, 48), t2 = kmax(t3, readlane_f64(x, 32)), t1 = kmax(t2, readlane_f64(x, 16));
-    const double suf = lane >= 48 ? 0.0 : (lane >= 32 ? t3 : (lane >= 16 ? t2 : t1));
-    return kmax(x, suf);
-  }
-}
-__device__ __forceinline__ unsigned wave_incl_add(unsigned x, int) {
-  x += dpp_u32<0x111>(x);
-  x += dpp_u32<0x112>(x);
-  x += dpp_u32<0x114>(x);
-  x += dpp_u32<0x118>(x);
-  x += dpp_u32<0x142, 0xa>(x);
-  x += dpp_u32<0x143, 0xc>(x);
-  return x;
-}
-__device__ __forceinline__ unsigned wave_incl_max_u32(unsigned x) {
-  auto mx = [](unsigned a, unsigned b) { return a > b ? a : b; };
-  x = mx(x, dpp_u32<0x111>(x));
-  x = mx(x, dpp_u32<0x112>(x));
-  x = mx(x, dpp_u32<0x114>(x));
-  x = mx(x, dpp_u32<0x118>(x));
-  x = mx(x, dpp_u32<0x142, 0xa>(x));
-  x = mx(x, dpp_u32<0x143, 0xc>(x));
-  return x;
-}
-
-__device__ __forceinline__ unsigned wave_max_u32(unsigned x) {  // (uniform) the maximum over the 64 lanes
-  auto mx = [](unsigned a, unsigned b) { return a > b ? a : b; };
-  x = mx(x, (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-  x = mx(x, (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  x = mx(x, (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x141, 0xf, 0xf, false));  // row_half_mirror
-  x = mx(x, (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x140, 0xf, 0xf, false));  // row_mirror: every lane = its row's maximum
-  return mx(mx((unsigned)__builtin_amdgcn_readlane((int)x, 0), (unsigned)__builtin_amdgcn_readlane((int)x, 16)),
-            mx((unsigned)__builtin_amdgcn_readlane((int)x, 32), (unsigned)__builtin_amdgcn_readlane((int)x, 48)));
-}
-
-__device__ __forceinline__ unsigned long long dev_wave_max_u64(unsigned long long v) {  // (rare paths: shuffles)
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long x = ((unsigned long long)(unsigned)__shfl_xor((int)(unsigned)(v >> 32), o) << 32) | (unsigned long long)(unsigned)__shfl_xor((int)(unsigned)v, o);
-    v = x > v ? x : v;
-  }
-  return v;
-}
+// (the scans and DPP moves of rsx_wave_dev.h: a lane without a source reads 0 = 0.0, below every key)
+using rsx::wave::dpp;
+using rsx::wave::readlane;
 
 // facts of the thread's C pixels of one row; pixels past the row end are walls: non-neg, below every h
 template <int C>
@@ -537,7 +448,7 @@ __device__ __forceinline__ void row_chunk(RowLds<C, NT> &L, const uint8_t *__res
     }
   }
   const unsigned cnt = (unsigned)__popc(~R.neg & FULL);
-  const unsigned incl = wave_incl_add(cnt, lane);
+  const unsigned incl = rsx::wave::incl_add_u32(cnt);
   if (lane == 63) L.nn_cnt[NW + w] = incl;
   __syncthreads();
   unsigned before = 0;
@@ -572,10 +483,10 @@ __device__ __forceinline__ unsigned row_opens(RowLds<C, NT> &L, const RowChunk<C
   }
   const double btot = run;
   // across the threads of the wavefront (exclusive: shifted by one lane), then across the wavefronts through LDS
-  const double fi = wave_incl_max<false>(ftot, lane), bi = wave_incl_max<true>(btot, lane);
-  double fx = dpp_f64<0x138>(fi), bx = dpp_f64<0x130>(bi);  // wave_shr:1 / wave_shl:1 (lane 0 / 63: 0.0)
-  unsigned eprev = dpp_u32<0x138>((R.neg >> (C - 1)) & 1u);  // previous thread's last pixel neg
-  unsigned enext = dpp_u32<0x130>(R.neg & 1u);               // next thread's first pixel neg
+  const double fi = rsx::wave::incl_max_f64<false>(ftot, lane, kmax), bi = rsx::wave::incl_max_f64<true>(btot, lane, kmax);
+  double fx = dpp<0x138>(fi), bx = dpp<0x130>(bi);  // wave_shr:1 / wave_shl:1 (lane 0 / 63: 0.0)
+  unsigned eprev = dpp<0x138>((R.neg >> (C - 1)) & 1u);  // previous thread's last pixel neg
+  unsigned enext = dpp<0x130>(R.neg & 1u);               // next thread's first pixel neg
   if (lane == 63) L.fwd[NW + w] = fi;
   if (lane == 0) L.bwd[w] = bi;
   const unsigned e0 = (unsigned)__builtin_amdgcn_readlane((int)(R.neg & 1u), 0), e1 = (unsigned)__builtin_amdgcn_readlane((int)((R.neg >> (C - 1)) & 1u), 63);
@@ -666,7 +577,7 @@ __global__ __launch_bounds__(NT) void cen_hist(const uint8_t *__restrict__ imgs,
       unsigned m = R.ordh[0];
 #pragma unroll
       for (int i = 1; i < C; i++) m = R.ordh[i] > m ? R.ordh[i] : m;
-      m = wave_max_u32(m);
+      m = rsx::wave::max_u32(m);
       if ((threadIdx.x & 63) == 0) wavemax[((int64_t)blockIdx.y * rows + a) * (NT / 64) + (threadIdx.x >> 6)] = m;
     }
     int top = 0;  // 1 + the highest histogram bin an opener of this thread fell into (0: the thread has no opener)
@@ -687,8 +598,8 @@ __global__ __launch_bounds__(NT) void cen_hist(const uint8_t *__restrict__ imgs,
     if ((int)threadIdx.x * C < cols)
       opener[((int64_t)blockIdx.y * rows + a) * NT + threadIdx.x] = (OpRec<C>)(opens | ((unsigned)((top + 31) >> 5) << kTopShift<C>));
     if ((rr & 1) || rr + 1 == rpb || a + 1 >= rows) {  // (uniform)
-      const int fhi = wave_sum_i32((int)ahi);  // (DPP + v_readlane: the xor butterfly was twelve ds_bpermute round trips)
-      const int flo = wave_sum_i32((int)alo);
+      const int fhi = rsx::wave::sum_i32((int)ahi);  // (DPP + v_readlane: the xor butterfly was twelve ds_bpermute round trips)
+      const int flo = rsx::wave::sum_i32((int)alo);
       fix += ((long long)fhi << 20) + (long long)flo;
       ahi = alo = 0;
     }
@@ -775,13 +686,13 @@ __global__ __launch_bounds__(64 * HW_WAVES) __attribute__((amdgpu_waves_per_eu(H
           alo += __float_as_uint(__fmaf_rn(r, S, M)) - 0x4B400000u;
         }
         if ((ch & 1) || ch + 1 >= nch) {  // (uniform) 16 pixels a lane at most between two sums, as in cen_hist
-          const int fhi = wave_sum_i32((int)ahi), flo = wave_sum_i32((int)alo);
+          const int fhi = rsx::wave::sum_i32((int)ahi), flo = rsx::wave::sum_i32((int)alo);
           fix += ((long long)fhi << 20) + (long long)flo;
           ahi = alo = 0;
         }
         const unsigned nn = ~neg[ch] & FULL;
         const unsigned cnt = (unsigned)__popc(nn);
-        const unsigned incl = wave_incl_add(cnt, lane);
+        const unsigned incl = rsx::wave::incl_add_u32(cnt);
         excl[ch] = carry_nn + incl - cnt;
         carry_nn += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
         // forward maxima (row_opens): thread-local, across the lanes, across the chunks
@@ -793,9 +704,9 @@ __global__ __launch_bounds__(64 * HW_WAVES) __attribute__((amdgpu_waves_per_eu(H
           const unsigned seg = excl[ch] + (unsigned)__popc(nn & ((2u << i) - 1u));  // non-neg pixels in [0, p]
           run = kmax(run, sc_key(seg, ordh[ch][i]));
         }
-        const double fi = wave_incl_max<false>(run, lane);
-        const double fx = kmax(dpp_f64<0x138>(fi), f_carry);
-        f_carry = kmax(f_carry, readlane_f64(fi, 63));
+        const double fi = rsx::wave::incl_max_f64<false>(run, lane, kmax);
+        const double fx = kmax(dpp<0x138>(fi), f_carry);
+        f_carry = kmax(f_carry, readlane(fi, 63));
         unsigned c = 0;
 #pragma unroll
         for (int i = C - 1; i >= 0; i--) {
@@ -820,17 +731,17 @@ __global__ __launch_bounds__(64 * HW_WAVES) __attribute__((amdgpu_waves_per_eu(H
           const unsigned seg = (unsigned)(NTR * C) + 64u - excl[ch] - (unsigned)__popc(nn & ((1u << i) - 1u));  // a constant minus the non-neg pixels before p: larger to the left
           run = kmax(run, sc_key(seg, ordh[ch][i]));
         }
-        const double bi = wave_incl_max<true>(run, lane);
-        const double bx = kmax(dpp_f64<0x130>(bi), b_carry);
-        b_carry = kmax(b_carry, readlane_f64(bi, 0));
+        const double bi = rsx::wave::incl_max_f64<true>(run, lane, kmax);
+        const double bx = kmax(dpp<0x130>(bi), b_carry);
+        b_carry = kmax(b_carry, readlane(bi, 0));
         unsigned cr = 0;
 #pragma unroll
         for (int i = C - 1; i >= 0; i--) {
           const unsigned b = sc_lo(kmax(bx, bl[i]));
           asm("v_cmp_ge_u32_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(cr) : "v"(ordh[ch][i]), "v"(b) : "vcc");  // h(p) >= G(p + 1)
         }
-        unsigned eprev = dpp_u32<0x138>((neg[ch] >> (C - 1)) & 1u);  // previous thread's last pixel neg
-        unsigned enext = dpp_u32<0x130>(neg[ch] & 1u);               // next thread's first pixel neg
+        unsigned eprev = dpp<0x138>((neg[ch] >> (C - 1)) & 1u);  // previous thread's last pixel neg
+        unsigned enext = dpp<0x130>(neg[ch] & 1u);               // next thread's first pixel neg
         const unsigned pv = ch > 0 ? (unsigned)__builtin_amdgcn_readlane((int)((neg[ch > 0 ? ch - 1 : 0] >> (C - 1)) & 1u), 63) : 0u;
         const unsigned nx = ch + 1 < HW_CH ? (unsigned)__builtin_amdgcn_readlane((int)(neg[ch + 1 < HW_CH ? ch + 1 : ch] & 1u), 0) : 0u;
         if (lane == 0) eprev = pv;
@@ -892,11 +803,7 @@ __global__ __launch_bounds__(256) void cen_pick(Scal *scal, const unsigned *__re
     hv[j] = gh[NBIN - 1 - (threadIdx.x * PER + j)];
     mine += hv[j];
   }
-  unsigned incl = mine;  // inclusive prefix over threads (descending h)
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned o = __shfl_up(incl, d);
-    if ((threadIdx.x & 63) >= d) incl += o;
-  }
+  unsigned incl = rsx::wave::incl_add_u32(mine);  // inclusive prefix over threads (descending h)
   if ((threadIdx.x & 63) == 63) s_cnt[threadIdx.x >> 6] = incl;
   __syncthreads();
   unsigned before = 0;
@@ -974,7 +881,7 @@ __global__ __launch_bounds__(NT) void cen_collect(const uint8_t *__restrict__ im
       const int t = t0 + lane;
       const unsigned rec = t * C < cols ? (unsigned)opener[((int64_t)blockIdx.y * rows + a) * NT + t] : 0u;
       unsigned op = ((int)((rec >> kTopShift<C>) << 5) > bstar) ? rec & ((1u << kTopShift<C>) - 1u) : 0u;  // 1 + highest opener bin (rounded up to 32) >= B* + 1
-      const unsigned cnt = (unsigned)__popc(op), incl = wave_incl_add(cnt, lane);
+      const unsigned cnt = (unsigned)__popc(op), incl = rsx::wave::incl_add_u32(cnt);
       const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
       if (total == 0) continue;              // (uniform)
       if (n + total > (unsigned)QCAP) drain();  // (uniform)
@@ -1055,10 +962,8 @@ __global__ __launch_bounds__(1024) void cen_resolve(Scal *scal, const unsigned l
         vo |= k;
       }
     }
-    for (int o = 32; o >= 1; o >>= 1) {
-      va &= __shfl_xor(va, o);
-      vo |= __shfl_xor(vo, o);
-    }
+    va = rsx::wave::butterfly(va, [](unsigned long long a, unsigned long long b) { return a & b; });
+    vo = rsx::wave::butterfly(vo, [](unsigned long long a, unsigned long long b) { return a | b; });
     if ((threadIdx.x & 63) == 0) {
       s_and[threadIdx.x >> 6] = va;
       s_or[threadIdx.x >> 6] = vo;
@@ -1113,11 +1018,7 @@ __global__ __launch_bounds__(1024) void cen_resolve(Scal *scal, const unsigned l
       const unsigned l = threadIdx.x;
       const unsigned c0 = s_h[4 * l], c1 = s_h[4 * l + 1], c2 = s_h[4 * l + 2], c3 = s_h[4 * l + 3];
       const unsigned mine = c0 + c1 + c2 + c3;
-      unsigned incl = mine;
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(incl, d);
-        if (l >= (unsigned)d) incl += o;
-      }
+      unsigned incl = rsx::wave::incl_add_u32(mine);  // (threadIdx.x < 64: the whole first wavefront)
       const unsigned t = s_t, excl = incl - mine;
       if (excl < t && incl >= t) {
         unsigned c = excl, dig;
@@ -1239,8 +1140,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT <= 512 ? 
     const int rmin = min_range < 0 ? 0 : min_range;
     const unsigned ge = p0 >= rmin ? FULL : (p0 + C <= rmin ? 0u : (FULL & ~((1u << (rmin - p0)) - 1u)));  // bit i: p >= rmin
     const unsigned live = marked & ge;
-    unsigned lprev = dpp_u32<0x138>((live >> (C - 1)) & 1u);   // previous thread's last pixel live
-    unsigned mnext = dpp_u32<0x130>(marked & 1u);               // next thread's first pixel marked
+    unsigned lprev = dpp<0x138>((live >> (C - 1)) & 1u);   // previous thread's last pixel live
+    unsigned mnext = dpp<0x130>(marked & 1u);               // next thread's first pixel marked
     {
       const unsigned e0 = (unsigned)__builtin_amdgcn_readlane((int)(marked & 1u), 0), e1 = (unsigned)__builtin_amdgcn_readlane((int)((live >> (C - 1)) & 1u), 63);
       if (lane == 0) L.edge[w] = e0 | (e1 << 1);
@@ -1255,9 +1156,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT <= 512 ? 
       close = live & ~((marked >> 1) | (mnext << (C - 1))) & in_row;
       // S: 1 + bin of the latest start (0: none yet)
       const unsigned sloc = start ? (unsigned)(p0 + (31 - __builtin_clz(start)) + 1) : 0u;
-      const unsigned x = wave_incl_max_u32(sloc);  // inclusive over the wavefront (positions only grow, so max = latest)
+      const unsigned x = rsx::wave::incl_max_u32(sloc);  // inclusive over the wavefront (positions only grow, so max = latest)
       if (lane == 63) s_cnt[NW + w] = x;
-      sin = dpp_u32<0x138>(x);  // exclusive
+      sin = dpp<0x138>(x);  // exclusive
     } else if (lane == 63) {
       s_cnt[NW + w] = 0u;  // (no start in this wavefront)
     }
@@ -1285,12 +1186,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT <= 512 ? 
         run = kmax(run, kd);
         kin[i] = run;
       }
-      const double ki = wave_incl_max<false>(run, lane);
-      kx = dpp_f64<0x138>(ki);
+      const double ki = rsx::wave::incl_max_f64<false>(run, lane, kmax);
+      kx = dpp<0x138>(ki);
       if (lane == 63) s_k[NW + w] = ki;
       // (the compaction's counts travel with the same barrier)
       cnt = (unsigned)__popc(close);
-      inc = wave_incl_add(cnt, lane);
+      inc = rsx::wave::incl_add_u32(cnt);
       if (lane == 63) s_cnt2[NW + w] = inc;
     } else {
 #pragma unroll
@@ -1397,7 +1298,7 @@ __global__ __launch_bounds__(64 * RW_WAVES) __attribute__((amdgpu_waves_per_eu(R
       neg[ch] = rec & FULL;
       const unsigned nn = ~neg[ch] & FULL;
       const unsigned cnt = (unsigned)__popc(nn);
-      const unsigned incl = wave_incl_add(cnt, lane);
+      const unsigned incl = rsx::wave::incl_add_u32(cnt);
       excl[ch] = carry_nn + incl - cnt;
       carry_nn += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
       const bool cand = p0 < cols && (rec >> 8) >= t8;
@@ -1505,8 +1406,8 @@ __global__ __launch_bounds__(64 * RW_WAVES) __attribute__((amdgpu_waves_per_eu(R
         const int p0 = (ch * 64 + lane) * C;
         const unsigned ge = p0 >= rmin ? FULL : (p0 + C <= rmin ? 0u : (FULL & ~((1u << (rmin - p0)) - 1u)));  // bit i: p >= rmin
         const unsigned live = marked[ch] & ge;
-        unsigned lprev = dpp_u32<0x138>((live >> (C - 1)) & 1u);  // previous thread's last pixel live
-        unsigned mnext = dpp_u32<0x130>(marked[ch] & 1u);         // next thread's first pixel marked
+        unsigned lprev = dpp<0x138>((live >> (C - 1)) & 1u);  // previous thread's last pixel live
+        unsigned mnext = dpp<0x130>(marked[ch] & 1u);         // next thread's first pixel marked
         if (lane == 0) lprev = lprev_c;
         const unsigned next0 = ch + 1 < RW_CH ? (unsigned)__builtin_amdgcn_readlane((int)(marked[ch + 1 < RW_CH ? ch + 1 : ch] & 1u), 0) : 0u;
         if (lane == 63) mnext = next0;
@@ -1556,8 +1457,8 @@ __global__ __launch_bounds__(64 * RW_WAVES) __attribute__((amdgpu_waves_per_eu(R
     const unsigned live = e_lsc & FULL, start = (e_lsc >> 8) & FULL, close = (e_lsc >> 16) & FULL;
     const int p0 = (int)e_p0;
     const unsigned sloc = start ? (unsigned)(p0 + (31 - __builtin_clz(start)) + 1) : 0u;
-    const unsigned x = wave_incl_max_u32(sloc);
-    unsigned sin = dpp_u32<0x138>(x);
+    const unsigned x = rsx::wave::incl_max_u32(sloc);
+    unsigned sin = dpp<0x138>(x);
     sin = s_carry > sin ? s_carry : sin;
     {
       const unsigned xt = (unsigned)__builtin_amdgcn_readlane((int)x, 63);
@@ -1576,11 +1477,11 @@ __global__ __launch_bounds__(64 * RW_WAVES) __attribute__((amdgpu_waves_per_eu(R
       run = kmax(run, kd);
       kin[i] = run;
     }
-    const double ki = wave_incl_max<false>(run, lane);
-    const double kx = kmax(dpp_f64<0x138>(ki), k_carry);
-    k_carry = kmax(k_carry, readlane_f64(ki, 63));
+    const double ki = rsx::wave::incl_max_f64<false>(run, lane, kmax);
+    const double kx = kmax(dpp<0x138>(ki), k_carry);
+    k_carry = kmax(k_carry, readlane(ki, 63));
     const unsigned cnt = (unsigned)__popc(close);
-    const unsigned inc = wave_incl_add(cnt, lane);
+    const unsigned inc = rsx::wave::incl_add_u32(cnt);
     unsigned pos = pos_base + inc - cnt;
     pos_base += (unsigned)__builtin_amdgcn_readlane((int)inc, 63);
 #pragma unroll
@@ -1608,7 +1509,7 @@ __global__ __launch_bounds__(64 * RW_WAVES) __attribute__((amdgpu_waves_per_eu(R
       const unsigned long long kq = ((unsigned long long)o << 32) | (unsigned long long)(~(unsigned)q);
       best = kq > best ? kq : best;
     }
-    best = dev_wave_max_u64(best);
+    best = rsx::wave::butterfly_u64(best, [](unsigned long long a, unsigned long long b) { return b > a ? b : a; });  // (a rare path: shuffles)
     if (lane == 0) ro[at].y = ~(unsigned)best;
   }
 }

@@ -51,6 +51,7 @@
 
 #include "cfear.h"
 #include "cfear_dev.h"
+#include "rsx_wave_dev.h"
 #include "ragged_host.h"
 
 #pragma STDC FP_CONTRACT OFF
@@ -418,11 +419,7 @@ __device__ void joint_register(const float4 *sp, int sstride, const float4 *sx, 
       acc[10] += 1.0;
     }
 #pragma unroll
-    for (int a = 0; a < N_SUMS; a++) {
-      double v = acc[a];
-      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-      acc[a] = v;
-    }
+    for (int a = 0; a < N_SUMS; a++) acc[a] = rsx::wave::butterfly(acc[a], rsx::wave::Add{});  // (fp64: this order is the result)
     if (lane == 0) {
 #pragma unroll
       for (int a = 0; a < N_SUMS; a++) s_red[w * N_SUMS + a] = acc[a];

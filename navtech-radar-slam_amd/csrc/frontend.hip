@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "rsx_common.h"
+#include "rsx_wave_dev.h"
 
 namespace {
 
@@ -378,23 +379,9 @@ __global__ __launch_bounds__(256) void fe_uv(const float *__restrict__ xy, const
 // zero; before: 16 raster steps with a division by 31 and the circle test), I_q from the fp32 product -- I * 2^24 is exact in
 // fp32 as in fp64 and the image holds values in [0, 1], far inside int32 -- and the lanes' sums and the maximum over the bins
 // by DPP (before: 36 dependent ds_bpermute round trips a keypoint, most of its time).
-__device__ __forceinline__ int fe_wave_sum_i32(int x) {  // every lane: the sum over the 64 lanes
-  x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, true);  // row_half_mirror
-  x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, true);  // row_mirror: every lane = its row's sum
-  return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48);
-}
 __device__ __forceinline__ long long fe_wave_sum_i64(long long p) {  // |p| < 2^40 per lane: as 16 low bits + the rest, two int32 sums
-  const int lo = fe_wave_sum_i32((int)(p & 0xffff)), hi = fe_wave_sum_i32((int)(p >> 16));
+  const int lo = rsx::wave::sum_i32((int)(p & 0xffff)), hi = rsx::wave::sum_i32((int)(p >> 16));
   return ((long long)hi << 16) + (long long)lo;
-}
-template <int CTRL>
-__device__ __forceinline__ double fe_dpp_f64(double x) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)u, (int)(unsigned)u, CTRL, 0xf, 0xf, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(u >> 32), (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 #ifndef FE_DESC_BLOCKS
 #define FE_DESC_BLOCKS 128
@@ -447,18 +434,9 @@ __global__ __launch_bounds__(256) void fe_describe(const float *__restrict__ car
       dd = a + b;
     }
     // maximum over the lanes (finite values in the first 30, -inf elsewhere: fmax is a plain maximum): inside the rows of 16 by
-    // DPP, the 30 bins live in rows 0 and 1
-    double mx = dd;
-    mx = fmax(mx, fe_dpp_f64<0xB1>(mx));
-    mx = fmax(mx, fe_dpp_f64<0x4E>(mx));
-    mx = fmax(mx, fe_dpp_f64<0x141>(mx));
-    mx = fmax(mx, fe_dpp_f64<0x140>(mx));
-    {
-      const unsigned long long u0 = (unsigned long long)__double_as_longlong(mx);
-      const unsigned l0 = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u0, 0), h0 = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u0 >> 32), 0);
-      const unsigned l1 = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u0, 16), h1 = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u0 >> 32), 16);
-      mx = fmax(__longlong_as_double((long long)(((unsigned long long)h0 << 32) | l0)), __longlong_as_double((long long)(((unsigned long long)h1 << 32) | l1)));
-    }
+    // DPP, the 30 bins live in rows 0 and 1 (the wavefront is whole here: the return and the continue above are wave-uniform)
+    double mx = rsx::wave::row_reduce(dd, [](double a, double b) { return fmax(a, b); });
+    mx = fmax(rsx::wave::readlane(mx, 0), rsx::wave::readlane(mx, 16));
     const unsigned long long at = __ballot(lane < NBINS && dd == mx);
     const int bin = at ? __ffsll((long long)at) - 1 : 0;  // first maximum (NaN cannot occur: finite integers)
     const int8_t *pp = pairs + (int64_t)bin * NPAIRS * 4;

@@ -40,6 +40,7 @@
 #include "rsx_common.h"
 #include "rsx_grid_dev.h"
 #include "rsx_persistent.h"
+#include "rsx_wave_dev.h"
 
 namespace {
 
@@ -204,28 +205,6 @@ __device__ __forceinline__ void rotation_from_covariance(const double (&H)[9], d
     for (int j = 0; j < 3; j++) R[3 * i + j] = U[3 * i + 0] * Vs[3 * j + 0] + U[3 * i + 1] * Vs[3 * j + 1] + U[3 * i + 2] * Vs[3 * j + 2];
 }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double x) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, true);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, true);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double readlane_f64(double x, int l) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// the four levels of the tree inside a row of 16 lanes: lanes that already hold the same partial sum add the partner
-// group's (quad_perm, then the mirrors, which pair every lane with one of the other group) -- DPP, no LDS traffic (the
-// __shfl_xor form was 180 ds_bpermute per wavefront and sum: the sixteen wavefronts of a workgroup queued on the LDS pipe)
-__device__ __forceinline__ double row_tree(double x) {
-  x += dpp_f64<0xB1>(x);   // quad_perm [1,0,3,2]
-  x += dpp_f64<0x4E>(x);   // quad_perm [2,3,0,1]
-  x += dpp_f64<0x141>(x);  // row_half_mirror
-  x += dpp_f64<0x140>(x);  // row_mirror
-  return x;
-}
 // N sums over the 1024 threads of the workgroup in a fixed order ("tree", restated by oracle/icp_ref.c): thread t holds
 // partial sum t; wavefront c adds the sixteen partial sums l, l + 64, l + 128, ... of sum c in its lane l one after the other,
 // then its 64 lanes as a balanced tree, neighbours first.  The partial sums go through LDS (part: N x 1024 doubles), so ONE
@@ -243,8 +222,7 @@ __device__ __forceinline__ void tree_sum(double (&v)[N], double *part, double *r
     double a = part[w * PI_NT + lane];
 #pragma unroll
     for (int j = 1; j < PI_NT / 64; j++) a += part[w * PI_NT + lane + 64 * j];
-    a = row_tree(a);
-    a = (readlane_f64(a, 0) + readlane_f64(a, 16)) + (readlane_f64(a, 32) + readlane_f64(a, 48));
+    a = rsx::wave::sum_f64_rows_pair(a);  // (w < N is wave-uniform: the whole wavefront is here)
     if (lane == 0) res[w] = a;
   }
   __syncthreads();

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "rsx_common.h"
+#include "rsx_wave_dev.h"
 
 namespace rsx {
 
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void kp_pack(int rows, int row_cap
   const unsigned *rn = row_n + (int64_t)img * rows;
   unsigned before = 0;
   for (int r = lane; r < a; r += 64) before += rn[r];
-  for (int o = 32; o >= 1; o >>= 1) before += __shfl_xor(before, o);
+  before = rsx::wave::butterfly(before, rsx::wave::Add{});
   const unsigned n = rn[a];
   int *tg = targets + (int64_t)img * max_targets * 2;
   float *pxy = xy ? xy + (int64_t)img * max_targets * 2 : nullptr;

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void odo_gather(const float2 *__restrict__ sta
   const int j = blockIdx.x;
   long long before = 0;
   for (int r = threadIdx.x; r < j; r += 256) before += pair_cnt[r];
-  for (int o = 32; o >= 1; o >>= 1) before += __shfl_xor(before, o);
+  before = rsx::wave::butterfly(before, rsx::wave::Add{});
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = before;
   __syncthreads();
   before = s_w[0] + s_w[1] + s_w[2] + s_w[3];

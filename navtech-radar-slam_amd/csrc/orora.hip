@@ -19,6 +19,7 @@
 #include <new>
 
 #include "rsx_common.h"
+#include "rsx_wave_dev.h"
 #include "pmc.h"
 #include "ragged_host.h"
 
@@ -61,22 +62,13 @@ __device__ unsigned long long g_orora_prof[8];
 #endif
 
 // ---- workgroup reductions, deterministic order ----
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
+// (inside a wavefront: the xor butterfly of rsx_wave_dev.h, whose order of additions oracle/orora_ref.c restates)
 
 template <int NW>
 struct Red {
   double *buf;  // 3 * NW doubles of LDS
   __device__ double sum(double v) {
-    v = wave_sum(v);
+    v = rsx::wave::butterfly(v, rsx::wave::Add{});
     __syncthreads();
     if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -86,8 +78,8 @@ struct Red {
     return r;
   }
   __device__ void sum2(double &a, double &b) {
-    a = wave_sum(a);
-    b = wave_sum(b);
+    a = rsx::wave::butterfly(a, rsx::wave::Add{});
+    b = rsx::wave::butterfly(b, rsx::wave::Add{});
     __syncthreads();
     if ((threadIdx.x & 63) == 0) {
       buf[threadIdx.x >> 6] = a;
@@ -103,9 +95,9 @@ struct Red {
     }
   }
   __device__ void sum3(double &a, double &b, double &c) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-    c = wave_sum(c);
+    a = rsx::wave::butterfly(a, rsx::wave::Add{});
+    b = rsx::wave::butterfly(b, rsx::wave::Add{});
+    c = rsx::wave::butterfly(c, rsx::wave::Add{});
     __syncthreads();
     if ((threadIdx.x & 63) == 0) {
       buf[threadIdx.x >> 6] = a;
@@ -124,7 +116,7 @@ struct Red {
     }
   }
   __device__ double max(double v) {
-    v = wave_max(v);
+    v = rsx::wave::butterfly(v, [](double x, double y) { return fmax(x, y); });
     __syncthreads();
     if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -392,8 +384,7 @@ __device__ __forceinline__ double scalar_tls_block(const double (&x)[TPT], const
       for (int j = 0; j < PER; j++) q[lane * PER + j] = base + pre[j];
       if (qn == 7) {
         const double total = __shfl(incl, 63);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        rsx::wave::lds_fence();
         if (lane == 0) q[0] = total;  // sum of all bounds
       }
     }

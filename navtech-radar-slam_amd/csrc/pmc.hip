@@ -37,6 +37,7 @@
 #include <cstdint>
 
 #include "pmc.h"
+#include "rsx_wave_dev.h"
 
 namespace {
 
@@ -62,19 +63,6 @@ struct Args {
   int32_t *sel_cnt;
   int64_t sel_cap;  // matches the sel arrays hold
 };
-
-__device__ __forceinline__ int wave_sum_i(int x) {  // every lane: the sum over the 64 lanes (DPP + v_readlane: no LDS round trips)
-  x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, true);  // row_half_mirror
-  x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, true);  // row_mirror: every lane = its row's sum
-  return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48);
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
-  return v;
-}
 
 // the edge predicate of oracle/pmc_ref.h, operation for operation (this file is compiled with -ffp-contract=off)
 __device__ __forceinline__ bool edge(double six, double siy, double dix, double diy, float2 sj, float2 dj, double tau2) {
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(NT) void pmc_build_kernel(Args a) {
     w &= vm;                                                   // columns past K
     if (lane == (i & 63)) w &= ~(1u << (i >> 6));              // no self loop
     adj[(size_t)i * ROWW + lane] = w;
-    const int d = wave_sum_i(__popc(w));
+    const int d = rsx::wave::sum_i32(__popc(w));
     if (lane == 0) g_deg[i] = d;
   }
 }
@@ -235,7 +223,7 @@ __global__ __launch_bounds__(NT) void pmc_cores_kernel(Args a) {
         }
       }
     }
-    my_min = wave_min_i(my_min);
+    my_min = rsx::wave::butterfly(my_min, [](int a, int b) { return min(a, b); });
     if (lane == 0) L.red[wave] = my_min;
     __syncthreads();
     const int nf = __builtin_amdgcn_readfirstlane(L.nfront);
@@ -348,7 +336,7 @@ __device__ __forceinline__ void pmc_walk(const Args &a) {
     }
     uint32_t P = adj[(size_t)v * ROWW + lane] & cm;
     uint32_t C = (lane == (v & 63)) ? (1u << (v >> 6)) : 0u;
-    int n = 1, np = __builtin_amdgcn_readfirstlane(wave_sum_i(__popc(P)));
+    int n = 1, np = __builtin_amdgcn_readfirstlane(rsx::wave::sum_i32(__popc(P)));
     bool abandoned = n + np <= best_n;
     for (int s = 0; s < K && np > 0 && !abandoned; s += 64) {
       const int idx = s + lane;
@@ -382,7 +370,7 @@ __device__ __forceinline__ void pmc_walk(const Args &a) {
               if (lane == (uq & 63)) C |= 1u << (uq >> 6);
               n++;
               P &= row[q];
-              np = __builtin_amdgcn_readfirstlane(wave_sum_i(__popc(P)));
+              np = __builtin_amdgcn_readfirstlane(rsx::wave::sum_i32(__popc(P)));
               if (n + np <= best_n) abandoned = true;
             }
           }
@@ -451,7 +439,7 @@ struct ExactLds {
   uint16_t C[MAX_K];  // the clique in hand, by depth (vertices of S)
 };
 
-__device__ __forceinline__ int set_count(uint32_t x) { return __builtin_amdgcn_readfirstlane(wave_sum_i(__popc(x))); }
+__device__ __forceinline__ int set_count(uint32_t x) { return __builtin_amdgcn_readfirstlane(rsx::wave::sum_i32(__popc(x))); }
 __device__ __forceinline__ int set_first(uint32_t x) {  // the first vertex of a set over S, -1 = empty
   const unsigned long long m = __ballot(x != 0u);
   if (m == 0ull) return -1;
@@ -592,7 +580,7 @@ __device__ __forceinline__ void exact_pair(const Args &a, const ExactArgs &x, in
     auto alive_of = [&](int bst) {
       int cnt = 0;
       for (int i = lane; i < n; i += 64) cnt += (int)g_core[L.S[i]] >= u + bst ? 1 : 0;
-      const int m = __builtin_amdgcn_readfirstlane(wave_sum_i(cnt)) - 32 * lane;
+      const int m = __builtin_amdgcn_readfirstlane(rsx::wave::sum_i32(cnt)) - 32 * lane;
       return m >= 32 ? 0xffffffffu : m <= 0 ? 0u : (1u << m) - 1u;
     };
     auto stk_get = [&](int d) { return stk_lds ? (lane < EX_LDS_W ? L.stk[d * EX_LDS_W + lane] : 0u) : gstk[(size_t)d * ROWW + lane]; };

@@ -25,6 +25,7 @@
 
 #include "ragged_host.h"
 #include "ransac.h"
+#include "rsx_wave_dev.h"
 
 namespace {
 
@@ -130,10 +131,7 @@ __device__ __forceinline__ bool gn_step(const double (&q)[9], double &d0, double
 template <int N>
 __device__ __forceinline__ void block_sum(double (&v)[N], double *buf) {
 #pragma unroll
-  for (int k = 0; k < N; k++) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off);
-  }
+  for (int k = 0; k < N; k++) v[k] = rsx::wave::butterfly(v[k], rsx::wave::Add{});
   __syncthreads();
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -151,11 +149,7 @@ __device__ __forceinline__ void block_sum(double (&v)[N], double *buf) {
 
 template <bool MAX>
 __device__ __forceinline__ int block_minmax(int v, int *buf) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off);
-    v = MAX ? (o > v ? o : v) : (o < v ? o : v);
-  }
+  v = rsx::wave::butterfly(v, [](int x, int o) { return MAX ? (o > x ? o : x) : (o < x ? o : x); });
   __syncthreads();
   if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
   __syncthreads();

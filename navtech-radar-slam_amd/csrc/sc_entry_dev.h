@@ -9,50 +9,13 @@
 #include <cmath>
 #include <cstdint>
 
+#include "rsx_wave_dev.h"
 #include "sc_kernels.h"
 #include "sc_redux_dev.h"
 
 namespace rsx {
 namespace sc {
 namespace dev {
-
-__device__ __forceinline__ void wave_lds_fence() {
-  // LDS operations of one wave execute in order; this only stops the compiler from moving LDS
-  // accesses across the point where lanes exchange data through LDS.
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// wave-wide reductions on 64-bit values by DPP inside the rows of 16 lanes + four v_readlane (a __shfl_xor butterfly is
-// two ds_bpermute per step: ~1.2 k cycles of dependent LDS-crossbar round trips for one 64-bit reduction)
-template <int CTRL>
-__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long x) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)x, CTRL, 0xf, 0xf, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(x >> 32), CTRL, 0xf, 0xf, false);
-  return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long x, int l) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
-  return ((unsigned long long)hi << 32) | lo;
-}
-template <bool MAX>
-__device__ __forceinline__ unsigned long long wave_minmax_u64(unsigned long long v) {
-  auto pick = [](unsigned long long a, unsigned long long b) { return MAX ? (a > b ? a : b) : (a < b ? a : b); };
-  v = pick(v, dpp_u64<0xB1>(v));   // quad_perm [1,0,3,2]
-  v = pick(v, dpp_u64<0x4E>(v));   // quad_perm [2,3,0,1]
-  v = pick(v, dpp_u64<0x141>(v));  // row_half_mirror
-  v = pick(v, dpp_u64<0x140>(v));  // row_mirror: every lane = its row's result
-  return pick(pick(readlane_u64(v, 0), readlane_u64(v, 16)), pick(readlane_u64(v, 32), readlane_u64(v, 48)));
-}
-__device__ __forceinline__ double wave_sum_f64(double x) {  // (row sums in butterfly order, then row 0 + 1 + 2 + 3)
-  auto d = [](double a) { return (unsigned long long)__double_as_longlong(a); };
-  auto f = [](unsigned long long a) { return __longlong_as_double((long long)a); };
-  x = x + f(dpp_u64<0xB1>(d(x)));
-  x = x + f(dpp_u64<0x4E>(d(x)));
-  x = x + f(dpp_u64<0x141>(d(x)));
-  x = x + f(dpp_u64<0x140>(d(x)));
-  return ((f(readlane_u64(d(x), 0)) + f(readlane_u64(d(x), 16))) + f(readlane_u64(d(x), 32))) + f(readlane_u64(d(x), 48));
-}
 
 // ------------------------------------------------------------------------------------------
 // keys: one wave per descriptor
@@ -259,7 +222,7 @@ __device__ __forceinline__ void img_db_entry(const float *__restrict__ desc, con
   if (lane < NS) normalise_column(desc + slot * DS + lane * NR, norm[slot * NS + lane], &st[lane * NR], nonzero, bad);
   unsigned long long m = __ballot(nonzero && lane < NS);
   if (__ballot(bad && lane < NS)) m |= kEntryNonFinite;
-  wave_lds_fence();
+  wave::lds_fence();
   const int64_t tile = slot >> 5;
   const int col = (int)(slot & 31);
   for (int c = lane; c < 2 * kSteps; c += 64) {
@@ -286,13 +249,9 @@ __device__ __forceinline__ KeySplit split_key(double v, int lane) {
   const double av = lane < NS ? fabs(v) : 0.0;
   double mx = av;
   if constexpr (DPP) {
-    mx = __longlong_as_double((long long)wave_minmax_u64<true>((unsigned long long)__double_as_longlong(av)));
+    mx = __longlong_as_double((long long)wave::minmax_u64<true>((unsigned long long)__double_as_longlong(av)));
   } else {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double o = __shfl_xor(mx, off);
-      mx = (o > mx || !(o == o)) ? o : mx;  // a NaN wins
-    }
+    mx = wave::butterfly(mx, [](double m, double o) { return (o > m || !(o == o)) ? o : m; });  // a NaN wins
   }
   KeySplit r;
   r.hi = (_Float16)0.0f;
@@ -310,10 +269,9 @@ __device__ __forceinline__ KeySplit split_key(double v, int lane) {
   const _Float16 lo = (_Float16)(float)(x - (double)(float)hi);
   double s = x * x;
   if constexpr (DPP) {
-    s = wave_sum_f64(s);
+    s = wave::sum_f64_rows_seq(s);
   } else {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    s = wave::butterfly(s, wave::Add{});
   }
   r.hi = hi;
   r.lo = lo;

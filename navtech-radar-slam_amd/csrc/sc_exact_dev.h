@@ -16,8 +16,6 @@ namespace rsx {
 namespace sc {
 namespace {
 
-using dev::wave_lds_fence;
-
 constexpr double kBig = 10000000.0;  // SC.cpp:96,134,362 "init with something large"
 
 // per entry: the sector key twice in a row (vk2[e] = v[e % 60], 120 doubles) for the rotated reads of
@@ -36,33 +34,6 @@ constexpr int ENT_SIZE = 3408;
 
 __device__ __forceinline__ bool hit_before(double ad, int ai, double bd, int bi) {
   return (ad < bd) || (ad == bd && ai < bi);
-}
-
-// sum of v over the 64 lanes (DPP butterfly inside each row of 16, row broadcasts across rows)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f32(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {
-  v += dpp_f32<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f32<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f32<0x141, 0xf>(v);  // row_half_mirror
-  v += dpp_f32<0x140, 0xf>(v);  // row_mirror: every lane = its row's sum
-  v += dpp_f32<0x142, 0xa>(v);  // row_bcast:15 into rows 1, 3
-  v += dpp_f32<0x143, 0xc>(v);  // row_bcast:31 into rows 2, 3
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
-__device__ __forceinline__ float wave_min_f32(float v) {
-  v = fminf(v, dpp_f32<0xB1, 0xf>(v));
-  v = fminf(v, dpp_f32<0x4E, 0xf>(v));
-  v = fminf(v, dpp_f32<0x141, 0xf>(v));
-  v = fminf(v, dpp_f32<0x140, 0xf>(v));
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return fminf(fminf(r0, r1), fminf(r2, r3));
 }
 
 // the per-lane registers of one entry (lane = column), loaded ahead of time by a caller that overlaps the global-memory
@@ -116,7 +87,7 @@ __device__ __forceinline__ int align_exact(const double *v1, char *wsm, int lane
     vkb[lane + 1] = ev;
     vkb[lane + NS + 1] = ev;
   }
-  wave_lds_fence();
+  wave::lds_fence();
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   const int eoff = (kk & 1) ? (ENT_VKEY_B + (NS + 1 - kk) * 8) : (ENT_VKEY_A + (NS - kk) * 8);
   const double2 *v2 = reinterpret_cast<const double2 *>(wsm + eoff);
@@ -142,10 +113,9 @@ __device__ __forceinline__ int align_exact(const double *v1, char *wsm, int lane
   }
   const bool ok = (lane < NS) && (nrm < kBig);
   double m = ok ? nrm : INFINITY;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+  m = wave::butterfly(m, [](double a, double b) { return fmin(a, b); });
   const unsigned long long bal = __ballot(ok && nrm == m);
-  wave_lds_fence();
+  wave::lds_fence();
   return bal ? (__ffsll((long long)bal) - 1) : 0;
 }
 
@@ -171,12 +141,10 @@ __device__ __forceinline__ void topk_insert_dpp(double &ld, int &li, int &ls, in
   const bool before = (lane < k) && hit_before(ld, li, dist, idx);
   const int pos = __popcll(__ballot(before));
   if (pos < k) {
-    auto shr1 = [](int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); };
-    const long long lb = __double_as_longlong(ld);
-    const long long ub = ((long long)shr1((int)(lb >> 32)) << 32) | (unsigned)shr1((int)lb);
-    const int ui = shr1(li), us = shr1(ls);
+    const double ud = wave::dpp<0x138>(ld);  // wave_shr:1 (lane 0 reads 0 and, never above pos, does not take it)
+    const int ui = wave::dpp<0x138>(li), us = wave::dpp<0x138>(ls);
     if (lane > pos) {
-      ld = __longlong_as_double(ub); li = ui; ls = us;
+      ld = ud; li = ui; ls = us;
     } else if (lane == pos) {
       ld = dist; li = idx; ls = shift;
     }
@@ -200,7 +168,7 @@ __device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane,
                                           double &bd_out, int &bk_out) {
   const int cl = lane < NS ? lane : 0;
   const double *qn1 = reinterpret_cast<const double *>(smem + WaveLds::OFF_QN1);
-  wave_lds_fence();
+  wave::lds_fence();
   double e[NR];
 #pragma unroll
   for (int i = 0; i < 5; i++) {
@@ -240,7 +208,7 @@ __device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane,
     const int ne = __popcll(__ballot(valid));
     if (lane == 0) misc[t] = ne;
   }
-  wave_lds_fence();
+  wave::lds_fence();
   const int tt = lane & 7;
   double bd = INFINITY;
   int bk = 0x7fffffff;

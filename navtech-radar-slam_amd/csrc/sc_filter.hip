@@ -80,7 +80,6 @@ constexpr int F_B_VGPR = 44;      // B fragments kept in VGPRs; the rest live in
 constexpr int F_PHASE_BYTES = F_QPP * FILTER_QIMG_BYTES;  // 39936 = 39 KiB
 using dev::kImgScale;  // 2^15 on both operands
 using dev::normalise_column;
-using dev::wave_lds_fence;
 constexpr float kAccScale = 1073741824.0f;            // 2^30 carried by the accumulators
 constexpr u64 kNonFinite = 1ull << 63;
 
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(256) void sc_img_query_kernel(const float *__restri
   if (lane < NS) normalise_column(desc + (int64_t)q * DS + lane * NR, norm[(int64_t)q * NS + lane], &st[wave][lane * NR], nonzero, bad);
   u64 m = __ballot(nonzero && lane < NS);
   if (__ballot(bad && lane < NS)) m |= kNonFinite;
-  wave_lds_fence();
+  wave::lds_fence();
   dev::img_query_image(st[wave], m, reinterpret_cast<uint4 *>(qimg + (int64_t)q * FILTER_QIMG_BYTES), lane);
 }
 
@@ -563,12 +562,7 @@ __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__
     run += hist[threadIdx.x * 8 + i];
     v[i] = run;
   }
-  int incl = run;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(incl, off);
-    if (lane >= off) incl += o;
-  }
+  const int incl = (int)wave::incl_add_u32((unsigned)run);
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();
   int base = incl - run;

@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "rsx_common.h"
+#include "rsx_wave_dev.h"
 #include "sc_kernels.h"
 #include "sc_redux_dev.h"
 
@@ -66,7 +67,7 @@ __device__ int fast_align(int so, const double *v1, const double *v2, double *sc
   }
   const bool ok = (lane < NS) && (nrm < kBig);  // SC.cpp:96,104
   double m = ok ? nrm : INFINITY;
-  for (int off = 32; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+  m = wave::butterfly(m, [](double x, double y) { return fmin(x, y); });
   const unsigned long long bal = __ballot(ok && nrm == m);
   return bal ? (__ffsll((long long)bal) - 1) : 0;
 }

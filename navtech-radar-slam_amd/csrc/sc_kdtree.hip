@@ -74,6 +74,7 @@
 #include <cstdint>
 
 #include "rsx_common.h"
+#include "rsx_wave_dev.h"
 #include "sc_kdtree.h"
 
 namespace rsx {
@@ -95,11 +96,6 @@ struct Frame {
   float mind;
   int32_t lo, hi;  // positions (in vind) the farther child covers
 };
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // Every lane runs the same scalar walk on the same values (the per-wave state in LDS is written by all lanes with
 // identical data, LDS operations of a wave execute in order): no lane-0 sections, no synchronisation inside the walk --
@@ -237,7 +233,7 @@ __global__ __launch_bounds__(64) void sc_knn_tree_kernel(KdSearchArgs a, int res
     rd[lane] = 0.0f;
     ri[lane] = 0;  // Scancontext.cpp:367: the caller's vectors are zero-initialised
   }
-  wave_sync();
+  wave::lds_fence();
   rd[k - 1] = FLT_MAX;  // KNNResultSet::init (all lanes, the same value)
   // computeInitialDistances (:1006-1023); `dists` starts at zero (:1235).  Lane i keeps q[i] and dists[i].
   const float qreg = lane < KD_DIM ? q[lane] : 0.0f;
@@ -260,7 +256,7 @@ __global__ __launch_bounds__(64) void sc_knn_tree_kernel(KdSearchArgs a, int res
   if (reduced) walk<false, true>(a, nodes_lds, dist_lds, qreg, dreg, stack, rd, ri, bound, distsq, candpos, lane);
   else if (resident) walk<true, false>(a, nodes_lds, dist_lds, qreg, dreg, stack, rd, ri, bound, distsq, candpos, lane);
   else walk<false, false>(a, nodes_lds, dist_lds, qreg, dreg, stack, rd, ri, bound, distsq, candpos, lane);
-  wave_sync();
+  wave::lds_fence();
   if (lane < k) {
     a.out_idx[lane] = ri[lane];
     a.out_dist[lane] = rd[lane];

@@ -165,7 +165,7 @@ __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, c
   const double *qn1 = reinterpret_cast<const double *>(smem + OFF_QN1);
   float4 ecol[B][5];
   double en2[B], ev[B];
-    wave_lds_fence();
+    wave::lds_fence();
 #pragma unroll
     for (int b = 0; b < B; b++) {
       ev[b] = db.vkey[eslot[b] * NS + cl];
@@ -188,7 +188,7 @@ __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, c
         vkb[lane + NS + 1] = v;
       }
     }
-    wave_lds_fence();
+    wave::lds_fence();
 
     // ---- stage 1: fastAlignUsingVkey (SC.cpp:93-113), lane = shift ----
     // Eigen's redux order (SSE2 build of the reference): term c goes to accumulator c % 4, the norm is
@@ -236,15 +236,14 @@ __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, c
       }
       bool ok = (lane < NS) && (nrm < kBig);     // SC.cpp:96,104 (NaN never passes `<`)
       double m = ok ? nrm : INFINITY;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+      m = wave::butterfly(m, [](double x, double y) { return fmin(x, y); });
       unsigned long long bal = __ballot(ok && nrm == m);
       kstar[b] = bal ? (__ffsll((long long)bal) - 1) : 0;  // first strict minimum = lowest shift
     }
 
     // ---- stage 2: column cosine terms for the 7 shifts k*-3..k*+3 (SC.cpp:123-144, 69-90) ----
     // lane = entry column j; shifted by k it lands on query column c = (j + k) % 60
-    wave_lds_fence();  // the similarity terms overwrite the key images read by stage 1
+    wave::lds_fence();  // the similarity terms overwrite the key images read by stage 1
 #pragma unroll
     for (int b = 0; b < B; b++) {
       const int ks = kstar[b];
@@ -287,7 +286,7 @@ __device__ __forceinline__ void pair_group(const DbView &db, const char *smem, c
       }
       if (lane == 0) misc[7] = ks;
     }
-    wave_lds_fence();
+    wave::lds_fence();
 
     // ---- stage 3: sequential column sum (SC.cpp:83,87-88), lane = (entry b, shift t) ----
     const int bb = lane >> 3, tt = lane & 7;
@@ -353,7 +352,7 @@ __device__ __forceinline__ int phase_a(const char *smem, char *wsm, int lane, co
   const int cl = lane < NS ? lane : 0;
   const int kk = lane < NS ? lane : NS - 1;
   const double *v1 = reinterpret_cast<const double *>(smem + OFF_QV1);
-  wave_lds_fence();
+  wave::lds_fence();
   const double ev = er.v;
   const float4 (&ecol)[5] = er.ecol;
   const double n2 = er.n2;
@@ -370,8 +369,8 @@ __device__ __forceinline__ int phase_a(const char *smem, char *wsm, int lane, co
         if (lane < j) img[lane + 2 * NS - j] = vf;
       }
     }
-    const float e2 = wave_sum_f32(lane < NS ? vf * vf : 0.0f);
-    wave_lds_fence();
+    const float e2 = wave::sum_f32_bcast(lane < NS ? vf * vf : 0.0f);
+    wave::lds_fence();
     const int j = (-kk) & 3;
     const float4 *yp = reinterpret_cast<const float4 *>(wsm + fimg_base(j) + (NS - kk - j) * 4);
     const float4 *xp = reinterpret_cast<const float4 *>(smem + off_preview + QP_V1F);
@@ -384,7 +383,7 @@ __device__ __forceinline__ int phase_a(const char *smem, char *wsm, int lane, co
       a1 = __builtin_elementwise_fma(d1, d1, a1);
     }
     const float D = (a0[0] + a0[1]) + (a1[0] + a1[1]);
-    const float dmin = wave_min_f32(lane < NS ? D : INFINITY);
+    const float dmin = wave::min_f32(lane < NS ? D : INFINITY);
     const float thr = dmin + 2.0f * kFastAlignEps * (e1 + e2);
     const unsigned long long nan_bal = __ballot(lane < NS && !(D == D));
     const unsigned long long cand = __ballot(lane < NS && D <= thr);
@@ -392,7 +391,7 @@ __device__ __forceinline__ int phase_a(const char *smem, char *wsm, int lane, co
       kstar = __ffsll((long long)cand) - 1;
       need_exact = false;
     }
-    wave_lds_fence();
+    wave::lds_fence();
   }
   if (need_exact) kstar = align_exact<SO>(v1, wsm, lane, ev);
   // fp32 preview of the window distances (see PREVIEW above), arranged for few instructions: the query's unit
@@ -478,7 +477,7 @@ __device__ __forceinline__ void phase_b(const char *smem, char *wsm, int lane, c
                                         int &bk_out) {
   const int cl = lane < NS ? lane : 0;
   const double *qn1 = reinterpret_cast<const double *>(smem + OFF_QN1);
-  wave_lds_fence();
+  wave::lds_fence();
   double e[NR];
 #pragma unroll
   for (int i = 0; i < 5; i++) {
@@ -515,7 +514,7 @@ __device__ __forceinline__ void phase_b(const char *smem, char *wsm, int lane, c
     const int ne = __popcll(__ballot(valid));
     if (lane == 0) misc[t] = ne;
   }
-  wave_lds_fence();
+  wave::lds_fence();
   const int tt = lane & 7;
   double bd = INFINITY;
   int bk = 0x7fffffff;
@@ -708,7 +707,7 @@ __global__ __launch_bounds__(256, W) void sc_pair2_kernel(PairArgs a) {
   load_query_to_lds(a.q, qi, smem, threadIdx.x, 256, PAIR2_OFF_QP32);
   __syncthreads();
   const float v1f = lane < NS ? reinterpret_cast<const float *>(smem + PAIR2_OFF_QP32 + QP_V1F)[lane] : 0.0f;
-  const float e1 = wave_sum_f32(v1f * v1f);
+  const float e1 = wave::sum_f32_bcast(v1f * v1f);
 
   int64_t n_elig = a.n_eligible;
   if (a.q_elig) {
@@ -1106,7 +1105,7 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       reinterpret_cast<double *>(smem + WaveLds::OFF_QN1)[lane] = kn;
       reinterpret_cast<double *>(smem + WaveLds::OFF_QV1)[lane] = kv;
     }
-    wave_lds_fence();
+    wave::lds_fence();
   }
 
   int64_t n_elig = a.n_eligible;
@@ -1251,7 +1250,7 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       }
       lap(1);  // [5]
       auto pick = [&](int32_t &slot, int &ks) -> float {  // the smallest lower bound left in this round
-        const float wm = wave_min_f32(mylo);
+        const float wm = wave::min_f32(mylo);
         if (wm == INFINITY) return wm;
         const int src = __ffsll((long long)__ballot(mylo == wm)) - 1;
         slot = __shfl(myslot, src);
@@ -1354,11 +1353,7 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
         }
       }
       if (done) break;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const int o = __shfl_xor(next, off);
-        next = o < next ? o : next;
-      }
+      next = wave::butterfly(next, [](int x, int o) { return o < x ? o : x; });
       if (next > b_to) break;  // (RESCORE_BINS: nothing above b)
       b = next;
       take = true;

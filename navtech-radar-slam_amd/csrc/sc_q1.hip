@@ -125,8 +125,6 @@ struct Q1Args {
 __device__ __forceinline__ void store_sc1(u64 *p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u64 load_sc1(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ u64 wave_min_u64(u64 v) { return dev::wave_minmax_u64<false>(v); }
-
 // RSX_EXPERIMENTS builds with profiling on: the last workgroup adds the length of its phases (10-ns ticks of the constant
 // clock) to stats words 4..10, 13, 14: prep | tiles | publish | ticket | header loads | bound merge | total | eager rounds | rest
 #ifdef RSX_EXPERIMENTS
@@ -309,17 +307,16 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
       if (have) lo = (pv == pv) ? pv - WINDOW_MARGIN : -INFINITY;  // NaN: no preview (non-finite data), must be looked at
       // the workgroup's k smallest upper bounds, ascending, one per lane
       float lub = s_ub[n];
-      auto lane_of = [](float x, int l) { return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(x), l)); };
-      float kth = lane_of(lub, a.k - 1);
+      float kth = wave::readlane(lub, a.k - 1);
       if (a.k == 1) {  // (the detector's case: the list is one value)
-        kth = fminf(kth, wave_min_f32(ub));
+        kth = fminf(kth, wave::min_f32(ub));
         lub = lane == 0 ? kth : lub;
       }
       u64 pend = a.k == 1 ? 0ull : __ballot(ub < kth);
       while (pend) {
         const int l = __ffsll((long long)pend) - 1;
         pend &= pend - 1;
-        const float v = lane_of(ub, l);
+        const float v = wave::readlane(ub, l);
         if (!(v < kth)) continue;
         const int pos = __popcll(__ballot(lane < a.k && lub <= v));  // < k: lub[k - 1] = kth > v
         const float up = __shfl_up(lub, 1);
@@ -327,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
           if (lane > pos) lub = up;
           else if (lane == pos) lub = v;
         }
-        kth = lane_of(lub, a.k - 1);
+        kth = wave::readlane(lub, a.k - 1);
       }
       if (lane < 32) s_ub[lane] = lub;
       // candidates: lower bound not above the workgroup's k-th smallest upper bound (which is never below the chip's)
@@ -342,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
           store_sc1(r0, ((u64)(unsigned)slot << 32) | (u64)__float_as_uint(lo));
           store_sc1(r1, (u64)(unsigned)kstar);
         }
-        wave_lds_fence();
+        wave::lds_fence();
         if (lane == 0) *s_cnt = base + __popcll(cb);
       }
     }
@@ -444,13 +441,7 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
       v[i] = j < G ? s_pref[j + 1] : 0;
       sum += v[i];
     }
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(inc, off);
-      if (lane >= off) inc += o;
-    }
-    int run = inc - sum;
+    int run = (int)wave::incl_add_u32((unsigned)sum) - sum;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       const int j = lane * 8 + i;
@@ -466,7 +457,7 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
     const float *L = reinterpret_cast<const float *>(scr + Q1_FIN_AB);
     float *s_redf = reinterpret_cast<float *>(misc + Q1_MISC_RED);
     if (a.k == 1) {
-      t0 = wave_min_f32(t0);
+      t0 = wave::min_f32(t0);
       if (lane == 0) s_redf[wave] = t0;
       __syncthreads();
       tau_ub = fminf(fminf(s_redf[0], s_redf[1]), fminf(s_redf[2], s_redf[3]));
@@ -485,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
           u64 m = head[0];
 #pragma unroll
           for (int i = 1; i < 8; i++) m = head[i] < m ? head[i] : m;
-          const u64 g = wave_min_u64(m);
+          const u64 g = wave::minmax_u64<false>(m);
           if (g == ~0ull) {  // fewer than k bounds at all
             kth = INFINITY;
             break;
@@ -608,7 +599,7 @@ __global__ __launch_bounds__(256, 2) void sc_q1_kernel(Q1Args a) {
           const Res o = s_res[w];
           if (o.d < kBig) topk_insert_dpp(ld, li, ls, lane, a.k, o.d, o.idx, o.shift);
         }
-        const double kd = __longlong_as_double((long long)dev::readlane_u64((u64)__double_as_longlong(ld), a.k - 1));
+        const double kd = wave::readlane(ld, a.k - 1);
         if (lane == 0) *s_tau = kd < (double)tau_ub ? kd : (double)tau_ub;
       }
       __syncthreads();

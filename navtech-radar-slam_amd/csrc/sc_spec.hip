@@ -165,11 +165,6 @@ constexpr float kE1 = 1.02e-3f, kE2 = 1.0e-3f;
 constexpr u64 kNonFinite = 1ull << 63;
 constexpr u64 kMask60 = (1ull << 60) - 1ull;
 
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 template <typename F, int... Is>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, Is...>) {
   (f(std::integral_constant<int, Is>{}), ...);
@@ -249,7 +244,7 @@ __device__ __forceinline__ u64 spectra_of(const float *__restrict__ d, const dou
   }
   u64 m = __ballot(nonzero && lane < NS);
   if (__ballot(bad && lane < NS)) m |= kNonFinite;
-  wave_lds_fence();
+  wave::lds_fence();
   double dc_energy = 0.0;  // this lane's share of sum |X_0|^2
   // One (a, r) pair per lane and pass (80 pairs: lanes 0..63, then 0..15): the pair's 15 column values are read from LDS once
   // and serve all 8 frequencies; a value is normalised where it is read, with the two operations of the first pass
@@ -305,10 +300,9 @@ __device__ __forceinline__ u64 spectra_of(const float *__restrict__ d, const dou
     }
   }
   if (lane < 16) kv[(lane >> 2) * 24 + 20 + (lane & 3)] = (_Float16)0.0f;  // K padding of f = 0
-  wave_lds_fence();
+  wave::lds_fence();
   // energy outside f = 0 (error budget of stage 2): a = n - sum |X_0|^2 / 15, rounded up a little
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) dc_energy += __shfl_xor(dc_energy, off);
+  dc_energy = wave::butterfly(dc_energy, wave::Add{});
   const double a_out = (double)__popcll(m & kMask60) - dc_energy / 15.0;
   sqrt_a = (a_out > 0.0) ? (float)(sqrt(a_out) * (1.0 + 1e-6)) + 1e-6f : 1e-6f;
   return m;

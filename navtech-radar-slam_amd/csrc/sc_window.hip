@@ -375,7 +375,7 @@ __global__ __launch_bounds__(256, WIN_OCC) void sc_window_kernel(WindowArgs a) {
       if (c) s_cand[nc + __popcll(bal & below)] = ub;
       nc += __popcll(bal);
     });
-    dev::wave_lds_fence();
+    wave::lds_fence();
     float tau_w = INFINITY;
     if (nc >= a.k) {  // rank by counting, as for the head; the ranks are a permutation of 0 .. nc - 1
       for (int c0 = 0; c0 < nc; c0 += 64) {
