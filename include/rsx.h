@@ -648,6 +648,88 @@ int rsx_kstrongest_extract_batch_device(rsx_kstrongest *h, const uint8_t *d_imgs
                                         int32_t azimuths_per_image, float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets,
                                         int32_t *d_counts, void *stream);
 
+/* ============================== CA-CFAR / BFAR keypoint extraction =====================
+ * A constant false-alarm rate detector: a range bin is compared with the noise AROUND it, not with a row-wide statistic or a
+ * fixed floor.  The threshold is affine in the local noise estimate Z (the mean of the training cells), T = a Z + b -- BFAR,
+ * the detector CFEAR's authors replaced the fixed floor with (Alhashimi, Adolfsson et al.).  b = 0 is cell-averaging CFAR,
+ * a = 0 is the fixed floor of k-strongest; greatest-of and smallest-of the two sides are the standard variants for clutter
+ * edges and for neighbouring targets.  On each azimuth the k strongest detections are kept, under k-strongest's separation
+ * rule.  Not part of the reference; the rule below is restated in tests/cfar_np.py, which is the arithmetic contract.
+ * Integers only: the keypoints equal the restatement's bit for bit.
+ * Per azimuth row, v[j] = the power byte of range bin j, 0 <= j < cols; t = train, g = guard, A = scale_q8 (a = A / 256),
+ * B = offset, s = min_separation:
+ *   1. key[j] and win[j] exactly as in k-strongest steps 1 and 2: raw power, the window cut at the row's ends
+ *   2. training cells of bin j: left, the bins i with j - g - t <= i <= j - g - 1 and i >= 0; right, the bins i with
+ *      j + g + 1 <= i <= j + g + t and i <= cols - 1.  Their sums and counts are S_L, n_L, S_R, n_R.  The cells are cut at the
+ *      row's ends (they never see metadata bytes, row padding or another row) and run over raw power whatever min_range and
+ *      max_range say
+ *   3. noise (S, n) by mode: RSX_CFAR_CA (0, cell averaging) (S_L + S_R, n_L + n_R); RSX_CFAR_GO (1, greatest-of) the side
+ *      with the larger mean -- left iff S_L n_R >= S_R n_L; RSX_CFAR_SO (2, smallest-of) the side with the smaller mean.  In
+ *      modes 1 and 2 an empty side (n = 0) gives way to the other; on equal means either side gives the same verdict in step 4
+ *   4. detection: 256 n v[j] > A S + 256 B n when n > 0; v[j] > B when n = 0 (a row too short to have any training cell).
+ *      Strict, so a flat row at A = 256 detects nothing.  Within the limits below both sides stay below 2^31: the right side
+ *      is at most 65535 x 32640 + 256 x 255 x 128 = 2 147 418 240
+ *   5. bin j is a candidate iff key[j] == win[j], it is a detection, and min_range <= j < hi (hi as in k-strongest)
+ *   6. steps 4 and 5 of k-strongest: the min(k, #candidates) candidates of highest key in ascending j, rows in row-major order
+ * So A = 0 is k-strongest with z_min = B + 1, and B = 0 is plain CA-CFAR with a = A / 256.
+ * The defaults of scale_q8 and offset come from the study that chose k-strongest's min_separation, on the CPU (restatement ->
+ * oracle front end -> cross-checked ratio matches -> max-clique selection -> ORORA; synth.polar_sequence(11, 5); k = 12,
+ * train = 20, guard = 2, mode 0, min_separation = 5; tools/cfar_defaults_study.py): the setting with the smallest worst pair
+ * error among those whose every pair has status 0.
+ * Translation error decides, the yaw error breaks ties at the millimetre; every pair of every row has status 0:
+ *     setting                    keypoints per scan   cross-checked matches per pair   worst pair error
+ *     k-strongest, z_min = 60    4800                 550 - 722                        0.045 m / 3.9e-3 rad
+ *     A =  512, B =  0           4800                 512 - 681                        0.036 m / 3.8e-3 rad
+ *     A =  512, B = 20           4800                 497 - 666                        0.023 m / 3.3e-3 rad
+ *     A =  512, B = 40           4800                 472 - 651                        0.025 m / 3.6e-3 rad
+ *     A =  768, B =  0           4800                 454 - 592                        0.024 m / 2.8e-3 rad
+ *     A =  768, B = 20           4799 - 4800          413 - 560                        0.021 m / 3.4e-3 rad   <- the defaults
+ *     A =  768, B = 40           4405 - 4488          353 - 470                        0.021 m / 4.4e-3 rad
+ *     A = 1024, B =  0           4665 - 4707          301 - 383                        0.026 m / 3.8e-3 rad
+ *     A = 1024, B = 20           3049 - 3152          200 - 266                        0.028 m / 4.6e-3 rad
+ *     A = 1024, B = 40           1679 - 1792          123 - 160                        0.031 m / 4.9e-3 rad
+ *     A = 1536, B =  0           713 - 772            45 - 60                          0.103 m / 5.4e-3 rad
+ *     A = 1536, B = 20           379 - 406            15 - 30                          0.106 m / 3.1e-3 rad
+ *     A = 1536, B = 40           191 - 218            8 - 16                           0.166 m / 3.3e-3 rad
+ * A synthetic sequence only: on it the detector halves k-strongest's worst pair error with fewer matches; no real radar
+ * data has been through it.
+ * Same argument shapes, output layout, truncation rules and create limits as the k-strongest group above.  Parameters outside
+ * the limits in the struct below return RSX_ERR_BAD_ARG.  Device workspace per handle: as k-strongest's. */
+
+#define RSX_CFAR_CA 0 /* cell averaging: both sides */
+#define RSX_CFAR_GO 1 /* greatest-of: the side with the larger mean */
+#define RSX_CFAR_SO 2 /* smallest-of: the side with the smaller mean */
+
+typedef struct rsx_cfar rsx_cfar;
+
+typedef struct {
+  int32_t k;              /* keypoints per azimuth at most, 1 .. 128 (12) */
+  int32_t train;          /* t, training cells on each side, 1 .. 64 (20) */
+  int32_t guard;          /* g, guard cells on each side between the bin and its training cells, 0 .. 16 (2) */
+  int32_t scale_q8;       /* A = 256 a, 0 .. 65535 (768: a = 3) */
+  int32_t offset;         /* B, 0 .. 255 (20) */
+  int32_t mode;           /* RSX_CFAR_CA / _GO / _SO (RSX_CFAR_CA) */
+  int32_t min_range;      /* first range bin considered for keypoints, >= 0 (58) */
+  int32_t max_range;      /* one past the last range bin considered, >= 0; 0 = cols (0) */
+  int32_t min_separation; /* s, 0 .. 32 (5) */
+  int32_t reserved;       /* 0 */
+} rsx_cfar_params;
+
+int rsx_cfar_default_params(rsx_cfar_params *p);
+/* one handle per image shape: rows (1 .. 4096) azimuths x cols (1 .. 8192) range bins */
+int rsx_cfar_create(int device, int32_t rows, int32_t cols, rsx_cfar **out);
+int rsx_cfar_destroy(rsx_cfar *h);
+int rsx_cfar_extract(rsx_cfar *h, const uint8_t *img, int32_t row_stride, int32_t col_offset, const rsx_cfar_params *params,
+                     const float *azimuths, float resolution, int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_count);
+int rsx_cfar_extract_batch(rsx_cfar *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride, int32_t col_offset,
+                           const rsx_cfar_params *params, const float *azimuths, int32_t azimuths_per_image, float resolution,
+                           int32_t *out_targets, float *out_xy, int32_t max_targets, int32_t *out_counts);
+/* two launches per 128 images, no host synchronisation.  Only bytes inside each image's rows x row_stride bytes are read,
+ * whatever the alignment of d_imgs. */
+int rsx_cfar_extract_batch_device(rsx_cfar *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                                  int32_t col_offset, const rsx_cfar_params *params, const float *d_azimuths, int32_t azimuths_per_image,
+                                  float resolution, int32_t *d_targets, float *d_xy, int32_t max_targets, int32_t *d_counts, void *stream);
+
 /* ============================== CFEAR surface points and registration ==================
  * What the k-strongest detector feeds in CFEAR radar odometry (Adolfsson et al.): no descriptors and no matcher.  The
  * filtered returns of a scan are summarised as ORIENTED SURFACE POINTS -- the mean and the surface normal of the returns
@@ -1040,7 +1122,7 @@ typedef struct {
 typedef struct {
   rsx_orora_result reg;  /* motion between the previous scan and this one: p_previous = R(yaw) p_this + (x, y);
                             reg.status = 3 for the first scan of a sequence (nothing to register against) */
-  int32_t n_keypoints;   /* keypoints of this scan (cen2019, or cen2018 / k-strongest: rsx_odometry_set_cen2018 / _set_kstrongest; only the first max_keypoints are used) */
+  int32_t n_keypoints;   /* keypoints of this scan (cen2019, or cen2018 / k-strongest / CFAR: rsx_odometry_set_cen2018 / _set_kstrongest / _set_cfar; only the first max_keypoints are used) */
   int32_t n_matches;     /* cross-checked ratio matches handed to ORORA */
 } rsx_odometry_scan;
 
@@ -1060,6 +1142,10 @@ int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params);
  * scan.  Independent of estimator and compensation.  At most rows x k keypoints per scan, of which the first max_keypoints
  * are used. */
 int rsx_odometry_set_kstrongest(rsx_odometry *h, const rsx_kstrongest_params *params);
+/* keypoints by CA-CFAR / BFAR with these settings (rsx_cfar above), under the rules of the two setters above: accepted only
+ * while the handle holds no scan, params = NULL goes back to cen2019, independent of estimator, compensation and the CFEAR
+ * switches.  At most rows x k keypoints per scan, of which the first max_keypoints are used. */
+int rsx_odometry_set_cfar(rsx_odometry *h, const rsx_cfar_params *params);
 /* The motion estimator a pair's cross-checked matches go to: ORORA behind the max-clique selection (the default), rigid
  * RANSAC or motion-compensated RANSAC (params = NULL: rsx_ransac_default_params; its MOTION_COMPENSATED flag follows
  * `estimator`).  Independent of the extractor; like it, only accepted while the handle holds no scan.  With a RANSAC

@@ -1,4 +1,4 @@
-"""What the host-side wrappers of the keypoint extractors (cen2018.Cen2018, cen2019.Cen2019, kstrongest.KStrongest) share: the handle, the
+"""What the host-side wrappers of the keypoint extractors (cen2018.Cen2018, cen2019.Cen2019, kstrongest.KStrongest, cfar.Cfar) share: the handle, the
 calls of rsx_<name>_extract / rsx_<name>_extract_batch with their output arrays, and how the results are returned."""
 import ctypes as C
 

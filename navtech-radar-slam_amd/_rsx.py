@@ -111,6 +111,14 @@ class KStrongestParams(C.Structure):
                 ("min_separation", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CfarParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("train", C.c_int32), ("guard", C.c_int32), ("scale_q8", C.c_int32), ("offset", C.c_int32), ("mode", C.c_int32),
+                ("min_range", C.c_int32), ("max_range", C.c_int32), ("min_separation", C.c_int32), ("reserved", C.c_int32)]
+
+
+CFAR_CA, CFAR_GO, CFAR_SO = 0, 1, 2  # rsx_cfar_params.mode (RSX_CFAR_*)
+
+
 class CfearParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("max_condition", C.c_double), ("cos_max_normal_angle", C.c_double), ("huber_delta", C.c_double),
                 ("step_epsilon", C.c_double), ("min_points", C.c_int32), ("max_iterations", C.c_int32), ("min_correspondences", C.c_int32),
@@ -213,6 +221,8 @@ SYMBOLS = [
     "rsx_cen2018_extract_batch", "rsx_cen2018_extract_batch_device", "rsx_cen2018_gauss_weights", "rsx_cen2018_debug_image",
     "rsx_kstrongest_default_params", "rsx_kstrongest_create", "rsx_kstrongest_destroy", "rsx_kstrongest_extract",
     "rsx_kstrongest_extract_batch", "rsx_kstrongest_extract_batch_device", "rsx_odometry_set_kstrongest",
+    "rsx_cfar_default_params", "rsx_cfar_create", "rsx_cfar_destroy", "rsx_cfar_extract", "rsx_cfar_extract_batch",
+    "rsx_cfar_extract_batch_device", "rsx_odometry_set_cfar",
     "rsx_cfear_default_params", "rsx_cfear_create", "rsx_cfear_destroy", "rsx_cfear_surface_points_batch",
     "rsx_cfear_surface_points_batch_device", "rsx_cfear_register_batch", "rsx_cfear_register_batch_device", "rsx_odometry_set_cfear", "rsx_odometry_set_cfear_tracking",
     "rsx_cfear_default_track_params", "rsx_cfear_register_keyframes_batch", "rsx_cfear_register_keyframes_batch_device",
@@ -352,6 +362,13 @@ def lib():
         L.rsx_kstrongest_extract_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(KStrongestParams), vp, i32, C.c_float, vp, vp,
                                                           i32, vp, vp]
         L.rsx_odometry_set_kstrongest.argtypes = [vp, C.POINTER(KStrongestParams)]
+        L.rsx_cfar_default_params.argtypes = [C.POINTER(CfarParams)]
+        L.rsx_cfar_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+        L.rsx_cfar_destroy.argtypes = [vp]
+        L.rsx_cfar_extract.argtypes = [vp, vp, i32, i32, C.POINTER(CfarParams), vp, C.c_float, vp, vp, i32, C.POINTER(i32)]
+        L.rsx_cfar_extract_batch.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(CfarParams), vp, i32, C.c_float, vp, vp, i32, vp]
+        L.rsx_cfar_extract_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, C.POINTER(CfarParams), vp, i32, C.c_float, vp, vp, i32, vp, vp]
+        L.rsx_odometry_set_cfar.argtypes = [vp, C.POINTER(CfarParams)]
         L.rsx_cfear_default_params.argtypes = [C.POINTER(CfearParams)]
         L.rsx_cfear_create.argtypes = [C.c_int, C.POINTER(vp)]
         L.rsx_cfear_destroy.argtypes = [vp]

@@ -1,4 +1,4 @@
-// keypoints_host.h -- what the keypoint extractors (cen2018.hip, cen2019.hip, kstrongest.hip) and the odometry share: the check of a polar image
+// keypoints_host.h -- what the keypoint extractors (cen2018.hip, cen2019.hip, kstrongest.hip, cfar.hip) and the odometry share: the check of a polar image
 // layout, the image upload, the kernel that packs the per-row keypoints, the staging of the host-buffer entries, and the host
 // scaffold of an extractor (its handle and the bodies of its create / destroy / extract entries, written once: "the scaffold" below).
 #pragma once
@@ -118,7 +118,7 @@ struct KeypointStaging {
   }
 };
 
-// ---- the scaffold: the host side that the three extractors have in common ----
+// ---- the scaffold: the host side that the extractors have in common ----
 // An extractor's own file keeps its kernels, its workspaces and three things the templates below are handed:
 //   its parameter type P (deduced from the entry's `params`);
 //   resolve: int(const P *params, P *p) -- the defaults, then *params over them when given, then the check of the result
@@ -130,7 +130,7 @@ struct KeypointStaging {
 // contract (include/rsx.h) and the one-handle, many-streams contract -- the lock, the device, StreamOrder::enter before anything
 // is enqueued or reserved -- are written here and nowhere else.
 
-// what every extractor handle holds; rsx_cen2018, rsx_cen2019 and rsx_kstrongest add their workspaces
+// what every extractor handle holds; rsx_cen2018, rsx_cen2019, rsx_kstrongest and rsx_cfar add their workspaces
 struct KeypointHandle {
   int device = 0, rows = 0, cols = 0;
   std::mutex mu;
@@ -233,7 +233,7 @@ int keypoints_extract(H *h, Resolve resolve, Extract extract, const uint8_t *img
 }
 
 // the launch chain of an extractor whose row kernel leaves up to row_cap uint16 range bins per row in h->row_kp and their number in
-// h->row_n (cen2018, k-strongest): per sub-batch launch_rows(b0, n) -- the row kernel over images b0 .. b0 + n -- then kp_pack
+// h->row_n (cen2018, k-strongest, CFAR): per sub-batch launch_rows(b0, n) -- the row kernel over images b0 .. b0 + n -- then kp_pack
 template <typename H, typename LaunchRows>
 int rows_then_pack(H *h, int row_cap, int nb, const float *d_az, int64_t az_stride, float resolution, int32_t max_targets, int *d_targets,
                    float *d_xy, int *d_counts, hipStream_t s, LaunchRows &&launch_rows) {

@@ -7,7 +7,8 @@
 // until the final composition: a WINDOW of n scans goes through each stage in ONE launch chain --
 //     rsx_<extractor>_extract_batch_device      n images   the ONE selected extractor (rsx_odometry::keypoints): cen2019
 //                                               (csrc/cen2019.hip) until rsx_odometry_set_cen2018 (csrc/cen2018.hip) or
-//                                               rsx_odometry_set_kstrongest (csrc/kstrongest.hip) selects another
+//                                               rsx_odometry_set_kstrongest (csrc/kstrongest.hip) or rsx_odometry_set_cfar
+//                                               (csrc/cfar.hip) selects another
 //     rsx_frontend_cartesian_batch_device       n images   (csrc/frontend.hip)
 //     rsx_frontend_describe_batch_device        n keypoint sets
 //     rsx_frontend_match_consecutive_device     all consecutive pairs, both directions
@@ -34,6 +35,7 @@
 #include <new>
 
 #include "cen2018.h"
+#include "cfar.h"
 #include "cfear.h"
 #include "keypoints_host.h"
 #include "kstrongest.h"
@@ -274,12 +276,14 @@ struct rsx_odometry {
   std::mutex mu;
   rsx::Stream lane_stream[N_LANES], match_stream, copy_stream;
   rsx::Event ev_up, ev_e[N_SETS], ev_m[N_SETS];
-  enum class Keypoints { cen2019, cen2018, kstrongest } keypoints = Keypoints::cen2019;  // the extractor E(g) runs (set_keypoints)
+  enum class Keypoints { cen2019, cen2018, kstrongest, cfar } keypoints = Keypoints::cen2019;  // the extractor E(g) runs (set_keypoints)
   rsx::Owned<rsx_cen2019, rsx_cen2019_destroy> cen[N_LANES];  // (its parameters: prm.cen)
   rsx::Owned<rsx_cen2018, rsx_cen2018_destroy> cen18[N_LANES];  // created at the first rsx_odometry_set_cen2018, kept across switches
   rsx_cen2018_params cen18_prm{};
   rsx::Owned<rsx_kstrongest, rsx_kstrongest_destroy> kstr[N_LANES];  // created at the first rsx_odometry_set_kstrongest, kept across switches
   rsx_kstrongest_params kstr_prm{};
+  rsx::Owned<rsx_cfar, rsx_cfar_destroy> cfar[N_LANES];  // created at the first rsx_odometry_set_cfar, kept across switches
+  rsx_cfar_params cfar_prm{};
   rsx::Owned<rsx_frontend, rsx_frontend_destroy> fe[N_LANES];
   rsx::Owned<rsx_orora, rsx_orora_destroy> reg;
   int estimator = RSX_ESTIMATOR_ORORA;
@@ -387,6 +391,7 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
     case Keypoints::cen2019: RSX_TRY(keypoints(rsx_cen2019_extract_batch_device, h->cen[lane].get(), &h->prm.cen)); break;
     case Keypoints::cen2018: RSX_TRY(keypoints(rsx_cen2018_extract_batch_device, h->cen18[lane].get(), &h->cen18_prm)); break;
     case Keypoints::kstrongest: RSX_TRY(keypoints(rsx_kstrongest_extract_batch_device, h->kstr[lane].get(), &h->kstr_prm)); break;
+    case Keypoints::cfar: RSX_TRY(keypoints(rsx_cfar_extract_batch_device, h->cfar[lane].get(), &h->cfar_prm)); break;
   }
   const bool cfear = h->estimator == RSX_ESTIMATOR_CFEAR;
   constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
@@ -609,7 +614,7 @@ int push_windows(rsx_odometry *h, int32_t n_scans, rsx_odometry_scan *out, float
   return st;
 }
 
-// rsx_odometry_set_cen2018 / rsx_odometry_set_kstrongest: params == NULL selects cen2019 again; otherwise extractor `which` with
+// rsx_odometry_set_cen2018 / rsx_odometry_set_kstrongest / rsx_odometry_set_cfar: params == NULL selects cen2019 again; otherwise extractor `which` with
 // *params (checked), its handle of every lane (h->*lanes) created when first needed and kept across later switches
 template <typename P, typename H, auto Destroy>
 int set_keypoints(rsx_odometry *h, Keypoints which, const P *params, int (*check_params)(const P &), int (*create)(int, int32_t, int32_t, H **),
@@ -720,6 +725,10 @@ int rsx_odometry_set_cen2018(rsx_odometry *h, const rsx_cen2018_params *params) 
 
 int rsx_odometry_set_kstrongest(rsx_odometry *h, const rsx_kstrongest_params *params) try {
   return set_keypoints(h, Keypoints::kstrongest, params, rsx::kstrongest_check_params, rsx_kstrongest_create, &rsx_odometry::kstr, &rsx_odometry::kstr_prm);
+} RSX_CATCH_ALL
+
+int rsx_odometry_set_cfar(rsx_odometry *h, const rsx_cfar_params *params) try {
+  return set_keypoints(h, Keypoints::cfar, params, rsx::cfar_check_params, rsx_cfar_create, &rsx_odometry::cfar, &rsx_odometry::cfar_prm);
 } RSX_CATCH_ALL
 
 int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_params *params) try {

@@ -24,6 +24,9 @@
 // (upstream's keypoint_extraction = 0: rsx_odometry_set_cen2018 on the windowed path, rsx_cen2018_extract on --per-scan).
 // `--keypoints kstrongest` (with `--k`, `--z-min`, `--min-separation`; min_range stays 58) keeps on every azimuth the k strongest
 // returns above a power floor (rsx_odometry_set_kstrongest on the windowed path, rsx_kstrongest_extract on --per-scan).
+// `--keypoints cfar` (with `--cfar-train`, `--cfar-guard`, `--cfar-scale`, `--cfar-offset`, `--cfar-mode ca|go|so`, and the `--k` and
+// `--min-separation` of kstrongest; min_range stays 58) keeps on every azimuth the k strongest returns above a x the mean of the
+// training cells around them + b (CA-CFAR / BFAR: rsx_odometry_set_cfar on the windowed path, rsx_cfar_extract on --per-scan).
 // `--estimator ransac|mcransac` (with `--ransac-threshold`, `--ransac-iterations`, `--scan-period`) hands a pair's matches to
 // rigid RANSAC or motion-compensated RANSAC instead of the max-clique selection + ORORA (upstream's other estimators:
 // rsx_odometry_set_estimator, windowed path only; mcransac takes a match's time from the azimuth rows of its keypoints).
@@ -160,6 +163,8 @@ int main(int argc, char **argv) {
     rsx_cen2018_default_params(&c18);
     rsx_kstrongest_params ksp;
     rsx_kstrongest_default_params(&ksp);
+    rsx_cfar_params cfa;
+    rsx_cfar_default_params(&cfa);
     rsx_ransac_params rsp;
     rsx_ransac_default_params(&rsp);
     rsx_cfear_params cfp;
@@ -182,13 +187,21 @@ int main(int argc, char **argv) {
       else if (a == "--matcher" && i + 1 < argc) matcher = argv[++i];  // orb (default) | nn
       else if (a == "--window" && i + 1 < argc) window = std::atoi(argv[++i]);    // scans per rsx_odometry_push (default: two of the library's windows)
       else if (a == "--threads" && i + 1 < argc) threads = std::atoi(argv[++i]);  // PNG decode threads (default: twice the usable cores, <= 64)
-      else if (a == "--keypoints" && i + 1 < argc) keypoints = argv[++i];         // cen2019 (default) | cen2018 | kstrongest
+      else if (a == "--keypoints" && i + 1 < argc) keypoints = argv[++i];         // cen2019 (default) | cen2018 | kstrongest | cfar
       else if (a == "--zq" && i + 1 < argc) c18.zq = (float)std::atof(argv[++i]);  // cen2018: threshold in noise sigmas (3.0)
       else if (a == "--sigma-gauss" && i + 1 < argc) c18.sigma_gauss = std::atoi(argv[++i]);  // cen2018: Gaussian sigma in range bins, odd (17)
-      else if (a == "--k" && i + 1 < argc) ksp.k = std::atoi(argv[++i]);          // kstrongest: keypoints per azimuth at most (12)
+      else if (a == "--k" && i + 1 < argc) ksp.k = std::atoi(argv[++i]);          // kstrongest, cfar: keypoints per azimuth at most (12)
       else if (a == "--z-min" && i + 1 < argc) ksp.z_min = std::atoi(argv[++i]);  // kstrongest: power floor (60)
-      else if (a == "--min-separation" && i + 1 < argc) ksp.min_separation = std::atoi(argv[++i]);  // kstrongest: range bins between two keypoints of an azimuth (5)
-      else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac | cfear
+      else if (a == "--min-separation" && i + 1 < argc) ksp.min_separation = std::atoi(argv[++i]);  // kstrongest, cfar: range bins between two keypoints of an azimuth (5)
+      else if (a == "--cfar-train" && i + 1 < argc) cfa.train = std::atoi(argv[++i]);  // cfar: training cells on each side (20)
+      else if (a == "--cfar-guard" && i + 1 < argc) cfa.guard = std::atoi(argv[++i]);  // cfar: guard cells on each side (2)
+      else if (a == "--cfar-scale" && i + 1 < argc) cfa.scale_q8 = (int32_t)std::lround(std::atof(argv[++i]) * 256.0);  // cfar: a of T = a Z + b, to the nearest 1/256 (3)
+      else if (a == "--cfar-offset" && i + 1 < argc) cfa.offset = std::atoi(argv[++i]);  // cfar: b of T = a Z + b (20)
+      else if (a == "--cfar-mode" && i + 1 < argc) {  // cfar: ca (default) | go | so, the noise estimate: both sides, the greater, the smaller
+        const std::string v = argv[++i];
+        if (v != "ca" && v != "go" && v != "so") die("--cfar-mode must be ca, go or so");
+        cfa.mode = v == "ca" ? RSX_CFAR_CA : (v == "go" ? RSX_CFAR_GO : RSX_CFAR_SO);
+      } else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac | cfear
       else if (a == "--cfear-radius" && i + 1 < argc) cfp.radius = std::atof(argv[++i]);               // cfear: cell side and search radius [m] (3.5)
       else if (a == "--cfear-normal-angle" && i + 1 < argc) cfp.cos_max_normal_angle = std::cos(std::atof(argv[++i]) * 3.14159265358979323846 / 180.0);  // cfear: largest angle between matched normals [deg] (30)
       else if (a == "--cfear-huber" && i + 1 < argc) cfp.huber_delta = std::atof(argv[++i]);           // cfear: the loss's threshold, Huber's or Cauchy's [m; with p2d dimensionless] (0.1)
@@ -229,7 +242,7 @@ int main(int argc, char **argv) {
     }
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
-      die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--window W] [--threads T] "
+      die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest|cfar] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--cfar-train T] [--cfar-guard G] [--cfar-scale A] [--cfar-offset B] [--cfar-mode ca|go|so] [--window W] [--threads T] "
           "[--estimator orora|ransac|mcransac|cfear] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-cost p2l|p2p|p2d] [--cfear-loss huber|cauchy|none] [--cfear-weights] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--cfear-compensate] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
           "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
@@ -322,8 +335,11 @@ int main(int argc, char **argv) {
       pyaw += r.yaw;
     };
     if (matcher != "nn" && matcher != "orb") die("--matcher must be orb or nn");
-    if (keypoints != "cen2019" && keypoints != "cen2018" && keypoints != "kstrongest") die("--keypoints must be cen2019, cen2018 or kstrongest");
-    const bool use_c18 = keypoints == "cen2018", use_ks = keypoints == "kstrongest";
+    if (keypoints != "cen2019" && keypoints != "cen2018" && keypoints != "kstrongest" && keypoints != "cfar")
+      die("--keypoints must be cen2019, cen2018, kstrongest or cfar");
+    const bool use_c18 = keypoints == "cen2018", use_ks = keypoints == "kstrongest", use_cfar = keypoints == "cfar";
+    cfa.k = ksp.k;  // --k and --min-separation are the one pair of flags of both
+    cfa.min_separation = ksp.min_separation;
     if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac" && estimator != "cfear") die("--estimator must be orora, ransac, mcransac or cfear");
     if (estimator != "orora" && (matcher != "orb" || per_scan)) die("--estimator " + estimator + " runs on the windowed path only (not with --per-scan / --matcher nn)");
     if (cfear_track && estimator != "cfear") die("--cfear-keyframes, --cfear-keyframe-distance, --cfear-keyframe-rotation, --cfear-no-prediction and --cfear-compensate need --estimator cfear");
@@ -360,6 +376,7 @@ int main(int argc, char **argv) {
       check(rsx_odometry_create(&op, rows, cols, &odo), "rsx_odometry_create");
       if (use_c18) check(rsx_odometry_set_cen2018(odo, &c18), "rsx_odometry_set_cen2018");
       if (use_ks) check(rsx_odometry_set_kstrongest(odo, &ksp), "rsx_odometry_set_kstrongest");
+      if (use_cfar) check(rsx_odometry_set_cfar(odo, &cfa), "rsx_odometry_set_cfar");
       if (estimator == "cfear") check(rsx_odometry_set_cfear(odo, &cfp), "rsx_odometry_set_cfear");
       else if (estimator != "orora")
         check(rsx_odometry_set_estimator(odo, estimator == "ransac" ? RSX_ESTIMATOR_RANSAC : RSX_ESTIMATOR_MCRANSAC, &rsp), "rsx_odometry_set_estimator");
@@ -545,6 +562,7 @@ int main(int argc, char **argv) {
     rsx_cen2019 *cen = nullptr;
     rsx_cen2018 *cen18 = nullptr;
     rsx_kstrongest *kstr = nullptr;
+    rsx_cfar *cfar = nullptr;
     rsx_orora *reg = nullptr;
     rsx_frontend *fe = nullptr;
     const bool use_orb = matcher != "nn";
@@ -558,10 +576,11 @@ int main(int argc, char **argv) {
     for (size_t fi = 0; fi < files.size(); fi++) {
       int w = 0, h = 0;
       const std::vector<uint8_t> img = read_png_gray8(dir + "/" + files[fi], &w, &h);
-      if (!cen && !cen18 && !kstr) {
+      if (!cen && !cen18 && !kstr && !cfar) {
         rows = h;
         cols = w - kMeta;
         if (use_ks) check(rsx_kstrongest_create(device, rows, cols, &kstr), "rsx_kstrongest_create");
+        else if (use_cfar) check(rsx_cfar_create(device, rows, cols, &cfar), "rsx_cfar_create");
         else if (use_c18) check(rsx_cen2018_create(device, rows, cols, &cen18), "rsx_cen2018_create");
         else check(rsx_cen2019_create(device, rows, cols, &cen), "rsx_cen2019_create");
         if (use_orb) check(rsx_frontend_create(device, rows, cols, nullptr, &fe), "rsx_frontend_create");
@@ -581,6 +600,8 @@ int main(int argc, char **argv) {
       if (use_ks)
         check(rsx_kstrongest_extract(kstr, img.data(), w, kMeta, &ksp, az.data(), kResolution, targets.data(), xy.data(), 200000, &n),
               "rsx_kstrongest_extract");
+      else if (use_cfar)
+        check(rsx_cfar_extract(cfar, img.data(), w, kMeta, &cfa, az.data(), kResolution, targets.data(), xy.data(), 200000, &n), "rsx_cfar_extract");
       else if (use_c18)
         check(rsx_cen2018_extract(cen18, img.data(), w, kMeta, &c18, az.data(), kResolution, targets.data(), xy.data(), 200000, &n),
               "rsx_cen2018_extract");
@@ -650,6 +671,7 @@ int main(int argc, char **argv) {
     rsx_cen2019_destroy(cen);
     rsx_cen2018_destroy(cen18);
     rsx_kstrongest_destroy(kstr);
+    rsx_cfar_destroy(cfar);
     rsx_orora_destroy(reg);
     rsx_frontend_destroy(fe);
     return 0;

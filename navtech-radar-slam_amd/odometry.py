@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, CfearParams, CfearTrackParams, KStrongestParams, MocompParams,
+from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, CfarParams, CfearParams, CfearTrackParams, KStrongestParams, MocompParams,
                    OdometryParams, RansacParams, check, lib)
 
 ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_* ("cfear", RSX_ESTIMATOR_CFEAR, has a setter of its own)
@@ -18,8 +18,8 @@ def default_params():
 
 
 class Odometry:
-    """keypoints: "cen2019" (default), "cen2018" or "kstrongest"; cen2018: its Cen2018Params (None: cen2018.default_params());
-    kstrongest: its KStrongestParams (None: kstrongest.default_params()).
+    """keypoints: "cen2019" (default), "cen2018", "kstrongest" or "cfar"; cen2018: its Cen2018Params (None: cen2018.default_params());
+    kstrongest: its KStrongestParams (None: kstrongest.default_params()); cfar: its CfarParams (None: cfar.default_params()).
     estimator: "orora" (default), "ransac", "mcransac" or "cfear"; ransac: the RANSAC estimators' RansacParams (None:
     ransac.default_params()); cfear: CfearParams (None: cfear.default_params()): CFEAR's surface points and point-to-line
     registration in place of descriptors, matcher and estimator (rsx_odometry_set_cfear; pair it with keypoints="kstrongest",
@@ -35,9 +35,9 @@ class Odometry:
 
     def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
                  exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None, cfear=None, cfear_track=None,
-                 cfear_compensate=False):
-        if keypoints not in ("cen2019", "cen2018", "kstrongest"):
-            raise ValueError("keypoints must be cen2019, cen2018 or kstrongest")
+                 cfear_compensate=False, cfar=None):
+        if keypoints not in ("cen2019", "cen2018", "kstrongest", "cfar"):
+            raise ValueError("keypoints must be cen2019, cen2018, kstrongest or cfar")
         if estimator not in ESTIMATORS and estimator != "cfear":
             raise ValueError("estimator must be orora, ransac, mcransac or cfear")
         if compensate is not None and compensate not in COMPENSATIONS:
@@ -56,6 +56,8 @@ class Odometry:
             self.set_cen2018(cen2018)
         if keypoints == "kstrongest":
             self.set_kstrongest(kstrongest)
+        if keypoints == "cfar":
+            self.set_cfar(cfar)
         if cfear_compensate and estimator != "cfear":
             raise ValueError("cfear_compensate needs estimator=\"cfear\"")
         if estimator == "cfear":
@@ -128,6 +130,11 @@ class Odometry:
         """Switch to k-strongest keypoints (kstrongest: KStrongestParams or None for the defaults) in place of whichever extractor
         was selected, or back to cen2019 with off=True.  Only while the handle holds no scan (fresh, or after reset())."""
         self._set(self._L.rsx_odometry_set_kstrongest, self._L.rsx_kstrongest_default_params, KStrongestParams, kstrongest, off)
+
+    def set_cfar(self, cfar=None, off=False):
+        """Switch to CA-CFAR / BFAR keypoints (cfar: CfarParams or None for the defaults) in place of whichever extractor was
+        selected, or back to cen2019 with off=True.  Only while the handle holds no scan (fresh, or after reset())."""
+        self._set(self._L.rsx_odometry_set_cfar, self._L.rsx_cfar_default_params, CfarParams, cfar, off)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
