@@ -97,10 +97,11 @@ typedef struct {
    * score every entry exactly, 2 = always the batched filter chain, 3 = the single-query path wherever it applies (<= 16
    * queries per call; auto otherwise).  Results are identical in every mode. */
   int32_t filter_mode;
-  /* which form of the filter: 0 = default (3: spectral, two waves per SIMD), 1 = direct (60-shift correlation as one K = 1200
-   * MFMA GEMM per shift), 2 = spectral (Z15 DFT + direct Z4 correlation, ~6x fewer MFMAs), 3 = the spectral form
-   * with two waves per SIMD (the entry tile split by frequency over a wave pair; same bounds bit for bit).  All give
-   * valid lower bounds of the same quantity; results are identical. */
+  /* which form of the filter: 0 = default (3: spectral), 1 = direct (60-shift correlation as one K = 1200 MFMA GEMM per
+   * shift), 3 = spectral (Z15 DFT + direct Z4 correlation, ~6x fewer MFMAs; two waves per SIMD, the entry tile split by
+   * frequency over a wave pair), 2 = a synonym of 3, kept for callers: it named the spectral kernel with one wave per SIMD,
+   * which gave the same bounds bit for bit and is gone.  All give valid lower bounds of the same quantity; results are
+   * identical. */
   int32_t filter_kind;
   /* summation order of the sums the reference takes through Eigen (mean, norm, dot): a property of how the REFERENCE was
    * built, which the bit-exact contract follows.  RSX_SC_SUM_EIGEN_SSE2 (0, default) = the reference as its CMakeLists.txt

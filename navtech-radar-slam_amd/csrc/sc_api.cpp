@@ -266,18 +266,17 @@ struct ProfScope {
   }
 };
 
-// 2 = the spectral form with two waves per SIMD (sc_spec2_filter_kernel: same images, same bounds bit for bit; the default
-// since round 4: 1.76 against 2.05 ms per 8192 x 9970 launch on the same box)
+// 2 = the spectral form, sc_spec2_filter_kernel (two waves per SIMD; the default since round 4: 1.76 against 2.05 ms per
+// 8192 x 9970 launch for the one-wave-per-SIMD kernel it replaced, same images, same bounds bit for bit)
 constexpr int kDefaultFilterKind = 2;
-// which form of the lower-bound filter: 0 = direct (sc_filter.hip), 1 = spectral (sc_spec.hip, the default:
-// same bounds up to a slightly larger error budget, ~6x fewer MFMAs).  rsx_sc_params.filter_kind or
-// RSX_SC_FILTER_KIND=direct|spectral override.
+// which form of the lower-bound filter: 0 = direct (sc_filter.hip), 1 and 2 = spectral (sc_spec.hip, the default:
+// same bounds up to a slightly larger error budget, ~6x fewer MFMAs; 1 named the one-wave-per-SIMD kernel and is kept
+// as a synonym of 2 for callers that pass it).  rsx_sc_params.filter_kind or RSX_SC_FILTER_KIND=direct|spectral override.
 int filter_kind_of(const rsx_sc *h) {
   static const int env = [] {
     const char *e = rsx::exp_env("RSX_SC_FILTER_KIND");
     if (!e || !*e) return -1;
-    if (e[0] == '2' || (e[0] == 's' && std::strstr(e, "2"))) return 2;  // spectral2 / spec2
-    return (e[0] == 's' || e[0] == '1') ? 1 : 0;
+    return (e[0] == 's' || e[0] == '1' || e[0] == '2') ? kDefaultFilterKind : 0;
   }();
   if (h->p.filter_kind) return h->p.filter_kind - 1;
   return env >= 0 ? env : kDefaultFilterKind;
@@ -301,14 +300,13 @@ int run_filter(rsx_sc *h, const QueryView &q, int64_t n_items, lb_t *lb, int64_t
   }
   if (plan) RSX_TRY(h->w->f_plan.reserve(filter_plan_bytes(n_items), s, false));
   if (filter_kind_of(h) >= 1) {
-    const bool two_waves = filter_kind_of(h) == 2;
-    h->prof_kernel = two_waves ? spec2_filter_kernel_name() : spec_filter_kernel_name();
+    h->prof_kernel = spec2_filter_kernel_name();
     RSX_TRY(launch_spec_query_images(q.desc, q.norm, q.nq, h->w->f_qimg.p, h->sp_tw.as<double>(), s));
     const int32_t *qmin = nullptr;
     const int64_t *cum = nullptr;
     if (plan) RSX_TRY(launch_filter_plan(db, *plan, q.nq, n_items, 4, h->w->f_plan.p, &qmin, &cum, s));
     ProfScope ps(&h->prof, s);
-    RSX_TRY(launch_spec_filter(db, h->w->f_qimg.p, q.nq, n_items, lb, ld, qmin, cum, s, two_waves));
+    RSX_TRY(launch_spec_filter(db, h->w->f_qimg.p, q.nq, n_items, lb, ld, qmin, cum, s));
     ps.stop();
     return RSX_OK;
   }
@@ -682,7 +680,7 @@ int rsx_sc_create(const rsx_sc_params *p, rsx_sc **out) try {
   if (d.filter_mode < 0 || d.filter_mode > 3) return fail(RSX_ERR_BAD_ARG, "filter_mode must be 0 (auto), 1 (off), 2 (force) or 3 (single-query path)");
   if (d.sum_order < 0 || d.sum_order > RSX_SC_SUM_EIGEN34_AVX_FMA) return fail(RSX_ERR_BAD_ARG, "sum_order must be RSX_SC_SUM_EIGEN_SSE2, _SEQ, _EIGEN_AVX_FMA or _EIGEN34_AVX_FMA");
   if (d.filter_kind < 0 || d.filter_kind > 3)
-    return fail(RSX_ERR_BAD_ARG, "filter_kind must be 0 (auto), 1 (direct), 2 (spectral) or 3 (spectral, two waves per SIMD)");
+    return fail(RSX_ERR_BAD_ARG, "filter_kind must be 0 (auto), 1 (direct), 2 or 3 (spectral)");
   RSX_TRY(check_device(d.device));
   std::unique_ptr<rsx_sc> h(new (std::nothrow) rsx_sc());
   if (!h) return fail(RSX_ERR_OOM, "host alloc");

@@ -208,11 +208,9 @@ int launch_spec_twiddles(double *tw, hipStream_t s);
 int launch_spec_db_images(const float *desc, const double *norm, int64_t first, int64_t count, void *spT, float *aux,
                           const double *tw, hipStream_t s);
 int launch_spec_query_images(const float *desc, const double *norm, int32_t nq, void *qimg, const double *tw, hipStream_t s);
-// two_waves: sc_spec2_filter_kernel (two waves per SIMD, the entry tile split by frequency) instead of sc_spec_filter_kernel;
-// same images, same bounds bit for bit
+// sc_spec2_filter_kernel: two waves per SIMD, the entry tile split by frequency
 int launch_spec_filter(const DbView &db, const void *qimg, int32_t nq, int64_t n_items, lb_t *lb, int64_t ld_lb,
-                       const int32_t *tb_qmin, const int64_t *tb_cum, hipStream_t s, bool two_waves);
-const char *spec_filter_kernel_name();
+                       const int32_t *tb_qmin, const int64_t *tb_cum, hipStream_t s);
 const char *spec2_filter_kernel_name();
 
 // ---- window previews of the short lists on the matrix cores (sc_window.hip) ----

@@ -51,12 +51,12 @@
 //        L~ = 1 - max_k S_k u(n_eff(k)) - (kE1 sqrt(n_q n_e) + kE2 sqrt(a_q a_e)) / n_lo + filter_eps()
 //   so that the direct filter's contract (L~ - filter_eps() <= L) holds unchanged downstream.
 //
-// Mapping: one wave per 32 entries (76 B fragments = 304 registers of entry spectra: 64 fragments in the AGPRs,
-// 4 in VGPRs, the first 8 parked in LDS), 4 waves = 128 entries per block, one wave per SIMD; queries
-// streamed through LDS in tiles of 4 (three tile buffers, global_load_lds two tiles ahead, counted vmcnt +
-// raw s_barrier).  Per (4 queries x 32 entries): 76 stage-1 MFMAs (one ds_read_b128 A fragment each, hand-
-// issued ring) + 16 stage-2 MFMAs + 8 (double-length fp8) mask MFMAs, against 600 MFMAs for the same pairs
-// in the direct filter.  DESIGN.md 4.1b has the cycle budget of a tile and what limits it.
+// Mapping (sc_spec2_filter_kernel, further down): 128 entries per 512-thread block; the 76 B fragments of a 32-entry
+// tile (304 registers of entry spectra) are split by frequency over the two waves that share a SIMD; queries
+// streamed through LDS in tiles of 4 (three tile buffers, global_load_lds a tile ahead, raw s_barrier).  Per
+// (4 queries x 32 entries): 76 stage-1 MFMAs (one ds_read_b128 A fragment each, hand-issued ring) + 16 stage-2
+// MFMAs + 8 (double-length fp8) mask MFMAs, against 600 MFMAs for the same pairs in the direct filter.
+// DESIGN.md 4.1c has the cycle budget of a tile and what limits it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -125,36 +125,8 @@ constexpr int SP_PHASE_BYTES = SP_MASKREG_OFF + SP_QPP * SP_MASK_BYTES;  // 2662
 __host__ __device__ constexpr int64_t sp_nq4(int32_t nq) { return ((int64_t)nq + 3) / 4 * 4; }
 __host__ __device__ constexpr int64_t sp_masks_at(int32_t nq) { return sp_nq4(nq) * SP_QS; }
 __host__ __device__ constexpr int64_t sp_flags_at(int32_t nq) { return sp_nq4(nq) * (SP_QS + SP_MASK_BYTES); }
-#ifndef SP_OPT_NBUF
-#define SP_OPT_NBUF 3
-#endif
-#ifndef SP_OPT_LOCKSTEP
-#define SP_OPT_LOCKSTEP 0   // 1: one unit per workgroup, query ranges outermost (no gain measured: the query stream is not L2-bound)
-#endif
-constexpr int SP_NBUF = SP_OPT_NBUF;                // LDS tile buffers: the DMA runs SP_NBUF - 1 tiles ahead
-constexpr int SP_DMA_PER_Q = 2;  // DMA pieces a wave issues in the tail of one query
-static_assert((SP_STREAM_PIECES + SP_MASK_PIECES + 3) / 4 <= 11, "wait_vmcnt_le covers <= 11 DMA instructions per wave and tile");
-static_assert((SP_STREAM_PIECES + SP_MASK_PIECES + 3) / 4 <= SP_DMA_PER_Q * SP_QPT, "the tail issues SP_DMA_PER_Q DMA pieces per query");
-#ifndef SP_OPT_BV
-#define SP_OPT_BV 12   // VGPR-resident B fragments are SP_B_LDS .. SP_OPT_BV-1
-#endif
-constexpr int SP_B_VGPR = SP_OPT_BV;  // B fragments kept in VGPRs; the rest live in AGPRs
-// 76 B fragments = 304 registers: 64 fragments fill the 256 AGPRs, 4 sit in VGPRs, and the first SP_B_LDS
-// (the 6 K-steps of f = 0 and the first 2 of f = 1) are parked in LDS (8 KiB per wave) and fetched with the A fragments of each tile
-// -- left to the register allocator they were spilled to scratch and reloaded every tile, and every scratch
-// reload drains the vmcnt queue (DMA and bound stores in flight)
-#ifndef SP_OPT_BLDS
-#define SP_OPT_BLDS 8
-#endif
-constexpr int SP_B_LDS = SP_OPT_BLDS;
-constexpr int SP_BPARK_OFF = 0;                              // before the tile buffers: a wrapped read address (row address
-                                                             // minus the stream length) then never runs below LDS address 0
-constexpr int SP_TILES_OFF = 4 * SP_B_LDS * 1024;
-constexpr int SP_LDS_BYTES = SP_TILES_OFF + SP_NBUF * SP_PHASE_BYTES;
-static_assert(SP_TILES_OFF >= SP_VS, "wrapped addresses stay non-negative");
-static_assert(SP_LDS_BYTES <= 160 * 1024, "LDS budget");
 
-// -DRSX_SPEC_INSTRUMENT=1 compiles in the timing experiments (RSX_SPEC_DBG: run without the DMA / the stores) and
+// -DRSX_SPEC_INSTRUMENT=1 compiles in the timing experiments (RSX_SPEC_DBG: one wave of a pair prioritised / idle) and
 // the per-region s_memtime profile (RSX_SPEC_PROF); they cost registers, so normal builds leave them out
 #ifndef RSX_SPEC_INSTRUMENT
 #define RSX_SPEC_INSTRUMENT 0
@@ -433,20 +405,20 @@ struct SpecArgs {
   const char *qimg;
   int64_t n_items;
   int32_t nq;
-  int32_t unit_len;   // no plan: workgroup u = (query range u / ntb, tile-block u % ntb), unit_len query tiles per range
   lb_t *lb;
   int64_t ld_lb;
   float eps_direct;
-  int32_t dbg;  // timing experiments of RSX_SPEC_INSTRUMENT builds (RSX_SPEC_DBG): 4 = no DMA, 8 = no stores
-  unsigned long long *prof;  // RSX_SPEC_PROF: s_memtime sums per region of (workgroup 0, wave 0)
+  int32_t dbg;  // timing experiments of RSX_SPEC_INSTRUMENT builds (RSX_SPEC_DBG): 1 / 2 = priority to the late / the early
+                // waves, 4 / 8 = the early / the late waves idle
+  unsigned long long *prof;  // RSX_SPEC_PROF: s_memtime sums per region of waves 0 and 4 of workgroup 0 (8 values each)
   const int32_t *tb_qmin;  // optional plan, in query-tile units (see sc_filter.hip)
   const int64_t *tb_cum;
-  // sc_spec2_filter_kernel without a plan (xcd_len > 0): query tiles per XCD and per sub-range (see the kernel's work split)
+  // without a plan (xcd_len > 0): query tiles per XCD and per sub-range (see the kernel's work split)
   int32_t xcd_nqt, xcd_len;
 };
 
-// the DMA of a later tile, issued piecewise from inside the tail of the current one: an LDS-DMA instruction
-// costs 100-185 cycles of issue next to ds_reads (stage 1) and 25-60 in VALU-only stretches (the tail)
+// the DMA of a later tile, issued between a tail and the next stage 1: an LDS-DMA instruction costs 100-185 cycles
+// of issue next to ds_reads (stage 1) and 25-60 in VALU-only stretches (the tail)
 struct TileDma {
   const char *gsrc;    // stream images of the tile's queries
   const char *gsrc_m;  // their mask images
@@ -454,40 +426,6 @@ struct TileDma {
   int nbytes;          // 0: nothing to load
   int nbytes_m;        // 0: no query of the tile has an empty column
 };
-// where the bounds of a tile go: a wave-uniform row base (&lb[first query of the tile][0], scalar registers) plus a
-// 32-bit per-lane byte offset -- a 64-bit per-lane address was spilled to scratch, and every scratch reload in the
-// tile loop is followed by s_waitcnt vmcnt(0): a full drain of the DMA pieces and bound stores in flight
-struct TileOut {
-  char *rowbase;      // uniform
-  unsigned lane_off;  // (this lane's entry + (lane >= 32 ? ld : 0)) * sizeof(lb_t): lanes 32..63 store the odd query of a pair
-  unsigned ld_bytes;  // uniform
-  int nq_here;        // valid queries in the tile
-  bool n_ok;          // this lane's entry exists
-};
-// The pieces of a tile are numbered 0 .. SP_STREAM_PIECES-1 (streams) and SP_STREAM_PIECES .. +SP_MASK_PIECES-1 (masks);
-// piece c belongs to wave c % 4.  Number of DMA instructions the wave issues for the tile (each counts once on vmcnt):
-__device__ __forceinline__ int dma_pieces_of_wave(const TileDma &d, int wave) {
-  const int np = (d.nbytes + 1023) >> 10, npm = (d.nbytes_m + 1023) >> 10;
-  const int w_m = (wave - SP_STREAM_PIECES) & 3;  // first mask piece of this wave
-  return (np > wave ? (np - wave + 3) >> 2 : 0) + (npm > w_m ? (npm - w_m + 3) >> 2 : 0);
-}
-// pieces j0 .. j0+count-1 of this wave (piece j of wave w is chunk w + 4 j)
-__device__ __forceinline__ void dma_issue(const TileDma &d, int wave, int lane, int j0, int count) {
-  const int wu = __builtin_amdgcn_readfirstlane(wave);  // scalar piece number: scalar base address and LDS address
-  for (int j = j0; j < j0 + count; j++) {
-    const int c = wu + 4 * j;
-    const bool is_mask = c >= SP_STREAM_PIECES;
-    const int cc = is_mask ? c - SP_STREAM_PIECES : c;
-    // scalar base + 32-bit lane offset, formed HERE: hoisted to the top of the tile the dozen 64-bit addresses
-    // do not fit the register file and come back from scratch
-    unsigned off = (unsigned)(cc * 1024 + lane * 16);
-    asm volatile("" : "+v"(off));
-    if ((int)off < (is_mask ? d.nbytes_m : d.nbytes))
-      __builtin_amdgcn_global_load_lds(
-          reinterpret_cast<const AS1 void *>(reinterpret_cast<uintptr_t>(is_mask ? d.gsrc_m : d.gsrc) + off),
-          (AS3 void *)(d.ldst + c * 1024), 16, 0, 0);
-  }
-}
 
 // one dword through the scalar cache, for a wave-uniform address, waited for on the spot (lgkmcnt(0): only where no
 // LDS read is meant to stay in flight).  Left to the compiler the flag words came through global_load_dword, and the
@@ -498,26 +436,6 @@ __device__ __forceinline__ unsigned scalar_load_u32(const unsigned *p) {
   return v;
 }
 
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
-__device__ __forceinline__ void wait_vmcnt_le(int n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-  }
-}
-
-__device__ __forceinline__ half8 lds_frag(const char *p) { return *reinterpret_cast<const half8 *>(p); }
-
 __device__ __forceinline__ unsigned pack2(float a, float b) {
   float2v f = {a, b};
   half2v h = __builtin_convertvector(f, half2v);  // round to nearest even (v_cvt_pk_f16_f32)
@@ -527,25 +445,13 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {
 typedef int intx8 __attribute__((ext_vector_type(8)));
 typedef unsigned frag4 __attribute__((ext_vector_type(4)));  // one MFMA A fragment in flight (8 x fp16 / 16 x fp8)
 
-// per-lane constants of one segment
-struct SpecLane {
-  unsigned dc_off, f_off;  // A-fragment offsets inside a tile of 4 query images (f = 0 / f >= 1 streams)
-  unsigned c_dc, c_f;      // first 16-byte chunk of the lane's row in its stream: the read of K-step s wraps when c + 2 s >= 12 / 20
-  unsigned m_off[2];       // mask-row offsets of the two n_eff M-tiles (k4 = 0,1 / 2,3) inside the tile buffer
-  unsigned bpark;          // LDS byte address of this lane's parked B fragments (1 KiB apart)
-  int hh;
-  half8 W;                 // stage-2 A operand (inverse DFT weights)
-  intx8 Bm;                // this lane's entry: column-mask bytes as fp8 0 / 1 (B operand of the n_eff MFMAs)
-  int n_e;
-  float sqrt_ne, sqrt_ae;
-  float r_ne;  // rcp(max(n_e, 1)): 1 / n_lo of a query without empty columns
-  bool e_bad;
-};
-
 // A-fragment reads are issued through inline asm with hand-counted s_waitcnt (see sc_filter.hip: left to
 // the compiler every read is followed by s_waitcnt lgkmcnt(0), a full LDS round trip per MFMA).  LDS
 // returns data in issue order, so "fragment t has landed" == "at most (number of reads issued after it)
-// are outstanding".
+// are outstanding".  The LDS reads of the tail (the queries' tail words, the mask rows, the entry constants) go through
+// inline asm too: a plain C++ LDS load after a global_load_lds makes the compiler insert s_waitcnt vmcnt(0) (the DMA
+// writes LDS, so it orders the load behind every outstanding VMEM operation) -- a full drain of the DMA pieces and bound
+// stores in flight, ~1 k cycles each (found in the ISA in round 2).
 __device__ __forceinline__ void lds_read_frag(frag4 &dst, unsigned addr, int off) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off));
 }
@@ -574,69 +480,6 @@ __device__ __forceinline__ unsigned long long prof_now() {
   unsigned long long t;
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
   return t;
-}
-
-constexpr int SP_S1 = SP_FRAGS;   // 76 stage-1 MFMA slots per tile
-#ifndef SP_OPT_DEPTH
-#define SP_OPT_DEPTH 8
-#endif
-constexpr int SP_DEPTH = SP_OPT_DEPTH;  // A fragments in flight
-// per-query LDS reads of the tail: the query's {n_q, flags, sqrt n_q, sqrt a_q} words, requested one query ahead, and --
-// only for a query with an empty column -- 4 mask reads (2 M-tiles x 32 bytes).  ALL of them go through inline asm: a
-// plain C++ LDS load after a global_load_lds makes the compiler insert s_waitcnt vmcnt(0) (the DMA writes LDS, so it
-// orders the load behind every outstanding VMEM operation) -- one full drain of the just-issued DMA pieces and bound
-// stores per query, ~1 k cycles each (found in the ISA in round 2)
-constexpr int SP_MREADS = 1;  // reads of query 0's tail data issued inside stage 1
-
-// Stage-1 slot schedule.  Two frequencies are always in progress and their MFMAs alternate, so that no MFMA
-// follows another one on the SAME accumulator with LDS reads / VALU instructions in between (that pattern
-// loses the accumulator forwarding of back-to-back dependent MFMAs: ~+40 cycles per MFMA).  When a
-// frequency finishes the next one takes its place: f0 (6 steps) and f1 start, f2 replaces f0, f3 replaces
-// f1, ...  Frequency f accumulates into acc[f % 4].
-struct S1Slot {
-  int f, s;  // frequency, K-step
-};
-struct S1Sched {
-  S1Slot slot[SP_S1];
-  int done[8];  // slot of the last MFMA of frequency f
-};
-constexpr int s1_steps(int f) { return f == 0 ? SP_DC_STEPS : SP_F_STEPS; }
-constexpr bool kS1Interleave = false;  // measured: alternating two frequencies is not faster than one after the other
-constexpr S1Sched make_s1_sched() {
-  S1Sched r{};
-  if (!kS1Interleave) {
-    int t = 0;
-    for (int f = 0; f < 8; f++) {
-      for (int st = 0; st < s1_steps(f); st++) r.slot[t++] = S1Slot{f, st};
-      r.done[f] = t - 1;
-    }
-    return r;
-  }
-  int act[2] = {0, 1}, pos[2] = {0, 0}, next_f = 2, turn = 0;
-  for (int t = 0; t < SP_S1; t++) {
-    if (act[turn] < 0) turn ^= 1;
-    r.slot[t] = S1Slot{act[turn], pos[turn]};
-    pos[turn]++;
-    if (pos[turn] == s1_steps(act[turn])) {
-      r.done[act[turn]] = t;
-      act[turn] = next_f < 8 ? next_f++ : -1;
-      pos[turn] = 0;
-    }
-    if (act[turn ^ 1] >= 0) turn ^= 1;
-  }
-  return r;
-}
-constexpr S1Sched kS1 = make_s1_sched();
-// LDS byte offset of the fragment of slot t (relative to the lane's f = 0 or f >= 1 stream base) and its B index
-constexpr int s1_off(int t) { return kS1.slot[t].f == 0 ? 32 * kS1.slot[t].s : (kS1.slot[t].f - 1) * SP_F_BYTES + 32 * kS1.slot[t].s; }
-constexpr int s1_b(int t) { return kS1.slot[t].f == 0 ? kS1.slot[t].s : SP_DC_STEPS + (kS1.slot[t].f - 1) * SP_F_STEPS + kS1.slot[t].s; }
-// fp16 packing of the finished pair G_g = (f_2g, f_2g+1): 4 j per slot from two slots after the pair is
-// complete; it must be over before f_2g+4 re-uses acc[2g % 4]
-constexpr int pack_begin(int g) { return (kS1.done[2 * g] > kS1.done[2 * g + 1] ? kS1.done[2 * g] : kS1.done[2 * g + 1]) + 2; }
-constexpr int first_slot_of(int f) {
-  for (int t = 0; t < SP_S1; t++)
-    if (kS1.slot[t].f == f) return t;
-  return SP_S1;
 }
 
 // 1/n <= u(n) = A + n (Bc + n C) on [L, H] = [n_lo, n_hi]
@@ -670,428 +513,14 @@ __device__ __forceinline__ void recip_coeffs(Recip &r, int n_e) {
   r.rL = __builtin_amdgcn_rcpf(L);
 }
 
-// One (4 queries x 32 entries) tile at LDS byte address `tile_lds`.
-//   slots 0..75    stage 1: one MFMA per slot, fragment t+SP_DEPTH requested right after MFMA t; frequency f
-//                  accumulates into acc[f % 3], and the fp16 packing of a finished frequency pair
-//                  (P[j][g] = {C_2g, C_2g+1} of (query j/4, k4 = j%4)) is spread over the slots of the next frequency
-//   tail           per query: n_eff of the 60 shifts (2 fp8 MFMAs, K = 64), 4 stage-2 MFMAs (inverse DFT of one
-//                  k4 each), S * u(n_eff) and the running maximum in packed fp32; the tail words of the next
-//                  query are in flight meanwhile
-// out[q] = the bound of (query q, this lane's entry), identical in both lane halves
-#ifndef SP_OPT_PACK
-#define SP_OPT_PACK 2   // j packed per slot
-#endif
-constexpr int kPackPerSlot = SP_OPT_PACK;
-constexpr int kPackSlots = 16 / kPackPerSlot;
-// three accumulator sets, frequency f -> acc[f % 3]: the pair (f_2g, f_2g+1) is packed while f_2g+2 runs and
-// must be done before f_2g+3 re-uses the set of f_2g; the hi/lo split of C_0 (in place) runs during f1
-constexpr int kAccSets = 3;
-static_assert(pack_begin(0) + kPackSlots <= first_slot_of(3) && pack_begin(1) + kPackSlots <= first_slot_of(5) &&
-                  pack_begin(2) + kPackSlots <= first_slot_of(7), "accumulators are re-used before they are packed");
-constexpr int split_begin() { return kS1.done[0] + 2; }
-static_assert(s1_b(0) == 0 && s1_b(SP_B_LDS - 1) == SP_B_LDS - 1 && SP_B_LDS <= SP_DEPTH, "the parked fragments are the first slots");
-static_assert(!kS1Interleave && split_begin() + 8 <= pack_begin(0) && split_begin() + 8 <= first_slot_of(3), "C_0 split window");
-
-__device__ __forceinline__ void spec_tile(unsigned tile_lds, const char *tbase, const half8 (&B)[SP_FRAGS], const SpecLane &ln,
-                                          float eps_direct, float (&out)[SP_QPT], int dbg, unsigned long long *tmid,
-                                          const TileDma &dma, int wave, int lane, const TileOut &to) {
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u8v __attribute__((ext_vector_type(8)));
-  u4 P[16];
-  floatx16 acc[kAccSets];
-  frag4 ring[SP_DEPTH];
-  frag4 tw;     // {n_q, flags, sqrt n_q, sqrt a_q} of the current query, requested one query ahead
-  frag4 mk[4];  // mask bytes (queries with an empty column only)
-  const unsigned a_dc = tile_lds + ln.dc_off, a_f = tile_lds + ln.f_off;
-  const unsigned a_dcw = a_dc - SP_DC_BYTES, a_fw = a_f - SP_VS;
-  const unsigned a_m0 = tile_lds + ln.m_off[0], a_m1 = tile_lds + ln.m_off[1];
-  const unsigned a_tl = tile_lds + SP_TAIL;
-  // the A fragment of stage-1 slot t
-  auto a_read = [&](frag4 &dst, auto tc) {
-    constexpr int t = decltype(tc)::value;
-    if constexpr (kS1.slot[t].f == 0) lds_read_stream<kS1.slot[t].s, SP_DC_BYTES / 16, 10>(dst, a_dc, a_dcw, ln.c_dc, s1_off(t));
-    else lds_read_stream<kS1.slot[t].s, SP_VS / 16, 16>(dst, a_f, a_fw, ln.c_f, s1_off(t));
-  };
-  floatx16 z;
-#pragma unroll
-  for (int i = 0; i < 16; i++) z[i] = 0.0f;
-
-  frag4 bx[SP_B_LDS];  // the parked B fragments
-  static_for<SP_DEPTH>([&](auto tc) { a_read(ring[decltype(tc)::value], tc); });
-  static_for<SP_B_LDS>([&](auto tc) {
-    constexpr int t = decltype(tc)::value;
-    lds_read_frag(bx[t], ln.bpark, 1024 * t);
-  });
-  static_for<SP_S1>([&](auto tc) {
-    constexpr int t = decltype(tc)::value;
-    constexpr int f = kS1.slot[t].f;
-    // reads issued after fragment t's: fragments t+1 .. min(t+DEPTH-1, S1-1), plus the mask reads of query 0
-    // (issued at slots S1-4 .. S1-1, each after that slot's ring read slot is gone)
-    constexpr int younger_ring = (t + SP_DEPTH - 1 < SP_S1 ? SP_DEPTH - 1 : SP_S1 - 1 - t);
-    constexpr int younger_mask = (t > SP_S1 - SP_MREADS) ? (t - (SP_S1 - SP_MREADS)) : 0;
-    // slots 0..3 also need parked fragment t, read after the SP_DEPTH prologue fragments: younger than it are
-    // the parked fragments t+1..3 and the ring reads of slots 0..t-1
-    if constexpr (t < SP_B_LDS) lds_wait_count<SP_B_LDS - 1>();
-    else lds_wait_count<younger_ring + younger_mask>();
-    __builtin_amdgcn_sched_barrier(0);
-    const half8 af = __builtin_bit_cast(half8, ring[t % SP_DEPTH]);
-    half8 bf;
-    if constexpr (t < SP_B_LDS) bf = __builtin_bit_cast(half8, bx[t]);
-    else bf = B[s1_b(t)];
-    if constexpr (kS1.slot[t].s == 0) acc[f % kAccSets] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, z, 0, 0, 0);
-    else acc[f % kAccSets] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[f % kAccSets], 0, 0, 0);
-    if constexpr (t + SP_DEPTH < SP_S1) a_read(ring[t % SP_DEPTH], std::integral_constant<int, t + SP_DEPTH>{});
-    if constexpr (t >= SP_S1 - SP_MREADS) lds_read_frag(tw, a_tl, 0);  // tail words of query 0
-    if constexpr (t >= split_begin() && t < split_begin() + 8) {
-      // C_0 as fp16 hi + lo: lanes 0..31 carry hi (k = 0), lanes 32..63 lo (k = 8); both weigh 1/16.  hi = C_0
-      // truncated to 11 significant bits (exact in fp16), lo = the rest (rounded to fp16 by the packing)
-#pragma unroll
-      for (int j = 2 * (t - split_begin()); j < 2 * (t - split_begin()) + 2; j++) {
-        const float v = acc[0][j];
-        const float hi = __uint_as_float(__float_as_uint(v) & 0xffffe000u);
-        float sp = ln.hh ? v - hi : hi;
-        asm volatile("" : "+v"(sp));  // computed HERE, in the slot's free VALU issue (the compiler sinks it into the tail otherwise)
-        acc[0][j] = sp;
-      }
-    }
-    // packing of finished frequency pairs, spread over the slots of the following frequency
-    static_for<3>([&](auto gc) {
-      constexpr int g = decltype(gc)::value;
-      if constexpr (t >= pack_begin(g) && t < pack_begin(g) + kPackSlots) {
-#pragma unroll
-        for (int j = kPackPerSlot * (t - pack_begin(g)); j < kPackPerSlot * (t - pack_begin(g) + 1); j++) {
-          unsigned pk = pack2(acc[(2 * g) % kAccSets][j], acc[(2 * g + 1) % kAccSets][j]);
-          asm volatile("" : "+v"(pk));  // pinned to this slot: left alone the compiler keeps all 8 accumulator sets alive and
-          P[j][g] = pk;                 // packs in the tail, where the 64 conversions are not hidden by MFMAs
-        }
-      }
-    });
-    __builtin_amdgcn_sched_barrier(0);
-  });
-  if (kInstr && tmid) {
-    asm volatile("" : "+v"(acc[0]), "+v"(acc[1]));
-    *tmid = prof_now();
-  }
-#pragma unroll
-  for (int j = 0; j < 16; j++) P[j][3] = pack2(acc[6 % kAccSets][j], acc[7 % kAccSets][j]);
-
-  static_for<SP_QPT>([&](auto qc) {
-    constexpr int q = decltype(qc)::value;
-    lds_wait_count<0>();
-    __builtin_amdgcn_sched_barrier(0);
-    frag4 tailw = tw;
-    asm volatile("" : "+v"(tailw));  // a value of its own: tw is re-loaded for the next query below
-    Recip r = recip_header(tailw);
-    if constexpr (q + 1 < SP_QPT) lds_read_frag(tw, a_tl, (q + 1) * SP_QS);
-    dma_issue(dma, wave, lane, SP_DMA_PER_Q * q, SP_DMA_PER_Q);
-    // A query whose 60 columns are all non-empty (the usual case for a radar scan) meets every entry with
-    // n_eff(k) = n_e at EVERY shift (SC.cpp:78: a column pair is skipped only if one of the two is empty), so
-    // [n_lo, n_hi] = {n_e}: no mask correlation, no u(n) -- max_k S_k u(n_k) = (max_k S_k) / n_e.  Wave-uniform.
-    const bool full_q = __builtin_amdgcn_readfirstlane(r.n_q) == NS;
-    float m = 0.0f;  // rows 15..31 of the weight matrix are zero anyway (S >= 0 or clamped: valid)
-    floatx16 nacc[2];
-    if (!full_q) {
-      // the mask image of the tile is in LDS (the tile's flag word said so when its DMA was issued)
-      lds_read_frag(mk[0], a_m0, q * SP_MASK_BYTES);
-      lds_read_frag(mk[1], a_m0, q * SP_MASK_BYTES + 16);
-      lds_read_frag(mk[2], a_m1, q * SP_MASK_BYTES);
-      lds_read_frag(mk[3], a_m1, q * SP_MASK_BYTES + 16);
-      lds_wait_count<0>();
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int mt = 0; mt < 2; mt++) {
-        const frag4 lo = mk[2 * mt], hi = mk[2 * mt + 1];
-        const u8v am = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        nacc[mt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(__builtin_bit_cast(intx8, am), ln.Bm, z, 0, 0, 0, 0, 0, 0);
-      }
-    }
-    if (full_q) {
-      // two result sets: the MFMA of k4 + 1 is in the pipe while the maxima of k4 are taken (one set: every group of
-      // v_max3 waited out its own MFMA; four sets: 64 live registers, spills -- see below)
-      auto max8 = [&](const floatx16 &dd) {
-#pragma unroll
-        for (int e = 0; e < 4; e++) m = fmaxf(fmaxf(m, dd[2 * e]), dd[2 * e + 1]);  // one v_max3_f32 per pair
-      };
-      floatx16 d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ln.W, __builtin_bit_cast(half8, P[q * 4 + 0]), z, 0, 0, 0);
-      floatx16 d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ln.W, __builtin_bit_cast(half8, P[q * 4 + 1]), z, 0, 0, 0);
-      max8(d0);
-      d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ln.W, __builtin_bit_cast(half8, P[q * 4 + 2]), z, 0, 0, 0);
-      max8(d1);
-      d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ln.W, __builtin_bit_cast(half8, P[q * 4 + 3]), z, 0, 0, 0);
-      max8(d0);
-      max8(d1);
-      // (issuing the four MFMAs back to back into four result sets and taking the maxima afterwards was tried: the 64
-      // live registers push two per-lane address registers to scratch, and their reload at the top of every tile
-      // is followed by s_waitcnt vmcnt(0) -- a drain of the DMA in flight)
-      r.rL = ln.r_ne;  // n_lo = n_hi = n_e: within 1 ulp of 1 / n_e, covered by the (1 + 4e-6) factor below
-      m *= r.rL;
-    } else {
-    recip_coeffs(r, ln.n_e);
-    // u(n) of all 32 n_eff values of the query first (independent of stage 2), then per k4: S * u and the maximum;
-    // written stage by stage over 4 independent pairs so that no packed instruction waits for the previous one
-    float2v u2[4][4];
-#pragma unroll
-    for (int k4 = 0; k4 < 4; k4++) {
-      float2v t2[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        const float2v n2 = {nacc[k4 >> 1][(k4 & 1) * 8 + 2 * e], nacc[k4 >> 1][(k4 & 1) * 8 + 2 * e + 1]};
-        t2[e] = __builtin_elementwise_fma(n2, r.C2, r.B2);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        const float2v n2 = {nacc[k4 >> 1][(k4 & 1) * 8 + 2 * e], nacc[k4 >> 1][(k4 & 1) * 8 + 2 * e + 1]};
-        u2[k4][e] = __builtin_elementwise_fma(n2, t2[e], r.A2);
-      }
-    }
-#pragma unroll
-    for (int k4 = 0; k4 < 4; k4++) {
-      const floatx16 dd = __builtin_amdgcn_mfma_f32_32x32x16_f16(ln.W, __builtin_bit_cast(half8, P[q * 4 + k4]), z, 0, 0, 0);
-      float2v v2[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        const float2v s2 = {dd[2 * e], dd[2 * e + 1]};
-        v2[e] = s2 * u2[k4][e];
-      }
-#pragma unroll
-      for (int e = 0; e < 4; e++) m = fmaxf(fmaxf(m, v2[e][0]), v2[e][1]);  // one v_max3_f32 per pair
-    }
-    }
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-    const float best = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));  // 15/16 max_k S_k u(n_k)
-    // the error of S is divided by n_k >= n_lo
-    const float err = kE1 * r.sqrt_nq * ln.sqrt_ne + kE2 * r.sqrt_aq * ln.sqrt_ae;
-    float v = (1.0f + eps_direct) - fmaf(best, (16.0f / 15.0f) * (1.0f + 4e-6f), err * r.rL);
-    if (r.n_q == 0 || ln.n_e == 0) v = INFINITY;    // no effective column at any shift: never a hit
-    if (r.flags != 0u || ln.e_bad) v = -INFINITY;   // non-finite input: always re-score exactly
-    out[q] = v;
-    // both lane halves hold the bounds: lanes 0..31 store the even query of a pair, lanes 32..63 the odd one --
-    // one store instruction per two queries, issued here inside the VALU-bound tail rather than after it
-    if constexpr (q & 1) {
-      const int qq = (q - 1) + ln.hh;
-      const float vv = ln.hh ? out[q] : out[q - 1];
-      if (to.n_ok && qq < to.nq_here && !(kInstr && (dbg & 8) && vv != 12345.0f))
-        *reinterpret_cast<lb_t *>(to.rowbase + (size_t)((unsigned)(q - 1) * to.ld_bytes) + to.lane_off) = lb_pack(vv);
-    }
-  });
-}
-
-__global__ __launch_bounds__(256, 1) void sc_spec_filter_kernel(SpecArgs a) {
-  extern __shared__ __attribute__((aligned(1024))) char smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 31, hh = lane >> 5;
-  const int64_t ntiles = (a.n_items + 31) >> 5;
-  const int64_t ntb = (ntiles + 3) >> 2;
-  const int nqt = (a.nq + SP_QPT - 1) / SP_QPT;
-  const int64_t total = a.tb_cum ? a.tb_cum[ntb] : ntb * (int64_t)nqt;
-  // Work split.  With a plan: equal contiguous segments of the (tile-block, query tile) list.  Without: one
-  // unit per workgroup = one tile-block x one contiguous range of query tiles, ranges outermost, so that the
-  // workgroups in flight at any time (consecutive indices) stream the SAME query images at about the same
-  // time: each image then comes out of HBM / Infinity Cache once per XCD and out of that XCD's L2 for the
-  // other workgroups (the query stream is 10 KB per 4 x 128 pairs -- five times the direct filter's rate).
-  int64_t L0, L1;
-  if (a.tb_cum || !SP_OPT_LOCKSTEP) {
-    const int64_t per = (total + gridDim.x - 1) / gridDim.x;
-    L0 = (int64_t)blockIdx.x * per;
-    L1 = (L0 + per < total) ? (L0 + per) : total;
-  } else {
-    const int64_t r = blockIdx.x / ntb, utb = blockIdx.x - r * ntb;
-    const int64_t u0 = r * a.unit_len, u1 = (u0 + a.unit_len < nqt) ? (u0 + a.unit_len) : nqt;
-    L0 = utb * nqt + u0;
-    L1 = u0 < u1 ? utb * nqt + u1 : L0;
-  }
-  const unsigned lds_base = (unsigned)(uintptr_t)((AS3 char *)smem);
-  SpecLane ln;
-  ln.hh = hh;
-  ln.bpark = lds_base + (unsigned)(SP_BPARK_OFF + wave * (SP_B_LDS * 1024) + lane * 16);
-  {
-    // A-fragment address of this lane inside a tile of 4 query images: row = col = 8 * query + 4 * variant + k4
-    const int rq = col >> 3, rv = (col >> 2) & 1, rk = col & 3;
-    ln.c_dc = rk * 3 + hh;
-    ln.c_f = rk * 5 + hh;
-    ln.dc_off = rq * SP_QS + ln.c_dc * 16;
-    ln.f_off = rq * SP_QS + SP_DC_BYTES + rv * SP_VS + ln.c_f * 16;
-    // n_eff rows: row = col <-> (k4 = 2 * mt + col / 16, k15 = col % 16), the row order of the stage-2 output
-#pragma unroll
-    for (int mt = 0; mt < 2; mt++) {
-      const int k4 = 2 * mt + (col >> 4), k15 = (col & 15) == 15 ? 0 : (col & 15);
-      const int k = (45 * k4 + 16 * k15) % NS;  // CRT
-      ln.m_off[mt] = SP_MASKREG_OFF + (k & 15) * SP_MASK_COPY + (k & ~15) + hh * 32;
-    }
-    // stage-2 A operand: row k15 = col (rows >= 15 are zero), k = part index: lanes 0..31 {C_0 hi, Re C_1..7},
-    // lanes 32..63 {C_0 lo, Im C_1..7}; weights scaled by 15/16
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      float w = 0.0f;
-      if (col < 15) {
-        if (i == 0) w = 1.0f / 16.0f;
-        else {
-          const int t = (i * col) % 15;
-          w = hh ? (float)(-sinpi(2.0 * t / 15.0) / 8.0) : (float)(cospi(2.0 * t / 15.0) / 8.0);
-        }
-      }
-      ln.W[i] = (_Float16)w;
-    }
-  }
-
-  int64_t tb = 0;
-  if (a.tb_cum && L0 < L1) {  // last tile-block whose first item is <= L0
-    int64_t lo = 0, hi = ntb - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (a.tb_cum[mid] <= L0) lo = mid;
-      else hi = mid - 1;
-    }
-    tb = lo;
-  }
-  while (L0 < L1) {
-    int t0;
-    if (a.tb_cum) {
-      while (a.tb_cum[tb + 1] <= L0) tb++;  // skip tile-blocks without items
-      t0 = a.tb_qmin[tb] + (int)(L0 - a.tb_cum[tb]);
-    } else {
-      tb = L0 / nqt;
-      t0 = (int)(L0 - tb * nqt);
-    }
-    const int t1 = (L1 - L0 < (int64_t)(nqt - t0)) ? (int)(t0 + (L1 - L0)) : nqt;
-    L0 += t1 - t0;
-    const int q0 = t0 * SP_QPT;
-    const int q1 = (t1 * SP_QPT < a.nq) ? t1 * SP_QPT : a.nq;
-    const int64_t tile = tb * 4 + wave;
-    const bool tile_ok = tile < ntiles;  // wave-uniform
-    const int64_t n = tile * 32 + col;
-    const bool n_ok = tile_ok && n < a.n_items;
-    const int nphase = (q1 - q0 + SP_QPP - 1) / SP_QPP;
-
-    // flag word of query tile t (4 flag bytes): non-zero when one of its queries has an empty column and the tile
-    // needs its mask image.  Wave-uniform scalar loads, requested a tile before they are used
-    const unsigned *qflags = reinterpret_cast<const unsigned *>(a.qimg + sp_flags_at(a.nq)) + __builtin_amdgcn_readfirstlane(t0);
-    auto tile_dma = [&](int p, unsigned flagword) {  // query tile p of this segment -> LDS buffer p % SP_NBUF
-      const int qn = q0 + p * SP_QPP;
-      const int nqs = (q1 - qn < SP_QPP) ? (q1 - qn) : SP_QPP;
-      return TileDma{a.qimg + (int64_t)qn * SP_QS, a.qimg + sp_masks_at(a.nq) + (int64_t)qn * SP_MASK_BYTES,
-                     smem + SP_TILES_OFF + (p % SP_NBUF) * SP_PHASE_BYTES, nqs * SP_QS, flagword ? nqs * SP_MASK_BYTES : 0};
-    };
-    auto stage_tile = [&](int p) {
-      if (kInstr && (a.dbg & 4)) return;
-      dma_issue(tile_dma(p, scalar_load_u32(qflags + p)), wave, lane, 0, SP_DMA_PER_Q * SP_QPT);
-    };
-    stage_tile(0);  // overlaps the B loads below
-    if (SP_NBUF > 2 && nphase > 1) stage_tile(1);
-    unsigned flag_next = (SP_NBUF - 1 < nphase) ? scalar_load_u32(qflags + SP_NBUF - 1) : 0u;  // of tile p + SP_NBUF - 1, p = 0
-    half8 B[SP_FRAGS];
-    {
-      const uint4 *src = a.spT + ((tile_ok ? tile : 0) * SP_FRAGS) * 64 + lane;
-#pragma unroll
-      for (int s = 0; s < SP_FRAGS; s++) {
-        const uint4 v = src[s * 64];
-        B[s] = *reinterpret_cast<const half8 *>(&v);
-      }
-#pragma unroll
-      for (int s = SP_B_VGPR; s < SP_FRAGS; s++) asm volatile("" : "+a"(B[s]));
-      // park fragments 0..SP_B_LDS-1 in LDS (this wave's private 4 KiB; the previous segment's tiles are done)
-#pragma unroll
-      for (int s = 0; s < SP_B_LDS; s++)
-        *reinterpret_cast<half8 *>(smem + SP_BPARK_OFF + wave * (SP_B_LDS * 1024) + s * 1024 + lane * 16) = B[s];
-    }
-    const u64 m2 = n_ok ? a.cmask[n] : 0ull;
-    ln.n_e = __popcll(m2 & kMask60);
-    ln.sqrt_ne = sqrtf((float)ln.n_e);
-    ln.r_ne = __builtin_amdgcn_rcpf((float)(ln.n_e > 1 ? ln.n_e : 1));
-    ln.sqrt_ae = n_ok ? a.aux[n] : 0.0f;
-    ln.e_bad = (m2 & kNonFinite) != 0;
-    {
-      const unsigned bits = (unsigned)((m2 & kMask60) >> (32 * hh));  // columns 32 hh .. 32 hh + 31 (K index of the lane half)
-#pragma unroll
-      for (int r = 0; r < 8; r++)  // 4 bits -> 4 bytes of fp8 (e4m3) 0.0 / 1.0 = 0x00 / 0x38
-        ln.Bm[r] = (int)(((((bits >> (4 * r)) & 0xfu) * 0x00204081u) & 0x01010101u) * 0x38u);
-    }
-
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // Tile p is computed from buffer p % 3 while the DMA of tile p + 2 is being issued (piecewise, inside the
-    // tail of tile p, interleaved with the tile's two bound stores).  At the end of tile p the wave waits for
-    // ITS pieces of tile p + 1 only: vmcnt(n_young), n_young = the number of DMA instructions of tile p + 2 it
-    // has issued.  VMEM operations retire in issue order and at least n_young + 3 operations are younger than
-    // the last piece of tile p + 1 (a store of tile p - 1, the pieces of tile p + 2, the stores of tile p), so
-    // that piece has landed; the youngest stores stay in flight (waiting for their acknowledgement every
-    // tile cost more than the stage-1 MFMAs).  The raw barrier (no vmcnt(0), unlike __syncthreads with an
-    // LDS-DMA pending) makes the other waves' pieces visible and frees buffer (p + 3) % 3 = p % 3.
-    const bool prof = kInstr && a.prof && blockIdx.x == 0 && wave == 0;
-    const bool clk = a.prof && blockIdx.x == 0 && wave == 0;  // any build: the segment's cycles and wall time
-    unsigned long long ps[5] = {0, 0, 0, 0, 0};
-    unsigned long long c_begin = 0, r_begin = 0;  // shader clock vs the constant 100 MHz clock: the clock the kernel ran at
-    if (clk) {
-      c_begin = prof_now();
-      asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_begin)::"memory");
-    }
-    for (int p = 0; p < nphase; p++) {
-      const int qp = q0 + p * SP_QPP;
-      unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-      if (prof) t0 = prof_now();
-      // the DMA of tile p + SP_NBUF - 1: issued piecewise inside this tile's tail (waves without a tile issue it here)
-      TileDma dma{nullptr, nullptr, nullptr, 0, 0};
-      if (p + SP_NBUF - 1 < nphase && !(kInstr && (a.dbg & 4))) dma = tile_dma(p + SP_NBUF - 1, flag_next);
-      const int n_issued = dma_pieces_of_wave(dma, wave);
-      if (!tile_ok) dma_issue(dma, wave, lane, 0, SP_DMA_PER_Q * SP_QPT);
-      const int n_young = SP_NBUF > 2 ? n_issued : 0;  // DMA instructions younger than those of tile p + 1
-      if (prof) t1 = prof_now();
-      const int nq_here = (q1 - qp < SP_QPP) ? (q1 - qp) : SP_QPP;
-      if (tile_ok) {
-        const char *tbase = smem + SP_TILES_OFF + (p % SP_NBUF) * SP_PHASE_BYTES;
-        float out[SP_QPT];
-        spec_tile(lds_base + (unsigned)(tbase - smem), tbase, B, ln, a.eps_direct, out, a.dbg, prof ? &t2 : nullptr, dma, wave, lane,
-                  TileOut{reinterpret_cast<char *>(a.lb + (int64_t)qp * a.ld_lb), (unsigned)(n * 2) + (unsigned)hh * (unsigned)(a.ld_lb * 2),
-                          (unsigned)(a.ld_lb * 2), nq_here, n_ok});
-        if (prof) {
-          asm volatile("" : "+v"(out[0]), "+v"(out[1]), "+v"(out[2]), "+v"(out[3]));
-          t3 = prof_now();
-        }
-      }
-      if (prof) t4 = prof_now();
-      if (p + 1 < nphase) {
-        // flag word of the tile whose DMA the next iteration issues; its latency falls into the wait for the DMA
-        flag_next = (p + SP_NBUF < nphase) ? scalar_load_u32(qflags + p + SP_NBUF) : 0u;
-        wait_vmcnt_le(n_young);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-      }
-      if (prof) {
-        const unsigned long long t5 = prof_now();
-        ps[0] += t1 - t0;  // DMA issue
-        ps[1] += t2 - t1;  // stage 1
-        ps[2] += t3 - t2;  // tail
-        ps[3] += t4 - t3;  // stores
-        ps[4] += t5 - t4;  // wait + barrier
-      }
-    }
-    if (clk) {
-      unsigned long long r_end;
-      const unsigned long long c_end = prof_now();
-      asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_end)::"memory");
-      if (lane == 0) {
-        if (prof) for (int i = 0; i < 5; i++) a.prof[i] = ps[i];
-        a.prof[5] = (unsigned long long)nphase;
-        a.prof[6] = c_end - c_begin;
-        a.prof[7] = r_end - r_begin;
-      }
-    }
-    // segment end: everything retired before the next segment's DMA reuses the buffers
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-}
-
-
 // ==========================================================================================
-// sc_spec2_filter_kernel -- the same filter with TWO waves per SIMD (round 4)
+// sc_spec2_filter_kernel -- the filter, TWO waves per SIMD (round 4)
 // ==========================================================================================
-// sc_spec_filter_kernel keeps the 76 B fragments of a 32-entry tile (304 registers) in ONE wave, so a SIMD holds a
-// single wave and everything a tile needs -- 76 stage-1 MFMAs, their LDS reads, the fp16 packing, 16 stage-2 MFMAs,
-// the maxima, the bound arithmetic, the DMA of the next tile -- issues one after the other on it: the matrix pipe is
-// busy 39 % of the time.  Here the entry tile is split BY FREQUENCY over the two waves w and w + 4 of a
-// 512-thread workgroup (they share SIMD w % 4):
+// A 32-entry tile has 76 B fragments (304 registers of entry spectra), and a tile of 4 queries needs 76 stage-1 MFMAs, their
+// LDS reads, the fp16 packing, 16 stage-2 MFMAs, the maxima, the bound arithmetic and the DMA of the next tile.  One wave
+// cannot hold the fragments and leave the SIMD room for a second one, and on a single wave all of that issues one after the
+// other (the one-wave-per-SIMD kernel of rounds 1-3 did: matrix pipe busy 39 % of the time).  So the entry
+// tile is split BY FREQUENCY over the two waves w and w + 4 of a 512-thread workgroup (they share SIMD w % 4):
 //   "late"  wave (0..3): f = 0..3 (B fragments 0..35),  stage 2 + bounds + store of queries 2, 3 of a tile
 //   "early" wave (4..7): f = 4..7 (B fragments 36..75), stage 2 + bounds + store of queries 0, 1, and every LDS-DMA piece
 // Both run stage 1 on the SAME (4 queries x 32 entries) tile for their own frequencies (the A fragments of a frequency
@@ -1105,7 +534,9 @@ __global__ __launch_bounds__(256, 1) void sc_spec_filter_kernel(SpecArgs a) {
 // direction is guarded by a sequence number: the reader bumps it once the half is in its registers, the writer checks
 // it before overwriting (the reads come half an interval before the writes: the check never waits in practice).
 // Round-4 builds before this one, both measured at 1.76-1.80 ms per 8192 x 9970 launch against 2.05 for the one-wave
-// kernel: (i) symmetric, in phase, two barriers per tile -- both waves sat in their tails together, the pipe idle;
+// kernel (retired; its bounds of a large ragged fixture are kept in tests/golden/sc_spec_onewave_bounds.npz, and this
+// kernel must reproduce them bit for bit):
+// (i) symmetric, in phase, two barriers per tile -- both waves sat in their tails together, the pipe idle;
 // (ii) producer (f = 4..7 + DMA, one tile ahead) / consumer (f = 0..3 + all four tails) -- during stage 1 the two waves
 // alternated on the matrix pipe at exactly 64 cycles per own MFMA (pipe 100 % busy), but the consumer's serial tail
 // (2.9 k cycles, ~350 issue states) then ran with the pipe idle.  A static s_setprio on either wave starved the other.
@@ -1166,7 +597,8 @@ static_assert(S2_DEPTH >= 3, "a slot's fragment is requested at least two slots 
 
 // per-lane A-fragment addressing of stage 1 (the only lane state that lives in registers across a tile)
 struct S2Lane {
-  unsigned dc_off, f_off, c_dc, c_f;  // as SpecLane
+  unsigned dc_off, f_off;  // A-fragment offsets inside a tile of 4 query images (f = 0 / f >= 1 streams)
+  unsigned c_dc, c_f;      // first 16-byte chunk of the lane's row in its stream: the read of K-step s wraps when c + 2 s >= 12 / 20
 };
 
 // every piece of a tile, over the 4 producer waves: piece c belongs to producer c % 4.  WHOLE pieces, no lane predicate:
@@ -1362,7 +794,9 @@ __device__ __forceinline__ void spec2_segment(const SpecArgs &a, char *smem, uns
       else acc[lf % 3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[lf % 3], 0, 0, 0);
       if constexpr (t + S2_DEPTH < NF) a_read(ring[t % S2_DEPTH], std::integral_constant<int, t + S2_DEPTH>{});
       if constexpr (HALF == 0) {
-        // C_0 as fp16 hi + lo (see spec_tile): during f = 1, two j per slot
+        // C_0 as fp16 hi + lo: lanes 0..31 carry hi (k = 0), lanes 32..63 lo (k = 8); both weigh 1/16.  hi = C_0 truncated
+        // to 11 significant bits (exact in fp16), lo = the rest (rounded to fp16 by the packing).  During f = 1, two j per
+        // slot, computed HERE, in the slot's free VALU issue (the compiler sinks it into the tail otherwise)
         constexpr int sb = H::last_slot(0) + 2;
         if constexpr (t >= sb && t < sb + 8) {
 #pragma unroll
@@ -1685,7 +1119,8 @@ __global__ __launch_bounds__(512, 2) void sc_spec2_filter_kernel(SpecArgs a) {
     ln.f_off = rq * SP_QS + SP_DC_BYTES + rv * SP_VS + ln.c_f * 16;
   }
   if (wave == 0) {
-    // stage-2 A operand (inverse DFT weights, see sc_spec_filter_kernel), once per workgroup, into LDS
+    // stage-2 A operand (inverse DFT weights), once per workgroup, into LDS: row k15 = col (rows >= 15 are zero), k = part
+    // index: lanes 0..31 {C_0 hi, Re C_1..7}, lanes 32..63 {C_0 lo, Im C_1..7}; weights scaled by 15/16
     frag4 wv;
     half8 W;
 #pragma unroll
@@ -1795,18 +1230,16 @@ int launch_insert(const void *d_pts, const int64_t *d_offs, int64_t n_pts, int64
   return RSX_OK;
 }
 
-const char *spec_filter_kernel_name() { return "sc_spec_filter_kernel"; }
-
 const char *spec2_filter_kernel_name() { return "sc_spec2_filter_kernel"; }
 
+// sc_spec2_filter_kernel: 512 threads, the entry tile split by frequency over two waves per SIMD
 int launch_spec_filter(const DbView &db, const void *qimg, int32_t nq, int64_t n_items, lb_t *lb, int64_t ld_lb,
-                       const int32_t *tb_qmin, const int64_t *tb_cum, hipStream_t s, bool two_waves) {
+                       const int32_t *tb_qmin, const int64_t *tb_cum, hipStream_t s) {
   if (nq <= 0 || n_items <= 0) return RSX_OK;
   static int n_cu = 0;
-  const int lds = SP_LDS_BYTES;
   if (!n_cu) {
-    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sc_spec_filter_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sc_spec2_filter_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, S2_LDS_BYTES));
     int dev = 0, cu = 0;
     RSX_HIP(hipGetDevice(&dev));
     RSX_HIP(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -1831,101 +1264,52 @@ int launch_spec_filter(const DbView &db, const void *qimg, int32_t nq, int64_t n
   const int64_t ntb = (ntiles + 3) / 4;
   a.tb_qmin = tb_qmin;
   a.tb_cum = tb_cum;
-  unsigned grid = (unsigned)n_cu;
-  a.unit_len = (int32_t)nqt;
-  if (!SP_OPT_LOCKSTEP) {
-    int64_t per = (ntb * nqt + n_cu - 1) / n_cu;
-    if (per < 4) per = 4;
-    grid = (unsigned)((ntb * nqt + per - 1) / per);
-  } else if (!tb_cum) {
-    // number of query ranges R: fill whole rounds of n_cu workgroups as evenly as possible; a unit keeps
-    // >= 16 query tiles so that the 304-register B load stays amortised
-    int64_t best_r = 1;
-    double best_eff = 0.0;
-    for (int64_t r = 1; r <= 64 && (r == 1 || (nqt + r - 1) / r >= 16); r++) {
-      const int64_t len = (nqt + r - 1) / r, rr = (nqt + len - 1) / len;  // rr ranges actually used
-      const int64_t units = rr * ntb, rounds = (units + n_cu - 1) / n_cu;
-      const double eff = (double)(ntb * nqt) / (double)(rounds * n_cu * len);
-      if (eff > best_eff + 1e-9) {
-        best_eff = eff;
-        best_r = rr;
-      }
-    }
-    if (const char *e = rsx::exp_env("RSX_SPEC_R")) {  // experiments: force the number of query ranges
-      const int64_t v = atoll(e);
-      if (v >= 1 && v <= nqt) best_r = v;
-    }
-    a.unit_len = (int32_t)((nqt + best_r - 1) / best_r);
-    const int64_t rr = (nqt + a.unit_len - 1) / a.unit_len;
-    grid = (unsigned)(rr * ntb);
-  }
-  if (two_waves) {
-    // sc_spec2_filter_kernel: 512 threads, the entry tile split by frequency over two waves per SIMD
-    static bool attr2 = false;
-    if (!attr2) {
-      RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sc_spec2_filter_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, S2_LDS_BYTES));
-      attr2 = true;
-    }
-    static unsigned long long *d_prof2 = nullptr;
-    static const bool want_prof2 = kInstr && rsx::exp_env("RSX_SPEC_PROF") != nullptr;
-    if (want_prof2 && !d_prof2) RSX_HIP(hipMalloc(&d_prof2, 16 * sizeof(unsigned long long)));
-    a.prof = want_prof2 ? d_prof2 : nullptr;
-    a.xcd_nqt = a.xcd_len = 0;
-    {
-      // XCD-aware split (no plan, every XCD gets >= 16 query tiles of its own).  Sub-ranges per XCD S: whole rounds of the
-      // XCD's workgroup slots (one per CU) filled best, cost = rounds x (tiles per sub-range + 3): a workgroup's start
-      // (311 KB tile-block load, LDS constants, pipeline fill) costs about 3 tiles -- measured on the bench launch: S = 16
-      // (39 full rounds of 16 tiles) 2.05 ms, S = 2 (4.875 -> 5 rounds of 128) 1.83 ms
-      static const bool xcd_on = [] {
-        const char *e = rsx::exp_env("RSX_SPEC_XCD");
-        return !(e && e[0] == '0');
-      }();
-      if (xcd_on && !tb_cum) {
-        int64_t forced = 0;
-        if (const char *e = rsx::exp_env("RSX_SPEC_XCD_S")) forced = atoll(e);
-        const plan::XcdSplit sp = plan::xcd_split(nqt, ntb, n_cu, forced);  // sc_plan.h
-        if (sp.on) {
-          a.xcd_nqt = sp.nqt_x;
-          a.xcd_len = sp.len;
-          grid = sp.grid;
-        }
-      }
-    }
-    hipLaunchKernelGGL(sc_spec2_filter_kernel, dim3(grid), dim3(512), S2_LDS_BYTES, s, a);
-    RSX_HIP(hipGetLastError());
-    if (want_prof2) {  // debugging aid only: synchronises
-      unsigned long long h[16] = {0};
-      RSX_HIP(hipStreamSynchronize(s));
-      RSX_HIP(hipMemcpy(h, d_prof2, sizeof(h), hipMemcpyDeviceToHost));
-      for (int hf = 0; hf < 2; hf++) {
-        const double n = h[hf * 8 + 5] ? (double)h[hf * 8 + 5] : 1.0;
-        if (hf == 0)
-          fprintf(stderr, "[sc_spec2 prof] late wave, %llu tiles of the last segment of workgroup 0: cycles per tile  stage1 %.0f  seq+exchange writes %.0f"
-                          "  exchange+const reads %.0f  stage2+bounds+store %.0f  wait %.0f | %.0f cycles per tile at %.0f MHz\n",
-                  h[5], h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[6] / n, h[7] ? 100.0 * h[6] / h[7] : 0.0);
-        else
-          fprintf(stderr, "[sc_spec2 prof] early wave, %llu tiles: cycles per tile  exchange+const reads %.0f  stage2+bounds+store %.0f  dma issue %.0f"
-                          "  stage1 %.0f  seq+exchange writes+wait %.0f | %.0f cycles per tile at %.0f MHz\n",
-                  h[13], h[8] / n, h[9] / n, h[10] / n, h[11] / n, h[12] / n, h[14] / n, h[15] ? 100.0 * h[14] / h[15] : 0.0);
-      }
-    }
-    return RSX_OK;
-  }
+  // with a plan, or a batch too small for the XCD-aware split: one workgroup per CU, >= 4 (tile-block, query tile) items each
+  int64_t per = (ntb * nqt + n_cu - 1) / n_cu;
+  if (per < 4) per = 4;
+  unsigned grid = (unsigned)((ntb * nqt + per - 1) / per);
   static unsigned long long *d_prof = nullptr;
-  static const bool want_prof = rsx::exp_env("RSX_SPEC_PROF") != nullptr;
-  if (want_prof && !d_prof) RSX_HIP(hipMalloc(&d_prof, 8 * sizeof(unsigned long long)));
+  static const bool want_prof = kInstr && rsx::exp_env("RSX_SPEC_PROF") != nullptr;
+  if (want_prof && !d_prof) RSX_HIP(hipMalloc(&d_prof, 16 * sizeof(unsigned long long)));
   a.prof = want_prof ? d_prof : nullptr;
-  hipLaunchKernelGGL(sc_spec_filter_kernel, dim3(grid), dim3(256), lds, s, a);
+  a.xcd_nqt = a.xcd_len = 0;
+  {
+    // XCD-aware split (no plan, every XCD gets >= 16 query tiles of its own).  Sub-ranges per XCD S: whole rounds of the
+    // XCD's workgroup slots (one per CU) filled best, cost = rounds x (tiles per sub-range + 3): a workgroup's start
+    // (311 KB tile-block load, LDS constants, pipeline fill) costs about 3 tiles -- measured on the bench launch: S = 16
+    // (39 full rounds of 16 tiles) 2.05 ms, S = 2 (4.875 -> 5 rounds of 128) 1.83 ms
+    static const bool xcd_on = [] {
+      const char *e = rsx::exp_env("RSX_SPEC_XCD");
+      return !(e && e[0] == '0');
+    }();
+    if (xcd_on && !tb_cum) {
+      int64_t forced = 0;
+      if (const char *e = rsx::exp_env("RSX_SPEC_XCD_S")) forced = atoll(e);
+      const plan::XcdSplit sp = plan::xcd_split(nqt, ntb, n_cu, forced);  // sc_plan.h
+      if (sp.on) {
+        a.xcd_nqt = sp.nqt_x;
+        a.xcd_len = sp.len;
+        grid = sp.grid;
+      }
+    }
+  }
+  hipLaunchKernelGGL(sc_spec2_filter_kernel, dim3(grid), dim3(512), S2_LDS_BYTES, s, a);
   RSX_HIP(hipGetLastError());
   if (want_prof) {  // debugging aid only: synchronises
-    unsigned long long h[8] = {0};
+    unsigned long long h[16] = {0};
     RSX_HIP(hipStreamSynchronize(s));
     RSX_HIP(hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost));
-    const double n = h[5] ? (double)h[5] : 1.0;
-    fprintf(stderr, "[sc_spec prof] tiles %llu: cycles per tile  dma %.0f  stage1 %.0f  tail %.0f  stores %.0f  wait+barrier %.0f"
-                    "  | tile loop %.0f cycles in %.1f us: shader clock %.0f MHz\n",
-            h[5], h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, (double)h[6], h[7] / 100.0, h[7] ? 100.0 * h[6] / h[7] : 0.0);
+    for (int hf = 0; hf < 2; hf++) {
+      const double n = h[hf * 8 + 5] ? (double)h[hf * 8 + 5] : 1.0;
+      if (hf == 0)
+        fprintf(stderr, "[sc_spec2 prof] late wave, %llu tiles of the last segment of workgroup 0: cycles per tile  stage1 %.0f  seq+exchange writes %.0f"
+                        "  exchange+const reads %.0f  stage2+bounds+store %.0f  wait %.0f | %.0f cycles per tile at %.0f MHz\n",
+                h[5], h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[6] / n, h[7] ? 100.0 * h[6] / h[7] : 0.0);
+      else
+        fprintf(stderr, "[sc_spec2 prof] early wave, %llu tiles: cycles per tile  exchange+const reads %.0f  stage2+bounds+store %.0f  dma issue %.0f"
+                        "  stage1 %.0f  seq+exchange writes+wait %.0f | %.0f cycles per tile at %.0f MHz\n",
+                h[13], h[8] / n, h[9] / n, h[10] / n, h[11] / n, h[12] / n, h[14] / n, h[15] ? 100.0 * h[14] / h[15] : 0.0);
+    }
   }
   return RSX_OK;
 }

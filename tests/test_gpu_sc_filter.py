@@ -17,7 +17,7 @@ from navtech_radar_slam_amd import synth
 pytestmark = pytest.mark.gpu
 
 FORCE, OFF = 2, 1
-FILTER_KERNELS = ("sc_filter_kernel", "sc_spec_filter_kernel", "sc_spec2_filter_kernel")
+FILTER_KERNELS = ("sc_filter_kernel", "sc_spec2_filter_kernel")
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +29,9 @@ def sc():
 
 @pytest.fixture(autouse=True, params=["direct", "spectral", "spectral2"])
 def filter_kind(request):
-    """every test of this module runs with every form of the filter (sc_filter.hip / sc_spec.hip, one and two waves per SIMD)"""
+    """every test of this module runs with both forms of the filter (sc_filter.hip / sc_spec.hip) and with every value of the
+    public parameter: KIND_SPECTRAL named the one-wave-per-SIMD kernel, is kept as a synonym of KIND_SPECTRAL2 for callers, and
+    has to reach sc_spec2_filter_kernel through every entry these tests use"""
     from navtech_radar_slam_amd import _rsx
     _rsx.default_filter_kind = {"direct": _rsx.KIND_DIRECT, "spectral": _rsx.KIND_SPECTRAL, "spectral2": _rsx.KIND_SPECTRAL2}[request.param]
     yield request.param
@@ -123,7 +125,7 @@ def test_filtered_query_matches_oracle(sc, oracle, binary, k, filter_kind):
     o = oracle.Manager()
     o.add_descriptors(descs.astype(np.float64))
     got = g.query(queries, k=k, n_eligible=n - 30)
-    assert g.profiled_kernel_name() == {"direct": "sc_filter_kernel", "spectral": "sc_spec_filter_kernel", "spectral2": "sc_spec2_filter_kernel"}[filter_kind]
+    assert g.profiled_kernel_name() == {"direct": "sc_filter_kernel", "spectral": "sc_spec2_filter_kernel", "spectral2": "sc_spec2_filter_kernel"}[filter_kind]
     for qi in range(nq):
         want = o.exhaustive(queries[qi].astype(np.float64), n_eligible=n - 30, k=k, nthreads=4)
         assert np.array_equal(got[qi], want), f"query {qi}"

@@ -1,12 +1,19 @@
 """Spectral form of the lower-bound filter (csrc/sc_spec.hip) on a real MI355X: its bounds are valid lower
 bounds of the fp64 all-shift minimum and close to it, and every query path gives the oracle's results
 with filter_kind = spectral exactly as with the direct filter."""
+import hashlib
+import os
+import zlib
+
 import numpy as np
 import pytest
 
 from test_gpu_sc_filter import all_shift_bound, make_db
 
 pytestmark = pytest.mark.gpu
+
+ONE_WAVE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sc_spec_onewave_bounds.npz")
+ONE_WAVE_COLS = np.r_[0:128, 4096:4096 + 77]      # the first tile-block and the ragged end, kept in full
 
 
 @pytest.fixture(scope="module")
@@ -33,11 +40,11 @@ def oracle():
     return pyoracle
 
 
-@pytest.fixture(params=["spectral", "spectral2"])
+@pytest.fixture(params=["spectral2"])
 def spec_kind(request, rsx):
-    """both mappings of the spectral filter: one wave per SIMD (sc_spec_filter_kernel) and the entry tile split by
-    frequency over two waves per SIMD (sc_spec2_filter_kernel)"""
-    return rsx.KIND_SPECTRAL if request.param == "spectral" else rsx.KIND_SPECTRAL2
+    """the spectral filter, sc_spec2_filter_kernel (KIND_SPECTRAL names the same kernel:
+    test_both_spectral_kinds_run_the_two_wave_kernel)"""
+    return rsx.KIND_SPECTRAL2
 
 
 def n_cols(d):
@@ -160,11 +167,10 @@ def test_spectral_self_queries_and_shards(sc, rsx, synth, spec_kind):
     torch.cuda.set_stream(torch.cuda.default_stream())
 
 
-@pytest.mark.parametrize("binary", [True, False])
-def test_two_wave_mapping_gives_the_same_bounds(sc, rsx, synth, binary):
-    """sc_spec2_filter_kernel splits the entry tile by frequency over two waves; every accumulator still sees its K-steps
-    in the same order, so its bounds equal sc_spec_filter_kernel's BIT FOR BIT -- ragged entry tiles, partial query tiles,
-    queries with and without empty columns, empty and non-finite descriptors"""
+def one_wave_fixture(synth, binary):
+    """(descs [4173][1200], queries [203][1200]) of the pin below and of tools/make_spec_onewave_golden.py, from fixed
+    seeds: ragged entry tiles, partial query tiles, queries with and without empty columns, empty and non-finite
+    descriptors"""
     n, nq = 4096 + 77, 203
     descs = make_db(300 + binary, n, binary)
     rng = np.random.default_rng(17)
@@ -175,13 +181,55 @@ def test_two_wave_mapping_gives_the_same_bounds(sc, rsx, synth, binary):
     queries[8:40] = synth.random_descriptors(5, 32, binary=False) + np.float32(0.5)   # no empty column: the short tail path
     queries[11, 5] = np.nan
     descs[12, 100] = np.inf
-    a = sc.SCManager(filter_kind=rsx.KIND_SPECTRAL, capacity_hint=n)
-    b = sc.SCManager(filter_kind=rsx.KIND_SPECTRAL2, capacity_hint=n)
-    a.add_descriptors_f32(descs)
+    return descs, queries
+
+
+def bound_digest(lb):
+    """what the golden file keeps of a float32 bound matrix [nq][n]: (SHA-256 of its uint32 view, one CRC32 per query
+    row [nq] uint32, the bit patterns of ONE_WAVE_COLS [nq][205] uint32)"""
+    bits = np.ascontiguousarray(lb).view(np.uint32)
+    crc = np.array([zlib.crc32(row.tobytes()) for row in bits], dtype=np.uint32)
+    return hashlib.sha256(bits.tobytes()).hexdigest(), crc, bits[:, ONE_WAVE_COLS].copy()
+
+
+@pytest.mark.parametrize("binary", [True, False])
+def test_two_wave_mapping_gives_the_same_bounds(sc, rsx, synth, binary):
+    """sc_spec2_filter_kernel splits the entry tile by frequency over two waves; every accumulator still sees its K-steps
+    in the same order as in the retired one-wave-per-SIMD kernel, so its bounds equal that kernel's BIT FOR BIT.  The
+    one-wave kernel's bounds of this fixture were recorded before it was deleted (tools/make_spec_onewave_golden.py):
+    a hash of the whole matrix, a CRC per query row, and the first tile-block and the ragged end in full"""
+    descs, queries = one_wave_fixture(synth, binary)
+    b = sc.SCManager(filter_kind=rsx.KIND_SPECTRAL2, capacity_hint=len(descs))
     b.add_descriptors_f32(descs)
-    la, lb2 = a.filter_bounds(queries), b.filter_bounds(queries)
-    assert b.profiled_kernel_name() == "sc_spec2_filter_kernel" and a.profiled_kernel_name() == "sc_spec_filter_kernel"
-    assert np.array_equal(la.view(np.uint32), lb2.view(np.uint32))
+    lb2 = b.filter_bounds(queries)
+    assert b.profiled_kernel_name() == "sc_spec2_filter_kernel"
+    assert lb2.shape == (len(queries), len(descs)) and lb2.dtype == np.float32
+    gold = np.load(ONE_WAVE_GOLDEN)
+    tag = "binary" if binary else "continuous"
+    sha, crc, cols = bound_digest(lb2)
+    rows = np.flatnonzero(crc != gold["crc32_" + tag])
+    diff = np.argwhere(cols != gold["cols_" + tag])
+    first = (int(diff[0, 0]), int(ONE_WAVE_COLS[diff[0, 1]])) if len(diff) else None
+    assert sha == str(gold["sha256_" + tag]) and len(rows) == 0, \
+        f"{len(rows)} query rows differ from the one-wave kernel's bounds: {rows[:16].tolist()}; " \
+        f"first differing (query, entry) inside the stored columns: {first}"
+    assert np.array_equal(cols, gold["cols_" + tag]), first
+
+
+def test_both_spectral_kinds_run_the_two_wave_kernel(sc, rsx, synth):
+    """KIND_SPECTRAL is kept as a synonym of KIND_SPECTRAL2: a ragged entry tile and a partial query tile"""
+    n, nq = 96 + 13, 9
+    descs = make_db(21, n, False)
+    queries = np.stack([synth.rotate_descriptor(descs[(11 * i) % n], (7 * i) % 60) for i in range(nq)])
+    queries[1] = 0
+    queries[::2, 40:60] = 0
+    bits = []
+    for kind in (rsx.KIND_SPECTRAL, rsx.KIND_SPECTRAL2):
+        g = sc.SCManager(filter_kind=kind)
+        g.add_descriptors_f32(descs)
+        bits.append(g.filter_bounds(queries).view(np.uint32))
+        assert g.profiled_kernel_name() == "sc_spec2_filter_kernel"
+    assert bits[0].shape == (nq, n) and np.array_equal(bits[0], bits[1])
 
 
 def test_default_kind_is_spectral(sc, rsx, synth):
@@ -194,7 +242,7 @@ def test_default_kind_is_spectral(sc, rsx, synth):
     g1 = sc.SCManager(filter_mode=rsx.FILTER_FORCE, filter_kind=rsx.KIND_SPECTRAL)
     g1.add_descriptors_f32(holes)
     g1.query(holes[:16], k=3)
-    assert g1.profiled_kernel_name() == "sc_spec_filter_kernel"
+    assert g1.profiled_kernel_name() == "sc_spec2_filter_kernel"     # the synonym
     g2 = sc.SCManager(filter_mode=rsx.FILTER_FORCE, filter_kind=rsx.KIND_DIRECT)
     g2.add_descriptors_f32(holes)
     g2.query(holes[:16], k=3)

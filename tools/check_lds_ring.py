@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Static check of the filter kernels' hand-issued LDS reads (inline-asm ds_read_b128 + counted
 s_waitcnt): no instruction may touch the destination registers of a read that can still be in
-flight.  Usage: tools/check_lds_ring.py [direct|spectral|spectral2]  (compiles sc_filter.hip / sc_spec.hip to ISA
-with hipcc and scans sc_filter_kernel / sc_spec_filter_kernel)."""
+flight.  Usage: tools/check_lds_ring.py [direct|spectral2]  (compiles sc_filter.hip / sc_spec.hip to ISA
+with hipcc and scans sc_filter_kernel / sc_spec2_filter_kernel)."""
 import os
 import re
 import subprocess
@@ -22,7 +22,6 @@ def regs(tok):
 
 
 KERNELS = {"direct": ("sc_filter.hip", "sc_filter_kernel", []),
-           "spectral": ("sc_spec.hip", "sc_spec_filter_kernel", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
            "spectral2": ("sc_spec.hip", "sc_spec2_filter_kernel", ["-mllvm", "-amdgpu-mfma-vgpr-form"])}
 
 

@@ -7,6 +7,7 @@ n, nq = int(sys.argv[1]) if len(sys.argv) > 1 else 10000, int(sys.argv[2]) if le
 descs = synth.random_descriptors(3, n, binary=True)
 rng = np.random.default_rng(1)
 q = np.stack([synth.rotate_descriptor(descs[int(rng.integers(0, n))], int(rng.integers(0, 60))) for _ in range(nq)])
+# KIND_SPECTRAL is a synonym of KIND_SPECTRAL2 since the one-wave-per-SIMD kernel was deleted: this checks sc_spec2_filter_kernel
 gs = sc.SCManager(filter_kind=_rsx.KIND_SPECTRAL, capacity_hint=n); gd = sc.SCManager(filter_kind=_rsx.KIND_DIRECT, capacity_hint=n)
 gs.add_descriptors_f32(descs); gd.add_descriptors_f32(descs)
 ls = gs.filter_bounds(q); ld = gd.filter_bounds(q)

@@ -13,7 +13,7 @@ for binary in (True, False):
     rng = np.random.default_rng(9)
     queries = np.stack([synth.rotate_descriptor(descs[int(rng.integers(0, n))], int(rng.integers(0, 60))) for _ in range(nq)])
     queries[::2, rng.integers(0, 1200, 20)] = 0
-    gs = sc.SCManager(filter_kind=_rsx.KIND_SPECTRAL)
+    gs = sc.SCManager(filter_kind=_rsx.KIND_SPECTRAL)   # a synonym of KIND_SPECTRAL2 since the one-wave-per-SIMD kernel was deleted
     gd = sc.SCManager(filter_kind=_rsx.KIND_DIRECT)
     gs.add_descriptors_f32(descs); gd.add_descriptors_f32(descs)
     eps = gs.filter_eps()

@@ -1,3 +1,4 @@
+// (historical: the one-wave-per-SIMD kernel this models was deleted; sc_spec2_filter_kernel's stage-1 slot has the same shape)
 // micro-benchmark of one stage-1 slot of sc_spec_filter_kernel: s_waitcnt lgkmcnt(N) ; MFMA (A fragment
 // from an LDS ring, B fragment register-resident) ; ds_read_b128 of the fragment DEPTH slots ahead.
 // Variants: B fragments in AGPRs or VGPRs, 1 or 2 accumulator chains; build with and without
