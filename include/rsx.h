@@ -986,6 +986,84 @@ int rsx_cfear_tracker_push_timed_device(rsx_cfear_tracker *h, const rsx_cfear_su
                                         const int64_t *d_offsets, const int32_t *d_n_scans, const rsx_cfear_params *params,
                                         const rsx_cfear_track_params *track, rsx_cfear_track_result *d_out, void *stream);
 
+/* ============================== CorAl alignment quality ================================
+ * How well two clouds are aligned, judged without any solver's residual (Adolfsson et al., "CorAl: Introspection for robust
+ * radar and lidar perception in diverse environments using differential entropy"): if two clouds are aligned, merging them does
+ * not blur the scene.  Per point, the differential entropy of the local point distribution in the merged cloud (joint) is compared
+ * with the one in the point's own cloud (separate); quality = mean joint - mean separate entropy is about 0 when aligned and grows
+ * with misalignment.  rsx_cfear_result.cost and rsx_icp_result.fitness are small wherever their solver found a minimum, right or
+ * wrong; this measure depends on no solver and judges every estimator here alike.  CorAl's own code is not part of the reference
+ * checkout: the rules below are restated in tests/coral_np.py, which is the arithmetic contract -- parity unpinned.
+ * One job: cloud A (n_a <= RSX_CORAL_MAX_POINTS points, float x, y, A's frame), cloud B (n_b points, B's frame), T = six doubles
+ * (r00, r01, tx, r10, r11, ty) taking B into A's frame -- a matrix, not a yaw: the device evaluates no sine.  All in fp64 on the
+ * float inputs, nothing fused, every sum sequential in the order stated:
+ *   - the joint cloud: joint index i < n_a is A's point i; n_a + k is B's point k moved, x' = (r00 bx + r01 by) + tx,
+ *     y' = (r10 bx + r11 by) + ty, each rounded to float once, from there on an ordinary float input
+ *   - the cell grid is CFEAR's: ix = floor(x / r), iy = floor(y / r) on 128 x 128 cells; a point with ix or iy outside [-64, 64)
+ *     (non-finite included) is ignored by everything and sets RSX_CORAL_STATUS_RANGE; the others are valid
+ *   - the walk of a valid point p: the 3 x 3 block of cells around p's cell, dy = -1, 0, 1 outer, dx = -1, 0, 1 inner, ascending
+ *     joint index inside a cell, cells off the grid skipped; a visited q is a neighbour iff |q - p|^2 <= r^2 (p is its own
+ *     neighbour).  The joint set: all neighbours in walk order; the separate set: those from p's own cloud, in the same order
+ *   - pass 1: the counts m_joint and m_separate and the coordinate sums of both sets; p is SCORED iff m_separate >= min_points
+ *     and m_joint - m_separate >= min_other (CorAl's "overlap only" rule)
+ *   - pass 2 (scored points, each set): mu = sum / m; sxx += ex ex, syy += ey ey, sxy += ex ey with e = q - mu in walk order,
+ *     each divided by (m - 1); det = sxx syy - sxy sxy
+ *   - the per-point records (joint-index order) equal the restatement's bit for bit: the counts for every valid point, the
+ *     determinants 0.0 for an unscored one, every field 0 for an invalid one
+ *   - h(det) = 0.5 log(max(det, det_min)) + (1 + log(2 pi)); h_joint and h_separate are the means of h over the scored points,
+ *     quality = h_joint - h_separate.  The logarithm and the order in which the per-point terms are added are the device's own
+ *     (a fixed order: a job's result does not depend on its place in a batch); they are the only part that is not bit-exact
+ * det_min: 1e-6 m^4 is of the order of the square of one range bin's area; it keeps a collinear neighbourhood from giving -inf. */
+
+typedef struct rsx_coral rsx_coral;
+
+#define RSX_CORAL_MAX_POINTS 8192 /* points of ONE cloud of a job (the joint cloud holds 16384) */
+#define RSX_CORAL_STATUS_RANGE 1  /* some point of the joint cloud lay outside the 128 x 128 cell grid (or was not finite) */
+#define RSX_CORAL_STATUS_POINTS 2 /* (device entries only) a cloud holds more than RSX_CORAL_MAX_POINTS points: nothing is computed,
+                                     the result and the records are zero (the host entry refuses such a job with RSX_ERR_BAD_ARG) */
+#define RSX_CORAL_STATUS_EMPTY 4  /* no point was scored: quality, h_joint and h_separate are 0 */
+
+typedef struct {
+  double radius;      /* r: cell side and neighbourhood radius [m], > 0 (3.5) */
+  double det_min;     /* floor of a covariance determinant [m^4], > 0 (1e-6) */
+  int32_t min_points; /* neighbours of its own cloud a scored point needs, >= 2 (6) */
+  int32_t min_other;  /* neighbours of the other cloud a scored point needs, >= 0 (1) */
+} rsx_coral_params;
+
+typedef struct {
+  double det_separate, det_joint; /* 0.0 unless the point is scored */
+  int32_t m_separate, m_joint;    /* neighbours in its own cloud / in the joint cloud (itself included); 0 for an invalid point */
+} rsx_coral_point;                /* 24 bytes */
+
+typedef struct {
+  double quality;     /* h_joint - h_separate */
+  double h_joint;     /* mean joint entropy of the scored points */
+  double h_separate;  /* mean separate entropy of the scored points */
+  int32_t n_scored;   /* scored points of both clouds */
+  int32_t n_scored_a; /* those of cloud A */
+  int32_t n_valid;    /* points of the joint cloud inside the grid */
+  int32_t status;     /* RSX_CORAL_STATUS_* */
+} rsx_coral_result;   /* 40 bytes */
+
+/* a violated rule of rsx_coral_params gives RSX_ERR_BAD_ARG in every entry that takes the struct (NULL = the defaults) */
+int rsx_coral_default_params(rsx_coral_params *p);
+int rsx_coral_create(int device, rsx_coral **out);
+int rsx_coral_destroy(rsx_coral *h);
+/* n_jobs jobs; job i owns points [a_offsets[i], a_offsets[i + 1]) of a_xy and [b_offsets[i], b_offsets[i + 1]) of b_xy (float x, y
+ * per point) and transforms[6 i .. 6 i + 5] (transforms NULL: every job at the identity); both offset arrays as for
+ * rsx_orora_register_batch (checked), and no cloud may hold more than RSX_CORAL_MAX_POINTS points (RSX_ERR_BAD_ARG).
+ * out_results[i] is job i's result; out_points (may be NULL) receives the records, job i's from a_offsets[i] + b_offsets[i] on.
+ * Host buffers, synchronous.  One workgroup per job, one launch. */
+int rsx_coral_quality_batch(rsx_coral *h, const float *a_xy, const int64_t *a_offsets, const float *b_xy, const int64_t *b_offsets, int32_t n_jobs,
+                            const double *transforms, const rsx_coral_params *params, rsx_coral_result *out_results,
+                            rsx_coral_point *out_points);
+/* device buffers (d_transforms and d_points too, or NULL), asynchronous on `stream`; a point is point_stride floats (>= 2), x and
+ * y first, so a packed float4 cloud is read in place (point_stride 4); the offsets are trusted, a job with a cloud above the cap
+ * gets RSX_CORAL_STATUS_POINTS.  The handle's workspace grows to min(n_jobs, 256) x 128 KiB; no allocation otherwise */
+int rsx_coral_quality_batch_device(rsx_coral *h, const float *d_a, const int64_t *d_a_offsets, const float *d_b, const int64_t *d_b_offsets,
+                                   int32_t point_stride, int32_t n_jobs, const double *d_transforms, const rsx_coral_params *params,
+                                   rsx_coral_result *d_results, rsx_coral_point *d_points, void *stream);
+
 /* ============================== radar scan context ====================================
  * The "radar scan context" of the MulRan paper (Kim et al., ICRA 2020; reference README.md:28-29): the 20 x 60 polar grid
  * of the ScanContext descriptor filled with received power straight from the polar image -- dense where the descriptors of
@@ -1328,6 +1406,12 @@ int rsx_loop_verify(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const do
  * VoxelGrid `leaf`; *out_count = its size (only the first max_out points are written) */
 int rsx_kfstore_build_map(rsx_kfstore *h, const double *poses6, int64_t n_poses, int32_t skip_frames, float leaf, float *out_xyzi,
                           int64_t max_out, int64_t *out_count);
+/* CorAl alignment quality (above) of two stored keyframe clouds: A = keyframe idx_a, B = keyframe idx_b, each in its own frame and
+ * read where the store keeps it (x and y of the packed float4); transform = the six doubles taking B into A's frame (NULL:
+ * identity).  Synchronous, under the store's lock; both handles on one device; an index that is not stored gives
+ * RSX_ERR_BAD_ARG; a keyframe above RSX_CORAL_MAX_POINTS points gives RSX_CORAL_STATUS_POINTS in *out_result */
+int rsx_kfstore_alignment_quality(rsx_kfstore *kf, rsx_coral *h, int32_t idx_a, int32_t idx_b, const double *transform,
+                                  const rsx_coral_params *params, rsx_coral_result *out_result);
 /* downSizeFilterScancontext.filter + keyframeLaserClouds.push_back + scManager.makeAndSaveScancontextAndKeys in one call
  * (PGO.cpp:482-492): the downsampled cloud goes from the VoxelGrid into the keyframe store and the descriptor build
  * without leaving the GPU.  intensity_offset as above.  All three handles on the same device. */

@@ -145,6 +145,22 @@ CFEAR_TRACK_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"),
                                      ("n_keyframes", "<i4")])
 
 
+class CoralParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("det_min", C.c_double), ("min_points", C.c_int32), ("min_other", C.c_int32)]
+
+
+class CoralResult(C.Structure):
+    _fields_ = [("quality", C.c_double), ("h_joint", C.c_double), ("h_separate", C.c_double), ("n_scored", C.c_int32),
+                ("n_scored_a", C.c_int32), ("n_valid", C.c_int32), ("status", C.c_int32)]
+
+
+CORAL_MAX_POINTS = 8192  # per cloud of a job
+CORAL_STATUS_RANGE, CORAL_STATUS_POINTS, CORAL_STATUS_EMPTY = 1, 2, 4  # rsx_coral_result.status
+CORAL_RESULT_DTYPE = np.dtype([("quality", "<f8"), ("h_joint", "<f8"), ("h_separate", "<f8"), ("n_scored", "<i4"), ("n_scored_a", "<i4"),
+                               ("n_valid", "<i4"), ("status", "<i4")])
+CORAL_POINT_DTYPE = np.dtype([("det_separate", "<f8"), ("det_joint", "<f8"), ("m_separate", "<i4"), ("m_joint", "<i4")])
+
+
 class RadarScParams(C.Structure):
     _fields_ = [("max_radius", C.c_double), ("resolution", C.c_float), ("min_range", C.c_int32), ("power_floor", C.c_int32),
                 ("stat", C.c_int32)]
@@ -230,6 +246,8 @@ SYMBOLS = [
     "rsx_cfear_tracker_create", "rsx_cfear_tracker_destroy", "rsx_cfear_tracker_reset", "rsx_cfear_tracker_push", "rsx_cfear_tracker_push_device",
     "rsx_cfear_surface_points_timed_batch", "rsx_cfear_surface_points_timed_batch_device", "rsx_cfear_compensate_batch",
     "rsx_cfear_compensate_batch_device", "rsx_cfear_tracker_push_timed", "rsx_cfear_tracker_push_timed_device",
+    "rsx_coral_default_params", "rsx_coral_create", "rsx_coral_destroy", "rsx_coral_quality_batch", "rsx_coral_quality_batch_device",
+    "rsx_kfstore_alignment_quality",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
@@ -394,6 +412,12 @@ def lib():
         L.rsx_cfear_compensate_batch_device.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.rsx_cfear_tracker_push_timed.argtypes = [vp, vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp]
         L.rsx_cfear_tracker_push_timed_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(CfearParams), C.POINTER(CfearTrackParams), vp, vp]
+        L.rsx_coral_default_params.argtypes = [C.POINTER(CoralParams)]
+        L.rsx_coral_create.argtypes = [C.c_int, C.POINTER(vp)]
+        L.rsx_coral_destroy.argtypes = [vp]
+        L.rsx_coral_quality_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.POINTER(CoralParams), vp, vp]
+        L.rsx_coral_quality_batch_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(CoralParams), vp, vp, vp]
+        L.rsx_kfstore_alignment_quality.argtypes = [vp, vp, i32, i32, vp, C.POINTER(CoralParams), C.POINTER(CoralResult)]
         L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
         L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
         L.rsx_radarsc_destroy.argtypes = [vp]

@@ -51,20 +51,6 @@ struct SpConsts {
   int min_points, max_records;
 };
 
-// f(input index) for every point of the 3 x 3 block of cells around (ix, iy): dy outer, dx inner, ascending index inside a cell
-template <typename F>
-__device__ __forceinline__ void for_block(const unsigned *keys, const unsigned short *start, unsigned n, int ix, int iy, F &&f) {
-  for (int dy = -1; dy <= 1; dy++)
-    for (int dx = -1; dx <= 1; dx++) {
-      const int jx = ix + dx, jy = iy + dy;
-      if (jx < 0 || jx >= GRID || jy < 0 || jy >= GRID) continue;
-      const unsigned cc = (unsigned)(jy * GRID + jx);
-      unsigned k = start[cc];
-      if (k == NO_CELL) continue;
-      for (; k < n && (keys[k] >> IDX_BITS) == cc; k++) f(keys[k] & IDX_MASK);
-    }
-}
-
 // TIMED: point i of the scan was measured on azimuth row rows[(begin + i) * row_stride] of n_rows; a record's time, the circular
 // mean of its neighbours' rows as a fraction of the revolution, goes to out_tau (laid out like out).  Untimed, the kernel is the
 // code it was: everything timed sits behind if constexpr
@@ -136,7 +122,7 @@ __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restr
         const double cx = sx / (double)own, cy = sy / (double)own;
         int m = 0;
         sx = sy = 0.0;
-        for_block(keys, start, n, ix, iy, [&](unsigned idx) {
+        for_block<IDX_BITS>(keys, start, n, ix, iy, [&](unsigned idx) {
           const float2 q = p[idx];
           const double ex = (double)q.x - cx, ey = (double)q.y - cy;
           if (ex * ex + ey * ey <= k.r2) {
@@ -150,7 +136,7 @@ __global__ __launch_bounds__(NT) void cfear_surface_kernel(const float2 *__restr
           double sxx = 0.0, syy = 0.0, sxy = 0.0;
           int a1 = -1, dsum = 0;  // the first neighbour's row; the sum of the others' signed row distances from it (|d| <= 32768,
                                   // m <= 16384: an int holds it)
-          for_block(keys, start, n, ix, iy, [&](unsigned idx) {
+          for_block<IDX_BITS>(keys, start, n, ix, iy, [&](unsigned idx) {
             const float2 q = p[idx];
             const double ex = (double)q.x - cx, ey = (double)q.y - cy;
             if (ex * ex + ey * ey <= k.r2) {

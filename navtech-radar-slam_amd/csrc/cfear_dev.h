@@ -1,5 +1,6 @@
-// cfear_dev.h -- the device code csrc/cfear.hip (surface points) and csrc/cfear_track.hip (registration) both need: the
-// 128 x 128 grid of cells of one radius, points / records sorted by cell in LDS, and the motion compensation of a record.  A key is cell << IDX_BITS | index, all
+// cfear_dev.h -- the device code csrc/cfear.hip (surface points), csrc/cfear_track.hip (registration) and csrc/coral.hip
+// (alignment quality) need: the 128 x 128 grid of cells of one radius, points / records sorted by cell in LDS, the walk of a
+// 3 x 3 block of cells, and the motion compensation of a record.  A key is cell << IDX_BITS | index, all
 // ones for an element outside the grid; sorted keys order the elements by cell and, inside a cell, by index.  Everything is
 // __forceinline__: a kernel keeps the instruction sequence it had with the code written out in place.
 #pragma once
@@ -43,6 +44,21 @@ __device__ __forceinline__ void fill_cell_table(const unsigned *keys, int n, uns
     if (OUTSIDE && key == NO_KEY) continue;
     if (i == 0 || (keys[i - 1] >> IDX_BITS) != (key >> IDX_BITS)) table[key >> IDX_BITS] = (unsigned short)i;
   }
+}
+
+// f(index) for every element of the 3 x 3 block of cells around (ix, iy), from the sorted keys[0 .. n) and their cell table:
+// dy outer, dx inner, ascending index inside a cell; cells off the grid are skipped
+template <unsigned IDX_BITS, typename F>
+__device__ __forceinline__ void for_block(const unsigned *keys, const unsigned short *start, unsigned n, int ix, int iy, F &&f) {
+  for (int dy = -1; dy <= 1; dy++)
+    for (int dx = -1; dx <= 1; dx++) {
+      const int jx = ix + dx, jy = iy + dy;
+      if (jx < 0 || jx >= GRID || jy < 0 || jy >= GRID) continue;
+      const unsigned cc = (unsigned)(jy * GRID + jx);
+      unsigned k = start[cc];
+      if (k == NO_CELL) continue;
+      for (; k < n && (keys[k] >> IDX_BITS) == cc; k++) f(keys[k] & ((1u << IDX_BITS) - 1u));
+    }
 }
 
 // Motion compensation of surface-point records (include/rsx.h, rsx_cfear_compensate_batch; tests/cfear_mocomp_np.py): the

@@ -231,6 +231,12 @@ int append_device_locked(rsx_kfstore *h, const void *d_xyzi, int64_t n, int32_t 
   RSX_HIP(hipStreamSynchronize(h->stream));
   return RSX_OK;
 }
+int keyframe_device_locked(rsx_kfstore *h, int32_t index, const float **d_xyzi, int64_t *n) {
+  if (index < 0 || index >= (int64_t)h->off.size() - 1) return fail(RSX_ERR_BAD_ARG, "keyframe %d out of range (%lld stored)", index, (long long)h->off.size() - 1);
+  *d_xyzi = reinterpret_cast<const float *>(h->clouds.as<float4>() + h->off[index]);
+  *n = h->off[index + 1] - h->off[index];
+  return RSX_OK;
+}
 
 }  // namespace kf
 }  // namespace rsx

@@ -12,9 +12,16 @@
 // keyframe, which is what the reference itself uses until the first iSAM2 update (PGO.cpp:489).
 // --save-map <file.pcd> writes the cloud pubMap publishes (PGO.cpp:631-655: every 2nd keyframe through its pose,
 // VoxelGrid of --map_viz_filter_size, default 0.4) as a binary PCD file: the map-saving utility of README.md:139.
+// --alignment-quality (with --verify-loops) judges every verified pair by a measure that is not the solver's own residual: the
+// CorAl alignment quality (rsx_kfstore_alignment_quality; include/rsx.h) of the loop keyframe's own cloud (A) and the current
+// keyframe's own cloud (B) under the transform ICP found, T = P^-1 T_icp P reduced to the plane (rows and columns 0, 1, 3 of the
+// 4 x 4), P = the root pose (x, y, yaw).  Radar recordings have z = roll = pitch = 0, which is what that reduction assumes.  One
+// "[SC loop] alignment quality ..." line follows every ICP line.  --max-quality X (implies --alignment-quality; there is no default
+// X) turns a pair that ICP accepted, with Q > X or with no scored point, into a rejected one in the printed verdict.  Without these
+// flags the output is what it was.
 //
 // usage: pgo_replay <recording> [--keyframe_meter_gap 2.0] [--sc_dist_thres 0.45] [--exhaustive] [--devices 0,1,..]
-//                   [--verify-loops] [--save-map map.pcd] [--map_viz_filter_size 0.4]
+//                   [--verify-loops [--alignment-quality] [--max-quality X]] [--save-map map.pcd] [--map_viz_filter_size 0.4]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -34,11 +41,17 @@ struct Pt32 {  // pcl::PointXYZI memory layout
 int main(int argc, char **argv) {
   try {
     if (argc < 2) {
-      std::fprintf(stderr, "usage: pgo_replay <recording> [--keyframe_meter_gap m] [--sc_dist_thres d] [--exhaustive] [--devices a,b]\n");
+      std::fprintf(stderr,
+                   "usage: pgo_replay <recording> [--keyframe_meter_gap m] [--sc_dist_thres d] [--exhaustive] [--devices a,b]\n"
+                   "                  [--verify-loops [--alignment-quality] [--max-quality X]] [--save-map map.pcd] [--map_viz_filter_size s]\n"
+                   "  --alignment-quality  after every ICP line, the CorAl alignment quality of the two keyframes' own clouds under ICP's\n"
+                   "                       transform, reduced to the plane: radar recordings have z = roll = pitch = 0\n"
+                   "  --max-quality X      (implies --alignment-quality; no default) reject an ICP-accepted pair with Q > X or no scored point\n");
       return 1;
     }
     double keyframe_meter_gap = 2.0, sc_dist_thres = 0.2;  // PGO.cpp:676-677 defaults (sc_pgo.launch sets 0.2 / 0.45)
-    bool exhaustive = false, verify_loops = false;
+    bool exhaustive = false, verify_loops = false, alignment_quality = false, have_max_quality = false;
+    double max_quality = 0.0;
     std::string map_path;
     float map_viz_filter_size = 0.4f;  // PGO.cpp:691 default of mapviz_filter_size
     std::vector<int> devices;
@@ -48,6 +61,11 @@ int main(int argc, char **argv) {
       else if (a == "--sc_dist_thres" && i + 1 < argc) sc_dist_thres = std::atof(argv[++i]);
       else if (a == "--exhaustive") exhaustive = true;
       else if (a == "--verify-loops") verify_loops = true;
+      else if (a == "--alignment-quality") alignment_quality = true;
+      else if (a == "--max-quality" && i + 1 < argc) {
+        max_quality = std::atof(argv[++i]);
+        alignment_quality = have_max_quality = true;
+      }
       else if (a == "--save-map" && i + 1 < argc) map_path = argv[++i];
       else if (a == "--map_viz_filter_size" && i + 1 < argc) map_viz_filter_size = (float)std::atof(argv[++i]);
       else if (a == "--devices" && i + 1 < argc)
@@ -57,6 +75,7 @@ int main(int argc, char **argv) {
           if (*p == ',') p++;
         }
     }
+    if (alignment_quality && !verify_loops) throw std::runtime_error("--alignment-quality and --max-quality need --verify-loops");
     FILE *f = std::fopen(argv[1], "rb");
     if (!f) throw std::runtime_error(std::string("cannot open ") + argv[1]);
     char magic[10];
@@ -77,6 +96,8 @@ int main(int argc, char **argv) {
       if (rsx_kfstore_create(devices.empty() ? 0 : devices[0], &kf) != RSX_OK) throw std::runtime_error(rsx_last_error_string());
       scManager.attachKeyframeStore(kf);
     }
+    rsx_coral *coral = nullptr;
+    if (alignment_quality && rsx_coral_create(devices.empty() ? 0 : devices[0], &coral) != RSX_OK) throw std::runtime_error(rsx_last_error_string());
 
     // laserOdometryHandler / laserCloudFullResHandler: the two queues (PGO.cpp:124-137)
     struct Msg {
@@ -131,8 +152,42 @@ int main(int argc, char **argv) {
               std::cout << "[SC loop] ICP fitness test failed (" << v.fitness << " > " << 0.3f << "). Reject this SC loop." << std::endl;
             } else {
               std::cout << "[SC loop] ICP fitness test passed (" << v.fitness << " < " << 0.3f << "). Add this SC loop." << std::endl;
-              n_accepted++;
             }
+            bool accepted = v.accepted != 0;
+            if (alignment_quality) {
+              // B = the current keyframe's frame into A = the loop keyframe's: both clouds were moved by the root pose P before the
+              // ICP, so T = P^-1 T_icp P; of P only x, y, yaw are used and of T only the plane (rows and columns 0, 1, 3)
+              const double *pose = &keyframePosesUpdated[6 * (size_t)r.first];
+              const double c = std::cos(pose[5]), s = std::sin(pose[5]);
+              const double P[16] = {c, -s, 0, pose[0], s, c, 0, pose[1], 0, 0, 1, 0, 0, 0, 0, 1};
+              const double Pi[16] = {c, s, 0, -(c * pose[0] + s * pose[1]), -s, c, 0, -(c * pose[1] - s * pose[0]), 0, 0, 1, 0, 0, 0, 0, 1};
+              double TP[16], M[16];
+              for (int i = 0; i < 4; i++)
+                for (int j = 0; j < 4; j++) {
+                  TP[4 * i + j] = 0.0;
+                  for (int k = 0; k < 4; k++) TP[4 * i + j] += (double)v.transform[4 * i + k] * P[4 * k + j];
+                }
+              for (int i = 0; i < 4; i++)
+                for (int j = 0; j < 4; j++) {
+                  M[4 * i + j] = 0.0;
+                  for (int k = 0; k < 4; k++) M[4 * i + j] += Pi[4 * i + k] * TP[4 * k + j];
+                }
+              const double T6[6] = {M[0], M[1], M[3], M[4], M[5], M[7]};
+              rsx_coral_result q;
+              if (rsx_kfstore_alignment_quality(kf, coral, r.first, (int32_t)(n_keyframes - 1), T6, nullptr, &q) != RSX_OK)
+                throw std::runtime_error(rsx_last_error_string());
+              std::printf("[SC loop] alignment quality Q = %.6f (H_joint %.6f, H_separate %.6f), scored %d / %d, status %d", q.quality, q.h_joint,
+                          q.h_separate, q.n_scored, q.n_valid, q.status);
+              if (have_max_quality && accepted) {
+                accepted = q.n_scored > 0 && !(q.quality > max_quality);
+                if (accepted) std::printf(". Q <= %g. Keep this SC loop.", max_quality);
+                else if (q.n_scored > 0) std::printf(". Q > %g. Reject this SC loop.", max_quality);
+                else std::printf(". No scored point. Reject this SC loop.");
+              }
+              std::printf("\n");
+              std::fflush(stdout);
+            }
+            if (accepted) n_accepted++;
           }
         }
       }
@@ -165,6 +220,7 @@ int main(int argc, char **argv) {
       pcd::write_binary_xyzi(map_path, map.data(), m);
       std::printf("map: %lld points from %lld keyframes -> %s\n", (long long)m, (long long)nk, map_path.c_str());
     }
+    if (coral) rsx_coral_destroy(coral);
     if (kf) rsx_kfstore_destroy(kf);
     std::printf("frames=%ld keyframes=%ld loops=%ld dropped_odom=%ld", n_frames, n_keyframes, n_loops, n_dropped);
     if (verify_loops) std::printf(" loops_accepted=%ld", n_accepted);

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import LoopVerifyParams, LoopVerifyResult, check, lib
+from ._rsx import CORAL_RESULT_DTYPE, CoralResult, LoopVerifyParams, LoopVerifyResult, check, lib
 
 
 class KeyframeStore:
@@ -81,6 +81,15 @@ class KeyframeStore:
         check(self._L.rsx_loop_verify_clouds(self._h, loop_idx, curr_idx, rp.ctypes.data, C.byref(self.params), src.ctypes.data,
                                              C.c_int64(src.shape[0]), C.byref(ns), tgt.ctypes.data, C.c_int64(tgt.shape[0]), C.byref(nt)))
         return src[:ns.value].copy(), tgt[:nt.value].copy()
+
+    def alignment_quality(self, idx_a, idx_b, transform, coral, params=None):
+        """CorAl alignment quality (coral.Coral) of keyframe idx_b against keyframe idx_a, both read in place in the store;
+        transform: (r00, r01, tx, r10, r11, ty) taking idx_b's frame into idx_a's, None = identity -> a CORAL_RESULT_DTYPE scalar"""
+        t = None if transform is None else np.ascontiguousarray(transform, dtype=np.float64).reshape(6)
+        r = CoralResult()
+        check(self._L.rsx_kfstore_alignment_quality(self._h, coral.handle, idx_a, idx_b, t.ctypes.data if t is not None else None,
+                                                    C.byref(params) if params is not None else None, C.byref(r)))
+        return np.frombuffer(bytes(r), dtype=CORAL_RESULT_DTYPE)[0]
 
     def build_map(self, poses, skip=2, leaf=0.4):
         ps = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 6)
