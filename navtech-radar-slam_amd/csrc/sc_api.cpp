@@ -1775,7 +1775,7 @@ int rsx_sc_profile_read_rescoring(rsx_sc *h, rsx_sc_rescoring_stats *out) try {
       for (int i = 0; i < RESCORE_STAT_WORDS; i++) v[i] += all[(size_t)c * RESCORE_STAT_WORDS + i];
   }
   if (rsx::exp_env("RSX_RESCORE_PROF") && v[1])  // region cycles of the re-scoring wave, averaged per query that scored
-    fprintf(stderr, "[sc_rescore prof] per query (cycles): start loads %.0f  round filter + touch %.0f  pick %.0f  phaseB %.0f  align %.0f  entry wait %.0f  total %.0f\n",
+    fprintf(stderr, "[sc_rescore prof] per query (cycles): start loads %.0f  round filter + rank + touch %.0f  between evaluations %.0f  phaseB %.0f  align %.0f  entry wait %.0f  total %.0f\n",
             (double)v[4] / v[1], (double)v[5] / v[1], (double)v[6] / v[1], (double)v[7] / v[1], (double)v[8] / v[1], (double)v[9] / v[1],
             (double)v[10] / v[1]);
   *candidates = (int64_t)v[0];

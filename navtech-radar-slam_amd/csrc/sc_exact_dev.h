@@ -74,6 +74,56 @@ __device__ __forceinline__ void touch_wait(Touch &t) {
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(t.d0), "+v"(t.d1), "+v"(t.d2)::"memory");
 }
 
+// load_entry for a caller that issues YOUNGER loads behind it (touch_entry) and wants the entry while those are still in
+// flight.  The compiler waits for its own loads with the count of the younger loads IT knows of, and it knows nothing of asm
+// loads: a load_entry followed by touches is waited for with vmcnt(0), touches included.  So these seven loads are asm too,
+// and the caller waits for them itself: entry_wait(r, n) with n = the touch_entry calls issued since (VMEM returns in order:
+// at most 3 n loads outstanding means these have landed).  Between the two calls the registers of `r` are reserved but NOT
+// valid -- the same contract as struct Touch, with entry_wait as the end of the reservation; nothing may read `r` before.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+struct EntryAsync {
+  f32x4 c0, c1, c2, c3, c4;
+  double v, n2;
+};
+__device__ __forceinline__ void load_entry_async(const DbView &db, int64_t slot, int lane, EntryAsync &r) {
+  const int cl = lane < NS ? lane : 0;
+  const float *pd = db.desc + slot * DS + cl * NR;
+  const double *pk = db.vkey + slot * NS + cl, *pn = db.norm + slot * NS + cl;
+  asm volatile("global_load_dwordx2 %0, %7, off\n\t"
+               "global_load_dwordx4 %1, %8, off\n\t"
+               "global_load_dwordx4 %2, %8, off offset:16\n\t"
+               "global_load_dwordx4 %3, %8, off offset:32\n\t"
+               "global_load_dwordx4 %4, %8, off offset:48\n\t"
+               "global_load_dwordx4 %5, %8, off offset:64\n\t"
+               "global_load_dwordx2 %6, %9, off"
+               : "=&v"(r.v), "=&v"(r.c0), "=&v"(r.c1), "=&v"(r.c2), "=&v"(r.c3), "=&v"(r.c4), "=&v"(r.n2)
+               : "v"(pk), "v"(pd), "v"(pn)
+               : "memory");
+}
+#define RSX_VMCNT_CASE(n) \
+  case n: asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); break;
+// n_touches (wave-uniform): touch_entry calls since load_entry_async(r), three loads each; s_waitcnt takes an immediate, hence
+// the switch.  The counter holds 6 bits: with 20 touches or more behind the entry, "at most 60 outstanding" still means that
+// the entry, older than all of them, has landed.  `out` receives the entry; `r` is dead afterwards.
+__device__ __forceinline__ void entry_wait(EntryAsync &r, int n_touches, EntryRegs &out) {
+  switch (n_touches < 20 ? 3 * n_touches : 60) {
+    RSX_VMCNT_CASE(0) RSX_VMCNT_CASE(3) RSX_VMCNT_CASE(6) RSX_VMCNT_CASE(9) RSX_VMCNT_CASE(12) RSX_VMCNT_CASE(15)
+    RSX_VMCNT_CASE(18) RSX_VMCNT_CASE(21) RSX_VMCNT_CASE(24) RSX_VMCNT_CASE(27) RSX_VMCNT_CASE(30) RSX_VMCNT_CASE(33)
+    RSX_VMCNT_CASE(36) RSX_VMCNT_CASE(39) RSX_VMCNT_CASE(42) RSX_VMCNT_CASE(45) RSX_VMCNT_CASE(48) RSX_VMCNT_CASE(51)
+    RSX_VMCNT_CASE(54) RSX_VMCNT_CASE(57)
+    default: asm volatile("s_waitcnt vmcnt(60)" ::: "memory"); break;
+  }
+  asm volatile("" : "+v"(r.v), "+v"(r.c0), "+v"(r.c1), "+v"(r.c2), "+v"(r.c3), "+v"(r.c4), "+v"(r.n2));
+  out.v = r.v;
+  out.n2 = r.n2;
+  out.ecol[0] = float4{r.c0.x, r.c0.y, r.c0.z, r.c0.w};
+  out.ecol[1] = float4{r.c1.x, r.c1.y, r.c1.z, r.c1.w};
+  out.ecol[2] = float4{r.c2.x, r.c2.y, r.c2.z, r.c2.w};
+  out.ecol[3] = float4{r.c3.x, r.c3.y, r.c3.z, r.c3.w};
+  out.ecol[4] = float4{r.c4.x, r.c4.y, r.c4.z, r.c4.w};
+}
+#undef RSX_VMCNT_CASE
+
 // exact stage 1 of pair_group (fastAlignUsingVkey, SC.cpp:93-113) for one entry: v1 = the query's sector key (60 doubles
 // in LDS), ev = the entry's key, one element per lane; uses the key-image part of the wave's LDS region
 template <int SO = dev::SO_SSE2>
@@ -113,7 +163,10 @@ __device__ __forceinline__ int align_exact(const double *v1, char *wsm, int lane
   }
   const bool ok = (lane < NS) && (nrm < kBig);
   double m = ok ? nrm : INFINITY;
-  m = wave::butterfly(m, [](double a, double b) { return fmin(a, b); });
+  {  // (no lane holds a NaN, and a minimum has no order: DPP inside the rows, v_readlane across them; the whole wave is active)
+    auto mn = [](double a, double b) { return fmin(a, b); };
+    m = wave::rows_pair(wave::row_reduce(m, mn), mn);
+  }
   const unsigned long long bal = __ballot(ok && nrm == m);
   wave::lds_fence();
   return bal ? (__ffsll((long long)bal) - 1) : 0;
@@ -234,17 +287,21 @@ __device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane,
       bk = k;
     }
   }
-#pragma unroll
-  for (int off = 1; off <= 4; off <<= 1) {
-    const double od = __shfl_xor(bd, off);
-    const int ok = __shfl_xor(bk, off);
+  // the best of lanes 0 .. 7 under (distance, shift): the candidates' shifts differ, so hit_before is a total order on them
+  // (the lanes without one hold the same {+inf, INT_MAX}) and its minimum does not depend on the order of the comparisons --
+  // three DPP steps inside the row (lane ^ 1, lane ^ 2, 7 - lane) and a v_readlane, where the xor ladder through
+  // ds_bpermute took twelve dependent LDS round trips per evaluation.  (The whole wave is active here.)
+  auto take = [&](double od, int ok) {
     if (hit_before(od, ok, bd, bk)) {
       bd = od;
       bk = ok;
     }
-  }
-  bd = __shfl(bd, 0);
-  bk = __shfl(bk, 0);
+  };
+  take(wave::dpp<0xB1>(bd), wave::dpp<0xB1>(bk));    // quad_perm [1,0,3,2]
+  take(wave::dpp<0x4E>(bd), wave::dpp<0x4E>(bk));    // quad_perm [2,3,0,1]
+  take(wave::dpp<0x141>(bd), wave::dpp<0x141>(bk));  // row_half_mirror
+  bd = wave::readlane(bd, 0);
+  bk = wave::readlane(bk, 0);
   if (bd == INFINITY) {
     bd = kBig;
     bk = 0;

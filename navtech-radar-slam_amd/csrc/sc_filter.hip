@@ -494,10 +494,48 @@ __device__ __forceinline__ int64_t n_elig_items(const Elig &el, int q, int64_t n
 //            from the row of bounds (writing all of it was 134 MB per 8192 queries, of which 121 records per query were used)
 // ------------------------------------------------------------------------------------------
 
+// Region timers of the kernel: -DRSX_SELECT_PROF=1 (tools/build_select_prof.sh; neither the product nor the experiments build
+// has them).  Every wave sums s_memtime differences per region -- each lap drains the wave's own memory and LDS queues first
+// -- and adds them to block (query % SEL_PROF_COPIES) of a buffer that launch_select prints after every launch.  cap_mode (the
+// same builds, RSX_SELECT_CAP_ATOMICS=1): a timing-only second launch whose histogram pass skips every bound above bin
+// b_cap + 1 of the first launch (read back from `thr`).  The counts up to that bin are exact and no consumer asks for more,
+// so it writes what the first launch wrote; its time against a plain launch is the ceiling of any scheme that histograms
+// less.
+#ifdef RSX_SELECT_PROF
+constexpr bool kSelProf = true, kSelLaps = RSX_SELECT_PROF == 1;  // (2: cap_mode without the timers, for the kernel trace)
+#else
+constexpr bool kSelProf = false, kSelLaps = false;
+#endif
+enum SelProfRegion {
+  SP_LOAD = 0,  // zeroing the histogram, the row's loads issued and landed (one-piece rows; a long row loads inside SP_HIST)
+  SP_HIST,      // the histogram pass and the barrier behind it
+  SP_SCAN,      // prefix sums, b_cap, the round edges, the head, the fill offsets
+  SP_COMPACT,   // the compaction pass and the stores of the records
+  SP_TOTAL,
+  SP_COUNT,     // waves that reported
+  SEL_PROF_WORDS
+};
+constexpr int SEL_PROF_COPIES = 64;
+
 __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__ lb, int64_t ld, int64_t n_items_all,
                                                         Elig el, int32_t first_target,
                                                         RescoreEntry *__restrict__ slist,
-                                                        int32_t *__restrict__ sl_cnt, float *__restrict__ thr) {
+                                                        int32_t *__restrict__ sl_cnt, float *__restrict__ thr,
+                                                        unsigned long long *prof, int cap_mode) {
+  long long t_mark = 0, t_begin = 0, tacc[SP_TOTAL] = {0, 0, 0, 0};
+  if constexpr (kSelLaps) t_begin = t_mark = clock64();
+  auto lap = [&](int region) {
+    if constexpr (kSelLaps) {
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      const long long t = clock64();
+      tacc[region] += t - t_mark;
+      t_mark = t;
+    }
+  };
+  int cap_bin = H_BINS;  // (cap_mode) bounds in bins above this one are not counted
+  if constexpr (kSelProf) {
+    if (cap_mode) cap_bin = lb_edge_bin(thr[(int64_t)blockIdx.x * RESCORE_THR_STRIDE + RESCORE_NUM_THR - 1]) + 1;
+  }
   __shared__ int hist[H_BINS];
   __shared__ int wsum[4];
   __shared__ int s_bcap;
@@ -539,7 +577,10 @@ __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__
   // first = true: the pass that loads; a later pass of a one-piece row walks the registers it left behind
   auto for_row = [&](bool first, auto &&f) {
     if (one_piece) {
-      if (first) load_piece(0, keep);
+      if (first) {
+        load_piece(0, keep);
+        lap(SP_LOAD);
+      }
       walk_piece(0, keep, f);
     } else {
       for (int64_t c0 = 0; c0 < n8; c0 += 256 * SEL_U) {
@@ -552,9 +593,13 @@ __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__
     if (i < n_items) f((float)row[i], i);
   };
   for_row(true, [&](float d, int64_t) {
+    if constexpr (kSelProf) {
+      if (lb_bin(d) > cap_bin) return;
+    }
     if (d != INFINITY) atomicAdd(&hist[lb_bin(d)], 1);  // +inf: no effective column at any shift, never a hit
   });
   __syncthreads();
+  lap(SP_HIST);
   int v[8];
   int run = 0;
 #pragma unroll
@@ -610,6 +655,7 @@ __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__
   __shared__ int fill[H_BINS];
   for (int i = threadIdx.x; i < H_BINS; i += 256) fill[i] = i ? hist[i - 1] : 0;  // exclusive prefix = first position
   __syncthreads();
+  lap(SP_SCAN);
   if (b_head >= 0) {
     for_row(false, [&](float d, int64_t i) {  // second pass: the kept registers (or, for a long row, a second reading)
       if (d == INFINITY) return;
@@ -624,6 +670,16 @@ __global__ __launch_bounds__(256) void sc_select_kernel(const lb_t *__restrict__
   if (threadIdx.x == 0) s_total = b_cap >= 0 ? hist[b_cap] : 0;
   __syncthreads();
   if (threadIdx.x == 0) sl_cnt[q] = s_total;
+  if constexpr (kSelLaps) {
+    lap(SP_COMPACT);
+    if (prof && lane == 0) {
+      unsigned long long *o = prof + (size_t)(q % SEL_PROF_COPIES) * SEL_PROF_WORDS;
+#pragma unroll
+      for (int r = 0; r < SP_TOTAL; r++) atomicAdd(o + r, (unsigned long long)tacc[r]);
+      atomicAdd(o + SP_TOTAL, (unsigned long long)(t_mark - t_begin));
+      atomicAdd(o + SP_COUNT, 1ull);
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -769,8 +825,36 @@ int launch_select(const DbView &db, const lb_t *lb, int64_t ld_lb, int64_t n_ite
   if (nq <= 0) return RSX_OK;
   if (first_target < 1 || first_target > 128) return fail(RSX_ERR_INTERNAL, "bad first_target");
   const Elig el{db.idx_base, db.idx_stride, n_eligible < 0 ? INT64_MAX : n_eligible, q_elig};
-  hipLaunchKernelGGL(sc_select_kernel, dim3(nq), dim3(256), 0, s, lb, ld_lb, n_items, el, first_target, slist, sl_cnt, thr);
+#ifndef RSX_SELECT_PROF
+  hipLaunchKernelGGL(sc_select_kernel, dim3(nq), dim3(256), 0, s, lb, ld_lb, n_items, el, first_target, slist, sl_cnt, thr,
+                     static_cast<unsigned long long *>(nullptr), 0);
   RSX_HIP(hipGetLastError());
+#else
+  // (a profiling build: one device, one launch at a time, never freed) with RSX_SELECT_CAP_ATOMICS=1 every selection is two
+  // launches, the second one capped by what the first one found
+  constexpr size_t kProfWords = (size_t)SEL_PROF_COPIES * SEL_PROF_WORDS;
+  static unsigned long long *d_prof = nullptr;
+  if (!d_prof) RSX_HIP(hipMalloc(reinterpret_cast<void **>(&d_prof), kProfWords * 8));
+  static const bool capped = [] {
+    const char *e = getenv("RSX_SELECT_CAP_ATOMICS");
+    return e && atoi(e) != 0;
+  }();
+  for (int pass = 0; pass < (capped ? 2 : 1); pass++) {
+    RSX_HIP(hipMemsetAsync(d_prof, 0, kProfWords * 8, s));
+    hipLaunchKernelGGL(sc_select_kernel, dim3(nq), dim3(256), 0, s, lb, ld_lb, n_items, el, first_target, slist, sl_cnt, thr, d_prof, pass);
+    RSX_HIP(hipGetLastError());
+    static unsigned long long h[kProfWords];
+    RSX_HIP(hipMemcpyAsync(h, d_prof, kProfWords * 8, hipMemcpyDeviceToHost, s));
+    RSX_HIP(hipStreamSynchronize(s));
+    double v[SEL_PROF_WORDS] = {0};
+    for (int c = 0; c < SEL_PROF_COPIES; c++)
+      for (int i = 0; i < SEL_PROF_WORDS; i++) v[i] += (double)h[(size_t)c * SEL_PROF_WORDS + i];
+    if (v[SP_COUNT] > 0)
+      fprintf(stderr, "[sc_select prof] nq %d%s (cycles per wave, %.0f reported):  load %.0f  histogram %.0f  scan + edges %.0f  compaction %.0f  total %.0f\n",
+              (int)nq, pass ? " capped" : "", v[SP_COUNT], v[SP_LOAD] / v[SP_COUNT], v[SP_HIST] / v[SP_COUNT], v[SP_SCAN] / v[SP_COUNT],
+              v[SP_COMPACT] / v[SP_COUNT], v[SP_TOTAL] / v[SP_COUNT]);
+  }
+#endif
   return RSX_OK;
 }
 

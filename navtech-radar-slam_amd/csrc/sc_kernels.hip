@@ -1060,7 +1060,7 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
 // ------------------------------------------------------------------------------------------
 
 #ifndef RW_OCC
-#define RW_OCC 3  // waves per SIMD the register budget is set for (168 VGPRs, 13 spilled; 4 = 128 VGPRs with 98 spilled: 0.42 against 0.24 ms)
+#define RW_OCC 3  // waves per SIMD the register budget is set for (168 VGPRs; the kernel takes 151, none spilled; 4 = 128 VGPRs had 98 spilled: 0.42 against 0.24 ms)
 #endif
 template <int SO>
 __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs a) {
@@ -1133,7 +1133,7 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
     }
   }
   auto kth_of = [&](double list) {
-    const double t = __shfl(list, a.k - 1);
+    const double t = wave::readlane(list, a.k - 1);  // (a.k is uniform: no LDS round trip between two evaluations)
     return t < tau_init ? t : tau_init;
   };
   double tau = kth_of(ld);
@@ -1142,9 +1142,11 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
   bool walked_tail = false;
 
   // score one entry exactly (ks < 0: the alignment is not known yet)
-  // region cycles for RSX_RESCORE_PROF (experiments builds): [4] headers + survivor + query load, [5] filtering + touching a
-  // round of survivors, [6] picking the next survivor, [7] phase B, [8] exact alignments, [9] waiting for the entry's
-  // registers, [10] the whole wave
+  // region cycles for RSX_RESCORE_PROF (experiments builds): [4] headers + survivor + query load, [5] filtering and ranking a
+  // round of survivors, requesting the first one and touching the others, [6] between two evaluations (top-k insertion, the
+  // next rank, requesting its registers), [7] phase B, [8] exact alignments, [9] waiting for the entry's registers -- with the
+  // timers on this wait drains ALL loads, so the touches a round's first evaluation would overlap are waited for here --
+  // [10] the whole wave
 #ifdef RSX_EXPERIMENTS
   const bool timing = a.stats != nullptr;
 #else
@@ -1187,8 +1189,8 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
     n_exact++;
     n_shifts += (unsigned)__builtin_popcount(tmask);
     const int64_t gidx = a.db.idx_base + slot * a.db.idx_stride;
-    if (gidx < n_elig && bd < kBig) {
-      topk_insert(ld, li, ls, lane, a.k, bd, (int)gidx, bk);
+    if (gidx < n_elig && bd < kBig) {  // (uniform: the whole wave is active, as the DPP shift of the insertion needs)
+      topk_insert_dpp(ld, li, ls, lane, a.k, bd, (int)gidx, bk);
       tau = kth_of(ld);
     }
   };
@@ -1231,49 +1233,73 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       n_windowed = (unsigned)hdr.n_prev;
     }
     // Rounds of 64 survivors, one per lane.  A memory round trip costs this kernel ~10 k cycles (random 4.8-KB rows of a 48 MB
-    // array), so the cache lines of ALL survivors of a round are requested at once, and only then are they evaluated -- in
-    // ascending order of their lower bound, the registers of the next one in flight while the current one is evaluated.
+    // array), so the cache lines of ALL survivors of a round are requested at once, and they are evaluated in ascending order
+    // of their lower bound, the registers of the next one in flight while the current one is evaluated.  Nothing between two
+    // evaluations goes through the LDS crossbar (ds_bpermute): ranks and v_readlane here, DPP in phase_b32 and topk_insert_dpp.
     for (int base = 0; base < n_list; base += 64) {
       WindowSurvivor e = first;
       if (base > 0 && base + lane < n_list) e = sv[1 + base + lane];
       const double t_now = tau < tau_ub ? tau : tau_ub;
       const bool mine = base + lane < n_list && e.pos >= i0 && e.pos < pw && !((double)e.lo > t_now);
-      float mylo = mine ? e.lo : INFINITY;
+      const float mylo = mine ? e.lo : INFINITY;
       const int32_t myslot = e.slot;
       const int myks = e.ks;  // (k* | shift mask << 8) or -1: alignment unknown
-      unsigned long long todo = __ballot(mine);
+      const unsigned long long todo = __ballot(mine);
       if (!todo) continue;  // (uniform)
-      {
-        Touch tch;
-        for (; todo; todo &= todo - 1) touch_entry(a.db, __shfl(myslot, __ffsll((long long)todo) - 1), lane, tch);
-        touch_wait(tch);  // ONE round trip for all of them (they overlap); from here on the entries come out of the L2
+      // The order of the evaluations is fixed here: ascending (lo, lane).  Every survivor counts the survivors in front of it,
+      // one v_readlane per survivor of the round (the set lanes of `todo`, a scalar loop); the ranks are a permutation of
+      // 0 .. n_mine - 1, and a lane without a survivor (lo = +inf) ranks behind all of them.  The i-th evaluation is then one
+      // compare, one ballot and three v_readlane -- no reduction over the wave and no LDS round trip per evaluation.
+      const int n_mine = __popcll(todo);
+      int myrank = 0;
+      for (unsigned long long m = todo; m; m &= m - 1) {
+        const int j = __ffsll((long long)m) - 1;
+        const float x = wave::readlane(mylo, j);
+        myrank += (x < mylo || (x == mylo && j < lane)) ? 1 : 0;
       }
-      lap(1);  // [5]
-      auto pick = [&](int32_t &slot, int &ks) -> float {  // the smallest lower bound left in this round
-        const float wm = wave::min_f32(mylo);
-        if (wm == INFINITY) return wm;
-        const int src = __ffsll((long long)__ballot(mylo == wm)) - 1;
-        slot = __shfl(myslot, src);
-        ks = __shfl(myks, src);
-        if (lane == src) mylo = INFINITY;
-        return wm;
+      auto ranked = [&](int i, int32_t &slot, int &ks) -> float {  // the survivor with rank i of this round (+inf: none left)
+        if (i >= n_mine) return INFINITY;
+        const unsigned long long at = __ballot(mine && myrank == i);
+        if (!at) return INFINITY;  // (never: sc_window_kernel writes no NaN lo, so (lo, lane) is a total order)
+        const int src = __ffsll((long long)at) - 1;
+        slot = wave::readlane(myslot, src);
+        ks = wave::readlane(myks, src);
+        return wave::readlane(mylo, src);
       };
       EntryRegs cur, nxt;
       int32_t cur_slot = 0, nxt_slot = 0;
       int cur_ks = -1, nxt_ks = -1;
-      float cur_lo = pick(cur_slot, cur_ks);
-      if (cur_lo < INFINITY) load_entry(a.db, cur_slot, lane, cur);
+      int rank_next = 0;
+      float cur_lo = ranked(rank_next++, cur_slot, cur_ks);
+      Touch tch;
+      // The first survivor's registers are requested AHEAD of the round's touches and waited for alone (VMEM returns in order):
+      // it is evaluated while the round trip of the touches runs.  It is always evaluated -- `mine` holds !(lo > t_now), and tau
+      // has not moved since.  The touch registers stay reserved until touch_wait behind that evaluation.
+      bool touching = cur_lo < INFINITY;
+      if (touching) {
+        EntryAsync ea;
+        load_entry_async(a.db, cur_slot, lane, ea);
+        const unsigned long long rest = todo & ~__ballot(mine && myrank == 0);
+        for (unsigned long long m = rest; m; m &= m - 1) touch_entry(a.db, wave::readlane(myslot, __ffsll((long long)m) - 1), lane, tch);
+        entry_wait(ea, __popcll(rest), cur);
+      }
+      lap(1);  // [5]
       while (cur_lo < INFINITY) {
         const double t_eff = tau < tau_ub ? tau : tau_ub;
         if ((double)cur_lo > t_eff) break;  // exact >= lower bound > an upper bound of the k-th best; the rest is larger still
-        const float nxt_lo = pick(nxt_slot, nxt_ks);
+        const float nxt_lo = ranked(rank_next++, nxt_slot, nxt_ks);
         if (nxt_lo < INFINITY && !((double)nxt_lo > t_eff)) load_entry(a.db, nxt_slot, lane, nxt);
         eval(cur_slot, cur_ks, cur);
+        if (touching) {  // (uniform) the touches of this round and the next survivor's registers have landed
+          touch_wait(tch);
+          touching = false;
+        }
         cur_lo = nxt_lo;
         cur_slot = nxt_slot;
         cur_ks = nxt_ks;
         cur = nxt;
       }
+      if (touching) touch_wait(tch);  // (never: the first survivor of a round is evaluated)
     }
     pos_next = pw > i0 ? pw : i0;
   }
