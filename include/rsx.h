@@ -1064,6 +1064,100 @@ int rsx_coral_quality_batch_device(rsx_coral *h, const float *d_a, const int64_t
                                    int32_t point_stride, int32_t n_jobs, const double *d_transforms, const rsx_coral_params *params,
                                    rsx_coral_result *d_results, rsx_coral_point *d_points, void *stream);
 
+/* ============================== phase-correlation registration ========================
+ * Dense, correspondence-free registration of two polar scans (Fourier-Mellin at scale 1; Checchin et al., "Radar scan matching
+ * SLAM using the Fourier-Mellin transform"; Park et al., "PhaRaO"): the one estimator here that reads the power image itself, so
+ * it needs no detector, no matches and no start value.  None of this is in the reference checkout: the rules below are restated
+ * in tests/phasecorr_np.py, which is the arithmetic contract -- parity unpinned.
+ * Frames: azimuth 0 is +x (forward), a return at azimuth phi and range rho sits at (rho cos phi, rho sin phi); image column j is
+ * x = (j - N/2) resolution, image row i is y = (i - N/2) resolution.  The result of a pair (src, dst) is the transform taking src
+ * into dst's frame, p_dst = R(theta) p_src + (x, y) -- the convention of rsx_cfear_result.  The azimuth rows are taken as EVENLY
+ * SPACED, row a at 2 pi a / rows; an uneven encoder grid is out of scope.
+ *   1. tables, made by the host in fp64 and rounded once to fp32, one set per handle: the resampling map (for every pixel of the
+ *      N x N grid the range-bin coordinate rho / range_resolution - 0.5 and the azimuth-row coordinate; a pixel with
+ *      rho > (N/2 - 1) resolution, or a range coordinate below min_range_bins or above cols - 1, is marked and reads 0), the Hann
+ *      window 0.5 - 0.5 cos(2 pi k / N), the table of cos and sin of 2 pi k / N (mirror-symmetric bit for bit), the N directions
+ *      of the polar resampling and cos(pi xi) of the high-pass
+ *   2. the windowed Cartesian image at rotation psi: azimuth coordinate = map + psi / azimuth step, wrapped to [0, rows); a
+ *      bilinear blend of four u8 samples; times hann[i], times hann[j].  fp32 in the operation order tests/phasecorr_np.py states:
+ *      BIT-IDENTICAL to the restatement
+ *   3. per scan, at psi = 0: the 2-D FFT F; its magnitude, fftshifted, times (1 - X)(2 - X) with X = cos(pi xi) cos(pi eta);
+ *      resampled bilinearly at N angles over [0, pi) x radii 4 .. N/2 - 1; a 1-D FFT along the angle for every radius.  Both
+ *      spectra stay in the handle's slot of the scan: every image of a batch is transformed once, whatever number of pairs reads it
+ *   4. rotation of a pair: C = A_dst conj(A_src), C / (|C| + 1e-9 max|C|), summed over the radii in ascending order -- radius r
+ *      contributes its angular frequencies |f| <= r only (above, the resampled ring holds the kinks of the interpolant, which belong
+ *      to the grid and vote for a rotation of 0) -- inverse 1-D FFT, divided by the sum of the terms' magnitudes (each about 1),
+ *      so the curve is 1 at a perfect match whatever the 1e-9 removes; the peak (ties: the lowest index) and a three-point parabola
+ *      give theta0 in [-pi/2, pi/2), known modulo pi
+ *   5. translation, for theta0 and (resolve_half_turn) theta0 + pi: the image of src at psi = -theta, its 2-D FFT G,
+ *      C = F_dst conj(G), C / (|C| + 1e-9 max|C|), inverse 2-D FFT over the sum of the terms' magnitudes (1 at a perfect match,
+ *      as above); the peak (ties: the lowest row-major index), a three-point
+ *      parabola per axis; the candidate with the higher peak wins (a tie: theta0).  peak_ratio = the largest value outside the
+ *      peak's 3 x 3 neighbourhood (wrapped) over the peak
+ * The three values under each parabola are sums of the inverse transform taken directly, in fp64 over the fp32 cross-power in
+ * index order: with the mirror-symmetric table a pair of a scan with itself gives x = y = theta = 0 exactly.  All transforms are
+ * fp32 in a fixed order, every maximum breaks ties by index, no float atomics: a pair's result does not depend on its place in
+ * the batch or on the batch's size.  The angles stay in device memory between the steps: a batch is nine launches and no host
+ * round trip, whatever its size.
+ * Defaults N = 256 at 0.5 m per pixel, from a sweep through the restatement on synth.polar_sequence(3, 6), five consecutive pairs
+ * (largest translation and rotation error, largest peak_ratio, smallest peak and rot_peak):
+ *     N    m/pixel   error [m]  [rad]    peak_ratio  peak   rot_peak
+ *     64   2.0       19.2       3.04     0.87        0.07   0.12     (wrong peaks)
+ *     64   1.0       0.45       0.054    0.73        0.15   0.13
+ *     128  1.0       0.26       0.016    0.21        0.21   0.10
+ *     128  0.5       0.083      0.0093   0.14        0.29   0.13
+ *     256  0.5       0.086      0.0016   0.062       0.43   0.21     (default)
+ *     256  0.25      0.030      0.0030   0.22        0.20   0.16
+ *     512  0.25      0.035      0.0008   0.087       0.24   0.18
+ * N = 64 does not register this drive; it registers pure rotations of one scene (by 0, 1, 100, 200, 333 rows of 400, at 2 m per
+ * pixel: within 0.81 angle bin; N = 256: within 0.36) and is the smallest size the transforms are built for. */
+
+typedef struct rsx_phasecorr rsx_phasecorr;
+
+#define RSX_PHASECORR_STATUS_ROTATION 1 /* |theta| > max_rotation: the result is reported as found */
+#define RSX_PHASECORR_STATUS_INDEX 2    /* (device entry only) a pair names an image outside the batch: nothing is computed, the
+                                           result is zero (the host entry refuses such a batch with RSX_ERR_BAD_ARG) */
+
+typedef struct {
+  int32_t n;                 /* image size N: 64, 128, 256 or 512 (256) */
+  int32_t min_range_bins;    /* range coordinates below it read 0, >= 0 (58: the keypoint extractors' min_range) */
+  double resolution;         /* metres per pixel, > 0 (0.5) */
+  double range_resolution;   /* metres per range bin, > 0 (0.0595) */
+  double max_rotation;       /* [rad] a pair with |theta| above it gets RSX_PHASECORR_STATUS_ROTATION; 0 = unlimited (0) */
+  int32_t resolve_half_turn; /* also try theta0 + pi (1) */
+  int32_t reserved;          /* 0 */
+} rsx_phasecorr_params;      /* 40 bytes */
+
+typedef struct {
+  double x, y, theta;   /* p_dst = R(theta) p_src + (x, y); metres, rad in (-pi, pi] */
+  double peak;          /* the translation surface at its peak (1 = identical images) */
+  double peak_ratio;    /* runner-up outside the peak's 3 x 3 neighbourhood / peak: small = unambiguous */
+  double rot_peak;      /* the rotation curve at its peak */
+  int32_t half_turn;    /* 1: theta0 + pi won */
+  int32_t status;       /* RSX_PHASECORR_STATUS_* */
+} rsx_phasecorr_result; /* 56 bytes */
+
+/* a violated rule of rsx_phasecorr_params gives RSX_ERR_BAD_ARG in every entry that takes the struct (NULL = the defaults): N not
+ * one of the four sizes, a resolution that is not positive and finite, a negative min_range_bins or max_rotation, and a disc that
+ * does not fit the scan: (N / 2) resolution > (cols - 1) range_resolution */
+int rsx_phasecorr_default_params(rsx_phasecorr_params *p);
+/* one handle per image shape (rows 1 .. 4096 azimuths x cols 2 .. 8192 range bins) and parameter set; the tables are made here */
+int rsx_phasecorr_create(int device, int32_t rows, int32_t cols, const rsx_phasecorr_params *params, rsx_phasecorr **out);
+int rsx_phasecorr_destroy(rsx_phasecorr *h);
+/* n_images host images image_stride_bytes apart, rows x row_stride bytes each, power samples at [col_offset, col_offset + cols) of
+ * a row; pairs: n_pairs x (src, dst) int32 image indices (checked: RSX_ERR_BAD_ARG outside [0, n_images)).  out_results[n_pairs];
+ * out_cart (may be NULL) receives the psi = 0 image of every scan, [n_images][N][N] floats.  Host buffers, synchronous. */
+int rsx_phasecorr_register_batch(rsx_phasecorr *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                                 int32_t col_offset, const int32_t *pairs, int32_t n_pairs, rsx_phasecorr_result *out_results, float *out_cart);
+/* the same on device buffers, asynchronous on `stream`, no host synchronisation; a pair with an index outside the batch gets
+ * RSX_PHASECORR_STATUS_INDEX.  No allocation beyond the handle's workspace, which grows to
+ *   n_images (12 N^2 - 32 N) + n_pairs (40 N^2 + 2048 + 4 N) + 64 bytes
+ * (per scan F and the angle spectrum; per pair, for both candidates, G, the column-transformed cross-power and the surface, the
+ * partial maxima and sums, the rotation curve) and is kept between calls: 0.75 MiB per scan and 2.5 MiB per pair at N = 256. */
+int rsx_phasecorr_register_batch_device(rsx_phasecorr *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                                        int32_t col_offset, const int32_t *d_pairs, int32_t n_pairs, rsx_phasecorr_result *d_results,
+                                        float *d_cart, void *stream);
+
 /* ============================== radar scan context ====================================
  * The "radar scan context" of the MulRan paper (Kim et al., ICRA 2020; reference README.md:28-29): the 20 x 60 polar grid
  * of the ScanContext descriptor filled with received power straight from the polar image -- dense where the descriptors of

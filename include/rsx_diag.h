@@ -57,6 +57,12 @@ int rsx_cen2018_debug_image(rsx_cen2018 *h, const uint8_t *img, int32_t row_stri
 int rsx_loop_verify_clouds(rsx_kfstore *h, int32_t loop_idx, int32_t curr_idx, const double *root_pose6, const rsx_loop_verify_params *params,
                            float *out_src, int64_t max_src, int64_t *n_src, float *out_tgt, int64_t max_tgt, int64_t *n_tgt);
 
+/* Parity helper of the phase-correlation registration (csrc/phasecorr.hip, tests/phasecorr_np.py): what pair `pair` of the handle's
+ * LAST rsx_phasecorr_register_batch(_device) call left in the workspace -- its rotation curve (N floats, 1 at a perfect match) and
+ * the translation surface of the candidate that won (N x N floats); either pointer may be null.  A result shows both only through
+ * their peaks.  Synchronous; RSX_ERR_BAD_ARG for a pair the last call did not have. */
+int rsx_phasecorr_correlation(rsx_phasecorr *h, int32_t pair, float *out_rot_curve, float *out_surface);
+
 /* Introspection of the candidate stage (host only, no device needed): the ring-key search tree the detector would build
  * over `n` keys of 20 floats -- nanoflann's tree (KDTreeVectorOfVectorsAdaptor.h:49-117, leaf size 10, Scancontext.cpp:284,356)
  * rebuilt node for node, because the order in which tied neighbours come back is the order of its leaves.  out_vind[n] =

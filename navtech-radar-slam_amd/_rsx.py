@@ -161,6 +161,16 @@ CORAL_RESULT_DTYPE = np.dtype([("quality", "<f8"), ("h_joint", "<f8"), ("h_separ
 CORAL_POINT_DTYPE = np.dtype([("det_separate", "<f8"), ("det_joint", "<f8"), ("m_separate", "<i4"), ("m_joint", "<i4")])
 
 
+class PhasecorrParams(C.Structure):
+    _fields_ = [("n", C.c_int32), ("min_range_bins", C.c_int32), ("resolution", C.c_double), ("range_resolution", C.c_double),
+                ("max_rotation", C.c_double), ("resolve_half_turn", C.c_int32), ("reserved", C.c_int32)]
+
+
+PHASECORR_STATUS_ROTATION, PHASECORR_STATUS_INDEX = 1, 2  # rsx_phasecorr_result.status
+PHASECORR_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("theta", "<f8"), ("peak", "<f8"), ("peak_ratio", "<f8"), ("rot_peak", "<f8"),
+                                   ("half_turn", "<i4"), ("status", "<i4")])
+
+
 class RadarScParams(C.Structure):
     _fields_ = [("max_radius", C.c_double), ("resolution", C.c_float), ("min_range", C.c_int32), ("power_floor", C.c_int32),
                 ("stat", C.c_int32)]
@@ -248,6 +258,8 @@ SYMBOLS = [
     "rsx_cfear_compensate_batch_device", "rsx_cfear_tracker_push_timed", "rsx_cfear_tracker_push_timed_device",
     "rsx_coral_default_params", "rsx_coral_create", "rsx_coral_destroy", "rsx_coral_quality_batch", "rsx_coral_quality_batch_device",
     "rsx_kfstore_alignment_quality",
+    "rsx_phasecorr_default_params", "rsx_phasecorr_create", "rsx_phasecorr_destroy", "rsx_phasecorr_register_batch",
+    "rsx_phasecorr_register_batch_device", "rsx_phasecorr_correlation",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
@@ -418,6 +430,12 @@ def lib():
         L.rsx_coral_quality_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.POINTER(CoralParams), vp, vp]
         L.rsx_coral_quality_batch_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(CoralParams), vp, vp, vp]
         L.rsx_kfstore_alignment_quality.argtypes = [vp, vp, i32, i32, vp, C.POINTER(CoralParams), C.POINTER(CoralResult)]
+        L.rsx_phasecorr_default_params.argtypes = [C.POINTER(PhasecorrParams)]
+        L.rsx_phasecorr_create.argtypes = [C.c_int, i32, i32, C.POINTER(PhasecorrParams), C.POINTER(vp)]
+        L.rsx_phasecorr_destroy.argtypes = [vp]
+        L.rsx_phasecorr_register_batch.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, vp, vp]
+        L.rsx_phasecorr_register_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, vp, vp, vp]
+        L.rsx_phasecorr_correlation.argtypes = [vp, i32, vp, vp]
         L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
         L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
         L.rsx_radarsc_destroy.argtypes = [vp]
