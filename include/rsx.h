@@ -1370,6 +1370,47 @@ int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params);
  * (rsx_cfear_tracker_push_timed).  out_xy stays the keypoints as measured: what compensation would mean for the published cloud
  * is out of scope.  rsx_odometry_set_compensation, which compensates MATCHES, still refuses while CFEAR is selected. */
 int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_params *params);
+/* Phase correlation (rsx_phasecorr above) in the window pipeline, in one of two modes.  Accepted only while the handle holds no scan;
+ * params = NULL goes back to the state before (ESTIMATE: the estimator it took the place of; FALLBACK: no fallback).  pc is judged by
+ * the rules of rsx_phasecorr_params against the handle's rows and cols (RSX_ERR_BAD_ARG), after pc.range_resolution has been
+ * overwritten with (double)radar_resolution of the handle; negative or non-finite gates and an unknown mode are refused too.  Refused
+ * while compensation is on and while the CFEAR tracker is on (both modes), and rsx_odometry_set_compensation and
+ * rsx_odometry_set_cfear_tracking refuse in return while either mode is on.  Without this call a handle allocates and launches
+ * nothing new.
+ *   RSX_ODOMETRY_PHASECORR_ESTIMATE  in place of the descriptors, the matcher and the estimator.  E(g) still runs the selected
+ *     keypoint extractor (n_keypoints and out_xy stay what they are) and then the spectra of the window's scans (launches 1 - 3 of
+ *     rsx_phasecorr) into the set's slots 1 .. n; the last scan's spectra are carried into slot 0 of the next set
+ *     (12 N^2 - 32 N bytes).  No Cartesian image, descriptors, matcher, cross check or max-clique selection run.  M(g) registers the
+ *     consecutive pairs (launches 4 - 9; src = this scan, dst = the previous one) and writes the records; n_matches = 0.
+ *     rsx_odometry_set_estimator and rsx_odometry_set_cfear leave this mode as they leave any other estimator, but
+ *     rsx_odometry_set_estimator refuses RSX_ESTIMATOR_PHASECORR itself: this setter carries the parameters.
+ *   RSX_ODOMETRY_PHASECORR_FALLBACK  beside the selected estimator (ORORA, RANSAC, MC-RANSAC or CFEAR pairs), whose whole chain runs
+ *     unchanged; E(g) additionally makes and carries the spectra.  Behind the estimator M(g) lists the pairs it FAILED on -- status
+ *     != 0, except CFEAR's 8 (max_iterations reached: the pose is carried) --, registers exactly those (the others take the
+ *     RSX_PHASECORR_STATUS_INDEX path, on which nothing is computed) and puts the phase-correlation record in place of each failed
+ *     pair's record; n_matches keeps the matcher's count.  Records of pairs that did not fail are byte for byte those of the same
+ *     handle without the fallback.
+ * A phase-correlation record in rsx_odometry_scan.reg (both modes): x, y, yaw = the rsx_phasecorr_result's x, y, theta, bit for bit
+ * (p_previous = R(yaw) p_this + (x, y)); iterations = -1 - half_turn (negative: "this record is phase correlation's");
+ * rot_inliers = (int32)rint(peak x 1e6), trans_inliers = (int32)rint(peak_ratio x 1e6); status = 0, or
+ * RSX_ODOMETRY_STATUS_PHASECORR | 1 (|theta| > pc.max_rotation) | 2 (a gate failed: peak_ratio > max_peak_ratio or peak < min_peak).
+ * The pose is reported as found in every case; a caller that composes poses skips status != 0 as for any other estimator.  The gates
+ * default to off: the levels of peak and peak_ratio depend on N, the resolution and the scene, and none has been measured on real
+ * data.  Device memory while on: per set (window + 1) x (12 N^2 - 32 N) bytes of spectra, once window x (40 N^2 + 2048 + 4 N) bytes
+ * of pair workspace (N = 256: 3 x 49 MiB + 161 MiB).  Results do not depend on how the sequence is cut into calls or windows. */
+#define RSX_ESTIMATOR_PHASECORR 4
+#define RSX_ODOMETRY_PHASECORR_ESTIMATE 0   /* in place of descriptors, matcher and estimator */
+#define RSX_ODOMETRY_PHASECORR_FALLBACK 1   /* beside the selected estimator, for the pairs it failed on */
+#define RSX_ODOMETRY_STATUS_PHASECORR 16    /* base of a phase-correlation record's non-zero status */
+typedef struct {
+  rsx_phasecorr_params pc;   /* range_resolution is overwritten with the handle's radar_resolution */
+  double max_peak_ratio;     /* gate: peak_ratio above it marks the record ambiguous; 0 = no gate (default) */
+  double min_peak;           /* gate: peak below it marks the record ambiguous; 0 = no gate (default) */
+  int32_t mode;              /* RSX_ODOMETRY_PHASECORR_* (ESTIMATE) */
+  int32_t reserved;          /* 0 */
+} rsx_odometry_phasecorr_params; /* 64 bytes */
+int rsx_odometry_default_phasecorr_params(rsx_odometry_phasecorr_params *p);   /* needs no device */
+int rsx_odometry_set_phasecorr(rsx_odometry *h, const rsx_odometry_phasecorr_params *params);  /* NULL: off */
 /* n_scans consecutive scans, host images image_stride_bytes apart (rows x row_stride bytes each); azimuths: rows floats
  * (rad, increasing) shared by all scans or n_scans x rows when azimuths_per_image != 0.  out [n_scans]; out_xy
  * (optional) [n_scans][max_xy][2]: the scan's keypoints in metres in the sensor frame (/orora/cloud_local).  Synchronous. */

@@ -166,7 +166,13 @@ class PhasecorrParams(C.Structure):
                 ("max_rotation", C.c_double), ("resolve_half_turn", C.c_int32), ("reserved", C.c_int32)]
 
 
+class OdometryPhasecorrParams(C.Structure):
+    _fields_ = [("pc", PhasecorrParams), ("max_peak_ratio", C.c_double), ("min_peak", C.c_double), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
 PHASECORR_STATUS_ROTATION, PHASECORR_STATUS_INDEX = 1, 2  # rsx_phasecorr_result.status
+ODOMETRY_PHASECORR_ESTIMATE, ODOMETRY_PHASECORR_FALLBACK = 0, 1  # rsx_odometry_phasecorr_params.mode
+ODOMETRY_STATUS_PHASECORR = 16  # base of a phase-correlation record's non-zero status (| 1: rotation, | 2: a gate)
 PHASECORR_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("theta", "<f8"), ("peak", "<f8"), ("peak_ratio", "<f8"), ("rot_peak", "<f8"),
                                    ("half_turn", "<i4"), ("status", "<i4")])
 
@@ -193,6 +199,7 @@ class RansacParams(C.Structure):
 RANSAC_MOTION_COMPENSATED = 1  # rsx_ransac_params.flags
 ESTIMATOR_ORORA, ESTIMATOR_RANSAC, ESTIMATOR_MCRANSAC = 0, 1, 2  # rsx_odometry_set_estimator
 ESTIMATOR_CFEAR = 3  # selected by rsx_odometry_set_cfear
+ESTIMATOR_PHASECORR = 4  # selected by rsx_odometry_set_phasecorr
 RANSAC_RESULT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("yaw", "<f8"), ("vx", "<f8"), ("vy", "<f8"), ("wz", "<f8"), ("inliers", "<i4"),
                                 ("hypotheses", "<i4"), ("gn_iterations", "<i4"), ("status", "<i4")])
 
@@ -260,6 +267,7 @@ SYMBOLS = [
     "rsx_kfstore_alignment_quality",
     "rsx_phasecorr_default_params", "rsx_phasecorr_create", "rsx_phasecorr_destroy", "rsx_phasecorr_register_batch",
     "rsx_phasecorr_register_batch_device", "rsx_phasecorr_correlation",
+    "rsx_odometry_default_phasecorr_params", "rsx_odometry_set_phasecorr",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
@@ -436,6 +444,8 @@ def lib():
         L.rsx_phasecorr_register_batch.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, vp, vp]
         L.rsx_phasecorr_register_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, vp, vp, vp]
         L.rsx_phasecorr_correlation.argtypes = [vp, i32, vp, vp]
+        L.rsx_odometry_default_phasecorr_params.argtypes = [C.POINTER(OdometryPhasecorrParams)]
+        L.rsx_odometry_set_phasecorr.argtypes = [vp, C.POINTER(OdometryPhasecorrParams)]
         L.rsx_radarsc_default_params.argtypes = [C.POINTER(RadarScParams)]
         L.rsx_radarsc_create.argtypes = [C.c_int, i32, i32, C.POINTER(RadarScParams), C.POINTER(vp)]
         L.rsx_radarsc_destroy.argtypes = [vp]

@@ -21,6 +21,12 @@
 //                                               (one launch per window); the Cartesian images, the descriptors, the matcher, the
 //                                               cross check and the selection do not run, and the consecutive pairs are
 //                                               registered point-to-line in one launch, src = this scan, dst = the previous one
+//     (rsx_odometry_set_phasecorr: csrc/phasecorr.hip)   after the extractor the spectra of every scan (launches 1 - 3 of a
+//                                               phase-correlation batch, into the set's slots; the last scan's are carried to the
+//                                               next set beside the keypoints).  ESTIMATE: nothing else runs, and the consecutive
+//                                               pairs are registered by launches 4 - 9, src = this scan, dst = the previous one.
+//                                               FALLBACK: the selected estimator's chain runs unchanged, then launches 4 - 9 over the
+//                                               pairs it failed on, whose records are replaced
 //     (rsx_odometry_set_compensation only)      the matches of every pair compensated with the pose the estimator just gave that
 //                                               pair (csrc/mocomp.hip), the estimator once more on them, and the keypoints of
 //                                               every scan compensated with its pair's second pose for out_xy
@@ -29,6 +35,7 @@
 // stays on the device as the "previous scan" of the next one.  Pose composition stays on the host (sequential, trivial).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -40,6 +47,7 @@
 #include "keypoints_host.h"
 #include "kstrongest.h"
 #include "mocomp.h"
+#include "phasecorr.h"
 #include "ransac.h"
 
 namespace {
@@ -248,6 +256,42 @@ __global__ __launch_bounds__(64) void odo_cfear_track_results(const rsx_cfear_tr
   }
 }
 
+// phase correlation (rsx_odometry_set_phasecorr): the pair list of a window for csrc/phasecorr.hip's pair stage.  Pair j is (src, dst) =
+// spectrum slots (first + j + 1, first + j): this scan, the previous one.  res == nullptr: every pair (ESTIMATE).  Otherwise only the
+// pairs the selected estimator FAILED on (FALLBACK): status != 0, except `carried` (CFEAR's 8: max_iterations reached, the pose is
+// carried); the others get (-1, -1), on which the pair stage computes nothing
+__global__ __launch_bounds__(64) void odo_pc_pairs(const rsx_orora_result *__restrict__ res, int n_pairs, int first, int carried,
+                                                   int32_t *__restrict__ pairs) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n_pairs) return;
+  const bool take = !res || (res[j].status != 0 && res[j].status != carried);
+  pairs[2 * j] = take ? first + j + 1 : -1;
+  pairs[2 * j + 1] = take ? first + j : -1;
+}
+
+// phase correlation's results in the records rsx_odometry_scan carries (include/rsx.h, rsx_odometry_set_phasecorr), for the pairs of
+// the list; the others' records stay.  pair_cnt (ESTIMATE; null in FALLBACK: the matcher's count stays): 0, there are no matches
+__global__ __launch_bounds__(64) void odo_pc_results(const rsx_phasecorr_result *__restrict__ in, const int32_t *__restrict__ pairs, int n_pairs,
+                                                     double max_peak_ratio, double min_peak, rsx_orora_result *__restrict__ out,
+                                                     int32_t *__restrict__ pair_cnt) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n_pairs) return;
+  if (pair_cnt) pair_cnt[j] = 0;
+  if (pairs[2 * j] < 0) return;
+  const rsx_phasecorr_result r = in[j];
+  rsx_orora_result o;
+  o.x = r.x;
+  o.y = r.y;
+  o.yaw = r.theta;
+  o.iterations = -1 - r.half_turn;
+  o.rot_inliers = __double2int_rn(r.peak * 1e6);
+  o.trans_inliers = __double2int_rn(r.peak_ratio * 1e6);
+  int st = r.status == RSX_PHASECORR_STATUS_ROTATION ? 1 : 0;
+  if ((max_peak_ratio > 0.0 && r.peak_ratio > max_peak_ratio) || (min_peak > 0.0 && r.peak < min_peak)) st |= 2;
+  o.status = st ? RSX_ODOMETRY_STATUS_PHASECORR | st : 0;
+  out[j] = o;
+}
+
 }  // namespace
 
 // Round 6: several windows in flight.  A window is two stages: EXTRACTION (cen2019, Cartesian images, descriptors: the wide
@@ -267,6 +311,7 @@ struct OdoSet {
   rsx::DevBuf az, targets, xy, counts, desc, valid;  // slot 0 = the previous scan, slots 1 .. MAX_WINDOW = the window (whichever extractor wrote them)
   rsx::DevBuf sp, sp_counts, pt_begin, pt_end;  // CFEAR only: surface points [slot][RSX_CFEAR_MAX_SURFACE_POINTS], their counts, the point ranges
   rsx::DevBuf sp_tau;  // CFEAR tracking with compensation only: the records' times, laid out like sp
+  rsx::DevBuf pc_F, pc_A;  // phase correlation only: the spectra [slot][N][N] and the angle spectra [slot][N / 2 - 4][N] (csrc/phasecorr.hip)
   rsx::PinnedBuf pin;  // pinned: counts[MAX_WINDOW + 1], pair_cnt[MAX_WINDOW], results[MAX_WINDOW], then the staged azimuth grids
 };
 
@@ -300,6 +345,15 @@ struct rsx_odometry {
   bool comp_on = false;  // rsx_odometry_set_compensation
   rsx_mocomp_params comp_prm{};
   rsx::DevBuf stage_acur, stage_aprev, a_cur, a_prev, src2, dst2, results2, xy_comp;  // allocated only with compensation
+  // rsx_odometry_set_phasecorr: ESTIMATE is estimator == RSX_ESTIMATOR_PHASECORR (pc_saved: the estimator it took the place of),
+  // FALLBACK is pc_fallback beside whichever estimator is selected
+  bool pc_fallback = false;
+  int pc_saved = RSX_ESTIMATOR_ORORA;
+  rsx_odometry_phasecorr_params pc_prm{};
+  rsx_phasecorr_params pc_tables_of{};  // what pc_tables was made for (n == 0: nothing yet)
+  rsx::DevBuf pc_tables, pc_work, pc_pairs, pc_res;  // one set of tables for both lanes and the matching stream; a window's pair workspace, list and results
+  struct { const uint8_t *d_imgs; int64_t image_stride; int32_t row_stride; } pc_imgs[N_SETS]{};  // where E(g) read window g's images: M(g) samples them again
+  bool pc_on() const { return pc_fallback || estimator == RSX_ESTIMATOR_PHASECORR; }
   OdoSet set[N_SETS];
   rsx::DevBuf imgs[N_SETS], fwd, bwd, stage_src, stage_dst, pair_cnt, src, dst, offsets, results;
   uint64_t windows = 0;  // windows enqueued since creation: window g works in set[g % N_SETS] on lane g & 1
@@ -352,7 +406,7 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
       RSX_TRY(h->track_n.reserve(4, s, false));
       RSX_TRY(h->track_prev.reserve(24, s, false));
     } else RSX_TRY(h->cfear_index.reserve(rsx::cfear::keyframe_index_bytes(MAX_WINDOW), s, false));
-  } else if (h->estimator != RSX_ESTIMATOR_ORORA) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
+  } else if (h->estimator == RSX_ESTIMATOR_RANSAC || h->estimator == RSX_ESTIMATOR_MCRANSAC) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
   if (h->estimator == RSX_ESTIMATOR_MCRANSAC) {
     RSX_TRY(h->stage_dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
     RSX_TRY(h->dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
@@ -361,6 +415,17 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
     for (rsx::DevBuf *b : {&h->stage_acur, &h->stage_aprev, &h->a_cur, &h->a_prev}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 4, s, false));
     for (rsx::DevBuf *b : {&h->src2, &h->dst2, &h->xy_comp}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 8, s, false));
     RSX_TRY(h->results2.reserve((size_t)MAX_WINDOW * sizeof(rsx_orora_result), s, false));
+  }
+  if (h->pc_on()) {  // (slot 0 of a set is only read while the handle holds a scan, and N cannot change then)
+    size_t per_F, per_A, per_pair;
+    rsx::phasecorr::workspace_bytes(h->pc_prm.pc.n, &per_F, &per_A, &per_pair);
+    for (OdoSet &q : h->set) {
+      RSX_TRY(q.pc_F.reserve(S * per_F, s, true));
+      RSX_TRY(q.pc_A.reserve(S * per_A, s, true));
+    }
+    RSX_TRY(h->pc_work.reserve((size_t)MAX_WINDOW * per_pair + 64, s, false));
+    RSX_TRY(h->pc_pairs.reserve((size_t)MAX_WINDOW * 8, s, false));
+    RSX_TRY(h->pc_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_phasecorr_result), s, false));
   }
   return RSX_OK;
 }
@@ -393,8 +458,16 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
     case Keypoints::kstrongest: RSX_TRY(keypoints(rsx_kstrongest_extract_batch_device, h->kstr[lane].get(), &h->kstr_prm)); break;
     case Keypoints::cfar: RSX_TRY(keypoints(rsx_cfar_extract_batch_device, h->cfar[lane].get(), &h->cfar_prm)); break;
   }
-  const bool cfear = h->estimator == RSX_ESTIMATOR_CFEAR;
+  const bool cfear = h->estimator == RSX_ESTIMATOR_CFEAR, pc_est = h->estimator == RSX_ESTIMATOR_PHASECORR;
   constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
+  size_t pc_F = 0, pc_A = 0;  // bytes of a slot
+  if (h->pc_on()) {  // the spectra of every scan into slots 1 .. n; M(g) samples the images once more
+    rsx::phasecorr::workspace_bytes(h->pc_prm.pc.n, &pc_F, &pc_A, nullptr);
+    h->pc_imgs[g % N_SETS] = {d_imgs, img_stride, row_stride};
+    RSX_TRY(rsx::phasecorr::launch_spectra(h->pc_prm.pc, h->rows, h->cols, h->pc_tables.p, {d_imgs, img_stride, row_stride, h->prm.col_offset}, n,
+                                           reinterpret_cast<float2 *>(q.pc_F.as<char>() + pc_F), reinterpret_cast<float2 *>(q.pc_A.as<char>() + pc_A),
+                                           nullptr, s));
+  }
   if (cfear) {  // the surface points of every scan; no Cartesian image, no descriptors
     hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 63) / 64), dim3(64), 0, s, d_counts + 1, n, (int64_t)K, 1, q.pt_begin.as<int64_t>(),
                        q.pt_end.as<int64_t>());
@@ -406,7 +479,7 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
     else
       RSX_TRY(rsx::cfear::launch_surface(q.xy.as<float>() + slot_xy, q.pt_begin.as<int64_t>(), q.pt_end.as<int64_t>(), n, h->cfear_prm,
                                          q.sp.as<rsx_cfear_surface_point>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
-  } else {
+  } else if (!pc_est) {  // (phase correlation as the estimator: no Cartesian image, no descriptors either)
     // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
     // how the sequence is cut into windows, and nothing about the grids is looked at on the host
     RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
@@ -417,11 +490,15 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   // the last scan of the window becomes the previous scan of the next one (slot 0 of the next set, which M(g - 2) read; the
   // next window's own extraction, on the other lane, writes slots 1 .. n of that set only)
   RSX_HIP(hipStreamWaitEvent(s, h->ev_m[(g + 1) % N_SETS], 0));
+  if (h->pc_on()) {
+    RSX_HIP(hipMemcpyAsync(nx.pc_F.p, q.pc_F.as<char>() + (size_t)n * pc_F, pc_F, hipMemcpyDeviceToDevice, s));
+    RSX_HIP(hipMemcpyAsync(nx.pc_A.p, q.pc_A.as<char>() + (size_t)n * pc_A, pc_A, hipMemcpyDeviceToDevice, s));
+  }
   if (cfear) {
     RSX_HIP(hipMemcpyAsync(nx.sp.p, q.sp.as<rsx_cfear_surface_point>() + (size_t)n * SP, SP * sizeof(rsx_cfear_surface_point),
                            hipMemcpyDeviceToDevice, s));
     RSX_HIP(hipMemcpyAsync(nx.sp_counts.p, q.sp_counts.as<int32_t>() + n, 4, hipMemcpyDeviceToDevice, s));
-  } else {
+  } else if (!pc_est) {  // (as the estimator it reports the keypoints and matches none: nothing of them is carried)
     RSX_HIP(hipMemcpyAsync(nx.xy.p, q.xy.as<float>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
     RSX_HIP(hipMemcpyAsync(nx.desc.p, q.desc.as<uint8_t>() + (size_t)n * K * 32, (size_t)K * 32, hipMemcpyDeviceToDevice, s));
     RSX_HIP(hipMemcpyAsync(nx.valid.p, q.valid.as<uint8_t>() + (size_t)n * K, (size_t)K, hipMemcpyDeviceToDevice, s));
@@ -445,7 +522,27 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
   int32_t *d_counts = q.counts.as<int32_t>();
   const int first = h->have_prev ? 0 : 1, n_pairs = n - first;
   *first_out = first;
-  if (h->estimator == RSX_ESTIMATOR_CFEAR && h->track_on) {  // one tracker launch over the window's scans (slots 1 .. n), its state in the handle
+  // phase correlation over the pairs of the list odo_pc_pairs writes: src = spectrum slot first + j + 1 = image first + j of window g
+  // (image = slot - 1), dst = slot first + j, slot 0 being the scan the window before carried here
+  auto phasecorr = [&](bool fallback) -> int {
+    int32_t *pairs = h->pc_pairs.as<int32_t>();
+    rsx_orora_result *rec = h->results.as<rsx_orora_result>();
+    const dim3 grid((unsigned)(n_pairs + 63) / 64), blk(64);
+    hipLaunchKernelGGL(odo_pc_pairs, grid, blk, 0, s, fallback ? rec : (const rsx_orora_result *)nullptr, n_pairs, first,
+                       h->estimator == RSX_ESTIMATOR_CFEAR ? 8 : 0, pairs);
+    RSX_HIP(hipGetLastError());
+    const auto &im = h->pc_imgs[g % N_SETS];
+    RSX_TRY(rsx::phasecorr::launch_pairs(h->pc_prm.pc, h->rows, h->cols, h->pc_tables.p, {im.d_imgs, im.image_stride, im.row_stride, h->prm.col_offset}, n,
+                                         -1, q.pc_F.as<float2>(), q.pc_A.as<float2>(), n + 1, pairs, n_pairs, h->pc_work.p,
+                                         h->pc_res.as<rsx_phasecorr_result>(), s));
+    hipLaunchKernelGGL(odo_pc_results, grid, blk, 0, s, h->pc_res.as<rsx_phasecorr_result>(), pairs, n_pairs, h->pc_prm.max_peak_ratio,
+                       h->pc_prm.min_peak, rec, fallback ? (int32_t *)nullptr : h->pair_cnt.as<int32_t>());
+    RSX_HIP(hipGetLastError());
+    return RSX_OK;
+  };
+  if (h->estimator == RSX_ESTIMATOR_PHASECORR) {
+    if (n_pairs > 0) RSX_TRY(phasecorr(false));
+  } else if (h->estimator == RSX_ESTIMATOR_CFEAR && h->track_on) {  // one tracker launch over the window's scans (slots 1 .. n), its state in the handle
     int64_t *b = h->sp_begin.as<int64_t>(), *e = h->sp_end.as<int64_t>();
     if (!h->have_prev) RSX_HIP(hipMemsetAsync(h->track_state.p, 0, rsx::cfear::track_state_bytes(), s));  // a new sequence
     hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 1 + 63) / 64), dim3(64), 0, s, q.sp_counts.as<int32_t>(), n + 1,
@@ -511,6 +608,7 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
       RSX_HIP(hipGetLastError());
     }
   }
+  if (h->pc_fallback && n_pairs > 0) RSX_TRY(phasecorr(true));  // (never with compensation or the tracker: the records are h->results)
   const rsx::DevBuf &res = h->comp_on ? h->results2 : h->results;
   if (h->comp_on && want_xy)  // /orora/cloud_local: scan i under the velocity of the pair (i - 1, i); the first scan of a sequence as measured
     RSX_TRY(rsx::mocomp::launch_slots(q.xy.as<float>() + (size_t)K * 2, q.targets.as<int32_t>() + (size_t)K * 2, d_counts + 1, K, n, first, res.p,
@@ -734,6 +832,8 @@ int rsx_odometry_set_cfar(rsx_odometry *h, const rsx_cfar_params *params) try {
 int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_params *params) try {
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
   if (estimator == RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "RSX_ESTIMATOR_CFEAR is selected with rsx_odometry_set_cfear, which carries its parameters");
+  if (estimator == RSX_ESTIMATOR_PHASECORR)
+    return fail(RSX_ERR_BAD_ARG, "RSX_ESTIMATOR_PHASECORR is selected with rsx_odometry_set_phasecorr, which carries its parameters");
   if (estimator != RSX_ESTIMATOR_ORORA && estimator != RSX_ESTIMATOR_RANSAC && estimator != RSX_ESTIMATOR_MCRANSAC)
     return fail(RSX_ERR_BAD_ARG, "unknown estimator %d", estimator);
   std::lock_guard<std::mutex> lk(h->mu);
@@ -771,6 +871,7 @@ int rsx_odometry_set_compensation(rsx_odometry *h, const rsx_mocomp_params *para
   }
   if (h->estimator == RSX_ESTIMATOR_MCRANSAC) return fail(RSX_ERR_BAD_ARG, "motion-compensated RANSAC has its own motion model");
   if (h->estimator == RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is selected: it has no matches to compensate (rsx_odometry_set_cfear(h, NULL) first)");
+  if (h->pc_on()) return fail(RSX_ERR_BAD_ARG, "phase correlation is on: it reads the scans as measured (rsx_odometry_set_phasecorr(h, NULL) first)");
   rsx_mocomp_params p = *params;
   p.rows = h->rows;
   RSX_TRY(rsx::mocomp::check_params(p));
@@ -804,10 +905,55 @@ int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_param
     return RSX_OK;
   }
   if (h->estimator != RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is not selected (rsx_odometry_set_cfear first)");
+  if (h->pc_fallback) return fail(RSX_ERR_BAD_ARG, "the phase-correlation fallback is on: it replaces pairs, the tracker has none (rsx_odometry_set_phasecorr(h, NULL) first)");
   RSX_TRY(rsx::cfear::check_track_params(*params));
   if (params->compensate && h->rows > 65536) return fail(RSX_ERR_BAD_ARG, "compensate = 1 takes images of at most 65536 rows");
   h->track_prm = *params;
   h->track_on = true;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_odometry_default_phasecorr_params(rsx_odometry_phasecorr_params *p) try {
+  if (!p) return fail(RSX_ERR_BAD_ARG, "null params");
+  std::memset(p, 0, sizeof(*p));
+  rsx_phasecorr_default_params(&p->pc);
+  p->mode = RSX_ODOMETRY_PHASECORR_ESTIMATE;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_odometry_set_phasecorr(rsx_odometry *h, const rsx_odometry_phasecorr_params *params) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
+  if (!params) {  // back to the state before: the estimator ESTIMATE took the place of, no fallback
+    if (h->estimator == RSX_ESTIMATOR_PHASECORR) h->estimator = h->pc_saved;
+    h->pc_fallback = false;
+    return RSX_OK;
+  }
+  rsx_odometry_phasecorr_params p = *params;
+  if (p.mode != RSX_ODOMETRY_PHASECORR_ESTIMATE && p.mode != RSX_ODOMETRY_PHASECORR_FALLBACK) return fail(RSX_ERR_BAD_ARG, "unknown mode %d", p.mode);
+  if (!(p.max_peak_ratio >= 0.0) || !std::isfinite(p.max_peak_ratio) || !(p.min_peak >= 0.0) || !std::isfinite(p.min_peak))
+    return fail(RSX_ERR_BAD_ARG, "max_peak_ratio and min_peak must not be negative");
+  p.pc.range_resolution = (double)h->prm.radar_resolution;
+  RSX_TRY(rsx::phasecorr::check_params(p.pc, h->rows, h->cols));
+  if (h->comp_on) return fail(RSX_ERR_BAD_ARG, "compensation is on: phase correlation reads the scans as measured (rsx_odometry_set_compensation(h, NULL) first)");
+  if (h->track_on) return fail(RSX_ERR_BAD_ARG, "the CFEAR tracker is on: phase correlation registers pairs (rsx_odometry_set_cfear_tracking(h, NULL) first)");
+  if (std::memcmp(&h->pc_tables_of, &p.pc, sizeof(p.pc)) != 0) {  // (nothing is in flight: every push is synchronous)
+    RSX_HIP(hipSetDevice(h->device));
+    h->pc_tables_of = rsx_phasecorr_params{};
+    RSX_TRY(rsx::phasecorr::make_tables(p.pc, h->rows, h->cols, h->pc_tables, h->match_stream));
+    h->pc_tables_of = p.pc;
+  }
+  const bool est = h->estimator == RSX_ESTIMATOR_PHASECORR;
+  if (p.mode == RSX_ODOMETRY_PHASECORR_ESTIMATE) {
+    if (!est) h->pc_saved = h->estimator;
+    h->estimator = RSX_ESTIMATOR_PHASECORR;
+    h->pc_fallback = false;
+  } else {
+    if (est) h->estimator = h->pc_saved;
+    h->pc_fallback = true;
+  }
+  h->pc_prm = p;
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -838,7 +984,10 @@ int rsx_odometry_push(rsx_odometry *h, const uint8_t *imgs, int32_t n_scans, int
     ~CopyDone() { (void)hipStreamSynchronize(cs); }
   } copy_done{h->copy_stream};
   return push_windows(h, n_scans, out, out_xy, max_xy, [&](int w, uint64_t g, int b0, int n) -> int {  // E(g) behind its upload
-    uint8_t *d_imgs = h->imgs[w % N_SETS].as<uint8_t>();  // (the buffer was read by the extraction of window w - 3: long done)
+    // (the buffer was read by the extraction of window w - 3: long done.  With phase correlation M(w - 3) read it as well: push_windows
+    // stages window w in the iteration of window w - 2, whose predecessor ended with finish_window's wait for M(w - 3), and a call
+    // returns with every M behind it.  Keep that order: an upload staged before that wait would overwrite images a pair stage reads)
+    uint8_t *d_imgs = h->imgs[w % N_SETS].as<uint8_t>();
     RSX_TRY(rsx::upload_images(d_imgs, imgs + (int64_t)b0 * image_stride_bytes, n, ibytes, image_stride_bytes, h->copy_stream));
     RSX_HIP(hipEventRecord(h->ev_up, h->copy_stream));
     RSX_HIP(hipStreamWaitEvent(h->lane_stream[g & 1], h->ev_up, 0));

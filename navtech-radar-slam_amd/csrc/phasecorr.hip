@@ -4,7 +4,10 @@
 // windowed Cartesian image is bit-identical to the restatement; the transforms are fp32 in a fixed order (no atomics, every maximum
 // breaks ties by index), so a pair's result does not depend on its place in a batch.
 //
-// One batch = nine launches, whatever its size, no host round trip (the angles stay in the pairs' records):
+// One batch = nine launches, whatever its size, no host round trip (the angles stay in the pairs' records), in two stages on
+// caller-given buffers (phasecorr.h: launch_spectra for the scans, launch_pairs for the pairs; they take the tables and the shape and
+// touch no handle).  The stand-alone entries run both in a row on the handle's workspace; the windowed odometry (csrc/odometry.hip) runs
+// the first in a window's extraction stage and the second in its matching stage, on slots of its own sets:
 //   scans   1. pc_rows_fwd    image at psi = 0 (resampled from the polar scan while the rows are filled) -> row transforms -> F
 //           2. pc_cols<0>     column transforms of F, in place
 //           3. pc_polar       |F| fftshifted, high-passed, resampled on N angles x N/2 - 4 radii -> transform along the angle -> A
@@ -53,11 +56,12 @@ struct Tables {
   const float *hp;     // [n] cos(pi (u - n / 2) / n)
 };
 
-// the scans of a call
+// the scans of a call: a pair's src is spectrum slot `src` and image `src + image_offset` (the stand-alone entries: 0; the odometry's
+// window: -1, slot 0 being the scan carried from the window before, whose image is not needed -- only src is re-sampled)
 struct Scans {
   const uint8_t *imgs;
   int64_t image_stride;
-  int n_images, row_stride, col_offset;
+  int n_images, n_slots, row_stride, col_offset, image_offset;
 };
 
 // where the pieces of the workspace lie (the sum is the size include/rsx.h states)
@@ -74,12 +78,6 @@ struct Layout {
     curve = rec + np * sizeof(PairRec);
     total = curve + np * (size_t)d.n * 4 + 64;
   }
-};
-
-struct Work {
-  float2 *F, *A, *G, *W;
-  float *surf, *curve;
-  PairRec *rec;
 };
 
 __device__ __forceinline__ bool pair_ok(const int32_t *__restrict__ pairs, int pair, int n_images, int &src, int &dst) {
@@ -103,8 +101,9 @@ __global__ __launch_bounds__(NT) void pc_rows_fwd(Dims d, Tables tb, Scans sc, c
   float s = 0.0f;
   if (pairs) {
     int src, dst;
-    if ((job & 1) >= n_cand || !pair_ok(pairs, job >> 1, sc.n_images, src, dst)) return;  // (uniform)
-    image = src;
+    if ((job & 1) >= n_cand || !pair_ok(pairs, job >> 1, sc.n_slots, src, dst)) return;  // (uniform)
+    image = src + sc.image_offset;
+    if (image < 0 || image >= sc.n_images) return;  // (uniform; no caller builds such a pair: a fence in front of the loads)
     s = azimuth_shift(-rec[job >> 1].theta[job & 1], d.rows);
   }
   load_table(E, tb.E, n, t);
@@ -420,7 +419,9 @@ __global__ __launch_bounds__(NT) void pc_peak(Dims d, Tables tb, const float2 *_
 
 // ---------------------------------------------------------------- host ----------------------------------------------------------------
 
-int check_params(const rsx_phasecorr_params &p, int rows, int cols) {
+}  // namespace
+
+int rsx::phasecorr::check_params(const rsx_phasecorr_params &p, int rows, int cols) {
   if (p.n != 64 && p.n != 128 && p.n != 256 && p.n != 512) return fail(RSX_ERR_BAD_ARG, "n %d is not 64, 128, 256 or 512", p.n);
   if (!(p.resolution > 0.0) || !std::isfinite(p.resolution)) return fail(RSX_ERR_BAD_ARG, "resolution must be positive");
   if (!(p.range_resolution > 0.0) || !std::isfinite(p.range_resolution)) return fail(RSX_ERR_BAD_ARG, "range_resolution must be positive");
@@ -432,17 +433,19 @@ int check_params(const rsx_phasecorr_params &p, int rows, int cols) {
   return RSX_OK;
 }
 
-Dims dims_of(const rsx_phasecorr *h) {
+namespace {
+
+Dims dims_of(const rsx_phasecorr_params &p, int rows, int cols) {
   Dims d;
-  d.n = h->p.n;
+  d.n = p.n;
   d.logn = 0;
   while ((1 << d.logn) < d.n) d.logn++;
   d.lines = 4096 / d.n < 16 ? 4096 / d.n : 16;
   d.llog = 0;
   while ((1 << d.llog) < d.lines) d.llog++;
   d.nb = d.n / d.lines;
-  d.rows = h->rows;
-  d.cols = h->cols;
+  d.rows = rows;
+  d.cols = cols;
   d.nr = d.n / 2 - R_MIN;
   return d;
 }
@@ -463,15 +466,15 @@ struct TableLayout {
   }
 };
 
-Tables tables_of(const rsx_phasecorr *h) {
-  const TableLayout L(h->p.n);
-  const unsigned char *b = h->tables.as<unsigned char>();
+Tables tables_of(const void *d_tables, int n) {
+  const TableLayout L(n);
+  const unsigned char *b = static_cast<const unsigned char *>(d_tables);
   return Tables{reinterpret_cast<const float2 *>(b + L.map), reinterpret_cast<const float2 *>(b + L.E), reinterpret_cast<const float2 *>(b + L.dirs),
                 reinterpret_cast<const float *>(b + L.hann), reinterpret_cast<const float *>(b + L.hp)};
 }
 
 // the tables of tests/phasecorr_np.py (Tables, cos_sin_table): fp64, the same expressions in the same order, one rounding to fp32
-void make_tables(const rsx_phasecorr_params &p, int rows, int cols, std::vector<unsigned char> &buf) {
+void fill_tables(const rsx_phasecorr_params &p, int rows, int cols, std::vector<unsigned char> &buf) {
   const int n = p.n, h = n / 2;
   const TableLayout L(n);
   buf.assign(L.total, 0);
@@ -521,37 +524,97 @@ int check_batch(const rsx_phasecorr *h, int32_t n_images, int64_t image_stride, 
   return RSX_OK;
 }
 
-// the nine launches behind both entries (the caller holds h->mu and has entered s); grows the workspace
+}  // namespace
+
+namespace rsx {
+namespace phasecorr {
+
+void workspace_bytes(int n, size_t *per_scan_F, size_t *per_scan_A, size_t *per_pair) {
+  const size_t n2 = (size_t)n * n;
+  if (per_scan_F) *per_scan_F = n2 * 8;
+  if (per_scan_A) *per_scan_A = (size_t)(n / 2 - R_MIN) * n * 8;
+  if (per_pair) *per_pair = 40 * n2 + sizeof(PairRec) + (size_t)n * 4;
+}
+
+int make_tables(const rsx_phasecorr_params &p, int rows, int cols, rsx::DevBuf &tables, hipStream_t s) {
+  std::vector<unsigned char> buf;
+  fill_tables(p, rows, cols, buf);
+  RSX_TRY(tables.reserve(buf.size(), s, false));
+  RSX_HIP(hipMemcpy(tables.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  const int lds = (int)MAX_LDS;  // (the attribute belongs to the kernel, not to the handle: the largest any handle launches with)
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_rows_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_cols<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_cols<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_cols<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_rows_inv), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_polar), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_rotation), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  return RSX_OK;
+}
+
+// launches 1 - 3
+int launch_spectra(const rsx_phasecorr_params &p, int rows, int cols, const void *d_tables, const Images &im, int32_t n_scans, float2 *d_F, float2 *d_A,
+                   float *d_cart, hipStream_t s) {
+  if (n_scans <= 0) return RSX_OK;
+  const Dims d = dims_of(p, rows, cols);
+  const Tables tb = tables_of(d_tables, d.n);
+  const Scans sc{im.d_imgs, im.image_stride, n_scans, n_scans, im.row_stride, im.col_offset, 0};
+  const size_t lds = lds_bytes(d);
+  const dim3 blk(NT), per_scan((unsigned)d.nb, (unsigned)n_scans);
+  hipLaunchKernelGGL(pc_rows_fwd, per_scan, blk, lds, s, d, tb, sc, (const int32_t *)nullptr, (const PairRec *)nullptr, 1, d_F, d_cart);
+  hipLaunchKernelGGL(pc_cols<0>, per_scan, blk, lds, s, d, tb, d_F, (const float2 *)nullptr, (const int32_t *)nullptr, n_scans, (PairRec *)nullptr, 1,
+                     (float2 *)nullptr);
+  hipLaunchKernelGGL(pc_polar, dim3((unsigned)((d.nr + d.lines - 1) / d.lines), (unsigned)n_scans), blk, lds, s, d, tb, d_F, d_A);
+  RSX_HIP(hipGetLastError());
+  return RSX_OK;
+}
+
+// launches 4 - 9
+int launch_pairs(const rsx_phasecorr_params &p, int rows, int cols, const void *d_tables, const Images &im, int32_t n_images, int32_t image_offset,
+                 const float2 *d_F, const float2 *d_A, int32_t n_slots, const int32_t *d_pairs, int32_t n_pairs, void *d_pair_work,
+                 rsx_phasecorr_result *d_results, hipStream_t s) {
+  if (n_pairs <= 0) return RSX_OK;
+  const Dims d = dims_of(p, rows, cols);
+  const Layout L(d, 0, n_pairs);  // (no scans: the offsets of the pairs' pieces from the first of them)
+  unsigned char *b = static_cast<unsigned char *>(d_pair_work);
+  float2 *G = reinterpret_cast<float2 *>(b + L.G), *W = reinterpret_cast<float2 *>(b + L.W);
+  float *surf = reinterpret_cast<float *>(b + L.surf), *curve = reinterpret_cast<float *>(b + L.curve);
+  PairRec *rec = reinterpret_cast<PairRec *>(b + L.rec);
+  const Tables tb = tables_of(d_tables, d.n);
+  const Scans sc{im.d_imgs, im.image_stride, n_images, n_slots, im.row_stride, im.col_offset, image_offset};
+  const size_t lds = lds_bytes(d);
+  const int n_cand = p.resolve_half_turn ? 2 : 1;
+  const dim3 blk(NT), per_cand((unsigned)d.nb, (unsigned)(2 * n_pairs));
+  hipLaunchKernelGGL(pc_rotation, dim3((unsigned)n_pairs), blk, lds, s, d, tb, d_A, d_pairs, n_slots, rec, curve);
+  hipLaunchKernelGGL(pc_rows_fwd, per_cand, blk, lds, s, d, tb, sc, d_pairs, rec, n_cand, G, (float *)nullptr);
+  hipLaunchKernelGGL(pc_cols<1>, per_cand, blk, lds, s, d, tb, G, d_F, d_pairs, n_slots, rec, n_cand, (float2 *)nullptr);
+  hipLaunchKernelGGL(pc_cols<2>, per_cand, blk, lds, s, d, tb, G, d_F, d_pairs, n_slots, rec, n_cand, W);
+  hipLaunchKernelGGL(pc_rows_inv, per_cand, blk, lds, s, d, tb, W, d_pairs, n_slots, n_cand, rec, surf);
+  hipLaunchKernelGGL(pc_peak, dim3((unsigned)n_pairs), blk, (size_t)d.n * sizeof(float2), s, d, tb, d_F, G, surf, d_pairs, n_slots, n_cand, p.resolution,
+                     p.max_rotation, rec, d_results);
+  RSX_HIP(hipGetLastError());
+  return RSX_OK;
+}
+
+}  // namespace phasecorr
+}  // namespace rsx
+
+namespace {
+
+// both stand-alone entries: the two stages in a row on the handle's own workspace, which grows here (the caller holds h->mu and has
+// entered s)
 int run(rsx_phasecorr *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride, int32_t row_stride, int32_t col_offset, const int32_t *d_pairs,
         int32_t n_pairs, rsx_phasecorr_result *d_results, float *d_cart, hipStream_t s) {
-  const Dims d = dims_of(h);
+  const Dims d = dims_of(h->p, h->rows, h->cols);
   const Layout L(d, n_images, n_pairs);
   RSX_TRY(h->work.reserve(L.total, s, false));
   h->last_images = n_images;
   h->last_pairs = n_pairs;
   unsigned char *b = h->work.as<unsigned char>();
-  Work w{reinterpret_cast<float2 *>(b + L.F),  reinterpret_cast<float2 *>(b + L.A), reinterpret_cast<float2 *>(b + L.G), reinterpret_cast<float2 *>(b + L.W),
-         reinterpret_cast<float *>(b + L.surf), reinterpret_cast<float *>(b + L.curve), reinterpret_cast<PairRec *>(b + L.rec)};
-  const Tables tb = tables_of(h);
-  const Scans sc{d_imgs, image_stride, n_images, row_stride, col_offset};
-  const size_t lds = lds_bytes(d);
-  const int n_cand = h->p.resolve_half_turn ? 2 : 1;
-  const dim3 blk(NT), per_scan((unsigned)d.nb, (unsigned)n_images), per_cand((unsigned)d.nb, (unsigned)(2 * n_pairs));
-  hipLaunchKernelGGL(pc_rows_fwd, per_scan, blk, lds, s, d, tb, sc, (const int32_t *)nullptr, (const PairRec *)nullptr, 1, w.F, d_cart);
-  hipLaunchKernelGGL(pc_cols<0>, per_scan, blk, lds, s, d, tb, w.F, (const float2 *)nullptr, (const int32_t *)nullptr, n_images, (PairRec *)nullptr, 1,
-                     (float2 *)nullptr);
-  hipLaunchKernelGGL(pc_polar, dim3((unsigned)((d.nr + d.lines - 1) / d.lines), (unsigned)n_images), blk, lds, s, d, tb, w.F, w.A);
-  if (n_pairs > 0) {
-    hipLaunchKernelGGL(pc_rotation, dim3((unsigned)n_pairs), blk, lds, s, d, tb, w.A, d_pairs, n_images, w.rec, w.curve);
-    hipLaunchKernelGGL(pc_rows_fwd, per_cand, blk, lds, s, d, tb, sc, d_pairs, w.rec, n_cand, w.G, (float *)nullptr);
-    hipLaunchKernelGGL(pc_cols<1>, per_cand, blk, lds, s, d, tb, w.G, w.F, d_pairs, n_images, w.rec, n_cand, (float2 *)nullptr);
-    hipLaunchKernelGGL(pc_cols<2>, per_cand, blk, lds, s, d, tb, w.G, w.F, d_pairs, n_images, w.rec, n_cand, w.W);
-    hipLaunchKernelGGL(pc_rows_inv, per_cand, blk, lds, s, d, tb, w.W, d_pairs, n_images, n_cand, w.rec, w.surf);
-    hipLaunchKernelGGL(pc_peak, dim3((unsigned)n_pairs), blk, (size_t)d.n * sizeof(float2), s, d, tb, w.F, w.G, w.surf, d_pairs, n_images, n_cand,
-                       h->p.resolution, h->p.max_rotation, w.rec, d_results);
-  }
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
+  float2 *F = reinterpret_cast<float2 *>(b + L.F), *A = reinterpret_cast<float2 *>(b + L.A);
+  const Images im{d_imgs, image_stride, row_stride, col_offset};
+  RSX_TRY(launch_spectra(h->p, h->rows, h->cols, h->tables.p, im, n_images, F, A, d_cart, s));
+  return launch_pairs(h->p, h->rows, h->cols, h->tables.p, im, n_images, 0, F, A, n_images, d_pairs, n_pairs, b + L.G, d_results, s);
 }
 
 }  // namespace
@@ -587,18 +650,7 @@ int rsx_phasecorr_create(int device, int32_t rows, int32_t cols, const rsx_phase
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = h->stream.create();
   if (e != hipSuccess) return fail(RSX_ERR_HIP, "create: %s", hipGetErrorString(e));
-  std::vector<unsigned char> buf;
-  make_tables(dp, rows, cols, buf);
-  RSX_TRY(h->tables.reserve(buf.size(), h->stream, false));
-  RSX_HIP(hipMemcpy(h->tables.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
-  const int lds = (int)MAX_LDS;  // (the attribute belongs to the kernel, not to the handle: the largest any handle launches with)
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_rows_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_cols<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_cols<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_cols<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_rows_inv), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_polar), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pc_rotation), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  RSX_TRY(make_tables(dp, rows, cols, h->tables, h->stream));
   *out = h.release();
   return RSX_OK;
 } RSX_CATCH_ALL
@@ -657,7 +709,7 @@ int rsx_phasecorr_correlation(rsx_phasecorr *h, int32_t pair, float *out_rot_cur
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   RSX_TRY(h->order.enter(s));
-  const Dims d = dims_of(h);
+  const Dims d = dims_of(h->p, h->rows, h->cols);
   const Layout L(d, h->last_images, h->last_pairs);
   const unsigned char *b = h->work.as<unsigned char>();
   PairRec rec;

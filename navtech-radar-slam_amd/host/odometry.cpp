@@ -43,6 +43,12 @@
 // (rsx_odometry_set_cfear_tracking; only with `--estimator cfear`).  `--cfear-compensate` (it switches the tracker on as well)
 // compensates the sensor's motion during a revolution inside the tracker: surface points with times, every scan registered
 // twice (rsx_cfear_track_params.compensate); the published cloud stays as measured.
+// `--estimator phasecorr` registers consecutive scans by phase correlation of the power images themselves (rsx_odometry_set_phasecorr,
+// mode ESTIMATE: no descriptors, matcher or estimator; the keypoint extractor still runs for n_keypoints and the cloud), and
+// `--fallback phasecorr` does so beside any other estimator for exactly the pairs that estimator failed on (mode FALLBACK); with
+// `--pc-n N` (64 | 128 | 256 | 512), `--pc-resolution M` (metres per pixel), `--pc-max-rotation DEG`, and the gates
+// `--pc-max-peak-ratio R`, `--pc-min-peak P` (off by default).  Windowed path only, not with --compensate or the CFEAR tracker.  A
+// phase-correlation record whose status is not 0 (16 | 1: rotation limit, | 2: a gate) is not composed, like any other failure.
 // `--compensate motion|doppler|both` (with `--doppler-beta`, `--scan-period`) corrects the keypoints for the sensor's motion
 // during the scan and / or the Doppler range shift: every pair is estimated, its matches compensated with that estimate and
 // estimated again, and the published cloud is the compensated one (upstream's deskewing / Doppler switches:
@@ -172,6 +178,10 @@ int main(int argc, char **argv) {
     rsx_cfear_track_params ctp;
     rsx_cfear_default_track_params(&ctp);
     bool cfear_track = false;
+    rsx_odometry_phasecorr_params pcp;
+    rsx_odometry_default_phasecorr_params(&pcp);
+    std::string fallback;
+    bool pc_flags = false;
     std::string compensate;
     rsx_mocomp_params mcp;
     rsx_mocomp_default_params(&mcp);
@@ -202,6 +212,12 @@ int main(int argc, char **argv) {
         if (v != "ca" && v != "go" && v != "so") die("--cfar-mode must be ca, go or so");
         cfa.mode = v == "ca" ? RSX_CFAR_CA : (v == "go" ? RSX_CFAR_GO : RSX_CFAR_SO);
       } else if (a == "--estimator" && i + 1 < argc) estimator = argv[++i];         // orora (default) | ransac | mcransac | cfear
+      else if (a == "--fallback" && i + 1 < argc) fallback = argv[++i];              // phasecorr (default: none)
+      else if (a == "--pc-n" && i + 1 < argc) { pcp.pc.n = std::atoi(argv[++i]); pc_flags = true; }  // phasecorr: image size N, 64 | 128 | 256 | 512 (256)
+      else if (a == "--pc-resolution" && i + 1 < argc) { pcp.pc.resolution = std::atof(argv[++i]); pc_flags = true; }  // phasecorr: metres per pixel (0.5)
+      else if (a == "--pc-max-rotation" && i + 1 < argc) { pcp.pc.max_rotation = std::atof(argv[++i]) * 3.14159265358979323846 / 180.0; pc_flags = true; }  // phasecorr: |yaw| above it marks the record [deg] (0: unlimited)
+      else if (a == "--pc-max-peak-ratio" && i + 1 < argc) { pcp.max_peak_ratio = std::atof(argv[++i]); pc_flags = true; }  // phasecorr: gate on runner-up / peak (0: off)
+      else if (a == "--pc-min-peak" && i + 1 < argc) { pcp.min_peak = std::atof(argv[++i]); pc_flags = true; }  // phasecorr: gate on the peak (0: off)
       else if (a == "--cfear-radius" && i + 1 < argc) cfp.radius = std::atof(argv[++i]);               // cfear: cell side and search radius [m] (3.5)
       else if (a == "--cfear-normal-angle" && i + 1 < argc) cfp.cos_max_normal_angle = std::cos(std::atof(argv[++i]) * 3.14159265358979323846 / 180.0);  // cfear: largest angle between matched normals [deg] (30)
       else if (a == "--cfear-huber" && i + 1 < argc) cfp.huber_delta = std::atof(argv[++i]);           // cfear: the loss's threshold, Huber's or Cauchy's [m; with p2d dimensionless] (0.1)
@@ -243,7 +259,7 @@ int main(int argc, char **argv) {
     (void)rate_hz;  // only the ROS publishers are paced
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest|cfar] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--cfar-train T] [--cfar-guard G] [--cfar-scale A] [--cfar-offset B] [--cfar-mode ca|go|so] [--window W] [--threads T] "
-          "[--estimator orora|ransac|mcransac|cfear] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-cost p2l|p2p|p2d] [--cfear-loss huber|cauchy|none] [--cfear-weights] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--cfear-compensate] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
+          "[--estimator orora|ransac|mcransac|cfear|phasecorr] [--fallback phasecorr] [--pc-n N] [--pc-resolution M] [--pc-max-rotation DEG] [--pc-max-peak-ratio R] [--pc-min-peak P] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-cost p2l|p2p|p2d] [--cfear-loss huber|cauchy|none] [--cfear-weights] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--cfear-compensate] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
           "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";
@@ -328,7 +344,8 @@ int main(int argc, char **argv) {
 #endif
     };
     auto compose = [&](const rsx_orora_result &r) {
-      if (r.status != 0 && !(estimator == "cfear" && r.status == 8)) return;  // (cfear's status 8, max_iterations reached, still carries a pose)
+      // (cfear's status 8, max_iterations reached, still carries a pose; a phase-correlation record -- iterations < 0 -- is 0 or 17 .. 19)
+      if (r.status != 0 && !(estimator == "cfear" && r.status == 8)) return;
       const double c = std::cos(pyaw), s = std::sin(pyaw);
       px += c * r.x - s * r.y;
       py += s * r.x + c * r.y;
@@ -340,7 +357,14 @@ int main(int argc, char **argv) {
     const bool use_c18 = keypoints == "cen2018", use_ks = keypoints == "kstrongest", use_cfar = keypoints == "cfar";
     cfa.k = ksp.k;  // --k and --min-separation are the one pair of flags of both
     cfa.min_separation = ksp.min_separation;
-    if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac" && estimator != "cfear") die("--estimator must be orora, ransac, mcransac or cfear");
+    if (estimator != "orora" && estimator != "ransac" && estimator != "mcransac" && estimator != "cfear" && estimator != "phasecorr")
+      die("--estimator must be orora, ransac, mcransac, cfear or phasecorr");
+    if (!fallback.empty() && fallback != "phasecorr") die("--fallback must be phasecorr");
+    const bool pc_est = estimator == "phasecorr", pc_fb = !fallback.empty();
+    if (pc_est && pc_fb) die("--estimator phasecorr and --fallback phasecorr: phase correlation is the estimator or the fallback, not both");
+    if (pc_flags && !pc_est && !pc_fb) die("--pc-n, --pc-resolution, --pc-max-rotation, --pc-max-peak-ratio and --pc-min-peak need --estimator phasecorr or --fallback phasecorr");
+    if (pc_fb && (matcher != "orb" || per_scan)) die("--fallback phasecorr runs on the windowed path only (not with --per-scan / --matcher nn)");
+    if (pc_fb && cfear_track) die("--fallback phasecorr replaces pairs: it does not go with the CFEAR tracker");
     if (estimator != "orora" && (matcher != "orb" || per_scan)) die("--estimator " + estimator + " runs on the windowed path only (not with --per-scan / --matcher nn)");
     if (cfear_track && estimator != "cfear") die("--cfear-keyframes, --cfear-keyframe-distance, --cfear-keyframe-rotation, --cfear-no-prediction and --cfear-compensate need --estimator cfear");
     if (!compensate.empty()) {
@@ -348,6 +372,7 @@ int main(int argc, char **argv) {
       if (matcher != "orb" || per_scan) die("--compensate runs on the windowed path only (not with --per-scan / --matcher nn)");
       if (estimator == "mcransac") die("--compensate does not go with --estimator mcransac, which has its own motion model");
       if (estimator == "cfear") die("--compensate does not go with --estimator cfear, which has no matches to compensate");
+      if (pc_est || pc_fb) die("--compensate does not go with phase correlation, which reads the scans as measured");
       mcp.flags = compensate == "motion" ? RSX_MOCOMP_DESKEW : compensate == "doppler" ? RSX_MOCOMP_DOPPLER : RSX_MOCOMP_DESKEW | RSX_MOCOMP_DOPPLER;
       mcp.dt_scan = rsp.dt_scan;
     }
@@ -378,9 +403,16 @@ int main(int argc, char **argv) {
       if (use_ks) check(rsx_odometry_set_kstrongest(odo, &ksp), "rsx_odometry_set_kstrongest");
       if (use_cfar) check(rsx_odometry_set_cfar(odo, &cfa), "rsx_odometry_set_cfar");
       if (estimator == "cfear") check(rsx_odometry_set_cfear(odo, &cfp), "rsx_odometry_set_cfear");
-      else if (estimator != "orora")
+      else if (pc_est) {
+        pcp.mode = RSX_ODOMETRY_PHASECORR_ESTIMATE;
+        check(rsx_odometry_set_phasecorr(odo, &pcp), "rsx_odometry_set_phasecorr");
+      } else if (estimator != "orora")
         check(rsx_odometry_set_estimator(odo, estimator == "ransac" ? RSX_ESTIMATOR_RANSAC : RSX_ESTIMATOR_MCRANSAC, &rsp), "rsx_odometry_set_estimator");
       if (cfear_track) check(rsx_odometry_set_cfear_tracking(odo, &ctp), "rsx_odometry_set_cfear_tracking");
+      if (pc_fb) {
+        pcp.mode = RSX_ODOMETRY_PHASECORR_FALLBACK;
+        check(rsx_odometry_set_phasecorr(odo, &pcp), "rsx_odometry_set_phasecorr");
+      }
       if (!compensate.empty()) check(rsx_odometry_set_compensation(odo, &mcp), "rsx_odometry_set_compensation");
       rsx_radarsc *rctx = nullptr;
       rsx_sc *rc_db = nullptr;

@@ -4,16 +4,45 @@ import ctypes as C
 
 import numpy as np
 
-from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params, CfarParams, CfearParams, CfearTrackParams, KStrongestParams, MocompParams,
-                   OdometryParams, RansacParams, check, lib)
+from ._rsx import (MOCOMP_DESKEW, MOCOMP_DOPPLER, ODOMETRY_PHASECORR_ESTIMATE, ODOMETRY_PHASECORR_FALLBACK, ORORA_PMC, ORORA_PMC_EXACT, ODOMETRY_SCAN_DTYPE, Cen2018Params,
+                   CfarParams, CfearParams, CfearTrackParams, KStrongestParams, MocompParams, OdometryParams, OdometryPhasecorrParams, PhasecorrParams, RansacParams, check,
+                   lib)
 
-ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_* ("cfear", RSX_ESTIMATOR_CFEAR, has a setter of its own)
+ESTIMATORS = {"orora": 0, "ransac": 1, "mcransac": 2}  # RSX_ESTIMATOR_* ("cfear" and "phasecorr", RSX_ESTIMATOR_CFEAR and _PHASECORR, have setters of their own)
 COMPENSATIONS = {"motion": MOCOMP_DESKEW, "doppler": MOCOMP_DOPPLER, "both": MOCOMP_DESKEW | MOCOMP_DOPPLER}  # rsx_mocomp_params.flags
 
 
 def default_params():
     p = OdometryParams()
     check(lib().rsx_odometry_default_params(C.byref(p)))
+    return p
+
+
+def default_phasecorr_params():
+    """rsx_phasecorr_default_params in .pc, both gates 0 (off), mode ESTIMATE; needs no device"""
+    p = OdometryPhasecorrParams()
+    check(lib().rsx_odometry_default_phasecorr_params(C.byref(p)))
+    return p
+
+
+def phasecorr_params(fields=None, mode=None):
+    """fields: None (the defaults), an OdometryPhasecorrParams (copied) or a dict: max_peak_ratio, min_peak and mode by name, any other
+    name a field of rsx_phasecorr_params (n, resolution, min_range_bins, max_rotation, resolve_half_turn).  mode, when given, wins."""
+    p = default_phasecorr_params()
+    if isinstance(fields, OdometryPhasecorrParams):
+        C.memmove(C.byref(p), C.byref(fields), C.sizeof(p))
+    elif fields is not None:
+        own = [name for name, _ in OdometryPhasecorrParams._fields_ if name != "pc"]
+        inner = [name for name, _ in PhasecorrParams._fields_]
+        for name, value in dict(fields).items():
+            if name in own:
+                setattr(p, name, value)
+            elif name in inner:
+                setattr(p.pc, name, value)
+            else:
+                raise TypeError("rsx_odometry_phasecorr_params has no field " + name)
+    if mode is not None:
+        p.mode = mode
     return p
 
 
@@ -31,15 +60,26 @@ class Odometry:
     exact_clique: the max-clique inlier selection returns a maximum clique (params.orora.flags |= ORORA_PMC_EXACT).
     compensate: None (default), "motion", "doppler" or "both": every pair is estimated, its matches compensated with that
     estimate, and estimated again (rsx_odometry_set_compensation; not with "mcransac"); beta, dt_scan: the Doppler factor and
-    the scan period of the model (None: the library's defaults)."""
+    the scan period of the model (None: the library's defaults).
+    estimator="phasecorr": phase correlation of the power images in place of descriptors, matcher and estimator
+    (rsx_odometry_set_phasecorr, mode ESTIMATE; the keypoint extractor still runs); fallback="phasecorr": beside any other estimator,
+    for exactly the pairs it failed on (mode FALLBACK); not both.  phasecorr: an OdometryPhasecorrParams, a dict of fields (see
+    phasecorr_params) or None for the defaults; not with compensate or the CFEAR tracker.  A record of phase correlation has
+    iterations = -1 - half_turn, rot_inliers = rint(peak * 1e6), trans_inliers = rint(peak_ratio * 1e6), status 0 or 16 | 1 | 2."""
 
     def __init__(self, rows=400, cols=3360, params=None, device=0, keypoints="cen2019", cen2018=None, estimator="orora", ransac=None,
                  exact_clique=False, compensate=None, beta=None, dt_scan=None, kstrongest=None, cfear=None, cfear_track=None,
-                 cfear_compensate=False, cfar=None):
+                 cfear_compensate=False, cfar=None, phasecorr=None, fallback=None):
         if keypoints not in ("cen2019", "cen2018", "kstrongest", "cfar"):
             raise ValueError("keypoints must be cen2019, cen2018, kstrongest or cfar")
-        if estimator not in ESTIMATORS and estimator != "cfear":
-            raise ValueError("estimator must be orora, ransac, mcransac or cfear")
+        if estimator not in ESTIMATORS and estimator not in ("cfear", "phasecorr"):
+            raise ValueError("estimator must be orora, ransac, mcransac, cfear or phasecorr")
+        if fallback not in (None, "phasecorr"):
+            raise ValueError("fallback must be None or phasecorr")
+        if estimator == "phasecorr" and fallback == "phasecorr":
+            raise ValueError("phasecorr is the estimator or the fallback, not both")
+        if phasecorr is not None and estimator != "phasecorr" and fallback is None:
+            raise ValueError("phasecorr parameters need estimator=\"phasecorr\" or fallback=\"phasecorr\"")
         if compensate is not None and compensate not in COMPENSATIONS:
             raise ValueError("compensate must be None, motion, doppler or both")
         self._L = lib()
@@ -72,8 +112,12 @@ class Odometry:
                 cfear_track = track
             if cfear_track is not None and cfear_track is not False:
                 self.set_cfear_tracking(None if cfear_track is True else cfear_track)
+        elif estimator == "phasecorr":
+            self.set_phasecorr(phasecorr_params(phasecorr, mode=ODOMETRY_PHASECORR_ESTIMATE))
         elif estimator != "orora":
             self.set_estimator(estimator, ransac)
+        if fallback == "phasecorr":
+            self.set_phasecorr(phasecorr_params(phasecorr, mode=ODOMETRY_PHASECORR_FALLBACK))
         if compensate is not None:
             self.set_compensation(compensate, beta=beta, dt_scan=dt_scan)
 
@@ -120,6 +164,14 @@ class Odometry:
         """Switch CFEAR to its keyframe tracker (track: CfearTrackParams or None for the defaults), or back to consecutive pairs with
         off=True.  Only while CFEAR is selected and the handle holds no scan."""
         self._set(self._L.rsx_odometry_set_cfear_tracking, self._L.rsx_cfear_default_track_params, CfearTrackParams, track, off)
+
+    def set_phasecorr(self, params=None, off=False):
+        """Switch phase correlation on (params: an OdometryPhasecorrParams whose mode picks ESTIMATE or FALLBACK, a dict of fields, or None
+        for the defaults: ESTIMATE at N = 256), or back to the state before with off=True.  Only while the handle holds no scan, and not
+        while compensation or the CFEAR tracker is on."""
+        if params is not None and not isinstance(params, OdometryPhasecorrParams):
+            params = phasecorr_params(params)
+        self._set(self._L.rsx_odometry_set_phasecorr, self._L.rsx_odometry_default_phasecorr_params, OdometryPhasecorrParams, params, off)
 
     def set_cen2018(self, cen2018=None, off=False):
         """Switch to cen2018 keypoints (cen2018: Cen2018Params or None for the defaults), or back to cen2019 with off=True.
