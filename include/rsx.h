@@ -1210,6 +1210,100 @@ int rsx_sc_add_polar_batch_device(rsx_sc *h, rsx_radarsc *rc, const uint8_t *d_i
 int rsx_sc_add_polar(rsx_sc *h, rsx_radarsc *rc, const uint8_t *img, int32_t row_stride, int32_t col_offset, const float *azimuths,
                      int32_t *out_index);
 
+/* ============================== radar grid map ========================================
+ * Polar scans at known poses accumulated into a fixed, georeferenced cell grid: the radar mosaic (mean received power per
+ * cell) and, for whatever plans on it, how often a cell returned a strong echo.  The one dense product of the library; also
+ * the one place where the poses can be judged by eye (a mosaic built at wrong poses is blurred: tests/test_gridmap_restatement.py
+ * measures it).  None of this is in the reference checkout: the rule below is restated in tests/gridmap_np.py, which is the
+ * arithmetic contract -- parity unpinned.
+ * State: three uint32 planes [height][width], row-major with row = y: `sum` of the samples a cell received, `cnt` the number of
+ * scans that observed it, `hit` the number of those whose sample was >= hit_threshold.  Integers only: the map does not depend
+ * on the order of the scans, on how a sequence is cut into batches or on the order of any reduction, and equals the restatement
+ * byte for byte.  (A plane wraps at 2^32: 16.8 million saturated observations of one cell.)
+ * Frames: azimuth 0 is +x, a return at azimuth phi and range rho sits at (rho cos phi, rho sin phi) in the sensor frame
+ * (rsx_phasecorr's convention); the azimuth rows are taken as EVENLY SPACED, row a at 2 pi a / rows (an uneven encoder grid is
+ * out of scope).  A scan's pose is six doubles r00, r01, tx, r10, r11, ty taking the sensor frame into the map frame,
+ * m = R p + t -- rsx_coral's transform, a matrix and not a yaw: the device evaluates no sine.  The matrix is taken as a rotation
+ * and not checked (the list of the tiles a scan can reach allows for one within 1e-7 of a rotation).
+ * Tables, made by the host at create in fp64 and rounded once to fp32: c[a] = cos(2 pi a / rows), s[a] = sin(2 pi a / rows),
+ * widened back to fp64 where used.
+ * Per (scan, cell (ix, iy)), fp64 on plain operations, nothing fused:
+ *   1. the cell centre mx = origin_x + (ix + 0.5) resolution, my = origin_y + (iy + 0.5) resolution
+ *   2. dx = mx - tx, dy = my - ty
+ *   3. px = r00 dx + r10 dy, py = r01 dx + r11 dy                      (the transposed matrix: map frame into sensor frame)
+ *   4. d2 = px px + py py
+ *   5. the range bin j with (j rr)^2 <= d2 < ((j + 1) rr)^2, j rr formed in fp64 and squared (bin j covers [j rr, (j + 1) rr):
+ *      rsx_radarsc's centre (j + 0.5) rr); the cell is NOT OBSERVED when j < min_range_bins, when j >= cols, or (max_range > 0)
+ *      when d2 > max_range^2
+ *   6. the azimuth row a that maximises c[a] px + s[a] py (the nearest beam); among equal rows the smallest a
+ *   7. the sample v = the maximum of the power bytes of row a at bins j - range_halfwidth .. j + range_halfwidth, bins below
+ *      min_range_bins or above cols - 1 left out
+ *   8. cnt += 1, sum += v, hit += (v >= hit_threshold)
+ * The kernel finds j and a from fp32 guesses and confirms them by the comparisons above: the guesses never show.  Cells outside
+ * the map do not exist; a scan whose footprint misses the map changes nothing.
+ * Render, on integers: RSX_GRIDMAP_MEAN gives uint8 (2 sum + cnt) / (2 cnt), 0 where cnt < min_observations; RSX_GRIDMAP_HITS
+ * gives int8 in the convention of nav_msgs/OccupancyGrid, -1 where cnt < min_observations, else (200 hit + cnt) / (2 cnt), which
+ * lies in 0 .. 100.  min_observations >= 1.
+ * One launch per call whatever the batch: one workgroup per 32 x 32 tile of the map lists the scans that can reach it (a circle
+ * against the box of its cell centres) and keeps its cells' accumulators in registers over the batch; no atomics, a tile's planes
+ * are read and written once per call.
+ * hit_threshold 120 is a value for the synthetic drive only (no real radar data has been seen).  Share of the cells seen by all
+ * six scans of synth.polar_sequence(11, 6) (1024 x 1024 cells of 0.5 m, the scans at their true poses) with at least half of
+ * their observations a hit, from tests/gridmap_np.py:
+ *     range_halfwidth   threshold 60    90      120     150
+ *     4                 0.58            0.36    0.27    0.21
+ *     0                 0.26            0.18    0.13    0.09        (493163 cells)
+ * The drive's world is dense, and a 1.8 degree beam is nine cells wide at 150 m. */
+
+typedef struct rsx_gridmap rsx_gridmap;
+
+#define RSX_GRIDMAP_MEAN 0
+#define RSX_GRIDMAP_HITS 1
+#define RSX_GRIDMAP_STATUS_TRANSFORM 1 /* (device entry only) the scan's transform holds a non-finite entry: the scan is skipped
+                                          (the host entry refuses such a batch with RSX_ERR_BAD_ARG) */
+
+typedef struct {
+  int32_t width, height;    /* cells; each 64 .. 8192 and a multiple of 64 (1024 x 1024) */
+  double resolution;        /* metres per cell, > 0 (0.5) */
+  double origin_x, origin_y; /* map coordinates of the outer corner of cell (0, 0) (-256, -256) */
+  double range_resolution;  /* metres per range bin, > 0 (0.0595) */
+  double max_range;         /* [m] cells farther than this are not observed; 0 = to the last bin (0) */
+  int32_t min_range_bins;   /* first range bin used, >= 0 (58: the keypoint extractors' min_range) */
+  int32_t range_halfwidth;  /* bins either side of j that the sample is the maximum of, 0 .. 8192 (4 = floor(resolution /
+                               (2 range_resolution)): a cell is as deep as 8.4 bins) */
+  int32_t hit_threshold;    /* sample level that counts as a hit, 0 .. 255 (120: see the table above) */
+  int32_t reserved;         /* 0 */
+} rsx_gridmap_params;       /* 64 bytes */
+
+/* a violated rule of rsx_gridmap_params gives RSX_ERR_BAD_ARG, judged before the device is looked at */
+int rsx_gridmap_default_params(rsx_gridmap_params *p);
+/* one handle per image shape (rows 1 .. 4096 azimuths x cols 2 .. 8192 range bins) and parameter set (NULL: the defaults);
+ * allocates and zeroes the planes (12 bytes per cell), makes the tables */
+int rsx_gridmap_create(int device, int32_t rows, int32_t cols, const rsx_gridmap_params *params, rsx_gridmap **out);
+int rsx_gridmap_destroy(rsx_gridmap *h);
+/* zeroes the planes; asynchronous on `stream` */
+int rsx_gridmap_clear(rsx_gridmap *h, void *stream);
+/* n_images host images (image arguments as for rsx_radarsc_build_batch) at transforms[6 i .. 6 i + 5] into the planes.  A
+ * non-finite transform entry refuses the whole batch (RSX_ERR_BAD_ARG, nothing added).  Host buffers, synchronous. */
+int rsx_gridmap_add_batch(rsx_gridmap *h, const uint8_t *imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                          int32_t col_offset, const double *transforms);
+/* device buffers, asynchronous on `stream`: one launch, no host synchronisation, no allocation.  A scan with a non-finite transform
+ * is skipped; d_status (may be NULL) receives per scan 0 or RSX_GRIDMAP_STATUS_TRANSFORM.  Only bytes inside each image's
+ * rows x row_stride bytes are read, whatever the alignment of d_imgs. */
+int rsx_gridmap_add_batch_device(rsx_gridmap *h, const uint8_t *d_imgs, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride,
+                                 int32_t col_offset, const double *d_transforms, int32_t *d_status, void *stream);
+/* the window [x, x + w) x [y, y + hgt) of the planes to host arrays [hgt][w]; any pointer may be NULL; a window that is empty or
+ * not inside the map is RSX_ERR_BAD_ARG.  Synchronous. */
+int rsx_gridmap_read(rsx_gridmap *h, int32_t x, int32_t y, int32_t w, int32_t hgt, uint32_t *out_sum, uint32_t *out_cnt, uint32_t *out_hit);
+/* the planes in device memory ([height][width] uint32, pitch_bytes = 4 width apart), for callers that stay on the GPU; any
+ * pointer may be NULL.  Valid until the handle is destroyed; the caller orders its reads behind the handle's calls. */
+int rsx_gridmap_planes_device(rsx_gridmap *h, uint32_t **d_sum, uint32_t **d_cnt, uint32_t **d_hit, int64_t *pitch_bytes);
+/* a window rendered to a host array [hgt][w] of bytes (uint8 for RSX_GRIDMAP_MEAN, int8 for RSX_GRIDMAP_HITS).  Synchronous. */
+int rsx_gridmap_render(rsx_gridmap *h, int32_t mode, int32_t min_observations, int32_t x, int32_t y, int32_t w, int32_t hgt, void *out);
+/* the same into a device buffer, asynchronous on `stream` */
+int rsx_gridmap_render_device(rsx_gridmap *h, int32_t mode, int32_t min_observations, int32_t x, int32_t y, int32_t w, int32_t hgt, void *d_out,
+                              void *stream);
+
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;
  * SURVEY 8f rank 3): polar -> Cartesian image, ORB-style binary descriptors at the keypoints, brute-force Hamming

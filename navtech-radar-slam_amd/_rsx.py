@@ -185,6 +185,16 @@ class RadarScParams(C.Structure):
 RADARSC_MEAN, RADARSC_MAX = 0, 1  # rsx_radarsc_params.stat
 
 
+class GridmapParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("resolution", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double),
+                ("range_resolution", C.c_double), ("max_range", C.c_double), ("min_range_bins", C.c_int32), ("range_halfwidth", C.c_int32),
+                ("hit_threshold", C.c_int32), ("reserved", C.c_int32)]
+
+
+GRIDMAP_MEAN, GRIDMAP_HITS = 0, 1  # render mode (RSX_GRIDMAP_*)
+GRIDMAP_STATUS_TRANSFORM = 1  # per-scan status word of rsx_gridmap_add_batch_device
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -270,6 +280,8 @@ SYMBOLS = [
     "rsx_odometry_default_phasecorr_params", "rsx_odometry_set_phasecorr",
     "rsx_radarsc_default_params", "rsx_radarsc_create", "rsx_radarsc_destroy", "rsx_radarsc_build_batch", "rsx_radarsc_build_batch_device",
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
+    "rsx_gridmap_default_params", "rsx_gridmap_create", "rsx_gridmap_destroy", "rsx_gridmap_clear", "rsx_gridmap_add_batch",
+    "rsx_gridmap_add_batch_device", "rsx_gridmap_read", "rsx_gridmap_planes_device", "rsx_gridmap_render", "rsx_gridmap_render_device",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
     "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
     "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
@@ -453,6 +465,16 @@ def lib():
         L.rsx_radarsc_build_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, vp, vp]
         L.rsx_sc_add_polar_batch_device.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, i32, vp]
         L.rsx_sc_add_polar.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(i32)]
+        L.rsx_gridmap_default_params.argtypes = [C.POINTER(GridmapParams)]
+        L.rsx_gridmap_create.argtypes = [C.c_int, i32, i32, C.POINTER(GridmapParams), C.POINTER(vp)]
+        L.rsx_gridmap_destroy.argtypes = [vp]
+        L.rsx_gridmap_clear.argtypes = [vp, vp]
+        L.rsx_gridmap_add_batch.argtypes = [vp, vp, i32, i64, i32, i32, vp]
+        L.rsx_gridmap_add_batch_device.argtypes = [vp, vp, i32, i64, i32, i32, vp, vp, vp]
+        L.rsx_gridmap_read.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+        L.rsx_gridmap_planes_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+        L.rsx_gridmap_render.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp]
+        L.rsx_gridmap_render_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
         L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]

@@ -56,6 +56,12 @@
 // `--radar-context FILE` (with `--rc-floor`, `--rc-stat mean|max`, `--rc-max-radius`; windowed path only) also builds the radar scan
 // context of every scan -- the 20 x 60 grid of received power, rsx_radarsc_build_batch on the window handed to
 // rsx_odometry_push -- into a ScanContext database and writes it to FILE (rsx_sc_save) at the end.
+// `--grid-map FILE.pgm` (with `--grid-hits FILE.pgm`, `--grid-size W H`, `--grid-resolution R`, `--grid-origin X Y`,
+// `--grid-hit-threshold Z`, `--grid-poses FILE`; windowed path only) also accumulates every scan into the radar grid map
+// (rsx_gridmap_add_batch on the window handed to rsx_odometry_push, at the poses composed here, or at the `x y yaw` lines of
+// --grid-poses, one per scan in file order: ground truth, or poses optimised elsewhere) and writes at the end the mean power per
+// cell as a binary PGM (row 0 = the lowest y), and with --grid-hits the hit ratio (255 unknown, else 254 - 2 percent).  Without
+// --grid-origin the map is centred on the first pose.
 //
 // Output: one line per frame on stdout / --out file:  stamp_ns x y yaw n_keypoints n_matches
 // With -DRSX_WITH_ROS (ROS 1 present) the same data is also published on /orora/odom and
@@ -188,6 +194,10 @@ int main(int argc, char **argv) {
     std::string rc_path, rc_stat = "mean";
     rsx_radarsc_params rcp;
     rsx_radarsc_default_params(&rcp);
+    std::string grid_path, grid_hits_path, grid_poses_path;
+    rsx_gridmap_params gmp;
+    rsx_gridmap_default_params(&gmp);
+    bool grid_flags = false, grid_origin = false;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       if (a == "--out" && i + 1 < argc) out_path = argv[++i];
@@ -245,6 +255,13 @@ int main(int argc, char **argv) {
       else if (a == "--rc-floor" && i + 1 < argc) rcp.power_floor = std::atoi(argv[++i]);  // radar context: power subtracted from every sample (0)
       else if (a == "--rc-stat" && i + 1 < argc) rc_stat = argv[++i];             // radar context: mean (default) | max
       else if (a == "--rc-max-radius" && i + 1 < argc) rcp.max_radius = std::atof(argv[++i]);  // radar context: outer ring edge [m] (80)
+      else if (a == "--grid-map" && i + 1 < argc) grid_path = argv[++i];           // write the radar mosaic (mean power per cell) to this PGM file
+      else if (a == "--grid-hits" && i + 1 < argc) { grid_hits_path = argv[++i]; grid_flags = true; }  // grid map: also the hit ratio, to this PGM file
+      else if (a == "--grid-size" && i + 2 < argc) { gmp.width = std::atoi(argv[++i]); gmp.height = std::atoi(argv[++i]); grid_flags = true; }  // grid map: cells, multiples of 64 (1024 1024)
+      else if (a == "--grid-resolution" && i + 1 < argc) { gmp.resolution = std::atof(argv[++i]); grid_flags = true; }  // grid map: metres per cell (0.5)
+      else if (a == "--grid-origin" && i + 2 < argc) { gmp.origin_x = std::atof(argv[++i]); gmp.origin_y = std::atof(argv[++i]); grid_flags = grid_origin = true; }  // grid map: corner of cell (0, 0) (centred on the first pose)
+      else if (a == "--grid-hit-threshold" && i + 1 < argc) { gmp.hit_threshold = std::atoi(argv[++i]); grid_flags = true; }  // grid map: sample level that counts as a hit (120)
+      else if (a == "--grid-poses" && i + 1 < argc) { grid_poses_path = argv[++i]; grid_flags = true; }  // grid map: `x y yaw` per scan instead of the poses composed here
       else if (a == "--no-pmc") use_pmc = false;                                   // skip the max-clique inlier selection before the solver
       else if (a == "--exact-clique") exact_clique = true;                        // RSX_ORORA_PMC_EXACT: the selection returns a maximum clique
       else if (a == "--per-scan") per_scan = true;                                // the round-2 loop: one scan per call, host vectors in between
@@ -260,7 +277,7 @@ int main(int argc, char **argv) {
     if (seq_dir.empty())
       die("usage: odometry <seq_dir> [--out poses.txt] [--max_frames N] [--matcher orb|nn] [--keypoints cen2019|cen2018|kstrongest|cfar] [--zq Z] [--sigma-gauss S] [--k K] [--z-min Z] [--min-separation S] [--cfar-train T] [--cfar-guard G] [--cfar-scale A] [--cfar-offset B] [--cfar-mode ca|go|so] [--window W] [--threads T] "
           "[--estimator orora|ransac|mcransac|cfear|phasecorr] [--fallback phasecorr] [--pc-n N] [--pc-resolution M] [--pc-max-rotation DEG] [--pc-max-peak-ratio R] [--pc-min-peak P] [--cfear-radius R] [--cfear-normal-angle DEG] [--cfear-huber D] [--cfear-cost p2l|p2p|p2d] [--cfear-loss huber|cauchy|none] [--cfear-weights] [--cfear-max-iterations N] [--cfear-keyframes S] [--cfear-keyframe-distance M] [--cfear-keyframe-rotation DEG] [--cfear-no-prediction] [--cfear-compensate] [--ransac-threshold M] [--ransac-iterations H] [--scan-period S] [--compensate motion|doppler|both] [--doppler-beta B] [--per-scan] [--no-pmc] "
-          "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--timing]");
+          "[--exact-clique] [--radar-context FILE] [--rc-floor P] [--rc-stat mean|max] [--rc-max-radius M] [--grid-map FILE.pgm] [--grid-hits FILE.pgm] [--grid-size W H] [--grid-resolution R] [--grid-origin X Y] [--grid-hit-threshold Z] [--grid-poses FILE] [--timing]");
     if (exact_clique && !use_pmc) die("--exact-clique makes the max-clique selection exact: it cannot go with --no-pmc");
     const std::string dir = seq_dir + "/polar_oxford_form";
     std::vector<std::string> files;
@@ -382,6 +399,20 @@ int main(int argc, char **argv) {
       rcp.stat = rc_stat == "max" ? RSX_RADARSC_MAX : RSX_RADARSC_MEAN;
       rcp.resolution = kResolution;
     }
+    std::vector<double> grid_poses;  // --grid-poses: x, y, yaw per scan
+    if (grid_path.empty()) {
+      if (grid_flags) die("--grid-hits, --grid-size, --grid-resolution, --grid-origin, --grid-hit-threshold and --grid-poses need --grid-map");
+    } else {
+      if (matcher != "orb" || per_scan) die("--grid-map runs on the windowed path only (not with --per-scan / --matcher nn)");
+      if (!grid_poses_path.empty()) {
+        FILE *f = std::fopen(grid_poses_path.c_str(), "r");
+        if (!f) die("cannot read " + grid_poses_path);
+        double v[3];
+        while (std::fscanf(f, "%lf %lf %lf", &v[0], &v[1], &v[2]) == 3) grid_poses.insert(grid_poses.end(), v, v + 3);
+        std::fclose(f);
+        if (grid_poses.size() < 3 * files.size()) die(grid_poses_path + ": fewer poses than scans");
+      }
+    }
 
     if (matcher == "orb" && !per_scan) {
       // ---------------- windows of scans through rsx_odometry_push ----------------
@@ -417,6 +448,8 @@ int main(int argc, char **argv) {
       rsx_radarsc *rctx = nullptr;
       rsx_sc *rc_db = nullptr;
       std::vector<float> rc_descs;
+      rsx_gridmap *grid = nullptr;  // (created with the first window: its default origin needs the first pose)
+      std::vector<double> grid_tf;
       if (!rc_path.empty()) {
         check(rsx_radarsc_create(device, rows, cols, &rcp, &rctx), "rsx_radarsc_create");
         rsx_sc_params sp;
@@ -564,10 +597,29 @@ int main(int argc, char **argv) {
           check(rsx_sc_add_descriptors_f32(rc_db, rc_descs.data(), wn.n), "rsx_sc_add_descriptors_f32");
         }
         push_s += std::chrono::duration<double>(clk::now() - tp).count();
+        grid_tf.clear();
         for (int i = 0; i < wn.n; i++, fi++) {
           compose(res[(size_t)i].reg);
           const int nk = std::min(res[(size_t)i].n_keypoints, op.max_keypoints);
           emit(fi, wn.stamp[(size_t)i], nk, (size_t)res[(size_t)i].n_matches, want_xy ? &xy[(size_t)i * max_xy * 2] : nullptr);
+          if (!grid_path.empty()) {  // the scan's pose as a matrix: sensor frame into map frame
+            const double *gp = grid_poses.empty() ? nullptr : &grid_poses[3 * fi];
+            const double gx = gp ? gp[0] : px, gy = gp ? gp[1] : py, gyaw = gp ? gp[2] : pyaw;
+            const double c = std::cos(gyaw), s = std::sin(gyaw);
+            grid_tf.insert(grid_tf.end(), {c, -s, gx, s, c, gy});
+          }
+        }
+        if (!grid_path.empty()) {  // the same window once more, at the poses just composed (another upload of its images)
+          const auto tg = clk::now();
+          if (!grid) {
+            if (!grid_origin) {
+              gmp.origin_x = grid_tf[2] - 0.5 * gmp.width * gmp.resolution;
+              gmp.origin_y = grid_tf[5] - 0.5 * gmp.height * gmp.resolution;
+            }
+            check(rsx_gridmap_create(device, rows, cols, &gmp, &grid), "rsx_gridmap_create");
+          }
+          check(rsx_gridmap_add_batch(grid, wn.img, wn.n, (int64_t)ibytes, w0, kMeta, grid_tf.data()), "rsx_gridmap_add_batch");
+          push_s += std::chrono::duration<double>(clk::now() - tg).count();
         }
 #ifdef RSX_WITH_ROS
         if (!ros::ok()) break;
@@ -581,9 +633,27 @@ int main(int argc, char **argv) {
                      files.size(), W, T, decode_cpu, 1e3 * decode_cpu / (double)files.size(), decode_wait, push_s, (double)files.size() / push_s,
                      all_s, (double)files.size() / all_s);
       if (rc_db) check(rsx_sc_save(rc_db, rc_path.c_str()), "rsx_sc_save");
+      if (grid) {
+        std::vector<uint8_t> px8((size_t)gmp.width * gmp.height);
+        auto write_pgm = [&](const std::string &path) {
+          FILE *f = std::fopen(path.c_str(), "wb");
+          if (!f) die("cannot write " + path);
+          std::fprintf(f, "P5\n%d %d\n255\n", gmp.width, gmp.height);
+          std::fwrite(px8.data(), 1, px8.size(), f);
+          std::fclose(f);
+        };
+        check(rsx_gridmap_render(grid, RSX_GRIDMAP_MEAN, 1, 0, 0, gmp.width, gmp.height, px8.data()), "rsx_gridmap_render");
+        write_pgm(grid_path);
+        if (!grid_hits_path.empty()) {
+          check(rsx_gridmap_render(grid, RSX_GRIDMAP_HITS, 1, 0, 0, gmp.width, gmp.height, px8.data()), "rsx_gridmap_render");
+          for (uint8_t &v : px8) v = v > 100 ? 255 : (uint8_t)(254 - 2 * v);  // (int8 -1 = unknown)
+          write_pgm(grid_hits_path);
+        }
+      }
       for (Win &wn : wins) rsx_host_free_pinned(wn.img);
       rsx_sc_destroy(rc_db);
       rsx_radarsc_destroy(rctx);
+      rsx_gridmap_destroy(grid);
       rsx_odometry_destroy(odo);
       if (out != stdout) std::fclose(out);
       if (rec) std::fclose(rec);
