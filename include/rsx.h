@@ -1304,6 +1304,98 @@ int rsx_gridmap_render(rsx_gridmap *h, int32_t mode, int32_t min_observations, i
 int rsx_gridmap_render_device(rsx_gridmap *h, int32_t mode, int32_t min_observations, int32_t x, int32_t y, int32_t w, int32_t hgt, void *d_out,
                               void *stream);
 
+/* ---- localising a point cloud in the map: correlative scan-to-map matching (Olson 2009; Cartographer's real-time correlative
+ * matcher), exhaustive over a window of rotations and whole-cell shifts around a prior pose.  None of this is in the reference
+ * checkout: the rule below is restated in tests/gridmatch_np.py, which is the arithmetic contract -- parity unpinned.  Integers
+ * from step 5 on: the scores equal the restatement byte for byte and do not depend on the order of any sum.
+ * The likelihood plane: uint8 [height][width], a frozen snapshot that matching reads (the planes may go on accumulating).  It is
+ * allocated at the first rsx_gridmap_likelihood_* call, (height + 256) x (width + 256) bytes: the plane in a zeroed frame of 128
+ * cells, which is why its pitch is not its width.  rsx_gridmap_likelihood_update fills it from the planes: with RSX_GRIDMAP_MEAN
+ * the byte that render gives, with RSX_GRIDMAP_HITS render's value with -1 replaced by 0 (0 .. 100).  rsx_gridmap_likelihood_set
+ * loads any image, a mosaic saved in an earlier session for one.
+ * A job: the points [offsets[i], offsets[i + 1]) of a float x, y array (rsx_coral's ragged convention: offsets[0] == 0, none
+ * below the one before it; at most RSX_GRIDMAP_MATCH_MAX_POINTS points) and a prior pose, six doubles r00 r01 tx r10 r11 ty taking
+ * the cloud's frame into the map frame.
+ * Candidates: the triples (k, v, u), |k| <= K = angle_steps, |v| <= V = y_cells, |u| <= U = x_cells; linear index
+ * ((k + K)(2V + 1) + (v + V))(2U + 1) + (u + U).
+ * Tables, made by the host per call in fp64 and rounded once to fp32: c[k] = cos(k angle_step), s[k] = sin(k angle_step), the
+ * angle formed as (double)k * angle_step; widened back to fp64 where used.  inv_res = 1.0 / resolution, on the host.
+ * Per (job, k, point (x, y)), fp64 on plain operations, nothing fused:
+ *   1. rx = c x - s y, ry = s x + c y
+ *   2. mx = r00 rx + r01 ry + tx, my = r10 rx + r11 ry + ty                      (left to right)
+ *   3. fx = (mx - origin_x) inv_res, fy = (my - origin_y) inv_res
+ *   4. the point is PLACED iff fx >= -64 && fx < width + 64 && fy >= -64 && fy < height + 64 (a non-finite point fails this and
+ *      is skipped; no candidate can reach a point that is not placed)
+ *   5. ix = (int)floor(fx), iy = (int)floor(fy)
+ * score(k, v, u) = the sum of L[iy + v][ix + u] over the placed points whose shifted cell is inside the map: a uint32, at most
+ * 8192 * 255.
+ * The winner is the highest score; among equal scores the smallest |k|, then the smallest u u + v v, then the smallest linear index.
+ * Result: transform = R_prior Rot(k) with the table values of the winner's k,
+ *     r00' = r00 c + r01 s, r01' = r01 c - r00 s, r10' = r10 c + r11 s, r11' = r11 c - r10 s,
+ *     tx' = tx + (double)u resolution, ty' = ty + (double)v resolution;
+ * score_prior = score(0, 0, 0); score_runner_up = the best score among the candidates farther than 1 from the winner in at least
+ * one of k, u, v (0 if there is none): peak_ratio's counterpart; n_points = the points placed at the winner's k, n_inside = those
+ * of them whose cell shifted by the winner's (u, v) is inside the map.
+ * Status: RSX_GRIDMAP_MATCH_STATUS_TRANSFORM, a prior with a non-finite entry: the job is skipped, its result is zero but for the
+ * status, its scores are zero.  _POINTS (device entry only; the host entry refuses the batch with RSX_ERR_BAD_ARG): more than the
+ * cap of points, treated like _TRANSFORM.  _EMPTY: the winning score is 0 (then k = u = v = 0): transform = the prior, unchanged.
+ * Two launches per call whatever the batch: one workgroup per (job, k) puts the cells of the rotated cloud into LDS and sums,
+ * every thread four neighbouring u of one v from one unaligned 32-bit read per point; one workgroup per job then picks the winner
+ * with an index-carrying key.  No atomics on device memory. */
+
+#define RSX_GRIDMAP_MATCH_MAX_POINTS 8192
+#define RSX_GRIDMAP_MATCH_STATUS_TRANSFORM 1
+#define RSX_GRIDMAP_MATCH_STATUS_POINTS 2
+#define RSX_GRIDMAP_MATCH_STATUS_EMPTY 4
+
+typedef struct {
+  double angle_step;    /* [rad] between two rotations; > 0 and finite when angle_steps > 0 (0.01) */
+  int32_t angle_steps;  /* K: rotations -K .. K, 0 .. 64 (8) */
+  int32_t x_cells;      /* U: shifts -U .. U cells along x, 0 .. 32 (8) */
+  int32_t y_cells;      /* V: shifts -V .. V cells along y, 0 .. 32 (8) */
+  int32_t reserved;     /* 0 */
+} rsx_gridmap_match_params; /* 24 bytes */
+
+typedef struct {
+  double transform[6];      /* r00 r01 tx r10 r11 ty of the winner */
+  int32_t k, u, v;          /* the winner */
+  uint32_t score, score_prior, score_runner_up;
+  int32_t n_points, n_inside;
+  int32_t status;           /* RSX_GRIDMAP_MATCH_STATUS_* */
+  int32_t reserved;         /* 0 */
+} rsx_gridmap_match_result; /* 88 bytes */
+
+/* a violated rule of rsx_gridmap_match_params gives RSX_ERR_BAD_ARG in every entry that takes the struct (NULL = the defaults),
+ * judged before the handle or the device is looked at */
+int rsx_gridmap_match_default_params(rsx_gridmap_match_params *p);
+/* the likelihood plane from the planes as they stand: mode and min_observations as for render.  Asynchronous on `stream`, one
+ * launch (the first rsx_gridmap_likelihood_* call of a handle also allocates the plane and zeroes its frame). */
+int rsx_gridmap_likelihood_update(rsx_gridmap *h, int32_t mode, int32_t min_observations, void *stream);
+/* the likelihood plane from a host image [height][width].  Synchronous. */
+int rsx_gridmap_likelihood_set(rsx_gridmap *h, const uint8_t *img);
+/* cell (0, 0) of the likelihood plane in device memory and the bytes from one row to the next (width + 256); allocates the plane
+ * when no call has yet.  A caller that writes the plane itself writes [height][width] bytes at that pitch, ordered against the
+ * handle's calls, and calls nothing else to make it count: handing out the pointer marks the plane as filled. */
+int rsx_gridmap_likelihood_device(rsx_gridmap *h, uint8_t **d_likelihood, int64_t *pitch_bytes);
+/* a window of the likelihood plane to a host array [hgt][w], as rsx_gridmap_read; RSX_ERR_BAD_ARG before any update or set.
+ * Synchronous. */
+int rsx_gridmap_likelihood_read(rsx_gridmap *h, int32_t x, int32_t y, int32_t w, int32_t hgt, uint8_t *out);
+/* n_jobs jobs against the likelihood plane.  Host buffers, synchronous.  out_scores (may be NULL): the whole volume, uint32
+ * [job][2K + 1][2V + 1][2U + 1].  The offsets are checked, a job above the cap refuses the batch; before any likelihood exists
+ * the call is RSX_ERR_BAD_ARG and touches nothing.  Staged in sub-batches of at most 64 MB of volume (a job's bytes do not
+ * depend on the cut). */
+int rsx_gridmap_match_batch(rsx_gridmap *h, const float *xy, const int64_t *offsets, int32_t n_jobs, const double *priors,
+                            const rsx_gridmap_match_params *params, rsx_gridmap_match_result *out_results, uint32_t *out_scores);
+/* device buffers, asynchronous on `stream`: two launches, no host synchronisation; point i of the array is d_xy[point_stride i]
+ * and d_xy[point_stride i + 1] (point_stride >= 2: a packed float4 cloud is read in place, whatever its alignment beyond 4
+ * bytes); the offsets are trusted; a job above the cap gets RSX_GRIDMAP_MATCH_STATUS_POINTS.  n_jobs (2K + 1) < 2^31.
+ * Workspace: with d_scores NULL the handle keeps the volume itself, a buffer that grows (to the next power of two) to
+ * n_jobs (2K + 1)(2V + 1)(2U + 1) * 4 bytes and is never given back before destroy -- 19652 bytes per job at the defaults, 2.2 MB
+ * per job at the largest window; with d_scores given nothing is allocated. */
+int rsx_gridmap_match_batch_device(rsx_gridmap *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride, int32_t n_jobs,
+                                   const double *d_priors, const rsx_gridmap_match_params *params, rsx_gridmap_match_result *d_results,
+                                   uint32_t *d_scores, void *stream);
+
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;
  * SURVEY 8f rank 3): polar -> Cartesian image, ORB-style binary descriptors at the keypoints, brute-force Hamming

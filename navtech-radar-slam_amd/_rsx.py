@@ -195,6 +195,22 @@ GRIDMAP_MEAN, GRIDMAP_HITS = 0, 1  # render mode (RSX_GRIDMAP_*)
 GRIDMAP_STATUS_TRANSFORM = 1  # per-scan status word of rsx_gridmap_add_batch_device
 
 
+class GridmapMatchParams(C.Structure):
+    _fields_ = [("angle_step", C.c_double), ("angle_steps", C.c_int32), ("x_cells", C.c_int32), ("y_cells", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GridmapMatchResult(C.Structure):
+    _fields_ = [("transform", C.c_double * 6), ("k", C.c_int32), ("u", C.c_int32), ("v", C.c_int32), ("score", C.c_uint32),
+                ("score_prior", C.c_uint32), ("score_runner_up", C.c_uint32), ("n_points", C.c_int32), ("n_inside", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+GRIDMAP_MATCH_MAX_POINTS = 8192  # RSX_GRIDMAP_MATCH_MAX_POINTS
+GRIDMAP_MATCH_STATUS_TRANSFORM, GRIDMAP_MATCH_STATUS_POINTS, GRIDMAP_MATCH_STATUS_EMPTY = 1, 2, 4
+GRIDMAP_MATCH_RESULT_DTYPE = np.dtype([("transform", "<f8", 6), ("k", "<i4"), ("u", "<i4"), ("v", "<i4"), ("score", "<u4"), ("score_prior", "<u4"),
+                                       ("score_runner_up", "<u4"), ("n_points", "<i4"), ("n_inside", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -282,6 +298,8 @@ SYMBOLS = [
     "rsx_sc_add_polar_batch_device", "rsx_sc_add_polar",
     "rsx_gridmap_default_params", "rsx_gridmap_create", "rsx_gridmap_destroy", "rsx_gridmap_clear", "rsx_gridmap_add_batch",
     "rsx_gridmap_add_batch_device", "rsx_gridmap_read", "rsx_gridmap_planes_device", "rsx_gridmap_render", "rsx_gridmap_render_device",
+    "rsx_gridmap_match_default_params", "rsx_gridmap_likelihood_update", "rsx_gridmap_likelihood_set", "rsx_gridmap_likelihood_device",
+    "rsx_gridmap_likelihood_read", "rsx_gridmap_match_batch", "rsx_gridmap_match_batch_device",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
     "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
     "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
@@ -475,6 +493,13 @@ def lib():
         L.rsx_gridmap_planes_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
         L.rsx_gridmap_render.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp]
         L.rsx_gridmap_render_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]
+        L.rsx_gridmap_match_default_params.argtypes = [C.POINTER(GridmapMatchParams)]
+        L.rsx_gridmap_likelihood_update.argtypes = [vp, i32, i32, vp]
+        L.rsx_gridmap_likelihood_set.argtypes = [vp, vp]
+        L.rsx_gridmap_likelihood_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+        L.rsx_gridmap_likelihood_read.argtypes = [vp, i32, i32, i32, i32, vp]
+        L.rsx_gridmap_match_batch.argtypes = [vp, vp, vp, i32, vp, C.POINTER(GridmapMatchParams), vp, vp]
+        L.rsx_gridmap_match_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(GridmapMatchParams), vp, vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
         L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]

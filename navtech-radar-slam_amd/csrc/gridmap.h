@@ -1,0 +1,48 @@
+// gridmap.h -- the handle of the radar grid map, shared by gridmap.hip (the planes: accumulate, read, render) and gridmatch.hip (the
+// likelihood plane and the correlative matching that reads it).
+#pragma once
+#include <cstdint>
+#include <mutex>
+
+#include "rsx_common.h"
+
+namespace rsx {
+
+struct GridmapGeometry {
+  double res, ox, oy, rr;
+  double e_hi;    // (cols rr)^2: d2 at or above it lies in bin `cols` or beyond
+  double max2;    // max_range^2 (+inf: none)
+  double reach2;  // tile test: no cell farther than this (squared, with margin) is observed
+  double hole2;   // tile test: no cell nearer than this (squared, with margin) is observed
+  float inv_rr, rows_per_rad;
+  int W, H, rows, cols, lo_bin, hw, thr;
+};
+
+// the likelihood plane sits in a zeroed frame of this many cells on every side, so that a shifted cell of a placed point (64 cells
+// outside the map at the most, shifted by 32 at the most, read four bytes at a time) is always a byte of the buffer: a cell outside
+// the map reads 0 and the matching kernel tests no bound
+constexpr int GRIDMAP_LIKE_MARGIN = 128;
+
+}  // namespace rsx
+
+struct rsx_gridmap {
+  int device = 0, rows = 0, cols = 0;
+  rsx_gridmap_params p{};
+  rsx::GridmapGeometry g{};
+  std::mutex mu;
+  rsx::Stream stream;
+  rsx::DevBuf planes;           // sum, cnt, hit: three [height][width] uint32 planes, one behind the other
+  rsx::DevBuf table;            // float2[rows]
+  rsx::DevBuf img, tf, out;     // staging of the host entries: images, transforms, a rendered window
+  rsx::StreamOrder order;
+  size_t plane_bytes() const { return (size_t)p.width * p.height * sizeof(unsigned); }
+  unsigned *plane(int k) const { return planes.as<unsigned>() + (size_t)k * p.width * p.height; }
+  // ---- gridmatch.hip: nothing below is allocated before the first rsx_gridmap_likelihood_* / rsx_gridmap_match_* call ----
+  rsx::DevBuf like;             // uint8 [height + 2 margin][width + 2 margin]: the likelihood plane in its zeroed frame
+  bool have_like = false;       // an update or a set has filled it
+  rsx::DevBuf volume;           // the score volumes of a call that asked for none (uint32, n_jobs x candidates)
+  rsx::DevBuf m_xy, m_off, m_tf, m_res;  // staging of rsx_gridmap_match_batch: points, offsets, priors, results
+  int64_t like_pitch() const { return (int64_t)p.width + 2 * rsx::GRIDMAP_LIKE_MARGIN; }
+  size_t like_bytes() const { return (size_t)like_pitch() * ((size_t)p.height + 2 * rsx::GRIDMAP_LIKE_MARGIN); }
+  uint8_t *like_origin() const { return like.as<uint8_t>() + (size_t)rsx::GRIDMAP_LIKE_MARGIN * like_pitch() + rsx::GRIDMAP_LIKE_MARGIN; }  // cell (0, 0)
+};

@@ -29,6 +29,7 @@
 #include <new>
 #include <vector>
 
+#include "gridmap.h"
 #include "keypoints_host.h"
 
 #pragma STDC FP_CONTRACT OFF
@@ -41,15 +42,7 @@ constexpr int LIST = 1024;                          // scans tested and listed a
 constexpr int GATHER = 9;                           // bytes of a sample loaded without a loop: range_halfwidth 4, the default
 constexpr int MAX_IMAGES = 1 << 24;
 
-struct Geometry {
-  double res, ox, oy, rr;
-  double e_hi;    // (cols rr)^2: d2 at or above it lies in bin `cols` or beyond
-  double max2;    // max_range^2 (+inf: none)
-  double reach2;  // tile test: no cell farther than this (squared, with margin) is observed
-  double hole2;   // tile test: no cell nearer than this (squared, with margin) is observed
-  float inv_rr, rows_per_rad;
-  int W, H, rows, cols, lo_bin, hw, thr;
-};
+using Geometry = rsx::GridmapGeometry;
 
 __device__ __forceinline__ bool finite6(const double *t) {
   bool ok = true;
@@ -244,20 +237,6 @@ __global__ __launch_bounds__(THREADS) void gm_render(const unsigned *__restrict_
 }
 
 }  // namespace
-
-struct rsx_gridmap {
-  int device = 0, rows = 0, cols = 0;
-  rsx_gridmap_params p{};
-  Geometry g{};
-  std::mutex mu;
-  rsx::Stream stream;
-  rsx::DevBuf planes;           // sum, cnt, hit: three [height][width] uint32 planes, one behind the other
-  rsx::DevBuf table;            // float2[rows]
-  rsx::DevBuf img, tf, out;     // staging of the host entries: images, transforms, a rendered window
-  rsx::StreamOrder order;
-  size_t plane_bytes() const { return (size_t)p.width * p.height * sizeof(unsigned); }
-  unsigned *plane(int k) const { return planes.as<unsigned>() + (size_t)k * p.width * p.height; }
-};
 
 using rsx::fail;
 

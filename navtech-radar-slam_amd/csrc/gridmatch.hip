@@ -1,0 +1,470 @@
+// gridmatch.hip -- localising a point cloud in the radar grid map on gfx950: the likelihood plane of the rsx_gridmap handle and the
+// exhaustive correlative matching of clouds against it (rotations -K .. K, whole-cell shifts -V .. V and -U .. U around a prior pose).
+// None of this is in the reference checkout: the rule is the one stated in include/rsx.h and restated in tests/gridmatch_np.py
+// (PARITY UNPINNED): fp64 on plain operations up to the cell of a point, integers from there on, so the scores are the restatement's
+// byte for byte whatever the order of the sums.
+//
+// The plane lies in a zeroed frame of GRIDMAP_LIKE_MARGIN cells (gridmap.h): a placed point's cell is at most 64 cells outside the
+// map, a shift at most 32, a read four bytes wide, so every read is a byte of the buffer, a cell outside the map reads 0 and the inner
+// loop tests no bound.  A point that is not placed is given the cell (-64, -64), from which no candidate reaches the map.
+// Two launches per call whatever the batch, no atomics on device memory:
+//   gmm_score  one workgroup per (job, k).  Every thread takes points t, t + 256, ... through steps 1 - 5 of the rule and leaves
+//              their byte offsets into the framed plane in LDS (32 KB at the cap).  Then a thread owns a SLOT, four neighbouring u
+//              of one v; with S = (2V + 1) ceil((2U + 1) / 4) slots and P = max(1, 256 / S), the points are dealt to P parts and
+//              thread part S + slot walks its part: the offset comes from LDS (a broadcast within a part), the four bytes from one
+//              unaligned 32-bit read (neighbouring slots read neighbouring bytes; the plane is served by L2), and they are added as
+//              two pairs of 16-bit sums that are flushed every 256 points, before they can overflow; eight reads are in flight
+//              per thread (the trip count is known before the loop: an exit test inside it costs a wait per read).  The parts are added
+//              through LDS; with S above 256 a thread walks several slots in turn.
+//   gmm_pick   one workgroup per job: the winner by a 64-bit key that carries the tie order and the linear index, then the
+//              runner-up and, from steps 1 - 5 again at the winner's k, the counts; thread 0 writes the record.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+
+#include "gridmap.h"
+#include "ragged_host.h"
+
+#pragma STDC FP_CONTRACT OFF
+
+namespace {
+
+using rsx::fail;
+using rsx::GRIDMAP_LIKE_MARGIN;
+
+constexpr int NT = 256;
+constexpr int MAX_POINTS = RSX_GRIDMAP_MATCH_MAX_POINTS;
+constexpr int MAX_K = 64, MAX_UV = 32, PLACE = 64;  // PLACE: how far outside the map a point is still placed (cells)
+constexpr int FLUSH = 256;                          // 256 * 255 < 2^16: points between two flushes of the 16-bit sums
+constexpr int DEPTH = 8;                            // reads of the plane a thread keeps in flight
+constexpr size_t VOLUME_STAGE = (size_t)64 << 20;   // rsx_gridmap_match_batch: the bytes of score volume staged per sub-batch
+static_assert(PLACE + MAX_UV + 3 < GRIDMAP_LIKE_MARGIN, "a shifted read must stay in the frame");
+static_assert((MAX_POINTS & (MAX_POINTS - 1)) == 0 && FLUSH * 255 < 65536, "");
+
+struct Tables {
+  float c[2 * MAX_K + 1], s[2 * MAX_K + 1];  // [k + K]
+};
+
+struct MatchGeo {
+  double ox, oy, inv_res, res;
+  int W, H, K, U, V;
+  unsigned pitch;  // of the framed plane
+};
+
+__device__ __forceinline__ bool finite6(const double *t) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 6; k++) ok = ok && ((__double_as_longlong(t[k]) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll);
+  return ok;
+}
+
+// steps 1 - 5 of the rule for one point: false when it is not placed
+__device__ __forceinline__ bool place(const MatchGeo &g, const double *t, double c, double s, double x, double y, int *ix, int *iy) {
+  const double rx = c * x - s * y, ry = s * x + c * y;
+  const double mx = t[0] * rx + t[1] * ry + t[2], my = t[3] * rx + t[4] * ry + t[5];
+  const double fx = (mx - g.ox) * g.inv_res, fy = (my - g.oy) * g.inv_res;
+  if (!(fx >= -(double)PLACE && fx < (double)(g.W + PLACE) && fy >= -(double)PLACE && fy < (double)(g.H + PLACE))) return false;
+  *ix = (int)floor(fx);
+  *iy = (int)floor(fy);
+  return true;
+}
+
+// the points of a job; n < 0 (offsets that decrease: the device entry trusts them, the kernel reads nothing through them) is 0
+__device__ __forceinline__ int64_t job_points(const int64_t *offsets, int job, int64_t *first) {
+  const int64_t a = offsets[job], n = offsets[job + 1] - a;
+  *first = a;
+  return n < 0 ? 0 : n;
+}
+
+// thread-owned slot (v, four u from u0): walks points part, part + parts, ... of cell[0 .. n) and adds the four bytes of each to sum
+__device__ __forceinline__ void walk(const uint8_t *__restrict__ plane, const unsigned *cell, int n, int part, int parts, unsigned shift,
+                                     unsigned sum[4]) {
+  const int mine = part < n ? (n - part + parts - 1) / parts : 0;  // points of this part
+  for (int done = 0; done < mine; done += FLUSH) {
+    const int m = mine - done < FLUSH ? mine - done : FLUSH;
+    const unsigned *c = cell + part + done * parts;
+    unsigned lo = 0u, hi = 0u;  // bytes 0 and 2, bytes 1 and 3, as two 16-bit sums each
+    int q = 0;
+    for (; q + DEPTH <= m; q += DEPTH) {  // DEPTH reads in flight: nothing in the loop depends on a read but the sums
+      unsigned w[DEPTH];
+#pragma unroll
+      for (int e = 0; e < DEPTH; e++) __builtin_memcpy(&w[e], plane + (c[(q + e) * parts] + shift), 4);
+#pragma unroll
+      for (int e = 0; e < DEPTH; e++) lo += w[e] & 0x00ff00ffu, hi += (w[e] >> 8) & 0x00ff00ffu;
+    }
+    for (; q < m; q++) {
+      unsigned w;
+      __builtin_memcpy(&w, plane + (c[q * parts] + shift), 4);
+      lo += w & 0x00ff00ffu, hi += (w >> 8) & 0x00ff00ffu;
+    }
+    sum[0] += lo & 0xffffu, sum[1] += hi & 0xffffu, sum[2] += lo >> 16, sum[3] += hi >> 16;
+  }
+}
+
+__global__ __launch_bounds__(NT) void gmm_score(const float *__restrict__ xy, int64_t stride, const int64_t *__restrict__ offsets,
+                                                const double *__restrict__ priors, Tables tab, MatchGeo g,
+                                                const uint8_t *__restrict__ plane, unsigned *__restrict__ volume) {
+  __shared__ unsigned cell[MAX_POINTS];  // byte offset of the point's cell in the framed plane
+  __shared__ unsigned red[NT * 4];
+  const int tid = threadIdx.x;
+  const int nk = 2 * g.K + 1, nv = 2 * g.V + 1, nu = 2 * g.U + 1, groups = (nu + 3) >> 2;
+  const int job = (int)(blockIdx.x / (unsigned)nk), kk = (int)(blockIdx.x % (unsigned)nk);
+  unsigned *out = volume + ((int64_t)job * nk + kk) * nv * nu;
+  const double *t = priors + 6 * (int64_t)job;
+  int64_t first;
+  const int64_t n64 = job_points(offsets, job, &first);
+  if (n64 > MAX_POINTS || !finite6(t)) {  // (workgroup-uniform) a skipped job: its scores are 0
+    for (int i = tid; i < nv * nu; i += NT) out[i] = 0u;
+    return;
+  }
+  const int n = (int)n64;
+  const double c = (double)tab.c[kk], s = (double)tab.s[kk];
+  const double t6[6] = {t[0], t[1], t[2], t[3], t[4], t[5]};
+  const unsigned nowhere = (unsigned)(GRIDMAP_LIKE_MARGIN - PLACE) * g.pitch + (unsigned)(GRIDMAP_LIKE_MARGIN - PLACE);  // cell (-64, -64)
+  for (int i = tid; i < n; i += NT) {
+    const float *p = xy + (first + i) * stride;
+    int ix, iy;
+    cell[i] = place(g, t6, c, s, (double)p[0], (double)p[1], &ix, &iy)
+                  ? (unsigned)(iy + GRIDMAP_LIKE_MARGIN) * g.pitch + (unsigned)(ix + GRIDMAP_LIKE_MARGIN)
+                  : nowhere;
+  }
+  __syncthreads();
+  const int slots = nv * groups;
+  const int parts = slots < NT ? NT / slots : 1;
+  if (parts > 1) {  // (workgroup-uniform) every slot has a thread in each part
+    unsigned sum[4] = {0u, 0u, 0u, 0u};
+    const int part = tid / slots, slot = tid - part * slots;
+    const int vi = slot / groups, gi = slot - vi * groups;
+    if (part < parts) walk(plane, cell, n, part, parts, (unsigned)((vi - g.V) * (int)g.pitch + (4 * gi - g.U)), sum);
+#pragma unroll
+    for (int j = 0; j < 4; j++) red[4 * tid + j] = sum[j];
+    __syncthreads();
+    if (tid < slots) {
+      for (int q = 1; q < parts; q++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) sum[j] += red[4 * (tid + q * slots) + j];
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (4 * gi + j < nu) out[vi * nu + 4 * gi + j] = sum[j];
+    }
+  } else {
+    for (int slot = tid; slot < slots; slot += NT) {
+      unsigned sum[4] = {0u, 0u, 0u, 0u};
+      const int vi = slot / groups, gi = slot - vi * groups;
+      walk(plane, cell, n, 0, 1, (unsigned)((vi - g.V) * (int)g.pitch + (4 * gi - g.U)), sum);
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (4 * gi + j < nu) out[vi * nu + 4 * gi + j] = sum[j];
+    }
+  }
+}
+
+// the maximum of v over the workgroup (every thread gets it); scratch: NT entries
+template <typename T>
+__device__ __forceinline__ T block_max(T v, T *scratch) {
+  const int tid = threadIdx.x;
+  __syncthreads();  // (the scratch may still be read from the call before)
+  scratch[tid] = v;
+  __syncthreads();
+  for (int h = NT / 2; h > 0; h >>= 1) {
+    if (tid < h) scratch[tid] = scratch[tid] > scratch[tid + h] ? scratch[tid] : scratch[tid + h];
+    __syncthreads();
+  }
+  return scratch[0];
+}
+
+__global__ __launch_bounds__(NT) void gmm_pick(const float *__restrict__ xy, int64_t stride, const int64_t *__restrict__ offsets,
+                                               const double *__restrict__ priors, Tables tab, MatchGeo g,
+                                               const unsigned *__restrict__ volume, rsx_gridmap_match_result *__restrict__ results) {
+  __shared__ unsigned long long keys[NT];
+  __shared__ unsigned seconds[NT];
+  __shared__ unsigned n_placed, n_inside;
+  const int tid = threadIdx.x, job = blockIdx.x;
+  const int nk = 2 * g.K + 1, nv = 2 * g.V + 1, nu = 2 * g.U + 1, total = nk * nv * nu;
+  const unsigned *vol = volume + (int64_t)job * total;
+  const double *t = priors + 6 * (int64_t)job;
+  int64_t first;
+  const int64_t n64 = job_points(offsets, job, &first);
+  rsx_gridmap_match_result r;
+  memset(&r, 0, sizeof(r));
+  const int skipped = (finite6(t) ? 0 : RSX_GRIDMAP_MATCH_STATUS_TRANSFORM) | (n64 > MAX_POINTS ? RSX_GRIDMAP_MATCH_STATUS_POINTS : 0);
+  if (skipped) {  // (workgroup-uniform)
+    r.status = skipped;
+    if (tid == 0) results[job] = r;
+    return;
+  }
+  // ---- the winner: score, then the smallest |k|, then the smallest u u + v v, then the smallest linear index ----
+  // score < 2^21 | 127 - |k| < 2^7 | 4095 - (u u + v v) < 2^12 | 2^20 - 1 - index < 2^20
+  unsigned long long key = 0ull;
+  for (int i = tid; i < total; i += NT) {
+    const int ui = i % nu, vi = (i / nu) % nv, ki = i / (nu * nv);
+    const int k = ki - g.K, v = vi - g.V, u = ui - g.U;
+    const unsigned long long cand = ((unsigned long long)vol[i] << 39) | ((unsigned long long)(127 - (k < 0 ? -k : k)) << 32) |
+                                    ((unsigned long long)(4095 - (u * u + v * v)) << 20) | (unsigned long long)(0xfffff - i);
+    key = cand > key ? cand : key;
+  }
+  key = block_max(key, keys);
+  const int best = 0xfffff - (int)(key & 0xfffffull);
+  const int bu = best % nu - g.U, bv = (best / nu) % nv - g.V, bk = best / (nu * nv) - g.K;
+  // ---- the runner-up: the best score farther than 1 from the winner in k, u or v ----
+  unsigned second = 0u;
+  for (int i = tid; i < total; i += NT) {
+    const int du = i % nu - g.U - bu, dv = (i / nu) % nv - g.V - bv, dk = i / (nu * nv) - g.K - bk;
+    const bool far = du > 1 || du < -1 || dv > 1 || dv < -1 || dk > 1 || dk < -1;
+    second = far && vol[i] > second ? vol[i] : second;
+  }
+  second = block_max(second, seconds);
+  // ---- the counts at the winner ----
+  if (tid == 0) n_placed = 0u, n_inside = 0u;
+  __syncthreads();
+  const double c = (double)tab.c[bk + g.K], s = (double)tab.s[bk + g.K];
+  const double t6[6] = {t[0], t[1], t[2], t[3], t[4], t[5]};
+  unsigned placed = 0u, inside = 0u;
+  for (int i = tid; i < (int)n64; i += NT) {
+    const float *p = xy + (first + i) * stride;
+    int ix, iy;
+    if (place(g, t6, c, s, (double)p[0], (double)p[1], &ix, &iy)) {
+      placed++;
+      inside += (ix + bu >= 0 && ix + bu < g.W && iy + bv >= 0 && iy + bv < g.H) ? 1u : 0u;
+    }
+  }
+  atomicAdd(&n_placed, placed);  // (LDS)
+  atomicAdd(&n_inside, inside);
+  __syncthreads();
+  if (tid != 0) return;
+  r.score = (unsigned)(key >> 39);
+  r.score_prior = vol[(g.K * nv + g.V) * nu + g.U];
+  r.score_runner_up = second;
+  r.k = bk, r.u = bu, r.v = bv;
+  r.n_points = (int)n_placed, r.n_inside = (int)n_inside;
+  if (r.score == 0u) {
+    r.status = RSX_GRIDMAP_MATCH_STATUS_EMPTY;
+    for (int q = 0; q < 6; q++) r.transform[q] = t6[q];
+  } else {
+    r.transform[0] = t6[0] * c + t6[1] * s;
+    r.transform[1] = t6[1] * c - t6[0] * s;
+    r.transform[2] = t6[2] + (double)bu * g.res;
+    r.transform[3] = t6[3] * c + t6[4] * s;
+    r.transform[4] = t6[4] * c - t6[3] * s;
+    r.transform[5] = t6[5] + (double)bv * g.res;
+  }
+  results[job] = r;
+}
+
+// one thread per cell: the byte of the likelihood plane from the planes -- render's rule (gm_render of gridmap.hip; include/rsx.h),
+// the hit ratio with "unknown" as 0
+__global__ __launch_bounds__(NT) void gmm_likelihood(const unsigned *__restrict__ p_sum, const unsigned *__restrict__ p_cnt,
+                                                     const unsigned *__restrict__ p_hit, int W, int H, int mode, unsigned min_obs,
+                                                     uint8_t *__restrict__ origin, int64_t pitch) {
+  const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (i >= (int64_t)W * H) return;
+  const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
+  const unsigned long long cnt = p_cnt[i];
+  unsigned long long v = 0ull;
+  if (cnt >= min_obs) {
+    if (mode == RSX_GRIDMAP_MEAN) {
+      v = (2ull * p_sum[i] + cnt) / (2ull * cnt);
+      v = v < 255ull ? v : 255ull;
+    } else {
+      v = (200ull * p_hit[i] + cnt) / (2ull * cnt);
+    }
+  }
+  origin[(int64_t)y * pitch + x] = (uint8_t)v;
+}
+
+int check_params(const rsx_gridmap_match_params &p) {
+  if (p.angle_steps < 0 || p.angle_steps > MAX_K) return fail(RSX_ERR_BAD_ARG, "angle_steps %d outside 0 .. %d", p.angle_steps, MAX_K);
+  if (p.angle_steps > 0 && (!(p.angle_step > 0.0) || !std::isfinite(p.angle_step)))
+    return fail(RSX_ERR_BAD_ARG, "angle_step must be positive and finite when angle_steps > 0");
+  if (p.x_cells < 0 || p.x_cells > MAX_UV) return fail(RSX_ERR_BAD_ARG, "x_cells %d outside 0 .. %d", p.x_cells, MAX_UV);
+  if (p.y_cells < 0 || p.y_cells > MAX_UV) return fail(RSX_ERR_BAD_ARG, "y_cells %d outside 0 .. %d", p.y_cells, MAX_UV);
+  if (p.reserved != 0) return fail(RSX_ERR_BAD_ARG, "reserved must be 0");
+  return RSX_OK;
+}
+
+int resolve(const rsx_gridmap_match_params *params, rsx_gridmap_match_params &dp) {
+  rsx_gridmap_match_default_params(&dp);
+  if (params) dp = *params;
+  return check_params(dp);
+}
+
+size_t candidates(const rsx_gridmap_match_params &p) { return (size_t)(2 * p.angle_steps + 1) * (2 * p.y_cells + 1) * (2 * p.x_cells + 1); }
+
+int check_render(int32_t mode, int32_t min_observations) {
+  if (mode != RSX_GRIDMAP_MEAN && mode != RSX_GRIDMAP_HITS) return fail(RSX_ERR_BAD_ARG, "unknown render mode %d", mode);
+  if (min_observations < 1) return fail(RSX_ERR_BAD_ARG, "min_observations %d < 1", min_observations);
+  return RSX_OK;
+}
+
+// the framed plane, allocated and zeroed at the first call that needs it (the caller holds h->mu and has entered s)
+int need_plane(rsx_gridmap *h, hipStream_t s) {
+  if (h->like.p) return RSX_OK;
+  RSX_TRY(h->like.reserve(h->like_bytes(), s, false));
+  RSX_HIP(hipMemsetAsync(h->like.p, 0, h->like.bytes, s));
+  return RSX_OK;
+}
+
+int no_likelihood() { return fail(RSX_ERR_BAD_ARG, "no likelihood plane yet: rsx_gridmap_likelihood_update or rsx_gridmap_likelihood_set first"); }
+
+// the two launches behind both entries (the caller holds h->mu and has entered s): n jobs, their volume at d_volume
+int launch(rsx_gridmap *h, const float *d_xy, const int64_t *d_off, int32_t stride, int n, const double *d_priors, const rsx_gridmap_match_params &p,
+           rsx_gridmap_match_result *d_results, uint32_t *d_volume, hipStream_t s) {
+  Tables tab;
+  memset(&tab, 0, sizeof(tab));
+  for (int k = -p.angle_steps; k <= p.angle_steps; k++) {  // fp64, rounded once
+    const double ang = (double)k * p.angle_step;
+    tab.c[k + p.angle_steps] = (float)std::cos(ang);
+    tab.s[k + p.angle_steps] = (float)std::sin(ang);
+  }
+  MatchGeo g{};
+  g.ox = h->p.origin_x, g.oy = h->p.origin_y, g.res = h->p.resolution, g.inv_res = 1.0 / h->p.resolution;
+  g.W = h->p.width, g.H = h->p.height, g.K = p.angle_steps, g.U = p.x_cells, g.V = p.y_cells;
+  g.pitch = (unsigned)h->like_pitch();
+  const unsigned nk = (unsigned)(2 * p.angle_steps + 1);
+  hipLaunchKernelGGL(gmm_score, dim3((unsigned)n * nk), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, tab, g, h->like.as<uint8_t>(), d_volume);
+  RSX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(gmm_pick, dim3((unsigned)n), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, tab, g, d_volume, d_results);
+  RSX_HIP(hipGetLastError());
+  return RSX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsx_gridmap_match_default_params(rsx_gridmap_match_params *p) try {
+  if (!p) return fail(RSX_ERR_BAD_ARG, "null params");
+  p->angle_step = 0.01;
+  p->angle_steps = 8;
+  p->x_cells = 8;
+  p->y_cells = 8;
+  p->reserved = 0;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_gridmap_likelihood_update(rsx_gridmap *h, int32_t mode, int32_t min_observations, void *stream) try {
+  RSX_TRY(check_render(mode, min_observations));
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(need_plane(h, s));
+  const int64_t n = (int64_t)h->p.width * h->p.height;
+  hipLaunchKernelGGL(gmm_likelihood, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, s, h->plane(0), h->plane(1), h->plane(2), h->p.width, h->p.height,
+                     mode, (unsigned)min_observations, h->like_origin(), h->like_pitch());
+  RSX_HIP(hipGetLastError());
+  h->have_like = true;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_gridmap_likelihood_set(rsx_gridmap *h, const uint8_t *img) try {
+  if (!img) return fail(RSX_ERR_BAD_ARG, "null image");
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(need_plane(h, s));
+  RSX_HIP(hipMemcpy2DAsync(h->like_origin(), (size_t)h->like_pitch(), img, (size_t)h->p.width, (size_t)h->p.width, (size_t)h->p.height,
+                           hipMemcpyHostToDevice, s));
+  RSX_HIP(hipStreamSynchronize(s));
+  h->have_like = true;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_gridmap_likelihood_device(rsx_gridmap *h, uint8_t **d_likelihood, int64_t *pitch_bytes) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_TRY(need_plane(h, s));
+  RSX_HIP(hipStreamSynchronize(s));  // (the frame is zero before the caller can write)
+  h->have_like = true;
+  if (d_likelihood) *d_likelihood = h->like_origin();
+  if (pitch_bytes) *pitch_bytes = h->like_pitch();
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_gridmap_likelihood_read(rsx_gridmap *h, int32_t x, int32_t y, int32_t w, int32_t hgt, uint8_t *out) try {
+  if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  if (x < 0 || y < 0 || w < 1 || hgt < 1 || x > h->p.width - w || y > h->p.height - hgt)
+    return fail(RSX_ERR_BAD_ARG, "window %d x %d at (%d, %d) outside the %d x %d map", w, hgt, x, y, h->p.width, h->p.height);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->have_like) return no_likelihood();
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  RSX_HIP(hipMemcpy2DAsync(out, (size_t)w, h->like_origin() + (size_t)y * h->like_pitch() + x, (size_t)h->like_pitch(), (size_t)w, (size_t)hgt,
+                           hipMemcpyDeviceToHost, s));
+  RSX_HIP(hipStreamSynchronize(s));
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_gridmap_match_batch_device(rsx_gridmap *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride, int32_t n_jobs,
+                                   const double *d_priors, const rsx_gridmap_match_params *params, rsx_gridmap_match_result *d_results,
+                                   uint32_t *d_scores, void *stream) try {
+  // (the arguments are judged before the handle is looked at: their rules need no device)
+  if (!d_xy || !d_offsets || !d_priors || !d_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  if (point_stride < 2) return fail(RSX_ERR_BAD_ARG, "point_stride %d below 2", point_stride);
+  rsx_gridmap_match_params dp;
+  RSX_TRY(resolve(params, dp));
+  if ((int64_t)n_jobs * (2 * dp.angle_steps + 1) > 0x7fffffffll) return fail(RSX_ERR_BAD_ARG, "n_jobs %d times %d rotations is 2^31 or more", n_jobs, 2 * dp.angle_steps + 1);
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->have_like) return no_likelihood();
+  if (n_jobs == 0) return RSX_OK;
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  RSX_TRY(h->order.enter(s));
+  if (!d_scores) {
+    RSX_TRY(h->volume.reserve((size_t)n_jobs * candidates(dp) * sizeof(uint32_t), s, false));
+    d_scores = h->volume.as<uint32_t>();
+  }
+  return launch(h, d_xy, d_offsets, point_stride, n_jobs, d_priors, dp, d_results, d_scores, s);
+} RSX_CATCH_ALL
+
+int rsx_gridmap_match_batch(rsx_gridmap *h, const float *xy, const int64_t *offsets, int32_t n_jobs, const double *priors,
+                            const rsx_gridmap_match_params *params, rsx_gridmap_match_result *out_results, uint32_t *out_scores) try {
+  // (the arguments are judged before the handle is looked at: their rules need no device)
+  if (!xy || !offsets || !priors || !out_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  rsx_gridmap_match_params dp;
+  RSX_TRY(resolve(params, dp));
+  if (n_jobs > 0) {
+    RSX_TRY(rsx::check_offsets(offsets, n_jobs, "rsx_gridmap_match_batch"));
+    for (int32_t i = 0; i < n_jobs; i++)
+      if (offsets[i + 1] - offsets[i] > MAX_POINTS)
+        return fail(RSX_ERR_BAD_ARG, "job %d has %lld points, more than %d", i, (long long)(offsets[i + 1] - offsets[i]), MAX_POINTS);
+  }
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->have_like) return no_likelihood();
+  if (n_jobs == 0) return RSX_OK;
+  RSX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  RSX_TRY(h->order.enter(s));
+  const size_t n = (size_t)n_jobs, cand = candidates(dp);
+  RSX_TRY(rsx::stage_up(h->m_xy, xy, (size_t)offsets[n_jobs] * 8, s));
+  RSX_TRY(rsx::stage_up(h->m_off, offsets, (n + 1) * 8, s));
+  RSX_TRY(rsx::stage_up(h->m_tf, priors, n * 48, s));
+  RSX_TRY(rsx::stage_room(h->m_res, n * sizeof(rsx_gridmap_match_result), s));
+  // sub-batches bound the staged volume; a job's bytes do not depend on the cut
+  const size_t per = VOLUME_STAGE / (cand * sizeof(uint32_t)), sub = per < n ? per : n;
+  RSX_TRY(rsx::stage_room(h->volume, sub * cand * sizeof(uint32_t), s));
+  for (size_t b0 = 0; b0 < n; b0 += sub) {
+    const size_t nb = n - b0 < sub ? n - b0 : sub;
+    RSX_TRY(launch(h, h->m_xy.as<float>(), h->m_off.as<int64_t>() + b0, 2, (int)nb, h->m_tf.as<double>() + 6 * b0, dp,
+                   h->m_res.as<rsx_gridmap_match_result>() + b0, h->volume.as<uint32_t>(), s));
+    if (out_scores) RSX_TRY(rsx::stage_down(out_scores + b0 * cand, h->volume, nb * cand * sizeof(uint32_t), s));
+  }
+  RSX_TRY(rsx::stage_down(out_results, h->m_res, n * sizeof(rsx_gridmap_match_result), s));
+  RSX_HIP(hipStreamSynchronize(s));
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+}  // extern "C"

@@ -5,7 +5,8 @@ import ctypes as C
 import numpy as np
 
 from . import synth
-from ._rsx import GRIDMAP_HITS, GRIDMAP_MEAN, GridmapParams, check, lib
+from ._rsx import GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GridmapMatchParams, GridmapParams, check, lib
+from .cfear import ragged
 
 
 def default_params():
@@ -24,6 +25,58 @@ def params(**fields):
             raise TypeError("rsx_gridmap_params has no field " + name)
         setattr(p, name, value)
     return p
+
+
+def default_match_params():
+    """rotations -8 .. 8 of 0.01 rad, shifts -8 .. 8 cells along x and y."""
+    p = GridmapMatchParams()
+    check(lib().rsx_gridmap_match_default_params(C.byref(p)))
+    return p
+
+
+def match_params(**fields):
+    """default_match_params() with the given fields replaced."""
+    p = default_match_params()
+    for name, value in fields.items():
+        if not hasattr(p, name):
+            raise TypeError("rsx_gridmap_match_params has no field " + name)
+        setattr(p, name, value)
+    return p
+
+
+def write_pgm(path, px):
+    """uint8 [h, w] -> binary PGM (P5), row 0 first"""
+    px = np.ascontiguousarray(px, dtype=np.uint8)
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (px.shape[1], px.shape[0]))
+        f.write(px.tobytes())
+
+
+def load_pgm(path):
+    """a binary PGM (P5, maxval 255; comments allowed in the header) -> uint8 [h, w]: the inverse of save_pgm for the mean, so that
+    set_likelihood(load_pgm(f)) localises in a mosaic saved earlier"""
+    with open(path, "rb") as f:
+        data = f.read()
+    fields, at = [], 0
+    while len(fields) < 4:
+        while at < len(data) and data[at:at + 1].isspace():
+            at += 1
+        if data[at:at + 1] == b"#":
+            at = data.index(b"\n", at) + 1
+            continue
+        end = at
+        while end < len(data) and not data[end:end + 1].isspace():
+            end += 1
+        if end == at:
+            raise ValueError(path + ": truncated PGM header")
+        fields.append(data[at:end])
+        at = end
+    if fields[0] != b"P5" or int(fields[3]) != 255:
+        raise ValueError(path + ": not a binary PGM with maxval 255")
+    w, h = int(fields[1]), int(fields[2])
+    if len(data) < at + 1 + w * h:
+        raise ValueError(path + ": truncated PGM")
+    return np.frombuffer(data, dtype=np.uint8, count=w * h, offset=at + 1).reshape(h, w).copy()
 
 
 class GridMap:
@@ -117,6 +170,68 @@ class GridMap:
         else:
             h = self.hits(min_observations).astype(np.int16)
             px = np.where(h < 0, 255, 254 - 2 * h).astype(np.uint8)
-        with open(path, "wb") as f:
-            f.write(b"P5\n%d %d\n255\n" % (px.shape[1], px.shape[0]))
-            f.write(px.tobytes())
+        write_pgm(path, px)
+
+    # ---- localising clouds in the map: the likelihood plane and the correlative matching (include/rsx.h, rsx_gridmap_match_*) ----
+
+    def update_likelihood(self, mode=GRIDMAP_MEAN, min_observations=1, stream=None):
+        """the likelihood plane (a frozen uint8 snapshot that matching reads) from the planes as they stand: the mean, or the hit
+        percentage with unknown as 0.  Asynchronous on `stream`"""
+        check(self._L.rsx_gridmap_likelihood_update(self._h, mode, min_observations, stream))
+
+    def set_likelihood(self, img):
+        """the likelihood plane from a uint8 [height, width] image (load_pgm of a saved mosaic, for one)"""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        assert img.shape == (self.params.height, self.params.width)
+        check(self._L.rsx_gridmap_likelihood_set(self._h, img.ctypes.data))
+
+    def likelihood(self, window=None):
+        """window: (x, y, w, h) in cells, None = the whole map -> uint8 [h, w]"""
+        x, y, w, h = self._window(window)
+        out = np.zeros((max(h, 0), max(w, 0)), dtype=np.uint8)
+        check(self._L.rsx_gridmap_likelihood_read(self._h, x, y, w, h, out.ctypes.data))
+        return out
+
+    def likelihood_device(self):
+        """-> (address of cell (0, 0) of the likelihood plane in device memory, pitch_bytes)"""
+        d, pitch = C.c_void_p(), C.c_int64()
+        check(self._L.rsx_gridmap_likelihood_device(self._h, C.byref(d), C.byref(pitch)))
+        return d.value, pitch.value
+
+    def match(self, clouds, priors, return_scores=False, params=None, **fields):
+        """clouds: list of (n_i, 2) float32 in the sensor frame; priors: (n, 6) float64 r00, r01, tx, r10, r11, ty (coral.pose_matrices
+        makes them from x, y, yaw); params: a GridmapMatchParams, or its fields by name (angle_steps, angle_step, x_cells, y_cells)
+        -> results (n,) GRIDMAP_MATCH_RESULT_DTYPE, and with return_scores=True also the volumes uint32 [n, 2K + 1, 2V + 1, 2U + 1]"""
+        if params is not None and fields:
+            raise TypeError("give params or its fields, not both")
+        p = params if params is not None else match_params(**fields)
+        xy, off = ragged(clouds, np.float32, 2)
+        n = len(clouds)
+        priors = np.ascontiguousarray(priors, dtype=np.float64).reshape(n, 6)
+        res = np.zeros(n, dtype=GRIDMAP_MATCH_RESULT_DTYPE)
+        vol = np.zeros((n, 2 * max(p.angle_steps, 0) + 1, 2 * max(p.y_cells, 0) + 1, 2 * max(p.x_cells, 0) + 1), dtype=np.uint32) if return_scores else None
+        check(self._L.rsx_gridmap_match_batch(self._h, xy.ctypes.data, off.ctypes.data, n, priors.ctypes.data, C.byref(p), res.ctypes.data,
+                                              vol.ctypes.data if return_scores else None))
+        return (res, vol) if return_scores else res
+
+    def match_device(self, xy, offsets, priors, results, scores=None, params=None, stream=None, **fields):
+        """the same on torch tensors of the handle's device: xy float32 [m, point_stride] (rows point_stride floats apart, x and y
+        first), offsets int64 (n + 1,), priors float64 (n, 6) contiguous, results uint8 of n * 88 bytes (view it as
+        GRIDMAP_MATCH_RESULT_DTYPE on the host), scores (optional) uint32 / int32 of n (2K + 1)(2V + 1)(2U + 1) elements.  Asynchronous on
+        `stream` (an int, None = the handle's own stream); a job above the cap gets GRIDMAP_MATCH_STATUS_POINTS"""
+        if params is not None and fields:
+            raise TypeError("give params or its fields, not both")
+        p = params if params is not None else match_params(**fields)
+        n = offsets.numel() - 1
+        assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and priors.is_contiguous()
+        assert priors.numel() == 6 * n and results.is_contiguous() and results.numel() * results.element_size() == n * GRIDMAP_MATCH_RESULT_DTYPE.itemsize
+        if scores is not None:
+            assert scores.is_contiguous() and scores.element_size() == 4
+            assert scores.numel() == n * (2 * p.angle_steps + 1) * (2 * p.y_cells + 1) * (2 * p.x_cells + 1)
+        check(self._L.rsx_gridmap_match_batch_device(self._h, xy.data_ptr(), offsets.data_ptr(), xy.stride(0), n, priors.data_ptr(), C.byref(p),
+                                                     results.data_ptr(), scores.data_ptr() if scores is not None else None, stream))
+
+    def score(self, clouds, poses):
+        """how well clouds fit the map at poses (n, 6): match with no window (K = U = V = 0) -> results; `score` is the sum of the
+        likelihood bytes under the cloud, n_inside the points it was taken over"""
+        return self.match(clouds, poses, angle_steps=0, x_cells=0, y_cells=0)
