@@ -89,10 +89,14 @@ def test_shapes_of_the_persistent_kernel(icpmod, oracle, ns, nt):
     assert abs(got["fitness"] - want["fitness"]) < 1e-6 * max(1.0, want["fitness"])
 
 
-def test_empty_clouds(icpmod):
+def test_empty_clouds(icpmod, oracle):
     ic = icpmod.Icp()
     pts = scene(3, 200)
     for src, tgt in ((pts[:0], pts), (pts, pts[:0]), (pts[:2], pts)):
         r = ic.align(src, tgt)
         assert not r["converged"] and r["state"] == 5 and r["iterations"] == 0
         assert np.array_equal(r["transform"], np.eye(4, dtype=np.float32))
+        # no source point with a neighbour: the largest double, as getFitnessScore(); two points still have their distances
+        want = oracle.icp_align(src, tgt, sum_order=oracle.ICP_SUM_TREE)["fitness"]
+        assert want == (1.7976931348623157e308 if min(len(src), len(tgt)) == 0 else 0.0)
+        assert r["fitness"] == want
