@@ -1396,6 +1396,80 @@ int rsx_gridmap_match_batch_device(rsx_gridmap *h, const float *d_xy, const int6
                                    const double *d_priors, const rsx_gridmap_match_params *params, rsx_gridmap_match_result *d_results,
                                    uint32_t *d_scores, void *stream);
 
+/* ---- the same search over a wide window, pruned by bounds (csrc/gridsearch.hip): re-localising after a lost track, starting in a
+ * saved mosaic, placing a loop candidate that has a yaw and no translation.  Two levels, exact: the winner is the winner that the
+ * exhaustive rule above would give over the same window; pruning changes the cost only.  Restated in tests/gridsearch_np.py, which
+ * is the arithmetic contract -- parity unpinned; integers from the cell on, bytes equal to the restatement.
+ * Jobs, priors, the ragged convention, the cap of points, the tables and steps 1 - 5 are those of rsx_gridmap_match_*, but for the
+ * placement margin of step 4: PL = max(64, U, V) replaces 64 (fx >= -PL && fx < width + PL, likewise fy); with U, V <= 64 that is
+ * the rule above.
+ * Candidates (k, v, u), |k| <= K <= 180, |v| <= V <= 256, |u| <= U <= 256; score(k, v, u), the tie order and the linear index as above.
+ * Pooled plane: P[y][x] = max of L[y + a][x + b] over 0 <= a, b < 8, for every integer y, x; cells outside the map count as 0.
+ * Blocks: nbu = ceil((2U + 1) / 8), nbv = ceil((2V + 1) / 8); block (k, bv, bu) holds the candidates with v in
+ * [-V + 8 bv, min(V, -V + 8 bv + 7)] and u likewise.  bound(k, bv, bu) = the sum over the placed points of
+ * P[iy - V + 8 bv][ix - U + 8 bu], a uint32: no smaller than any score of the block.
+ * Threshold: seed(k) = the highest score among the candidates of that block of k which has the highest bound (among equal bounds
+ * the smallest bv nbu + bu); T0 = max(min_score, score(0, 0, 0), max over k of seed(k)).  A block is REFINED iff its bound >=
+ * max(T0, 1): a block whose bound equals T0 stays, because a tie can win the order.
+ * The winner is the best candidate by the tie order with score >= max(min_score, 1) among the refined blocks.  (The exhaustive
+ * winner's score s* is >= T0 once it is eligible, and its block's bound >= s*: its block is refined.)
+ * Result: transform, k, u, v, score, score_prior, n_points, n_inside as in rsx_gridmap_match_result; n_blocks = (2K + 1) nbv nbu;
+ * n_refined = the number of refined blocks, by the rule above whatever the kernel skips on top; bound_runner_up = the largest bound
+ * among the blocks farther than 1 from the winner's block in k, bv or bu (0 if there is none, or if status != 0): score >
+ * bound_runner_up proves that nothing outside the neighbourhood of the winner's block comes near.
+ * Status: _TRANSFORM and _POINTS as above (the record is zero but for the status).  _EMPTY: min_score == 0 and the best score is
+ * 0: k = u = v = 0, transform = the prior bit for bit.  _BELOW: min_score > 0 and no candidate reaches it: k = u = v = 0, transform =
+ * the prior, score = 0; score_prior, n_blocks, n_refined and the counts (at k = 0) still by the rule.
+ * For K <= 64, U, V <= 32 and min_score 0 the fields transform, k, u, v, score, score_prior, n_points, n_inside and status equal
+ * rsx_gridmap_match_batch's byte for byte.
+ * Three launches per call whatever the batch (bounds and seeds, one workgroup per (job, k); refinement, likewise; the pick, one
+ * workgroup per job); no atomics on device memory. */
+
+#define RSX_GRIDMAP_SEARCH_STATUS_BELOW 8
+#define RSX_GRIDMAP_SEARCH_MAX_CELLS 256
+#define RSX_GRIDMAP_SEARCH_MAX_ANGLE_STEPS 180
+
+typedef struct {
+  double angle_step;    /* as rsx_gridmap_match_params (0.01) */
+  int32_t angle_steps;  /* K: 0 .. 180 (32) */
+  int32_t x_cells;      /* U: 0 .. 256 (64) */
+  int32_t y_cells;      /* V: 0 .. 256 (64) */
+  uint32_t min_score;   /* a winner must reach it; 0 = none (0) */
+} rsx_gridmap_search_params; /* 24 bytes */
+
+typedef struct {
+  double transform[6];      /* r00 r01 tx r10 r11 ty of the winner */
+  int32_t k, u, v;          /* the winner */
+  uint32_t score, score_prior, bound_runner_up;
+  int32_t n_points, n_inside;
+  int32_t status;           /* RSX_GRIDMAP_MATCH_STATUS_* | RSX_GRIDMAP_SEARCH_STATUS_BELOW */
+  int32_t n_blocks, n_refined;
+  int32_t reserved;         /* 0 */
+} rsx_gridmap_search_result; /* 96 bytes */
+
+/* a violated rule of rsx_gridmap_search_params gives RSX_ERR_BAD_ARG in every entry that takes the struct (NULL = the defaults),
+ * judged before the handle or the device is looked at */
+int rsx_gridmap_search_default_params(rsx_gridmap_search_params *p);
+/* what a search reads: a frozen snapshot of the likelihood plane as it stands (later likelihood changes are not seen until the next
+ * prepare), good for searches with U, V <= max_cells (0 .. 256).  Two buffers of the search's own: a copy of the plane in a zeroed
+ * frame of max(64, max_cells) + max_cells + 32 cells (rounded up to 8), and the pooled plane, de-interleaved by phase; about
+ * 2 (width + 2 frame)(height + 2 frame) bytes.  RSX_ERR_BAD_ARG before any likelihood exists.  Asynchronous on `stream`, one launch
+ * (and a memset of the two buffers when it allocates them). */
+int rsx_gridmap_search_prepare(rsx_gridmap *h, int32_t max_cells, void *stream);
+/* n_jobs jobs against the prepared snapshot.  Host buffers, synchronous.  out_bounds (may be NULL): uint32 [job][2K + 1][nbv][nbu].
+ * The offsets are checked, a job above the cap refuses the batch; before any prepare, or with U or V above the prepared max_cells,
+ * the call is RSX_ERR_BAD_ARG and touches nothing.  Staged in sub-batches of at most 64 MB of bounds (a job's bytes do not depend
+ * on the cut). */
+int rsx_gridmap_search_batch(rsx_gridmap *h, const float *xy, const int64_t *offsets, int32_t n_jobs, const double *priors,
+                             const rsx_gridmap_search_params *params, rsx_gridmap_search_result *out_results, uint32_t *out_bounds);
+/* device buffers, asynchronous on `stream`: three launches, no host synchronisation; point_stride >= 2 as for
+ * rsx_gridmap_match_batch_device; the offsets are trusted; a job above the cap gets RSX_GRIDMAP_MATCH_STATUS_POINTS.
+ * n_jobs (2K + 1) < 2^31.  Workspace: 16 bytes per (job, k) and 4 per job, and with d_bounds NULL the bounds, n_jobs (2K + 1) nbv nbu * 4 bytes,
+ * in buffers of the handle that grow (to the next power of two) and are never given back before destroy. */
+int rsx_gridmap_search_batch_device(rsx_gridmap *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride, int32_t n_jobs,
+                                    const double *d_priors, const rsx_gridmap_search_params *params, rsx_gridmap_search_result *d_results,
+                                    uint32_t *d_bounds, void *stream);
+
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;
  * SURVEY 8f rank 3): polar -> Cartesian image, ORB-style binary descriptors at the keypoints, brute-force Hamming

@@ -211,6 +211,23 @@ GRIDMAP_MATCH_RESULT_DTYPE = np.dtype([("transform", "<f8", 6), ("k", "<i4"), ("
                                        ("score_runner_up", "<u4"), ("n_points", "<i4"), ("n_inside", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
 
 
+class GridmapSearchParams(C.Structure):
+    _fields_ = [("angle_step", C.c_double), ("angle_steps", C.c_int32), ("x_cells", C.c_int32), ("y_cells", C.c_int32), ("min_score", C.c_uint32)]
+
+
+class GridmapSearchResult(C.Structure):
+    _fields_ = [("transform", C.c_double * 6), ("k", C.c_int32), ("u", C.c_int32), ("v", C.c_int32), ("score", C.c_uint32),
+                ("score_prior", C.c_uint32), ("bound_runner_up", C.c_uint32), ("n_points", C.c_int32), ("n_inside", C.c_int32),
+                ("status", C.c_int32), ("n_blocks", C.c_int32), ("n_refined", C.c_int32), ("reserved", C.c_int32)]
+
+
+GRIDMAP_SEARCH_STATUS_BELOW = 8  # RSX_GRIDMAP_SEARCH_STATUS_BELOW
+GRIDMAP_SEARCH_MAX_CELLS, GRIDMAP_SEARCH_MAX_ANGLE_STEPS = 256, 180
+GRIDMAP_SEARCH_RESULT_DTYPE = np.dtype([("transform", "<f8", 6), ("k", "<i4"), ("u", "<i4"), ("v", "<i4"), ("score", "<u4"), ("score_prior", "<u4"),
+                                        ("bound_runner_up", "<u4"), ("n_points", "<i4"), ("n_inside", "<i4"), ("status", "<i4"), ("n_blocks", "<i4"),
+                                        ("n_refined", "<i4"), ("reserved", "<i4")])
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -300,6 +317,7 @@ SYMBOLS = [
     "rsx_gridmap_add_batch_device", "rsx_gridmap_read", "rsx_gridmap_planes_device", "rsx_gridmap_render", "rsx_gridmap_render_device",
     "rsx_gridmap_match_default_params", "rsx_gridmap_likelihood_update", "rsx_gridmap_likelihood_set", "rsx_gridmap_likelihood_device",
     "rsx_gridmap_likelihood_read", "rsx_gridmap_match_batch", "rsx_gridmap_match_batch_device",
+    "rsx_gridmap_search_default_params", "rsx_gridmap_search_prepare", "rsx_gridmap_search_batch", "rsx_gridmap_search_batch_device",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
     "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
     "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
@@ -500,6 +518,10 @@ def lib():
         L.rsx_gridmap_likelihood_read.argtypes = [vp, i32, i32, i32, i32, vp]
         L.rsx_gridmap_match_batch.argtypes = [vp, vp, vp, i32, vp, C.POINTER(GridmapMatchParams), vp, vp]
         L.rsx_gridmap_match_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(GridmapMatchParams), vp, vp, vp]
+        L.rsx_gridmap_search_default_params.argtypes = [C.POINTER(GridmapSearchParams)]
+        L.rsx_gridmap_search_prepare.argtypes = [vp, i32, vp]
+        L.rsx_gridmap_search_batch.argtypes = [vp, vp, vp, i32, vp, C.POINTER(GridmapSearchParams), vp, vp]
+        L.rsx_gridmap_search_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(GridmapSearchParams), vp, vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
         L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]

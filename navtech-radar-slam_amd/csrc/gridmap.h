@@ -1,5 +1,5 @@
 // gridmap.h -- the handle of the radar grid map, shared by gridmap.hip (the planes: accumulate, read, render) and gridmatch.hip (the
-// likelihood plane and the correlative matching that reads it).
+// likelihood plane and the correlative matching that reads it) and gridsearch.hip (the wide-window search over a snapshot of it).
 #pragma once
 #include <cstdint>
 #include <mutex>
@@ -44,5 +44,11 @@ struct rsx_gridmap {
   rsx::DevBuf m_xy, m_off, m_tf, m_res;  // staging of rsx_gridmap_match_batch: points, offsets, priors, results
   int64_t like_pitch() const { return (int64_t)p.width + 2 * rsx::GRIDMAP_LIKE_MARGIN; }
   size_t like_bytes() const { return (size_t)like_pitch() * ((size_t)p.height + 2 * rsx::GRIDMAP_LIKE_MARGIN); }
+  // ---- gridsearch.hip: nothing below is allocated before the first rsx_gridmap_search_prepare ----
+  int s_cells = -1;             // the max_cells of the last prepare (-1: none yet)
+  int s_margin = 0, s_cw = 0, s_ch = 0;  // the frame of that prepare: cells on every side (a multiple of 8), coarse columns and rows
+  rsx::DevBuf s_frame;          // uint8 [8 s_ch][8 s_cw]: a copy of the likelihood plane in a zeroed frame of s_margin cells
+  rsx::DevBuf s_pool;           // uint8 [8][8][s_ch][s_cw]: the 8 x 8 pooled plane, de-interleaved by phase
+  rsx::DevBuf s_bounds, s_aux;  // workspace of a search: the bounds of a call that asked for none; seeds, prior scores, keys, counts
   uint8_t *like_origin() const { return like.as<uint8_t>() + (size_t)rsx::GRIDMAP_LIKE_MARGIN * like_pitch() + rsx::GRIDMAP_LIKE_MARGIN; }  // cell (0, 0)
 };

@@ -5,7 +5,8 @@ import ctypes as C
 import numpy as np
 
 from . import synth
-from ._rsx import GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GridmapMatchParams, GridmapParams, check, lib
+from ._rsx import (GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GRIDMAP_SEARCH_RESULT_DTYPE, GridmapMatchParams, GridmapParams,
+                   GridmapSearchParams, check, lib)
 from .cfear import ragged
 
 
@@ -42,6 +43,28 @@ def match_params(**fields):
             raise TypeError("rsx_gridmap_match_params has no field " + name)
         setattr(p, name, value)
     return p
+
+
+def default_search_params():
+    """rotations -32 .. 32 of 0.01 rad, shifts -64 .. 64 cells along x and y, no min_score."""
+    p = GridmapSearchParams()
+    check(lib().rsx_gridmap_search_default_params(C.byref(p)))
+    return p
+
+
+def search_params(**fields):
+    """default_search_params() with the given fields replaced."""
+    p = default_search_params()
+    for name, value in fields.items():
+        if not hasattr(p, name):
+            raise TypeError("rsx_gridmap_search_params has no field " + name)
+        setattr(p, name, value)
+    return p
+
+
+def search_blocks(p):
+    """-> (2K + 1, nbv, nbu): the shape of a job's bounds under the parameters p"""
+    return 2 * max(p.angle_steps, 0) + 1, (2 * max(p.y_cells, 0) + 8) // 8, (2 * max(p.x_cells, 0) + 8) // 8
 
 
 def write_pgm(path, px):
@@ -235,3 +258,42 @@ class GridMap:
         """how well clouds fit the map at poses (n, 6): match with no window (K = U = V = 0) -> results; `score` is the sum of the
         likelihood bytes under the cloud, n_inside the points it was taken over"""
         return self.match(clouds, poses, angle_steps=0, x_cells=0, y_cells=0)
+
+    # ---- the same over a wide window, pruned by bounds (include/rsx.h, rsx_gridmap_search_*) ----
+
+    def prepare_search(self, max_cells=64, stream=None):
+        """snapshot the likelihood plane as it stands for searches with x_cells, y_cells <= max_cells (0 .. 256): a framed copy and the
+        8 x 8 pooled plane.  Later likelihood changes are not seen until the next prepare_search.  Asynchronous on `stream`"""
+        check(self._L.rsx_gridmap_search_prepare(self._h, max_cells, stream))
+
+    def search(self, clouds, priors, return_bounds=False, params=None, **fields):
+        """match over a window of up to 180 rotations and 256 cells either way, with the same winner as the exhaustive rule; clouds
+        and priors as for match; params: a GridmapSearchParams, or its fields by name (angle_steps, angle_step, x_cells, y_cells,
+        min_score) -> results (n,) GRIDMAP_SEARCH_RESULT_DTYPE, and with return_bounds=True also the bounds uint32 [n, 2K + 1, nbv, nbu]"""
+        if params is not None and fields:
+            raise TypeError("give params or its fields, not both")
+        p = params if params is not None else search_params(**fields)
+        xy, off = ragged(clouds, np.float32, 2)
+        n = len(clouds)
+        priors = np.ascontiguousarray(priors, dtype=np.float64).reshape(n, 6)
+        res = np.zeros(n, dtype=GRIDMAP_SEARCH_RESULT_DTYPE)
+        bounds = np.zeros((n,) + search_blocks(p), dtype=np.uint32) if return_bounds else None
+        check(self._L.rsx_gridmap_search_batch(self._h, xy.ctypes.data, off.ctypes.data, n, priors.ctypes.data, C.byref(p), res.ctypes.data,
+                                               bounds.ctypes.data if return_bounds else None))
+        return (res, bounds) if return_bounds else res
+
+    def search_device(self, xy, offsets, priors, results, bounds=None, params=None, stream=None, **fields):
+        """the same on torch tensors of the handle's device, as match_device: results uint8 of n * 96 bytes (view it as
+        GRIDMAP_SEARCH_RESULT_DTYPE on the host), bounds (optional) uint32 / int32 of n (2K + 1) nbv nbu elements.  Asynchronous on
+        `stream`; a job above the cap gets GRIDMAP_MATCH_STATUS_POINTS"""
+        if params is not None and fields:
+            raise TypeError("give params or its fields, not both")
+        p = params if params is not None else search_params(**fields)
+        n = offsets.numel() - 1
+        assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and priors.is_contiguous()
+        assert priors.numel() == 6 * n and results.is_contiguous() and results.numel() * results.element_size() == n * GRIDMAP_SEARCH_RESULT_DTYPE.itemsize
+        if bounds is not None:
+            nk, nbv, nbu = search_blocks(p)
+            assert bounds.is_contiguous() and bounds.element_size() == 4 and bounds.numel() == n * nk * nbv * nbu
+        check(self._L.rsx_gridmap_search_batch_device(self._h, xy.data_ptr(), offsets.data_ptr(), xy.stride(0), n, priors.data_ptr(), C.byref(p),
+                                                      results.data_ptr(), bounds.data_ptr() if bounds is not None else None, stream))
