@@ -1470,6 +1470,94 @@ int rsx_gridmap_search_batch_device(rsx_gridmap *h, const float *d_xy, const int
                                     const double *d_priors, const rsx_gridmap_search_params *params, rsx_gridmap_search_result *d_results,
                                     uint32_t *d_bounds, void *stream);
 
+/* ---- the pose below the cell (csrc/gridrefine.hip): rsx_gridmap_match_* and rsx_gridmap_search_* stop at the grid, a whole-cell shift
+ * and a whole rotation step.  This refines such a pose on the bilinearly interpolated likelihood plane: Gauss-Newton with
+ * Levenberg-Marquardt damping and an accept test (Hector SLAM's matcher; the stage that Olson's and Cartographer's matchers put
+ * behind the correlative one).  None of this is in the reference checkout: the rule below is restated in tests/gridrefine_np.py,
+ * which is the arithmetic contract -- parity unpinned; the records equal the restatement's byte for byte.
+ * A job is rsx_gridmap_match_*'s: the points [offsets[i], offsets[i + 1]) of a float x, y array, at most
+ * RSX_GRIDMAP_MATCH_MAX_POINTS, and a prior of six doubles r00 r01 tx r10 r11 ty -- typically the transform of a match or search
+ * record.  The plane L is the handle's likelihood plane, uint8, cells outside the map reading 0.  All arithmetic is fp64 on plain
+ * operations, nothing fused.
+ * ONE EVALUATION at a pose (r00 r01 tx r10 r11 ty).  A point with a non-finite x or y is skipped entirely.  Every other point (x, y):
+ *   1. rx = r00 x + r01 y, ry = r10 x + r11 y
+ *   2. fx = ((rx + tx) - origin_x) inv_res, fy = ((ry + ty) - origin_y) inv_res, inv_res = 1.0 / resolution made on the host
+ *   3. the point is PLACED iff fx >= -64 && fx < width + 64 && fy >= -64 && fy < height + 64 (step 4 of the matching rule)
+ *   4. a finite point that is not placed contributes r = 255, M = 0 and a zero Jacobian (gx = gy = jt = 0): what it would read deep in
+ *      the zero frame, so that the cost stays comparable between poses
+ *   5. placed: samples sit at cell centres: px = fx - 0.5, py = fy - 0.5, i0 = floor(px), j0 = floor(py), a = px - i0, b = py - j0
+ *   6. l00 = L[j0][i0], l01 = L[j0][i0 + 1], l10 = L[j0 + 1][i0], l11 = L[j0 + 1][i0 + 1], as doubles
+ *   7. top = (1 - a) l00 + a l01, bot = (1 - a) l10 + a l11, M = (1 - b) top + b bot
+ *   8. gx = (1 - b)(l01 - l00) + b (l11 - l10), gy = (1 - a)(l10 - l00) + a (l11 - l01)
+ *   9. jt = (gy rx - gx ry) inv_res: the rotation is about the sensor's position, in the map frame
+ *  10. r = 255 - M
+ * The eleven sums: cost = sum r r; score = sum M; g = sum (gx r, gy r, jt r); H = sum (gx gx, gx gy, gx jt, gy gy, gy jt, jt jt).
+ * ORDER of every sum (part of the contract): partial p[t], t = 0 .. 255, is the sequential sum over points t, t + 256, ... of the
+ * job in that order, starting from 0.0; the total is the balanced adjacent tree over the 256 partials, a[i] = a[2 i] + a[2 i + 1]
+ * eight times.
+ * THE LOOP.  Evaluate at the prior: cost_initial, score_initial.  lambda = damping.  While evaluations < max_evaluations:
+ *   1. a_ii = H_ii (1 + lambda); the off-diagonals stay H's
+ *   2. solve a delta = g by LDL^T written out, no square root:
+ *        d0 = a00; l10 = a01 / d0; l20 = a02 / d0; d1 = a11 - l10 a01; e = a12 - l20 a01; l21 = e / d1; d2 = (a22 - l20 a02) - l21 e;
+ *      each pivot must be > 0 as it is formed (a NaN fails): otherwise status SINGULAR, stop;
+ *        z0 = g0; z1 = g1 - l10 z0; z2 = (g2 - l20 z0) - l21 z1; w_i = z_i / d_i;
+ *        delta2 = w2; delta1 = w1 - l21 delta2; delta0 = (w0 - l10 delta1) - l20 delta2
+ *   3. clamp delta0 and delta1 to +- max_shift_step (cells), delta2 to +- max_rotation_step, each by two comparisons (v > m ? m : v,
+ *      then v < -m ? -m : v: a NaN passes through, its trial is rejected)
+ *   4. the trial pose: tx' = tx + delta0 resolution, ty' = ty + delta1 resolution; (cs, sn) = the fixed polynomials of the deskewing
+ *      model (csrc/mocomp_dev.h) at delta2; r00' = cs r00 - sn r10, r01' = cs r01 - sn r11, r10' = sn r00 + cs r10, r11' = sn r01 + cs r11
+ *   5. evaluate at the trial pose
+ *   6. cost' < cost: ACCEPT -- pose, sums and counts become the trial's, accepted += 1, lambda = max(lambda / 10, 1e-9); stop as
+ *      converged if max(|delta0|, |delta1|) < shift_tolerance && |delta2| < rotation_tolerance
+ *   7. otherwise lambda = 10 lambda; stop as converged if lambda > 1e6: nothing better is within reach
+ * When the budget runs out first the status is MAX.  The returned pose is the last accepted one, so cost <= cost_initial always;
+ * with nothing accepted the returned transform is the prior, bit for bit.
+ * Status: RSX_GRIDMAP_MATCH_STATUS_TRANSFORM, a non-finite prior: the job is skipped, its record zero but for the status.  _POINTS
+ * (device entry only; the host entry refuses the batch): more than the cap of points, treated like _TRANSFORM.  _EMPTY:
+ * score_initial == 0: one evaluation, the prior is returned.  RSX_GRIDMAP_REFINE_STATUS_SINGULAR, _MAX: as above.  0: converged.
+ * The Hessian's units are likelihood (the plane's byte) per cell (x, y) and per radian, multiplied in pairs: it is the curvature of
+ * the cost at the returned pose, which a pose graph would weigh the constraint by.  It is NOT a calibrated covariance.
+ * One launch per call whatever the batch: one workgroup of 256 threads per job runs the whole iteration; no atomics, no host round
+ * trip.  Throughput comes from the jobs of a batch. */
+
+#define RSX_GRIDMAP_REFINE_STATUS_SINGULAR 16
+#define RSX_GRIDMAP_REFINE_STATUS_MAX 32
+
+typedef struct {
+  double damping;            /* the first lambda; > 0 and finite (1e-3) */
+  double max_shift_step;     /* [cells] a step's |delta0|, |delta1| at the most; in (0, 8] (1.0) */
+  double max_rotation_step;  /* [rad] a step's |delta2| at the most; in (0, 0.5], the polynomials' range (0.02) */
+  double shift_tolerance;    /* [cells] >= 0 and finite (1e-3) */
+  double rotation_tolerance; /* [rad] >= 0 and finite (1e-5) */
+  int32_t max_evaluations;   /* 1 .. 64 (32) */
+  int32_t reserved;          /* 0 */
+} rsx_gridmap_refine_params; /* 48 bytes */
+
+typedef struct {
+  double transform[6];       /* r00 r01 tx r10 r11 ty: the returned pose */
+  double hessian[6];         /* H00 H01 H02 H11 H12 H22, undamped, at the returned pose */
+  double cost_initial, cost; /* sum r r at the prior and at the returned pose */
+  double score_initial, score; /* sum M at the prior and at the returned pose */
+  int32_t evaluations, accepted;
+  int32_t n_points;          /* points placed at the returned pose */
+  int32_t n_inside;          /* of those, floor(fx), floor(fy) inside the map */
+  int32_t status;            /* RSX_GRIDMAP_MATCH_STATUS_* | RSX_GRIDMAP_REFINE_STATUS_* */
+  int32_t reserved;          /* 0 */
+} rsx_gridmap_refine_result; /* 152 bytes */
+
+/* a violated rule of rsx_gridmap_refine_params gives RSX_ERR_BAD_ARG in every entry that takes the struct (NULL = the defaults),
+ * judged before the handle or the device is looked at */
+int rsx_gridmap_refine_default_params(rsx_gridmap_refine_params *p);
+/* n_jobs jobs against the likelihood plane.  Host buffers, synchronous.  The offsets are checked, a job above the cap refuses the
+ * batch; before any likelihood exists the call is RSX_ERR_BAD_ARG and touches nothing. */
+int rsx_gridmap_refine_batch(rsx_gridmap *h, const float *xy, const int64_t *offsets, int32_t n_jobs, const double *priors,
+                             const rsx_gridmap_refine_params *params, rsx_gridmap_refine_result *out_results);
+/* device buffers, asynchronous on `stream`: one launch, no allocation, no host synchronisation; point_stride >= 2 as for
+ * rsx_gridmap_match_batch_device; the offsets are trusted; a job above the cap gets RSX_GRIDMAP_MATCH_STATUS_POINTS. */
+int rsx_gridmap_refine_batch_device(rsx_gridmap *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride, int32_t n_jobs,
+                                    const double *d_priors, const rsx_gridmap_refine_params *params, rsx_gridmap_refine_result *d_results,
+                                    void *stream);
+
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;
  * SURVEY 8f rank 3): polar -> Cartesian image, ORB-style binary descriptors at the keypoints, brute-force Hamming

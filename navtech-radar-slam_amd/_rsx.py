@@ -228,6 +228,23 @@ GRIDMAP_SEARCH_RESULT_DTYPE = np.dtype([("transform", "<f8", 6), ("k", "<i4"), (
                                         ("n_refined", "<i4"), ("reserved", "<i4")])
 
 
+class GridmapRefineParams(C.Structure):
+    _fields_ = [("damping", C.c_double), ("max_shift_step", C.c_double), ("max_rotation_step", C.c_double), ("shift_tolerance", C.c_double),
+                ("rotation_tolerance", C.c_double), ("max_evaluations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GridmapRefineResult(C.Structure):
+    _fields_ = [("transform", C.c_double * 6), ("hessian", C.c_double * 6), ("cost_initial", C.c_double), ("cost", C.c_double),
+                ("score_initial", C.c_double), ("score", C.c_double), ("evaluations", C.c_int32), ("accepted", C.c_int32),
+                ("n_points", C.c_int32), ("n_inside", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+GRIDMAP_REFINE_STATUS_SINGULAR, GRIDMAP_REFINE_STATUS_MAX = 16, 32  # RSX_GRIDMAP_REFINE_STATUS_*
+GRIDMAP_REFINE_RESULT_DTYPE = np.dtype([("transform", "<f8", 6), ("hessian", "<f8", 6), ("cost_initial", "<f8"), ("cost", "<f8"), ("score_initial", "<f8"),
+                                        ("score", "<f8"), ("evaluations", "<i4"), ("accepted", "<i4"), ("n_points", "<i4"), ("n_inside", "<i4"),
+                                        ("status", "<i4"), ("reserved", "<i4")])
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -318,6 +335,7 @@ SYMBOLS = [
     "rsx_gridmap_match_default_params", "rsx_gridmap_likelihood_update", "rsx_gridmap_likelihood_set", "rsx_gridmap_likelihood_device",
     "rsx_gridmap_likelihood_read", "rsx_gridmap_match_batch", "rsx_gridmap_match_batch_device",
     "rsx_gridmap_search_default_params", "rsx_gridmap_search_prepare", "rsx_gridmap_search_batch", "rsx_gridmap_search_batch_device",
+    "rsx_gridmap_refine_default_params", "rsx_gridmap_refine_batch", "rsx_gridmap_refine_batch_device",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
     "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
     "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
@@ -522,6 +540,9 @@ def lib():
         L.rsx_gridmap_search_prepare.argtypes = [vp, i32, vp]
         L.rsx_gridmap_search_batch.argtypes = [vp, vp, vp, i32, vp, C.POINTER(GridmapSearchParams), vp, vp]
         L.rsx_gridmap_search_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(GridmapSearchParams), vp, vp, vp]
+        L.rsx_gridmap_refine_default_params.argtypes = [C.POINTER(GridmapRefineParams)]
+        L.rsx_gridmap_refine_batch.argtypes = [vp, vp, vp, i32, vp, C.POINTER(GridmapRefineParams), vp]
+        L.rsx_gridmap_refine_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(GridmapRefineParams), vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
         L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]

@@ -1,5 +1,6 @@
 // gridmap.h -- the handle of the radar grid map, shared by gridmap.hip (the planes: accumulate, read, render) and gridmatch.hip (the
-// likelihood plane and the correlative matching that reads it) and gridsearch.hip (the wide-window search over a snapshot of it).
+// likelihood plane and the correlative matching that reads it), gridsearch.hip (the wide-window search over a snapshot of it) and
+// gridrefine.hip (the sub-cell refinement that interpolates the likelihood plane).
 #pragma once
 #include <cstdint>
 #include <mutex>
@@ -50,5 +51,7 @@ struct rsx_gridmap {
   rsx::DevBuf s_frame;          // uint8 [8 s_ch][8 s_cw]: a copy of the likelihood plane in a zeroed frame of s_margin cells
   rsx::DevBuf s_pool;           // uint8 [8][8][s_ch][s_cw]: the 8 x 8 pooled plane, de-interleaved by phase
   rsx::DevBuf s_bounds, s_aux;  // workspace of a search: the bounds of a call that asked for none; seeds, prior scores, keys, counts
+  // ---- gridrefine.hip: nothing below is allocated before the first rsx_gridmap_refine_batch ----
+  rsx::DevBuf r_xy, r_off, r_tf, r_res;  // staging of rsx_gridmap_refine_batch: points, offsets, priors, results
   uint8_t *like_origin() const { return like.as<uint8_t>() + (size_t)rsx::GRIDMAP_LIKE_MARGIN * like_pitch() + rsx::GRIDMAP_LIKE_MARGIN; }  // cell (0, 0)
 };

@@ -5,8 +5,8 @@ import ctypes as C
 import numpy as np
 
 from . import synth
-from ._rsx import (GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GRIDMAP_SEARCH_RESULT_DTYPE, GridmapMatchParams, GridmapParams,
-                   GridmapSearchParams, check, lib)
+from ._rsx import (GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GRIDMAP_REFINE_RESULT_DTYPE, GRIDMAP_SEARCH_RESULT_DTYPE,
+                   GridmapMatchParams, GridmapParams, GridmapRefineParams, GridmapSearchParams, check, lib)
 from .cfear import ragged
 
 
@@ -65,6 +65,31 @@ def search_params(**fields):
 def search_blocks(p):
     """-> (2K + 1, nbv, nbu): the shape of a job's bounds under the parameters p"""
     return 2 * max(p.angle_steps, 0) + 1, (2 * max(p.y_cells, 0) + 8) // 8, (2 * max(p.x_cells, 0) + 8) // 8
+
+
+def default_refine_params():
+    """damping 1e-3, steps of at most 1 cell and 0.02 rad, tolerances 1e-3 cells and 1e-5 rad, at most 32 evaluations."""
+    p = GridmapRefineParams()
+    check(lib().rsx_gridmap_refine_default_params(C.byref(p)))
+    return p
+
+
+def refine_params(**fields):
+    """default_refine_params() with the given fields replaced."""
+    p = default_refine_params()
+    for name, value in fields.items():
+        if not hasattr(p, name):
+            raise TypeError("rsx_gridmap_refine_params has no field " + name)
+        setattr(p, name, value)
+    return p
+
+
+def prior_transforms(priors, n):
+    """(n, 6) float64 from an (n, 6) array, or from the record array of match or search, whose `transform` is taken"""
+    priors = np.asarray(priors)
+    if priors.dtype.names and "transform" in priors.dtype.names:
+        priors = priors["transform"]
+    return np.ascontiguousarray(priors, dtype=np.float64).reshape(n, 6)
 
 
 def write_pgm(path, px):
@@ -297,3 +322,33 @@ class GridMap:
             assert bounds.is_contiguous() and bounds.element_size() == 4 and bounds.numel() == n * nk * nbv * nbu
         check(self._L.rsx_gridmap_search_batch_device(self._h, xy.data_ptr(), offsets.data_ptr(), xy.stride(0), n, priors.data_ptr(), C.byref(p),
                                                       results.data_ptr(), bounds.data_ptr() if bounds is not None else None, stream))
+
+    # ---- the pose below the cell: Levenberg-Marquardt on the interpolated likelihood plane (include/rsx.h, rsx_gridmap_refine_*) ----
+
+    def refine(self, clouds, priors, params=None, **fields):
+        """clouds as for match; priors: (n, 6) float64, or the records that match or search returned (their `transform` is taken, so
+        gm.refine(clouds, gm.match(clouds, priors)) is the whole chain); params: a GridmapRefineParams, or its fields by name (damping,
+        max_shift_step, max_rotation_step, shift_tolerance, rotation_tolerance, max_evaluations)
+        -> results (n,) GRIDMAP_REFINE_RESULT_DTYPE: the refined transform, the Hessian at it, cost and score before and after"""
+        if params is not None and fields:
+            raise TypeError("give params or its fields, not both")
+        p = params if params is not None else refine_params(**fields)
+        xy, off = ragged(clouds, np.float32, 2)
+        n = len(clouds)
+        priors = prior_transforms(priors, n)
+        res = np.zeros(n, dtype=GRIDMAP_REFINE_RESULT_DTYPE)
+        check(self._L.rsx_gridmap_refine_batch(self._h, xy.ctypes.data, off.ctypes.data, n, priors.ctypes.data, C.byref(p), res.ctypes.data))
+        return res
+
+    def refine_device(self, xy, offsets, priors, results, params=None, stream=None, **fields):
+        """the same on torch tensors of the handle's device, as match_device: priors float64 (n, 6) contiguous, results uint8 of
+        n * 152 bytes (view it as GRIDMAP_REFINE_RESULT_DTYPE on the host).  One launch, asynchronous on `stream`; a job above the cap
+        gets GRIDMAP_MATCH_STATUS_POINTS"""
+        if params is not None and fields:
+            raise TypeError("give params or its fields, not both")
+        p = params if params is not None else refine_params(**fields)
+        n = offsets.numel() - 1
+        assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and priors.is_contiguous()
+        assert priors.numel() == 6 * n and results.is_contiguous() and results.numel() * results.element_size() == n * GRIDMAP_REFINE_RESULT_DTYPE.itemsize
+        check(self._L.rsx_gridmap_refine_batch_device(self._h, xy.data_ptr(), offsets.data_ptr(), xy.stride(0), n, priors.data_ptr(), C.byref(p),
+                                                      results.data_ptr(), stream))
