@@ -1,6 +1,8 @@
 // gridmap.h -- the handle of the radar grid map, shared by gridmap.hip (the planes: accumulate, read, render) and gridmatch.hip (the
 // likelihood plane and the correlative matching that reads it), gridsearch.hip (the wide-window search over a snapshot of it) and
-// gridrefine.hip (the sub-cell refinement that interpolates the likelihood plane).
+// gridrefine.hip (the sub-cell refinement that interpolates the likelihood plane); and the rules that more than one of them judges
+// (the render mode, a window of the map, the missing likelihood plane).  What the three localisers share beyond the handle is in
+// gridloc_host.h (the scaffold of their entries) and gridmatch_dev.h (their device code).
 #pragma once
 #include <cstdint>
 #include <mutex>
@@ -42,7 +44,9 @@ struct rsx_gridmap {
   rsx::DevBuf like;             // uint8 [height + 2 margin][width + 2 margin]: the likelihood plane in its zeroed frame
   bool have_like = false;       // an update or a set has filled it
   rsx::DevBuf volume;           // the score volumes of a call that asked for none (uint32, n_jobs x candidates)
-  rsx::DevBuf m_xy, m_off, m_tf, m_res;  // staging of rsx_gridmap_match_batch: points, offsets, priors, results
+  // staging of the host entries of match, search and refine (gridloc_host.h): points, offsets, priors, results.  One set: every
+  // one of them synchronises before it returns
+  rsx::DevBuf m_xy, m_off, m_tf, m_res;
   int64_t like_pitch() const { return (int64_t)p.width + 2 * rsx::GRIDMAP_LIKE_MARGIN; }
   size_t like_bytes() const { return (size_t)like_pitch() * ((size_t)p.height + 2 * rsx::GRIDMAP_LIKE_MARGIN); }
   // ---- gridsearch.hip: nothing below is allocated before the first rsx_gridmap_search_prepare ----
@@ -51,7 +55,23 @@ struct rsx_gridmap {
   rsx::DevBuf s_frame;          // uint8 [8 s_ch][8 s_cw]: a copy of the likelihood plane in a zeroed frame of s_margin cells
   rsx::DevBuf s_pool;           // uint8 [8][8][s_ch][s_cw]: the 8 x 8 pooled plane, de-interleaved by phase
   rsx::DevBuf s_bounds, s_aux;  // workspace of a search: the bounds of a call that asked for none; seeds, prior scores, keys, counts
-  // ---- gridrefine.hip: nothing below is allocated before the first rsx_gridmap_refine_batch ----
-  rsx::DevBuf r_xy, r_off, r_tf, r_res;  // staging of rsx_gridmap_refine_batch: points, offsets, priors, results
   uint8_t *like_origin() const { return like.as<uint8_t>() + (size_t)rsx::GRIDMAP_LIKE_MARGIN * like_pitch() + rsx::GRIDMAP_LIKE_MARGIN; }  // cell (0, 0)
 };
+
+namespace rsx {
+
+inline int check_window(const rsx_gridmap *h, int32_t x, int32_t y, int32_t w, int32_t hgt) {
+  if (x < 0 || y < 0 || w < 1 || hgt < 1 || x > h->p.width - w || y > h->p.height - hgt)
+    return fail(RSX_ERR_BAD_ARG, "window %d x %d at (%d, %d) outside the %d x %d map", w, hgt, x, y, h->p.width, h->p.height);
+  return RSX_OK;
+}
+
+inline int check_render(int32_t mode, int32_t min_observations) {
+  if (mode != RSX_GRIDMAP_MEAN && mode != RSX_GRIDMAP_HITS) return fail(RSX_ERR_BAD_ARG, "unknown render mode %d", mode);
+  if (min_observations < 1) return fail(RSX_ERR_BAD_ARG, "min_observations %d < 1", min_observations);
+  return RSX_OK;
+}
+
+inline int no_likelihood() { return fail(RSX_ERR_BAD_ARG, "no likelihood plane yet: rsx_gridmap_likelihood_update or rsx_gridmap_likelihood_set first"); }
+
+}  // namespace rsx

@@ -238,6 +238,8 @@ __global__ __launch_bounds__(THREADS) void gm_render(const unsigned *__restrict_
 
 }  // namespace
 
+using rsx::check_render;  // (gridmap.h)
+using rsx::check_window;
 using rsx::fail;
 
 namespace {
@@ -279,18 +281,6 @@ Geometry geometry_of(const rsx_gridmap_params &p, int rows, int cols) {
 int check_batch(const rsx_gridmap *h, int32_t n_images, int64_t image_stride_bytes, int32_t row_stride, int32_t col_offset) {
   if (n_images < 0 || n_images > MAX_IMAGES) return fail(RSX_ERR_BAD_ARG, "n_images %d outside 0 .. %d", n_images, MAX_IMAGES);
   return rsx::check_polar_layout(h->rows, h->cols, n_images, image_stride_bytes, row_stride, col_offset);
-}
-
-int check_window(const rsx_gridmap *h, int32_t x, int32_t y, int32_t w, int32_t hgt) {
-  if (x < 0 || y < 0 || w < 1 || hgt < 1 || x > h->p.width - w || y > h->p.height - hgt)
-    return fail(RSX_ERR_BAD_ARG, "window %d x %d at (%d, %d) outside the %d x %d map", w, hgt, x, y, h->p.width, h->p.height);
-  return RSX_OK;
-}
-
-int check_render(int32_t mode, int32_t min_observations) {
-  if (mode != RSX_GRIDMAP_MEAN && mode != RSX_GRIDMAP_HITS) return fail(RSX_ERR_BAD_ARG, "unknown render mode %d", mode);
-  if (min_observations < 1) return fail(RSX_ERR_BAD_ARG, "min_observations %d < 1", min_observations);
-  return RSX_OK;
 }
 
 // n device images at their transforms into the planes: one launch, nothing read on the host

@@ -15,9 +15,11 @@
 //              unaligned 32-bit read (neighbouring slots read neighbouring bytes; the plane is served by L2), and they are added as
 //              two pairs of 16-bit sums that are flushed every 256 points, before they can overflow; eight reads are in flight
 //              per thread (the trip count is known before the loop: an exit test inside it costs a wait per read).  The parts are added
-//              through LDS; with S above 256 a thread walks several slots in turn.
+//              through LDS; with S above 256 a thread walks several slots in turn (slot_sums of gridmatch_dev.h, which the
+//              search's gms_bound shares).
 //   gmm_pick   one workgroup per job: the winner by a 64-bit key that carries the tie order and the linear index, then the
 //              runner-up and, from steps 1 - 5 again at the winner's k, the counts; thread 0 writes the record.
+// The two batch entries are the scaffold of gridloc_host.h behind their own rules; the rules that gridmap.hip judges too are in gridmap.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,27 +27,27 @@
 #include <cstring>
 #include <mutex>
 
+#include "gridloc_host.h"
 #include "gridmap.h"
 #include "gridmatch_dev.h"
-#include "ragged_host.h"
 
 #pragma STDC FP_CONTRACT OFF
 
 namespace {
 
+using rsx::check_render;  // (gridmap.h)
 using rsx::fail;
+using rsx::no_likelihood;
 using rsx::GRIDMAP_LIKE_MARGIN;
-using namespace rsx::gridmatch_dev;  // NT, MatchGeo, finite6, place, job_points, walk, block_max
+using namespace rsx::gridmatch_dev;  // NT, PLACE, MatchGeo, Rotations, place, job_points, skip_status, slot_sums, count_at, winner_transform, block_max
+namespace gridloc = rsx::gridloc;
 
 constexpr int MAX_POINTS = RSX_GRIDMAP_MATCH_MAX_POINTS;
-constexpr int MAX_K = 64, MAX_UV = 32, PLACE = 64;  // PLACE: how far outside the map a point is still placed (cells)
-constexpr size_t VOLUME_STAGE = (size_t)64 << 20;   // rsx_gridmap_match_batch: the bytes of score volume staged per sub-batch
+constexpr int MAX_K = 64, MAX_UV = 32;
 static_assert(PLACE + MAX_UV + 3 < GRIDMAP_LIKE_MARGIN, "a shifted read must stay in the frame");
 static_assert((MAX_POINTS & (MAX_POINTS - 1)) == 0, "");
 
-struct Tables {
-  float c[2 * MAX_K + 1], s[2 * MAX_K + 1];  // [k + K]
-};
+using Tables = Rotations<MAX_K>;
 
 __global__ __launch_bounds__(NT) void gmm_score(const float *__restrict__ xy, int64_t stride, const int64_t *__restrict__ offsets,
                                                 const double *__restrict__ priors, Tables tab, MatchGeo g,
@@ -53,13 +55,13 @@ __global__ __launch_bounds__(NT) void gmm_score(const float *__restrict__ xy, in
   __shared__ unsigned cell[MAX_POINTS];  // byte offset of the point's cell in the framed plane
   __shared__ unsigned red[NT * 4];
   const int tid = threadIdx.x;
-  const int nk = 2 * g.K + 1, nv = 2 * g.V + 1, nu = 2 * g.U + 1, groups = (nu + 3) >> 2;
+  const int nk = 2 * g.K + 1, nv = 2 * g.V + 1, nu = 2 * g.U + 1;
   const int job = (int)(blockIdx.x / (unsigned)nk), kk = (int)(blockIdx.x % (unsigned)nk);
   unsigned *out = volume + ((int64_t)job * nk + kk) * nv * nu;
   const double *t = priors + 6 * (int64_t)job;
   int64_t first;
   const int64_t n64 = job_points(offsets, job, &first);
-  if (n64 > MAX_POINTS || !finite6(t)) {  // (workgroup-uniform) a skipped job: its scores are 0
+  if (skip_status(t, n64)) {  // (workgroup-uniform) a skipped job: its scores are 0
     for (int i = tid; i < nv * nu; i += NT) out[i] = 0u;
     return;
   }
@@ -75,34 +77,9 @@ __global__ __launch_bounds__(NT) void gmm_score(const float *__restrict__ xy, in
                   : nowhere;
   }
   __syncthreads();
-  const int slots = nv * groups;
-  const int parts = slots < NT ? NT / slots : 1;
-  if (parts > 1) {  // (workgroup-uniform) every slot has a thread in each part
-    unsigned sum[4] = {0u, 0u, 0u, 0u};
-    const int part = tid / slots, slot = tid - part * slots;
-    const int vi = slot / groups, gi = slot - vi * groups;
-    if (part < parts) walk(plane, cell, n, part, parts, (unsigned)((vi - g.V) * (int)g.pitch + (4 * gi - g.U)), sum);
-#pragma unroll
-    for (int j = 0; j < 4; j++) red[4 * tid + j] = sum[j];
-    __syncthreads();
-    if (tid < slots) {
-      for (int q = 1; q < parts; q++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) sum[j] += red[4 * (tid + q * slots) + j];
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * gi + j < nu) out[vi * nu + 4 * gi + j] = sum[j];
-    }
-  } else {
-    for (int slot = tid; slot < slots; slot += NT) {
-      unsigned sum[4] = {0u, 0u, 0u, 0u};
-      const int vi = slot / groups, gi = slot - vi * groups;
-      walk(plane, cell, n, 0, 1, (unsigned)((vi - g.V) * (int)g.pitch + (4 * gi - g.U)), sum);
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * gi + j < nu) out[vi * nu + 4 * gi + j] = sum[j];
-    }
-  }
+  slot_sums(
+      plane, cell, red, n, nv, nu, [&](int vi, int gi) { return (unsigned)((vi - g.V) * (int)g.pitch + (4 * gi - g.U)); },
+      [&](int vi, int ui, unsigned sum) { out[vi * nu + ui] = sum; });
 }
 
 __global__ __launch_bounds__(NT) void gmm_pick(const float *__restrict__ xy, int64_t stride, const int64_t *__restrict__ offsets,
@@ -119,7 +96,7 @@ __global__ __launch_bounds__(NT) void gmm_pick(const float *__restrict__ xy, int
   const int64_t n64 = job_points(offsets, job, &first);
   rsx_gridmap_match_result r;
   memset(&r, 0, sizeof(r));
-  const int skipped = (finite6(t) ? 0 : RSX_GRIDMAP_MATCH_STATUS_TRANSFORM) | (n64 > MAX_POINTS ? RSX_GRIDMAP_MATCH_STATUS_POINTS : 0);
+  const int skipped = skip_status(t, n64);
   if (skipped) {  // (workgroup-uniform)
     r.status = skipped;
     if (tid == 0) results[job] = r;
@@ -151,17 +128,7 @@ __global__ __launch_bounds__(NT) void gmm_pick(const float *__restrict__ xy, int
   __syncthreads();
   const double c = (double)tab.c[bk + g.K], s = (double)tab.s[bk + g.K];
   const double t6[6] = {t[0], t[1], t[2], t[3], t[4], t[5]};
-  unsigned placed = 0u, inside = 0u;
-  for (int i = tid; i < (int)n64; i += NT) {
-    const float *p = xy + (first + i) * stride;
-    int ix, iy;
-    if (place(g, PLACE, t6, c, s, (double)p[0], (double)p[1], &ix, &iy)) {
-      placed++;
-      inside += (ix + bu >= 0 && ix + bu < g.W && iy + bv >= 0 && iy + bv < g.H) ? 1u : 0u;
-    }
-  }
-  atomicAdd(&n_placed, placed);  // (LDS)
-  atomicAdd(&n_inside, inside);
+  count_at(g, PLACE, xy, stride, first, (int)n64, t6, c, s, bu, bv, &n_placed, &n_inside);
   __syncthreads();
   if (tid != 0) return;
   r.score = (unsigned)(key >> 39);
@@ -169,17 +136,8 @@ __global__ __launch_bounds__(NT) void gmm_pick(const float *__restrict__ xy, int
   r.score_runner_up = second;
   r.k = bk, r.u = bu, r.v = bv;
   r.n_points = (int)n_placed, r.n_inside = (int)n_inside;
-  if (r.score == 0u) {
-    r.status = RSX_GRIDMAP_MATCH_STATUS_EMPTY;
-    for (int q = 0; q < 6; q++) r.transform[q] = t6[q];
-  } else {
-    r.transform[0] = t6[0] * c + t6[1] * s;
-    r.transform[1] = t6[1] * c - t6[0] * s;
-    r.transform[2] = t6[2] + (double)bu * g.res;
-    r.transform[3] = t6[3] * c + t6[4] * s;
-    r.transform[4] = t6[4] * c - t6[3] * s;
-    r.transform[5] = t6[5] + (double)bv * g.res;
-  }
+  if (r.score == 0u) r.status = RSX_GRIDMAP_MATCH_STATUS_EMPTY;
+  winner_transform(r.transform, r.score != 0u, t6, c, s, bu, bv, g.res);
   results[job] = r;
 }
 
@@ -205,11 +163,7 @@ __global__ __launch_bounds__(NT) void gmm_likelihood(const unsigned *__restrict_
 }
 
 int check_params(const rsx_gridmap_match_params &p) {
-  if (p.angle_steps < 0 || p.angle_steps > MAX_K) return fail(RSX_ERR_BAD_ARG, "angle_steps %d outside 0 .. %d", p.angle_steps, MAX_K);
-  if (p.angle_steps > 0 && (!(p.angle_step > 0.0) || !std::isfinite(p.angle_step)))
-    return fail(RSX_ERR_BAD_ARG, "angle_step must be positive and finite when angle_steps > 0");
-  if (p.x_cells < 0 || p.x_cells > MAX_UV) return fail(RSX_ERR_BAD_ARG, "x_cells %d outside 0 .. %d", p.x_cells, MAX_UV);
-  if (p.y_cells < 0 || p.y_cells > MAX_UV) return fail(RSX_ERR_BAD_ARG, "y_cells %d outside 0 .. %d", p.y_cells, MAX_UV);
+  RSX_TRY(gridloc::check_window_params(p, MAX_K, MAX_UV));
   if (p.reserved != 0) return fail(RSX_ERR_BAD_ARG, "reserved must be 0");
   return RSX_OK;
 }
@@ -222,12 +176,6 @@ int resolve(const rsx_gridmap_match_params *params, rsx_gridmap_match_params &dp
 
 size_t candidates(const rsx_gridmap_match_params &p) { return (size_t)(2 * p.angle_steps + 1) * (2 * p.y_cells + 1) * (2 * p.x_cells + 1); }
 
-int check_render(int32_t mode, int32_t min_observations) {
-  if (mode != RSX_GRIDMAP_MEAN && mode != RSX_GRIDMAP_HITS) return fail(RSX_ERR_BAD_ARG, "unknown render mode %d", mode);
-  if (min_observations < 1) return fail(RSX_ERR_BAD_ARG, "min_observations %d < 1", min_observations);
-  return RSX_OK;
-}
-
 // the framed plane, allocated and zeroed at the first call that needs it (the caller holds h->mu and has entered s)
 int need_plane(rsx_gridmap *h, hipStream_t s) {
   if (h->like.p) return RSX_OK;
@@ -236,28 +184,21 @@ int need_plane(rsx_gridmap *h, hipStream_t s) {
   return RSX_OK;
 }
 
-int no_likelihood() { return fail(RSX_ERR_BAD_ARG, "no likelihood plane yet: rsx_gridmap_likelihood_update or rsx_gridmap_likelihood_set first"); }
-
-// the two launches behind both entries (the caller holds h->mu and has entered s): n jobs, their volume at d_volume
-int launch(rsx_gridmap *h, const float *d_xy, const int64_t *d_off, int32_t stride, int n, const double *d_priors, const rsx_gridmap_match_params &p,
-           rsx_gridmap_match_result *d_results, uint32_t *d_volume, hipStream_t s) {
-  Tables tab;
-  memset(&tab, 0, sizeof(tab));
-  for (int k = -p.angle_steps; k <= p.angle_steps; k++) {  // fp64, rounded once
-    const double ang = (double)k * p.angle_step;
-    tab.c[k + p.angle_steps] = (float)std::cos(ang);
-    tab.s[k + p.angle_steps] = (float)std::sin(ang);
-  }
-  MatchGeo g{};
-  g.ox = h->p.origin_x, g.oy = h->p.origin_y, g.res = h->p.resolution, g.inv_res = 1.0 / h->p.resolution;
-  g.W = h->p.width, g.H = h->p.height, g.K = p.angle_steps, g.U = p.x_cells, g.V = p.y_cells;
-  g.pitch = (unsigned)h->like_pitch();
-  const unsigned nk = (unsigned)(2 * p.angle_steps + 1);
-  hipLaunchKernelGGL(gmm_score, dim3((unsigned)n * nk), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, tab, g, h->like.as<uint8_t>(), d_volume);
-  RSX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(gmm_pick, dim3((unsigned)n), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, tab, g, d_volume, d_results);
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
+// the call as gridloc_host.h's scaffold takes it: a score volume of (2K + 1)(2V + 1)(2U + 1) words per job, in h->volume unless the
+// caller gave room, and the two launches
+gridloc::LocCall describe(const rsx_gridmap_match_params &p) {
+  return {gridloc::have_likelihood, candidates(p), &rsx_gridmap::volume, sizeof(rsx_gridmap_match_result),
+          [&p](rsx_gridmap *h, const gridloc::LocJobs &j, void *d_results, uint32_t *d_volume, hipStream_t s) -> int {
+            const Tables tab(p.angle_steps, p.angle_step);
+            const MatchGeo g = gridloc::match_geo(h, p.angle_steps, p.x_cells, p.y_cells, (unsigned)h->like_pitch());
+            const unsigned nk = (unsigned)(2 * p.angle_steps + 1);
+            hipLaunchKernelGGL(gmm_score, dim3((unsigned)j.n * nk), dim3(NT), 0, s, j.xy, j.stride, j.off, j.priors, tab, g, h->like.as<uint8_t>(), d_volume);
+            RSX_HIP(hipGetLastError());
+            hipLaunchKernelGGL(gmm_pick, dim3((unsigned)j.n), dim3(NT), 0, s, j.xy, j.stride, j.off, j.priors, tab, g, d_volume,
+                               static_cast<rsx_gridmap_match_result *>(d_results));
+            RSX_HIP(hipGetLastError());
+            return RSX_OK;
+          }};
 }
 
 }  // namespace
@@ -322,8 +263,7 @@ int rsx_gridmap_likelihood_device(rsx_gridmap *h, uint8_t **d_likelihood, int64_
 int rsx_gridmap_likelihood_read(rsx_gridmap *h, int32_t x, int32_t y, int32_t w, int32_t hgt, uint8_t *out) try {
   if (!out) return fail(RSX_ERR_BAD_ARG, "null out");
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  if (x < 0 || y < 0 || w < 1 || hgt < 1 || x > h->p.width - w || y > h->p.height - hgt)
-    return fail(RSX_ERR_BAD_ARG, "window %d x %d at (%d, %d) outside the %d x %d map", w, hgt, x, y, h->p.width, h->p.height);
+  RSX_TRY(rsx::check_window(h, x, y, w, hgt));
   std::lock_guard<std::mutex> lk(h->mu);
   if (!h->have_like) return no_likelihood();
   RSX_HIP(hipSetDevice(h->device));
@@ -338,62 +278,19 @@ int rsx_gridmap_likelihood_read(rsx_gridmap *h, int32_t x, int32_t y, int32_t w,
 int rsx_gridmap_match_batch_device(rsx_gridmap *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride, int32_t n_jobs,
                                    const double *d_priors, const rsx_gridmap_match_params *params, rsx_gridmap_match_result *d_results,
                                    uint32_t *d_scores, void *stream) try {
-  // (the arguments are judged before the handle is looked at: their rules need no device)
-  if (!d_xy || !d_offsets || !d_priors || !d_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (point_stride < 2) return fail(RSX_ERR_BAD_ARG, "point_stride %d below 2", point_stride);
+  RSX_TRY(gridloc::check_args(d_xy, d_offsets, d_priors, d_results, n_jobs, point_stride));
   rsx_gridmap_match_params dp;
   RSX_TRY(resolve(params, dp));
   if ((int64_t)n_jobs * (2 * dp.angle_steps + 1) > 0x7fffffffll) return fail(RSX_ERR_BAD_ARG, "n_jobs %d times %d rotations is 2^31 or more", n_jobs, 2 * dp.angle_steps + 1);
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->have_like) return no_likelihood();
-  if (n_jobs == 0) return RSX_OK;
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  RSX_TRY(h->order.enter(s));
-  if (!d_scores) {
-    RSX_TRY(h->volume.reserve((size_t)n_jobs * candidates(dp) * sizeof(uint32_t), s, false));
-    d_scores = h->volume.as<uint32_t>();
-  }
-  return launch(h, d_xy, d_offsets, point_stride, n_jobs, d_priors, dp, d_results, d_scores, s);
+  return gridloc::run_device(h, describe(dp), {d_xy, d_offsets, point_stride, n_jobs, d_priors}, d_results, d_scores, stream);
 } RSX_CATCH_ALL
 
 int rsx_gridmap_match_batch(rsx_gridmap *h, const float *xy, const int64_t *offsets, int32_t n_jobs, const double *priors,
                             const rsx_gridmap_match_params *params, rsx_gridmap_match_result *out_results, uint32_t *out_scores) try {
-  // (the arguments are judged before the handle is looked at: their rules need no device)
-  if (!xy || !offsets || !priors || !out_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  RSX_TRY(gridloc::check_args(xy, offsets, priors, out_results, n_jobs, 2));
   rsx_gridmap_match_params dp;
   RSX_TRY(resolve(params, dp));
-  if (n_jobs > 0) {
-    RSX_TRY(rsx::check_offsets(offsets, n_jobs, "rsx_gridmap_match_batch"));
-    for (int32_t i = 0; i < n_jobs; i++)
-      if (offsets[i + 1] - offsets[i] > MAX_POINTS)
-        return fail(RSX_ERR_BAD_ARG, "job %d has %lld points, more than %d", i, (long long)(offsets[i + 1] - offsets[i]), MAX_POINTS);
-  }
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->have_like) return no_likelihood();
-  if (n_jobs == 0) return RSX_OK;
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  RSX_TRY(h->order.enter(s));
-  const size_t n = (size_t)n_jobs, cand = candidates(dp);
-  RSX_TRY(rsx::stage_up(h->m_xy, xy, (size_t)offsets[n_jobs] * 8, s));
-  RSX_TRY(rsx::stage_up(h->m_off, offsets, (n + 1) * 8, s));
-  RSX_TRY(rsx::stage_up(h->m_tf, priors, n * 48, s));
-  RSX_TRY(rsx::stage_room(h->m_res, n * sizeof(rsx_gridmap_match_result), s));
-  // sub-batches bound the staged volume; a job's bytes do not depend on the cut
-  const size_t per = VOLUME_STAGE / (cand * sizeof(uint32_t)), sub = per < n ? per : n;
-  RSX_TRY(rsx::stage_room(h->volume, sub * cand * sizeof(uint32_t), s));
-  for (size_t b0 = 0; b0 < n; b0 += sub) {
-    const size_t nb = n - b0 < sub ? n - b0 : sub;
-    RSX_TRY(launch(h, h->m_xy.as<float>(), h->m_off.as<int64_t>() + b0, 2, (int)nb, h->m_tf.as<double>() + 6 * b0, dp,
-                   h->m_res.as<rsx_gridmap_match_result>() + b0, h->volume.as<uint32_t>(), s));
-    if (out_scores) RSX_TRY(rsx::stage_down(out_scores + b0 * cand, h->volume, nb * cand * sizeof(uint32_t), s));
-  }
-  RSX_TRY(rsx::stage_down(out_results, h->m_res, n * sizeof(rsx_gridmap_match_result), s));
-  RSX_HIP(hipStreamSynchronize(s));
-  return RSX_OK;
+  return gridloc::run_host(h, describe(dp), "rsx_gridmap_match_batch", xy, offsets, n_jobs, priors, out_results, out_scores);
 } RSX_CATCH_ALL
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 //                  thread adds (w0 + w1) + (w2 + w3): the balanced adjacent tree over the 256 partials.
 //   the step       the 3 x 3 solve, the clamp, the pose update and the accept test are computed by every thread from the same sums:
 //                  the same bits in every thread, every branch on them workgroup-uniform, no broadcast.
+// The two batch entries are the scaffold of gridloc_host.h behind their own rules: a call with no side output, so one cut of the batch.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,10 +25,10 @@
 #include <cstring>
 #include <mutex>
 
+#include "gridloc_host.h"
 #include "gridmap.h"
 #include "gridmatch_dev.h"
 #include "mocomp_dev.h"
-#include "ragged_host.h"
 #include "rsx_wave_dev.h"
 
 #pragma STDC FP_CONTRACT OFF
@@ -36,12 +37,12 @@ namespace {
 
 using rsx::fail;
 using rsx::GRIDMAP_LIKE_MARGIN;
-using rsx::gridmatch_dev::finite6;
 using rsx::gridmatch_dev::job_points;
 using rsx::gridmatch_dev::NT;
+using rsx::gridmatch_dev::PLACE;
+using rsx::gridmatch_dev::skip_status;
+namespace gridloc = rsx::gridloc;
 
-constexpr int MAX_POINTS = RSX_GRIDMAP_MATCH_MAX_POINTS;
-constexpr int PLACE = 64;   // how far outside the map a point is still placed (cells)
 constexpr int NS = 11;      // cost, score, g0 g1 g2, H00 H01 H02 H11 H12 H22
 constexpr int DEPTH = 4;    // points of a thread whose reads are in flight together
 constexpr double LAMBDA_MIN = 1e-9, LAMBDA_MAX = 1e6;
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(NT) void gmr_refine(const float *__restrict__ xy, i
   const int64_t n64 = job_points(offsets, job, &first);
   rsx_gridmap_refine_result r;
   memset(&r, 0, sizeof(r));
-  const int skipped = (finite6(t) ? 0 : RSX_GRIDMAP_MATCH_STATUS_TRANSFORM) | (n64 > MAX_POINTS ? RSX_GRIDMAP_MATCH_STATUS_POINTS : 0);
+  const int skipped = skip_status(t, n64);
   if (skipped) {  // (workgroup-uniform)
     r.status = skipped;
     if (tid == 0) results[job] = r;
@@ -260,19 +261,20 @@ int resolve(const rsx_gridmap_refine_params *params, rsx_gridmap_refine_params &
   return check_params(dp);
 }
 
-int no_likelihood() { return fail(RSX_ERR_BAD_ARG, "no likelihood plane yet: rsx_gridmap_likelihood_update or rsx_gridmap_likelihood_set first"); }
-
-// the one launch behind both entries (the caller holds h->mu, has entered s and has seen h->have_like)
-int launch(rsx_gridmap *h, const float *d_xy, const int64_t *d_off, int32_t stride, int n, const double *d_priors, const rsx_gridmap_refine_params &p,
-           rsx_gridmap_refine_result *d_results, hipStream_t s) {
-  RefineGeo g{};
-  g.ox = h->p.origin_x, g.oy = h->p.origin_y, g.res = h->p.resolution, g.inv_res = 1.0 / h->p.resolution;
-  g.w = (double)h->p.width, g.h = (double)h->p.height;
-  g.x_hi = (double)(h->p.width + PLACE), g.y_hi = (double)(h->p.height + PLACE);
-  g.pitch = h->like_pitch();
-  hipLaunchKernelGGL(gmr_refine, dim3((unsigned)n), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, g, p, (const uint8_t *)h->like_origin(), d_results);
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
+// the call as gridloc_host.h's scaffold takes it: no side output, and the one launch
+gridloc::LocCall describe(const rsx_gridmap_refine_params &p) {
+  return {gridloc::have_likelihood, 0, nullptr, sizeof(rsx_gridmap_refine_result),
+          [&p](rsx_gridmap *h, const gridloc::LocJobs &j, void *d_results, uint32_t *, hipStream_t s) -> int {
+            RefineGeo g{};
+            g.ox = h->p.origin_x, g.oy = h->p.origin_y, g.res = h->p.resolution, g.inv_res = 1.0 / h->p.resolution;
+            g.w = (double)h->p.width, g.h = (double)h->p.height;
+            g.x_hi = (double)(h->p.width + PLACE), g.y_hi = (double)(h->p.height + PLACE);
+            g.pitch = h->like_pitch();
+            hipLaunchKernelGGL(gmr_refine, dim3((unsigned)j.n), dim3(NT), 0, s, j.xy, j.stride, j.off, j.priors, g, p, (const uint8_t *)h->like_origin(),
+                               static_cast<rsx_gridmap_refine_result *>(d_results));
+            RSX_HIP(hipGetLastError());
+            return RSX_OK;
+          }};
 }
 
 }  // namespace
@@ -294,49 +296,18 @@ int rsx_gridmap_refine_default_params(rsx_gridmap_refine_params *p) try {
 int rsx_gridmap_refine_batch_device(rsx_gridmap *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride, int32_t n_jobs,
                                     const double *d_priors, const rsx_gridmap_refine_params *params, rsx_gridmap_refine_result *d_results,
                                     void *stream) try {
-  // (the arguments are judged before the handle is looked at: their rules need no device)
-  if (!d_xy || !d_offsets || !d_priors || !d_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (point_stride < 2) return fail(RSX_ERR_BAD_ARG, "point_stride %d below 2", point_stride);
+  RSX_TRY(gridloc::check_args(d_xy, d_offsets, d_priors, d_results, n_jobs, point_stride));
   rsx_gridmap_refine_params dp;
   RSX_TRY(resolve(params, dp));
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->have_like) return no_likelihood();
-  if (n_jobs == 0) return RSX_OK;
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  RSX_TRY(h->order.enter(s));
-  return launch(h, d_xy, d_offsets, point_stride, n_jobs, d_priors, dp, d_results, s);
+  return gridloc::run_device(h, describe(dp), {d_xy, d_offsets, point_stride, n_jobs, d_priors}, d_results, nullptr, stream);
 } RSX_CATCH_ALL
 
 int rsx_gridmap_refine_batch(rsx_gridmap *h, const float *xy, const int64_t *offsets, int32_t n_jobs, const double *priors,
                              const rsx_gridmap_refine_params *params, rsx_gridmap_refine_result *out_results) try {
-  // (the arguments are judged before the handle is looked at: their rules need no device)
-  if (!xy || !offsets || !priors || !out_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  RSX_TRY(gridloc::check_args(xy, offsets, priors, out_results, n_jobs, 2));
   rsx_gridmap_refine_params dp;
   RSX_TRY(resolve(params, dp));
-  if (n_jobs > 0) {
-    RSX_TRY(rsx::check_offsets(offsets, n_jobs, "rsx_gridmap_refine_batch"));
-    for (int32_t i = 0; i < n_jobs; i++)
-      if (offsets[i + 1] - offsets[i] > MAX_POINTS)
-        return fail(RSX_ERR_BAD_ARG, "job %d has %lld points, more than %d", i, (long long)(offsets[i + 1] - offsets[i]), MAX_POINTS);
-  }
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->have_like) return no_likelihood();
-  if (n_jobs == 0) return RSX_OK;
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  RSX_TRY(h->order.enter(s));
-  const size_t n = (size_t)n_jobs;
-  RSX_TRY(rsx::stage_up(h->r_xy, xy, (size_t)offsets[n_jobs] * 8, s));
-  RSX_TRY(rsx::stage_up(h->r_off, offsets, (n + 1) * 8, s));
-  RSX_TRY(rsx::stage_up(h->r_tf, priors, n * 48, s));
-  RSX_TRY(rsx::stage_room(h->r_res, n * sizeof(rsx_gridmap_refine_result), s));
-  RSX_TRY(launch(h, h->r_xy.as<float>(), h->r_off.as<int64_t>(), 2, n_jobs, h->r_tf.as<double>(), dp, h->r_res.as<rsx_gridmap_refine_result>(), s));
-  RSX_TRY(rsx::stage_down(out_results, h->r_res, n * sizeof(rsx_gridmap_refine_result), s));
-  RSX_HIP(hipStreamSynchronize(s));
-  return RSX_OK;
+  return gridloc::run_host(h, describe(dp), "rsx_gridmap_refine_batch", xy, offsets, n_jobs, priors, out_results, nullptr);
 } RSX_CATCH_ALL
 
 }  // extern "C"

@@ -13,7 +13,7 @@
 // is not placed is given the cell (-(max_cells + 32), ...), from which no candidate and no block reaches a byte that is not 0.
 // Three launches per call whatever the batch, no atomics on device memory:
 //   gms_bound   one workgroup per (job, k).  Cells of the rotated cloud into LDS as offsets into Pd; bounds of every block with the
-//               slot and part scheme of gmm_score; the best block by an index-carrying maximum; cells again as offsets into F; that
+//               slot and part scheme of gmm_score (slot_sums); the best block by an index-carrying maximum; cells again as offsets into F; that
 //               block's <= 64 candidates exactly (8 v x 2 groups of four u = 16 slots x 16 parts of points): seed(k).  The
 //               workgroup of k = 0 also writes score(0, 0, 0).
 //   gms_refine  one workgroup per (job, k).  T0 from the 2K + 1 seeds; cells; a pass over its bounds that lists the blocks reaching
@@ -23,6 +23,7 @@
 //               the tie order and its count.
 //   gms_pick    one workgroup per job: the winner over the 2K + 1 keys by a two-word comparison that carries the whole tie order,
 //               bound_runner_up from the bounds, the counts at the winner's k; thread 0 writes the record.
+// The two batch entries are the scaffold of gridloc_host.h behind their own rules.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,27 +31,25 @@
 #include <cstring>
 #include <mutex>
 
+#include "gridloc_host.h"
 #include "gridmap.h"
 #include "gridmatch_dev.h"
-#include "ragged_host.h"
 
 #pragma STDC FP_CONTRACT OFF
 
 namespace {
 
 using rsx::fail;
-using namespace rsx::gridmatch_dev;  // NT, MatchGeo, finite6, place, job_points, walk, block_max
+using namespace rsx::gridmatch_dev;  // NT, MatchGeo, Rotations, place, job_points, skip_status, walk, slot_sums, count_at, winner_transform, block_max
+namespace gridloc = rsx::gridloc;
 
 constexpr int MAX_POINTS = RSX_GRIDMAP_MATCH_MAX_POINTS;
 constexpr int MAX_K = RSX_GRIDMAP_SEARCH_MAX_ANGLE_STEPS, MAX_UV = RSX_GRIDMAP_SEARCH_MAX_CELLS;
 constexpr int MAX_BLOCKS = ((2 * MAX_UV + 1 + 7) / 8) * ((2 * MAX_UV + 1 + 7) / 8);  // of one k: 65 x 65
 constexpr int TILE = 32;                                                             // gms_prepare: cells of a tile's side
-constexpr size_t BOUNDS_STAGE = (size_t)64 << 20;                                    // rsx_gridmap_search_batch: bytes of bounds per sub-batch
 static_assert(MAX_BLOCKS <= 65536, "the refine list holds block indices in 16 bits");
 
-struct Tables {
-  float c[2 * MAX_K + 1], s[2 * MAX_K + 1];  // [k + K]
-};
+using Tables = Rotations<MAX_K>;
 static_assert(sizeof(Tables) == 2888, "");
 
 struct SearchGeo {
@@ -142,13 +141,13 @@ __global__ __launch_bounds__(NT) void gms_bound(const float *__restrict__ xy, in
   __shared__ unsigned prior_sum;
   const MatchGeo &g = sg.g;
   const int tid = threadIdx.x;
-  const int nk = 2 * g.K + 1, nb = sg.nbv * sg.nbu, groups = (sg.nbu + 3) >> 2;
+  const int nk = 2 * g.K + 1, nb = sg.nbv * sg.nbu;
   const int job = (int)(blockIdx.x / (unsigned)nk), kk = (int)(blockIdx.x % (unsigned)nk);
   unsigned *out = bounds + ((int64_t)job * nk + kk) * nb;
   const double *t = priors + 6 * (int64_t)job;
   int64_t first;
   const int64_t n64 = job_points(offsets, job, &first);
-  if (n64 > MAX_POINTS || !finite6(t)) {  // (workgroup-uniform) a skipped job: its bounds are 0
+  if (skip_status(t, n64)) {  // (workgroup-uniform) a skipped job: its bounds are 0
     for (int i = tid; i < nb; i += NT) out[i] = 0u;
     if (tid == 0) {
       seeds[(int64_t)job * nk + kk] = 0u;
@@ -164,44 +163,14 @@ __global__ __launch_bounds__(NT) void gms_bound(const float *__restrict__ xy, in
   __syncthreads();
   // ---- the bounds of every block, and the best of them (bound << 32 | ~index: the highest bound, then the smallest index) ----
   unsigned long long best = 0ull;
-  const int slots = sg.nbv * groups;
-  const int parts = slots < NT ? NT / slots : 1;
-  if (parts > 1) {  // (workgroup-uniform) every slot has a thread in each part
-    unsigned sum[4] = {0u, 0u, 0u, 0u};
-    const int part = tid / slots, slot = tid - part * slots;
-    const int bv = slot / groups, gi = slot - bv * groups;
-    if (part < parts) walk(Pd, cell, n, part, parts, (unsigned)(bv * sg.cw + 4 * gi), sum);
-#pragma unroll
-    for (int j = 0; j < 4; j++) red[4 * tid + j] = sum[j];
-    __syncthreads();
-    if (tid < slots) {
-      for (int q = 1; q < parts; q++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) sum[j] += red[4 * (tid + q * slots) + j];
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * gi + j < sg.nbu) {
-          const int idx = bv * sg.nbu + 4 * gi + j;
-          out[idx] = sum[j];
-          const unsigned long long cand = ((unsigned long long)sum[j] << 32) | (unsigned long long)(0xffffffffu - (unsigned)idx);
-          best = cand > best ? cand : best;
-        }
-    }
-  } else {
-    for (int slot = tid; slot < slots; slot += NT) {
-      unsigned sum[4] = {0u, 0u, 0u, 0u};
-      const int bv = slot / groups, gi = slot - bv * groups;
-      walk(Pd, cell, n, 0, 1, (unsigned)(bv * sg.cw + 4 * gi), sum);
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * gi + j < sg.nbu) {
-          const int idx = bv * sg.nbu + 4 * gi + j;
-          out[idx] = sum[j];
-          const unsigned long long cand = ((unsigned long long)sum[j] << 32) | (unsigned long long)(0xffffffffu - (unsigned)idx);
-          best = cand > best ? cand : best;
-        }
-    }
-  }
+  slot_sums(
+      Pd, cell, red, n, sg.nbv, sg.nbu, [&](int bv, int gi) { return (unsigned)(bv * sg.cw + 4 * gi); },
+      [&](int bv, int bu, unsigned sum) {
+        const int idx = bv * sg.nbu + bu;
+        out[idx] = sum;
+        const unsigned long long cand = ((unsigned long long)sum << 32) | (unsigned long long)(0xffffffffu - (unsigned)idx);
+        best = cand > best ? cand : best;
+      });
   best = block_max(best, keys);  // (its barriers: every walk over the pooled cells has ended)
   const int bi = (int)(0xffffffffu - (unsigned)(best & 0xffffffffull));
   const int bv = bi / sg.nbu, bu = bi - bv * sg.nbu;
@@ -250,7 +219,7 @@ __global__ __launch_bounds__(NT) void gms_refine(const float *__restrict__ xy, i
   const double *t = priors + 6 * (int64_t)job;
   int64_t first;
   const int64_t n64 = job_points(offsets, job, &first);
-  if (n64 > MAX_POINTS || !finite6(t)) {  // (workgroup-uniform) a skipped job
+  if (skip_status(t, n64)) {  // (workgroup-uniform) a skipped job
     if (tid == 0) out_keys[(int64_t)job * nk + kk] = 0ull, out_counts[(int64_t)job * nk + kk] = 0;
     return;
   }
@@ -345,7 +314,7 @@ __global__ __launch_bounds__(NT) void gms_pick(const float *__restrict__ xy, int
   const double *t = priors + 6 * (int64_t)job;
   int64_t first;
   const int64_t n64 = job_points(offsets, job, &first);
-  const int skipped = (finite6(t) ? 0 : RSX_GRIDMAP_MATCH_STATUS_TRANSFORM) | (n64 > MAX_POINTS ? RSX_GRIDMAP_MATCH_STATUS_POINTS : 0);
+  const int skipped = skip_status(t, n64);
   if (skipped) {  // (workgroup-uniform) a zero record but for the status
     if (tid == 0) {
       rsx_gridmap_search_result r;
@@ -390,17 +359,7 @@ __global__ __launch_bounds__(NT) void gms_pick(const float *__restrict__ xy, int
   // ---- the counts at the winner (at k = 0 without one) ----
   const double c = (double)tab.c[ki], s = (double)tab.s[ki];
   const double t6[6] = {t[0], t[1], t[2], t[3], t[4], t[5]};
-  unsigned placed = 0u, inside = 0u;
-  for (int i = tid; i < (int)n64; i += NT) {
-    const float *p = xy + (first + i) * stride;
-    int ix, iy;
-    if (place(g, sg.PL, t6, c, s, (double)p[0], (double)p[1], &ix, &iy)) {
-      placed++;
-      inside += (ix + bu >= 0 && ix + bu < g.W && iy + bv >= 0 && iy + bv < g.H) ? 1u : 0u;
-    }
-  }
-  atomicAdd(&n_placed, placed);  // (LDS)
-  atomicAdd(&n_inside, inside);
+  count_at(g, sg.PL, xy, stride, first, (int)n64, t6, c, s, bu, bv, &n_placed, &n_inside);
   __syncthreads();
   if (tid != 0) return;
   rsx_gridmap_search_result r;
@@ -411,17 +370,8 @@ __global__ __launch_bounds__(NT) void gms_pick(const float *__restrict__ xy, int
   r.k = bk, r.u = bu, r.v = bv;
   r.n_points = (int)n_placed, r.n_inside = (int)n_inside;
   r.n_blocks = nk * nb, r.n_refined = (int)n_refined;
-  if (!found) {
-    r.status = sg.min_score == 0u ? RSX_GRIDMAP_MATCH_STATUS_EMPTY : RSX_GRIDMAP_SEARCH_STATUS_BELOW;
-    for (int q = 0; q < 6; q++) r.transform[q] = t6[q];
-  } else {
-    r.transform[0] = t6[0] * c + t6[1] * s;
-    r.transform[1] = t6[1] * c - t6[0] * s;
-    r.transform[2] = t6[2] + (double)bu * g.res;
-    r.transform[3] = t6[3] * c + t6[4] * s;
-    r.transform[4] = t6[4] * c - t6[3] * s;
-    r.transform[5] = t6[5] + (double)bv * g.res;
-  }
+  if (!found) r.status = sg.min_score == 0u ? RSX_GRIDMAP_MATCH_STATUS_EMPTY : RSX_GRIDMAP_SEARCH_STATUS_BELOW;
+  winner_transform(r.transform, found, t6, c, s, bu, bv, g.res);
   results[job] = r;
 }
 
@@ -458,19 +408,10 @@ __global__ __launch_bounds__(NT) void gms_prepare(const uint8_t *__restrict__ li
   }
 }
 
-int check_params(const rsx_gridmap_search_params &p) {
-  if (p.angle_steps < 0 || p.angle_steps > MAX_K) return fail(RSX_ERR_BAD_ARG, "angle_steps %d outside 0 .. %d", p.angle_steps, MAX_K);
-  if (p.angle_steps > 0 && (!(p.angle_step > 0.0) || !std::isfinite(p.angle_step)))
-    return fail(RSX_ERR_BAD_ARG, "angle_step must be positive and finite when angle_steps > 0");
-  if (p.x_cells < 0 || p.x_cells > MAX_UV) return fail(RSX_ERR_BAD_ARG, "x_cells %d outside 0 .. %d", p.x_cells, MAX_UV);
-  if (p.y_cells < 0 || p.y_cells > MAX_UV) return fail(RSX_ERR_BAD_ARG, "y_cells %d outside 0 .. %d", p.y_cells, MAX_UV);
-  return RSX_OK;
-}
-
 int resolve(const rsx_gridmap_search_params *params, rsx_gridmap_search_params &dp) {
   rsx_gridmap_search_default_params(&dp);
   if (params) dp = *params;
-  return check_params(dp);
+  return gridloc::check_window_params(dp, MAX_K, MAX_UV);
 }
 
 int blocks_of(int cells) { return (2 * cells + 1 + 7) / 8; }
@@ -484,42 +425,36 @@ int check_prepared(const rsx_gridmap *h, const rsx_gridmap_search_params &p) {
   return RSX_OK;
 }
 
-// the three launches behind both entries (the caller holds h->mu and has entered s): n jobs, their bounds at d_bounds
-int launch(rsx_gridmap *h, const float *d_xy, const int64_t *d_off, int32_t stride, int n, const double *d_priors, const rsx_gridmap_search_params &p,
-           rsx_gridmap_search_result *d_results, uint32_t *d_bounds, hipStream_t s) {
-  Tables tab;
-  memset(&tab, 0, sizeof(tab));
-  for (int k = -p.angle_steps; k <= p.angle_steps; k++) {  // fp64, rounded once
-    const double ang = (double)k * p.angle_step;
-    tab.c[k + p.angle_steps] = (float)std::cos(ang);
-    tab.s[k + p.angle_steps] = (float)std::sin(ang);
-  }
-  SearchGeo sg{};
-  MatchGeo &g = sg.g;
-  g.ox = h->p.origin_x, g.oy = h->p.origin_y, g.res = h->p.resolution, g.inv_res = 1.0 / h->p.resolution;
-  g.W = h->p.width, g.H = h->p.height, g.K = p.angle_steps, g.U = p.x_cells, g.V = p.y_cells;
-  g.pitch = (unsigned)(8 * h->s_cw);
-  sg.M = h->s_margin, sg.cw = h->s_cw, sg.ch = h->s_ch;
-  sg.PL = std::max(64, std::max(p.x_cells, p.y_cells));
-  sg.nbu = blocks_of(p.x_cells), sg.nbv = blocks_of(p.y_cells);
-  sg.nowhere = -(h->s_cells + 32);
-  sg.min_score = p.min_score;
-  const size_t nk = (size_t)(2 * p.angle_steps + 1), per_k = (size_t)n * nk;
-  RSX_TRY(h->s_aux.reserve(16 * per_k + 4 * (size_t)n, s, false));
-  unsigned long long *keys = h->s_aux.as<unsigned long long>();
-  unsigned *seeds = reinterpret_cast<unsigned *>(keys + per_k);
-  int *counts = reinterpret_cast<int *>(seeds + per_k);
-  unsigned *prior_scores = reinterpret_cast<unsigned *>(counts + per_k);
-  const uint8_t *F = h->s_frame.as<uint8_t>(), *Pd = h->s_pool.as<uint8_t>();
-  hipLaunchKernelGGL(gms_bound, dim3((unsigned)per_k), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, tab, sg, F, Pd, d_bounds, seeds, prior_scores);
-  RSX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(gms_refine, dim3((unsigned)per_k), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, tab, sg, F, d_bounds, seeds, prior_scores,
-                     keys, counts);
-  RSX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(gms_pick, dim3((unsigned)n), dim3(NT), 0, s, d_xy, (int64_t)stride, d_off, d_priors, tab, sg, d_bounds, prior_scores, keys, counts,
-                     d_results);
-  RSX_HIP(hipGetLastError());
-  return RSX_OK;
+// the call as gridloc_host.h's scaffold takes it: the bounds of (2K + 1) nbv nbu words per job, in h->s_bounds unless the caller
+// gave room, and the three launches
+gridloc::LocCall describe(const rsx_gridmap_search_params &p) {
+  return {[&p](const rsx_gridmap *h) { return check_prepared(h, p); }, blocks(p), &rsx_gridmap::s_bounds, sizeof(rsx_gridmap_search_result),
+          [&p](rsx_gridmap *h, const gridloc::LocJobs &j, void *d_results, uint32_t *d_bounds, hipStream_t s) -> int {
+            const Tables tab(p.angle_steps, p.angle_step);
+            SearchGeo sg{};
+            sg.g = gridloc::match_geo(h, p.angle_steps, p.x_cells, p.y_cells, (unsigned)(8 * h->s_cw));
+            sg.M = h->s_margin, sg.cw = h->s_cw, sg.ch = h->s_ch;
+            sg.PL = std::max(64, std::max(p.x_cells, p.y_cells));
+            sg.nbu = blocks_of(p.x_cells), sg.nbv = blocks_of(p.y_cells);
+            sg.nowhere = -(h->s_cells + 32);
+            sg.min_score = p.min_score;
+            const size_t nk = (size_t)(2 * p.angle_steps + 1), per_k = (size_t)j.n * nk;
+            RSX_TRY(h->s_aux.reserve(16 * per_k + 4 * (size_t)j.n, s, false));
+            unsigned long long *keys = h->s_aux.as<unsigned long long>();
+            unsigned *seeds = reinterpret_cast<unsigned *>(keys + per_k);
+            int *counts = reinterpret_cast<int *>(seeds + per_k);
+            unsigned *prior_scores = reinterpret_cast<unsigned *>(counts + per_k);
+            const uint8_t *F = h->s_frame.as<uint8_t>(), *Pd = h->s_pool.as<uint8_t>();
+            hipLaunchKernelGGL(gms_bound, dim3((unsigned)per_k), dim3(NT), 0, s, j.xy, j.stride, j.off, j.priors, tab, sg, F, Pd, d_bounds, seeds, prior_scores);
+            RSX_HIP(hipGetLastError());
+            hipLaunchKernelGGL(gms_refine, dim3((unsigned)per_k), dim3(NT), 0, s, j.xy, j.stride, j.off, j.priors, tab, sg, F, d_bounds, seeds, prior_scores,
+                               keys, counts);
+            RSX_HIP(hipGetLastError());
+            hipLaunchKernelGGL(gms_pick, dim3((unsigned)j.n), dim3(NT), 0, s, j.xy, j.stride, j.off, j.priors, tab, sg, d_bounds, prior_scores, keys, counts,
+                               static_cast<rsx_gridmap_search_result *>(d_results));
+            RSX_HIP(hipGetLastError());
+            return RSX_OK;
+          }};
 }
 
 }  // namespace
@@ -540,7 +475,7 @@ int rsx_gridmap_search_prepare(rsx_gridmap *h, int32_t max_cells, void *stream) 
   if (max_cells < 0 || max_cells > MAX_UV) return fail(RSX_ERR_BAD_ARG, "max_cells %d outside 0 .. %d", max_cells, MAX_UV);
   if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
   std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->have_like) return fail(RSX_ERR_BAD_ARG, "no likelihood plane yet: rsx_gridmap_likelihood_update or rsx_gridmap_likelihood_set first");
+  if (!h->have_like) return rsx::no_likelihood();
   RSX_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
   RSX_TRY(h->order.enter(s));
@@ -566,62 +501,19 @@ int rsx_gridmap_search_prepare(rsx_gridmap *h, int32_t max_cells, void *stream) 
 int rsx_gridmap_search_batch_device(rsx_gridmap *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride, int32_t n_jobs,
                                     const double *d_priors, const rsx_gridmap_search_params *params, rsx_gridmap_search_result *d_results,
                                     uint32_t *d_bounds, void *stream) try {
-  // (the arguments are judged before the handle is looked at: their rules need no device)
-  if (!d_xy || !d_offsets || !d_priors || !d_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (point_stride < 2) return fail(RSX_ERR_BAD_ARG, "point_stride %d below 2", point_stride);
+  RSX_TRY(gridloc::check_args(d_xy, d_offsets, d_priors, d_results, n_jobs, point_stride));
   rsx_gridmap_search_params dp;
   RSX_TRY(resolve(params, dp));
   if ((int64_t)n_jobs * (2 * dp.angle_steps + 1) > 0x7fffffffll) return fail(RSX_ERR_BAD_ARG, "n_jobs %d times %d rotations is 2^31 or more", n_jobs, 2 * dp.angle_steps + 1);
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(check_prepared(h, dp));
-  if (n_jobs == 0) return RSX_OK;
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  RSX_TRY(h->order.enter(s));
-  if (!d_bounds) {
-    RSX_TRY(h->s_bounds.reserve((size_t)n_jobs * blocks(dp) * sizeof(uint32_t), s, false));
-    d_bounds = h->s_bounds.as<uint32_t>();
-  }
-  return launch(h, d_xy, d_offsets, point_stride, n_jobs, d_priors, dp, d_results, d_bounds, s);
+  return gridloc::run_device(h, describe(dp), {d_xy, d_offsets, point_stride, n_jobs, d_priors}, d_results, d_bounds, stream);
 } RSX_CATCH_ALL
 
 int rsx_gridmap_search_batch(rsx_gridmap *h, const float *xy, const int64_t *offsets, int32_t n_jobs, const double *priors,
                              const rsx_gridmap_search_params *params, rsx_gridmap_search_result *out_results, uint32_t *out_bounds) try {
-  // (the arguments are judged before the handle is looked at: their rules need no device)
-  if (!xy || !offsets || !priors || !out_results || n_jobs < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
+  RSX_TRY(gridloc::check_args(xy, offsets, priors, out_results, n_jobs, 2));
   rsx_gridmap_search_params dp;
   RSX_TRY(resolve(params, dp));
-  if (n_jobs > 0) {
-    RSX_TRY(rsx::check_offsets(offsets, n_jobs, "rsx_gridmap_search_batch"));
-    for (int32_t i = 0; i < n_jobs; i++)
-      if (offsets[i + 1] - offsets[i] > MAX_POINTS)
-        return fail(RSX_ERR_BAD_ARG, "job %d has %lld points, more than %d", i, (long long)(offsets[i + 1] - offsets[i]), MAX_POINTS);
-  }
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(check_prepared(h, dp));
-  if (n_jobs == 0) return RSX_OK;
-  RSX_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  RSX_TRY(h->order.enter(s));
-  const size_t n = (size_t)n_jobs, nblk = blocks(dp);
-  RSX_TRY(rsx::stage_up(h->m_xy, xy, (size_t)offsets[n_jobs] * 8, s));
-  RSX_TRY(rsx::stage_up(h->m_off, offsets, (n + 1) * 8, s));
-  RSX_TRY(rsx::stage_up(h->m_tf, priors, n * 48, s));
-  RSX_TRY(rsx::stage_room(h->m_res, n * sizeof(rsx_gridmap_search_result), s));
-  // sub-batches bound the staged bounds; a job's bytes do not depend on the cut
-  const size_t per = BOUNDS_STAGE / (nblk * sizeof(uint32_t)), sub = per < n ? per : n;
-  RSX_TRY(rsx::stage_room(h->s_bounds, sub * nblk * sizeof(uint32_t), s));
-  for (size_t b0 = 0; b0 < n; b0 += sub) {
-    const size_t nb = n - b0 < sub ? n - b0 : sub;
-    RSX_TRY(launch(h, h->m_xy.as<float>(), h->m_off.as<int64_t>() + b0, 2, (int)nb, h->m_tf.as<double>() + 6 * b0, dp,
-                   h->m_res.as<rsx_gridmap_search_result>() + b0, h->s_bounds.as<uint32_t>(), s));
-    if (out_bounds) RSX_TRY(rsx::stage_down(out_bounds + b0 * nblk, h->s_bounds, nb * nblk * sizeof(uint32_t), s));
-  }
-  RSX_TRY(rsx::stage_down(out_results, h->m_res, n * sizeof(rsx_gridmap_search_result), s));
-  RSX_HIP(hipStreamSynchronize(s));
-  return RSX_OK;
+  return gridloc::run_host(h, describe(dp), "rsx_gridmap_search_batch", xy, offsets, n_jobs, priors, out_results, out_bounds);
 } RSX_CATCH_ALL
 
 }  // extern "C"

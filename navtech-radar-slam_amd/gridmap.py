@@ -10,6 +10,14 @@ from ._rsx import (GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GRIDM
 from .cfear import ragged
 
 
+def _with_fields(p, struct, fields):
+    for name, value in fields.items():
+        if not hasattr(p, name):
+            raise TypeError(struct + " has no field " + name)
+        setattr(p, name, value)
+    return p
+
+
 def default_params():
     """1024 x 1024 cells of 0.5 m with the corner at (-256, -256), 0.0595 m per range bin, min_range_bins 58, range_halfwidth 4,
     hit_threshold 120, max_range 0 (to the last bin)."""
@@ -20,12 +28,7 @@ def default_params():
 
 def params(**fields):
     """default_params() with the given fields replaced."""
-    p = default_params()
-    for name, value in fields.items():
-        if not hasattr(p, name):
-            raise TypeError("rsx_gridmap_params has no field " + name)
-        setattr(p, name, value)
-    return p
+    return _with_fields(default_params(), "rsx_gridmap_params", fields)
 
 
 def default_match_params():
@@ -37,12 +40,7 @@ def default_match_params():
 
 def match_params(**fields):
     """default_match_params() with the given fields replaced."""
-    p = default_match_params()
-    for name, value in fields.items():
-        if not hasattr(p, name):
-            raise TypeError("rsx_gridmap_match_params has no field " + name)
-        setattr(p, name, value)
-    return p
+    return _with_fields(default_match_params(), "rsx_gridmap_match_params", fields)
 
 
 def default_search_params():
@@ -54,12 +52,7 @@ def default_search_params():
 
 def search_params(**fields):
     """default_search_params() with the given fields replaced."""
-    p = default_search_params()
-    for name, value in fields.items():
-        if not hasattr(p, name):
-            raise TypeError("rsx_gridmap_search_params has no field " + name)
-        setattr(p, name, value)
-    return p
+    return _with_fields(default_search_params(), "rsx_gridmap_search_params", fields)
 
 
 def search_blocks(p):
@@ -76,12 +69,7 @@ def default_refine_params():
 
 def refine_params(**fields):
     """default_refine_params() with the given fields replaced."""
-    p = default_refine_params()
-    for name, value in fields.items():
-        if not hasattr(p, name):
-            raise TypeError("rsx_gridmap_refine_params has no field " + name)
-        setattr(p, name, value)
-    return p
+    return _with_fields(default_refine_params(), "rsx_gridmap_refine_params", fields)
 
 
 def prior_transforms(priors, n):
@@ -90,6 +78,30 @@ def prior_transforms(priors, n):
     if priors.dtype.names and "transform" in priors.dtype.names:
         priors = priors["transform"]
     return np.ascontiguousarray(priors, dtype=np.float64).reshape(n, 6)
+
+
+def _choose(params, fields, maker):
+    """the params struct of a call that may give it whole or as fields by name"""
+    if params is not None and fields:
+        raise TypeError("give params or its fields, not both")
+    return params if params is not None else maker(**fields)
+
+
+def _jobs(clouds, priors, dtype, records=False):
+    """-> xy, offsets, n, priors (n, 6) float64 and zeroed results (n,) of `dtype` for a host entry; records: priors may also be what
+    prior_transforms takes"""
+    xy, off = ragged(clouds, np.float32, 2)
+    n = len(clouds)
+    priors = prior_transforms(priors, n) if records else np.ascontiguousarray(priors, dtype=np.float64).reshape(n, 6)
+    return xy, off, n, priors, np.zeros(n, dtype=dtype)
+
+
+def _device_jobs(xy, offsets, priors, results, dtype):
+    """the layout that a device entry asks of its tensors -> n; dtype: of a result record"""
+    n = offsets.numel() - 1
+    assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and priors.is_contiguous()
+    assert priors.numel() == 6 * n and results.is_contiguous() and results.numel() * results.element_size() == n * dtype.itemsize
+    return n
 
 
 def write_pgm(path, px):
@@ -250,13 +262,8 @@ class GridMap:
         """clouds: list of (n_i, 2) float32 in the sensor frame; priors: (n, 6) float64 r00, r01, tx, r10, r11, ty (coral.pose_matrices
         makes them from x, y, yaw); params: a GridmapMatchParams, or its fields by name (angle_steps, angle_step, x_cells, y_cells)
         -> results (n,) GRIDMAP_MATCH_RESULT_DTYPE, and with return_scores=True also the volumes uint32 [n, 2K + 1, 2V + 1, 2U + 1]"""
-        if params is not None and fields:
-            raise TypeError("give params or its fields, not both")
-        p = params if params is not None else match_params(**fields)
-        xy, off = ragged(clouds, np.float32, 2)
-        n = len(clouds)
-        priors = np.ascontiguousarray(priors, dtype=np.float64).reshape(n, 6)
-        res = np.zeros(n, dtype=GRIDMAP_MATCH_RESULT_DTYPE)
+        p = _choose(params, fields, match_params)
+        xy, off, n, priors, res = _jobs(clouds, priors, GRIDMAP_MATCH_RESULT_DTYPE)
         vol = np.zeros((n, 2 * max(p.angle_steps, 0) + 1, 2 * max(p.y_cells, 0) + 1, 2 * max(p.x_cells, 0) + 1), dtype=np.uint32) if return_scores else None
         check(self._L.rsx_gridmap_match_batch(self._h, xy.ctypes.data, off.ctypes.data, n, priors.ctypes.data, C.byref(p), res.ctypes.data,
                                               vol.ctypes.data if return_scores else None))
@@ -267,12 +274,8 @@ class GridMap:
         first), offsets int64 (n + 1,), priors float64 (n, 6) contiguous, results uint8 of n * 88 bytes (view it as
         GRIDMAP_MATCH_RESULT_DTYPE on the host), scores (optional) uint32 / int32 of n (2K + 1)(2V + 1)(2U + 1) elements.  Asynchronous on
         `stream` (an int, None = the handle's own stream); a job above the cap gets GRIDMAP_MATCH_STATUS_POINTS"""
-        if params is not None and fields:
-            raise TypeError("give params or its fields, not both")
-        p = params if params is not None else match_params(**fields)
-        n = offsets.numel() - 1
-        assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and priors.is_contiguous()
-        assert priors.numel() == 6 * n and results.is_contiguous() and results.numel() * results.element_size() == n * GRIDMAP_MATCH_RESULT_DTYPE.itemsize
+        p = _choose(params, fields, match_params)
+        n = _device_jobs(xy, offsets, priors, results, GRIDMAP_MATCH_RESULT_DTYPE)
         if scores is not None:
             assert scores.is_contiguous() and scores.element_size() == 4
             assert scores.numel() == n * (2 * p.angle_steps + 1) * (2 * p.y_cells + 1) * (2 * p.x_cells + 1)
@@ -295,13 +298,8 @@ class GridMap:
         """match over a window of up to 180 rotations and 256 cells either way, with the same winner as the exhaustive rule; clouds
         and priors as for match; params: a GridmapSearchParams, or its fields by name (angle_steps, angle_step, x_cells, y_cells,
         min_score) -> results (n,) GRIDMAP_SEARCH_RESULT_DTYPE, and with return_bounds=True also the bounds uint32 [n, 2K + 1, nbv, nbu]"""
-        if params is not None and fields:
-            raise TypeError("give params or its fields, not both")
-        p = params if params is not None else search_params(**fields)
-        xy, off = ragged(clouds, np.float32, 2)
-        n = len(clouds)
-        priors = np.ascontiguousarray(priors, dtype=np.float64).reshape(n, 6)
-        res = np.zeros(n, dtype=GRIDMAP_SEARCH_RESULT_DTYPE)
+        p = _choose(params, fields, search_params)
+        xy, off, n, priors, res = _jobs(clouds, priors, GRIDMAP_SEARCH_RESULT_DTYPE)
         bounds = np.zeros((n,) + search_blocks(p), dtype=np.uint32) if return_bounds else None
         check(self._L.rsx_gridmap_search_batch(self._h, xy.ctypes.data, off.ctypes.data, n, priors.ctypes.data, C.byref(p), res.ctypes.data,
                                                bounds.ctypes.data if return_bounds else None))
@@ -311,12 +309,8 @@ class GridMap:
         """the same on torch tensors of the handle's device, as match_device: results uint8 of n * 96 bytes (view it as
         GRIDMAP_SEARCH_RESULT_DTYPE on the host), bounds (optional) uint32 / int32 of n (2K + 1) nbv nbu elements.  Asynchronous on
         `stream`; a job above the cap gets GRIDMAP_MATCH_STATUS_POINTS"""
-        if params is not None and fields:
-            raise TypeError("give params or its fields, not both")
-        p = params if params is not None else search_params(**fields)
-        n = offsets.numel() - 1
-        assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and priors.is_contiguous()
-        assert priors.numel() == 6 * n and results.is_contiguous() and results.numel() * results.element_size() == n * GRIDMAP_SEARCH_RESULT_DTYPE.itemsize
+        p = _choose(params, fields, search_params)
+        n = _device_jobs(xy, offsets, priors, results, GRIDMAP_SEARCH_RESULT_DTYPE)
         if bounds is not None:
             nk, nbv, nbu = search_blocks(p)
             assert bounds.is_contiguous() and bounds.element_size() == 4 and bounds.numel() == n * nk * nbv * nbu
@@ -330,13 +324,8 @@ class GridMap:
         gm.refine(clouds, gm.match(clouds, priors)) is the whole chain); params: a GridmapRefineParams, or its fields by name (damping,
         max_shift_step, max_rotation_step, shift_tolerance, rotation_tolerance, max_evaluations)
         -> results (n,) GRIDMAP_REFINE_RESULT_DTYPE: the refined transform, the Hessian at it, cost and score before and after"""
-        if params is not None and fields:
-            raise TypeError("give params or its fields, not both")
-        p = params if params is not None else refine_params(**fields)
-        xy, off = ragged(clouds, np.float32, 2)
-        n = len(clouds)
-        priors = prior_transforms(priors, n)
-        res = np.zeros(n, dtype=GRIDMAP_REFINE_RESULT_DTYPE)
+        p = _choose(params, fields, refine_params)
+        xy, off, n, priors, res = _jobs(clouds, priors, GRIDMAP_REFINE_RESULT_DTYPE, records=True)
         check(self._L.rsx_gridmap_refine_batch(self._h, xy.ctypes.data, off.ctypes.data, n, priors.ctypes.data, C.byref(p), res.ctypes.data))
         return res
 
@@ -344,11 +333,7 @@ class GridMap:
         """the same on torch tensors of the handle's device, as match_device: priors float64 (n, 6) contiguous, results uint8 of
         n * 152 bytes (view it as GRIDMAP_REFINE_RESULT_DTYPE on the host).  One launch, asynchronous on `stream`; a job above the cap
         gets GRIDMAP_MATCH_STATUS_POINTS"""
-        if params is not None and fields:
-            raise TypeError("give params or its fields, not both")
-        p = params if params is not None else refine_params(**fields)
-        n = offsets.numel() - 1
-        assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and priors.is_contiguous()
-        assert priors.numel() == 6 * n and results.is_contiguous() and results.numel() * results.element_size() == n * GRIDMAP_REFINE_RESULT_DTYPE.itemsize
+        p = _choose(params, fields, refine_params)
+        n = _device_jobs(xy, offsets, priors, results, GRIDMAP_REFINE_RESULT_DTYPE)
         check(self._L.rsx_gridmap_refine_batch_device(self._h, xy.data_ptr(), offsets.data_ptr(), xy.stride(0), n, priors.data_ptr(), C.byref(p),
                                                       results.data_ptr(), stream))

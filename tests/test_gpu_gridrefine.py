@@ -167,6 +167,35 @@ def test_device_entry_reads_a_packed_cloud_in_place(rsx):
     m.close()
 
 
+def test_host_entries_share_one_handle(rsx):
+    """refine, match and search stage their points, offsets, priors and records through one set of buffers of the handle: the host
+    entries in turn on one handle, with batches that grow and shrink (a buffer left by a larger call serves a smaller one and the other
+    way round), each return what a fresh handle returns for that call alone -- records, volumes and bounds byte for byte"""
+    L, clouds, priors, p = grc.random_case(64, 64)
+    mid = len(clouds) // 2
+    calls = [("refine", slice(None), {}),
+             ("match", slice(len(clouds) - 2, None), dict(return_scores=True)),            # two jobs of 8192 points
+             ("search", slice(mid, mid + 3), dict(return_bounds=True, x_cells=8, y_cells=8)),
+             ("refine", slice(mid + 3, mid + 4), {}),
+             ("match", slice(None), {})]
+
+    def run(m, name, jobs, options):
+        if name == "search":
+            m.prepare_search(8)
+        out = getattr(m, name)(clouds[jobs], priors[jobs], **options)
+        return [a.tobytes() for a in (out if isinstance(out, tuple) else (out,))]
+
+    shared = _map(p)
+    shared.set_likelihood(L)
+    for step, call in enumerate(calls):
+        fresh = _map(p)
+        fresh.set_likelihood(L)
+        want = run(fresh, *call)
+        fresh.close()
+        assert len(want[0]) > 0 and run(shared, *call) == want, (step, call[0])
+    shared.close()
+
+
 def test_rules_and_refusals_with_a_handle(rsx):
     """the argument rules of tests/test_gridrefine_abi.py hold with a handle too, and a handle without a likelihood refuses to refine
     and leaves the output buffer untouched"""
