@@ -1558,6 +1558,53 @@ int rsx_gridmap_refine_batch_device(rsx_gridmap *h, const float *d_xy, const int
                                     const double *d_priors, const rsx_gridmap_refine_params *params, rsx_gridmap_refine_result *d_results,
                                     void *stream);
 
+/* ---- a likelihood field in the plane (csrc/gridfield.hip): the three localisers above read one frozen uint8 plane, and on a raw radar
+ * plane (the mean, the hits) the refinement converges only from nearby.  This fills the plane with a function of the distance to the
+ * map's structure instead -- the likelihood field of AMCL and Hector SLAM, Cartographer's smoothed probability grid -- by an exact
+ * Euclidean distance transform, truncated at a radius.  None of this is in the reference checkout: the rule below is restated in
+ * tests/gridfield_np.py, which is the arithmetic contract -- parity unpinned.  Integers throughout: the plane equals the restatement's
+ * byte for byte, every cell.
+ * rsx_gridmap_likelihood_field transforms the likelihood plane of the handle IN PLACE, whatever filled it (the mean, the hits, a loaded
+ * image, a field):
+ *   1. a map cell is a SEED iff its byte >= threshold; the cells of the frame are never seeds
+ *   2. q(x, y) = the smallest dx dx + dy dy over the seeds (x + dx, y + dy) with dx dx + dy dy <= radius radius: an integer, exact
+ *   3. the new byte is table[q], and 0 where no seed lies within the radius; table: the caller's uint8 [radius radius + 1]
+ *   4. the frame of 128 cells stays zero
+ * A second call transforms the field itself (its seeds: the field's bytes >= threshold); that is defined and nothing special.
+ * The device evaluates no exponential: the table is an input, so that the bytes cannot hinge on a libm's last bit.
+ * rsx_gridmap_field_gaussian_table makes the usual one on the host, in fp64: out[q] = (uint8)floor(peak exp(-q / (2 sigma sigma)) + 0.5),
+ * q = 0 .. radius radius, the exponent formed as -(double)q / ((2.0 * sigma) * sigma).
+ * The field costs accuracy (its seeds are whole cells), so the chain is: refine on the field from far away, then update the plane from
+ * the mean and refine again (tests/test_gridfield_restatement.py has the figures of both stages on the synthetic drive).
+ * rsx_gridmap_search_prepare snapshots the plane: a search in the field needs a prepare AFTER this call.
+ * Two launches per call whatever the map: the seeds as a bit per cell (one 64-bit ballot per wavefront); then one workgroup per tile
+ * of 64 x 32 cells, which reads bits only, never a byte that another workgroup writes: the bit rows of the tile and a halo of `radius`
+ * go into LDS, the distance to the nearest seed along its own row comes from a count of leading / trailing zeros on the windowed
+ * words, q is the smallest dy dy + that distance squared over |dy| <= radius, and the table sits in LDS too.  No atomics. */
+
+typedef struct {
+  int32_t threshold;  /* a cell is a seed iff its byte >= threshold; 1 .. 255 (50) */
+  int32_t radius;     /* [cells] 1 .. 64 (12) */
+  int32_t reserved0;  /* 0 */
+  int32_t reserved1;  /* 0 */
+} rsx_gridmap_field_params; /* 16 bytes */
+
+#define RSX_GRIDMAP_FIELD_MAX_RADIUS 64
+
+/* threshold 50, radius 12 (and, with table NULL below, sigma 3 cells and peak 255): the values of a prototype on the hits plane of the
+ * synthetic drive (cells of 1 m).  NO REAL RADAR DATA BACKS THEM.  A violated rule of rsx_gridmap_field_params gives RSX_ERR_BAD_ARG,
+ * judged before the handle or the device is looked at */
+int rsx_gridmap_field_default_params(rsx_gridmap_field_params *p);
+/* host only, no device: out[0 .. radius radius] by the formula above; sigma_cells > 0 and finite, peak 1 .. 255, radius 1 .. 64, else
+ * RSX_ERR_BAD_ARG.  out[0] == peak and the table does not increase */
+int rsx_gridmap_field_gaussian_table(double sigma_cells, int32_t peak, int32_t radius, uint8_t *out);
+/* the transform.  params NULL: the defaults; table (host memory, radius radius + 1 bytes) NULL: the Gaussian of sigma 3, peak 255 at
+ * the radius of params.  RSX_ERR_BAD_ARG before any likelihood exists (nothing is allocated then).  Asynchronous on `stream`, two
+ * launches, ordered like rsx_gridmap_likelihood_update; the caller may free table on return: the handle keeps a copy on the host and on
+ * the device, and a call whose table differs from the previous call's uploads it and waits for that one copy (4097 bytes at the most)
+ * before it launches.  Workspace, allocated at the first call and kept until destroy: width height / 8 bytes of seeds and the table. */
+int rsx_gridmap_likelihood_field(rsx_gridmap *h, const rsx_gridmap_field_params *params, const uint8_t *table, void *stream);
+
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;
  * SURVEY 8f rank 3): polar -> Cartesian image, ORB-style binary descriptors at the keypoints, brute-force Hamming

@@ -245,6 +245,13 @@ GRIDMAP_REFINE_RESULT_DTYPE = np.dtype([("transform", "<f8", 6), ("hessian", "<f
                                         ("status", "<i4"), ("reserved", "<i4")])
 
 
+class GridmapFieldParams(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("radius", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
+GRIDMAP_FIELD_MAX_RADIUS = 64  # RSX_GRIDMAP_FIELD_MAX_RADIUS
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -336,6 +343,7 @@ SYMBOLS = [
     "rsx_gridmap_likelihood_read", "rsx_gridmap_match_batch", "rsx_gridmap_match_batch_device",
     "rsx_gridmap_search_default_params", "rsx_gridmap_search_prepare", "rsx_gridmap_search_batch", "rsx_gridmap_search_batch_device",
     "rsx_gridmap_refine_default_params", "rsx_gridmap_refine_batch", "rsx_gridmap_refine_batch_device",
+    "rsx_gridmap_field_default_params", "rsx_gridmap_field_gaussian_table", "rsx_gridmap_likelihood_field",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
     "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
     "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
@@ -543,6 +551,9 @@ def lib():
         L.rsx_gridmap_refine_default_params.argtypes = [C.POINTER(GridmapRefineParams)]
         L.rsx_gridmap_refine_batch.argtypes = [vp, vp, vp, i32, vp, C.POINTER(GridmapRefineParams), vp]
         L.rsx_gridmap_refine_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(GridmapRefineParams), vp, vp]
+        L.rsx_gridmap_field_default_params.argtypes = [C.POINTER(GridmapFieldParams)]
+        L.rsx_gridmap_field_gaussian_table.argtypes = [C.c_double, i32, i32, vp]
+        L.rsx_gridmap_likelihood_field.argtypes = [vp, C.POINTER(GridmapFieldParams), vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
         L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]

@@ -1,11 +1,13 @@
 // gridmap.h -- the handle of the radar grid map, shared by gridmap.hip (the planes: accumulate, read, render) and gridmatch.hip (the
 // likelihood plane and the correlative matching that reads it), gridsearch.hip (the wide-window search over a snapshot of it) and
-// gridrefine.hip (the sub-cell refinement that interpolates the likelihood plane); and the rules that more than one of them judges
+// gridrefine.hip (the sub-cell refinement that interpolates the likelihood plane) and gridfield.hip (the distance transform that turns
+// the likelihood plane into a likelihood field); and the rules that more than one of them judges
 // (the render mode, a window of the map, the missing likelihood plane).  What the three localisers share beyond the handle is in
 // gridloc_host.h (the scaffold of their entries) and gridmatch_dev.h (their device code).
 #pragma once
 #include <cstdint>
 #include <mutex>
+#include <vector>
 
 #include "rsx_common.h"
 
@@ -55,6 +57,10 @@ struct rsx_gridmap {
   rsx::DevBuf s_frame;          // uint8 [8 s_ch][8 s_cw]: a copy of the likelihood plane in a zeroed frame of s_margin cells
   rsx::DevBuf s_pool;           // uint8 [8][8][s_ch][s_cw]: the 8 x 8 pooled plane, de-interleaved by phase
   rsx::DevBuf s_bounds, s_aux;  // workspace of a search: the bounds of a call that asked for none; seeds, prior scores, keys, counts
+  // ---- gridfield.hip: nothing below is allocated before the first rsx_gridmap_likelihood_field that finds a likelihood ----
+  rsx::DevBuf f_bits;           // uint64 [height][width / 64]: the seeds, a bit per cell
+  rsx::DevBuf f_table;          // uint8 [radius^2 + 1]: the table of the last call, which f_table_host mirrors
+  std::vector<uint8_t> f_table_host;
   uint8_t *like_origin() const { return like.as<uint8_t>() + (size_t)rsx::GRIDMAP_LIKE_MARGIN * like_pitch() + rsx::GRIDMAP_LIKE_MARGIN; }  // cell (0, 0)
 };
 

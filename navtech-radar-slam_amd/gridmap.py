@@ -6,7 +6,7 @@ import numpy as np
 
 from . import synth
 from ._rsx import (GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GRIDMAP_REFINE_RESULT_DTYPE, GRIDMAP_SEARCH_RESULT_DTYPE,
-                   GridmapMatchParams, GridmapParams, GridmapRefineParams, GridmapSearchParams, check, lib)
+                   GridmapFieldParams, GridmapMatchParams, GridmapParams, GridmapRefineParams, GridmapSearchParams, check, lib)
 from .cfear import ragged
 
 
@@ -70,6 +70,25 @@ def default_refine_params():
 def refine_params(**fields):
     """default_refine_params() with the given fields replaced."""
     return _with_fields(default_refine_params(), "rsx_gridmap_refine_params", fields)
+
+
+def default_field_params():
+    """seeds at bytes >= 50, radius 12 cells: a prototype's values on the hits plane of the synthetic drive; no real radar data backs them."""
+    p = GridmapFieldParams()
+    check(lib().rsx_gridmap_field_default_params(C.byref(p)))
+    return p
+
+
+def field_params(**fields):
+    """default_field_params() with the given fields replaced."""
+    return _with_fields(default_field_params(), "rsx_gridmap_field_params", fields)
+
+
+def gaussian_table(sigma, radius, peak=255):
+    """uint8 [radius^2 + 1]: floor(peak exp(-q / (2 sigma^2)) + 0.5) at the squared distance q [cells^2], made on the host in fp64"""
+    out = np.zeros(max(int(radius), 0) ** 2 + 1, dtype=np.uint8)
+    check(lib().rsx_gridmap_field_gaussian_table(float(sigma), int(peak), int(radius), out.ctypes.data))
+    return out
 
 
 def prior_transforms(priors, n):
@@ -257,6 +276,19 @@ class GridMap:
         d, pitch = C.c_void_p(), C.c_int64()
         check(self._L.rsx_gridmap_likelihood_device(self._h, C.byref(d), C.byref(pitch)))
         return d.value, pitch.value
+
+    def likelihood_field(self, table=None, sigma=3.0, peak=255, params=None, stream=None, **fields):
+        """turn the likelihood plane, in place, into a likelihood field (include/rsx.h, rsx_gridmap_likelihood_field): the cells at or
+        above `threshold` are seeds, a cell within `radius` cells of a seed gets table[q] at the squared distance q to the nearest one,
+        every other cell 0.  table: uint8 [radius^2 + 1], None = gaussian_table(sigma, radius, peak); params: a GridmapFieldParams, or
+        its fields by name (threshold, radius).  Asynchronous on `stream`; a search in the field needs a prepare_search after it"""
+        p = _choose(params, fields, field_params)
+        if table is None and (float(sigma), int(peak)) != (3.0, 255):
+            table = gaussian_table(sigma, p.radius, peak)
+        if table is not None:
+            table = np.ascontiguousarray(table, dtype=np.uint8)
+            assert table.shape == (p.radius * p.radius + 1,)
+        check(self._L.rsx_gridmap_likelihood_field(self._h, C.byref(p), table.ctypes.data if table is not None else None, stream))
 
     def match(self, clouds, priors, return_scores=False, params=None, **fields):
         """clouds: list of (n_i, 2) float32 in the sensor frame; priors: (n, 6) float64 r00, r01, tx, r10, r11, ty (coral.pose_matrices
