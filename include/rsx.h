@@ -1605,6 +1605,87 @@ int rsx_gridmap_field_gaussian_table(double sigma_cells, int32_t peak, int32_t r
  * before it launches.  Workspace, allocated at the first call and kept until destroy: width height / 8 bytes of seeds and the table. */
 int rsx_gridmap_likelihood_field(rsx_gridmap *h, const rsx_gridmap_field_params *params, const uint8_t *table, void *stream);
 
+/* ---- following a sensor through the map, scan after scan (csrc/gridtrack.hip): match on the grid around a constant-velocity
+ * prediction, refine below the cell, compose the motion -- whole sequences in ONE launch, one workgroup per sequence, the state
+ * resident in device memory (what rsx_cfear_tracker_* is to rsx_cfear_register_*).  None of this is in the reference checkout: the
+ * rule below is restated in tests/gridtrack_np.py, which is the arithmetic contract -- parity unpinned; the records equal the
+ * restatement's byte for byte.
+ * All arithmetic of the glue is fp64 on plain operations, nothing fused, every expression formed in the order written; no square root,
+ * sine or cosine.  Poses are six doubles r00 r01 tx r10 r11 ty (indices 0 .. 5):
+ *   mul(A, B)  = (A0 B0 + A1 B3,  A0 B1 + A1 B4,  (A0 B2 + A1 B5) + A2,
+ *                 A3 B0 + A4 B3,  A3 B1 + A4 B4,  (A3 B2 + A4 B5) + A5)
+ *   inv(A)     = (A0, A3, -(A0 A2 + A3 A5),  A1, A4, -(A1 A2 + A4 A5))
+ *   renorm(T)  : n2 = T0 T0 + T3 T3;  f = 1.5 - 0.5 n2;  c = T0 f;  s = T3 f;   -> (c, -s, T2, s, c, T5)
+ * renorm is one Newton step towards a unit first column and rebuilds the second from it.  It is part of the rule: match turns its
+ * prior by fp32-rounded (c, s), and the chain inv, mul compounds that -- without it det R is 1 + 6.6e-5 after 10 scans of the synthetic
+ * drive and growing; with it |det R - 1| <= 2e-15 after 16.
+ * State per sequence: the pose P, the motion M (the identity after a reset) and n, the scans seen since the reset.  Per scan, cloud xy:
+ *   1. start = P when n == 0 or predict == 0, else renorm(mul(P, M)): scan 0 is matched from the reset pose bit for bit
+ *   2. m = the record of the rule of rsx_gridmap_match_* for (xy, prior start, params.match)
+ *   3. the scan is LOST iff m.status != 0 or m.score < min_score (the device entry's _POINTS counts as m.status != 0).  Then
+ *      P = start, M stays, the refine record is all zero, flags = RSX_GRIDMAP_TRACK_LOST
+ *   4. otherwise r = the record of the rule of rsx_gridmap_refine_* for (xy, prior m.transform, params.refine); every refine status is
+ *      accepted, because its cost never rises.  new = renorm(r.transform); if n > 0, M = mul(inv(P), new); P = new; flags = 0
+ *   5. n += 1; the record's transform is P after the scan
+ * A lost scan dead-reckons; re-localising it is the caller's job: rsx_gridmap_search_*, then rsx_gridmap_tracker_set_pose.
+ * The tracker reads the map's likelihood plane as it stands at each push and locks the map's mutex; its calls are ordered with the
+ * map's own (rsx_gridmap_likelihood_*, ...) through the map's stream order.  The map must outlive the tracker.
+ * One launch per push whatever the batch: one workgroup of 256 threads per sequence loops over the sequence's scans of the push; per
+ * rotation the cloud's cells go into LDS and the slot sums of the match kernel run, the score volume ((2K + 1)(2V + 1)(2U + 1) <= 4913
+ * words) never leaves LDS, the pick and the refinement loop are the device functions that rsx_gridmap_match_* and rsx_gridmap_refine_*
+ * run.  No atomics on device memory, no dependence between workgroups.  Throughput comes from sequences side by side. */
+
+#define RSX_GRIDMAP_TRACK_LOST 1
+#define RSX_GRIDMAP_TRACK_MAX_ANGLE_STEPS 8
+#define RSX_GRIDMAP_TRACK_MAX_CELLS 8
+
+typedef struct {
+  rsx_gridmap_match_params match;    /* K <= 8, U, V <= 8 here (defaults 2, 2, 2, angle_step 0.01) */
+  rsx_gridmap_refine_params refine;  /* its own rules and defaults */
+  uint32_t min_score;                /* 0 = none (0): no real radar data backs any other value */
+  int32_t predict;                   /* 0 / 1 (1) */
+  int32_t reserved[2];               /* 0 */
+} rsx_gridmap_track_params;          /* 88 bytes */
+
+typedef struct {
+  double transform[6];               /* P after the scan */
+  double start[6];                   /* the prior the scan was matched from */
+  rsx_gridmap_match_result match;    /* 88 bytes */
+  rsx_gridmap_refine_result refine;  /* 152 bytes; all zero on a lost scan */
+  int32_t flags;                     /* RSX_GRIDMAP_TRACK_* */
+  int32_t reserved;                  /* 0 */
+} rsx_gridmap_track_result;          /* 344 bytes */
+
+typedef struct rsx_gridmap_tracker rsx_gridmap_tracker;
+
+/* a violated rule of rsx_gridmap_track_params (its match and refine parts included) gives RSX_ERR_BAD_ARG in both pushes (NULL = the
+ * defaults), judged before the handle or the device is looked at */
+int rsx_gridmap_track_default_params(rsx_gridmap_track_params *p);
+/* n_sequences (1 .. 4096) sequences in `map`, every one at the identity pose with n = 0.  104 bytes of state per sequence */
+int rsx_gridmap_tracker_create(rsx_gridmap *map, int32_t n_sequences, rsx_gridmap_tracker **out);
+int rsx_gridmap_tracker_destroy(rsx_gridmap_tracker *h);
+/* poses: host, [n_sequences][6].  Every sequence: P = its pose, M = the identity, n = 0.  A non-finite entry gives RSX_ERR_BAD_ARG and
+ * changes nothing.  Synchronous. */
+int rsx_gridmap_tracker_reset(rsx_gridmap_tracker *h, const double *poses);
+/* one sequence (0 .. n_sequences - 1): P = pose6 (finite), M = the identity, n = 0.  Synchronous. */
+int rsx_gridmap_tracker_set_pose(rsx_gridmap_tracker *h, int32_t sequence, const double *pose6);
+/* the state to host arrays [n_sequences][6], [n_sequences][6], [n_sequences]; any pointer may be NULL.  Synchronous. */
+int rsx_gridmap_tracker_state(rsx_gridmap_tracker *h, double *out_poses, double *out_motions, int32_t *out_counts);
+/* n_scans[q] >= 0 scans for sequence q, sequence after sequence (rsx_cfear_tracker_push's layout): scan j of the total owns the points
+ * [offsets[j], offsets[j + 1]) of xy and out[j].  Host buffers, synchronous.  The offsets are checked; a scan above
+ * RSX_GRIDMAP_MATCH_MAX_POINTS refuses the batch.  Before any likelihood exists on the map the call is RSX_ERR_BAD_ARG and touches
+ * nothing.  The parameters may differ from push to push (the state holds none); the records do not depend on how a sequence is cut
+ * into pushes, on how many sequences run side by side, or on a sequence's index. */
+int rsx_gridmap_tracker_push(rsx_gridmap_tracker *h, const float *xy, const int64_t *offsets, const int32_t *n_scans,
+                             const rsx_gridmap_track_params *params, rsx_gridmap_track_result *out);
+/* device buffers, asynchronous on `stream`: one launch, no allocation, no host synchronisation.  point_stride >= 2 as for
+ * rsx_gridmap_match_batch_device; d_n_scans: int32 [n_sequences] in device memory; total_scans: the records that d_out and the
+ * offsets (total_scans + 1) have room for -- a scan whose index is total_scans or more is neither read nor written nor counted.  The
+ * offsets are trusted; a scan above the cap is LOST with RSX_GRIDMAP_MATCH_STATUS_POINTS. */
+int rsx_gridmap_tracker_push_device(rsx_gridmap_tracker *h, const float *d_xy, const int64_t *d_offsets, int32_t point_stride,
+                                    const int32_t *d_n_scans, int32_t total_scans, const rsx_gridmap_track_params *params,
+                                    rsx_gridmap_track_result *d_out, void *stream);
+
 /* ============================== ORORA front end ========================================
  * The steps between the cen2019 keypoints and the solver in the upstream file-based entry (reference README.md:26-29;
  * SURVEY 8f rank 3): polar -> Cartesian image, ORB-style binary descriptors at the keypoints, brute-force Hamming

@@ -252,6 +252,22 @@ class GridmapFieldParams(C.Structure):
 GRIDMAP_FIELD_MAX_RADIUS = 64  # RSX_GRIDMAP_FIELD_MAX_RADIUS
 
 
+class GridmapTrackParams(C.Structure):
+    _fields_ = [("match", GridmapMatchParams), ("refine", GridmapRefineParams), ("min_score", C.c_uint32), ("predict", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class GridmapTrackResult(C.Structure):
+    _fields_ = [("transform", C.c_double * 6), ("start", C.c_double * 6), ("match", GridmapMatchResult), ("refine", GridmapRefineResult),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+GRIDMAP_TRACK_LOST = 1  # RSX_GRIDMAP_TRACK_LOST
+GRIDMAP_TRACK_MAX_ANGLE_STEPS, GRIDMAP_TRACK_MAX_CELLS = 8, 8
+GRIDMAP_TRACK_RESULT_DTYPE = np.dtype([("transform", "<f8", 6), ("start", "<f8", 6), ("match", GRIDMAP_MATCH_RESULT_DTYPE),
+                                       ("refine", GRIDMAP_REFINE_RESULT_DTYPE), ("flags", "<i4"), ("reserved", "<i4")])
+
+
 class OroraResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double), ("iterations", C.c_int32), ("rot_inliers", C.c_int32),
                 ("trans_inliers", C.c_int32), ("status", C.c_int32)]
@@ -344,6 +360,8 @@ SYMBOLS = [
     "rsx_gridmap_search_default_params", "rsx_gridmap_search_prepare", "rsx_gridmap_search_batch", "rsx_gridmap_search_batch_device",
     "rsx_gridmap_refine_default_params", "rsx_gridmap_refine_batch", "rsx_gridmap_refine_batch_device",
     "rsx_gridmap_field_default_params", "rsx_gridmap_field_gaussian_table", "rsx_gridmap_likelihood_field",
+    "rsx_gridmap_track_default_params", "rsx_gridmap_tracker_create", "rsx_gridmap_tracker_destroy", "rsx_gridmap_tracker_reset",
+    "rsx_gridmap_tracker_set_pose", "rsx_gridmap_tracker_state", "rsx_gridmap_tracker_push", "rsx_gridmap_tracker_push_device",
     "rsx_odometry_set_cen2018", "rsx_odometry_set_estimator", "rsx_odometry_set_compensation",
     "rsx_mocomp_default_params", "rsx_mocomp_create", "rsx_mocomp_destroy", "rsx_mocomp_points_batch", "rsx_mocomp_points_batch_device",
     "rsx_mocomp_matches_batch", "rsx_mocomp_matches_batch_device",
@@ -554,6 +572,14 @@ def lib():
         L.rsx_gridmap_field_default_params.argtypes = [C.POINTER(GridmapFieldParams)]
         L.rsx_gridmap_field_gaussian_table.argtypes = [C.c_double, i32, i32, vp]
         L.rsx_gridmap_likelihood_field.argtypes = [vp, C.POINTER(GridmapFieldParams), vp, vp]
+        L.rsx_gridmap_track_default_params.argtypes = [C.POINTER(GridmapTrackParams)]
+        L.rsx_gridmap_tracker_create.argtypes = [vp, i32, C.POINTER(vp)]
+        L.rsx_gridmap_tracker_destroy.argtypes = [vp]
+        L.rsx_gridmap_tracker_reset.argtypes = [vp, vp]
+        L.rsx_gridmap_tracker_set_pose.argtypes = [vp, i32, vp]
+        L.rsx_gridmap_tracker_state.argtypes = [vp, vp, vp, vp]
+        L.rsx_gridmap_tracker_push.argtypes = [vp, vp, vp, vp, C.POINTER(GridmapTrackParams), vp]
+        L.rsx_gridmap_tracker_push_device.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(GridmapTrackParams), vp, vp]
         L.rsx_odometry_set_cen2018.argtypes = [vp, C.POINTER(Cen2018Params)]
         L.rsx_odometry_set_estimator.argtypes = [vp, C.c_int, C.POINTER(RansacParams)]
         L.rsx_odometry_set_compensation.argtypes = [vp, C.POINTER(MocompParams)]

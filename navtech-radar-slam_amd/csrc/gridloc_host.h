@@ -1,12 +1,15 @@
-// gridloc_host.h -- the host code that the grid-map localisers share (gridmatch.hip, gridsearch.hip, gridrefine.hip): the scaffold of
-// their six rsx_gridmap_{match,search,refine}_batch[_device] entries, and the window's rules and the MatchGeo of the two window
-// matchers.  A stage describes its call as data (LocCall); nothing here knows which stage calls it.
+// gridloc_host.h -- the host code that the grid-map localisers share (gridmatch.hip, gridsearch.hip, gridrefine.hip, gridtrack.hip): the
+// scaffold of the six rsx_gridmap_{match,search,refine}_batch[_device] entries, and the window's rules, the refinement's rules and the
+// geometry that the kernels of the window matchers, the refinement and the tracker take.  A stage describes its call as data (LocCall);
+// nothing here knows which stage calls it.
 #pragma once
+#include <cmath>
 #include <functional>
 #include <mutex>
 
 #include "gridmap.h"
 #include "gridmatch_dev.h"
+#include "gridrefine_dev.h"
 #include "ragged_host.h"
 
 namespace rsx {
@@ -114,6 +117,29 @@ inline gridmatch_dev::MatchGeo match_geo(const rsx_gridmap *h, int K, int U, int
   g.ox = h->p.origin_x, g.oy = h->p.origin_y, g.res = h->p.resolution, g.inv_res = 1.0 / h->p.resolution;
   g.W = h->p.width, g.H = h->p.height, g.K = K, g.U = U, g.V = V;
   g.pitch = pitch;
+  return g;
+}
+
+// the rules of rsx_gridmap_refine_params
+inline int check_refine_params(const rsx_gridmap_refine_params &p) {
+  if (!(p.damping > 0.0) || !std::isfinite(p.damping)) return fail(RSX_ERR_BAD_ARG, "damping must be positive and finite");
+  if (!(p.max_shift_step > 0.0 && p.max_shift_step <= 8.0)) return fail(RSX_ERR_BAD_ARG, "max_shift_step outside (0, 8]");
+  if (!(p.max_rotation_step > 0.0 && p.max_rotation_step <= rsx::mocomp::TH_MAX)) return fail(RSX_ERR_BAD_ARG, "max_rotation_step outside (0, 0.5]");
+  if (!(p.shift_tolerance >= 0.0) || !std::isfinite(p.shift_tolerance)) return fail(RSX_ERR_BAD_ARG, "shift_tolerance must be finite and not negative");
+  if (!(p.rotation_tolerance >= 0.0) || !std::isfinite(p.rotation_tolerance))
+    return fail(RSX_ERR_BAD_ARG, "rotation_tolerance must be finite and not negative");
+  if (p.max_evaluations < 1 || p.max_evaluations > 64) return fail(RSX_ERR_BAD_ARG, "max_evaluations %d outside 1 .. 64", p.max_evaluations);
+  if (p.reserved != 0) return fail(RSX_ERR_BAD_ARG, "reserved must be 0");
+  return RSX_OK;
+}
+
+// the map of the handle as the refinement's evaluation reads it
+inline gridrefine_dev::RefineGeo refine_geo(const rsx_gridmap *h) {
+  gridrefine_dev::RefineGeo g{};
+  g.ox = h->p.origin_x, g.oy = h->p.origin_y, g.res = h->p.resolution, g.inv_res = 1.0 / h->p.resolution;
+  g.w = (double)h->p.width, g.h = (double)h->p.height;
+  g.x_hi = (double)(h->p.width + gridmatch_dev::PLACE), g.y_hi = (double)(h->p.height + gridmatch_dev::PLACE);
+  g.pitch = h->like_pitch();
   return g;
 }
 

@@ -1,7 +1,8 @@
 // gridmap.h -- the handle of the radar grid map, shared by gridmap.hip (the planes: accumulate, read, render) and gridmatch.hip (the
 // likelihood plane and the correlative matching that reads it), gridsearch.hip (the wide-window search over a snapshot of it) and
 // gridrefine.hip (the sub-cell refinement that interpolates the likelihood plane) and gridfield.hip (the distance transform that turns
-// the likelihood plane into a likelihood field); and the rules that more than one of them judges
+// the likelihood plane into a likelihood field) and gridtrack.hip (the tracker, whose handle borrows this one's plane, mutex, stream and
+// stream order); and the rules that more than one of them judges
 // (the render mode, a window of the map, the missing likelihood plane).  What the three localisers share beyond the handle is in
 // gridloc_host.h (the scaffold of their entries) and gridmatch_dev.h (their device code).
 #pragma once

@@ -17,8 +17,8 @@
 //              per thread (the trip count is known before the loop: an exit test inside it costs a wait per read).  The parts are added
 //              through LDS; with S above 256 a thread walks several slots in turn (slot_sums of gridmatch_dev.h, which the
 //              search's gms_bound shares).
-//   gmm_pick   one workgroup per job: the winner by a 64-bit key that carries the tie order and the linear index, then the
-//              runner-up and, from steps 1 - 5 again at the winner's k, the counts; thread 0 writes the record.
+//   gmm_pick   one workgroup per job: pick_record of gridmatch_dev.h -- the winner by a 64-bit key that carries the tie order and the
+//              linear index, then the runner-up and, from steps 1 - 5 again at the winner's k, the counts; thread 0 writes the record.
 // The two batch entries are the scaffold of gridloc_host.h behind their own rules; the rules that gridmap.hip judges too are in gridmap.h.
 #include <hip/hip_runtime.h>
 
@@ -39,7 +39,7 @@ using rsx::check_render;  // (gridmap.h)
 using rsx::fail;
 using rsx::no_likelihood;
 using rsx::GRIDMAP_LIKE_MARGIN;
-using namespace rsx::gridmatch_dev;  // NT, PLACE, MatchGeo, Rotations, place, job_points, skip_status, slot_sums, count_at, winner_transform, block_max
+using namespace rsx::gridmatch_dev;  // NT, PLACE, MatchGeo, Rotations, place, job_points, skip_status, fill_cells, slot_sums, pick_record
 namespace gridloc = rsx::gridloc;
 
 constexpr int MAX_POINTS = RSX_GRIDMAP_MATCH_MAX_POINTS;
@@ -65,17 +65,10 @@ __global__ __launch_bounds__(NT) void gmm_score(const float *__restrict__ xy, in
     for (int i = tid; i < nv * nu; i += NT) out[i] = 0u;
     return;
   }
-  const int n = (int)n64;
   const double c = (double)tab.c[kk], s = (double)tab.s[kk];
   const double t6[6] = {t[0], t[1], t[2], t[3], t[4], t[5]};
-  const unsigned nowhere = (unsigned)(GRIDMAP_LIKE_MARGIN - PLACE) * g.pitch + (unsigned)(GRIDMAP_LIKE_MARGIN - PLACE);  // cell (-64, -64)
-  for (int i = tid; i < n; i += NT) {
-    const float *p = xy + (first + i) * stride;
-    int ix, iy;
-    cell[i] = place(g, PLACE, t6, c, s, (double)p[0], (double)p[1], &ix, &iy)
-                  ? (unsigned)(iy + GRIDMAP_LIKE_MARGIN) * g.pitch + (unsigned)(ix + GRIDMAP_LIKE_MARGIN)
-                  : nowhere;
-  }
+  const int n = (int)n64;
+  fill_cells(g, GRIDMAP_LIKE_MARGIN, xy, stride, first, n, t6, c, s, cell);
   __syncthreads();
   slot_sums(
       plane, cell, red, n, nv, nu, [&](int vi, int gi) { return (unsigned)((vi - g.V) * (int)g.pitch + (4 * gi - g.U)); },
@@ -85,60 +78,13 @@ __global__ __launch_bounds__(NT) void gmm_score(const float *__restrict__ xy, in
 __global__ __launch_bounds__(NT) void gmm_pick(const float *__restrict__ xy, int64_t stride, const int64_t *__restrict__ offsets,
                                                const double *__restrict__ priors, Tables tab, MatchGeo g,
                                                const unsigned *__restrict__ volume, rsx_gridmap_match_result *__restrict__ results) {
-  __shared__ unsigned long long keys[NT];
-  __shared__ unsigned seconds[NT];
-  __shared__ unsigned n_placed, n_inside;
-  const int tid = threadIdx.x, job = blockIdx.x;
-  const int nk = 2 * g.K + 1, nv = 2 * g.V + 1, nu = 2 * g.U + 1, total = nk * nv * nu;
-  const unsigned *vol = volume + (int64_t)job * total;
-  const double *t = priors + 6 * (int64_t)job;
+  __shared__ PickLds lds;
+  const int job = blockIdx.x;
+  const int total = (2 * g.K + 1) * (2 * g.V + 1) * (2 * g.U + 1);
   int64_t first;
   const int64_t n64 = job_points(offsets, job, &first);
-  rsx_gridmap_match_result r;
-  memset(&r, 0, sizeof(r));
-  const int skipped = skip_status(t, n64);
-  if (skipped) {  // (workgroup-uniform)
-    r.status = skipped;
-    if (tid == 0) results[job] = r;
-    return;
-  }
-  // ---- the winner: score, then the smallest |k|, then the smallest u u + v v, then the smallest linear index ----
-  // score < 2^21 | 127 - |k| < 2^7 | 4095 - (u u + v v) < 2^12 | 2^20 - 1 - index < 2^20
-  unsigned long long key = 0ull;
-  for (int i = tid; i < total; i += NT) {
-    const int ui = i % nu, vi = (i / nu) % nv, ki = i / (nu * nv);
-    const int k = ki - g.K, v = vi - g.V, u = ui - g.U;
-    const unsigned long long cand = ((unsigned long long)vol[i] << 39) | ((unsigned long long)(127 - (k < 0 ? -k : k)) << 32) |
-                                    ((unsigned long long)(4095 - (u * u + v * v)) << 20) | (unsigned long long)(0xfffff - i);
-    key = cand > key ? cand : key;
-  }
-  key = block_max(key, keys);
-  const int best = 0xfffff - (int)(key & 0xfffffull);
-  const int bu = best % nu - g.U, bv = (best / nu) % nv - g.V, bk = best / (nu * nv) - g.K;
-  // ---- the runner-up: the best score farther than 1 from the winner in k, u or v ----
-  unsigned second = 0u;
-  for (int i = tid; i < total; i += NT) {
-    const int du = i % nu - g.U - bu, dv = (i / nu) % nv - g.V - bv, dk = i / (nu * nv) - g.K - bk;
-    const bool far = du > 1 || du < -1 || dv > 1 || dv < -1 || dk > 1 || dk < -1;
-    second = far && vol[i] > second ? vol[i] : second;
-  }
-  second = block_max(second, seconds);
-  // ---- the counts at the winner ----
-  if (tid == 0) n_placed = 0u, n_inside = 0u;
-  __syncthreads();
-  const double c = (double)tab.c[bk + g.K], s = (double)tab.s[bk + g.K];
-  const double t6[6] = {t[0], t[1], t[2], t[3], t[4], t[5]};
-  count_at(g, PLACE, xy, stride, first, (int)n64, t6, c, s, bu, bv, &n_placed, &n_inside);
-  __syncthreads();
-  if (tid != 0) return;
-  r.score = (unsigned)(key >> 39);
-  r.score_prior = vol[(g.K * nv + g.V) * nu + g.U];
-  r.score_runner_up = second;
-  r.k = bk, r.u = bu, r.v = bv;
-  r.n_points = (int)n_placed, r.n_inside = (int)n_inside;
-  if (r.score == 0u) r.status = RSX_GRIDMAP_MATCH_STATUS_EMPTY;
-  winner_transform(r.transform, r.score != 0u, t6, c, s, bu, bv, g.res);
-  results[job] = r;
+  const rsx_gridmap_match_result r = pick_record(xy, stride, first, n64, priors + 6 * (int64_t)job, tab, g, volume + (int64_t)job * total, &lds);
+  if (threadIdx.x == 0) results[job] = r;
 }
 
 // one thread per cell: the byte of the likelihood plane from the planes -- render's rule (gm_render of gridmap.hip; include/rsx.h),

@@ -1,13 +1,14 @@
 // gridmatch_dev.h -- the device code that gridmatch.hip (exhaustive correlative matching) and gridsearch.hip (the wide-window search
 // pruned by bounds) share: steps 1 - 5 of the rule of include/rsx.h for one point, the slot walk over a framed byte plane, the slot
-// and part scheme that deals it to a workgroup, the workgroup maximum, and the counts and the transform of a record's winner; and,
-// with gridrefine.hip as well, the ragged job convention and the status of a skipped job.  Everything here is integers from the
-// cell on.  No fp64 expression here may be fused or re-associated (the Makefile's -ffp-contract=off covers a header too).
+// and part scheme that deals it to a workgroup, the workgroup maximum, and the pick of a record from its score volume (which
+// gridtrack.hip, the one-launch tracker, runs on a volume in LDS); and, with gridrefine_dev.h as well, the ragged job convention and
+// the status of a skipped job.  Everything here is integers from the cell on.  No fp64 expression here may be fused or re-associated (the Makefile's -ffp-contract=off covers a header too).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 
 #include "rsx.h"
 
@@ -173,6 +174,80 @@ __device__ __forceinline__ T block_max(T v, T *scratch) {
     __syncthreads();
   }
   return scratch[0];
+}
+
+// the LDS words of pick_record
+struct PickLds {
+  unsigned long long keys[NT];
+  unsigned seconds[NT];
+  unsigned n_placed, n_inside;
+};
+
+// The record of one job from its score volume vol[(2K + 1)(2V + 1)(2U + 1)] (global memory or LDS, written before a barrier that
+// the caller has passed): the winner by a 64-bit key that carries the tie order and the linear index, the runner-up and, from steps
+// 1 - 5 again at the winner's k, the counts.  A skipped job (skip_status) gives a zero record but for the status and reads nothing.
+// Called by the whole workgroup; every thread returns the same record.  Tab: a Rotations<>
+template <typename Tab>
+__device__ __forceinline__ rsx_gridmap_match_result pick_record(const float *__restrict__ xy, int64_t stride, int64_t first, int64_t n64, const double *t,
+                                                                const Tab &tab, const MatchGeo &g, const unsigned *vol, PickLds *lds) {
+  const int tid = threadIdx.x;
+  const int nk = 2 * g.K + 1, nv = 2 * g.V + 1, nu = 2 * g.U + 1, total = nk * nv * nu;
+  rsx_gridmap_match_result r;
+  memset(&r, 0, sizeof(r));
+  const int skipped = skip_status(t, n64);
+  if (skipped) {  // (workgroup-uniform)
+    r.status = skipped;
+    return r;
+  }
+  // ---- the winner: score, then the smallest |k|, then the smallest u u + v v, then the smallest linear index ----
+  // score < 2^21 | 127 - |k| < 2^7 | 4095 - (u u + v v) < 2^12 | 2^20 - 1 - index < 2^20
+  unsigned long long key = 0ull;
+  for (int i = tid; i < total; i += NT) {
+    const int ui = i % nu, vi = (i / nu) % nv, ki = i / (nu * nv);
+    const int k = ki - g.K, v = vi - g.V, u = ui - g.U;
+    const unsigned long long cand = ((unsigned long long)vol[i] << 39) | ((unsigned long long)(127 - (k < 0 ? -k : k)) << 32) |
+                                    ((unsigned long long)(4095 - (u * u + v * v)) << 20) | (unsigned long long)(0xfffff - i);
+    key = cand > key ? cand : key;
+  }
+  key = block_max(key, lds->keys);
+  const int best = 0xfffff - (int)(key & 0xfffffull);
+  const int bu = best % nu - g.U, bv = (best / nu) % nv - g.V, bk = best / (nu * nv) - g.K;
+  // ---- the runner-up: the best score farther than 1 from the winner in k, u or v ----
+  unsigned second = 0u;
+  for (int i = tid; i < total; i += NT) {
+    const int du = i % nu - g.U - bu, dv = (i / nu) % nv - g.V - bv, dk = i / (nu * nv) - g.K - bk;
+    const bool far = du > 1 || du < -1 || dv > 1 || dv < -1 || dk > 1 || dk < -1;
+    second = far && vol[i] > second ? vol[i] : second;
+  }
+  second = block_max(second, lds->seconds);
+  // ---- the counts at the winner ----
+  if (tid == 0) lds->n_placed = 0u, lds->n_inside = 0u;
+  __syncthreads();
+  const double c = (double)tab.c[bk + g.K], s = (double)tab.s[bk + g.K];
+  const double t6[6] = {t[0], t[1], t[2], t[3], t[4], t[5]};
+  count_at(g, PLACE, xy, stride, first, (int)n64, t6, c, s, bu, bv, &lds->n_placed, &lds->n_inside);
+  __syncthreads();
+  r.score = (unsigned)(key >> 39);
+  r.score_prior = vol[(g.K * nv + g.V) * nu + g.U];
+  r.score_runner_up = second;
+  r.k = bk, r.u = bu, r.v = bv;
+  r.n_points = (int)lds->n_placed, r.n_inside = (int)lds->n_inside;
+  if (r.score == 0u) r.status = RSX_GRIDMAP_MATCH_STATUS_EMPTY;
+  winner_transform(r.transform, r.score != 0u, t6, c, s, bu, bv, g.res);
+  return r;
+}
+
+// the cells of one rotation (c, s) of a job's n points into LDS: the byte offset of a placed point's cell in the framed plane (frame:
+// its margin in cells), cell (-PLACE, -PLACE) for a point that is not placed, from which no candidate reaches the map.  The caller
+// passes a barrier before it reads them
+__device__ __forceinline__ void fill_cells(const MatchGeo &g, int frame, const float *__restrict__ xy, int64_t stride, int64_t first, int n, const double *t6,
+                                           double c, double s, unsigned *cell) {
+  const unsigned nowhere = (unsigned)(frame - PLACE) * g.pitch + (unsigned)(frame - PLACE);
+  for (int i = threadIdx.x; i < n; i += NT) {
+    const float *p = xy + (first + i) * stride;
+    int ix, iy;
+    cell[i] = place(g, PLACE, t6, c, s, (double)p[0], (double)p[1], &ix, &iy) ? (unsigned)(iy + frame) * g.pitch + (unsigned)(ix + frame) : nowhere;
+  }
 }
 
 }  // namespace gridmatch_dev

@@ -1,12 +1,14 @@
 """Host-side wrapper of the radar grid map entry points of librsx.so (include/rsx.h, rsx_gridmap_*): polar scans and their poses in, the
 radar mosaic (mean power per world cell) and the hit counts out."""
 import ctypes as C
+import weakref
 
 import numpy as np
 
 from . import synth
 from ._rsx import (GRIDMAP_HITS, GRIDMAP_MATCH_RESULT_DTYPE, GRIDMAP_MEAN, GRIDMAP_REFINE_RESULT_DTYPE, GRIDMAP_SEARCH_RESULT_DTYPE,
-                   GridmapFieldParams, GridmapMatchParams, GridmapParams, GridmapRefineParams, GridmapSearchParams, check, lib)
+                   GRIDMAP_TRACK_RESULT_DTYPE, GridmapFieldParams, GridmapMatchParams, GridmapParams, GridmapRefineParams, GridmapSearchParams,
+                   GridmapTrackParams, check, lib)
 from .cfear import ragged
 
 
@@ -82,6 +84,23 @@ def default_field_params():
 def field_params(**fields):
     """default_field_params() with the given fields replaced."""
     return _with_fields(default_field_params(), "rsx_gridmap_field_params", fields)
+
+
+def default_track_params():
+    """a window of rotations -2 .. 2 of 0.01 rad and shifts -2 .. 2 cells, the refinement's defaults, no min_score, predict 1."""
+    p = GridmapTrackParams()
+    check(lib().rsx_gridmap_track_default_params(C.byref(p)))
+    return p
+
+
+def track_params(**fields):
+    """default_track_params() with the given fields replaced: min_score, predict, match or refine (whole structs), or a field of the
+    match part (angle_steps, angle_step, x_cells, y_cells) or of the refine part (damping, ..., max_evaluations) by its own name"""
+    p = default_track_params()
+    for name, value in fields.items():
+        part = next((q for q in (p.match, p.refine) if name != "reserved" and hasattr(q, name)), p)
+        _with_fields(part, "rsx_gridmap_track_params", {name: value})
+    return p
 
 
 def gaussian_table(sigma, radius, peak=255):
@@ -170,6 +189,8 @@ class GridMap:
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
+            for t in list(getattr(self, "_trackers", ())):   # (a tracker reads this map: it goes first)
+                t.close()
             self._L.rsx_gridmap_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -368,4 +389,82 @@ class GridMap:
         p = _choose(params, fields, refine_params)
         n = _device_jobs(xy, offsets, priors, results, GRIDMAP_REFINE_RESULT_DTYPE)
         check(self._L.rsx_gridmap_refine_batch_device(self._h, xy.data_ptr(), offsets.data_ptr(), xy.stride(0), n, priors.data_ptr(), C.byref(p),
+                                                      results.data_ptr(), stream))
+
+    # ---- following a sensor through the map: match, refine and compose in one launch per push (include/rsx.h, rsx_gridmap_tracker_*) ----
+
+    def tracker(self, n_sequences):
+        """a GridTracker of n_sequences sequences in this map, every one at the identity pose; the map must stay open while it is used"""
+        return GridTracker(self, n_sequences)
+
+
+class GridTracker:
+    """n_sequences sensors followed through one GridMap scan after scan (include/rsx.h, rsx_gridmap_tracker_*): per scan a match on the grid
+    around a constant-velocity prediction, the refinement below the cell, and the composed motion; the state stays on the device"""
+
+    def __init__(self, gridmap, n_sequences):
+        self._L = lib()
+        self._h = C.c_void_p()
+        self.map = gridmap          # (kept alive: the tracker reads its plane)
+        self.n_sequences = int(n_sequences)
+        check(self._L.rsx_gridmap_tracker_create(gridmap.handle, self.n_sequences, C.byref(self._h)))
+        if not hasattr(gridmap, "_trackers"):
+            gridmap._trackers = weakref.WeakSet()
+        gridmap._trackers.add(self)   # (GridMap.close closes its trackers first)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.rsx_gridmap_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def reset(self, poses):
+        """poses: (n_sequences, 6) float64 r00, r01, tx, r10, r11, ty -> every sequence starts again at its pose (no motion, no scan seen)"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(self.n_sequences, 6)
+        check(self._L.rsx_gridmap_tracker_reset(self._h, poses.ctypes.data))
+
+    def set_pose(self, q, pose):
+        """sequence q starts again at pose (6,): what follows a search after a lost scan"""
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(6)
+        check(self._L.rsx_gridmap_tracker_set_pose(self._h, int(q), pose.ctypes.data))
+
+    def state(self):
+        """-> poses (n_sequences, 6) float64, motions (n_sequences, 6) float64, counts (n_sequences,) int32"""
+        poses, motions = np.zeros((self.n_sequences, 6)), np.zeros((self.n_sequences, 6))
+        counts = np.zeros(self.n_sequences, dtype=np.int32)
+        check(self._L.rsx_gridmap_tracker_state(self._h, poses.ctypes.data, motions.ctypes.data, counts.ctypes.data))
+        return poses, motions, counts
+
+    def push(self, clouds_per_sequence, params=None, **fields):
+        """clouds_per_sequence: for every sequence the list of its next scans, each (n_i, 2) float32 in the sensor frame (an empty list: no
+        scan for that sequence in this push); params: a GridmapTrackParams, or what track_params takes
+        -> records (total scans,) GRIDMAP_TRACK_RESULT_DTYPE, sequence after sequence in the order given"""
+        assert len(clouds_per_sequence) == self.n_sequences
+        p = _choose(params, fields, track_params)
+        clouds = [c for seq in clouds_per_sequence for c in seq]
+        xy, off = ragged(clouds, np.float32, 2)
+        n_scans = np.array([len(seq) for seq in clouds_per_sequence], dtype=np.int32)
+        res = np.zeros(len(clouds), dtype=GRIDMAP_TRACK_RESULT_DTYPE)
+        check(self._L.rsx_gridmap_tracker_push(self._h, xy.ctypes.data, off.ctypes.data, n_scans.ctypes.data, C.byref(p), res.ctypes.data))
+        return res
+
+    def push_device(self, xy, offsets, n_scans, results, params=None, stream=None, **fields):
+        """the same on torch tensors of the map's device: xy float32 [m, point_stride], offsets int64 (total scans + 1,), n_scans int32
+        (n_sequences,), results uint8 of total scans * 344 bytes (view it as GRIDMAP_TRACK_RESULT_DTYPE on the host).  One launch,
+        asynchronous on `stream` (an int, None = the map's own stream); a scan above the cap is lost with GRIDMAP_MATCH_STATUS_POINTS"""
+        p = _choose(params, fields, track_params)
+        total = offsets.numel() - 1
+        assert xy.dim() == 2 and xy.stride(1) == 1 and xy.element_size() == 4 and offsets.is_contiguous() and offsets.element_size() == 8
+        assert n_scans.is_contiguous() and n_scans.element_size() == 4 and n_scans.numel() == self.n_sequences
+        assert results.is_contiguous() and results.numel() * results.element_size() == total * GRIDMAP_TRACK_RESULT_DTYPE.itemsize
+        check(self._L.rsx_gridmap_tracker_push_device(self._h, xy.data_ptr(), offsets.data_ptr(), xy.stride(0), n_scans.data_ptr(), total, C.byref(p),
                                                       results.data_ptr(), stream))
