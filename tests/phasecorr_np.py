@@ -224,13 +224,15 @@ class Restatement:
         out = []
         for s, d in pairs:
             curve, k0, th0, rot_peak = rotation(spectra[s][1], spectra[d][1], n)
-            best = None
+            best, peaks = None, []
             for c in range(2 if p["resolve_half_turn"] else 1):
                 th = th0 if c == 0 else wrap_pi(th0 + math.pi)
                 surf, ij, dx, dy, peak, ratio = translation(spectra[d][0], cart_image(images[s], col_offset, tab, psi=-th), n)
+                peaks.append(peak)
                 if best is None or peak > best["peak"]:
                     best = dict(x=dx * p["resolution"], y=dy * p["resolution"], theta=th, peak=peak, peak_ratio=ratio, rot_peak=rot_peak,
                                 half_turn=c, status=0, rot_k0=k0, rot_curve=curve, surface=surf, peak_ij=ij)
+            best["other_peak"] = peaks[1 - best["half_turn"]] if len(peaks) == 2 else None   # the losing candidate's peak
             if p["max_rotation"] > 0.0 and abs(best["theta"]) > p["max_rotation"]:
                 best["status"] |= STATUS_ROTATION
             out.append(best)
