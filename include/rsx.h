@@ -218,7 +218,7 @@ int rsx_sc_query(rsx_sc *h, const float *q_descs, int32_t nq, int32_t k, int64_t
 int rsx_sc_query_device(rsx_sc *h, const float *d_q_descs, int32_t nq, int32_t k, int64_t n_eligible,
                         rsx_sc_hit *d_out, void *stream);
 /* Filter shards over a REPLICATED database (the layout that scales when the batch is large and the DB small
- * next to HBM: 0.83 GB per 100 000 keyframes).  Every rank holds every keyframe (shard_world 1); only the lower-bound
+ * next to HBM: 1.43 GB per 100 000 keyframes -- 14 308 B each, 960 B of them the packed columns).  Every rank holds every keyframe (shard_world 1); only the lower-bound
  * filter -- the per-pair cost -- is cut over the ranks by slot range, the per-query stages (short list, window previews,
  * exact re-scoring) run on each rank for ITS slice of the batch against the whole DB:
  *   every rank r   rsx_sc_filter_range_device: all nq queries x slots [first_r, first_r + n_r)  -> d_lb[nq][ld_r]

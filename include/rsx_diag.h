@@ -119,6 +119,21 @@ typedef struct {
 } rsx_sc_rescoring_stats;
 int rsx_sc_profile_read_rescoring(rsx_sc *h, rsx_sc_rescoring_stats *out);
 
+/* The packed columns of the database (rsx.h "Memory"; csrc/sc_kernels.h PackedCol) and the form of the exact re-scoring kernel
+ * that reads them.  A record is 16 bytes, { uint32 bits (bit r = ring r occupied), float val, double norm }, 60 per entry.
+ * An entry is packable when every element of every column is +0.0 or bit-equal to one finite value of that column; the records
+ * of an unpackable entry describe nothing.
+ * rsx_sc_packed_export: the raw records of local slots [first_slot, first_slot + count) into out (count * 960 bytes, host).
+ * rsx_sc_rescore_form: *form = the form the next launch would take, 0 generic, 1 packed; *unpackable = the number of unpackable
+ *   entries as the host knows it (it may over-count, never under-count), -1 = unknown: entries were added by a call that does
+ *   not synchronise (rsx_sc_add_points) and no synchronising call has read the count back since.  The packed form is taken only
+ *   at a known 0.  Either pointer may be null.
+ * rsx_sc_rescore_force_generic: on != 0 keeps the handle on the generic form whatever it knows (tests compare the two forms on
+ *   one database); 0 gives the choice back. */
+int rsx_sc_packed_export(rsx_sc *h, int64_t first_slot, int64_t count, void *out);
+int rsx_sc_rescore_form(rsx_sc *h, int32_t *form, int64_t *unpackable);
+int rsx_sc_rescore_force_generic(rsx_sc *h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("RSX_LIB_PATH") or os.path.join(_HERE, "librsx.so")  #
 
 NUM_RING, NUM_SECTOR, DESC_SIZE, MAX_TOPK = 20, 60, 1200, 32
 MODE_CANDIDATE, MODE_EXHAUSTIVE = 0, 1
+# one column of the packed image of the database (rsx_sc_packed_export, include/rsx_diag.h)
+PACKED_COL_DTYPE = np.dtype([("bits", np.uint32), ("val", np.float32), ("norm", np.float64)])
 FILTER_AUTO, FILTER_OFF, FILTER_FORCE, FILTER_Q1 = 0, 1, 2, 3   # rsx_sc_params.filter_mode
 KIND_AUTO, KIND_DIRECT, KIND_SPECTRAL, KIND_SPECTRAL2 = 0, 1, 2, 3   # rsx_sc_params.filter_kind; KIND_SPECTRAL is a synonym of
                                                                      # KIND_SPECTRAL2 (sc_spec2_filter_kernel), kept for callers
@@ -325,6 +327,7 @@ SYMBOLS = [
     "rsx_sc_pair_distances", "rsx_sc_filter_bounds", "rsx_sc_filter_eps", "rsx_sc_profiled_kernel_name",
     "rsx_sc_merge_topk", "rsx_sc_merge_topk_device", "rsx_sc_hit_to_loop",
     "rsx_sc_dominant_kernel_name", "rsx_sc_profile_enable", "rsx_sc_profile_read", "rsx_sc_profile_read_rescoring", "rsx_sc_window_previews",
+    "rsx_sc_packed_export", "rsx_sc_rescore_form", "rsx_sc_rescore_force_generic",
     "rsx_scs_create", "rsx_scs_create_layout", "rsx_scs_num_query_groups", "rsx_scs_destroy", "rsx_scs_num_shards", "rsx_scs_set_dist_thres", "rsx_scs_size",
     "rsx_scs_add_points", "rsx_scs_add_descriptors_f32", "rsx_scs_get_descriptor", "rsx_scs_query",
     "rsx_scs_detect_loop_closure",
@@ -444,6 +447,9 @@ def lib():
         L.rsx_sc_profile_read.argtypes = [vp, C.POINTER(i64), C.POINTER(dbl)]
         L.rsx_sc_profile_read_rescoring.argtypes = [vp, C.POINTER(RescoringStats)]
         L.rsx_sc_window_previews.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+        L.rsx_sc_packed_export.argtypes = [vp, i64, i64, vp]
+        L.rsx_sc_rescore_form.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+        L.rsx_sc_rescore_force_generic.argtypes = [vp, C.c_int]
         L.rsx_sc_hit_to_loop.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(C.c_float)]
         L.rsx_scs_create.argtypes = [C.POINTER(ScParams), C.POINTER(i32), i32, C.POINTER(vp)]
         L.rsx_scs_create_layout.argtypes = [C.POINTER(ScParams), C.POINTER(i32), i32, i32, i32, C.POINTER(vp)]

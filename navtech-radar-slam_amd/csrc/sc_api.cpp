@@ -39,6 +39,15 @@ struct rsx_sc {
   DevBuf sp, sp_aux; // fp16 spectral filter image + per-entry error-budget scalar (sc_spec.hip)
   DevBuf sp_tw;      // the twiddle table its image kernels read, filled when the handle is created
   DevBuf hnr, vk16, vk_n;  // entry-major fp16 image + fp16 hi/lo sector keys and their norms (sc_window.hip)
+  // packed columns (sc_kernels.h PackedCol) and what the host knows of them.  pk_bad: ONE device counter of the unpackable
+  // entries ever written (it may over-count -- entries overwritten or dropped stay counted -- and never under-counts).
+  // unpackable: its value as last read back, -1 = unknown: an insert that does not synchronise (insert_cloud) leaves it unknown,
+  // a path that synchronises its stream anyway reads the four bytes back in front of that synchronisation (sync_learning).
+  // The query path never reads it: launch_rescore takes the packed form only while the host KNOWS the count is 0.
+  DevBuf pk, pk_bad;
+  PinnedBuf pk_bad_host;
+  int64_t unpackable = 0;
+  bool force_generic = false;  // rsx_sc_rescore_force_generic (rsx_diag.h)
   // detector state (SC.h:104,117-120)
   int tree_counter = 0;
   int64_t tree_size = 0;
@@ -134,11 +143,26 @@ int own_stream(rsx_sc *h) {
 
 // one new entry from a cloud in device memory, all of it in one launch
 int insert_cloud(rsx_sc *h, const void *d_pts, int64_t n_pts, int64_t stride, int64_t slot, hipStream_t s) {
+  h->unpackable = -1;  // unknown until a synchronising path reads the counter back
   return launch_insert(d_pts, nullptr, n_pts, 1, stride, h->p.lidar_height, h->p.max_radius, slot, h->desc.as<float>(),
                        h->vkey.as<double>(), h->norm.as<double>(), h->rkey.as<float>(), h->hn.p, h->hnr.p,
-                       h->cmask.as<uint64_t>(), h->sp.p, h->sp_aux.as<float>(), h->sp_tw.as<double>(), h->vk16.p, h->vk_n.as<float>(), s,
-                       h->p.sum_order);
+                       h->cmask.as<uint64_t>(), h->sp.p, h->sp_aux.as<float>(), h->sp_tw.as<double>(), h->vk16.p, h->vk_n.as<float>(),
+                       h->pk.as<PackedCol>(), h->pk_bad.as<uint32_t>(), s, h->p.sum_order);
 }
+
+// hipStreamSynchronize(s) of a path that is ordered behind every insert (own_stream / use_stream), with the counter of
+// unpackable entries read back in front of it when the host does not know it (always: the caller has just launched kernels
+// that may have moved it)
+int sync_learning(rsx_sc *h, hipStream_t s, bool always = false) {
+  const bool read = always || h->unpackable < 0;
+  if (read) RSX_HIP(hipMemcpyAsync(h->pk_bad_host.p, h->pk_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  RSX_HIP(hipStreamSynchronize(s));
+  if (read) h->unpackable = (int64_t)*static_cast<const uint32_t *>(h->pk_bad_host.p);
+  return RSX_OK;
+}
+
+// the form the next launch_rescore takes
+bool rescore_packed(const rsx_sc *h) { return !h->force_generic && h->unpackable == 0; }
 
 int ensure_capacity(rsx_sc *h, int64_t want_local) {
   if (want_local <= h->cap) return RSX_OK;
@@ -155,6 +179,7 @@ int ensure_capacity(rsx_sc *h, int64_t want_local) {
   RSX_TRY(h->hnr.reserve((size_t)nc * FILTER_DB_BYTES_PER_ENTRY, h->stream, true));
   RSX_TRY(h->vk16.reserve((size_t)nc * 256, h->stream, true));
   RSX_TRY(h->vk_n.reserve((size_t)nc * 2 * sizeof(float), h->stream, true));
+  RSX_TRY(h->pk.reserve((size_t)nc * NS * sizeof(PackedCol), h->stream, true));
   h->cap = nc;
   return RSX_OK;
 }
@@ -172,6 +197,7 @@ DbView db_view(const rsx_sc *h) {
   v.hnR = h->hnr.p;
   v.vk16 = h->vk16.p;
   v.vk_n = h->vk_n.as<float>();
+  v.pk = h->pk.as<PackedCol>();
   v.n_local = h->n_local;
   v.idx_base = h->p.shard_rank;
   v.idx_stride = h->p.shard_world;
@@ -179,14 +205,14 @@ DbView db_view(const rsx_sc *h) {
   return v;
 }
 
-// both filter images + column masks of local slots [slot, slot+count); synchronises s
+// both filter images + column masks + packed columns of local slots [slot, slot+count); synchronises s
 int build_db_images(rsx_sc *h, int64_t slot, int64_t count, hipStream_t s) {
-  RSX_TRY(launch_db_images(h->desc.as<float>(), h->norm.as<double>(), slot, count, h->hn.p, h->hnr.p, h->cmask.as<uint64_t>(), s));
+  RSX_TRY(launch_db_images(h->desc.as<float>(), h->norm.as<double>(), slot, count, h->hn.p, h->hnr.p, h->cmask.as<uint64_t>(),
+                           h->pk.as<PackedCol>(), h->pk_bad.as<uint32_t>(), s));
   RSX_TRY(launch_window_db_keys(h->vkey.as<double>(), slot, count, h->vk16.p, h->vk_n.as<float>(), s));
   RSX_TRY(launch_spec_db_images(h->desc.as<float>(), h->norm.as<double>(), slot, count, h->sp.p, h->sp_aux.as<float>(),
                                 h->sp_tw.as<double>(), s));
-  RSX_HIP(hipStreamSynchronize(s));
-  return RSX_OK;
+  return sync_learning(h, s, true);
 }
 
 bool owns(const rsx_sc *h, int64_t g) { return (g % h->p.shard_world) == h->p.shard_rank; }
@@ -362,7 +388,7 @@ int rescore(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, 
   return launch_rescore(db_view(h), q, h->w->f_lb.as<lb_t>(), ld, n_items, n_eligible, elig, h->w->f_cand.as<RescoreEntry>(),
                         h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), filter_eps(), round_begin, round_end, tau_src,
                         seed, d_out, k, s, (h->prof.on && h->stats.p) ? h->stats.as<unsigned long long>() : nullptr,
-                        h->w->f_surv.as<WindowSurvivor>());
+                        h->w->f_surv.as<WindowSurvivor>(), rescore_packed(h));
 }
 
 int32_t first_round_target() {
@@ -692,6 +718,9 @@ int rsx_sc_create(const rsx_sc_params *p, rsx_sc **out) try {
   // the spectra's twiddle table: once per handle, complete before any other stream can ask for it
   RSX_TRY(h->sp_tw.reserve(SPEC_TWIDDLE_DOUBLES * sizeof(double), h->stream, false));
   RSX_TRY(launch_spec_twiddles(h->sp_tw.as<double>(), h->stream));
+  RSX_TRY(h->pk_bad.reserve(sizeof(uint32_t), h->stream, false));
+  RSX_HIP(hipMemsetAsync(h->pk_bad.p, 0, sizeof(uint32_t), h->stream));
+  RSX_TRY(h->pk_bad_host.reserve(64));
   RSX_HIP(hipStreamSynchronize(h->stream));
   *out = h.release();
   return RSX_OK;
@@ -795,7 +824,7 @@ int rsx_sc_add_points_downsampled(rsx_sc *h, rsx_voxelgrid *vg, const void *pts,
     RSX_TRY(ensure_capacity(h, slot + 1));
     // upload_and_filter synchronised vg's stream: d_ds is complete and stays valid under vg's lock
     RSX_TRY(insert_cloud(h, d_ds ? static_cast<const void *>(d_ds) : h->desc.p, nds, 16, slot, h->stream));
-    RSX_HIP(hipStreamSynchronize(h->stream));  // d_ds belongs to vg: its next call must not overwrite it under the kernel
+    RSX_TRY(sync_learning(h, h->stream));  // d_ds belongs to vg: its next call must not overwrite it under the kernel
     h->n_local = slot + 1;
   }
   h->n_global = g + 1;
@@ -829,7 +858,7 @@ int rsx_sc_add_keyframe(rsx_sc *h, rsx_voxelgrid *vg, rsx_kfstore *kf, const voi
     const int64_t slot = h->n_local;
     RSX_TRY(ensure_capacity(h, slot + 1));
     RSX_TRY(insert_cloud(h, d_ds ? static_cast<const void *>(d_ds) : h->desc.p, nds, 16, slot, h->stream));  // makeAndSaveScancontextAndKeys (PGO.cpp:492)
-    RSX_HIP(hipStreamSynchronize(h->stream));  // d_ds belongs to vg: it must not be overwritten by vg's next call before the build has read it
+    RSX_TRY(sync_learning(h, h->stream));  // d_ds belongs to vg: it must not be overwritten by vg's next call before the build has read it
   }
   int32_t kf_index = -1;
   RSX_TRY(rsx::kf::append_device_locked(kf, d_ds, nds, &kf_index));  // keyframeLaserClouds.push_back (PGO.cpp:487)
@@ -953,6 +982,34 @@ int rsx_sc_export_descriptors_f32(rsx_sc *h, int64_t first_slot, int64_t count, 
   RSX_HIP(hipMemcpyAsync(out, h->desc.as<float>() + first_slot * DS, (size_t)count * DS * sizeof(float), hipMemcpyDeviceToHost,
                          h->stream));
   RSX_HIP(hipStreamSynchronize(h->stream));
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+// ---- diagnostics of the packed columns (rsx_diag.h) ----
+int rsx_sc_packed_export(rsx_sc *h, int64_t first_slot, int64_t count, void *out) try {
+  if (!h || (!out && count)) return fail(RSX_ERR_BAD_ARG, "null arg");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (first_slot < 0 || count < 0 || first_slot + count > h->n_local) return fail(RSX_ERR_RANGE, "slot range out of bounds");
+  if (count == 0) return RSX_OK;
+  RSX_TRY(own_stream(h));
+  RSX_HIP(hipMemcpyAsync(out, h->pk.as<PackedCol>() + first_slot * NS, (size_t)count * NS * sizeof(PackedCol), hipMemcpyDeviceToHost,
+                         h->stream));
+  RSX_HIP(hipStreamSynchronize(h->stream));  // (a diagnostic: what the host knows of the counter stays as it is)
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_sc_rescore_form(rsx_sc *h, int32_t *form, int64_t *unpackable) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null arg");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (form) *form = rescore_packed(h) ? 1 : 0;
+  if (unpackable) *unpackable = h->unpackable;
+  return RSX_OK;
+} RSX_CATCH_ALL
+
+int rsx_sc_rescore_force_generic(rsx_sc *h, int on) try {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null arg");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->force_generic = on != 0;
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -1319,7 +1376,7 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
     }
     RSX_HIP(hipMemcpyAsync(h->q_desc.p, src, q_bytes, hipMemcpyHostToDevice, h->stream));
     RSX_TRY(query_device_locked(h, h->q_desc.as<float>(), nq, k, n_eligible, static_cast<rsx_sc_hit *>(h->pinned.p), h->stream));
-    RSX_HIP(hipStreamSynchronize(h->stream));
+    RSX_TRY(sync_learning(h, h->stream));
     std::memcpy(out, h->pinned.p, out_bytes);
     return RSX_OK;
   }
@@ -1425,8 +1482,7 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
     }
   }
   RSX_HIP(hipMemcpyAsync(out, h->topk.p, (size_t)nq * k * sizeof(rsx_sc_hit), hipMemcpyDeviceToHost, h->stream));
-  RSX_HIP(hipStreamSynchronize(h->stream));
-  return RSX_OK;
+  return sync_learning(h, h->stream);
 } RSX_CATCH_ALL
 
 // ---- filter shards over a replicated database (rsx.h: "filter-shard layout") ----

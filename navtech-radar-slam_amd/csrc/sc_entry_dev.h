@@ -233,6 +233,36 @@ __device__ __forceinline__ void img_db_entry(const float *__restrict__ desc, con
   if (lane == 0) cmask[slot] = m;
 }
 
+// packed columns of one entry (one wave, lane = column; sc_kernels.h PackedCol states when an entry is packable): the record
+// of every column, and one more in *n_unpackable when some column of the entry is not packable
+__device__ __forceinline__ void pack_entry(const float *__restrict__ desc, const double *__restrict__ norm, int64_t slot,
+                                           PackedCol *__restrict__ pk, uint32_t *__restrict__ n_unpackable, int lane) {
+  bool ok = true;
+  if (lane < NS) {
+    const uint4 *p = reinterpret_cast<const uint4 *>(desc + slot * DS + lane * NR);
+    uint32_t bits = 0u, val = 0u;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+      const uint4 v = p[i];
+      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        if (x[j] == 0u) continue;  // +0.0
+        if (!bits) val = x[j];     // the column's first occupied ring sets its value
+        ok = ok && x[j] == val;
+        bits |= 1u << (4 * i + j);
+      }
+    }
+    ok = ok && val != 0x80000000u && (val & 0x7f800000u) != 0x7f800000u;  // no -0.0, no NaN, no inf
+    PackedCol c;
+    c.bits = bits;
+    c.val = __uint_as_float(val);
+    c.norm = norm[slot * NS + lane];
+    pk[slot * NS + lane] = c;
+  }
+  if (__ballot(!ok) && lane == 0) atomicAdd(n_unpackable, 1u);
+}
+
 constexpr double kWinMaxKeyNorm = 4.0e6;
 
 // scaled hi/lo split of one 60-element sector key held one element per lane (lanes >= 60: 0)

@@ -122,6 +122,60 @@ __device__ __forceinline__ void entry_wait(EntryAsync &r, int n_touches, EntryRe
   out.ecol[3] = float4{r.c3.x, r.c3.y, r.c3.z, r.c3.w};
   out.ecol[4] = float4{r.c4.x, r.c4.y, r.c4.z, r.c4.w};
 }
+
+// ---- the same four for an entry of packed columns (sc_kernels.h PackedCol; every entry of the database packable) ----
+// The lane's column is ONE 16-byte record: an entry is 960 contiguous bytes = 7.5 cache lines instead of 46, one load per lane
+// instead of seven and one touch instead of three, 4 registers instead of 24.  The sector key is read by align_exact alone, so
+// it is requested only where the caller says the entry will be aligned (want_key, wave-uniform), together with the record: one
+// round trip for both.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+struct PackedRegs {
+  u32x4 w;   // bits, val, norm (lo, hi)
+  double v;  // the sector key; valid only when it was asked for
+};
+__device__ __forceinline__ double packed_norm(const PackedRegs &r) {
+  return __hiloint2double((int)r.w.w, (int)r.w.z);
+}
+// element r of the column, as the fp64 operand of phase_b32
+__device__ __forceinline__ double packed_elem(const PackedRegs &r, int ring) {
+  return ((r.w.x >> ring) & 1u) ? (double)__uint_as_float(r.w.y) : 0.0;
+}
+__device__ __forceinline__ void load_entry(const DbView &db, int64_t slot, int lane, PackedRegs &r, bool want_key) {
+  const int cl = lane < NS ? lane : 0;
+  r.v = 0.0;
+  if (want_key) r.v = db.vkey[slot * NS + cl];
+  r.w = *reinterpret_cast<const u32x4 *>(db.pk + slot * NS + cl);
+}
+// (60 lanes x 16 B cover every line of the 960 bytes)
+struct TouchPacked {
+  int d0 = 0;
+};
+__device__ __forceinline__ void touch_entry(const DbView &db, int64_t slot, int lane, TouchPacked &t) {
+  const int cl = lane < NS ? lane : 0;
+  const PackedCol *p = db.pk + slot * NS + cl;
+  asm volatile("global_load_dword %0, %1, off" : "+v"(t.d0) : "v"(p) : "memory");
+}
+__device__ __forceinline__ void touch_wait(TouchPacked &t) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(t.d0)::"memory"); }
+// the contract of load_entry_async / entry_wait above, with ONE load per touch behind the entry's one or two
+__device__ __forceinline__ void load_entry_async(const DbView &db, int64_t slot, int lane, PackedRegs &r, bool want_key) {
+  const int cl = lane < NS ? lane : 0;
+  const PackedCol *p = db.pk + slot * NS + cl;
+  const double *pk = db.vkey + slot * NS + cl;
+  r.v = 0.0;
+  if (want_key) asm volatile("global_load_dwordx2 %0, %1, off" : "+v"(r.v) : "v"(pk) : "memory");
+  asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r.w) : "v"(p) : "memory");
+}
+#define RSX_VMCNT_CASE4(n) RSX_VMCNT_CASE(n) RSX_VMCNT_CASE(n + 1) RSX_VMCNT_CASE(n + 2) RSX_VMCNT_CASE(n + 3)
+__device__ __forceinline__ void entry_wait(PackedRegs &r, int n_touches) {
+  switch (n_touches < 60 ? n_touches : 60) {
+    RSX_VMCNT_CASE4(0) RSX_VMCNT_CASE4(4) RSX_VMCNT_CASE4(8) RSX_VMCNT_CASE4(12) RSX_VMCNT_CASE4(16) RSX_VMCNT_CASE4(20)
+    RSX_VMCNT_CASE4(24) RSX_VMCNT_CASE4(28) RSX_VMCNT_CASE4(32) RSX_VMCNT_CASE4(36) RSX_VMCNT_CASE4(40) RSX_VMCNT_CASE4(44)
+    RSX_VMCNT_CASE4(48) RSX_VMCNT_CASE4(52) RSX_VMCNT_CASE4(56)
+    default: asm volatile("s_waitcnt vmcnt(60)" ::: "memory"); break;
+  }
+  asm volatile("" : "+v"(r.w), "+v"(r.v));
+}
+#undef RSX_VMCNT_CASE4
 #undef RSX_VMCNT_CASE
 
 // exact stage 1 of pair_group (fastAlignUsingVkey, SC.cpp:93-113) for one entry: v1 = the query's sector key (60 doubles
@@ -216,19 +270,12 @@ struct WaveLds {
 // exact), half the LDS bytes per column
 // tmask: bit t set = window shift ks - 3 + t is evaluated (wave-uniform; the shifts left out are known to be strictly worse
 // than the best one, so the winner under (distance, shift value) is the same)
-template <int SO = dev::SO_SSE2>
-__device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane, const EntryRegs &er, int ks, unsigned tmask,
-                                          double &bd_out, int &bk_out) {
+// elem(r): element r of the entry's column as a double (r is a constant after unrolling); n2: the column's norm
+template <int SO, class Elem>
+__device__ __forceinline__ void phase_b32_cols(const char *smem, char *wsm, int lane, const Elem &elem, const double n2, int ks,
+                                               unsigned tmask, double &bd_out, int &bk_out) {
   const int cl = lane < NS ? lane : 0;
   const double *qn1 = reinterpret_cast<const double *>(smem + WaveLds::OFF_QN1);
-  wave::lds_fence();
-  double e[NR];
-#pragma unroll
-  for (int i = 0; i < 5; i++) {
-    const float4 v = er.ecol[i];
-    e[4 * i + 0] = v.x; e[4 * i + 1] = v.y; e[4 * i + 2] = v.z; e[4 * i + 3] = v.w;
-  }
-  const double n2 = er.n2;
   double *simp = reinterpret_cast<double *>(wsm + ENT_SIM);
   int *misc = reinterpret_cast<int *>(wsm + ENT_MISC);
 #pragma unroll
@@ -244,15 +291,15 @@ __device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane,
 #pragma unroll
     for (int i = 0; i < 5; i++) {  // element r feeds accumulator r % 4 (Eigen's redux order), as in phase_b
       const float4 q4 = qp[i];
-      da[0] = fma((double)q4.x, e[4 * i + 0], da[0]);
-      da[1] = fma((double)q4.y, e[4 * i + 1], da[1]);
-      da[2] = fma((double)q4.z, e[4 * i + 2], da[2]);
-      da[3] = fma((double)q4.w, e[4 * i + 3], da[3]);
+      da[0] = fma((double)q4.x, elem(4 * i + 0), da[0]);
+      da[1] = fma((double)q4.y, elem(4 * i + 1), da[1]);
+      da[2] = fma((double)q4.z, elem(4 * i + 2), da[2]);
+      da[3] = fma((double)q4.w, elem(4 * i + 3), da[3]);
     }
     double dot = (da[0] + da[2]) + (da[1] + da[3]);
     if constexpr (SO != dev::SO_SSE2) {  // (products of two fp32 values are exact in fp64: fused or not is the same number)
       const float *qf = reinterpret_cast<const float *>(qp);
-      dot = dev::redux_prod<SO, NR>([&](int r) { return (double)qf[r]; }, [&](int r) { return e[r]; });
+      dot = dev::redux_prod<SO, NR>([&](int r) { return (double)qf[r]; }, [&](int r) { return elem(r); });
     }
     const double n1 = qn1[c];
     const bool valid = (lane < NS) && !((n1 == 0.0) | (n2 == 0.0));
@@ -308,6 +355,26 @@ __device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane,
   }
   bd_out = bd;
   bk_out = bk;
+}
+template <int SO = dev::SO_SSE2>
+__device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane, const EntryRegs &er, int ks, unsigned tmask,
+                                          double &bd_out, int &bk_out) {
+  wave::lds_fence();
+  double e[NR];
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    const float4 v = er.ecol[i];
+    e[4 * i + 0] = v.x; e[4 * i + 1] = v.y; e[4 * i + 2] = v.z; e[4 * i + 3] = v.w;
+  }
+  phase_b32_cols<SO>(smem, wsm, lane, [&](int r) { return e[r]; }, er.n2, ks, tmask, bd_out, bk_out);
+}
+// the packed column: element r is (bit r ? (double)val : 0.0), formed where it is multiplied -- the twenty doubles are never
+// held.  The product is formed for an empty ring too: a non-finite query value times 0.0 is NaN, as with the full column.
+template <int SO = dev::SO_SSE2>
+__device__ __forceinline__ void phase_b32(const char *smem, char *wsm, int lane, const PackedRegs &er, int ks, unsigned tmask,
+                                          double &bd_out, int &bk_out) {
+  wave::lds_fence();
+  phase_b32_cols<SO>(smem, wsm, lane, [&](int r) { return packed_elem(er, r); }, packed_norm(er), ks, tmask, bd_out, bk_out);
 }
 
 }  // namespace

@@ -89,17 +89,19 @@ static_assert(QIMG_ODD == FILTER_QIMG_ODD && QIMG_EVEN_CHUNKS * 16 == FILTER_QIM
 static_assert(F_PHASE_BYTES % 1024 == 0, "phase must be whole 1 KiB DMA pieces");
 
 // ------------------------------------------------------------------------------------------
-// database image: fp16, tile-major [tile of 32 entries][75 K-steps][64 lanes][8 halves]
+// database image: fp16, tile-major [tile of 32 entries][75 K-steps][64 lanes][8 halves]; and the packed columns
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sc_img_db_kernel(const float *__restrict__ desc,
                                                         const double *__restrict__ norm, int64_t first,
                                                         int64_t count, uint4 *__restrict__ hnT,
-                                                        uint4 *__restrict__ hnR, u64 *__restrict__ cmask) {
+                                                        uint4 *__restrict__ hnR, u64 *__restrict__ cmask,
+                                                        PackedCol *__restrict__ pk, uint32_t *__restrict__ n_unpackable) {
   __shared__ __attribute__((aligned(16))) _Float16 st[4][DS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t it = (int64_t)blockIdx.x * 4 + wave;
   if (it >= count) return;
   dev::img_db_entry(desc, norm, first + it, st[wave], hnT, hnR, cmask, lane);
+  dev::pack_entry(desc, norm, first + it, pk, n_unpackable, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -742,10 +744,11 @@ double filter_eps() {
 size_t filter_qimg_bytes(int32_t nq) { return (size_t)nq * FILTER_QIMG_BYTES + 1024; }
 
 int launch_db_images(const float *desc, const double *norm, int64_t first, int64_t count, void *hnT, void *hnR,
-                     uint64_t *cmask, hipStream_t s) {
+                     uint64_t *cmask, PackedCol *pk, uint32_t *n_unpackable, hipStream_t s) {
   if (count <= 0) return RSX_OK;
   hipLaunchKernelGGL(sc_img_db_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, desc, norm, first, count,
-                     static_cast<uint4 *>(hnT), static_cast<uint4 *>(hnR), reinterpret_cast<u64 *>(cmask));
+                     static_cast<uint4 *>(hnT), static_cast<uint4 *>(hnR), reinterpret_cast<u64 *>(cmask), pk,
+                     n_unpackable);
   RSX_HIP(hipGetLastError());
   return RSX_OK;
 }

@@ -13,6 +13,18 @@ constexpr int NR = RSX_SC_NUM_RING;
 constexpr int NS = RSX_SC_NUM_SECTOR;
 constexpr int DS = RSX_SC_DESC_SIZE;
 
+// One column of the packed image (DbView::pk).  A radar feature cloud has z = 0, so every occupied bin of a descriptor column
+// holds the same value: the column is 20 bits, that value and its norm.  An entry is PACKABLE when every element of every
+// column is +0.0 (all bits zero) or bit-equal to ONE finite value of that column (the values of two columns may differ); a
+// -0.0, a NaN, an inf or two different non-zero values in a column make it unpackable.  An unpackable entry still has a
+// record (the array has no holes; its content describes nothing) and counts in the handle's counter of unpackable entries.
+struct PackedCol {
+  uint32_t bits;  // bit r = ring r of the column is occupied (element != +0.0)
+  float val;      // the value of the occupied rings (+0.0: empty column)
+  double norm;    // DbView::norm of the column
+};
+static_assert(sizeof(PackedCol) == 16, "one 16-byte load per column");
+
 // One database shard in HBM (SoA, see DESIGN.md "Data layout"):
 struct DbView {
   const float *desc;   // [n_local][60][20] fp32, sector-major == Eigen col-major order
@@ -26,6 +38,7 @@ struct DbView {
   const void *hnR;     // the fp16 filter image once more, entry-major [n_local][1200] (sc_window.hip gathers single entries)
   const void *vk16;    // [n_local][128] fp16: sector key scaled by a power of two, hi[64] | lo[64] (sc_window.hip)
   const float *vk_n;   // [n_local][2] l2 norm of the scaled key (NaN: no matrix-core alignment for this entry), of the key
+  const PackedCol *pk; // [n_local][60] packed columns, 960 B per entry (the packed form of sc_rescore_wave_kernel)
   int64_t n_local;
   int64_t idx_base;    // global index of local slot s = idx_base + s * idx_stride
   int64_t idx_stride;
@@ -100,7 +113,7 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
 int launch_insert(const void *d_pts, const int64_t *d_offs, int64_t n_pts, int64_t n_clouds, int64_t stride_bytes,
                   double lidar_height, double max_radius, int64_t first_slot, float *desc, double *vkey, double *norm,
                   float *rkey, void *hnT, void *hnR, uint64_t *cmask, void *spT, float *aux, const double *tw, void *vk16,
-                  float *vk_n, hipStream_t s, int sum_order);
+                  float *vk_n, PackedCol *pk, uint32_t *n_unpackable, hipStream_t s, int sum_order);
 
 // merge [nparts][nq][k] -> [nq][k]
 int launch_merge(const rsx_sc_hit *d_parts, int32_t nparts, int32_t nq, int32_t k, rsx_sc_hit *d_out,
@@ -159,12 +172,14 @@ int launch_select(const DbView &db, const lb_t *lb, int64_t ld_lb, int64_t n_ite
 // surv: the survivor lists launch_window wrote for the same short lists (what of the head of every list is left to score);
 // tau_src (optional): a top-k that covers more than this shard -- its k-th distance caps tau;
 // seed (optional): this shard's hits from an earlier stage, merged into the output.
+// packed: every entry of db is packable (PackedCol) -- the kernel reads db.pk instead of db.desc / db.norm and the sector key
+// only where it aligns; same records, same statistics
 constexpr int RESCORE_ALL_ROUNDS = RESCORE_NUM_THR + 1;
 int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t ld_lb, int64_t n_items,
                    int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
                    const float *thr, double eps, int32_t round_begin, int32_t round_end, const rsx_sc_hit *tau_src,
                    const rsx_sc_hit *seed, rsx_sc_hit *d_out, int32_t k, hipStream_t s, unsigned long long *d_stats,
-                   const WindowSurvivor *surv);
+                   const WindowSurvivor *surv, bool packed);
 
 // ---- MFMA lower-bound filter (sc_filter.hip) ----
 constexpr int FILTER_QIMG_BYTES = 9984;  // LDS image of one query (two displaced fp16 copies)
@@ -174,9 +189,10 @@ constexpr float FILTER_ACC_SCALE = 1073741824.0f;  // 2^30: both fp16 images are
 constexpr int FILTER_DB_BYTES_PER_ENTRY = 2 * DS;
 double filter_eps();
 size_t filter_qimg_bytes(int32_t nq);
-// fp16 filter images of local slots [first, first+count) (needs their norms)
+// fp16 filter images and packed columns of local slots [first, first+count) (needs their norms); *n_unpackable (device) grows
+// by the number of these entries that are not packable
 int launch_db_images(const float *desc, const double *norm, int64_t first, int64_t count, void *hnT, void *hnR,
-                     uint64_t *cmask, hipStream_t s);
+                     uint64_t *cmask, PackedCol *pk, uint32_t *n_unpackable, hipStream_t s);
 int launch_query_images(const float *desc, const double *norm, int32_t nq, void *qimg, hipStream_t s);
 // lb[q*ld_lb + slot] = lower bound of dist(query q, local slot), slots [0, n_items); +inf when no
 // shift has an effective column (never a hit), -inf when the pair must be re-scored regardless

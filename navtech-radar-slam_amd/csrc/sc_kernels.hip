@@ -8,7 +8,8 @@
 //                     kd-tree candidates, rsx_sc_pair_distances)
 //   sc_pair2_kernel   the same in top-k form, in two phases (fp32 alignment + preview, then exact fp64)
 //   sc_rescore_wave_kernel  the exact distances of the entries the MFMA filter (sc_filter.hip / sc_spec.hip) and
-//                     the window previews (sc_window.hip) could not exclude (batched exhaustive queries)
+//                     the window previews (sc_window.hip) could not exclude (batched exhaustive queries); in two forms:
+//                     <SO, false> reads the fp32 descriptor, <SO, true> the packed columns of an all-packable database
 //   sc_merge_kernel   the strict-< "first wins" candidate loop           SC.cpp:380-395 (generalised to top-k)
 //   sc_knn_kernel     nanoflann 3-NN on ring keys                        SC.cpp:367-374, NF.hpp:383-408
 //
@@ -38,6 +39,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "rsx_common.h"
 #include "sc_kernels.h"
@@ -1062,8 +1064,15 @@ int launch_pairs(const DbView &db, const QueryView &q, const int32_t *gather, in
 #ifndef RW_OCC
 #define RW_OCC 3  // waves per SIMD the register budget is set for (168 VGPRs; the kernel takes 151, none spilled; 4 = 128 VGPRs had 98 spilled: 0.42 against 0.24 ms)
 #endif
-template <int SO>
-__global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs a) {
+// PACKED: the form for a database whose entries are all packable (sc_kernels.h PackedCol, sc_exact_dev.h PackedRegs): the same
+// walk, the same operations in the same order, the entries read as 16-byte columns.  launch_rescore picks it.
+#ifndef RW_OCC_PACKED
+#define RW_OCC_PACKED 4  // 128 VGPRs: <0> takes them all with 3 dwords spilled outside the evaluation loops, <1> 111, <2> 125, <3> 127; at 9.0 KiB of LDS 16 waves per CU fit: 132.5-133.7 us against 141.9-142.4 at 3 (131 VGPRs) and 174 generic
+#endif
+template <int SO, bool PACKED = false>
+__global__ __launch_bounds__(64, PACKED ? RW_OCC_PACKED : RW_OCC) void sc_rescore_wave_kernel(RescoreArgs a) {
+  using Regs = typename std::conditional<PACKED, PackedRegs, EntryRegs>::type;
+  using Tch = typename std::conditional<PACKED, TouchPacked, Touch>::type;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if (a.stats) a.stats += (blockIdx.x % RESCORE_STAT_COPIES) * RESCORE_STAT_WORDS;
   const int lane = threadIdx.x;
@@ -1161,7 +1170,12 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
     tacc[slot_] += t - t_mark;
     t_mark = t;
   };
-  auto eval = [&](int64_t slot, int ksm, const EntryRegs &er) {
+  // an entry's registers; want_key: it will be aligned exactly (the packed form asks for the sector key only then)
+  auto fetch = [&](int64_t slot, bool want_key, Regs &r) {
+    if constexpr (PACKED) load_entry(a.db, slot, lane, r, want_key);
+    else load_entry(a.db, slot, lane, r);
+  };
+  auto eval = [&](int64_t slot, int ksm, const Regs &er) {
     if (timing) {
       lap(2);  // [6] since the last lap: picking / requesting
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1266,29 +1280,35 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
         ks = wave::readlane(myks, src);
         return wave::readlane(mylo, src);
       };
-      EntryRegs cur, nxt;
+      Regs cur, nxt;
       int32_t cur_slot = 0, nxt_slot = 0;
       int cur_ks = -1, nxt_ks = -1;
       int rank_next = 0;
       float cur_lo = ranked(rank_next++, cur_slot, cur_ks);
-      Touch tch;
+      Tch tch;
       // The first survivor's registers are requested AHEAD of the round's touches and waited for alone (VMEM returns in order):
       // it is evaluated while the round trip of the touches runs.  It is always evaluated -- `mine` holds !(lo > t_now), and tau
       // has not moved since.  The touch registers stay reserved until touch_wait behind that evaluation.
       bool touching = cur_lo < INFINITY;
       if (touching) {
-        EntryAsync ea;
-        load_entry_async(a.db, cur_slot, lane, ea);
         const unsigned long long rest = todo & ~__ballot(mine && myrank == 0);
-        for (unsigned long long m = rest; m; m &= m - 1) touch_entry(a.db, wave::readlane(myslot, __ffsll((long long)m) - 1), lane, tch);
-        entry_wait(ea, __popcll(rest), cur);
+        if constexpr (PACKED) {
+          load_entry_async(a.db, cur_slot, lane, cur, cur_ks < 0);
+          for (unsigned long long m = rest; m; m &= m - 1) touch_entry(a.db, wave::readlane(myslot, __ffsll((long long)m) - 1), lane, tch);
+          entry_wait(cur, __popcll(rest));
+        } else {
+          EntryAsync ea;
+          load_entry_async(a.db, cur_slot, lane, ea);
+          for (unsigned long long m = rest; m; m &= m - 1) touch_entry(a.db, wave::readlane(myslot, __ffsll((long long)m) - 1), lane, tch);
+          entry_wait(ea, __popcll(rest), cur);
+        }
       }
       lap(1);  // [5]
       while (cur_lo < INFINITY) {
         const double t_eff = tau < tau_ub ? tau : tau_ub;
         if ((double)cur_lo > t_eff) break;  // exact >= lower bound > an upper bound of the k-th best; the rest is larger still
         const float nxt_lo = ranked(rank_next++, nxt_slot, nxt_ks);
-        if (nxt_lo < INFINITY && !((double)nxt_lo > t_eff)) load_entry(a.db, nxt_slot, lane, nxt);
+        if (nxt_lo < INFINITY && !((double)nxt_lo > t_eff)) fetch(nxt_slot, nxt_ks < 0, nxt);
         eval(cur_slot, cur_ks, cur);
         if (touching) {  // (uniform) the touches of this round and the next survivor's registers have landed
           touch_wait(tch);
@@ -1324,8 +1344,8 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
       if ((double)lb - a.eps > tau) continue;  // (NaN / -inf bounds: always scored)
       const int64_t gidx = a.db.idx_base + (int64_t)slot * a.db.idx_stride;
       if (!(gidx < n_elig)) continue;
-      EntryRegs er;
-      load_entry(a.db, slot, lane, er);
+      Regs er;
+      fetch(slot, true, er);
       n_looked++;
       eval(slot, -1, er);
     }
@@ -1370,8 +1390,8 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
             const float dl = __shfl(d[u], l);
             if ((double)dl - a.eps > tau) continue;  // (NaN / -inf bounds: always scored)
             const int64_t slot = pos + 64 * u + l;
-            EntryRegs er;
-            load_entry(a.db, slot, lane, er);
+            Regs er;
+            fetch(slot, true, er);
             n_looked++;
             n_tail++;
             eval(slot, -1, er);
@@ -1401,8 +1421,8 @@ __global__ __launch_bounds__(64, RW_OCC) void sc_rescore_wave_kernel(RescoreArgs
         bal &= bal - 1;
         const float dl = __shfl(d, l);
         if ((double)dl - a.eps > tau) continue;
-        EntryRegs er;
-        load_entry(a.db, pos + l, lane, er);
+        Regs er;
+        fetch(pos + l, true, er);
         n_looked++;
         eval(pos + l, -1, er);
       }
@@ -1440,7 +1460,7 @@ int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t
                    int64_t n_eligible, const int64_t *q_elig, const RescoreEntry *slist, const int32_t *sl_cnt,
                    const float *thr, double eps, int32_t round_begin, int32_t round_end, const rsx_sc_hit *tau_src,
                    const rsx_sc_hit *seed, rsx_sc_hit *d_out, int32_t k, hipStream_t s, unsigned long long *d_stats,
-                   const WindowSurvivor *surv) {
+                   const WindowSurvivor *surv, bool packed) {
   if (q.nq <= 0) return RSX_OK;
   if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k=%d out of range [1,%d]", k, RSX_SC_MAX_TOPK);
   RescoreArgs a;
@@ -1463,7 +1483,11 @@ int launch_rescore(const DbView &db, const QueryView &q, const lb_t *lb, int64_t
   a.round_end = round_end;
   a.stats = d_stats;
   a.surv = surv;
-  RSX_SO_DISPATCH(db.sum_order, hipLaunchKernelGGL(sc_rescore_wave_kernel<SO>, dim3(q.nq), dim3(64), WaveLds::SIZE, s, a));
+  if (packed) {
+    RSX_SO_DISPATCH(db.sum_order, hipLaunchKernelGGL((sc_rescore_wave_kernel<SO, true>), dim3(q.nq), dim3(64), WaveLds::SIZE, s, a));
+  } else {
+    RSX_SO_DISPATCH(db.sum_order, hipLaunchKernelGGL((sc_rescore_wave_kernel<SO, false>), dim3(q.nq), dim3(64), WaveLds::SIZE, s, a));
+  }
   RSX_HIP(hipGetLastError());
   return RSX_OK;
 }

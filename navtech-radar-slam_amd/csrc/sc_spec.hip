@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void sc_spec_db_kernel(const float *__restrict
 // One new keyframe in ONE launch (the reference's makeAndSaveScancontextAndKeys, SC.cpp:229-247, plus everything the
 // query path keeps per entry): the 256-thread block builds the descriptor and its keys from the cloud (sc_entry_dev.h
 // build_block == sc_build_kernel), then wave 0 writes the spectral image, wave 1 the fp16 image (tile-major and
-// entry-major) and wave 2 the fp16 sector-key image.  Before round 4 these were four dependent launches of one block or one
+// entry-major), wave 2 the fp16 sector-key image and wave 3 the packed columns.  Before round 4 these were four dependent launches of one block or one
 // wave each (9 + 4.6 + 10 + 4.5 us of kernels, ~60 us per insert with their gaps and the synchronise).
 // blockIdx.x = cloud: points [offs[b], offs[b + 1]) of pts (offs = nullptr: one cloud of n_pts points), slot first + b.
 // ------------------------------------------------------------------------------------------
@@ -323,6 +323,8 @@ struct InsertArgs {
   const double *tw;  // the twiddle table of the spectra
   _Float16 *vk16;
   float *vk_n;
+  PackedCol *pk;
+  uint32_t *n_unpackable;
 };
 
 template <int SO>
@@ -356,6 +358,8 @@ __global__ __launch_bounds__(256) void sc_insert_kernel(InsertArgs a) {
     dev::img_db_entry(a.desc, a.norm, slot, st, a.hnT, a.hnR, a.cmask, lane);
   } else if (wave == 2) {
     dev::win_db_keys_entry(a.vkey, slot, a.vk16, a.vk_n, lane);
+  } else {
+    dev::pack_entry(a.desc, a.norm, slot, a.pk, a.n_unpackable, lane);
   }
 }
 
@@ -1203,7 +1207,7 @@ int launch_spec_query_images(const float *desc, const double *norm, int32_t nq, 
 int launch_insert(const void *d_pts, const int64_t *d_offs, int64_t n_pts, int64_t n_clouds, int64_t stride_bytes,
                   double lidar_height, double max_radius, int64_t first_slot, float *desc, double *vkey, double *norm,
                   float *rkey, void *hnT, void *hnR, uint64_t *cmask, void *spT, float *aux, const double *tw, void *vk16,
-                  float *vk_n, hipStream_t s, int sum_order) {
+                  float *vk_n, PackedCol *pk, uint32_t *n_unpackable, hipStream_t s, int sum_order) {
   if (n_clouds <= 0) return RSX_OK;
   InsertArgs a;
   a.pts = static_cast<const char *>(d_pts);
@@ -1225,6 +1229,8 @@ int launch_insert(const void *d_pts, const int64_t *d_offs, int64_t n_pts, int64
   a.tw = tw;
   a.vk16 = static_cast<_Float16 *>(vk16);
   a.vk_n = vk_n;
+  a.pk = pk;
+  a.n_unpackable = n_unpackable;
   RSX_SO_DISPATCH(sum_order, hipLaunchKernelGGL(sc_insert_kernel<SO>, dim3((unsigned)n_clouds), dim3(256), 0, s, a));
   RSX_HIP(hipGetLastError());
   return RSX_OK;

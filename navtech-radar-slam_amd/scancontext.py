@@ -234,6 +234,23 @@ class SCManager:
         check(self._L.rsx_sc_export_descriptors_f32(self._h, first_slot, count, out.ctypes.data))
         return out
 
+    def packed_export(self, first_slot=0, count=None):
+        """packed columns of local slots [first_slot, first_slot + count) -> (count, 60) of _rsx.PACKED_COL_DTYPE."""
+        if count is None:
+            count = self.local_size - first_slot
+        out = np.empty((count, 60), dtype=_rsx.PACKED_COL_DTYPE)
+        check(self._L.rsx_sc_packed_export(self._h, first_slot, count, out.ctypes.data))
+        return out
+
+    def rescore_form(self):
+        """-> (form the next re-scoring launch takes: 0 generic, 1 packed; unpackable entries as the host knows them, -1 unknown)"""
+        form, n = C.c_int32(), C.c_int64()
+        check(self._L.rsx_sc_rescore_form(self._h, C.byref(form), C.byref(n)))
+        return form.value, n.value
+
+    def rescore_force_generic(self, on=True):
+        check(self._L.rsx_sc_rescore_force_generic(self._h, 1 if on else 0))
+
     def save(self, path):
         check(self._L.rsx_sc_save(self._h, os.fsencode(path)))
 
