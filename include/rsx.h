@@ -1847,7 +1847,7 @@ int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params);
  * is out of scope.  rsx_odometry_set_compensation, which compensates MATCHES, still refuses while CFEAR is selected. */
 int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_params *params);
 /* Phase correlation (rsx_phasecorr above) in the window pipeline, in one of two modes.  Accepted only while the handle holds no scan;
- * params = NULL goes back to the state before (ESTIMATE: the estimator it took the place of; FALLBACK: no fallback).  pc is judged by
+ * params = NULL switches it off (the selected estimator, which ESTIMATE stands in for but never replaces, alone).  pc is judged by
  * the rules of rsx_phasecorr_params against the handle's rows and cols (RSX_ERR_BAD_ARG), after pc.range_resolution has been
  * overwritten with (double)radar_resolution of the handle; negative or non-finite gates and an unknown mode are refused too.  Refused
  * while compensation is on and while the CFEAR tracker is on (both modes), and rsx_odometry_set_compensation and

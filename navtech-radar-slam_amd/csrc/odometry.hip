@@ -5,36 +5,19 @@
 // -> ORB descriptors -> BFMatcher knnMatch(2) + ratio against the previous scan -> ORORA (GNC rotation, A-COTE
 // translation) -> pose composition.  The sequence is on disk, so every scan and every consecutive pair is independent
 // until the final composition: a WINDOW of n scans goes through each stage in ONE launch chain --
-//     rsx_<extractor>_extract_batch_device      n images   the ONE selected extractor (rsx_odometry::keypoints): cen2019
-//                                               (csrc/cen2019.hip) until rsx_odometry_set_cen2018 (csrc/cen2018.hip) or
-//                                               rsx_odometry_set_kstrongest (csrc/kstrongest.hip) or rsx_odometry_set_cfar
-//                                               (csrc/cfar.hip) selects another
-//     rsx_frontend_cartesian_batch_device       n images   (csrc/frontend.hip)
-//     rsx_frontend_describe_batch_device        n keypoint sets
-//     rsx_frontend_match_consecutive_device     all consecutive pairs, both directions
-//     odo_cross / odo_gather                    cross check (the two directions must agree) + correspondence lists
-//     rsx_orora_register_batch_device           all pairs of the window in one call (csrc/orora.hip): max-clique inlier
-//                                               selection (csrc/pmc.hip, RSX_ORORA_PMC: on by default here) + the solver
-//                                               (or rsx_ransac_estimate_batch_device, csrc/ransac.hip, after
-//                                               rsx_odometry_set_estimator: no selection; MC-RANSAC also gets a dt per match)
-//     (rsx_odometry_set_cfear: CFEAR's own pipeline, csrc/cfear.hip)   after the extractor the surface points of every scan
-//                                               (one launch per window); the Cartesian images, the descriptors, the matcher, the
-//                                               cross check and the selection do not run, and the consecutive pairs are
-//                                               registered point-to-line in one launch, src = this scan, dst = the previous one
-//     (rsx_odometry_set_phasecorr: csrc/phasecorr.hip)   after the extractor the spectra of every scan (launches 1 - 3 of a
-//                                               phase-correlation batch, into the set's slots; the last scan's are carried to the
-//                                               next set beside the keypoints).  ESTIMATE: nothing else runs, and the consecutive
-//                                               pairs are registered by launches 4 - 9, src = this scan, dst = the previous one.
-//                                               FALLBACK: the selected estimator's chain runs unchanged, then launches 4 - 9 over the
-//                                               pairs it failed on, whose records are replaced
-//     (rsx_odometry_set_compensation only)      the matches of every pair compensated with the pose the estimator just gave that
-//                                               pair (csrc/mocomp.hip), the estimator once more on them, and the keypoints of
-//                                               every scan compensated with its pair's second pose for out_xy
+//     the ONE selected extractor (rsx_odometry::keypoints: cen2019 until rsx_odometry_set_cen2018 / _kstrongest / _cfar selects another),
+//     Cartesian images, descriptors, consecutive matches in both directions, cross check + correspondence lists (odo_cross / odo_gather),
+//     and ORORA over all pairs of the window in one call, max-clique selection first (DESIGN.md 4.11 names every launch).
+// That is the default configuration.  The setters of the estimator side (rsx_odometry_set_estimator, _set_cfear, _set_cfear_tracking,
+// _set_compensation, _set_phasecorr) change ONE value, OdoConfig, under the rules of check_config; what a configuration builds per scan,
+// which pair stage registers the consecutive pairs (src = this scan, dst = the previous one) and what is carried to the next window is
+// answered once per push by needs_of -- OdoNeeds below says it field by field, and enqueue_match has one branch per pair stage
 // -- with every intermediate (keypoints, descriptors, matches, correspondences) in HBM; one upload of the images and one
 // download of 48 bytes per scan (+ the keypoints when the caller wants /orora/cloud_local).  The last scan of a window
 // stays on the device as the "previous scan" of the next one.  Pose composition stays on the host (sequential, trivial).
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -297,7 +280,8 @@ __global__ __launch_bounds__(64) void odo_pc_results(const rsx_phasecorr_result 
 // Round 6: several windows in flight.  A window is two stages: EXTRACTION (cen2019, Cartesian images, descriptors: the wide
 // kernels, independent of every other window) and MATCHING (consecutive matches, cross check, max-clique selection, solver:
 // a chain of small grids -- one or two workgroups per pair -- that leaves most of the device idle, and the only stage that
-// needs the previous window).  While window g is matched, windows g + 1 AND g + 2 are extracted, on two extraction LANES (a
+// needs the previous window); what the two are under another configuration, OdoNeeds below says.
+// While window g is matched, windows g + 1 AND g + 2 are extracted, on two extraction LANES (a
 // stream, a cen2019 handle and a front-end handle each; window g takes lane g & 1): the extraction chain has its own narrow
 // launches (the selection kernels of cen2019: one workgroup per image) that a second chain fills -- two independent handles
 // on one device reach 66.7 k scans/s where one with a single lane reaches 59.3 k.  What the stages hand over -- keypoints,
@@ -307,6 +291,29 @@ __global__ __launch_bounds__(64) void odo_pc_results(const rsx_phasecorr_result 
 //   matching stream:   M(g):   [wait E(g), E(g-1)]  match, cross, gather, select + solve -> pinned results g%3
 // The host enqueues M(g), then E(g + 2), and only then waits for M(g).
 constexpr int N_SETS = 3, N_LANES = 2;
+
+// what the setters of the estimator side select: the ONE value they change, and only to one that check_config accepts
+struct OdoConfig {
+  int estimator = RSX_ESTIMATOR_ORORA;  // the SELECTED estimator: ORORA, RANSAC, MCRANSAC or CFEAR, never PHASECORR
+  bool track = false;  // rsx_odometry_set_cfear_tracking: the keyframe tracker in place of the pair registration
+  bool comp = false;  // rsx_odometry_set_compensation
+  enum class Pc : uint8_t { off, estimate, fallback } pc = Pc::off;  // rsx_odometry_set_phasecorr: in place of the selected estimator | beside it
+};
+
+// what a configuration needs, every question asked once (needs_of) per push: the stages below read these answers, never the configuration
+enum class PairStage { features, cfear_pairs, cfear_track, phasecorr };
+struct OdoNeeds {
+  PairStage stage;  // M(g): matcher, cross check + the estimator | one CFEAR registration launch | one CFEAR tracker launch | phase correlation
+  bool desc;  // E(g): Cartesian images and descriptors; the keypoints (xy, counts, desc, valid) are carried
+  bool sp, sp_times;  // E(g): CFEAR's surface points, carried; with the records' times (the tracker's compensation)
+  bool spectra;  // E(g): the phase-correlation spectra, carried
+  size_t pc_F, pc_A;  // bytes of a slot of the two spectrum arrays (0 without spectra)
+  bool ransac;  // features: a RANSAC estimator in place of ORORA
+  bool match_dt;  // features: the azimuth rows of a match gathered as its dt (MC-RANSAC)
+  bool match_rows;  // features: gathered as rows (compensation: a second pass on the compensated matches into results2, out_xy from xy_comp)
+  bool fallback;  // M(g): phase correlation once more, over the pairs the stage failed on
+};
+
 struct OdoSet {
   rsx::DevBuf az, targets, xy, counts, desc, valid;  // slot 0 = the previous scan, slots 1 .. MAX_WINDOW = the window (whichever extractor wrote them)
   rsx::DevBuf sp, sp_counts, pt_begin, pt_end;  // CFEAR only: surface points [slot][RSX_CFEAR_MAX_SURFACE_POINTS], their counts, the point ranges
@@ -331,29 +338,22 @@ struct rsx_odometry {
   rsx_cfar_params cfar_prm{};
   rsx::Owned<rsx_frontend, rsx_frontend_destroy> fe[N_LANES];
   rsx::Owned<rsx_orora, rsx_orora_destroy> reg;
-  int estimator = RSX_ESTIMATOR_ORORA;
+  OdoConfig cfg;
   rsx::Owned<rsx_ransac, rsx_ransac_destroy> ransac;  // created at the first rsx_odometry_set_estimator that asks for one
   rsx_ransac_params ransac_prm{};
   rsx::DevBuf ransac_res, stage_dt, dt;  // allocated only with a RANSAC estimator (stage_dt, dt: MC-RANSAC)
-  rsx_cfear_params cfear_prm{};  // estimator == RSX_ESTIMATOR_CFEAR (rsx_odometry_set_cfear)
+  rsx_cfear_params cfear_prm{};  // rsx_odometry_set_cfear
   rsx::DevBuf cfear_res, sp_begin, sp_end;  // allocated only with CFEAR: results of a window, the record ranges of its slots
   rsx::DevBuf cfear_index;  // CFEAR without tracking: the cell-index workspace of a window's pair registration (20 MiB)
-  bool track_on = false;  // rsx_odometry_set_cfear_tracking: the keyframe tracker in place of the pair registration
   rsx_cfear_track_params track_prm{};
   rsx::DevBuf track_state, track_res, track_n, track_prev;  // allocated only with tracking: the sequence's state (csrc/cfear_track.hip), a
                                                             // window's results, its scan count, the pose of the scan before it
-  bool comp_on = false;  // rsx_odometry_set_compensation
   rsx_mocomp_params comp_prm{};
   rsx::DevBuf stage_acur, stage_aprev, a_cur, a_prev, src2, dst2, results2, xy_comp;  // allocated only with compensation
-  // rsx_odometry_set_phasecorr: ESTIMATE is estimator == RSX_ESTIMATOR_PHASECORR (pc_saved: the estimator it took the place of),
-  // FALLBACK is pc_fallback beside whichever estimator is selected
-  bool pc_fallback = false;
-  int pc_saved = RSX_ESTIMATOR_ORORA;
   rsx_odometry_phasecorr_params pc_prm{};
   rsx_phasecorr_params pc_tables_of{};  // what pc_tables was made for (n == 0: nothing yet)
   rsx::DevBuf pc_tables, pc_work, pc_pairs, pc_res;  // one set of tables for both lanes and the matching stream; a window's pair workspace, list and results
   struct { const uint8_t *d_imgs; int64_t image_stride; int32_t row_stride; } pc_imgs[N_SETS]{};  // where E(g) read window g's images: M(g) samples them again
-  bool pc_on() const { return pc_fallback || estimator == RSX_ESTIMATOR_PHASECORR; }
   OdoSet set[N_SETS];
   rsx::DevBuf imgs[N_SETS], fwd, bwd, stage_src, stage_dst, pair_cnt, src, dst, offsets, results;
   uint64_t windows = 0;  // windows enqueued since creation: window g works in set[g % N_SETS] on lane g & 1
@@ -369,60 +369,102 @@ constexpr size_t PIN_COUNTS = 0, PIN_PAIRS = 4 * (MAX_WINDOW + 1), PIN_RES = PIN
                  PIN_AZ = (PIN_RES + sizeof(rsx_orora_result) * MAX_WINDOW + 255) / 256 * 256;
 size_t pin_bytes(const rsx_odometry *h) { return PIN_AZ + (size_t)h->rows * 4 * MAX_WINDOW; }
 
-int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
+using Pc = OdoConfig::Pc;
+
+// the rules of a configuration, each once: RSX_OK, or the first one `c` breaks (its message names the calls that lift the conflict)
+int check_config(const OdoConfig &c) {
+  const bool cfear = c.estimator == RSX_ESTIMATOR_CFEAR, pc = c.pc != Pc::off;
+  if (c.track && !cfear) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is not selected (rsx_odometry_set_cfear first)");
+  if (c.comp && c.estimator == RSX_ESTIMATOR_MCRANSAC)
+    return fail(RSX_ERR_BAD_ARG, "compensation and motion-compensated RANSAC exclude each other: it has its own motion model "
+                                 "(rsx_odometry_set_compensation(h, NULL) or rsx_odometry_set_estimator with another estimator first)");
+  if (c.comp && cfear)
+    return fail(RSX_ERR_BAD_ARG, "compensation and CFEAR registration exclude each other: CFEAR has no matches to compensate "
+                                 "(rsx_odometry_set_compensation(h, NULL) or rsx_odometry_set_cfear(h, NULL) first)");
+  if (c.comp && pc)
+    return fail(RSX_ERR_BAD_ARG, "compensation and phase correlation exclude each other: phase correlation reads the scans as measured "
+                                 "(rsx_odometry_set_compensation(h, NULL) or rsx_odometry_set_phasecorr(h, NULL) first)");
+  if (c.track && pc)
+    return fail(RSX_ERR_BAD_ARG, "the CFEAR tracker and phase correlation, estimator or fallback, exclude each other: the tracker has no pairs "
+                                 "(rsx_odometry_set_cfear_tracking(h, NULL) or rsx_odometry_set_phasecorr(h, NULL) first)");
+  return RSX_OK;
+}
+
+OdoNeeds needs_of(const rsx_odometry *h) {
+  const OdoConfig &c = h->cfg;
+  OdoNeeds n{};
+  n.stage = c.pc == Pc::estimate                  ? PairStage::phasecorr
+            : c.estimator != RSX_ESTIMATOR_CFEAR ? PairStage::features
+            : c.track                            ? PairStage::cfear_track
+                                                 : PairStage::cfear_pairs;
+  const bool features = n.stage == PairStage::features;
+  n.desc = features;  // (phase correlation as the estimator reports the keypoints and matches none: no descriptors, nothing of them carried)
+  n.sp = n.stage == PairStage::cfear_pairs || n.stage == PairStage::cfear_track;
+  n.sp_times = n.stage == PairStage::cfear_track && h->track_prm.compensate;
+  n.spectra = c.pc != Pc::off;  // (slot 0 of a set is only read while the handle holds a scan, and N cannot change then)
+  if (n.spectra) rsx::phasecorr::workspace_bytes(h->pc_prm.pc.n, &n.pc_F, &n.pc_A, nullptr);
+  n.ransac = features && c.estimator != RSX_ESTIMATOR_ORORA;
+  n.match_dt = features && c.estimator == RSX_ESTIMATOR_MCRANSAC;
+  n.match_rows = features && c.comp;
+  n.fallback = c.pc == Pc::fallback;  // (never with compensation or the tracker: the records it replaces are h->results)
+  return n;
+}
+
+// the arrays of an OdoSet with a slot per scan (slot 0 = the previous scan), in the order the carry copies them: reserved for
+// MAX_WINDOW + 1 slots of `bytes` when `on`, and the window's last slot copied into slot 0 of the next set when `carried`
+struct SlotArray { rsx::DevBuf OdoSet::*buf; size_t bytes; bool keep, on, carried; };  // (keep: the contents, when the buffer grows)
+using SlotArrays = std::array<SlotArray, 10>;
+SlotArrays slot_arrays(const rsx_odometry *h, const OdoNeeds &need) {
+  constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
+  const size_t K = (size_t)h->prm.max_keypoints;
+  return {{{&OdoSet::pc_F, need.pc_F, true, need.spectra, need.spectra},
+           {&OdoSet::pc_A, need.pc_A, true, need.spectra, need.spectra},
+           {&OdoSet::sp, SP * sizeof(rsx_cfear_surface_point), true, need.sp, need.sp},
+           {&OdoSet::sp_counts, 4, true, need.sp, need.sp},
+           {&OdoSet::sp_tau, SP * 4, false, need.sp_times, false},  // (the tracker reads the window's own slots only)
+           {&OdoSet::xy, K * 8, true, true, need.desc},  // (every extractor writes xy, counts and targets, whatever reads them)
+           {&OdoSet::desc, K * 32, true, true, need.desc},
+           {&OdoSet::valid, K, true, true, need.desc},
+           {&OdoSet::counts, 4, true, true, need.desc},
+           {&OdoSet::targets, K * 8, false, true, need.match_dt || need.match_rows}}};  // (the rows of the previous scan's keypoints: the straddling pair)
+}
+
+int reserve_all(rsx_odometry *h, const OdoNeeds &need, const SlotArrays &slots, size_t ibytes, hipStream_t s) {
   const size_t K = (size_t)h->prm.max_keypoints, S = MAX_WINDOW + 1;
   for (rsx::DevBuf &b : h->imgs) RSX_TRY(b.reserve(ibytes * MAX_WINDOW, s, false));
   for (OdoSet &q : h->set) {
     RSX_TRY(q.az.reserve((size_t)h->rows * 4 * MAX_WINDOW, s, false));
-    RSX_TRY(q.targets.reserve(S * K * 8, s, false));
-    RSX_TRY(q.xy.reserve(S * K * 8, s, true));
-    RSX_TRY(q.counts.reserve(S * 4, s, true));
-    RSX_TRY(q.desc.reserve(S * K * 32, s, true));
-    RSX_TRY(q.valid.reserve(S * K, s, true));
-    if (h->estimator == RSX_ESTIMATOR_CFEAR) {
-      RSX_TRY(q.sp.reserve(S * RSX_CFEAR_MAX_SURFACE_POINTS * sizeof(rsx_cfear_surface_point), s, true));
-      RSX_TRY(q.sp_counts.reserve(S * 4, s, true));
-      RSX_TRY(q.pt_begin.reserve((size_t)MAX_WINDOW * 8, s, false));
-      RSX_TRY(q.pt_end.reserve((size_t)MAX_WINDOW * 8, s, false));
-      if (h->track_on && h->track_prm.compensate) RSX_TRY(q.sp_tau.reserve(S * RSX_CFEAR_MAX_SURFACE_POINTS * 4, s, false));
-    }
+    for (const SlotArray &a : slots)
+      if (a.on) RSX_TRY((q.*a.buf).reserve(S * a.bytes, s, a.keep));
+    if (need.sp)
+      for (rsx::DevBuf *b : {&q.pt_begin, &q.pt_end}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * 8, s, false));
   }
-  RSX_TRY(h->fwd.reserve((size_t)MAX_WINDOW * K * 4, s, false));
-  RSX_TRY(h->bwd.reserve((size_t)MAX_WINDOW * K * 4, s, false));
-  RSX_TRY(h->stage_src.reserve((size_t)MAX_WINDOW * K * 8, s, false));
-  RSX_TRY(h->stage_dst.reserve((size_t)MAX_WINDOW * K * 8, s, false));
+  for (rsx::DevBuf *b : {&h->fwd, &h->bwd}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 4, s, false));
+  for (rsx::DevBuf *b : {&h->stage_src, &h->stage_dst, &h->src, &h->dst}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 8, s, false));
   RSX_TRY(h->pair_cnt.reserve((size_t)MAX_WINDOW * 4, s, false));
-  RSX_TRY(h->src.reserve((size_t)MAX_WINDOW * K * 8, s, false));
-  RSX_TRY(h->dst.reserve((size_t)MAX_WINDOW * K * 8, s, false));
   RSX_TRY(h->offsets.reserve((size_t)(MAX_WINDOW + 1) * 8, s, false));
   RSX_TRY(h->results.reserve((size_t)MAX_WINDOW * sizeof(rsx_orora_result), s, false));
-  if (h->estimator == RSX_ESTIMATOR_CFEAR) {
+  if (need.sp) {
     RSX_TRY(h->cfear_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_cfear_result), s, false));
-    RSX_TRY(h->sp_begin.reserve(S * 8, s, false));
-    RSX_TRY(h->sp_end.reserve(S * 8, s, false));
-    if (h->track_on) {
+    for (rsx::DevBuf *b : {&h->sp_begin, &h->sp_end}) RSX_TRY(b->reserve(S * 8, s, false));
+    if (need.stage == PairStage::cfear_track) {
       RSX_TRY(h->track_state.reserve(rsx::cfear::track_state_bytes(), s, false));
       RSX_TRY(h->track_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_cfear_track_result), s, false));
       RSX_TRY(h->track_n.reserve(4, s, false));
       RSX_TRY(h->track_prev.reserve(24, s, false));
     } else RSX_TRY(h->cfear_index.reserve(rsx::cfear::keyframe_index_bytes(MAX_WINDOW), s, false));
-  } else if (h->estimator == RSX_ESTIMATOR_RANSAC || h->estimator == RSX_ESTIMATOR_MCRANSAC) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
-  if (h->estimator == RSX_ESTIMATOR_MCRANSAC) {
-    RSX_TRY(h->stage_dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
-    RSX_TRY(h->dt.reserve((size_t)MAX_WINDOW * K * 4, s, false));
   }
-  if (h->comp_on) {
+  if (need.ransac) RSX_TRY(h->ransac_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_ransac_result), s, false));
+  if (need.match_dt)
+    for (rsx::DevBuf *b : {&h->stage_dt, &h->dt}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 4, s, false));
+  if (need.match_rows) {
     for (rsx::DevBuf *b : {&h->stage_acur, &h->stage_aprev, &h->a_cur, &h->a_prev}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 4, s, false));
     for (rsx::DevBuf *b : {&h->src2, &h->dst2, &h->xy_comp}) RSX_TRY(b->reserve((size_t)MAX_WINDOW * K * 8, s, false));
     RSX_TRY(h->results2.reserve((size_t)MAX_WINDOW * sizeof(rsx_orora_result), s, false));
   }
-  if (h->pc_on()) {  // (slot 0 of a set is only read while the handle holds a scan, and N cannot change then)
-    size_t per_F, per_A, per_pair;
-    rsx::phasecorr::workspace_bytes(h->pc_prm.pc.n, &per_F, &per_A, &per_pair);
-    for (OdoSet &q : h->set) {
-      RSX_TRY(q.pc_F.reserve(S * per_F, s, true));
-      RSX_TRY(q.pc_A.reserve(S * per_A, s, true));
-    }
+  if (need.spectra) {
+    size_t per_pair;
+    rsx::phasecorr::workspace_bytes(h->pc_prm.pc.n, nullptr, nullptr, &per_pair);
     RSX_TRY(h->pc_work.reserve((size_t)MAX_WINDOW * per_pair + 64, s, false));
     RSX_TRY(h->pc_pairs.reserve((size_t)MAX_WINDOW * 8, s, false));
     RSX_TRY(h->pc_res.reserve((size_t)MAX_WINDOW * sizeof(rsx_phasecorr_result), s, false));
@@ -430,11 +472,10 @@ int reserve_all(rsx_odometry *h, size_t ibytes, hipStream_t s) {
   return RSX_OK;
 }
 
-// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through the selected extractor, the Cartesian images and the
-// descriptors (CFEAR: the surface points) into set g % 3, then its last scan into slot 0 of the next set.  Asynchronous on the
-// stream of lane g & 1.
-int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, int64_t img_stride, int32_t row_stride, const float *azimuths,
-                    int32_t azimuths_per_image) {
+// E(g): window g (n <= MAX_WINDOW scans whose images are at d_imgs, device) through the selected extractor and what `need` asks of every
+// scan into set g % 3, then its last scan into slot 0 of the next set.  Asynchronous on the stream of lane g & 1.
+int enqueue_extract(rsx_odometry *h, const OdoNeeds &need, const SlotArrays &slots, uint64_t g, const uint8_t *d_imgs, int n, int64_t img_stride, int32_t row_stride,
+                    const float *azimuths, int32_t azimuths_per_image) {
   const int lane = (int)(g & 1);
   hipStream_t s = h->lane_stream[lane];
   OdoSet &q = h->set[g % N_SETS], &nx = h->set[(g + 1) % N_SETS];
@@ -458,28 +499,26 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
     case Keypoints::kstrongest: RSX_TRY(keypoints(rsx_kstrongest_extract_batch_device, h->kstr[lane].get(), &h->kstr_prm)); break;
     case Keypoints::cfar: RSX_TRY(keypoints(rsx_cfar_extract_batch_device, h->cfar[lane].get(), &h->cfar_prm)); break;
   }
-  const bool cfear = h->estimator == RSX_ESTIMATOR_CFEAR, pc_est = h->estimator == RSX_ESTIMATOR_PHASECORR;
-  constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
-  size_t pc_F = 0, pc_A = 0;  // bytes of a slot
-  if (h->pc_on()) {  // the spectra of every scan into slots 1 .. n; M(g) samples the images once more
-    rsx::phasecorr::workspace_bytes(h->pc_prm.pc.n, &pc_F, &pc_A, nullptr);
+  if (need.spectra) {  // the spectra of every scan into slots 1 .. n; M(g) samples the images once more
     h->pc_imgs[g % N_SETS] = {d_imgs, img_stride, row_stride};
     RSX_TRY(rsx::phasecorr::launch_spectra(h->pc_prm.pc, h->rows, h->cols, h->pc_tables.p, {d_imgs, img_stride, row_stride, h->prm.col_offset}, n,
-                                           reinterpret_cast<float2 *>(q.pc_F.as<char>() + pc_F), reinterpret_cast<float2 *>(q.pc_A.as<char>() + pc_A),
+                                           reinterpret_cast<float2 *>(q.pc_F.as<char>() + need.pc_F), reinterpret_cast<float2 *>(q.pc_A.as<char>() + need.pc_A),
                                            nullptr, s));
   }
-  if (cfear) {  // the surface points of every scan; no Cartesian image, no descriptors
+  if (need.sp) {  // the surface points of every scan
+    constexpr size_t SP = RSX_CFEAR_MAX_SURFACE_POINTS;
     hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 63) / 64), dim3(64), 0, s, d_counts + 1, n, (int64_t)K, 1, q.pt_begin.as<int64_t>(),
                        q.pt_end.as<int64_t>());
     RSX_HIP(hipGetLastError());
-    if (h->track_on && h->track_prm.compensate)  // with the records' times: a keypoint's azimuth row is the first word of its target
+    if (need.sp_times)  // with the records' times: a keypoint's azimuth row is the first word of its target
       RSX_TRY(rsx::cfear::launch_surface_timed(q.xy.as<float>() + slot_xy, q.targets.as<int32_t>() + slot_xy, 2, h->rows, q.pt_begin.as<int64_t>(),
                                                q.pt_end.as<int64_t>(), n, h->cfear_prm, q.sp.as<rsx_cfear_surface_point>() + SP,
                                                q.sp_tau.as<float>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
     else
       RSX_TRY(rsx::cfear::launch_surface(q.xy.as<float>() + slot_xy, q.pt_begin.as<int64_t>(), q.pt_end.as<int64_t>(), n, h->cfear_prm,
                                          q.sp.as<rsx_cfear_surface_point>() + SP, (int32_t)SP, q.sp_counts.as<int32_t>() + 1, nullptr, s));
-  } else if (!pc_est) {  // (phase correlation as the estimator: no Cartesian image, no descriptors either)
+  }
+  if (need.desc) {
     // the Cartesian image of scan i through scan i's OWN azimuth grid (already in HBM for cen2019): results do not depend on
     // how the sequence is cut into windows, and nothing about the grids is looked at on the host
     RSX_TRY(rsx_frontend_cartesian_batch_device_az(h->fe[lane].get(), d_imgs, n, img_stride, row_stride, h->prm.col_offset, q.az.as<float>(),
@@ -490,30 +529,15 @@ int enqueue_extract(rsx_odometry *h, uint64_t g, const uint8_t *d_imgs, int n, i
   // the last scan of the window becomes the previous scan of the next one (slot 0 of the next set, which M(g - 2) read; the
   // next window's own extraction, on the other lane, writes slots 1 .. n of that set only)
   RSX_HIP(hipStreamWaitEvent(s, h->ev_m[(g + 1) % N_SETS], 0));
-  if (h->pc_on()) {
-    RSX_HIP(hipMemcpyAsync(nx.pc_F.p, q.pc_F.as<char>() + (size_t)n * pc_F, pc_F, hipMemcpyDeviceToDevice, s));
-    RSX_HIP(hipMemcpyAsync(nx.pc_A.p, q.pc_A.as<char>() + (size_t)n * pc_A, pc_A, hipMemcpyDeviceToDevice, s));
-  }
-  if (cfear) {
-    RSX_HIP(hipMemcpyAsync(nx.sp.p, q.sp.as<rsx_cfear_surface_point>() + (size_t)n * SP, SP * sizeof(rsx_cfear_surface_point),
-                           hipMemcpyDeviceToDevice, s));
-    RSX_HIP(hipMemcpyAsync(nx.sp_counts.p, q.sp_counts.as<int32_t>() + n, 4, hipMemcpyDeviceToDevice, s));
-  } else if (!pc_est) {  // (as the estimator it reports the keypoints and matches none: nothing of them is carried)
-    RSX_HIP(hipMemcpyAsync(nx.xy.p, q.xy.as<float>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
-    RSX_HIP(hipMemcpyAsync(nx.desc.p, q.desc.as<uint8_t>() + (size_t)n * K * 32, (size_t)K * 32, hipMemcpyDeviceToDevice, s));
-    RSX_HIP(hipMemcpyAsync(nx.valid.p, q.valid.as<uint8_t>() + (size_t)n * K, (size_t)K, hipMemcpyDeviceToDevice, s));
-    RSX_HIP(hipMemcpyAsync(nx.counts.p, d_counts + n, 4, hipMemcpyDeviceToDevice, s));
-    if (h->estimator == RSX_ESTIMATOR_MCRANSAC || h->comp_on)  // the azimuth rows of the previous scan's keypoints: the dt (the
-                                                                // compensation) of the straddling pair
-      RSX_HIP(hipMemcpyAsync(nx.targets.p, q.targets.as<int32_t>() + (size_t)n * slot_xy, slot_xy * 4, hipMemcpyDeviceToDevice, s));
-  }
+  for (const SlotArray &a : slots)
+    if (a.carried) RSX_HIP(hipMemcpyAsync((nx.*a.buf).p, (q.*a.buf).as<char>() + (size_t)n * a.bytes, a.bytes, hipMemcpyDeviceToDevice, s));
   RSX_HIP(hipEventRecord(h->ev_e[g % N_SETS], s));
   return RSX_OK;
 }
 
-// M(g): the consecutive pairs of window g (with the previous scan in slot 0 when there is one) matched, selected and solved,
+// M(g): the consecutive pairs of window g (with the previous scan in slot 0 when there is one) through the pair stage of `need`,
 // the results on their way to the set's pinned area.  Asynchronous on the matching stream.  *first_out: 0 when slot 0 takes part.
-int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_xy) {
+int enqueue_match(rsx_odometry *h, const OdoNeeds &need, uint64_t g, int n, int *first_out, bool want_xy) {
   hipStream_t s = h->match_stream;
   OdoSet &q = h->set[g % N_SETS];
   const int K = h->prm.max_keypoints;
@@ -523,13 +547,14 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
   const int first = h->have_prev ? 0 : 1, n_pairs = n - first;
   *first_out = first;
   // phase correlation over the pairs of the list odo_pc_pairs writes: src = spectrum slot first + j + 1 = image first + j of window g
-  // (image = slot - 1), dst = slot first + j, slot 0 being the scan the window before carried here
+  // (image = slot - 1), dst = slot first + j, slot 0 being the scan the window before carried here.  As the fallback only over the pairs
+  // the stage before it failed on (CFEAR's status 8 is no failure: max_iterations reached, the pose is carried)
   auto phasecorr = [&](bool fallback) -> int {
     int32_t *pairs = h->pc_pairs.as<int32_t>();
     rsx_orora_result *rec = h->results.as<rsx_orora_result>();
     const dim3 grid((unsigned)(n_pairs + 63) / 64), blk(64);
     hipLaunchKernelGGL(odo_pc_pairs, grid, blk, 0, s, fallback ? rec : (const rsx_orora_result *)nullptr, n_pairs, first,
-                       h->estimator == RSX_ESTIMATOR_CFEAR ? 8 : 0, pairs);
+                       need.stage == PairStage::cfear_pairs ? 8 : 0, pairs);
     RSX_HIP(hipGetLastError());
     const auto &im = h->pc_imgs[g % N_SETS];
     RSX_TRY(rsx::phasecorr::launch_pairs(h->pc_prm.pc, h->rows, h->cols, h->pc_tables.p, {im.d_imgs, im.image_stride, im.row_stride, h->prm.col_offset}, n,
@@ -540,65 +565,60 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
     RSX_HIP(hipGetLastError());
     return RSX_OK;
   };
-  if (h->estimator == RSX_ESTIMATOR_PHASECORR) {
-    if (n_pairs > 0) RSX_TRY(phasecorr(false));
-  } else if (h->estimator == RSX_ESTIMATOR_CFEAR && h->track_on) {  // one tracker launch over the window's scans (slots 1 .. n), its state in the handle
-    int64_t *b = h->sp_begin.as<int64_t>(), *e = h->sp_end.as<int64_t>();
-    if (!h->have_prev) RSX_HIP(hipMemsetAsync(h->track_state.p, 0, rsx::cfear::track_state_bytes(), s));  // a new sequence
+  int64_t *b = h->sp_begin.as<int64_t>(), *e = h->sp_end.as<int64_t>();
+  auto sp_ranges = [&]() -> int {  // CFEAR: the record ranges of slots 0 .. n of the set's surface points into b, e
     hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 1 + 63) / 64), dim3(64), 0, s, q.sp_counts.as<int32_t>(), n + 1,
                        (int64_t)RSX_CFEAR_MAX_SURFACE_POINTS, 0, b, e);
     RSX_HIP(hipGetLastError());
+    return RSX_OK;
+  };
+  if (need.stage == PairStage::phasecorr) {
+    if (n_pairs > 0) RSX_TRY(phasecorr(false));
+  } else if (need.stage == PairStage::cfear_track) {  // one tracker launch over the window's scans (slots 1 .. n), its state in the handle
+    if (!h->have_prev) RSX_HIP(hipMemsetAsync(h->track_state.p, 0, rsx::cfear::track_state_bytes(), s));  // a new sequence
+    RSX_TRY(sp_ranges());
     RSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->track_n.p), n, 1, s));
-    RSX_TRY(rsx::cfear::launch_track(q.sp.as<rsx_cfear_surface_point>(), h->track_prm.compensate ? q.sp_tau.as<float>() : nullptr, b + 1, e + 1, h->track_n.as<int32_t>(), 1, h->cfear_prm, h->track_prm,
-                                     h->track_state.p, h->track_res.as<rsx_cfear_track_result>(), s));
+    RSX_TRY(rsx::cfear::launch_track(q.sp.as<rsx_cfear_surface_point>(), need.sp_times ? q.sp_tau.as<float>() : nullptr, b + 1, e + 1, h->track_n.as<int32_t>(), 1,
+                                     h->cfear_prm, h->track_prm, h->track_state.p, h->track_res.as<rsx_cfear_track_result>(), s));
     hipLaunchKernelGGL(odo_cfear_track_results, dim3(1), dim3(64), 0, s, h->track_res.as<rsx_cfear_track_result>(), n, first,
                        h->track_prev.as<double>(), h->results.as<rsx_orora_result>(), h->pair_cnt.as<int32_t>());
     RSX_HIP(hipGetLastError());
-  } else if (n_pairs > 0 && h->estimator == RSX_ESTIMATOR_CFEAR) {  // one registration launch over the pairs; src = slot first + j + 1, dst = slot first + j
-    int64_t *b = h->sp_begin.as<int64_t>(), *e = h->sp_end.as<int64_t>();
-    hipLaunchKernelGGL(odo_cfear_ranges, dim3((unsigned)(n + 1 + 63) / 64), dim3(64), 0, s, q.sp_counts.as<int32_t>(), n + 1,
-                       (int64_t)RSX_CFEAR_MAX_SURFACE_POINTS, 0, b, e);
-    RSX_HIP(hipGetLastError());
+  } else if (n_pairs > 0 && need.stage == PairStage::cfear_pairs) {  // one registration launch over the pairs; src = slot first + j + 1, dst = slot first + j
+    RSX_TRY(sp_ranges());
     const rsx_cfear_surface_point *sp = q.sp.as<rsx_cfear_surface_point>();
     RSX_TRY(rsx::cfear::launch_register(sp, b + first + 1, e + first + 1, sp, b + first, e + first, n_pairs, nullptr, h->cfear_prm,
                                         h->cfear_index.p, h->cfear_res.as<rsx_cfear_result>(), s));
     hipLaunchKernelGGL(odo_cfear_results, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->cfear_res.as<rsx_cfear_result>(), n_pairs,
                        h->results.as<rsx_orora_result>(), h->pair_cnt.as<int32_t>());
     RSX_HIP(hipGetLastError());
-  } else if (n_pairs > 0) {
+  } else if (n_pairs > 0) {  // features: matcher, cross check, correspondence lists and the estimator
     RSX_TRY(rsx_frontend_match_consecutive_device(h->fe[g & 1].get(), q.desc.as<uint8_t>(), q.valid.as<uint8_t>(), d_counts, K, first, n_pairs,
                                                   h->prm.frontend.ratio, h->fwd.as<int32_t>(), h->bwd.as<int32_t>(), s));
-    const bool mc = h->estimator == RSX_ESTIMATOR_MCRANSAC;
-    if (h->comp_on)
-      hipLaunchKernelGGL(odo_cross_az, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
-                         h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>(),
-                         q.targets.as<int32_t>(), h->stage_acur.as<int32_t>(), h->stage_aprev.as<int32_t>());
-    else if (mc)
-      hipLaunchKernelGGL(odo_cross_dt, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
-                         h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>(),
-                         q.targets.as<int32_t>(), h->rows, h->ransac_prm.dt_scan, h->stage_dt.as<float>());
-    else
-      hipLaunchKernelGGL(odo_cross, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
-                         h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>());
+    auto cross = [&](auto kernel, auto... more) {  // the cross check; `more`: what it stages beside the matches, and from what
+      hipLaunchKernelGGL(kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, q.xy.as<float>(), d_counts, K, first, h->fwd.as<int32_t>(),
+                         h->bwd.as<int32_t>(), h->stage_src.as<float2>(), h->stage_dst.as<float2>(), h->pair_cnt.as<int32_t>(), more...);
+    };
+    if (need.match_rows) cross(odo_cross_az, q.targets.as<int32_t>(), h->stage_acur.as<int32_t>(), h->stage_aprev.as<int32_t>());
+    else if (need.match_dt) cross(odo_cross_dt, q.targets.as<int32_t>(), h->rows, h->ransac_prm.dt_scan, h->stage_dt.as<float>());
+    else cross(odo_cross);
     hipLaunchKernelGGL(odo_gather, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_src.as<float2>(), h->stage_dst.as<float2>(),
                        h->pair_cnt.as<int32_t>(), n_pairs, K, h->src.as<float2>(), h->dst.as<float2>(), h->offsets.as<int64_t>());
-    if (mc)
+    if (need.match_dt)
       hipLaunchKernelGGL(odo_gather_dt, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_dt.as<float>(), h->offsets.as<int64_t>(), K, h->dt.as<float>());
-    if (h->comp_on)
+    if (need.match_rows)
       hipLaunchKernelGGL(odo_gather_az, dim3((unsigned)n_pairs), dim3(256), 0, s, h->stage_acur.as<int32_t>(), h->stage_aprev.as<int32_t>(),
                          h->offsets.as<int64_t>(), K, h->a_cur.as<int32_t>(), h->a_prev.as<int32_t>());
     RSX_HIP(hipGetLastError());
     auto estimate = [&](const float *d_src, const float *d_dst, rsx_orora_result *d_res) -> int {
-      if (h->estimator == RSX_ESTIMATOR_ORORA)
-        return rsx_orora_register_batch_device(h->reg.get(), d_src, d_dst, h->offsets.as<int64_t>(), n_pairs, &h->prm.orora, d_res, s);
-      RSX_TRY(rsx_ransac_estimate_batch_device(h->ransac.get(), d_src, d_dst, mc ? h->dt.as<float>() : nullptr, h->offsets.as<int64_t>(), n_pairs,
-                                               &h->ransac_prm, h->ransac_res.as<rsx_ransac_result>(), nullptr, s));
+      if (!need.ransac) return rsx_orora_register_batch_device(h->reg.get(), d_src, d_dst, h->offsets.as<int64_t>(), n_pairs, &h->prm.orora, d_res, s);
+      RSX_TRY(rsx_ransac_estimate_batch_device(h->ransac.get(), d_src, d_dst, need.match_dt ? h->dt.as<float>() : nullptr, h->offsets.as<int64_t>(),
+                                               n_pairs, &h->ransac_prm, h->ransac_res.as<rsx_ransac_result>(), nullptr, s));
       hipLaunchKernelGGL(odo_ransac_results, dim3((unsigned)(n_pairs + 63) / 64), dim3(64), 0, s, h->ransac_res.as<rsx_ransac_result>(), n_pairs, d_res);
       RSX_HIP(hipGetLastError());
       return RSX_OK;
     };
     RSX_TRY(estimate(h->src.as<float>(), h->dst.as<float>(), h->results.as<rsx_orora_result>()));
-    if (h->comp_on) {  // estimated, compensated with its own estimate, estimated again: every pair of the window in each launch
+    if (need.match_rows) {  // estimated, compensated with its own estimate, estimated again: every pair of the window in each launch
       RSX_TRY(rsx::mocomp::launch_matches(h->src.as<float>(), h->dst.as<float>(), h->a_cur.as<int32_t>(), h->a_prev.as<int32_t>(),
                                           h->offsets.as<int64_t>(), n_pairs, h->results.p, sizeof(rsx_orora_result), offsetof(rsx_orora_result, status),
                                           h->comp_prm, h->src2.as<float>(), h->dst2.as<float>(), nullptr, s));
@@ -608,9 +628,9 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
       RSX_HIP(hipGetLastError());
     }
   }
-  if (h->pc_fallback && n_pairs > 0) RSX_TRY(phasecorr(true));  // (never with compensation or the tracker: the records are h->results)
-  const rsx::DevBuf &res = h->comp_on ? h->results2 : h->results;
-  if (h->comp_on && want_xy)  // /orora/cloud_local: scan i under the velocity of the pair (i - 1, i); the first scan of a sequence as measured
+  if (need.fallback && n_pairs > 0) RSX_TRY(phasecorr(true));  // (never with compensation or the tracker: the records are h->results)
+  const rsx::DevBuf &res = need.match_rows ? h->results2 : h->results;
+  if (need.match_rows && want_xy)  // /orora/cloud_local: scan i under the velocity of the pair (i - 1, i); the first scan of a sequence as measured
     RSX_TRY(rsx::mocomp::launch_slots(q.xy.as<float>() + (size_t)K * 2, q.targets.as<int32_t>() + (size_t)K * 2, d_counts + 1, K, n, first, res.p,
                                       sizeof(rsx_orora_result), offsetof(rsx_orora_result, status), h->comp_prm, h->xy_comp.as<float>(), s));
   char *pin = static_cast<char *>(q.pin.p);
@@ -625,7 +645,7 @@ int enqueue_match(rsx_odometry *h, uint64_t g, int n, int *first_out, bool want_
 }
 
 // wait for M(g), fill out[0..n) (+ the keypoints)
-int finish_window(rsx_odometry *h, uint64_t g, int n, int first, rsx_odometry_scan *out, float *out_xy, int32_t max_xy) {
+int finish_window(rsx_odometry *h, const OdoNeeds &need, uint64_t g, int n, int first, rsx_odometry_scan *out, float *out_xy, int32_t max_xy) {
   OdoSet &q = h->set[g % N_SETS];
   const int K = h->prm.max_keypoints;
   const size_t slot_xy = (size_t)K * 2;
@@ -651,7 +671,7 @@ int finish_window(rsx_odometry *h, uint64_t g, int n, int first, rsx_odometry_sc
       const int c = hc[1 + i] < K ? hc[1 + i] : K, wn = c < max_xy ? c : max_xy;
       if (wn > 0)
         RSX_HIP(hipMemcpyAsync(out_xy + (size_t)i * max_xy * 2,
-                               h->comp_on ? h->xy_comp.as<float>() + (size_t)i * slot_xy : q.xy.as<float>() + (size_t)(1 + i) * slot_xy,
+                               need.match_rows ? h->xy_comp.as<float>() + (size_t)i * slot_xy : q.xy.as<float>() + (size_t)(1 + i) * slot_xy,
                                (size_t)wn * 8, hipMemcpyDeviceToHost, s));
     }
     RSX_HIP(hipStreamSynchronize(s));
@@ -691,7 +711,7 @@ int check_push(rsx_odometry *h, const uint8_t *imgs, int32_t n_scans, int64_t im
 // matching -- and the wait for M(g).  stage(w, g, b0, n) enqueues E(g) of the call's window w (scans b0 .. b0 + n) once its images
 // are where the extraction can read them
 template <typename Stage>
-int push_windows(rsx_odometry *h, int32_t n_scans, rsx_odometry_scan *out, float *out_xy, int32_t max_xy, Stage &&stage) {
+int push_windows(rsx_odometry *h, const OdoNeeds &need, int32_t n_scans, rsx_odometry_scan *out, float *out_xy, int32_t max_xy, Stage &&stage) {
   const int nwin = (n_scans + MAX_WINDOW - 1) / MAX_WINDOW;
   auto extract = [&](int w, uint64_t g) -> int {
     const int b0 = w * MAX_WINDOW;
@@ -703,9 +723,9 @@ int push_windows(rsx_odometry *h, int32_t n_scans, rsx_odometry_scan *out, float
     const uint64_t g = h->windows + (uint64_t)w;
     const int b0 = w * MAX_WINDOW, n = n_scans - b0 < MAX_WINDOW ? n_scans - b0 : MAX_WINDOW;
     int first = 0;
-    st = enqueue_match(h, g, n, &first, out_xy && max_xy > 0);
+    st = enqueue_match(h, need, g, n, &first, out_xy && max_xy > 0);
     if (st == RSX_OK && w + 2 < nwin) st = extract(w + 2, g + 2);
-    if (st == RSX_OK) st = finish_window(h, g, n, first, out + b0, out_xy ? out_xy + (size_t)b0 * max_xy * 2 : nullptr, max_xy);
+    if (st == RSX_OK) st = finish_window(h, need, g, n, first, out + b0, out_xy ? out_xy + (size_t)b0 * max_xy * 2 : nullptr, max_xy);
   }
   h->windows += (uint64_t)nwin;
   if (st != RSX_OK) abandon(h);
@@ -733,6 +753,23 @@ int set_keypoints(rsx_odometry *h, Keypoints which, const P *params, int (*check
   }
   h->*prm = *params;
   h->keypoints = which;
+  return RSX_OK;
+}
+
+// The setters of the estimator side, all in this one sequence: candidate(c, p) turns the current configuration and the setter's stored
+// parameters (h->*prm) into the call's and checks the parameters; check_config on the candidate; and only then both are stored -- a call
+// that fails leaves the configuration as it was.  one: what a sequence has one of
+template <typename P, typename Candidate>
+int set_config(rsx_odometry *h, const char *one, P rsx_odometry::*prm, Candidate &&candidate) {
+  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one %s)", one);
+  OdoConfig c = h->cfg;
+  P p = h->*prm;
+  RSX_TRY(candidate(c, p));
+  RSX_TRY(check_config(c));
+  h->*prm = p;
+  h->cfg = c;
   return RSX_OK;
 }
 
@@ -836,81 +873,55 @@ int rsx_odometry_set_estimator(rsx_odometry *h, int estimator, const rsx_ransac_
     return fail(RSX_ERR_BAD_ARG, "RSX_ESTIMATOR_PHASECORR is selected with rsx_odometry_set_phasecorr, which carries its parameters");
   if (estimator != RSX_ESTIMATOR_ORORA && estimator != RSX_ESTIMATOR_RANSAC && estimator != RSX_ESTIMATOR_MCRANSAC)
     return fail(RSX_ERR_BAD_ARG, "unknown estimator %d", estimator);
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
-  if (estimator == RSX_ESTIMATOR_MCRANSAC && h->comp_on)
-    return fail(RSX_ERR_BAD_ARG, "compensation is on: motion-compensated RANSAC has its own motion model (rsx_odometry_set_compensation(h, NULL) first)");
-  h->track_on = false;  // (tracking belongs to CFEAR)
-  if (estimator == RSX_ESTIMATOR_ORORA) {
-    h->estimator = estimator;
-    return RSX_OK;
-  }
-  rsx_ransac_params p;
-  rsx_ransac_default_params(&p);
-  if (params) p = *params;
-  if (estimator == RSX_ESTIMATOR_MCRANSAC) p.flags |= RSX_RANSAC_MOTION_COMPENSATED;
-  else p.flags &= ~RSX_RANSAC_MOTION_COMPENSATED;
-  RSX_TRY(rsx::ransac_check_params(p));
-  if (!h->ransac) {
+  const bool ransac = estimator != RSX_ESTIMATOR_ORORA;
+  return set_config(h, "estimator", &rsx_odometry::ransac_prm, [&](OdoConfig &c, rsx_ransac_params &p) -> int {
+    c.estimator = estimator;
+    c.track = false;  // (tracking belongs to CFEAR)
+    if (c.pc == Pc::estimate) c.pc = Pc::off;  // (selecting an estimator leaves the one that stood in for it)
+    if (!ransac) return RSX_OK;
+    rsx_ransac_default_params(&p);
+    if (params) p = *params;
+    if (estimator == RSX_ESTIMATOR_MCRANSAC) p.flags |= RSX_RANSAC_MOTION_COMPENSATED;
+    else p.flags &= ~RSX_RANSAC_MOTION_COMPENSATED;
+    RSX_TRY(rsx::ransac_check_params(p));
+    if (h->ransac) return RSX_OK;  // (the estimator's handle: made once, kept whatever becomes of this call)
     rsx_ransac *r = nullptr;
     RSX_TRY(rsx_ransac_create(h->device, &r));
     h->ransac.reset(r);
-  }
-  h->ransac_prm = p;
-  h->estimator = estimator;
-  return RSX_OK;
+    return RSX_OK;
+  });
 } RSX_CATCH_ALL
 
 int rsx_odometry_set_compensation(rsx_odometry *h, const rsx_mocomp_params *params) try {
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one model)");
-  if (!params) {
-    h->comp_on = false;
-    return RSX_OK;
-  }
-  if (h->estimator == RSX_ESTIMATOR_MCRANSAC) return fail(RSX_ERR_BAD_ARG, "motion-compensated RANSAC has its own motion model");
-  if (h->estimator == RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is selected: it has no matches to compensate (rsx_odometry_set_cfear(h, NULL) first)");
-  if (h->pc_on()) return fail(RSX_ERR_BAD_ARG, "phase correlation is on: it reads the scans as measured (rsx_odometry_set_phasecorr(h, NULL) first)");
-  rsx_mocomp_params p = *params;
-  p.rows = h->rows;
-  RSX_TRY(rsx::mocomp::check_params(p));
-  h->comp_prm = p;
-  h->comp_on = true;
-  return RSX_OK;
+  return set_config(h, "model", &rsx_odometry::comp_prm, [&](OdoConfig &c, rsx_mocomp_params &p) -> int {
+    c.comp = params != nullptr;
+    if (!params) return RSX_OK;
+    p = *params;
+    p.rows = h->rows;
+    return rsx::mocomp::check_params(p);
+  });
 } RSX_CATCH_ALL
 
 int rsx_odometry_set_cfear(rsx_odometry *h, const rsx_cfear_params *params) try {
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
-  if (!params) {
-    h->estimator = RSX_ESTIMATOR_ORORA;
-    h->track_on = false;
-    return RSX_OK;
-  }
-  if (h->comp_on) return fail(RSX_ERR_BAD_ARG, "compensation is on: CFEAR registration has no matches to compensate (rsx_odometry_set_compensation(h, NULL) first)");
-  RSX_TRY(rsx::cfear::check_params(*params));
-  h->cfear_prm = *params;
-  h->estimator = RSX_ESTIMATOR_CFEAR;
-  return RSX_OK;
+  return set_config(h, "estimator", &rsx_odometry::cfear_prm, [&](OdoConfig &c, rsx_cfear_params &p) -> int {
+    c.estimator = params ? RSX_ESTIMATOR_CFEAR : RSX_ESTIMATOR_ORORA;
+    if (!params) c.track = false;
+    if (c.pc == Pc::estimate) c.pc = Pc::off;  // (as rsx_odometry_set_estimator)
+    if (!params) return RSX_OK;
+    p = *params;
+    return rsx::cfear::check_params(p);
+  });
 } RSX_CATCH_ALL
 
 int rsx_odometry_set_cfear_tracking(rsx_odometry *h, const rsx_cfear_track_params *params) try {
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
-  if (!params) {
-    h->track_on = false;
+  return set_config(h, "estimator", &rsx_odometry::track_prm, [&](OdoConfig &c, rsx_cfear_track_params &p) -> int {
+    c.track = params != nullptr;
+    if (!params) return RSX_OK;
+    p = *params;
+    RSX_TRY(rsx::cfear::check_track_params(p));
+    if (p.compensate && h->rows > 65536) return fail(RSX_ERR_BAD_ARG, "compensate = 1 takes images of at most 65536 rows");
     return RSX_OK;
-  }
-  if (h->estimator != RSX_ESTIMATOR_CFEAR) return fail(RSX_ERR_BAD_ARG, "CFEAR registration is not selected (rsx_odometry_set_cfear first)");
-  if (h->pc_fallback) return fail(RSX_ERR_BAD_ARG, "the phase-correlation fallback is on: it replaces pairs, the tracker has none (rsx_odometry_set_phasecorr(h, NULL) first)");
-  RSX_TRY(rsx::cfear::check_track_params(*params));
-  if (params->compensate && h->rows > 65536) return fail(RSX_ERR_BAD_ARG, "compensate = 1 takes images of at most 65536 rows");
-  h->track_prm = *params;
-  h->track_on = true;
-  return RSX_OK;
+  });
 } RSX_CATCH_ALL
 
 int rsx_odometry_default_phasecorr_params(rsx_odometry_phasecorr_params *p) try {
@@ -922,39 +933,24 @@ int rsx_odometry_default_phasecorr_params(rsx_odometry_phasecorr_params *p) try 
 } RSX_CATCH_ALL
 
 int rsx_odometry_set_phasecorr(rsx_odometry *h, const rsx_odometry_phasecorr_params *params) try {
-  if (!h) return fail(RSX_ERR_BAD_ARG, "null handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->have_prev) return fail(RSX_ERR_BAD_ARG, "the handle holds a scan: rsx_odometry_reset first (one sequence, one estimator)");
-  if (!params) {  // back to the state before: the estimator ESTIMATE took the place of, no fallback
-    if (h->estimator == RSX_ESTIMATOR_PHASECORR) h->estimator = h->pc_saved;
-    h->pc_fallback = false;
-    return RSX_OK;
-  }
-  rsx_odometry_phasecorr_params p = *params;
-  if (p.mode != RSX_ODOMETRY_PHASECORR_ESTIMATE && p.mode != RSX_ODOMETRY_PHASECORR_FALLBACK) return fail(RSX_ERR_BAD_ARG, "unknown mode %d", p.mode);
-  if (!(p.max_peak_ratio >= 0.0) || !std::isfinite(p.max_peak_ratio) || !(p.min_peak >= 0.0) || !std::isfinite(p.min_peak))
-    return fail(RSX_ERR_BAD_ARG, "max_peak_ratio and min_peak must not be negative");
-  p.pc.range_resolution = (double)h->prm.radar_resolution;
-  RSX_TRY(rsx::phasecorr::check_params(p.pc, h->rows, h->cols));
-  if (h->comp_on) return fail(RSX_ERR_BAD_ARG, "compensation is on: phase correlation reads the scans as measured (rsx_odometry_set_compensation(h, NULL) first)");
-  if (h->track_on) return fail(RSX_ERR_BAD_ARG, "the CFEAR tracker is on: phase correlation registers pairs (rsx_odometry_set_cfear_tracking(h, NULL) first)");
-  if (std::memcmp(&h->pc_tables_of, &p.pc, sizeof(p.pc)) != 0) {  // (nothing is in flight: every push is synchronous)
+  return set_config(h, "estimator", &rsx_odometry::pc_prm, [&](OdoConfig &c, rsx_odometry_phasecorr_params &p) -> int {
+    c.pc = Pc::off;  // (NULL: back to the state before, the selected estimator alone)
+    if (!params) return RSX_OK;
+    p = *params;
+    if (p.mode != RSX_ODOMETRY_PHASECORR_ESTIMATE && p.mode != RSX_ODOMETRY_PHASECORR_FALLBACK) return fail(RSX_ERR_BAD_ARG, "unknown mode %d", p.mode);
+    c.pc = p.mode == RSX_ODOMETRY_PHASECORR_ESTIMATE ? Pc::estimate : Pc::fallback;
+    if (!(p.max_peak_ratio >= 0.0) || !std::isfinite(p.max_peak_ratio) || !(p.min_peak >= 0.0) || !std::isfinite(p.min_peak))
+      return fail(RSX_ERR_BAD_ARG, "max_peak_ratio and min_peak must not be negative");
+    p.pc.range_resolution = (double)h->prm.radar_resolution;
+    RSX_TRY(rsx::phasecorr::check_params(p.pc, h->rows, h->cols));
+    RSX_TRY(check_config(c));  // (before the tables: a refused call makes none)
+    if (std::memcmp(&h->pc_tables_of, &p.pc, sizeof(p.pc)) == 0) return RSX_OK;  // (nothing is in flight: every push is synchronous)
     RSX_HIP(hipSetDevice(h->device));
     h->pc_tables_of = rsx_phasecorr_params{};
     RSX_TRY(rsx::phasecorr::make_tables(p.pc, h->rows, h->cols, h->pc_tables, h->match_stream));
     h->pc_tables_of = p.pc;
-  }
-  const bool est = h->estimator == RSX_ESTIMATOR_PHASECORR;
-  if (p.mode == RSX_ODOMETRY_PHASECORR_ESTIMATE) {
-    if (!est) h->pc_saved = h->estimator;
-    h->estimator = RSX_ESTIMATOR_PHASECORR;
-    h->pc_fallback = false;
-  } else {
-    if (est) h->estimator = h->pc_saved;
-    h->pc_fallback = true;
-  }
-  h->pc_prm = p;
-  return RSX_OK;
+    return RSX_OK;
+  });
 } RSX_CATCH_ALL
 
 int rsx_odometry_push_device(rsx_odometry *h, const uint8_t *d_imgs, int32_t n_scans, int64_t image_stride_bytes, int32_t row_stride,
@@ -963,9 +959,11 @@ int rsx_odometry_push_device(rsx_odometry *h, const uint8_t *d_imgs, int32_t n_s
   if (n_scans == 0) return RSX_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
-  RSX_TRY(reserve_all(h, 0, h->match_stream));
-  return push_windows(h, n_scans, out, out_xy, max_xy, [&](int, uint64_t g, int b0, int n) {
-    return enqueue_extract(h, g, d_imgs + (int64_t)b0 * image_stride_bytes, n, image_stride_bytes, row_stride,
+  const OdoNeeds need = needs_of(h);
+  const SlotArrays slots = slot_arrays(h, need);
+  RSX_TRY(reserve_all(h, need, slots, 0, h->match_stream));
+  return push_windows(h, need, n_scans, out, out_xy, max_xy, [&](int, uint64_t g, int b0, int n) {
+    return enqueue_extract(h, need, slots, g, d_imgs + (int64_t)b0 * image_stride_bytes, n, image_stride_bytes, row_stride,
                            azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), azimuths_per_image);
   });
 } RSX_CATCH_ALL
@@ -977,13 +975,15 @@ int rsx_odometry_push(rsx_odometry *h, const uint8_t *imgs, int32_t n_scans, int
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_HIP(hipSetDevice(h->device));
   const size_t ibytes = (size_t)h->rows * row_stride;
-  RSX_TRY(reserve_all(h, ibytes, h->match_stream));
+  const OdoNeeds need = needs_of(h);
+  const SlotArrays slots = slot_arrays(h, need);
+  RSX_TRY(reserve_all(h, need, slots, ibytes, h->match_stream));
   // three image buffers: the upload of window w + 2 (copy stream) runs while the kernels of windows w and w + 1 do
   struct CopyDone {  // the caller's host images must not be in flight when this call returns, error or not
     hipStream_t cs;
     ~CopyDone() { (void)hipStreamSynchronize(cs); }
   } copy_done{h->copy_stream};
-  return push_windows(h, n_scans, out, out_xy, max_xy, [&](int w, uint64_t g, int b0, int n) -> int {  // E(g) behind its upload
+  return push_windows(h, need, n_scans, out, out_xy, max_xy, [&](int w, uint64_t g, int b0, int n) -> int {  // E(g) behind its upload
     // (the buffer was read by the extraction of window w - 3: long done.  With phase correlation M(w - 3) read it as well: push_windows
     // stages window w in the iteration of window w - 2, whose predecessor ended with finish_window's wait for M(w - 3), and a call
     // returns with every M behind it.  Keep that order: an upload staged before that wait would overwrite images a pair stage reads)
@@ -991,7 +991,7 @@ int rsx_odometry_push(rsx_odometry *h, const uint8_t *imgs, int32_t n_scans, int
     RSX_TRY(rsx::upload_images(d_imgs, imgs + (int64_t)b0 * image_stride_bytes, n, ibytes, image_stride_bytes, h->copy_stream));
     RSX_HIP(hipEventRecord(h->ev_up, h->copy_stream));
     RSX_HIP(hipStreamWaitEvent(h->lane_stream[g & 1], h->ev_up, 0));
-    return enqueue_extract(h, g, d_imgs, n, (int64_t)ibytes, row_stride, azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), azimuths_per_image);
+    return enqueue_extract(h, need, slots, g, d_imgs, n, (int64_t)ibytes, row_stride, azimuths + (azimuths_per_image ? (size_t)b0 * h->rows : 0), azimuths_per_image);
   });
 } RSX_CATCH_ALL
 

@@ -167,7 +167,7 @@ class Odometry:
 
     def set_phasecorr(self, params=None, off=False):
         """Switch phase correlation on (params: an OdometryPhasecorrParams whose mode picks ESTIMATE or FALLBACK, a dict of fields, or None
-        for the defaults: ESTIMATE at N = 256), or back to the state before with off=True.  Only while the handle holds no scan, and not
+        for the defaults: ESTIMATE at N = 256), or off with off=True (the selected estimator alone again).  Only while the handle holds no scan, and not
         while compensation or the CFEAR tracker is on."""
         if params is not None and not isinstance(params, OdometryPhasecorrParams):
             params = phasecorr_params(params)
