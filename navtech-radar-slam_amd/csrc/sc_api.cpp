@@ -28,6 +28,40 @@ std::string &last_error() {
 using namespace rsx;
 using namespace rsx::sc;
 
+namespace {
+
+// what one query batch in flight owns between its keys and its records
+struct QueryWs {
+  DevBuf q_vkey, q_norm, q_rkey, partial;
+  DevBuf f_qimg, f_lb, f_cand, f_cnt, f_thr, f_plan;  // filter path
+  DevBuf f_win, f_surv;                               // window previews of the short lists and what is left of them to score (sc_window.hip)
+};
+
+// One query batch against a handle's shard, as every stage of the query chain sees it (the stages: make_keys / build_keys,
+// run_filter, shortlist, rescore -- and run_q1 and the exact-all branch of run_topk beside them).  batch_of makes it, slice
+// cuts it; a stage takes nothing else, so what it reads and which workspace set it writes stands in its one argument.
+struct Batch {
+  rsx_sc *h;
+  QueryWs *w;     // the workspace set the stages write and read
+  hipStream_t s;  // ... and the stream they run on
+  QueryView q;
+  int64_t q0, row0;     // where q's first query sits among the keys of w / in the per-query arrays of w (bounds, short lists ...)
+                        // row0 == q0 for a whole batch and its own_rows slices; a plain slice restarts at row 0 (slice)
+  int64_t n_items, ld;  // this shard's entries in play, local slots [0, n_items), and the leading dimension of a row of bounds
+  int64_t n_elig;       // entries with a global index below it are ranked (normalised: elig_limit)
+  const int64_t *elig;  // optional per-query limits (device)
+  bool elig_monotone;   // ... which do not decrease with the query index (self queries): the filter skips what a query cannot see
+  int32_t k;
+  lb_t *lb() const { return w->f_lb.as<lb_t>() + row0 * ld; }
+  RescoreEntry *cand() const { return w->f_cand.as<RescoreEntry>() + row0 * RESCORE_SHORTLIST_CAP; }
+  int32_t *cnt() const { return w->f_cnt.as<int32_t>() + row0; }
+  float *thr() const { return w->f_thr.as<float>() + row0 * RESCORE_THR_STRIDE; }
+  WindowPreview *win() const { return w->f_win.as<WindowPreview>() + row0 * WINDOW_P; }
+  WindowSurvivor *surv() const { return w->f_surv.as<WindowSurvivor>() + row0 * WINDOW_LIST_STRIDE; }
+};
+
+}  // namespace
+
 struct rsx_sc {
   rsx_sc_params p;
   std::mutex mu;
@@ -64,23 +98,16 @@ struct rsx_sc {
   } tree, tree_batch;
   // workspaces
   DevBuf pts_ws, q_desc, topk, knn_ws, small, pair_out, q_elig;
-  // what one query batch in flight owns between its keys and its records.  Two sets: the host-buffer entry scores the
-  // pieces of a large batch alternately on two streams, each with its own set (rsx_sc_query); everything else uses set 0
-  struct QueryWs {
-    DevBuf q_vkey, q_norm, q_rkey, partial;
-    DevBuf f_qimg, f_lb, f_cand, f_cnt, f_thr, f_plan;  // filter path
-    DevBuf f_win, f_surv;                               // window previews of the short lists and what is left of them to score (sc_window.hip)
-  } ws[2];
-  QueryWs *w = &ws[0];  // the set the calls below work in (guarded by mu like the rest)
+  // Two workspace sets: the host-buffer entry scores the pieces of a large batch alternately on two streams, each with its
+  // own set (rsx_sc_query); everything else uses set 0.  A Batch names the set its stages work in
+  QueryWs ws[2];
   PairProfiler prof;
   const char *prof_kernel = "sc_pair_kernel";  // which kernel the profiler events bracket
-  // state between rsx_sc_query_stage1_device and rsx_sc_query_stage2_device
+  // state between rsx_sc_query_stage1_device and rsx_sc_query_stage2_device: the batch stage 1 scored (in set 0) and whether
+  // its chain stopped after round 0
   struct {
     bool valid = false, filtered = false;
-    int32_t nq = 0, k = 0;
-    int64_t n_items = 0, n_eligible = 0;
-    const int64_t *q_elig = nullptr;
-    QueryView qv{};
+    Batch b{};
   } st;
   DevBuf st_partial;  // this shard's stage-1 hits
   // the one-launch single-query path (sc_q1.hip): candidate records / bound lists of the workgroups, and the arrival counters
@@ -121,6 +148,7 @@ int set_device(rsx_sc *h) {
 
 // the stream a device entry works on: the caller's, ordered behind the inserts still in flight on the handle's own
 int use_stream(rsx_sc *h, void *stream, hipStream_t *s) {
+  RSX_TRY(set_device(h));
   *s = stream ? static_cast<hipStream_t>(stream) : h->stream;
   if (!stream) {
     // no stream named: the caller's device buffers may still be in the making on the legacy default stream (a framework's
@@ -217,13 +245,21 @@ int build_db_images(rsx_sc *h, int64_t slot, int64_t count, hipStream_t s) {
 
 bool owns(const rsx_sc *h, int64_t g) { return (g % h->p.shard_world) == h->p.shard_rank; }
 
-// number of local slots whose global index is < n_eligible
-int64_t local_count_below(const rsx_sc *h, int64_t n_eligible) {
-  if (n_eligible < 0 || n_eligible > h->n_global) n_eligible = h->n_global;
-  const int64_t w = h->p.shard_world, r = h->p.shard_rank;
-  if (n_eligible <= r) return 0;
-  int64_t c = (n_eligible - r + w - 1) / w;
+// the eligibility limit of a query entry as the kernels take it: a global index bound, negative = every keyframe.  No entry
+// has a global index at or above n_global, so the clamp changes no record
+int64_t elig_limit(const rsx_sc *h, int64_t n_eligible) {
+  return (n_eligible < 0 || n_eligible > h->n_global) ? h->n_global : n_eligible;
+}
+
+// number of local slots whose global index is below the (normalised) limit
+int64_t local_count_below(const rsx_sc *h, int64_t limit) {
+  const int64_t c = plan::owned_below(limit, h->p.shard_rank, h->p.shard_world);
   return c < h->n_local ? c : h->n_local;
+}
+
+int check_k(int32_t k) {
+  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k must be in [1,%d]", RSX_SC_MAX_TOPK);
+  return RSX_OK;
 }
 
 // SC.cpp:17-20,417: deg2rad(float) of nn_align * PC_UNIT_SECTORANGLE
@@ -240,18 +276,52 @@ int ensure_pinned(rsx_sc *h, size_t bytes) {
   return h->pinned.reserve(nb);
 }
 
-// keys for nq query descriptors already in h->q_desc (or external device pointer)
-int prepare_queries(rsx_sc *h, const float *d_q, int32_t nq, hipStream_t s, QueryView *qv) {
-  h->st.valid = false;  // q_vkey / q_norm are about to be overwritten: a pending stage 2 would read the wrong keys
-  RSX_TRY(h->w->q_vkey.reserve((size_t)nq * NS * sizeof(double), s, false));
-  RSX_TRY(h->w->q_norm.reserve((size_t)nq * NS * sizeof(double), s, false));
-  RSX_TRY(h->w->q_rkey.reserve((size_t)nq * NR * sizeof(float), s, false));
-  RSX_TRY(launch_keys(d_q, nq, h->w->q_vkey.as<double>(), h->w->q_norm.as<double>(), h->w->q_rkey.as<float>(), s, h->p.sum_order));
-  qv->desc = d_q;
-  qv->vkey = h->w->q_vkey.as<double>();
-  qv->norm = h->w->q_norm.as<double>();
-  qv->nq = nq;
-  return RSX_OK;
+// nq queries whose descriptors (and, where q names them, keys) are in device memory, against the entries below n_eligible
+// (an entry's argument as it came: negative = all), in workspace set w on stream s
+Batch batch_of(rsx_sc *h, QueryWs *w, hipStream_t s, const QueryView &q, int64_t n_eligible, int32_t k,
+               const int64_t *elig = nullptr, bool elig_monotone = false) {
+  const int64_t limit = elig_limit(h, n_eligible), n_items = local_count_below(h, limit);
+  return Batch{h, w, s, q, 0, 0, n_items, plan::padded_ld(n_items), limit, elig, elig_monotone, k};
+}
+
+// queries [first, first + count) of a batch.  own_rows: they keep their rows in the parent's per-query arrays (pieces whose
+// stages behind the bounds run once over the parent); else they are a batch of their own that uses the arrays from row 0
+Batch slice(const Batch &b, int64_t first, int32_t count, bool own_rows = false) {
+  Batch p = b;
+  p.q.desc += first * DS;
+  if (p.q.vkey) p.q.vkey += first * NS;
+  if (p.q.norm) p.q.norm += first * NS;
+  p.q.nq = count;
+  if (p.elig) p.elig += first;
+  p.q0 = b.q0 + first;
+  p.row0 = own_rows ? b.row0 + first : 0;
+  return p;
+}
+
+// Every buffer of a workspace set that a pending stage 2 reads (keys, bounds, short lists) is sized here and nowhere else:
+// whoever is about to overwrite one passes this line, and the pending stage 1 is void
+int ws_reserve(rsx_sc *h, DevBuf &buf, size_t bytes, hipStream_t s) {
+  h->st.valid = false;
+  return buf.reserve(bytes, s, false);
+}
+
+// Keys of a batch of descriptors from outside.  build_keys: the launch, for the batch or a slice of it; make_keys: room for
+// them in the workspace set (the batch's view points there), then the launch -- unless the caller builds them slice by slice
+// (the host entry, as its pieces arrive)
+int build_keys(const Batch &b) {
+  QueryWs *w = b.w;
+  return launch_keys(b.q.desc, b.q.nq, w->q_vkey.as<double>() + b.q0 * NS, w->q_norm.as<double>() + b.q0 * NS,
+                     w->q_rkey.as<float>() + b.q0 * NR, b.s, b.h->p.sum_order);
+}
+
+int make_keys(Batch *b, bool launch = true) {
+  const size_t nq = (size_t)b->q.nq;
+  RSX_TRY(ws_reserve(b->h, b->w->q_vkey, nq * NS * sizeof(double), b->s));
+  RSX_TRY(ws_reserve(b->h, b->w->q_norm, nq * NS * sizeof(double), b->s));
+  RSX_TRY(ws_reserve(b->h, b->w->q_rkey, nq * NR * sizeof(float), b->s));
+  b->q.vkey = b->w->q_vkey.as<double>();
+  b->q.norm = b->w->q_norm.as<double>();
+  return launch ? build_keys(*b) : RSX_OK;
 }
 
 // rsx_sc_params.filter_mode (1 off, 2 force) decides; when it says 0 = auto, RSX_SC_FILTER=0/1 may
@@ -266,17 +336,19 @@ int filter_mode_of(const rsx_sc *h) {
   return env >= 0 ? env : 0;
 }
 
-bool use_filter(const rsx_sc *h, int32_t nq, int64_t n_items) {
-  const int m = filter_mode_of(h);  // (3 = the single-query path where it applies: like auto for everything else)
-  if (m == 1 || n_items <= 0) return false;
-  if (m == 2) return true;
-  // the filter amortises a 300-register DB tile load over the queries of a block and costs five
-  // extra launches: worth it for batched queries against a sizeable DB -- and for ANY number of queries once the DB is
-  // so large that scoring every entry exactly costs more than the launches (one query, MI355X, us per query
-  // exact-all / filtered: 1 000 keyframes 22 / 85, 10 000: 55 / 94, 100 000: 232 / 178)
-  // (a handful of queries never gets here in auto mode unless the single-query path declined them: use_q1)
-  if (n_items >= 50000) return true;
-  return (int64_t)nq * n_items >= (1ll << 17);  // exact-all scores ~1 G pairs/s, the chain's fixed cost is ~85 us
+// What scores nq queries against n_items entries of this handle: sc_plan.h decides (thresholds and measurements there), from
+// the handle's filter mode; RSX_SC_Q1=0 (experiments build) takes the single-query path out.  An entry asks once per batch
+// and hands the answer down
+static_assert(plan::kQ1MaxQueries == Q1_MAX_NQ, "sc_plan.h decides for the kernel's own limit");
+bool q1_allowed() {
+  static const bool off = [] {
+    const char *e = rsx::exp_env("RSX_SC_Q1");
+    return e && e[0] == '0';
+  }();
+  return !off;
+}
+plan::Path path_of(const rsx_sc *h, int32_t nq, int64_t n_items) {
+  return plan::query_path(filter_mode_of(h), nq, n_items, q1_allowed());
 }
 
 struct ProfScope {
@@ -313,84 +385,94 @@ size_t any_qimg_bytes(int32_t nq) {
   return a > b ? a : b;
 }
 
-// query images + bounds of one batch with the chosen filter form
-// first (a multiple of 32, the images are tile-major): the bounds of local slots [first, first + n_items), lb[q * ld + slot - first]
-int run_filter(rsx_sc *h, const QueryView &q, int64_t n_items, lb_t *lb, int64_t ld, const FilterPlanInput *plan,
-               hipStream_t s, int64_t first = 0) {
+// ---- the stages of the query chain.  Each exists once; the entries below compose them ----
+
+// Bounds: query images + lower bounds of a batch with the chosen filter form, into the batch's rows of the bound matrix.
+// to (rsx_sc_filter_range_device): the bounds of local slots [first, first + n) go to lb[q * ld + slot - first] instead
+// (first a multiple of 32: the images are tile-major)
+struct BoundsTarget {
+  lb_t *lb;
+  int64_t ld, first, n;
+};
+int run_filter(const Batch &b, const BoundsTarget *to = nullptr) {
+  rsx_sc *h = b.h;
+  QueryWs *w = b.w;
+  hipStream_t s = b.s;
+  const QueryView &q = b.q;
+  const BoundsTarget t = to ? *to : BoundsTarget{b.lb(), b.ld, 0, b.n_items};
   DbView db = db_view(h);
-  if (first) {
-    db.hnT = static_cast<const char *>(db.hnT) + first * FILTER_DB_BYTES_PER_ENTRY;
-    db.spT = static_cast<const char *>(db.spT) + first * SPEC_DB_BYTES_PER_ENTRY;
-    db.cmask += first;
-    db.sp_aux += first;
+  if (t.first) {
+    db.hnT = static_cast<const char *>(db.hnT) + t.first * FILTER_DB_BYTES_PER_ENTRY;
+    db.spT = static_cast<const char *>(db.spT) + t.first * SPEC_DB_BYTES_PER_ENTRY;
+    db.cmask += t.first;
+    db.sp_aux += t.first;
   }
-  if (plan) RSX_TRY(h->w->f_plan.reserve(filter_plan_bytes(n_items), s, false));
+  const FilterPlanInput plan_in{b.n_elig, b.elig};
+  const FilterPlanInput *plan = (b.elig_monotone && b.elig) ? &plan_in : nullptr;
+  if (plan) RSX_TRY(w->f_plan.reserve(filter_plan_bytes(t.n), s, false));
   if (filter_kind_of(h) >= 1) {
     h->prof_kernel = spec2_filter_kernel_name();
-    RSX_TRY(launch_spec_query_images(q.desc, q.norm, q.nq, h->w->f_qimg.p, h->sp_tw.as<double>(), s));
+    RSX_TRY(launch_spec_query_images(q.desc, q.norm, q.nq, w->f_qimg.p, h->sp_tw.as<double>(), s));
     const int32_t *qmin = nullptr;
     const int64_t *cum = nullptr;
-    if (plan) RSX_TRY(launch_filter_plan(db, *plan, q.nq, n_items, 4, h->w->f_plan.p, &qmin, &cum, s));
+    if (plan) RSX_TRY(launch_filter_plan(db, *plan, q.nq, t.n, 4, w->f_plan.p, &qmin, &cum, s));
     ProfScope ps(&h->prof, s);
-    RSX_TRY(launch_spec_filter(db, h->w->f_qimg.p, q.nq, n_items, lb, ld, qmin, cum, s));
+    RSX_TRY(launch_spec_filter(db, w->f_qimg.p, q.nq, t.n, t.lb, t.ld, qmin, cum, s));
     ps.stop();
     return RSX_OK;
   }
   h->prof_kernel = filter_kernel_name();
-  RSX_TRY(launch_query_images(q.desc, q.norm, q.nq, h->w->f_qimg.p, s));
+  RSX_TRY(launch_query_images(q.desc, q.norm, q.nq, w->f_qimg.p, s));
   ProfScope ps(&h->prof, s);
-  RSX_TRY(launch_filter(db, h->w->f_qimg.p, q.nq, n_items, lb, ld, plan, plan ? h->w->f_plan.p : nullptr, s));
+  RSX_TRY(launch_filter(db, w->f_qimg.p, q.nq, t.n, t.lb, t.ld, plan, plan ? w->f_plan.p : nullptr, s));
   ps.stop();
   return RSX_OK;
 }
 
-// query batch size the filter workspaces are sized for: <= 1 GiB of (fp16) bounds, and the batches of a call equally long
-// (8192 queries against 100 000 entries used to run as 3 x 2684 + 140: the last launch chain at a fraction of the rate)
-int64_t filter_batch(int64_t n_items, int64_t nq) { return plan::filter_batch(n_items, nq); }  // sc_plan.h
-
-int filter_reserve(rsx_sc *h, int64_t n_items, int64_t qb, hipStream_t s) {
-  h->st.valid = false;  // bounds / short lists of a pending stage 2 are about to be overwritten
-  const int64_t ld = (n_items + 31) / 32 * 32;
-  RSX_TRY(h->w->f_qimg.reserve(any_qimg_bytes((int32_t)qb), s, false));
-  RSX_TRY(h->w->f_lb.reserve((size_t)qb * ld * sizeof(lb_t), s, false));
-  RSX_TRY(h->w->f_cand.reserve((size_t)qb * RESCORE_SHORTLIST_CAP * sizeof(RescoreEntry), s, false));
-  RSX_TRY(h->w->f_cnt.reserve((size_t)qb * sizeof(int32_t), s, false));
-  RSX_TRY(h->w->f_thr.reserve((size_t)qb * RESCORE_THR_STRIDE * sizeof(float), s, false));
-  RSX_TRY(h->w->f_win.reserve((size_t)qb * WINDOW_P * sizeof(WindowPreview), s, false));
-  RSX_TRY(h->w->f_surv.reserve((size_t)qb * WINDOW_LIST_STRIDE * sizeof(WindowSurvivor), s, false));
+// room for what run_filter writes for qb queries of the batch: their images and (rows: unless they go elsewhere) rows of bounds
+int reserve_bounds(const Batch &b, int64_t qb, bool rows = true) {
+  RSX_TRY(ws_reserve(b.h, b.w->f_qimg, any_qimg_bytes((int32_t)qb), b.s));
+  if (rows) RSX_TRY(ws_reserve(b.h, b.w->f_lb, (size_t)qb * b.ld * sizeof(lb_t), b.s));
   return RSX_OK;
 }
 
-// images -> MFMA filter -> short list + round edges of one query batch
-// elig_monotone: the per-query limits elig[] do not decrease with the query index (self queries)
-int filter_and_select(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, const int64_t *elig,
-                      int32_t first_target, int32_t k, hipStream_t s, bool elig_monotone = false) {
-  const DbView db = db_view(h);
-  const int64_t ld = (n_items + 31) / 32 * 32;
-  lb_t *lb = h->w->f_lb.as<lb_t>();
-  {
-    FilterPlanInput plan{n_eligible, elig};
-    const bool planned = elig_monotone && elig != nullptr;
-    RSX_TRY(run_filter(h, q, n_items, lb, ld, planned ? &plan : nullptr, s));
-  }
-  RSX_TRY(launch_select(db, lb, ld, n_items, q.nq, n_eligible, elig, first_target, h->w->f_cand.as<RescoreEntry>(),
-                        h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
-  // alignment + window preview of the head of every short list on the matrix cores (what re-scoring would otherwise
-  // do on the VALU, one entry per wavefront)
-  return launch_window(db, q, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                       h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s);
+// ... and for the stages behind it.  qb: the queries that go through the workspaces at a time (plan::filter_batch: <= 1 GiB of
+// fp16 bounds, and the batches of a call equally long)
+int filter_reserve(const Batch &b, int64_t qb) {
+  RSX_TRY(reserve_bounds(b, qb));
+  QueryWs *w = b.w;
+  RSX_TRY(ws_reserve(b.h, w->f_cand, (size_t)qb * RESCORE_SHORTLIST_CAP * sizeof(RescoreEntry), b.s));
+  RSX_TRY(ws_reserve(b.h, w->f_cnt, (size_t)qb * sizeof(int32_t), b.s));
+  RSX_TRY(ws_reserve(b.h, w->f_thr, (size_t)qb * RESCORE_THR_STRIDE * sizeof(float), b.s));
+  RSX_TRY(ws_reserve(b.h, w->f_win, (size_t)qb * WINDOW_P * sizeof(WindowPreview), b.s));
+  RSX_TRY(ws_reserve(b.h, w->f_surv, (size_t)qb * WINDOW_LIST_STRIDE * sizeof(WindowSurvivor), b.s));
+  return RSX_OK;
 }
 
-int rescore(rsx_sc *h, const QueryView &q, int64_t n_items, int64_t n_eligible, const int64_t *elig, int32_t round_begin,
-            int32_t round_end, const rsx_sc_hit *tau_src, const rsx_sc_hit *seed, int32_t k, rsx_sc_hit *d_out,
-            hipStream_t s) {
-  const int64_t ld = (n_items + 31) / 32 * 32;
-  return launch_rescore(db_view(h), q, h->w->f_lb.as<lb_t>(), ld, n_items, n_eligible, elig, h->w->f_cand.as<RescoreEntry>(),
-                        h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), filter_eps(), round_begin, round_end, tau_src,
-                        seed, d_out, k, s, (h->prof.on && h->stats.p) ? h->stats.as<unsigned long long>() : nullptr,
-                        h->w->f_surv.as<WindowSurvivor>(), rescore_packed(h));
+// Short list: the lowest bounds of every query with their round edges (first_target: the size of round 0), then alignment +
+// window preview of the head of every short list on the matrix cores (what re-scoring would otherwise do on the VALU, one
+// entry per wavefront)
+int shortlist(const Batch &b, int32_t first_target) {
+  const DbView db = db_view(b.h);
+  RSX_TRY(launch_select(db, b.lb(), b.ld, b.n_items, b.q.nq, b.n_elig, b.elig, first_target, b.cand(), b.cnt(), b.thr(), b.s));
+  return launch_window(db, b.q, b.cand(), b.cnt(), b.k, filter_eps(), b.win(), b.surv(), b.s);
 }
 
+// Exact re-scoring of the short lists in rounds of ascending bound -> records.  Every round by default; the two-stage protocol
+// runs round 0 first and the rest later, capped by the merged list of all shards (tau_src) and seeded with its own round 0
+struct Rounds {
+  int32_t begin = 0, end = RESCORE_ALL_ROUNDS;
+  const rsx_sc_hit *tau_src = nullptr, *seed = nullptr;
+};
+int rescore(const Batch &b, rsx_sc_hit *d_out, const Rounds &r = Rounds()) {
+  rsx_sc *h = b.h;
+  return launch_rescore(db_view(h), b.q, b.lb(), b.ld, b.n_items, b.n_elig, b.elig, b.cand(), b.cnt(), b.thr(), filter_eps(),
+                        r.begin, r.end, r.tau_src, r.seed, d_out, b.k, b.s,
+                        (h->prof.on && h->stats.p) ? h->stats.as<unsigned long long>() : nullptr, b.surv(), rescore_packed(h));
+}
+
+// size of the first re-scoring round; later rounds double (measured on MI355X with the earlier 4-wave rounds kernel, 10k
+// trajectory DB, 8192 queries, ms per step / exact evaluations per query: 64 -> 4.24 / 11.2, 128 -> 4.18 / 10.4)
 int32_t first_round_target() {
   static const int32_t v = [] {
     const char *e = rsx::exp_env("RSX_SC_FIRST_TARGET");
@@ -400,75 +482,52 @@ int32_t first_round_target() {
   return v;
 }
 
-// exhaustive top-k through the MFMA lower-bound filter (sc_filter.hip): filter -> short list ->
-// exact re-scoring in rounds of ascending bound.  Everything stays on the stream; no host sync.
-int run_topk_filtered(rsx_sc *h, const QueryView &qv, int64_t n_items, int64_t n_eligible, const int64_t *d_q_elig,
-                      int32_t k, rsx_sc_hit *d_out, hipStream_t s, bool elig_monotone) {
-  const int64_t qb = filter_batch(n_items, qv.nq);
-  RSX_TRY(filter_reserve(h, n_items, qb, s));
-  for (int64_t b0 = 0; b0 < qv.nq; b0 += qb) {
-    const int32_t bn = (int32_t)((qv.nq - b0 < qb) ? (qv.nq - b0) : qb);
-    QueryView q = qv;
-    q.desc = qv.desc + b0 * DS;
-    q.vkey = qv.vkey + b0 * NS;
-    q.norm = qv.norm + b0 * NS;
-    q.nq = bn;
-    const int64_t *elig = d_q_elig ? d_q_elig + b0 : nullptr;
-    // size of the first re-scoring round; later rounds double (measured on MI355X with the earlier 4-wave rounds kernel, 10k
-    // trajectory DB, 8192 queries, ms per step / exact evaluations per query: 64 -> 4.24 / 11.2, 128 -> 4.18 / 10.4)
-    RSX_TRY(filter_and_select(h, q, n_items, n_eligible, elig, first_round_target(), k, s, elig_monotone));
-    RSX_TRY(rescore(h, q, n_items, n_eligible, elig, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, d_out + b0 * k, s));
+// The chain behind the keys, one filter batch after the other: bounds(batch) puts the batch's rows of bounds in place (run_filter,
+// or the gather of rsx_sc_query_bounds_device), then short list -> exact re-scoring in rounds of ascending bound.  Everything
+// stays on the stream; no host sync
+template <class Bounds>
+int run_chain(const Batch &all, rsx_sc_hit *d_out, Bounds bounds) {
+  const int64_t nq = all.q.nq, qb = plan::filter_batch(all.n_items, nq);
+  RSX_TRY(filter_reserve(all, qb));
+  for (int64_t b0 = 0; b0 < nq; b0 += qb) {
+    const Batch b = slice(all, b0, (int32_t)((nq - b0 < qb) ? (nq - b0) : qb));
+    RSX_TRY(bounds(b));
+    RSX_TRY(shortlist(b, first_round_target()));
+    RSX_TRY(rescore(b, d_out + b0 * all.k));
   }
   return RSX_OK;
 }
 
-// a handful of queries (the live detector asks one at a time, PGO.cpp:561,577): ONE launch that streams the fp16 images of
-// every eligible entry once, previews every pair on the matrix cores and scores the few entries the previews cannot exclude
-// exactly (sc_q1.hip) -- instead of the exact-all kernel (one entry per wavefront in fp64) or the six launches of the batched
-// filter chain.  filter_mode 1 / 2 keep those paths; 3 asks for this one wherever it applies.  Records are identical.
-bool use_q1(const rsx_sc *h, int32_t nq, int64_t n_items) {
-  static const bool off = [] {
-    const char *e = rsx::exp_env("RSX_SC_Q1");
-    return e && e[0] == '0';
-  }();
-  const int m = filter_mode_of(h);
-  if (off || nq < 1 || nq > Q1_MAX_NQ || !(m == 0 || m == 3)) return false;
-  // every query streams the whole database again, so with several queries against a large database the batched chain (one
-  // pass of the spectral filter for all of them) takes over.  Round 6 (the queries of a call share the device's 512 workgroup
-  // slots, q1_grid): MI355X, top-1, us per call single-query path / filter chain -- 10 000 keyframes: 1 query 18 / 91, 2: 22 / 94,
-  // 4: 27 / 94, 8: 36 / 89; 100 000: 1 query 54 / 173, 2: 71 / 175, 4: 112 / 176, 8: 187 / 191 (round 5: 8 x 10 000 55, 8 x 100 000 305)
-  // 9 .. 16 queries (32 workgroups each): 10 000 keyframes 12 queries 47 / 92, 16: 53 / 87; 50 000: 8 queries 103 / 127, 12: 167 / 134, 16: 176 / 147
-  return m == 3 || nq == 1 || (int64_t)nq * n_items <= (nq <= 8 ? 800000 : 400000);
-}
-
-int run_q1(rsx_sc *h, const float *d_q, int32_t nq, int64_t n_items, int64_t n_eligible, const int64_t *d_q_elig, int32_t k,
-           rsx_sc_hit *d_out, hipStream_t s) {
-  if (n_items < 0) n_items = 0;
+// the single-query kernel (plan::Path::SingleQuery): needs no keys, b.q.desc is all it reads of the queries
+int run_q1(const Batch &b, rsx_sc_hit *d_out) {
+  rsx_sc *h = b.h;
+  hipStream_t s = b.s;
   if (!h->q1_ticket.p) {
     RSX_TRY(h->q1_ticket.reserve(q1_ticket_bytes(), s, false));
     RSX_HIP(hipMemsetAsync(h->q1_ticket.p, 0, q1_ticket_bytes(), s));
   }
-  RSX_TRY(h->q1_ws.reserve(q1_workspace_bytes(n_items, nq, k), s, false));
+  RSX_TRY(h->q1_ws.reserve(q1_workspace_bytes(b.n_items, b.q.nq, b.k), s, false));
   h->prof_kernel = q1_kernel_name();
   ProfScope ps(&h->prof, s);
-  RSX_TRY(launch_q1(db_view(h), d_q, nq, n_items, n_eligible, d_q_elig, k, d_out, h->q1_ws.p, h->q1_ticket.as<unsigned>(),
+  RSX_TRY(launch_q1(db_view(h), b.q.desc, b.q.nq, b.n_items, b.n_elig, b.elig, b.k, d_out, h->q1_ws.p, h->q1_ticket.as<unsigned>(),
                     (h->prof.on && h->stats.p) ? h->stats.as<unsigned long long>() : nullptr, s));
   ps.stop();
   return RSX_OK;
 }
 
-int run_topk(rsx_sc *h, const QueryView &qv, int64_t n_items, int64_t n_eligible, const int64_t *d_q_elig,
-             int32_t k, rsx_sc_hit *d_out, hipStream_t s, bool elig_monotone = false) {
-  if (use_q1(h, qv.nq, n_items)) return run_q1(h, qv.desc, qv.nq, n_items, n_eligible, d_q_elig, k, d_out, s);
-  if (use_filter(h, qv.nq, n_items)) return run_topk_filtered(h, qv, n_items, n_eligible, d_q_elig, k, d_out, s, elig_monotone);
+// exhaustive top-k of a batch on the path its entry chose (path_of)
+int run_topk(const Batch &b, plan::Path path, rsx_sc_hit *d_out) {
+  if (path == plan::Path::SingleQuery) return run_q1(b, d_out);
+  if (path == plan::Path::FilterChain) return run_chain(b, d_out, [](const Batch &fb) { return run_filter(fb); });
+  rsx_sc *h = b.h;
   h->prof_kernel = pair_kernel_name();
-  RSX_TRY(h->w->partial.reserve(pair_partial_bytes(n_items > 0 ? n_items : 1, qv.nq, k), s, false));
+  RSX_TRY(b.w->partial.reserve(pair_partial_bytes(b.n_items > 0 ? b.n_items : 1, b.q.nq, b.k), b.s, false));
   struct Hook {
     explicit Hook(PairProfiler *p) { set_pair_profiler(p); }
     ~Hook() { set_pair_profiler(nullptr); }
   } hook(&h->prof);
-  return launch_pairs(db_view(h), qv, nullptr, 0, n_items, n_eligible, d_q_elig, nullptr, nullptr,
-                      h->w->partial.as<rsx_sc_hit>(), d_out, k, s);
+  return launch_pairs(db_view(h), b.q, nullptr, 0, b.n_items, b.n_elig, b.elig, nullptr, nullptr, b.w->partial.as<rsx_sc_hit>(),
+                      d_out, b.k, b.s);
 }
 
 // the search tree over the ring keys of entries [0, n): built on the host exactly like the reference's nanoflann tree
@@ -557,6 +616,27 @@ int ensure_tree(rsx_sc *h, rsx_sc::KdTreeDev *t, int64_t n, std::unique_lock<std
   return upload_tree(h, t, p);
 }
 
+// The detector's device scratch (`small`): what the ring-key search and the candidate scoring hand each other.  Every array
+// has storage of its own -- nothing here depends on one kernel being done with a range before the next writes it
+struct DetectScratch {
+  // the candidates, kNN order: read back in ONE copy of kDetectReadBack bytes
+  int32_t idx[RSX_SC_MAX_TOPK];    // the tree walk's neighbours (zero where none was found)
+  int32_t shift[RSX_SC_MAX_TOPK];  // their alignments and exact distances (launch_pairs)
+  double dist[RSX_SC_MAX_TOPK];
+  // device only
+  float kd[RSX_SC_MAX_TOPK];       // the walk's ring-key distances
+  int32_t found;
+  int32_t b_idx[RSX_SC_MAX_TOPK];  // the brute-force pass: the true k nearest, whose k-th distance bounds the walk
+  float b_kd[RSX_SC_MAX_TOPK];
+  int32_t b_found;
+  int32_t cand_pos[KD_CAND_CAP];   // tree positions within that bound (the reduced walk)
+  int32_t cand_count;
+};
+constexpr size_t kSmallBytes = 4096, kDetectReadBack = offsetof(DetectScratch, kd);
+static_assert(sizeof(DetectScratch) <= kSmallBytes, "the detector's scratch must fit its reservation");
+static_assert(offsetof(DetectScratch, dist) % sizeof(double) == 0 && kDetectReadBack == RSX_SC_MAX_TOPK * (2 * sizeof(int32_t) + sizeof(double)),
+              "idx, shift and dist are contiguous: one read-back");
+
 // candidate scoring shared by detect_loop_closure / between_session (SC.cpp:362-417)
 int score_candidates_and_finish(rsx_sc *h, const QueryView &qv, const float *d_qkey, int64_t n_search, rsx_sc::KdTreeDev *tree,
                                 int mode, int32_t *loop_id, float *yaw, double *min_dist, int32_t *nn_idx) {
@@ -565,28 +645,23 @@ int score_candidates_and_finish(rsx_sc *h, const QueryView &qv, const float *d_q
   double best_d = 10000000;  // SC.cpp:362
   int best_align = 0, best_idx = 0;
   if (mode == RSX_SC_MODE_CANDIDATE) {
-    RSX_TRY(h->small.reserve(4096, s, false));
-    int32_t *d_idx = h->small.as<int32_t>();              // [k]
-    float *d_kd = reinterpret_cast<float *>(d_idx + 64);  // [k]
-    int32_t *d_found = d_idx + 128;
+    RSX_TRY(h->small.reserve(kSmallBytes, s, false));
+    DetectScratch *sm = h->small.as<DetectScratch>();
     if (n_search > 0) {
       // nanoflann's own walk of nanoflann's own tree: the reference's candidates, ties included (sc_kdtree.h)
       if (tree->n != n_search) return fail(RSX_ERR_INTERNAL, "ring-key tree over %lld keys was not prepared", (long long)n_search);
       // the true k-th smallest distance, by the parallel brute-force pass: lets the walk skip what cannot matter
-      int32_t *b_idx = d_idx + 192;
-      float *b_kd = reinterpret_cast<float *>(d_idx + 256);
-      int32_t *b_found = d_idx + 320;
       RSX_TRY(h->knn_ws.reserve((size_t)n_search * 2 * sizeof(float), s, false));
       float *dist_all = h->knn_ws.as<float>(), *dist_tree = dist_all + n_search;
-      RSX_TRY(launch_knn(h->rkey.as<float>(), n_search, d_qkey, k, dist_all, b_idx, b_kd, b_found, s));
-      int32_t *cand_pos = d_idx + 384, *cand_count = d_idx + 384 + 64;
-      RSX_TRY(launch_knn_tree_order(dist_all, tree->vind.as<int32_t>(), n_search, dist_tree, k, b_kd, b_found, cand_pos, cand_count, s));
+      RSX_TRY(launch_knn(h->rkey.as<float>(), n_search, d_qkey, k, dist_all, sm->b_idx, sm->b_kd, &sm->b_found, s));
+      RSX_TRY(launch_knn_tree_order(dist_all, tree->vind.as<int32_t>(), n_search, dist_tree, k, sm->b_kd, &sm->b_found, sm->cand_pos,
+                                    &sm->cand_count, s));
       KdSearchArgs ka;
-      ka.bound_dist = b_kd;
-      ka.bound_found = b_found;
+      ka.bound_dist = sm->b_kd;
+      ka.bound_found = &sm->b_found;
       ka.dist_tree = dist_tree;
-      ka.cand_pos = cand_pos;
-      ka.cand_count = cand_count;
+      ka.cand_pos = sm->cand_pos;
+      ka.cand_count = &sm->cand_count;
       ka.nodes = tree->nodes.as<KdNode16>();
       ka.n_nodes = tree->n_nodes;
       ka.n = n_search;
@@ -596,36 +671,32 @@ int score_candidates_and_finish(rsx_sc *h, const QueryView &qv, const float *d_q
       std::memcpy(ka.low, tree->low, sizeof(ka.low));
       std::memcpy(ka.high, tree->high, sizeof(ka.high));
       ka.k = k;
-      ka.out_idx = d_idx;
-      ka.out_dist = d_kd;
-      ka.out_found = d_found;
+      ka.out_idx = sm->idx;
+      ka.out_dist = sm->kd;
+      ka.out_found = &sm->found;
       RSX_TRY(launch_knn_tree(ka, s));
     } else {  // an empty search set (tree_making_period > 1 with num_exclude_recent changes): no neighbour, slots stay 0
       RSX_TRY(h->knn_ws.reserve(sizeof(float), s, false));
-      RSX_TRY(launch_knn(h->rkey.as<float>(), 0, d_qkey, k, h->knn_ws.as<float>(), d_idx, d_kd, d_found, s));
+      RSX_TRY(launch_knn(h->rkey.as<float>(), 0, d_qkey, k, h->knn_ws.as<float>(), sm->idx, sm->kd, &sm->found, s));
     }
-    // the k distances and shifts next to the indices in `small`: ONE read-back for all three
-    double *d_dist = reinterpret_cast<double *>(h->small.as<char>() + 1024);
-    int32_t *d_shift = reinterpret_cast<int32_t *>(h->small.as<char>() + 2048);
-    RSX_TRY(launch_pairs(db_view(h), qv, d_idx, 0, k, -1, nullptr, d_dist, d_shift, nullptr, nullptr, 0, s));
+    // the k distances and shifts next to the indices: ONE read-back for all three
+    RSX_TRY(launch_pairs(db_view(h), qv, sm->idx, 0, k, -1, nullptr, sm->dist, sm->shift, nullptr, nullptr, 0, s));
     RSX_TRY(ensure_pinned(h, 4096));
-    char *hp = static_cast<char *>(h->pinned.p);
-    RSX_HIP(hipMemcpyAsync(hp, h->small.p, 2048 + 256, hipMemcpyDeviceToHost, s));
+    RSX_HIP(hipMemcpyAsync(h->pinned.p, sm, kDetectReadBack, hipMemcpyDeviceToHost, s));
     RSX_HIP(hipStreamSynchronize(s));
-    const int32_t *ci = reinterpret_cast<const int32_t *>(hp);
-    const double *cd = reinterpret_cast<const double *>(hp + 1024);
-    const int32_t *cs = reinterpret_cast<const int32_t *>(hp + 2048);
+    const DetectScratch *got = static_cast<const DetectScratch *>(h->pinned.p);  // (its first kDetectReadBack bytes)
     for (int c = 0; c < k; c++) {  // SC.cpp:380-395: kNN order, strict <
-      if (cd[c] < best_d) {
-        best_d = cd[c];
-        best_align = cs[c];
-        best_idx = ci[c];
+      if (got->dist[c] < best_d) {
+        best_d = got->dist[c];
+        best_align = got->shift[c];
+        best_idx = got->idx[c];
       }
     }
   } else {
     // the one record goes straight into pinned host memory (device-visible): no copy to enqueue
     RSX_TRY(ensure_pinned(h, 4096));
-    RSX_TRY(run_topk(h, qv, n_search, n_search, nullptr, 1, static_cast<rsx_sc_hit *>(h->pinned.p), s));
+    const Batch b = batch_of(h, &h->ws[0], s, qv, n_search, 1);
+    RSX_TRY(run_topk(b, path_of(h, 1, b.n_items), static_cast<rsx_sc_hit *>(h->pinned.p)));
     RSX_HIP(hipStreamSynchronize(s));
     const rsx_sc_hit *r = static_cast<const rsx_sc_hit *>(h->pinned.p);
     if (r->dist < best_d) {
@@ -872,8 +943,8 @@ static int add_f32_locked(rsx_sc *h, const float *src, int64_t n, bool src_is_de
   // n consecutive global keyframes starting at h->n_global; copy the owned rows
   const int64_t g0 = h->n_global;
   const int64_t w = h->p.shard_world, r = h->p.shard_rank;
-  int64_t first = g0 + (((r - g0) % w) + w) % w;  // first owned global index >= g0
-  int64_t count = first < g0 + n ? (g0 + n - first + w - 1) / w : 0;
+  const int64_t first = g0 + (((r - g0) % w) + w) % w;  // first owned global index >= g0
+  const int64_t count = plan::owned_below(g0 + n, r, w) - plan::owned_below(g0, r, w);
   if (count > 0) {
     const int64_t slot = h->n_local;
     RSX_TRY(ensure_capacity(h, slot + count));
@@ -932,7 +1003,6 @@ int rsx_sc_add_descriptors_f32_device(rsx_sc *h, const float *d_descs, int64_t n
   if (!h || (!d_descs && n) || n < 0) return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (n == 0) return RSX_OK;
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
   return add_f32_locked(h, d_descs, n, true, s);
@@ -945,7 +1015,6 @@ int rsx_sc_add_polar_batch_device(rsx_sc *h, rsx_radarsc *rc, const uint8_t *d_i
   if (n_images == 0) return RSX_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   std::lock_guard<std::mutex> lkr(rsx::rc::mutex_of(rc));
-  RSX_TRY(set_device(h));
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
   // the descriptors stay in rc's scratch, which rc orders behind s for its next call
@@ -1070,8 +1139,7 @@ int rsx_sc_load(rsx_sc *h, const char *path, int64_t *n_loaded) try {
   // the header is not trusted: a shard holds exactly the indices i < n_global with i % world == rank, and the file must
   // be as long as it says BEFORE anything is allocated from its numbers
   if (ok) {
-    const int64_t expect = hd.n_global > hd.shard_rank ? (hd.n_global - hd.shard_rank + hd.shard_world - 1) / hd.shard_world : 0;
-    ok = hd.n_local == expect;
+    ok = hd.n_local == plan::owned_below(hd.n_global, hd.shard_rank, hd.shard_world);
   }
   if (ok) {
     const long here = std::ftell(f);
@@ -1293,29 +1361,27 @@ int rsx_sc_detect_between_session(rsx_sc *h, const float *curr_key20, const doub
   RSX_HIP(hipMemcpyAsync(h->q_desc.p, f, sizeof(f), hipMemcpyHostToDevice, s));
   float *d_key = reinterpret_cast<float *>(static_cast<char *>(h->q_desc.p) + sizeof(f));
   RSX_HIP(hipMemcpyAsync(d_key, curr_key20, NR * sizeof(float), hipMemcpyHostToDevice, s));
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, h->q_desc.as<float>(), 1, s, &qv));
-  return score_candidates_and_finish(h, qv, d_key, h->batch_size, &h->tree_batch, RSX_SC_MODE_CANDIDATE, loop_id, yaw, min_dist, nn_idx);
+  Batch b = batch_of(h, &h->ws[0], s, QueryView{h->q_desc.as<float>(), nullptr, nullptr, 1}, h->batch_size, 1);
+  RSX_TRY(make_keys(&b));
+  return score_candidates_and_finish(h, b.q, d_key, h->batch_size, &h->tree_batch, RSX_SC_MODE_CANDIDATE, loop_id, yaw, min_dist, nn_idx);
 } RSX_CATCH_ALL
 
-static int query_device_locked(rsx_sc *h, const float *d_q, int32_t nq, int32_t k, int64_t n_eligible, rsx_sc_hit *d_out,
-                               hipStream_t s) {
-  const int64_t items = local_count_below(h, n_eligible);
-  if (use_q1(h, nq, items))  // builds the query's keys and images itself: no keys launch
-    return run_q1(h, d_q, nq, items, n_eligible < 0 ? h->n_global : n_eligible, nullptr, k, d_out, s);
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, d_q, nq, s, &qv));
-  return run_topk(h, qv, items, n_eligible < 0 ? h->n_global : n_eligible, nullptr, k, d_out, s);
+// exhaustive top-k of device queries: keys (unless the single-query kernel takes them: it builds its own) -> the chosen path
+static int query_device_locked(rsx_sc *h, QueryWs *w, hipStream_t s, const float *d_q, int32_t nq, int32_t k, int64_t n_eligible,
+                               rsx_sc_hit *d_out) {
+  Batch b = batch_of(h, w, s, QueryView{d_q, nullptr, nullptr, nq}, n_eligible, k);
+  const plan::Path path = path_of(h, nq, b.n_items);
+  if (path != plan::Path::SingleQuery) RSX_TRY(make_keys(&b));
+  return run_topk(b, path, d_out);
 }
 
 int rsx_sc_query_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t k, int64_t n_eligible, rsx_sc_hit *d_out, void *stream) try {
   if (!h || !d_q || !d_out || nq < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k must be in [1,%d]", RSX_SC_MAX_TOPK);
+  RSX_TRY(check_k(k));
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
-  return query_device_locked(h, d_q, nq, k, n_eligible, d_out, s);
+  return query_device_locked(h, &h->ws[0], s, d_q, nq, k, n_eligible, d_out);
 } RSX_CATCH_ALL
 
 // How the host-buffer entry cuts a batch into pieces: the upload of the first piece is the only one nothing hides, every
@@ -1348,7 +1414,7 @@ int host_pieces(int32_t nq, int32_t *sizes) {
 
 int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eligible, rsx_sc_hit *out) try {
   if (!h || !q || !out || nq < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k must be in [1,%d]", RSX_SC_MAX_TOPK);
+  RSX_TRY(check_k(k));
   // one lock for staging, query and read-back: two concurrent callers share q_desc / topk
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_TRY(own_stream(h));
@@ -1375,14 +1441,14 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
       src = static_cast<char *>(h->pinned.p) + 4096;
     }
     RSX_HIP(hipMemcpyAsync(h->q_desc.p, src, q_bytes, hipMemcpyHostToDevice, h->stream));
-    RSX_TRY(query_device_locked(h, h->q_desc.as<float>(), nq, k, n_eligible, static_cast<rsx_sc_hit *>(h->pinned.p), h->stream));
+    RSX_TRY(query_device_locked(h, &h->ws[0], h->stream, h->q_desc.as<float>(), nq, k, n_eligible, static_cast<rsx_sc_hit *>(h->pinned.p)));
     RSX_TRY(sync_learning(h, h->stream));
     std::memcpy(out, h->pinned.p, out_bytes);
     return RSX_OK;
   }
   if (np == 1) {
     RSX_HIP(hipMemcpyAsync(h->q_desc.p, q, (size_t)nq * DS * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    RSX_TRY(query_device_locked(h, h->q_desc.as<float>(), nq, k, n_eligible, h->topk.as<rsx_sc_hit>(), h->stream));
+    RSX_TRY(query_device_locked(h, &h->ws[0], h->stream, h->q_desc.as<float>(), nq, k, n_eligible, h->topk.as<rsx_sc_hit>()));
   } else {
     // Piece c + 1 goes up on up_stream while piece c is scored.  The order of the calls matters for pageable memory,
     // where hipMemcpyAsync returns only when the runtime has staged the whole piece: the scoring of piece c is enqueued
@@ -1407,46 +1473,23 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
     // the FILTER runs piece by piece -- keys, query images and bound rows of piece c while piece c + 1 goes up -- and the stages
     // behind it (short lists, window previews, re-scoring) run ONCE over the whole batch: their fixed costs (~90 us of dependent
     // small kernels per piece) are what the piecewise chains paid three times.
-    const int64_t items = local_count_below(h, n_eligible), elig_all = n_eligible < 0 ? h->n_global : n_eligible;
-    const bool one_tail = !use_q1(h, nq, items) && use_filter(h, nq, items) && filter_batch(items, nq) >= nq;
+    Batch all = batch_of(h, &h->ws[0], h->stream, QueryView{h->q_desc.as<float>(), nullptr, nullptr, nq}, n_eligible, k);
+    const bool one_tail = plan::one_tail(path_of(h, nq, all.n_items), all.n_items, nq);
     auto filter_pieces_one_tail = [&]() -> int {
-      hipStream_t s = h->stream;
-      h->w = &h->ws[0];
-      RSX_TRY(filter_reserve(h, items, nq, s));
-      QueryView all;
-      {  // (prepare_queries without its launch: the keys are built piece by piece)
-        h->st.valid = false;
-        RSX_TRY(h->w->q_vkey.reserve((size_t)nq * NS * sizeof(double), s, false));
-        RSX_TRY(h->w->q_norm.reserve((size_t)nq * NS * sizeof(double), s, false));
-        RSX_TRY(h->w->q_rkey.reserve((size_t)nq * NR * sizeof(float), s, false));
-        all.desc = h->q_desc.as<float>();
-        all.vkey = h->w->q_vkey.as<double>();
-        all.norm = h->w->q_norm.as<double>();
-        all.nq = nq;
-      }
-      const int64_t ld = (items + 31) / 32 * 32;
-      lb_t *lb = h->w->f_lb.as<lb_t>();
+      RSX_TRY(filter_reserve(all, nq));
+      RSX_TRY(make_keys(&all, /*launch=*/false));
       RSX_TRY(upload(0, 0));
       int64_t q0 = 0;
       for (int c = 0; c < np; c++) {
-        RSX_HIP(hipStreamWaitEvent(s, h->up_ev[c], 0));
-        RSX_TRY(launch_keys(all.desc + q0 * DS, sizes[c], h->w->q_vkey.as<double>() + q0 * NS, h->w->q_norm.as<double>() + q0 * NS,
-                            h->w->q_rkey.as<float>() + q0 * NR, s, h->p.sum_order));
-        QueryView piece = all;
-        piece.desc = all.desc + q0 * DS;
-        piece.vkey = all.vkey + q0 * NS;
-        piece.norm = all.norm + q0 * NS;
-        piece.nq = sizes[c];
-        RSX_TRY(run_filter(h, piece, items, lb + q0 * ld, ld, nullptr, s));  // (the query images of a piece are consumed by its own launch)
+        RSX_HIP(hipStreamWaitEvent(all.s, h->up_ev[c], 0));
+        const Batch piece = slice(all, q0, sizes[c], /*own_rows=*/true);
+        RSX_TRY(build_keys(piece));
+        RSX_TRY(run_filter(piece));  // (the query images of a piece are consumed by its own launch)
         q0 += sizes[c];
         if (c + 1 < np) RSX_TRY(upload(c + 1, q0));
       }
-      const DbView db = db_view(h);
-      RSX_TRY(launch_select(db, lb, ld, items, nq, elig_all, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
-                            h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
-      RSX_TRY(launch_window(db, all, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                            h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s));
-      return rescore(h, all, items, elig_all, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, h->topk.as<rsx_sc_hit>(), s);
+      RSX_TRY(shortlist(all, first_round_target()));
+      return rescore(all, h->topk.as<rsx_sc_hit>());
     };
     auto all_pieces = [&]() -> int {
       if (one_tail) return filter_pieces_one_tail();
@@ -1455,12 +1498,12 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
       RSX_HIP(hipStreamWaitEvent(h->stream_b, h->lane_ev, 0));
       RSX_TRY(upload(0, 0));
       int64_t q0 = 0;
-      for (int c = 0; c < np; c++) {
-        hipStream_t lane = two_lanes && (c & 1) ? h->stream_b : h->stream;
-        h->w = &h->ws[two_lanes ? (c & 1) : 0];
-        RSX_HIP(hipStreamWaitEvent(lane, h->up_ev[c], 0));
-        RSX_TRY(query_device_locked(h, h->q_desc.as<float>() + q0 * DS, sizes[c], k, n_eligible,
-                                    h->topk.as<rsx_sc_hit>() + q0 * k, lane));
+      for (int c = 0; c < np; c++) {  // every piece a query of its own (it chooses its own path), in the set of its lane
+        const int lane = two_lanes ? (c & 1) : 0;
+        hipStream_t ls = lane ? h->stream_b : h->stream;
+        RSX_HIP(hipStreamWaitEvent(ls, h->up_ev[c], 0));
+        RSX_TRY(query_device_locked(h, &h->ws[lane], ls, h->q_desc.as<float>() + q0 * DS, sizes[c], k, n_eligible,
+                                    h->topk.as<rsx_sc_hit>() + q0 * k));
         q0 += sizes[c];
         if (c + 1 < np) RSX_TRY(upload(c + 1, q0));
       }
@@ -1468,12 +1511,7 @@ int rsx_sc_query(rsx_sc *h, const float *q, int32_t nq, int32_t k, int64_t n_eli
       RSX_HIP(hipStreamWaitEvent(h->stream, h->lane_ev, 0));
       return RSX_OK;
     };
-    struct BackToSetZero {  // also when something below throws (the firewall turns that into a status)
-      rsx_sc *h;
-      ~BackToSetZero() { h->w = &h->ws[0]; }
-    } back{h};
     const int st = all_pieces();
-    h->w = &h->ws[0];
     if (st != RSX_OK) {  // nothing of this call may still be in flight when the caller gets its buffers back
       (void)hipStreamSynchronize(h->up_stream);
       (void)hipStreamSynchronize(h->stream_b);
@@ -1490,58 +1528,44 @@ int rsx_sc_filter_range_device(rsx_sc *h, const float *d_q, int32_t nq, int64_t 
                                int64_t ld, void *stream) try {
   if (!h || !d_q || !d_lb || nq < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
   if (first_slot < 0 || first_slot % 32 || n_slots < 0) return fail(RSX_ERR_BAD_ARG, "the range must start at a multiple of 32 slots");
-  if (ld < (n_slots + 31) / 32 * 32 || ld % 8) return fail(RSX_ERR_BAD_ARG, "ld must cover the range rounded up to 32 slots");
+  if (ld < plan::padded_ld(n_slots) || ld % 8) return fail(RSX_ERR_BAD_ARG, "ld must cover the range rounded up to 32 slots");
   if ((reinterpret_cast<uintptr_t>(d_lb) & 15u) != 0) return fail(RSX_ERR_BAD_ARG, "d_lb must be 16-byte aligned");
   if (n_slots == 0) return RSX_OK;  // an empty range (a rank beyond the entries of a small database) names no slot
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
   if (first_slot + n_slots > h->n_local) return fail(RSX_ERR_RANGE, "slots [%lld, %lld) of %lld", (long long)first_slot,
                                                      (long long)(first_slot + n_slots), (long long)h->n_local);
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, d_q, nq, s, &qv));
-  RSX_TRY(h->w->f_qimg.reserve(any_qimg_bytes(nq), s, false));
-  return run_filter(h, qv, n_slots, reinterpret_cast<lb_t *>(d_lb), ld, nullptr, s, first_slot);
+  Batch b = batch_of(h, &h->ws[0], s, QueryView{d_q, nullptr, nullptr, nq}, -1, 0);
+  RSX_TRY(make_keys(&b));
+  RSX_TRY(reserve_bounds(b, nq, /*rows=*/false));
+  const BoundsTarget to{reinterpret_cast<lb_t *>(d_lb), ld, first_slot, n_slots};
+  return run_filter(b, &to);
 } RSX_CATCH_ALL
 
 int rsx_sc_query_bounds_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t k, int64_t n_eligible, const rsx_f16 *d_lb_blocks,
                                int32_t n_blocks, int64_t block_ld, int64_t block_stride, rsx_sc_hit *d_out, void *stream) try {
   if (!h || !d_q || !d_lb_blocks || !d_out || nq < 1 || n_blocks < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k must be in [1,%d]", RSX_SC_MAX_TOPK);
+  RSX_TRY(check_k(k));
   if ((reinterpret_cast<uintptr_t>(d_lb_blocks) & 15u) != 0)  // the blocks are read with 16-byte loads
     return fail(RSX_ERR_BAD_ARG, "d_lb_blocks must be 16-byte aligned");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
   if (h->p.shard_world != 1) return fail(RSX_ERR_BAD_ARG, "bounds from filter shards need the whole database in this handle (shard_world 1)");
-  hipStream_t s;
-  RSX_TRY(use_stream(h, stream, &s));
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, d_q, nq, s, &qv));
-  const int64_t n_elig = n_eligible < 0 ? h->n_global : n_eligible;
-  const int64_t n_items = local_count_below(h, n_eligible);
-  if (n_items <= 0) return launch_pairs(db_view(h), qv, nullptr, 0, 0, n_elig, nullptr, nullptr, nullptr, nullptr, d_out, k, s);
-  const int64_t ld = (n_items + 31) / 32 * 32;
-  if (block_ld < 32 || block_ld % 32 || (int64_t)n_blocks * block_ld < ld || block_stride < (int64_t)nq * block_ld || block_stride % 8)
+  // every check before the first reservation or launch: a refused call leaves the workspaces (and a pending stage 1) alone
+  const int64_t n_items = local_count_below(h, elig_limit(h, n_eligible));
+  if (n_items > 0 && (block_ld < 32 || block_ld % 32 || (int64_t)n_blocks * block_ld < plan::padded_ld(n_items) ||
+                      block_stride < (int64_t)nq * block_ld || block_stride % 8))
     return fail(RSX_ERR_BAD_ARG, "%d blocks of %lld columns do not cover %lld eligible entries", n_blocks, (long long)block_ld,
                 (long long)n_items);
-  const int64_t qb = filter_batch(n_items, nq);
-  RSX_TRY(filter_reserve(h, n_items, qb, s));
-  const DbView db = db_view(h);
-  for (int64_t b0 = 0; b0 < nq; b0 += qb) {
-    QueryView q = qv;
-    q.desc = qv.desc + b0 * DS;
-    q.vkey = qv.vkey + b0 * NS;
-    q.norm = qv.norm + b0 * NS;
-    q.nq = (int32_t)((nq - b0 < qb) ? (nq - b0) : qb);
-    RSX_TRY(launch_gather_bounds(reinterpret_cast<const lb_t *>(d_lb_blocks), block_ld, block_stride, b0, q.nq, h->w->f_lb.as<lb_t>(), ld, s));
-    RSX_TRY(launch_select(db, h->w->f_lb.as<lb_t>(), ld, n_items, q.nq, n_elig, nullptr, first_round_target(), h->w->f_cand.as<RescoreEntry>(),
-                          h->w->f_cnt.as<int32_t>(), h->w->f_thr.as<float>(), s));
-    RSX_TRY(launch_window(db, q, h->w->f_cand.as<RescoreEntry>(), h->w->f_cnt.as<int32_t>(), k, filter_eps(),
-                          h->w->f_win.as<WindowPreview>(), h->w->f_surv.as<WindowSurvivor>(), s));
-    RSX_TRY(rescore(h, q, n_items, n_elig, nullptr, 0, RESCORE_ALL_ROUNDS, nullptr, nullptr, k, d_out + b0 * k, s));
-  }
-  return RSX_OK;
+  hipStream_t s;
+  RSX_TRY(use_stream(h, stream, &s));
+  Batch b = batch_of(h, &h->ws[0], s, QueryView{d_q, nullptr, nullptr, nq}, n_eligible, k);
+  RSX_TRY(make_keys(&b));
+  if (b.n_items <= 0)  // nothing to rank: k padding records per query
+    return launch_pairs(db_view(h), b.q, nullptr, 0, 0, b.n_elig, nullptr, nullptr, nullptr, nullptr, d_out, k, b.s);
+  return run_chain(b, d_out, [&](const Batch &fb) {
+    return launch_gather_bounds(reinterpret_cast<const lb_t *>(d_lb_blocks), block_ld, block_stride, fb.q0, fb.q.nq, fb.lb(), fb.ld, fb.s);
+  });
 } RSX_CATCH_ALL
 
 int rsx_sc_query_stage1_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t k, int64_t n_eligible,
@@ -1552,18 +1576,17 @@ int rsx_sc_query_stage1_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t 
 int rsx_sc_query_stage1_elig_device(rsx_sc *h, const float *d_q, int32_t nq, int32_t k, int64_t n_eligible,
                                     const int64_t *d_q_elig, int32_t elig_monotone, rsx_sc_hit *d_partial, void *stream) try {
   if (!h || !d_q || !d_partial || nq < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k must be in [1,%d]", RSX_SC_MAX_TOPK);
+  RSX_TRY(check_k(k));
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
-  h->st.valid = false;
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, d_q, nq, s, &qv));
-  const int64_t items = local_count_below(h, n_eligible);
-  const int64_t n_elig = n_eligible < 0 ? h->n_global : n_eligible;
+  Batch b = batch_of(h, &h->ws[0], s, QueryView{d_q, nullptr, nullptr, nq}, n_eligible, k, d_q_elig, elig_monotone != 0);
+  RSX_TRY(make_keys(&b));  // (voids a pending stage 1: ws_reserve)
   RSX_TRY(h->st_partial.reserve((size_t)nq * k * sizeof(rsx_sc_hit), s, false));
-  const bool filtered = use_filter(h, nq, items) && filter_batch(items, nq) >= nq;
+  // one question: is the chain split between the stages (the workspaces then stay as they are until stage 2), and if not,
+  // which path scores the batch whole (sc_plan.h stage1_plan)
+  const plan::Stage1Plan sp = plan::stage1_plan(filter_mode_of(h), nq, b.n_items, q1_allowed());
+  const bool filtered = sp.split;
   if (filtered) {
     // round 0 only: this shard's share of the ~160 lowest bounds per query -- enough for the merged
     // k-th distance to be the final one for almost every query (a single GPU needs ~120 exact scores
@@ -1575,26 +1598,19 @@ int rsx_sc_query_stage1_elig_device(rsx_sc *h, const float *d_q, int32_t nq, int
       const int v = (e && *e) ? atoi(e) : 0;
       return v > 0 ? v : 160;
     }();
-    int32_t first = (stage1_total + h->p.shard_world - 1) / h->p.shard_world;
-    if (first < 8) first = 8;
-    if (first > 128) first = 128;
-    RSX_TRY(filter_reserve(h, items, nq, s));
+    RSX_TRY(filter_reserve(b, nq));
+    RSX_TRY(run_filter(b));
     // (every shard makes the window records of its whole list head in stage 1: making the records behind a shorter head on
     // demand in stage 2 was measured slower)
-    RSX_TRY(filter_and_select(h, qv, items, n_elig, d_q_elig, first, k, s, elig_monotone != 0));
-    RSX_TRY(rescore(h, qv, items, n_elig, d_q_elig, 0, 1, nullptr, nullptr, k, h->st_partial.as<rsx_sc_hit>(), s));
+    RSX_TRY(shortlist(b, plan::stage1_share(stage1_total, h->p.shard_world)));
+    RSX_TRY(rescore(b, h->st_partial.as<rsx_sc_hit>(), Rounds{0, 1}));
   } else {
-    RSX_TRY(run_topk(h, qv, items, n_elig, d_q_elig, k, h->st_partial.as<rsx_sc_hit>(), s, elig_monotone != 0));  // complete already
+    RSX_TRY(run_topk(b, sp.whole, h->st_partial.as<rsx_sc_hit>()));  // complete already
   }
   RSX_HIP(hipMemcpyAsync(d_partial, h->st_partial.p, (size_t)nq * k * sizeof(rsx_sc_hit), hipMemcpyDeviceToDevice, s));
   h->st.valid = true;
   h->st.filtered = filtered;
-  h->st.nq = nq;
-  h->st.k = k;
-  h->st.n_items = items;
-  h->st.n_eligible = n_elig;
-  h->st.q_elig = d_q_elig;
-  h->st.qv = qv;
+  h->st.b = b;
   return RSX_OK;
 } RSX_CATCH_ALL
 
@@ -1602,27 +1618,24 @@ int rsx_sc_query_stage2_device(rsx_sc *h, int32_t nq, int32_t k, const rsx_sc_hi
                                void *stream) try {
   if (!h || !d_global || !d_out) return fail(RSX_ERR_BAD_ARG, "null arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->st.valid || h->st.nq != nq || h->st.k != k)
+  if (!h->st.valid || h->st.b.q.nq != nq || h->st.b.k != k)
     return fail(RSX_ERR_BAD_ARG, "stage 2 without a matching stage 1 (nq=%d k=%d)", nq, k);
-  RSX_TRY(set_device(h));
-  hipStream_t s;
-  RSX_TRY(use_stream(h, stream, &s));
-  h->st.valid = false;
-  if (h->st.filtered)
-    return rescore(h, h->st.qv, h->st.n_items, h->st.n_eligible, h->st.q_elig, 1, RESCORE_ALL_ROUNDS, d_global,
-                   h->st_partial.as<rsx_sc_hit>(), k, d_out, s);
-  RSX_HIP(hipMemcpyAsync(d_out, h->st_partial.p, (size_t)nq * k * sizeof(rsx_sc_hit), hipMemcpyDeviceToDevice, s));
+  Batch b = h->st.b;  // as stage 1 left it, on this call's stream
+  const bool filtered = h->st.filtered;
+  RSX_TRY(use_stream(h, stream, &b.s));
+  h->st = {};  // consumed
+  if (filtered) return rescore(b, d_out, Rounds{1, RESCORE_ALL_ROUNDS, d_global, h->st_partial.as<rsx_sc_hit>()});
+  RSX_HIP(hipMemcpyAsync(d_out, h->st_partial.p, (size_t)nq * k * sizeof(rsx_sc_hit), hipMemcpyDeviceToDevice, b.s));
   return RSX_OK;
 } RSX_CATCH_ALL
 
 int rsx_sc_query_self_device(rsx_sc *h, int64_t q_first, int32_t nq, int32_t k, int64_t n_eligible, int32_t exclude_recent,
                              rsx_sc_hit *d_out, void *stream) try {
   if (!h || !d_out || nq < 1) return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k must be in [1,%d]", RSX_SC_MAX_TOPK);
+  RSX_TRY(check_k(k));
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->p.shard_world != 1) return fail(RSX_ERR_BAD_ARG, "query_self needs an unsharded handle (queries must be local)");
   if (q_first < 0 || q_first + nq > h->n_global) return fail(RSX_ERR_RANGE, "query range out of bounds");
-  RSX_TRY(set_device(h));
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
   QueryView qv;
@@ -1630,7 +1643,6 @@ int rsx_sc_query_self_device(rsx_sc *h, int64_t q_first, int32_t nq, int32_t k, 
   qv.vkey = h->vkey.as<double>() + q_first * NS;
   qv.norm = h->norm.as<double>() + q_first * NS;
   qv.nq = nq;
-  if (n_eligible < 0 || n_eligible > h->n_global) n_eligible = h->n_global;
   const int64_t *d_elig = nullptr;
   if (exclude_recent >= 0) {
     std::vector<int64_t> e((size_t)nq);
@@ -1644,7 +1656,8 @@ int rsx_sc_query_self_device(rsx_sc *h, int64_t q_first, int32_t nq, int32_t k, 
     d_elig = h->q_elig.as<int64_t>();
   }
   // the limits q_first + i - exclude_recent grow with i: the filter skips what a query cannot see
-  return run_topk(h, qv, local_count_below(h, n_eligible), n_eligible, d_elig, k, d_out, s, /*elig_monotone=*/true);
+  const Batch b = batch_of(h, &h->ws[0], s, qv, n_eligible, k, d_elig, /*elig_monotone=*/true);
+  return run_topk(b, path_of(h, nq, b.n_items), d_out);
 } RSX_CATCH_ALL
 
 int rsx_sc_pair_distances(rsx_sc *h, const float *q_desc, int64_t first, int64_t count, double *out_dist, int32_t *out_shift) try {
@@ -1656,12 +1669,12 @@ int rsx_sc_pair_distances(rsx_sc *h, const float *q_desc, int64_t first, int64_t
   hipStream_t s = h->stream;
   RSX_TRY(h->q_desc.reserve(DS * sizeof(float), s, false));
   RSX_HIP(hipMemcpyAsync(h->q_desc.p, q_desc, DS * sizeof(float), hipMemcpyHostToDevice, s));
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, h->q_desc.as<float>(), 1, s, &qv));
+  Batch b = batch_of(h, &h->ws[0], s, QueryView{h->q_desc.as<float>(), nullptr, nullptr, 1}, -1, 0);
+  RSX_TRY(make_keys(&b));
   RSX_TRY(h->pair_out.reserve((size_t)count * (sizeof(double) + sizeof(int32_t)), s, false));
   double *d_dist = h->pair_out.as<double>();
   int32_t *d_shift = reinterpret_cast<int32_t *>(d_dist + count);
-  RSX_TRY(launch_pairs(db_view(h), qv, nullptr, first, count, -1, nullptr, d_dist, d_shift, nullptr, nullptr, 0, s));
+  RSX_TRY(launch_pairs(db_view(h), b.q, nullptr, first, count, -1, nullptr, d_dist, d_shift, nullptr, nullptr, 0, s));
   RSX_HIP(hipMemcpyAsync(out_dist, d_dist, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s));
   RSX_HIP(hipMemcpyAsync(out_shift, d_shift, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   RSX_HIP(hipStreamSynchronize(s));
@@ -1675,17 +1688,15 @@ int rsx_sc_filter_bounds(rsx_sc *h, const float *q_descs, int32_t nq, float *out
   hipStream_t s = h->stream;
   const int64_t n = h->n_local;
   if (n == 0) return RSX_OK;
-  const int64_t ld = (n + 31) / 32 * 32;
   RSX_TRY(h->q_desc.reserve((size_t)nq * DS * sizeof(float), s, false));
   RSX_HIP(hipMemcpyAsync(h->q_desc.p, q_descs, (size_t)nq * DS * sizeof(float), hipMemcpyHostToDevice, s));
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, h->q_desc.as<float>(), nq, s, &qv));
-  RSX_TRY(h->w->f_qimg.reserve(any_qimg_bytes(nq), s, false));
-  RSX_TRY(h->w->f_lb.reserve((size_t)nq * ld * sizeof(lb_t), s, false));
-  RSX_TRY(run_filter(h, qv, n, h->w->f_lb.as<lb_t>(), ld, nullptr, s));
+  Batch b = batch_of(h, &h->ws[0], s, QueryView{h->q_desc.as<float>(), nullptr, nullptr, nq}, -1, 0);  // every local entry
+  RSX_TRY(make_keys(&b));
+  RSX_TRY(reserve_bounds(b, nq));
+  RSX_TRY(run_filter(b));
   // the matrix is fp16 on the device (sc_kernels.h lb_t); this diagnostic entry hands out the same values as float
   std::vector<lb_t> host((size_t)nq * (size_t)n);
-  RSX_HIP(hipMemcpy2DAsync(host.data(), (size_t)n * sizeof(lb_t), h->w->f_lb.p, (size_t)ld * sizeof(lb_t), (size_t)n * sizeof(lb_t),
+  RSX_HIP(hipMemcpy2DAsync(host.data(), (size_t)n * sizeof(lb_t), b.lb(), (size_t)b.ld * sizeof(lb_t), (size_t)n * sizeof(lb_t),
                            (size_t)nq, hipMemcpyDeviceToHost, s));
   RSX_HIP(hipStreamSynchronize(s));
   for (size_t i = 0; i < host.size(); i++) out_lb[i] = (float)host[i];
@@ -1698,7 +1709,7 @@ int rsx_sc_window_previews(rsx_sc *h, const float *q_descs, int32_t nq, int32_t 
                            int32_t *out_kstar, int32_t *out_shift_mask, int32_t *out_counts) try {
   if (!h || !q_descs || !out_slots || !out_pv || !out_kstar || !out_shift_mask || !out_counts || nq < 1)
     return fail(RSX_ERR_BAD_ARG, "bad arg");
-  if (k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "k=%d out of range [1,%d]", k, RSX_SC_MAX_TOPK);
+  RSX_TRY(check_k(k));
   std::lock_guard<std::mutex> lk(h->mu);
   RSX_TRY(own_stream(h));
   hipStream_t s = h->stream;
@@ -1707,17 +1718,18 @@ int rsx_sc_window_previews(rsx_sc *h, const float *q_descs, int32_t nq, int32_t 
   if (n == 0) return RSX_OK;
   RSX_TRY(h->q_desc.reserve((size_t)nq * DS * sizeof(float), s, false));
   RSX_HIP(hipMemcpyAsync(h->q_desc.p, q_descs, (size_t)nq * DS * sizeof(float), hipMemcpyHostToDevice, s));
-  QueryView qv;
-  RSX_TRY(prepare_queries(h, h->q_desc.as<float>(), nq, s, &qv));
-  RSX_TRY(filter_reserve(h, n, nq, s));
-  RSX_HIP(hipMemsetAsync(h->w->f_win.p, 0xff, (size_t)nq * WINDOW_P * sizeof(WindowPreview), s));
-  RSX_TRY(filter_and_select(h, qv, n, h->n_global, nullptr, 128, k, s));
+  Batch b = batch_of(h, &h->ws[0], s, QueryView{h->q_desc.as<float>(), nullptr, nullptr, nq}, -1, k);  // every local entry
+  RSX_TRY(make_keys(&b));
+  RSX_TRY(filter_reserve(b, nq));
+  RSX_HIP(hipMemsetAsync(b.win(), 0xff, (size_t)nq * WINDOW_P * sizeof(WindowPreview), s));
+  RSX_TRY(run_filter(b));
+  RSX_TRY(shortlist(b, 128));
   std::vector<RescoreEntry> sl((size_t)nq * RESCORE_SHORTLIST_CAP);
   std::vector<WindowPreview> wp((size_t)nq * WINDOW_P);
   std::vector<int32_t> cnt((size_t)nq);
-  RSX_HIP(hipMemcpyAsync(sl.data(), h->w->f_cand.p, sl.size() * sizeof(RescoreEntry), hipMemcpyDeviceToHost, s));
-  RSX_HIP(hipMemcpyAsync(wp.data(), h->w->f_win.p, wp.size() * sizeof(WindowPreview), hipMemcpyDeviceToHost, s));
-  RSX_HIP(hipMemcpyAsync(cnt.data(), h->w->f_cnt.p, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  RSX_HIP(hipMemcpyAsync(sl.data(), b.cand(), sl.size() * sizeof(RescoreEntry), hipMemcpyDeviceToHost, s));
+  RSX_HIP(hipMemcpyAsync(wp.data(), b.win(), wp.size() * sizeof(WindowPreview), hipMemcpyDeviceToHost, s));
+  RSX_HIP(hipMemcpyAsync(cnt.data(), b.cnt(), cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   RSX_HIP(hipStreamSynchronize(s));
   for (int32_t q = 0; q < nq; q++) {
     const int32_t c = cnt[(size_t)q] < WINDOW_P ? cnt[(size_t)q] : WINDOW_P;
@@ -1777,7 +1789,6 @@ int rsx_sc_merge_topk_device(rsx_sc *h, const rsx_sc_hit *d_parts, int32_t npart
                              rsx_sc_hit *d_out, void *stream) try {
   if (!h || !d_parts || !d_out || nparts < 1 || nq < 1 || k < 1 || k > RSX_SC_MAX_TOPK) return fail(RSX_ERR_BAD_ARG, "bad arg");
   std::lock_guard<std::mutex> lk(h->mu);
-  RSX_TRY(set_device(h));
   hipStream_t s;
   RSX_TRY(use_stream(h, stream, &s));
   return launch_merge(d_parts, nparts, nq, k, d_out, s);

@@ -47,6 +47,8 @@ struct KdNode16 {
   float divlow, divhigh;
 };
 
+constexpr int KD_CAND_CAP = 64;  // candidates of the reduced walk: one per lane (cand_pos holds this many)
+
 struct KdSearchArgs {
   const KdNode16 *nodes;
   int32_t n_nodes;

@@ -83,7 +83,6 @@ namespace sc {
 namespace {
 
 constexpr int KD_KMAX = 64;
-constexpr int KD_CAND_CAP = 64;  // candidates of the reduced walk: one per lane
 constexpr int KD_LDS_BUDGET = 150 * 1024;  // nodes + tree-ordered distances are staged in LDS when they fit (~12 k keys)
 
 // One entry of the explicit stack.  node >= 0: the farther child of an inner node, still to be considered once the

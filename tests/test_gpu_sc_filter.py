@@ -287,6 +287,43 @@ def test_two_stage_sharded_query(sc, oracle, world, mode):
     torch.cuda.set_stream(torch.cuda.default_stream())
 
 
+def test_refused_call_leaves_a_pending_stage1_alone(sc):
+    """A query entry that refuses its arguments enqueues nothing and overwrites nothing: stage 1 -> a refused
+    query_bounds_device -> stage 2 gives the records of stage 1 -> stage 2, which are query_device's."""
+    import torch
+    from navtech_radar_slam_amd._rsx import RsxError
+    n, nq, k = 300, 70, 3
+    descs = synth.random_descriptors(61, n, binary=True)
+    queries = synth.random_descriptors(62, nq, binary=True)
+    g = sc.SCManager(filter_mode=FORCE)
+    g.add_descriptors_f32(descs)
+    st = torch.cuda.current_stream().cuda_stream
+    dq = torch.from_numpy(queries).cuda()
+
+    def two_stage(between=None):
+        part = torch.zeros((nq, k, 2), dtype=torch.float64, device="cuda")
+        out = torch.zeros((nq, k, 2), dtype=torch.float64, device="cuda")
+        g.query_stage1_device(dq.data_ptr(), nq, k, part.data_ptr(), stream=st)
+        if between:
+            between()
+        g.query_stage2_device(nq, k, part.data_ptr(), out.data_ptr(), stream=st)   # one shard: its partial list is the global one
+        torch.cuda.synchronize()
+        return out.cpu().numpy().view(sc.HIT_DTYPE).reshape(nq, k)
+
+    want = torch.zeros((nq, k, 2), dtype=torch.float64, device="cuda")
+    g.query_device(dq.data_ptr(), nq, k, want.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    records = two_stage()
+    assert np.array_equal(records, want.cpu().numpy().view(sc.HIT_DTYPE).reshape(nq, k))
+
+    def refused():
+        blocks = torch.zeros((nq, 32), dtype=torch.float16, device="cuda")        # one block of 32 columns cannot cover 300 entries
+        with pytest.raises(RsxError) as e:
+            g.query_bounds_device(dq.data_ptr(), nq, k, want.data_ptr(), blocks.data_ptr(), 1, 32, nq * 32, stream=st)
+        assert e.value.status == -1 and "do not cover" in str(e.value)            # RSX_ERR_BAD_ARG (rsx.h)
+    assert np.array_equal(two_stage(between=refused), records)
+
+
 def test_full_size_100k_properties(sc, oracle):
     """BASELINE config 5 scale on one GPU: 100 000-keyframe DB (0.8 GB resident), batched exhaustive
     top-10.  Size-independent properties (planted loops come back as top-1 with distance ~0 and the

@@ -1,6 +1,8 @@
 """csrc/sc_plan.h -- the integer logic that cuts a query batch into host-entry pieces, filter batches and the XCD-aware work
 split of the two-wave filter kernel -- compiled with the host compiler and checked over a sweep of sizes: every query / every
-(tile-block, query tile) unit is covered exactly once, the shapes are the documented ones."""
+(tile-block, query tile) unit is covered exactly once, the shapes are the documented ones.  Likewise the decisions the query
+entries of csrc/sc_api.cpp take from it: which kernels score a batch (at every threshold edge), a shard's share of the indices,
+the stage-1 share and the padded leading dimension."""
 import json
 import os
 import subprocess
@@ -38,6 +40,30 @@ int main() {
     const long long nqt = (nq + 3) / 4, ntb = ((n + 31) / 32 + 3) / 4;
     const XcdSplit s = xcd_split(nqt, ntb, cu);
     std::printf("%s[%lld, %lld, %d, %d, %d, %d, %u]", first ? "" : ", ", nqt, ntb, cu, s.on ? 1 : 0, s.nqt_x, s.len, s.grid);
+    first = false;
+  }
+  std::printf("], \"owned\": [");
+  first = true;
+  for (int w = 1; w <= 9; w++) for (int r = 0; r < w; r++) for (int n = 0; n <= 40; n++) {
+    std::printf("%s[%d, %d, %d, %lld]", first ? "" : ", ", w, r, n, (long long)owned_below(n, r, w));
+    first = false;
+  }
+  std::printf("], \"paths\": [");
+  first = true;
+  for (int m = 0; m <= 3; m++) for (int nq : {1, 2, 8, 9, 16, 17, 64})
+    for (long long e : {0ll, (1ll << 17) / nq, 400000ll / nq, 800000ll / nq, 50000ll}) for (long long n = e > 0 ? e - 1 : 0; n <= e + 1; n++) {
+      const int with = (int)query_path(m, nq, n), without = (int)query_path(m, nq, n, false);
+      const Stage1Plan s1 = stage1_plan(m, nq, n);
+      std::printf("%s[%d, %d, %lld, %d, %d, %d, %d, %d]", first ? "" : ", ", m, nq, n, with, without, one_tail(query_path(m, nq, n), n, nq) ? 1 : 0,
+                  s1.split ? 1 : 0, (int)s1.whole);
+      first = false;
+    }
+  std::printf("], \"path_names\": [%d, %d, %d], \"share\": [", (int)Path::SingleQuery, (int)Path::FilterChain, (int)Path::ExactAll);
+  for (int w = 1; w <= 64; w++) std::printf("%s[%d, %d]", w > 1 ? ", " : "", w, stage1_share(160, w));
+  std::printf("], \"ld\": [");
+  first = true;
+  for (long long n : {0ll, 1ll, 31ll, 32ll, 33ll, 970ll, 9970ll, 99970ll, 1000000ll, 40000000ll}) {
+    std::printf("%s[%lld, %lld]", first ? "" : ", ", n, (long long)padded_ld(n));
     first = false;
   }
   std::printf("]}\n");
@@ -105,3 +131,71 @@ def test_xcd_split_covers_every_unit_once(plans):
     assert [r[3:] for r in plans["xcd"] if r[:3] == [2048, 78, 256]][0] == [1, 256, 128, 8 * 2 * 78]
     # a 1024-query piece keeps the contiguous split (whole rounds would cost 17 %)
     assert [r[3] for r in plans["xcd"] if r[:3] == [256, 78, 256]] == [0]
+
+
+def test_owned_below_counts_a_shards_indices(plans):
+    """owned_below(n, rank, world) = |{i < n : i % world == rank}|: what the eligibility count, the appended range and the file
+    check of a shard each used to work out for themselves"""
+    table = {}
+    for world, rank, n, got in plans["owned"]:
+        assert got == sum(1 for i in range(n) if i % world == rank), (world, rank, n)
+        table[world, rank, n] = got
+    assert len(table) == sum(range(1, 10)) * 41
+    # appending n keyframes at g0: the shard takes the owned indices of [g0, g0 + n)
+    for world in range(1, 10):
+        for rank in range(world):
+            for g0 in range(0, 21):
+                for n in range(0, 21):
+                    want = sum(1 for i in range(g0, g0 + n) if i % world == rank)
+                    assert table[world, rank, g0 + n] - table[world, rank, g0] == want, (world, rank, g0, n)
+
+
+def _path_before(mode, nq, n, single_query=True):
+    """the choice as the entries made it before it moved to sc_plan.h: use_q1, then use_filter, else exact-all"""
+    q1 = single_query and 1 <= nq <= 16 and mode in (0, 3) and (mode == 3 or nq == 1 or nq * n <= (800000 if nq <= 8 else 400000))
+    if q1:
+        return "single"
+    chain = not (mode == 1 or n <= 0) and (mode == 2 or n >= 50000 or nq * n >= 2 ** 17)
+    return "chain" if chain else "exact"
+
+
+def test_query_path_at_its_threshold_edges(plans):
+    names = dict(zip(plans["path_names"], ("single", "chain", "exact")))
+    seen = {}
+    for mode, nq, n, with_q1, without_q1, one_tail, s1_split, s1_whole in plans["paths"]:
+        # stage 1 as it decided before: split wherever use_filter said yes (whatever use_q1 said), else run_topk's own choice
+        assert s1_split == (_path_before(mode, nq, n, single_query=False) == "chain") and s1_whole == with_q1, (mode, nq, n)
+        assert names[with_q1] == _path_before(mode, nq, n), (mode, nq, n)
+        assert names[without_q1] == _path_before(mode, nq, n, single_query=False), (mode, nq, n)
+        # one tail: the filter chain, and one set of workspaces holds the batch (true for every size of this sweep: <= 2^29 bounds)
+        assert one_tail == (names[with_q1] == "chain"), (mode, nq, n)
+        seen[mode, nq, n] = names[with_q1]
+    # every edge from both sides, for every mode and batch size
+    for mode in range(4):
+        for nq in (1, 2, 8, 9, 16, 17, 64):
+            for e in (0, 2 ** 17 // nq, 400000 // nq, 800000 // nq, 50000):
+                assert (mode, nq, e) in seen and (mode, nq, e + 1) in seen and (e == 0 or (mode, nq, e - 1) in seen)
+    # the table itself, where the rules meet (auto mode unless said)
+    assert seen[0, 1, 50001] == "single" and seen[1, 1, 50001] == "exact" and seen[2, 1, 50001] == "chain"     # one query: always the single-query kernel in auto
+    assert seen[0, 8, 100000] == "single" and seen[0, 8, 100001] == "chain"                                      # nq <= 8: up to 800 000 pairs
+    assert seen[0, 9, 44444] == "single" and seen[0, 9, 44445] == "chain"                                        # 9 .. 16: up to 400 000
+    assert seen[0, 16, 25000] == "single" and seen[0, 16, 25001] == "chain" and seen[3, 16, 50001] == "single"   # mode 3: wherever it applies
+    assert seen[0, 17, 7710] == "exact" and seen[0, 17, 7711] == "chain"                                         # 17 * 7711 >= 2^17
+    assert seen[0, 64, 2047] == "exact" and seen[0, 64, 2048] == "chain" and seen[3, 64, 2047] == "exact"
+    assert seen[2, 64, 0] == "exact" and seen[2, 64, 1] == "chain" and seen[1, 64, 50001] == "exact"             # nothing to filter / forced / off
+
+
+def test_stage1_share_is_the_clamped_ceiling(plans):
+    assert [w for w, _ in plans["share"]] == list(range(1, 65))
+    for world, share in plans["share"]:
+        assert share == min(128, max(8, -(-160 // world))), world
+    assert dict(map(tuple, plans["share"]))[1] == 128 and dict(map(tuple, plans["share"]))[2] == 80 and dict(map(tuple, plans["share"]))[64] == 8
+
+
+def test_padded_ld_is_what_filter_batch_sizes_by(plans):
+    ld = dict(map(tuple, plans["ld"]))
+    for n, got in ld.items():
+        assert got == (n + 31) // 32 * 32 and got % 32 == 0 and 0 <= got - n < 32
+    for n, nq, qb in plans["batches"]:
+        if qb < nq:
+            assert qb * ld[n] <= 2 ** 29 or qb == 64, (n, nq, qb)
